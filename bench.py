@@ -13,6 +13,12 @@ contiguously over the ranks (4096 / N each: total work fixed, "strong"), one pro
 encoded records to rank 0, inside the timed region and overlapped with the next step's codecs.
 `--workload config3` runs the same workload on one GPU (the curve's 1-GPU point).
 
+A plain run sets up, warms up, times `--steps` steps and prints the result line.  `--full` adds everything else
+the benchmark measures or checks: the steady state over more steps, plain single-stream calls with the dominant
+kernel's roofline, decompression (with its error-bound check), the reference chunker's framing, host-to-host
+calls, the CPU baseline, and at N > 1 the same loop without the gather.  `--dump-outputs DIR` writes what the
+last timed step computed (records, record offsets, chosen codecs, per-frame errors) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -318,6 +324,26 @@ C3_ERROR_PCT = 1
 C3_ROTATE = 3       # resident batches per rank for configs[3] (different series values, same classes); coprime with the 4 scratch sets
 SPINUP_S = 0.25     # untimed spin-up in front of the timed loop (GPU clocks ramp with load)
 XGMI_LINK_GBS = 70.0  # per-direction rate of one xGMI link assumed by --root-weight auto
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_SAMPLE = 1 << 20  # elements kept of each array when the whole set would not fit
+DUMP_SEED = 20240
+
+
+def dump_outputs(d, arrays):
+    """Writes every array of `arrays` (name -> 1-D float32 / float64 numpy array) as d/<name>.npy.  When the set
+    exceeds DUMP_BYTES, each array longer than DUMP_SAMPLE keeps DUMP_SAMPLE elements at positions drawn once with a
+    fixed seed (sorted; a function of the array's length alone).  -> {name: elements written}"""
+    os.makedirs(d, exist_ok=True)
+    sample = sum(a.nbytes for a in arrays.values()) > DUMP_BYTES
+    out = {}
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if sample and len(a) > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), DUMP_SAMPLE, replace=False))
+            a = a[idx]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+        out[name] = len(a)
+    return out
 
 
 def main():
@@ -346,7 +372,14 @@ def main():
     ap.add_argument("--no-gather", action="store_true",
                     help="N > 1: every rank keeps its records (the reference writes one .bro per input file, "
                          "main.rs:121-124): no collective at all in the timed loop")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (steady state, plain calls and "
+                         "roofline, decompression, chunker framing, host end-to-end, CPU baseline; N > 1: codec-only loop)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -583,10 +616,22 @@ def main():
             gather_mode = ("one asynchronous fixed-capacity gather per step (PipelinedGather: capacity = the largest "
                            "peer's records, the root's stay in place), overlapped with the next step's codecs")
     dt = timed_loop(args.steps, pipelined)
+    # what the last timed step handed its caller (the loop above has joined and synchronised), before anything else
+    # reuses the output sets
+    if args.dump_outputs and rank == 0:
+        o = outs2[(args.steps - 1) % len(outs2)]
+        nb = int(o["rec_off"][-1].item())
+        dumped = dump_outputs(args.dump_outputs, {
+            "body": o["body"][:nb].cpu().numpy().astype(np.float32),
+            "rec_off": o["rec_off"].cpu().numpy().astype(np.float64),
+            "chosen": o["chosen"].cpu().numpy().astype(np.float32),
+            "err": o["err"].cpu().numpy().astype(np.float64),
+        })
+        sys.stderr.write("outputs of step %d written to %s: %s\n" % (args.steps - 1, args.dump_outputs, dumped))
     # the same loop over ten times the steps (at least 200): what the fill and drain of the chains cost a short timed
     # region shows as the difference (`steady_state`); never `value`
     steady = None
-    if world == 1 and pipelined and args.steps < 200:
+    if args.full and world == 1 and pipelined and args.steps < 200:
         k2 = max(200, 10 * args.steps)
         dt2 = timed_loop(k2, pipelined)
         steady = {"steps": k2, "value": units_total * k2 / dt2 / 1e6, "ms_per_step": dt2 / k2 * 1e3,
@@ -602,7 +647,7 @@ def main():
     # N > 1: the same loop without the exchange -- what the codecs alone sustain (the curve's fabric-free reading)
     value_codec_only = None
     gather_ms = None
-    if world > 1:
+    if args.full and world > 1:
         dt_codec = timed_loop(args.steps, pipelined, gather=False)
         value_codec_only = units_total * args.steps / dt_codec / 1e6
         gather_ms = max(0.0, (dt - dt_codec) / args.steps * 1e3)
@@ -611,7 +656,8 @@ def main():
     # each other: the dominant kernel's HIP events (start / stop of the dispatch itself) are taken here.
     value_no_hint = None
     kern_ms, launches = 0.0, 0
-    if world == 1:
+    ordered = None
+    if args.full and world == 1:
         for i in range(2):
             step(i, False)
         torch.cuda.synchronize()
@@ -623,7 +669,6 @@ def main():
         # For continuity with rounds 1-2 (whose roofline launches ran costliest-first on a hint from a batch of the same
         # layout): the same kernel on ONE chain with the cost order on and one resident batch -- the order is exact,
         # i.e. what the kernel does when its drain is not the issue.  Reported beside the roofline, never as `value`.
-        ordered = None
         if workload == "config2" and pipelined:
             ctx.set_chains(1)
             ctx.set_adaptive_order(True)
@@ -648,7 +693,7 @@ def main():
     # BASELINE.json configs[4] beside it: every rank decodes the records it encoded, device resident (the frame
     # table of the records is parsed once, untimed: atsc_dplan_create); no exchange of any kind on this path.
     decomp = None
-    if not args.no_decompress:
+    if args.full and not args.no_decompress:
         o = outs2[0]
         plan.compress(d_xs[0], o, atsc_amd.AUTO, True, me, 0, stream, pipelined=False)
         torch.cuda.synchronize()
@@ -756,12 +801,13 @@ def main():
             },
         }
         if world > 1:
+            out["root_weight"] = root_weight
+        if value_codec_only is not None:
             out["value_codec_only"] = value_codec_only
             out["gather_ms_per_step"] = gather_ms
-            out["root_weight"] = root_weight
             out["note_scaling"] = ("value = all ranks' samples / max-over-ranks time with the gather inside the timed region; "
                                    "value_codec_only = the same loop without the exchange")
-        if world == 1:
+        if args.full and world == 1:
             out["roofline"] = {
                 "bound": "hbm",
                 "kernel": "k_compress<1,5,false,256>",
@@ -792,7 +838,7 @@ def main():
         if value_no_hint is not None:
             out["value_no_hint"] = value_no_hint
         vmod = os.path.join(ROOT, "profiles", "valu_model.json")
-        if os.path.exists(vmod) and workload == "config2" and world == 1:
+        if args.full and os.path.exists(vmod) and workload == "config2" and world == 1:
             try:
                 vm = json.load(open(vmod))
                 floor_ms = float(vm["issue_floor_us_per_launch"]) * 1e-3
@@ -803,10 +849,10 @@ def main():
                 }
             except Exception:
                 pass
-        if world == 1 and workload == "config2" and not args.no_end_to_end:
+        if args.full and world == 1 and workload == "config2" and not args.no_end_to_end:
             out["chunker_framing"] = chunker_framing(ctx, atsc_amd, torch, dev, d_xs, me, stream)
             out["end_to_end"] = end_to_end(ctx, atsc_amd, xs[0], off, me)
-        if world == 1 and workload == "config2" and not args.no_cpu_baseline:
+        if args.full and world == 1 and workload == "config2" and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(xs[0], off, me)
         print(json.dumps(out))
     if world > 1:

@@ -7,9 +7,9 @@ root="${GRAFT_REPO_ROOT:-/root/repo}"
 cd /tmp && export TMPDIR=/tmp && cd "$root"
 G=gpurun_out
 mkdir -p $G
-echo "== bench"; python3 bench.py > $G/${tag}_bench.json 2> $G/${tag}_bench.err
-for c in 1 4; do echo "== bench, $c chain(s)"; python3 bench.py --chains $c --no-cpu-baseline --no-end-to-end > $G/${tag}_bench_chains$c.json 2>/dev/null; done
-echo "== kernel stats"; rocprofv3 --kernel-trace --stats --output-format csv -d $G/${tag}_stats -- python3 bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-end-to-end > $G/${tag}_stats_bench.json 2>/dev/null
+echo "== bench"; python3 bench.py --full > $G/${tag}_bench.json 2> $G/${tag}_bench.err
+for c in 1 4; do echo "== bench, $c chain(s)"; python3 bench.py --full --chains $c --no-cpu-baseline --no-end-to-end > $G/${tag}_bench_chains$c.json 2>/dev/null; done
+echo "== kernel stats"; rocprofv3 --kernel-trace --stats --output-format csv -d $G/${tag}_stats -- python3 bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-end-to-end > $G/${tag}_stats_bench.json 2>/dev/null
 echo "== pmc"; tools/pmc_collect.sh $G/${tag}_pmc --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end > $G/${tag}_pmc_summary.txt 2>&1
 for nf in 80 256; do
   echo "== large $nf"
@@ -30,6 +30,6 @@ echo "== large decode"; python3 tools/large_decode_probe.py > $G/${tag}_large_de
 NF=80 KLASS=mix bash tools/large_dkstats.sh $G/${tag}_ldk > $G/${tag}_large80_decode_kernels.txt 2>&1
 echo "== large ties"; python3 tools/large_tie_fraction.py > $G/${tag}_large_ties.txt 2>&1
 echo "== queue probe"; python3 tools/queue_pipe_probe.py > $G/${tag}_queue_probe.txt 2>&1
-echo "== config3 full"; python3 bench.py --workload config3 --steps 5 --warmup 2 --no-cpu-baseline --no-end-to-end > $G/${tag}_config3_full_1gpu.txt 2>&1
-echo "== share2"; ATSC_BENCH_SHARE_GPU=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --series 128 --steps 5 --warmup 2 > $G/${tag}_bench_share2.json 2>/dev/null
+echo "== config3 full"; python3 bench.py --full --workload config3 --steps 5 --warmup 2 --no-cpu-baseline --no-end-to-end > $G/${tag}_config3_full_1gpu.txt 2>&1
+echo "== share2"; ATSC_BENCH_SHARE_GPU=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --series 128 --steps 5 --warmup 2 > $G/${tag}_bench_share2.json 2>/dev/null
 echo done

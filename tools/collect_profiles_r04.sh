@@ -9,11 +9,11 @@ cd /tmp && export TMPDIR=/tmp && cd "$root"
 G=gpurun_out
 mkdir -p $G
 if [ $part = all ] || [ $part = bench ]; then
-echo "== bench (default: 200 steps)"; python3 bench.py > $G/${tag}_bench.json 2> $G/${tag}_bench.err
-echo "== bench (the driver's flags)"; python3 bench.py --steps 20 --warmup 5 > $G/${tag}_bench_driver.json 2> $G/${tag}_bench_driver.err
-for c in 1 4; do echo "== bench, $c chain(s)"; python3 bench.py --chains $c --no-cpu-baseline --no-end-to-end > $G/${tag}_bench_chains$c.json 2>/dev/null; done
+echo "== bench (default: 200 steps)"; python3 bench.py --full > $G/${tag}_bench.json 2> $G/${tag}_bench.err
+echo "== bench (the driver's flags)"; python3 bench.py --full --steps 20 --warmup 5 > $G/${tag}_bench_driver.json 2> $G/${tag}_bench_driver.err
+for c in 1 4; do echo "== bench, $c chain(s)"; python3 bench.py --full --chains $c --no-cpu-baseline --no-end-to-end > $G/${tag}_bench_chains$c.json 2>/dev/null; done
 # kernel stats of a run whose headline launches do NOT overlap: one chain, plain single-stream calls
-echo "== kernel stats"; rocprofv3 --kernel-trace --stats --output-format csv -d $G/${tag}_stats -- python3 bench.py --chains 1 --no-pipeline --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end > $G/${tag}_stats_bench.json 2>/dev/null
+echo "== kernel stats"; rocprofv3 --kernel-trace --stats --output-format csv -d $G/${tag}_stats -- python3 bench.py --full --chains 1 --no-pipeline --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end > $G/${tag}_stats_bench.json 2>/dev/null
 fi
 if [ $part = all ] || [ $part = pmc ]; then
 echo "== pmc"; tools/pmc_collect.sh $G/${tag}_pmc --chains 1 --no-pipeline --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end > $G/${tag}_pmc_summary.txt 2>&1
@@ -45,8 +45,8 @@ echo "== fast left"
   echo "# 32 frames, e = 1 %"; ERR=1 NF=32 python3 tools/fast_left_probe.py; } > $G/${tag}_fast_left.txt 2>&1
 echo "== stamps"; ATSC_LIB_VARIANT=stamps python3 tools/stamp_probe.py > $G/${tag}_stamps_256.txt 2>&1
 echo "== large decode probe"; python3 tools/large_decode_probe.py > $G/${tag}_large_decode_probe.txt 2>&1
-echo "== config3 full"; python3 bench.py --workload config3 --steps 5 --warmup 2 --no-cpu-baseline --no-end-to-end > $G/${tag}_config3_full_1gpu.txt 2>&1
-echo "== share2"; ATSC_BENCH_SHARE_GPU=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --series 128 --steps 5 --warmup 2 > $G/${tag}_bench_share2.json 2>/dev/null
+echo "== config3 full"; python3 bench.py --full --workload config3 --steps 5 --warmup 2 --no-cpu-baseline --no-end-to-end > $G/${tag}_config3_full_1gpu.txt 2>&1
+echo "== share2"; ATSC_BENCH_SHARE_GPU=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --series 128 --steps 5 --warmup 2 > $G/${tag}_bench_share2.json 2>/dev/null
 echo "== fuzz soak"
 { python3 tools/fuzz_soak.py 500 560; FUZZ_LARGE=2 python3 tools/fuzz_soak.py 600 630; FUZZ_LARGE=1 python3 tools/fuzz_soak.py 700 715; python3 tools/fuzz_decode.py; } > $G/${tag}_fuzz_soak.txt 2>&1
 fi

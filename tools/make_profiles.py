@@ -41,7 +41,7 @@ if f:
     gaps = [(int(b["Start_Timestamp"]) - int(a["End_Timestamp"])) / 1e3 for a, b in zip(rows, rows[1:])]
     with open(os.path.join(P, tag + "_kernel_launches.txt"), "w") as o:
         o.write("k_compress<1,5,false,256>: %d launches of `%s` in start order, duration in us (rocprofv3 --kernel-trace); "
-                "launches that overlap their predecessor: %d\n" % (len(d), "bench.py --chains 1 --no-pipeline --steps 20 --warmup 5",
+                "launches that overlap their predecessor: %d\n" % (len(d), "bench.py --full --chains 1 --no-pipeline --steps 20 --warmup 5",
                                                                     sum(1 for g in gaps if g < 0)))
         o.write("mean %.2f  min %.2f  max %.2f  last 20 (the plain-call timed loop the bench line's roofline reads): mean %.2f\n"
                 % (sum(d) / len(d), min(d), max(d), sum(d[-20:]) / len(d[-20:])))
@@ -72,7 +72,7 @@ if agg:
     write = 1024 * c.get("WRITE_SIZE", 0)
     out = {
         "note": "rocprofv3 --pmc passes (tools/pmc_collect.sh: one counter set per pass, --kernel-trace only) over "
-                "`python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end`; averages per "
+                "`python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end`; averages per "
                 "k_compress<1,5,false,256> launch (%d launches).  FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes "
                 "for gfx950 (128-B requests tallied at 64 B); FETCH / WRITE unit KiB; SQ_WAVE_CYCLES, SQ_WAIT_*, "
                 "SQ_ACTIVE_INST_* count quad-cycles." % launches,

@@ -13,6 +13,6 @@ for set in \
   "SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_INSTS_VALU_IOPS" \
   "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  rocprofv3 --pmc $set --kernel-trace --output-format csv -d $out/pass$i -- python3 bench.py $args > $out.pass$i.log 2>&1 || echo "pass $i failed"
+  rocprofv3 --pmc $set --kernel-trace --output-format csv -d $out/pass$i -- python3 bench.py --full $args > $out.pass$i.log 2>&1 || echo "pass $i failed"
 done
 python3 tools/pmc_summary.py "$out/pass*" k_compress
