@@ -45,14 +45,8 @@ CFLAGS = [f for f in FLAGS if f != "-shared"] + os.environ.get("ATSC_BUILD_DEFS"
 
 # per-source additions to CFLAGS.  atsc_kernels.hip: no machine-level loop-invariant code motion -- in kernels this
 # long it hoists dozens of constant materialisations out of the frame's loops and keeps them in registers across
-# everything else (k_compress<1,5,false,256>: 32 -> 16 spilled SGPRs; 1-2 % on every frame length; the resident-workgroup
-# experiment does not fit its registers without it).  ATSC_BUILD_MLICM=1 builds with the compiler's default.
-FILE_FLAGS = {}
-if not os.environ.get("ATSC_BUILD_MLICM"):
-    FILE_FLAGS["atsc_kernels.hip"] = ["-mllvm", "-disable-machine-licm"]
-for _f in os.environ.get("ATSC_BUILD_NOMLICM_ALSO", "").split(","):  # (A/B aid: the same for other sources)
-    if _f:
-        FILE_FLAGS[_f] = ["-mllvm", "-disable-machine-licm"]
+# everything else (k_compress<1,5,false,256>: 32 -> 16 spilled SGPRs; 1-2 % on every frame length).
+FILE_FLAGS = {"atsc_kernels.hip": ["-mllvm", "-disable-machine-licm"]}
 
 
 def _flags_key(src=None):

@@ -14,10 +14,7 @@
 
 namespace atsc {
 
-#ifndef ATSC_DEC_FFT_MIN_K
-#define ATSC_DEC_FFT_MIN_K 16
-#endif
-constexpr uint32_t DEC_FFT_MIN_K = ATSC_DEC_FFT_MIN_K;  // stored bins from which a multi-wavefront frame decodes by inverse FFT
+constexpr uint32_t DEC_FFT_MIN_K = 16;  // stored bins from which a multi-wavefront frame decodes by inverse FFT
 
 template <int W, int SPL>
 __global__ __launch_bounds__(64 * W) void k_decompress(

@@ -13,13 +13,13 @@
 namespace atsc {
 
 #define DEVI __device__ __forceinline__
-// threadIdx.x through an opaque move: code built on it cannot be hoisted out of a loop over frames (k_compress_resident),
-// where every per-lane address and constant would otherwise stay in registers across the whole frame body
+// threadIdx.x through an opaque move: code built on it cannot be hoisted across the frame body, where every per-lane
+// address and constant would otherwise stay in registers for the whole of it
 template <int W = 0>
 DEVI uint32_t tid_now()
 {
     // one-wavefront workgroups: the lane count below this lane (two instructions) instead of the thread-id register,
-    // which the resident kernel's register allocation would rather spill than keep for the whole loop
+    // which the register allocation would rather spill than keep for the whole frame
     uint32_t t = (W == 1) ? __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : threadIdx.x;
     asm volatile("" : "+v"(t));
     return t;

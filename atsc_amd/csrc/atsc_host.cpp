@@ -63,8 +63,7 @@ static const uint32_t LARGE_WS_SLOTS = 256;      // large frames in flight (one 
 // 8192-sample frames is 2 M samples: every grid of the large tier would be latency-bound on it)
 static uint32_t large_ws_slots(uint64_t ws_stride)
 {
-    uint64_t budget = 1600ull << 20;
-    if (const char *e = getenv("ATSC_LARGE_WS_MB")) budget = (uint64_t)std::max(1, atoi(e)) << 20;
+    const uint64_t budget = 1600ull << 20;
     const uint64_t fit = ws_stride ? budget / ws_stride : LARGE_WS_SLOTS;
     return (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(LARGE_WS_SLOTS, fit));
 }
@@ -85,24 +84,13 @@ struct atsc_ctx {
     std::map<void *, size_t> pool_live;
     size_t pool_held = 0;
     // Streams of the context's own (created on first use; few, because the runtime maps streams onto a handful of
-    // hardware queues).  Two uses:
-    //  * pipelined calls (atsc_compress_plan_dev_pipelined): consecutive batches go round-robin over the chains of a
-    //    plan, chain c on chain_streams[c] -- a dependent launch starts 6-10 us after its predecessor ends on this system
-    //    (tools/gap_probe.hip), and a frame kernel's freed wave slots refill slowly from a single queue; several queues
-    //    feeding the same CUs hide both (what bench.py --chains did from outside in round 2);
-    //  * the large tier: see large groups below.
-    // resident launches (k_compress_resident): one set of frame counters per stream that has carried one (launches
-    // on a stream are sequential, and a launch leaves its counters zero)
-    uint32_t *d_queues = nullptr;
-    hipStream_t q_stream[16] = {};
-    uint32_t q_used = 0;
+    // hardware queues).  Pipelined calls (atsc_compress_plan_dev_pipelined): consecutive batches go round-robin over the
+    // chains of a plan, chain c on chain_streams[c] -- a dependent launch starts 6-10 us after its predecessor ends on this
+    // system (tools/gap_probe.hip), and a frame kernel's freed wave slots refill slowly from a single queue; several
+    // queues feeding the same CUs hide both (what bench.py --chains did from outside in round 2).
     hipStream_t chain_streams[4] = {nullptr, nullptr, nullptr, nullptr};
     hipStream_t pack_streams[4] = {nullptr, nullptr, nullptr, nullptr};  // a chain's packing: beside its next batch's codecs
-    int n_chains = 2;                   // atsc_ctx_set_chains / ATSC_CHAINS (1..4)
-    // The large tier's kernel chain is bound by latency, not by throughput (a chain of launches, several of them one
-    // workgroup per frame): the large frames of a call are dealt over LARGE_GROUPS contiguous groups, each on a stream
-    // of the context's own, forked from and joined to the caller's stream by events -- the groups' chains overlap.
-    // (the groups run on chain_streams[])
+    int n_chains = 2;                   // atsc_ctx_set_chains (1..4)
     bool adaptive_order = false;        // pipelined calls start a class's costliest frames first (atsc_ctx_set_adaptive_order)
     int debug_stop = 0;  // ATSC_DEBUG_STOP: phase-timing aid for tools/, never set in production
     // optional timing of the dominant k_compress launch (HIP events on the launch stream)
@@ -185,10 +173,8 @@ struct atsc_plan {
         Scratch S;
         unsigned char *d_ws = nullptr;      // large-tier workspace set
         hipEvent_t ev_fork = nullptr;       // the caller's stream at the call
-        hipEvent_t ev_lfork = nullptr;      // large tier: this call's stream where the groups fork
         hipEvent_t ev_codec = nullptr;      // every kernel that reads d_samples is done (atsc_plan_input_release)
         hipEvent_t ev_done = nullptr;       // records packed (atsc_plan_join)
-        hipEvent_t ev_group[4] = {nullptr, nullptr, nullptr, nullptr};  // large tier: group chains done
         bool pending = false;               // ev_done recorded and not yet known to have passed
         // scheduling hint: clocks per frame in this chain's last batch and the launch order derived from them
         uint32_t *d_cost = nullptr;
@@ -333,8 +319,7 @@ static LargePre large_pre_extents(const std::vector<DevPlan> &plans, const std::
 {
     LargePre pre{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     bool first_large = true, rows_ok = true;
-    if (getenv("ATSC_LARGE_NO_PREPASS")) return pre;
-    pre.cols243 = getenv("ATSC_LARGE_OLD_COLS") ? 0u : 1u;
+    pre.cols243 = 1;
     for (uint32_t pi : large_plan_ids) {
         const DevPlan &p = plans[pi];
         if (!p.f4_m1) return LargePre{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -348,7 +333,7 @@ static LargePre large_pre_extents(const std::vector<DevPlan> &plans, const std::
         if (p.f4_m1 != 243) pre.cols243 = 0;
         // rows9p: the set of P (as a bit mask) over the large frames when EVERY one of them has M = 243 x 9 P, else 0
         uint32_t rp = 0;
-        if (p.f4_m1 == 243 && p.f4_m2 % 9 == 0 && !getenv("ATSC_LARGE_OLD_ROWS")) {
+        if (p.f4_m1 == 243 && p.f4_m2 % 9 == 0) {
             const uint32_t P9 = p.f4_m2 / 9;
             if (P9 >= 2 && P9 <= 32 && (P9 & (P9 - 1)) == 0) rp = P9;
         }
@@ -477,7 +462,7 @@ static int build_plan_entry(uint32_t n, PlanTables &T, std::map<uint32_t, uint64
         // large tier's grid path are written for (k_large_cols243, k_large_rows9p<P>, atsc_large_fast.h)
         if (p.half && p.M % (243u * 9u) == 0) {
             const uint32_t P9 = p.M / (243u * 9u);
-            if (P9 >= 2 && P9 <= 32 && (P9 & (P9 - 1)) == 0 && !getenv("ATSC_LARGE_SQRT_SPLIT")) { p.f4_m1 = 243; p.f4_m2 = 9 * P9; }
+            if (P9 >= 2 && P9 <= 32 && (P9 & (P9 - 1)) == 0) { p.f4_m1 = 243; p.f4_m2 = 9 * P9; }
         }
     }
     p.sp_mf = p.sp_md = 0;
@@ -593,14 +578,11 @@ extern "C" int atsc_ctx_create(atsc_ctx **out, int device)
     c->device = device;
     c->want_diag = getenv("ATSC_DIAG") != nullptr;
     if (const char *ds = getenv("ATSC_DEBUG_STOP")) c->debug_stop = atoi(ds);
-    if (getenv("ATSC_NO_ADAPTIVE_ORDER")) c->adaptive_order = false;
-    if (getenv("ATSC_ADAPTIVE_ORDER")) c->adaptive_order = true;
     // Two chains by default; four where the process runs with eight or more hardware queues (GPU_MAX_HW_QUEUES, read by
     // the HIP runtime at start-up: four by default): with four queues, four chains plus the caller's stream share
     // queues and gain nothing over two (106 us per step either way), with eight they are worth 3 % (97 -> 100 Gsamples/s,
     // three runs each)
     if (const char *hq = getenv("GPU_MAX_HW_QUEUES")) c->n_chains = atoi(hq) >= 8 ? 4 : 2;
-    if (const char *ch = getenv("ATSC_CHAINS")) c->n_chains = std::min(4, std::max(1, atoi(ch)));
     *out = c;
     return ATSC_OK;
     ATSC_API_END
@@ -619,7 +601,6 @@ extern "C" void atsc_ctx_destroy(atsc_ctx *ctx)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &pr : ctx->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (ctx->d_diag) (void)hipFree(ctx->d_diag);
-    if (ctx->d_queues) (void)hipFree(ctx->d_queues);
     for (auto &cs : ctx->chain_streams)
         if (cs) (void)hipStreamDestroy(cs);
     for (auto &cs : ctx->pack_streams)
@@ -766,11 +747,8 @@ extern "C" void atsc_plan_destroy(atsc_plan *p)
         pool_free(p->ctx, ch.d_hist);
         pool_free(p->ctx, ch.d_ids_adapt);
         if (ch.ev_fork) (void)hipEventDestroy(ch.ev_fork);
-        if (ch.ev_lfork) (void)hipEventDestroy(ch.ev_lfork);
         if (ch.ev_codec) (void)hipEventDestroy(ch.ev_codec);
         if (ch.ev_done) (void)hipEventDestroy(ch.ev_done);
-        for (int g = 0; g < 4; ++g)
-            if (ch.ev_group[g]) (void)hipEventDestroy(ch.ev_group[g]);
     }
     delete p;
 }
@@ -897,7 +875,8 @@ extern "C" int atsc_plan_create(atsc_ctx *ctx, const uint64_t *frame_off, uint64
     PCHK(pool_alloc(ctx, (void **)&p->d_local, n_frames * sizeof(uint32_t)));
     PCHK(pool_alloc(ctx, (void **)&p->d_blocksum, (nb + 1) * sizeof(uint64_t)));
     if (p->class_count[CLASS_LARGE]) {
-        // (a multiple of 4: the groups of a call get equal shares of the slots)
+        // (a multiple of 4, from when a call's large frames could be split into groups with equal shares of the slots;
+        // the slot count is also how many large frames one launch takes)
         p->ws_slots = (std::min<uint32_t>(p->class_count[CLASS_LARGE], large_ws_slots(p->ws_stride)) + 3u) & ~3u;
         PCHK(pool_alloc(ctx, (void **)&p->d_ws, p->ws_stride * p->ws_slots));
     }
@@ -1001,9 +980,9 @@ static int launch_sub(atsc_ctx *ctx, const atsc_plan *plan, const SubPlan *t, co
     return ATSC_OK;
 }
 
-// Streams and events a call needs from chain c; full: also the chain's scratch set, workspace and cost records
-// (pipelined calls; chain 0 borrows the plan's own scratch set).
-static int ensure_chain(atsc_ctx *ctx, const atsc_plan *plan, uint32_t c, bool full, uint32_t q)
+// Streams, events, scratch set, workspace and cost records a pipelined call needs from chain c (chain 0 borrows the
+// plan's own scratch set).
+static int ensure_chain(atsc_ctx *ctx, const atsc_plan *plan, uint32_t c, uint32_t q)
 {
     atsc_plan::Chain &ch = plan->chains[q];  // set q (scratch, events), run on chain stream c
     if (!ctx->chain_streams[c]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->chain_streams[c], hipStreamNonBlocking));
@@ -1012,18 +991,16 @@ static int ensure_chain(atsc_ctx *ctx, const atsc_plan *plan, uint32_t c, bool f
     // beside chain 0 it took four chains from 101 to 86 Gsamples/s)
     if (!ch.ev_fork) {
         HIPCHK(ctx, hipEventCreateWithFlags(&ch.ev_fork, hipEventDisableTiming));
-        HIPCHK(ctx, hipEventCreateWithFlags(&ch.ev_lfork, hipEventDisableTiming));
         // (ev_codec rides on the last k_compress dispatch as its stop event -- hipExtLaunchKernel -- when that is possible:
         // a recorded marker between two codec launches opens a bubble of 10-20 us on the stream)
         HIPCHK(ctx, hipEventCreateWithFlags(&ch.ev_codec, hipEventReleaseToDevice));
         HIPCHK(ctx, hipEventCreateWithFlags(&ch.ev_done, hipEventDisableTiming));
-        for (int g = 0; g < 4; ++g) HIPCHK(ctx, hipEventCreateWithFlags(&ch.ev_group[g], hipEventDisableTiming));
     }
     if (q == 0 && !ch.S.d_res) {
         ch.S.d_res = plan->d_res; ch.S.d_slots = plan->d_slots; ch.S.d_local = plan->d_local; ch.S.d_blocksum = plan->d_blocksum;
         ch.d_ws = plan->d_ws;
     }
-    if (!full || ch.ready) return ATSC_OK;
+    if (ch.ready) return ATSC_OK;
     // A set that cannot be built completely is taken apart again (its blocks would otherwise stay in pool_live with
     // the pointers overwritten by the next attempt) and the caller goes on with fewer chains.
     hipError_t e = hipSuccess;
@@ -1115,7 +1092,7 @@ static int compress_impl(atsc_ctx *ctx, const atsc_plan *plan, const double *d_s
         // sets built so far stay -- their batches may be in flight -- and the rotation goes over fewer of them; one
         // chain's first set is the plan's own, so the call itself only fails when not even the cost records fit)
         for (uint32_t q = 0; q < (plan->single_set ? 1u : 2 * nch); ++q) {
-            int rc = ensure_chain(ctx, plan, q % nch, true, q);
+            int rc = ensure_chain(ctx, plan, q % nch, q);
             if (!rc) continue;
             if (q == 0) return rc;  // (set 0 is the plan's own scratch: only its cost records were asked for)
             // sets 0 .. q-1 exist: the most chains whose two sets each are among them; one set alone means every call
@@ -1131,8 +1108,8 @@ static int compress_impl(atsc_ctx *ctx, const atsc_plan *plan, const double *d_s
         plan->turn++;
         atsc_plan::Chain &ch = plan->chains[qi];
         // The chain's previous batch owns this scratch set until its records are packed.  Its kernels precede this
-        // call's on the chain's stream, but the large tier's groups run on the other chains' streams as well; waiting
-        // on the host keeps that simple and bounds the host's run-ahead to one batch per chain.
+        // call's on the chain's stream, but its packing may run on a pack stream of its own; waiting on the host keeps
+        // that simple and bounds the host's run-ahead to one batch per chain.
         if (ch.pending) HIPCHK(ctx, hipEventSynchronize(ch.ev_done));
         ch.pending = false;
         s = ctx->chain_streams[ci];
@@ -1160,7 +1137,6 @@ static int compress_impl(atsc_ctx *ctx, const atsc_plan *plan, const double *d_s
     atsc_plan::Scratch S;
     S.d_res = plan->d_res; S.d_slots = plan->d_slots; S.d_local = plan->d_local; S.d_blocksum = plan->d_blocksum;
     if (pipelined) S = CH.S;
-    uint32_t large_groups = 0;  // the large tier ran as this many group chains on the context's streams (CH.ev_group[])
     const bool adapt = pipelined && ctx->adaptive_order;
     bool want_order = false;  // set once the main launches (which record the costs) are enqueued
     const uint32_t *ids_main = (adapt && CH.adapt_valid) ? CH.d_ids_adapt : plan->d_ids;
@@ -1170,16 +1146,12 @@ static int compress_impl(atsc_ctx *ctx, const atsc_plan *plan, const double *d_s
     // its queue with another chain's packing waits behind that packing's wait for *its* codecs.  Measured on the
     // 10.5 M-sample batch, two chains: 115.5 us per step with packing streams, 106.4 without (104.8 with
     // GPU_MAX_HW_QUEUES=8 and packing streams, i.e. no sharing); tools/chain_stamp_probe.py shows the stalls.
-    static const bool pack_same_env = getenv("ATSC_PACK_SAME_STREAM") != nullptr, pack_apart_env = getenv("ATSC_PACK_APART") != nullptr;
     // (a context that has run three or four chains and is then set to one keeps packing on the chain's stream: a pack
     // stream created behind four chain streams was seen to serialise with chain 0 -- 176 instead of 113 us per step, and
     // no cost order -- whatever GPU_MAX_HW_QUEUES said)
-    const bool pack_apart = pipelined && !pack_same_env &&
-                            (pack_apart_env || (plan_chains(ctx, plan) == 1 && (ctx->pack_streams[0] || !ctx->chain_streams[2])));
+    const bool pack_apart = pipelined && plan_chains(ctx, plan) == 1 && (ctx->pack_streams[0] || !ctx->chain_streams[2]);
     bool codec_attached = false;  // ev_codec is the stop event of this call's last codec dispatch
     auto pack = [&]() -> int {
-        for (uint32_t g = 0; g < large_groups; ++g)
-            if (ctx->chain_streams[g] != s) HIPCHK(ctx, hipStreamWaitEvent(s, CH.ev_group[g], 0));
         hipStream_t ps = s;
         if (pipelined) {
             if (!codec_attached) HIPCHK(ctx, hipEventRecord(CH.ev_codec, s));  // nothing reads d_samples from here on
@@ -1329,76 +1301,16 @@ static int compress_impl(atsc_ctx *ctx, const atsc_plan *plan, const double *d_s
             // the pre-pass transforms every large frame; a trial launch or a forced codec other than
             // FFT / Auto would not use its results
             const bool pre = plan->large_pre.tiles1 && (compressor == ATSC_AUTO || compressor == ATSC_FFT);
-            const uint32_t cnt = plan->class_count[c];
-            // groups: contiguous shares of the large frames, each with its share of the workspace slots, on the
-            // context's chain streams (see atsc_ctx::chain_streams)
-            uint32_t G = 1;  // (measured: 80 frames of 131072 samples 0.45 ms as one chain, 0.50 as two, 0.73 as four)
-            if (const char *ge = getenv("ATSC_LARGE_GROUPS")) G = (uint32_t)std::min(4, std::max(1, atoi(ge)));
-            if (ctx->debug_stop != 0 || ctx->want_diag) G = 1;  // the probes read one launch's output
-            G = std::min(G, cnt);
-            if (G <= 1) {
-                e = launch_compress_large(cnt, d_samples, plan->d_frames, plan->d_ids + plan->class_first[c],
-                                          plan->tabs.d_plans, plan->tabs.d_tw, lp, S.d_slots, S.d_res, d_diag, ws_set,
-                                          plan->ws_stride, plan->ws_slots, s, pre ? &plan->large_pre : nullptr);
-            } else {
-                // group g runs on chain stream g, forked from this call's stream (which may be one of them)
-                for (uint32_t g = 0; g < G; ++g) {
-                    int rc = ensure_chain(ctx, plan, g, false, g);
-                    if (rc) return rc;
-                }
-                {
-                    int rc = ensure_chain(ctx, plan, ci, false, qi);
-                    if (rc) return rc;
-                }
-                hipEvent_t fork = CH.ev_lfork;
-                HIPCHK(ctx, hipEventRecord(fork, s));
-                const uint32_t per = (cnt + G - 1) / G, slots_g = plan->ws_slots / G;
-                e = hipSuccess;
-                uint32_t used = 0;
-                for (uint32_t g = 0; g < G; ++g) {
-                    const uint32_t g0 = g * per, g1 = std::min(cnt, g0 + per);
-                    if (g0 >= g1) break;
-                    hipStream_t ls = ctx->chain_streams[g];
-                    if (ls != s) HIPCHK(ctx, hipStreamWaitEvent(ls, fork, 0));
-                    e = launch_compress_large(g1 - g0, d_samples, plan->d_frames, plan->d_ids + plan->class_first[c] + g0,
-                                              plan->tabs.d_plans, plan->tabs.d_tw, lp, S.d_slots, S.d_res, d_diag,
-                                              ws_set + (uint64_t)g * slots_g * plan->ws_stride, plan->ws_stride, slots_g, ls,
-                                              pre ? &plan->large_pre : nullptr);
-                    if (e != hipSuccess) break;
-                    if (ls != s) HIPCHK(ctx, hipEventRecord(CH.ev_group[g], ls));
-                    ++used;
-                }
-                large_groups = used;
-                if (e == hipSuccess && bracket)  // the bracket's end event follows every group
-                    for (uint32_t g = 0; g < used; ++g)
-                        if (ctx->chain_streams[g] != s) HIPCHK(ctx, hipStreamWaitEvent(s, CH.ev_group[g], 0));
-            }
+            e = launch_compress_large(plan->class_count[c], d_samples, plan->d_frames, plan->d_ids + plan->class_first[c],
+                                      plan->tabs.d_plans, plan->tabs.d_tw, lp, S.d_slots, S.d_res, d_diag, ws_set,
+                                      plan->ws_stride, plan->ws_slots, s, pre ? &plan->large_pre : nullptr);
         }
         else {
             UniArgs u = plan->class_uni[c];
             u.adaptive = (ids_main != plan->d_ids) ? 1u : 0u;
             u.count = plan->class_count[c];
             u.spread = 0;
-            static const bool resident_on = getenv("ATSC_RESIDENT") != nullptr;
-            if (resident_on && u.enabled && compressor == ATSC_AUTO && bounded && 0.0 <= prm.max_err && !d_diag &&
-                (prm.debug_stop & 0xffffff) == 0 && !prm.trial && !prm.trial_res) {
-                const uint32_t g = resident_grid(c, u.n, plan->class_lds[c]);
-                if (g && u.count >= 2 * g) {
-                    if (!ctx->d_queues) {
-                        HIPCHK(ctx, hipMalloc((void **)&ctx->d_queues, 16 * RESIDENT_Q_WORDS * sizeof(uint32_t)));
-                        HIPCHK(ctx, hipMemset(ctx->d_queues, 0, 16 * RESIDENT_Q_WORDS * sizeof(uint32_t)));
-                    }
-                    uint32_t qx = 0;
-                    while (qx < ctx->q_used && ctx->q_stream[qx] != s) ++qx;
-                    if (qx == ctx->q_used && qx < 16) { ctx->q_stream[qx] = s; ctx->q_used++; }
-                    if (qx < 16) {
-                        u.queue = ctx->d_queues + RESIDENT_Q_WORDS * qx;
-                        u.q_grid = g;
-                    }
-                }
-            }
-            static const bool no_spread = getenv("ATSC_NO_SPREAD") != nullptr;
-            if (u.enabled && !u.adaptive && !no_spread && u.count >= 4096) {
+            if (u.enabled && !u.adaptive && u.count >= 4096) {
                 // a stride near count / golden ratio, made coprime to count
                 uint32_t sp = (uint32_t)((double)u.count * 0.6180339887) | 1u;
                 auto gcd = [](uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; };
@@ -1552,7 +1464,6 @@ static int compress_frames_impl(atsc_ctx *ctx, const double *samples, const uint
     if (uniform) {
         // (large frames run best many to a launch: two parts, and only when each still has 32 frames)
         parts = fl <= MAX_FRAME_TIER_M ? std::min<uint64_t>(8, std::max<uint64_t>(1, ns >> 21)) : (n_frames >= 64 ? 2 : 1);
-        if (const char *e = getenv("ATSC_HOST_PARTS")) parts = std::max(1, atoi(e));
         if (ctx->want_diag) parts = 1;  // atsc_ctx_last_diag reports one launch
         parts = std::min(parts, n_frames);
     }
@@ -1570,13 +1481,13 @@ static int compress_frames_impl(atsc_ctx *ctx, const double *samples, const uint
     }
     lap("plans");
     int rc = ATSC_OK;
-    uint64_t piece = 2u << 20;  // samples per copy call
+    const uint64_t piece = 2u << 20;  // samples per copy call
     bool by_parts = false, parts_overflow = false;
     if (!out_alloc && parts > 1 && body) {
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, samples) == hipSuccess && at.type == hipMemoryTypeHost &&
             hipPointerGetAttributes(&at, body) == hipSuccess && at.type == hipMemoryTypeHost)
-            by_parts = getenv("ATSC_NO_D2H_PARTS") == nullptr;
+            by_parts = true;
         else
             (void)hipGetLastError();  // (unregistered memory is an answer, not an error)
     }
@@ -1588,7 +1499,6 @@ static int compress_frames_impl(atsc_ctx *ctx, const double *samples, const uint
             ctx->ev_parts.push_back(ev);
         }
     }
-    if (const char *e2 = getenv("ATSC_H2D_PIECE_MB")) piece = (uint64_t)std::max(1, atoi(e2)) << 17;
     double *d_x = nullptr, *d_err = nullptr;
     uint8_t *d_body = nullptr, *d_ch = nullptr;
     uint64_t *d_off = nullptr;  // part g's n_g + 1 offsets start at f0_g + g; then parts + 1 chain words:
@@ -2151,7 +2061,7 @@ extern "C" int atsc_decompress_plan_dev(atsc_ctx *ctx, const atsc_dplan *dp, con
 }
 
 // atsc_decompress_frames into memory the caller registered (atsc_host_register), for a stream without a count in
-// front: in parts (six; ATSC_DECODE_PARTS).  The samples' way back is the call (84 MB: 1.58 ms at the link's 53 GB/s) and
+// front: in six parts.  The samples' way back is the call (84 MB: 1.58 ms at the link's 53 GB/s) and
 // the host's walk over the record headers is the largest part of the rest (0.15-0.35 ms for 40960 records: sequential,
 // each header locates the next); with a page-locked destination a part's samples are a DMA transfer the host does not
 // wait behind, so the next part is walked, uploaded and decoded meanwhile.  Two things keep the copy engine fed: the first
@@ -2174,33 +2084,28 @@ static int decompress_frames_halves(atsc_ctx *ctx, const uint8_t *body, uint64_t
     }
     if (!ctx->work_stream && hipStreamCreateWithFlags(&ctx->work_stream, hipStreamNonBlocking) != hipSuccess) return -1;
     if (!ctx->d2h_stream && hipStreamCreateWithFlags(&ctx->d2h_stream, hipStreamNonBlocking) != hipSuccess) return -1;
-    static const int n_parts_env = getenv("ATSC_DECODE_PARTS") ? atoi(getenv("ATSC_DECODE_PARTS")) : 0;
-    constexpr int MAXP = 8;
-    const int NP = n_parts_env >= 2 ? std::min(n_parts_env, MAXP) : 6;
+    constexpr int NP = 6;
     while (ctx->ev_parts.size() < (size_t)NP) {
         hipEvent_t ev;
         if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return -1;
         ctx->ev_parts.push_back(ev);
     }
     hipStream_t ws = ctx->work_stream, ds = ctx->d2h_stream;
-    static const bool no_kernel_up = getenv("ATSC_NO_KERNEL_UPLOAD") != nullptr;
-    if (!ctx->h_stage && !no_kernel_up) {  // the parts' tables: 32-byte frame records, ids, plans, twiddles
+    if (!ctx->h_stage) {  // the parts' tables: 32-byte frame records, ids, plans, twiddles
         const size_t cap = 8u << 20;
         if (hipHostMalloc((void **)&ctx->h_stage, cap, hipHostMallocDefault) == hipSuccess) ctx->h_stage_cap = cap;
         else { ctx->h_stage = nullptr; (void)hipGetLastError(); }
     }
     ctx->h_stage_used = 0;  // (every earlier call ended with its streams drained)
-    hipStream_t up = no_kernel_up ? nullptr : ws;
     volatile int *h_status = ctx->h_stage ? (volatile int *)(ctx->h_stage + ctx->h_stage_cap - 256) : nullptr;
-    atsc_dplan *dp[MAXP] = {};
-    double *d_o[MAXP] = {};
-    uint64_t n[MAXP] = {}, done_n = 0, pos = 0;
+    atsc_dplan *dp[NP] = {};
+    double *d_o[NP] = {};
+    uint64_t n[NP] = {}, done_n = 0, pos = 0;
     // the first part: if one record holds everything behind it there is nothing to split
     // a short first part -- the copy engine starts after its walk, upload and decode -- and even ones behind it (each is
     // walked while its predecessor's samples travel: the walk is four to five times faster than the link)
-    static const int first_div = getenv("ATSC_DECODE_FIRST") ? std::max(2, atoi(getenv("ATSC_DECODE_FIRST"))) : 16;
-    const uint64_t lim0 = body_len / (uint64_t)std::max(first_div, NP);
-    int rc = dplan_create_range(ctx, body, body_len, 0, 0, lim0, &pos, &dp[0], up);
+    const uint64_t lim0 = body_len / 16;
+    int rc = dplan_create_range(ctx, body, body_len, 0, 0, lim0, &pos, &dp[0], ws);
     if (rc) return rc;
     if (pos >= body_len) {
         (void)hipStreamSynchronize(ws);  // (its tables may still be on their way up)
@@ -2222,7 +2127,7 @@ static int decompress_frames_halves(atsc_ctx *ctx, const uint8_t *body, uint64_t
             // a record longer than a part's stride (131072-sample Noop / RLE / deep FFT records) can end behind this
             // part's limit: the part is then empty and the next one starts where the walk stands
             if (pos >= lim) continue;
-            rc = dplan_create_range(ctx, body, body_len, 0, pos, lim, h == NP - 1 ? nullptr : &pos, &dp[h], up);
+            rc = dplan_create_range(ctx, body, body_len, 0, pos, lim, h == NP - 1 ? nullptr : &pos, &dp[h], ws);
             if (rc) goto done;
             if (h == NP - 1) pos = body_len;
         }
@@ -2255,7 +2160,7 @@ done:
         (void)hipStreamSynchronize(ds);
         *out_n = 0;  // (the caller's buffer may hold the first parts' samples: they are not a result)
     }
-    for (int h = 0; h < MAXP; ++h) {
+    for (int h = 0; h < NP; ++h) {
         pool_free(ctx, d_o[h]);
         if (dp[h]) atsc_dplan_destroy(dp[h]);
     }

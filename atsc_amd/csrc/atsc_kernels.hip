@@ -61,11 +61,8 @@ DEVI void fft_untangle(const DevPlan &P, const float2 *Z, float2 *out, const flo
 // that get their own instantiation of k_compress): identical arithmetic, operation for operation, but
 // strides, trip counts and the t / stride split are constants.
 // pairs of radix-3 stages fused (fft_stage33_fixed): multi-wavefront frames, whose stages end in a real barrier
-#ifndef ATSC_FUSE33_MIN_W
-#define ATSC_FUSE33_MIN_W 2
-#endif
 template <int W>
-constexpr bool FUSE33 = W >= ATSC_FUSE33_MIN_W;
+constexpr bool FUSE33 = W >= 2;
 template <int W, int M, int SC, int R, int ST>
 DEVI void fft_stage_fixed(const float2 *X, float2 *Y, const float2 *tw)
 {
@@ -324,16 +321,6 @@ __device__ unsigned long long g_frame_span[4 * 65536 * 3];  // wall clock (100 M
 // one-wavefront frames of the 256-sample class: ask for 6 wavefronts per SIMD (<= 80 VGPRs).
 // FN != 0: every frame of the launch has FN samples (FN >= 128, even transform length) and the frame
 // geometry is folded at compile time; FN == 0 reads it from the per-length table.
-DEVI void frame_prio(uint32_t trips)  // (s_setprio takes an immediate)
-{
-#ifndef ATSC_FRAME_PRIO  // off: measured 1-2 % slower for the one-workgroup-per-frame launch (below)
-    return;
-#endif
-    if (trips == 3) __builtin_amdgcn_s_setprio(1);
-    else if (trips == 7) __builtin_amdgcn_s_setprio(2);
-    else if (trips == 12) __builtin_amdgcn_s_setprio(3);
-}
-
 template <int W, int SPL, bool IDW, int FN, bool LEAN_ = (FN != 0)>
 __device__ __forceinline__ void compress_frame(
     const double *__restrict__ samples, const DevFrame *__restrict__ frames,
@@ -345,13 +332,6 @@ __device__ __forceinline__ void compress_frame(
     constexpr bool FIX_ = FN != 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t tid = tid_now<W>();  // (opaque: see tid_now)
-    // (-DATSC_FRAME_PRIO: issue priority follows the frame's age in ladder trips, frame_prio above.  It exists for
-    // resident workgroups -- k_compress_resident: their wavefronts were all started together, the hardware's oldest-first
-    // arbitration ranks them once and for all, and the last of a SIMD's five took 100 us and more over a frame that
-    // takes 15 -- and costs the per-frame grid 1-2 %: 97.3 vs 99.2 Gsamples/s, configs[3] 58.3 vs 58.8.)
-#ifdef ATSC_FRAME_PRIO
-    if (W == 1) __builtin_amdgcn_s_setprio(0);
-#endif
     uint32_t fid;
     DevFrame fr;
     const long long t_start = prm.cost ? clock64() : 0;
@@ -385,8 +365,8 @@ __device__ __forceinline__ void compress_frame(
         fr = frames[fid];
     }
     // (through the constant address space: the plan table is read-only for the life of the kernel, and a pointer that
-    // reached this function through memory -- k_compress_resident -- carries no such promise by itself; without it
-    // every table read is a vector load that has to be repeated after each store)
+    // reached this function through memory carries no such promise by itself; without it every table read is a vector
+    // load that has to be repeated after each store)
     typedef const __attribute__((address_space(4))) DevPlan PlanConst;
     PlanConst &P = *(PlanConst *)(plans + fr.plan);
 #define P_GENERIC (*(const DevPlan *)&P)  // for the helpers that take the plan by (generic) reference
@@ -873,7 +853,6 @@ __device__ __forceinline__ void compress_frame(
                     const uint32_t K = P.pK[ti];
                     if (prune && !can_win(poly_payload_size(step, K), 1)) { poly_pruned = true; break; }
                     ++poly_trips;
-                    if (W == 1) frame_prio(poly_trips);
                     poly_step = step;
                     poly_K = K;
                     // A trip whose (step, K) are the trip's before -- n / points rounds to the same step for two point
@@ -1254,7 +1233,6 @@ __device__ __forceinline__ void compress_frame(
                 const uint32_t K = min(mf + jump, Z);
                 if (prune && !can_win(1 + vlen(K) + 9 * K + 8, 0)) { fft_pruned = true; break; }
                 ++fft_trips;
-                if (W == 1) frame_prio(fft_trips);
                 if (W > 1 && !heap_order && K > sorted_n) {
                     const uint32_t first = mf + 2 * dk1;
                     build_order((K <= first && first < kcap) ? first : kcap);
@@ -1696,87 +1674,6 @@ __global__ __launch_bounds__(64 * W, (W == 1 && SPL <= 5 && !IDW) ? 6 : 1) void 
     compress_frame<W, SPL, IDW, FN, LEAN_>(samples, frames, ids, plans, twpool, prm, slots, res, diag, uni, blockIdx.x);
 }
 
-// Resident workgroups: as many as the GPU holds at once, each taking the next frame of the class from a counter
-// until the list is done.  A workgroup slot that has to be refilled by the dispatcher stays empty for 1-2.5 us
-// (tools/dispatch_probe.hip: 40960 workgroups of 10 us each with 7008 bytes of LDS keep 18.7 of a CU's 23 slots
-// busy); a 256-sample frame lives 13 us.  queue[0] counts the frames handed out since the counter was made; the
-// launch's share starts at q_base (the host adds every launch's count), so nothing resets it.
-struct ResidentArgs {
-    const double *samples;
-    const DevFrame *frames;
-    const uint32_t *ids;
-    const DevPlan *plans;
-    const float2 *twpool;
-    KParams prm;
-    uint8_t *slots;
-    DevResult *res;
-    atsc_frame_diag *diag;
-    UniArgs uni;
-    uint32_t *queue;  // RESIDENT_Q_WORDS words: head x at word 32 x (a 128-byte line each), x < 8; exits at word 256
-    uint32_t count;
-};
-// Resident workgroups: as many as the GPU holds at once (resident_grid), each taking frame after frame of the
-// class until none is left.  A workgroup slot the dispatcher has to refill stays empty for 1-2.5 us
-// (tools/dispatch_probe.hip: 40960 workgroups that live 10 us each with 7008 bytes of LDS keep 18.7 of a CU's 23
-// slots busy), a 256-sample frame lives 13 us, and a second launch's workgroups only get on the GPU as these leave:
-// its head fills this launch's tail.
-// The frame list is cut into eight contiguous shares with a head counter each, and a workgroup starts on the share
-// of the XCD it runs on: one counter word takes ~88 returning atomics per microsecond (MI355X_MICROARCH.md,
-// "dequeue") where this kernel asks for ~400; when its share is done it goes on to the next XCD's, so the shares'
-// different costs even out.  The last workgroup to leave zeroes the counters for the next launch on the stream.
-// STATUS: an experiment behind ATSC_RESIDENT=1, not the default.  Measured on the 10.5 M-sample batch (two chains):
-// 170 us per step against 106 for one workgroup per frame.  The slots do stay full (4830 frames in flight against
-// 4700) and the refill gap shrinks from 2.7 to 1.1 us, but the returning device-scope adds of ~5000 pullers cost
-// more than that: a launch ends in a 70-us tail in which the last few hundred frames live 80 us each, fewer
-// resident workgroups are FASTER (16 per CU: 158 us, 22: 176), and a relaxed agent-scope load of the head in front
-// of every add (to spare the failing adds) took the whole launch to 480 us with every frame's life doubled --
-// the queue traffic slows the frames' own memory operations.  DESIGN.md section 3 has the numbers.
-template <int W, int SPL, bool IDW, int FN, bool LEAN_ = (FN != 0)>
-__global__ __launch_bounds__(64 * W, 5) void k_compress_resident(const ResidentArgs args)
-{
-    // The arguments are read where they are used, through the kernel-argument segment's own pointer made opaque once
-    // per frame: held in registers across the loop they would take ~60 scalar registers from the frame's code.
-    typedef const __attribute__((address_space(4))) ResidentArgs *ArgPtr;
-    ArgPtr ka = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    __shared__ uint32_t q_bid, q_cur, q_tried;
-    if (threadIdx.x == 0) {
-        q_cur = (uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;  // XCC_ID
-        q_tried = 0;
-    }
-    for (;;) {
-        asm volatile("" : "+s"(ka));
-        if (threadIdx.x == 0) {
-            const uint32_t count = ka->count, per = (count + 7u) >> 3;
-            uint32_t *q = ka->queue;
-            uint32_t cur = q_cur, tried = q_tried, b = 0xFFFFFFFFu;
-            while (tried < 8) {
-                const uint32_t start = cur * per;
-                const uint32_t size = start < count ? min(per, count - start) : 0u;
-                const uint32_t i = size ? atomicAdd(&q[32 * cur], 1u) : 0xFFFFFFFFu;
-                if (i < size) { b = start + i; break; }
-                cur = (cur + 1) & 7u;
-                ++tried;
-            }
-            q_cur = cur;
-            q_tried = tried;
-            q_bid = b;
-        }
-        __syncthreads();
-        const uint32_t bid = (uint32_t)__builtin_amdgcn_readfirstlane((int)q_bid);
-        __syncthreads();
-        if (bid == 0xFFFFFFFFu) break;
-        compress_frame<W, SPL, IDW, FN, LEAN_>(ka->samples, ka->frames, ka->ids, ka->plans, ka->twpool, *(const KParams *)&ka->prm,
-                                               ka->slots, ka->res, ka->diag, *(const UniArgs *)&ka->uni, bid);
-    }
-    if (threadIdx.x == 0) {
-        uint32_t *q = ka->queue;
-        if (atomicAdd(&q[256], 1u) == gridDim.x - 1) {  // everybody else has made its last request
-            for (int x = 0; x < 8; ++x) q[32 * x] = 0;
-            q[256] = 0;
-        }
-    }
-}
-
 // --------------------------------------------------------------------------------------------
 // Scheduling hint.  A frame costs between a few hundred and tens of thousands of instruction slots
 // depending on how far its ladders run, and workgroups start in grid order: when the costliest
@@ -2139,48 +2036,15 @@ static hipError_t launch_class2(uint32_t count, uint32_t lds, const double *samp
 {
     if (count == 0) return hipSuccess;
     auto kern = k_compress<W, SPL, IDW, FN, LEAN_>;
-    static const uint32_t lds_pad = [] {  // ATSC_DEBUG_LDS_PAD: occupancy experiments only, read once
-        const char *pad = getenv("ATSC_DEBUG_LDS_PAD");
-        return pad ? (uint32_t)atoi(pad) : 0u;
-    }();
-    lds += lds_pad;
     if (lds > 48 * 1024) {
         hipError_t e = ensure_dyn_lds((const void *)kern, lds);
         if (e != hipSuccess) return e;
     }
     // ev0 / ev1 (optional) take the start / end timestamps of this dispatch itself: no separate
     // event packets, hence no bubbles around the kernel when it is being timed
-    if constexpr (W == 1 && FN == 256) {
-        if (uni.queue && uni.q_grid) {
-            ResidentArgs ra;
-            ra.samples = samples; ra.frames = frames; ra.ids = ids; ra.plans = plans; ra.twpool = twpool; ra.prm = prm;
-            ra.slots = slots; ra.res = res; ra.diag = diag; ra.uni = uni; ra.queue = uni.queue;
-            ra.count = count;
-            hipExtLaunchKernelGGL((k_compress_resident<W, SPL, IDW, FN, LEAN_>), dim3(uni.q_grid), dim3(64 * W), lds, s, ev0, ev1, 0, ra);
-            return hipGetLastError();
-        }
-    }
     hipExtLaunchKernelGGL(kern, dim3(count), dim3(64 * W), lds, s, ev0, ev1, 0, samples, frames, ids,
                           plans, twpool, prm, slots, res, diag, uni);
     return hipGetLastError();
-}
-
-uint32_t resident_grid(int cls, uint32_t n, uint32_t lds)
-{
-    if (cls != 1 || n != 256) return 0;
-    static int per_cu = 0, cus = 0;
-    if (!per_cu) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_compress_resident<1, 5, false, 256>, 64, lds) != hipSuccess || nb <= 0)
-            return 0;
-        if (const char *e = getenv("ATSC_RESIDENT_PER_CU")) nb = atoi(e);
-        per_cu = nb;
-        cus = pr.multiProcessorCount;
-    }
-    return (uint32_t)(per_cu * cus);
 }
 
 template <int W, int SPL>

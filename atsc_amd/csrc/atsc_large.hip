@@ -2521,19 +2521,11 @@ static void launch_rows9p(uint32_t pmask, uint32_t row_tiles, uint32_t pieces, u
     if (pmask & 32u) hipLaunchKernelGGL(k_large_rows9p<32>, g, dim3(RT), 0, s, samples, frames, ids, plans, twpool, ws, ws_stride, sparse_inv, row_tiles);
     if (pmask & 16u) hipLaunchKernelGGL(k_large_rows9p<16>, g, dim3(RT), 0, s, samples, frames, ids, plans, twpool, ws, ws_stride, sparse_inv, row_tiles);
     if (pmask & 8u) hipLaunchKernelGGL(k_large_rows9p<8>, g, dim3(RT), 0, s, samples, frames, ids, plans, twpool, ws, ws_stride, sparse_inv, row_tiles);
+    // (36-point rows stay here: one thread per row takes 166 VGPRs and 70 KB of LDS, two such workgroups on a CU --
+    // 16384-sample frames 46 -> 42 Gsamples/s)
+    if (pmask & 4u) hipLaunchKernelGGL(k_large_rows9p<4>, g, dim3(RT), 0, s, samples, frames, ids, plans, twpool, ws, ws_stride, sparse_inv, row_tiles);
     // rows of 18 points: one thread per row, one workgroup per frame (k_large_rows_thread)
-    static const bool old_rows = getenv("ATSC_LARGE_ROWS9P_ONLY") != nullptr;
-    const dim3 gt(1 + pieces, nb);
-    // (36-point rows: 166 VGPRs and 70 KB of LDS leave two such workgroups on a CU: 16384-sample frames 46 -> 42 Gsamples/s)
-    static const bool thread4 = getenv("ATSC_LARGE_ROWS_THREAD4") != nullptr;
-    if (pmask & 4u) {
-        if (!thread4) hipLaunchKernelGGL(k_large_rows9p<4>, g, dim3(RT), 0, s, samples, frames, ids, plans, twpool, ws, ws_stride, sparse_inv, row_tiles);
-        else hipLaunchKernelGGL(k_large_rows_thread<4>, gt, dim3(RT), 0, s, samples, frames, ids, plans, twpool, ws, ws_stride, sparse_inv);
-    }
-    if (pmask & 2u) {
-        if (old_rows) hipLaunchKernelGGL(k_large_rows9p<2>, g, dim3(RT), 0, s, samples, frames, ids, plans, twpool, ws, ws_stride, sparse_inv, row_tiles);
-        else hipLaunchKernelGGL(k_large_rows_thread<2>, gt, dim3(RT), 0, s, samples, frames, ids, plans, twpool, ws, ws_stride, sparse_inv);
-    }
+    if (pmask & 2u) hipLaunchKernelGGL(k_large_rows_thread<2>, dim3(1 + pieces, nb), dim3(RT), 0, s, samples, frames, ids, plans, twpool, ws, ws_stride, sparse_inv);
 }
 
 hipError_t launch_compress_large(uint32_t count, const double *samples, const DevFrame *frames,
@@ -2542,9 +2534,6 @@ hipError_t launch_compress_large(uint32_t count, const double *samples, const De
                                  unsigned char *ws, uint64_t ws_stride, uint32_t ws_slots, hipStream_t s,
                                  const LargePre *pre)
 {
-    // (The caller deals the large frames of a batch over several streams, a contiguous group of frames and workspace
-    // slots each: the chain below is bound by latency -- a dependent launch starts 6-10 us after its predecessor ends on
-    // this system, tools/gap_probe.hip, and several links run one workgroup per frame -- so the groups' chains overlap.)
     const uint32_t lds = 384 + 1024 + 64 + max(8 * LKEYS_MAX, SP_LDS_BYTES);
     hipError_t e = ensure_dyn_lds((const void *)k_compress_large<0>, lds);
     if (e != hipSuccess) return e;

@@ -459,10 +459,11 @@ __global__ __launch_bounds__(RT) void k_large_rows9p(const double *__restrict__ 
     const float2 *tw = twpool + Pl->tw_off;
     const uint32_t tid = threadIdx.x;
     for (uint32_t e = tid; e < M2; e += RT) w2[e] = tw[e * (M1 * f.sc)];
-    // Short rows (P <= 8): a workgroup takes G tiles one after the other -- a tile of 16 rows is 288 points at P = 2, and a
+    // Short rows (P <= 8): a workgroup takes G tiles one after the other -- a tile of 16 rows is 576 points at P = 4, and a
     // workgroup per tile spends its life on the launch, the table and three barriers (the other workgroups of such a
     // group leave at once)
-    constexpr uint32_t G = (P <= 4) ? 4u : (P == 8 ? 2u : 1u);
+    static_assert(P >= 4, "18-point rows are k_large_rows_thread's");
+    constexpr uint32_t G = (P == 4) ? 4u : (P == 8 ? 2u : 1u);
     if (blockIdx.x % G) return;
     uint32_t zeros = 0;
     __syncthreads();  // w2
@@ -586,8 +587,8 @@ __global__ __launch_bounds__(RT) void k_large_rows9p(const double *__restrict__ 
     }
 }
 
-// The same row pass for the two shortest row dimensions (M2 = 18, 36: frames of 8192 and 16384 samples), one THREAD per
-// row: a frame's 243 rows fit one workgroup, a row's 9 P points fit a thread's registers, and what k_large_rows9p<P> does
+// The same row pass for the shortest row dimension (M2 = 18: frames of 8192 samples; P = 2), one THREAD per row: a
+// frame's 243 rows fit one workgroup, a row's 9 P points fit a thread's registers, and what k_large_rows9p<P> does
 // through three barriers and two trips through LDS per 16-row tile -- with most of its 256 threads idle on rows this
 // short -- is a straight run here: load the row, radix 9 over u, twiddle, radix P over v (the same butterflies and the
 // same twiddles, operation for operation), one exchange through LDS for the untangle step's partner row (thread r

@@ -22,10 +22,8 @@ echo "== length probe"; python3 tools/length_probe.py > $G/${tag}_length_probe.t
 echo "== stamps"; ATSC_LIB_VARIANT=stamps python3 tools/stamp_probe.py > $G/${tag}_stamps_256.txt 2>&1
 for f in 2048 4096; do FLEN=$f ATSC_LIB_VARIANT=stamps python3 tools/stamp_probe.py > $G/${tag}_stamps_$f.txt 2>&1; done
 echo "== chain stamps"; for c in 1 2; do CHAINS=$c ATSC_LIB_VARIANT=stamps python3 tools/chain_stamp_probe.py > $G/${tag}_chain_stamps_$c.txt 2>&1; done
-echo "== resident experiment"; for r in 0 1; do for c in 1 2; do if [ $r = 1 ]; then export ATSC_RESIDENT=1; else unset ATSC_RESIDENT; fi; echo "resident $r"; ATSC_LIB_VARIANT= BRIEF=1 STEPS=200 CHAINS=$c python3 tools/chain_stamp_probe.py 2>&1 | grep chains; done; done > $G/${tag}_resident_ab.txt 2>&1; unset ATSC_RESIDENT
 echo "== dispatch probe"; ./tools/dispatch_probe > $G/${tag}_dispatch_probe.txt 2>&1
 echo "== gap probe"; ./tools/gap_probe > $G/${tag}_gap_probe.txt 2>&1
-echo "== host path"; python3 tools/host_path_probe.py > $G/${tag}_host_path.txt 2>&1
 echo "== large decode"; python3 tools/large_decode_probe.py > $G/${tag}_large_decode_probe.txt 2>&1
 NF=80 KLASS=mix bash tools/large_dkstats.sh $G/${tag}_ldk > $G/${tag}_large80_decode_kernels.txt 2>&1
 echo "== large ties"; python3 tools/large_tie_fraction.py > $G/${tag}_large_ties.txt 2>&1
