@@ -1,7 +1,7 @@
 // atsc -- command line front end over libatsc_hip.so with the reference's flags and file naming
 // (atsc/src/main.rs:29-127,176-243).  Every frame is compressed / decompressed on the GPU.
 //
-//   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u]
+//   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -26,6 +26,8 @@ struct Args {
     int level = 0;
     bool verbose = false, csv = false, no_header = false;
     std::string fields = "time,value";  // main.rs:218
+    bool window = false;                // --samples BEGIN:COUNT (with -u): decode only that window
+    uint64_t win_begin = 0, win_count = 0;
 };
 
 void usage()
@@ -35,6 +37,7 @@ void usage()
             "      --compressor <COMPRESSOR>  auto, noop, fft, constant, polynomial, idw, rle [default: auto]\n"
             "  -e, --error <ERROR>            maximum allowed error in %% (0..50) [default: 3]\n"
             "  -u                             uncompress the input file/directory\n"
+            "      --samples <BEGIN:COUNT>    with -u: write only the samples [BEGIN, BEGIN+COUNT) to the .wbro\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -102,9 +105,19 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
         if (!bro) return ATSC_OK;  // not a BRO file: skipped silently
         double *out = nullptr;
         uint64_t n = 0;
-        rc = atsc_decompress_data(ctx, bro, len, &out, &n);
+        if (a.window) {
+            // the records from the frame-count varint on, as atsc_decompress_data reads them
+            rc = atsc_bro_open(bro, len, nullptr, nullptr);
+            if (!rc) {
+                out = (double *)malloc((a.win_count ? a.win_count : 1) * sizeof(double));
+                rc = out ? atsc_decompress_window(ctx, bro + 9, len - 9, 1, a.win_begin, a.win_count, out, a.win_count, &n)
+                         : ATSC_E_NOMEM;
+            }
+        } else {
+            rc = atsc_decompress_data(ctx, bro, len, &out, &n);
+        }
         atsc_free(bro);
-        if (rc) return rc;
+        if (rc) { atsc_free(out); return rc; }
         if (a.verbose) dump("Output", out, n);
         rc = atsc_wbro_write(with_ext(path, "wbro").c_str(), out, n);
         atsc_free(out);
@@ -191,10 +204,24 @@ int main(int argc, char **argv)
         else if (value("--error") || value("-e")) { if (!parse_int(v, 0, 50, a.error)) { fprintf(stderr, "error: invalid value '%s' for '--error': not in 0..=50\n", v.c_str()); return 2; } }
         else if (value("--compression-selection-sample-level") || value("-c")) { if (!parse_int(v, 0, 6, a.level)) { fprintf(stderr, "error: invalid value '%s' for '-c': not in 0..=6\n", v.c_str()); return 2; } }
         else if (value("--fields")) a.fields = v;
+        else if (value("--samples")) {
+            const size_t colon = v.find(':');
+            char *e1 = nullptr, *e2 = nullptr;
+            const std::string b = colon == std::string::npos ? std::string() : v.substr(0, colon);
+            const std::string c = colon == std::string::npos ? std::string() : v.substr(colon + 1);
+            a.win_begin = strtoull(b.c_str(), &e1, 10);
+            a.win_count = strtoull(c.c_str(), &e2, 10);
+            if (b.empty() || c.empty() || *e1 || *e2 || b[0] == '-' || c[0] == '-') {
+                fprintf(stderr, "error: invalid value '%s' for '--samples': expected BEGIN:COUNT\n", v.c_str());
+                return 2;
+            }
+            a.window = true;
+        }
         else if (!s.empty() && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); usage(); return 2; }
         else a.input = s;
     }
     if (a.input.empty()) { usage(); return 2; }
+    if (a.window && !a.uncompress) { fprintf(stderr, "error: '--samples' needs '-u'\n"); return 2; }
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) { fprintf(stderr, "[ERROR] %s: No such file or directory\n", a.input.c_str()); return 1; }
     atsc_ctx *ctx = nullptr;

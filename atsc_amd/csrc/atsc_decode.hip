@@ -16,7 +16,14 @@ namespace atsc {
 
 constexpr uint32_t DEC_FFT_MIN_K = 16;  // stored bins from which a multi-wavefront frame decodes by inverse FFT
 
-template <int W, int SPL>
+// WIN = true: the window decoder (atsc_decompress_windows_dev).  Workgroup b takes task b of the list that `ids`
+// points to then (DevWTask: frame, samples [lo, hi) of it, destination): the payload is parsed as in the full decode,
+// the decode path is the frame's own (an FFT frame with K >= DEC_FFT_MIN_K still runs its whole inverse transform),
+// and only the samples [lo, hi) are computed where a sample's arithmetic is its own (the direct sum, splines, IDW,
+// runs) -- in the same order of operations, so that every stored sample has the bits the full decode gives it.
+// Sample j of the frame goes to outp[dst + j - lo], the offset taken modulo 2^64 (a task into the call's scratch
+// names it by its distance from outp).  WIN = false compiles to the full decoder as it was.
+template <int W, int SPL, bool WIN = false>
 __global__ __launch_bounds__(64 * W) void k_decompress(
     const DevDFrame *__restrict__ frames, const uint32_t *__restrict__ ids,
     const DevPlan *__restrict__ plans, const float2 *__restrict__ twpool,
@@ -25,10 +32,15 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
     constexpr int T = 64 * W;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t tid = threadIdx.x;
-    const DevDFrame fr = frames[ids ? ids[blockIdx.x] : blockIdx.x];  // ids == nullptr: the class is every frame, in order
+    DevWTask wt{};
+    if constexpr (WIN) wt = ((const DevWTask *)(const void *)ids)[blockIdx.x];
+    // ids == nullptr: the class is every frame, in order
+    const DevDFrame fr = frames[WIN ? wt.frame : (ids ? ids[blockIdx.x] : blockIdx.x)];
     const DevPlan &P = plans[fr.plan];
     const uint32_t n = fr.n;
-    double *out = outp + fr.out_off;
+    // samples [j0, j1) of the frame are stored, sample j at out[j - j0]
+    const uint32_t j0 = WIN ? wt.lo : 0u, j1 = WIN ? wt.hi : n;
+    double *out = WIN ? (double *)((uintptr_t)outp + wt.dst * sizeof(double)) : outp + fr.out_off;
     const uint8_t *pay = body + fr.payload_off;
 
     double *xs = (double *)(smem + P.o_xs);      // 8n : knot values / rle group values
@@ -155,17 +167,17 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
     if (h.bad) return;
 
     if (fr.tag == ATSC_CONSTANT) {
-        for (uint32_t j = tid; j < n; j += T) out[j] = h.d0;
+        for (uint32_t j = j0 + tid; j < j1; j += T) out[j - j0] = h.d0;
         return;
     }
     if (fr.tag == ATSC_NOOP) {
-        for (uint32_t j = tid; j < n; j += T) out[j] = xs[j];
+        for (uint32_t j = j0 + tid; j < j1; j += T) out[j - j0] = xs[j];
         return;
     }
     if (fr.tag == ATSC_POLYNOMIAL || fr.tag == ATSC_IDW) {
         const double mn = h.d0, mx = h.d1;
         if (mx == mn) {  // polynomial.rs:396-399
-            for (uint32_t j = tid; j < n; j += T) out[j] = mx;
+            for (uint32_t j = j0 + tid; j < j1; j += T) out[j - j0] = mx;
             return;
         }
         const uint32_t step = h.u1, K = h.u0, bd = __float_as_uint(h.f1);
@@ -193,7 +205,7 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
             return;
         }
         if (h.u2 == 1) {  // idw_to_data: polynomial.rs:375-393
-            for (uint32_t j = tid; j < n; j += T) {
+            for (uint32_t j = j0 + tid; j < j1; j += T) {
                 const double x = (double)j;
                 double num = 0.0, den = 0.0, sv = 0.0;
                 bool hit = false;
@@ -207,7 +219,7 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
                 double o = round(sv * 100000.0) / 100000.0;
                 if (o < mn) o = mn;
                 else if (o > mx) o = mx;
-                out[j] = o;
+                out[j - j0] = o;
             }
             return;
         }
@@ -224,7 +236,10 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
             const double stepd = (double)step, gapLd = (double)gapL;
             const double ry = 1.0 / stepd, ryL = 1.0 / gapLd;
             __syncthreads();
-            for (uint32_t sg = tid + 1; sg + 2 < K; sg += T) {
+            // (a window needs the tangents of the segments it covers only)
+            const uint32_t sg_first = WIN ? max(1u, min(j0 / step, K - 2)) : 1u;
+            const uint32_t sg_end = WIN ? min((j1 - 1) / step, K - 2) + 1 : K;
+            for (uint32_t sg = sg_first + tid; sg + 2 < K && (!WIN || sg < sg_end); sg += T) {
                 const uint32_t t0i = sg * step;
                 const uint32_t t1i = (sg + 1 == K - 1) ? (n - 1) : (sg + 1) * step;
                 const uint32_t tmi = (sg - 1) * step;
@@ -251,7 +266,7 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
                 hbt[r] = hh;
             }
             __syncthreads();
-            for (uint32_t i = tid; i < n; i += T) {
+            for (uint32_t i = j0 + tid; i < j1; i += T) {
                 double sv;
                 if (i == n - 1) {
                     sv = xs[K - 1];
@@ -273,23 +288,23 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
                 double o = div1e5(round(sv * 100000.0));  // utils/mod.rs:66-74 (min first)
                 if (o < mn) o = mn;
                 else if (o > mx) o = mx;
-                out[i] = o;
+                out[i - j0] = o;
             }
             return;
         }
-        for (uint32_t j = tid; j < n; j += T) {
+        for (uint32_t j = j0 + tid; j < j1; j += T) {
             const double sv = spline_eval([&](uint32_t k) { return xs[k]; }, j, n, step, K, magic);
             double o = round(sv * 100000.0) / 100000.0;  // utils/mod.rs:66-74 (min first)
             if (o < mn) o = mn;
             else if (o > mx) o = mx;
-            out[j] = o;
+            out[j - j0] = o;
         }
         return;
     }
     if (fr.tag == ATSC_FFT) {
         const float mxf = h.f0, mnf = h.f1;
         if (mxf == mnf) {  // fft.rs:427-430
-            for (uint32_t j = tid; j < n; j += T) out[j] = (double)mxf;
+            for (uint32_t j = j0 + tid; j < j1; j += T) out[j - j0] = (double)mxf;
             return;
         }
         // fft.rs:432-444: the decoder recomputes the Gibbs padding from the frame size
@@ -356,8 +371,8 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
                 }
 #pragma unroll
                 for (int m = 0; m < SPL; ++m) {
-                    const uint32_t j = tid + m * T;
-                    if (j < n) {
+                    const uint32_t j = j0 + tid + m * T;
+                    if (j < j1) {
                         const uint32_t jj = j + pre;
                         float re;
                         if (P.half) {
@@ -370,7 +385,7 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
                         double o = round((double)v * 100000.0) / 100000.0;
                         if (o > mxd) o = mxd;
                         if (o < mnd) o = mnd;
-                        out[j] = o;
+                        out[j - j0] = o;
                     }
                 }
                 return;
@@ -392,7 +407,8 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
             }
             const double cf = (2 * pos == L) ? 1.0 : 2.0;  // fft.rs:401-422
             const double a = cf * (double)re, bq = cf * (double)im;
-            uint32_t idx = mod_magic(pos * (tid + pre), L, magicL);  // pos * jj < 2^32
+            // (a window's samples start at j0: tw[pos * (j + pre) mod L] is the same twiddle whichever thread takes j)
+            uint32_t idx = mod_magic(pos * (j0 + tid + pre), L, magicL);  // pos * jj < 2^32
             const uint32_t stp = mod_magic(pos * (uint32_t)T, L, magicL);
 #pragma unroll
             for (int m = 0; m < MAXS; ++m) {
@@ -430,13 +446,13 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
         }
 #pragma unroll
         for (int m = 0; m < MAXS; ++m) {
-            const uint32_t j = tid + m * T;
-            if (j < n) {
+            const uint32_t j = j0 + tid + m * T;
+            if (j < j1) {
                 const float v = (float)acc[m] / Lf;  // fft.rs:460  f.re / len (f32)
                 double o = round((double)v * 100000.0) / 100000.0;  // fft.rs:208-218 (max first)
                 if (o > mxd) o = mxd;
                 if (o < mnd) o = mnd;
-                out[j] = o;
+                out[j - j0] = o;
             }
         }
         return;
@@ -449,31 +465,71 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
         uint32_t p2 = 1;
         while (p2 < E) p2 <<= 1;
         block_sort<W, true>(keys, nullptr, E, p2);
-        for (uint32_t j = tid; j < n; j += T) {
+        for (uint32_t j = j0 + tid; j < j1; j += T) {
             uint32_t lo = 0, hi = E;  // first entry with start > j
             while (lo < hi) {
                 const uint32_t mid = (lo + hi) >> 1;
                 if ((uint32_t)(keys[mid] >> 32) <= j) lo = mid + 1;
                 else hi = mid;
             }
-            out[j] = lo ? xs[(uint32_t)(keys[lo - 1] & 0xffffffffu)] : 0.0;
+            out[j - j0] = lo ? xs[(uint32_t)(keys[lo - 1] & 0xffffffffu)] : 0.0;
         }
         (void)aux;
     }
 }
 
-template <int W, int SPL>
+template <int W, int SPL, bool WIN = false>
 static hipError_t launch_d(uint32_t count, uint32_t lds, const DevDFrame *frames,
                            const uint32_t *ids, const DevPlan *plans, const float2 *twpool,
                            const uint8_t *body, double *out, int *status, hipStream_t s)
 {
-    auto kern = k_decompress<W, SPL>;
+    auto kern = k_decompress<W, SPL, WIN>;
     if (lds > 48 * 1024) {
         hipError_t e = ensure_dyn_lds((const void *)kern, lds);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(kern, dim3(count), dim3(64 * W), lds, s, frames, ids, plans, twpool, body, out,
                        status);
+    return hipGetLastError();
+}
+
+// frame classes as in launch_decompress; tasks: `count` DevWTask of that class
+hipError_t launch_decompress_window(const DevDFrame *frames, const DevWTask *tasks, int cls, uint32_t count,
+                                    uint32_t lds, const DevPlan *plans, const float2 *twpool, const uint8_t *body,
+                                    double *out, int *status, hipStream_t s)
+{
+    if (count == 0) return hipSuccess;
+    const uint32_t *ids = (const uint32_t *)(const void *)tasks;
+    switch (cls) {
+    case 0: return launch_d<1, 2, true>(count, lds, frames, ids, plans, twpool, body, out, status, s);
+    case 1: return launch_d<1, 5, true>(count, lds, frames, ids, plans, twpool, body, out, status, s);
+    case 2: return launch_d<1, 9, true>(count, lds, frames, ids, plans, twpool, body, out, status, s);
+    case 3: return launch_d<4, 5, true>(count, lds, frames, ids, plans, twpool, body, out, status, s);
+    case 4: return launch_d<4, 9, true>(count, lds, frames, ids, plans, twpool, body, out, status, s);
+    case 5: return launch_d<16, 5, true>(count, lds, frames, ids, plans, twpool, body, out, status, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// The window decode's last step: the parts of frames decoded into scratch (edge frames of the large tier, frames several
+// windows share) go to their windows.  Workgroup (g, c) copies chunk c (WG_CHUNK samples) of copy g.
+constexpr uint32_t WG_CHUNK = 4096;
+__global__ __launch_bounds__(256) void k_window_gather(const DevWGather *__restrict__ g, const double *__restrict__ scratch,
+                                                       double *__restrict__ out)
+{
+    const DevWGather c = g[blockIdx.x];
+    const uint32_t b = blockIdx.y * WG_CHUNK;
+    if (b >= c.len) return;
+    const uint32_t e = min(c.len, b + WG_CHUNK);
+    const double *src = scratch + c.src;
+    double *dst = out + c.dst;
+    for (uint32_t i = b + threadIdx.x; i < e; i += 256) dst[i] = src[i];
+}
+hipError_t launch_window_gather(const DevWGather *g, uint32_t n, uint32_t max_len, const double *scratch, double *out,
+                                hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_window_gather, dim3(n, (max_len + WG_CHUNK - 1) / WG_CHUNK), dim3(256), 0, s, g, scratch, out);
     return hipGetLastError();
 }
 

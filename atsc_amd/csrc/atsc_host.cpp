@@ -50,6 +50,13 @@ hipError_t launch_decompress(const struct DevDFrame *frames, uint64_t n_frames, 
                              int cls, uint32_t count, uint32_t lds, const DevPlan *plans,
                              const float2 *twpool, const uint8_t *body, double *out, int *status,
                              hipStream_t s);
+// (weak: the sanitizer build of the host sources, tests/asan, links without the window kernels and never decodes a window)
+__attribute__((weak)) hipError_t launch_decompress_window(const DevDFrame *frames, const DevWTask *tasks, int cls,
+                                                          uint32_t count, uint32_t lds, const DevPlan *plans,
+                                                          const float2 *twpool, const uint8_t *body, double *out,
+                                                          int *status, hipStream_t s);
+__attribute__((weak)) hipError_t launch_window_gather(const DevWGather *g, uint32_t n, uint32_t max_len,
+                                                      const double *scratch, double *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -205,6 +212,19 @@ struct atsc_dplan {
     bool large_tiled = false;
     LargePre large_pre{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // batched inverse transform of the large FFT frames (tiles1 == 0: off)
     uint32_t large_sp_tiles = 0;        // tiles per frame of the sparse inverse's (tile, frame) grid (0: off)
+    uint32_t large_choice_count = 0;    // large frames of the plan the forms above were chosen for
+    // host copies for the window decode (atsc_dplan_find_frames, atsc_decompress_windows_dev): frame f holds the
+    // samples [h_frames[f].out_off, h_frames[f + 1].out_off or n_samples)
+    std::vector<DevDFrame> h_frames;
+    std::vector<int> h_cls;
+    // what the last atsc_decompress_windows_dev call owns: its task tables (page-locked staging and device copy)
+    // and its scratch; ev_win marks the end of its work
+    mutable unsigned char *h_win = nullptr, *d_win = nullptr;
+    mutable size_t win_cap = 0;
+    mutable double *d_win_scratch = nullptr;
+    mutable uint64_t win_scratch_cap = 0;
+    mutable hipEvent_t ev_win = nullptr;
+    mutable bool win_pending = false;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1807,6 +1827,10 @@ extern "C" void atsc_dplan_destroy(atsc_dplan *p)
     if (!p) return;
     (void)hipDeviceSynchronize();
     free_tables(p->ctx, p->tabs);
+    if (p->h_win) (void)hipHostFree(p->h_win);
+    pool_free(p->ctx, p->d_win);
+    pool_free(p->ctx, p->d_win_scratch);
+    if (p->ev_win) (void)hipEventDestroy(p->ev_win);
     pool_free(p->ctx, p->d_frames);
     pool_free(p->ctx, p->d_ids);
     pool_free(p->ctx, p->d_status);
@@ -1927,6 +1951,47 @@ extern "C" int atsc_internal_dplan_parse(const uint8_t *body, uint64_t body_len,
 
 static int dplan_create_range(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t begin,
                               uint64_t soft_limit, uint64_t *end_pos, atsc_dplan **out, hipStream_t up = nullptr);
+// The large tier's launch forms of a plan, from every large frame of it: the transform form, the batched pre-pass and the
+// sparse inverse's tile grid.  They depend on the set of large frames, so a window decode takes them from its stream's.
+static void large_choices(atsc_dplan *p, const std::vector<DevPlan> &plans, const std::vector<DevDFrame> &frames,
+                          const std::vector<int> &cls)
+{
+    uint32_t n_large = 0;
+    for (size_t f = 0; f < frames.size(); ++f) n_large += cls[f] == CLASS_LARGE;
+    p->large_choice_count = n_large;
+    p->large_tiled = choose_large_tiled(n_large);
+    p->large_pre = LargePre{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    p->large_sp_tiles = 0;
+    if (n_large) {
+        std::vector<uint32_t> lp;
+        for (size_t f = 0; f < frames.size(); ++f)
+            if (cls[f] == CLASS_LARGE) lp.push_back(frames[f].plan);
+        std::sort(lp.begin(), lp.end());
+        lp.erase(std::unique(lp.begin(), lp.end()), lp.end());
+        p->large_pre = large_pre_extents(plans, lp);
+        // grid extent of k_decompress_large_tiles: the most tiles (8 output columns each) a large frame has
+        for (uint32_t pi : lp)
+            if (plans[pi].sp_mf) p->large_sp_tiles = std::max(p->large_sp_tiles, (plans[pi].sp_md + 7) / 8);
+        if (getenv("ATSC_LARGE_DECODE_ONE_KERNEL")) p->large_sp_tiles = 0;
+        // When every large FFT frame is one the decoder's grid path takes (k_large_dparse: a power-of-two chunk whose
+        // payload fits its LDS window and holds at most 1344 entries -- what this library's first ladder trip stores),
+        // the general decoder behind it has no FFT frame to bucket, and the launch of its tile grid (4.7 us of nothing)
+        // is left out; should k_large_dparse leave such a frame alone after all (a malformed or flat payload), the
+        // general kernel then transforms it by itself.
+        if (p->large_sp_tiles && !getenv("ATSC_LARGE_NO_FAST")) {
+            bool all_fast = true;
+            for (size_t f = 0; f < frames.size() && all_fast; ++f) {
+                if (cls[f] != CLASS_LARGE || frames[f].tag != ATSC_FFT) continue;
+                const DevPlan &q = plans[frames[f].plan];
+                const uint32_t p9 = q.f4_m2 / 9u;
+                const bool geo = q.f4_m1 == 243 && q.half && p9 * 9u == q.f4_m2 && p9 >= 2 && p9 <= 32 && (p9 & (p9 - 1)) == 0 &&
+                                 q.mf <= 1344 && !(q.pre & 1u) && !(frames[f].n & 1u);
+                all_fast = geo && frames[f].payload_len + 4u <= 16384u && frames[f].payload_len <= 11u * 1344u + 12u;
+            }
+            if (all_fast) p->large_sp_tiles = 0;
+        }
+    }
+}
 extern "C" int atsc_dplan_create(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len,
                                  int has_count, atsc_dplan **out)
 {
@@ -1976,37 +2041,9 @@ static int dplan_create_range(atsc_ctx *ctx, const uint8_t *body, uint64_t body_
         std::vector<uint32_t> cur(p->class_first);
         for (size_t f = 0; f < frames.size(); ++f) ids[cur[cls[f]]++] = (uint32_t)f;
     }
-    p->large_tiled = choose_large_tiled(p->class_count[CLASS_LARGE]);
-    if (p->class_count[CLASS_LARGE]) {
-        std::vector<uint32_t> lp;
-        for (size_t f = 0; f < frames.size(); ++f)
-            if (cls[f] == CLASS_LARGE) lp.push_back(frames[f].plan);
-        std::sort(lp.begin(), lp.end());
-        lp.erase(std::unique(lp.begin(), lp.end()), lp.end());
-        p->large_pre = large_pre_extents(p->tabs.plans, lp);
-        // grid extent of k_decompress_large_tiles: the most tiles (8 output columns each) a large frame has
-        for (uint32_t pi : lp)
-            if (p->tabs.plans[pi].sp_mf) p->large_sp_tiles = std::max(p->large_sp_tiles, (p->tabs.plans[pi].sp_md + 7) / 8);
-        if (getenv("ATSC_LARGE_DECODE_ONE_KERNEL")) p->large_sp_tiles = 0;
-        // When every large FFT frame is one the decoder's grid path takes (k_large_dparse: a power-of-two chunk whose
-        // payload fits its LDS window and holds at most 1344 entries -- what this library's first ladder trip stores),
-        // the general decoder behind it has no FFT frame to bucket, and the launch of its tile grid (4.7 us of nothing)
-        // is left out; should k_large_dparse leave such a frame alone after all (a malformed or flat payload), the
-        // general kernel then transforms it by itself.
-        if (p->large_sp_tiles && !getenv("ATSC_LARGE_NO_FAST")) {
-            bool all_fast = true;
-            for (size_t f = 0; f < frames.size() && all_fast; ++f) {
-                if (cls[f] != CLASS_LARGE || frames[f].tag != ATSC_FFT) continue;
-                const DevPlan &q = p->tabs.plans[frames[f].plan];
-                const uint32_t p9 = q.f4_m2 / 9u;
-                const bool geo = q.f4_m1 == 243 && q.half && p9 * 9u == q.f4_m2 && p9 >= 2 && p9 <= 32 && (p9 & (p9 - 1)) == 0 &&
-                                 q.mf <= 1344 && !(q.pre & 1u) && !(frames[f].n & 1u);
-                all_fast = geo && frames[f].payload_len + 4u <= 16384u && frames[f].payload_len <= 11u * 1344u + 12u;
-            }
-            if (all_fast) p->large_sp_tiles = 0;
-        }
-    }
+    large_choices(p, p->tabs.plans, frames, cls);
     lap("class lists");
+
     int rc = upload_tables(ctx, p->tabs, up);
     if (rc) { atsc_dplan_destroy(p); return rc; }
     lap("tables up");
@@ -2028,6 +2065,8 @@ static int dplan_create_range(atsc_ctx *ctx, const uint8_t *body, uint64_t body_
     }
 #undef PCHK
     lap("frames + ids up");
+    p->h_frames = std::move(frames);
+    p->h_cls = std::move(cls);
     *out = p;
     return ATSC_OK;
     ATSC_API_END
@@ -2286,6 +2325,329 @@ extern "C" int atsc_decompress_frames_alloc(atsc_ctx *ctx, const uint8_t *body, 
     *out = nullptr;
     const int rc = decompress_frames_impl(ctx, body, body_len, has_count, nullptr, 0, out, out_n);
     if (rc) *out_n = 0;
+    return rc;
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
+// window decode: samples [begin, begin + count) of the decoded stream without decoding the rest
+// ------------------------------------------------------------------------------------------
+// The record walk of a window read over untrusted bytes: from `pos`, at most max_frames records, with the header checks
+// of atsc_bro_scan, up to the record that holds sample begin + count - 1 (count == 0: the record that holds `begin`).
+// A Noop record counts the samples it stores (noop.rs:79-83), as the decoder does.  decode: the frame-length checks of
+// dplan_parse as well (a frame the decoders cannot take).  ATSC_E_INVALID when the stream ends in front of the window's end.
+struct WindowWalk {
+    uint64_t byte_begin = 0, byte_end = 0, frame_begin = 0, frame_end = 0, sample_begin = 0;
+};
+static int window_walk(const uint8_t *b, uint64_t len, uint64_t pos, uint64_t max_frames, uint64_t begin, uint64_t count,
+                       bool decode, WindowWalk &w)
+{
+    if (begin + count < begin) return ATSC_E_INVALID;
+    const uint64_t end = begin + count;
+    uint64_t s_off = 0, f = 0;
+    bool found = false;
+    for (; max_frames == ~0ull ? pos < len : f < max_frames; ++f) {
+        HostRecord hr;
+        if (!host_next_record(b, len, pos, hr)) return ATSC_E_FORMAT;
+        if (hr.tag > 6 || hr.tag == ATSC_AUTO) return ATSC_E_FORMAT;
+        uint64_t n = hr.sample_count;
+        if (hr.tag == ATSC_NOOP) {
+            uint64_t q = hr.payload_off + 1, cnt = 0;
+            if (hr.payload_len < 2 || !host_varint(b, hr.payload_off + hr.payload_len, q, cnt) || cnt > hr.payload_len)
+                return ATSC_E_FORMAT;
+            n = cnt;
+        }
+        if (decode && n == 0) return ATSC_E_FORMAT;
+        if (decode && n > MAX_FRAME) return ATSC_E_UNSUPPORTED;
+        if (s_off + n < s_off) return ATSC_E_FORMAT;
+        if (!found && s_off + n > begin) {
+            found = true;
+            w.frame_begin = f;
+            w.byte_begin = hr.start;
+            w.sample_begin = s_off;
+            if (count == 0) {
+                w.frame_end = f;
+                w.byte_end = hr.start;
+                return ATSC_OK;
+            }
+        }
+        s_off += n;
+        if (found && s_off >= end) {
+            w.frame_end = f + 1;
+            w.byte_end = pos;
+            return ATSC_OK;
+        }
+    }
+    if (count == 0 && begin == s_off) {  // the empty window at the stream's end
+        w.frame_begin = w.frame_end = f;
+        w.byte_begin = w.byte_end = pos;
+        w.sample_begin = s_off;
+        return ATSC_OK;
+    }
+    return ATSC_E_INVALID;
+}
+
+extern "C" int atsc_bro_find_window(const uint8_t *bro, uint64_t len, uint64_t begin, uint64_t count,
+                                    uint64_t *byte_begin, uint64_t *byte_end, uint64_t *frame_begin, uint64_t *frame_end,
+                                    uint64_t *sample_begin)
+{
+    ATSC_API_BEGIN
+    if (!bro) return ATSC_E_INVALID;
+    uint64_t pos = 0, nf = 0;
+    int rc = atsc_bro_open(bro, len, &pos, &nf);
+    if (rc) return rc;
+    if (nf > len / 4) return ATSC_E_FORMAT;
+    WindowWalk w;
+    rc = window_walk(bro, len, pos, nf, begin, count, false, w);
+    if (rc) return rc;
+    if (byte_begin) *byte_begin = w.byte_begin;
+    if (byte_end) *byte_end = w.byte_end;
+    if (frame_begin) *frame_begin = w.frame_begin;
+    if (frame_end) *frame_end = w.frame_end;
+    if (sample_begin) *sample_begin = w.sample_begin;
+    return ATSC_OK;
+    ATSC_API_END
+}
+
+extern "C" int atsc_dplan_find_frames(const atsc_dplan *dp, uint64_t begin, uint64_t count, uint64_t *frame_begin,
+                                      uint64_t *frame_end)
+{
+    if (!dp || !frame_begin || !frame_end) return ATSC_E_INVALID;
+    if (begin > dp->n_samples || count > dp->n_samples - begin) return ATSC_E_INVALID;
+    const auto &F = dp->h_frames;
+    auto by_off = [](uint64_t v, const DevDFrame &d) { return v < d.out_off; };
+    // the frame holding `begin` (every frame holds at least one sample), or n_frames at the stream's end
+    const uint64_t fb = (uint64_t)(std::upper_bound(F.begin(), F.end(), begin, by_off) - F.begin()) - 1;
+    *frame_begin = begin == dp->n_samples ? F.size() : fb;
+    *frame_end = count == 0 ? *frame_begin
+                            : (uint64_t)(std::upper_bound(F.begin(), F.end(), begin + count - 1, by_off) - F.begin());
+    return ATSC_OK;
+}
+
+// The window decode.  One task per (window, touched frame); tasks go by frame:
+//  * a frame of the LDS-resident classes that one window touches: k_decompress<W, SPL, true> straight into d_out;
+//  * one that several windows touch: decoded once, over the union of their ranges, into scratch;
+//  * a large frame: the large tier's launch sequence over a sub-plan of the touched large frames -- one that a window
+//    holds whole is written straight into d_out (its out_off rebased), the others go to scratch whole;
+//  * k_window_gather then copies the scratch parts to their windows.
+// A destination in scratch is named by its distance from d_out in doubles, modulo 2^64: one base pointer serves both.
+extern "C" int atsc_decompress_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                           const uint64_t *begin, const uint64_t *count, const uint64_t *out_off,
+                                           double *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !dp || !d_body || !d_out || (n_windows && (!begin || !count || !out_off)))
+        return fail(ctx, ATSC_E_INVALID, "decompress_windows: null argument");
+    if ((uintptr_t)d_out & 7u) return fail(ctx, ATSC_E_INVALID, "decompress_windows: d_out is not 8-byte aligned");
+    const uint64_t ns = dp->n_samples;
+    for (uint64_t i = 0; i < n_windows; ++i)
+        if (begin[i] > ns || count[i] > ns - begin[i]) return fail(ctx, ATSC_E_INVALID, "decompress_windows: window beyond the stream");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const auto &F = dp->h_frames;
+    struct Ent {
+        uint64_t dst;
+        uint32_t frame, lo, hi;
+    };
+    std::vector<Ent> ents;
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        if (!count[i]) continue;
+        uint64_t fb, fe;
+        (void)atsc_dplan_find_frames(dp, begin[i], count[i], &fb, &fe);
+        const uint64_t b = begin[i], e = begin[i] + count[i];
+        for (uint64_t f = fb; f < fe; ++f) {
+            const uint64_t fo = F[f].out_off, fn = F[f].n;
+            const uint64_t lo = std::max(b, fo) - fo, hi = std::min(e, fo + fn) - fo;
+            ents.push_back(Ent{out_off[i] + (fo + lo - b), (uint32_t)f, (uint32_t)lo, (uint32_t)hi});
+        }
+    }
+    if (ents.empty()) return ATSC_OK;
+    if (!launch_decompress_window || !launch_window_gather) return fail(ctx, ATSC_E_UNSUPPORTED, "decompress_windows: no window kernels");
+    auto by_frame = [](const Ent &a, const Ent &b) { return a.frame < b.frame; };
+    if (!std::is_sorted(ents.begin(), ents.end(), by_frame)) std::stable_sort(ents.begin(), ents.end(), by_frame);
+    // the tables and scratch of the previous call on this plan are reused once its work is done
+    if (dp->win_pending) {
+        HIPCHK(ctx, hipEventSynchronize(dp->ev_win));
+        dp->win_pending = false;
+    }
+    std::vector<DevWTask> small[CLASS_LARGE];
+    std::vector<DevDFrame> big;
+    std::vector<DevWGather> gat;
+    std::vector<std::pair<int, size_t>> small_scr;  // (class, task) whose dst is a scratch offset
+    std::vector<size_t> big_scr;
+    uint64_t scr = 0;
+    uint32_t max_len = 0;
+    for (size_t a = 0; a < ents.size();) {
+        size_t z = a + 1;
+        while (z < ents.size() && ents[z].frame == ents[a].frame) ++z;
+        const uint32_t f = ents[a].frame, n = F[f].n;
+        const int c = dp->h_cls[f];
+        const bool one = z - a == 1;
+        if (c != CLASS_LARGE) {
+            if (one) {
+                small[c].push_back(DevWTask{ents[a].dst, f, ents[a].lo, ents[a].hi, 0});
+            } else {
+                uint32_t ulo = n, uhi = 0;
+                for (size_t k = a; k < z; ++k) { ulo = std::min(ulo, ents[k].lo); uhi = std::max(uhi, ents[k].hi); }
+                small_scr.emplace_back(c, small[c].size());
+                small[c].push_back(DevWTask{scr, f, ulo, uhi, 0});
+                for (size_t k = a; k < z; ++k) {
+                    gat.push_back(DevWGather{scr + ents[k].lo - ulo, ents[k].dst, ents[k].hi - ents[k].lo, 0});
+                    max_len = std::max(max_len, ents[k].hi - ents[k].lo);
+                }
+                scr += uhi - ulo;
+            }
+        } else {
+            DevDFrame d = F[f];
+            if (one && ents[a].lo == 0 && ents[a].hi == n) {
+                d.out_off = ents[a].dst;
+            } else {
+                big_scr.push_back(big.size());
+                d.out_off = scr;
+                for (size_t k = a; k < z; ++k) {
+                    gat.push_back(DevWGather{scr + ents[k].lo, ents[k].dst, ents[k].hi - ents[k].lo, 0});
+                    max_len = std::max(max_len, ents[k].hi - ents[k].lo);
+                }
+                scr += n;
+            }
+            big.push_back(d);
+        }
+        a = z;
+    }
+    if (scr > dp->win_scratch_cap) {
+        pool_free(ctx, dp->d_win_scratch);
+        dp->d_win_scratch = nullptr;
+        dp->win_scratch_cap = 0;
+        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_win_scratch, scr * sizeof(double)));
+        dp->win_scratch_cap = scr;
+    }
+    if (scr) {
+        const uint64_t base = ((uint64_t)(uintptr_t)dp->d_win_scratch - (uint64_t)(uintptr_t)d_out) / sizeof(double);
+        for (const auto &t : small_scr) small[t.first][t.second].dst += base;
+        for (size_t i : big_scr) big[i].out_off += base;
+    }
+    // one upload: the classes' task lists, the large sub-plan (frames, ids), the copies
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t off_small[CLASS_LARGE], bytes = 0;
+    for (int c = 0; c < CLASS_LARGE; ++c) { off_small[c] = bytes; bytes = al(bytes + small[c].size() * sizeof(DevWTask)); }
+    const size_t off_big = bytes;
+    bytes = al(bytes + big.size() * sizeof(DevDFrame));
+    const size_t off_ids = bytes;
+    bytes = al(bytes + big.size() * sizeof(uint32_t));
+    const size_t off_gat = bytes;
+    bytes = al(bytes + gat.size() * sizeof(DevWGather));
+    if (bytes > dp->win_cap) {
+        if (dp->h_win) (void)hipHostFree(dp->h_win);
+        dp->h_win = nullptr;
+        pool_free(ctx, dp->d_win);
+        dp->d_win = nullptr;
+        dp->win_cap = 0;
+        const size_t cap = std::max<size_t>(bytes, 64u << 10);
+        HIPCHK(ctx, hipHostMalloc((void **)&dp->h_win, cap, hipHostMallocDefault));
+        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_win, cap));
+        dp->win_cap = cap;
+    }
+    if (!dp->ev_win) HIPCHK(ctx, hipEventCreateWithFlags(&dp->ev_win, hipEventDisableTiming));
+    unsigned char *h = dp->h_win, *d = dp->d_win;
+    for (int c = 0; c < CLASS_LARGE; ++c)
+        if (!small[c].empty()) memcpy(h + off_small[c], small[c].data(), small[c].size() * sizeof(DevWTask));
+    if (!big.empty()) {
+        memcpy(h + off_big, big.data(), big.size() * sizeof(DevDFrame));
+        uint32_t *ids = (uint32_t *)(h + off_ids);
+        for (size_t i = 0; i < big.size(); ++i) ids[i] = (uint32_t)i;
+    }
+    if (!gat.empty()) memcpy(h + off_gat, gat.data(), gat.size() * sizeof(DevWGather));
+    HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+    for (int c = 0; c < CLASS_LARGE; ++c) {
+        const hipError_t e = launch_decompress_window(dp->d_frames, (const DevWTask *)(d + off_small[c]), c,
+                                                      (uint32_t)small[c].size(), dp->class_lds[c], dp->tabs.d_plans,
+                                                      dp->tabs.d_tw, d_body, d_out, dp->d_status, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_decompress (window)", e);
+    }
+    if (!big.empty()) {
+        const hipError_t e = launch_decompress_large(
+            (uint32_t)big.size(), (const DevDFrame *)(d + off_big), (const uint32_t *)(d + off_ids), dp->tabs.d_plans,
+            dp->tabs.d_tw, d_body, d_out, dp->d_status, dp->d_ws, dp->ws_stride, dp->ws_slots, dp->large_tiled ? 1 : 0,
+            large_sparse() ? 1 : 0, s, dp->large_pre.tiles1 ? &dp->large_pre : nullptr,
+            // the (tile, frame) split of the sparse inverse runs for launches of up to LARGE_SPLIT_MAX frames: a window
+            // launch of fewer frames than its plan's full decode takes the full decode's side of that line
+            dp->large_choice_count <= LARGE_SPLIT_MAX ? dp->large_sp_tiles : 0);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_decompress_large (window)", e);
+    }
+    if (!gat.empty()) {
+        const hipError_t e = launch_window_gather((const DevWGather *)(d + off_gat), (uint32_t)gat.size(), max_len,
+                                                  dp->d_win_scratch, d_out, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_window_gather", e);
+    }
+    HIPCHK(ctx, hipEventRecord(dp->ev_win, s));
+    dp->win_pending = true;
+    return ATSC_OK;
+    ATSC_API_END
+}
+
+// Host call: walks the headers up to the window's last record, plans the touched records only and uploads only their bytes.
+extern "C" int atsc_decompress_window(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t begin,
+                                      uint64_t count, double *out, uint64_t out_cap, uint64_t *out_n)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body || !out_n || (count && !out)) return fail(ctx, ATSC_E_INVALID, "decompress_window: null argument");
+    *out_n = 0;
+    static const bool trace = getenv("ATSC_TRACE_HOST") != nullptr;
+    uint64_t pos = 0, max_frames = ~0ull;
+    if (has_count) {
+        if (!host_varint(body, body_len, pos, max_frames)) return fail(ctx, ATSC_E_FORMAT, "decompress_window: frame count");
+        if (max_frames > body_len / 4) return fail(ctx, ATSC_E_FORMAT, "decompress_window: frame count exceeds the bytes present");
+    }
+    WindowWalk w;
+    int rc = window_walk(body, body_len, pos, max_frames, begin, count, true, w);
+    if (rc) return fail(ctx, rc, rc == ATSC_E_INVALID ? "decompress_window: window beyond the stream" : "decompress_window: record walk");
+    if (out_cap < count) return fail(ctx, ATSC_E_CAPACITY, "decompress_window: out_cap");
+    if (count == 0) return ATSC_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->work_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->work_stream, hipStreamNonBlocking));
+    hipStream_t ws = ctx->work_stream;
+    const uint64_t slice = w.byte_end - w.byte_begin;
+    atsc_dplan *dp = nullptr;
+    rc = dplan_create_range(ctx, body + w.byte_begin, slice, 0, 0, ~0ull, nullptr, &dp);
+    if (rc) return rc;
+    if (dp->class_count[CLASS_LARGE]) {
+        // The large tier's launch forms depend on every large frame of the stream (large_choices): the rest of the
+        // record headers is walked as well, so that the touched large frames decode as the full decode does them.
+        DPlanHost Hw;
+        const char *why;
+        rc = dplan_parse(body, body_len, has_count, Hw, &why);
+        if (rc) { atsc_dplan_destroy(dp); return fail(ctx, rc, why); }
+        large_choices(dp, Hw.tabs.plans, Hw.frames, Hw.cls);
+    }
+    uint8_t *d_body = nullptr;
+    double *d_out = nullptr;
+    int status = 0;
+    const uint64_t b0 = begin - w.sample_begin, zero = 0;
+    hipError_t e = hipSuccess;
+#define WCHK(call)                                                                 \
+    do {                                                                           \
+        e = (call);                                                                \
+        if (e != hipSuccess) { rc = fail(ctx, ATSC_E_HIP, #call, e); goto done; } \
+    } while (0)
+    WCHK(pool_alloc(ctx, (void **)&d_body, std::max<uint64_t>(slice, 16)));
+    WCHK(pool_alloc(ctx, (void **)&d_out, count * sizeof(double)));
+    WCHK(hipMemcpyAsync(d_body, body + w.byte_begin, slice, hipMemcpyHostToDevice, ws));
+    if (trace) fprintf(stderr, "[window]     h2d records %llu bytes (frames %llu..%llu)\n", (unsigned long long)slice,
+                       (unsigned long long)w.frame_begin, (unsigned long long)w.frame_end);
+    rc = atsc_decompress_windows_dev(ctx, dp, d_body, 1, &b0, &count, &zero, d_out, ws);
+    if (rc) goto done;
+    WCHK(hipMemcpyAsync(&status, dp->d_status, sizeof(int), hipMemcpyDeviceToHost, ws));
+    WCHK(hipStreamSynchronize(ws));
+    if (status) { rc = fail(ctx, ATSC_E_FORMAT, "decompress_window: malformed payload"); goto done; }
+    WCHK(hipMemcpyAsync(out, d_out, count * sizeof(double), hipMemcpyDeviceToHost, ws));
+    WCHK(hipStreamSynchronize(ws));
+    *out_n = count;
+#undef WCHK
+done:
+    if (rc) (void)hipStreamSynchronize(ws);
+    pool_free(ctx, d_body);
+    pool_free(ctx, d_out);
+    atsc_dplan_destroy(dp);
     return rc;
     ATSC_API_END
 }

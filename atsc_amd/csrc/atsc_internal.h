@@ -168,6 +168,20 @@ struct DevDFrame {
     uint32_t plan;         // index into DevPlan table (by n)
 };
 
+// window decode (atsc_decompress_windows_dev): samples [lo, hi) of frame `frame` land at out[dst + j - lo]
+// (k_decompress<W, SPL, true>); dst is counted in doubles from the call's d_out, modulo 2^64
+struct DevWTask {
+    uint64_t dst;
+    uint32_t frame;  // index into the plan's DevDFrame table
+    uint32_t lo, hi;
+    uint32_t pad;
+};
+// one copy of k_window_gather: len samples from scratch[src] to out[dst]
+struct DevWGather {
+    uint64_t src, dst;
+    uint32_t len, pad;
+};
+
 static inline uint32_t varint_len_u64(uint64_t v)
 {
     return v < 251 ? 1u : v < (1ull << 16) ? 3u : v < (1ull << 32) ? 5u : 9u;

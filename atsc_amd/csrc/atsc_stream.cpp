@@ -283,6 +283,35 @@ extern "C" int atsc_bro_scan(const uint8_t *bro, uint64_t len, uint64_t *n_frame
     ATSC_API_END
 }
 
+extern "C" int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uint64_t count, double **out, uint64_t *n)
+{
+    ATSC_API_BEGIN
+    if (!s || !out || !n) return ATSC_E_INVALID;
+    *out = nullptr;
+    *n = 0;
+    int rc = flush(s);
+    if (rc) return rc;
+    std::vector<uint8_t> body;
+    for (const Item &it : s->items) body.insert(body.end(), it.record.begin(), it.record.end());
+    if (body.empty()) {
+        if (begin != 0 || count != 0) return ATSC_E_INVALID;
+        *out = (double *)malloc(8);
+        return *out ? ATSC_OK : ATSC_E_NOMEM;
+    }
+    double *buf = (double *)atsc::big_alloc((count ? count : 1) * sizeof(double));
+    if (!buf) return ATSC_E_NOMEM;
+    uint64_t got = 0;
+    rc = atsc_decompress_window(s->ctx, body.data(), body.size(), 0, begin, count, buf, count, &got);
+    if (rc) {
+        atsc_free(buf);
+        return rc;
+    }
+    *out = buf;
+    *n = got;
+    return ATSC_OK;
+    ATSC_API_END
+}
+
 extern "C" int atsc_stream_decompress(atsc_stream *s, double **out, uint64_t *n)
 {
     ATSC_API_BEGIN

@@ -292,6 +292,35 @@ extern "C" int atsc_vsri_get_all_timestamps(const atsc_vsri *v, int32_t **out, u
     ATSC_API_END
 }
 
+// The samples with indexed times in [t0, t1] (a window for the window decode): this-or-next(t0) .. this-or-previous(t1),
+// each end moved inwards while its sample's get_time falls outside [t0, t1] -- an off-grid time looks up the sample in
+// front of it (integer division, lib.rs:311), and a time behind the index looks up sample_count (lib.rs:175-193)
+extern "C" int atsc_vsri_sample_window(const atsc_vsri *v, int32_t t0, int32_t t1, uint64_t *begin, uint64_t *count)
+{
+    if (!v || !begin || !count) return ATSC_E_INVALID;
+    *begin = 0;
+    *count = 0;
+    const int32_t n = sample_count(v);
+    if (v->seg.empty() || n <= 0 || t1 < t0) return ATSC_OK;
+    int32_t i = 0, j = 0;
+    int r = atsc_vsri_get_this_or_next(v, t0, &i);
+    if (r < 0) return r;
+    if (r == 0) return ATSC_OK;
+    r = atsc_vsri_get_this_or_previous(v, t1, &j);
+    if (r < 0) return r;
+    if (r == 0) return ATSC_OK;
+    if (i < 0) i = 0;
+    if (j > n - 1) j = n - 1;
+    auto time_of = [&](int32_t x, int32_t &t) { return atsc_vsri_get_time(v, x, &t) == 1; };
+    int32_t t;
+    while (i <= j && (!time_of(i, t) || t < t0)) ++i;
+    while (j >= i && (!time_of(j, t) || t > t1)) --j;
+    if (j < i) return ATSC_OK;
+    *begin = (uint64_t)i;
+    *count = (uint64_t)(j - i) + 1;
+    return ATSC_OK;
+}
+
 // Vsri::flush_to (lib.rs:424-443): min, max, then one "m,x0,y0,count" line per segment
 extern "C" int atsc_vsri_flush_to(const atsc_vsri *v, const char *path)
 {

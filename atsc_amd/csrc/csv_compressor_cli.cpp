@@ -3,8 +3,8 @@
 // .bro (+ .vsri index, + .wavbro samples) out; `-u` turns .bro + .vsri back into .wbro + .csv.
 // Compression and decompression run on the GPU; the index and the text formats are host code.
 //
-//   csv-compressor [-o OUT] [-u] [--no-compression] [--output-vsri] [--output-wavbrro] [--output-csv]
-//                  [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
+//   csv-compressor [-o OUT] [-u [--from T0 --to T1]] [--no-compression] [--output-vsri] [--output-wavbrro]
+//                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
 
 #include <cstdio>
@@ -24,6 +24,8 @@ struct Args {
     int compressor = ATSC_AUTO;  // default_value = "auto" (main.rs:66)
     int error = 5;               // default_value_t = 5 (main.rs:73)
     int level = 0;
+    bool window = false;  // --from / --to (with -u): only the samples whose indexed times lie in [t0, t1]
+    int32_t t0 = 0, t1 = 0;
 };
 
 constexpr int PANIC = 101;  // exit status of a Rust panic: every failure below is an expect()/panic!()
@@ -35,6 +37,7 @@ void usage()
             "Usage: csv-compressor [OPTIONS] <INPUT>\n\nOptions:\n"
             "  -o, --output <OUTPUT>          where the result will be stored\n"
             "  -u                             uncompress the input\n"
+            "      --from <T0> --to <T1>      with -u: only the samples indexed at T0..=T1 (seconds since midnight)\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -78,6 +81,40 @@ int die(const char *what, int rc = 0, const char *detail = "")
     return PANIC;
 }
 
+// -u --from T0 --to T1: the index finds the window, only its samples are decoded; .wbro and .csv hold those samples,
+// their timestamps from the same get_time path as the whole file's (Metric::get_samples)
+int uncompress_window(const Args &a, const std::string &output_base, uint8_t *bro, uint64_t len)
+{
+    atsc_vsri *index = nullptr;
+    int rc = atsc_vsri_load(with_ext(a.input, "vsri").c_str(), &index);
+    if (rc) { atsc_free(bro); return die("failed to read vsri", rc); }
+    uint64_t begin = 0, count = 0;
+    rc = atsc_vsri_sample_window(index, a.t0, a.t1, &begin, &count);
+    if (rc) { atsc_free(bro); atsc_vsri_free(index); return die("vsri window", rc); }
+    std::vector<int64_t> ts(begin + count + 1);
+    rc = atsc_metric_sample_times(index, begin + count, ts.data());
+    atsc_vsri_free(index);
+    if (rc) { atsc_free(bro); return die("called `Option::unwrap()` on a `None` value (index has no time for a sample)"); }
+    std::vector<double> data(count ? count : 1);
+    uint64_t n = 0;
+    if (count) {
+        atsc_ctx *ctx = nullptr;
+        rc = atsc_ctx_create(&ctx, 0);
+        if (rc) { atsc_free(bro); return die("no GPU context", rc); }
+        rc = atsc_bro_open(bro, len, nullptr, nullptr);
+        if (!rc) rc = atsc_decompress_window(ctx, bro + 9, len - 9, 1, begin, count, data.data(), count, &n);
+        if (rc) { int e = die("decompress", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+        atsc_ctx_destroy(ctx);
+    }
+    atsc_free(bro);
+    const std::string wbro_path = with_ext(output_base, "wbro");
+    rc = atsc_wbro_write(wbro_path.c_str(), data.data(), n);
+    if (rc) return die("writing wavbrro", rc);
+    rc = atsc_samples_csv_write(with_ext(wbro_path, "csv").c_str(), ts.data() + begin, data.data(), n);
+    if (rc) return die("failed to write samples to file", rc);
+    return 0;
+}
+
 int uncompress(const Args &a, const std::string &output_base)  // main.rs:139-173
 {
     uint8_t *bro = nullptr;
@@ -85,6 +122,7 @@ int uncompress(const Args &a, const std::string &output_base)  // main.rs:139-17
     int rc = atsc_bro_read_file(a.input.c_str(), &bro, &len);
     if (rc) return die("failed to read bro file", rc);
     if (!bro) return 0;  // not a BRO file: nothing happens
+    if (a.window) return uncompress_window(a, output_base, bro, len);
     atsc_ctx *ctx = nullptr;
     rc = atsc_ctx_create(&ctx, 0);
     if (rc) { atsc_free(bro); return die("no GPU context", rc); }
@@ -159,6 +197,7 @@ int compress(const Args &a, const std::string &output_base)  // main.rs:174-207
 int main(int argc, char **argv)
 {
     Args a;
+    bool have_from = false, have_to = false;
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i], v;
         auto value = [&](const char *name) -> bool {
@@ -175,6 +214,17 @@ int main(int argc, char **argv)
         else if (s == "--output-wavbrro") a.output_wavbrro = true;
         else if (s == "--output-csv") a.output_csv = true;
         else if (value("--output") || value("-o")) { a.output = v; a.has_output = true; }
+        else if (value("--from") || value("--to")) {
+            const bool from = s.rfind("--from", 0) == 0;
+            char *end = nullptr;
+            const long long t = strtoll(v.c_str(), &end, 10);
+            if (v.empty() || *end || t < INT32_MIN || t > INT32_MAX) {
+                fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), from ? "--from" : "--to");
+                return 2;
+            }
+            (from ? a.t0 : a.t1) = (int32_t)t;
+            (from ? have_from : have_to) = true;
+        }
         else if (value("--compressor")) { if (!parse_compressor(v, a.compressor)) { fprintf(stderr, "error: invalid value '%s' for '--compressor'\n", v.c_str()); return 2; } }
         else if (value("--error") || value("-e")) { if (!parse_int(v, 0, 50, a.error)) { fprintf(stderr, "error: invalid value '%s' for '--error': not in 0..=50\n", v.c_str()); return 2; } }
         else if (value("--compression-selection-sample-level") || value("-c")) { if (!parse_int(v, 0, 6, a.level)) { fprintf(stderr, "error: invalid value '%s' for '-c': not in 0..=6\n", v.c_str()); return 2; } }
@@ -182,6 +232,11 @@ int main(int argc, char **argv)
         else a.input = s;
     }
     if (a.input.empty()) { usage(); return 2; }
+    if (have_from != have_to || ((have_from || have_to) && !a.uncompress)) {
+        fprintf(stderr, "error: '--from' and '--to' go together, with '-u'\n");
+        return 2;
+    }
+    a.window = have_from;
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) return die("Failed to retrieve metadata of the input");  // main.rs:226-229
     if (!S_ISREG(st.st_mode)) return die("Input is not a file");                                 // main.rs:219-221

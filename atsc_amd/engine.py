@@ -98,6 +98,18 @@ class Context:
         capi.check(rc, self._h)
         return out[: on.value]
 
+    def decompress_window_host(self, records, begin, count, has_count=False):
+        """Samples [begin, begin + count) of the decoded records (atsc_decompress_window): only the touched records
+        are planned and uploaded."""
+        b = np.frombuffer(bytes(records), dtype=np.uint8)
+        out = np.empty(max(int(count), 1), dtype=np.float64)
+        on = C.c_uint64()
+        rc = capi.lib().atsc_decompress_window(
+            self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count), int(begin), int(count),
+            out.ctypes.data_as(C.POINTER(C.c_double)), int(count), C.byref(on))
+        capi.check(rc, self._h)
+        return out[: on.value]
+
     # ---- device-resident path --------------------------------------------------------------
     def plan(self, frame_off):
         return Plan(self, frame_off)
@@ -193,6 +205,25 @@ class DPlan:
             C.c_void_p(stream))
         capi.check(rc, self.ctx._h)
 
+    def find_frames(self, begin, count):
+        """-> (frame_begin, frame_end): the frames the window [begin, begin + count) touches"""
+        fb, fe = C.c_uint64(), C.c_uint64()
+        capi.check(capi.lib().atsc_dplan_find_frames(self._h, int(begin), int(count), C.byref(fb), C.byref(fe)),
+                   self.ctx._h)
+        return fb.value, fe.value
+
+    def decompress_windows(self, d_body, begins, counts, d_out, out_off, stream=0):
+        """Enqueues the windows [begins[i], begins[i] + counts[i]) into d_out at out_off[i] (atsc_decompress_windows_dev)"""
+        b, pb = _u64(begins)
+        c, pc = _u64(counts)
+        o, po = _u64(out_off)
+        assert len(b) == len(c) == len(o)
+        assert d_out.element_size() == 8 and d_out.is_contiguous()
+        rc = capi.lib().atsc_decompress_windows_dev(
+            self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc, po, C.c_void_p(d_out.data_ptr()),
+            C.c_void_p(stream))
+        capi.check(rc, self.ctx._h)
+
 
 # ---- host-only helpers (no GPU) ------------------------------------------------------------
 def chunk_sizes(n):
@@ -214,6 +245,17 @@ def bro_prefix(n_frames):
     buf = (C.c_uint8 * 32)()
     k = capi.lib().atsc_bro_prefix(n_frames, buf)
     return bytes(buf[:k])
+
+
+def bro_find_window(bro, begin, count):
+    """-> dict(byte_begin, byte_end, frame_begin, frame_end, sample_begin): the records of a .bro image that the window
+    [begin, begin + count) touches (atsc_bro_find_window; host only)"""
+    b = np.frombuffer(bytes(bro), dtype=np.uint8)
+    v = [C.c_uint64() for _ in range(5)]
+    rc = capi.lib().atsc_bro_find_window(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(begin), int(count),
+                                         *[C.byref(x) for x in v])
+    capi.check(rc)
+    return dict(zip(("byte_begin", "byte_end", "frame_begin", "frame_end", "sample_begin"), (x.value for x in v)))
 
 
 def bro_open(bro):

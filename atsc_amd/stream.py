@@ -82,6 +82,14 @@ class CompressedStream:
         capi.check(capi.lib().atsc_stream_decompress(self._h, C.byref(p), C.byref(n)), self.ctx._h)
         return _take_f64(p, n)
 
+    def decompress_window(self, begin, count):
+        """decompress()[begin:begin + count] without decoding the frames outside it"""
+        p = C.POINTER(C.c_double)()
+        n = C.c_uint64()
+        capi.check(capi.lib().atsc_stream_decompress_window(self._h, int(begin), int(count), C.byref(p), C.byref(n)),
+                   self.ctx._h)
+        return _take_f64(p, n)
+
 
 def compress_data(ctx, vec, compressor=capi.AUTO, error=3, sample_level=0):
     """atsc/src/main.rs:130-165"""
@@ -101,6 +109,21 @@ def decompress_data(ctx, bro):
     capi.check(capi.lib().atsc_decompress_data(ctx._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b),
                                                C.byref(p), C.byref(n)), ctx._h)
     return _take_f64(p, n)
+
+
+def decompress_data_window(ctx, bro, begin, count):
+    """decompress_data(ctx, bro)[begin:begin + count]: atsc_bro_open, then atsc_decompress_window over the records"""
+    b = np.frombuffer(bytes(bro), dtype=np.uint8)
+    pb = b.ctypes.data_as(C.POINTER(C.c_uint8))
+    capi.check(capi.lib().atsc_bro_open(pb, len(b), None, None))
+    out = np.empty(max(int(count), 1), dtype=np.float64)
+    on = C.c_uint64()
+    # the records from the frame-count varint (offset 9) on, as atsc_decompress_data reads them
+    r = b[9:]
+    rc = capi.lib().atsc_decompress_window(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, int(begin), int(count),
+                                           out.ctypes.data_as(C.POINTER(C.c_double)), int(count), C.byref(on))
+    capi.check(rc, ctx._h)
+    return out[: on.value]
 
 
 def wbro_from_bytes(data):

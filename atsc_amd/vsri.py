@@ -92,6 +92,12 @@ class Vsri:
             raise capi.AtscError(r)
         return bool(r)
 
+    def sample_window(self, t0, t1):
+        """-> (begin, count): the samples whose indexed times lie in [t0, t1] (atsc_vsri_sample_window)"""
+        b, c = C.c_uint64(), C.c_uint64()
+        capi.check(capi.lib().atsc_vsri_sample_window(self._h, int(t0), int(t1), C.byref(b), C.byref(c)))
+        return b.value, c.value
+
     def get_all_timestamps(self):
         p = C.POINTER(C.c_int32)()
         n = C.c_uint64()

@@ -245,6 +245,41 @@ int atsc_decompress_frames(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len
 int atsc_decompress_frames_alloc(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count,
                                  double **out, uint64_t *out_n);
 
+/* Window decode: the samples [begin, begin + count) of the decoded stream (the indices atsc_decompress_frames
+ * returns), bit for bit what the full decode gives there, without decoding the frames the window does not touch.
+ * Frame records are independent (frame/mod.rs:25-33), so a window needs only the frames that overlap it; every
+ * frame keeps its own decode path (an FFT frame that runs an inverse transform in the full decode runs it here too).
+ * Validation: the record headers in front of the window's end are walked and checked as atsc_dplan_create checks
+ * them; payloads are checked only for the frames the window touches -- a corrupt payload outside the window is not
+ * seen.  begin + count beyond the stream: ATSC_E_INVALID, nothing written.  count == 0 is valid and does nothing. */
+/* The records a window touches in a .bro image (host only, no GPU): walks the record headers with the checks of
+ * atsc_bro_scan up to the first record that ends at or behind the window's end.  Outputs (each may be NULL): the byte
+ * range [byte_begin, byte_end) of the touched records in `bro`, their frame range [frame_begin, frame_end) and the
+ * stream sample index at which frame_begin starts -- what a storage layer needs to read only those bytes.  count == 0:
+ * an empty range at the record holding `begin`. */
+int atsc_bro_find_window(const uint8_t *bro, uint64_t len, uint64_t begin, uint64_t count, uint64_t *byte_begin,
+                         uint64_t *byte_end, uint64_t *frame_begin, uint64_t *frame_end, uint64_t *sample_begin);
+/* The frames [frame_begin, frame_end) of a plan that the window touches (binary search over the plan's host copy of
+ * the frame offsets). */
+int atsc_dplan_find_frames(const atsc_dplan *dp, uint64_t begin, uint64_t count, uint64_t *frame_begin,
+                           uint64_t *frame_end);
+/* Decodes n_windows windows of the plan's stream in one call: window i = [begin[i], begin[i] + count[i]) lands at
+ * d_out + out_off[i].  begin / count / out_off are HOST arrays, d_body / d_out device memory (d_out 8-byte aligned).
+ * Windows may overlap and come in any order; a frame several windows touch is decoded once per call.  Enqueued on
+ * `stream`, not synchronised.  A malformed payload inside a window sets the plan's status word, which this call does
+ * not read (atsc_decompress_window does).  The plan keeps the call's task tables and scratch: the next window call on
+ * the same plan waits (host side) until this one's work is done before it reuses them. */
+int atsc_decompress_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                const uint64_t *begin, const uint64_t *count, const uint64_t *out_off, double *d_out,
+                                void *stream);
+/* Host-pointer window decode (synchronous): walks the record headers only up to the window's last record, plans the
+ * touched records and uploads only their bytes.  (A window that touches a frame longer than 4096 samples walks the
+ * remaining headers as well: the large tier's launch forms depend on every large frame of the stream, and the window
+ * has to decode as the full decode does.)  *out_n = count on success, 0 on any error (ATSC_E_FORMAT for a
+ * malformed payload inside the window); ATSC_E_CAPACITY when out_cap < count. */
+int atsc_decompress_window(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t begin,
+                           uint64_t count, double *out, uint64_t out_cap, uint64_t *out_n);
+
 /* ------------------------------------------------------------------------ */
 /* CompressedStream mirror (atsc/src/data.rs:29-110)                          */
 /* ------------------------------------------------------------------------ */
@@ -267,6 +302,8 @@ uint64_t atsc_stream_frame_count(const atsc_stream *s);
 int atsc_stream_to_bytes(atsc_stream *s, uint8_t **out, uint64_t *len);
 /* data.rs:104-109 ; *out is malloc'd, release with atsc_free */
 int atsc_stream_decompress(atsc_stream *s, double **out, uint64_t *n);
+/* atsc_stream_decompress of the samples [begin, begin + count) only (atsc_decompress_window); release with atsc_free */
+int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uint64_t count, double **out, uint64_t *n);
 void atsc_free(void *p);
 
 /* compress_data / decompress_data of the atsc CLI (atsc/src/main.rs:130-172): clean (drop NaN/Inf),
@@ -342,6 +379,11 @@ int atsc_vsri_get_this_or_previous(const atsc_vsri *v, int32_t y, int32_t *out);
 int atsc_vsri_get_time(const atsc_vsri *v, int32_t x, int32_t *out);             /* lib.rs:320-341 */
 int atsc_vsri_is_empty(const atsc_vsri *v, int32_t t0, int32_t t1);  /* lib.rs:198-232; 1 / 0 */
 int atsc_vsri_get_all_timestamps(const atsc_vsri *v, int32_t **out, uint64_t *n); /* lib.rs:344-353; atsc_free */
+/* The samples whose indexed times (get_time, lib.rs:320-341) lie in [t0, t1], as a window for atsc_decompress_window:
+ * begin = get_this_or_next(t0), last = get_this_or_previous(t1) (lib.rs:137-148), each end then moved inwards past
+ * samples whose time falls outside [t0, t1] (an off-grid time looks up the sample in front of it).  *count = 0 when
+ * no sample falls inside.  ATSC_E_INVALID where a look-up panics in the reference. */
+int atsc_vsri_sample_window(const atsc_vsri *v, int32_t t0, int32_t t1, uint64_t *begin, uint64_t *count);
 /* vsri::day_elapsed_seconds (lib.rs:49-57); ATSC_E_INVALID outside chrono's DateTime range */
 int atsc_day_elapsed_seconds(int64_t timestamp_sec, int32_t *out);
 /* csv-compressor/src/csv.rs:41-56: `timestamp,value` files (i64, f64; csv crate reader / writer,
