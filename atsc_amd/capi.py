@@ -88,6 +88,9 @@ SIGNATURES = {
     "atsc_decompress_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, _u64p, _vp, _vp]),
     "atsc_decompress_window": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, _f64p, C.c_uint64,
                                          _u64p]),
+    "atsc_aggregate_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, _vp, _vp]),
+    "atsc_aggregate_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, _vp]),
+    "atsc_ctx_set_aggregate_scratch": (C.c_int, [_vp, C.c_uint64]),
     "atsc_stream_new": (C.c_int, [_vp, C.POINTER(_vp)]),
     "atsc_stream_from_bytes": (C.c_int, [_vp, _u8p, C.c_uint64, C.POINTER(_vp)]),
     "atsc_stream_free": (None, [_vp]),
@@ -98,6 +101,7 @@ SIGNATURES = {
     "atsc_stream_to_bytes": (C.c_int, [_vp, C.POINTER(_u8p), _u64p]),
     "atsc_stream_decompress": (C.c_int, [_vp, C.POINTER(_f64p), _u64p]),
     "atsc_stream_decompress_window": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(_f64p), _u64p]),
+    "atsc_stream_aggregate_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_free": (None, [_vp]),
     "atsc_compress_data": (C.c_int, [_vp, _f64p, C.c_uint64, C.c_int, C.c_uint8, C.c_int, C.POINTER(_u8p), _u64p]),
     "atsc_decompress_data": (C.c_int, [_vp, _u8p, C.c_uint64, C.POINTER(_f64p), _u64p]),
@@ -133,6 +137,7 @@ SIGNATURES = {
     "atsc_vsri_is_empty": (C.c_int, [_vp, C.c_int32, C.c_int32]),
     "atsc_vsri_get_all_timestamps": (C.c_int, [_vp, C.POINTER(_i32p), _u64p]),
     "atsc_vsri_sample_window": (C.c_int, [_vp, C.c_int32, C.c_int32, _u64p, _u64p]),
+    "atsc_vsri_step_windows": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _u64p, _u64p, C.c_uint64, _u64p]),
     "atsc_day_elapsed_seconds": (C.c_int, [C.c_int64, _i32p]),
     "atsc_samples_csv_read": (C.c_int, [C.c_char_p, C.POINTER(_i64p), C.POINTER(_f64p), _u64p]),
     "atsc_samples_csv_write": (C.c_int, [C.c_char_p, _i64p, _f64p, C.c_uint64]),

@@ -1,11 +1,12 @@
 // atsc -- command line front end over libatsc_hip.so with the reference's flags and file naming
 // (atsc/src/main.rs:29-127,176-243).  Every frame is compressed / decompressed on the GPU.
 //
-//   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT]]
+//   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
 
+#include <algorithm>
 #include <charconv>
 #include <cmath>
 #include <cstdio>
@@ -28,6 +29,7 @@ struct Args {
     std::string fields = "time,value";  // main.rs:218
     bool window = false;                // --samples BEGIN:COUNT (with -u): decode only that window
     uint64_t win_begin = 0, win_count = 0;
+    uint64_t buckets = 0;               // --buckets N (with -u): summaries of N-sample buckets into <file>.agg.csv
 };
 
 void usage()
@@ -38,6 +40,7 @@ void usage()
             "  -e, --error <ERROR>            maximum allowed error in %% (0..50) [default: 3]\n"
             "  -u                             uncompress the input file/directory\n"
             "      --samples <BEGIN:COUNT>    with -u: write only the samples [BEGIN, BEGIN+COUNT) to the .wbro\n"
+            "      --buckets <N>              with -u: write count,min,max,sum,first,last of every N samples to .agg.csv\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -95,6 +98,30 @@ std::string with_ext(const std::string &path, const char *ext)  // PathBuf::set_
     return base + "." + ext;
 }
 
+// -u --buckets N: one atsc_window_stats row per bucket of N samples of [begin, begin + count), the last bucket shorter
+int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const uint8_t *bro, uint64_t len, uint64_t begin,
+                  uint64_t count)
+{
+    const uint64_t nb = (count + a.buckets - 1) / a.buckets;
+    std::vector<uint64_t> b(nb), c(nb);
+    for (uint64_t k = 0; k < nb; ++k) {
+        b[k] = begin + k * a.buckets;
+        c[k] = std::min(a.buckets, begin + count - b[k]);
+    }
+    std::vector<atsc_window_stats> st(nb ? nb : 1);
+    // the records from the frame-count varint on, as atsc_decompress_data reads them
+    int rc = atsc_aggregate_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), st.data());
+    if (rc) return rc;
+    FILE *f = fopen(with_ext(path, "agg.csv").c_str(), "w");
+    if (!f) return ATSC_E_IO;
+    fprintf(f, "begin,count,min,max,sum,first,last\n");
+    for (uint64_t k = 0; k < nb; ++k)
+        fprintf(f, "%llu,%llu,%s,%s,%s,%s,%s\n", (unsigned long long)b[k], (unsigned long long)st[k].count,
+                debug_f64(st[k].min).c_str(), debug_f64(st[k].max).c_str(), debug_f64(st[k].sum).c_str(),
+                debug_f64(st[k].first).c_str(), debug_f64(st[k].last).c_str());
+    return fclose(f) == 0 ? ATSC_OK : ATSC_E_IO;
+}
+
 int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
 {
     if (a.uncompress) {  // main.rs:72-83
@@ -103,6 +130,14 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
         int rc = atsc_bro_read_file(path.c_str(), &bro, &len);
         if (rc) return rc;
         if (!bro) return ATSC_OK;  // not a BRO file: skipped silently
+        if (a.buckets) {
+            uint64_t ns = 0;
+            rc = atsc_bro_open(bro, len, nullptr, nullptr);
+            if (!rc && !a.window) rc = atsc_bro_scan(bro, len, nullptr, &ns);
+            if (!rc) rc = write_buckets(ctx, path, a, bro, len, a.window ? a.win_begin : 0, a.window ? a.win_count : ns);
+            atsc_free(bro);
+            return rc;
+        }
         double *out = nullptr;
         uint64_t n = 0;
         if (a.window) {
@@ -217,11 +252,20 @@ int main(int argc, char **argv)
             }
             a.window = true;
         }
+        else if (value("--buckets")) {
+            char *e = nullptr;
+            a.buckets = strtoull(v.c_str(), &e, 10);
+            if (v.empty() || *e || v[0] == '-' || a.buckets == 0) {
+                fprintf(stderr, "error: invalid value '%s' for '--buckets': expected a positive sample count\n", v.c_str());
+                return 2;
+            }
+        }
         else if (!s.empty() && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); usage(); return 2; }
         else a.input = s;
     }
     if (a.input.empty()) { usage(); return 2; }
     if (a.window && !a.uncompress) { fprintf(stderr, "error: '--samples' needs '-u'\n"); return 2; }
+    if (a.buckets && !a.uncompress) { fprintf(stderr, "error: '--buckets' needs '-u'\n"); return 2; }
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) { fprintf(stderr, "[ERROR] %s: No such file or directory\n", a.input.c_str()); return 1; }
     atsc_ctx *ctx = nullptr;

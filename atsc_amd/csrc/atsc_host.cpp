@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -57,6 +58,11 @@ __attribute__((weak)) hipError_t launch_decompress_window(const DevDFrame *frame
                                                           int *status, hipStream_t s);
 __attribute__((weak)) hipError_t launch_window_gather(const DevWGather *g, uint32_t n, uint32_t max_len,
                                                       const double *scratch, double *out, hipStream_t s);
+// the windowed aggregates' reduce kernels (atsc_aggregate.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_agg_tiles(const DevAggTile *tasks, uint32_t n, const double *scratch,
+                                                  DevAggPart *part, double *fl, hipStream_t s);
+__attribute__((weak)) hipError_t launch_agg_combine(const DevAggComb *tasks, uint32_t n, DevAggPart *part,
+                                                    const double *fl, void *stats, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -122,6 +128,7 @@ struct atsc_ctx {
     unsigned char *h_stage = nullptr;              // page-locked staging for tables a kernel copies up (h2d_small)
     size_t h_stage_cap = 0, h_stage_used = 0;
     hipEvent_t ev_copy[2] = {nullptr, nullptr};    // "part g's samples are on the device"
+    uint64_t agg_budget = 0;                       // atsc_ctx_set_aggregate_scratch (bytes; 0: the default)
 };
 
 struct PlanTables {
@@ -225,6 +232,14 @@ struct atsc_dplan {
     mutable uint64_t win_scratch_cap = 0;
     mutable hipEvent_t ev_win = nullptr;
     mutable bool win_pending = false;
+    // the same for the last atsc_aggregate_windows_dev call: tables (staging; device copy followed by the partials),
+    // decoded-sample scratch, end of work
+    mutable unsigned char *h_agg = nullptr, *d_agg = nullptr;
+    mutable size_t agg_hcap = 0, agg_dcap = 0;
+    mutable double *d_agg_scratch = nullptr;
+    mutable uint64_t agg_scratch_cap = 0;
+    mutable hipEvent_t ev_agg = nullptr;
+    mutable bool agg_pending = false;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1831,6 +1846,10 @@ extern "C" void atsc_dplan_destroy(atsc_dplan *p)
     pool_free(p->ctx, p->d_win);
     pool_free(p->ctx, p->d_win_scratch);
     if (p->ev_win) (void)hipEventDestroy(p->ev_win);
+    if (p->h_agg) (void)hipHostFree(p->h_agg);
+    pool_free(p->ctx, p->d_agg);
+    pool_free(p->ctx, p->d_agg_scratch);
+    if (p->ev_agg) (void)hipEventDestroy(p->ev_agg);
     pool_free(p->ctx, p->d_frames);
     pool_free(p->ctx, p->d_ids);
     pool_free(p->ctx, p->d_status);
@@ -2647,6 +2666,421 @@ done:
     if (rc) (void)hipStreamSynchronize(ws);
     pool_free(ctx, d_body);
     pool_free(ctx, d_out);
+    atsc_dplan_destroy(dp);
+    return rc;
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
+// windowed aggregates: count / min / max / sum / first / last of sample windows (atsc_aggregate.hip)
+// ------------------------------------------------------------------------------------------
+// Decoded samples reach the reduce kernels through one scratch region of whole tiles, piece after piece in stream
+// order: the windows' union ("covering intervals") is cut into pieces at multiples of AGG_TILE.  Covered tile ranges
+// closer than AGG_GAP_TILES share a span, so that scattered windows do not each cost a piece of launches.
+static const uint64_t AGG_MIN_PIECE = 32ull * AGG_TILE;  // the least a piece holds, whatever the budget
+static const uint64_t AGG_GAP_TILES = 64;
+// default piece length (samples) by the tier of the touched frames.  The sweep of profiles/aggregate_probe.json found no
+// gain from pieces that fit the Infinity Cache (2^21-2^22 samples): fewer pieces win in both framings, most where the
+// large tier's launch sequence (~65 us whatever its frame count) runs once per piece.
+static const uint64_t AGG_PIECE_SMALL = 1ull << 24;
+static const uint64_t AGG_PIECE_LARGE = 1ull << 24;
+
+extern "C" int atsc_ctx_set_aggregate_scratch(atsc_ctx *ctx, uint64_t bytes)
+{
+    if (!ctx) return ATSC_E_INVALID;
+    ctx->agg_budget = bytes;
+    return ATSC_OK;
+}
+
+static void agg_empty_record(atsc_window_stats &r)
+{
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    r.count = 0;
+    r.min = r.max = r.first = r.last = nan;
+    r.sum = 0.0;
+}
+
+// The device call.  Host work: covering intervals, pieces, the decode tasks of every piece (one per touched frame: its
+// covered samples' hull in the piece), the tile tasks (a full tile that windows cover past their first tile and before
+// their last one is reduced once, into a shared partial; every window's first and last tile are reduced for it alone)
+// and the combine passes (groups of 64 partials until one is left per window).  All of it goes up in one copy; then,
+// per piece, the window decode's launchers into scratch and k_agg_tiles, and k_agg_combine once per pass.
+// org: the stream index of the plan's first sample (a plan of the touched records only, in the host call): tiles lie at
+// multiples of AGG_TILE in the stream's index, not the plan's.  Indices below are the stream's unless named otherwise.
+static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                         const uint64_t *begin, const uint64_t *count, atsc_window_stats *d_stats, void *stream, uint64_t org)
+{
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_stats)))
+        return fail(ctx, ATSC_E_INVALID, "aggregate_windows: null argument");
+    if ((uintptr_t)d_stats & 7u) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: d_stats is not 8-byte aligned");
+    const uint64_t ns = dp->n_samples;
+    for (uint64_t i = 0; i < n_windows; ++i)
+        if (begin[i] > ns || count[i] > ns - begin[i]) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: window beyond the stream");
+    if (n_windows == 0) return ATSC_OK;
+    if (n_windows >= 0xffffffffull) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: more than 2^32 - 2 windows");
+    if (!launch_decompress_window || !launch_window_gather || !launch_agg_tiles || !launch_agg_combine)
+        return fail(ctx, ATSC_E_UNSUPPORTED, "aggregate_windows: no aggregate kernels");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint64_t T = AGG_TILE, W = n_windows;
+    const auto &F = dp->h_frames;
+    // covering intervals: the union of the non-empty windows
+    std::vector<std::pair<uint64_t, uint64_t>> cov;
+    for (uint64_t i = 0; i < W; ++i)
+        if (count[i]) cov.emplace_back(org + begin[i], org + begin[i] + count[i]);
+    std::sort(cov.begin(), cov.end());
+    {
+        size_t m = 0;
+        for (const auto &v : cov) {
+            if (m && v.first <= cov[m - 1].second) cov[m - 1].second = std::max(cov[m - 1].second, v.second);
+            else cov[m++] = v;
+        }
+        cov.resize(m);
+    }
+    bool large = false;
+    for (size_t c = 0; c < cov.size() && !large; ++c) {
+        uint64_t fb, fe;
+        (void)atsc_dplan_find_frames(dp, cov[c].first - org, cov[c].second - cov[c].first, &fb, &fe);
+        for (uint64_t f = fb; f < fe && !large; ++f) large = dp->h_cls[f] == CLASS_LARGE;
+    }
+    // piece length: the budget less room for two large frames that cross the piece's ends
+    const uint64_t spill = large ? 2ull * MAX_FRAME : 0;
+    const uint64_t want = ctx->agg_budget ? ctx->agg_budget / sizeof(double) : (large ? AGG_PIECE_LARGE : AGG_PIECE_SMALL) + spill;
+    const uint64_t piece_tiles = std::max<uint64_t>(AGG_MIN_PIECE, want > spill ? (want - spill) / T * T : 0) / T;
+    struct Piece {
+        uint64_t k0, k1;  // tiles [k0, k1): samples [k0 T, k1 T) at scratch[0, (k1 - k0) T)
+    };
+    std::vector<Piece> pcs;
+    uint64_t region_tiles = 0;
+    for (size_t a = 0; a < cov.size();) {
+        const uint64_t k0 = cov[a].first / T;
+        uint64_t k1 = (cov[a].second + T - 1) / T;
+        size_t z = a + 1;
+        while (z < cov.size() && cov[z].first / T < k1 + AGG_GAP_TILES) k1 = std::max(k1, (cov[z++].second + T - 1) / T);
+        for (uint64_t k = k0; k < k1; k += piece_tiles) {
+            pcs.push_back(Piece{k, std::min(k1, k + piece_tiles)});
+            region_tiles = std::max(region_tiles, pcs.back().k1 - k);
+        }
+        a = z;
+    }
+    const uint64_t region = region_tiles * T;
+    // shared full tiles: the tiles past a window's first and before its last, merged over the windows
+    std::vector<std::pair<uint64_t, uint64_t>> mids;
+    for (uint64_t i = 0; i < W; ++i) {
+        if (!count[i]) continue;
+        const uint64_t kb = (org + begin[i]) / T, ke = (org + begin[i] + count[i] - 1) / T;
+        if (ke >= kb + 2) mids.emplace_back(kb + 1, ke);
+    }
+    std::sort(mids.begin(), mids.end());
+    {
+        size_t m = 0;
+        for (const auto &v : mids) {
+            if (m && v.first <= mids[m - 1].second) mids[m - 1].second = std::max(mids[m - 1].second, v.second);
+            else mids[m++] = v;
+        }
+        mids.resize(m);
+    }
+    std::vector<uint64_t> mid_at(mids.size());
+    uint64_t U = 0;
+    for (size_t r = 0; r < mids.size(); ++r) { mid_at[r] = U; U += mids[r].second - mids[r].first; }
+    auto shared_index = [&](uint64_t k) {  // index of full tile k among the shared partials
+        const size_t r = (size_t)(std::upper_bound(mids.begin(), mids.end(), std::pair<uint64_t, uint64_t>(k, ~0ull)) - mids.begin()) - 1;
+        return mid_at[r] + (k - mids[r].first);
+    };
+    // tile tasks, by tile; part[] = [U shared | first, last tile of each window | combine levels]
+    struct TT {
+        uint64_t k;
+        DevAggTile t;
+    };
+    std::vector<TT> tt;
+    tt.reserve(U + 2 * W);
+    for (size_t r = 0; r < mids.size(); ++r)
+        for (uint64_t k = mids[r].first; k < mids[r].second; ++k)
+            tt.push_back(TT{k, DevAggTile{0, mid_at[r] + (k - mids[r].first), 0, (uint32_t)T, 0, 0}});
+    struct Lv {
+        uint64_t head, tail, mid, n;
+    };
+    std::vector<Lv> lv(W);
+    for (uint64_t i = 0; i < W; ++i) {
+        if (!count[i]) { lv[i] = Lv{0, 0, 0, 0}; continue; }
+        const uint64_t b = org + begin[i], e = b + count[i], kb = b / T, ke = (e - 1) / T;
+        tt.push_back(TT{kb, DevAggTile{0, U + 2 * i, (uint32_t)(b - kb * T), (uint32_t)(std::min(e, (kb + 1) * T) - kb * T),
+                                       (uint32_t)i, AGG_FIRST | (ke == kb ? AGG_LAST : 0u)}});
+        if (ke > kb) tt.push_back(TT{ke, DevAggTile{0, U + 2 * i + 1, 0, (uint32_t)(e - ke * T), (uint32_t)i, AGG_LAST}});
+        lv[i] = Lv{U + 2 * i, ke > kb ? U + 2 * i + 1 : U + 2 * i, ke >= kb + 2 ? shared_index(kb + 1) - 1 : 0, ke - kb + 1};
+    }
+    std::stable_sort(tt.begin(), tt.end(), [](const TT &x, const TT &y) { return x.k < y.k; });
+    // combine passes: groups of 64 entries of each window's list until one is left
+    uint64_t part_n = U + 2 * W;
+    std::vector<DevAggComb> comb;
+    std::vector<size_t> pass_at{0};
+    {
+        std::vector<uint32_t> live(W), next;
+        for (uint64_t i = 0; i < W; ++i) live[i] = (uint32_t)i;
+        while (!live.empty()) {
+            next.clear();
+            for (uint32_t i : live) {
+                Lv &l = lv[i];
+                const uint64_t G = std::max<uint64_t>(1, (l.n + 63) / 64);
+                if (G == 1) {
+                    comb.push_back(DevAggComb{l.head, l.tail, l.mid, i, (uint32_t)l.n, 0, i, 1});
+                    continue;
+                }
+                const uint64_t base = part_n;
+                part_n += G;
+                for (uint64_t g = 0; g < G; ++g) comb.push_back(DevAggComb{l.head, l.tail, l.mid, base + g, (uint32_t)l.n, (uint32_t)g, i, 0});
+                l = Lv{base, base + G - 1, base, G};
+                next.push_back(i);
+            }
+            pass_at.push_back(comb.size());
+            live.swap(next);
+        }
+    }
+    // decode tasks of every piece: per touched frame, the hull of its covered samples inside the piece.  A large frame
+    // is decoded whole: in place when it lies inside the piece's tiles, else into one of two spill slots behind the
+    // region and copied from there (k_window_gather).
+    struct PieceTab {
+        size_t small_at[CLASS_LARGE], big_at, gat_at, tile_at;
+        uint32_t small_n[CLASS_LARGE], big_n, gat_n, tile_n, max_len;
+    };
+    std::vector<PieceTab> ptab(pcs.size());
+    std::vector<DevWTask> small[CLASS_LARGE];
+    std::vector<DevDFrame> big;
+    std::vector<DevWGather> gat;
+    std::vector<DevAggTile> tiles;
+    tiles.reserve(tt.size());
+    uint32_t max_big = 0, spills_used = 0;
+    size_t ci = 0, ti = 0;
+    for (size_t p = 0; p < pcs.size(); ++p) {
+        PieceTab &pt = ptab[p];
+        const uint64_t S0 = pcs[p].k0 * T, S1 = pcs[p].k1 * T;
+        for (int c = 0; c < CLASS_LARGE; ++c) pt.small_at[c] = small[c].size();
+        pt.big_at = big.size();
+        pt.gat_at = gat.size();
+        pt.tile_at = tiles.size();
+        pt.max_len = 0;
+        uint32_t n_spill = 0;
+        auto emit = [&](uint64_t f, uint64_t lo, uint64_t hi) {
+            const uint64_t fo = org + F[f].out_off, fn = F[f].n;
+            const int c = dp->h_cls[f];
+            if (c != CLASS_LARGE) {
+                small[c].push_back(DevWTask{fo + lo - S0, (uint32_t)f, (uint32_t)lo, (uint32_t)hi, 0});
+                return;
+            }
+            DevDFrame d = F[f];
+            if (fo >= S0 && fo + fn <= S1) {
+                d.out_off = fo - S0;
+            } else {
+                const uint64_t sp = region + (uint64_t)MAX_FRAME * n_spill++;
+                d.out_off = sp;
+                gat.push_back(DevWGather{sp + lo, fo + lo - S0, (uint32_t)(hi - lo), 0});
+                pt.max_len = std::max(pt.max_len, (uint32_t)(hi - lo));
+            }
+            big.push_back(d);
+        };
+        while (ci < cov.size() && cov[ci].second <= S0) ++ci;
+        uint64_t hf = ~0ull, hlo = 0, hhi = 0;
+        for (size_t c = ci; c < cov.size() && cov[c].first < S1; ++c) {
+            const uint64_t a = std::max(cov[c].first, S0), z = std::min(cov[c].second, S1);
+            uint64_t fb, fe;
+            (void)atsc_dplan_find_frames(dp, a - org, z - a, &fb, &fe);
+            for (uint64_t f = fb; f < fe; ++f) {
+                const uint64_t fo = org + F[f].out_off, fn = F[f].n;
+                const uint64_t lo = std::max(a, fo) - fo, hi = std::min(z, fo + fn) - fo;
+                if (f == hf) { hhi = hi; continue; }
+                if (hf != ~0ull) emit(hf, hlo, hhi);
+                hf = f;
+                hlo = lo;
+                hhi = hi;
+            }
+        }
+        if (hf != ~0ull) emit(hf, hlo, hhi);
+        if (n_spill > 2) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (spill slots)");
+        spills_used = std::max(spills_used, n_spill);
+        for (; ti < tt.size() && tt[ti].k < pcs[p].k1; ++ti) {
+            DevAggTile t = tt[ti].t;
+            t.src = (tt[ti].k - pcs[p].k0) * T;
+            tiles.push_back(t);
+        }
+        for (int c = 0; c < CLASS_LARGE; ++c) pt.small_n[c] = (uint32_t)(small[c].size() - pt.small_at[c]);
+        pt.big_n = (uint32_t)(big.size() - pt.big_at);
+        pt.gat_n = (uint32_t)(gat.size() - pt.gat_at);
+        pt.tile_n = (uint32_t)(tiles.size() - pt.tile_at);
+        max_big = std::max(max_big, pt.big_n);
+    }
+    if (ti != tt.size()) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (tile outside the pieces)");
+    // the previous call's tables, partials and scratch are reused once its work is done
+    if (dp->agg_pending) {
+        HIPCHK(ctx, hipEventSynchronize(dp->ev_agg));
+        dp->agg_pending = false;
+    }
+    // one upload: per class the pieces' task lists, the large sub-plans, ids 0.., copies, tile tasks, combine tasks;
+    // behind them (device only) the partials and the windows' first / last samples
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t off_small[CLASS_LARGE], bytes = 0;
+    for (int c = 0; c < CLASS_LARGE; ++c) { off_small[c] = bytes; bytes = al(bytes + small[c].size() * sizeof(DevWTask)); }
+    const size_t off_big = bytes;
+    bytes = al(bytes + big.size() * sizeof(DevDFrame));
+    const size_t off_ids = bytes;
+    bytes = al(bytes + max_big * sizeof(uint32_t));
+    const size_t off_gat = bytes;
+    bytes = al(bytes + gat.size() * sizeof(DevWGather));
+    const size_t off_tiles = bytes;
+    bytes = al(bytes + tiles.size() * sizeof(DevAggTile));
+    const size_t off_comb = bytes;
+    bytes = al(bytes + comb.size() * sizeof(DevAggComb));
+    const size_t up_bytes = bytes, off_part = bytes;
+    bytes = al(bytes + part_n * sizeof(DevAggPart));
+    const size_t off_fl = bytes;
+    bytes = al(bytes + 2 * W * sizeof(double));
+    if (up_bytes > dp->agg_hcap) {
+        if (dp->h_agg) (void)hipHostFree(dp->h_agg);
+        dp->h_agg = nullptr;
+        dp->agg_hcap = 0;
+        const size_t cap = std::max<size_t>(up_bytes, 64u << 10);
+        HIPCHK(ctx, hipHostMalloc((void **)&dp->h_agg, cap, hipHostMallocDefault));
+        dp->agg_hcap = cap;
+    }
+    if (bytes > dp->agg_dcap) {
+        pool_free(ctx, dp->d_agg);
+        dp->d_agg = nullptr;
+        dp->agg_dcap = 0;
+        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_agg, bytes));
+        dp->agg_dcap = bytes;
+    }
+    const uint64_t scr_need = region + (uint64_t)MAX_FRAME * spills_used;
+    if (scr_need > dp->agg_scratch_cap) {
+        pool_free(ctx, dp->d_agg_scratch);
+        dp->d_agg_scratch = nullptr;
+        dp->agg_scratch_cap = 0;
+        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_agg_scratch, scr_need * sizeof(double)));
+        dp->agg_scratch_cap = scr_need;
+    }
+    if (!dp->ev_agg) HIPCHK(ctx, hipEventCreateWithFlags(&dp->ev_agg, hipEventDisableTiming));
+    unsigned char *h = dp->h_agg, *d = dp->d_agg;
+    for (int c = 0; c < CLASS_LARGE; ++c)
+        if (!small[c].empty()) memcpy(h + off_small[c], small[c].data(), small[c].size() * sizeof(DevWTask));
+    if (!big.empty()) memcpy(h + off_big, big.data(), big.size() * sizeof(DevDFrame));
+    for (uint32_t i = 0; i < max_big; ++i) ((uint32_t *)(h + off_ids))[i] = i;
+    if (!gat.empty()) memcpy(h + off_gat, gat.data(), gat.size() * sizeof(DevWGather));
+    if (!tiles.empty()) memcpy(h + off_tiles, tiles.data(), tiles.size() * sizeof(DevAggTile));
+    memcpy(h + off_comb, comb.data(), comb.size() * sizeof(DevAggComb));
+    HIPCHK(ctx, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, s));
+    double *scr = dp->d_agg_scratch;
+    DevAggPart *part = (DevAggPart *)(d + off_part);
+    double *fl = (double *)(d + off_fl);
+    for (size_t p = 0; p < pcs.size(); ++p) {
+        const PieceTab &pt = ptab[p];
+        for (int c = 0; c < CLASS_LARGE; ++c) {
+            if (!pt.small_n[c]) continue;
+            const hipError_t e = launch_decompress_window(dp->d_frames, (const DevWTask *)(d + off_small[c]) + pt.small_at[c], c,
+                                                          pt.small_n[c], dp->class_lds[c], dp->tabs.d_plans, dp->tabs.d_tw,
+                                                          d_body, scr, dp->d_status, s);
+            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_decompress (aggregate)", e);
+        }
+        if (pt.big_n) {
+            const hipError_t e = launch_decompress_large(
+                pt.big_n, (const DevDFrame *)(d + off_big) + pt.big_at, (const uint32_t *)(d + off_ids), dp->tabs.d_plans,
+                dp->tabs.d_tw, d_body, scr, dp->d_status, dp->d_ws, dp->ws_stride, dp->ws_slots, dp->large_tiled ? 1 : 0,
+                large_sparse() ? 1 : 0, s, dp->large_pre.tiles1 ? &dp->large_pre : nullptr,
+                dp->large_choice_count <= LARGE_SPLIT_MAX ? dp->large_sp_tiles : 0);
+            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_decompress_large (aggregate)", e);
+        }
+        if (pt.gat_n) {
+            const hipError_t e = launch_window_gather((const DevWGather *)(d + off_gat) + pt.gat_at, pt.gat_n, pt.max_len, scr,
+                                                      scr, s);
+            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_window_gather (aggregate)", e);
+        }
+        const hipError_t e = launch_agg_tiles((const DevAggTile *)(d + off_tiles) + pt.tile_at, pt.tile_n, scr, part, fl, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_agg_tiles", e);
+    }
+    for (size_t q = 0; q + 1 < pass_at.size(); ++q) {
+        const hipError_t e = launch_agg_combine((const DevAggComb *)(d + off_comb) + pass_at[q], (uint32_t)(pass_at[q + 1] - pass_at[q]),
+                                                part, fl, d_stats, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_agg_combine", e);
+    }
+    HIPCHK(ctx, hipEventRecord(dp->ev_agg, s));
+    dp->agg_pending = true;
+    return ATSC_OK;
+}
+extern "C" int atsc_aggregate_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                          const uint64_t *begin, const uint64_t *count, atsc_window_stats *d_stats,
+                                          void *stream)
+{
+    ATSC_API_BEGIN
+    return aggregate_dev(ctx, dp, d_body, n_windows, begin, count, d_stats, stream, 0);
+    ATSC_API_END
+}
+
+// Host call: walks the headers from the first non-empty window's first record to the record holding the last window's
+// end, plans those records only and uploads only their bytes (atsc_decompress_window's path for a set of windows).
+extern "C" int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                      const uint64_t *begin, const uint64_t *count, atsc_window_stats *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: null argument");
+    if (n_windows == 0) return ATSC_OK;
+    uint64_t pos = 0, max_frames = ~0ull;
+    if (has_count) {
+        if (!host_varint(body, body_len, pos, max_frames)) return fail(ctx, ATSC_E_FORMAT, "aggregate_windows: frame count");
+        if (max_frames > body_len / 4) return fail(ctx, ATSC_E_FORMAT, "aggregate_windows: frame count exceeds the bytes present");
+    }
+    uint64_t B = ~0ull, E = 0;
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        if (begin[i] + count[i] < begin[i]) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: window beyond the stream");
+        E = std::max(E, begin[i] + count[i]);
+        if (count[i]) B = std::min(B, begin[i]);
+    }
+    const bool any = B != ~0ull;
+    if (!any) B = E;  // only empty windows: the walk checks that each begins inside the stream
+    WindowWalk w;
+    int rc = window_walk(body, body_len, pos, max_frames, B, E - B, true, w);
+    if (rc) return fail(ctx, rc, rc == ATSC_E_INVALID ? "aggregate_windows: window beyond the stream" : "aggregate_windows: record walk");
+    if (!any) {
+        for (uint64_t i = 0; i < n_windows; ++i) agg_empty_record(out[i]);
+        return ATSC_OK;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->work_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->work_stream, hipStreamNonBlocking));
+    hipStream_t ws = ctx->work_stream;
+    const uint64_t slice = w.byte_end - w.byte_begin;
+    atsc_dplan *dp = nullptr;
+    rc = dplan_create_range(ctx, body + w.byte_begin, slice, 0, 0, ~0ull, nullptr, &dp);
+    if (rc) return rc;
+    if (dp->class_count[CLASS_LARGE]) {
+        // the large tier's launch forms from every large frame of the stream, as in atsc_decompress_window
+        DPlanHost Hw;
+        const char *why;
+        rc = dplan_parse(body, body_len, has_count, Hw, &why);
+        if (rc) { atsc_dplan_destroy(dp); return fail(ctx, rc, why); }
+        large_choices(dp, Hw.tabs.plans, Hw.frames, Hw.cls);
+    }
+    std::vector<uint64_t> b2(n_windows);
+    for (uint64_t i = 0; i < n_windows; ++i) b2[i] = count[i] ? begin[i] - w.sample_begin : 0;
+    uint8_t *d_body = nullptr;
+    atsc_window_stats *d_stats = nullptr;
+    int status = 0;
+    hipError_t e = hipSuccess;
+#define ACHK(call)                                                                 \
+    do {                                                                           \
+        e = (call);                                                                \
+        if (e != hipSuccess) { rc = fail(ctx, ATSC_E_HIP, #call, e); goto done; } \
+    } while (0)
+    ACHK(pool_alloc(ctx, (void **)&d_body, std::max<uint64_t>(slice, 16)));
+    ACHK(pool_alloc(ctx, (void **)&d_stats, n_windows * sizeof(atsc_window_stats)));
+    ACHK(hipMemcpyAsync(d_body, body + w.byte_begin, slice, hipMemcpyHostToDevice, ws));
+    rc = aggregate_dev(ctx, dp, d_body, n_windows, b2.data(), count, d_stats, ws, w.sample_begin);
+    if (rc) goto done;
+    ACHK(hipMemcpyAsync(&status, dp->d_status, sizeof(int), hipMemcpyDeviceToHost, ws));
+    ACHK(hipStreamSynchronize(ws));
+    if (status) { rc = fail(ctx, ATSC_E_FORMAT, "aggregate_windows: malformed payload"); goto done; }
+    ACHK(hipMemcpyAsync(out, d_stats, n_windows * sizeof(atsc_window_stats), hipMemcpyDeviceToHost, ws));
+    ACHK(hipStreamSynchronize(ws));
+#undef ACHK
+done:
+    if (rc) (void)hipStreamSynchronize(ws);
+    pool_free(ctx, d_body);
+    pool_free(ctx, d_stats);
     atsc_dplan_destroy(dp);
     return rc;
     ATSC_API_END

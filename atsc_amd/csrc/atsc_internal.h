@@ -182,6 +182,29 @@ struct DevWGather {
     uint32_t len, pad;
 };
 
+// windowed aggregates (atsc_aggregate_windows_dev, atsc_aggregate.hip): tiles of AGG_TILE samples at multiples of
+// AGG_TILE in the stream index
+constexpr uint32_t AGG_TILE = 2048;
+// the partial of a tile or of a group of tiles: NaN-free sum / min / max / count (min = +inf, max = -inf when count == 0)
+struct DevAggPart {
+    double sum, mn, mx;
+    uint64_t count;
+};
+enum : uint32_t { AGG_FIRST = 1, AGG_LAST = 2 };
+// one tile of k_agg_tiles: slots [lo, hi) of the tile whose slot 0 is scratch[src] -> part[dst]; AGG_FIRST / AGG_LAST:
+// also fl[2 win] = slot lo / fl[2 win + 1] = slot hi - 1
+struct DevAggTile {
+    uint64_t src, dst;
+    uint32_t lo, hi;
+    uint32_t win, flags;
+};
+// one group of k_agg_combine: entries j in [64 g, min(64 g + 64, n)) of a window's partial list (entry 0 at part[head],
+// entry n - 1 at part[tail], entry j else at part[mid + j]) -> part[dst], or (final_) -> the stats record of window dst
+struct DevAggComb {
+    uint64_t head, tail, mid, dst;
+    uint32_t n, g, win, final_;
+};
+
 static inline uint32_t varint_len_u64(uint64_t v)
 {
     return v < 251 ? 1u : v < (1ull << 16) ? 3u : v < (1ull << 32) ? 5u : 9u;

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -309,6 +310,26 @@ extern "C" int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uin
     *out = buf;
     *n = got;
     return ATSC_OK;
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                             atsc_window_stats *out)
+{
+    ATSC_API_BEGIN
+    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
+    int rc = flush(s);
+    if (rc) return rc;
+    std::vector<uint8_t> body;
+    for (const Item &it : s->items) body.insert(body.end(), it.record.begin(), it.record.end());
+    if (body.empty()) {  // no frame: only empty windows at 0
+        for (uint64_t i = 0; i < n_windows; ++i)
+            if (begin[i] != 0 || count[i] != 0) return ATSC_E_INVALID;
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (uint64_t i = 0; i < n_windows; ++i) out[i] = atsc_window_stats{0, nan, nan, 0.0, nan, nan};
+        return ATSC_OK;
+    }
+    return atsc_aggregate_windows(s->ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
     ATSC_API_END
 }
 

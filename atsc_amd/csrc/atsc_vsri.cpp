@@ -6,6 +6,7 @@
 // Arithmetic is Rust's i32 in a release build: wrapping add / sub / mul, division truncating toward
 // zero; where the reference panics (division by zero on a one-point segment, i32::MIN / -1, unwrap
 // of a missing value) the entry points return an error code instead.
+#include <algorithm>
 #include <charconv>
 #include <cmath>
 #include <cstdio>
@@ -318,6 +319,27 @@ extern "C" int atsc_vsri_sample_window(const atsc_vsri *v, int32_t t0, int32_t t
     if (j < i) return ATSC_OK;
     *begin = (uint64_t)i;
     *count = (uint64_t)(j - i) + 1;
+    return ATSC_OK;
+}
+
+// Time buckets of `step` from t0 through t1 as sample windows (atsc_vsri_sample_window of each); the bucket starts are
+// counted in 64 bits, so that a bucket near INT32_MAX neither wraps nor loops
+extern "C" int atsc_vsri_step_windows(const atsc_vsri *v, int32_t t0, int32_t t1, int32_t step, uint64_t *begin,
+                                      uint64_t *count, uint64_t cap, uint64_t *n)
+{
+    if (!v || !n || step < 1) return ATSC_E_INVALID;
+    *n = 0;
+    if (t1 < t0) return ATSC_OK;
+    const uint64_t nb = (uint64_t)(((int64_t)t1 - (int64_t)t0) / step) + 1;
+    *n = nb;
+    if (cap < nb) return ATSC_E_CAPACITY;
+    if (!begin || !count) return ATSC_E_INVALID;
+    for (uint64_t k = 0; k < nb; ++k) {
+        const int64_t a = (int64_t)t0 + (int64_t)k * step;
+        const int64_t z = std::min<int64_t>(a + step - 1, t1);
+        const int rc = atsc_vsri_sample_window(v, (int32_t)a, (int32_t)z, &begin[k], &count[k]);
+        if (rc < 0) return rc;
+    }
     return ATSC_OK;
 }
 

@@ -3,10 +3,12 @@
 // .bro (+ .vsri index, + .wavbro samples) out; `-u` turns .bro + .vsri back into .wbro + .csv.
 // Compression and decompression run on the GPU; the index and the text formats are host code.
 //
-//   csv-compressor [-o OUT] [-u [--from T0 --to T1]] [--no-compression] [--output-vsri] [--output-wavbrro]
+//   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S]]] [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
 
+#include <charconv>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +28,7 @@ struct Args {
     int level = 0;
     bool window = false;  // --from / --to (with -u): only the samples whose indexed times lie in [t0, t1]
     int32_t t0 = 0, t1 = 0;
+    int32_t step = 0;  // --step S (with --from / --to): summaries of S-second buckets into <out>.agg.csv
 };
 
 constexpr int PANIC = 101;  // exit status of a Rust panic: every failure below is an expect()/panic!()
@@ -38,6 +41,7 @@ void usage()
             "  -o, --output <OUTPUT>          where the result will be stored\n"
             "  -u                             uncompress the input\n"
             "      --from <T0> --to <T1>      with -u: only the samples indexed at T0..=T1 (seconds since midnight)\n"
+            "      --step <S>                 with --from/--to: count,min,max,sum,first,last of every S seconds to .agg.csv\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -115,6 +119,49 @@ int uncompress_window(const Args &a, const std::string &output_base, uint8_t *br
     return 0;
 }
 
+// -u --from T0 --to T1 --step S: the time buckets [T0 + k S, min(T0 + (k + 1) S - 1, T1)] as sample windows of the index,
+// one atsc_window_stats row each (timestamp = the bucket's start) into <out>.agg.csv; nothing else is written
+std::string debug_f64(double v)  // Rust `{:?}` of an f64: shortest round-trip digits, ".0" appended to integers
+{
+    if (std::isnan(v)) return "NaN";
+    if (std::isinf(v)) return v < 0 ? "-inf" : "inf";
+    char buf[64];
+    auto r = std::to_chars(buf, buf + sizeof(buf), v);
+    std::string s(buf, r.ptr);
+    if (s.find('e') == std::string::npos && s.find('.') == std::string::npos) s += ".0";
+    return s;
+}
+int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *bro, uint64_t len)
+{
+    atsc_vsri *index = nullptr;
+    int rc = atsc_vsri_load(with_ext(a.input, "vsri").c_str(), &index);
+    if (rc) { atsc_free(bro); return die("failed to read vsri", rc); }
+    uint64_t nb = 0;
+    rc = atsc_vsri_step_windows(index, a.t0, a.t1, a.step, nullptr, nullptr, 0, &nb);
+    std::vector<uint64_t> b(nb ? nb : 1), c(nb ? nb : 1);
+    if (rc == ATSC_E_CAPACITY || rc == ATSC_OK) rc = atsc_vsri_step_windows(index, a.t0, a.t1, a.step, b.data(), c.data(), nb, &nb);
+    atsc_vsri_free(index);
+    if (rc) { atsc_free(bro); return die("vsri buckets", rc); }
+    std::vector<atsc_window_stats> st(nb ? nb : 1);
+    atsc_ctx *ctx = nullptr;
+    rc = atsc_ctx_create(&ctx, 0);
+    if (rc) { atsc_free(bro); return die("no GPU context", rc); }
+    rc = atsc_bro_open(bro, len, nullptr, nullptr);
+    if (!rc) rc = atsc_aggregate_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), st.data());
+    if (rc) { int e = die("aggregate", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    atsc_ctx_destroy(ctx);
+    atsc_free(bro);
+    FILE *f = fopen(with_ext(output_base, "agg.csv").c_str(), "w");
+    if (!f) return die("failed to write aggregates to file");
+    fprintf(f, "timestamp,count,min,max,sum,first,last\n");
+    for (uint64_t k = 0; k < nb; ++k)
+        fprintf(f, "%lld,%llu,%s,%s,%s,%s,%s\n", (long long)a.t0 + (long long)k * a.step, (unsigned long long)st[k].count,
+                debug_f64(st[k].min).c_str(), debug_f64(st[k].max).c_str(), debug_f64(st[k].sum).c_str(),
+                debug_f64(st[k].first).c_str(), debug_f64(st[k].last).c_str());
+    if (fclose(f) != 0) return die("failed to write aggregates to file");
+    return 0;
+}
+
 int uncompress(const Args &a, const std::string &output_base)  // main.rs:139-173
 {
     uint8_t *bro = nullptr;
@@ -122,6 +169,7 @@ int uncompress(const Args &a, const std::string &output_base)  // main.rs:139-17
     int rc = atsc_bro_read_file(a.input.c_str(), &bro, &len);
     if (rc) return die("failed to read bro file", rc);
     if (!bro) return 0;  // not a BRO file: nothing happens
+    if (a.step) return uncompress_buckets(a, output_base, bro, len);
     if (a.window) return uncompress_window(a, output_base, bro, len);
     atsc_ctx *ctx = nullptr;
     rc = atsc_ctx_create(&ctx, 0);
@@ -225,6 +273,15 @@ int main(int argc, char **argv)
             (from ? a.t0 : a.t1) = (int32_t)t;
             (from ? have_from : have_to) = true;
         }
+        else if (value("--step")) {
+            char *end = nullptr;
+            const long long t = strtoll(v.c_str(), &end, 10);
+            if (v.empty() || *end || t < 1 || t > INT32_MAX) {
+                fprintf(stderr, "error: invalid value '%s' for '--step': expected 1..=%d\n", v.c_str(), INT32_MAX);
+                return 2;
+            }
+            a.step = (int32_t)t;
+        }
         else if (value("--compressor")) { if (!parse_compressor(v, a.compressor)) { fprintf(stderr, "error: invalid value '%s' for '--compressor'\n", v.c_str()); return 2; } }
         else if (value("--error") || value("-e")) { if (!parse_int(v, 0, 50, a.error)) { fprintf(stderr, "error: invalid value '%s' for '--error': not in 0..=50\n", v.c_str()); return 2; } }
         else if (value("--compression-selection-sample-level") || value("-c")) { if (!parse_int(v, 0, 6, a.level)) { fprintf(stderr, "error: invalid value '%s' for '-c': not in 0..=6\n", v.c_str()); return 2; } }
@@ -234,6 +291,10 @@ int main(int argc, char **argv)
     if (a.input.empty()) { usage(); return 2; }
     if (have_from != have_to || ((have_from || have_to) && !a.uncompress)) {
         fprintf(stderr, "error: '--from' and '--to' go together, with '-u'\n");
+        return 2;
+    }
+    if (a.step && !have_from) {
+        fprintf(stderr, "error: '--step' needs '--from' and '--to'\n");
         return 2;
     }
     a.window = have_from;

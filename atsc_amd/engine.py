@@ -13,6 +13,29 @@ def _u64(arr):
     return a, a.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
+# atsc_window_stats (include/atsc_hip.h): the summary record of one window, 48 bytes
+WINDOW_STATS = np.dtype([("count", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sum", "<f8"), ("first", "<f8"),
+                         ("last", "<f8")])
+
+
+def _windows(begins, counts):
+    b, pb = _u64(np.atleast_1d(begins))
+    c, pc = _u64(np.atleast_1d(counts))
+    if len(b) != len(c):
+        raise ValueError("begins and counts differ in length")
+    return b, pb, c, pc
+
+
+def bucket_windows(begin, count, bucket):
+    """-> (begins, counts): [begin, begin + count) cut into windows of `bucket` samples, the last one shorter"""
+    begin, count, bucket = int(begin), int(count), int(bucket)
+    if bucket < 1:
+        raise ValueError("bucket must be >= 1")
+    b = np.arange(begin, begin + count, bucket, dtype=np.uint64)
+    c = np.minimum(np.uint64(bucket), np.uint64(begin + count) - b).astype(np.uint64)
+    return b, c
+
+
 class Context:
     """One atsc_ctx (one per host thread / per GPU rank)."""
 
@@ -109,6 +132,21 @@ class Context:
             out.ctypes.data_as(C.POINTER(C.c_double)), int(count), C.byref(on))
         capi.check(rc, self._h)
         return out[: on.value]
+
+    def aggregate_windows_host(self, records, begins, counts, has_count=False):
+        """-> WINDOW_STATS array: count / min / max / sum / first / last of every window [begins[i], begins[i] +
+        counts[i]) of the decoded records (atsc_aggregate_windows)"""
+        b = np.frombuffer(bytes(records), dtype=np.uint8)
+        wb, pb, wc, pc = _windows(begins, counts)
+        out = np.zeros(max(len(wb), 1), dtype=WINDOW_STATS)
+        rc = capi.lib().atsc_aggregate_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
+                                               len(wb), pb, pc, C.c_void_p(out.ctypes.data))
+        capi.check(rc, self._h)
+        return out[: len(wb)]
+
+    def set_aggregate_scratch(self, nbytes):
+        """Upper bound on the decoded-sample scratch of the aggregate calls (0: the default; raised to one piece)"""
+        capi.check(capi.lib().atsc_ctx_set_aggregate_scratch(self._h, int(nbytes)), self._h)
 
     # ---- device-resident path --------------------------------------------------------------
     def plan(self, frame_off):
@@ -222,6 +260,15 @@ class DPlan:
         rc = capi.lib().atsc_decompress_windows_dev(
             self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc, po, C.c_void_p(d_out.data_ptr()),
             C.c_void_p(stream))
+        capi.check(rc, self.ctx._h)
+
+    def aggregate_windows(self, d_body, begins, counts, d_stats, stream=0):
+        """Enqueues the summaries of the windows [begins[i], begins[i] + counts[i]) into d_stats, a device tensor of at
+        least 48 bytes per window (atsc_aggregate_windows_dev; WINDOW_STATS records)"""
+        b, pb, c, pc = _windows(begins, counts)
+        assert d_stats.is_contiguous() and d_stats.numel() * d_stats.element_size() >= 48 * len(b)
+        rc = capi.lib().atsc_aggregate_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
+                                                   C.c_void_p(d_stats.data_ptr()), C.c_void_p(stream))
         capi.check(rc, self.ctx._h)
 
 

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from .engine import WINDOW_STATS, _windows
 
 
 def _f64(x):
@@ -90,6 +91,14 @@ class CompressedStream:
                    self.ctx._h)
         return _take_f64(p, n)
 
+    def aggregate_windows(self, begins, counts):
+        """-> WINDOW_STATS array of the windows [begins[i], begins[i] + counts[i]) (atsc_stream_aggregate_windows)"""
+        wb, pb, wc, pc = _windows(begins, counts)
+        out = np.zeros(max(len(wb), 1), dtype=WINDOW_STATS)
+        capi.check(capi.lib().atsc_stream_aggregate_windows(self._h, len(wb), pb, pc, C.c_void_p(out.ctypes.data)),
+                   self.ctx._h)
+        return out[: len(wb)]
+
 
 def compress_data(ctx, vec, compressor=capi.AUTO, error=3, sample_level=0):
     """atsc/src/main.rs:130-165"""
@@ -124,6 +133,20 @@ def decompress_data_window(ctx, bro, begin, count):
                                            out.ctypes.data_as(C.POINTER(C.c_double)), int(count), C.byref(on))
     capi.check(rc, ctx._h)
     return out[: on.value]
+
+
+def aggregate_data_windows(ctx, bro, begins, counts):
+    """-> WINDOW_STATS array of windows of decompress_data(ctx, bro): atsc_bro_open, then atsc_aggregate_windows over
+    the records"""
+    b = np.frombuffer(bytes(bro), dtype=np.uint8)
+    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
+    wb, pb, wc, pc = _windows(begins, counts)
+    out = np.zeros(max(len(wb), 1), dtype=WINDOW_STATS)
+    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
+    rc = capi.lib().atsc_aggregate_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
+                                           C.c_void_p(out.ctypes.data))
+    capi.check(rc, ctx._h)
+    return out[: len(wb)]
 
 
 def wbro_from_bytes(data):

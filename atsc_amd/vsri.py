@@ -98,6 +98,20 @@ class Vsri:
         capi.check(capi.lib().atsc_vsri_sample_window(self._h, int(t0), int(t1), C.byref(b), C.byref(c)))
         return b.value, c.value
 
+    def step_windows(self, t0, t1, step):
+        """-> (begins, counts): the time buckets [t0 + k step, min(t0 + (k + 1) step - 1, t1)] as sample windows
+        (atsc_vsri_step_windows)"""
+        n = C.c_uint64()
+        rc = capi.lib().atsc_vsri_step_windows(self._h, int(t0), int(t1), int(step), None, None, 0, C.byref(n))
+        if rc != capi.E_CAPACITY:
+            capi.check(rc)
+        b = np.zeros(max(n.value, 1), dtype=np.uint64)
+        c = np.zeros(max(n.value, 1), dtype=np.uint64)
+        p = C.POINTER(C.c_uint64)
+        capi.check(capi.lib().atsc_vsri_step_windows(self._h, int(t0), int(t1), int(step), b.ctypes.data_as(p),
+                                                     c.ctypes.data_as(p), n.value, C.byref(n)))
+        return b[: n.value], c[: n.value]
+
     def get_all_timestamps(self):
         p = C.POINTER(C.c_int32)()
         n = C.c_uint64()

@@ -280,6 +280,47 @@ int atsc_decompress_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8
 int atsc_decompress_window(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t begin,
                            uint64_t count, double *out, uint64_t out_cap, uint64_t *out_n);
 
+/* Windowed aggregates: one summary record per window [begin, begin + count) of the decoded stream (the indices of
+ * atsc_decompress_frames), from the same decoded samples as the window decode, without handing the samples out.
+ *   count       samples of the window that are not NaN
+ *   min, max    over those samples (compared as values; a zero extreme comes back with a fixed sign); NaN when count == 0
+ *   sum         over those samples in the order below; +0.0 when count == 0
+ *   first, last the window's first and last decoded samples as they are (NaN included); NaN for an empty window
+ * The order of `sum` depends only on the stream's samples and the window's (begin, count):
+ *   1. tiles of 2048 samples at multiples of 2048 in the stream index; a slot outside the window or holding NaN
+ *      contributes -0.0, IEEE's exact additive identity;
+ *   2. in a tile x[0..2047]: for v = 0..255, p_t = x[512 t + 2 v] + x[512 t + 2 v + 1] (t = 0..3) and
+ *      s[v] = (p_0 + p_1) + (p_2 + p_3); then s[v] = s[v] + s[v + h] for v < h, h = 128, 64, 32, 16, 8, 4, 2, 1: s[0];
+ *   3. the window's tile partials q[0..P-1] in tile order: q[i] = q[2 i] + q[2 i + 1] level by level (an odd last
+ *      entry is added to -0.0) until one is left.
+ * |sum - exact| <= (ceil(log2 count) + 2) 2^-53 sum|x| for finite data; with +-Inf the result is IEEE's (+Inf, -Inf, or
+ * NaN when both occur).  Validation is the window decode's: a window beyond the stream gives ATSC_E_INVALID with nothing
+ * written; payloads are checked only of the frames a window touches.  Windows may overlap and come in any order;
+ * count == 0 and n_windows == 0 are valid. */
+typedef struct {
+    uint64_t count;
+    double min, max;
+    double sum;
+    double first, last;
+} atsc_window_stats; /* 48 bytes */
+/* d_stats[i] summarises window i.  begin / count are HOST arrays; d_body and d_stats are device memory (d_stats 8-byte
+ * aligned).  Enqueued on `stream`, not synchronised.  Decoded samples go through device scratch of at most the
+ * context's aggregate budget (raised to one piece's minimum, 65536 samples plus two large frames' room), whatever the
+ * windows' total length; a frame cut by a piece boundary is decoded once per piece.  A malformed payload inside a
+ * window sets the plan's status word.  The plan keeps the call's tables, partials and scratch: the next aggregate call
+ * on the same plan waits (host side) until this one's work is done. */
+int atsc_aggregate_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                               const uint64_t *begin, const uint64_t *count, atsc_window_stats *d_stats, void *stream);
+/* Host bytes in, host records out, synchronous.  Walks the record headers only up to the last window's end and uploads
+ * only the touched records' byte range, as atsc_decompress_window does.  ATSC_E_FORMAT (nothing written) for a
+ * malformed payload inside a window. */
+int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                           const uint64_t *begin, const uint64_t *count, atsc_window_stats *out);
+/* Upper bound in bytes on the decoded-sample scratch the aggregate calls hold; 0 (the default) gives pieces of 16 Mi
+ * samples (128 MiB, plus 2 MiB of room for two large frames cut by a piece's ends where a frame longer than 4096 samples
+ * is touched).  A budget below what one piece needs is raised to that minimum, never an error. */
+int atsc_ctx_set_aggregate_scratch(atsc_ctx *ctx, uint64_t bytes);
+
 /* ------------------------------------------------------------------------ */
 /* CompressedStream mirror (atsc/src/data.rs:29-110)                          */
 /* ------------------------------------------------------------------------ */
@@ -304,6 +345,9 @@ int atsc_stream_to_bytes(atsc_stream *s, uint8_t **out, uint64_t *len);
 int atsc_stream_decompress(atsc_stream *s, double **out, uint64_t *n);
 /* atsc_stream_decompress of the samples [begin, begin + count) only (atsc_decompress_window); release with atsc_free */
 int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uint64_t count, double **out, uint64_t *n);
+/* atsc_aggregate_windows over the stream's frames */
+int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                  atsc_window_stats *out);
 void atsc_free(void *p);
 
 /* compress_data / decompress_data of the atsc CLI (atsc/src/main.rs:130-172): clean (drop NaN/Inf),
@@ -384,6 +428,12 @@ int atsc_vsri_get_all_timestamps(const atsc_vsri *v, int32_t **out, uint64_t *n)
  * samples whose time falls outside [t0, t1] (an off-grid time looks up the sample in front of it).  *count = 0 when
  * no sample falls inside.  ATSC_E_INVALID where a look-up panics in the reference. */
 int atsc_vsri_sample_window(const atsc_vsri *v, int32_t t0, int32_t t1, uint64_t *begin, uint64_t *count);
+/* Time buckets [t0 + k*step, min(t0 + (k+1)*step - 1, t1)], k = 0.., as sample windows: atsc_vsri_sample_window of
+ * each bucket (an empty bucket gives count 0).  Host only.  *n = number of buckets (0 when t1 < t0); ATSC_E_CAPACITY
+ * when cap < *n (nothing written); ATSC_E_INVALID for step < 1, or where a look-up panics in the reference.
+ * t0 + k*step is computed without int32 overflow. */
+int atsc_vsri_step_windows(const atsc_vsri *v, int32_t t0, int32_t t1, int32_t step, uint64_t *begin,
+                           uint64_t *count, uint64_t cap, uint64_t *n);
 /* vsri::day_elapsed_seconds (lib.rs:49-57); ATSC_E_INVALID outside chrono's DateTime range */
 int atsc_day_elapsed_seconds(int64_t timestamp_sec, int32_t *out);
 /* csv-compressor/src/csv.rs:41-56: `timestamp,value` files (i64, f64; csv crate reader / writer,
