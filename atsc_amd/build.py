@@ -9,8 +9,8 @@ CSRC = os.path.join(HERE, "csrc")
 # (objects under build_<name>/), loaded by atsc_amd.capi when ATSC_LIB_VARIANT=<name> (tools/stamp_probe.py)
 VARIANT = os.environ.get("ATSC_BUILD_VARIANT", "")
 LIB = os.path.join(HERE, "libatsc_hip%s.so" % ("_" + VARIANT if VARIANT else ""))
-SOURCES = ["atsc_kernels.hip", "atsc_large.hip", "atsc_decode.hip", "atsc_aggregate.hip", "atsc_host.cpp",
-           "atsc_stream.cpp", "atsc_vsri.cpp"]
+SOURCES = ["atsc_kernels.hip", "atsc_large.hip", "atsc_decode.hip", "atsc_aggregate.hip", "atsc_quantile.hip",
+           "atsc_host.cpp", "atsc_stream.cpp", "atsc_vsri.cpp"]
 CLI = os.path.join(HERE, "bin", "atsc")
 CLI_SRC = "atsc_cli.cpp"
 CLI2 = os.path.join(HERE, "bin", "csv-compressor")

@@ -1,12 +1,14 @@
 // atsc -- command line front end over libatsc_hip.so with the reference's flags and file naming
 // (atsc/src/main.rs:29-127,176-243).  Every frame is compressed / decompressed on the GPU.
 //
-//   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N]]
+//   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
+//        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <cctype>
 #include <charconv>
 #include <cmath>
 #include <cstdio>
@@ -30,6 +32,10 @@ struct Args {
     bool window = false;                // --samples BEGIN:COUNT (with -u): decode only that window
     uint64_t win_begin = 0, win_count = 0;
     uint64_t buckets = 0;               // --buckets N (with -u): summaries of N-sample buckets into <file>.agg.csv
+    std::vector<double> levels;         // --quantiles (with --buckets): one more .agg.csv column per level
+    std::vector<std::string> level_names;
+    int method = ATSC_QUANTILE_LINEAR;  // --quantile-method
+    bool have_method = false;
 };
 
 void usage()
@@ -41,6 +47,8 @@ void usage()
             "  -u                             uncompress the input file/directory\n"
             "      --samples <BEGIN:COUNT>    with -u: write only the samples [BEGIN, BEGIN+COUNT) to the .wbro\n"
             "      --buckets <N>              with -u: write count,min,max,sum,first,last of every N samples to .agg.csv\n"
+            "      --quantiles <Q,Q,..>       with --buckets: also the levels Q (0..1, at most 64) of every bucket\n"
+            "      --quantile-method <M>      linear | lower | higher | nearest [default: linear]\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -98,6 +106,32 @@ std::string with_ext(const std::string &path, const char *ext)  // PathBuf::set_
     return base + "." + ext;
 }
 
+// --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
+bool parse_levels(const std::string &v, std::vector<double> &q, std::vector<std::string> &names)
+{
+    q.clear();
+    names.clear();
+    for (size_t p = 0;;) {
+        const size_t c = v.find(',', p);
+        const std::string t = v.substr(p, c == std::string::npos ? std::string::npos : c - p);
+        char *e = nullptr;
+        const double x = strtod(t.c_str(), &e);
+        if (t.empty() || isspace((unsigned char)t[0]) || *e || !(x >= 0.0 && x <= 1.0)) return false;
+        q.push_back(x);
+        names.push_back(t);
+        if (c == std::string::npos) return true;
+        p = c + 1;
+    }
+}
+
+bool parse_method(const std::string &v, int &m)
+{
+    static const char *names[] = {"linear", "lower", "higher", "nearest"};  // ATSC_QUANTILE_* order
+    for (int k = 0; k < 4; ++k)
+        if (v == names[k]) { m = k; return true; }
+    return false;
+}
+
 // -u --buckets N: one atsc_window_stats row per bucket of N samples of [begin, begin + count), the last bucket shorter
 int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const uint8_t *bro, uint64_t len, uint64_t begin,
                   uint64_t count)
@@ -112,13 +146,23 @@ int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const u
     // the records from the frame-count varint on, as atsc_decompress_data reads them
     int rc = atsc_aggregate_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), st.data());
     if (rc) return rc;
+    const uint64_t nq = a.levels.size();
+    std::vector<double> qv(nb * nq ? nb * nq : 1);
+    if (nq) rc = atsc_quantile_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), (uint32_t)nq, a.levels.data(), a.method,
+                                       qv.data());
+    if (rc) return rc;
     FILE *f = fopen(with_ext(path, "agg.csv").c_str(), "w");
     if (!f) return ATSC_E_IO;
-    fprintf(f, "begin,count,min,max,sum,first,last\n");
-    for (uint64_t k = 0; k < nb; ++k)
-        fprintf(f, "%llu,%llu,%s,%s,%s,%s,%s\n", (unsigned long long)b[k], (unsigned long long)st[k].count,
+    fprintf(f, "begin,count,min,max,sum,first,last");
+    for (const std::string &n : a.level_names) fprintf(f, ",q%s", n.c_str());
+    fprintf(f, "\n");
+    for (uint64_t k = 0; k < nb; ++k) {
+        fprintf(f, "%llu,%llu,%s,%s,%s,%s,%s", (unsigned long long)b[k], (unsigned long long)st[k].count,
                 debug_f64(st[k].min).c_str(), debug_f64(st[k].max).c_str(), debug_f64(st[k].sum).c_str(),
                 debug_f64(st[k].first).c_str(), debug_f64(st[k].last).c_str());
+        for (uint64_t j = 0; j < nq; ++j) fprintf(f, ",%s", debug_f64(qv[k * nq + j]).c_str());
+        fprintf(f, "\n");
+    }
     return fclose(f) == 0 ? ATSC_OK : ATSC_E_IO;
 }
 
@@ -260,12 +304,33 @@ int main(int argc, char **argv)
                 return 2;
             }
         }
+        else if (value("--quantiles")) {
+            if (!parse_levels(v, a.levels, a.level_names)) {
+                fprintf(stderr, "error: invalid value '%s' for '--quantiles': expected levels in 0..=1, comma separated\n",
+                        v.c_str());
+                return 2;
+            }
+            if (a.levels.size() > 64) {
+                fprintf(stderr, "error: invalid value for '--quantiles': %zu levels, at most 64\n", a.levels.size());
+                return 2;
+            }
+        }
+        else if (value("--quantile-method")) {
+            if (!parse_method(v, a.method)) {
+                fprintf(stderr, "error: invalid value '%s' for '--quantile-method': linear, lower, higher or nearest\n",
+                        v.c_str());
+                return 2;
+            }
+            a.have_method = true;
+        }
         else if (!s.empty() && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); usage(); return 2; }
         else a.input = s;
     }
     if (a.input.empty()) { usage(); return 2; }
     if (a.window && !a.uncompress) { fprintf(stderr, "error: '--samples' needs '-u'\n"); return 2; }
     if (a.buckets && !a.uncompress) { fprintf(stderr, "error: '--buckets' needs '-u'\n"); return 2; }
+    if (!a.levels.empty() && !a.buckets) { fprintf(stderr, "error: '--quantiles' needs '--buckets'\n"); return 2; }
+    if (a.have_method && a.levels.empty()) { fprintf(stderr, "error: '--quantile-method' needs '--quantiles'\n"); return 2; }
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) { fprintf(stderr, "[ERROR] %s: No such file or directory\n", a.input.c_str()); return 1; }
     atsc_ctx *ctx = nullptr;

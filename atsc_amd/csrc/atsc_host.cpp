@@ -63,6 +63,17 @@ __attribute__((weak)) hipError_t launch_agg_tiles(const DevAggTile *tasks, uint3
                                                   DevAggPart *part, double *fl, hipStream_t s);
 __attribute__((weak)) hipError_t launch_agg_combine(const DevAggComb *tasks, uint32_t n, DevAggPart *part,
                                                     const double *fl, void *stats, hipStream_t s);
+// the windowed quantiles' selection kernels (atsc_quantile.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_qnt_short(const DevQTask *tasks, uint32_t n, const double *scratch, const double *q,
+                                                  uint32_t n_q, int method, double *out, hipStream_t s);
+__attribute__((weak)) hipError_t launch_qnt_medium(const DevQTask *tasks, uint32_t n, uint32_t P, const double *scratch,
+                                                   const double *q, uint32_t n_q, int method, double *out, hipStream_t s);
+__attribute__((weak)) hipError_t launch_qnt_hist(const DevQChunk *chunks, uint32_t n, const double *scratch,
+                                                 const DevQState *st, uint32_t *hist, uint32_t rows, uint32_t pass,
+                                                 hipStream_t s);
+__attribute__((weak)) hipError_t launch_qnt_pick(const DevQTask *tasks, uint32_t n, DevQState *st, uint32_t *hist,
+                                                 uint32_t rows, uint32_t pass, const double *q, uint32_t n_q, int method,
+                                                 double *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -240,6 +251,14 @@ struct atsc_dplan {
     mutable uint64_t agg_scratch_cap = 0;
     mutable hipEvent_t ev_agg = nullptr;
     mutable bool agg_pending = false;
+    // the same for the last atsc_quantile_windows_dev call: tables (staging; device copy followed by the long tier's
+    // state and counts), decoded-sample scratch, end of work
+    mutable unsigned char *h_qnt = nullptr, *d_qnt = nullptr;
+    mutable size_t qnt_hcap = 0, qnt_dcap = 0;
+    mutable double *d_qnt_scratch = nullptr;
+    mutable uint64_t qnt_scratch_cap = 0;
+    mutable hipEvent_t ev_qnt = nullptr;
+    mutable bool qnt_pending = false;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1850,6 +1869,10 @@ extern "C" void atsc_dplan_destroy(atsc_dplan *p)
     pool_free(p->ctx, p->d_agg);
     pool_free(p->ctx, p->d_agg_scratch);
     if (p->ev_agg) (void)hipEventDestroy(p->ev_agg);
+    if (p->h_qnt) (void)hipHostFree(p->h_qnt);
+    pool_free(p->ctx, p->d_qnt);
+    pool_free(p->ctx, p->d_qnt_scratch);
+    if (p->ev_qnt) (void)hipEventDestroy(p->ev_qnt);
     pool_free(p->ctx, p->d_frames);
     pool_free(p->ctx, p->d_ids);
     pool_free(p->ctx, p->d_status);
@@ -2700,6 +2723,160 @@ static void agg_empty_record(atsc_window_stats &r)
     r.sum = 0.0;
 }
 
+// ---- decoded samples of window pieces in scratch (the aggregate and the quantile calls) ----
+using Span = std::pair<uint64_t, uint64_t>;
+
+// the decode tasks of all pieces of one call, and their place in the call's upload
+struct DecodeTasks {
+    std::vector<DevWTask> small[CLASS_LARGE];
+    std::vector<DevDFrame> big;
+    std::vector<DevWGather> gat;
+    uint32_t max_big = 0, spills_used = 0;
+    size_t off_small[CLASS_LARGE] = {}, off_big = 0, off_ids = 0, off_gat = 0;
+};
+// one piece's run of them
+struct PieceDecode {
+    size_t small_at[CLASS_LARGE], big_at, gat_at;
+    uint32_t small_n[CLASS_LARGE], big_n, gat_n, max_len;
+};
+
+static size_t upload_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// the decoded samples a call's scratch may hold: the context's budget, else the default piece and room for two large
+// frames cut by its ends
+static uint64_t scratch_budget_samples(const atsc_ctx *ctx, bool large)
+{
+    return ctx->agg_budget ? ctx->agg_budget / sizeof(double)
+                           : (large ? AGG_PIECE_LARGE + 2ull * MAX_FRAME : AGG_PIECE_SMALL);
+}
+
+// whether the covering intervals (stream index; org: the plan's first sample) touch a large frame
+static bool spans_touch_large(const atsc_dplan *dp, uint64_t org, const std::vector<Span> &cov)
+{
+    for (const Span &c : cov) {
+        uint64_t fb, fe;
+        (void)atsc_dplan_find_frames(dp, c.first - org, c.second - c.first, &fb, &fe);
+        for (uint64_t f = fb; f < fe; ++f)
+            if (dp->h_cls[f] == CLASS_LARGE) return true;
+    }
+    return false;
+}
+
+// The decode tasks of the piece [S0, S1) into scratch[0, S1 - S0): per touched frame, the hull of its covered samples
+// inside the piece.  cov: ascending disjoint covering intervals, *ci the first that may still meet the piece (advanced
+// past those that end before it).  A large frame is decoded whole: in place when it lies inside the piece, else into
+// one of two spill slots behind the region (scratch[region + MAX_FRAME k]) and copied from there (k_window_gather).
+// false: more than two spill slots (only the frames across S0 and S1 can stick out).
+static bool emit_piece_decode(const atsc_dplan *dp, uint64_t org, const std::vector<Span> &cov, size_t &ci, uint64_t S0,
+                              uint64_t S1, uint64_t region, DecodeTasks &D, PieceDecode &pt)
+{
+    const auto &F = dp->h_frames;
+    for (int c = 0; c < CLASS_LARGE; ++c) pt.small_at[c] = D.small[c].size();
+    pt.big_at = D.big.size();
+    pt.gat_at = D.gat.size();
+    pt.max_len = 0;
+    uint32_t n_spill = 0;
+    auto emit = [&](uint64_t f, uint64_t lo, uint64_t hi) {
+        const uint64_t fo = org + F[f].out_off, fn = F[f].n;
+        const int c = dp->h_cls[f];
+        if (c != CLASS_LARGE) {
+            D.small[c].push_back(DevWTask{fo + lo - S0, (uint32_t)f, (uint32_t)lo, (uint32_t)hi, 0});
+            return;
+        }
+        DevDFrame d = F[f];
+        if (fo >= S0 && fo + fn <= S1) {
+            d.out_off = fo - S0;
+        } else {
+            const uint64_t sp = region + (uint64_t)MAX_FRAME * n_spill++;
+            d.out_off = sp;
+            D.gat.push_back(DevWGather{sp + lo, fo + lo - S0, (uint32_t)(hi - lo), 0});
+            pt.max_len = std::max(pt.max_len, (uint32_t)(hi - lo));
+        }
+        D.big.push_back(d);
+    };
+    while (ci < cov.size() && cov[ci].second <= S0) ++ci;
+    uint64_t hf = ~0ull, hlo = 0, hhi = 0;
+    for (size_t c = ci; c < cov.size() && cov[c].first < S1; ++c) {
+        const uint64_t a = std::max(cov[c].first, S0), z = std::min(cov[c].second, S1);
+        uint64_t fb, fe;
+        (void)atsc_dplan_find_frames(dp, a - org, z - a, &fb, &fe);
+        for (uint64_t f = fb; f < fe; ++f) {
+            const uint64_t fo = org + F[f].out_off, fn = F[f].n;
+            const uint64_t lo = std::max(a, fo) - fo, hi = std::min(z, fo + fn) - fo;
+            if (f == hf) { hhi = hi; continue; }
+            if (hf != ~0ull) emit(hf, hlo, hhi);
+            hf = f;
+            hlo = lo;
+            hhi = hi;
+        }
+    }
+    if (hf != ~0ull) emit(hf, hlo, hhi);
+    if (n_spill > 2) return false;
+    D.spills_used = std::max(D.spills_used, n_spill);
+    for (int c = 0; c < CLASS_LARGE; ++c) pt.small_n[c] = (uint32_t)(D.small[c].size() - pt.small_at[c]);
+    pt.big_n = (uint32_t)(D.big.size() - pt.big_at);
+    pt.gat_n = (uint32_t)(D.gat.size() - pt.gat_at);
+    D.max_big = std::max(D.max_big, pt.big_n);
+    return true;
+}
+
+// places the decode tasks at the front of an upload (per class the pieces' task lists, the large sub-plans, ids 0..,
+// copies); returns the upload's size so far
+static size_t place_decode_tasks(DecodeTasks &D)
+{
+    size_t bytes = 0;
+    for (int c = 0; c < CLASS_LARGE; ++c) {
+        D.off_small[c] = bytes;
+        bytes = upload_align(bytes + D.small[c].size() * sizeof(DevWTask));
+    }
+    D.off_big = bytes;
+    bytes = upload_align(bytes + D.big.size() * sizeof(DevDFrame));
+    D.off_ids = bytes;
+    bytes = upload_align(bytes + D.max_big * sizeof(uint32_t));
+    D.off_gat = bytes;
+    return upload_align(bytes + D.gat.size() * sizeof(DevWGather));
+}
+
+static void stage_decode_tasks(const DecodeTasks &D, unsigned char *h)
+{
+    for (int c = 0; c < CLASS_LARGE; ++c)
+        if (!D.small[c].empty()) memcpy(h + D.off_small[c], D.small[c].data(), D.small[c].size() * sizeof(DevWTask));
+    if (!D.big.empty()) memcpy(h + D.off_big, D.big.data(), D.big.size() * sizeof(DevDFrame));
+    for (uint32_t i = 0; i < D.max_big; ++i) ((uint32_t *)(h + D.off_ids))[i] = i;
+    if (!D.gat.empty()) memcpy(h + D.off_gat, D.gat.data(), D.gat.size() * sizeof(DevWGather));
+}
+
+// enqueues one piece's decode into scr (d: the device copy of the upload)
+static int launch_piece_decode(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, const unsigned char *d,
+                               const DecodeTasks &D, const PieceDecode &pt, double *scr, hipStream_t s, bool quantile)
+{
+    for (int c = 0; c < CLASS_LARGE; ++c) {
+        if (!pt.small_n[c]) continue;
+        const hipError_t e = launch_decompress_window(dp->d_frames, (const DevWTask *)(d + D.off_small[c]) + pt.small_at[c], c,
+                                                      pt.small_n[c], dp->class_lds[c], dp->tabs.d_plans, dp->tabs.d_tw,
+                                                      d_body, scr, dp->d_status, s);
+        if (e != hipSuccess)
+            return fail(ctx, ATSC_E_HIP, quantile ? "launch k_decompress (quantile)" : "launch k_decompress (aggregate)", e);
+    }
+    if (pt.big_n) {
+        const hipError_t e = launch_decompress_large(
+            pt.big_n, (const DevDFrame *)(d + D.off_big) + pt.big_at, (const uint32_t *)(d + D.off_ids), dp->tabs.d_plans,
+            dp->tabs.d_tw, d_body, scr, dp->d_status, dp->d_ws, dp->ws_stride, dp->ws_slots, dp->large_tiled ? 1 : 0,
+            large_sparse() ? 1 : 0, s, dp->large_pre.tiles1 ? &dp->large_pre : nullptr,
+            dp->large_choice_count <= LARGE_SPLIT_MAX ? dp->large_sp_tiles : 0);
+        if (e != hipSuccess)
+            return fail(ctx, ATSC_E_HIP,
+                        quantile ? "launch k_decompress_large (quantile)" : "launch k_decompress_large (aggregate)", e);
+    }
+    if (pt.gat_n) {
+        const hipError_t e = launch_window_gather((const DevWGather *)(d + D.off_gat) + pt.gat_at, pt.gat_n, pt.max_len, scr,
+                                                  scr, s);
+        if (e != hipSuccess)
+            return fail(ctx, ATSC_E_HIP, quantile ? "launch k_window_gather (quantile)" : "launch k_window_gather (aggregate)", e);
+    }
+    return ATSC_OK;
+}
+
 // The device call.  Host work: covering intervals, pieces, the decode tasks of every piece (one per touched frame: its
 // covered samples' hull in the piece), the tile tasks (a full tile that windows cover past their first tile and before
 // their last one is reduced once, into a shared partial; every window's first and last tile are reduced for it alone)
@@ -2723,9 +2900,8 @@ static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const uint64_t T = AGG_TILE, W = n_windows;
-    const auto &F = dp->h_frames;
     // covering intervals: the union of the non-empty windows
-    std::vector<std::pair<uint64_t, uint64_t>> cov;
+    std::vector<Span> cov;
     for (uint64_t i = 0; i < W; ++i)
         if (count[i]) cov.emplace_back(org + begin[i], org + begin[i] + count[i]);
     std::sort(cov.begin(), cov.end());
@@ -2737,15 +2913,10 @@ static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
         }
         cov.resize(m);
     }
-    bool large = false;
-    for (size_t c = 0; c < cov.size() && !large; ++c) {
-        uint64_t fb, fe;
-        (void)atsc_dplan_find_frames(dp, cov[c].first - org, cov[c].second - cov[c].first, &fb, &fe);
-        for (uint64_t f = fb; f < fe && !large; ++f) large = dp->h_cls[f] == CLASS_LARGE;
-    }
+    const bool large = spans_touch_large(dp, org, cov);
     // piece length: the budget less room for two large frames that cross the piece's ends
     const uint64_t spill = large ? 2ull * MAX_FRAME : 0;
-    const uint64_t want = ctx->agg_budget ? ctx->agg_budget / sizeof(double) : (large ? AGG_PIECE_LARGE : AGG_PIECE_SMALL) + spill;
+    const uint64_t want = scratch_budget_samples(ctx, large);
     const uint64_t piece_tiles = std::max<uint64_t>(AGG_MIN_PIECE, want > spill ? (want - spill) / T * T : 0) / T;
     struct Piece {
         uint64_t k0, k1;  // tiles [k0, k1): samples [k0 T, k1 T) at scratch[0, (k1 - k0) T)
@@ -2836,77 +3007,24 @@ static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
             live.swap(next);
         }
     }
-    // decode tasks of every piece: per touched frame, the hull of its covered samples inside the piece.  A large frame
-    // is decoded whole: in place when it lies inside the piece's tiles, else into one of two spill slots behind the
-    // region and copied from there (k_window_gather).
-    struct PieceTab {
-        size_t small_at[CLASS_LARGE], big_at, gat_at, tile_at;
-        uint32_t small_n[CLASS_LARGE], big_n, gat_n, tile_n, max_len;
-    };
-    std::vector<PieceTab> ptab(pcs.size());
-    std::vector<DevWTask> small[CLASS_LARGE];
-    std::vector<DevDFrame> big;
-    std::vector<DevWGather> gat;
+    // decode tasks of every piece (emit_piece_decode) and its tile tasks
+    std::vector<PieceDecode> pdec(pcs.size());
+    std::vector<size_t> tile_at(pcs.size());
+    std::vector<uint32_t> tile_n(pcs.size());
+    DecodeTasks D;
     std::vector<DevAggTile> tiles;
     tiles.reserve(tt.size());
-    uint32_t max_big = 0, spills_used = 0;
     size_t ci = 0, ti = 0;
     for (size_t p = 0; p < pcs.size(); ++p) {
-        PieceTab &pt = ptab[p];
-        const uint64_t S0 = pcs[p].k0 * T, S1 = pcs[p].k1 * T;
-        for (int c = 0; c < CLASS_LARGE; ++c) pt.small_at[c] = small[c].size();
-        pt.big_at = big.size();
-        pt.gat_at = gat.size();
-        pt.tile_at = tiles.size();
-        pt.max_len = 0;
-        uint32_t n_spill = 0;
-        auto emit = [&](uint64_t f, uint64_t lo, uint64_t hi) {
-            const uint64_t fo = org + F[f].out_off, fn = F[f].n;
-            const int c = dp->h_cls[f];
-            if (c != CLASS_LARGE) {
-                small[c].push_back(DevWTask{fo + lo - S0, (uint32_t)f, (uint32_t)lo, (uint32_t)hi, 0});
-                return;
-            }
-            DevDFrame d = F[f];
-            if (fo >= S0 && fo + fn <= S1) {
-                d.out_off = fo - S0;
-            } else {
-                const uint64_t sp = region + (uint64_t)MAX_FRAME * n_spill++;
-                d.out_off = sp;
-                gat.push_back(DevWGather{sp + lo, fo + lo - S0, (uint32_t)(hi - lo), 0});
-                pt.max_len = std::max(pt.max_len, (uint32_t)(hi - lo));
-            }
-            big.push_back(d);
-        };
-        while (ci < cov.size() && cov[ci].second <= S0) ++ci;
-        uint64_t hf = ~0ull, hlo = 0, hhi = 0;
-        for (size_t c = ci; c < cov.size() && cov[c].first < S1; ++c) {
-            const uint64_t a = std::max(cov[c].first, S0), z = std::min(cov[c].second, S1);
-            uint64_t fb, fe;
-            (void)atsc_dplan_find_frames(dp, a - org, z - a, &fb, &fe);
-            for (uint64_t f = fb; f < fe; ++f) {
-                const uint64_t fo = org + F[f].out_off, fn = F[f].n;
-                const uint64_t lo = std::max(a, fo) - fo, hi = std::min(z, fo + fn) - fo;
-                if (f == hf) { hhi = hi; continue; }
-                if (hf != ~0ull) emit(hf, hlo, hhi);
-                hf = f;
-                hlo = lo;
-                hhi = hi;
-            }
-        }
-        if (hf != ~0ull) emit(hf, hlo, hhi);
-        if (n_spill > 2) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (spill slots)");
-        spills_used = std::max(spills_used, n_spill);
+        tile_at[p] = tiles.size();
+        if (!emit_piece_decode(dp, org, cov, ci, pcs[p].k0 * T, pcs[p].k1 * T, region, D, pdec[p]))
+            return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (spill slots)");
         for (; ti < tt.size() && tt[ti].k < pcs[p].k1; ++ti) {
             DevAggTile t = tt[ti].t;
             t.src = (tt[ti].k - pcs[p].k0) * T;
             tiles.push_back(t);
         }
-        for (int c = 0; c < CLASS_LARGE; ++c) pt.small_n[c] = (uint32_t)(small[c].size() - pt.small_at[c]);
-        pt.big_n = (uint32_t)(big.size() - pt.big_at);
-        pt.gat_n = (uint32_t)(gat.size() - pt.gat_at);
-        pt.tile_n = (uint32_t)(tiles.size() - pt.tile_at);
-        max_big = std::max(max_big, pt.big_n);
+        tile_n[p] = (uint32_t)(tiles.size() - tile_at[p]);
     }
     if (ti != tt.size()) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (tile outside the pieces)");
     // the previous call's tables, partials and scratch are reused once its work is done
@@ -2914,17 +3032,10 @@ static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
         HIPCHK(ctx, hipEventSynchronize(dp->ev_agg));
         dp->agg_pending = false;
     }
-    // one upload: per class the pieces' task lists, the large sub-plans, ids 0.., copies, tile tasks, combine tasks;
-    // behind them (device only) the partials and the windows' first / last samples
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t off_small[CLASS_LARGE], bytes = 0;
-    for (int c = 0; c < CLASS_LARGE; ++c) { off_small[c] = bytes; bytes = al(bytes + small[c].size() * sizeof(DevWTask)); }
-    const size_t off_big = bytes;
-    bytes = al(bytes + big.size() * sizeof(DevDFrame));
-    const size_t off_ids = bytes;
-    bytes = al(bytes + max_big * sizeof(uint32_t));
-    const size_t off_gat = bytes;
-    bytes = al(bytes + gat.size() * sizeof(DevWGather));
+    // one upload: the decode tasks (place_decode_tasks), tile tasks, combine tasks; behind them (device only) the
+    // partials and the windows' first / last samples
+    auto al = upload_align;
+    size_t bytes = place_decode_tasks(D);
     const size_t off_tiles = bytes;
     bytes = al(bytes + tiles.size() * sizeof(DevAggTile));
     const size_t off_comb = bytes;
@@ -2948,7 +3059,7 @@ static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
         HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_agg, bytes));
         dp->agg_dcap = bytes;
     }
-    const uint64_t scr_need = region + (uint64_t)MAX_FRAME * spills_used;
+    const uint64_t scr_need = region + (uint64_t)MAX_FRAME * D.spills_used;
     if (scr_need > dp->agg_scratch_cap) {
         pool_free(ctx, dp->d_agg_scratch);
         dp->d_agg_scratch = nullptr;
@@ -2958,11 +3069,7 @@ static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
     }
     if (!dp->ev_agg) HIPCHK(ctx, hipEventCreateWithFlags(&dp->ev_agg, hipEventDisableTiming));
     unsigned char *h = dp->h_agg, *d = dp->d_agg;
-    for (int c = 0; c < CLASS_LARGE; ++c)
-        if (!small[c].empty()) memcpy(h + off_small[c], small[c].data(), small[c].size() * sizeof(DevWTask));
-    if (!big.empty()) memcpy(h + off_big, big.data(), big.size() * sizeof(DevDFrame));
-    for (uint32_t i = 0; i < max_big; ++i) ((uint32_t *)(h + off_ids))[i] = i;
-    if (!gat.empty()) memcpy(h + off_gat, gat.data(), gat.size() * sizeof(DevWGather));
+    stage_decode_tasks(D, h);
     if (!tiles.empty()) memcpy(h + off_tiles, tiles.data(), tiles.size() * sizeof(DevAggTile));
     memcpy(h + off_comb, comb.data(), comb.size() * sizeof(DevAggComb));
     HIPCHK(ctx, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, s));
@@ -2970,28 +3077,9 @@ static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
     DevAggPart *part = (DevAggPart *)(d + off_part);
     double *fl = (double *)(d + off_fl);
     for (size_t p = 0; p < pcs.size(); ++p) {
-        const PieceTab &pt = ptab[p];
-        for (int c = 0; c < CLASS_LARGE; ++c) {
-            if (!pt.small_n[c]) continue;
-            const hipError_t e = launch_decompress_window(dp->d_frames, (const DevWTask *)(d + off_small[c]) + pt.small_at[c], c,
-                                                          pt.small_n[c], dp->class_lds[c], dp->tabs.d_plans, dp->tabs.d_tw,
-                                                          d_body, scr, dp->d_status, s);
-            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_decompress (aggregate)", e);
-        }
-        if (pt.big_n) {
-            const hipError_t e = launch_decompress_large(
-                pt.big_n, (const DevDFrame *)(d + off_big) + pt.big_at, (const uint32_t *)(d + off_ids), dp->tabs.d_plans,
-                dp->tabs.d_tw, d_body, scr, dp->d_status, dp->d_ws, dp->ws_stride, dp->ws_slots, dp->large_tiled ? 1 : 0,
-                large_sparse() ? 1 : 0, s, dp->large_pre.tiles1 ? &dp->large_pre : nullptr,
-                dp->large_choice_count <= LARGE_SPLIT_MAX ? dp->large_sp_tiles : 0);
-            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_decompress_large (aggregate)", e);
-        }
-        if (pt.gat_n) {
-            const hipError_t e = launch_window_gather((const DevWGather *)(d + off_gat) + pt.gat_at, pt.gat_n, pt.max_len, scr,
-                                                      scr, s);
-            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_window_gather (aggregate)", e);
-        }
-        const hipError_t e = launch_agg_tiles((const DevAggTile *)(d + off_tiles) + pt.tile_at, pt.tile_n, scr, part, fl, s);
+        const int rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, s, false);
+        if (rc) return rc;
+        const hipError_t e = launch_agg_tiles((const DevAggTile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, fl, s);
         if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_agg_tiles", e);
     }
     for (size_t q = 0; q + 1 < pass_at.size(); ++q) {
@@ -3081,6 +3169,330 @@ done:
     if (rc) (void)hipStreamSynchronize(ws);
     pool_free(ctx, d_body);
     pool_free(ctx, d_stats);
+    atsc_dplan_destroy(dp);
+    return rc;
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
+// windowed quantiles: exact order statistics of sample windows (atsc_quantile.hip)
+// ------------------------------------------------------------------------------------------
+static int quantile_check_levels(atsc_ctx *ctx, uint32_t n_q, const double *q, int method)
+{
+    if (!q) return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
+    if (n_q == 0 || n_q > QNT_MAX_LEVELS) return fail(ctx, ATSC_E_INVALID, "quantile_windows: n_q outside [1, 64]");
+    for (uint32_t j = 0; j < n_q; ++j)
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(ctx, ATSC_E_INVALID, "quantile_windows: a level is NaN or outside [0, 1]");
+    if (method < ATSC_QUANTILE_LINEAR || method > ATSC_QUANTILE_NEAREST)
+        return fail(ctx, ATSC_E_INVALID, "quantile_windows: unknown method");
+    return ATSC_OK;
+}
+
+// The device call.  Every window is held whole in scratch: the windows, by begin, go into pieces of at most L samples
+// (a piece starts at the first window not yet placed and takes every unplaced window that ends within L of that
+// start; pieces overlap where windows do).  Per piece: the decode tasks of its windows' union (emit_piece_decode), then
+// the tiers by window length: short and medium windows one launch each (medium: one per power-of-two key count), long
+// windows QNT_PASSES histogram + pick launches whatever their number.  Everything goes up in one copy; nothing waits
+// on the host between pieces.  org: the stream index of the plan's first sample (see aggregate_dev).
+static int quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                        const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
+                        double *d_out, void *stream, uint64_t org)
+{
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_out)))
+        return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
+    int rc = quantile_check_levels(ctx, n_q, q, method);
+    if (rc) return rc;
+    if ((uintptr_t)d_out & 7u) return fail(ctx, ATSC_E_INVALID, "quantile_windows: d_out is not 8-byte aligned");
+    const uint64_t ns = dp->n_samples;
+    for (uint64_t i = 0; i < n_windows; ++i)
+        if (begin[i] > ns || count[i] > ns - begin[i]) return fail(ctx, ATSC_E_INVALID, "quantile_windows: window beyond the stream");
+    if (n_windows == 0) return ATSC_OK;
+    if (n_windows >= 0xffffffffull) return fail(ctx, ATSC_E_INVALID, "quantile_windows: more than 2^32 - 2 windows");
+    if (!launch_decompress_window || !launch_window_gather || !launch_qnt_short || !launch_qnt_medium || !launch_qnt_hist ||
+        !launch_qnt_pick)
+        return fail(ctx, ATSC_E_UNSUPPORTED, "quantile_windows: no quantile kernels");
+    const uint64_t W = n_windows;
+    std::vector<uint32_t> ord;  // the non-empty windows by begin
+    std::vector<Span> cov;
+    for (uint64_t i = 0; i < W; ++i)
+        if (count[i]) { ord.push_back((uint32_t)i); cov.emplace_back(org + begin[i], org + begin[i] + count[i]); }
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return begin[a] < begin[b]; });
+    std::sort(cov.begin(), cov.end());
+    // piece length: the budget less room for two large frames that cross the piece's ends
+    const bool large = spans_touch_large(dp, org, cov);
+    const uint64_t spill = large ? 2ull * MAX_FRAME : 0;
+    const uint64_t want = scratch_budget_samples(ctx, large);
+    const uint64_t L = std::max<uint64_t>(AGG_MIN_PIECE, want > spill ? want - spill : 0);
+    for (uint32_t i : ord) {
+        if (count[i] <= L && count[i] < (1ull << 32)) continue;
+        char msg[192];
+        if (count[i] >= (1ull << 32))
+            snprintf(msg, sizeof msg, "quantile_windows: window %u holds %llu samples, more than 2^32 - 1", i,
+                     (unsigned long long)count[i]);
+        else
+            snprintf(msg, sizeof msg,
+                     "quantile_windows: window %u (%llu samples) does not fit one scratch piece; an aggregate scratch "
+                     "budget of %llu bytes would hold it", i, (unsigned long long)count[i],
+                     (unsigned long long)((count[i] + spill) * sizeof(double)));
+        return fail(ctx, ATSC_E_CAPACITY, msg);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // pieces: windows ord[w_at, w_at + w_n) of pw, samples [S0, S1) of the stream at scratch[0, S1 - S0)
+    struct Piece {
+        uint64_t S0, S1;
+        size_t w_at, w_n;
+    };
+    std::vector<Piece> pcs;
+    std::vector<uint32_t> pw;
+    pw.reserve(ord.size());
+    {
+        std::vector<char> placed(ord.size(), 0);
+        size_t a = 0;
+        while (a < ord.size()) {
+            Piece pc{org + begin[ord[a]], 0, pw.size(), 0};
+            pc.S1 = pc.S0;
+            for (size_t k = a; k < ord.size() && org + begin[ord[k]] < pc.S0 + L; ++k) {
+                const uint64_t e = org + begin[ord[k]] + count[ord[k]];
+                if (placed[k] || e > pc.S0 + L) continue;
+                placed[k] = 1;
+                pw.push_back(ord[k]);
+                pc.S1 = std::max(pc.S1, e);
+            }
+            pc.w_n = pw.size() - pc.w_at;
+            pcs.push_back(pc);
+            while (a < ord.size() && placed[a]) ++a;
+        }
+    }
+    uint64_t region = 0;
+    for (const Piece &pc : pcs) region = std::max(region, pc.S1 - pc.S0);
+    // per piece: decode tasks, then the windows by tier
+    const uint32_t n_med = 6;  // medium key counts 2^9 .. 2^14 (the ones up to QNT_MEDIUM_MAX are used)
+    struct PieceQ {
+        size_t short_at, med_at[n_med], long_at, chunk_at;
+        uint32_t short_n, med_n[n_med], long_n, chunk_n;
+    };
+    std::vector<PieceDecode> pdec(pcs.size());
+    std::vector<PieceQ> pq(pcs.size());
+    DecodeTasks D;
+    std::vector<DevQTask> shorts, meds, longs;
+    std::vector<DevQTask> med_class[n_med];
+    std::vector<DevQChunk> chunks;
+    uint32_t max_long = 0;
+    for (size_t p = 0; p < pcs.size(); ++p) {
+        const Piece &pc = pcs[p];
+        std::vector<Span> pcov;
+        for (size_t k = pc.w_at; k < pc.w_at + pc.w_n; ++k) {
+            const uint64_t b = org + begin[pw[k]], e = b + count[pw[k]];
+            if (!pcov.empty() && b <= pcov.back().second) pcov.back().second = std::max(pcov.back().second, e);
+            else pcov.emplace_back(b, e);
+        }
+        size_t ci = 0;
+        if (!emit_piece_decode(dp, org, pcov, ci, pc.S0, pc.S1, region, D, pdec[p]))
+            return fail(ctx, ATSC_E_INVALID, "quantile_windows: internal error (spill slots)");
+        PieceQ &t = pq[p];
+        t.short_at = shorts.size();
+        t.long_at = longs.size();
+        t.chunk_at = chunks.size();
+        for (uint32_t c = 0; c < n_med; ++c) med_class[c].clear();
+        for (size_t k = pc.w_at; k < pc.w_at + pc.w_n; ++k) {
+            const uint32_t i = pw[k];
+            const uint64_t src = org + begin[i] - pc.S0, n = count[i];
+            if (n <= QNT_SHORT_MAX) {
+                shorts.push_back(DevQTask{src, n, i, 0});
+            } else if (n <= QNT_MEDIUM_MAX) {
+                uint32_t c = 0;
+                while ((512ull << c) < n) ++c;
+                med_class[c].push_back(DevQTask{src, n, i, 0});
+            } else {
+                const uint32_t slot = (uint32_t)(longs.size() - t.long_at);
+                longs.push_back(DevQTask{src, n, i, slot});
+                for (uint64_t o = 0; o < n; o += QNT_CHUNK)
+                    chunks.push_back(DevQChunk{src + o, (uint32_t)std::min<uint64_t>(QNT_CHUNK, n - o), slot});
+            }
+        }
+        for (uint32_t c = 0; c < n_med; ++c) {
+            t.med_at[c] = meds.size();
+            t.med_n[c] = (uint32_t)med_class[c].size();
+            meds.insert(meds.end(), med_class[c].begin(), med_class[c].end());
+        }
+        t.short_n = (uint32_t)(shorts.size() - t.short_at);
+        t.long_n = (uint32_t)(longs.size() - t.long_at);
+        t.chunk_n = (uint32_t)(chunks.size() - t.chunk_at);
+        max_long = std::max(max_long, t.long_n);
+    }
+    // empty windows: NaN from the short tier, once
+    const size_t empty_at = shorts.size();
+    for (uint64_t i = 0; i < W; ++i)
+        if (!count[i]) shorts.push_back(DevQTask{0, 0, (uint32_t)i, 0});
+    const uint32_t empty_n = (uint32_t)(shorts.size() - empty_at);
+    // the previous call's tables and scratch are reused once its work is done
+    if (dp->qnt_pending) {
+        HIPCHK(ctx, hipEventSynchronize(dp->ev_qnt));
+        dp->qnt_pending = false;
+    }
+    // one upload: the decode tasks, the levels, the tiers' task lists, the chunks; behind them (device only) the long
+    // tier's state and counts
+    const uint32_t rows = 2 * n_q;
+    size_t bytes = place_decode_tasks(D);
+    const size_t off_q = bytes;
+    bytes = upload_align(bytes + n_q * sizeof(double));
+    const size_t off_short = bytes;
+    bytes = upload_align(bytes + shorts.size() * sizeof(DevQTask));
+    const size_t off_med = bytes;
+    bytes = upload_align(bytes + meds.size() * sizeof(DevQTask));
+    const size_t off_long = bytes;
+    bytes = upload_align(bytes + longs.size() * sizeof(DevQTask));
+    const size_t off_chunk = bytes;
+    bytes = upload_align(bytes + chunks.size() * sizeof(DevQChunk));
+    const size_t up_bytes = bytes, off_state = bytes;
+    bytes = upload_align(bytes + (size_t)max_long * sizeof(DevQState));
+    const size_t off_hist = bytes, hist_bytes = (size_t)max_long * rows * 256 * sizeof(uint32_t);
+    bytes = upload_align(bytes + hist_bytes);
+    if (up_bytes > dp->qnt_hcap) {
+        if (dp->h_qnt) (void)hipHostFree(dp->h_qnt);
+        dp->h_qnt = nullptr;
+        dp->qnt_hcap = 0;
+        const size_t cap = std::max<size_t>(up_bytes, 64u << 10);
+        HIPCHK(ctx, hipHostMalloc((void **)&dp->h_qnt, cap, hipHostMallocDefault));
+        dp->qnt_hcap = cap;
+    }
+    if (bytes > dp->qnt_dcap) {
+        pool_free(ctx, dp->d_qnt);
+        dp->d_qnt = nullptr;
+        dp->qnt_dcap = 0;
+        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_qnt, bytes));
+        dp->qnt_dcap = bytes;
+    }
+    const uint64_t scr_need = std::max<uint64_t>(1, region + (uint64_t)MAX_FRAME * D.spills_used);
+    if (scr_need > dp->qnt_scratch_cap) {
+        pool_free(ctx, dp->d_qnt_scratch);
+        dp->d_qnt_scratch = nullptr;
+        dp->qnt_scratch_cap = 0;
+        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_qnt_scratch, scr_need * sizeof(double)));
+        dp->qnt_scratch_cap = scr_need;
+    }
+    if (!dp->ev_qnt) HIPCHK(ctx, hipEventCreateWithFlags(&dp->ev_qnt, hipEventDisableTiming));
+    unsigned char *h = dp->h_qnt, *d = dp->d_qnt;
+    stage_decode_tasks(D, h);
+    memcpy(h + off_q, q, n_q * sizeof(double));
+    if (!shorts.empty()) memcpy(h + off_short, shorts.data(), shorts.size() * sizeof(DevQTask));
+    if (!meds.empty()) memcpy(h + off_med, meds.data(), meds.size() * sizeof(DevQTask));
+    if (!longs.empty()) memcpy(h + off_long, longs.data(), longs.size() * sizeof(DevQTask));
+    if (!chunks.empty()) memcpy(h + off_chunk, chunks.data(), chunks.size() * sizeof(DevQChunk));
+    HIPCHK(ctx, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, s));
+    if (hist_bytes) HIPCHK(ctx, hipMemsetAsync(d + off_hist, 0, hist_bytes, s));  // k_qnt_pick clears what it reads
+    double *scr = dp->d_qnt_scratch;
+    const double *dq = (const double *)(d + off_q);
+    const DevQTask *d_short = (const DevQTask *)(d + off_short), *d_med = (const DevQTask *)(d + off_med),
+                   *d_long = (const DevQTask *)(d + off_long);
+    const DevQChunk *d_chunk = (const DevQChunk *)(d + off_chunk);
+    DevQState *st = (DevQState *)(d + off_state);
+    uint32_t *hist = (uint32_t *)(d + off_hist);
+    hipError_t e = launch_qnt_short(d_short + empty_at, empty_n, scr, dq, n_q, method, d_out, s);
+    if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_short", e);
+    for (size_t p = 0; p < pcs.size(); ++p) {
+        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, s, true);
+        if (rc) return rc;
+        const PieceQ &t = pq[p];
+        e = launch_qnt_short(d_short + t.short_at, t.short_n, scr, dq, n_q, method, d_out, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_short", e);
+        for (uint32_t c = 0; c < n_med; ++c) {
+            e = launch_qnt_medium(d_med + t.med_at[c], t.med_n[c], 512u << c, scr, dq, n_q, method, d_out, s);
+            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_medium", e);
+        }
+        if (!t.long_n) continue;
+        for (uint32_t pass = 0; pass < QNT_PASSES; ++pass) {
+            e = launch_qnt_hist(d_chunk + t.chunk_at, t.chunk_n, scr, st, hist, rows, pass, s);
+            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_hist", e);
+            e = launch_qnt_pick(d_long + t.long_at, t.long_n, st, hist, rows, pass, dq, n_q, method, d_out, s);
+            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_pick", e);
+        }
+    }
+    HIPCHK(ctx, hipEventRecord(dp->ev_qnt, s));
+    dp->qnt_pending = true;
+    return ATSC_OK;
+}
+extern "C" int atsc_quantile_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                         const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q,
+                                         int method, double *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    return quantile_dev(ctx, dp, d_body, n_windows, begin, count, n_q, q, method, d_out, stream, 0);
+    ATSC_API_END
+}
+
+// Host call: atsc_aggregate_windows' path (the touched records only) into quantile_dev.
+extern "C" int atsc_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                     const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
+                                     double *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
+    int rc = quantile_check_levels(ctx, n_q, q, method);
+    if (rc) return rc;
+    if (n_windows == 0) return ATSC_OK;
+    uint64_t pos = 0, max_frames = ~0ull;
+    if (has_count) {
+        if (!host_varint(body, body_len, pos, max_frames)) return fail(ctx, ATSC_E_FORMAT, "quantile_windows: frame count");
+        if (max_frames > body_len / 4) return fail(ctx, ATSC_E_FORMAT, "quantile_windows: frame count exceeds the bytes present");
+    }
+    uint64_t B = ~0ull, E = 0;
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        if (begin[i] + count[i] < begin[i]) return fail(ctx, ATSC_E_INVALID, "quantile_windows: window beyond the stream");
+        E = std::max(E, begin[i] + count[i]);
+        if (count[i]) B = std::min(B, begin[i]);
+    }
+    const bool any = B != ~0ull;
+    if (!any) B = E;  // only empty windows: the walk checks that each begins inside the stream
+    WindowWalk w;
+    rc = window_walk(body, body_len, pos, max_frames, B, E - B, true, w);
+    if (rc) return fail(ctx, rc, rc == ATSC_E_INVALID ? "quantile_windows: window beyond the stream" : "quantile_windows: record walk");
+    if (!any) {
+        for (uint64_t i = 0; i < n_windows * n_q; ++i) out[i] = std::numeric_limits<double>::quiet_NaN();
+        return ATSC_OK;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->work_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->work_stream, hipStreamNonBlocking));
+    hipStream_t ws = ctx->work_stream;
+    const uint64_t slice = w.byte_end - w.byte_begin;
+    atsc_dplan *dp = nullptr;
+    rc = dplan_create_range(ctx, body + w.byte_begin, slice, 0, 0, ~0ull, nullptr, &dp);
+    if (rc) return rc;
+    if (dp->class_count[CLASS_LARGE]) {
+        // the large tier's launch forms from every large frame of the stream, as in atsc_decompress_window
+        DPlanHost Hw;
+        const char *why;
+        rc = dplan_parse(body, body_len, has_count, Hw, &why);
+        if (rc) { atsc_dplan_destroy(dp); return fail(ctx, rc, why); }
+        large_choices(dp, Hw.tabs.plans, Hw.frames, Hw.cls);
+    }
+    std::vector<uint64_t> b2(n_windows);
+    for (uint64_t i = 0; i < n_windows; ++i) b2[i] = count[i] ? begin[i] - w.sample_begin : 0;
+    uint8_t *d_body = nullptr;
+    double *d_out = nullptr;
+    int status = 0;
+    hipError_t e = hipSuccess;
+#define QCHK(call)                                                                 \
+    do {                                                                           \
+        e = (call);                                                                \
+        if (e != hipSuccess) { rc = fail(ctx, ATSC_E_HIP, #call, e); goto done; } \
+    } while (0)
+    QCHK(pool_alloc(ctx, (void **)&d_body, std::max<uint64_t>(slice, 16)));
+    QCHK(pool_alloc(ctx, (void **)&d_out, n_windows * n_q * sizeof(double)));
+    QCHK(hipMemcpyAsync(d_body, body + w.byte_begin, slice, hipMemcpyHostToDevice, ws));
+    rc = quantile_dev(ctx, dp, d_body, n_windows, b2.data(), count, n_q, q, method, d_out, ws, w.sample_begin);
+    if (rc) goto done;
+    QCHK(hipMemcpyAsync(&status, dp->d_status, sizeof(int), hipMemcpyDeviceToHost, ws));
+    QCHK(hipStreamSynchronize(ws));
+    if (status) { rc = fail(ctx, ATSC_E_FORMAT, "quantile_windows: malformed payload"); goto done; }
+    QCHK(hipMemcpyAsync(out, d_out, n_windows * n_q * sizeof(double), hipMemcpyDeviceToHost, ws));
+    QCHK(hipStreamSynchronize(ws));
+#undef QCHK
+done:
+    if (rc) (void)hipStreamSynchronize(ws);
+    pool_free(ctx, d_body);
+    pool_free(ctx, d_out);
     atsc_dplan_destroy(dp);
     return rc;
     ATSC_API_END

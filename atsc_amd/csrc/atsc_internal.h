@@ -205,6 +205,34 @@ struct DevAggComb {
     uint32_t n, g, win, final_;
 };
 
+// windowed quantiles (atsc_quantile_windows_dev, atsc_quantile.hip).  The tier of a window is chosen from its length:
+// short (one wavefront, keys in registers), medium (one workgroup, keys in LDS), long (MSD radix select, 8-bit digits)
+constexpr uint32_t QNT_MAX_LEVELS = 64;
+constexpr uint32_t QNT_SLOTS = 2 * QNT_MAX_LEVELS;  // long tier: the ranks a window needs, two per level
+constexpr uint64_t QNT_SHORT_MAX = 256;
+constexpr uint64_t QNT_MEDIUM_MAX = 8192;
+constexpr uint32_t QNT_CHUNK = 16384;  // long tier: samples per histogram workgroup
+constexpr uint32_t QNT_PASSES = 8;
+// one window: samples scratch[src, src + n) -> out[win * n_q ..]; slot: its long-tier state
+struct DevQTask {
+    uint64_t src, n;
+    uint32_t win, slot;
+};
+// one histogram workgroup of the long tier: samples scratch[src, src + len) of the window in state `slot`
+struct DevQChunk {
+    uint64_t src;
+    uint32_t len, slot;
+};
+// the radix select's state of one long window: n non-NaN samples; rank slot r (2 j: level j's lower rank, 2 j + 1: its
+// upper one) is rank[r] among the samples whose key starts with prefix upre[ridx[r]]; upre[0, nu) ascending and distinct
+struct DevQState {
+    uint64_t n;
+    uint32_t nr, nu;
+    uint64_t rank[QNT_SLOTS];
+    uint64_t upre[QNT_SLOTS];
+    uint32_t ridx[QNT_SLOTS];
+};
+
 static inline uint32_t varint_len_u64(uint64_t v)
 {
     return v < 251 ? 1u : v < (1ull << 16) ? 3u : v < (1ull << 32) ? 5u : 9u;

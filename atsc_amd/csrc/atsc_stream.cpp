@@ -333,6 +333,28 @@ extern "C" int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows,
     ATSC_API_END
 }
 
+extern "C" int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                            uint32_t n_q, const double *q, int method, double *out)
+{
+    ATSC_API_BEGIN
+    if (!s || !q || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
+    if (n_q == 0 || n_q > 64 || method < ATSC_QUANTILE_LINEAR || method > ATSC_QUANTILE_NEAREST) return ATSC_E_INVALID;
+    for (uint32_t j = 0; j < n_q; ++j)
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return ATSC_E_INVALID;
+    int rc = flush(s);
+    if (rc) return rc;
+    std::vector<uint8_t> body;
+    for (const Item &it : s->items) body.insert(body.end(), it.record.begin(), it.record.end());
+    if (body.empty()) {  // no frame: only empty windows at 0
+        for (uint64_t i = 0; i < n_windows; ++i)
+            if (begin[i] != 0 || count[i] != 0) return ATSC_E_INVALID;
+        for (uint64_t i = 0; i < n_windows * n_q; ++i) out[i] = std::numeric_limits<double>::quiet_NaN();
+        return ATSC_OK;
+    }
+    return atsc_quantile_windows(s->ctx, body.data(), body.size(), 0, n_windows, begin, count, n_q, q, method, out);
+    ATSC_API_END
+}
+
 extern "C" int atsc_stream_decompress(atsc_stream *s, double **out, uint64_t *n)
 {
     ATSC_API_BEGIN

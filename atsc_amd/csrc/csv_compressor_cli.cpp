@@ -3,10 +3,12 @@
 // .bro (+ .vsri index, + .wavbro samples) out; `-u` turns .bro + .vsri back into .wbro + .csv.
 // Compression and decompression run on the GPU; the index and the text formats are host code.
 //
-//   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S]]] [--no-compression] [--output-vsri] [--output-wavbrro]
+//   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]]]]
+//                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
 
+#include <cctype>
 #include <charconv>
 #include <cmath>
 #include <cstdio>
@@ -29,6 +31,10 @@ struct Args {
     bool window = false;  // --from / --to (with -u): only the samples whose indexed times lie in [t0, t1]
     int32_t t0 = 0, t1 = 0;
     int32_t step = 0;  // --step S (with --from / --to): summaries of S-second buckets into <out>.agg.csv
+    std::vector<double> levels;  // --quantiles (with --step): one more .agg.csv column per level
+    std::vector<std::string> level_names;
+    int method = ATSC_QUANTILE_LINEAR;  // --quantile-method
+    bool have_method = false;
 };
 
 constexpr int PANIC = 101;  // exit status of a Rust panic: every failure below is an expect()/panic!()
@@ -42,6 +48,8 @@ void usage()
             "  -u                             uncompress the input\n"
             "      --from <T0> --to <T1>      with -u: only the samples indexed at T0..=T1 (seconds since midnight)\n"
             "      --step <S>                 with --from/--to: count,min,max,sum,first,last of every S seconds to .agg.csv\n"
+            "      --quantiles <Q,Q,..>       with --step: also the levels Q (0..1, at most 64) of every bucket\n"
+            "      --quantile-method <M>      linear | lower | higher | nearest [default: linear]\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -131,6 +139,30 @@ std::string debug_f64(double v)  // Rust `{:?}` of an f64: shortest round-trip d
     if (s.find('e') == std::string::npos && s.find('.') == std::string::npos) s += ".0";
     return s;
 }
+// --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
+bool parse_levels(const std::string &v, std::vector<double> &q, std::vector<std::string> &names)
+{
+    q.clear();
+    names.clear();
+    for (size_t p = 0;;) {
+        const size_t c = v.find(',', p);
+        const std::string t = v.substr(p, c == std::string::npos ? std::string::npos : c - p);
+        char *e = nullptr;
+        const double x = strtod(t.c_str(), &e);
+        if (t.empty() || isspace((unsigned char)t[0]) || *e || !(x >= 0.0 && x <= 1.0)) return false;
+        q.push_back(x);
+        names.push_back(t);
+        if (c == std::string::npos) return true;
+        p = c + 1;
+    }
+}
+bool parse_method(const std::string &v, int &m)
+{
+    static const char *names[] = {"linear", "lower", "higher", "nearest"};  // ATSC_QUANTILE_* order
+    for (int k = 0; k < 4; ++k)
+        if (v == names[k]) { m = k; return true; }
+    return false;
+}
 int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *bro, uint64_t len)
 {
     atsc_vsri *index = nullptr;
@@ -149,15 +181,25 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
     rc = atsc_bro_open(bro, len, nullptr, nullptr);
     if (!rc) rc = atsc_aggregate_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), st.data());
     if (rc) { int e = die("aggregate", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    const uint64_t nq = a.levels.size();
+    std::vector<double> qv(nb * nq ? nb * nq : 1);
+    if (nq) rc = atsc_quantile_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), (uint32_t)nq, a.levels.data(), a.method,
+                                       qv.data());
+    if (rc) { int e = die("quantiles", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
     atsc_ctx_destroy(ctx);
     atsc_free(bro);
     FILE *f = fopen(with_ext(output_base, "agg.csv").c_str(), "w");
     if (!f) return die("failed to write aggregates to file");
-    fprintf(f, "timestamp,count,min,max,sum,first,last\n");
-    for (uint64_t k = 0; k < nb; ++k)
-        fprintf(f, "%lld,%llu,%s,%s,%s,%s,%s\n", (long long)a.t0 + (long long)k * a.step, (unsigned long long)st[k].count,
+    fprintf(f, "timestamp,count,min,max,sum,first,last");
+    for (const std::string &n : a.level_names) fprintf(f, ",q%s", n.c_str());
+    fprintf(f, "\n");
+    for (uint64_t k = 0; k < nb; ++k) {
+        fprintf(f, "%lld,%llu,%s,%s,%s,%s,%s", (long long)a.t0 + (long long)k * a.step, (unsigned long long)st[k].count,
                 debug_f64(st[k].min).c_str(), debug_f64(st[k].max).c_str(), debug_f64(st[k].sum).c_str(),
                 debug_f64(st[k].first).c_str(), debug_f64(st[k].last).c_str());
+        for (uint64_t j = 0; j < nq; ++j) fprintf(f, ",%s", debug_f64(qv[k * nq + j]).c_str());
+        fprintf(f, "\n");
+    }
     if (fclose(f) != 0) return die("failed to write aggregates to file");
     return 0;
 }
@@ -282,6 +324,25 @@ int main(int argc, char **argv)
             }
             a.step = (int32_t)t;
         }
+        else if (value("--quantiles")) {
+            if (!parse_levels(v, a.levels, a.level_names)) {
+                fprintf(stderr, "error: invalid value '%s' for '--quantiles': expected levels in 0..=1, comma separated\n",
+                        v.c_str());
+                return 2;
+            }
+            if (a.levels.size() > 64) {
+                fprintf(stderr, "error: invalid value for '--quantiles': %zu levels, at most 64\n", a.levels.size());
+                return 2;
+            }
+        }
+        else if (value("--quantile-method")) {
+            if (!parse_method(v, a.method)) {
+                fprintf(stderr, "error: invalid value '%s' for '--quantile-method': linear, lower, higher or nearest\n",
+                        v.c_str());
+                return 2;
+            }
+            a.have_method = true;
+        }
         else if (value("--compressor")) { if (!parse_compressor(v, a.compressor)) { fprintf(stderr, "error: invalid value '%s' for '--compressor'\n", v.c_str()); return 2; } }
         else if (value("--error") || value("-e")) { if (!parse_int(v, 0, 50, a.error)) { fprintf(stderr, "error: invalid value '%s' for '--error': not in 0..=50\n", v.c_str()); return 2; } }
         else if (value("--compression-selection-sample-level") || value("-c")) { if (!parse_int(v, 0, 6, a.level)) { fprintf(stderr, "error: invalid value '%s' for '-c': not in 0..=6\n", v.c_str()); return 2; } }
@@ -295,6 +356,14 @@ int main(int argc, char **argv)
     }
     if (a.step && !have_from) {
         fprintf(stderr, "error: '--step' needs '--from' and '--to'\n");
+        return 2;
+    }
+    if (!a.levels.empty() && !a.step) {
+        fprintf(stderr, "error: '--quantiles' needs '--step'\n");
+        return 2;
+    }
+    if (a.have_method && a.levels.empty()) {
+        fprintf(stderr, "error: '--quantile-method' needs '--quantiles'\n");
         return 2;
     }
     a.window = have_from;

@@ -26,6 +26,11 @@ def _windows(begins, counts):
     return b, pb, c, pc
 
 
+def _levels(levels):
+    q = np.ascontiguousarray(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+    return q, q.ctypes.data_as(C.POINTER(C.c_double))
+
+
 def bucket_windows(begin, count, bucket):
     """-> (begins, counts): [begin, begin + count) cut into windows of `bucket` samples, the last one shorter"""
     begin, count, bucket = int(begin), int(count), int(bucket)
@@ -141,6 +146,19 @@ class Context:
         out = np.zeros(max(len(wb), 1), dtype=WINDOW_STATS)
         rc = capi.lib().atsc_aggregate_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
                                                len(wb), pb, pc, C.c_void_p(out.ctypes.data))
+        capi.check(rc, self._h)
+        return out[: len(wb)]
+
+    def quantile_windows_host(self, records, begins, counts, levels, method=capi.QUANTILE_LINEAR, has_count=False):
+        """-> (n_windows, n_levels) float64 array: the levels of every window [begins[i], begins[i] + counts[i]) of the
+        decoded records (atsc_quantile_windows)"""
+        b = np.frombuffer(bytes(records), dtype=np.uint8)
+        wb, pb, wc, pc = _windows(begins, counts)
+        q, pq = _levels(levels)
+        out = np.zeros((max(len(wb), 1), len(q)), dtype=np.float64)
+        rc = capi.lib().atsc_quantile_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
+                                              len(wb), pb, pc, len(q), pq, int(method),
+                                              out.ctypes.data_as(C.POINTER(C.c_double)))
         capi.check(rc, self._h)
         return out[: len(wb)]
 
@@ -269,6 +287,17 @@ class DPlan:
         assert d_stats.is_contiguous() and d_stats.numel() * d_stats.element_size() >= 48 * len(b)
         rc = capi.lib().atsc_aggregate_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
                                                    C.c_void_p(d_stats.data_ptr()), C.c_void_p(stream))
+        capi.check(rc, self.ctx._h)
+
+    def quantile_windows(self, d_body, begins, counts, levels, d_out, method=capi.QUANTILE_LINEAR, stream=0):
+        """Enqueues the levels of the windows [begins[i], begins[i] + counts[i]) into d_out, a float64 device tensor of
+        at least n_windows * n_levels elements, window-major (atsc_quantile_windows_dev)"""
+        b, pb, c, pc = _windows(begins, counts)
+        q, pq = _levels(levels)
+        assert d_out.is_contiguous() and d_out.element_size() == 8 and d_out.numel() >= len(b) * len(q)
+        rc = capi.lib().atsc_quantile_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
+                                                  len(q), pq, int(method), C.c_void_p(d_out.data_ptr()),
+                                                  C.c_void_p(stream))
         capi.check(rc, self.ctx._h)
 
 

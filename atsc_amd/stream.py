@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .engine import WINDOW_STATS, _windows
+from .engine import WINDOW_STATS, _levels, _windows
 
 
 def _f64(x):
@@ -99,6 +99,15 @@ class CompressedStream:
                    self.ctx._h)
         return out[: len(wb)]
 
+    def quantile_windows(self, begins, counts, levels, method=capi.QUANTILE_LINEAR):
+        """-> (n_windows, n_levels) float64 array of the windows' levels (atsc_stream_quantile_windows)"""
+        wb, pb, wc, pc = _windows(begins, counts)
+        q, pq = _levels(levels)
+        out = np.zeros((max(len(wb), 1), len(q)), dtype=np.float64)
+        capi.check(capi.lib().atsc_stream_quantile_windows(self._h, len(wb), pb, pc, len(q), pq, int(method),
+                                                           out.ctypes.data_as(C.POINTER(C.c_double))), self.ctx._h)
+        return out[: len(wb)]
+
 
 def compress_data(ctx, vec, compressor=capi.AUTO, error=3, sample_level=0):
     """atsc/src/main.rs:130-165"""
@@ -145,6 +154,21 @@ def aggregate_data_windows(ctx, bro, begins, counts):
     r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
     rc = capi.lib().atsc_aggregate_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
                                            C.c_void_p(out.ctypes.data))
+    capi.check(rc, ctx._h)
+    return out[: len(wb)]
+
+
+def quantile_data_windows(ctx, bro, begins, counts, levels, method=capi.QUANTILE_LINEAR):
+    """-> (n_windows, n_levels) float64 array: levels of windows of decompress_data(ctx, bro): atsc_bro_open, then
+    atsc_quantile_windows over the records"""
+    b = np.frombuffer(bytes(bro), dtype=np.uint8)
+    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
+    wb, pb, wc, pc = _windows(begins, counts)
+    q, pq = _levels(levels)
+    out = np.zeros((max(len(wb), 1), len(q)), dtype=np.float64)
+    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
+    rc = capi.lib().atsc_quantile_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
+                                          len(q), pq, int(method), out.ctypes.data_as(C.POINTER(C.c_double)))
     capi.check(rc, ctx._h)
     return out[: len(wb)]
 

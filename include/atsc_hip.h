@@ -318,8 +318,41 @@ int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len
                            const uint64_t *begin, const uint64_t *count, atsc_window_stats *out);
 /* Upper bound in bytes on the decoded-sample scratch the aggregate calls hold; 0 (the default) gives pieces of 16 Mi
  * samples (128 MiB, plus 2 MiB of room for two large frames cut by a piece's ends where a frame longer than 4096 samples
- * is touched).  A budget below what one piece needs is raised to that minimum, never an error. */
+ * is touched).  A budget below what one piece needs is raised to that minimum, never an error.  It bounds the quantile
+ * calls below too, whose windows must each fit one piece. */
 int atsc_ctx_set_aggregate_scratch(atsc_ctx *ctx, uint64_t bytes);
+
+/* Windowed quantiles: exact order statistics of windows [begin, begin + count) of the decoded stream (the indices of
+ * atsc_decompress_frames), from the same decoded samples as the window decode.  For window i:
+ *   x  the window's non-NaN samples, n of them, sorted in IEEE total order (-0.0 before +0.0), i.e. by the keys
+ *      bits(v) ^ (sign(v) ? 0xFFFFFFFFFFFFFFFF : 0x8000000000000000);
+ *   v = (double)(n - 1) * q[j] (one f64 multiply); out[i * n_q + j] by the method:
+ *     LOWER x[floor(v)]; HIGHER x[ceil(v)]; NEAREST x[rint(v)] (ties to even, as numpy.around);
+ *     LINEAR (NumPy's default method) lo = floor(v), hi = min(lo + 1, n - 1), t = v - lo: x[lo] when t == 0 or
+ *       lo == hi, else with d = x[hi] - x[lo]: t >= 0.5 ? x[hi] - d * (1 - t) : x[lo] + d * t (NumPy's _lerp, no fused
+ *       multiply-add);
+ *   n == 0 (an empty or all-NaN window): NaN for every level.
+ * The result depends only on the window's samples, not on the other windows, the other levels, the budget or the
+ * device.  It equals numpy.nanquantile as a value on finite data; where NumPy's interpolation meets Inf - Inf and gives
+ * NaN, the rule above gives the Inf (np.quantile([1, inf], 1.0) is NaN, here +Inf).
+ * Validation (ATSC_E_INVALID, nothing written): a null argument, a window beyond the stream, n_q == 0 or n_q > 64, a
+ * level that is NaN or outside [0, 1], an unknown method.  n_windows == 0 is valid; windows may overlap and come in any
+ * order.  Every window is held whole in the decoded-sample scratch that atsc_ctx_set_aggregate_scratch bounds: a window
+ * longer than one piece of that budget gives ATSC_E_CAPACITY with nothing written, and atsc_ctx_last_error names the
+ * budget that would hold it. */
+enum { ATSC_QUANTILE_LINEAR = 0, ATSC_QUANTILE_LOWER = 1, ATSC_QUANTILE_HIGHER = 2, ATSC_QUANTILE_NEAREST = 3 };
+/* begin / count / q are HOST arrays; d_body and d_out (n_windows * n_q doubles, 8-byte aligned) are device memory.
+ * Enqueued on `stream`, not synchronised.  A malformed payload inside a window sets the plan's status word.  The plan
+ * keeps the call's tables and scratch: the next quantile call on the same plan waits (host side) until this one's work
+ * is done; atsc_dplan_destroy frees them. */
+int atsc_quantile_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                              const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
+                              double *d_out, void *stream);
+/* Host bytes in, host results out (n_windows * n_q doubles), synchronous; walks and uploads only the touched records,
+ * as atsc_aggregate_windows does.  ATSC_E_FORMAT (nothing written) for a malformed payload inside a window. */
+int atsc_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                          const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
+                          double *out);
 
 /* ------------------------------------------------------------------------ */
 /* CompressedStream mirror (atsc/src/data.rs:29-110)                          */
@@ -348,6 +381,9 @@ int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uint64_t count
 /* atsc_aggregate_windows over the stream's frames */
 int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                   atsc_window_stats *out);
+/* atsc_quantile_windows over the stream's frames */
+int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                 uint32_t n_q, const double *q, int method, double *out);
 void atsc_free(void *p);
 
 /* compress_data / decompress_data of the atsc CLI (atsc/src/main.rs:130-172): clean (drop NaN/Inf),
