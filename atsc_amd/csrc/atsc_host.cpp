@@ -1,6 +1,8 @@
 // atsc_host.cpp -- host side of libatsc_hip.so: context, plans, launch orchestration and the
 // format helpers that sit either side of the GPU path.  There is NO CPU compression path in
 // this library: without a HIP device atsc_ctx_create fails with ATSC_E_NO_DEVICE.
+// The window queries (window decode, windowed aggregates and quantiles) are in atsc_windows.cpp; what the two files
+// share is declared in atsc_host_private.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,8 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/atsc_hip.h"
-#include "atsc_internal.h"
+#include "atsc_host_private.h"
 
 namespace atsc {
 hipError_t launch_compress_class(int cls, uint32_t count, uint32_t lds, const double *samples,
@@ -33,11 +34,6 @@ hipError_t launch_compress_large(uint32_t count, const double *samples, const De
                                  unsigned char *ws, uint64_t ws_stride, uint32_t ws_slots, hipStream_t s,
                                  const LargePre *pre = nullptr);
 uint64_t large_ws_bytes(uint32_t n, uint32_t L, uint32_t kcap);
-hipError_t launch_decompress_large(uint32_t count, const struct DevDFrame *frames, const uint32_t *ids,
-                                   const DevPlan *plans, const float2 *twpool, const uint8_t *body,
-                                   double *out, int *status, unsigned char *ws, uint64_t ws_stride,
-                                   uint32_t ws_slots, int tiled, int sparse, hipStream_t s, const LargePre *pre = nullptr,
-                                   uint32_t sp_tiles = 0);
 hipError_t launch_order_by_cost(const uint32_t *ids_src, uint32_t *ids_dst, const uint32_t *cost, uint8_t *bkt,
                                 uint32_t *hist_cursor, const uint32_t *class_first,
                                 const uint32_t *class_count, int n_classes, hipStream_t s);
@@ -51,37 +47,12 @@ hipError_t launch_decompress(const struct DevDFrame *frames, uint64_t n_frames, 
                              int cls, uint32_t count, uint32_t lds, const DevPlan *plans,
                              const float2 *twpool, const uint8_t *body, double *out, int *status,
                              hipStream_t s);
-// (weak: the sanitizer build of the host sources, tests/asan, links without the window kernels and never decodes a window)
-__attribute__((weak)) hipError_t launch_decompress_window(const DevDFrame *frames, const DevWTask *tasks, int cls,
-                                                          uint32_t count, uint32_t lds, const DevPlan *plans,
-                                                          const float2 *twpool, const uint8_t *body, double *out,
-                                                          int *status, hipStream_t s);
-__attribute__((weak)) hipError_t launch_window_gather(const DevWGather *g, uint32_t n, uint32_t max_len,
-                                                      const double *scratch, double *out, hipStream_t s);
-// the windowed aggregates' reduce kernels (atsc_aggregate.hip; weak for the same reason)
-__attribute__((weak)) hipError_t launch_agg_tiles(const DevAggTile *tasks, uint32_t n, const double *scratch,
-                                                  DevAggPart *part, double *fl, hipStream_t s);
-__attribute__((weak)) hipError_t launch_agg_combine(const DevAggComb *tasks, uint32_t n, DevAggPart *part,
-                                                    const double *fl, void *stats, hipStream_t s);
-// the windowed quantiles' selection kernels (atsc_quantile.hip; weak for the same reason)
-__attribute__((weak)) hipError_t launch_qnt_short(const DevQTask *tasks, uint32_t n, const double *scratch, const double *q,
-                                                  uint32_t n_q, int method, double *out, hipStream_t s);
-__attribute__((weak)) hipError_t launch_qnt_medium(const DevQTask *tasks, uint32_t n, uint32_t P, const double *scratch,
-                                                   const double *q, uint32_t n_q, int method, double *out, hipStream_t s);
-__attribute__((weak)) hipError_t launch_qnt_hist(const DevQChunk *chunks, uint32_t n, const double *scratch,
-                                                 const DevQState *st, uint32_t *hist, uint32_t rows, uint32_t pass,
-                                                 hipStream_t s);
-__attribute__((weak)) hipError_t launch_qnt_pick(const DevQTask *tasks, uint32_t n, DevQState *st, uint32_t *hist,
-                                                 uint32_t rows, uint32_t pass, const double *q, uint32_t n_q, int method,
-                                                 double *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
 
 static const int N_CLASSES = 7;       // 0..5: LDS-resident frame kernels, 6: large frames (atsc_large.hip)
-static const int CLASS_LARGE = 6;
 static const uint32_t MAX_FRAME_TIER_M = 4096;   // longest frame of the LDS-resident kernels
-static const uint32_t MAX_FRAME = 131072;        // MAX_FRAME_SIZE of the reference chunker (optimizer/mod.rs:27)
 static const uint32_t LARGE_WS_SLOTS = 256;      // large frames in flight (one workgroup + workspace each) ...
 // ... of the longest kind; a batch of shorter large frames gets as many slots as the same memory holds (a launch of 256
 // 8192-sample frames is 2 M samples: every grid of the large tier would be latency-bound on it)
@@ -91,64 +62,6 @@ static uint32_t large_ws_slots(uint64_t ws_stride)
     const uint64_t fit = ws_stride ? budget / ws_stride : LARGE_WS_SLOTS;
     return (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(LARGE_WS_SLOTS, fit));
 }
-
-struct atsc_ctx {
-    int device = 0;
-    std::string last_error;
-    // diagnostics of the last compress call
-    atsc_frame_diag *d_diag = nullptr;
-    uint64_t diag_cap = 0;
-    uint64_t diag_n = 0;
-    hipStream_t diag_stream = nullptr;
-    bool want_diag = false;
-    // Device memory pool.  The host-pointer entry points build a plan and five buffers per call and
-    // drop them at the end; hipMalloc / hipFree of hundreds of megabytes cost milliseconds each, so
-    // freed blocks are kept (up to POOL_MAX_BYTES) and handed out again when the size fits.
-    std::vector<std::pair<void *, size_t>> pool_free_list;
-    std::map<void *, size_t> pool_live;
-    size_t pool_held = 0;
-    // Streams of the context's own (created on first use; few, because the runtime maps streams onto a handful of
-    // hardware queues).  Pipelined calls (atsc_compress_plan_dev_pipelined): consecutive batches go round-robin over the
-    // chains of a plan, chain c on chain_streams[c] -- a dependent launch starts 6-10 us after its predecessor ends on this
-    // system (tools/gap_probe.hip), and a frame kernel's freed wave slots refill slowly from a single queue; several
-    // queues feeding the same CUs hide both (what bench.py --chains did from outside in round 2).
-    hipStream_t chain_streams[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t pack_streams[4] = {nullptr, nullptr, nullptr, nullptr};  // a chain's packing: beside its next batch's codecs
-    int n_chains = 2;                   // atsc_ctx_set_chains (1..4)
-    bool adaptive_order = false;        // pipelined calls start a class's costliest frames first (atsc_ctx_set_adaptive_order)
-    int debug_stop = 0;  // ATSC_DEBUG_STOP: phase-timing aid for tools/, never set in production
-    // optional timing of the dominant k_compress launch (HIP events on the launch stream)
-    bool profiling = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    size_t ev_used = 0;
-    // Host-pointer entry points (atsc_compress_frames ...): plans kept by frame layout (a service compresses
-    // the same layout batch after batch; building a plan walks every frame and uploads its tables), and a
-    // stream of their own so that the blocking host-to-device copy of one part of a batch does not order
-    // itself behind the kernels of the part before it (the legacy default stream would).
-    struct CachedPlan {
-        uint64_t hash = 0, stamp = 0;
-        std::vector<uint32_t> lens;
-        atsc_plan *plan = nullptr;
-    };
-    std::vector<CachedPlan> plan_cache;
-    uint64_t plan_stamp = 0;
-    hipStream_t work_stream = nullptr;
-    hipStream_t copy_stream = nullptr;             // host-to-device copies of the host-pointer entry points
-    hipStream_t d2h_stream = nullptr;              // ... and the records' way back, part by part (registered memory)
-    std::vector<hipEvent_t> ev_parts;              // "part g's records are packed"
-    unsigned char *h_stage = nullptr;              // page-locked staging for tables a kernel copies up (h2d_small)
-    size_t h_stage_cap = 0, h_stage_used = 0;
-    hipEvent_t ev_copy[2] = {nullptr, nullptr};    // "part g's samples are on the device"
-    uint64_t agg_budget = 0;                       // atsc_ctx_set_aggregate_scratch (bytes; 0: the default)
-};
-
-struct PlanTables {
-    std::vector<DevPlan> plans;   // host copy
-    std::vector<float2> twpool;   // host copy
-    std::map<uint32_t, uint32_t> by_n;
-    DevPlan *d_plans = nullptr;
-    float2 *d_tw = nullptr;
-};
 
 // A second view of the same batch with other per-frame transform parameters:
 //  * trial launch of the sample-level selector: the first COMPRESSION_SPEED[level] samples of every
@@ -216,55 +129,11 @@ struct atsc_plan {
     uint64_t slots_bytes = 0;
 };
 
-struct atsc_dplan {
-    atsc_ctx *ctx = nullptr;
-    uint64_t n_frames = 0, n_samples = 0;
-    PlanTables tabs;
-    std::vector<uint32_t> class_count, class_lds, class_first;
-    DevDFrame *d_frames = nullptr;
-    uint32_t *d_ids = nullptr;
-    int *d_status = nullptr;
-    unsigned char *d_ws = nullptr;
-    uint64_t ws_stride = 0;
-    uint32_t ws_slots = 0;
-    bool large_tiled = false;
-    LargePre large_pre{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // batched inverse transform of the large FFT frames (tiles1 == 0: off)
-    uint32_t large_sp_tiles = 0;        // tiles per frame of the sparse inverse's (tile, frame) grid (0: off)
-    uint32_t large_choice_count = 0;    // large frames of the plan the forms above were chosen for
-    // host copies for the window decode (atsc_dplan_find_frames, atsc_decompress_windows_dev): frame f holds the
-    // samples [h_frames[f].out_off, h_frames[f + 1].out_off or n_samples)
-    std::vector<DevDFrame> h_frames;
-    std::vector<int> h_cls;
-    // what the last atsc_decompress_windows_dev call owns: its task tables (page-locked staging and device copy)
-    // and its scratch; ev_win marks the end of its work
-    mutable unsigned char *h_win = nullptr, *d_win = nullptr;
-    mutable size_t win_cap = 0;
-    mutable double *d_win_scratch = nullptr;
-    mutable uint64_t win_scratch_cap = 0;
-    mutable hipEvent_t ev_win = nullptr;
-    mutable bool win_pending = false;
-    // the same for the last atsc_aggregate_windows_dev call: tables (staging; device copy followed by the partials),
-    // decoded-sample scratch, end of work
-    mutable unsigned char *h_agg = nullptr, *d_agg = nullptr;
-    mutable size_t agg_hcap = 0, agg_dcap = 0;
-    mutable double *d_agg_scratch = nullptr;
-    mutable uint64_t agg_scratch_cap = 0;
-    mutable hipEvent_t ev_agg = nullptr;
-    mutable bool agg_pending = false;
-    // the same for the last atsc_quantile_windows_dev call: tables (staging; device copy followed by the long tier's
-    // state and counts), decoded-sample scratch, end of work
-    mutable unsigned char *h_qnt = nullptr, *d_qnt = nullptr;
-    mutable size_t qnt_hcap = 0, qnt_dcap = 0;
-    mutable double *d_qnt_scratch = nullptr;
-    mutable uint64_t qnt_scratch_cap = 0;
-    mutable hipEvent_t ev_qnt = nullptr;
-    mutable bool qnt_pending = false;
-};
-
 // ------------------------------------------------------------------------------------------
 // small helpers
 // ------------------------------------------------------------------------------------------
-static int fail(atsc_ctx *ctx, int rc, const char *what, hipError_t e = hipSuccess)
+namespace atsc {
+int fail(atsc_ctx *ctx, int rc, const char *what, hipError_t e)
 {
     if (ctx) {
         ctx->last_error = what;
@@ -275,14 +144,11 @@ static int fail(atsc_ctx *ctx, int rc, const char *what, hipError_t e = hipSucce
     }
     return rc;
 }
-#define HIPCHK(ctx, call)                                                    \
-    do {                                                                     \
-        hipError_t e__ = (call);                                             \
-        if (e__ != hipSuccess) return fail((ctx), ATSC_E_HIP, #call, e__);   \
-    } while (0)
+}  // namespace atsc
 
 static const size_t POOL_MAX_BYTES = 8ull << 30;
-static hipError_t pool_alloc(atsc_ctx *ctx, void **out, size_t bytes)
+namespace atsc {
+hipError_t pool_alloc(atsc_ctx *ctx, void **out, size_t bytes)
 {
     if (bytes == 0) bytes = 16;
     // smallest kept block that fits without wasting more than half of itself (or 4 MB)
@@ -310,9 +176,7 @@ static hipError_t pool_alloc(atsc_ctx *ctx, void **out, size_t bytes)
     if (e == hipSuccess) ctx->pool_live[*out] = bytes;
     return e;
 }
-// The caller guarantees that no kernel still uses the block (plan destruction synchronises the device
-// once, as hipFree would for every block; the host-pointer entry points have synchronised already).
-static void pool_free(atsc_ctx *ctx, void *p)
+void pool_free(atsc_ctx *ctx, void *p)
 {
     if (!p) return;
     auto it = ctx->pool_live.find(p);
@@ -323,6 +187,7 @@ static void pool_free(atsc_ctx *ctx, void *p)
     ctx->pool_free_list.emplace_back(p, sz);
     ctx->pool_held += sz;
 }
+}  // namespace atsc
 
 static bool is_decomposable(uint64_t n)
 {
@@ -364,9 +229,6 @@ static bool choose_large_tiled(uint32_t n_large_frames)
     if (const char *e = getenv("ATSC_LARGE_FFT")) tiled = strcmp(e, "tiled") == 0;
     return tiled;
 }
-// Inverse transforms of the large tier run from the sparse list of admitted bins (sparse_inverse,
-// atsc_large.hip); ATSC_LARGE_DENSE=1 keeps the dense transforms through the workspace (A/B runs).
-static bool large_sparse() { return getenv("ATSC_LARGE_DENSE") == nullptr; }
 // Grid extents of the batched pre-pass (forward transform, untangle, norms of every large frame over
 // the whole GPU before the per-frame kernel); all zero when a large frame length has no M1 x M2 split.
 static LargePre large_pre_extents(const std::vector<DevPlan> &plans, const std::vector<uint32_t> &large_plan_ids)
@@ -1861,18 +1723,9 @@ extern "C" void atsc_dplan_destroy(atsc_dplan *p)
     if (!p) return;
     (void)hipDeviceSynchronize();
     free_tables(p->ctx, p->tabs);
-    if (p->h_win) (void)hipHostFree(p->h_win);
-    pool_free(p->ctx, p->d_win);
-    pool_free(p->ctx, p->d_win_scratch);
-    if (p->ev_win) (void)hipEventDestroy(p->ev_win);
-    if (p->h_agg) (void)hipHostFree(p->h_agg);
-    pool_free(p->ctx, p->d_agg);
-    pool_free(p->ctx, p->d_agg_scratch);
-    if (p->ev_agg) (void)hipEventDestroy(p->ev_agg);
-    if (p->h_qnt) (void)hipHostFree(p->h_qnt);
-    pool_free(p->ctx, p->d_qnt);
-    pool_free(p->ctx, p->d_qnt_scratch);
-    if (p->ev_qnt) (void)hipEventDestroy(p->ev_qnt);
+    p->win.release(p->ctx);
+    p->agg.release(p->ctx);
+    p->qnt.release(p->ctx);
     pool_free(p->ctx, p->d_frames);
     pool_free(p->ctx, p->d_ids);
     pool_free(p->ctx, p->d_status);
@@ -1882,20 +1735,10 @@ extern "C" void atsc_dplan_destroy(atsc_dplan *p)
 extern "C" uint64_t atsc_dplan_n_frames(const atsc_dplan *p) { return p ? p->n_frames : 0; }
 extern "C" uint64_t atsc_dplan_n_samples(const atsc_dplan *p) { return p ? p->n_samples : 0; }
 
-// Host half of atsc_dplan_create: walks the untrusted record bytes and builds the per-frame table and the
-// per-length tables.  No HIP call in here (the sanitizer build of tests/asan drives it without a GPU
-// through atsc_internal_dplan_parse).
-struct DPlanHost {
-    std::vector<DevDFrame> frames;
-    std::vector<int> cls;
-    PlanTables tabs;
-    std::vector<uint32_t> class_count, class_lds;
-    uint64_t ws_stride = 0, n_samples = 0;
-};
-// begin / soft_limit / end_pos: a stream without a count in front can be walked in pieces -- the records from byte
-// `begin` up to the first record boundary at or behind `soft_limit` (*end_pos: where that is)
-static int dplan_parse(const uint8_t *body, uint64_t body_len, int has_count, DPlanHost &H, const char **why,
-                       uint64_t begin = 0, uint64_t soft_limit = ~0ull, uint64_t *end_pos = nullptr)
+// the host half of atsc_dplan_create (atsc_host_private.h)
+namespace atsc {
+int dplan_parse(const uint8_t *body, uint64_t body_len, int has_count, DPlanHost &H, const char **why, uint64_t begin,
+                uint64_t soft_limit, uint64_t *end_pos)
 {
     uint64_t pos = begin, declared = 0;
     *why = "";
@@ -1975,6 +1818,7 @@ static int dplan_parse(const uint8_t *body, uint64_t body_len, int has_count, DP
     if (end_pos) *end_pos = pos;
     return ATSC_OK;
 }
+}  // namespace atsc
 // test hook of the sanitizer build (declared in atsc_internal.h, not part of the public ABI)
 extern "C" int atsc_internal_dplan_parse(const uint8_t *body, uint64_t body_len, int has_count,
                                          uint64_t *n_frames, uint64_t *n_samples)
@@ -1991,12 +1835,9 @@ extern "C" int atsc_internal_dplan_parse(const uint8_t *body, uint64_t body_len,
     ATSC_API_END
 }
 
-static int dplan_create_range(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t begin,
-                              uint64_t soft_limit, uint64_t *end_pos, atsc_dplan **out, hipStream_t up = nullptr);
-// The large tier's launch forms of a plan, from every large frame of it: the transform form, the batched pre-pass and the
-// sparse inverse's tile grid.  They depend on the set of large frames, so a window decode takes them from its stream's.
-static void large_choices(atsc_dplan *p, const std::vector<DevPlan> &plans, const std::vector<DevDFrame> &frames,
-                          const std::vector<int> &cls)
+namespace atsc {
+void large_choices(atsc_dplan *p, const std::vector<DevPlan> &plans, const std::vector<DevDFrame> &frames,
+                   const std::vector<int> &cls)
 {
     uint32_t n_large = 0;
     for (size_t f = 0; f < frames.size(); ++f) n_large += cls[f] == CLASS_LARGE;
@@ -2034,15 +1875,15 @@ static void large_choices(atsc_dplan *p, const std::vector<DevPlan> &plans, cons
         }
     }
 }
+}  // namespace atsc
 extern "C" int atsc_dplan_create(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len,
                                  int has_count, atsc_dplan **out)
 {
     return dplan_create_range(ctx, body, body_len, has_count, 0, ~0ull, nullptr, out);
 }
-// up: the stream a kernel copies the plan's tables up on instead of synchronous copies (h2d_small); the plan may then
-// only be used on that stream (or behind it)
-static int dplan_create_range(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t begin,
-                              uint64_t soft_limit, uint64_t *end_pos, atsc_dplan **out, hipStream_t up)
+namespace atsc {
+int dplan_create_range(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t begin,
+                       uint64_t soft_limit, uint64_t *end_pos, atsc_dplan **out, hipStream_t up)
 {
     ATSC_API_BEGIN
     if (!ctx || !body || !out) return fail(ctx, ATSC_E_INVALID, "dplan_create: null argument");
@@ -2113,6 +1954,7 @@ static int dplan_create_range(atsc_ctx *ctx, const uint8_t *body, uint64_t body_
     return ATSC_OK;
     ATSC_API_END
 }
+}  // namespace atsc
 
 extern "C" int atsc_decompress_plan_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body,
                                         double *d_out, void *stream)
@@ -2367,1133 +2209,6 @@ extern "C" int atsc_decompress_frames_alloc(atsc_ctx *ctx, const uint8_t *body, 
     *out = nullptr;
     const int rc = decompress_frames_impl(ctx, body, body_len, has_count, nullptr, 0, out, out_n);
     if (rc) *out_n = 0;
-    return rc;
-    ATSC_API_END
-}
-
-// ------------------------------------------------------------------------------------------
-// window decode: samples [begin, begin + count) of the decoded stream without decoding the rest
-// ------------------------------------------------------------------------------------------
-// The record walk of a window read over untrusted bytes: from `pos`, at most max_frames records, with the header checks
-// of atsc_bro_scan, up to the record that holds sample begin + count - 1 (count == 0: the record that holds `begin`).
-// A Noop record counts the samples it stores (noop.rs:79-83), as the decoder does.  decode: the frame-length checks of
-// dplan_parse as well (a frame the decoders cannot take).  ATSC_E_INVALID when the stream ends in front of the window's end.
-struct WindowWalk {
-    uint64_t byte_begin = 0, byte_end = 0, frame_begin = 0, frame_end = 0, sample_begin = 0;
-};
-static int window_walk(const uint8_t *b, uint64_t len, uint64_t pos, uint64_t max_frames, uint64_t begin, uint64_t count,
-                       bool decode, WindowWalk &w)
-{
-    if (begin + count < begin) return ATSC_E_INVALID;
-    const uint64_t end = begin + count;
-    uint64_t s_off = 0, f = 0;
-    bool found = false;
-    for (; max_frames == ~0ull ? pos < len : f < max_frames; ++f) {
-        HostRecord hr;
-        if (!host_next_record(b, len, pos, hr)) return ATSC_E_FORMAT;
-        if (hr.tag > 6 || hr.tag == ATSC_AUTO) return ATSC_E_FORMAT;
-        uint64_t n = hr.sample_count;
-        if (hr.tag == ATSC_NOOP) {
-            uint64_t q = hr.payload_off + 1, cnt = 0;
-            if (hr.payload_len < 2 || !host_varint(b, hr.payload_off + hr.payload_len, q, cnt) || cnt > hr.payload_len)
-                return ATSC_E_FORMAT;
-            n = cnt;
-        }
-        if (decode && n == 0) return ATSC_E_FORMAT;
-        if (decode && n > MAX_FRAME) return ATSC_E_UNSUPPORTED;
-        if (s_off + n < s_off) return ATSC_E_FORMAT;
-        if (!found && s_off + n > begin) {
-            found = true;
-            w.frame_begin = f;
-            w.byte_begin = hr.start;
-            w.sample_begin = s_off;
-            if (count == 0) {
-                w.frame_end = f;
-                w.byte_end = hr.start;
-                return ATSC_OK;
-            }
-        }
-        s_off += n;
-        if (found && s_off >= end) {
-            w.frame_end = f + 1;
-            w.byte_end = pos;
-            return ATSC_OK;
-        }
-    }
-    if (count == 0 && begin == s_off) {  // the empty window at the stream's end
-        w.frame_begin = w.frame_end = f;
-        w.byte_begin = w.byte_end = pos;
-        w.sample_begin = s_off;
-        return ATSC_OK;
-    }
-    return ATSC_E_INVALID;
-}
-
-extern "C" int atsc_bro_find_window(const uint8_t *bro, uint64_t len, uint64_t begin, uint64_t count,
-                                    uint64_t *byte_begin, uint64_t *byte_end, uint64_t *frame_begin, uint64_t *frame_end,
-                                    uint64_t *sample_begin)
-{
-    ATSC_API_BEGIN
-    if (!bro) return ATSC_E_INVALID;
-    uint64_t pos = 0, nf = 0;
-    int rc = atsc_bro_open(bro, len, &pos, &nf);
-    if (rc) return rc;
-    if (nf > len / 4) return ATSC_E_FORMAT;
-    WindowWalk w;
-    rc = window_walk(bro, len, pos, nf, begin, count, false, w);
-    if (rc) return rc;
-    if (byte_begin) *byte_begin = w.byte_begin;
-    if (byte_end) *byte_end = w.byte_end;
-    if (frame_begin) *frame_begin = w.frame_begin;
-    if (frame_end) *frame_end = w.frame_end;
-    if (sample_begin) *sample_begin = w.sample_begin;
-    return ATSC_OK;
-    ATSC_API_END
-}
-
-extern "C" int atsc_dplan_find_frames(const atsc_dplan *dp, uint64_t begin, uint64_t count, uint64_t *frame_begin,
-                                      uint64_t *frame_end)
-{
-    if (!dp || !frame_begin || !frame_end) return ATSC_E_INVALID;
-    if (begin > dp->n_samples || count > dp->n_samples - begin) return ATSC_E_INVALID;
-    const auto &F = dp->h_frames;
-    auto by_off = [](uint64_t v, const DevDFrame &d) { return v < d.out_off; };
-    // the frame holding `begin` (every frame holds at least one sample), or n_frames at the stream's end
-    const uint64_t fb = (uint64_t)(std::upper_bound(F.begin(), F.end(), begin, by_off) - F.begin()) - 1;
-    *frame_begin = begin == dp->n_samples ? F.size() : fb;
-    *frame_end = count == 0 ? *frame_begin
-                            : (uint64_t)(std::upper_bound(F.begin(), F.end(), begin + count - 1, by_off) - F.begin());
-    return ATSC_OK;
-}
-
-// The window decode.  One task per (window, touched frame); tasks go by frame:
-//  * a frame of the LDS-resident classes that one window touches: k_decompress<W, SPL, true> straight into d_out;
-//  * one that several windows touch: decoded once, over the union of their ranges, into scratch;
-//  * a large frame: the large tier's launch sequence over a sub-plan of the touched large frames -- one that a window
-//    holds whole is written straight into d_out (its out_off rebased), the others go to scratch whole;
-//  * k_window_gather then copies the scratch parts to their windows.
-// A destination in scratch is named by its distance from d_out in doubles, modulo 2^64: one base pointer serves both.
-extern "C" int atsc_decompress_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
-                                           const uint64_t *begin, const uint64_t *count, const uint64_t *out_off,
-                                           double *d_out, void *stream)
-{
-    ATSC_API_BEGIN
-    if (!ctx || !dp || !d_body || !d_out || (n_windows && (!begin || !count || !out_off)))
-        return fail(ctx, ATSC_E_INVALID, "decompress_windows: null argument");
-    if ((uintptr_t)d_out & 7u) return fail(ctx, ATSC_E_INVALID, "decompress_windows: d_out is not 8-byte aligned");
-    const uint64_t ns = dp->n_samples;
-    for (uint64_t i = 0; i < n_windows; ++i)
-        if (begin[i] > ns || count[i] > ns - begin[i]) return fail(ctx, ATSC_E_INVALID, "decompress_windows: window beyond the stream");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const auto &F = dp->h_frames;
-    struct Ent {
-        uint64_t dst;
-        uint32_t frame, lo, hi;
-    };
-    std::vector<Ent> ents;
-    for (uint64_t i = 0; i < n_windows; ++i) {
-        if (!count[i]) continue;
-        uint64_t fb, fe;
-        (void)atsc_dplan_find_frames(dp, begin[i], count[i], &fb, &fe);
-        const uint64_t b = begin[i], e = begin[i] + count[i];
-        for (uint64_t f = fb; f < fe; ++f) {
-            const uint64_t fo = F[f].out_off, fn = F[f].n;
-            const uint64_t lo = std::max(b, fo) - fo, hi = std::min(e, fo + fn) - fo;
-            ents.push_back(Ent{out_off[i] + (fo + lo - b), (uint32_t)f, (uint32_t)lo, (uint32_t)hi});
-        }
-    }
-    if (ents.empty()) return ATSC_OK;
-    if (!launch_decompress_window || !launch_window_gather) return fail(ctx, ATSC_E_UNSUPPORTED, "decompress_windows: no window kernels");
-    auto by_frame = [](const Ent &a, const Ent &b) { return a.frame < b.frame; };
-    if (!std::is_sorted(ents.begin(), ents.end(), by_frame)) std::stable_sort(ents.begin(), ents.end(), by_frame);
-    // the tables and scratch of the previous call on this plan are reused once its work is done
-    if (dp->win_pending) {
-        HIPCHK(ctx, hipEventSynchronize(dp->ev_win));
-        dp->win_pending = false;
-    }
-    std::vector<DevWTask> small[CLASS_LARGE];
-    std::vector<DevDFrame> big;
-    std::vector<DevWGather> gat;
-    std::vector<std::pair<int, size_t>> small_scr;  // (class, task) whose dst is a scratch offset
-    std::vector<size_t> big_scr;
-    uint64_t scr = 0;
-    uint32_t max_len = 0;
-    for (size_t a = 0; a < ents.size();) {
-        size_t z = a + 1;
-        while (z < ents.size() && ents[z].frame == ents[a].frame) ++z;
-        const uint32_t f = ents[a].frame, n = F[f].n;
-        const int c = dp->h_cls[f];
-        const bool one = z - a == 1;
-        if (c != CLASS_LARGE) {
-            if (one) {
-                small[c].push_back(DevWTask{ents[a].dst, f, ents[a].lo, ents[a].hi, 0});
-            } else {
-                uint32_t ulo = n, uhi = 0;
-                for (size_t k = a; k < z; ++k) { ulo = std::min(ulo, ents[k].lo); uhi = std::max(uhi, ents[k].hi); }
-                small_scr.emplace_back(c, small[c].size());
-                small[c].push_back(DevWTask{scr, f, ulo, uhi, 0});
-                for (size_t k = a; k < z; ++k) {
-                    gat.push_back(DevWGather{scr + ents[k].lo - ulo, ents[k].dst, ents[k].hi - ents[k].lo, 0});
-                    max_len = std::max(max_len, ents[k].hi - ents[k].lo);
-                }
-                scr += uhi - ulo;
-            }
-        } else {
-            DevDFrame d = F[f];
-            if (one && ents[a].lo == 0 && ents[a].hi == n) {
-                d.out_off = ents[a].dst;
-            } else {
-                big_scr.push_back(big.size());
-                d.out_off = scr;
-                for (size_t k = a; k < z; ++k) {
-                    gat.push_back(DevWGather{scr + ents[k].lo, ents[k].dst, ents[k].hi - ents[k].lo, 0});
-                    max_len = std::max(max_len, ents[k].hi - ents[k].lo);
-                }
-                scr += n;
-            }
-            big.push_back(d);
-        }
-        a = z;
-    }
-    if (scr > dp->win_scratch_cap) {
-        pool_free(ctx, dp->d_win_scratch);
-        dp->d_win_scratch = nullptr;
-        dp->win_scratch_cap = 0;
-        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_win_scratch, scr * sizeof(double)));
-        dp->win_scratch_cap = scr;
-    }
-    if (scr) {
-        const uint64_t base = ((uint64_t)(uintptr_t)dp->d_win_scratch - (uint64_t)(uintptr_t)d_out) / sizeof(double);
-        for (const auto &t : small_scr) small[t.first][t.second].dst += base;
-        for (size_t i : big_scr) big[i].out_off += base;
-    }
-    // one upload: the classes' task lists, the large sub-plan (frames, ids), the copies
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t off_small[CLASS_LARGE], bytes = 0;
-    for (int c = 0; c < CLASS_LARGE; ++c) { off_small[c] = bytes; bytes = al(bytes + small[c].size() * sizeof(DevWTask)); }
-    const size_t off_big = bytes;
-    bytes = al(bytes + big.size() * sizeof(DevDFrame));
-    const size_t off_ids = bytes;
-    bytes = al(bytes + big.size() * sizeof(uint32_t));
-    const size_t off_gat = bytes;
-    bytes = al(bytes + gat.size() * sizeof(DevWGather));
-    if (bytes > dp->win_cap) {
-        if (dp->h_win) (void)hipHostFree(dp->h_win);
-        dp->h_win = nullptr;
-        pool_free(ctx, dp->d_win);
-        dp->d_win = nullptr;
-        dp->win_cap = 0;
-        const size_t cap = std::max<size_t>(bytes, 64u << 10);
-        HIPCHK(ctx, hipHostMalloc((void **)&dp->h_win, cap, hipHostMallocDefault));
-        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_win, cap));
-        dp->win_cap = cap;
-    }
-    if (!dp->ev_win) HIPCHK(ctx, hipEventCreateWithFlags(&dp->ev_win, hipEventDisableTiming));
-    unsigned char *h = dp->h_win, *d = dp->d_win;
-    for (int c = 0; c < CLASS_LARGE; ++c)
-        if (!small[c].empty()) memcpy(h + off_small[c], small[c].data(), small[c].size() * sizeof(DevWTask));
-    if (!big.empty()) {
-        memcpy(h + off_big, big.data(), big.size() * sizeof(DevDFrame));
-        uint32_t *ids = (uint32_t *)(h + off_ids);
-        for (size_t i = 0; i < big.size(); ++i) ids[i] = (uint32_t)i;
-    }
-    if (!gat.empty()) memcpy(h + off_gat, gat.data(), gat.size() * sizeof(DevWGather));
-    HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-    for (int c = 0; c < CLASS_LARGE; ++c) {
-        const hipError_t e = launch_decompress_window(dp->d_frames, (const DevWTask *)(d + off_small[c]), c,
-                                                      (uint32_t)small[c].size(), dp->class_lds[c], dp->tabs.d_plans,
-                                                      dp->tabs.d_tw, d_body, d_out, dp->d_status, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_decompress (window)", e);
-    }
-    if (!big.empty()) {
-        const hipError_t e = launch_decompress_large(
-            (uint32_t)big.size(), (const DevDFrame *)(d + off_big), (const uint32_t *)(d + off_ids), dp->tabs.d_plans,
-            dp->tabs.d_tw, d_body, d_out, dp->d_status, dp->d_ws, dp->ws_stride, dp->ws_slots, dp->large_tiled ? 1 : 0,
-            large_sparse() ? 1 : 0, s, dp->large_pre.tiles1 ? &dp->large_pre : nullptr,
-            // the (tile, frame) split of the sparse inverse runs for launches of up to LARGE_SPLIT_MAX frames: a window
-            // launch of fewer frames than its plan's full decode takes the full decode's side of that line
-            dp->large_choice_count <= LARGE_SPLIT_MAX ? dp->large_sp_tiles : 0);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_decompress_large (window)", e);
-    }
-    if (!gat.empty()) {
-        const hipError_t e = launch_window_gather((const DevWGather *)(d + off_gat), (uint32_t)gat.size(), max_len,
-                                                  dp->d_win_scratch, d_out, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_window_gather", e);
-    }
-    HIPCHK(ctx, hipEventRecord(dp->ev_win, s));
-    dp->win_pending = true;
-    return ATSC_OK;
-    ATSC_API_END
-}
-
-// Host call: walks the headers up to the window's last record, plans the touched records only and uploads only their bytes.
-extern "C" int atsc_decompress_window(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t begin,
-                                      uint64_t count, double *out, uint64_t out_cap, uint64_t *out_n)
-{
-    ATSC_API_BEGIN
-    if (!ctx || !body || !out_n || (count && !out)) return fail(ctx, ATSC_E_INVALID, "decompress_window: null argument");
-    *out_n = 0;
-    static const bool trace = getenv("ATSC_TRACE_HOST") != nullptr;
-    uint64_t pos = 0, max_frames = ~0ull;
-    if (has_count) {
-        if (!host_varint(body, body_len, pos, max_frames)) return fail(ctx, ATSC_E_FORMAT, "decompress_window: frame count");
-        if (max_frames > body_len / 4) return fail(ctx, ATSC_E_FORMAT, "decompress_window: frame count exceeds the bytes present");
-    }
-    WindowWalk w;
-    int rc = window_walk(body, body_len, pos, max_frames, begin, count, true, w);
-    if (rc) return fail(ctx, rc, rc == ATSC_E_INVALID ? "decompress_window: window beyond the stream" : "decompress_window: record walk");
-    if (out_cap < count) return fail(ctx, ATSC_E_CAPACITY, "decompress_window: out_cap");
-    if (count == 0) return ATSC_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->work_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->work_stream, hipStreamNonBlocking));
-    hipStream_t ws = ctx->work_stream;
-    const uint64_t slice = w.byte_end - w.byte_begin;
-    atsc_dplan *dp = nullptr;
-    rc = dplan_create_range(ctx, body + w.byte_begin, slice, 0, 0, ~0ull, nullptr, &dp);
-    if (rc) return rc;
-    if (dp->class_count[CLASS_LARGE]) {
-        // The large tier's launch forms depend on every large frame of the stream (large_choices): the rest of the
-        // record headers is walked as well, so that the touched large frames decode as the full decode does them.
-        DPlanHost Hw;
-        const char *why;
-        rc = dplan_parse(body, body_len, has_count, Hw, &why);
-        if (rc) { atsc_dplan_destroy(dp); return fail(ctx, rc, why); }
-        large_choices(dp, Hw.tabs.plans, Hw.frames, Hw.cls);
-    }
-    uint8_t *d_body = nullptr;
-    double *d_out = nullptr;
-    int status = 0;
-    const uint64_t b0 = begin - w.sample_begin, zero = 0;
-    hipError_t e = hipSuccess;
-#define WCHK(call)                                                                 \
-    do {                                                                           \
-        e = (call);                                                                \
-        if (e != hipSuccess) { rc = fail(ctx, ATSC_E_HIP, #call, e); goto done; } \
-    } while (0)
-    WCHK(pool_alloc(ctx, (void **)&d_body, std::max<uint64_t>(slice, 16)));
-    WCHK(pool_alloc(ctx, (void **)&d_out, count * sizeof(double)));
-    WCHK(hipMemcpyAsync(d_body, body + w.byte_begin, slice, hipMemcpyHostToDevice, ws));
-    if (trace) fprintf(stderr, "[window]     h2d records %llu bytes (frames %llu..%llu)\n", (unsigned long long)slice,
-                       (unsigned long long)w.frame_begin, (unsigned long long)w.frame_end);
-    rc = atsc_decompress_windows_dev(ctx, dp, d_body, 1, &b0, &count, &zero, d_out, ws);
-    if (rc) goto done;
-    WCHK(hipMemcpyAsync(&status, dp->d_status, sizeof(int), hipMemcpyDeviceToHost, ws));
-    WCHK(hipStreamSynchronize(ws));
-    if (status) { rc = fail(ctx, ATSC_E_FORMAT, "decompress_window: malformed payload"); goto done; }
-    WCHK(hipMemcpyAsync(out, d_out, count * sizeof(double), hipMemcpyDeviceToHost, ws));
-    WCHK(hipStreamSynchronize(ws));
-    *out_n = count;
-#undef WCHK
-done:
-    if (rc) (void)hipStreamSynchronize(ws);
-    pool_free(ctx, d_body);
-    pool_free(ctx, d_out);
-    atsc_dplan_destroy(dp);
-    return rc;
-    ATSC_API_END
-}
-
-// ------------------------------------------------------------------------------------------
-// windowed aggregates: count / min / max / sum / first / last of sample windows (atsc_aggregate.hip)
-// ------------------------------------------------------------------------------------------
-// Decoded samples reach the reduce kernels through one scratch region of whole tiles, piece after piece in stream
-// order: the windows' union ("covering intervals") is cut into pieces at multiples of AGG_TILE.  Covered tile ranges
-// closer than AGG_GAP_TILES share a span, so that scattered windows do not each cost a piece of launches.
-static const uint64_t AGG_MIN_PIECE = 32ull * AGG_TILE;  // the least a piece holds, whatever the budget
-static const uint64_t AGG_GAP_TILES = 64;
-// default piece length (samples) by the tier of the touched frames.  The sweep of profiles/aggregate_probe.json found no
-// gain from pieces that fit the Infinity Cache (2^21-2^22 samples): fewer pieces win in both framings, most where the
-// large tier's launch sequence (~65 us whatever its frame count) runs once per piece.
-static const uint64_t AGG_PIECE_SMALL = 1ull << 24;
-static const uint64_t AGG_PIECE_LARGE = 1ull << 24;
-
-extern "C" int atsc_ctx_set_aggregate_scratch(atsc_ctx *ctx, uint64_t bytes)
-{
-    if (!ctx) return ATSC_E_INVALID;
-    ctx->agg_budget = bytes;
-    return ATSC_OK;
-}
-
-static void agg_empty_record(atsc_window_stats &r)
-{
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    r.count = 0;
-    r.min = r.max = r.first = r.last = nan;
-    r.sum = 0.0;
-}
-
-// ---- decoded samples of window pieces in scratch (the aggregate and the quantile calls) ----
-using Span = std::pair<uint64_t, uint64_t>;
-
-// the decode tasks of all pieces of one call, and their place in the call's upload
-struct DecodeTasks {
-    std::vector<DevWTask> small[CLASS_LARGE];
-    std::vector<DevDFrame> big;
-    std::vector<DevWGather> gat;
-    uint32_t max_big = 0, spills_used = 0;
-    size_t off_small[CLASS_LARGE] = {}, off_big = 0, off_ids = 0, off_gat = 0;
-};
-// one piece's run of them
-struct PieceDecode {
-    size_t small_at[CLASS_LARGE], big_at, gat_at;
-    uint32_t small_n[CLASS_LARGE], big_n, gat_n, max_len;
-};
-
-static size_t upload_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// the decoded samples a call's scratch may hold: the context's budget, else the default piece and room for two large
-// frames cut by its ends
-static uint64_t scratch_budget_samples(const atsc_ctx *ctx, bool large)
-{
-    return ctx->agg_budget ? ctx->agg_budget / sizeof(double)
-                           : (large ? AGG_PIECE_LARGE + 2ull * MAX_FRAME : AGG_PIECE_SMALL);
-}
-
-// whether the covering intervals (stream index; org: the plan's first sample) touch a large frame
-static bool spans_touch_large(const atsc_dplan *dp, uint64_t org, const std::vector<Span> &cov)
-{
-    for (const Span &c : cov) {
-        uint64_t fb, fe;
-        (void)atsc_dplan_find_frames(dp, c.first - org, c.second - c.first, &fb, &fe);
-        for (uint64_t f = fb; f < fe; ++f)
-            if (dp->h_cls[f] == CLASS_LARGE) return true;
-    }
-    return false;
-}
-
-// The decode tasks of the piece [S0, S1) into scratch[0, S1 - S0): per touched frame, the hull of its covered samples
-// inside the piece.  cov: ascending disjoint covering intervals, *ci the first that may still meet the piece (advanced
-// past those that end before it).  A large frame is decoded whole: in place when it lies inside the piece, else into
-// one of two spill slots behind the region (scratch[region + MAX_FRAME k]) and copied from there (k_window_gather).
-// false: more than two spill slots (only the frames across S0 and S1 can stick out).
-static bool emit_piece_decode(const atsc_dplan *dp, uint64_t org, const std::vector<Span> &cov, size_t &ci, uint64_t S0,
-                              uint64_t S1, uint64_t region, DecodeTasks &D, PieceDecode &pt)
-{
-    const auto &F = dp->h_frames;
-    for (int c = 0; c < CLASS_LARGE; ++c) pt.small_at[c] = D.small[c].size();
-    pt.big_at = D.big.size();
-    pt.gat_at = D.gat.size();
-    pt.max_len = 0;
-    uint32_t n_spill = 0;
-    auto emit = [&](uint64_t f, uint64_t lo, uint64_t hi) {
-        const uint64_t fo = org + F[f].out_off, fn = F[f].n;
-        const int c = dp->h_cls[f];
-        if (c != CLASS_LARGE) {
-            D.small[c].push_back(DevWTask{fo + lo - S0, (uint32_t)f, (uint32_t)lo, (uint32_t)hi, 0});
-            return;
-        }
-        DevDFrame d = F[f];
-        if (fo >= S0 && fo + fn <= S1) {
-            d.out_off = fo - S0;
-        } else {
-            const uint64_t sp = region + (uint64_t)MAX_FRAME * n_spill++;
-            d.out_off = sp;
-            D.gat.push_back(DevWGather{sp + lo, fo + lo - S0, (uint32_t)(hi - lo), 0});
-            pt.max_len = std::max(pt.max_len, (uint32_t)(hi - lo));
-        }
-        D.big.push_back(d);
-    };
-    while (ci < cov.size() && cov[ci].second <= S0) ++ci;
-    uint64_t hf = ~0ull, hlo = 0, hhi = 0;
-    for (size_t c = ci; c < cov.size() && cov[c].first < S1; ++c) {
-        const uint64_t a = std::max(cov[c].first, S0), z = std::min(cov[c].second, S1);
-        uint64_t fb, fe;
-        (void)atsc_dplan_find_frames(dp, a - org, z - a, &fb, &fe);
-        for (uint64_t f = fb; f < fe; ++f) {
-            const uint64_t fo = org + F[f].out_off, fn = F[f].n;
-            const uint64_t lo = std::max(a, fo) - fo, hi = std::min(z, fo + fn) - fo;
-            if (f == hf) { hhi = hi; continue; }
-            if (hf != ~0ull) emit(hf, hlo, hhi);
-            hf = f;
-            hlo = lo;
-            hhi = hi;
-        }
-    }
-    if (hf != ~0ull) emit(hf, hlo, hhi);
-    if (n_spill > 2) return false;
-    D.spills_used = std::max(D.spills_used, n_spill);
-    for (int c = 0; c < CLASS_LARGE; ++c) pt.small_n[c] = (uint32_t)(D.small[c].size() - pt.small_at[c]);
-    pt.big_n = (uint32_t)(D.big.size() - pt.big_at);
-    pt.gat_n = (uint32_t)(D.gat.size() - pt.gat_at);
-    D.max_big = std::max(D.max_big, pt.big_n);
-    return true;
-}
-
-// places the decode tasks at the front of an upload (per class the pieces' task lists, the large sub-plans, ids 0..,
-// copies); returns the upload's size so far
-static size_t place_decode_tasks(DecodeTasks &D)
-{
-    size_t bytes = 0;
-    for (int c = 0; c < CLASS_LARGE; ++c) {
-        D.off_small[c] = bytes;
-        bytes = upload_align(bytes + D.small[c].size() * sizeof(DevWTask));
-    }
-    D.off_big = bytes;
-    bytes = upload_align(bytes + D.big.size() * sizeof(DevDFrame));
-    D.off_ids = bytes;
-    bytes = upload_align(bytes + D.max_big * sizeof(uint32_t));
-    D.off_gat = bytes;
-    return upload_align(bytes + D.gat.size() * sizeof(DevWGather));
-}
-
-static void stage_decode_tasks(const DecodeTasks &D, unsigned char *h)
-{
-    for (int c = 0; c < CLASS_LARGE; ++c)
-        if (!D.small[c].empty()) memcpy(h + D.off_small[c], D.small[c].data(), D.small[c].size() * sizeof(DevWTask));
-    if (!D.big.empty()) memcpy(h + D.off_big, D.big.data(), D.big.size() * sizeof(DevDFrame));
-    for (uint32_t i = 0; i < D.max_big; ++i) ((uint32_t *)(h + D.off_ids))[i] = i;
-    if (!D.gat.empty()) memcpy(h + D.off_gat, D.gat.data(), D.gat.size() * sizeof(DevWGather));
-}
-
-// enqueues one piece's decode into scr (d: the device copy of the upload)
-static int launch_piece_decode(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, const unsigned char *d,
-                               const DecodeTasks &D, const PieceDecode &pt, double *scr, hipStream_t s, bool quantile)
-{
-    for (int c = 0; c < CLASS_LARGE; ++c) {
-        if (!pt.small_n[c]) continue;
-        const hipError_t e = launch_decompress_window(dp->d_frames, (const DevWTask *)(d + D.off_small[c]) + pt.small_at[c], c,
-                                                      pt.small_n[c], dp->class_lds[c], dp->tabs.d_plans, dp->tabs.d_tw,
-                                                      d_body, scr, dp->d_status, s);
-        if (e != hipSuccess)
-            return fail(ctx, ATSC_E_HIP, quantile ? "launch k_decompress (quantile)" : "launch k_decompress (aggregate)", e);
-    }
-    if (pt.big_n) {
-        const hipError_t e = launch_decompress_large(
-            pt.big_n, (const DevDFrame *)(d + D.off_big) + pt.big_at, (const uint32_t *)(d + D.off_ids), dp->tabs.d_plans,
-            dp->tabs.d_tw, d_body, scr, dp->d_status, dp->d_ws, dp->ws_stride, dp->ws_slots, dp->large_tiled ? 1 : 0,
-            large_sparse() ? 1 : 0, s, dp->large_pre.tiles1 ? &dp->large_pre : nullptr,
-            dp->large_choice_count <= LARGE_SPLIT_MAX ? dp->large_sp_tiles : 0);
-        if (e != hipSuccess)
-            return fail(ctx, ATSC_E_HIP,
-                        quantile ? "launch k_decompress_large (quantile)" : "launch k_decompress_large (aggregate)", e);
-    }
-    if (pt.gat_n) {
-        const hipError_t e = launch_window_gather((const DevWGather *)(d + D.off_gat) + pt.gat_at, pt.gat_n, pt.max_len, scr,
-                                                  scr, s);
-        if (e != hipSuccess)
-            return fail(ctx, ATSC_E_HIP, quantile ? "launch k_window_gather (quantile)" : "launch k_window_gather (aggregate)", e);
-    }
-    return ATSC_OK;
-}
-
-// The device call.  Host work: covering intervals, pieces, the decode tasks of every piece (one per touched frame: its
-// covered samples' hull in the piece), the tile tasks (a full tile that windows cover past their first tile and before
-// their last one is reduced once, into a shared partial; every window's first and last tile are reduced for it alone)
-// and the combine passes (groups of 64 partials until one is left per window).  All of it goes up in one copy; then,
-// per piece, the window decode's launchers into scratch and k_agg_tiles, and k_agg_combine once per pass.
-// org: the stream index of the plan's first sample (a plan of the touched records only, in the host call): tiles lie at
-// multiples of AGG_TILE in the stream's index, not the plan's.  Indices below are the stream's unless named otherwise.
-static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
-                         const uint64_t *begin, const uint64_t *count, atsc_window_stats *d_stats, void *stream, uint64_t org)
-{
-    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_stats)))
-        return fail(ctx, ATSC_E_INVALID, "aggregate_windows: null argument");
-    if ((uintptr_t)d_stats & 7u) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: d_stats is not 8-byte aligned");
-    const uint64_t ns = dp->n_samples;
-    for (uint64_t i = 0; i < n_windows; ++i)
-        if (begin[i] > ns || count[i] > ns - begin[i]) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: window beyond the stream");
-    if (n_windows == 0) return ATSC_OK;
-    if (n_windows >= 0xffffffffull) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: more than 2^32 - 2 windows");
-    if (!launch_decompress_window || !launch_window_gather || !launch_agg_tiles || !launch_agg_combine)
-        return fail(ctx, ATSC_E_UNSUPPORTED, "aggregate_windows: no aggregate kernels");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const uint64_t T = AGG_TILE, W = n_windows;
-    // covering intervals: the union of the non-empty windows
-    std::vector<Span> cov;
-    for (uint64_t i = 0; i < W; ++i)
-        if (count[i]) cov.emplace_back(org + begin[i], org + begin[i] + count[i]);
-    std::sort(cov.begin(), cov.end());
-    {
-        size_t m = 0;
-        for (const auto &v : cov) {
-            if (m && v.first <= cov[m - 1].second) cov[m - 1].second = std::max(cov[m - 1].second, v.second);
-            else cov[m++] = v;
-        }
-        cov.resize(m);
-    }
-    const bool large = spans_touch_large(dp, org, cov);
-    // piece length: the budget less room for two large frames that cross the piece's ends
-    const uint64_t spill = large ? 2ull * MAX_FRAME : 0;
-    const uint64_t want = scratch_budget_samples(ctx, large);
-    const uint64_t piece_tiles = std::max<uint64_t>(AGG_MIN_PIECE, want > spill ? (want - spill) / T * T : 0) / T;
-    struct Piece {
-        uint64_t k0, k1;  // tiles [k0, k1): samples [k0 T, k1 T) at scratch[0, (k1 - k0) T)
-    };
-    std::vector<Piece> pcs;
-    uint64_t region_tiles = 0;
-    for (size_t a = 0; a < cov.size();) {
-        const uint64_t k0 = cov[a].first / T;
-        uint64_t k1 = (cov[a].second + T - 1) / T;
-        size_t z = a + 1;
-        while (z < cov.size() && cov[z].first / T < k1 + AGG_GAP_TILES) k1 = std::max(k1, (cov[z++].second + T - 1) / T);
-        for (uint64_t k = k0; k < k1; k += piece_tiles) {
-            pcs.push_back(Piece{k, std::min(k1, k + piece_tiles)});
-            region_tiles = std::max(region_tiles, pcs.back().k1 - k);
-        }
-        a = z;
-    }
-    const uint64_t region = region_tiles * T;
-    // shared full tiles: the tiles past a window's first and before its last, merged over the windows
-    std::vector<std::pair<uint64_t, uint64_t>> mids;
-    for (uint64_t i = 0; i < W; ++i) {
-        if (!count[i]) continue;
-        const uint64_t kb = (org + begin[i]) / T, ke = (org + begin[i] + count[i] - 1) / T;
-        if (ke >= kb + 2) mids.emplace_back(kb + 1, ke);
-    }
-    std::sort(mids.begin(), mids.end());
-    {
-        size_t m = 0;
-        for (const auto &v : mids) {
-            if (m && v.first <= mids[m - 1].second) mids[m - 1].second = std::max(mids[m - 1].second, v.second);
-            else mids[m++] = v;
-        }
-        mids.resize(m);
-    }
-    std::vector<uint64_t> mid_at(mids.size());
-    uint64_t U = 0;
-    for (size_t r = 0; r < mids.size(); ++r) { mid_at[r] = U; U += mids[r].second - mids[r].first; }
-    auto shared_index = [&](uint64_t k) {  // index of full tile k among the shared partials
-        const size_t r = (size_t)(std::upper_bound(mids.begin(), mids.end(), std::pair<uint64_t, uint64_t>(k, ~0ull)) - mids.begin()) - 1;
-        return mid_at[r] + (k - mids[r].first);
-    };
-    // tile tasks, by tile; part[] = [U shared | first, last tile of each window | combine levels]
-    struct TT {
-        uint64_t k;
-        DevAggTile t;
-    };
-    std::vector<TT> tt;
-    tt.reserve(U + 2 * W);
-    for (size_t r = 0; r < mids.size(); ++r)
-        for (uint64_t k = mids[r].first; k < mids[r].second; ++k)
-            tt.push_back(TT{k, DevAggTile{0, mid_at[r] + (k - mids[r].first), 0, (uint32_t)T, 0, 0}});
-    struct Lv {
-        uint64_t head, tail, mid, n;
-    };
-    std::vector<Lv> lv(W);
-    for (uint64_t i = 0; i < W; ++i) {
-        if (!count[i]) { lv[i] = Lv{0, 0, 0, 0}; continue; }
-        const uint64_t b = org + begin[i], e = b + count[i], kb = b / T, ke = (e - 1) / T;
-        tt.push_back(TT{kb, DevAggTile{0, U + 2 * i, (uint32_t)(b - kb * T), (uint32_t)(std::min(e, (kb + 1) * T) - kb * T),
-                                       (uint32_t)i, AGG_FIRST | (ke == kb ? AGG_LAST : 0u)}});
-        if (ke > kb) tt.push_back(TT{ke, DevAggTile{0, U + 2 * i + 1, 0, (uint32_t)(e - ke * T), (uint32_t)i, AGG_LAST}});
-        lv[i] = Lv{U + 2 * i, ke > kb ? U + 2 * i + 1 : U + 2 * i, ke >= kb + 2 ? shared_index(kb + 1) - 1 : 0, ke - kb + 1};
-    }
-    std::stable_sort(tt.begin(), tt.end(), [](const TT &x, const TT &y) { return x.k < y.k; });
-    // combine passes: groups of 64 entries of each window's list until one is left
-    uint64_t part_n = U + 2 * W;
-    std::vector<DevAggComb> comb;
-    std::vector<size_t> pass_at{0};
-    {
-        std::vector<uint32_t> live(W), next;
-        for (uint64_t i = 0; i < W; ++i) live[i] = (uint32_t)i;
-        while (!live.empty()) {
-            next.clear();
-            for (uint32_t i : live) {
-                Lv &l = lv[i];
-                const uint64_t G = std::max<uint64_t>(1, (l.n + 63) / 64);
-                if (G == 1) {
-                    comb.push_back(DevAggComb{l.head, l.tail, l.mid, i, (uint32_t)l.n, 0, i, 1});
-                    continue;
-                }
-                const uint64_t base = part_n;
-                part_n += G;
-                for (uint64_t g = 0; g < G; ++g) comb.push_back(DevAggComb{l.head, l.tail, l.mid, base + g, (uint32_t)l.n, (uint32_t)g, i, 0});
-                l = Lv{base, base + G - 1, base, G};
-                next.push_back(i);
-            }
-            pass_at.push_back(comb.size());
-            live.swap(next);
-        }
-    }
-    // decode tasks of every piece (emit_piece_decode) and its tile tasks
-    std::vector<PieceDecode> pdec(pcs.size());
-    std::vector<size_t> tile_at(pcs.size());
-    std::vector<uint32_t> tile_n(pcs.size());
-    DecodeTasks D;
-    std::vector<DevAggTile> tiles;
-    tiles.reserve(tt.size());
-    size_t ci = 0, ti = 0;
-    for (size_t p = 0; p < pcs.size(); ++p) {
-        tile_at[p] = tiles.size();
-        if (!emit_piece_decode(dp, org, cov, ci, pcs[p].k0 * T, pcs[p].k1 * T, region, D, pdec[p]))
-            return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (spill slots)");
-        for (; ti < tt.size() && tt[ti].k < pcs[p].k1; ++ti) {
-            DevAggTile t = tt[ti].t;
-            t.src = (tt[ti].k - pcs[p].k0) * T;
-            tiles.push_back(t);
-        }
-        tile_n[p] = (uint32_t)(tiles.size() - tile_at[p]);
-    }
-    if (ti != tt.size()) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (tile outside the pieces)");
-    // the previous call's tables, partials and scratch are reused once its work is done
-    if (dp->agg_pending) {
-        HIPCHK(ctx, hipEventSynchronize(dp->ev_agg));
-        dp->agg_pending = false;
-    }
-    // one upload: the decode tasks (place_decode_tasks), tile tasks, combine tasks; behind them (device only) the
-    // partials and the windows' first / last samples
-    auto al = upload_align;
-    size_t bytes = place_decode_tasks(D);
-    const size_t off_tiles = bytes;
-    bytes = al(bytes + tiles.size() * sizeof(DevAggTile));
-    const size_t off_comb = bytes;
-    bytes = al(bytes + comb.size() * sizeof(DevAggComb));
-    const size_t up_bytes = bytes, off_part = bytes;
-    bytes = al(bytes + part_n * sizeof(DevAggPart));
-    const size_t off_fl = bytes;
-    bytes = al(bytes + 2 * W * sizeof(double));
-    if (up_bytes > dp->agg_hcap) {
-        if (dp->h_agg) (void)hipHostFree(dp->h_agg);
-        dp->h_agg = nullptr;
-        dp->agg_hcap = 0;
-        const size_t cap = std::max<size_t>(up_bytes, 64u << 10);
-        HIPCHK(ctx, hipHostMalloc((void **)&dp->h_agg, cap, hipHostMallocDefault));
-        dp->agg_hcap = cap;
-    }
-    if (bytes > dp->agg_dcap) {
-        pool_free(ctx, dp->d_agg);
-        dp->d_agg = nullptr;
-        dp->agg_dcap = 0;
-        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_agg, bytes));
-        dp->agg_dcap = bytes;
-    }
-    const uint64_t scr_need = region + (uint64_t)MAX_FRAME * D.spills_used;
-    if (scr_need > dp->agg_scratch_cap) {
-        pool_free(ctx, dp->d_agg_scratch);
-        dp->d_agg_scratch = nullptr;
-        dp->agg_scratch_cap = 0;
-        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_agg_scratch, scr_need * sizeof(double)));
-        dp->agg_scratch_cap = scr_need;
-    }
-    if (!dp->ev_agg) HIPCHK(ctx, hipEventCreateWithFlags(&dp->ev_agg, hipEventDisableTiming));
-    unsigned char *h = dp->h_agg, *d = dp->d_agg;
-    stage_decode_tasks(D, h);
-    if (!tiles.empty()) memcpy(h + off_tiles, tiles.data(), tiles.size() * sizeof(DevAggTile));
-    memcpy(h + off_comb, comb.data(), comb.size() * sizeof(DevAggComb));
-    HIPCHK(ctx, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, s));
-    double *scr = dp->d_agg_scratch;
-    DevAggPart *part = (DevAggPart *)(d + off_part);
-    double *fl = (double *)(d + off_fl);
-    for (size_t p = 0; p < pcs.size(); ++p) {
-        const int rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, s, false);
-        if (rc) return rc;
-        const hipError_t e = launch_agg_tiles((const DevAggTile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, fl, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_agg_tiles", e);
-    }
-    for (size_t q = 0; q + 1 < pass_at.size(); ++q) {
-        const hipError_t e = launch_agg_combine((const DevAggComb *)(d + off_comb) + pass_at[q], (uint32_t)(pass_at[q + 1] - pass_at[q]),
-                                                part, fl, d_stats, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_agg_combine", e);
-    }
-    HIPCHK(ctx, hipEventRecord(dp->ev_agg, s));
-    dp->agg_pending = true;
-    return ATSC_OK;
-}
-extern "C" int atsc_aggregate_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
-                                          const uint64_t *begin, const uint64_t *count, atsc_window_stats *d_stats,
-                                          void *stream)
-{
-    ATSC_API_BEGIN
-    return aggregate_dev(ctx, dp, d_body, n_windows, begin, count, d_stats, stream, 0);
-    ATSC_API_END
-}
-
-// Host call: walks the headers from the first non-empty window's first record to the record holding the last window's
-// end, plans those records only and uploads only their bytes (atsc_decompress_window's path for a set of windows).
-extern "C" int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
-                                      const uint64_t *begin, const uint64_t *count, atsc_window_stats *out)
-{
-    ATSC_API_BEGIN
-    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: null argument");
-    if (n_windows == 0) return ATSC_OK;
-    uint64_t pos = 0, max_frames = ~0ull;
-    if (has_count) {
-        if (!host_varint(body, body_len, pos, max_frames)) return fail(ctx, ATSC_E_FORMAT, "aggregate_windows: frame count");
-        if (max_frames > body_len / 4) return fail(ctx, ATSC_E_FORMAT, "aggregate_windows: frame count exceeds the bytes present");
-    }
-    uint64_t B = ~0ull, E = 0;
-    for (uint64_t i = 0; i < n_windows; ++i) {
-        if (begin[i] + count[i] < begin[i]) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: window beyond the stream");
-        E = std::max(E, begin[i] + count[i]);
-        if (count[i]) B = std::min(B, begin[i]);
-    }
-    const bool any = B != ~0ull;
-    if (!any) B = E;  // only empty windows: the walk checks that each begins inside the stream
-    WindowWalk w;
-    int rc = window_walk(body, body_len, pos, max_frames, B, E - B, true, w);
-    if (rc) return fail(ctx, rc, rc == ATSC_E_INVALID ? "aggregate_windows: window beyond the stream" : "aggregate_windows: record walk");
-    if (!any) {
-        for (uint64_t i = 0; i < n_windows; ++i) agg_empty_record(out[i]);
-        return ATSC_OK;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->work_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->work_stream, hipStreamNonBlocking));
-    hipStream_t ws = ctx->work_stream;
-    const uint64_t slice = w.byte_end - w.byte_begin;
-    atsc_dplan *dp = nullptr;
-    rc = dplan_create_range(ctx, body + w.byte_begin, slice, 0, 0, ~0ull, nullptr, &dp);
-    if (rc) return rc;
-    if (dp->class_count[CLASS_LARGE]) {
-        // the large tier's launch forms from every large frame of the stream, as in atsc_decompress_window
-        DPlanHost Hw;
-        const char *why;
-        rc = dplan_parse(body, body_len, has_count, Hw, &why);
-        if (rc) { atsc_dplan_destroy(dp); return fail(ctx, rc, why); }
-        large_choices(dp, Hw.tabs.plans, Hw.frames, Hw.cls);
-    }
-    std::vector<uint64_t> b2(n_windows);
-    for (uint64_t i = 0; i < n_windows; ++i) b2[i] = count[i] ? begin[i] - w.sample_begin : 0;
-    uint8_t *d_body = nullptr;
-    atsc_window_stats *d_stats = nullptr;
-    int status = 0;
-    hipError_t e = hipSuccess;
-#define ACHK(call)                                                                 \
-    do {                                                                           \
-        e = (call);                                                                \
-        if (e != hipSuccess) { rc = fail(ctx, ATSC_E_HIP, #call, e); goto done; } \
-    } while (0)
-    ACHK(pool_alloc(ctx, (void **)&d_body, std::max<uint64_t>(slice, 16)));
-    ACHK(pool_alloc(ctx, (void **)&d_stats, n_windows * sizeof(atsc_window_stats)));
-    ACHK(hipMemcpyAsync(d_body, body + w.byte_begin, slice, hipMemcpyHostToDevice, ws));
-    rc = aggregate_dev(ctx, dp, d_body, n_windows, b2.data(), count, d_stats, ws, w.sample_begin);
-    if (rc) goto done;
-    ACHK(hipMemcpyAsync(&status, dp->d_status, sizeof(int), hipMemcpyDeviceToHost, ws));
-    ACHK(hipStreamSynchronize(ws));
-    if (status) { rc = fail(ctx, ATSC_E_FORMAT, "aggregate_windows: malformed payload"); goto done; }
-    ACHK(hipMemcpyAsync(out, d_stats, n_windows * sizeof(atsc_window_stats), hipMemcpyDeviceToHost, ws));
-    ACHK(hipStreamSynchronize(ws));
-#undef ACHK
-done:
-    if (rc) (void)hipStreamSynchronize(ws);
-    pool_free(ctx, d_body);
-    pool_free(ctx, d_stats);
-    atsc_dplan_destroy(dp);
-    return rc;
-    ATSC_API_END
-}
-
-// ------------------------------------------------------------------------------------------
-// windowed quantiles: exact order statistics of sample windows (atsc_quantile.hip)
-// ------------------------------------------------------------------------------------------
-static int quantile_check_levels(atsc_ctx *ctx, uint32_t n_q, const double *q, int method)
-{
-    if (!q) return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
-    if (n_q == 0 || n_q > QNT_MAX_LEVELS) return fail(ctx, ATSC_E_INVALID, "quantile_windows: n_q outside [1, 64]");
-    for (uint32_t j = 0; j < n_q; ++j)
-        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(ctx, ATSC_E_INVALID, "quantile_windows: a level is NaN or outside [0, 1]");
-    if (method < ATSC_QUANTILE_LINEAR || method > ATSC_QUANTILE_NEAREST)
-        return fail(ctx, ATSC_E_INVALID, "quantile_windows: unknown method");
-    return ATSC_OK;
-}
-
-// The device call.  Every window is held whole in scratch: the windows, by begin, go into pieces of at most L samples
-// (a piece starts at the first window not yet placed and takes every unplaced window that ends within L of that
-// start; pieces overlap where windows do).  Per piece: the decode tasks of its windows' union (emit_piece_decode), then
-// the tiers by window length: short and medium windows one launch each (medium: one per power-of-two key count), long
-// windows QNT_PASSES histogram + pick launches whatever their number.  Everything goes up in one copy; nothing waits
-// on the host between pieces.  org: the stream index of the plan's first sample (see aggregate_dev).
-static int quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
-                        const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
-                        double *d_out, void *stream, uint64_t org)
-{
-    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_out)))
-        return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
-    int rc = quantile_check_levels(ctx, n_q, q, method);
-    if (rc) return rc;
-    if ((uintptr_t)d_out & 7u) return fail(ctx, ATSC_E_INVALID, "quantile_windows: d_out is not 8-byte aligned");
-    const uint64_t ns = dp->n_samples;
-    for (uint64_t i = 0; i < n_windows; ++i)
-        if (begin[i] > ns || count[i] > ns - begin[i]) return fail(ctx, ATSC_E_INVALID, "quantile_windows: window beyond the stream");
-    if (n_windows == 0) return ATSC_OK;
-    if (n_windows >= 0xffffffffull) return fail(ctx, ATSC_E_INVALID, "quantile_windows: more than 2^32 - 2 windows");
-    if (!launch_decompress_window || !launch_window_gather || !launch_qnt_short || !launch_qnt_medium || !launch_qnt_hist ||
-        !launch_qnt_pick)
-        return fail(ctx, ATSC_E_UNSUPPORTED, "quantile_windows: no quantile kernels");
-    const uint64_t W = n_windows;
-    std::vector<uint32_t> ord;  // the non-empty windows by begin
-    std::vector<Span> cov;
-    for (uint64_t i = 0; i < W; ++i)
-        if (count[i]) { ord.push_back((uint32_t)i); cov.emplace_back(org + begin[i], org + begin[i] + count[i]); }
-    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return begin[a] < begin[b]; });
-    std::sort(cov.begin(), cov.end());
-    // piece length: the budget less room for two large frames that cross the piece's ends
-    const bool large = spans_touch_large(dp, org, cov);
-    const uint64_t spill = large ? 2ull * MAX_FRAME : 0;
-    const uint64_t want = scratch_budget_samples(ctx, large);
-    const uint64_t L = std::max<uint64_t>(AGG_MIN_PIECE, want > spill ? want - spill : 0);
-    for (uint32_t i : ord) {
-        if (count[i] <= L && count[i] < (1ull << 32)) continue;
-        char msg[192];
-        if (count[i] >= (1ull << 32))
-            snprintf(msg, sizeof msg, "quantile_windows: window %u holds %llu samples, more than 2^32 - 1", i,
-                     (unsigned long long)count[i]);
-        else
-            snprintf(msg, sizeof msg,
-                     "quantile_windows: window %u (%llu samples) does not fit one scratch piece; an aggregate scratch "
-                     "budget of %llu bytes would hold it", i, (unsigned long long)count[i],
-                     (unsigned long long)((count[i] + spill) * sizeof(double)));
-        return fail(ctx, ATSC_E_CAPACITY, msg);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // pieces: windows ord[w_at, w_at + w_n) of pw, samples [S0, S1) of the stream at scratch[0, S1 - S0)
-    struct Piece {
-        uint64_t S0, S1;
-        size_t w_at, w_n;
-    };
-    std::vector<Piece> pcs;
-    std::vector<uint32_t> pw;
-    pw.reserve(ord.size());
-    {
-        std::vector<char> placed(ord.size(), 0);
-        size_t a = 0;
-        while (a < ord.size()) {
-            Piece pc{org + begin[ord[a]], 0, pw.size(), 0};
-            pc.S1 = pc.S0;
-            for (size_t k = a; k < ord.size() && org + begin[ord[k]] < pc.S0 + L; ++k) {
-                const uint64_t e = org + begin[ord[k]] + count[ord[k]];
-                if (placed[k] || e > pc.S0 + L) continue;
-                placed[k] = 1;
-                pw.push_back(ord[k]);
-                pc.S1 = std::max(pc.S1, e);
-            }
-            pc.w_n = pw.size() - pc.w_at;
-            pcs.push_back(pc);
-            while (a < ord.size() && placed[a]) ++a;
-        }
-    }
-    uint64_t region = 0;
-    for (const Piece &pc : pcs) region = std::max(region, pc.S1 - pc.S0);
-    // per piece: decode tasks, then the windows by tier
-    const uint32_t n_med = 6;  // medium key counts 2^9 .. 2^14 (the ones up to QNT_MEDIUM_MAX are used)
-    struct PieceQ {
-        size_t short_at, med_at[n_med], long_at, chunk_at;
-        uint32_t short_n, med_n[n_med], long_n, chunk_n;
-    };
-    std::vector<PieceDecode> pdec(pcs.size());
-    std::vector<PieceQ> pq(pcs.size());
-    DecodeTasks D;
-    std::vector<DevQTask> shorts, meds, longs;
-    std::vector<DevQTask> med_class[n_med];
-    std::vector<DevQChunk> chunks;
-    uint32_t max_long = 0;
-    for (size_t p = 0; p < pcs.size(); ++p) {
-        const Piece &pc = pcs[p];
-        std::vector<Span> pcov;
-        for (size_t k = pc.w_at; k < pc.w_at + pc.w_n; ++k) {
-            const uint64_t b = org + begin[pw[k]], e = b + count[pw[k]];
-            if (!pcov.empty() && b <= pcov.back().second) pcov.back().second = std::max(pcov.back().second, e);
-            else pcov.emplace_back(b, e);
-        }
-        size_t ci = 0;
-        if (!emit_piece_decode(dp, org, pcov, ci, pc.S0, pc.S1, region, D, pdec[p]))
-            return fail(ctx, ATSC_E_INVALID, "quantile_windows: internal error (spill slots)");
-        PieceQ &t = pq[p];
-        t.short_at = shorts.size();
-        t.long_at = longs.size();
-        t.chunk_at = chunks.size();
-        for (uint32_t c = 0; c < n_med; ++c) med_class[c].clear();
-        for (size_t k = pc.w_at; k < pc.w_at + pc.w_n; ++k) {
-            const uint32_t i = pw[k];
-            const uint64_t src = org + begin[i] - pc.S0, n = count[i];
-            if (n <= QNT_SHORT_MAX) {
-                shorts.push_back(DevQTask{src, n, i, 0});
-            } else if (n <= QNT_MEDIUM_MAX) {
-                uint32_t c = 0;
-                while ((512ull << c) < n) ++c;
-                med_class[c].push_back(DevQTask{src, n, i, 0});
-            } else {
-                const uint32_t slot = (uint32_t)(longs.size() - t.long_at);
-                longs.push_back(DevQTask{src, n, i, slot});
-                for (uint64_t o = 0; o < n; o += QNT_CHUNK)
-                    chunks.push_back(DevQChunk{src + o, (uint32_t)std::min<uint64_t>(QNT_CHUNK, n - o), slot});
-            }
-        }
-        for (uint32_t c = 0; c < n_med; ++c) {
-            t.med_at[c] = meds.size();
-            t.med_n[c] = (uint32_t)med_class[c].size();
-            meds.insert(meds.end(), med_class[c].begin(), med_class[c].end());
-        }
-        t.short_n = (uint32_t)(shorts.size() - t.short_at);
-        t.long_n = (uint32_t)(longs.size() - t.long_at);
-        t.chunk_n = (uint32_t)(chunks.size() - t.chunk_at);
-        max_long = std::max(max_long, t.long_n);
-    }
-    // empty windows: NaN from the short tier, once
-    const size_t empty_at = shorts.size();
-    for (uint64_t i = 0; i < W; ++i)
-        if (!count[i]) shorts.push_back(DevQTask{0, 0, (uint32_t)i, 0});
-    const uint32_t empty_n = (uint32_t)(shorts.size() - empty_at);
-    // the previous call's tables and scratch are reused once its work is done
-    if (dp->qnt_pending) {
-        HIPCHK(ctx, hipEventSynchronize(dp->ev_qnt));
-        dp->qnt_pending = false;
-    }
-    // one upload: the decode tasks, the levels, the tiers' task lists, the chunks; behind them (device only) the long
-    // tier's state and counts
-    const uint32_t rows = 2 * n_q;
-    size_t bytes = place_decode_tasks(D);
-    const size_t off_q = bytes;
-    bytes = upload_align(bytes + n_q * sizeof(double));
-    const size_t off_short = bytes;
-    bytes = upload_align(bytes + shorts.size() * sizeof(DevQTask));
-    const size_t off_med = bytes;
-    bytes = upload_align(bytes + meds.size() * sizeof(DevQTask));
-    const size_t off_long = bytes;
-    bytes = upload_align(bytes + longs.size() * sizeof(DevQTask));
-    const size_t off_chunk = bytes;
-    bytes = upload_align(bytes + chunks.size() * sizeof(DevQChunk));
-    const size_t up_bytes = bytes, off_state = bytes;
-    bytes = upload_align(bytes + (size_t)max_long * sizeof(DevQState));
-    const size_t off_hist = bytes, hist_bytes = (size_t)max_long * rows * 256 * sizeof(uint32_t);
-    bytes = upload_align(bytes + hist_bytes);
-    if (up_bytes > dp->qnt_hcap) {
-        if (dp->h_qnt) (void)hipHostFree(dp->h_qnt);
-        dp->h_qnt = nullptr;
-        dp->qnt_hcap = 0;
-        const size_t cap = std::max<size_t>(up_bytes, 64u << 10);
-        HIPCHK(ctx, hipHostMalloc((void **)&dp->h_qnt, cap, hipHostMallocDefault));
-        dp->qnt_hcap = cap;
-    }
-    if (bytes > dp->qnt_dcap) {
-        pool_free(ctx, dp->d_qnt);
-        dp->d_qnt = nullptr;
-        dp->qnt_dcap = 0;
-        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_qnt, bytes));
-        dp->qnt_dcap = bytes;
-    }
-    const uint64_t scr_need = std::max<uint64_t>(1, region + (uint64_t)MAX_FRAME * D.spills_used);
-    if (scr_need > dp->qnt_scratch_cap) {
-        pool_free(ctx, dp->d_qnt_scratch);
-        dp->d_qnt_scratch = nullptr;
-        dp->qnt_scratch_cap = 0;
-        HIPCHK(ctx, pool_alloc(ctx, (void **)&dp->d_qnt_scratch, scr_need * sizeof(double)));
-        dp->qnt_scratch_cap = scr_need;
-    }
-    if (!dp->ev_qnt) HIPCHK(ctx, hipEventCreateWithFlags(&dp->ev_qnt, hipEventDisableTiming));
-    unsigned char *h = dp->h_qnt, *d = dp->d_qnt;
-    stage_decode_tasks(D, h);
-    memcpy(h + off_q, q, n_q * sizeof(double));
-    if (!shorts.empty()) memcpy(h + off_short, shorts.data(), shorts.size() * sizeof(DevQTask));
-    if (!meds.empty()) memcpy(h + off_med, meds.data(), meds.size() * sizeof(DevQTask));
-    if (!longs.empty()) memcpy(h + off_long, longs.data(), longs.size() * sizeof(DevQTask));
-    if (!chunks.empty()) memcpy(h + off_chunk, chunks.data(), chunks.size() * sizeof(DevQChunk));
-    HIPCHK(ctx, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, s));
-    if (hist_bytes) HIPCHK(ctx, hipMemsetAsync(d + off_hist, 0, hist_bytes, s));  // k_qnt_pick clears what it reads
-    double *scr = dp->d_qnt_scratch;
-    const double *dq = (const double *)(d + off_q);
-    const DevQTask *d_short = (const DevQTask *)(d + off_short), *d_med = (const DevQTask *)(d + off_med),
-                   *d_long = (const DevQTask *)(d + off_long);
-    const DevQChunk *d_chunk = (const DevQChunk *)(d + off_chunk);
-    DevQState *st = (DevQState *)(d + off_state);
-    uint32_t *hist = (uint32_t *)(d + off_hist);
-    hipError_t e = launch_qnt_short(d_short + empty_at, empty_n, scr, dq, n_q, method, d_out, s);
-    if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_short", e);
-    for (size_t p = 0; p < pcs.size(); ++p) {
-        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, s, true);
-        if (rc) return rc;
-        const PieceQ &t = pq[p];
-        e = launch_qnt_short(d_short + t.short_at, t.short_n, scr, dq, n_q, method, d_out, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_short", e);
-        for (uint32_t c = 0; c < n_med; ++c) {
-            e = launch_qnt_medium(d_med + t.med_at[c], t.med_n[c], 512u << c, scr, dq, n_q, method, d_out, s);
-            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_medium", e);
-        }
-        if (!t.long_n) continue;
-        for (uint32_t pass = 0; pass < QNT_PASSES; ++pass) {
-            e = launch_qnt_hist(d_chunk + t.chunk_at, t.chunk_n, scr, st, hist, rows, pass, s);
-            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_hist", e);
-            e = launch_qnt_pick(d_long + t.long_at, t.long_n, st, hist, rows, pass, dq, n_q, method, d_out, s);
-            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_pick", e);
-        }
-    }
-    HIPCHK(ctx, hipEventRecord(dp->ev_qnt, s));
-    dp->qnt_pending = true;
-    return ATSC_OK;
-}
-extern "C" int atsc_quantile_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
-                                         const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q,
-                                         int method, double *d_out, void *stream)
-{
-    ATSC_API_BEGIN
-    return quantile_dev(ctx, dp, d_body, n_windows, begin, count, n_q, q, method, d_out, stream, 0);
-    ATSC_API_END
-}
-
-// Host call: atsc_aggregate_windows' path (the touched records only) into quantile_dev.
-extern "C" int atsc_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
-                                     const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
-                                     double *out)
-{
-    ATSC_API_BEGIN
-    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
-    int rc = quantile_check_levels(ctx, n_q, q, method);
-    if (rc) return rc;
-    if (n_windows == 0) return ATSC_OK;
-    uint64_t pos = 0, max_frames = ~0ull;
-    if (has_count) {
-        if (!host_varint(body, body_len, pos, max_frames)) return fail(ctx, ATSC_E_FORMAT, "quantile_windows: frame count");
-        if (max_frames > body_len / 4) return fail(ctx, ATSC_E_FORMAT, "quantile_windows: frame count exceeds the bytes present");
-    }
-    uint64_t B = ~0ull, E = 0;
-    for (uint64_t i = 0; i < n_windows; ++i) {
-        if (begin[i] + count[i] < begin[i]) return fail(ctx, ATSC_E_INVALID, "quantile_windows: window beyond the stream");
-        E = std::max(E, begin[i] + count[i]);
-        if (count[i]) B = std::min(B, begin[i]);
-    }
-    const bool any = B != ~0ull;
-    if (!any) B = E;  // only empty windows: the walk checks that each begins inside the stream
-    WindowWalk w;
-    rc = window_walk(body, body_len, pos, max_frames, B, E - B, true, w);
-    if (rc) return fail(ctx, rc, rc == ATSC_E_INVALID ? "quantile_windows: window beyond the stream" : "quantile_windows: record walk");
-    if (!any) {
-        for (uint64_t i = 0; i < n_windows * n_q; ++i) out[i] = std::numeric_limits<double>::quiet_NaN();
-        return ATSC_OK;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->work_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->work_stream, hipStreamNonBlocking));
-    hipStream_t ws = ctx->work_stream;
-    const uint64_t slice = w.byte_end - w.byte_begin;
-    atsc_dplan *dp = nullptr;
-    rc = dplan_create_range(ctx, body + w.byte_begin, slice, 0, 0, ~0ull, nullptr, &dp);
-    if (rc) return rc;
-    if (dp->class_count[CLASS_LARGE]) {
-        // the large tier's launch forms from every large frame of the stream, as in atsc_decompress_window
-        DPlanHost Hw;
-        const char *why;
-        rc = dplan_parse(body, body_len, has_count, Hw, &why);
-        if (rc) { atsc_dplan_destroy(dp); return fail(ctx, rc, why); }
-        large_choices(dp, Hw.tabs.plans, Hw.frames, Hw.cls);
-    }
-    std::vector<uint64_t> b2(n_windows);
-    for (uint64_t i = 0; i < n_windows; ++i) b2[i] = count[i] ? begin[i] - w.sample_begin : 0;
-    uint8_t *d_body = nullptr;
-    double *d_out = nullptr;
-    int status = 0;
-    hipError_t e = hipSuccess;
-#define QCHK(call)                                                                 \
-    do {                                                                           \
-        e = (call);                                                                \
-        if (e != hipSuccess) { rc = fail(ctx, ATSC_E_HIP, #call, e); goto done; } \
-    } while (0)
-    QCHK(pool_alloc(ctx, (void **)&d_body, std::max<uint64_t>(slice, 16)));
-    QCHK(pool_alloc(ctx, (void **)&d_out, n_windows * n_q * sizeof(double)));
-    QCHK(hipMemcpyAsync(d_body, body + w.byte_begin, slice, hipMemcpyHostToDevice, ws));
-    rc = quantile_dev(ctx, dp, d_body, n_windows, b2.data(), count, n_q, q, method, d_out, ws, w.sample_begin);
-    if (rc) goto done;
-    QCHK(hipMemcpyAsync(&status, dp->d_status, sizeof(int), hipMemcpyDeviceToHost, ws));
-    QCHK(hipStreamSynchronize(ws));
-    if (status) { rc = fail(ctx, ATSC_E_FORMAT, "quantile_windows: malformed payload"); goto done; }
-    QCHK(hipMemcpyAsync(out, d_out, n_windows * n_q * sizeof(double), hipMemcpyDeviceToHost, ws));
-    QCHK(hipStreamSynchronize(ws));
-#undef QCHK
-done:
-    if (rc) (void)hipStreamSynchronize(ws);
-    pool_free(ctx, d_body);
-    pool_free(ctx, d_out);
-    atsc_dplan_destroy(dp);
     return rc;
     ATSC_API_END
 }

@@ -3,6 +3,7 @@
 #include <stdint.h>
 #include <new>
 #include <stdexcept>
+#include <vector>
 
 namespace atsc {
 
@@ -301,10 +302,17 @@ bool big_release(void *p);  // true: p was a big_alloc block and has been taken 
 void big_trim();            // frees the kept block
 }  // namespace atsc
 
+// The records of a stream one behind the other (pending chunks compressed first) and the stream's context: what
+// the stream's window queries (atsc_windows.cpp) take from atsc_stream.cpp
+struct atsc_ctx;
+struct atsc_stream;
+namespace atsc {
+int stream_body(atsc_stream *s, std::vector<uint8_t> &body, atsc_ctx **ctx);
+}  // namespace atsc
+
 // atsc_compress_frames with the output allocated by the library once its length is known (*out: malloc'd,
 // head_room bytes left free in front of the records) and, when nonfinite != NULL, a device-side flag for NaN /
 // infinite samples (atsc_compress_data's clean_data check)
-struct atsc_ctx;
 extern "C" int atsc_internal_compress_frames_scan(atsc_ctx *ctx, const double *samples, const uint64_t *frame_off,
                                                   uint64_t n_frames, int compressor, int bounded, float max_error,
                                                   int sample_level, uint64_t head_room, uint8_t **out,

@@ -284,77 +284,16 @@ extern "C" int atsc_bro_scan(const uint8_t *bro, uint64_t len, uint64_t *n_frame
     ATSC_API_END
 }
 
-extern "C" int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uint64_t count, double **out, uint64_t *n)
+// The stream's records one behind the other, as its window queries read them (atsc_windows.cpp; pending chunks are
+// compressed first), and the context they run on.
+int atsc::stream_body(atsc_stream *s, std::vector<uint8_t> &body, atsc_ctx **ctx)
 {
-    ATSC_API_BEGIN
-    if (!s || !out || !n) return ATSC_E_INVALID;
-    *out = nullptr;
-    *n = 0;
-    int rc = flush(s);
+    const int rc = flush(s);
     if (rc) return rc;
-    std::vector<uint8_t> body;
+    *ctx = s->ctx;
     for (const Item &it : s->items) body.insert(body.end(), it.record.begin(), it.record.end());
-    if (body.empty()) {
-        if (begin != 0 || count != 0) return ATSC_E_INVALID;
-        *out = (double *)malloc(8);
-        return *out ? ATSC_OK : ATSC_E_NOMEM;
-    }
-    double *buf = (double *)atsc::big_alloc((count ? count : 1) * sizeof(double));
-    if (!buf) return ATSC_E_NOMEM;
-    uint64_t got = 0;
-    rc = atsc_decompress_window(s->ctx, body.data(), body.size(), 0, begin, count, buf, count, &got);
-    if (rc) {
-        atsc_free(buf);
-        return rc;
-    }
-    *out = buf;
-    *n = got;
     return ATSC_OK;
-    ATSC_API_END
 }
-
-extern "C" int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
-                                             atsc_window_stats *out)
-{
-    ATSC_API_BEGIN
-    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
-    int rc = flush(s);
-    if (rc) return rc;
-    std::vector<uint8_t> body;
-    for (const Item &it : s->items) body.insert(body.end(), it.record.begin(), it.record.end());
-    if (body.empty()) {  // no frame: only empty windows at 0
-        for (uint64_t i = 0; i < n_windows; ++i)
-            if (begin[i] != 0 || count[i] != 0) return ATSC_E_INVALID;
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        for (uint64_t i = 0; i < n_windows; ++i) out[i] = atsc_window_stats{0, nan, nan, 0.0, nan, nan};
-        return ATSC_OK;
-    }
-    return atsc_aggregate_windows(s->ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
-    ATSC_API_END
-}
-
-extern "C" int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
-                                            uint32_t n_q, const double *q, int method, double *out)
-{
-    ATSC_API_BEGIN
-    if (!s || !q || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
-    if (n_q == 0 || n_q > 64 || method < ATSC_QUANTILE_LINEAR || method > ATSC_QUANTILE_NEAREST) return ATSC_E_INVALID;
-    for (uint32_t j = 0; j < n_q; ++j)
-        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return ATSC_E_INVALID;
-    int rc = flush(s);
-    if (rc) return rc;
-    std::vector<uint8_t> body;
-    for (const Item &it : s->items) body.insert(body.end(), it.record.begin(), it.record.end());
-    if (body.empty()) {  // no frame: only empty windows at 0
-        for (uint64_t i = 0; i < n_windows; ++i)
-            if (begin[i] != 0 || count[i] != 0) return ATSC_E_INVALID;
-        for (uint64_t i = 0; i < n_windows * n_q; ++i) out[i] = std::numeric_limits<double>::quiet_NaN();
-        return ATSC_OK;
-    }
-    return atsc_quantile_windows(s->ctx, body.data(), body.size(), 0, n_windows, begin, count, n_q, q, method, out);
-    ATSC_API_END
-}
-
 extern "C" int atsc_stream_decompress(atsc_stream *s, double **out, uint64_t *n)
 {
     ATSC_API_BEGIN

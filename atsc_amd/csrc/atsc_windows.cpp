@@ -1,0 +1,1110 @@
+// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates and quantiles of ranges of the decoded
+// stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
+// stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
+// queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
+// scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
+// and the pool are atsc_host.cpp's (atsc_host_private.h); nothing in atsc_host.cpp or atsc_stream.cpp calls into this file.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <numeric>
+
+#include "atsc_host_private.h"
+
+namespace atsc {
+// (weak: the sanitizer build of the host sources, tests/asan, links without the window kernels and never decodes a window)
+__attribute__((weak)) hipError_t launch_decompress_window(const DevDFrame *frames, const DevWTask *tasks, int cls,
+                                                          uint32_t count, uint32_t lds, const DevPlan *plans,
+                                                          const float2 *twpool, const uint8_t *body, double *out,
+                                                          int *status, hipStream_t s);
+__attribute__((weak)) hipError_t launch_window_gather(const DevWGather *g, uint32_t n, uint32_t max_len,
+                                                      const double *scratch, double *out, hipStream_t s);
+// the windowed aggregates' reduce kernels (atsc_aggregate.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_agg_tiles(const DevAggTile *tasks, uint32_t n, const double *scratch,
+                                                  DevAggPart *part, double *fl, hipStream_t s);
+__attribute__((weak)) hipError_t launch_agg_combine(const DevAggComb *tasks, uint32_t n, DevAggPart *part,
+                                                    const double *fl, void *stats, hipStream_t s);
+// the windowed quantiles' selection kernels (atsc_quantile.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_qnt_short(const DevQTask *tasks, uint32_t n, const double *scratch, const double *q,
+                                                  uint32_t n_q, int method, double *out, hipStream_t s);
+__attribute__((weak)) hipError_t launch_qnt_medium(const DevQTask *tasks, uint32_t n, uint32_t P, const double *scratch,
+                                                   const double *q, uint32_t n_q, int method, double *out, hipStream_t s);
+__attribute__((weak)) hipError_t launch_qnt_hist(const DevQChunk *chunks, uint32_t n, const double *scratch,
+                                                 const DevQState *st, uint32_t *hist, uint32_t rows, uint32_t pass,
+                                                 hipStream_t s);
+__attribute__((weak)) hipError_t launch_qnt_pick(const DevQTask *tasks, uint32_t n, DevQState *st, uint32_t *hist,
+                                                 uint32_t rows, uint32_t pass, const double *q, uint32_t n_q, int method,
+                                                 double *out, hipStream_t s);
+}  // namespace atsc
+
+using namespace atsc;
+
+// "<call>: <what>"
+static int fail_in(atsc_ctx *ctx, int rc, const char *call, const char *what, hipError_t e = hipSuccess)
+{
+    return fail(ctx, rc, (std::string(call) + ": " + what).c_str(), e);
+}
+
+// ------------------------------------------------------------------------------------------
+// the record walk of a window, and where a window lies in a stream or a plan
+// ------------------------------------------------------------------------------------------
+// The record walk of a window read over untrusted bytes: from `pos`, at most max_frames records, with the header checks
+// of atsc_bro_scan, up to the record that holds sample begin + count - 1 (count == 0: the record that holds `begin`).
+// A Noop record counts the samples it stores (noop.rs:79-83), as the decoder does.  decode: the frame-length checks of
+// dplan_parse as well (a frame the decoders cannot take).  ATSC_E_INVALID when the stream ends in front of the window's end.
+struct WindowWalk {
+    uint64_t byte_begin = 0, byte_end = 0, frame_begin = 0, frame_end = 0, sample_begin = 0;
+};
+static int window_walk(const uint8_t *b, uint64_t len, uint64_t pos, uint64_t max_frames, uint64_t begin, uint64_t count,
+                       bool decode, WindowWalk &w)
+{
+    if (begin + count < begin) return ATSC_E_INVALID;
+    const uint64_t end = begin + count;
+    uint64_t s_off = 0, f = 0;
+    bool found = false;
+    for (; max_frames == ~0ull ? pos < len : f < max_frames; ++f) {
+        HostRecord hr;
+        if (!host_next_record(b, len, pos, hr)) return ATSC_E_FORMAT;
+        if (hr.tag > 6 || hr.tag == ATSC_AUTO) return ATSC_E_FORMAT;
+        uint64_t n = hr.sample_count;
+        if (hr.tag == ATSC_NOOP) {
+            uint64_t q = hr.payload_off + 1, cnt = 0;
+            if (hr.payload_len < 2 || !host_varint(b, hr.payload_off + hr.payload_len, q, cnt) || cnt > hr.payload_len)
+                return ATSC_E_FORMAT;
+            n = cnt;
+        }
+        if (decode && n == 0) return ATSC_E_FORMAT;
+        if (decode && n > MAX_FRAME) return ATSC_E_UNSUPPORTED;
+        if (s_off + n < s_off) return ATSC_E_FORMAT;
+        if (!found && s_off + n > begin) {
+            found = true;
+            w.frame_begin = f;
+            w.byte_begin = hr.start;
+            w.sample_begin = s_off;
+            if (count == 0) {
+                w.frame_end = f;
+                w.byte_end = hr.start;
+                return ATSC_OK;
+            }
+        }
+        s_off += n;
+        if (found && s_off >= end) {
+            w.frame_end = f + 1;
+            w.byte_end = pos;
+            return ATSC_OK;
+        }
+    }
+    if (count == 0 && begin == s_off) {  // the empty window at the stream's end
+        w.frame_begin = w.frame_end = f;
+        w.byte_begin = w.byte_end = pos;
+        w.sample_begin = s_off;
+        return ATSC_OK;
+    }
+    return ATSC_E_INVALID;
+}
+
+extern "C" int atsc_bro_find_window(const uint8_t *bro, uint64_t len, uint64_t begin, uint64_t count,
+                                    uint64_t *byte_begin, uint64_t *byte_end, uint64_t *frame_begin, uint64_t *frame_end,
+                                    uint64_t *sample_begin)
+{
+    ATSC_API_BEGIN
+    if (!bro) return ATSC_E_INVALID;
+    uint64_t pos = 0, nf = 0;
+    int rc = atsc_bro_open(bro, len, &pos, &nf);
+    if (rc) return rc;
+    if (nf > len / 4) return ATSC_E_FORMAT;
+    WindowWalk w;
+    rc = window_walk(bro, len, pos, nf, begin, count, false, w);
+    if (rc) return rc;
+    if (byte_begin) *byte_begin = w.byte_begin;
+    if (byte_end) *byte_end = w.byte_end;
+    if (frame_begin) *frame_begin = w.frame_begin;
+    if (frame_end) *frame_end = w.frame_end;
+    if (sample_begin) *sample_begin = w.sample_begin;
+    return ATSC_OK;
+    ATSC_API_END
+}
+
+extern "C" int atsc_dplan_find_frames(const atsc_dplan *dp, uint64_t begin, uint64_t count, uint64_t *frame_begin,
+                                      uint64_t *frame_end)
+{
+    if (!dp || !frame_begin || !frame_end) return ATSC_E_INVALID;
+    if (begin > dp->n_samples || count > dp->n_samples - begin) return ATSC_E_INVALID;
+    const auto &F = dp->h_frames;
+    auto by_off = [](uint64_t v, const DevDFrame &d) { return v < d.out_off; };
+    // the frame holding `begin` (every frame holds at least one sample), or n_frames at the stream's end
+    const uint64_t fb = (uint64_t)(std::upper_bound(F.begin(), F.end(), begin, by_off) - F.begin()) - 1;
+    *frame_begin = begin == dp->n_samples ? F.size() : fb;
+    *frame_end = count == 0 ? *frame_begin
+                            : (uint64_t)(std::upper_bound(F.begin(), F.end(), begin + count - 1, by_off) - F.begin());
+    return ATSC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// what a device call holds on its plan, and its one upload
+// ------------------------------------------------------------------------------------------
+static size_t upload_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The layout of a device call's tables: each at a multiple of 256 bytes, first the ones that go up in the call's one
+// copy (add), behind them the ones that only the kernels write and read (device_only).  Both hand back the table's
+// offset.  The tables' memory must stay where it is until stage() has copied it.
+struct Upload {
+    struct Table {
+        size_t off;
+        const void *src;
+        size_t bytes;
+    };
+    std::vector<Table> tables;
+    size_t up_bytes = 0, bytes = 0;
+    Upload() { tables.reserve(16); }
+    size_t add(const void *src, size_t n)
+    {
+        const size_t off = bytes;
+        tables.push_back(Table{off, src, n});
+        up_bytes = bytes = upload_align(bytes + n);
+        return off;
+    }
+    template <class T>
+    size_t add(const std::vector<T> &v)
+    {
+        return add(v.data(), v.size() * sizeof(T));
+    }
+    size_t device_only(size_t n)
+    {
+        const size_t off = bytes;
+        bytes = upload_align(bytes + n);
+        return off;
+    }
+    void stage(unsigned char *h) const
+    {
+        for (const Table &t : tables)
+            if (t.bytes) memcpy(h + t.off, t.src, t.bytes);
+    }
+};
+
+// ------------------------------------------------------------------------------------------
+// decode tasks: frames, or parts of frames, decoded to where a query wants them
+// ------------------------------------------------------------------------------------------
+using Span = std::pair<uint64_t, uint64_t>;
+
+// The interval merge: `last` takes in x, which begins at or behind last's begin, when they overlap or touch.
+static bool absorb_span(Span &last, const Span &x)
+{
+    if (x.first > last.second) return false;
+    last.second = std::max(last.second, x.second);
+    return true;
+}
+// sorts the intervals and merges them in place
+static void merge_spans(std::vector<Span> &v)
+{
+    if (!std::is_sorted(v.begin(), v.end())) std::sort(v.begin(), v.end());
+    size_t m = 0;
+    for (const Span &x : v)
+        if (!m || !absorb_span(v[m - 1], x)) v[m++] = x;
+    v.resize(m);
+}
+
+// the decode tasks of all pieces of one call, and their place in the call's upload
+struct DecodeTasks {
+    std::vector<DevWTask> small[CLASS_LARGE];
+    std::vector<DevDFrame> big;
+    std::vector<DevWGather> gat;
+    std::vector<uint32_t> ids;  // 0 .. max_big - 1: every piece's large sub-plan is launched in the order of its frames
+    uint32_t max_big = 0, spills_used = 0;
+    size_t off_small[CLASS_LARGE] = {}, off_big = 0, off_ids = 0, off_gat = 0;
+    // per class the pieces' task lists, the large sub-plans, ids 0.., copies
+    void place(Upload &U)
+    {
+        for (int c = 0; c < CLASS_LARGE; ++c) off_small[c] = U.add(small[c]);
+        off_big = U.add(big);
+        ids.resize(max_big);
+        std::iota(ids.begin(), ids.end(), 0u);
+        off_ids = U.add(ids);
+        off_gat = U.add(gat);
+    }
+};
+// one piece's run of them
+struct PieceDecode {
+    size_t small_at[CLASS_LARGE], big_at, gat_at;
+    uint32_t small_n[CLASS_LARGE], big_n, gat_n, max_len;
+};
+
+// the messages of a failed launch, by caller
+struct DecodeCaller {
+    const char *small, *large, *gather;
+};
+static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
+                                       "launch k_window_gather"};
+static const DecodeCaller BY_AGGREGATE = {"launch k_decompress (aggregate)", "launch k_decompress_large (aggregate)",
+                                          "launch k_window_gather (aggregate)"};
+static const DecodeCaller BY_QUANTILE = {"launch k_decompress (quantile)", "launch k_decompress_large (quantile)",
+                                         "launch k_window_gather (quantile)"};
+
+// Enqueues one piece's decode (d: the device copy of the upload).  out: the base the tasks' destinations count from;
+// the copies go from gat_src to gat_dst.
+static int launch_piece_decode(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, const unsigned char *d,
+                               const DecodeTasks &D, const PieceDecode &pt, double *out, const double *gat_src,
+                               double *gat_dst, hipStream_t s, const DecodeCaller &who)
+{
+    for (int c = 0; c < CLASS_LARGE; ++c) {
+        if (!pt.small_n[c]) continue;
+        const hipError_t e = launch_decompress_window(dp->d_frames, (const DevWTask *)(d + D.off_small[c]) + pt.small_at[c], c,
+                                                      pt.small_n[c], dp->class_lds[c], dp->tabs.d_plans, dp->tabs.d_tw,
+                                                      d_body, out, dp->d_status, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, who.small, e);
+    }
+    if (pt.big_n) {
+        const hipError_t e = launch_decompress_large(
+            pt.big_n, (const DevDFrame *)(d + D.off_big) + pt.big_at, (const uint32_t *)(d + D.off_ids), dp->tabs.d_plans,
+            dp->tabs.d_tw, d_body, out, dp->d_status, dp->d_ws, dp->ws_stride, dp->ws_slots, dp->large_tiled ? 1 : 0,
+            large_sparse() ? 1 : 0, s, dp->large_pre.tiles1 ? &dp->large_pre : nullptr,
+            // the (tile, frame) split of the sparse inverse runs for launches of up to LARGE_SPLIT_MAX frames: a window
+            // launch of fewer frames than its plan's full decode takes the full decode's side of that line
+            dp->large_choice_count <= LARGE_SPLIT_MAX ? dp->large_sp_tiles : 0);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, who.large, e);
+    }
+    if (pt.gat_n) {
+        const hipError_t e = launch_window_gather((const DevWGather *)(d + D.off_gat) + pt.gat_at, pt.gat_n, pt.max_len,
+                                                  gat_src, gat_dst, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, who.gather, e);
+    }
+    return ATSC_OK;
+}
+
+// What every device call checks of its result pointer and its windows; `call` names the caller in the message.
+// max_windows: the most windows the call's tasks can name (~0ull: no limit).
+static int check_windows(atsc_ctx *ctx, const char *call, const atsc_dplan *dp, const void *d_res, const char *res_name,
+                         uint64_t n_windows, const uint64_t *begin, const uint64_t *count, uint64_t max_windows)
+{
+    if ((uintptr_t)d_res & 7u) return fail_in(ctx, ATSC_E_INVALID, call, (std::string(res_name) + " is not 8-byte aligned").c_str());
+    const uint64_t ns = dp->n_samples;
+    for (uint64_t i = 0; i < n_windows; ++i)
+        if (begin[i] > ns || count[i] > ns - begin[i]) return fail_in(ctx, ATSC_E_INVALID, call, "window beyond the stream");
+    if (n_windows > max_windows) return fail_in(ctx, ATSC_E_INVALID, call, "more than 2^32 - 2 windows");
+    return ATSC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the host call of a query: the touched records only
+// ------------------------------------------------------------------------------------------
+// Walks the headers from the first non-empty window's first record to the record that holds the last window's end,
+// plans those records only and uploads only their bytes; the result comes back once the payloads proved well-formed (a
+// malformed one leaves `out` untouched).  `call` names the caller in the messages.  The caller's two steps:
+//   located(any)  after the walk, which is what rejects a window beyond the stream: the caller's own checks, and its
+//                 result when every window is empty (any == false: the call ends there);
+//   enqueue(dp, d_body, begin2, d_res, stream, org)  its device call on the range plan, whose first sample is sample
+//                 `org` of the stream; begin2: the windows' begins counted from there.
+// trace: the ATSC_TRACE_HOST line of the upload.
+template <class Located, class Enqueue>
+static int window_host_call(atsc_ctx *ctx, const char *call, const uint8_t *body, uint64_t body_len, int has_count,
+                            uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *out, size_t out_bytes,
+                            bool trace, Located located, Enqueue enqueue)
+{
+    uint64_t pos = 0, max_frames = ~0ull;
+    if (has_count) {
+        if (!host_varint(body, body_len, pos, max_frames)) return fail_in(ctx, ATSC_E_FORMAT, call, "frame count");
+        if (max_frames > body_len / 4) return fail_in(ctx, ATSC_E_FORMAT, call, "frame count exceeds the bytes present");
+    }
+    uint64_t B = ~0ull, E = 0;
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        if (begin[i] + count[i] < begin[i]) return fail_in(ctx, ATSC_E_INVALID, call, "window beyond the stream");
+        E = std::max(E, begin[i] + count[i]);
+        if (count[i]) B = std::min(B, begin[i]);
+    }
+    const bool any = B != ~0ull;
+    if (!any) B = E;  // only empty windows: the walk checks that each begins inside the stream
+    WindowWalk w;
+    int rc = window_walk(body, body_len, pos, max_frames, B, E - B, true, w);
+    if (rc) return fail_in(ctx, rc, call, rc == ATSC_E_INVALID ? "window beyond the stream" : "record walk");
+    rc = located(any);
+    if (rc || !any) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->work_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->work_stream, hipStreamNonBlocking));
+    hipStream_t ws = ctx->work_stream;
+    const uint64_t slice = w.byte_end - w.byte_begin;
+    atsc_dplan *dp = nullptr;
+    rc = dplan_create_range(ctx, body + w.byte_begin, slice, 0, 0, ~0ull, nullptr, &dp);
+    if (rc) return rc;
+    std::vector<uint64_t> begin2(n_windows);
+    for (uint64_t i = 0; i < n_windows; ++i) begin2[i] = count[i] ? begin[i] - w.sample_begin : 0;
+    uint8_t *d_body = nullptr;
+    void *d_res = nullptr;
+    int status = 0;
+    hipError_t e = hipSuccess;
+#define WCHK(call_)                                                                 \
+    do {                                                                            \
+        e = (call_);                                                                \
+        if (e != hipSuccess) { rc = fail(ctx, ATSC_E_HIP, #call_, e); goto done; } \
+    } while (0)
+    if (dp->class_count[CLASS_LARGE]) {
+        // The large tier's launch forms depend on every large frame of the stream (large_choices): the rest of the
+        // record headers is walked as well, so that the touched large frames decode as the full decode does them.
+        DPlanHost Hw;
+        const char *why;
+        rc = dplan_parse(body, body_len, has_count, Hw, &why);
+        if (rc) { rc = fail(ctx, rc, why); goto done; }
+        large_choices(dp, Hw.tabs.plans, Hw.frames, Hw.cls);
+    }
+    WCHK(pool_alloc(ctx, (void **)&d_body, std::max<uint64_t>(slice, 16)));
+    WCHK(pool_alloc(ctx, &d_res, out_bytes));
+    WCHK(hipMemcpyAsync(d_body, body + w.byte_begin, slice, hipMemcpyHostToDevice, ws));
+    if (trace) fprintf(stderr, "[window]     h2d records %llu bytes (frames %llu..%llu)\n", (unsigned long long)slice,
+                       (unsigned long long)w.frame_begin, (unsigned long long)w.frame_end);
+    rc = enqueue(dp, d_body, begin2.data(), d_res, ws, w.sample_begin);
+    if (rc) goto done;
+    WCHK(hipMemcpyAsync(&status, dp->d_status, sizeof(int), hipMemcpyDeviceToHost, ws));
+    WCHK(hipStreamSynchronize(ws));
+    if (status) { rc = fail_in(ctx, ATSC_E_FORMAT, call, "malformed payload"); goto done; }
+    WCHK(hipMemcpyAsync(out, d_res, out_bytes, hipMemcpyDeviceToHost, ws));
+    WCHK(hipStreamSynchronize(ws));
+#undef WCHK
+done:
+    if (rc) (void)hipStreamSynchronize(ws);
+    pool_free(ctx, d_body);
+    pool_free(ctx, d_res);
+    atsc_dplan_destroy(dp);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// window decode: samples [begin, begin + count) of the decoded stream without decoding the rest
+// ------------------------------------------------------------------------------------------
+// The window decode.  One task per (window, touched frame); tasks go by frame:
+//  * a frame of the LDS-resident classes that one window touches: k_decompress<W, SPL, true> straight into d_out;
+//  * one that several windows touch: decoded once, over the union of their ranges, into scratch;
+//  * a large frame: the large tier's launch sequence over a sub-plan of the touched large frames -- one that a window
+//    holds whole is written straight into d_out (its out_off rebased), the others go to scratch whole;
+//  * k_window_gather then copies the scratch parts to their windows.
+// A destination in scratch is named by its distance from d_out in doubles, modulo 2^64: one base pointer serves both.
+extern "C" int atsc_decompress_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                           const uint64_t *begin, const uint64_t *count, const uint64_t *out_off,
+                                           double *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !dp || !d_body || !d_out || (n_windows && (!begin || !count || !out_off)))
+        return fail(ctx, ATSC_E_INVALID, "decompress_windows: null argument");
+    int rc = check_windows(ctx, "decompress_windows", dp, d_out, "d_out", n_windows, begin, count, ~0ull);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const auto &F = dp->h_frames;
+    struct Ent {
+        uint64_t dst;
+        uint32_t frame, lo, hi;
+    };
+    std::vector<Ent> ents;
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        if (!count[i]) continue;
+        uint64_t fb, fe;
+        (void)atsc_dplan_find_frames(dp, begin[i], count[i], &fb, &fe);
+        const uint64_t b = begin[i], e = begin[i] + count[i];
+        for (uint64_t f = fb; f < fe; ++f) {
+            const uint64_t fo = F[f].out_off, fn = F[f].n;
+            const uint64_t lo = std::max(b, fo) - fo, hi = std::min(e, fo + fn) - fo;
+            ents.push_back(Ent{out_off[i] + (fo + lo - b), (uint32_t)f, (uint32_t)lo, (uint32_t)hi});
+        }
+    }
+    if (ents.empty()) return ATSC_OK;
+    if (!launch_decompress_window || !launch_window_gather) return fail(ctx, ATSC_E_UNSUPPORTED, "decompress_windows: no window kernels");
+    auto by_frame = [](const Ent &a, const Ent &b) { return a.frame < b.frame; };
+    if (!std::is_sorted(ents.begin(), ents.end(), by_frame)) std::stable_sort(ents.begin(), ents.end(), by_frame);
+    QueryRes &R = dp->win;
+    HIPCHK(ctx, R.wait());
+    // one piece holds every task; destinations in scratch count from the scratch's start until it is known where it lies
+    DecodeTasks D;
+    std::vector<size_t> small_scr_at[CLASS_LARGE], big_scr;
+    uint64_t scr = 0;
+    uint32_t max_len = 0;
+    for (size_t a = 0; a < ents.size();) {
+        size_t z = a + 1;
+        while (z < ents.size() && ents[z].frame == ents[a].frame) ++z;
+        const uint32_t f = ents[a].frame, n = F[f].n;
+        const int c = dp->h_cls[f];
+        const bool one = z - a == 1;
+        if (c != CLASS_LARGE) {
+            if (one) {
+                D.small[c].push_back(DevWTask{ents[a].dst, f, ents[a].lo, ents[a].hi, 0});
+            } else {
+                uint32_t ulo = n, uhi = 0;
+                for (size_t k = a; k < z; ++k) { ulo = std::min(ulo, ents[k].lo); uhi = std::max(uhi, ents[k].hi); }
+                small_scr_at[c].push_back(D.small[c].size());
+                D.small[c].push_back(DevWTask{scr, f, ulo, uhi, 0});
+                for (size_t k = a; k < z; ++k) {
+                    D.gat.push_back(DevWGather{scr + ents[k].lo - ulo, ents[k].dst, ents[k].hi - ents[k].lo, 0});
+                    max_len = std::max(max_len, ents[k].hi - ents[k].lo);
+                }
+                scr += uhi - ulo;
+            }
+        } else {
+            DevDFrame d = F[f];
+            if (one && ents[a].lo == 0 && ents[a].hi == n) {
+                d.out_off = ents[a].dst;
+            } else {
+                big_scr.push_back(D.big.size());
+                d.out_off = scr;
+                for (size_t k = a; k < z; ++k) {
+                    D.gat.push_back(DevWGather{scr + ents[k].lo, ents[k].dst, ents[k].hi - ents[k].lo, 0});
+                    max_len = std::max(max_len, ents[k].hi - ents[k].lo);
+                }
+                scr += n;
+            }
+            D.big.push_back(d);
+        }
+        a = z;
+    }
+    PieceDecode pt;
+    for (int c = 0; c < CLASS_LARGE; ++c) { pt.small_at[c] = 0; pt.small_n[c] = (uint32_t)D.small[c].size(); }
+    pt.big_at = pt.gat_at = 0;
+    pt.big_n = D.max_big = (uint32_t)D.big.size();
+    pt.gat_n = (uint32_t)D.gat.size();
+    pt.max_len = max_len;
+    // one upload: the classes' task lists, the large sub-plan (frames, ids), the copies
+    Upload U;
+    D.place(U);
+    HIPCHK(ctx, R.reserve(ctx, U.up_bytes, U.bytes, scr));
+    if (scr) {
+        const uint64_t base = ((uint64_t)(uintptr_t)R.scratch - (uint64_t)(uintptr_t)d_out) / sizeof(double);
+        for (int c = 0; c < CLASS_LARGE; ++c)
+            for (size_t i : small_scr_at[c]) D.small[c][i].dst += base;
+        for (size_t i : big_scr) D.big[i].out_off += base;
+    }
+    U.stage(R.h);
+    HIPCHK(ctx, hipMemcpyAsync(R.d, R.h, U.up_bytes, hipMemcpyHostToDevice, s));
+    rc = launch_piece_decode(ctx, dp, d_body, R.d, D, pt, d_out, R.scratch, d_out, s, BY_WINDOW);
+    if (rc) return rc;
+    HIPCHK(ctx, R.record(s));
+    return ATSC_OK;
+    ATSC_API_END
+}
+
+// Host call: walks the headers up to the window's last record, plans the touched records only and uploads only their bytes.
+extern "C" int atsc_decompress_window(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t begin,
+                                      uint64_t count, double *out, uint64_t out_cap, uint64_t *out_n)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body || !out_n || (count && !out)) return fail(ctx, ATSC_E_INVALID, "decompress_window: null argument");
+    *out_n = 0;
+    static const bool trace = getenv("ATSC_TRACE_HOST") != nullptr;
+    const uint64_t zero = 0;
+    const int rc = window_host_call(
+        ctx, "decompress_window", body, body_len, has_count, 1, &begin, &count, out, count * sizeof(double), trace,
+        [&](bool) { return out_cap < count ? fail(ctx, ATSC_E_CAPACITY, "decompress_window: out_cap") : ATSC_OK; },
+        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t) {
+            return atsc_decompress_windows_dev(ctx, dp, d_body, 1, begin2, &count, &zero, (double *)d_res, ws);
+        });
+    if (!rc) *out_n = count;
+    return rc;
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
+// decoded samples of window pieces in scratch (the aggregate and the quantile calls)
+// ------------------------------------------------------------------------------------------
+// Decoded samples reach the reduce and selection kernels through one scratch region, piece after piece in stream order.
+static const uint64_t AGG_MIN_PIECE = 32ull * AGG_TILE;  // the least a piece holds, whatever the budget
+// default piece length (samples) by the tier of the touched frames.  The sweep of profiles/aggregate_probe.json found no
+// gain from pieces that fit the Infinity Cache (2^21-2^22 samples): fewer pieces win in both framings, most where the
+// large tier's launch sequence (~65 us whatever its frame count) runs once per piece.
+static const uint64_t AGG_PIECE_SMALL = 1ull << 24;
+static const uint64_t AGG_PIECE_LARGE = 1ull << 24;
+
+extern "C" int atsc_ctx_set_aggregate_scratch(atsc_ctx *ctx, uint64_t bytes)
+{
+    if (!ctx) return ATSC_E_INVALID;
+    ctx->agg_budget = bytes;
+    return ATSC_OK;
+}
+
+// the decoded samples a call's scratch may hold: the context's budget, else the default piece and room for two large
+// frames cut by its ends
+static uint64_t scratch_budget_samples(const atsc_ctx *ctx, bool large)
+{
+    return ctx->agg_budget ? ctx->agg_budget / sizeof(double)
+                           : (large ? AGG_PIECE_LARGE + 2ull * MAX_FRAME : AGG_PIECE_SMALL);
+}
+
+// whether the covering intervals (stream index; org: the plan's first sample) touch a large frame
+static bool spans_touch_large(const atsc_dplan *dp, uint64_t org, const std::vector<Span> &cov)
+{
+    for (const Span &c : cov) {
+        uint64_t fb, fe;
+        (void)atsc_dplan_find_frames(dp, c.first - org, c.second - c.first, &fb, &fe);
+        for (uint64_t f = fb; f < fe; ++f)
+            if (dp->h_cls[f] == CLASS_LARGE) return true;
+    }
+    return false;
+}
+
+// Piece length in samples, a multiple of `unit`: the budget less *spill, the room for two large frames that cross the
+// piece's ends (none when the covering intervals touch no large frame), and at least AGG_MIN_PIECE.
+static uint64_t piece_samples(const atsc_ctx *ctx, const atsc_dplan *dp, uint64_t org, const std::vector<Span> &cov,
+                              uint64_t unit, uint64_t *spill)
+{
+    const bool large = spans_touch_large(dp, org, cov);
+    *spill = large ? 2ull * MAX_FRAME : 0;
+    const uint64_t want = scratch_budget_samples(ctx, large);
+    return std::max<uint64_t>(AGG_MIN_PIECE, want > *spill ? (want - *spill) / unit * unit : 0);
+}
+
+// The decode tasks of the piece [S0, S1) into scratch[0, S1 - S0): per touched frame, the hull of its covered samples
+// inside the piece.  cov: ascending disjoint covering intervals, *ci the first that may still meet the piece (advanced
+// past those that end before it).  A large frame is decoded whole: in place when it lies inside the piece, else into
+// one of two spill slots behind the region (scratch[region + MAX_FRAME k]) and copied from there (k_window_gather).
+// false: more than two spill slots (only the frames across S0 and S1 can stick out).
+static bool emit_piece_decode(const atsc_dplan *dp, uint64_t org, const std::vector<Span> &cov, size_t &ci, uint64_t S0,
+                              uint64_t S1, uint64_t region, DecodeTasks &D, PieceDecode &pt)
+{
+    const auto &F = dp->h_frames;
+    for (int c = 0; c < CLASS_LARGE; ++c) pt.small_at[c] = D.small[c].size();
+    pt.big_at = D.big.size();
+    pt.gat_at = D.gat.size();
+    pt.max_len = 0;
+    uint32_t n_spill = 0;
+    auto emit = [&](uint64_t f, uint64_t lo, uint64_t hi) {
+        const uint64_t fo = org + F[f].out_off, fn = F[f].n;
+        const int c = dp->h_cls[f];
+        if (c != CLASS_LARGE) {
+            D.small[c].push_back(DevWTask{fo + lo - S0, (uint32_t)f, (uint32_t)lo, (uint32_t)hi, 0});
+            return;
+        }
+        DevDFrame d = F[f];
+        if (fo >= S0 && fo + fn <= S1) {
+            d.out_off = fo - S0;
+        } else {
+            const uint64_t sp = region + (uint64_t)MAX_FRAME * n_spill++;
+            d.out_off = sp;
+            D.gat.push_back(DevWGather{sp + lo, fo + lo - S0, (uint32_t)(hi - lo), 0});
+            pt.max_len = std::max(pt.max_len, (uint32_t)(hi - lo));
+        }
+        D.big.push_back(d);
+    };
+    while (ci < cov.size() && cov[ci].second <= S0) ++ci;
+    uint64_t hf = ~0ull, hlo = 0, hhi = 0;
+    for (size_t c = ci; c < cov.size() && cov[c].first < S1; ++c) {
+        const uint64_t a = std::max(cov[c].first, S0), z = std::min(cov[c].second, S1);
+        uint64_t fb, fe;
+        (void)atsc_dplan_find_frames(dp, a - org, z - a, &fb, &fe);
+        for (uint64_t f = fb; f < fe; ++f) {
+            const uint64_t fo = org + F[f].out_off, fn = F[f].n;
+            const uint64_t lo = std::max(a, fo) - fo, hi = std::min(z, fo + fn) - fo;
+            if (f == hf) { hhi = hi; continue; }
+            if (hf != ~0ull) emit(hf, hlo, hhi);
+            hf = f;
+            hlo = lo;
+            hhi = hi;
+        }
+    }
+    if (hf != ~0ull) emit(hf, hlo, hhi);
+    if (n_spill > 2) return false;
+    D.spills_used = std::max(D.spills_used, n_spill);
+    for (int c = 0; c < CLASS_LARGE; ++c) pt.small_n[c] = (uint32_t)(D.small[c].size() - pt.small_at[c]);
+    pt.big_n = (uint32_t)(D.big.size() - pt.big_at);
+    pt.gat_n = (uint32_t)(D.gat.size() - pt.gat_at);
+    D.max_big = std::max(D.max_big, pt.big_n);
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------
+// windowed aggregates: count / min / max / sum / first / last of sample windows (atsc_aggregate.hip)
+// ------------------------------------------------------------------------------------------
+// The scratch region holds whole tiles: the windows' union ("covering intervals") is cut into pieces at multiples of
+// AGG_TILE.  Covered tile ranges closer than AGG_GAP_TILES share a span, so that scattered windows do not each cost a
+// piece of launches.
+static const uint64_t AGG_GAP_TILES = 64;
+
+static void agg_empty_record(atsc_window_stats &r)
+{
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    r.count = 0;
+    r.min = r.max = r.first = r.last = nan;
+    r.sum = 0.0;
+}
+
+// The device call.  Host work: covering intervals, pieces, the decode tasks of every piece (one per touched frame: its
+// covered samples' hull in the piece), the tile tasks (a full tile that windows cover past their first tile and before
+// their last one is reduced once, into a shared partial; every window's first and last tile are reduced for it alone)
+// and the combine passes (groups of 64 partials until one is left per window).  All of it goes up in one copy; then,
+// per piece, the window decode's launchers into scratch and k_agg_tiles, and k_agg_combine once per pass.
+// org: the stream index of the plan's first sample (a plan of the touched records only, in the host call): tiles lie at
+// multiples of AGG_TILE in the stream's index, not the plan's.  Indices below are the stream's unless named otherwise.
+static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                         const uint64_t *begin, const uint64_t *count, atsc_window_stats *d_stats, void *stream, uint64_t org)
+{
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_stats)))
+        return fail(ctx, ATSC_E_INVALID, "aggregate_windows: null argument");
+    int rc = check_windows(ctx, "aggregate_windows", dp, d_stats, "d_stats", n_windows, begin, count, 0xfffffffeull);
+    if (rc || n_windows == 0) return rc;
+    if (!launch_decompress_window || !launch_window_gather || !launch_agg_tiles || !launch_agg_combine)
+        return fail(ctx, ATSC_E_UNSUPPORTED, "aggregate_windows: no aggregate kernels");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint64_t T = AGG_TILE, W = n_windows;
+    // covering intervals: the union of the non-empty windows
+    std::vector<Span> cov;
+    for (uint64_t i = 0; i < W; ++i)
+        if (count[i]) cov.emplace_back(org + begin[i], org + begin[i] + count[i]);
+    merge_spans(cov);
+    uint64_t spill;
+    const uint64_t piece_tiles = piece_samples(ctx, dp, org, cov, T, &spill) / T;
+    struct Piece {
+        uint64_t k0, k1;  // tiles [k0, k1): samples [k0 T, k1 T) at scratch[0, (k1 - k0) T)
+    };
+    std::vector<Piece> pcs;
+    uint64_t region_tiles = 0;
+    for (size_t a = 0; a < cov.size();) {
+        const uint64_t k0 = cov[a].first / T;
+        uint64_t k1 = (cov[a].second + T - 1) / T;
+        size_t z = a + 1;
+        while (z < cov.size() && cov[z].first / T < k1 + AGG_GAP_TILES) k1 = std::max(k1, (cov[z++].second + T - 1) / T);
+        for (uint64_t k = k0; k < k1; k += piece_tiles) {
+            pcs.push_back(Piece{k, std::min(k1, k + piece_tiles)});
+            region_tiles = std::max(region_tiles, pcs.back().k1 - k);
+        }
+        a = z;
+    }
+    const uint64_t region = region_tiles * T;
+    // shared full tiles: the tiles past a window's first and before its last, merged over the windows
+    std::vector<Span> mids;
+    for (uint64_t i = 0; i < W; ++i) {
+        if (!count[i]) continue;
+        const uint64_t kb = (org + begin[i]) / T, ke = (org + begin[i] + count[i] - 1) / T;
+        if (ke >= kb + 2) mids.emplace_back(kb + 1, ke);
+    }
+    merge_spans(mids);
+    std::vector<uint64_t> mid_at(mids.size());
+    uint64_t U = 0;
+    for (size_t r = 0; r < mids.size(); ++r) { mid_at[r] = U; U += mids[r].second - mids[r].first; }
+    auto shared_index = [&](uint64_t k) {  // index of full tile k among the shared partials
+        const size_t r = (size_t)(std::upper_bound(mids.begin(), mids.end(), Span(k, ~0ull)) - mids.begin()) - 1;
+        return mid_at[r] + (k - mids[r].first);
+    };
+    // tile tasks, by tile; part[] = [U shared | first, last tile of each window | combine levels]
+    struct TT {
+        uint64_t k;
+        DevAggTile t;
+    };
+    std::vector<TT> tt;
+    tt.reserve(U + 2 * W);
+    for (size_t r = 0; r < mids.size(); ++r)
+        for (uint64_t k = mids[r].first; k < mids[r].second; ++k)
+            tt.push_back(TT{k, DevAggTile{0, mid_at[r] + (k - mids[r].first), 0, (uint32_t)T, 0, 0}});
+    struct Lv {
+        uint64_t head, tail, mid, n;
+    };
+    std::vector<Lv> lv(W);
+    for (uint64_t i = 0; i < W; ++i) {
+        if (!count[i]) { lv[i] = Lv{0, 0, 0, 0}; continue; }
+        const uint64_t b = org + begin[i], e = b + count[i], kb = b / T, ke = (e - 1) / T;
+        tt.push_back(TT{kb, DevAggTile{0, U + 2 * i, (uint32_t)(b - kb * T), (uint32_t)(std::min(e, (kb + 1) * T) - kb * T),
+                                       (uint32_t)i, AGG_FIRST | (ke == kb ? AGG_LAST : 0u)}});
+        if (ke > kb) tt.push_back(TT{ke, DevAggTile{0, U + 2 * i + 1, 0, (uint32_t)(e - ke * T), (uint32_t)i, AGG_LAST}});
+        lv[i] = Lv{U + 2 * i, ke > kb ? U + 2 * i + 1 : U + 2 * i, ke >= kb + 2 ? shared_index(kb + 1) - 1 : 0, ke - kb + 1};
+    }
+    std::stable_sort(tt.begin(), tt.end(), [](const TT &x, const TT &y) { return x.k < y.k; });
+    // combine passes: groups of 64 entries of each window's list until one is left
+    uint64_t part_n = U + 2 * W;
+    std::vector<DevAggComb> comb;
+    std::vector<size_t> pass_at{0};
+    {
+        std::vector<uint32_t> live(W), next;
+        for (uint64_t i = 0; i < W; ++i) live[i] = (uint32_t)i;
+        while (!live.empty()) {
+            next.clear();
+            for (uint32_t i : live) {
+                Lv &l = lv[i];
+                const uint64_t G = std::max<uint64_t>(1, (l.n + 63) / 64);
+                if (G == 1) {
+                    comb.push_back(DevAggComb{l.head, l.tail, l.mid, i, (uint32_t)l.n, 0, i, 1});
+                    continue;
+                }
+                const uint64_t base = part_n;
+                part_n += G;
+                for (uint64_t g = 0; g < G; ++g) comb.push_back(DevAggComb{l.head, l.tail, l.mid, base + g, (uint32_t)l.n, (uint32_t)g, i, 0});
+                l = Lv{base, base + G - 1, base, G};
+                next.push_back(i);
+            }
+            pass_at.push_back(comb.size());
+            live.swap(next);
+        }
+    }
+    // decode tasks of every piece (emit_piece_decode) and its tile tasks
+    std::vector<PieceDecode> pdec(pcs.size());
+    std::vector<size_t> tile_at(pcs.size());
+    std::vector<uint32_t> tile_n(pcs.size());
+    DecodeTasks D;
+    std::vector<DevAggTile> tiles;
+    tiles.reserve(tt.size());
+    size_t ci = 0, ti = 0;
+    for (size_t p = 0; p < pcs.size(); ++p) {
+        tile_at[p] = tiles.size();
+        if (!emit_piece_decode(dp, org, cov, ci, pcs[p].k0 * T, pcs[p].k1 * T, region, D, pdec[p]))
+            return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (spill slots)");
+        for (; ti < tt.size() && tt[ti].k < pcs[p].k1; ++ti) {
+            DevAggTile t = tt[ti].t;
+            t.src = (tt[ti].k - pcs[p].k0) * T;
+            tiles.push_back(t);
+        }
+        tile_n[p] = (uint32_t)(tiles.size() - tile_at[p]);
+    }
+    if (ti != tt.size()) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (tile outside the pieces)");
+    QueryRes &R = dp->agg;
+    HIPCHK(ctx, R.wait());
+    // one upload: the decode tasks, tile tasks, combine tasks; behind them (device only) the partials and the windows'
+    // first / last samples
+    Upload up;
+    D.place(up);
+    const size_t off_tiles = up.add(tiles), off_comb = up.add(comb);
+    const size_t off_part = up.device_only(part_n * sizeof(DevAggPart)), off_fl = up.device_only(2 * W * sizeof(double));
+    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, region + (uint64_t)MAX_FRAME * D.spills_used));
+    unsigned char *d = R.d;
+    up.stage(R.h);
+    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
+    double *scr = R.scratch;
+    DevAggPart *part = (DevAggPart *)(d + off_part);
+    double *fl = (double *)(d + off_fl);
+    for (size_t p = 0; p < pcs.size(); ++p) {
+        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_AGGREGATE);
+        if (rc) return rc;
+        const hipError_t e = launch_agg_tiles((const DevAggTile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, fl, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_agg_tiles", e);
+    }
+    for (size_t q = 0; q + 1 < pass_at.size(); ++q) {
+        const hipError_t e = launch_agg_combine((const DevAggComb *)(d + off_comb) + pass_at[q], (uint32_t)(pass_at[q + 1] - pass_at[q]),
+                                                part, fl, d_stats, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_agg_combine", e);
+    }
+    HIPCHK(ctx, R.record(s));
+    return ATSC_OK;
+}
+extern "C" int atsc_aggregate_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                          const uint64_t *begin, const uint64_t *count, atsc_window_stats *d_stats,
+                                          void *stream)
+{
+    ATSC_API_BEGIN
+    return aggregate_dev(ctx, dp, d_body, n_windows, begin, count, d_stats, stream, 0);
+    ATSC_API_END
+}
+
+// Host call: window_host_call into aggregate_dev.
+extern "C" int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                      const uint64_t *begin, const uint64_t *count, atsc_window_stats *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: null argument");
+    if (n_windows == 0) return ATSC_OK;
+    return window_host_call(
+        ctx, "aggregate_windows", body, body_len, has_count, n_windows, begin, count, out,
+        n_windows * sizeof(atsc_window_stats), false,
+        [&](bool any) {
+            for (uint64_t i = 0; !any && i < n_windows; ++i) agg_empty_record(out[i]);
+            return ATSC_OK;
+        },
+        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
+            return aggregate_dev(ctx, dp, d_body, n_windows, begin2, count, (atsc_window_stats *)d_res, ws, org);
+        });
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
+// windowed quantiles: exact order statistics of sample windows (atsc_quantile.hip)
+// ------------------------------------------------------------------------------------------
+// ctx may be null: then no message is kept
+static int quantile_check_levels(atsc_ctx *ctx, uint32_t n_q, const double *q, int method)
+{
+    if (!q) return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
+    if (n_q == 0 || n_q > QNT_MAX_LEVELS) return fail(ctx, ATSC_E_INVALID, "quantile_windows: n_q outside [1, 64]");
+    for (uint32_t j = 0; j < n_q; ++j)
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(ctx, ATSC_E_INVALID, "quantile_windows: a level is NaN or outside [0, 1]");
+    if (method < ATSC_QUANTILE_LINEAR || method > ATSC_QUANTILE_NEAREST)
+        return fail(ctx, ATSC_E_INVALID, "quantile_windows: unknown method");
+    return ATSC_OK;
+}
+
+// The device call.  Every window is held whole in scratch: the windows, by begin, go into pieces of at most L samples
+// (a piece starts at the first window not yet placed and takes every unplaced window that ends within L of that
+// start; pieces overlap where windows do).  Per piece: the decode tasks of its windows' union (emit_piece_decode), then
+// the tiers by window length: short and medium windows one launch each (medium: one per power-of-two key count), long
+// windows QNT_PASSES histogram + pick launches whatever their number.  Everything goes up in one copy; nothing waits
+// on the host between pieces.  org: the stream index of the plan's first sample (see aggregate_dev).
+static int quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                        const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
+                        double *d_out, void *stream, uint64_t org)
+{
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_out)))
+        return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
+    int rc = quantile_check_levels(ctx, n_q, q, method);
+    if (rc) return rc;
+    rc = check_windows(ctx, "quantile_windows", dp, d_out, "d_out", n_windows, begin, count, 0xfffffffeull);
+    if (rc || n_windows == 0) return rc;
+    if (!launch_decompress_window || !launch_window_gather || !launch_qnt_short || !launch_qnt_medium || !launch_qnt_hist ||
+        !launch_qnt_pick)
+        return fail(ctx, ATSC_E_UNSUPPORTED, "quantile_windows: no quantile kernels");
+    const uint64_t W = n_windows;
+    std::vector<uint32_t> ord;  // the non-empty windows by begin
+    std::vector<Span> cov;
+    for (uint64_t i = 0; i < W; ++i)
+        if (count[i]) { ord.push_back((uint32_t)i); cov.emplace_back(org + begin[i], org + begin[i] + count[i]); }
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return begin[a] < begin[b]; });
+    merge_spans(cov);
+    uint64_t spill;
+    const uint64_t L = piece_samples(ctx, dp, org, cov, 1, &spill);
+    for (uint32_t i : ord) {
+        if (count[i] <= L && count[i] < (1ull << 32)) continue;
+        char msg[192];
+        if (count[i] >= (1ull << 32))
+            snprintf(msg, sizeof msg, "quantile_windows: window %u holds %llu samples, more than 2^32 - 1", i,
+                     (unsigned long long)count[i]);
+        else
+            snprintf(msg, sizeof msg,
+                     "quantile_windows: window %u (%llu samples) does not fit one scratch piece; an aggregate scratch "
+                     "budget of %llu bytes would hold it", i, (unsigned long long)count[i],
+                     (unsigned long long)((count[i] + spill) * sizeof(double)));
+        return fail(ctx, ATSC_E_CAPACITY, msg);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // pieces: windows ord[w_at, w_at + w_n) of pw, samples [S0, S1) of the stream at scratch[0, S1 - S0)
+    struct Piece {
+        uint64_t S0, S1;
+        size_t w_at, w_n;
+    };
+    std::vector<Piece> pcs;
+    std::vector<uint32_t> pw;
+    pw.reserve(ord.size());
+    {
+        std::vector<char> placed(ord.size(), 0);
+        size_t a = 0;
+        while (a < ord.size()) {
+            Piece pc{org + begin[ord[a]], 0, pw.size(), 0};
+            pc.S1 = pc.S0;
+            for (size_t k = a; k < ord.size() && org + begin[ord[k]] < pc.S0 + L; ++k) {
+                const uint64_t e = org + begin[ord[k]] + count[ord[k]];
+                if (placed[k] || e > pc.S0 + L) continue;
+                placed[k] = 1;
+                pw.push_back(ord[k]);
+                pc.S1 = std::max(pc.S1, e);
+            }
+            pc.w_n = pw.size() - pc.w_at;
+            pcs.push_back(pc);
+            while (a < ord.size() && placed[a]) ++a;
+        }
+    }
+    uint64_t region = 0;
+    for (const Piece &pc : pcs) region = std::max(region, pc.S1 - pc.S0);
+    // per piece: decode tasks, then the windows by tier
+    const uint32_t n_med = 6;  // medium key counts 2^9 .. 2^14 (the ones up to QNT_MEDIUM_MAX are used)
+    struct PieceQ {
+        size_t short_at, med_at[n_med], long_at, chunk_at;
+        uint32_t short_n, med_n[n_med], long_n, chunk_n;
+    };
+    std::vector<PieceDecode> pdec(pcs.size());
+    std::vector<PieceQ> pq(pcs.size());
+    DecodeTasks D;
+    std::vector<DevQTask> shorts, meds, longs;
+    std::vector<DevQTask> med_class[n_med];
+    std::vector<DevQChunk> chunks;
+    std::vector<Span> pcov;
+    uint32_t max_long = 0;
+    for (size_t p = 0; p < pcs.size(); ++p) {
+        const Piece &pc = pcs[p];
+        pcov.clear();  // the piece's windows come by begin: merged as they come
+        for (size_t k = pc.w_at; k < pc.w_at + pc.w_n; ++k) {
+            const Span x(org + begin[pw[k]], org + begin[pw[k]] + count[pw[k]]);
+            if (pcov.empty() || !absorb_span(pcov.back(), x)) pcov.push_back(x);
+        }
+        size_t ci = 0;
+        if (!emit_piece_decode(dp, org, pcov, ci, pc.S0, pc.S1, region, D, pdec[p]))
+            return fail(ctx, ATSC_E_INVALID, "quantile_windows: internal error (spill slots)");
+        PieceQ &t = pq[p];
+        t.short_at = shorts.size();
+        t.long_at = longs.size();
+        t.chunk_at = chunks.size();
+        for (uint32_t c = 0; c < n_med; ++c) med_class[c].clear();
+        for (size_t k = pc.w_at; k < pc.w_at + pc.w_n; ++k) {
+            const uint32_t i = pw[k];
+            const uint64_t src = org + begin[i] - pc.S0, n = count[i];
+            if (n <= QNT_SHORT_MAX) {
+                shorts.push_back(DevQTask{src, n, i, 0});
+            } else if (n <= QNT_MEDIUM_MAX) {
+                uint32_t c = 0;
+                while ((512ull << c) < n) ++c;
+                med_class[c].push_back(DevQTask{src, n, i, 0});
+            } else {
+                const uint32_t slot = (uint32_t)(longs.size() - t.long_at);
+                longs.push_back(DevQTask{src, n, i, slot});
+                for (uint64_t o = 0; o < n; o += QNT_CHUNK)
+                    chunks.push_back(DevQChunk{src + o, (uint32_t)std::min<uint64_t>(QNT_CHUNK, n - o), slot});
+            }
+        }
+        for (uint32_t c = 0; c < n_med; ++c) {
+            t.med_at[c] = meds.size();
+            t.med_n[c] = (uint32_t)med_class[c].size();
+            meds.insert(meds.end(), med_class[c].begin(), med_class[c].end());
+        }
+        t.short_n = (uint32_t)(shorts.size() - t.short_at);
+        t.long_n = (uint32_t)(longs.size() - t.long_at);
+        t.chunk_n = (uint32_t)(chunks.size() - t.chunk_at);
+        max_long = std::max(max_long, t.long_n);
+    }
+    // empty windows: NaN from the short tier, once
+    const size_t empty_at = shorts.size();
+    for (uint64_t i = 0; i < W; ++i)
+        if (!count[i]) shorts.push_back(DevQTask{0, 0, (uint32_t)i, 0});
+    const uint32_t empty_n = (uint32_t)(shorts.size() - empty_at);
+    QueryRes &R = dp->qnt;
+    HIPCHK(ctx, R.wait());
+    // one upload: the decode tasks, the levels, the tiers' task lists, the chunks; behind them (device only) the long
+    // tier's state and counts
+    const uint32_t rows = 2 * n_q;
+    Upload up;
+    D.place(up);
+    const size_t off_q = up.add(q, n_q * sizeof(double)), off_short = up.add(shorts), off_med = up.add(meds),
+                 off_long = up.add(longs), off_chunk = up.add(chunks);
+    const size_t hist_bytes = (size_t)max_long * rows * 256 * sizeof(uint32_t);
+    const size_t off_state = up.device_only((size_t)max_long * sizeof(DevQState)), off_hist = up.device_only(hist_bytes);
+    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, std::max<uint64_t>(1, region + (uint64_t)MAX_FRAME * D.spills_used)));
+    unsigned char *d = R.d;
+    up.stage(R.h);
+    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
+    if (hist_bytes) HIPCHK(ctx, hipMemsetAsync(d + off_hist, 0, hist_bytes, s));  // k_qnt_pick clears what it reads
+    double *scr = R.scratch;
+    const double *dq = (const double *)(d + off_q);
+    const DevQTask *d_short = (const DevQTask *)(d + off_short), *d_med = (const DevQTask *)(d + off_med),
+                   *d_long = (const DevQTask *)(d + off_long);
+    const DevQChunk *d_chunk = (const DevQChunk *)(d + off_chunk);
+    DevQState *st = (DevQState *)(d + off_state);
+    uint32_t *hist = (uint32_t *)(d + off_hist);
+    hipError_t e = launch_qnt_short(d_short + empty_at, empty_n, scr, dq, n_q, method, d_out, s);
+    if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_short", e);
+    for (size_t p = 0; p < pcs.size(); ++p) {
+        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_QUANTILE);
+        if (rc) return rc;
+        const PieceQ &t = pq[p];
+        e = launch_qnt_short(d_short + t.short_at, t.short_n, scr, dq, n_q, method, d_out, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_short", e);
+        for (uint32_t c = 0; c < n_med; ++c) {
+            e = launch_qnt_medium(d_med + t.med_at[c], t.med_n[c], 512u << c, scr, dq, n_q, method, d_out, s);
+            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_medium", e);
+        }
+        if (!t.long_n) continue;
+        for (uint32_t pass = 0; pass < QNT_PASSES; ++pass) {
+            e = launch_qnt_hist(d_chunk + t.chunk_at, t.chunk_n, scr, st, hist, rows, pass, s);
+            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_hist", e);
+            e = launch_qnt_pick(d_long + t.long_at, t.long_n, st, hist, rows, pass, dq, n_q, method, d_out, s);
+            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_pick", e);
+        }
+    }
+    HIPCHK(ctx, R.record(s));
+    return ATSC_OK;
+}
+extern "C" int atsc_quantile_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                         const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q,
+                                         int method, double *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    return quantile_dev(ctx, dp, d_body, n_windows, begin, count, n_q, q, method, d_out, stream, 0);
+    ATSC_API_END
+}
+
+// Host call: window_host_call into quantile_dev.
+extern "C" int atsc_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                     const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
+                                     double *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
+    const int rc = quantile_check_levels(ctx, n_q, q, method);
+    if (rc) return rc;
+    if (n_windows == 0) return ATSC_OK;
+    return window_host_call(
+        ctx, "quantile_windows", body, body_len, has_count, n_windows, begin, count, out,
+        n_windows * n_q * sizeof(double), false,
+        [&](bool any) {
+            for (uint64_t i = 0; !any && i < n_windows * n_q; ++i) out[i] = std::numeric_limits<double>::quiet_NaN();
+            return ATSC_OK;
+        },
+        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
+            return quantile_dev(ctx, dp, d_body, n_windows, begin2, count, n_q, q, method, (double *)d_res, ws, org);
+        });
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
+// the same three queries on a stream under construction (atsc_stream.cpp): its records, then the host call
+// ------------------------------------------------------------------------------------------
+// a stream without a frame holds only empty windows at 0
+static bool only_empty_at_zero(uint64_t n_windows, const uint64_t *begin, const uint64_t *count)
+{
+    for (uint64_t i = 0; i < n_windows; ++i)
+        if (begin[i] != 0 || count[i] != 0) return false;
+    return true;
+}
+
+extern "C" int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uint64_t count, double **out, uint64_t *n)
+{
+    ATSC_API_BEGIN
+    if (!s || !out || !n) return ATSC_E_INVALID;
+    *out = nullptr;
+    *n = 0;
+    std::vector<uint8_t> body;
+    atsc_ctx *ctx = nullptr;
+    int rc = stream_body(s, body, &ctx);
+    if (rc) return rc;
+    if (body.empty()) {
+        if (!only_empty_at_zero(1, &begin, &count)) return ATSC_E_INVALID;
+        *out = (double *)malloc(8);
+        return *out ? ATSC_OK : ATSC_E_NOMEM;
+    }
+    double *buf = (double *)big_alloc((count ? count : 1) * sizeof(double));
+    if (!buf) return ATSC_E_NOMEM;
+    uint64_t got = 0;
+    rc = atsc_decompress_window(ctx, body.data(), body.size(), 0, begin, count, buf, count, &got);
+    if (rc) {
+        atsc_free(buf);
+        return rc;
+    }
+    *out = buf;
+    *n = got;
+    return ATSC_OK;
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                             atsc_window_stats *out)
+{
+    ATSC_API_BEGIN
+    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
+    std::vector<uint8_t> body;
+    atsc_ctx *ctx = nullptr;
+    const int rc = stream_body(s, body, &ctx);
+    if (rc) return rc;
+    if (body.empty()) {
+        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
+        for (uint64_t i = 0; i < n_windows; ++i) agg_empty_record(out[i]);
+        return ATSC_OK;
+    }
+    return atsc_aggregate_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                            uint32_t n_q, const double *q, int method, double *out)
+{
+    ATSC_API_BEGIN
+    if (!s || !q || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
+    // (no context: this check has never left a message on the stream's)
+    int rc = quantile_check_levels(nullptr, n_q, q, method);
+    if (rc) return rc;
+    std::vector<uint8_t> body;
+    atsc_ctx *ctx = nullptr;
+    rc = stream_body(s, body, &ctx);
+    if (rc) return rc;
+    if (body.empty()) {
+        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
+        for (uint64_t i = 0; i < n_windows * n_q; ++i) out[i] = std::numeric_limits<double>::quiet_NaN();
+        return ATSC_OK;
+    }
+    return atsc_quantile_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, n_q, q, method, out);
+    ATSC_API_END
+}

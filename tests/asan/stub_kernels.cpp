@@ -1,5 +1,5 @@
 // tests/asan -- link-time stand-ins for the kernel launchers of libatsc_hip.so (the .hip files), so that
-// the HOST sources of the library (atsc_host.cpp, atsc_stream.cpp, atsc_vsri.cpp) build with
+// the HOST sources of the library (atsc_host.cpp, atsc_windows.cpp, atsc_stream.cpp, atsc_vsri.cpp) build with
 // AddressSanitizer + UBSan on a box without a GPU.  Nothing here is ever reached: atsc_ctx_create fails
 // with ATSC_E_NO_DEVICE before a launch can happen.  Test infrastructure only.
 #include <hip/hip_runtime.h>

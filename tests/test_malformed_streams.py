@@ -131,7 +131,7 @@ def test_wbro_survives_mutations(A, golden_dir):
 
 
 def test_host_parsers_under_sanitizers(A, oracle, golden_dir, tmp_path):
-    """ASan + UBSan build (g++) of atsc_host.cpp / atsc_stream.cpp / atsc_vsri.cpp; tests/asan/host_fuzz.cpp feeds
+    """ASan + UBSan build (g++) of atsc_host.cpp / atsc_windows.cpp / atsc_stream.cpp / atsc_vsri.cpp; tests/asan/host_fuzz.cpp feeds
     the corpus written here through the parsers: as is, truncated, bit-flipped and with hostile varints."""
     if shutil.which("g++") is None or not os.path.isdir("/opt/rocm/include"):
         pytest.skip("no g++ / ROCm headers")
