@@ -13,6 +13,9 @@ LIB_PATH = os.path.join(_HERE, "libatsc_hip%s.so" % ("_" + _VARIANT if _VARIANT 
 NOOP, FFT, IDW, CONSTANT, POLYNOMIAL, AUTO, RLE = 0, 1, 2, 3, 4, 5, 6
 # atsc_quantile_windows methods (include/atsc_hip.h)
 QUANTILE_LINEAR, QUANTILE_LOWER, QUANTILE_HIGHER, QUANTILE_NEAREST = 0, 1, 2, 3
+# atsc_histogram_windows: which side of a bin is closed, and the most edges (include/atsc_hip.h)
+HIST_LEFT_CLOSED, HIST_RIGHT_CLOSED = 0, 1
+HIST_MAX_EDGES = 1024
 COMPRESSOR_NAMES = {0: "noop", 1: "fft", 2: "idw", 3: "constant", 4: "polynomial", 5: "auto", 6: "rle"}
 
 OK = 0
@@ -97,6 +100,11 @@ SIGNATURES = {
                                             _vp]),
     "atsc_quantile_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p,
                                         C.c_int, _f64p]),
+    "atsc_histogram_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _vp,
+                                             _vp]),
+    "atsc_histogram_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p,
+                                         C.c_int, _u64p]),
+    "atsc_histogram_edges_uniform": (C.c_int, [C.c_double, C.c_double, C.c_uint32, _f64p]),
     "atsc_stream_new": (C.c_int, [_vp, C.POINTER(_vp)]),
     "atsc_stream_from_bytes": (C.c_int, [_vp, _u8p, C.c_uint64, C.POINTER(_vp)]),
     "atsc_stream_free": (None, [_vp]),
@@ -109,6 +117,7 @@ SIGNATURES = {
     "atsc_stream_decompress_window": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(_f64p), _u64p]),
     "atsc_stream_aggregate_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_quantile_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _f64p]),
+    "atsc_stream_histogram_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _u64p]),
     "atsc_free": (None, [_vp]),
     "atsc_compress_data": (C.c_int, [_vp, _f64p, C.c_uint64, C.c_int, C.c_uint8, C.c_int, C.POINTER(_u8p), _u64p]),
     "atsc_decompress_data": (C.c_int, [_vp, _u8p, C.c_uint64, C.POINTER(_f64p), _u64p]),

@@ -1,7 +1,7 @@
 // atsc_host.cpp -- host side of libatsc_hip.so: context, plans, launch orchestration and the
 // format helpers that sit either side of the GPU path.  There is NO CPU compression path in
 // this library: without a HIP device atsc_ctx_create fails with ATSC_E_NO_DEVICE.
-// The window queries (window decode, windowed aggregates and quantiles) are in atsc_windows.cpp; what the two files
+// The window queries (window decode, windowed aggregates, quantiles and histograms) are in atsc_windows.cpp; what the two files
 // share is declared in atsc_host_private.h.
 #include <hip/hip_runtime.h>
 
@@ -1726,6 +1726,7 @@ extern "C" void atsc_dplan_destroy(atsc_dplan *p)
     p->win.release(p->ctx);
     p->agg.release(p->ctx);
     p->qnt.release(p->ctx);
+    p->hst.release(p->ctx);
     pool_free(p->ctx, p->d_frames);
     pool_free(p->ctx, p->d_ids);
     pool_free(p->ctx, p->d_status);

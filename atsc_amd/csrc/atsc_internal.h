@@ -234,6 +234,19 @@ struct DevQState {
     uint32_t ridx[QNT_SLOTS];
 };
 
+// windowed histograms (atsc_histogram_windows_dev, atsc_histogram.hip).  The tier of a task is chosen from its length:
+// short (one wavefront), chunk (one workgroup; a longer stretch of a window is cut into tasks of HST_CHUNK samples)
+constexpr uint32_t HST_MAX_EDGES = 1024;     // ATSC_HIST_MAX_EDGES: 8 KiB of edges in LDS
+constexpr uint32_t HST_SHORT_MAX = 256;
+constexpr uint32_t HST_CHUNK = 16384;        // samples per workgroup, as QNT_CHUNK
+constexpr uint32_t HST_SHORT_GRID = 2048;    // the most workgroups of k_hst_short: they walk the task list in strides
+constexpr uint32_t HST_OWN = 0x80000000u;    // in DevHistTask::len: the window's only task, which stores the row whole
+// one task: samples scratch[src, src + (len & ~HST_OWN)) counted into row `win` of the result
+struct DevHistTask {
+    uint64_t src;
+    uint32_t len, win;
+};
+
 static inline uint32_t varint_len_u64(uint64_t v)
 {
     return v < 251 ? 1u : v < (1ull << 16) ? 3u : v < (1ull << 32) ? 5u : 9u;

@@ -1,5 +1,5 @@
-// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates and quantiles of ranges of the decoded
-// stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
+// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, quantiles and histograms of ranges of
+// the decoded stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
@@ -36,6 +36,13 @@ __attribute__((weak)) hipError_t launch_qnt_hist(const DevQChunk *chunks, uint32
 __attribute__((weak)) hipError_t launch_qnt_pick(const DevQTask *tasks, uint32_t n, DevQState *st, uint32_t *hist,
                                                  uint32_t rows, uint32_t pass, const double *q, uint32_t n_q, int method,
                                                  double *out, hipStream_t s);
+// the windowed histograms' counting kernels (atsc_histogram.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_hst_short(const DevHistTask *tasks, uint32_t n, const double *scratch,
+                                                  const double *edges, uint32_t n_edges, int closed, uint64_t *out,
+                                                  hipStream_t s);
+__attribute__((weak)) hipError_t launch_hst_chunk(const DevHistTask *tasks, uint32_t n, const double *scratch,
+                                                  const double *edges, uint32_t n_edges, int closed, uint64_t *out,
+                                                  hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -240,6 +247,8 @@ static const DecodeCaller BY_AGGREGATE = {"launch k_decompress (aggregate)", "la
                                           "launch k_window_gather (aggregate)"};
 static const DecodeCaller BY_QUANTILE = {"launch k_decompress (quantile)", "launch k_decompress_large (quantile)",
                                          "launch k_window_gather (quantile)"};
+static const DecodeCaller BY_HISTOGRAM = {"launch k_decompress (histogram)", "launch k_decompress_large (histogram)",
+                                          "launch k_window_gather (histogram)"};
 
 // Enqueues one piece's decode (d: the device copy of the upload).  out: the base the tasks' destinations count from;
 // the copies go from gat_src to gat_dst.
@@ -499,7 +508,7 @@ extern "C" int atsc_decompress_window(atsc_ctx *ctx, const uint8_t *body, uint64
 }
 
 // ------------------------------------------------------------------------------------------
-// decoded samples of window pieces in scratch (the aggregate and the quantile calls)
+// decoded samples of window pieces in scratch (the aggregate, the quantile and the histogram calls)
 // ------------------------------------------------------------------------------------------
 // Decoded samples reach the reduce and selection kernels through one scratch region, piece after piece in stream order.
 static const uint64_t AGG_MIN_PIECE = 32ull * AGG_TILE;  // the least a piece holds, whatever the budget
@@ -1031,7 +1040,194 @@ extern "C" int atsc_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_
 }
 
 // ------------------------------------------------------------------------------------------
-// the same three queries on a stream under construction (atsc_stream.cpp): its records, then the host call
+// windowed histograms: per-window counts of the samples over value bins (atsc_histogram.hip)
+// ------------------------------------------------------------------------------------------
+// Covering intervals closer than this share a span of pieces, as the aggregates' AGG_GAP_TILES tiles
+static const uint64_t HST_GAP = 64ull * AGG_TILE;
+
+// ctx may be null: then no message is kept
+static int histogram_check_edges(atsc_ctx *ctx, uint32_t n_edges, const double *edges, int closed)
+{
+    if (!edges) return fail(ctx, ATSC_E_INVALID, "histogram_windows: null argument");
+    if (n_edges == 0 || n_edges > HST_MAX_EDGES) return fail(ctx, ATSC_E_INVALID, "histogram_windows: n_edges outside [1, 1024]");
+    for (uint32_t j = 0; j < n_edges; ++j)
+        if (edges[j] != edges[j]) return fail(ctx, ATSC_E_INVALID, "histogram_windows: an edge is NaN");
+    for (uint32_t j = 1; j < n_edges; ++j)
+        if (!(edges[j - 1] < edges[j])) return fail(ctx, ATSC_E_INVALID, "histogram_windows: edges are not strictly ascending");
+    if (closed != ATSC_HIST_LEFT_CLOSED && closed != ATSC_HIST_RIGHT_CLOSED)
+        return fail(ctx, ATSC_E_INVALID, "histogram_windows: unknown closed");
+    return ATSC_OK;
+}
+
+extern "C" int atsc_histogram_edges_uniform(double lo, double hi, uint32_t n_bins, double *edges)
+{
+    if (!edges || !(lo - lo == 0.0) || !(hi - hi == 0.0) || !(hi > lo)) return ATSC_E_INVALID;
+    if (n_bins == 0 || n_bins >= HST_MAX_EDGES) return ATSC_E_INVALID;
+    const double step = (hi - lo) / (double)n_bins;
+    if (!(step > 0.0)) return ATSC_E_INVALID;
+    double e[HST_MAX_EDGES];
+    for (uint32_t k = 0; k < n_bins; ++k) e[k] = (double)k * step + lo;
+    e[n_bins] = hi;
+    for (uint32_t k = 0; k < n_bins; ++k)
+        if (!(e[k] < e[k + 1])) return ATSC_E_INVALID;  // a width of a few ulps of lo, or a step that overflowed
+    memcpy(edges, e, ((size_t)n_bins + 1) * sizeof(double));
+    return ATSC_OK;
+}
+
+// The device call.  Host work: covering intervals; spans of them cut into pieces of at most one scratch piece, at any
+// sample; the decode tasks of every piece (emit_piece_decode); per window and touched piece, the window's stretch
+// inside the piece cut into tasks of at most HST_CHUNK samples (a task of at most HST_SHORT_MAX samples goes to the
+// one-wavefront tier, so a call of many short windows is one launch of few workgroups).  A window with a single task
+// owns its row (HST_OWN: stored whole); when any window has none or several, the result is cleared first and the
+// tasks add.  Everything, the edges included, goes up in one copy; nothing waits on the host between pieces.
+// org: the stream index of the plan's first sample (see aggregate_dev).
+static int histogram_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                         const uint64_t *begin, const uint64_t *count, uint32_t n_edges, const double *edges, int closed,
+                         uint64_t *d_out, void *stream, uint64_t org)
+{
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_out)))
+        return fail(ctx, ATSC_E_INVALID, "histogram_windows: null argument");
+    int rc = histogram_check_edges(ctx, n_edges, edges, closed);
+    if (rc) return rc;
+    rc = check_windows(ctx, "histogram_windows", dp, d_out, "d_out", n_windows, begin, count, 0xfffffffeull);
+    if (rc || n_windows == 0) return rc;
+    if (!launch_decompress_window || !launch_window_gather || !launch_hst_short || !launch_hst_chunk)
+        return fail(ctx, ATSC_E_UNSUPPORTED, "histogram_windows: no histogram kernels");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint64_t W = n_windows, rows = (uint64_t)n_edges + 2;
+    std::vector<Span> cov;
+    for (uint64_t i = 0; i < W; ++i)
+        if (count[i]) cov.emplace_back(org + begin[i], org + begin[i] + count[i]);
+    if (cov.empty()) {  // only empty windows
+        HIPCHK(ctx, hipMemsetAsync(d_out, 0, W * rows * sizeof(uint64_t), s));
+        return ATSC_OK;
+    }
+    bool all_own = cov.size() == W;
+    merge_spans(cov);
+    uint64_t spill;
+    const uint64_t L = piece_samples(ctx, dp, org, cov, 1, &spill);
+    // pieces: samples [S0, S1) of the stream at scratch[0, S1 - S0), ascending and disjoint
+    std::vector<Span> pcs;
+    uint64_t region = 0;
+    for (size_t a = 0; a < cov.size();) {
+        const uint64_t s0 = cov[a].first;
+        uint64_t s1 = cov[a].second;
+        size_t z = a + 1;
+        while (z < cov.size() && cov[z].first < s1 + HST_GAP) s1 = cov[z++].second;
+        for (uint64_t p = s0; p < s1; p += L) pcs.emplace_back(p, std::min(s1, p + L));
+        region = std::max(region, std::min(L, s1 - s0));
+        a = z;
+    }
+    // tasks, by tier: a window cut by a piece boundary gets tasks on each side
+    struct PT {
+        uint32_t piece;
+        DevHistTask t;
+    };
+    std::vector<PT> tk[2];  // 0: short, 1: chunk
+    tk[0].reserve(W);
+    for (uint64_t i = 0; i < W; ++i) {
+        if (!count[i]) continue;
+        const uint64_t b = org + begin[i], e = b + count[i];
+        size_t p = (size_t)(std::upper_bound(pcs.begin(), pcs.end(), b, [](uint64_t v, const Span &x) { return v < x.second; }) -
+                            pcs.begin());
+        uint32_t n_tasks = 0;
+        PT *last = nullptr;
+        for (; p < pcs.size() && pcs[p].first < e; ++p) {
+            const uint64_t lo = std::max(b, pcs[p].first), hi = std::min(e, pcs[p].second);
+            for (uint64_t o = lo; o < hi; o += HST_CHUNK) {
+                const uint32_t len = (uint32_t)std::min<uint64_t>(HST_CHUNK, hi - o);
+                std::vector<PT> &v = tk[len <= HST_SHORT_MAX ? 0 : 1];
+                v.push_back(PT{(uint32_t)p, DevHistTask{o - pcs[p].first, len, (uint32_t)i}});
+                last = &v.back();
+                ++n_tasks;
+            }
+        }
+        if (n_tasks == 1) last->t.len |= HST_OWN;
+        else all_own = false;
+    }
+    const size_t P = pcs.size();
+    std::vector<DevHistTask> tasks[2];
+    std::vector<size_t> at[2];
+    for (int k = 0; k < 2; ++k) {
+        auto by_piece = [](const PT &x, const PT &y) { return x.piece < y.piece; };
+        if (P > 1 && !std::is_sorted(tk[k].begin(), tk[k].end(), by_piece)) std::stable_sort(tk[k].begin(), tk[k].end(), by_piece);
+        tasks[k].reserve(tk[k].size());
+        at[k].assign(P + 1, 0);
+        for (const PT &x : tk[k]) { tasks[k].push_back(x.t); ++at[k][x.piece + 1]; }
+        for (size_t p = 0; p < P; ++p) {
+            if (at[k][p + 1] > 0x7fffffffull) return fail(ctx, ATSC_E_INVALID, "histogram_windows: more than 2^31 - 1 tasks in a piece");
+            at[k][p + 1] += at[k][p];
+        }
+        std::vector<PT>().swap(tk[k]);
+    }
+    // decode tasks of every piece
+    std::vector<PieceDecode> pdec(P);
+    DecodeTasks D;
+    size_t ci = 0;
+    for (size_t p = 0; p < P; ++p)
+        if (!emit_piece_decode(dp, org, cov, ci, pcs[p].first, pcs[p].second, region, D, pdec[p]))
+            return fail(ctx, ATSC_E_INVALID, "histogram_windows: internal error (spill slots)");
+    QueryRes &R = dp->hst;
+    HIPCHK(ctx, R.wait());
+    // one upload: the decode tasks, the edges, the two tiers' task lists
+    Upload up;
+    D.place(up);
+    const size_t off_edges = up.add(edges, n_edges * sizeof(double)), off_short = up.add(tasks[0]), off_chunk = up.add(tasks[1]);
+    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, std::max<uint64_t>(1, region + (uint64_t)MAX_FRAME * D.spills_used)));
+    unsigned char *d = R.d;
+    up.stage(R.h);
+    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
+    if (!all_own) HIPCHK(ctx, hipMemsetAsync(d_out, 0, W * rows * sizeof(uint64_t), s));
+    double *scr = R.scratch;
+    const double *d_edges = (const double *)(d + off_edges);
+    const DevHistTask *d_short = (const DevHistTask *)(d + off_short), *d_chunk = (const DevHistTask *)(d + off_chunk);
+    for (size_t p = 0; p < P; ++p) {
+        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_HISTOGRAM);
+        if (rc) return rc;
+        hipError_t e = launch_hst_short(d_short + at[0][p], (uint32_t)(at[0][p + 1] - at[0][p]), scr, d_edges, n_edges, closed,
+                                        d_out, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_hst_short", e);
+        e = launch_hst_chunk(d_chunk + at[1][p], (uint32_t)(at[1][p + 1] - at[1][p]), scr, d_edges, n_edges, closed, d_out, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_hst_chunk", e);
+    }
+    HIPCHK(ctx, R.record(s));
+    return ATSC_OK;
+}
+extern "C" int atsc_histogram_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                          const uint64_t *begin, const uint64_t *count, uint32_t n_edges,
+                                          const double *edges, int closed, uint64_t *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    return histogram_dev(ctx, dp, d_body, n_windows, begin, count, n_edges, edges, closed, d_out, stream, 0);
+    ATSC_API_END
+}
+
+// Host call: window_host_call into histogram_dev.
+extern "C" int atsc_histogram_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                      const uint64_t *begin, const uint64_t *count, uint32_t n_edges, const double *edges,
+                                      int closed, uint64_t *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "histogram_windows: null argument");
+    const int rc = histogram_check_edges(ctx, n_edges, edges, closed);
+    if (rc) return rc;
+    if (n_windows == 0) return ATSC_OK;
+    const size_t out_bytes = n_windows * ((size_t)n_edges + 2) * sizeof(uint64_t);
+    return window_host_call(
+        ctx, "histogram_windows", body, body_len, has_count, n_windows, begin, count, out, out_bytes, false,
+        [&](bool any) {
+            if (!any) memset(out, 0, out_bytes);
+            return ATSC_OK;
+        },
+        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
+            return histogram_dev(ctx, dp, d_body, n_windows, begin2, count, n_edges, edges, closed, (uint64_t *)d_res, ws, org);
+        });
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
+// the same queries on a stream under construction (atsc_stream.cpp): its records, then the host call
 // ------------------------------------------------------------------------------------------
 // a stream without a frame holds only empty windows at 0
 static bool only_empty_at_zero(uint64_t n_windows, const uint64_t *begin, const uint64_t *count)
@@ -1106,5 +1302,26 @@ extern "C" int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, 
         return ATSC_OK;
     }
     return atsc_quantile_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, n_q, q, method, out);
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_histogram_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                             uint32_t n_edges, const double *edges, int closed, uint64_t *out)
+{
+    ATSC_API_BEGIN
+    if (!s || !edges || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
+    // (no context yet: the check comes before the pending chunks are compressed)
+    int rc = histogram_check_edges(nullptr, n_edges, edges, closed);
+    if (rc) return rc;
+    std::vector<uint8_t> body;
+    atsc_ctx *ctx = nullptr;
+    rc = stream_body(s, body, &ctx);
+    if (rc) return rc;
+    if (body.empty()) {
+        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
+        if (n_windows) memset(out, 0, n_windows * ((size_t)n_edges + 2) * sizeof(uint64_t));
+        return ATSC_OK;
+    }
+    return atsc_histogram_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, n_edges, edges, closed, out);
     ATSC_API_END
 }

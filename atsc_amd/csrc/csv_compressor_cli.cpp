@@ -3,7 +3,8 @@
 // .bro (+ .vsri index, + .wavbro samples) out; `-u` turns .bro + .vsri back into .wbro + .csv.
 // Compression and decompression run on the GPU; the index and the text formats are host code.
 //
-//   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]]]]
+//   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
+//                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]]]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
@@ -35,6 +36,10 @@ struct Args {
     std::vector<std::string> level_names;
     int method = ATSC_QUANTILE_LINEAR;  // --quantile-method
     bool have_method = false;
+    std::vector<double> edges;  // --histogram (with --step): the .agg.csv columns h0 .. h<n_edges>,hnan
+    bool have_hist = false;
+    int closed = ATSC_HIST_LEFT_CLOSED;  // --histogram-closed
+    bool have_closed = false;
 };
 
 constexpr int PANIC = 101;  // exit status of a Rust panic: every failure below is an expect()/panic!()
@@ -50,6 +55,9 @@ void usage()
             "      --step <S>                 with --from/--to: count,min,max,sum,first,last of every S seconds to .agg.csv\n"
             "      --quantiles <Q,Q,..>       with --step: also the levels Q (0..1, at most 64) of every bucket\n"
             "      --quantile-method <M>      linear | lower | higher | nearest [default: linear]\n"
+            "      --histogram <SPEC>         with --step: also every bucket's counts over the value bins of the edges\n"
+            "                                 E,E,.. (ascending, at most 1024) or LO:HI:N (N equal bins over LO..HI)\n"
+            "      --histogram-closed <SIDE>  left: E[k-1] <= v < E[k] | right: E[k-1] < v <= E[k] [default: left]\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -163,6 +171,41 @@ bool parse_method(const std::string &v, int &m)
         if (v == names[k]) { m = k; return true; }
     return false;
 }
+// --histogram SPEC: explicit edges E,E,.. or LO:HI:N, N equal bins over [LO, HI] (atsc_histogram_edges_uniform).
+// 0: fine; 1: unparsable, NaN or not ascending, or a bad uniform spec; 2: more than ATSC_HIST_MAX_EDGES edges
+int parse_histogram(const std::string &v, std::vector<double> &edges)
+{
+    edges.clear();
+    auto number = [](const std::string &t, double &x) {
+        char *e = nullptr;
+        x = strtod(t.c_str(), &e);
+        return !t.empty() && !isspace((unsigned char)t[0]) && !*e && x == x;
+    };
+    const size_t c1 = v.find(':');
+    if (c1 != std::string::npos) {
+        const size_t c2 = v.find(':', c1 + 1);
+        if (c2 == std::string::npos) return 1;
+        double lo, hi;
+        const std::string ns = v.substr(c2 + 1);
+        char *e = nullptr;
+        const unsigned long long n = strtoull(ns.c_str(), &e, 10);
+        if (!number(v.substr(0, c1), lo) || !number(v.substr(c1 + 1, c2 - c1 - 1), hi) || ns.empty() || *e ||
+            !isdigit((unsigned char)ns[0]))
+            return 1;
+        if (n >= ATSC_HIST_MAX_EDGES) return 2;
+        edges.resize(n + 1);
+        return atsc_histogram_edges_uniform(lo, hi, (uint32_t)n, edges.data()) ? 1 : 0;
+    }
+    for (size_t p = 0;;) {
+        const size_t c = v.find(',', p);
+        double x;
+        if (!number(v.substr(p, c == std::string::npos ? std::string::npos : c - p), x)) return 1;
+        if (!edges.empty() && !(edges.back() < x)) return 1;
+        edges.push_back(x);
+        if (c == std::string::npos) return edges.size() > (size_t)ATSC_HIST_MAX_EDGES ? 2 : 0;
+        p = c + 1;
+    }
+}
 int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *bro, uint64_t len)
 {
     atsc_vsri *index = nullptr;
@@ -186,18 +229,26 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
     if (nq) rc = atsc_quantile_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), (uint32_t)nq, a.levels.data(), a.method,
                                        qv.data());
     if (rc) { int e = die("quantiles", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    const uint64_t nh = a.have_hist ? a.edges.size() + 2 : 0;  // counters per bucket
+    std::vector<uint64_t> hv(nb * nh ? nb * nh : 1);
+    if (nh) rc = atsc_histogram_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), (uint32_t)a.edges.size(),
+                                        a.edges.data(), a.closed, hv.data());
+    if (rc) { int e = die("histogram", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
     atsc_ctx_destroy(ctx);
     atsc_free(bro);
     FILE *f = fopen(with_ext(output_base, "agg.csv").c_str(), "w");
     if (!f) return die("failed to write aggregates to file");
     fprintf(f, "timestamp,count,min,max,sum,first,last");
     for (const std::string &n : a.level_names) fprintf(f, ",q%s", n.c_str());
+    for (uint64_t j = 0; j + 1 < nh; ++j) fprintf(f, ",h%llu", (unsigned long long)j);
+    if (nh) fprintf(f, ",hnan");
     fprintf(f, "\n");
     for (uint64_t k = 0; k < nb; ++k) {
         fprintf(f, "%lld,%llu,%s,%s,%s,%s,%s", (long long)a.t0 + (long long)k * a.step, (unsigned long long)st[k].count,
                 debug_f64(st[k].min).c_str(), debug_f64(st[k].max).c_str(), debug_f64(st[k].sum).c_str(),
                 debug_f64(st[k].first).c_str(), debug_f64(st[k].last).c_str());
         for (uint64_t j = 0; j < nq; ++j) fprintf(f, ",%s", debug_f64(qv[k * nq + j]).c_str());
+        for (uint64_t j = 0; j < nh; ++j) fprintf(f, ",%llu", (unsigned long long)hv[k * nh + j]);
         fprintf(f, "\n");
     }
     if (fclose(f) != 0) return die("failed to write aggregates to file");
@@ -343,6 +394,27 @@ int main(int argc, char **argv)
             }
             a.have_method = true;
         }
+        else if (value("--histogram")) {
+            const int bad = parse_histogram(v, a.edges);
+            if (bad == 1) {
+                fprintf(stderr, "error: invalid value '%s' for '--histogram': expected ascending edges E,E,.. or LO:HI:N\n",
+                        v.c_str());
+                return 2;
+            }
+            if (bad == 2) {
+                fprintf(stderr, "error: invalid value for '--histogram': more than %d edges\n", (int)ATSC_HIST_MAX_EDGES);
+                return 2;
+            }
+            a.have_hist = true;
+        }
+        else if (value("--histogram-closed")) {
+            if (v != "left" && v != "right") {
+                fprintf(stderr, "error: invalid value '%s' for '--histogram-closed': left or right\n", v.c_str());
+                return 2;
+            }
+            a.closed = v == "right" ? ATSC_HIST_RIGHT_CLOSED : ATSC_HIST_LEFT_CLOSED;
+            a.have_closed = true;
+        }
         else if (value("--compressor")) { if (!parse_compressor(v, a.compressor)) { fprintf(stderr, "error: invalid value '%s' for '--compressor'\n", v.c_str()); return 2; } }
         else if (value("--error") || value("-e")) { if (!parse_int(v, 0, 50, a.error)) { fprintf(stderr, "error: invalid value '%s' for '--error': not in 0..=50\n", v.c_str()); return 2; } }
         else if (value("--compression-selection-sample-level") || value("-c")) { if (!parse_int(v, 0, 6, a.level)) { fprintf(stderr, "error: invalid value '%s' for '-c': not in 0..=6\n", v.c_str()); return 2; } }
@@ -364,6 +436,14 @@ int main(int argc, char **argv)
     }
     if (a.have_method && a.levels.empty()) {
         fprintf(stderr, "error: '--quantile-method' needs '--quantiles'\n");
+        return 2;
+    }
+    if (a.have_hist && !a.step) {
+        fprintf(stderr, "error: '--histogram' needs '--step'\n");
+        return 2;
+    }
+    if (a.have_closed && !a.have_hist) {
+        fprintf(stderr, "error: '--histogram-closed' needs '--histogram'\n");
         return 2;
     }
     a.window = have_from;

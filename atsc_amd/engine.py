@@ -31,6 +31,18 @@ def _levels(levels):
     return q, q.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def histogram_edges_uniform(lo, hi, n_bins):
+    """-> the n_bins + 1 edges of n_bins equal bins over [lo, hi]: numpy.linspace(lo, hi, n_bins + 1) bit for bit, or
+    AtscError(E_INVALID) where that is no strictly ascending edge set (atsc_histogram_edges_uniform; no GPU)"""
+    n_bins = int(n_bins)
+    if not 0 <= n_bins < 2 ** 32:
+        raise ValueError("n_bins outside uint32")
+    out = np.zeros(min(n_bins, capi.HIST_MAX_EDGES) + 1, dtype=np.float64)
+    capi.check(capi.lib().atsc_histogram_edges_uniform(float(lo), float(hi), n_bins,
+                                                       out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
 def bucket_windows(begin, count, bucket):
     """-> (begins, counts): [begin, begin + count) cut into windows of `bucket` samples, the last one shorter"""
     begin, count, bucket = int(begin), int(count), int(bucket)
@@ -159,6 +171,20 @@ class Context:
         rc = capi.lib().atsc_quantile_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
                                               len(wb), pb, pc, len(q), pq, int(method),
                                               out.ctypes.data_as(C.POINTER(C.c_double)))
+        capi.check(rc, self._h)
+        return out[: len(wb)]
+
+    def histogram_windows_host(self, records, begins, counts, edges, closed=capi.HIST_LEFT_CLOSED, has_count=False):
+        """-> (n_windows, n_edges + 2) uint64 array: per window [begins[i], begins[i] + counts[i]) of the decoded
+        records, the samples in each of the n_edges + 1 bins the ascending edges cut, then the NaN samples
+        (atsc_histogram_windows)"""
+        b = np.frombuffer(bytes(records), dtype=np.uint8)
+        wb, pb, wc, pc = _windows(begins, counts)
+        e, pe = _levels(edges)
+        out = np.zeros((max(len(wb), 1), len(e) + 2), dtype=np.uint64)
+        rc = capi.lib().atsc_histogram_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
+                                               len(wb), pb, pc, len(e), pe, int(closed),
+                                               out.ctypes.data_as(C.POINTER(C.c_uint64)))
         capi.check(rc, self._h)
         return out[: len(wb)]
 
@@ -298,6 +324,17 @@ class DPlan:
         rc = capi.lib().atsc_quantile_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
                                                   len(q), pq, int(method), C.c_void_p(d_out.data_ptr()),
                                                   C.c_void_p(stream))
+        capi.check(rc, self.ctx._h)
+
+    def histogram_windows(self, d_body, begins, counts, edges, d_out, closed=capi.HIST_LEFT_CLOSED, stream=0):
+        """Enqueues the bin counts of the windows [begins[i], begins[i] + counts[i]) into d_out, a 64-bit integer
+        device tensor of at least n_windows * (n_edges + 2) elements, window-major (atsc_histogram_windows_dev)"""
+        b, pb, c, pc = _windows(begins, counts)
+        e, pe = _levels(edges)
+        assert d_out.is_contiguous() and d_out.element_size() == 8 and d_out.numel() >= len(b) * (len(e) + 2)
+        rc = capi.lib().atsc_histogram_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
+                                                   len(e), pe, int(closed), C.c_void_p(d_out.data_ptr()),
+                                                   C.c_void_p(stream))
         capi.check(rc, self.ctx._h)
 
 

@@ -108,6 +108,15 @@ class CompressedStream:
                                                            out.ctypes.data_as(C.POINTER(C.c_double))), self.ctx._h)
         return out[: len(wb)]
 
+    def histogram_windows(self, begins, counts, edges, closed=capi.HIST_LEFT_CLOSED):
+        """-> (n_windows, n_edges + 2) uint64 array of the windows' bin counts (atsc_stream_histogram_windows)"""
+        wb, pb, wc, pc = _windows(begins, counts)
+        e, pe = _levels(edges)
+        out = np.zeros((max(len(wb), 1), len(e) + 2), dtype=np.uint64)
+        capi.check(capi.lib().atsc_stream_histogram_windows(self._h, len(wb), pb, pc, len(e), pe, int(closed),
+                                                            out.ctypes.data_as(C.POINTER(C.c_uint64))), self.ctx._h)
+        return out[: len(wb)]
+
 
 def compress_data(ctx, vec, compressor=capi.AUTO, error=3, sample_level=0):
     """atsc/src/main.rs:130-165"""
@@ -169,6 +178,21 @@ def quantile_data_windows(ctx, bro, begins, counts, levels, method=capi.QUANTILE
     r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
     rc = capi.lib().atsc_quantile_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
                                           len(q), pq, int(method), out.ctypes.data_as(C.POINTER(C.c_double)))
+    capi.check(rc, ctx._h)
+    return out[: len(wb)]
+
+
+def histogram_data_windows(ctx, bro, begins, counts, edges, closed=capi.HIST_LEFT_CLOSED):
+    """-> (n_windows, n_edges + 2) uint64 array: bin counts of windows of decompress_data(ctx, bro): atsc_bro_open, then
+    atsc_histogram_windows over the records"""
+    b = np.frombuffer(bytes(bro), dtype=np.uint8)
+    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
+    wb, pb, wc, pc = _windows(begins, counts)
+    e, pe = _levels(edges)
+    out = np.zeros((max(len(wb), 1), len(e) + 2), dtype=np.uint64)
+    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
+    rc = capi.lib().atsc_histogram_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
+                                           len(e), pe, int(closed), out.ctypes.data_as(C.POINTER(C.c_uint64)))
     capi.check(rc, ctx._h)
     return out[: len(wb)]
 

@@ -319,7 +319,8 @@ int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len
 /* Upper bound in bytes on the decoded-sample scratch the aggregate calls hold; 0 (the default) gives pieces of 16 Mi
  * samples (128 MiB, plus 2 MiB of room for two large frames cut by a piece's ends where a frame longer than 4096 samples
  * is touched).  A budget below what one piece needs is raised to that minimum, never an error.  It bounds the quantile
- * calls below too, whose windows must each fit one piece. */
+ * calls below too, whose windows must each fit one piece, and the histogram calls (atsc_histogram_windows_dev), whose
+ * windows may be of any length. */
 int atsc_ctx_set_aggregate_scratch(atsc_ctx *ctx, uint64_t bytes);
 
 /* Windowed quantiles: exact order statistics of windows [begin, begin + count) of the decoded stream (the indices of
@@ -354,6 +355,47 @@ int atsc_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len,
                           const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
                           double *out);
 
+/* Windowed histograms: how the samples of windows [begin, begin + count) of the decoded stream (the indices of
+ * atsc_decompress_frames) are distributed over value bins, from the same decoded samples as the window decode.  The
+ * bins are given by n_edges ascending edges, the same for every window.  For window i:
+ *   a row of n_edges + 2 counters at out[i * (n_edges + 2) ..]: bins 0 .. n_edges, then the number of NaN samples;
+ *   samples are compared with the edges as values (-0.0 equals +0.0); +-Inf samples are counted like any other value;
+ *   LEFT_CLOSED   a non-NaN sample v goes to bin k = the number of edges <= v: bin k holds edges[k-1] <= v < edges[k],
+ *                 bin 0 v < edges[0], bin n_edges v >= edges[n_edges-1] (numpy.searchsorted(edges, v, side="right"));
+ *   RIGHT_CLOSED  k = the number of edges < v: bin k holds edges[k-1] < v <= edges[k], the reading of Prometheus' `le`
+ *                 buckets (side="left").
+ * A row's counters always sum to count[i].  The call writes every row whole: the caller does not have to clear the
+ * result, and an empty window gives a row of zeros.  The result depends only on the window's samples and the edges,
+ * not on the other windows, their order, the budget or the device.  A window may be longer than one piece of the
+ * decoded-sample scratch that atsc_ctx_set_aggregate_scratch bounds: counts add across pieces, there is no
+ * ATSC_E_CAPACITY case.
+ * Validation (ATSC_E_INVALID, nothing written): a null argument, a window beyond the stream, n_edges == 0 or
+ * n_edges > ATSC_HIST_MAX_EDGES, an edge that is NaN, edges that are not strictly ascending as values (0.0, -0.0 is
+ * not), an unknown `closed`, a result pointer that is not 8-byte aligned.  +-Inf edges are allowed; n_windows == 0 is
+ * valid; windows may overlap and come in any order.  The edges, n_edges and `closed` are checked before any GPU work. */
+enum { ATSC_HIST_LEFT_CLOSED = 0, ATSC_HIST_RIGHT_CLOSED = 1 };
+enum { ATSC_HIST_MAX_EDGES = 1024 };
+/* begin / count / edges are HOST arrays; d_body and d_out (n_windows * (n_edges + 2) u64, 8-byte aligned) are device
+ * memory.  Enqueued on `stream`, not synchronised.  A malformed payload inside a window sets the plan's status word.
+ * The plan keeps the call's tables and scratch: the next histogram call on the same plan waits (host side) until this
+ * one's work is done; atsc_dplan_destroy frees them. */
+int atsc_histogram_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                               const uint64_t *begin, const uint64_t *count, uint32_t n_edges, const double *edges,
+                               int closed, uint64_t *d_out, void *stream);
+/* Host bytes in, host rows out (n_windows * (n_edges + 2) u64), synchronous; walks and uploads only the touched
+ * records, as atsc_aggregate_windows does.  ATSC_E_FORMAT (nothing written) for a malformed payload inside a window. */
+int atsc_histogram_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                           const uint64_t *begin, const uint64_t *count, uint32_t n_edges, const double *edges,
+                           int closed, uint64_t *out);
+/* The n_bins + 1 edges of n_bins equal bins over [lo, hi], host only (no GPU):
+ *   edges[k] = (double)k * ((hi - lo) / (double)n_bins) + lo for k < n_bins (one divide, then one multiply and one add
+ *   per edge, not fused), edges[n_bins] = hi: numpy.linspace(lo, hi, n_bins + 1) bit for bit.
+ * ATSC_E_INVALID with nothing written: edges == NULL, lo or hi not finite, hi <= lo, n_bins == 0 or
+ * n_bins + 1 > ATSC_HIST_MAX_EDGES, a step of 0, or rounded edges that are not strictly ascending (a width of a few
+ * ulps of lo).  Unlike numpy.histogram, whose last bin is closed on both sides, a sample equal to hi lands in the
+ * overflow bin (bin n_bins + 1 of the row) under ATSC_HIST_LEFT_CLOSED. */
+int atsc_histogram_edges_uniform(double lo, double hi, uint32_t n_bins, double *edges);
+
 /* ------------------------------------------------------------------------ */
 /* CompressedStream mirror (atsc/src/data.rs:29-110)                          */
 /* ------------------------------------------------------------------------ */
@@ -384,6 +426,9 @@ int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint
 /* atsc_quantile_windows over the stream's frames */
 int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint32_t n_q, const double *q, int method, double *out);
+/* atsc_histogram_windows over the stream's frames */
+int atsc_stream_histogram_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                  uint32_t n_edges, const double *edges, int closed, uint64_t *out);
 void atsc_free(void *p);
 
 /* compress_data / decompress_data of the atsc CLI (atsc/src/main.rs:130-172): clean (drop NaN/Inf),
