@@ -3,7 +3,7 @@
 //
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
-//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]]]]
+//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -41,6 +41,7 @@ struct Args {
     bool have_hist = false;
     int closed = ATSC_HIST_LEFT_CLOSED;  // --histogram-closed
     bool have_closed = false;
+    bool moments = false;  // --moments (with --buckets): the .agg.csv columns mean,stdvar,stddev,slope,intercept
 };
 
 void usage()
@@ -57,6 +58,8 @@ void usage()
             "      --histogram <SPEC>         with --buckets: also every bucket's counts over the value bins of the edges\n"
             "                                 E,E,.. (ascending, at most 1024) or LO:HI:N (N equal bins over LO..HI)\n"
             "      --histogram-closed <SIDE>  left: E[k-1] <= v < E[k] | right: E[k-1] < v <= E[k] [default: left]\n"
+            "      --moments                  with --buckets: also every bucket's mean, stdvar, stddev (population forms) and\n"
+            "                                 least-squares slope (value units per sample) and intercept (at its first sample)\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -200,12 +203,18 @@ int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const u
     if (nh) rc = atsc_histogram_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), (uint32_t)a.edges.size(),
                                         a.edges.data(), a.closed, hv.data());
     if (rc) return rc;
+    std::vector<atsc_window_moments> mv(a.moments && nb ? nb : 1);
+    std::vector<atsc_window_fit> fv(mv.size());
+    if (a.moments) rc = atsc_moments_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), mv.data());
+    if (!rc && a.moments) rc = atsc_moments_fit(mv.data(), nb, fv.data());
+    if (rc) return rc;
     FILE *f = fopen(with_ext(path, "agg.csv").c_str(), "w");
     if (!f) return ATSC_E_IO;
     fprintf(f, "begin,count,min,max,sum,first,last");
     for (const std::string &n : a.level_names) fprintf(f, ",q%s", n.c_str());
     for (uint64_t j = 0; j + 1 < nh; ++j) fprintf(f, ",h%llu", (unsigned long long)j);
     if (nh) fprintf(f, ",hnan");
+    if (a.moments) fprintf(f, ",mean,stdvar,stddev,slope,intercept");
     fprintf(f, "\n");
     for (uint64_t k = 0; k < nb; ++k) {
         fprintf(f, "%llu,%llu,%s,%s,%s,%s,%s", (unsigned long long)b[k], (unsigned long long)st[k].count,
@@ -213,6 +222,9 @@ int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const u
                 debug_f64(st[k].first).c_str(), debug_f64(st[k].last).c_str());
         for (uint64_t j = 0; j < nq; ++j) fprintf(f, ",%s", debug_f64(qv[k * nq + j]).c_str());
         for (uint64_t j = 0; j < nh; ++j) fprintf(f, ",%llu", (unsigned long long)hv[k * nh + j]);
+        if (a.moments)
+            fprintf(f, ",%s,%s,%s,%s,%s", debug_f64(fv[k].mean).c_str(), debug_f64(fv[k].variance).c_str(),
+                    debug_f64(fv[k].stddev).c_str(), debug_f64(fv[k].slope).c_str(), debug_f64(fv[k].intercept).c_str());
         fprintf(f, "\n");
     }
     return fclose(f) == 0 ? ATSC_OK : ATSC_E_IO;
@@ -396,6 +408,7 @@ int main(int argc, char **argv)
             a.closed = v == "right" ? ATSC_HIST_RIGHT_CLOSED : ATSC_HIST_LEFT_CLOSED;
             a.have_closed = true;
         }
+        else if (s == "--moments") a.moments = true;
         else if (!s.empty() && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); usage(); return 2; }
         else a.input = s;
     }
@@ -406,6 +419,7 @@ int main(int argc, char **argv)
     if (a.have_method && a.levels.empty()) { fprintf(stderr, "error: '--quantile-method' needs '--quantiles'\n"); return 2; }
     if (a.have_hist && !a.buckets) { fprintf(stderr, "error: '--histogram' needs '--buckets'\n"); return 2; }
     if (a.have_closed && !a.have_hist) { fprintf(stderr, "error: '--histogram-closed' needs '--histogram'\n"); return 2; }
+    if (a.moments && !a.buckets) { fprintf(stderr, "error: '--moments' needs '--buckets'\n"); return 2; }
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) { fprintf(stderr, "[ERROR] %s: No such file or directory\n", a.input.c_str()); return 1; }
     atsc_ctx *ctx = nullptr;

@@ -1727,6 +1727,7 @@ extern "C" void atsc_dplan_destroy(atsc_dplan *p)
     p->agg.release(p->ctx);
     p->qnt.release(p->ctx);
     p->hst.release(p->ctx);
+    p->mom.release(p->ctx);
     pool_free(p->ctx, p->d_frames);
     pool_free(p->ctx, p->d_ids);
     pool_free(p->ctx, p->d_status);

@@ -171,9 +171,9 @@ struct atsc_dplan {
     // samples [h_frames[f].out_off, h_frames[f + 1].out_off or n_samples)
     std::vector<atsc::DevDFrame> h_frames;
     std::vector<int> h_cls;
-    // what the last atsc_decompress_windows_dev, atsc_aggregate_windows_dev, atsc_quantile_windows_dev and
-    // atsc_histogram_windows_dev call own
-    mutable atsc::QueryRes win, agg, qnt, hst;
+    // what the last atsc_decompress_windows_dev, atsc_aggregate_windows_dev, atsc_quantile_windows_dev,
+    // atsc_histogram_windows_dev and atsc_moments_windows_dev call own
+    mutable atsc::QueryRes win, agg, qnt, hst, mom;
 };
 
 namespace atsc {

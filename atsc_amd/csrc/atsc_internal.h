@@ -206,6 +206,19 @@ struct DevAggComb {
     uint32_t n, g, win, final_;
 };
 
+// windowed moments (atsc_moments_windows_dev, atsc_moments.hip): the aggregates' tiles, pieces and combine passes
+// (DevAggComb) over nodes of the centred moments of value and position
+// the partial of a tile or of a group of tiles: the node (n, mx, M2x, mt, M2t, C) of include/atsc_hip.h
+struct DevMomPart {
+    double mx, m2x, mt, m2t, c;
+    uint64_t n;
+};
+// one tile of k_mom_tiles: slots [lo, hi) of the tile whose slot 0 is scratch[src] and sample t0 of the stream -> part[dst]
+struct DevMomTile {
+    uint64_t src, dst, t0;
+    uint32_t lo, hi;
+};
+
 // windowed quantiles (atsc_quantile_windows_dev, atsc_quantile.hip).  The tier of a window is chosen from its length:
 // short (one wavefront, keys in registers), medium (one workgroup, keys in LDS), long (MSD radix select, 8-bit digits)
 constexpr uint32_t QNT_MAX_LEVELS = 64;

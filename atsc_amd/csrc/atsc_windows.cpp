@@ -1,10 +1,11 @@
-// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, quantiles and histograms of ranges of
-// the decoded stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
+// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, quantiles and histograms of ranges
+// of the decoded stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
 // and the pool are atsc_host.cpp's (atsc_host_private.h); nothing in atsc_host.cpp or atsc_stream.cpp calls into this file.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -43,6 +44,11 @@ __attribute__((weak)) hipError_t launch_hst_short(const DevHistTask *tasks, uint
 __attribute__((weak)) hipError_t launch_hst_chunk(const DevHistTask *tasks, uint32_t n, const double *scratch,
                                                   const double *edges, uint32_t n_edges, int closed, uint64_t *out,
                                                   hipStream_t s);
+// the windowed moments' reduce kernels (atsc_moments.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_mom_tiles(const DevMomTile *tasks, uint32_t n, const double *scratch,
+                                                  DevMomPart *part, hipStream_t s);
+__attribute__((weak)) hipError_t launch_mom_combine(const DevAggComb *tasks, uint32_t n, DevMomPart *part,
+                                                    const uint64_t *begin, void *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -249,6 +255,8 @@ static const DecodeCaller BY_QUANTILE = {"launch k_decompress (quantile)", "laun
                                          "launch k_window_gather (quantile)"};
 static const DecodeCaller BY_HISTOGRAM = {"launch k_decompress (histogram)", "launch k_decompress_large (histogram)",
                                           "launch k_window_gather (histogram)"};
+static const DecodeCaller BY_MOMENTS = {"launch k_decompress (moments)", "launch k_decompress_large (moments)",
+                                        "launch k_window_gather (moments)"};
 
 // Enqueues one piece's decode (d: the device copy of the upload).  out: the base the tasks' destinations count from;
 // the copies go from gat_src to gat_dst.
@@ -508,7 +516,7 @@ extern "C" int atsc_decompress_window(atsc_ctx *ctx, const uint8_t *body, uint64
 }
 
 // ------------------------------------------------------------------------------------------
-// decoded samples of window pieces in scratch (the aggregate, the quantile and the histogram calls)
+// decoded samples of window pieces in scratch (the aggregate, the moments, the quantile and the histogram calls)
 // ------------------------------------------------------------------------------------------
 // Decoded samples reach the reduce and selection kernels through one scratch region, piece after piece in stream order.
 static const uint64_t AGG_MIN_PIECE = 32ull * AGG_TILE;  // the least a piece holds, whatever the budget
@@ -630,22 +638,67 @@ static void agg_empty_record(atsc_window_stats &r)
     r.sum = 0.0;
 }
 
-// The device call.  Host work: covering intervals, pieces, the decode tasks of every piece (one per touched frame: its
+// What the two reductions over tiles differ in: the aggregates (atsc_aggregate.hip) and the moments (atsc_moments.hip).
+//   Tile, tile(t, k)   the tile kernel's task, from the plan's DevAggTile of tile k of the stream
+//   PART               bytes of a partial
+//   SIDE               the table both kernels share beside the partials: the windows' first / last samples, which the
+//                      tile kernel writes (device only), or the windows' begins in the stream's index (uploaded)
+struct AggQuery {
+    using Tile = DevAggTile;
+    static constexpr const char *CALL = "aggregate_windows", *RES_NAME = "d_stats", *NO_KERNELS = "no aggregate kernels",
+                                *TILES = "launch k_agg_tiles", *COMBINE = "launch k_agg_combine";
+    static constexpr size_t PART = sizeof(DevAggPart);
+    static constexpr bool SIDE_BEGINS = false;
+    static const DecodeCaller &who() { return BY_AGGREGATE; }
+    static bool have() { return launch_agg_tiles && launch_agg_combine; }
+    static QueryRes &res(const atsc_dplan *dp) { return dp->agg; }
+    static Tile tile(const DevAggTile &t, uint64_t) { return t; }
+    static hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *side, hipStream_t s)
+    {
+        return launch_agg_tiles(t, n, scr, (DevAggPart *)part, (double *)side, s);
+    }
+    static hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *side, void *out, hipStream_t s)
+    {
+        return launch_agg_combine(c, n, (DevAggPart *)part, (const double *)side, out, s);
+    }
+};
+struct MomQuery {
+    using Tile = DevMomTile;
+    static constexpr const char *CALL = "moments_windows", *RES_NAME = "d_out", *NO_KERNELS = "no moments kernels",
+                                *TILES = "launch k_mom_tiles", *COMBINE = "launch k_mom_combine";
+    static constexpr size_t PART = sizeof(DevMomPart);
+    static constexpr bool SIDE_BEGINS = true;
+    static const DecodeCaller &who() { return BY_MOMENTS; }
+    static bool have() { return launch_mom_tiles && launch_mom_combine; }
+    static QueryRes &res(const atsc_dplan *dp) { return dp->mom; }
+    static Tile tile(const DevAggTile &t, uint64_t k) { return Tile{t.src, t.dst, k * AGG_TILE, t.lo, t.hi}; }
+    static hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s)
+    {
+        return launch_mom_tiles(t, n, scr, (DevMomPart *)part, s);
+    }
+    static hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *side, void *out, hipStream_t s)
+    {
+        return launch_mom_combine(c, n, (DevMomPart *)part, (const uint64_t *)side, out, s);
+    }
+};
+
+// The device call of a reduction over tiles (Q: AggQuery or MomQuery; the kernels named below are the aggregates').
+// Host work: covering intervals, pieces, the decode tasks of every piece (one per touched frame: its
 // covered samples' hull in the piece), the tile tasks (a full tile that windows cover past their first tile and before
 // their last one is reduced once, into a shared partial; every window's first and last tile are reduced for it alone)
 // and the combine passes (groups of 64 partials until one is left per window).  All of it goes up in one copy; then,
 // per piece, the window decode's launchers into scratch and k_agg_tiles, and k_agg_combine once per pass.
 // org: the stream index of the plan's first sample (a plan of the touched records only, in the host call): tiles lie at
 // multiples of AGG_TILE in the stream's index, not the plan's.  Indices below are the stream's unless named otherwise.
-static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
-                         const uint64_t *begin, const uint64_t *count, atsc_window_stats *d_stats, void *stream, uint64_t org)
+template <class Q>
+static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+                      const uint64_t *count, void *d_out, void *stream, uint64_t org)
 {
-    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_stats)))
-        return fail(ctx, ATSC_E_INVALID, "aggregate_windows: null argument");
-    int rc = check_windows(ctx, "aggregate_windows", dp, d_stats, "d_stats", n_windows, begin, count, 0xfffffffeull);
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_out)))
+        return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
+    int rc = check_windows(ctx, Q::CALL, dp, d_out, Q::RES_NAME, n_windows, begin, count, 0xfffffffeull);
     if (rc || n_windows == 0) return rc;
-    if (!launch_decompress_window || !launch_window_gather || !launch_agg_tiles || !launch_agg_combine)
-        return fail(ctx, ATSC_E_UNSUPPORTED, "aggregate_windows: no aggregate kernels");
+    if (!launch_decompress_window || !launch_window_gather || !Q::have()) return fail_in(ctx, ATSC_E_UNSUPPORTED, Q::CALL, Q::NO_KERNELS);
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const uint64_t T = AGG_TILE, W = n_windows;
@@ -742,46 +795,52 @@ static int aggregate_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
     std::vector<size_t> tile_at(pcs.size());
     std::vector<uint32_t> tile_n(pcs.size());
     DecodeTasks D;
-    std::vector<DevAggTile> tiles;
+    std::vector<typename Q::Tile> tiles;
     tiles.reserve(tt.size());
     size_t ci = 0, ti = 0;
     for (size_t p = 0; p < pcs.size(); ++p) {
         tile_at[p] = tiles.size();
         if (!emit_piece_decode(dp, org, cov, ci, pcs[p].k0 * T, pcs[p].k1 * T, region, D, pdec[p]))
-            return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (spill slots)");
+            return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "internal error (spill slots)");
         for (; ti < tt.size() && tt[ti].k < pcs[p].k1; ++ti) {
             DevAggTile t = tt[ti].t;
             t.src = (tt[ti].k - pcs[p].k0) * T;
-            tiles.push_back(t);
+            tiles.push_back(Q::tile(t, tt[ti].k));
         }
         tile_n[p] = (uint32_t)(tiles.size() - tile_at[p]);
     }
-    if (ti != tt.size()) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: internal error (tile outside the pieces)");
-    QueryRes &R = dp->agg;
+    if (ti != tt.size()) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "internal error (tile outside the pieces)");
+    std::vector<uint64_t> wb;  // the windows' begins in the stream's index
+    if (Q::SIDE_BEGINS) {
+        wb.resize(W);
+        for (uint64_t i = 0; i < W; ++i) wb[i] = org + begin[i];
+    }
+    QueryRes &R = Q::res(dp);
     HIPCHK(ctx, R.wait());
-    // one upload: the decode tasks, tile tasks, combine tasks; behind them (device only) the partials and the windows'
-    // first / last samples
+    // one upload: the decode tasks, tile tasks, combine tasks (and the begins); behind them (device only) the partials
+    // (and the windows' first / last samples)
     Upload up;
     D.place(up);
     const size_t off_tiles = up.add(tiles), off_comb = up.add(comb);
-    const size_t off_part = up.device_only(part_n * sizeof(DevAggPart)), off_fl = up.device_only(2 * W * sizeof(double));
+    const size_t off_begins = Q::SIDE_BEGINS ? up.add(wb) : 0;
+    const size_t off_part = up.device_only(part_n * Q::PART);
+    const size_t off_side = Q::SIDE_BEGINS ? off_begins : up.device_only(2 * W * sizeof(double));
     HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, region + (uint64_t)MAX_FRAME * D.spills_used));
     unsigned char *d = R.d;
     up.stage(R.h);
     HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
     double *scr = R.scratch;
-    DevAggPart *part = (DevAggPart *)(d + off_part);
-    double *fl = (double *)(d + off_fl);
+    void *part = d + off_part, *side = d + off_side;
     for (size_t p = 0; p < pcs.size(); ++p) {
-        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_AGGREGATE);
+        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, Q::who());
         if (rc) return rc;
-        const hipError_t e = launch_agg_tiles((const DevAggTile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, fl, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_agg_tiles", e);
+        const hipError_t e = Q::tiles((const typename Q::Tile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, side, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, Q::TILES, e);
     }
     for (size_t q = 0; q + 1 < pass_at.size(); ++q) {
-        const hipError_t e = launch_agg_combine((const DevAggComb *)(d + off_comb) + pass_at[q], (uint32_t)(pass_at[q + 1] - pass_at[q]),
-                                                part, fl, d_stats, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_agg_combine", e);
+        const hipError_t e = Q::combine((const DevAggComb *)(d + off_comb) + pass_at[q], (uint32_t)(pass_at[q + 1] - pass_at[q]),
+                                        part, side, d_out, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, Q::COMBINE, e);
     }
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
@@ -791,11 +850,11 @@ extern "C" int atsc_aggregate_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, c
                                           void *stream)
 {
     ATSC_API_BEGIN
-    return aggregate_dev(ctx, dp, d_body, n_windows, begin, count, d_stats, stream, 0);
+    return reduce_dev<AggQuery>(ctx, dp, d_body, n_windows, begin, count, d_stats, stream, 0);
     ATSC_API_END
 }
 
-// Host call: window_host_call into aggregate_dev.
+// Host call: window_host_call into reduce_dev.
 extern "C" int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
                                       const uint64_t *begin, const uint64_t *count, atsc_window_stats *out)
 {
@@ -810,9 +869,73 @@ extern "C" int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64
             return ATSC_OK;
         },
         [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
-            return aggregate_dev(ctx, dp, d_body, n_windows, begin2, count, (atsc_window_stats *)d_res, ws, org);
+            return reduce_dev<AggQuery>(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org);
         });
     ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
+// windowed moments: centred moments of value and position of sample windows (atsc_moments.hip)
+// ------------------------------------------------------------------------------------------
+static void mom_empty_record(atsc_window_moments &r)
+{
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    r.count = 0;
+    r.mean = r.m2 = r.t_mean = r.t_m2 = r.c_tx = nan;
+}
+
+// The device call: reduce_dev with the moments' kernels.
+extern "C" int atsc_moments_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                        const uint64_t *begin, const uint64_t *count, atsc_window_moments *d_out,
+                                        void *stream)
+{
+    ATSC_API_BEGIN
+    return reduce_dev<MomQuery>(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    ATSC_API_END
+}
+
+// Host call: window_host_call into reduce_dev.
+extern "C" int atsc_moments_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                    const uint64_t *begin, const uint64_t *count, atsc_window_moments *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "moments_windows: null argument");
+    if (n_windows == 0) return ATSC_OK;
+    return window_host_call(
+        ctx, "moments_windows", body, body_len, has_count, n_windows, begin, count, out,
+        n_windows * sizeof(atsc_window_moments), false,
+        [&](bool any) {
+            for (uint64_t i = 0; !any && i < n_windows; ++i) mom_empty_record(out[i]);
+            return ATSC_OK;
+        },
+        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
+            return reduce_dev<MomQuery>(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org);
+        });
+    ATSC_API_END
+}
+
+// Host only: what a caller reads off the moments.  Each line is one rounded operation, as include/atsc_hip.h states it.
+extern "C" int atsc_moments_fit(const atsc_window_moments *m, uint64_t n, atsc_window_fit *out)
+{
+    if (n && (!m || !out)) return ATSC_E_INVALID;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (uint64_t i = 0; i < n; ++i) {
+        const atsc_window_moments &a = m[i];
+        atsc_window_fit &r = out[i];
+        if (a.count == 0) {
+            r.mean = r.variance = r.stddev = r.sample_variance = r.sample_stddev = r.slope = r.intercept = nan;
+            continue;
+        }
+        r.mean = a.mean;
+        r.variance = a.m2 / (double)a.count;
+        r.stddev = std::sqrt(r.variance);
+        r.sample_variance = a.count < 2 ? nan : a.m2 / (double)(a.count - 1);
+        r.sample_stddev = std::sqrt(r.sample_variance);
+        r.slope = a.t_m2 > 0.0 ? a.c_tx / a.t_m2 : nan;
+        const double st = r.slope * a.t_mean;
+        r.intercept = a.mean - st;
+    }
+    return ATSC_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -835,7 +958,7 @@ static int quantile_check_levels(atsc_ctx *ctx, uint32_t n_q, const double *q, i
 // start; pieces overlap where windows do).  Per piece: the decode tasks of its windows' union (emit_piece_decode), then
 // the tiers by window length: short and medium windows one launch each (medium: one per power-of-two key count), long
 // windows QNT_PASSES histogram + pick launches whatever their number.  Everything goes up in one copy; nothing waits
-// on the host between pieces.  org: the stream index of the plan's first sample (see aggregate_dev).
+// on the host between pieces.  org: the stream index of the plan's first sample (see reduce_dev).
 static int quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
                         const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
                         double *d_out, void *stream, uint64_t org)
@@ -1080,7 +1203,7 @@ extern "C" int atsc_histogram_edges_uniform(double lo, double hi, uint32_t n_bin
 // one-wavefront tier, so a call of many short windows is one launch of few workgroups).  A window with a single task
 // owns its row (HST_OWN: stored whole); when any window has none or several, the result is cleared first and the
 // tasks add.  Everything, the edges included, goes up in one copy; nothing waits on the host between pieces.
-// org: the stream index of the plan's first sample (see aggregate_dev).
+// org: the stream index of the plan's first sample (see reduce_dev).
 static int histogram_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
                          const uint64_t *begin, const uint64_t *count, uint32_t n_edges, const double *edges, int closed,
                          uint64_t *d_out, void *stream, uint64_t org)
@@ -1281,6 +1404,24 @@ extern "C" int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows,
         return ATSC_OK;
     }
     return atsc_aggregate_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                           atsc_window_moments *out)
+{
+    ATSC_API_BEGIN
+    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
+    std::vector<uint8_t> body;
+    atsc_ctx *ctx = nullptr;
+    const int rc = stream_body(s, body, &ctx);
+    if (rc) return rc;
+    if (body.empty()) {
+        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
+        for (uint64_t i = 0; i < n_windows; ++i) mom_empty_record(out[i]);
+        return ATSC_OK;
+    }
+    return atsc_moments_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
     ATSC_API_END
 }
 

@@ -4,7 +4,7 @@
 // Compression and decompression run on the GPU; the index and the text formats are host code.
 //
 //   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
-//                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]]]]]
+//                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments]]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
@@ -40,6 +40,7 @@ struct Args {
     bool have_hist = false;
     int closed = ATSC_HIST_LEFT_CLOSED;  // --histogram-closed
     bool have_closed = false;
+    bool moments = false;  // --moments (with --step): the .agg.csv columns mean,stdvar,stddev,slope,intercept
 };
 
 constexpr int PANIC = 101;  // exit status of a Rust panic: every failure below is an expect()/panic!()
@@ -58,6 +59,9 @@ void usage()
             "      --histogram <SPEC>         with --step: also every bucket's counts over the value bins of the edges\n"
             "                                 E,E,.. (ascending, at most 1024) or LO:HI:N (N equal bins over LO..HI)\n"
             "      --histogram-closed <SIDE>  left: E[k-1] <= v < E[k] | right: E[k-1] < v <= E[k] [default: left]\n"
+            "      --moments                  with --step: also every bucket's mean, stdvar, stddev (population forms) and\n"
+            "                                 least-squares slope (value units per SAMPLE, not per second) and intercept\n"
+            "                                 (at its first sample)\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -234,6 +238,11 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
     if (nh) rc = atsc_histogram_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), (uint32_t)a.edges.size(),
                                         a.edges.data(), a.closed, hv.data());
     if (rc) { int e = die("histogram", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    std::vector<atsc_window_moments> mv(a.moments && nb ? nb : 1);
+    std::vector<atsc_window_fit> fv(mv.size());
+    if (a.moments) rc = atsc_moments_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), mv.data());
+    if (!rc && a.moments) rc = atsc_moments_fit(mv.data(), nb, fv.data());
+    if (rc) { int e = die("moments", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
     atsc_ctx_destroy(ctx);
     atsc_free(bro);
     FILE *f = fopen(with_ext(output_base, "agg.csv").c_str(), "w");
@@ -242,6 +251,7 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
     for (const std::string &n : a.level_names) fprintf(f, ",q%s", n.c_str());
     for (uint64_t j = 0; j + 1 < nh; ++j) fprintf(f, ",h%llu", (unsigned long long)j);
     if (nh) fprintf(f, ",hnan");
+    if (a.moments) fprintf(f, ",mean,stdvar,stddev,slope,intercept");
     fprintf(f, "\n");
     for (uint64_t k = 0; k < nb; ++k) {
         fprintf(f, "%lld,%llu,%s,%s,%s,%s,%s", (long long)a.t0 + (long long)k * a.step, (unsigned long long)st[k].count,
@@ -249,6 +259,9 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
                 debug_f64(st[k].first).c_str(), debug_f64(st[k].last).c_str());
         for (uint64_t j = 0; j < nq; ++j) fprintf(f, ",%s", debug_f64(qv[k * nq + j]).c_str());
         for (uint64_t j = 0; j < nh; ++j) fprintf(f, ",%llu", (unsigned long long)hv[k * nh + j]);
+        if (a.moments)
+            fprintf(f, ",%s,%s,%s,%s,%s", debug_f64(fv[k].mean).c_str(), debug_f64(fv[k].variance).c_str(),
+                    debug_f64(fv[k].stddev).c_str(), debug_f64(fv[k].slope).c_str(), debug_f64(fv[k].intercept).c_str());
         fprintf(f, "\n");
     }
     if (fclose(f) != 0) return die("failed to write aggregates to file");
@@ -415,6 +428,7 @@ int main(int argc, char **argv)
             a.closed = v == "right" ? ATSC_HIST_RIGHT_CLOSED : ATSC_HIST_LEFT_CLOSED;
             a.have_closed = true;
         }
+        else if (s == "--moments") a.moments = true;
         else if (value("--compressor")) { if (!parse_compressor(v, a.compressor)) { fprintf(stderr, "error: invalid value '%s' for '--compressor'\n", v.c_str()); return 2; } }
         else if (value("--error") || value("-e")) { if (!parse_int(v, 0, 50, a.error)) { fprintf(stderr, "error: invalid value '%s' for '--error': not in 0..=50\n", v.c_str()); return 2; } }
         else if (value("--compression-selection-sample-level") || value("-c")) { if (!parse_int(v, 0, 6, a.level)) { fprintf(stderr, "error: invalid value '%s' for '-c': not in 0..=6\n", v.c_str()); return 2; } }
@@ -444,6 +458,10 @@ int main(int argc, char **argv)
     }
     if (a.have_closed && !a.have_hist) {
         fprintf(stderr, "error: '--histogram-closed' needs '--histogram'\n");
+        return 2;
+    }
+    if (a.moments && !a.step) {
+        fprintf(stderr, "error: '--moments' needs '--step'\n");
         return 2;
     }
     a.window = have_from;

@@ -16,6 +16,12 @@ def _u64(arr):
 # atsc_window_stats (include/atsc_hip.h): the summary record of one window, 48 bytes
 WINDOW_STATS = np.dtype([("count", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sum", "<f8"), ("first", "<f8"),
                          ("last", "<f8")])
+# atsc_window_moments (include/atsc_hip.h): the centred moments of one window, 48 bytes
+WINDOW_MOMENTS = np.dtype([("count", "<u8"), ("mean", "<f8"), ("m2", "<f8"), ("t_mean", "<f8"), ("t_m2", "<f8"),
+                           ("c_tx", "<f8")])
+# atsc_window_fit: what atsc_moments_fit reads off them, 56 bytes; slope is in value units per sample
+WINDOW_FIT = np.dtype([("mean", "<f8"), ("variance", "<f8"), ("stddev", "<f8"), ("sample_variance", "<f8"),
+                       ("sample_stddev", "<f8"), ("slope", "<f8"), ("intercept", "<f8")])
 
 
 def _windows(begins, counts):
@@ -41,6 +47,15 @@ def histogram_edges_uniform(lo, hi, n_bins):
     capi.check(capi.lib().atsc_histogram_edges_uniform(float(lo), float(hi), n_bins,
                                                        out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
+
+
+def moments_fit(moments):
+    """-> WINDOW_FIT array: mean, population and sample variance / stddev, and the least-squares slope (per sample) and
+    intercept (at the window's first sample) of every WINDOW_MOMENTS record (atsc_moments_fit; no GPU)"""
+    m = np.ascontiguousarray(np.atleast_1d(np.asarray(moments, dtype=WINDOW_MOMENTS)))
+    out = np.zeros(max(len(m), 1), dtype=WINDOW_FIT)
+    capi.check(capi.lib().atsc_moments_fit(C.c_void_p(m.ctypes.data), len(m), C.c_void_p(out.ctypes.data)))
+    return out[: len(m)]
 
 
 def bucket_windows(begin, count, bucket):
@@ -158,6 +173,17 @@ class Context:
         out = np.zeros(max(len(wb), 1), dtype=WINDOW_STATS)
         rc = capi.lib().atsc_aggregate_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
                                                len(wb), pb, pc, C.c_void_p(out.ctypes.data))
+        capi.check(rc, self._h)
+        return out[: len(wb)]
+
+    def moments_windows_host(self, records, begins, counts, has_count=False):
+        """-> WINDOW_MOMENTS array: count, mean and the centred moments of value and position of every window
+        [begins[i], begins[i] + counts[i]) of the decoded records (atsc_moments_windows)"""
+        b = np.frombuffer(bytes(records), dtype=np.uint8)
+        wb, pb, wc, pc = _windows(begins, counts)
+        out = np.zeros(max(len(wb), 1), dtype=WINDOW_MOMENTS)
+        rc = capi.lib().atsc_moments_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
+                                             len(wb), pb, pc, C.c_void_p(out.ctypes.data))
         capi.check(rc, self._h)
         return out[: len(wb)]
 
@@ -313,6 +339,15 @@ class DPlan:
         assert d_stats.is_contiguous() and d_stats.numel() * d_stats.element_size() >= 48 * len(b)
         rc = capi.lib().atsc_aggregate_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
                                                    C.c_void_p(d_stats.data_ptr()), C.c_void_p(stream))
+        capi.check(rc, self.ctx._h)
+
+    def moments_windows(self, d_body, begins, counts, d_out, stream=0):
+        """Enqueues the moments of the windows [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least
+        48 bytes per window (atsc_moments_windows_dev; WINDOW_MOMENTS records)"""
+        b, pb, c, pc = _windows(begins, counts)
+        assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= 48 * len(b)
+        rc = capi.lib().atsc_moments_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
+                                                 C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
         capi.check(rc, self.ctx._h)
 
     def quantile_windows(self, d_body, begins, counts, levels, d_out, method=capi.QUANTILE_LINEAR, stream=0):

@@ -319,9 +319,77 @@ int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len
 /* Upper bound in bytes on the decoded-sample scratch the aggregate calls hold; 0 (the default) gives pieces of 16 Mi
  * samples (128 MiB, plus 2 MiB of room for two large frames cut by a piece's ends where a frame longer than 4096 samples
  * is touched).  A budget below what one piece needs is raised to that minimum, never an error.  It bounds the quantile
- * calls below too, whose windows must each fit one piece, and the histogram calls (atsc_histogram_windows_dev), whose
- * windows may be of any length. */
+ * calls below too, whose windows must each fit one piece, and the moments (atsc_moments_windows_dev) and histogram
+ * calls (atsc_histogram_windows_dev), whose windows may be of any length. */
 int atsc_ctx_set_aggregate_scratch(atsc_ctx *ctx, uint64_t bytes);
+
+/* Windowed moments: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames) the
+ * centred moments of the sample value x and the sample position t, from the same decoded samples as the window decode:
+ * what mean, variance / standard deviation and the least-squares line through (t, x) are read from (atsc_moments_fit).
+ * They are reduced by pairwise merges of centred nodes, never from sums of squares, so a window of 1e9 +- 1e-3 keeps its
+ * variance.  The result is bit-exact: it depends only on the stream's samples and the window's (begin, count), not on
+ * the other windows, their order, the budget, piece boundaries or the device.
+ *   Node   (n, mx, M2x, mt, M2t, C).
+ *   Leaf   of stream index i: (1, x[i], 0, (double)i, 0, 0); a slot outside the window or holding NaN is the empty node
+ *          (n = 0).
+ *   Merge(a, b)   nb == 0: a, bit for bit; na == 0: b; else
+ *          n = na + nb; w = (double)nb / (double)n; f = (double)na * w; dx = mxb - mxa; dt = mtb - mta;
+ *          mx = mxa + dx * w; mt = mta + dt * w;
+ *          M2x = (M2xa + M2xb) + (dx * dx) * f; M2t = (M2ta + M2tb) + (dt * dt) * f; C = (Ca + Cb) + (dx * dt) * f
+ *          -- every operation one correctly rounded f64 + - * /, evaluated as written, never fused.
+ *   Tree   the aggregate sum's tree (above) with + replaced by Merge, the left operand as a:
+ *          1. tiles of 2048 slots at multiples of 2048 in the stream index;
+ *          2. in a tile, for v = 0..255: p_t = Merge(leaf[512 t + 2 v], leaf[512 t + 2 v + 1]) (t = 0..3) and
+ *             s[v] = Merge(Merge(p_0, p_1), Merge(p_2, p_3)); then s[v] = Merge(s[v], s[v + h]) for v < h,
+ *             h = 128, 64, 32, 16, 8, 4, 2, 1: s[0];
+ *          3. the window's tile partials q[0..P-1] in tile order: q[i] = Merge(q[2 i], q[2 i + 1]) level by level (an odd
+ *             last entry merges with the empty node) until one is left.
+ *   Result count = n, mean = mx, m2 = M2x, t_m2 = M2t, c_tx = C, t_mean = mt - (double)begin (one subtract); when
+ *          count == 0 all five doubles are NaN.  +-Inf samples give what IEEE gives under these rules; where the rule
+ *          yields NaN, any NaN bit pattern conforms.
+ * With u = 2^-53, L = max(1, ceil(log2 count)), kappa = sqrt(1 + count mean^2 / m2) and r = (begin + count) / count,
+ * for finite data:
+ *   |mean - exact| <= (L + 2) u mean|x|;              |m2 - exact| <= (L + 2) u kappa m2;
+ *   |t_m2 - exact| <= (L + 2) u r t_m2;               |c_tx - exact| <= (L + 2) u r kappa sqrt(t_m2 m2);
+ *   |t_mean - exact| <= (L + 2) u (begin + count);
+ * m2 == 0 and c_tx == 0 exactly on a constant window.  r is the price of positions counted in the stream's index (what
+ * lets windows share tiles): where a merge joins unequal counts -- a window's edges, NaN holes -- a node's mean position
+ * rounds relative to its absolute position, not to the window's extent.  r == 1 for a window at the stream's start,
+ * where t_mean came out exact in every NaN-free window tried; a bucket of 60 samples at sample 10^9 keeps about 8 digits
+ * of t_m2, c_tx and the slope.
+ * Validation and the other semantics are atsc_aggregate_windows_dev's: a window beyond the stream gives ATSC_E_INVALID
+ * with nothing written; payloads are checked only of the frames a window touches; windows may overlap and come in any
+ * order; count == 0 and n_windows == 0 are valid.  Windows may be of any length (partials merge across the pieces of the
+ * scratch that atsc_ctx_set_aggregate_scratch bounds): there is no ATSC_E_CAPACITY case. */
+typedef struct {
+    uint64_t count; /* samples of the window that are not NaN */
+    double mean;    /* of those samples */
+    double m2;      /* sum (x - mean)^2 */
+    double t_mean;  /* mean position of those samples, in samples from the window's begin */
+    double t_m2;    /* sum (t - t_mean)^2 */
+    double c_tx;    /* sum (t - t_mean)(x - mean) */
+} atsc_window_moments; /* 48 bytes */
+/* d_out[i] holds window i.  begin / count are HOST arrays; d_body and d_out are device memory (d_out 8-byte aligned).
+ * Enqueued on `stream`, not synchronised.  A malformed payload inside a window sets the plan's status word.  The plan
+ * keeps the call's tables, partials and scratch: the next moments call on the same plan waits (host side) until this
+ * one's work is done; atsc_dplan_destroy frees them. */
+int atsc_moments_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                             const uint64_t *begin, const uint64_t *count, atsc_window_moments *d_out, void *stream);
+/* Host bytes in, host records out, synchronous; walks and uploads only the touched records, as atsc_aggregate_windows
+ * does.  ATSC_E_FORMAT (nothing written) for a malformed payload inside a window. */
+int atsc_moments_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                         const uint64_t *begin, const uint64_t *count, atsc_window_moments *out);
+/* What is read off the moments, host only (no GPU); out[i] from m[i], i < n:
+ *   mean; variance = m2 / (double)count, stddev = sqrt(variance) (population forms);
+ *   sample_variance = m2 / (double)(count - 1), NaN when count < 2; sample_stddev = sqrt(sample_variance);
+ *   slope = c_tx / t_m2, NaN unless t_m2 > 0: the least-squares trend in value units PER SAMPLE (not per second: the
+ *     spacing of samples in time is the caller's, and may differ between the segments of a VSRI index);
+ *   intercept = mean - slope * t_mean (not fused): the fitted value at the window's first sample.
+ * count == 0 gives NaN in all seven.  ATSC_E_INVALID for a null pointer with n > 0. */
+typedef struct {
+    double mean, variance, stddev, sample_variance, sample_stddev, slope, intercept;
+} atsc_window_fit;
+int atsc_moments_fit(const atsc_window_moments *m, uint64_t n, atsc_window_fit *out);
 
 /* Windowed quantiles: exact order statistics of windows [begin, begin + count) of the decoded stream (the indices of
  * atsc_decompress_frames), from the same decoded samples as the window decode.  For window i:
@@ -423,6 +491,9 @@ int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uint64_t count
 /* atsc_aggregate_windows over the stream's frames */
 int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                   atsc_window_stats *out);
+/* atsc_moments_windows over the stream's frames */
+int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                atsc_window_moments *out);
 /* atsc_quantile_windows over the stream's frames */
 int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint32_t n_q, const double *q, int method, double *out);
