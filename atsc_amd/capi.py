@@ -99,6 +99,9 @@ SIGNATURES = {
     "atsc_moments_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, _vp, _vp]),
     "atsc_moments_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_moments_fit": (C.c_int, [_vp, C.c_uint64, _vp]),
+    "atsc_delta_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, _vp, _vp]),
+    "atsc_delta_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, _vp]),
+    "atsc_delta_derive": (C.c_int, [_vp, C.c_uint64, _vp]),
     "atsc_quantile_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _vp,
                                             _vp]),
     "atsc_quantile_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p,
@@ -120,6 +123,7 @@ SIGNATURES = {
     "atsc_stream_decompress_window": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(_f64p), _u64p]),
     "atsc_stream_aggregate_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_moments_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
+    "atsc_stream_delta_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_quantile_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _f64p]),
     "atsc_stream_histogram_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _u64p]),
     "atsc_free": (None, [_vp]),

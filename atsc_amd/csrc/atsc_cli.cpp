@@ -3,7 +3,7 @@
 //
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
-//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments]]]
+//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -42,6 +42,8 @@ struct Args {
     int closed = ATSC_HIST_LEFT_CLOSED;  // --histogram-closed
     bool have_closed = false;
     bool moments = false;  // --moments (with --buckets): the .agg.csv columns mean,stdvar,stddev,slope,intercept
+    // --deltas (with --buckets): the .agg.csv columns pairs,rises,falls,up,down,increase,variation,max_rise,max_fall
+    bool deltas = false;
 };
 
 void usage()
@@ -60,6 +62,10 @@ void usage()
             "      --histogram-closed <SIDE>  left: E[k-1] <= v < E[k] | right: E[k-1] < v <= E[k] [default: left]\n"
             "      --moments                  with --buckets: also every bucket's mean, stdvar, stddev (population forms) and\n"
             "                                 least-squares slope (value units per sample) and intercept (at its first sample)\n"
+            "      --deltas                   with --buckets: also every bucket's steps from one sample to the next: counted\n"
+            "                                 pairs, rises, falls (a counter's resets), the sums of the rises (up) and of the\n"
+            "                                 falls (down), the counter increase (every fall a restart from zero), the total\n"
+            "                                 variation (up + down) and the largest single rise and fall\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -208,6 +214,11 @@ int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const u
     if (a.moments) rc = atsc_moments_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), mv.data());
     if (!rc && a.moments) rc = atsc_moments_fit(mv.data(), nb, fv.data());
     if (rc) return rc;
+    std::vector<atsc_window_delta> dv(a.deltas && nb ? nb : 1);
+    std::vector<atsc_window_delta_fit> df(dv.size());
+    if (a.deltas) rc = atsc_delta_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), dv.data());
+    if (!rc && a.deltas) rc = atsc_delta_derive(dv.data(), nb, df.data());
+    if (rc) return rc;
     FILE *f = fopen(with_ext(path, "agg.csv").c_str(), "w");
     if (!f) return ATSC_E_IO;
     fprintf(f, "begin,count,min,max,sum,first,last");
@@ -215,6 +226,7 @@ int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const u
     for (uint64_t j = 0; j + 1 < nh; ++j) fprintf(f, ",h%llu", (unsigned long long)j);
     if (nh) fprintf(f, ",hnan");
     if (a.moments) fprintf(f, ",mean,stdvar,stddev,slope,intercept");
+    if (a.deltas) fprintf(f, ",pairs,rises,falls,up,down,increase,variation,max_rise,max_fall");
     fprintf(f, "\n");
     for (uint64_t k = 0; k < nb; ++k) {
         fprintf(f, "%llu,%llu,%s,%s,%s,%s,%s", (unsigned long long)b[k], (unsigned long long)st[k].count,
@@ -225,6 +237,11 @@ int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const u
         if (a.moments)
             fprintf(f, ",%s,%s,%s,%s,%s", debug_f64(fv[k].mean).c_str(), debug_f64(fv[k].variance).c_str(),
                     debug_f64(fv[k].stddev).c_str(), debug_f64(fv[k].slope).c_str(), debug_f64(fv[k].intercept).c_str());
+        if (a.deltas)
+            fprintf(f, ",%llu,%llu,%llu,%s,%s,%s,%s,%s,%s", (unsigned long long)dv[k].pairs, (unsigned long long)dv[k].rises,
+                    (unsigned long long)dv[k].falls, debug_f64(dv[k].up).c_str(), debug_f64(dv[k].down).c_str(),
+                    debug_f64(df[k].increase).c_str(), debug_f64(df[k].variation).c_str(),
+                    debug_f64(dv[k].max_rise).c_str(), debug_f64(dv[k].max_fall).c_str());
         fprintf(f, "\n");
     }
     return fclose(f) == 0 ? ATSC_OK : ATSC_E_IO;
@@ -409,6 +426,7 @@ int main(int argc, char **argv)
             a.have_closed = true;
         }
         else if (s == "--moments") a.moments = true;
+        else if (s == "--deltas") a.deltas = true;
         else if (!s.empty() && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); usage(); return 2; }
         else a.input = s;
     }
@@ -420,6 +438,7 @@ int main(int argc, char **argv)
     if (a.have_hist && !a.buckets) { fprintf(stderr, "error: '--histogram' needs '--buckets'\n"); return 2; }
     if (a.have_closed && !a.have_hist) { fprintf(stderr, "error: '--histogram-closed' needs '--histogram'\n"); return 2; }
     if (a.moments && !a.buckets) { fprintf(stderr, "error: '--moments' needs '--buckets'\n"); return 2; }
+    if (a.deltas && !a.buckets) { fprintf(stderr, "error: '--deltas' needs '--buckets'\n"); return 2; }
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) { fprintf(stderr, "[ERROR] %s: No such file or directory\n", a.input.c_str()); return 1; }
     atsc_ctx *ctx = nullptr;

@@ -219,6 +219,24 @@ struct DevMomTile {
     uint32_t lo, hi;
 };
 
+// windowed deltas (atsc_delta_windows_dev, atsc_delta.hip): the aggregates' tiles, pieces and combine passes
+// (DevAggComb) over the pairs of stream-adjacent samples
+// the partial of a tile or of a group of tiles: the three sums (-0.0 without a term), the largest rise and fall (+0.0
+// without one) and the counts of include/atsc_hip.h
+struct DevDltPart {
+    double up, down, after_falls, max_rise, max_fall;
+    uint64_t pairs, rises, falls;
+};
+// DLT_CONT: the window continues from the slot in front of the tile, so the pair at slot lo (== 0) is the window's;
+// DLT_CARRY: that slot lies in the previous piece of the scratch, and its sample in the call's carry slot
+enum : uint32_t { DLT_CONT = 1, DLT_CARRY = 2 };
+// one tile of k_dlt_tiles: the pairs at the slots of [lo, hi) of the tile whose slot 0 is scratch[src] -> part[dst]
+struct DevDltTile {
+    uint64_t src, dst;
+    uint32_t lo, hi;
+    uint32_t flags, pad;
+};
+
 // windowed quantiles (atsc_quantile_windows_dev, atsc_quantile.hip).  The tier of a window is chosen from its length:
 // short (one wavefront, keys in registers), medium (one workgroup, keys in LDS), long (MSD radix select, 8-bit digits)
 constexpr uint32_t QNT_MAX_LEVELS = 64;

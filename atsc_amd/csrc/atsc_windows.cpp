@@ -1,5 +1,5 @@
-// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, quantiles and histograms of ranges
-// of the decoded stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
+// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, quantiles and histograms
+// of ranges of the decoded stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
@@ -49,6 +49,11 @@ __attribute__((weak)) hipError_t launch_mom_tiles(const DevMomTile *tasks, uint3
                                                   DevMomPart *part, hipStream_t s);
 __attribute__((weak)) hipError_t launch_mom_combine(const DevAggComb *tasks, uint32_t n, DevMomPart *part,
                                                     const uint64_t *begin, void *out, hipStream_t s);
+// the windowed deltas' reduce kernels (atsc_delta.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_dlt_tiles(const DevDltTile *tasks, uint32_t n, const double *scratch,
+                                                  const double *carry, DevDltPart *part, hipStream_t s);
+__attribute__((weak)) hipError_t launch_dlt_combine(const DevAggComb *tasks, uint32_t n, DevDltPart *part, void *out,
+                                                    hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -257,6 +262,8 @@ static const DecodeCaller BY_HISTOGRAM = {"launch k_decompress (histogram)", "la
                                           "launch k_window_gather (histogram)"};
 static const DecodeCaller BY_MOMENTS = {"launch k_decompress (moments)", "launch k_decompress_large (moments)",
                                         "launch k_window_gather (moments)"};
+static const DecodeCaller BY_DELTA = {"launch k_decompress (delta)", "launch k_decompress_large (delta)",
+                                      "launch k_window_gather (delta)"};
 
 // Enqueues one piece's decode (d: the device copy of the upload).  out: the base the tasks' destinations count from;
 // the copies go from gat_src to gat_dst.
@@ -516,7 +523,7 @@ extern "C" int atsc_decompress_window(atsc_ctx *ctx, const uint8_t *body, uint64
 }
 
 // ------------------------------------------------------------------------------------------
-// decoded samples of window pieces in scratch (the aggregate, the moments, the quantile and the histogram calls)
+// decoded samples of window pieces in scratch (the aggregate, the moments, the delta, the quantile and the histogram calls)
 // ------------------------------------------------------------------------------------------
 // Decoded samples reach the reduce and selection kernels through one scratch region, piece after piece in stream order.
 static const uint64_t AGG_MIN_PIECE = 32ull * AGG_TILE;  // the least a piece holds, whatever the budget
@@ -638,11 +645,14 @@ static void agg_empty_record(atsc_window_stats &r)
     r.sum = 0.0;
 }
 
-// What the two reductions over tiles differ in: the aggregates (atsc_aggregate.hip) and the moments (atsc_moments.hip).
+// What the three reductions over tiles differ in: the aggregates (atsc_aggregate.hip), the moments (atsc_moments.hip)
+// and the deltas (atsc_delta.hip).
 //   Tile, tile(t, k)   the tile kernel's task, from the plan's DevAggTile of tile k of the stream
 //   PART               bytes of a partial
 //   SIDE               the table both kernels share beside the partials: the windows' first / last samples, which the
 //                      tile kernel writes (device only), or the windows' begins in the stream's index (uploaded)
+//   CARRY, carried(t)  the tile kernel looks at the sample in front of a tile: the side table is one carry slot (device
+//                      only), which holds the previous piece's last sample for a piece's first tile where carried(t)
 struct AggQuery {
     using Tile = DevAggTile;
     static constexpr const char *CALL = "aggregate_windows", *RES_NAME = "d_stats", *NO_KERNELS = "no aggregate kernels",
@@ -652,7 +662,9 @@ struct AggQuery {
     static const DecodeCaller &who() { return BY_AGGREGATE; }
     static bool have() { return launch_agg_tiles && launch_agg_combine; }
     static QueryRes &res(const atsc_dplan *dp) { return dp->agg; }
+    static constexpr bool CARRY = false;
     static Tile tile(const DevAggTile &t, uint64_t) { return t; }
+    static bool carried(const Tile &) { return false; }
     static hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *side, hipStream_t s)
     {
         return launch_agg_tiles(t, n, scr, (DevAggPart *)part, (double *)side, s);
@@ -671,7 +683,9 @@ struct MomQuery {
     static const DecodeCaller &who() { return BY_MOMENTS; }
     static bool have() { return launch_mom_tiles && launch_mom_combine; }
     static QueryRes &res(const atsc_dplan *dp) { return dp->mom; }
+    static constexpr bool CARRY = false;
     static Tile tile(const DevAggTile &t, uint64_t k) { return Tile{t.src, t.dst, k * AGG_TILE, t.lo, t.hi}; }
+    static bool carried(const Tile &) { return false; }
     static hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s)
     {
         return launch_mom_tiles(t, n, scr, (DevMomPart *)part, s);
@@ -682,7 +696,36 @@ struct MomQuery {
     }
 };
 
-// The device call of a reduction over tiles (Q: AggQuery or MomQuery; the kernels named below are the aggregates').
+struct DltQuery {
+    using Tile = DevDltTile;
+    static constexpr const char *CALL = "delta_windows", *RES_NAME = "d_out", *NO_KERNELS = "no delta kernels",
+                                *TILES = "launch k_dlt_tiles", *COMBINE = "launch k_dlt_combine";
+    static constexpr size_t PART = sizeof(DevDltPart);
+    static constexpr bool SIDE_BEGINS = false;
+    static constexpr bool CARRY = true;
+    static const DecodeCaller &who() { return BY_DELTA; }
+    static bool have() { return launch_dlt_tiles && launch_dlt_combine; }
+    static QueryRes &res(const atsc_dplan *dp) { return dp->dlt; }
+    // every tile but a window's first continues from the slot in front of it (the window covers that slot, so it was
+    // decoded): scratch[src - 1], or the carry slot where the tile is the first of its piece
+    static Tile tile(const DevAggTile &t, uint64_t)
+    {
+        const uint32_t cont = (t.flags & AGG_FIRST) ? 0u : (uint32_t)DLT_CONT;
+        return Tile{t.src, t.dst, t.lo, t.hi, cont | (cont && t.src == 0 ? (uint32_t)DLT_CARRY : 0u), 0};
+    }
+    static bool carried(const Tile &t) { return (t.flags & DLT_CARRY) != 0; }
+    static hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *side, hipStream_t s)
+    {
+        return launch_dlt_tiles(t, n, scr, (const double *)side, (DevDltPart *)part, s);
+    }
+    static hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *, void *out, hipStream_t s)
+    {
+        return launch_dlt_combine(c, n, (DevDltPart *)part, out, s);
+    }
+};
+
+// The device call of a reduction over tiles (Q: AggQuery, MomQuery or DltQuery; the kernels named below are the
+// aggregates').
 // Host work: covering intervals, pieces, the decode tasks of every piece (one per touched frame: its
 // covered samples' hull in the piece), the tile tasks (a full tile that windows cover past their first tile and before
 // their last one is reduced once, into a shared partial; every window's first and last tile are reduced for it alone)
@@ -690,6 +733,10 @@ struct MomQuery {
 // per piece, the window decode's launchers into scratch and k_agg_tiles, and k_agg_combine once per pass.
 // org: the stream index of the plan's first sample (a plan of the touched records only, in the host call): tiles lie at
 // multiples of AGG_TILE in the stream's index, not the plan's.  Indices below are the stream's unless named otherwise.
+// Q::CARRY: a piece's decode overwrites the scratch, and with it the sample in front of the next piece's first tile.
+// Where a window runs on into the next piece, an 8-byte copy behind the piece's tile launch (stream-ordered: behind
+// the launch that read the slot's previous value, in front of the next decode) takes the piece's last sample to the
+// carry slot in the call's tables.  The tile kernel never writes that slot.
 template <class Q>
 static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
                       const uint64_t *count, void *d_out, void *stream, uint64_t org)
@@ -794,6 +841,7 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
     std::vector<PieceDecode> pdec(pcs.size());
     std::vector<size_t> tile_at(pcs.size());
     std::vector<uint32_t> tile_n(pcs.size());
+    std::vector<char> carry_in(pcs.size(), 0);  // the piece's first tile reads the previous piece's last sample
     DecodeTasks D;
     std::vector<typename Q::Tile> tiles;
     tiles.reserve(tt.size());
@@ -806,7 +854,11 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
             DevAggTile t = tt[ti].t;
             t.src = (tt[ti].k - pcs[p].k0) * T;
             tiles.push_back(Q::tile(t, tt[ti].k));
+            if (Q::carried(tiles.back())) carry_in[p] = 1;
         }
+        // (a window that covers the slot in front of the piece covers the tile in front: the previous piece ends there)
+        if (carry_in[p] && (p == 0 || pcs[p - 1].k1 != pcs[p].k0))
+            return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "internal error (carry without a previous piece)");
         tile_n[p] = (uint32_t)(tiles.size() - tile_at[p]);
     }
     if (ti != tt.size()) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "internal error (tile outside the pieces)");
@@ -818,13 +870,13 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
     QueryRes &R = Q::res(dp);
     HIPCHK(ctx, R.wait());
     // one upload: the decode tasks, tile tasks, combine tasks (and the begins); behind them (device only) the partials
-    // (and the windows' first / last samples)
+    // (and the windows' first / last samples, or the carry slot)
     Upload up;
     D.place(up);
     const size_t off_tiles = up.add(tiles), off_comb = up.add(comb);
     const size_t off_begins = Q::SIDE_BEGINS ? up.add(wb) : 0;
     const size_t off_part = up.device_only(part_n * Q::PART);
-    const size_t off_side = Q::SIDE_BEGINS ? off_begins : up.device_only(2 * W * sizeof(double));
+    const size_t off_side = Q::SIDE_BEGINS ? off_begins : up.device_only(Q::CARRY ? sizeof(double) : 2 * W * sizeof(double));
     HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, region + (uint64_t)MAX_FRAME * D.spills_used));
     unsigned char *d = R.d;
     up.stage(R.h);
@@ -836,6 +888,8 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
         if (rc) return rc;
         const hipError_t e = Q::tiles((const typename Q::Tile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, side, s);
         if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, Q::TILES, e);
+        if (Q::CARRY && p + 1 < pcs.size() && carry_in[p + 1])
+            HIPCHK(ctx, hipMemcpyAsync(side, scr + (pcs[p].k1 - pcs[p].k0) * T - 1, sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     for (size_t q = 0; q + 1 < pass_at.size(); ++q) {
         const hipError_t e = Q::combine((const DevAggComb *)(d + off_comb) + pass_at[q], (uint32_t)(pass_at[q + 1] - pass_at[q]),
@@ -934,6 +988,60 @@ extern "C" int atsc_moments_fit(const atsc_window_moments *m, uint64_t n, atsc_w
         r.slope = a.t_m2 > 0.0 ? a.c_tx / a.t_m2 : nan;
         const double st = r.slope * a.t_mean;
         r.intercept = a.mean - st;
+    }
+    return ATSC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// windowed deltas: counted pairs, rises, falls, their sums and largest steps of sample windows (atsc_delta.hip)
+// ------------------------------------------------------------------------------------------
+static void dlt_empty_record(atsc_window_delta &r)
+{
+    r.pairs = r.rises = r.falls = 0;
+    r.up = r.down = r.after_falls = r.max_rise = r.max_fall = 0.0;
+}
+
+// The device call: reduce_dev with the deltas' kernels and the carry.
+extern "C" int atsc_delta_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                      const uint64_t *begin, const uint64_t *count, atsc_window_delta *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    return reduce_dev<DltQuery>(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    ATSC_API_END
+}
+
+// Host call: window_host_call into reduce_dev.
+extern "C" int atsc_delta_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                  const uint64_t *begin, const uint64_t *count, atsc_window_delta *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "delta_windows: null argument");
+    if (n_windows == 0) return ATSC_OK;
+    return window_host_call(
+        ctx, "delta_windows", body, body_len, has_count, n_windows, begin, count, out,
+        n_windows * sizeof(atsc_window_delta), false,
+        [&](bool any) {
+            for (uint64_t i = 0; !any && i < n_windows; ++i) dlt_empty_record(out[i]);
+            return ATSC_OK;
+        },
+        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
+            return reduce_dev<DltQuery>(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org);
+        });
+    ATSC_API_END
+}
+
+// Host only: what a caller reads off the deltas.  Each line is one rounded operation, as include/atsc_hip.h states it.
+extern "C" int atsc_delta_derive(const atsc_window_delta *d, uint64_t n, atsc_window_delta_fit *out)
+{
+    if (n && (!d || !out)) return ATSC_E_INVALID;
+    for (uint64_t i = 0; i < n; ++i) {
+        const atsc_window_delta &a = d[i];
+        atsc_window_delta_fit &r = out[i];
+        r.changes = a.rises + a.falls;
+        r.variation = a.up + a.down;
+        r.net = a.up - a.down;
+        r.increase = a.up + a.after_falls;
+        r.mean_step = a.pairs ? r.variation / (double)a.pairs : std::numeric_limits<double>::quiet_NaN();
     }
     return ATSC_OK;
 }
@@ -1422,6 +1530,24 @@ extern "C" int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, c
         return ATSC_OK;
     }
     return atsc_moments_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_delta_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                         atsc_window_delta *out)
+{
+    ATSC_API_BEGIN
+    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
+    std::vector<uint8_t> body;
+    atsc_ctx *ctx = nullptr;
+    const int rc = stream_body(s, body, &ctx);
+    if (rc) return rc;
+    if (body.empty()) {
+        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
+        for (uint64_t i = 0; i < n_windows; ++i) dlt_empty_record(out[i]);
+        return ATSC_OK;
+    }
+    return atsc_delta_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
     ATSC_API_END
 }
 

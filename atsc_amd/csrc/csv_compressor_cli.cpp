@@ -4,7 +4,7 @@
 // Compression and decompression run on the GPU; the index and the text formats are host code.
 //
 //   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
-//                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments]]]]
+//                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas]]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
@@ -41,6 +41,8 @@ struct Args {
     int closed = ATSC_HIST_LEFT_CLOSED;  // --histogram-closed
     bool have_closed = false;
     bool moments = false;  // --moments (with --step): the .agg.csv columns mean,stdvar,stddev,slope,intercept
+    // --deltas (with --step): the .agg.csv columns pairs,rises,falls,up,down,increase,variation,max_rise,max_fall
+    bool deltas = false;
 };
 
 constexpr int PANIC = 101;  // exit status of a Rust panic: every failure below is an expect()/panic!()
@@ -62,6 +64,10 @@ void usage()
             "      --moments                  with --step: also every bucket's mean, stdvar, stddev (population forms) and\n"
             "                                 least-squares slope (value units per SAMPLE, not per second) and intercept\n"
             "                                 (at its first sample)\n"
+            "      --deltas                   with --step: also every bucket's steps from one sample to the next: counted\n"
+            "                                 pairs, rises, falls (a counter's resets), the sums of the rises (up) and of the\n"
+            "                                 falls (down), the counter increase (every fall a restart from zero), the total\n"
+            "                                 variation (up + down) and the largest single rise and fall\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -243,6 +249,11 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
     if (a.moments) rc = atsc_moments_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), mv.data());
     if (!rc && a.moments) rc = atsc_moments_fit(mv.data(), nb, fv.data());
     if (rc) { int e = die("moments", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    std::vector<atsc_window_delta> dv(a.deltas && nb ? nb : 1);
+    std::vector<atsc_window_delta_fit> df(dv.size());
+    if (a.deltas) rc = atsc_delta_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), dv.data());
+    if (!rc && a.deltas) rc = atsc_delta_derive(dv.data(), nb, df.data());
+    if (rc) { int e = die("deltas", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
     atsc_ctx_destroy(ctx);
     atsc_free(bro);
     FILE *f = fopen(with_ext(output_base, "agg.csv").c_str(), "w");
@@ -252,6 +263,7 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
     for (uint64_t j = 0; j + 1 < nh; ++j) fprintf(f, ",h%llu", (unsigned long long)j);
     if (nh) fprintf(f, ",hnan");
     if (a.moments) fprintf(f, ",mean,stdvar,stddev,slope,intercept");
+    if (a.deltas) fprintf(f, ",pairs,rises,falls,up,down,increase,variation,max_rise,max_fall");
     fprintf(f, "\n");
     for (uint64_t k = 0; k < nb; ++k) {
         fprintf(f, "%lld,%llu,%s,%s,%s,%s,%s", (long long)a.t0 + (long long)k * a.step, (unsigned long long)st[k].count,
@@ -262,6 +274,11 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
         if (a.moments)
             fprintf(f, ",%s,%s,%s,%s,%s", debug_f64(fv[k].mean).c_str(), debug_f64(fv[k].variance).c_str(),
                     debug_f64(fv[k].stddev).c_str(), debug_f64(fv[k].slope).c_str(), debug_f64(fv[k].intercept).c_str());
+        if (a.deltas)
+            fprintf(f, ",%llu,%llu,%llu,%s,%s,%s,%s,%s,%s", (unsigned long long)dv[k].pairs, (unsigned long long)dv[k].rises,
+                    (unsigned long long)dv[k].falls, debug_f64(dv[k].up).c_str(), debug_f64(dv[k].down).c_str(),
+                    debug_f64(df[k].increase).c_str(), debug_f64(df[k].variation).c_str(),
+                    debug_f64(dv[k].max_rise).c_str(), debug_f64(dv[k].max_fall).c_str());
         fprintf(f, "\n");
     }
     if (fclose(f) != 0) return die("failed to write aggregates to file");
@@ -429,6 +446,7 @@ int main(int argc, char **argv)
             a.have_closed = true;
         }
         else if (s == "--moments") a.moments = true;
+        else if (s == "--deltas") a.deltas = true;
         else if (value("--compressor")) { if (!parse_compressor(v, a.compressor)) { fprintf(stderr, "error: invalid value '%s' for '--compressor'\n", v.c_str()); return 2; } }
         else if (value("--error") || value("-e")) { if (!parse_int(v, 0, 50, a.error)) { fprintf(stderr, "error: invalid value '%s' for '--error': not in 0..=50\n", v.c_str()); return 2; } }
         else if (value("--compression-selection-sample-level") || value("-c")) { if (!parse_int(v, 0, 6, a.level)) { fprintf(stderr, "error: invalid value '%s' for '-c': not in 0..=6\n", v.c_str()); return 2; } }
@@ -462,6 +480,10 @@ int main(int argc, char **argv)
     }
     if (a.moments && !a.step) {
         fprintf(stderr, "error: '--moments' needs '--step'\n");
+        return 2;
+    }
+    if (a.deltas && !a.step) {
+        fprintf(stderr, "error: '--deltas' needs '--step'\n");
         return 2;
     }
     a.window = have_from;

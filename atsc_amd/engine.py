@@ -22,6 +22,12 @@ WINDOW_MOMENTS = np.dtype([("count", "<u8"), ("mean", "<f8"), ("m2", "<f8"), ("t
 # atsc_window_fit: what atsc_moments_fit reads off them, 56 bytes; slope is in value units per sample
 WINDOW_FIT = np.dtype([("mean", "<f8"), ("variance", "<f8"), ("stddev", "<f8"), ("sample_variance", "<f8"),
                        ("sample_stddev", "<f8"), ("slope", "<f8"), ("intercept", "<f8")])
+# atsc_window_delta (include/atsc_hip.h): what the samples of one window do from one to the next, 64 bytes
+WINDOW_DELTA = np.dtype([("pairs", "<u8"), ("rises", "<u8"), ("falls", "<u8"), ("up", "<f8"), ("down", "<f8"),
+                         ("after_falls", "<f8"), ("max_rise", "<f8"), ("max_fall", "<f8")])
+# atsc_window_delta_fit: what atsc_delta_derive reads off them, 40 bytes
+WINDOW_DELTA_FIT = np.dtype([("changes", "<u8"), ("variation", "<f8"), ("net", "<f8"), ("increase", "<f8"),
+                             ("mean_step", "<f8")])
 
 
 def _windows(begins, counts):
@@ -56,6 +62,15 @@ def moments_fit(moments):
     out = np.zeros(max(len(m), 1), dtype=WINDOW_FIT)
     capi.check(capi.lib().atsc_moments_fit(C.c_void_p(m.ctypes.data), len(m), C.c_void_p(out.ctypes.data)))
     return out[: len(m)]
+
+
+def delta_derive(deltas):
+    """-> WINDOW_DELTA_FIT array: changes, total variation, net change, counter increase and mean step of every
+    WINDOW_DELTA record (atsc_delta_derive; no GPU)"""
+    d = np.ascontiguousarray(np.atleast_1d(np.asarray(deltas, dtype=WINDOW_DELTA)))
+    out = np.zeros(max(len(d), 1), dtype=WINDOW_DELTA_FIT)
+    capi.check(capi.lib().atsc_delta_derive(C.c_void_p(d.ctypes.data), len(d), C.c_void_p(out.ctypes.data)))
+    return out[: len(d)]
 
 
 def bucket_windows(begin, count, bucket):
@@ -184,6 +199,17 @@ class Context:
         out = np.zeros(max(len(wb), 1), dtype=WINDOW_MOMENTS)
         rc = capi.lib().atsc_moments_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
                                              len(wb), pb, pc, C.c_void_p(out.ctypes.data))
+        capi.check(rc, self._h)
+        return out[: len(wb)]
+
+    def delta_windows_host(self, records, begins, counts, has_count=False):
+        """-> WINDOW_DELTA array: the counted pairs of adjacent samples, the rises and falls among them, their sums and
+        largest steps of every window [begins[i], begins[i] + counts[i]) of the decoded records (atsc_delta_windows)"""
+        b = np.frombuffer(bytes(records), dtype=np.uint8)
+        wb, pb, wc, pc = _windows(begins, counts)
+        out = np.zeros(max(len(wb), 1), dtype=WINDOW_DELTA)
+        rc = capi.lib().atsc_delta_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
+                                           len(wb), pb, pc, C.c_void_p(out.ctypes.data))
         capi.check(rc, self._h)
         return out[: len(wb)]
 
@@ -348,6 +374,15 @@ class DPlan:
         assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= 48 * len(b)
         rc = capi.lib().atsc_moments_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
                                                  C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
+        capi.check(rc, self.ctx._h)
+
+    def delta_windows(self, d_body, begins, counts, d_out, stream=0):
+        """Enqueues the deltas of the windows [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least
+        64 bytes per window (atsc_delta_windows_dev; WINDOW_DELTA records)"""
+        b, pb, c, pc = _windows(begins, counts)
+        assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= 64 * len(b)
+        rc = capi.lib().atsc_delta_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
+                                               C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
         capi.check(rc, self.ctx._h)
 
     def quantile_windows(self, d_body, begins, counts, levels, d_out, method=capi.QUANTILE_LINEAR, stream=0):

@@ -319,8 +319,8 @@ int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len
 /* Upper bound in bytes on the decoded-sample scratch the aggregate calls hold; 0 (the default) gives pieces of 16 Mi
  * samples (128 MiB, plus 2 MiB of room for two large frames cut by a piece's ends where a frame longer than 4096 samples
  * is touched).  A budget below what one piece needs is raised to that minimum, never an error.  It bounds the quantile
- * calls below too, whose windows must each fit one piece, and the moments (atsc_moments_windows_dev) and histogram
- * calls (atsc_histogram_windows_dev), whose windows may be of any length. */
+ * calls below too, whose windows must each fit one piece, and the moments (atsc_moments_windows_dev), delta
+ * (atsc_delta_windows_dev) and histogram calls (atsc_histogram_windows_dev), whose windows may be of any length. */
 int atsc_ctx_set_aggregate_scratch(atsc_ctx *ctx, uint64_t bytes);
 
 /* Windowed moments: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames) the
@@ -390,6 +390,62 @@ typedef struct {
     double mean, variance, stddev, sample_variance, sample_stddev, slope, intercept;
 } atsc_window_fit;
 int atsc_moments_fit(const atsc_window_moments *m, uint64_t n, atsc_window_fit *out);
+
+/* Windowed deltas: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames) what
+ * its samples do from one to the next, from the same decoded samples as the window decode: how much a counter grew and
+ * how often it reset, how much a gauge moved up and down (total variation), the largest single jump and drop.
+ *   Pairs  For every stream index j with begin < j < begin + count the pair of j is (a, b) = (x[j - 1], x[j]).  A pair
+ *          is counted iff neither a nor b is NaN.  Pairs are stream-adjacent: a NaN sample removes the two pairs it
+ *          belongs to, and nothing reaches across it.  A counted pair is a rise iff b > a and a fall iff b < a, compared
+ *          as values: -0.0, +0.0 is neither, and +Inf, +Inf is neither.
+ *   Terms  b - a of a rise (up, max_rise), a - b of a fall (down, max_fall), b of a fall (after_falls): each one correctly
+ *          rounded f64 subtract, or b itself.
+ *   Order  The three sums take the aggregate sum's tree unchanged (atsc_aggregate_windows, steps 1-3 above).  The term
+ *          of pair j sits at slot j, the index of b; every other slot holds -0.0: slots outside the window, the window's
+ *          own first slot, a pair that is not counted, a pair of the wrong direction.  A sum without a term is +0.0, as
+ *          the aggregate's sum is for count == 0.  The counts and the two maxima are exact in any order.
+ * count <= 1 gives the all-zero record.  +-Inf samples give what IEEE gives under these rules; where that is NaN, any NaN
+ * conforms.  The record is bit-exact: it depends only on the stream's samples and the window's (begin, count), not on
+ * the other windows, their order, the budget, piece boundaries or the device.  With u = 2^-53 and
+ * L = max(1, ceil(log2 pairs)), for finite data |up - exact| <= (L + 3) u up_exact, and likewise for down (one rounding
+ * for the subtract, L + 2 for the tree); on integer samples below 2^53 in sum all three sums are exact.
+ * Validation and the other semantics are atsc_aggregate_windows_dev's: a window beyond the stream gives ATSC_E_INVALID
+ * with nothing written; payloads are checked only of the frames a window touches; windows may overlap and come in any
+ * order; count == 0 and n_windows == 0 are valid.  Windows may be of any length (partials add across the pieces of the
+ * scratch that atsc_ctx_set_aggregate_scratch bounds, and the last sample of a piece is carried over to the next in the
+ * call's tables, not in that scratch): there is no ATSC_E_CAPACITY case. */
+typedef struct {
+    uint64_t pairs;     /* counted pairs */
+    uint64_t rises;     /* counted pairs with b > a */
+    uint64_t falls;     /* counted pairs with b < a (a counter's resets) */
+    double up;          /* sum of (b - a) over the rises */
+    double down;        /* sum of (a - b) over the falls: >= 0 */
+    double after_falls; /* sum of b over the falls: what a counter restarted at */
+    double max_rise;    /* largest b - a of a rise; +0.0 when rises == 0 */
+    double max_fall;    /* largest a - b of a fall; +0.0 when falls == 0 */
+} atsc_window_delta; /* 64 bytes */
+/* d_out[i] holds window i.  begin / count are HOST arrays; d_body and d_out are device memory (d_out 8-byte aligned).
+ * Enqueued on `stream`, not synchronised.  A malformed payload inside a window sets the plan's status word.  The plan
+ * keeps the call's tables, partials and scratch: the next delta call on the same plan waits (host side) until this
+ * one's work is done; atsc_dplan_destroy frees them. */
+int atsc_delta_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                           const uint64_t *begin, const uint64_t *count, atsc_window_delta *d_out, void *stream);
+/* Host bytes in, host records out, synchronous; walks and uploads only the touched records, as atsc_aggregate_windows
+ * does.  ATSC_E_FORMAT (nothing written) for a malformed payload inside a window. */
+int atsc_delta_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                       const uint64_t *begin, const uint64_t *count, atsc_window_delta *out);
+/* What is read off the deltas, host only (no GPU); out[i] from d[i], i < n; each value one f64 operation, not fused:
+ *   changes = rises + falls (64-bit unsigned);
+ *   variation = up + down: the total variation of the window's counted pairs;
+ *   net = up - down: last - first of a NaN-free window, up to rounding;
+ *   increase = up + after_falls: the counter increase in Prometheus terms, where every fall is a restart from zero;
+ *   mean_step = variation / (double)pairs, NaN when pairs == 0.
+ * ATSC_E_INVALID for a null pointer with n > 0. */
+typedef struct {
+    uint64_t changes;
+    double variation, net, increase, mean_step;
+} atsc_window_delta_fit; /* 40 bytes */
+int atsc_delta_derive(const atsc_window_delta *d, uint64_t n, atsc_window_delta_fit *out);
 
 /* Windowed quantiles: exact order statistics of windows [begin, begin + count) of the decoded stream (the indices of
  * atsc_decompress_frames), from the same decoded samples as the window decode.  For window i:
@@ -491,6 +547,9 @@ int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uint64_t count
 /* atsc_aggregate_windows over the stream's frames */
 int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                   atsc_window_stats *out);
+/* atsc_delta_windows over the stream's frames */
+int atsc_stream_delta_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                              atsc_window_delta *out);
 /* atsc_moments_windows over the stream's frames */
 int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 atsc_window_moments *out);
