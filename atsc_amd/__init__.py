@@ -6,12 +6,13 @@ from . import capi  # noqa: F401
 from .capi import AUTO, CONSTANT, FFT, IDW, NOOP, POLYNOMIAL, RLE, AtscError  # noqa: F401
 from .capi import QUANTILE_HIGHER, QUANTILE_LINEAR, QUANTILE_LOWER, QUANTILE_NEAREST  # noqa: F401
 from .capi import HIST_LEFT_CLOSED, HIST_MAX_EDGES, HIST_RIGHT_CLOSED  # noqa: F401
-from .engine import (WINDOW_DELTA, WINDOW_DELTA_FIT, WINDOW_FIT, WINDOW_MOMENTS, WINDOW_STATS, Context, DPlan, Plan,  # noqa: F401
+from .capi import RUNS_EQ, RUNS_GE, RUNS_GT, RUNS_LE, RUNS_LT, RUNS_NE, RUNS_NONE  # noqa: F401
+from .engine import (WINDOW_DELTA, WINDOW_DELTA_FIT, WINDOW_FIT, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, Context, DPlan, Plan,  # noqa: F401
                      bro_find_window, bro_open, bro_prefix, bucket_windows, chunk_sizes, clean_data, delta_derive,
-                     histogram_edges_uniform, moments_fit)
+                     histogram_edges_uniform, moments_fit, runs_merge)
 from .stream import (CompressedStream, aggregate_data_windows, bro_read_file, compress_data, csv_read,  # noqa: F401
                      decompress_data, decompress_data_window, delta_data_windows, histogram_data_windows,
                      moments_data_windows,
-                     quantile_data_windows,
+                     quantile_data_windows, runs_data_windows,
                      wbro_from_bytes, wbro_read, wbro_to_bytes, wbro_write)
 from .vsri import Metric, Vsri, day_elapsed_seconds, read_samples_from_csv_file, write_samples_to_csv_file  # noqa: F401

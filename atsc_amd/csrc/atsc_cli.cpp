@@ -3,7 +3,7 @@
 //
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
-//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas]]]
+//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -44,6 +44,10 @@ struct Args {
     bool moments = false;  // --moments (with --buckets): the .agg.csv columns mean,stdvar,stddev,slope,intercept
     // --deltas (with --buckets): the .agg.csv columns pairs,rises,falls,up,down,increase,variation,max_rise,max_fall
     bool deltas = false;
+    // --runs OP:LIMIT (with --buckets): the .agg.csv columns inside,runs,longest,longest_at,first_at,last_at,head,tail,excess
+    bool have_runs = false;
+    int runs_op = ATSC_RUNS_GT;
+    double runs_limit = 0.0;
 };
 
 void usage()
@@ -66,6 +70,10 @@ void usage()
             "                                 pairs, rises, falls (a counter's resets), the sums of the rises (up) and of the\n"
             "                                 falls (down), the counter increase (every fall a restart from zero), the total\n"
             "                                 variation (up + down) and the largest single rise and fall\n"
+            "      --runs <OP:LIMIT>          with --buckets: also every bucket's samples with value OP LIMIT (OP: gt ge lt le eq\n"
+            "                                 ne, e.g. gt:0.9) and their runs of adjacent samples, as the last columns: inside,\n"
+            "                                 runs, longest, longest_at, first_at, last_at (sample offsets in the bucket, empty\n"
+            "                                 where there is none), head, tail, excess (the sum of |value - LIMIT| over them)\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -185,6 +193,23 @@ int parse_histogram(const std::string &v, std::vector<double> &edges)
     }
 }
 
+// --runs OP:LIMIT: OP one of gt ge lt le eq ne, LIMIT a number that is not NaN, nothing behind it
+bool parse_runs(const std::string &v, int &op, double &limit)
+{
+    static const char *const OPS[] = {"gt", "ge", "lt", "le", "eq", "ne"};
+    const size_t c = v.find(':');
+    if (c == std::string::npos) return false;
+    const std::string o = v.substr(0, c), t = v.substr(c + 1);
+    int k = 0;
+    while (k < 6 && o != OPS[k]) ++k;
+    char *e = nullptr;
+    const double x = strtod(t.c_str(), &e);
+    if (k == 6 || t.empty() || isspace((unsigned char)t[0]) || *e || x != x) return false;
+    op = k;  // ATSC_RUNS_GT .. ATSC_RUNS_NE in this order
+    limit = x;
+    return true;
+}
+
 // -u --buckets N: one atsc_window_stats row per bucket of N samples of [begin, begin + count), the last bucket shorter
 int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const uint8_t *bro, uint64_t len, uint64_t begin,
                   uint64_t count)
@@ -219,6 +244,10 @@ int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const u
     if (a.deltas) rc = atsc_delta_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), dv.data());
     if (!rc && a.deltas) rc = atsc_delta_derive(dv.data(), nb, df.data());
     if (rc) return rc;
+    std::vector<atsc_window_runs> rv(a.have_runs && nb ? nb : 1);
+    if (a.have_runs) rc = atsc_runs_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), a.runs_op, a.runs_limit, rv.data());
+    if (rc) return rc;
+    auto pos = [](uint64_t p) { return p == ATSC_RUNS_NONE ? std::string() : std::to_string(p); };
     FILE *f = fopen(with_ext(path, "agg.csv").c_str(), "w");
     if (!f) return ATSC_E_IO;
     fprintf(f, "begin,count,min,max,sum,first,last");
@@ -227,6 +256,7 @@ int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const u
     if (nh) fprintf(f, ",hnan");
     if (a.moments) fprintf(f, ",mean,stdvar,stddev,slope,intercept");
     if (a.deltas) fprintf(f, ",pairs,rises,falls,up,down,increase,variation,max_rise,max_fall");
+    if (a.have_runs) fprintf(f, ",inside,runs,longest,longest_at,first_at,last_at,head,tail,excess");
     fprintf(f, "\n");
     for (uint64_t k = 0; k < nb; ++k) {
         fprintf(f, "%llu,%llu,%s,%s,%s,%s,%s", (unsigned long long)b[k], (unsigned long long)st[k].count,
@@ -242,6 +272,11 @@ int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const u
                     (unsigned long long)dv[k].falls, debug_f64(dv[k].up).c_str(), debug_f64(dv[k].down).c_str(),
                     debug_f64(df[k].increase).c_str(), debug_f64(df[k].variation).c_str(),
                     debug_f64(dv[k].max_rise).c_str(), debug_f64(dv[k].max_fall).c_str());
+        if (a.have_runs)
+            fprintf(f, ",%llu,%llu,%llu,%s,%s,%s,%llu,%llu,%s", (unsigned long long)rv[k].inside, (unsigned long long)rv[k].runs,
+                    (unsigned long long)rv[k].longest, pos(rv[k].longest_at).c_str(), pos(rv[k].first_at).c_str(),
+                    pos(rv[k].last_at).c_str(), (unsigned long long)rv[k].head, (unsigned long long)rv[k].tail,
+                    debug_f64(rv[k].excess).c_str());
         fprintf(f, "\n");
     }
     return fclose(f) == 0 ? ATSC_OK : ATSC_E_IO;
@@ -427,6 +462,13 @@ int main(int argc, char **argv)
         }
         else if (s == "--moments") a.moments = true;
         else if (s == "--deltas") a.deltas = true;
+        else if (value("--runs")) {
+            if (!parse_runs(v, a.runs_op, a.runs_limit)) {
+                fprintf(stderr, "error: invalid value '%s': '--runs' wants OP:LIMIT (OP: gt ge lt le eq ne)\n", v.c_str());
+                return 2;
+            }
+            a.have_runs = true;
+        }
         else if (!s.empty() && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); usage(); return 2; }
         else a.input = s;
     }
@@ -439,6 +481,7 @@ int main(int argc, char **argv)
     if (a.have_closed && !a.have_hist) { fprintf(stderr, "error: '--histogram-closed' needs '--histogram'\n"); return 2; }
     if (a.moments && !a.buckets) { fprintf(stderr, "error: '--moments' needs '--buckets'\n"); return 2; }
     if (a.deltas && !a.buckets) { fprintf(stderr, "error: '--deltas' needs '--buckets'\n"); return 2; }
+    if (a.have_runs && !a.buckets) { fprintf(stderr, "error: '--runs' needs '--buckets'\n"); return 2; }
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) { fprintf(stderr, "[ERROR] %s: No such file or directory\n", a.input.c_str()); return 1; }
     atsc_ctx *ctx = nullptr;

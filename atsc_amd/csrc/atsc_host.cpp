@@ -1729,6 +1729,7 @@ extern "C" void atsc_dplan_destroy(atsc_dplan *p)
     p->hst.release(p->ctx);
     p->mom.release(p->ctx);
     p->dlt.release(p->ctx);
+    p->run.release(p->ctx);
     pool_free(p->ctx, p->d_frames);
     pool_free(p->ctx, p->d_ids);
     pool_free(p->ctx, p->d_status);

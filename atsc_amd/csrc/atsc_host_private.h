@@ -172,8 +172,8 @@ struct atsc_dplan {
     std::vector<atsc::DevDFrame> h_frames;
     std::vector<int> h_cls;
     // what the last atsc_decompress_windows_dev, atsc_aggregate_windows_dev, atsc_quantile_windows_dev,
-    // atsc_histogram_windows_dev, atsc_moments_windows_dev and atsc_delta_windows_dev call own
-    mutable atsc::QueryRes win, agg, qnt, hst, mom, dlt;
+    // atsc_histogram_windows_dev, atsc_moments_windows_dev, atsc_delta_windows_dev and atsc_runs_windows_dev call own
+    mutable atsc::QueryRes win, agg, qnt, hst, mom, dlt, run;
 };
 
 namespace atsc {

@@ -237,6 +237,20 @@ struct DevDltTile {
     uint32_t flags, pad;
 };
 
+// windowed runs (atsc_runs_windows_dev, atsc_runs.hip): the aggregates' tiles, pieces and combine passes (DevAggComb)
+// over the nodes of include/atsc_hip.h's merge rule
+// the partial of a tile or of a group of tiles: the nine integers of its stretch of the window, the three positions as
+// stream indices (~0 where the record has ATSC_RUNS_NONE), and the sum of the inside samples' terms (-0.0 without one)
+struct DevRunPart {
+    uint64_t samples, inside, runs, longest, longest_at, first_at, last_at, head, tail;
+    double excess;
+};
+// one tile of k_run_tiles: slots [lo, hi) of the tile whose slot 0 is scratch[src] and sample t0 of the stream -> part[dst]
+struct DevRunTile {
+    uint64_t src, dst, t0;
+    uint32_t lo, hi;
+};
+
 // windowed quantiles (atsc_quantile_windows_dev, atsc_quantile.hip).  The tier of a window is chosen from its length:
 // short (one wavefront, keys in registers), medium (one workgroup, keys in LDS), long (MSD radix select, 8-bit digits)
 constexpr uint32_t QNT_MAX_LEVELS = 64;

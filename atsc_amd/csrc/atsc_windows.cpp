@@ -1,4 +1,4 @@
-// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, quantiles and histograms
+// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, quantiles and histograms
 // of ranges of the decoded stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
@@ -54,6 +54,11 @@ __attribute__((weak)) hipError_t launch_dlt_tiles(const DevDltTile *tasks, uint3
                                                   const double *carry, DevDltPart *part, hipStream_t s);
 __attribute__((weak)) hipError_t launch_dlt_combine(const DevAggComb *tasks, uint32_t n, DevDltPart *part, void *out,
                                                     hipStream_t s);
+// the windowed runs' reduce kernels (atsc_runs.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_run_tiles(const DevRunTile *tasks, uint32_t n, const double *scratch, int op,
+                                                  double limit, DevRunPart *part, hipStream_t s);
+__attribute__((weak)) hipError_t launch_run_combine(const DevAggComb *tasks, uint32_t n, DevRunPart *part,
+                                                    const uint64_t *begin, void *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -264,6 +269,8 @@ static const DecodeCaller BY_MOMENTS = {"launch k_decompress (moments)", "launch
                                         "launch k_window_gather (moments)"};
 static const DecodeCaller BY_DELTA = {"launch k_decompress (delta)", "launch k_decompress_large (delta)",
                                       "launch k_window_gather (delta)"};
+static const DecodeCaller BY_RUNS = {"launch k_decompress (runs)", "launch k_decompress_large (runs)",
+                                     "launch k_window_gather (runs)"};
 
 // Enqueues one piece's decode (d: the device copy of the upload).  out: the base the tasks' destinations count from;
 // the copies go from gat_src to gat_dst.
@@ -724,8 +731,35 @@ struct DltQuery {
     }
 };
 
-// The device call of a reduction over tiles (Q: AggQuery, MomQuery or DltQuery; the kernels named below are the
-// aggregates').
+// The runs (atsc_runs.hip).  The one query with parameters of a call, the condition: they are the query object's members,
+// which reduce_dev hands to tiles() by calling it on that object.  No carry: the merge joins a run across two tiles,
+// whichever pieces they lie in.
+struct RunQuery {
+    using Tile = DevRunTile;
+    static constexpr const char *CALL = "runs_windows", *RES_NAME = "d_out", *NO_KERNELS = "no runs kernels",
+                                *TILES = "launch k_run_tiles", *COMBINE = "launch k_run_combine";
+    static constexpr size_t PART = sizeof(DevRunPart);
+    static constexpr bool SIDE_BEGINS = true;
+    static constexpr bool CARRY = false;
+    int op = 0;
+    double limit = 0.0;
+    static const DecodeCaller &who() { return BY_RUNS; }
+    static bool have() { return launch_run_tiles && launch_run_combine; }
+    static QueryRes &res(const atsc_dplan *dp) { return dp->run; }
+    static Tile tile(const DevAggTile &t, uint64_t k) { return Tile{t.src, t.dst, k * AGG_TILE, t.lo, t.hi}; }
+    static bool carried(const Tile &) { return false; }
+    hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s) const
+    {
+        return launch_run_tiles(t, n, scr, op, limit, (DevRunPart *)part, s);
+    }
+    static hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *side, void *out, hipStream_t s)
+    {
+        return launch_run_combine(c, n, (DevRunPart *)part, (const uint64_t *)side, out, s);
+    }
+};
+
+// The device call of a reduction over tiles (Q: AggQuery, MomQuery, DltQuery or RunQuery; the kernels named below are
+// the aggregates').  q: the query's parameters of this call, where it has any (RunQuery).
 // Host work: covering intervals, pieces, the decode tasks of every piece (one per touched frame: its
 // covered samples' hull in the piece), the tile tasks (a full tile that windows cover past their first tile and before
 // their last one is reduced once, into a shared partial; every window's first and last tile are reduced for it alone)
@@ -739,7 +773,7 @@ struct DltQuery {
 // carry slot in the call's tables.  The tile kernel never writes that slot.
 template <class Q>
 static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
-                      const uint64_t *count, void *d_out, void *stream, uint64_t org)
+                      const uint64_t *count, void *d_out, void *stream, uint64_t org, const Q &q = Q())
 {
     if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_out)))
         return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
@@ -886,7 +920,7 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
     for (size_t p = 0; p < pcs.size(); ++p) {
         rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, Q::who());
         if (rc) return rc;
-        const hipError_t e = Q::tiles((const typename Q::Tile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, side, s);
+        const hipError_t e = q.tiles((const typename Q::Tile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, side, s);
         if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, Q::TILES, e);
         if (Q::CARRY && p + 1 < pcs.size() && carry_in[p + 1])
             HIPCHK(ctx, hipMemcpyAsync(side, scr + (pcs[p].k1 - pcs[p].k0) * T - 1, sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -1043,6 +1077,91 @@ extern "C" int atsc_delta_derive(const atsc_window_delta *d, uint64_t n, atsc_wi
         r.increase = a.up + a.after_falls;
         r.mean_step = a.pairs ? r.variation / (double)a.pairs : std::numeric_limits<double>::quiet_NaN();
     }
+    return ATSC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// windowed runs: the samples that meet a condition and the runs of adjacent ones among them (atsc_runs.hip)
+// ------------------------------------------------------------------------------------------
+static void run_empty_record(atsc_window_runs &r)
+{
+    r.samples = r.inside = r.runs = r.longest = r.head = r.tail = 0;
+    r.longest_at = r.first_at = r.last_at = ATSC_RUNS_NONE;
+    r.excess = 0.0;
+}
+
+// ctx may be null: then no message is kept
+static int runs_check_condition(atsc_ctx *ctx, int op, double limit)
+{
+    if (op < ATSC_RUNS_GT || op > ATSC_RUNS_NE) return fail(ctx, ATSC_E_INVALID, "runs_windows: unknown op");
+    if (std::isnan(limit)) return fail(ctx, ATSC_E_INVALID, "runs_windows: limit is NaN");
+    return ATSC_OK;
+}
+
+// The device call: reduce_dev with the runs' kernels and the call's condition.
+extern "C" int atsc_runs_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                     const uint64_t *begin, const uint64_t *count, int op, double limit,
+                                     atsc_window_runs *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    const int rc = runs_check_condition(ctx, op, limit);
+    if (rc) return rc;
+    RunQuery q;
+    q.op = op;
+    q.limit = limit;
+    return reduce_dev<RunQuery>(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0, q);
+    ATSC_API_END
+}
+
+// Host call: window_host_call into reduce_dev.
+extern "C" int atsc_runs_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                 const uint64_t *begin, const uint64_t *count, int op, double limit, atsc_window_runs *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "runs_windows: null argument");
+    const int rc = runs_check_condition(ctx, op, limit);
+    if (rc) return rc;
+    if (n_windows == 0) return ATSC_OK;
+    RunQuery q;
+    q.op = op;
+    q.limit = limit;
+    return window_host_call(
+        ctx, "runs_windows", body, body_len, has_count, n_windows, begin, count, out,
+        n_windows * sizeof(atsc_window_runs), false,
+        [&](bool any) {
+            for (uint64_t i = 0; !any && i < n_windows; ++i) run_empty_record(out[i]);
+            return ATSC_OK;
+        },
+        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
+            return reduce_dev<RunQuery>(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org, q);
+        });
+    ATSC_API_END
+}
+
+// Host only: the records of adjacent windows, left to right, into the record of their union (include/atsc_hip.h's rule).
+extern "C" int atsc_runs_merge(const atsc_window_runs *r, uint64_t n, atsc_window_runs *out)
+{
+    if (!out || (n && !r)) return ATSC_E_INVALID;
+    atsc_window_runs a;
+    run_empty_record(a);
+    for (uint64_t i = 0; i < n; ++i) {
+        const atsc_window_runs &b = r[i];
+        if (b.samples == 0) continue;
+        if (a.samples == 0) { a = b; continue; }
+        const uint64_t o = a.samples;
+        const bool join = a.tail && b.head;
+        if (join && a.tail + b.head > a.longest) { a.longest = a.tail + b.head; a.longest_at = o - a.tail; }
+        if (b.longest > a.longest) { a.longest = b.longest; a.longest_at = b.longest_at + o; }
+        a.runs = a.runs + b.runs - (join ? 1 : 0);
+        if (a.head == a.samples) a.head = a.samples + b.head;
+        a.tail = b.tail == b.samples ? b.samples + a.tail : b.tail;
+        if (!a.inside) a.first_at = b.inside ? b.first_at + o : ATSC_RUNS_NONE;
+        if (b.inside) a.last_at = b.last_at + o;
+        a.samples += b.samples;
+        a.inside += b.inside;
+        a.excess = a.excess + b.excess;
+    }
+    *out = a;
     return ATSC_OK;
 }
 
@@ -1548,6 +1667,27 @@ extern "C" int atsc_stream_delta_windows(atsc_stream *s, uint64_t n_windows, con
         return ATSC_OK;
     }
     return atsc_delta_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_runs_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                        int op, double limit, atsc_window_runs *out)
+{
+    ATSC_API_BEGIN
+    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
+    // (no context yet: the check comes before the pending chunks are compressed)
+    int rc = runs_check_condition(nullptr, op, limit);
+    if (rc) return rc;
+    std::vector<uint8_t> body;
+    atsc_ctx *ctx = nullptr;
+    rc = stream_body(s, body, &ctx);
+    if (rc) return rc;
+    if (body.empty()) {
+        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
+        for (uint64_t i = 0; i < n_windows; ++i) run_empty_record(out[i]);
+        return ATSC_OK;
+    }
+    return atsc_runs_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, op, limit, out);
     ATSC_API_END
 }
 

@@ -4,7 +4,7 @@
 // Compression and decompression run on the GPU; the index and the text formats are host code.
 //
 //   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
-//                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas]]]]
+//                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
@@ -43,6 +43,10 @@ struct Args {
     bool moments = false;  // --moments (with --step): the .agg.csv columns mean,stdvar,stddev,slope,intercept
     // --deltas (with --step): the .agg.csv columns pairs,rises,falls,up,down,increase,variation,max_rise,max_fall
     bool deltas = false;
+    // --runs OP:LIMIT (with --step): the .agg.csv columns inside,runs,longest,longest_at,first_at,last_at,head,tail,excess
+    bool have_runs = false;
+    int runs_op = ATSC_RUNS_GT;
+    double runs_limit = 0.0;
 };
 
 constexpr int PANIC = 101;  // exit status of a Rust panic: every failure below is an expect()/panic!()
@@ -68,6 +72,11 @@ void usage()
             "                                 pairs, rises, falls (a counter's resets), the sums of the rises (up) and of the\n"
             "                                 falls (down), the counter increase (every fall a restart from zero), the total\n"
             "                                 variation (up + down) and the largest single rise and fall\n"
+            "      --runs <OP:LIMIT>          with --step: also every bucket's samples with value OP LIMIT (OP: gt ge lt le eq\n"
+            "                                 ne, e.g. gt:0.9) and their runs of adjacent samples, as the last columns: inside,\n"
+            "                                 runs, longest (in samples), longest_at, first_at, last_at (the indexed times of\n"
+            "                                 those samples, empty where there is none), head, tail (in samples), excess (the\n"
+            "                                 sum of |value - LIMIT| over them)\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -216,6 +225,23 @@ int parse_histogram(const std::string &v, std::vector<double> &edges)
         p = c + 1;
     }
 }
+// --runs OP:LIMIT: OP one of gt ge lt le eq ne, LIMIT a number that is not NaN, nothing behind it
+bool parse_runs(const std::string &v, int &op, double &limit)
+{
+    static const char *const OPS[] = {"gt", "ge", "lt", "le", "eq", "ne"};
+    const size_t c = v.find(':');
+    if (c == std::string::npos) return false;
+    const std::string o = v.substr(0, c), t = v.substr(c + 1);
+    int k = 0;
+    while (k < 6 && o != OPS[k]) ++k;
+    char *e = nullptr;
+    const double x = strtod(t.c_str(), &e);
+    if (k == 6 || t.empty() || isspace((unsigned char)t[0]) || *e || x != x) return false;
+    op = k;  // ATSC_RUNS_GT .. ATSC_RUNS_NE in this order
+    limit = x;
+    return true;
+}
+
 int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *bro, uint64_t len)
 {
     atsc_vsri *index = nullptr;
@@ -254,6 +280,27 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
     if (a.deltas) rc = atsc_delta_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), dv.data());
     if (!rc && a.deltas) rc = atsc_delta_derive(dv.data(), nb, df.data());
     if (rc) { int e = die("deltas", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    std::vector<atsc_window_runs> rv(a.have_runs && nb ? nb : 1);
+    if (a.have_runs) rc = atsc_runs_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), a.runs_op, a.runs_limit, rv.data());
+    if (rc) { int e = die("runs", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    // "when did it start": the three positions as the indexed times of their samples, get_time(begin + offset)
+    std::vector<std::string> rt(a.have_runs ? 3 * nb : 0);
+    if (a.have_runs && nb) {
+        index = nullptr;
+        rc = atsc_vsri_load(with_ext(a.input, "vsri").c_str(), &index);
+        for (uint64_t k = 0; !rc && k < nb; ++k) {
+            const uint64_t at[3] = {rv[k].longest_at, rv[k].first_at, rv[k].last_at};
+            for (int j = 0; !rc && j < 3; ++j) {
+                if (at[j] == ATSC_RUNS_NONE) continue;
+                int32_t t = 0;
+                const int got = atsc_vsri_get_time(index, (int32_t)(b[k] + at[j]), &t);  // 1: Some(t), 0: None
+                if (got < 0) rc = got;
+                if (got == 1) rt[3 * k + j] = std::to_string(t);
+            }
+        }
+        if (index) atsc_vsri_free(index);
+        if (rc) { int e = die("runs: indexed time", rc); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    }
     atsc_ctx_destroy(ctx);
     atsc_free(bro);
     FILE *f = fopen(with_ext(output_base, "agg.csv").c_str(), "w");
@@ -264,6 +311,7 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
     if (nh) fprintf(f, ",hnan");
     if (a.moments) fprintf(f, ",mean,stdvar,stddev,slope,intercept");
     if (a.deltas) fprintf(f, ",pairs,rises,falls,up,down,increase,variation,max_rise,max_fall");
+    if (a.have_runs) fprintf(f, ",inside,runs,longest,longest_at,first_at,last_at,head,tail,excess");
     fprintf(f, "\n");
     for (uint64_t k = 0; k < nb; ++k) {
         fprintf(f, "%lld,%llu,%s,%s,%s,%s,%s", (long long)a.t0 + (long long)k * a.step, (unsigned long long)st[k].count,
@@ -279,6 +327,10 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
                     (unsigned long long)dv[k].falls, debug_f64(dv[k].up).c_str(), debug_f64(dv[k].down).c_str(),
                     debug_f64(df[k].increase).c_str(), debug_f64(df[k].variation).c_str(),
                     debug_f64(dv[k].max_rise).c_str(), debug_f64(dv[k].max_fall).c_str());
+        if (a.have_runs)
+            fprintf(f, ",%llu,%llu,%llu,%s,%s,%s,%llu,%llu,%s", (unsigned long long)rv[k].inside, (unsigned long long)rv[k].runs,
+                    (unsigned long long)rv[k].longest, rt[3 * k].c_str(), rt[3 * k + 1].c_str(), rt[3 * k + 2].c_str(),
+                    (unsigned long long)rv[k].head, (unsigned long long)rv[k].tail, debug_f64(rv[k].excess).c_str());
         fprintf(f, "\n");
     }
     if (fclose(f) != 0) return die("failed to write aggregates to file");
@@ -447,6 +499,13 @@ int main(int argc, char **argv)
         }
         else if (s == "--moments") a.moments = true;
         else if (s == "--deltas") a.deltas = true;
+        else if (value("--runs")) {
+            if (!parse_runs(v, a.runs_op, a.runs_limit)) {
+                fprintf(stderr, "error: invalid value '%s': '--runs' wants OP:LIMIT (OP: gt ge lt le eq ne)\n", v.c_str());
+                return 2;
+            }
+            a.have_runs = true;
+        }
         else if (value("--compressor")) { if (!parse_compressor(v, a.compressor)) { fprintf(stderr, "error: invalid value '%s' for '--compressor'\n", v.c_str()); return 2; } }
         else if (value("--error") || value("-e")) { if (!parse_int(v, 0, 50, a.error)) { fprintf(stderr, "error: invalid value '%s' for '--error': not in 0..=50\n", v.c_str()); return 2; } }
         else if (value("--compression-selection-sample-level") || value("-c")) { if (!parse_int(v, 0, 6, a.level)) { fprintf(stderr, "error: invalid value '%s' for '-c': not in 0..=6\n", v.c_str()); return 2; } }
@@ -484,6 +543,10 @@ int main(int argc, char **argv)
     }
     if (a.deltas && !a.step) {
         fprintf(stderr, "error: '--deltas' needs '--step'\n");
+        return 2;
+    }
+    if (a.have_runs && !a.step) {
+        fprintf(stderr, "error: '--runs' needs '--step'\n");
         return 2;
     }
     a.window = have_from;

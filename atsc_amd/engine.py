@@ -29,6 +29,15 @@ WINDOW_DELTA = np.dtype([("pairs", "<u8"), ("rises", "<u8"), ("falls", "<u8"), (
 WINDOW_DELTA_FIT = np.dtype([("changes", "<u8"), ("variation", "<f8"), ("net", "<f8"), ("increase", "<f8"),
                              ("mean_step", "<f8")])
 
+# atsc_window_runs (include/atsc_hip.h): the samples of one window that meet a condition and their runs, 80 bytes
+WINDOW_RUNS = np.dtype([("samples", "<u8"), ("inside", "<u8"), ("runs", "<u8"), ("longest", "<u8"),
+                        ("longest_at", "<u8"), ("first_at", "<u8"), ("last_at", "<u8"), ("head", "<u8"), ("tail", "<u8"),
+                        ("excess", "<f8")])
+# the condition's operators, and the position of a record that has none (ATSC_RUNS_*)
+RUNS_GT, RUNS_GE, RUNS_LT, RUNS_LE, RUNS_EQ, RUNS_NE = (capi.RUNS_GT, capi.RUNS_GE, capi.RUNS_LT, capi.RUNS_LE,
+                                                        capi.RUNS_EQ, capi.RUNS_NE)
+RUNS_NONE = capi.RUNS_NONE
+
 
 def _windows(begins, counts):
     b, pb = _u64(np.atleast_1d(begins))
@@ -71,6 +80,17 @@ def delta_derive(deltas):
     out = np.zeros(max(len(d), 1), dtype=WINDOW_DELTA_FIT)
     capi.check(capi.lib().atsc_delta_derive(C.c_void_p(d.ctypes.data), len(d), C.c_void_p(out.ctypes.data)))
     return out[: len(d)]
+
+
+def runs_merge(records):
+    """-> one WINDOW_RUNS record (a 0-d array): the records of adjacent windows, left to right, folded into the record of
+    their union (atsc_runs_merge; no GPU).  The nine integers are the union window's; excess is the records' sum, one add
+    per record"""
+    r = np.ascontiguousarray(np.atleast_1d(np.asarray(records, dtype=WINDOW_RUNS)))
+    out = np.zeros(1, dtype=WINDOW_RUNS)
+    capi.check(capi.lib().atsc_runs_merge(C.c_void_p(r.ctypes.data if len(r) else None), len(r),
+                                          C.c_void_p(out.ctypes.data)))
+    return out[0]
 
 
 def bucket_windows(begin, count, bucket):
@@ -210,6 +230,18 @@ class Context:
         out = np.zeros(max(len(wb), 1), dtype=WINDOW_DELTA)
         rc = capi.lib().atsc_delta_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
                                            len(wb), pb, pc, C.c_void_p(out.ctypes.data))
+        capi.check(rc, self._h)
+        return out[: len(wb)]
+
+    def runs_windows_host(self, records, begins, counts, op, limit, has_count=False):
+        """-> WINDOW_RUNS array: the samples with x OP limit (op: RUNS_GT .. RUNS_NE), their maximal runs, the longest
+        run, the first and last such sample, the runs at the two ends and the sum of |x - limit| of every window
+        [begins[i], begins[i] + counts[i]) of the decoded records (atsc_runs_windows)"""
+        b = np.frombuffer(bytes(records), dtype=np.uint8)
+        wb, pb, wc, pc = _windows(begins, counts)
+        out = np.zeros(max(len(wb), 1), dtype=WINDOW_RUNS)
+        rc = capi.lib().atsc_runs_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
+                                          len(wb), pb, pc, int(op), float(limit), C.c_void_p(out.ctypes.data))
         capi.check(rc, self._h)
         return out[: len(wb)]
 
@@ -383,6 +415,15 @@ class DPlan:
         assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= 64 * len(b)
         rc = capi.lib().atsc_delta_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
                                                C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
+        capi.check(rc, self.ctx._h)
+
+    def runs_windows(self, d_body, begins, counts, op, limit, d_out, stream=0):
+        """Enqueues the runs of the samples with x OP limit of the windows [begins[i], begins[i] + counts[i]) into d_out,
+        a device tensor of at least 80 bytes per window (atsc_runs_windows_dev; WINDOW_RUNS records)"""
+        b, pb, c, pc = _windows(begins, counts)
+        assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= 80 * len(b)
+        rc = capi.lib().atsc_runs_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
+                                              int(op), float(limit), C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
         capi.check(rc, self.ctx._h)
 
     def quantile_windows(self, d_body, begins, counts, levels, d_out, method=capi.QUANTILE_LINEAR, stream=0):

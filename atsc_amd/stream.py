@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit  # noqa: F401
+from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit  # noqa: F401
 
 
 def _f64(x):
@@ -115,6 +115,15 @@ class CompressedStream:
                    self.ctx._h)
         return out[: len(wb)]
 
+    def runs_windows(self, begins, counts, op, limit):
+        """-> WINDOW_RUNS array of the windows [begins[i], begins[i] + counts[i]) under the condition x OP limit
+        (atsc_stream_runs_windows)"""
+        wb, pb, wc, pc = _windows(begins, counts)
+        out = np.zeros(max(len(wb), 1), dtype=WINDOW_RUNS)
+        capi.check(capi.lib().atsc_stream_runs_windows(self._h, len(wb), pb, pc, int(op), float(limit),
+                                                       C.c_void_p(out.ctypes.data)), self.ctx._h)
+        return out[: len(wb)]
+
     def quantile_windows(self, begins, counts, levels, method=capi.QUANTILE_LINEAR):
         """-> (n_windows, n_levels) float64 array of the windows' levels (atsc_stream_quantile_windows)"""
         wb, pb, wc, pc = _windows(begins, counts)
@@ -207,6 +216,20 @@ def delta_data_windows(ctx, bro, begins, counts):
     r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
     rc = capi.lib().atsc_delta_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
                                        C.c_void_p(out.ctypes.data))
+    capi.check(rc, ctx._h)
+    return out[: len(wb)]
+
+
+def runs_data_windows(ctx, bro, begins, counts, op, limit):
+    """-> WINDOW_RUNS array of windows of decompress_data(ctx, bro) under the condition x OP limit: atsc_bro_open, then
+    atsc_runs_windows over the records"""
+    b = np.frombuffer(bytes(bro), dtype=np.uint8)
+    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
+    wb, pb, wc, pc = _windows(begins, counts)
+    out = np.zeros(max(len(wb), 1), dtype=WINDOW_RUNS)
+    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
+    rc = capi.lib().atsc_runs_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
+                                      int(op), float(limit), C.c_void_p(out.ctypes.data))
     capi.check(rc, ctx._h)
     return out[: len(wb)]
 

@@ -320,7 +320,7 @@ int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len
  * samples (128 MiB, plus 2 MiB of room for two large frames cut by a piece's ends where a frame longer than 4096 samples
  * is touched).  A budget below what one piece needs is raised to that minimum, never an error.  It bounds the quantile
  * calls below too, whose windows must each fit one piece, and the moments (atsc_moments_windows_dev), delta
- * (atsc_delta_windows_dev) and histogram calls (atsc_histogram_windows_dev), whose windows may be of any length. */
+ * (atsc_delta_windows_dev), runs (atsc_runs_windows_dev) and histogram calls (atsc_histogram_windows_dev), whose windows may be of any length. */
 int atsc_ctx_set_aggregate_scratch(atsc_ctx *ctx, uint64_t bytes);
 
 /* Windowed moments: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames) the
@@ -447,6 +447,68 @@ typedef struct {
 } atsc_window_delta_fit; /* 40 bytes */
 int atsc_delta_derive(const atsc_window_delta *d, uint64_t n, atsc_window_delta_fit *out);
 
+/* Windowed runs: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames) which of
+ * its samples meet a condition and whether those lie together, from the same decoded samples as the window decode: was
+ * the series over a limit for 300 samples in a row (an alerting rule's `for:`), how many excursions were there, how long
+ * was the longest and where did it start, is the series still over the limit at the window's end and for how long.
+ *   Condition  an operator and a limit, the same for every window of a call.  A sample x is INSIDE iff it is not NaN and
+ *          x OP limit holds, compared as values: -0.0 equals +0.0, +-Inf samples compare like any other value.  NaN is
+ *          never inside, under ATSC_RUNS_NE too, so it ends a run.  limit may be +-Inf, not NaN.
+ *   Runs   A run is a maximal stretch of stream-adjacent inside samples within the window; a run that the window's edge
+ *          cuts counts with the length it has inside the window.  Positions are offsets from `begin`.
+ *   excess The term of an inside sample is fabs(x - limit), one correctly rounded subtract, at the sample's own slot; every
+ *          other slot holds -0.0, and the sum takes the aggregate sum's tree unchanged (atsc_aggregate_windows, steps 1-3
+ *          above).  inside == 0 gives +0.0.  Where IEEE gives NaN, any NaN conforms: that is Inf - Inf alone, a +Inf
+ *          sample against a +Inf limit under GE / LE / EQ, and likewise with -Inf.  With u = 2^-53 and
+ *          L = max(1, ceil(log2 inside)), for finite data |excess - exact| <= (L + 3) u exact (one rounding for the
+ *          subtract, L + 2 for the tree, as for the delta sums).
+ * A window that is inside throughout has head == tail == longest == samples and runs == 1.  count == 0 gives samples =
+ * inside = runs = longest = head = tail = 0, the three positions ATSC_RUNS_NONE and excess = +0.0.  The nine integers are
+ * exact, and the whole record is bit-exact: it depends only on the stream's samples, the window and the condition, not on
+ * the other windows, their order, the budget, piece boundaries or the device.
+ * ATSC_E_INVALID with nothing written, before any GPU work, for an unknown op or a NaN limit.  Validation and the other
+ * semantics are atsc_aggregate_windows_dev's: a window beyond the stream gives ATSC_E_INVALID with nothing written;
+ * payloads are checked only of the frames a window touches; windows may overlap and come in any order; count == 0 and
+ * n_windows == 0 are valid.  Windows may be of any length (a run that crosses two pieces of the scratch that
+ * atsc_ctx_set_aggregate_scratch bounds is joined when their partials merge): there is no ATSC_E_CAPACITY case. */
+enum { ATSC_RUNS_GT = 0, ATSC_RUNS_GE = 1, ATSC_RUNS_LT = 2, ATSC_RUNS_LE = 3, ATSC_RUNS_EQ = 4, ATSC_RUNS_NE = 5 };
+#define ATSC_RUNS_NONE UINT64_MAX
+typedef struct {
+    uint64_t samples;    /* count[i], NaN included */
+    uint64_t inside;     /* samples that meet the condition */
+    uint64_t runs;       /* maximal runs */
+    uint64_t longest;    /* length of the longest run; 0 when runs == 0 */
+    uint64_t longest_at; /* offset of its first sample; of equal runs the earliest; ATSC_RUNS_NONE when runs == 0 */
+    uint64_t first_at;   /* offset of the first inside sample; ATSC_RUNS_NONE when inside == 0 */
+    uint64_t last_at;    /* offset of the last inside sample; ATSC_RUNS_NONE when inside == 0 */
+    uint64_t head;       /* length of the run that starts at the window's first sample, else 0 */
+    uint64_t tail;       /* length of the run that ends at the window's last sample, else 0 */
+    double excess;       /* sum of |x - limit| over the inside samples */
+} atsc_window_runs; /* 80 bytes */
+/* d_out[i] holds window i.  begin / count are HOST arrays; d_body and d_out are device memory (d_out 8-byte aligned).
+ * Enqueued on `stream`, not synchronised.  A malformed payload inside a window sets the plan's status word.  The plan
+ * keeps the call's tables, partials and scratch: the next runs call on the same plan waits (host side) until this
+ * one's work is done; atsc_dplan_destroy frees them. */
+int atsc_runs_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                          const uint64_t *begin, const uint64_t *count, int op, double limit, atsc_window_runs *d_out,
+                          void *stream);
+/* Host bytes in, host records out, synchronous; walks and uploads only the touched records, as atsc_aggregate_windows
+ * does.  ATSC_E_FORMAT (nothing written) for a malformed payload inside a window. */
+int atsc_runs_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                      const uint64_t *begin, const uint64_t *count, int op, double limit, atsc_window_runs *out);
+/* Folds the records of n adjacent windows, left to right, into the record of their union, host only (no GPU): r[i + 1]
+ * begins where r[i] ends -- per-minute buckets into hours, a run that goes on from one day's file into the next.  Records
+ * with samples == 0 are skipped; n == 0 gives the empty record; ATSC_E_INVALID for a null pointer with n > 0 or a null
+ * out.  The merge of a followed by b, o = a.samples, both non-empty:
+ *   samples and inside add;  runs = a.runs + b.runs - (a.tail && b.head ? 1 : 0);
+ *   head = a.head == a.samples ? a.samples + b.head : a.head;  tail = b.tail == b.samples ? b.samples + a.tail : b.tail;
+ *   first_at = a.inside ? a.first_at : (b.inside ? b.first_at + o : NONE);  last_at = b.inside ? b.last_at + o : a.last_at;
+ *   longest / longest_at: a's; the joined run a.tail + b.head at o - a.tail replaces it if both parts are non-zero and it
+ *   is strictly longer; then b's, at b.longest_at + o, replaces that if strictly longer (so the earliest of equal runs wins).
+ * The nine integers come out as the union window's, exactly.  excess is (r[0].excess + r[1].excess) + r[2].excess ...,
+ * one add per record: it may differ from the union window's own value in its last bits. */
+int atsc_runs_merge(const atsc_window_runs *r, uint64_t n, atsc_window_runs *out);
+
 /* Windowed quantiles: exact order statistics of windows [begin, begin + count) of the decoded stream (the indices of
  * atsc_decompress_frames), from the same decoded samples as the window decode.  For window i:
  *   x  the window's non-NaN samples, n of them, sorted in IEEE total order (-0.0 before +0.0), i.e. by the keys
@@ -550,6 +612,9 @@ int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint
 /* atsc_delta_windows over the stream's frames */
 int atsc_stream_delta_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                               atsc_window_delta *out);
+/* atsc_runs_windows over the stream's frames */
+int atsc_stream_runs_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count, int op,
+                             double limit, atsc_window_runs *out);
 /* atsc_moments_windows over the stream's frames */
 int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 atsc_window_moments *out);
