@@ -15,6 +15,7 @@ CLI = os.path.join(HERE, "bin", "atsc")
 CLI_SRC = "atsc_cli.cpp"
 CLI2 = os.path.join(HERE, "bin", "csv-compressor")
 CLI2_SRC = "csv_compressor_cli.cpp"
+CLI_HEADER = "atsc_cli_buckets.h"  # what the two front ends share; no library source includes it
 DEPS = SOURCES + ["atsc_device.h", "atsc_internal.h", "atsc_host_private.h", "atsc_large_cols.h", "atsc_large_fast.h",
                   os.path.join("..", "..", "include", "atsc_hip.h")]
 # -ffp-contract=off: the f64 spline / rounding arithmetic must evaluate exactly as written
@@ -34,7 +35,7 @@ def stale():
     if not os.path.exists(LIB) or not os.path.exists(CLI) or not os.path.exists(CLI2):
         return True
     t = min(os.path.getmtime(LIB), os.path.getmtime(CLI), os.path.getmtime(CLI2))
-    return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS + [CLI_SRC, CLI2_SRC])
+    return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS + [CLI_SRC, CLI2_SRC, CLI_HEADER])
 
 
 OBJDIR = os.path.join(HERE, "build" + ("_" + VARIANT if VARIANT else ""))

@@ -1,0 +1,317 @@
+// atsc_cli_buckets.h -- what the two command lines (atsc_cli.cpp, csv_compressor_cli.cpp) share: the small text helpers
+// and the bucket queries behind `atsc -u --buckets N` and `csv-compressor -u --from --to --step S`: their options, the
+// usage errors, the calls over the buckets and the columns of the .agg.csv.  The two differ in the row's first cell,
+// in how a failure is reported and in the three run positions, which the caller hands in.
+#pragma once
+#include <cctype>
+#include <charconv>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../include/atsc_hip.h"
+
+namespace {
+
+bool parse_int(const std::string &v, int lo, int hi, int &out)
+{
+    if (v.empty()) return false;
+    char *end = nullptr;
+    long x = strtol(v.c_str(), &end, 10);
+    if (*end || x < lo || x > hi) return false;
+    out = (int)x;
+    return true;
+}
+
+// Rust `{:?}` of an f64: shortest round-trip digits (exponent form where that is shorter), ".0" appended to integers
+std::string debug_f64(double v)
+{
+    if (std::isnan(v)) return "NaN";
+    if (std::isinf(v)) return v < 0 ? "-inf" : "inf";
+    char buf[64];
+    auto r = std::to_chars(buf, buf + sizeof(buf), v);
+    std::string s(buf, r.ptr);
+    if (s.find('e') == std::string::npos && s.find('.') == std::string::npos) s += ".0";
+    return s;
+}
+
+std::string with_ext(const std::string &path, const char *ext)  // PathBuf::set_extension
+{
+    const size_t slash = path.find_last_of('/');
+    const size_t dot = path.find_last_of('.');
+    std::string base = (dot != std::string::npos && (slash == std::string::npos || dot > slash + 1)) ? path.substr(0, dot) : path;
+    return base + "." + ext;
+}
+
+// The queries beside the buckets' count,min,max,sum,first,last, each with the .agg.csv columns it adds
+struct BucketOptions {
+    std::vector<double> levels;  // --quantiles: one column per level
+    std::vector<std::string> level_names;
+    int method = ATSC_QUANTILE_LINEAR;  // --quantile-method
+    bool have_method = false;
+    std::vector<double> edges;  // --histogram: h0 .. h<n_edges>,hnan
+    bool have_hist = false;
+    int closed = ATSC_HIST_LEFT_CLOSED;  // --histogram-closed
+    bool have_closed = false;
+    bool moments = false;  // --moments: mean,stdvar,stddev,slope,intercept
+    bool deltas = false;   // --deltas: pairs,rises,falls,up,down,increase,variation,max_rise,max_fall
+    bool have_runs = false;  // --runs OP:LIMIT: inside,runs,longest,longest_at,first_at,last_at,head,tail,excess
+    int runs_op = ATSC_RUNS_GT;
+    double runs_limit = 0.0;
+};
+
+// --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
+bool parse_levels(const std::string &v, std::vector<double> &q, std::vector<std::string> &names)
+{
+    q.clear();
+    names.clear();
+    for (size_t p = 0;;) {
+        const size_t c = v.find(',', p);
+        const std::string t = v.substr(p, c == std::string::npos ? std::string::npos : c - p);
+        char *e = nullptr;
+        const double x = strtod(t.c_str(), &e);
+        if (t.empty() || isspace((unsigned char)t[0]) || *e || !(x >= 0.0 && x <= 1.0)) return false;
+        q.push_back(x);
+        names.push_back(t);
+        if (c == std::string::npos) return true;
+        p = c + 1;
+    }
+}
+
+bool parse_method(const std::string &v, int &m)
+{
+    static const char *names[] = {"linear", "lower", "higher", "nearest"};  // ATSC_QUANTILE_* order
+    for (int k = 0; k < 4; ++k)
+        if (v == names[k]) { m = k; return true; }
+    return false;
+}
+
+// --histogram SPEC: explicit edges E,E,.. or LO:HI:N, N equal bins over [LO, HI] (atsc_histogram_edges_uniform).
+// 0: fine; 1: unparsable, NaN or not ascending, or a bad uniform spec; 2: more than ATSC_HIST_MAX_EDGES edges
+int parse_histogram(const std::string &v, std::vector<double> &edges)
+{
+    edges.clear();
+    auto number = [](const std::string &t, double &x) {
+        char *e = nullptr;
+        x = strtod(t.c_str(), &e);
+        return !t.empty() && !isspace((unsigned char)t[0]) && !*e && x == x;
+    };
+    const size_t c1 = v.find(':');
+    if (c1 != std::string::npos) {
+        const size_t c2 = v.find(':', c1 + 1);
+        if (c2 == std::string::npos) return 1;
+        double lo, hi;
+        const std::string ns = v.substr(c2 + 1);
+        char *e = nullptr;
+        const unsigned long long n = strtoull(ns.c_str(), &e, 10);
+        if (!number(v.substr(0, c1), lo) || !number(v.substr(c1 + 1, c2 - c1 - 1), hi) || ns.empty() || *e ||
+            !isdigit((unsigned char)ns[0]))
+            return 1;
+        if (n >= ATSC_HIST_MAX_EDGES) return 2;
+        edges.resize(n + 1);
+        return atsc_histogram_edges_uniform(lo, hi, (uint32_t)n, edges.data()) ? 1 : 0;
+    }
+    for (size_t p = 0;;) {
+        const size_t c = v.find(',', p);
+        double x;
+        if (!number(v.substr(p, c == std::string::npos ? std::string::npos : c - p), x)) return 1;
+        if (!edges.empty() && !(edges.back() < x)) return 1;
+        edges.push_back(x);
+        if (c == std::string::npos) return edges.size() > (size_t)ATSC_HIST_MAX_EDGES ? 2 : 0;
+        p = c + 1;
+    }
+}
+
+// --runs OP:LIMIT: OP one of gt ge lt le eq ne, LIMIT a number that is not NaN, nothing behind it
+bool parse_runs(const std::string &v, int &op, double &limit)
+{
+    static const char *const OPS[] = {"gt", "ge", "lt", "le", "eq", "ne"};
+    const size_t c = v.find(':');
+    if (c == std::string::npos) return false;
+    const std::string o = v.substr(0, c), t = v.substr(c + 1);
+    int k = 0;
+    while (k < 6 && o != OPS[k]) ++k;
+    char *e = nullptr;
+    const double x = strtod(t.c_str(), &e);
+    if (k == 6 || t.empty() || isspace((unsigned char)t[0]) || *e || x != x) return false;
+    op = k;  // ATSC_RUNS_GT .. ATSC_RUNS_NE in this order
+    limit = x;
+    return true;
+}
+
+// One argument of the command line, where it is a bucket-query option.  s: the argument; value(name): whether s is the
+// option `name` with a value, which it leaves in v (the callers' lambda).  0: none of them; 1: taken; 2: a usage error,
+// reported on stderr.
+template <class Value>
+int bucket_option(const std::string &s, const std::string &v, Value value, BucketOptions &o)
+{
+    if (value("--quantiles")) {
+        if (!parse_levels(v, o.levels, o.level_names)) {
+            fprintf(stderr, "error: invalid value '%s' for '--quantiles': expected levels in 0..=1, comma separated\n", v.c_str());
+            return 2;
+        }
+        if (o.levels.size() > 64) {
+            fprintf(stderr, "error: invalid value for '--quantiles': %zu levels, at most 64\n", o.levels.size());
+            return 2;
+        }
+    } else if (value("--quantile-method")) {
+        if (!parse_method(v, o.method)) {
+            fprintf(stderr, "error: invalid value '%s' for '--quantile-method': linear, lower, higher or nearest\n", v.c_str());
+            return 2;
+        }
+        o.have_method = true;
+    } else if (value("--histogram")) {
+        const int bad = parse_histogram(v, o.edges);
+        if (bad == 1) {
+            fprintf(stderr, "error: invalid value '%s' for '--histogram': expected ascending edges E,E,.. or LO:HI:N\n", v.c_str());
+            return 2;
+        }
+        if (bad == 2) {
+            fprintf(stderr, "error: invalid value for '--histogram': more than %d edges\n", (int)ATSC_HIST_MAX_EDGES);
+            return 2;
+        }
+        o.have_hist = true;
+    } else if (value("--histogram-closed")) {
+        if (v != "left" && v != "right") {
+            fprintf(stderr, "error: invalid value '%s' for '--histogram-closed': left or right\n", v.c_str());
+            return 2;
+        }
+        o.closed = v == "right" ? ATSC_HIST_RIGHT_CLOSED : ATSC_HIST_LEFT_CLOSED;
+        o.have_closed = true;
+    } else if (s == "--moments") {
+        o.moments = true;
+    } else if (s == "--deltas") {
+        o.deltas = true;
+    } else if (value("--runs")) {
+        if (!parse_runs(v, o.runs_op, o.runs_limit)) {
+            fprintf(stderr, "error: invalid value '%s': '--runs' wants OP:LIMIT (OP: gt ge lt le eq ne)\n", v.c_str());
+            return 2;
+        }
+        o.have_runs = true;
+    } else {
+        return 0;
+    }
+    return 1;
+}
+
+// The options that need another one.  bucketing: the caller's option that cuts the buckets ("--buckets" or "--step"),
+// given: whether it was there.  false: a usage error, reported on stderr.
+bool bucket_options_complete(const BucketOptions &o, const char *bucketing, bool given)
+{
+    const struct {
+        bool have, needed;
+        const char *name, *needs;
+    } T[] = {{!o.levels.empty(), given, "--quantiles", bucketing},
+             {o.have_method, !o.levels.empty(), "--quantile-method", "--quantiles"},
+             {o.have_hist, given, "--histogram", bucketing},
+             {o.have_closed, o.have_hist, "--histogram-closed", "--histogram"},
+             {o.moments, given, "--moments", bucketing},
+             {o.deltas, given, "--deltas", bucketing},
+             {o.have_runs, given, "--runs", bucketing}};
+    for (const auto &t : T)
+        if (t.have && !t.needed) {
+            fprintf(stderr, "error: '%s' needs '%s'\n", t.name, t.needs);
+            return false;
+        }
+    return true;
+}
+
+// what the queries gave, per bucket
+struct BucketResults {
+    std::vector<atsc_window_stats> st;
+    uint64_t nq = 0, nh = 0;  // levels and counters per bucket
+    std::vector<double> qv;
+    std::vector<uint64_t> hv;
+    std::vector<atsc_window_moments> mv;
+    std::vector<atsc_window_fit> fv;
+    std::vector<atsc_window_delta> dv;
+    std::vector<atsc_window_delta_fit> df;
+    std::vector<atsc_window_runs> rv;
+};
+
+// Runs the aggregates and the selected queries over the nb buckets (b, c) of a .bro image, the records from the
+// frame-count varint on, as atsc_decompress_data reads them.  A failure ends it: its rc, and *failed names the query.
+int bucket_queries(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t nb, const uint64_t *b,
+                   const uint64_t *c, BucketResults &r, const char **failed)
+{
+    const uint8_t *body = bro + 9;
+    const uint64_t body_len = len - 9;
+    r.st.resize(nb ? nb : 1);
+    *failed = "aggregate";
+    int rc = atsc_aggregate_windows(ctx, body, body_len, 1, nb, b, c, r.st.data());
+    if (rc) return rc;
+    *failed = "quantiles";
+    r.nq = o.levels.size();
+    r.qv.resize(nb * r.nq ? nb * r.nq : 1);
+    if (r.nq) rc = atsc_quantile_windows(ctx, body, body_len, 1, nb, b, c, (uint32_t)r.nq, o.levels.data(), o.method, r.qv.data());
+    if (rc) return rc;
+    *failed = "histogram";
+    r.nh = o.have_hist ? o.edges.size() + 2 : 0;
+    r.hv.resize(nb * r.nh ? nb * r.nh : 1);
+    if (r.nh) rc = atsc_histogram_windows(ctx, body, body_len, 1, nb, b, c, (uint32_t)o.edges.size(), o.edges.data(), o.closed,
+                                          r.hv.data());
+    if (rc) return rc;
+    *failed = "moments";
+    r.mv.resize(o.moments && nb ? nb : 1);
+    r.fv.resize(r.mv.size());
+    if (o.moments) rc = atsc_moments_windows(ctx, body, body_len, 1, nb, b, c, r.mv.data());
+    if (!rc && o.moments) rc = atsc_moments_fit(r.mv.data(), nb, r.fv.data());
+    if (rc) return rc;
+    *failed = "deltas";
+    r.dv.resize(o.deltas && nb ? nb : 1);
+    r.df.resize(r.dv.size());
+    if (o.deltas) rc = atsc_delta_windows(ctx, body, body_len, 1, nb, b, c, r.dv.data());
+    if (!rc && o.deltas) rc = atsc_delta_derive(r.dv.data(), nb, r.df.data());
+    if (rc) return rc;
+    *failed = "runs";
+    r.rv.resize(o.have_runs && nb ? nb : 1);
+    if (o.have_runs) rc = atsc_runs_windows(ctx, body, body_len, 1, nb, b, c, o.runs_op, o.runs_limit, r.rv.data());
+    return rc;
+}
+
+// the .agg.csv header; first: the name of the rows' first cell
+void bucket_header(FILE *f, const char *first, const BucketOptions &o, const BucketResults &r)
+{
+    fprintf(f, "%s,count,min,max,sum,first,last", first);
+    for (const std::string &n : o.level_names) fprintf(f, ",q%s", n.c_str());
+    for (uint64_t j = 0; j + 1 < r.nh; ++j) fprintf(f, ",h%llu", (unsigned long long)j);
+    if (r.nh) fprintf(f, ",hnan");
+    if (o.moments) fprintf(f, ",mean,stdvar,stddev,slope,intercept");
+    if (o.deltas) fprintf(f, ",pairs,rises,falls,up,down,increase,variation,max_rise,max_fall");
+    if (o.have_runs) fprintf(f, ",inside,runs,longest,longest_at,first_at,last_at,head,tail,excess");
+    fprintf(f, "\n");
+}
+
+// the row of bucket k; first: its first cell; run_at: with --runs, the cells longest_at, first_at, last_at
+void bucket_row(FILE *f, const std::string &first, const BucketOptions &o, const BucketResults &r, uint64_t k,
+                const std::string *run_at)
+{
+    const atsc_window_stats &st = r.st[k];
+    fprintf(f, "%s,%llu,%s,%s,%s,%s,%s", first.c_str(), (unsigned long long)st.count, debug_f64(st.min).c_str(),
+            debug_f64(st.max).c_str(), debug_f64(st.sum).c_str(), debug_f64(st.first).c_str(), debug_f64(st.last).c_str());
+    for (uint64_t j = 0; j < r.nq; ++j) fprintf(f, ",%s", debug_f64(r.qv[k * r.nq + j]).c_str());
+    for (uint64_t j = 0; j < r.nh; ++j) fprintf(f, ",%llu", (unsigned long long)r.hv[k * r.nh + j]);
+    if (o.moments) {
+        const atsc_window_fit &fv = r.fv[k];
+        fprintf(f, ",%s,%s,%s,%s,%s", debug_f64(fv.mean).c_str(), debug_f64(fv.variance).c_str(), debug_f64(fv.stddev).c_str(),
+                debug_f64(fv.slope).c_str(), debug_f64(fv.intercept).c_str());
+    }
+    if (o.deltas) {
+        const atsc_window_delta &dv = r.dv[k];
+        fprintf(f, ",%llu,%llu,%llu,%s,%s,%s,%s,%s,%s", (unsigned long long)dv.pairs, (unsigned long long)dv.rises,
+                (unsigned long long)dv.falls, debug_f64(dv.up).c_str(), debug_f64(dv.down).c_str(),
+                debug_f64(r.df[k].increase).c_str(), debug_f64(r.df[k].variation).c_str(), debug_f64(dv.max_rise).c_str(),
+                debug_f64(dv.max_fall).c_str());
+    }
+    if (o.have_runs) {
+        const atsc_window_runs &rv = r.rv[k];
+        fprintf(f, ",%llu,%llu,%llu,%s,%s,%s,%llu,%llu,%s", (unsigned long long)rv.inside, (unsigned long long)rv.runs,
+                (unsigned long long)rv.longest, run_at[0].c_str(), run_at[1].c_str(), run_at[2].c_str(),
+                (unsigned long long)rv.head, (unsigned long long)rv.tail, debug_f64(rv.excess).c_str());
+    }
+    fprintf(f, "\n");
+}
+
+}  // namespace

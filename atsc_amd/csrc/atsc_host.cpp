@@ -1723,13 +1723,7 @@ extern "C" void atsc_dplan_destroy(atsc_dplan *p)
     if (!p) return;
     (void)hipDeviceSynchronize();
     free_tables(p->ctx, p->tabs);
-    p->win.release(p->ctx);
-    p->agg.release(p->ctx);
-    p->qnt.release(p->ctx);
-    p->hst.release(p->ctx);
-    p->mom.release(p->ctx);
-    p->dlt.release(p->ctx);
-    p->run.release(p->ctx);
+    for (QueryRes &r : p->res) r.release(p->ctx);
     pool_free(p->ctx, p->d_frames);
     pool_free(p->ctx, p->d_ids);
     pool_free(p->ctx, p->d_status);

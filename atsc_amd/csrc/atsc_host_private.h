@@ -90,7 +90,8 @@ void pool_free(atsc_ctx *ctx, void *p);
 // What the last window query of one kind on a decode plan owns (atsc_windows.cpp): its task tables -- page-locked
 // staging `h` and the device copy `d`, which the call's device-only tables follow -- its scratch of decoded samples, and
 // the event that marks the end of its work.  A plan holds one per kind of query, so that a call waits only for the
-// previous call of its own kind.
+// previous call of its own kind (atsc_dplan::res, by QueryKind).
+enum QueryKind { Q_WINDOW, Q_AGGREGATE, Q_QUANTILE, Q_HISTOGRAM, Q_MOMENTS, Q_DELTA, Q_RUNS, Q_KINDS };
 struct QueryRes {
     unsigned char *h = nullptr, *d = nullptr;
     size_t h_cap = 0, d_cap = 0;
@@ -171,9 +172,8 @@ struct atsc_dplan {
     // samples [h_frames[f].out_off, h_frames[f + 1].out_off or n_samples)
     std::vector<atsc::DevDFrame> h_frames;
     std::vector<int> h_cls;
-    // what the last atsc_decompress_windows_dev, atsc_aggregate_windows_dev, atsc_quantile_windows_dev,
-    // atsc_histogram_windows_dev, atsc_moments_windows_dev, atsc_delta_windows_dev and atsc_runs_windows_dev call own
-    mutable atsc::QueryRes win, agg, qnt, hst, mom, dlt, run;
+    // what the last device call of each kind of window query owns
+    mutable atsc::QueryRes res[atsc::Q_KINDS];
 };
 
 namespace atsc {

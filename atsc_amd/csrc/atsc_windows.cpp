@@ -253,24 +253,19 @@ struct PieceDecode {
     uint32_t small_n[CLASS_LARGE], big_n, gat_n, max_len;
 };
 
-// the messages of a failed launch, by caller
+// the messages of a failed launch, by caller: the query's word in parentheses behind the kernel's name
 struct DecodeCaller {
     const char *small, *large, *gather;
 };
+#define DECODE_CALLER(word) \
+    { "launch k_decompress (" word ")", "launch k_decompress_large (" word ")", "launch k_window_gather (" word ")" }
+static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE = DECODE_CALLER("quantile"),
+                          BY_HISTOGRAM = DECODE_CALLER("histogram"), BY_MOMENTS = DECODE_CALLER("moments"),
+                          BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs");
+#undef DECODE_CALLER
+// (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
                                        "launch k_window_gather"};
-static const DecodeCaller BY_AGGREGATE = {"launch k_decompress (aggregate)", "launch k_decompress_large (aggregate)",
-                                          "launch k_window_gather (aggregate)"};
-static const DecodeCaller BY_QUANTILE = {"launch k_decompress (quantile)", "launch k_decompress_large (quantile)",
-                                         "launch k_window_gather (quantile)"};
-static const DecodeCaller BY_HISTOGRAM = {"launch k_decompress (histogram)", "launch k_decompress_large (histogram)",
-                                          "launch k_window_gather (histogram)"};
-static const DecodeCaller BY_MOMENTS = {"launch k_decompress (moments)", "launch k_decompress_large (moments)",
-                                        "launch k_window_gather (moments)"};
-static const DecodeCaller BY_DELTA = {"launch k_decompress (delta)", "launch k_decompress_large (delta)",
-                                      "launch k_window_gather (delta)"};
-static const DecodeCaller BY_RUNS = {"launch k_decompress (runs)", "launch k_decompress_large (runs)",
-                                     "launch k_window_gather (runs)"};
 
 // Enqueues one piece's decode (d: the device copy of the upload).  out: the base the tasks' destinations count from;
 // the copies go from gat_src to gat_dst.
@@ -440,7 +435,7 @@ extern "C" int atsc_decompress_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, 
     if (!launch_decompress_window || !launch_window_gather) return fail(ctx, ATSC_E_UNSUPPORTED, "decompress_windows: no window kernels");
     auto by_frame = [](const Ent &a, const Ent &b) { return a.frame < b.frame; };
     if (!std::is_sorted(ents.begin(), ents.end(), by_frame)) std::stable_sort(ents.begin(), ents.end(), by_frame);
-    QueryRes &R = dp->win;
+    QueryRes &R = dp->res[Q_WINDOW];
     HIPCHK(ctx, R.wait());
     // one piece holds every task; destinations in scratch count from the scratch's start until it is known where it lies
     DecodeTasks D;
@@ -644,16 +639,19 @@ static bool emit_piece_decode(const atsc_dplan *dp, uint64_t org, const std::vec
 // piece of launches.
 static const uint64_t AGG_GAP_TILES = 64;
 
-static void agg_empty_record(atsc_window_stats &r)
-{
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    r.count = 0;
-    r.min = r.max = r.first = r.last = nan;
-    r.sum = 0.0;
-}
+template <class Q>
+static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+                      const uint64_t *count, void *d_out, void *stream, uint64_t org, const Q &q);
 
-// What the three reductions over tiles differ in: the aggregates (atsc_aggregate.hip), the moments (atsc_moments.hip)
-// and the deltas (atsc_delta.hip).
+// A query's descriptor: what query_host and query_stream (below) need of it, and for the four reductions over tiles
+// what reduce_dev does.  The front end's part:
+//   CALL                the call's name in the messages
+//   out_bytes(n)        bytes of the result of n windows
+//   check(ctx)          the check of the call's parameters (ctx may be null: then no message is kept)
+//   fill_empty(out, n)  the result of n empty windows
+//   dev(...)            the device call; org: the stream index of the plan's first sample
+// What the reductions over tiles differ in: the aggregates (atsc_aggregate.hip), the moments (atsc_moments.hip), the
+// deltas (atsc_delta.hip) and the runs (atsc_runs.hip).
 //   Tile, tile(t, k)   the tile kernel's task, from the plan's DevAggTile of tile k of the stream
 //   PART               bytes of a partial
 //   SIDE               the table both kernels share beside the partials: the windows' first / last samples, which the
@@ -666,9 +664,9 @@ struct AggQuery {
                                 *TILES = "launch k_agg_tiles", *COMBINE = "launch k_agg_combine";
     static constexpr size_t PART = sizeof(DevAggPart);
     static constexpr bool SIDE_BEGINS = false;
+    static constexpr QueryKind KIND = Q_AGGREGATE;
     static const DecodeCaller &who() { return BY_AGGREGATE; }
     static bool have() { return launch_agg_tiles && launch_agg_combine; }
-    static QueryRes &res(const atsc_dplan *dp) { return dp->agg; }
     static constexpr bool CARRY = false;
     static Tile tile(const DevAggTile &t, uint64_t) { return t; }
     static bool carried(const Tile &) { return false; }
@@ -680,6 +678,23 @@ struct AggQuery {
     {
         return launch_agg_combine(c, n, (DevAggPart *)part, (const double *)side, out, s);
     }
+    static size_t out_bytes(uint64_t n) { return n * sizeof(atsc_window_stats); }
+    static int check(atsc_ctx *) { return ATSC_OK; }
+    static void fill_empty(void *out, uint64_t n)
+    {
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (uint64_t i = 0; i < n; ++i) {
+            atsc_window_stats &r = ((atsc_window_stats *)out)[i];
+            r.count = 0;
+            r.min = r.max = r.first = r.last = nan;
+            r.sum = 0.0;
+        }
+    }
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *count, void *d_res, void *stream, uint64_t org) const
+    {
+        return reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
+    }
 };
 struct MomQuery {
     using Tile = DevMomTile;
@@ -687,9 +702,9 @@ struct MomQuery {
                                 *TILES = "launch k_mom_tiles", *COMBINE = "launch k_mom_combine";
     static constexpr size_t PART = sizeof(DevMomPart);
     static constexpr bool SIDE_BEGINS = true;
+    static constexpr QueryKind KIND = Q_MOMENTS;
     static const DecodeCaller &who() { return BY_MOMENTS; }
     static bool have() { return launch_mom_tiles && launch_mom_combine; }
-    static QueryRes &res(const atsc_dplan *dp) { return dp->mom; }
     static constexpr bool CARRY = false;
     static Tile tile(const DevAggTile &t, uint64_t k) { return Tile{t.src, t.dst, k * AGG_TILE, t.lo, t.hi}; }
     static bool carried(const Tile &) { return false; }
@@ -701,6 +716,22 @@ struct MomQuery {
     {
         return launch_mom_combine(c, n, (DevMomPart *)part, (const uint64_t *)side, out, s);
     }
+    static size_t out_bytes(uint64_t n) { return n * sizeof(atsc_window_moments); }
+    static int check(atsc_ctx *) { return ATSC_OK; }
+    static void fill_empty(void *out, uint64_t n)
+    {
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (uint64_t i = 0; i < n; ++i) {
+            atsc_window_moments &r = ((atsc_window_moments *)out)[i];
+            r.count = 0;
+            r.mean = r.m2 = r.t_mean = r.t_m2 = r.c_tx = nan;
+        }
+    }
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *count, void *d_res, void *stream, uint64_t org) const
+    {
+        return reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
+    }
 };
 
 struct DltQuery {
@@ -710,9 +741,9 @@ struct DltQuery {
     static constexpr size_t PART = sizeof(DevDltPart);
     static constexpr bool SIDE_BEGINS = false;
     static constexpr bool CARRY = true;
+    static constexpr QueryKind KIND = Q_DELTA;
     static const DecodeCaller &who() { return BY_DELTA; }
     static bool have() { return launch_dlt_tiles && launch_dlt_combine; }
-    static QueryRes &res(const atsc_dplan *dp) { return dp->dlt; }
     // every tile but a window's first continues from the slot in front of it (the window covers that slot, so it was
     // decoded): scratch[src - 1], or the carry slot where the tile is the first of its piece
     static Tile tile(const DevAggTile &t, uint64_t)
@@ -729,11 +760,33 @@ struct DltQuery {
     {
         return launch_dlt_combine(c, n, (DevDltPart *)part, out, s);
     }
+    static size_t out_bytes(uint64_t n) { return n * sizeof(atsc_window_delta); }
+    static int check(atsc_ctx *) { return ATSC_OK; }
+    static void fill_empty(void *out, uint64_t n)
+    {
+        for (uint64_t i = 0; i < n; ++i) {
+            atsc_window_delta &r = ((atsc_window_delta *)out)[i];
+            r.pairs = r.rises = r.falls = 0;
+            r.up = r.down = r.after_falls = r.max_rise = r.max_fall = 0.0;
+        }
+    }
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *count, void *d_res, void *stream, uint64_t org) const
+    {
+        return reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
+    }
 };
 
-// The runs (atsc_runs.hip).  The one query with parameters of a call, the condition: they are the query object's members,
-// which reduce_dev hands to tiles() by calling it on that object.  No carry: the merge joins a run across two tiles,
-// whichever pieces they lie in.
+static void run_empty_record(atsc_window_runs &r)
+{
+    r.samples = r.inside = r.runs = r.longest = r.head = r.tail = 0;
+    r.longest_at = r.first_at = r.last_at = ATSC_RUNS_NONE;
+    r.excess = 0.0;
+}
+
+// The runs (atsc_runs.hip).  The one reduction with parameters of a call, the condition: they are the query object's
+// members, which reduce_dev hands to tiles() by calling it on that object.  No carry: the merge joins a run across two
+// tiles, whichever pieces they lie in.
 struct RunQuery {
     using Tile = DevRunTile;
     static constexpr const char *CALL = "runs_windows", *RES_NAME = "d_out", *NO_KERNELS = "no runs kernels",
@@ -741,11 +794,11 @@ struct RunQuery {
     static constexpr size_t PART = sizeof(DevRunPart);
     static constexpr bool SIDE_BEGINS = true;
     static constexpr bool CARRY = false;
-    int op = 0;
-    double limit = 0.0;
+    static constexpr QueryKind KIND = Q_RUNS;
+    int op;
+    double limit;
     static const DecodeCaller &who() { return BY_RUNS; }
     static bool have() { return launch_run_tiles && launch_run_combine; }
-    static QueryRes &res(const atsc_dplan *dp) { return dp->run; }
     static Tile tile(const DevAggTile &t, uint64_t k) { return Tile{t.src, t.dst, k * AGG_TILE, t.lo, t.hi}; }
     static bool carried(const Tile &) { return false; }
     hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s) const
@@ -755,6 +808,24 @@ struct RunQuery {
     static hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *side, void *out, hipStream_t s)
     {
         return launch_run_combine(c, n, (DevRunPart *)part, (const uint64_t *)side, out, s);
+    }
+    static size_t out_bytes(uint64_t n) { return n * sizeof(atsc_window_runs); }
+    int check(atsc_ctx *ctx) const
+    {
+        if (op < ATSC_RUNS_GT || op > ATSC_RUNS_NE) return fail(ctx, ATSC_E_INVALID, "runs_windows: unknown op");
+        if (std::isnan(limit)) return fail(ctx, ATSC_E_INVALID, "runs_windows: limit is NaN");
+        return ATSC_OK;
+    }
+    static void fill_empty(void *out, uint64_t n)
+    {
+        for (uint64_t i = 0; i < n; ++i) run_empty_record(((atsc_window_runs *)out)[i]);
+    }
+    // (the condition is checked in front of the arguments)
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *count, void *d_res, void *stream, uint64_t org) const
+    {
+        const int rc = check(ctx);
+        return rc ? rc : reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
     }
 };
 
@@ -773,7 +844,7 @@ struct RunQuery {
 // carry slot in the call's tables.  The tile kernel never writes that slot.
 template <class Q>
 static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
-                      const uint64_t *count, void *d_out, void *stream, uint64_t org, const Q &q = Q())
+                      const uint64_t *count, void *d_out, void *stream, uint64_t org, const Q &q)
 {
     if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_out)))
         return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
@@ -901,7 +972,7 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
         wb.resize(W);
         for (uint64_t i = 0; i < W; ++i) wb[i] = org + begin[i];
     }
-    QueryRes &R = Q::res(dp);
+    QueryRes &R = dp->res[Q::KIND];
     HIPCHK(ctx, R.wait());
     // one upload: the decode tasks, tile tasks, combine tasks (and the begins); behind them (device only) the partials
     // (and the windows' first / last samples, or the carry slot)
@@ -933,72 +1004,61 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
 }
+
+// The host call of a query: the argument check, the query's own, then window_host_call into its device call.
+template <class Q>
+static int query_host(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                      const uint64_t *begin, const uint64_t *count, void *out, const Q &q)
+{
+    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
+    const int rc = q.check(ctx);
+    if (rc) return rc;
+    if (n_windows == 0) return ATSC_OK;
+    return window_host_call(
+        ctx, Q::CALL, body, body_len, has_count, n_windows, begin, count, out, q.out_bytes(n_windows), false,
+        [&](bool any) {
+            if (!any) q.fill_empty(out, n_windows);
+            return ATSC_OK;
+        },
+        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
+            return q.dev(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org);
+        });
+}
+
 extern "C" int atsc_aggregate_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
                                           const uint64_t *begin, const uint64_t *count, atsc_window_stats *d_stats,
                                           void *stream)
 {
     ATSC_API_BEGIN
-    return reduce_dev<AggQuery>(ctx, dp, d_body, n_windows, begin, count, d_stats, stream, 0);
+    return AggQuery().dev(ctx, dp, d_body, n_windows, begin, count, d_stats, stream, 0);
     ATSC_API_END
 }
 
-// Host call: window_host_call into reduce_dev.
 extern "C" int atsc_aggregate_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
                                       const uint64_t *begin, const uint64_t *count, atsc_window_stats *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "aggregate_windows: null argument");
-    if (n_windows == 0) return ATSC_OK;
-    return window_host_call(
-        ctx, "aggregate_windows", body, body_len, has_count, n_windows, begin, count, out,
-        n_windows * sizeof(atsc_window_stats), false,
-        [&](bool any) {
-            for (uint64_t i = 0; !any && i < n_windows; ++i) agg_empty_record(out[i]);
-            return ATSC_OK;
-        },
-        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
-            return reduce_dev<AggQuery>(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org);
-        });
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, AggQuery());
     ATSC_API_END
 }
 
 // ------------------------------------------------------------------------------------------
 // windowed moments: centred moments of value and position of sample windows (atsc_moments.hip)
 // ------------------------------------------------------------------------------------------
-static void mom_empty_record(atsc_window_moments &r)
-{
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    r.count = 0;
-    r.mean = r.m2 = r.t_mean = r.t_m2 = r.c_tx = nan;
-}
-
-// The device call: reduce_dev with the moments' kernels.
 extern "C" int atsc_moments_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
                                         const uint64_t *begin, const uint64_t *count, atsc_window_moments *d_out,
                                         void *stream)
 {
     ATSC_API_BEGIN
-    return reduce_dev<MomQuery>(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    return MomQuery().dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
     ATSC_API_END
 }
 
-// Host call: window_host_call into reduce_dev.
 extern "C" int atsc_moments_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
                                     const uint64_t *begin, const uint64_t *count, atsc_window_moments *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "moments_windows: null argument");
-    if (n_windows == 0) return ATSC_OK;
-    return window_host_call(
-        ctx, "moments_windows", body, body_len, has_count, n_windows, begin, count, out,
-        n_windows * sizeof(atsc_window_moments), false,
-        [&](bool any) {
-            for (uint64_t i = 0; !any && i < n_windows; ++i) mom_empty_record(out[i]);
-            return ATSC_OK;
-        },
-        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
-            return reduce_dev<MomQuery>(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org);
-        });
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, MomQuery());
     ATSC_API_END
 }
 
@@ -1029,38 +1089,19 @@ extern "C" int atsc_moments_fit(const atsc_window_moments *m, uint64_t n, atsc_w
 // ------------------------------------------------------------------------------------------
 // windowed deltas: counted pairs, rises, falls, their sums and largest steps of sample windows (atsc_delta.hip)
 // ------------------------------------------------------------------------------------------
-static void dlt_empty_record(atsc_window_delta &r)
-{
-    r.pairs = r.rises = r.falls = 0;
-    r.up = r.down = r.after_falls = r.max_rise = r.max_fall = 0.0;
-}
-
-// The device call: reduce_dev with the deltas' kernels and the carry.
 extern "C" int atsc_delta_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
                                       const uint64_t *begin, const uint64_t *count, atsc_window_delta *d_out, void *stream)
 {
     ATSC_API_BEGIN
-    return reduce_dev<DltQuery>(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    return DltQuery().dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
     ATSC_API_END
 }
 
-// Host call: window_host_call into reduce_dev.
 extern "C" int atsc_delta_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
                                   const uint64_t *begin, const uint64_t *count, atsc_window_delta *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "delta_windows: null argument");
-    if (n_windows == 0) return ATSC_OK;
-    return window_host_call(
-        ctx, "delta_windows", body, body_len, has_count, n_windows, begin, count, out,
-        n_windows * sizeof(atsc_window_delta), false,
-        [&](bool any) {
-            for (uint64_t i = 0; !any && i < n_windows; ++i) dlt_empty_record(out[i]);
-            return ATSC_OK;
-        },
-        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
-            return reduce_dev<DltQuery>(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org);
-        });
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, DltQuery());
     ATSC_API_END
 }
 
@@ -1083,58 +1124,20 @@ extern "C" int atsc_delta_derive(const atsc_window_delta *d, uint64_t n, atsc_wi
 // ------------------------------------------------------------------------------------------
 // windowed runs: the samples that meet a condition and the runs of adjacent ones among them (atsc_runs.hip)
 // ------------------------------------------------------------------------------------------
-static void run_empty_record(atsc_window_runs &r)
-{
-    r.samples = r.inside = r.runs = r.longest = r.head = r.tail = 0;
-    r.longest_at = r.first_at = r.last_at = ATSC_RUNS_NONE;
-    r.excess = 0.0;
-}
-
-// ctx may be null: then no message is kept
-static int runs_check_condition(atsc_ctx *ctx, int op, double limit)
-{
-    if (op < ATSC_RUNS_GT || op > ATSC_RUNS_NE) return fail(ctx, ATSC_E_INVALID, "runs_windows: unknown op");
-    if (std::isnan(limit)) return fail(ctx, ATSC_E_INVALID, "runs_windows: limit is NaN");
-    return ATSC_OK;
-}
-
-// The device call: reduce_dev with the runs' kernels and the call's condition.
 extern "C" int atsc_runs_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
                                      const uint64_t *begin, const uint64_t *count, int op, double limit,
                                      atsc_window_runs *d_out, void *stream)
 {
     ATSC_API_BEGIN
-    const int rc = runs_check_condition(ctx, op, limit);
-    if (rc) return rc;
-    RunQuery q;
-    q.op = op;
-    q.limit = limit;
-    return reduce_dev<RunQuery>(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0, q);
+    return RunQuery{op, limit}.dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
     ATSC_API_END
 }
 
-// Host call: window_host_call into reduce_dev.
 extern "C" int atsc_runs_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
                                  const uint64_t *begin, const uint64_t *count, int op, double limit, atsc_window_runs *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "runs_windows: null argument");
-    const int rc = runs_check_condition(ctx, op, limit);
-    if (rc) return rc;
-    if (n_windows == 0) return ATSC_OK;
-    RunQuery q;
-    q.op = op;
-    q.limit = limit;
-    return window_host_call(
-        ctx, "runs_windows", body, body_len, has_count, n_windows, begin, count, out,
-        n_windows * sizeof(atsc_window_runs), false,
-        [&](bool any) {
-            for (uint64_t i = 0; !any && i < n_windows; ++i) run_empty_record(out[i]);
-            return ATSC_OK;
-        },
-        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
-            return reduce_dev<RunQuery>(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org, q);
-        });
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, RunQuery{op, limit});
     ATSC_API_END
 }
 
@@ -1311,7 +1314,7 @@ static int quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bo
     for (uint64_t i = 0; i < W; ++i)
         if (!count[i]) shorts.push_back(DevQTask{0, 0, (uint32_t)i, 0});
     const uint32_t empty_n = (uint32_t)(shorts.size() - empty_at);
-    QueryRes &R = dp->qnt;
+    QueryRes &R = dp->res[Q_QUANTILE];
     HIPCHK(ctx, R.wait());
     // one upload: the decode tasks, the levels, the tiers' task lists, the chunks; behind them (device only) the long
     // tier's state and counts
@@ -1357,35 +1360,41 @@ static int quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bo
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
 }
+
+// the quantiles' descriptor (see AggQuery): the levels and the method are the call's parameters
+struct QntQuery {
+    static constexpr const char *CALL = "quantile_windows";
+    uint32_t n_q;
+    const double *q;
+    int method;
+    size_t out_bytes(uint64_t n) const { return n * n_q * sizeof(double); }
+    int check(atsc_ctx *ctx) const { return quantile_check_levels(ctx, n_q, q, method); }
+    void fill_empty(void *out, uint64_t n) const
+    {
+        for (uint64_t i = 0; i < n * n_q; ++i) ((double *)out)[i] = std::numeric_limits<double>::quiet_NaN();
+    }
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *count, void *d_res, void *stream, uint64_t org) const
+    {
+        return quantile_dev(ctx, dp, d_body, n_windows, begin, count, n_q, q, method, (double *)d_res, stream, org);
+    }
+};
+
 extern "C" int atsc_quantile_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
                                          const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q,
                                          int method, double *d_out, void *stream)
 {
     ATSC_API_BEGIN
-    return quantile_dev(ctx, dp, d_body, n_windows, begin, count, n_q, q, method, d_out, stream, 0);
+    return QntQuery{n_q, q, method}.dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
     ATSC_API_END
 }
 
-// Host call: window_host_call into quantile_dev.
 extern "C" int atsc_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
                                      const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
                                      double *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
-    const int rc = quantile_check_levels(ctx, n_q, q, method);
-    if (rc) return rc;
-    if (n_windows == 0) return ATSC_OK;
-    return window_host_call(
-        ctx, "quantile_windows", body, body_len, has_count, n_windows, begin, count, out,
-        n_windows * n_q * sizeof(double), false,
-        [&](bool any) {
-            for (uint64_t i = 0; !any && i < n_windows * n_q; ++i) out[i] = std::numeric_limits<double>::quiet_NaN();
-            return ATSC_OK;
-        },
-        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
-            return quantile_dev(ctx, dp, d_body, n_windows, begin2, count, n_q, q, method, (double *)d_res, ws, org);
-        });
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, QntQuery{n_q, q, method});
     ATSC_API_END
 }
 
@@ -1518,7 +1527,7 @@ static int histogram_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
     for (size_t p = 0; p < P; ++p)
         if (!emit_piece_decode(dp, org, cov, ci, pcs[p].first, pcs[p].second, region, D, pdec[p]))
             return fail(ctx, ATSC_E_INVALID, "histogram_windows: internal error (spill slots)");
-    QueryRes &R = dp->hst;
+    QueryRes &R = dp->res[Q_HISTOGRAM];
     HIPCHK(ctx, R.wait());
     // one upload: the decode tasks, the edges, the two tiers' task lists
     Upload up;
@@ -1544,35 +1553,41 @@ static int histogram_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
 }
+
+// the histograms' descriptor (see AggQuery): the edges and the closed side are the call's parameters
+struct HstQuery {
+    static constexpr const char *CALL = "histogram_windows";
+    uint32_t n_edges;
+    const double *edges;
+    int closed;
+    size_t out_bytes(uint64_t n) const { return n * ((size_t)n_edges + 2) * sizeof(uint64_t); }
+    int check(atsc_ctx *ctx) const { return histogram_check_edges(ctx, n_edges, edges, closed); }
+    void fill_empty(void *out, uint64_t n) const
+    {
+        if (n) memset(out, 0, out_bytes(n));
+    }
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *count, void *d_res, void *stream, uint64_t org) const
+    {
+        return histogram_dev(ctx, dp, d_body, n_windows, begin, count, n_edges, edges, closed, (uint64_t *)d_res, stream, org);
+    }
+};
+
 extern "C" int atsc_histogram_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
                                           const uint64_t *begin, const uint64_t *count, uint32_t n_edges,
                                           const double *edges, int closed, uint64_t *d_out, void *stream)
 {
     ATSC_API_BEGIN
-    return histogram_dev(ctx, dp, d_body, n_windows, begin, count, n_edges, edges, closed, d_out, stream, 0);
+    return HstQuery{n_edges, edges, closed}.dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
     ATSC_API_END
 }
 
-// Host call: window_host_call into histogram_dev.
 extern "C" int atsc_histogram_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
                                       const uint64_t *begin, const uint64_t *count, uint32_t n_edges, const double *edges,
                                       int closed, uint64_t *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail(ctx, ATSC_E_INVALID, "histogram_windows: null argument");
-    const int rc = histogram_check_edges(ctx, n_edges, edges, closed);
-    if (rc) return rc;
-    if (n_windows == 0) return ATSC_OK;
-    const size_t out_bytes = n_windows * ((size_t)n_edges + 2) * sizeof(uint64_t);
-    return window_host_call(
-        ctx, "histogram_windows", body, body_len, has_count, n_windows, begin, count, out, out_bytes, false,
-        [&](bool any) {
-            if (!any) memset(out, 0, out_bytes);
-            return ATSC_OK;
-        },
-        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
-            return histogram_dev(ctx, dp, d_body, n_windows, begin2, count, n_edges, edges, closed, (uint64_t *)d_res, ws, org);
-        });
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, HstQuery{n_edges, edges, closed});
     ATSC_API_END
 }
 
@@ -1616,21 +1631,31 @@ extern "C" int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uin
     ATSC_API_END
 }
 
+// The stream call of a query.  The query's own check comes without a context (it has never left a message on the
+// stream's) and before the pending chunks are compressed; a stream without a frame gets the query's empty result.
+template <class Q>
+static int query_stream(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *out, const Q &q)
+{
+    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
+    int rc = q.check(nullptr);
+    if (rc) return rc;
+    std::vector<uint8_t> body;
+    atsc_ctx *ctx = nullptr;
+    rc = stream_body(s, body, &ctx);
+    if (rc) return rc;
+    if (body.empty()) {
+        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
+        q.fill_empty(out, n_windows);
+        return ATSC_OK;
+    }
+    return query_host(ctx, body.data(), body.size(), 0, n_windows, begin, count, out, q);
+}
+
 extern "C" int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                              atsc_window_stats *out)
 {
     ATSC_API_BEGIN
-    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
-    std::vector<uint8_t> body;
-    atsc_ctx *ctx = nullptr;
-    const int rc = stream_body(s, body, &ctx);
-    if (rc) return rc;
-    if (body.empty()) {
-        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
-        for (uint64_t i = 0; i < n_windows; ++i) agg_empty_record(out[i]);
-        return ATSC_OK;
-    }
-    return atsc_aggregate_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
+    return query_stream(s, n_windows, begin, count, out, AggQuery());
     ATSC_API_END
 }
 
@@ -1638,17 +1663,7 @@ extern "C" int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, c
                                            atsc_window_moments *out)
 {
     ATSC_API_BEGIN
-    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
-    std::vector<uint8_t> body;
-    atsc_ctx *ctx = nullptr;
-    const int rc = stream_body(s, body, &ctx);
-    if (rc) return rc;
-    if (body.empty()) {
-        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
-        for (uint64_t i = 0; i < n_windows; ++i) mom_empty_record(out[i]);
-        return ATSC_OK;
-    }
-    return atsc_moments_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
+    return query_stream(s, n_windows, begin, count, out, MomQuery());
     ATSC_API_END
 }
 
@@ -1656,17 +1671,7 @@ extern "C" int atsc_stream_delta_windows(atsc_stream *s, uint64_t n_windows, con
                                          atsc_window_delta *out)
 {
     ATSC_API_BEGIN
-    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
-    std::vector<uint8_t> body;
-    atsc_ctx *ctx = nullptr;
-    const int rc = stream_body(s, body, &ctx);
-    if (rc) return rc;
-    if (body.empty()) {
-        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
-        for (uint64_t i = 0; i < n_windows; ++i) dlt_empty_record(out[i]);
-        return ATSC_OK;
-    }
-    return atsc_delta_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, out);
+    return query_stream(s, n_windows, begin, count, out, DltQuery());
     ATSC_API_END
 }
 
@@ -1674,20 +1679,7 @@ extern "C" int atsc_stream_runs_windows(atsc_stream *s, uint64_t n_windows, cons
                                         int op, double limit, atsc_window_runs *out)
 {
     ATSC_API_BEGIN
-    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
-    // (no context yet: the check comes before the pending chunks are compressed)
-    int rc = runs_check_condition(nullptr, op, limit);
-    if (rc) return rc;
-    std::vector<uint8_t> body;
-    atsc_ctx *ctx = nullptr;
-    rc = stream_body(s, body, &ctx);
-    if (rc) return rc;
-    if (body.empty()) {
-        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
-        for (uint64_t i = 0; i < n_windows; ++i) run_empty_record(out[i]);
-        return ATSC_OK;
-    }
-    return atsc_runs_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, op, limit, out);
+    return query_stream(s, n_windows, begin, count, out, RunQuery{op, limit});
     ATSC_API_END
 }
 
@@ -1695,20 +1687,7 @@ extern "C" int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, 
                                             uint32_t n_q, const double *q, int method, double *out)
 {
     ATSC_API_BEGIN
-    if (!s || !q || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
-    // (no context: this check has never left a message on the stream's)
-    int rc = quantile_check_levels(nullptr, n_q, q, method);
-    if (rc) return rc;
-    std::vector<uint8_t> body;
-    atsc_ctx *ctx = nullptr;
-    rc = stream_body(s, body, &ctx);
-    if (rc) return rc;
-    if (body.empty()) {
-        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
-        for (uint64_t i = 0; i < n_windows * n_q; ++i) out[i] = std::numeric_limits<double>::quiet_NaN();
-        return ATSC_OK;
-    }
-    return atsc_quantile_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, n_q, q, method, out);
+    return query_stream(s, n_windows, begin, count, out, QntQuery{n_q, q, method});
     ATSC_API_END
 }
 
@@ -1716,19 +1695,6 @@ extern "C" int atsc_stream_histogram_windows(atsc_stream *s, uint64_t n_windows,
                                              uint32_t n_edges, const double *edges, int closed, uint64_t *out)
 {
     ATSC_API_BEGIN
-    if (!s || !edges || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
-    // (no context yet: the check comes before the pending chunks are compressed)
-    int rc = histogram_check_edges(nullptr, n_edges, edges, closed);
-    if (rc) return rc;
-    std::vector<uint8_t> body;
-    atsc_ctx *ctx = nullptr;
-    rc = stream_body(s, body, &ctx);
-    if (rc) return rc;
-    if (body.empty()) {
-        if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
-        if (n_windows) memset(out, 0, n_windows * ((size_t)n_edges + 2) * sizeof(uint64_t));
-        return ATSC_OK;
-    }
-    return atsc_histogram_windows(ctx, body.data(), body.size(), 0, n_windows, begin, count, n_edges, edges, closed, out);
+    return query_stream(s, n_windows, begin, count, out, HstQuery{n_edges, edges, closed});
     ATSC_API_END
 }

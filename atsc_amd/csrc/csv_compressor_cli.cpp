@@ -9,9 +9,6 @@
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
 
-#include <cctype>
-#include <charconv>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +16,7 @@
 #include <vector>
 
 #include "../../include/atsc_hip.h"
+#include "atsc_cli_buckets.h"
 
 namespace {
 
@@ -32,21 +30,7 @@ struct Args {
     bool window = false;  // --from / --to (with -u): only the samples whose indexed times lie in [t0, t1]
     int32_t t0 = 0, t1 = 0;
     int32_t step = 0;  // --step S (with --from / --to): summaries of S-second buckets into <out>.agg.csv
-    std::vector<double> levels;  // --quantiles (with --step): one more .agg.csv column per level
-    std::vector<std::string> level_names;
-    int method = ATSC_QUANTILE_LINEAR;  // --quantile-method
-    bool have_method = false;
-    std::vector<double> edges;  // --histogram (with --step): the .agg.csv columns h0 .. h<n_edges>,hnan
-    bool have_hist = false;
-    int closed = ATSC_HIST_LEFT_CLOSED;  // --histogram-closed
-    bool have_closed = false;
-    bool moments = false;  // --moments (with --step): the .agg.csv columns mean,stdvar,stddev,slope,intercept
-    // --deltas (with --step): the .agg.csv columns pairs,rises,falls,up,down,increase,variation,max_rise,max_fall
-    bool deltas = false;
-    // --runs OP:LIMIT (with --step): the .agg.csv columns inside,runs,longest,longest_at,first_at,last_at,head,tail,excess
-    bool have_runs = false;
-    int runs_op = ATSC_RUNS_GT;
-    double runs_limit = 0.0;
+    BucketOptions q;   // with --step: the queries beside the summaries (atsc_cli_buckets.h)
 };
 
 constexpr int PANIC = 101;  // exit status of a Rust panic: every failure below is an expect()/panic!()
@@ -96,24 +80,6 @@ bool parse_compressor(const std::string &v, int &out)  // main.rs:85-94: no rle 
         if (v == t.n) { out = t.id; return true; }
     return false;
 }
-bool parse_int(const std::string &v, int lo, int hi, int &out)
-{
-    if (v.empty()) return false;
-    char *end = nullptr;
-    long x = strtol(v.c_str(), &end, 10);
-    if (*end || x < lo || x > hi) return false;
-    out = (int)x;
-    return true;
-}
-
-std::string with_ext(const std::string &path, const char *ext)  // PathBuf::set_extension
-{
-    const size_t slash = path.find_last_of('/');
-    const size_t dot = path.find_last_of('.');
-    std::string base = (dot != std::string::npos && (slash == std::string::npos || dot > slash + 1)) ? path.substr(0, dot) : path;
-    return base + "." + ext;
-}
-
 int die(const char *what, int rc = 0, const char *detail = "")
 {
     fprintf(stderr, "thread 'main' panicked: %s%s%s%s\n", what, rc ? ": " : "", rc ? atsc_strerror(rc) : "", detail);
@@ -156,92 +122,6 @@ int uncompress_window(const Args &a, const std::string &output_base, uint8_t *br
 
 // -u --from T0 --to T1 --step S: the time buckets [T0 + k S, min(T0 + (k + 1) S - 1, T1)] as sample windows of the index,
 // one atsc_window_stats row each (timestamp = the bucket's start) into <out>.agg.csv; nothing else is written
-std::string debug_f64(double v)  // Rust `{:?}` of an f64: shortest round-trip digits, ".0" appended to integers
-{
-    if (std::isnan(v)) return "NaN";
-    if (std::isinf(v)) return v < 0 ? "-inf" : "inf";
-    char buf[64];
-    auto r = std::to_chars(buf, buf + sizeof(buf), v);
-    std::string s(buf, r.ptr);
-    if (s.find('e') == std::string::npos && s.find('.') == std::string::npos) s += ".0";
-    return s;
-}
-// --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
-bool parse_levels(const std::string &v, std::vector<double> &q, std::vector<std::string> &names)
-{
-    q.clear();
-    names.clear();
-    for (size_t p = 0;;) {
-        const size_t c = v.find(',', p);
-        const std::string t = v.substr(p, c == std::string::npos ? std::string::npos : c - p);
-        char *e = nullptr;
-        const double x = strtod(t.c_str(), &e);
-        if (t.empty() || isspace((unsigned char)t[0]) || *e || !(x >= 0.0 && x <= 1.0)) return false;
-        q.push_back(x);
-        names.push_back(t);
-        if (c == std::string::npos) return true;
-        p = c + 1;
-    }
-}
-bool parse_method(const std::string &v, int &m)
-{
-    static const char *names[] = {"linear", "lower", "higher", "nearest"};  // ATSC_QUANTILE_* order
-    for (int k = 0; k < 4; ++k)
-        if (v == names[k]) { m = k; return true; }
-    return false;
-}
-// --histogram SPEC: explicit edges E,E,.. or LO:HI:N, N equal bins over [LO, HI] (atsc_histogram_edges_uniform).
-// 0: fine; 1: unparsable, NaN or not ascending, or a bad uniform spec; 2: more than ATSC_HIST_MAX_EDGES edges
-int parse_histogram(const std::string &v, std::vector<double> &edges)
-{
-    edges.clear();
-    auto number = [](const std::string &t, double &x) {
-        char *e = nullptr;
-        x = strtod(t.c_str(), &e);
-        return !t.empty() && !isspace((unsigned char)t[0]) && !*e && x == x;
-    };
-    const size_t c1 = v.find(':');
-    if (c1 != std::string::npos) {
-        const size_t c2 = v.find(':', c1 + 1);
-        if (c2 == std::string::npos) return 1;
-        double lo, hi;
-        const std::string ns = v.substr(c2 + 1);
-        char *e = nullptr;
-        const unsigned long long n = strtoull(ns.c_str(), &e, 10);
-        if (!number(v.substr(0, c1), lo) || !number(v.substr(c1 + 1, c2 - c1 - 1), hi) || ns.empty() || *e ||
-            !isdigit((unsigned char)ns[0]))
-            return 1;
-        if (n >= ATSC_HIST_MAX_EDGES) return 2;
-        edges.resize(n + 1);
-        return atsc_histogram_edges_uniform(lo, hi, (uint32_t)n, edges.data()) ? 1 : 0;
-    }
-    for (size_t p = 0;;) {
-        const size_t c = v.find(',', p);
-        double x;
-        if (!number(v.substr(p, c == std::string::npos ? std::string::npos : c - p), x)) return 1;
-        if (!edges.empty() && !(edges.back() < x)) return 1;
-        edges.push_back(x);
-        if (c == std::string::npos) return edges.size() > (size_t)ATSC_HIST_MAX_EDGES ? 2 : 0;
-        p = c + 1;
-    }
-}
-// --runs OP:LIMIT: OP one of gt ge lt le eq ne, LIMIT a number that is not NaN, nothing behind it
-bool parse_runs(const std::string &v, int &op, double &limit)
-{
-    static const char *const OPS[] = {"gt", "ge", "lt", "le", "eq", "ne"};
-    const size_t c = v.find(':');
-    if (c == std::string::npos) return false;
-    const std::string o = v.substr(0, c), t = v.substr(c + 1);
-    int k = 0;
-    while (k < 6 && o != OPS[k]) ++k;
-    char *e = nullptr;
-    const double x = strtod(t.c_str(), &e);
-    if (k == 6 || t.empty() || isspace((unsigned char)t[0]) || *e || x != x) return false;
-    op = k;  // ATSC_RUNS_GT .. ATSC_RUNS_NE in this order
-    limit = x;
-    return true;
-}
-
 int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *bro, uint64_t len)
 {
     atsc_vsri *index = nullptr;
@@ -253,39 +133,18 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
     if (rc == ATSC_E_CAPACITY || rc == ATSC_OK) rc = atsc_vsri_step_windows(index, a.t0, a.t1, a.step, b.data(), c.data(), nb, &nb);
     atsc_vsri_free(index);
     if (rc) { atsc_free(bro); return die("vsri buckets", rc); }
-    std::vector<atsc_window_stats> st(nb ? nb : 1);
     atsc_ctx *ctx = nullptr;
     rc = atsc_ctx_create(&ctx, 0);
     if (rc) { atsc_free(bro); return die("no GPU context", rc); }
+    BucketResults r;
+    const char *failed = "aggregate";
     rc = atsc_bro_open(bro, len, nullptr, nullptr);
-    if (!rc) rc = atsc_aggregate_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), st.data());
-    if (rc) { int e = die("aggregate", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
-    const uint64_t nq = a.levels.size();
-    std::vector<double> qv(nb * nq ? nb * nq : 1);
-    if (nq) rc = atsc_quantile_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), (uint32_t)nq, a.levels.data(), a.method,
-                                       qv.data());
-    if (rc) { int e = die("quantiles", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
-    const uint64_t nh = a.have_hist ? a.edges.size() + 2 : 0;  // counters per bucket
-    std::vector<uint64_t> hv(nb * nh ? nb * nh : 1);
-    if (nh) rc = atsc_histogram_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), (uint32_t)a.edges.size(),
-                                        a.edges.data(), a.closed, hv.data());
-    if (rc) { int e = die("histogram", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
-    std::vector<atsc_window_moments> mv(a.moments && nb ? nb : 1);
-    std::vector<atsc_window_fit> fv(mv.size());
-    if (a.moments) rc = atsc_moments_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), mv.data());
-    if (!rc && a.moments) rc = atsc_moments_fit(mv.data(), nb, fv.data());
-    if (rc) { int e = die("moments", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
-    std::vector<atsc_window_delta> dv(a.deltas && nb ? nb : 1);
-    std::vector<atsc_window_delta_fit> df(dv.size());
-    if (a.deltas) rc = atsc_delta_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), dv.data());
-    if (!rc && a.deltas) rc = atsc_delta_derive(dv.data(), nb, df.data());
-    if (rc) { int e = die("deltas", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
-    std::vector<atsc_window_runs> rv(a.have_runs && nb ? nb : 1);
-    if (a.have_runs) rc = atsc_runs_windows(ctx, bro + 9, len - 9, 1, nb, b.data(), c.data(), a.runs_op, a.runs_limit, rv.data());
-    if (rc) { int e = die("runs", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    if (!rc) rc = bucket_queries(ctx, bro, len, a.q, nb, b.data(), c.data(), r, &failed);
+    if (rc) { int e = die(failed, rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    const std::vector<atsc_window_runs> &rv = r.rv;
     // "when did it start": the three positions as the indexed times of their samples, get_time(begin + offset)
-    std::vector<std::string> rt(a.have_runs ? 3 * nb : 0);
-    if (a.have_runs && nb) {
+    std::vector<std::string> rt(3 * nb);
+    if (a.q.have_runs && nb) {
         index = nullptr;
         rc = atsc_vsri_load(with_ext(a.input, "vsri").c_str(), &index);
         for (uint64_t k = 0; !rc && k < nb; ++k) {
@@ -305,34 +164,8 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
     atsc_free(bro);
     FILE *f = fopen(with_ext(output_base, "agg.csv").c_str(), "w");
     if (!f) return die("failed to write aggregates to file");
-    fprintf(f, "timestamp,count,min,max,sum,first,last");
-    for (const std::string &n : a.level_names) fprintf(f, ",q%s", n.c_str());
-    for (uint64_t j = 0; j + 1 < nh; ++j) fprintf(f, ",h%llu", (unsigned long long)j);
-    if (nh) fprintf(f, ",hnan");
-    if (a.moments) fprintf(f, ",mean,stdvar,stddev,slope,intercept");
-    if (a.deltas) fprintf(f, ",pairs,rises,falls,up,down,increase,variation,max_rise,max_fall");
-    if (a.have_runs) fprintf(f, ",inside,runs,longest,longest_at,first_at,last_at,head,tail,excess");
-    fprintf(f, "\n");
-    for (uint64_t k = 0; k < nb; ++k) {
-        fprintf(f, "%lld,%llu,%s,%s,%s,%s,%s", (long long)a.t0 + (long long)k * a.step, (unsigned long long)st[k].count,
-                debug_f64(st[k].min).c_str(), debug_f64(st[k].max).c_str(), debug_f64(st[k].sum).c_str(),
-                debug_f64(st[k].first).c_str(), debug_f64(st[k].last).c_str());
-        for (uint64_t j = 0; j < nq; ++j) fprintf(f, ",%s", debug_f64(qv[k * nq + j]).c_str());
-        for (uint64_t j = 0; j < nh; ++j) fprintf(f, ",%llu", (unsigned long long)hv[k * nh + j]);
-        if (a.moments)
-            fprintf(f, ",%s,%s,%s,%s,%s", debug_f64(fv[k].mean).c_str(), debug_f64(fv[k].variance).c_str(),
-                    debug_f64(fv[k].stddev).c_str(), debug_f64(fv[k].slope).c_str(), debug_f64(fv[k].intercept).c_str());
-        if (a.deltas)
-            fprintf(f, ",%llu,%llu,%llu,%s,%s,%s,%s,%s,%s", (unsigned long long)dv[k].pairs, (unsigned long long)dv[k].rises,
-                    (unsigned long long)dv[k].falls, debug_f64(dv[k].up).c_str(), debug_f64(dv[k].down).c_str(),
-                    debug_f64(df[k].increase).c_str(), debug_f64(df[k].variation).c_str(),
-                    debug_f64(dv[k].max_rise).c_str(), debug_f64(dv[k].max_fall).c_str());
-        if (a.have_runs)
-            fprintf(f, ",%llu,%llu,%llu,%s,%s,%s,%llu,%llu,%s", (unsigned long long)rv[k].inside, (unsigned long long)rv[k].runs,
-                    (unsigned long long)rv[k].longest, rt[3 * k].c_str(), rt[3 * k + 1].c_str(), rt[3 * k + 2].c_str(),
-                    (unsigned long long)rv[k].head, (unsigned long long)rv[k].tail, debug_f64(rv[k].excess).c_str());
-        fprintf(f, "\n");
-    }
+    bucket_header(f, "timestamp", a.q, r);
+    for (uint64_t k = 0; k < nb; ++k) bucket_row(f, std::to_string((long long)a.t0 + (long long)k * a.step), a.q, r, k, &rt[3 * k]);
     if (fclose(f) != 0) return die("failed to write aggregates to file");
     return 0;
 }
@@ -457,55 +290,7 @@ int main(int argc, char **argv)
             }
             a.step = (int32_t)t;
         }
-        else if (value("--quantiles")) {
-            if (!parse_levels(v, a.levels, a.level_names)) {
-                fprintf(stderr, "error: invalid value '%s' for '--quantiles': expected levels in 0..=1, comma separated\n",
-                        v.c_str());
-                return 2;
-            }
-            if (a.levels.size() > 64) {
-                fprintf(stderr, "error: invalid value for '--quantiles': %zu levels, at most 64\n", a.levels.size());
-                return 2;
-            }
-        }
-        else if (value("--quantile-method")) {
-            if (!parse_method(v, a.method)) {
-                fprintf(stderr, "error: invalid value '%s' for '--quantile-method': linear, lower, higher or nearest\n",
-                        v.c_str());
-                return 2;
-            }
-            a.have_method = true;
-        }
-        else if (value("--histogram")) {
-            const int bad = parse_histogram(v, a.edges);
-            if (bad == 1) {
-                fprintf(stderr, "error: invalid value '%s' for '--histogram': expected ascending edges E,E,.. or LO:HI:N\n",
-                        v.c_str());
-                return 2;
-            }
-            if (bad == 2) {
-                fprintf(stderr, "error: invalid value for '--histogram': more than %d edges\n", (int)ATSC_HIST_MAX_EDGES);
-                return 2;
-            }
-            a.have_hist = true;
-        }
-        else if (value("--histogram-closed")) {
-            if (v != "left" && v != "right") {
-                fprintf(stderr, "error: invalid value '%s' for '--histogram-closed': left or right\n", v.c_str());
-                return 2;
-            }
-            a.closed = v == "right" ? ATSC_HIST_RIGHT_CLOSED : ATSC_HIST_LEFT_CLOSED;
-            a.have_closed = true;
-        }
-        else if (s == "--moments") a.moments = true;
-        else if (s == "--deltas") a.deltas = true;
-        else if (value("--runs")) {
-            if (!parse_runs(v, a.runs_op, a.runs_limit)) {
-                fprintf(stderr, "error: invalid value '%s': '--runs' wants OP:LIMIT (OP: gt ge lt le eq ne)\n", v.c_str());
-                return 2;
-            }
-            a.have_runs = true;
-        }
+        else if (const int k = bucket_option(s, v, value, a.q)) { if (k == 2) return 2; }
         else if (value("--compressor")) { if (!parse_compressor(v, a.compressor)) { fprintf(stderr, "error: invalid value '%s' for '--compressor'\n", v.c_str()); return 2; } }
         else if (value("--error") || value("-e")) { if (!parse_int(v, 0, 50, a.error)) { fprintf(stderr, "error: invalid value '%s' for '--error': not in 0..=50\n", v.c_str()); return 2; } }
         else if (value("--compression-selection-sample-level") || value("-c")) { if (!parse_int(v, 0, 6, a.level)) { fprintf(stderr, "error: invalid value '%s' for '-c': not in 0..=6\n", v.c_str()); return 2; } }
@@ -521,34 +306,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "error: '--step' needs '--from' and '--to'\n");
         return 2;
     }
-    if (!a.levels.empty() && !a.step) {
-        fprintf(stderr, "error: '--quantiles' needs '--step'\n");
-        return 2;
-    }
-    if (a.have_method && a.levels.empty()) {
-        fprintf(stderr, "error: '--quantile-method' needs '--quantiles'\n");
-        return 2;
-    }
-    if (a.have_hist && !a.step) {
-        fprintf(stderr, "error: '--histogram' needs '--step'\n");
-        return 2;
-    }
-    if (a.have_closed && !a.have_hist) {
-        fprintf(stderr, "error: '--histogram-closed' needs '--histogram'\n");
-        return 2;
-    }
-    if (a.moments && !a.step) {
-        fprintf(stderr, "error: '--moments' needs '--step'\n");
-        return 2;
-    }
-    if (a.deltas && !a.step) {
-        fprintf(stderr, "error: '--deltas' needs '--step'\n");
-        return 2;
-    }
-    if (a.have_runs && !a.step) {
-        fprintf(stderr, "error: '--runs' needs '--step'\n");
-        return 2;
-    }
+    if (!bucket_options_complete(a.q, "--step", a.step != 0)) return 2;
     a.window = have_from;
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) return die("Failed to retrieve metadata of the input");  // main.rs:226-229

@@ -1,5 +1,6 @@
 """Thin Python plumbing over the C ABI: device memory and streams come from PyTorch-ROCm,
 everything else happens inside libatsc_hip.so.  No compression logic lives here."""
+import collections
 import ctypes as C
 import weakref
 
@@ -50,6 +51,73 @@ def _windows(begins, counts):
 def _levels(levels):
     q = np.ascontiguousarray(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
     return q, q.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# One window query, as its four surfaces (Context.*_windows_host, DPlan.*_windows, CompressedStream.*_windows and
+# *_data_windows) need it:
+#   stem    the C calls are atsc_<stem>, atsc_<stem>_dev and atsc_stream_<stem>
+#   dtype   of the result: one record per window (extra is None), or per window a row of `extra` cells more than the
+#           call's levels or edges; the device tensor holds at least that many bytes per window
+#   params  the call's own arguments -> their C arguments, which stand between the windows and the result
+_Query = collections.namedtuple("_Query", "stem dtype extra params")
+
+
+def _no_params():
+    return ()
+
+
+def _runs_params(op, limit):
+    return int(op), float(limit)
+
+
+def _array_params(values, flag):
+    """levels and method, or edges and closed"""
+    a, pa = _levels(values)
+    return len(a), pa, int(flag)
+
+
+_AGGREGATE = _Query("aggregate_windows", WINDOW_STATS, None, _no_params)
+_MOMENTS = _Query("moments_windows", WINDOW_MOMENTS, None, _no_params)
+_DELTA = _Query("delta_windows", WINDOW_DELTA, None, _no_params)
+_RUNS = _Query("runs_windows", WINDOW_RUNS, None, _runs_params)
+_QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
+_HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
+
+
+def _query_width(q, cargs):
+    """elements of q.dtype per window"""
+    return 1 if q.extra is None else cargs[0] + q.extra
+
+
+def _query_result(q, n, cargs, fn):
+    """-> (the zeroed host result of n windows, at least one, and its pointer as fn's last argument)"""
+    rows = max(n, 1)
+    out = np.zeros(rows if q.extra is None else (rows, _query_width(q, cargs)), dtype=q.dtype)
+    return out, out.ctypes.data_as(fn.argtypes[-1])
+
+
+def _query_host(q, ctx, records, begins, counts, has_count, *params):
+    """Context.*_windows_host: atsc_<stem> over the records"""
+    b = np.frombuffer(bytes(records), dtype=np.uint8)
+    wb, pb, wc, pc = _windows(begins, counts)
+    cargs = q.params(*params)
+    fn = getattr(capi.lib(), "atsc_" + q.stem)
+    out, po = _query_result(q, len(wb), cargs, fn)
+    rc = fn(ctx._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count), len(wb), pb, pc, *cargs, po)
+    capi.check(rc, ctx._h)
+    return out[: len(wb)]
+
+
+def _query_dev(q, dplan, d_body, begins, counts, d_out, stream, *params):
+    """DPlan.*_windows: atsc_<stem>_dev into the device tensor d_out"""
+    b, pb, c, pc = _windows(begins, counts)
+    cargs = q.params(*params)
+    assert q.extra is None or d_out.element_size() == 8
+    assert d_out.is_contiguous()
+    assert d_out.numel() * d_out.element_size() >= q.dtype.itemsize * _query_width(q, cargs) * len(b)
+    rc = getattr(capi.lib(), "atsc_%s_dev" % q.stem)(dplan.ctx._h, dplan._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
+                                                     *cargs, C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
+    capi.check(rc, dplan.ctx._h)
 
 
 def histogram_edges_uniform(lo, hi, n_bins):
@@ -203,74 +271,34 @@ class Context:
     def aggregate_windows_host(self, records, begins, counts, has_count=False):
         """-> WINDOW_STATS array: count / min / max / sum / first / last of every window [begins[i], begins[i] +
         counts[i]) of the decoded records (atsc_aggregate_windows)"""
-        b = np.frombuffer(bytes(records), dtype=np.uint8)
-        wb, pb, wc, pc = _windows(begins, counts)
-        out = np.zeros(max(len(wb), 1), dtype=WINDOW_STATS)
-        rc = capi.lib().atsc_aggregate_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
-                                               len(wb), pb, pc, C.c_void_p(out.ctypes.data))
-        capi.check(rc, self._h)
-        return out[: len(wb)]
+        return _query_host(_AGGREGATE, self, records, begins, counts, has_count)
 
     def moments_windows_host(self, records, begins, counts, has_count=False):
         """-> WINDOW_MOMENTS array: count, mean and the centred moments of value and position of every window
         [begins[i], begins[i] + counts[i]) of the decoded records (atsc_moments_windows)"""
-        b = np.frombuffer(bytes(records), dtype=np.uint8)
-        wb, pb, wc, pc = _windows(begins, counts)
-        out = np.zeros(max(len(wb), 1), dtype=WINDOW_MOMENTS)
-        rc = capi.lib().atsc_moments_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
-                                             len(wb), pb, pc, C.c_void_p(out.ctypes.data))
-        capi.check(rc, self._h)
-        return out[: len(wb)]
+        return _query_host(_MOMENTS, self, records, begins, counts, has_count)
 
     def delta_windows_host(self, records, begins, counts, has_count=False):
         """-> WINDOW_DELTA array: the counted pairs of adjacent samples, the rises and falls among them, their sums and
         largest steps of every window [begins[i], begins[i] + counts[i]) of the decoded records (atsc_delta_windows)"""
-        b = np.frombuffer(bytes(records), dtype=np.uint8)
-        wb, pb, wc, pc = _windows(begins, counts)
-        out = np.zeros(max(len(wb), 1), dtype=WINDOW_DELTA)
-        rc = capi.lib().atsc_delta_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
-                                           len(wb), pb, pc, C.c_void_p(out.ctypes.data))
-        capi.check(rc, self._h)
-        return out[: len(wb)]
+        return _query_host(_DELTA, self, records, begins, counts, has_count)
 
     def runs_windows_host(self, records, begins, counts, op, limit, has_count=False):
         """-> WINDOW_RUNS array: the samples with x OP limit (op: RUNS_GT .. RUNS_NE), their maximal runs, the longest
         run, the first and last such sample, the runs at the two ends and the sum of |x - limit| of every window
         [begins[i], begins[i] + counts[i]) of the decoded records (atsc_runs_windows)"""
-        b = np.frombuffer(bytes(records), dtype=np.uint8)
-        wb, pb, wc, pc = _windows(begins, counts)
-        out = np.zeros(max(len(wb), 1), dtype=WINDOW_RUNS)
-        rc = capi.lib().atsc_runs_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
-                                          len(wb), pb, pc, int(op), float(limit), C.c_void_p(out.ctypes.data))
-        capi.check(rc, self._h)
-        return out[: len(wb)]
+        return _query_host(_RUNS, self, records, begins, counts, has_count, op, limit)
 
     def quantile_windows_host(self, records, begins, counts, levels, method=capi.QUANTILE_LINEAR, has_count=False):
         """-> (n_windows, n_levels) float64 array: the levels of every window [begins[i], begins[i] + counts[i]) of the
         decoded records (atsc_quantile_windows)"""
-        b = np.frombuffer(bytes(records), dtype=np.uint8)
-        wb, pb, wc, pc = _windows(begins, counts)
-        q, pq = _levels(levels)
-        out = np.zeros((max(len(wb), 1), len(q)), dtype=np.float64)
-        rc = capi.lib().atsc_quantile_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
-                                              len(wb), pb, pc, len(q), pq, int(method),
-                                              out.ctypes.data_as(C.POINTER(C.c_double)))
-        capi.check(rc, self._h)
-        return out[: len(wb)]
+        return _query_host(_QUANTILE, self, records, begins, counts, has_count, levels, method)
 
     def histogram_windows_host(self, records, begins, counts, edges, closed=capi.HIST_LEFT_CLOSED, has_count=False):
         """-> (n_windows, n_edges + 2) uint64 array: per window [begins[i], begins[i] + counts[i]) of the decoded
         records, the samples in each of the n_edges + 1 bins the ascending edges cut, then the NaN samples
         (atsc_histogram_windows)"""
-        b = np.frombuffer(bytes(records), dtype=np.uint8)
-        wb, pb, wc, pc = _windows(begins, counts)
-        e, pe = _levels(edges)
-        out = np.zeros((max(len(wb), 1), len(e) + 2), dtype=np.uint64)
-        rc = capi.lib().atsc_histogram_windows(self._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count),
-                                               len(wb), pb, pc, len(e), pe, int(closed),
-                                               out.ctypes.data_as(C.POINTER(C.c_uint64)))
-        capi.check(rc, self._h)
-        return out[: len(wb)]
+        return _query_host(_HISTOGRAM, self, records, begins, counts, has_count, edges, closed)
 
     def set_aggregate_scratch(self, nbytes):
         """Upper bound on the decoded-sample scratch of the aggregate calls (0: the default; raised to one piece)"""
@@ -393,60 +421,32 @@ class DPlan:
     def aggregate_windows(self, d_body, begins, counts, d_stats, stream=0):
         """Enqueues the summaries of the windows [begins[i], begins[i] + counts[i]) into d_stats, a device tensor of at
         least 48 bytes per window (atsc_aggregate_windows_dev; WINDOW_STATS records)"""
-        b, pb, c, pc = _windows(begins, counts)
-        assert d_stats.is_contiguous() and d_stats.numel() * d_stats.element_size() >= 48 * len(b)
-        rc = capi.lib().atsc_aggregate_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
-                                                   C.c_void_p(d_stats.data_ptr()), C.c_void_p(stream))
-        capi.check(rc, self.ctx._h)
+        _query_dev(_AGGREGATE, self, d_body, begins, counts, d_stats, stream)
 
     def moments_windows(self, d_body, begins, counts, d_out, stream=0):
         """Enqueues the moments of the windows [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least
         48 bytes per window (atsc_moments_windows_dev; WINDOW_MOMENTS records)"""
-        b, pb, c, pc = _windows(begins, counts)
-        assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= 48 * len(b)
-        rc = capi.lib().atsc_moments_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
-                                                 C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
-        capi.check(rc, self.ctx._h)
+        _query_dev(_MOMENTS, self, d_body, begins, counts, d_out, stream)
 
     def delta_windows(self, d_body, begins, counts, d_out, stream=0):
         """Enqueues the deltas of the windows [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least
         64 bytes per window (atsc_delta_windows_dev; WINDOW_DELTA records)"""
-        b, pb, c, pc = _windows(begins, counts)
-        assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= 64 * len(b)
-        rc = capi.lib().atsc_delta_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
-                                               C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
-        capi.check(rc, self.ctx._h)
+        _query_dev(_DELTA, self, d_body, begins, counts, d_out, stream)
 
     def runs_windows(self, d_body, begins, counts, op, limit, d_out, stream=0):
         """Enqueues the runs of the samples with x OP limit of the windows [begins[i], begins[i] + counts[i]) into d_out,
         a device tensor of at least 80 bytes per window (atsc_runs_windows_dev; WINDOW_RUNS records)"""
-        b, pb, c, pc = _windows(begins, counts)
-        assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= 80 * len(b)
-        rc = capi.lib().atsc_runs_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
-                                              int(op), float(limit), C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
-        capi.check(rc, self.ctx._h)
+        _query_dev(_RUNS, self, d_body, begins, counts, d_out, stream, op, limit)
 
     def quantile_windows(self, d_body, begins, counts, levels, d_out, method=capi.QUANTILE_LINEAR, stream=0):
         """Enqueues the levels of the windows [begins[i], begins[i] + counts[i]) into d_out, a float64 device tensor of
         at least n_windows * n_levels elements, window-major (atsc_quantile_windows_dev)"""
-        b, pb, c, pc = _windows(begins, counts)
-        q, pq = _levels(levels)
-        assert d_out.is_contiguous() and d_out.element_size() == 8 and d_out.numel() >= len(b) * len(q)
-        rc = capi.lib().atsc_quantile_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
-                                                  len(q), pq, int(method), C.c_void_p(d_out.data_ptr()),
-                                                  C.c_void_p(stream))
-        capi.check(rc, self.ctx._h)
+        _query_dev(_QUANTILE, self, d_body, begins, counts, d_out, stream, levels, method)
 
     def histogram_windows(self, d_body, begins, counts, edges, d_out, closed=capi.HIST_LEFT_CLOSED, stream=0):
         """Enqueues the bin counts of the windows [begins[i], begins[i] + counts[i]) into d_out, a 64-bit integer
         device tensor of at least n_windows * (n_edges + 2) elements, window-major (atsc_histogram_windows_dev)"""
-        b, pb, c, pc = _windows(begins, counts)
-        e, pe = _levels(edges)
-        assert d_out.is_contiguous() and d_out.element_size() == 8 and d_out.numel() >= len(b) * (len(e) + 2)
-        rc = capi.lib().atsc_histogram_windows_dev(self.ctx._h, self._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
-                                                   len(e), pe, int(closed), C.c_void_p(d_out.data_ptr()),
-                                                   C.c_void_p(stream))
-        capi.check(rc, self.ctx._h)
+        _query_dev(_HISTOGRAM, self, d_body, begins, counts, d_out, stream, edges, closed)
 
 
 # ---- host-only helpers (no GPU) ------------------------------------------------------------

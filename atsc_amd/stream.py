@@ -7,6 +7,7 @@ import numpy as np
 
 from . import capi
 from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit  # noqa: F401
+from .engine import _AGGREGATE, _DELTA, _HISTOGRAM, _MOMENTS, _QUANTILE, _RUNS, _query_result
 
 
 def _f64(x):
@@ -24,6 +25,30 @@ def _take_f64(p, n):
     out = np.ctypeslib.as_array(p, shape=(max(n.value, 1),))[: n.value].copy()
     capi.lib().atsc_free(p)
     return out
+
+
+def _query_stream(q, stream, begins, counts, *params):
+    """CompressedStream.*_windows: atsc_stream_<stem> (q: the query's description, engine._Query)"""
+    wb, pb, wc, pc = _windows(begins, counts)
+    cargs = q.params(*params)
+    fn = getattr(capi.lib(), "atsc_stream_" + q.stem)
+    out, po = _query_result(q, len(wb), cargs, fn)
+    capi.check(fn(stream._h, len(wb), pb, pc, *cargs, po), stream.ctx._h)
+    return out[: len(wb)]
+
+
+def _query_image(q, ctx, bro, begins, counts, *params):
+    """*_data_windows: atsc_bro_open, then atsc_<stem> over the records of the .bro image"""
+    b = np.frombuffer(bytes(bro), dtype=np.uint8)
+    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
+    wb, pb, wc, pc = _windows(begins, counts)
+    cargs = q.params(*params)
+    fn = getattr(capi.lib(), "atsc_" + q.stem)
+    out, po = _query_result(q, len(wb), cargs, fn)
+    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
+    rc = fn(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc, *cargs, po)
+    capi.check(rc, ctx._h)
+    return out[: len(wb)]
 
 
 class CompressedStream:
@@ -93,54 +118,28 @@ class CompressedStream:
 
     def aggregate_windows(self, begins, counts):
         """-> WINDOW_STATS array of the windows [begins[i], begins[i] + counts[i]) (atsc_stream_aggregate_windows)"""
-        wb, pb, wc, pc = _windows(begins, counts)
-        out = np.zeros(max(len(wb), 1), dtype=WINDOW_STATS)
-        capi.check(capi.lib().atsc_stream_aggregate_windows(self._h, len(wb), pb, pc, C.c_void_p(out.ctypes.data)),
-                   self.ctx._h)
-        return out[: len(wb)]
+        return _query_stream(_AGGREGATE, self, begins, counts)
 
     def moments_windows(self, begins, counts):
         """-> WINDOW_MOMENTS array of the windows [begins[i], begins[i] + counts[i]) (atsc_stream_moments_windows)"""
-        wb, pb, wc, pc = _windows(begins, counts)
-        out = np.zeros(max(len(wb), 1), dtype=WINDOW_MOMENTS)
-        capi.check(capi.lib().atsc_stream_moments_windows(self._h, len(wb), pb, pc, C.c_void_p(out.ctypes.data)),
-                   self.ctx._h)
-        return out[: len(wb)]
+        return _query_stream(_MOMENTS, self, begins, counts)
 
     def delta_windows(self, begins, counts):
         """-> WINDOW_DELTA array of the windows [begins[i], begins[i] + counts[i]) (atsc_stream_delta_windows)"""
-        wb, pb, wc, pc = _windows(begins, counts)
-        out = np.zeros(max(len(wb), 1), dtype=WINDOW_DELTA)
-        capi.check(capi.lib().atsc_stream_delta_windows(self._h, len(wb), pb, pc, C.c_void_p(out.ctypes.data)),
-                   self.ctx._h)
-        return out[: len(wb)]
+        return _query_stream(_DELTA, self, begins, counts)
 
     def runs_windows(self, begins, counts, op, limit):
         """-> WINDOW_RUNS array of the windows [begins[i], begins[i] + counts[i]) under the condition x OP limit
         (atsc_stream_runs_windows)"""
-        wb, pb, wc, pc = _windows(begins, counts)
-        out = np.zeros(max(len(wb), 1), dtype=WINDOW_RUNS)
-        capi.check(capi.lib().atsc_stream_runs_windows(self._h, len(wb), pb, pc, int(op), float(limit),
-                                                       C.c_void_p(out.ctypes.data)), self.ctx._h)
-        return out[: len(wb)]
+        return _query_stream(_RUNS, self, begins, counts, op, limit)
 
     def quantile_windows(self, begins, counts, levels, method=capi.QUANTILE_LINEAR):
         """-> (n_windows, n_levels) float64 array of the windows' levels (atsc_stream_quantile_windows)"""
-        wb, pb, wc, pc = _windows(begins, counts)
-        q, pq = _levels(levels)
-        out = np.zeros((max(len(wb), 1), len(q)), dtype=np.float64)
-        capi.check(capi.lib().atsc_stream_quantile_windows(self._h, len(wb), pb, pc, len(q), pq, int(method),
-                                                           out.ctypes.data_as(C.POINTER(C.c_double))), self.ctx._h)
-        return out[: len(wb)]
+        return _query_stream(_QUANTILE, self, begins, counts, levels, method)
 
     def histogram_windows(self, begins, counts, edges, closed=capi.HIST_LEFT_CLOSED):
         """-> (n_windows, n_edges + 2) uint64 array of the windows' bin counts (atsc_stream_histogram_windows)"""
-        wb, pb, wc, pc = _windows(begins, counts)
-        e, pe = _levels(edges)
-        out = np.zeros((max(len(wb), 1), len(e) + 2), dtype=np.uint64)
-        capi.check(capi.lib().atsc_stream_histogram_windows(self._h, len(wb), pb, pc, len(e), pe, int(closed),
-                                                            out.ctypes.data_as(C.POINTER(C.c_uint64))), self.ctx._h)
-        return out[: len(wb)]
+        return _query_stream(_HISTOGRAM, self, begins, counts, edges, closed)
 
 
 def compress_data(ctx, vec, compressor=capi.AUTO, error=3, sample_level=0):
@@ -181,87 +180,37 @@ def decompress_data_window(ctx, bro, begin, count):
 def aggregate_data_windows(ctx, bro, begins, counts):
     """-> WINDOW_STATS array of windows of decompress_data(ctx, bro): atsc_bro_open, then atsc_aggregate_windows over
     the records"""
-    b = np.frombuffer(bytes(bro), dtype=np.uint8)
-    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
-    wb, pb, wc, pc = _windows(begins, counts)
-    out = np.zeros(max(len(wb), 1), dtype=WINDOW_STATS)
-    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
-    rc = capi.lib().atsc_aggregate_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
-                                           C.c_void_p(out.ctypes.data))
-    capi.check(rc, ctx._h)
-    return out[: len(wb)]
+    return _query_image(_AGGREGATE, ctx, bro, begins, counts)
 
 
 def moments_data_windows(ctx, bro, begins, counts):
     """-> WINDOW_MOMENTS array of windows of decompress_data(ctx, bro): atsc_bro_open, then atsc_moments_windows over
     the records"""
-    b = np.frombuffer(bytes(bro), dtype=np.uint8)
-    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
-    wb, pb, wc, pc = _windows(begins, counts)
-    out = np.zeros(max(len(wb), 1), dtype=WINDOW_MOMENTS)
-    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
-    rc = capi.lib().atsc_moments_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
-                                         C.c_void_p(out.ctypes.data))
-    capi.check(rc, ctx._h)
-    return out[: len(wb)]
+    return _query_image(_MOMENTS, ctx, bro, begins, counts)
 
 
 def delta_data_windows(ctx, bro, begins, counts):
     """-> WINDOW_DELTA array of windows of decompress_data(ctx, bro): atsc_bro_open, then atsc_delta_windows over the
     records"""
-    b = np.frombuffer(bytes(bro), dtype=np.uint8)
-    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
-    wb, pb, wc, pc = _windows(begins, counts)
-    out = np.zeros(max(len(wb), 1), dtype=WINDOW_DELTA)
-    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
-    rc = capi.lib().atsc_delta_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
-                                       C.c_void_p(out.ctypes.data))
-    capi.check(rc, ctx._h)
-    return out[: len(wb)]
+    return _query_image(_DELTA, ctx, bro, begins, counts)
 
 
 def runs_data_windows(ctx, bro, begins, counts, op, limit):
     """-> WINDOW_RUNS array of windows of decompress_data(ctx, bro) under the condition x OP limit: atsc_bro_open, then
     atsc_runs_windows over the records"""
-    b = np.frombuffer(bytes(bro), dtype=np.uint8)
-    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
-    wb, pb, wc, pc = _windows(begins, counts)
-    out = np.zeros(max(len(wb), 1), dtype=WINDOW_RUNS)
-    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
-    rc = capi.lib().atsc_runs_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
-                                      int(op), float(limit), C.c_void_p(out.ctypes.data))
-    capi.check(rc, ctx._h)
-    return out[: len(wb)]
+    return _query_image(_RUNS, ctx, bro, begins, counts, op, limit)
 
 
 def quantile_data_windows(ctx, bro, begins, counts, levels, method=capi.QUANTILE_LINEAR):
     """-> (n_windows, n_levels) float64 array: levels of windows of decompress_data(ctx, bro): atsc_bro_open, then
     atsc_quantile_windows over the records"""
-    b = np.frombuffer(bytes(bro), dtype=np.uint8)
-    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
-    wb, pb, wc, pc = _windows(begins, counts)
-    q, pq = _levels(levels)
-    out = np.zeros((max(len(wb), 1), len(q)), dtype=np.float64)
-    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
-    rc = capi.lib().atsc_quantile_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
-                                          len(q), pq, int(method), out.ctypes.data_as(C.POINTER(C.c_double)))
-    capi.check(rc, ctx._h)
-    return out[: len(wb)]
+    return _query_image(_QUANTILE, ctx, bro, begins, counts, levels, method)
 
 
 def histogram_data_windows(ctx, bro, begins, counts, edges, closed=capi.HIST_LEFT_CLOSED):
     """-> (n_windows, n_edges + 2) uint64 array: bin counts of windows of decompress_data(ctx, bro): atsc_bro_open, then
     atsc_histogram_windows over the records"""
-    b = np.frombuffer(bytes(bro), dtype=np.uint8)
-    capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
-    wb, pb, wc, pc = _windows(begins, counts)
-    e, pe = _levels(edges)
-    out = np.zeros((max(len(wb), 1), len(e) + 2), dtype=np.uint64)
-    r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
-    rc = capi.lib().atsc_histogram_windows(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc,
-                                           len(e), pe, int(closed), out.ctypes.data_as(C.POINTER(C.c_uint64)))
-    capi.check(rc, ctx._h)
-    return out[: len(wb)]
+    return _query_image(_HISTOGRAM, ctx, bro, begins, counts, edges, closed)
 
 
 def wbro_from_bytes(data):

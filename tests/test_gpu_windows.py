@@ -304,3 +304,90 @@ def test_command_lines(A, ctx, golden_dir, tmp_path):
             assert [r for r in got if r] == want, (t0, t1)
         sel = np.array([t0 <= t <= t1 for t in times])
         assert _eq(A.wbro_read(tmp_path / "win.wbro"), all_vals[sel]), (t0, t1)
+
+
+# what each query's calls say of a null argument, of a window beyond the stream and of a misaligned result (device call)
+MESSAGES = {
+    "aggregate": ("aggregate_windows: null argument", "aggregate_windows: window beyond the stream",
+                  "aggregate_windows: d_stats is not 8-byte aligned"),
+    "moments": ("moments_windows: null argument", "moments_windows: window beyond the stream",
+                "moments_windows: d_out is not 8-byte aligned"),
+    "delta": ("delta_windows: null argument", "delta_windows: window beyond the stream",
+              "delta_windows: d_out is not 8-byte aligned"),
+    "runs": ("runs_windows: null argument", "runs_windows: window beyond the stream",
+             "runs_windows: d_out is not 8-byte aligned"),
+    "quantile": ("quantile_windows: null argument", "quantile_windows: window beyond the stream",
+                 "quantile_windows: d_out is not 8-byte aligned"),
+    "histogram": ("histogram_windows: null argument", "histogram_windows: window beyond the stream",
+                  "histogram_windows: d_out is not 8-byte aligned"),
+}
+
+
+def test_messages_by_query(A, ctx, torch):
+    """Every query's host and device call over one stream of 8 frames x 256 samples: a null argument, a window that
+    ends one sample beyond the stream, a result pointer off by 4 bytes (device call) and the query's bad parameters.
+    Each fails with E_INVALID and leaves exactly its message in atsc_ctx_last_error; nothing is enqueued and the
+    result buffers keep their fill."""
+    import ctypes as C
+
+    n, nf = 256, 8
+    x = H.synth_series(1912, n * nf, klass=2)
+    off = np.arange(nf + 1, dtype=np.uint64) * n
+    recs, _, _, _ = ctx.compress_host(x, off, A.FFT, True, float(np.float32(0.05)), 0)
+    lib = A.capi.lib()
+    gb = np.frombuffer(recs, dtype=np.uint8)
+    dp = A.DPlan(ctx, recs)
+    assert dp.n_samples == n * nf
+    body = torch.from_numpy(gb.copy()).to("cuda")
+    d_out = torch.full((64,), -1, dtype=torch.int64, device="cuda")
+    h_out = np.full(512, 0xA5, dtype=np.uint8)
+    u64p, f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+
+    def f64(*v):
+        a = np.array(v, dtype=np.float64)
+        return a, a.ctypes.data_as(f64p)
+
+    levels, p_levels = f64(0.5, 0.9)
+    high, p_high = f64(0.5, 1.5)
+    edges, p_edges = f64(0.0, 1.0, 2.0)
+    desc, p_desc = f64(2.0, 1.0, 0.0)
+    good = {"aggregate": (), "moments": (), "delta": (), "runs": (A.RUNS_GT, 0.0),
+            "quantile": (2, p_levels, A.QUANTILE_LINEAR), "histogram": (3, p_edges, A.HIST_LEFT_CLOSED)}
+    bad = {"runs": [((6, 0.0), "runs_windows: unknown op"), ((A.RUNS_GT, float("nan")), "runs_windows: limit is NaN")],
+           "quantile": [((0, p_levels, A.QUANTILE_LINEAR), "quantile_windows: n_q outside [1, 64]"),
+                        ((2, p_high, A.QUANTILE_LINEAR), "quantile_windows: a level is NaN or outside [0, 1]"),
+                        ((2, p_levels, 9), "quantile_windows: unknown method")],
+           "histogram": [((3, p_desc, A.HIST_LEFT_CLOSED), "histogram_windows: edges are not strictly ascending"),
+                         ((3, p_edges, 7), "histogram_windows: unknown closed")]}
+    inside = (np.array([0], dtype=np.uint64), np.array([10], dtype=np.uint64))
+    beyond = (np.array([n * nf - 9], dtype=np.uint64), np.array([10], dtype=np.uint64))  # ends at n_samples + 1
+
+    def host(q, wins, params, out):
+        fn = getattr(lib, "atsc_%s_windows" % q)
+        po = None if out is None else out.ctypes.data_as(fn.argtypes[-1])
+        return fn(ctx._h, gb.ctypes.data_as(C.POINTER(C.c_uint8)), len(gb), 0, 1, wins[0].ctypes.data_as(u64p),
+                  wins[1].ctypes.data_as(u64p), *params, po)
+
+    def dev(q, wins, params, ptr):
+        fn = getattr(lib, "atsc_%s_windows_dev" % q)
+        return fn(ctx._h, dp._h, C.c_void_p(body.data_ptr()), 1, wins[0].ctypes.data_as(u64p), wins[1].ctypes.data_as(u64p),
+                  *params, C.c_void_p(ptr), None)
+
+    def failed(rc, text):
+        assert rc == A.capi.E_INVALID, (rc, text)
+        assert lib.atsc_ctx_last_error(ctx._h).decode() == text
+
+    for q, (null, past, misaligned) in MESSAGES.items():
+        failed(host(q, inside, good[q], None), null)
+        failed(host(q, beyond, good[q], h_out), past)
+        failed(dev(q, inside, good[q], 0), null)
+        failed(dev(q, beyond, good[q], d_out.data_ptr()), past)
+        failed(dev(q, inside, good[q], d_out.data_ptr() + 4), misaligned)
+        for params, text in bad.get(q, []):
+            failed(host(q, inside, params, h_out), text)
+        for params, text in bad.get(q, []):
+            failed(dev(q, inside, params, d_out.data_ptr()), text)
+    torch.cuda.synchronize()
+    assert bool((d_out == -1).all())
+    assert np.all(h_out == 0xA5)
+    dp.close()
