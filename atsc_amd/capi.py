@@ -19,6 +19,9 @@ HIST_MAX_EDGES = 1024
 # atsc_runs_windows: the condition's operator, and the position of a record without one (include/atsc_hip.h)
 RUNS_GT, RUNS_GE, RUNS_LT, RUNS_LE, RUNS_EQ, RUNS_NE = 0, 1, 2, 3, 4, 5
 RUNS_NONE = 2 ** 64 - 1
+# atsc_extremes_windows: the most entries per list, and the position of an empty entry (include/atsc_hip.h)
+EXTREMES_MAX_K = 16
+EXTREMES_NONE = 2 ** 64 - 1
 COMPRESSOR_NAMES = {0: "noop", 1: "fft", 2: "idw", 3: "constant", 4: "polynomial", 5: "auto", 6: "rle"}
 
 OK = 0
@@ -109,6 +112,9 @@ SIGNATURES = {
     "atsc_runs_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double,
                                     _vp]),
     "atsc_runs_merge": (C.c_int, [_vp, C.c_uint64, _vp]),
+    "atsc_extremes_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp, _vp]),
+    "atsc_extremes_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp]),
+    "atsc_extremes_merge": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp]),
     "atsc_quantile_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _vp,
                                             _vp]),
     "atsc_quantile_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p,
@@ -132,6 +138,7 @@ SIGNATURES = {
     "atsc_stream_moments_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_delta_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_runs_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double, _vp]),
+    "atsc_stream_extremes_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp]),
     "atsc_stream_quantile_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _f64p]),
     "atsc_stream_histogram_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _u64p]),
     "atsc_free": (None, [_vp]),

@@ -3,7 +3,7 @@
 //
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
-//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]]]
+//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -58,6 +58,10 @@ void usage()
             "                                 ne, e.g. gt:0.9) and their runs of adjacent samples, as the last columns: inside,\n"
             "                                 runs, longest, longest_at, first_at, last_at (sample offsets in the bucket, empty\n"
             "                                 where there is none), head, tail, excess (the sum of |value - LIMIT| over them)\n"
+            "      --extremes <K>             with --buckets: also every bucket's K largest and K smallest samples (K: 1..16) and\n"
+            "                                 where they are, as the last columns: nans, max1, max1_at .. maxK, maxK_at, min1,\n"
+            "                                 min1_at .. minK, minK_at (equal values earliest first; *_at the sample's offset\n"
+            "                                 in the bucket; both cells empty where the bucket has fewer samples)\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"

@@ -1,7 +1,8 @@
 // atsc_cli_buckets.h -- what the two command lines (atsc_cli.cpp, csv_compressor_cli.cpp) share: the small text helpers
 // and the bucket queries behind `atsc -u --buckets N` and `csv-compressor -u --from --to --step S`: their options, the
 // usage errors, the calls over the buckets and the columns of the .agg.csv.  The two differ in the row's first cell,
-// in how a failure is reported and in the three run positions, which the caller hands in.
+// in how a failure is reported and in how a position inside a bucket is written: the three run positions, which the
+// caller hands in, and the extremes' positions, which csv-compressor rewrites as times (bucket_extreme_places).
 #pragma once
 #include <cctype>
 #include <charconv>
@@ -60,6 +61,7 @@ struct BucketOptions {
     bool have_runs = false;  // --runs OP:LIMIT: inside,runs,longest,longest_at,first_at,last_at,head,tail,excess
     int runs_op = ATSC_RUNS_GT;
     double runs_limit = 0.0;
+    int extremes = 0;  // --extremes K: nans,max1,max1_at,..,maxK,maxK_at,min1,min1_at,..,minK,minK_at
 };
 
 // --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
@@ -190,6 +192,11 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             return 2;
         }
         o.have_runs = true;
+    } else if (value("--extremes")) {
+        if (!parse_int(v, 1, ATSC_EXTREMES_MAX_K, o.extremes)) {
+            fprintf(stderr, "error: invalid value '%s' for '--extremes': expected 1..=%d\n", v.c_str(), (int)ATSC_EXTREMES_MAX_K);
+            return 2;
+        }
     } else {
         return 0;
     }
@@ -209,7 +216,8 @@ bool bucket_options_complete(const BucketOptions &o, const char *bucketing, bool
              {o.have_closed, o.have_hist, "--histogram-closed", "--histogram"},
              {o.moments, given, "--moments", bucketing},
              {o.deltas, given, "--deltas", bucketing},
-             {o.have_runs, given, "--runs", bucketing}};
+             {o.have_runs, given, "--runs", bucketing},
+             {o.extremes != 0, given, "--extremes", bucketing}};
     for (const auto &t : T)
         if (t.have && !t.needed) {
             fprintf(stderr, "error: '%s' needs '%s'\n", t.name, t.needs);
@@ -229,7 +237,32 @@ struct BucketResults {
     std::vector<atsc_window_delta> dv;
     std::vector<atsc_window_delta_fit> df;
     std::vector<atsc_window_runs> rv;
+    uint32_t ek = 0;                  // --extremes: entries per list
+    std::vector<unsigned char> ev;    // the buckets' records, ATSC_EXTREMES_BYTES(ek) each
+    std::vector<std::string> eat;     // 2 ek cells per bucket: the entries' places, as offsets in the bucket
+    const atsc_window_extremes_head &ext_head(uint64_t k) const
+    {
+        return *(const atsc_window_extremes_head *)(ev.data() + k * ATSC_EXTREMES_BYTES(ek));
+    }
+    // entry j of bucket k: j < ek the largest, then the smallest
+    const atsc_extreme &ext_entry(uint64_t k, uint32_t j) const { return ((const atsc_extreme *)(&ext_head(k) + 1))[j]; }
 };
+
+// With --extremes: writes the cell of every entry's place: place(k, at, cell) for the sample at offset `at` of bucket k
+// (non-zero: a failure, which ends it); an empty entry's cell stays empty, as a run position that is ATSC_RUNS_NONE.
+template <class Place>
+int bucket_extreme_places(BucketResults &r, uint64_t nb, Place place)
+{
+    r.eat.assign(2 * (size_t)r.ek * nb, std::string());
+    for (uint64_t k = 0; k < nb; ++k)
+        for (uint32_t j = 0; j < 2 * r.ek; ++j) {
+            const uint64_t at = r.ext_entry(k, j).at;
+            if (at == ATSC_EXTREMES_NONE) continue;
+            const int rc = place(k, at, r.eat[2 * (size_t)r.ek * k + j]);
+            if (rc) return rc;
+        }
+    return 0;
+}
 
 // Runs the aggregates and the selected queries over the nb buckets (b, c) of a .bro image, the records from the
 // frame-count varint on, as atsc_decompress_data reads them.  A failure ends it: its rc, and *failed names the query.
@@ -268,6 +301,13 @@ int bucket_queries(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const Bucket
     *failed = "runs";
     r.rv.resize(o.have_runs && nb ? nb : 1);
     if (o.have_runs) rc = atsc_runs_windows(ctx, body, body_len, 1, nb, b, c, o.runs_op, o.runs_limit, r.rv.data());
+    if (rc) return rc;
+    *failed = "extremes";
+    r.ek = (uint32_t)o.extremes;
+    r.ev.resize(r.ek && nb ? nb * ATSC_EXTREMES_BYTES(r.ek) : 8);
+    if (r.ek) rc = atsc_extremes_windows(ctx, body, body_len, 1, nb, b, c, r.ek, r.ev.data());
+    if (!rc && r.ek)
+        rc = bucket_extreme_places(r, nb, [](uint64_t, uint64_t at, std::string &cell) { cell = std::to_string(at); return 0; });
     return rc;
 }
 
@@ -281,6 +321,11 @@ void bucket_header(FILE *f, const char *first, const BucketOptions &o, const Buc
     if (o.moments) fprintf(f, ",mean,stdvar,stddev,slope,intercept");
     if (o.deltas) fprintf(f, ",pairs,rises,falls,up,down,increase,variation,max_rise,max_fall");
     if (o.have_runs) fprintf(f, ",inside,runs,longest,longest_at,first_at,last_at,head,tail,excess");
+    if (o.extremes) {
+        fprintf(f, ",nans");
+        for (int e = 0; e < 2; ++e)
+            for (int j = 1; j <= o.extremes; ++j) fprintf(f, ",%s%d,%s%d_at", e ? "min" : "max", j, e ? "min" : "max", j);
+    }
     fprintf(f, "\n");
 }
 
@@ -310,6 +355,14 @@ void bucket_row(FILE *f, const std::string &first, const BucketOptions &o, const
         fprintf(f, ",%llu,%llu,%llu,%s,%s,%s,%llu,%llu,%s", (unsigned long long)rv.inside, (unsigned long long)rv.runs,
                 (unsigned long long)rv.longest, run_at[0].c_str(), run_at[1].c_str(), run_at[2].c_str(),
                 (unsigned long long)rv.head, (unsigned long long)rv.tail, debug_f64(rv.excess).c_str());
+    }
+    if (o.extremes) {
+        fprintf(f, ",%llu", (unsigned long long)r.ext_head(k).nans);
+        for (uint32_t j = 0; j < 2 * r.ek; ++j) {
+            const atsc_extreme &x = r.ext_entry(k, j);
+            fprintf(f, ",%s,%s", x.at == ATSC_EXTREMES_NONE ? "" : debug_f64(x.value).c_str(),
+                    r.eat[2 * (size_t)r.ek * k + j].c_str());
+        }
     }
     fprintf(f, "\n");
 }

@@ -251,6 +251,16 @@ struct DevRunTile {
     uint32_t lo, hi;
 };
 
+// windowed extremes (atsc_extremes_windows_dev, atsc_extremes.hip): the aggregates' tiles, pieces and combine passes
+// (DevAggComb) over partials of 2 + 4 k eight-byte words, the record's layout with positions as stream indices: count,
+// nans, k largest entries, k smallest entries, an entry being (value bits, position) and (NaN, ~0) where there is none
+constexpr uint32_t EXT_MAX_K = 16;
+// one tile of k_ext_tiles: slots [lo, hi) of the tile whose slot 0 is scratch[src] and sample t0 of the stream -> partial dst
+struct DevExtTile {
+    uint64_t src, dst, t0;
+    uint32_t lo, hi;
+};
+
 // windowed quantiles (atsc_quantile_windows_dev, atsc_quantile.hip).  The tier of a window is chosen from its length:
 // short (one wavefront, keys in registers), medium (one workgroup, keys in LDS), long (MSD radix select, 8-bit digits)
 constexpr uint32_t QNT_MAX_LEVELS = 64;

@@ -1,4 +1,4 @@
-// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, quantiles and histograms
+// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, quantiles and histograms
 // of ranges of the decoded stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
@@ -58,6 +58,11 @@ __attribute__((weak)) hipError_t launch_dlt_combine(const DevAggComb *tasks, uin
 __attribute__((weak)) hipError_t launch_run_tiles(const DevRunTile *tasks, uint32_t n, const double *scratch, int op,
                                                   double limit, DevRunPart *part, hipStream_t s);
 __attribute__((weak)) hipError_t launch_run_combine(const DevAggComb *tasks, uint32_t n, DevRunPart *part,
+                                                    const uint64_t *begin, void *out, hipStream_t s);
+// the windowed extremes' selection kernels (atsc_extremes.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_ext_tiles(const DevExtTile *tasks, uint32_t n, const double *scratch, uint32_t k,
+                                                  void *part, hipStream_t s);
+__attribute__((weak)) hipError_t launch_ext_combine(const DevAggComb *tasks, uint32_t n, uint32_t k, void *part,
                                                     const uint64_t *begin, void *out, hipStream_t s);
 }  // namespace atsc
 
@@ -261,7 +266,8 @@ struct DecodeCaller {
     { "launch k_decompress (" word ")", "launch k_decompress_large (" word ")", "launch k_window_gather (" word ")" }
 static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE = DECODE_CALLER("quantile"),
                           BY_HISTOGRAM = DECODE_CALLER("histogram"), BY_MOMENTS = DECODE_CALLER("moments"),
-                          BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs");
+                          BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs"),
+                          BY_EXTREMES = DECODE_CALLER("extremes");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -651,9 +657,10 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
 //   fill_empty(out, n)  the result of n empty windows
 //   dev(...)            the device call; org: the stream index of the plan's first sample
 // What the reductions over tiles differ in: the aggregates (atsc_aggregate.hip), the moments (atsc_moments.hip), the
-// deltas (atsc_delta.hip) and the runs (atsc_runs.hip).
+// deltas (atsc_delta.hip), the runs (atsc_runs.hip) and the extremes (atsc_extremes.hip).
 //   Tile, tile(t, k)   the tile kernel's task, from the plan's DevAggTile of tile k of the stream
-//   PART               bytes of a partial
+//   part()             bytes of a partial: a member call, so that a query may size its partials by a parameter of the
+//                      call (ExtQuery, by k); the others hand back their static PART
 //   SIDE               the table both kernels share beside the partials: the windows' first / last samples, which the
 //                      tile kernel writes (device only), or the windows' begins in the stream's index (uploaded)
 //   CARRY, carried(t)  the tile kernel looks at the sample in front of a tile: the side table is one carry slot (device
@@ -663,6 +670,7 @@ struct AggQuery {
     static constexpr const char *CALL = "aggregate_windows", *RES_NAME = "d_stats", *NO_KERNELS = "no aggregate kernels",
                                 *TILES = "launch k_agg_tiles", *COMBINE = "launch k_agg_combine";
     static constexpr size_t PART = sizeof(DevAggPart);
+    static size_t part() { return PART; }
     static constexpr bool SIDE_BEGINS = false;
     static constexpr QueryKind KIND = Q_AGGREGATE;
     static const DecodeCaller &who() { return BY_AGGREGATE; }
@@ -701,6 +709,7 @@ struct MomQuery {
     static constexpr const char *CALL = "moments_windows", *RES_NAME = "d_out", *NO_KERNELS = "no moments kernels",
                                 *TILES = "launch k_mom_tiles", *COMBINE = "launch k_mom_combine";
     static constexpr size_t PART = sizeof(DevMomPart);
+    static size_t part() { return PART; }
     static constexpr bool SIDE_BEGINS = true;
     static constexpr QueryKind KIND = Q_MOMENTS;
     static const DecodeCaller &who() { return BY_MOMENTS; }
@@ -739,6 +748,7 @@ struct DltQuery {
     static constexpr const char *CALL = "delta_windows", *RES_NAME = "d_out", *NO_KERNELS = "no delta kernels",
                                 *TILES = "launch k_dlt_tiles", *COMBINE = "launch k_dlt_combine";
     static constexpr size_t PART = sizeof(DevDltPart);
+    static size_t part() { return PART; }
     static constexpr bool SIDE_BEGINS = false;
     static constexpr bool CARRY = true;
     static constexpr QueryKind KIND = Q_DELTA;
@@ -792,6 +802,7 @@ struct RunQuery {
     static constexpr const char *CALL = "runs_windows", *RES_NAME = "d_out", *NO_KERNELS = "no runs kernels",
                                 *TILES = "launch k_run_tiles", *COMBINE = "launch k_run_combine";
     static constexpr size_t PART = sizeof(DevRunPart);
+    static size_t part() { return PART; }
     static constexpr bool SIDE_BEGINS = true;
     static constexpr bool CARRY = false;
     static constexpr QueryKind KIND = Q_RUNS;
@@ -829,8 +840,62 @@ struct RunQuery {
     }
 };
 
-// The device call of a reduction over tiles (Q: AggQuery, MomQuery, DltQuery or RunQuery; the kernels named below are
-// the aggregates').  q: the query's parameters of this call, where it has any (RunQuery).
+static void ext_empty_record(void *rec, uint32_t k)
+{
+    atsc_window_extremes_head *h = (atsc_window_extremes_head *)rec;
+    h->count = h->nans = 0;
+    atsc_extreme *e = (atsc_extreme *)(h + 1);
+    for (uint32_t j = 0; j < 2 * k; ++j) {
+        e[j].value = std::numeric_limits<double>::quiet_NaN();
+        e[j].at = ATSC_EXTREMES_NONE;
+    }
+}
+
+// The extremes (atsc_extremes.hip).  k is the call's parameter and a member, as the runs' condition is; it also sizes the
+// partials, which have the record's layout (2 + 4 k words) with positions as stream indices, so that a shared mid
+// tile's partial serves every window that shares it; the final combine pass subtracts the window's begin.  No carry.
+struct ExtQuery {
+    using Tile = DevExtTile;
+    static constexpr const char *CALL = "extremes_windows", *RES_NAME = "d_out", *NO_KERNELS = "no extremes kernels",
+                                *TILES = "launch k_ext_tiles", *COMBINE = "launch k_ext_combine";
+    static constexpr bool SIDE_BEGINS = true;
+    static constexpr bool CARRY = false;
+    static constexpr QueryKind KIND = Q_EXTREMES;
+    uint32_t k;
+    size_t part() const { return ATSC_EXTREMES_BYTES(k); }
+    static const DecodeCaller &who() { return BY_EXTREMES; }
+    static bool have() { return launch_ext_tiles && launch_ext_combine; }
+    static Tile tile(const DevAggTile &t, uint64_t kt) { return Tile{t.src, t.dst, kt * AGG_TILE, t.lo, t.hi}; }
+    static bool carried(const Tile &) { return false; }
+    hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s) const
+    {
+        return launch_ext_tiles(t, n, scr, k, part, s);
+    }
+    hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *side, void *out, hipStream_t s) const
+    {
+        return launch_ext_combine(c, n, k, part, (const uint64_t *)side, out, s);
+    }
+    size_t out_bytes(uint64_t n) const { return n * ATSC_EXTREMES_BYTES(k); }
+    int check(atsc_ctx *ctx) const
+    {
+        if (k == 0 || k > ATSC_EXTREMES_MAX_K) return fail(ctx, ATSC_E_INVALID, "extremes_windows: k outside [1, 16]");
+        return ATSC_OK;
+    }
+    void fill_empty(void *out, uint64_t n) const
+    {
+        for (uint64_t i = 0; i < n; ++i) ext_empty_record((char *)out + i * ATSC_EXTREMES_BYTES(k), k);
+    }
+    // (k is checked in front of the arguments)
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *count, void *d_res, void *stream, uint64_t org) const
+    {
+        const int rc = check(ctx);
+        return rc ? rc : reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
+    }
+};
+
+// The device call of a reduction over tiles (Q: AggQuery, MomQuery, DltQuery, RunQuery or ExtQuery; the kernels named
+// below are the aggregates').  q: the query's parameters of this call, where it has any (RunQuery, ExtQuery).
 // Host work: covering intervals, pieces, the decode tasks of every piece (one per touched frame: its
 // covered samples' hull in the piece), the tile tasks (a full tile that windows cover past their first tile and before
 // their last one is reduced once, into a shared partial; every window's first and last tile are reduced for it alone)
@@ -980,7 +1045,7 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
     D.place(up);
     const size_t off_tiles = up.add(tiles), off_comb = up.add(comb);
     const size_t off_begins = Q::SIDE_BEGINS ? up.add(wb) : 0;
-    const size_t off_part = up.device_only(part_n * Q::PART);
+    const size_t off_part = up.device_only(part_n * q.part());
     const size_t off_side = Q::SIDE_BEGINS ? off_begins : up.device_only(Q::CARRY ? sizeof(double) : 2 * W * sizeof(double));
     HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, region + (uint64_t)MAX_FRAME * D.spills_used));
     unsigned char *d = R.d;
@@ -996,9 +1061,9 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
         if (Q::CARRY && p + 1 < pcs.size() && carry_in[p + 1])
             HIPCHK(ctx, hipMemcpyAsync(side, scr + (pcs[p].k1 - pcs[p].k0) * T - 1, sizeof(double), hipMemcpyDeviceToDevice, s));
     }
-    for (size_t q = 0; q + 1 < pass_at.size(); ++q) {
-        const hipError_t e = Q::combine((const DevAggComb *)(d + off_comb) + pass_at[q], (uint32_t)(pass_at[q + 1] - pass_at[q]),
-                                        part, side, d_out, s);
+    for (size_t a = 0; a + 1 < pass_at.size(); ++a) {
+        const hipError_t e = q.combine((const DevAggComb *)(d + off_comb) + pass_at[a], (uint32_t)(pass_at[a + 1] - pass_at[a]),
+                                       part, side, d_out, s);
         if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, Q::COMBINE, e);
     }
     HIPCHK(ctx, R.record(s));
@@ -1165,6 +1230,68 @@ extern "C" int atsc_runs_merge(const atsc_window_runs *r, uint64_t n, atsc_windo
         a.excess = a.excess + b.excess;
     }
     *out = a;
+    return ATSC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// windowed extremes: the k largest and the k smallest samples of sample windows and where they are (atsc_extremes.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" int atsc_extremes_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                         const uint64_t *begin, const uint64_t *count, uint32_t k, void *d_out,
+                                         void *stream)
+{
+    ATSC_API_BEGIN
+    return ExtQuery{k}.dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    ATSC_API_END
+}
+
+extern "C" int atsc_extremes_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                     const uint64_t *begin, const uint64_t *count, uint32_t k, void *out)
+{
+    ATSC_API_BEGIN
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, ExtQuery{k});
+    ATSC_API_END
+}
+
+// Host only: the records of adjacent windows, left to right, into the record of their union (include/atsc_hip.h's rule).
+// A list of the union is the first k of its parts' lists merged in the list's order; a part's entries are in that order
+// already, and of equal values the earlier part's come first, so taking from the merged list so far unless the next
+// part's head is strictly better keeps the earliest position in front.
+extern "C" int atsc_extremes_merge(const void *records, uint64_t n, uint32_t k, void *out)
+{
+    if (!out || (n && !records) || k == 0 || k > ATSC_EXTREMES_MAX_K) return ATSC_E_INVALID;
+    const size_t bytes = ATSC_EXTREMES_BYTES(k);
+    alignas(8) unsigned char acc[ATSC_EXTREMES_BYTES(ATSC_EXTREMES_MAX_K)], next[ATSC_EXTREMES_BYTES(ATSC_EXTREMES_MAX_K)];
+    ext_empty_record(acc, k);
+    atsc_window_extremes_head *a = (atsc_window_extremes_head *)acc;
+    for (uint64_t i = 0; i < n; ++i) {
+        alignas(8) unsigned char part[ATSC_EXTREMES_BYTES(ATSC_EXTREMES_MAX_K)];
+        memcpy(part, (const char *)records + i * bytes, bytes);
+        const atsc_window_extremes_head *b = (const atsc_window_extremes_head *)part;
+        if (b->count == 0) continue;
+        ext_empty_record(next, k);
+        for (int end = 0; end < 2; ++end) {
+            const atsc_extreme *la = (const atsc_extreme *)(a + 1) + end * k, *lb = (const atsc_extreme *)(b + 1) + end * k;
+            atsc_extreme *lo = (atsc_extreme *)((atsc_window_extremes_head *)next + 1) + end * k;
+            uint32_t ia = 0, ib = 0;
+            for (uint32_t j = 0; j < k; ++j) {
+                const bool ha = ia < k && la[ia].at != ATSC_EXTREMES_NONE, hb = ib < k && lb[ib].at != ATSC_EXTREMES_NONE;
+                if (!ha && !hb) break;
+                const bool take_b = hb && (!ha || (end ? lb[ib].value < la[ia].value : lb[ib].value > la[ia].value));
+                if (take_b) {
+                    lo[j].value = lb[ib].value;
+                    lo[j].at = lb[ib++].at + a->count;
+                } else {
+                    lo[j] = la[ia++];
+                }
+            }
+        }
+        atsc_window_extremes_head *nh = (atsc_window_extremes_head *)next;
+        nh->count = a->count + b->count;
+        nh->nans = a->nans + b->nans;
+        memcpy(acc, next, bytes);
+    }
+    memcpy(out, acc, bytes);
     return ATSC_OK;
 }
 
@@ -1680,6 +1807,14 @@ extern "C" int atsc_stream_runs_windows(atsc_stream *s, uint64_t n_windows, cons
 {
     ATSC_API_BEGIN
     return query_stream(s, n_windows, begin, count, out, RunQuery{op, limit});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_extremes_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                            uint32_t k, void *out)
+{
+    ATSC_API_BEGIN
+    return query_stream(s, n_windows, begin, count, out, ExtQuery{k});
     ATSC_API_END
 }
 

@@ -4,7 +4,8 @@
 // Compression and decompression run on the GPU; the index and the text formats are host code.
 //
 //   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
-//                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]]]]
+//                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]
+//                  [--extremes K]]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
@@ -61,6 +62,10 @@ void usage()
             "                                 runs, longest (in samples), longest_at, first_at, last_at (the indexed times of\n"
             "                                 those samples, empty where there is none), head, tail (in samples), excess (the\n"
             "                                 sum of |value - LIMIT| over them)\n"
+            "      --extremes <K>             with --step: also every bucket's K largest and K smallest samples (K: 1..16) and\n"
+            "                                 when they happened, as the last columns: nans, max1, max1_at .. maxK, maxK_at,\n"
+            "                                 min1, min1_at .. minK, minK_at (equal values earliest first; *_at the indexed\n"
+            "                                 time of the sample; both cells empty where the bucket has fewer samples)\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -159,6 +164,20 @@ int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *b
         }
         if (index) atsc_vsri_free(index);
         if (rc) { int e = die("runs: indexed time", rc); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+    }
+    // "when was the peak": the extremes' places as the indexed times of their samples, likewise
+    if (a.q.extremes && nb) {
+        index = nullptr;
+        rc = atsc_vsri_load(with_ext(a.input, "vsri").c_str(), &index);
+        if (!rc)
+            rc = bucket_extreme_places(r, nb, [&](uint64_t k, uint64_t at, std::string &cell) {
+                int32_t t = 0;
+                const int got = atsc_vsri_get_time(index, (int32_t)(b[k] + at), &t);  // 1: Some(t), 0: None
+                if (got == 1) cell = std::to_string(t);
+                return got < 0 ? got : 0;
+            });
+        if (index) atsc_vsri_free(index);
+        if (rc) { int e = die("extremes: indexed time", rc); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
     }
     atsc_ctx_destroy(ctx);
     atsc_free(bro);

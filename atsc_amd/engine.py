@@ -39,6 +39,19 @@ RUNS_GT, RUNS_GE, RUNS_LT, RUNS_LE, RUNS_EQ, RUNS_NE = (capi.RUNS_GT, capi.RUNS_
                                                         capi.RUNS_EQ, capi.RUNS_NE)
 RUNS_NONE = capi.RUNS_NONE
 
+# one entry of a window's extremes (atsc_extreme): the sample's own bits and its offset from the window's begin
+EXTREME = np.dtype([("value", "<f8"), ("at", "<u8")])
+EXTREMES_MAX_K, EXTREMES_NONE = capi.EXTREMES_MAX_K, capi.EXTREMES_NONE
+
+
+def window_extremes_dtype(k):
+    """-> the record of one window of an extremes call with k entries per list (include/atsc_hip.h), 16 + 32 k bytes:
+    count, nans, largest[k] and smallest[k], the last two of (value, at); an empty entry is (NaN, EXTREMES_NONE)"""
+    k = int(k)
+    if not 1 <= k <= EXTREMES_MAX_K:
+        raise ValueError("k outside 1..%d" % EXTREMES_MAX_K)
+    return np.dtype([("count", "<u8"), ("nans", "<u8"), ("largest", EXTREME, (k,)), ("smallest", EXTREME, (k,))])
+
 
 def _windows(begins, counts):
     b, pb = _u64(np.atleast_1d(begins))
@@ -57,7 +70,8 @@ def _levels(levels):
 # *_data_windows) need it:
 #   stem    the C calls are atsc_<stem>, atsc_<stem>_dev and atsc_stream_<stem>
 #   dtype   of the result: one record per window (extra is None), or per window a row of `extra` cells more than the
-#           call's levels or edges; the device tensor holds at least that many bytes per window
+#           call's levels or edges; the device tensor holds at least that many bytes per window.  A function of the
+#           call's own arguments where the record depends on them (the extremes' k)
 #   params  the call's own arguments -> their C arguments, which stand between the windows and the result
 _Query = collections.namedtuple("_Query", "stem dtype extra params")
 
@@ -70,6 +84,22 @@ def _runs_params(op, limit):
     return int(op), float(limit)
 
 
+def _extremes_params(k):
+    return (C.c_uint32(_extremes_k(k)),)
+
+
+def _extremes_k(k):
+    k = int(k)
+    if not 0 <= k < 2 ** 32:
+        raise ValueError("k outside uint32")
+    return k
+
+
+def _extremes_dtype(k):
+    """the record of a call with k; a k that the library refuses still gets a result to leave untouched"""
+    return window_extremes_dtype(min(max(_extremes_k(k), 1), EXTREMES_MAX_K))
+
+
 def _array_params(values, flag):
     """levels and method, or edges and closed"""
     a, pa = _levels(values)
@@ -80,6 +110,7 @@ _AGGREGATE = _Query("aggregate_windows", WINDOW_STATS, None, _no_params)
 _MOMENTS = _Query("moments_windows", WINDOW_MOMENTS, None, _no_params)
 _DELTA = _Query("delta_windows", WINDOW_DELTA, None, _no_params)
 _RUNS = _Query("runs_windows", WINDOW_RUNS, None, _runs_params)
+_EXTREMES = _Query("extremes_windows", _extremes_dtype, None, _extremes_params)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
 _HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
 
@@ -89,10 +120,14 @@ def _query_width(q, cargs):
     return 1 if q.extra is None else cargs[0] + q.extra
 
 
-def _query_result(q, n, cargs, fn):
+def _query_dtype(q, params):
+    return q.dtype(*params) if callable(q.dtype) else q.dtype
+
+
+def _query_result(q, n, cargs, fn, params=()):
     """-> (the zeroed host result of n windows, at least one, and its pointer as fn's last argument)"""
     rows = max(n, 1)
-    out = np.zeros(rows if q.extra is None else (rows, _query_width(q, cargs)), dtype=q.dtype)
+    out = np.zeros(rows if q.extra is None else (rows, _query_width(q, cargs)), dtype=_query_dtype(q, params))
     return out, out.ctypes.data_as(fn.argtypes[-1])
 
 
@@ -102,7 +137,7 @@ def _query_host(q, ctx, records, begins, counts, has_count, *params):
     wb, pb, wc, pc = _windows(begins, counts)
     cargs = q.params(*params)
     fn = getattr(capi.lib(), "atsc_" + q.stem)
-    out, po = _query_result(q, len(wb), cargs, fn)
+    out, po = _query_result(q, len(wb), cargs, fn, params)
     rc = fn(ctx._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count), len(wb), pb, pc, *cargs, po)
     capi.check(rc, ctx._h)
     return out[: len(wb)]
@@ -114,7 +149,7 @@ def _query_dev(q, dplan, d_body, begins, counts, d_out, stream, *params):
     cargs = q.params(*params)
     assert q.extra is None or d_out.element_size() == 8
     assert d_out.is_contiguous()
-    assert d_out.numel() * d_out.element_size() >= q.dtype.itemsize * _query_width(q, cargs) * len(b)
+    assert d_out.numel() * d_out.element_size() >= _query_dtype(q, params).itemsize * _query_width(q, cargs) * len(b)
     rc = getattr(capi.lib(), "atsc_%s_dev" % q.stem)(dplan.ctx._h, dplan._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
                                                      *cargs, C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
     capi.check(rc, dplan.ctx._h)
@@ -158,6 +193,17 @@ def runs_merge(records):
     out = np.zeros(1, dtype=WINDOW_RUNS)
     capi.check(capi.lib().atsc_runs_merge(C.c_void_p(r.ctypes.data if len(r) else None), len(r),
                                           C.c_void_p(out.ctypes.data)))
+    return out[0]
+
+
+def extremes_merge(records, k):
+    """-> one record of window_extremes_dtype(k) (a 0-d array): the records of adjacent windows, left to right, folded
+    into the record of their union, which it equals bit for bit (atsc_extremes_merge; no GPU)"""
+    dt = window_extremes_dtype(k)
+    r = np.ascontiguousarray(np.atleast_1d(np.asarray(records, dtype=dt)))
+    out = np.zeros(1, dtype=dt)
+    capi.check(capi.lib().atsc_extremes_merge(C.c_void_p(r.ctypes.data if len(r) else None), len(r), int(k),
+                                              C.c_void_p(out.ctypes.data)))
     return out[0]
 
 
@@ -288,6 +334,12 @@ class Context:
         run, the first and last such sample, the runs at the two ends and the sum of |x - limit| of every window
         [begins[i], begins[i] + counts[i]) of the decoded records (atsc_runs_windows)"""
         return _query_host(_RUNS, self, records, begins, counts, has_count, op, limit)
+
+    def extremes_windows_host(self, records, begins, counts, k, has_count=False):
+        """-> array of window_extremes_dtype(k): the k largest and the k smallest non-NaN samples, each with its offset
+        in the window, the number of NaN samples and the length of every window [begins[i], begins[i] + counts[i]) of
+        the decoded records (atsc_extremes_windows)"""
+        return _query_host(_EXTREMES, self, records, begins, counts, has_count, k)
 
     def quantile_windows_host(self, records, begins, counts, levels, method=capi.QUANTILE_LINEAR, has_count=False):
         """-> (n_windows, n_levels) float64 array: the levels of every window [begins[i], begins[i] + counts[i]) of the
@@ -437,6 +489,12 @@ class DPlan:
         """Enqueues the runs of the samples with x OP limit of the windows [begins[i], begins[i] + counts[i]) into d_out,
         a device tensor of at least 80 bytes per window (atsc_runs_windows_dev; WINDOW_RUNS records)"""
         _query_dev(_RUNS, self, d_body, begins, counts, d_out, stream, op, limit)
+
+    def extremes_windows(self, d_body, begins, counts, k, d_out, stream=0):
+        """Enqueues the k largest and the k smallest samples of the windows [begins[i], begins[i] + counts[i]) into
+        d_out, a device tensor of at least 16 + 32 k bytes per window (atsc_extremes_windows_dev; records of
+        window_extremes_dtype(k))"""
+        _query_dev(_EXTREMES, self, d_body, begins, counts, d_out, stream, k)
 
     def quantile_windows(self, d_body, begins, counts, levels, d_out, method=capi.QUANTILE_LINEAR, stream=0):
         """Enqueues the levels of the windows [begins[i], begins[i] + counts[i]) into d_out, a float64 device tensor of

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import capi
 from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit  # noqa: F401
-from .engine import _AGGREGATE, _DELTA, _HISTOGRAM, _MOMENTS, _QUANTILE, _RUNS, _query_result
+from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _QUANTILE, _RUNS, _query_result
 
 
 def _f64(x):
@@ -32,7 +32,7 @@ def _query_stream(q, stream, begins, counts, *params):
     wb, pb, wc, pc = _windows(begins, counts)
     cargs = q.params(*params)
     fn = getattr(capi.lib(), "atsc_stream_" + q.stem)
-    out, po = _query_result(q, len(wb), cargs, fn)
+    out, po = _query_result(q, len(wb), cargs, fn, params)
     capi.check(fn(stream._h, len(wb), pb, pc, *cargs, po), stream.ctx._h)
     return out[: len(wb)]
 
@@ -44,7 +44,7 @@ def _query_image(q, ctx, bro, begins, counts, *params):
     wb, pb, wc, pc = _windows(begins, counts)
     cargs = q.params(*params)
     fn = getattr(capi.lib(), "atsc_" + q.stem)
-    out, po = _query_result(q, len(wb), cargs, fn)
+    out, po = _query_result(q, len(wb), cargs, fn, params)
     r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
     rc = fn(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc, *cargs, po)
     capi.check(rc, ctx._h)
@@ -133,6 +133,11 @@ class CompressedStream:
         (atsc_stream_runs_windows)"""
         return _query_stream(_RUNS, self, begins, counts, op, limit)
 
+    def extremes_windows(self, begins, counts, k):
+        """-> array of window_extremes_dtype(k) of the windows [begins[i], begins[i] + counts[i]): their k largest and k
+        smallest samples and where they are (atsc_stream_extremes_windows)"""
+        return _query_stream(_EXTREMES, self, begins, counts, k)
+
     def quantile_windows(self, begins, counts, levels, method=capi.QUANTILE_LINEAR):
         """-> (n_windows, n_levels) float64 array of the windows' levels (atsc_stream_quantile_windows)"""
         return _query_stream(_QUANTILE, self, begins, counts, levels, method)
@@ -199,6 +204,12 @@ def runs_data_windows(ctx, bro, begins, counts, op, limit):
     """-> WINDOW_RUNS array of windows of decompress_data(ctx, bro) under the condition x OP limit: atsc_bro_open, then
     atsc_runs_windows over the records"""
     return _query_image(_RUNS, ctx, bro, begins, counts, op, limit)
+
+
+def extremes_data_windows(ctx, bro, begins, counts, k):
+    """-> array of window_extremes_dtype(k) of windows of decompress_data(ctx, bro): their k largest and k smallest
+    samples and where they are: atsc_bro_open, then atsc_extremes_windows over the records"""
+    return _query_image(_EXTREMES, ctx, bro, begins, counts, k)
 
 
 def quantile_data_windows(ctx, bro, begins, counts, levels, method=capi.QUANTILE_LINEAR):

@@ -509,6 +509,58 @@ int atsc_runs_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int
  * one add per record: it may differ from the union window's own value in its last bits. */
 int atsc_runs_merge(const atsc_window_runs *r, uint64_t n, atsc_window_runs *out);
 
+/* Windowed extremes: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames) its
+ * k largest and its k smallest samples and where they are, from the same decoded samples as the window decode: when was
+ * the peak of each hour, what are the five worst spikes of the day and when did they happen, first / last / min / max
+ * with their positions per pixel column (M4 downsampling, together with atsc_aggregate_windows' first and last).
+ * One k, 1 <= k <= ATSC_EXTREMES_MAX_K, holds for every window of a call.  The record of a window is 2 + 4 k eight-byte
+ * words, ATSC_EXTREMES_BYTES(k) bytes: an atsc_window_extremes_head, then largest[0 .. k), then smallest[0 .. k), each an
+ * atsc_extreme; record i lies at (char *)out + i * ATSC_EXTREMES_BYTES(k).
+ *   Order    largest lists the window's non-NaN samples by value descending, smallest by value ascending, in both equal
+ *            values earliest position first.  Samples are compared as values: -0.0 equals +0.0, so position decides
+ *            between them; +-Inf are ordinary values.  That is numpy.argsort(-x, kind="stable") and
+ *            numpy.argsort(x, kind="stable") with the NaNs dropped.
+ *   Entries  value is the sample's own bits (a -0.0 stays -0.0), at its offset from `begin`.  NaN is never an entry; nans
+ *            counts them.  count is count[i], NaN included.  A window with fewer than k non-NaN samples fills the
+ *            remaining entries with value = NaN, at = ATSC_EXTREMES_NONE.  One sample may appear in both lists.
+ *            count == 0 gives zeros in the head and 2 k empty entries.
+ * There is no floating-point arithmetic in the contract: the record is bit-exact, and it depends only on the stream's
+ * samples, the window and k, not on the other windows, their order, the budget, piece boundaries or the device.  The
+ * first j entries of a call with k are the entries of a call with j < k; largest[0].value equals atsc_aggregate_windows'
+ * max as a value and smallest[0].value its min.
+ * ATSC_E_INVALID with nothing written, before any GPU work, for k == 0 or k > ATSC_EXTREMES_MAX_K.  Validation and the
+ * other semantics are atsc_aggregate_windows_dev's: a window beyond the stream gives ATSC_E_INVALID with nothing written;
+ * payloads are checked only of the frames a window touches; windows may overlap and come in any order; count == 0 and
+ * n_windows == 0 are valid.  Windows may be of any length: there is no ATSC_E_CAPACITY case. */
+typedef struct {
+    double value; /* the sample's own bits; NaN in an empty entry */
+    uint64_t at;  /* its offset from the window's begin; ATSC_EXTREMES_NONE in an empty entry */
+} atsc_extreme; /* 16 bytes */
+typedef struct {
+    uint64_t count; /* count[i], NaN included */
+    uint64_t nans;  /* NaN samples */
+} atsc_window_extremes_head; /* 16 bytes */
+#define ATSC_EXTREMES_MAX_K 16
+#define ATSC_EXTREMES_NONE UINT64_MAX
+#define ATSC_EXTREMES_BYTES(k) (16u + 32u * (size_t)(k))
+/* Record i at (char *)d_out + i * ATSC_EXTREMES_BYTES(k).  begin / count are HOST arrays; d_body and d_out are device
+ * memory (d_out 8-byte aligned).  Enqueued on `stream`, not synchronised.  A malformed payload inside a window sets the
+ * plan's status word.  The plan keeps the call's tables, partials (2 + 4 k words each) and scratch: the next extremes
+ * call on the same plan waits (host side) until this one's work is done; atsc_dplan_destroy frees them. */
+int atsc_extremes_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                              const uint64_t *begin, const uint64_t *count, uint32_t k, void *d_out, void *stream);
+/* Host bytes in, host records out, synchronous; walks and uploads only the touched records, as atsc_aggregate_windows
+ * does.  ATSC_E_FORMAT (nothing written) for a malformed payload inside a window. */
+int atsc_extremes_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                          const uint64_t *begin, const uint64_t *count, uint32_t k, void *out);
+/* Folds the records of n adjacent windows (all of the same k), left to right, into the record of their union at `out`,
+ * host only (no GPU): record i + 1 begins where record i ends.  count and nans add; every `at` of record i is shifted by
+ * the counts in front of it; each list is the first k of the parts' lists merged in the order above.  The k best of a
+ * union are among the k best of its parts, so -- unlike atsc_runs_merge's excess -- the merged record equals the union
+ * window's own record bit for bit.  Records with count == 0 are skipped; n == 0 gives the empty record.  ATSC_E_INVALID
+ * for a null pointer with n > 0, a null out, or k outside 1 .. ATSC_EXTREMES_MAX_K. */
+int atsc_extremes_merge(const void *records, uint64_t n, uint32_t k, void *out);
+
 /* Windowed quantiles: exact order statistics of windows [begin, begin + count) of the decoded stream (the indices of
  * atsc_decompress_frames), from the same decoded samples as the window decode.  For window i:
  *   x  the window's non-NaN samples, n of them, sorted in IEEE total order (-0.0 before +0.0), i.e. by the keys
@@ -615,6 +667,9 @@ int atsc_stream_delta_windows(atsc_stream *s, uint64_t n_windows, const uint64_t
 /* atsc_runs_windows over the stream's frames */
 int atsc_stream_runs_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count, int op,
                              double limit, atsc_window_runs *out);
+/* atsc_extremes_windows over the stream's frames */
+int atsc_stream_extremes_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                 uint32_t k, void *out);
 /* atsc_moments_windows over the stream's frames */
 int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 atsc_window_moments *out);
