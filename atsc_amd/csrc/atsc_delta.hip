@@ -5,8 +5,8 @@
 // The contract is include/atsc_hip.h's (DESIGN.md "Windowed deltas").  The pair of stream index j is (a, b) =
 // (x[j - 1], x[j]), for begin < j < begin + count; it is counted iff neither is NaN, a rise iff b > a and a fall iff
 // b < a.  Its terms sit at slot j, the slot of b: b - a in `up` for a rise, a - b in `down` and b in `after_falls` for
-// a fall; every other slot holds -0.0, and the three sums go through the aggregate sum's tree (atsc_aggregate.hip)
-// unchanged.  The counts and the two maxima are exact in any order.
+// a fall; every other slot holds -0.0, and the three sums go through the tile sum's tree (tile_lane_sums,
+// atsc_tile_reduce.h) side by side.  The counts and the two maxima are exact in any order.
 // One wavefront reduces one tile (lane l holds the virtual lanes l, l + 64, l + 128, l + 192) or one group of 64 tile
 // partials of a window.  No atomics: every partial has one writer.
 //
@@ -17,43 +17,23 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "atsc_device.h"
+#include "atsc_tile_reduce.h"
 
 namespace atsc {
 
 namespace {
 
-struct Dlt {
-    double up, down, af, mr, mf;
-    uint64_t pairs, rises, falls;
-};
-
-__device__ __forceinline__ Dlt dlt_identity() { return Dlt{-0.0, -0.0, -0.0, 0.0, 0.0, 0, 0, 0}; }
-
-__device__ __forceinline__ Dlt dlt_shfl_down(const Dlt &a, unsigned off)
-{
-    Dlt o;
-    o.up = __shfl_down(a.up, off, 64);
-    o.down = __shfl_down(a.down, off, 64);
-    o.af = __shfl_down(a.af, off, 64);
-    o.mr = __shfl_down(a.mr, off, 64);
-    o.mf = __shfl_down(a.mf, off, 64);
-    o.pairs = __shfl_down(a.pairs, off, 64);
-    o.rises = __shfl_down(a.rises, off, 64);
-    o.falls = __shfl_down(a.falls, off, 64);
-    return o;
-}
-
-__device__ __forceinline__ void dlt_add(Dlt &a, const Dlt &b)
+__device__ __forceinline__ DevDltPart dlt_add(DevDltPart a, const DevDltPart &b)
 {
     a.up = a.up + b.up;
     a.down = a.down + b.down;
-    a.af = a.af + b.af;
-    a.mr = b.mr > a.mr ? b.mr : a.mr;
-    a.mf = b.mf > a.mf ? b.mf : a.mf;
+    a.after_falls = a.after_falls + b.after_falls;
+    a.max_rise = b.max_rise > a.max_rise ? b.max_rise : a.max_rise;
+    a.max_fall = b.max_fall > a.max_fall ? b.max_fall : a.max_fall;
     a.pairs += b.pairs;
     a.rises += b.rises;
     a.falls += b.falls;
+    return a;
 }
 
 // what a lane keeps beside the three sums' terms while it walks its 32 slots: the maxima and the counts
@@ -87,29 +67,28 @@ __global__ __launch_bounds__(256) void k_dlt_tiles(const DevDltTile *__restrict_
                                                    const double *__restrict__ scratch, const double *__restrict__ carry,
                                                    DevDltPart *__restrict__ part)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = wave_lane(), i = wave_task();
     if (i >= n) return;
     const DevDltTile t = tasks[i];
     const double *x = scratch + t.src;
     const bool cont = (t.flags & DLT_CONT) != 0;
     Side sd{0.0, 0.0, 0, 0, 0};
-    // The virtual lanes go two at a time, (lane, lane + 128) and then (lane + 64, lane + 192), in a loop that is not
-    // unrolled: the halving tree's first step inside the lane, s[v] + s[v + 128], closes each trip, its second step
-    // joins the two trips.  Unrolled four times the 32 loads and their predicates take 238 VGPRs.
-    double tu = -0.0, td = -0.0, ta = -0.0;
+    // The three tile sums in the order tile_lane_sums (atsc_tile_reduce.h) defines, written out: through that helper
+    // this kernel's schedule comes out at 148 VGPRs and more instead of 126, a wave less per SIMD.  The virtual lanes
+    // go two at a time, (lane, lane + 128) and then (lane + 64, lane + 192), in a loop that is not unrolled: the halving
+    // tree's first step inside the lane, s[v] + s[v + 128], closes each trip, its second step joins the two trips.
+    // Unrolled four times the 32 loads and their predicates take 238 VGPRs.
+    double r[3] = {-0.0, -0.0, -0.0};
 #pragma unroll 1
     for (uint32_t kk = 0; kk < 2; ++kk) {
-        double su[2], sdn[2], sa[2];
+        double h[3];
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const uint32_t v = lane + 64u * kk + 128u * e;
-            double pu[4], pd[4], pa[4];
+        for (uint32_t e = 0; e < 2; ++e) {
+            double p[4][3];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t j = 512u * q + 2u * v;
-                double2 d = make_double2(-0.0, -0.0);
-                if (j < t.hi && j + 2u > t.lo) d = *(const double2 *)(x + j);  // 16-byte load; scratch tiles are 16-byte aligned
+            for (uint32_t q = 0; q < 4; ++q) {
+                const uint32_t j = tile_slot(lane + 64u * kk + 128u * e, q);
+                const double2 d = tile_load(x, j, t.lo, t.hi, -0.0);
                 const bool in0 = j < t.hi && (j > t.lo || (cont && j == t.lo));
                 const bool in1 = j + 1u < t.hi && j + 1u > t.lo;
                 double a = -0.0;  // x[j - 1]: inside the tile, in front of it, or carried over from the previous piece
@@ -117,53 +96,37 @@ __global__ __launch_bounds__(256) void k_dlt_tiles(const DevDltTile *__restrict_
                 double u0, d0, a0, u1, d1, a1;
                 pair_take(a, d.x, in0, u0, d0, a0, sd);
                 pair_take(d.x, d.y, in1, u1, d1, a1, sd);
-                pu[q] = u0 + u1;
-                pd[q] = d0 + d1;
-                pa[q] = a0 + a1;
+                p[q][0] = u0 + u1;
+                p[q][1] = d0 + d1;
+                p[q][2] = a0 + a1;
             }
-            su[e] = (pu[0] + pu[1]) + (pu[2] + pu[3]);
-            sdn[e] = (pd[0] + pd[1]) + (pd[2] + pd[3]);
-            sa[e] = (pa[0] + pa[1]) + (pa[2] + pa[3]);
-        }
-        // halving tree over the 256 virtual lanes, h = 128 and 64: (s[l] + s[l + 128]) + (s[l + 64] + s[l + 192])
-        const double hu = su[0] + su[1], hd = sdn[0] + sdn[1], ha = sa[0] + sa[1];
-        tu = kk ? tu + hu : hu;
-        td = kk ? td + hd : hd;
-        ta = kk ? ta + ha : ha;
-    }
-    // then h = 32 .. 1 across the wavefront
-    Dlt r{tu, td, ta, sd.mr, sd.mf, sd.pairs, sd.rises, sd.falls};
 #pragma unroll
-    for (unsigned off = 32; off >= 1; off >>= 1) dlt_add(r, dlt_shfl_down(r, off));
-    if (lane == 0) part[t.dst] = DevDltPart{r.up, r.down, r.af, r.mr, r.mf, r.pairs, r.rises, r.falls};
+            for (int c = 0; c < 3; ++c) {
+                const double v = (p[0][c] + p[1][c]) + (p[2][c] + p[3][c]);
+                h[c] = e ? h[c] + v : v;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[c] = kk ? r[c] + h[c] : h[c];
+    }
+    const DevDltPart o{r[0], r[1], r[2], sd.mr, sd.mf, sd.pairs, sd.rises, sd.falls};
+    const DevDltPart w = wave_halve(o, dlt_add);
+    if (lane == 0) part[t.dst] = w;
 }
 
-// One wavefront per DevAggComb: partials j = 64 g .. 64 g + 63 of a window's list (j < n; j == 0 at head, j == n - 1 at
-// tail, else at mid + j) through the pairwise tree (lane l + 2^k into lane l; a missing right operand is -0.0), then
-// into part[dst] or, in the final pass, the window's atsc_window_delta (eight 8-byte fields, one per lane): a sum
-// without a term is +0.0.
+// One wavefront per DevAggComb: the group's partials through comb_reduce (a missing right operand is -0.0), then, in
+// the final pass, into the window's atsc_window_delta (eight 8-byte fields, one per lane): a sum without a term is +0.0.
 __global__ __launch_bounds__(256) void k_dlt_combine(const DevAggComb *__restrict__ tasks, uint32_t n_tasks,
                                                      DevDltPart *__restrict__ part, uint64_t *__restrict__ out)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = wave_lane(), i = wave_task();
     if (i >= n_tasks) return;
     const DevAggComb c = tasks[i];
-    const uint64_t j = 64ull * c.g + lane;
-    Dlt a = dlt_identity();
-    if (j < c.n) {
-        const DevDltPart p = part[j == 0 ? c.head : j == c.n - 1 ? c.tail : c.mid + j];
-        a = Dlt{p.up, p.down, p.after_falls, p.max_rise, p.max_fall, p.pairs, p.rises, p.falls};
-    }
-#pragma unroll
-    for (unsigned off = 1; off < 64; off <<= 1) dlt_add(a, dlt_shfl_down(a, off));
-    if (!c.final_) {
-        if (lane == 0) part[c.dst] = DevDltPart{a.up, a.down, a.af, a.mr, a.mf, a.pairs, a.rises, a.falls};
-        return;
-    }
+    const DevDltPart a = comb_reduce(c, lane, part, DevDltPart{-0.0, -0.0, -0.0, 0.0, 0.0, 0, 0, 0}, dlt_add);
+    if (!c.final_) return;
     const uint64_t pairs = __shfl(a.pairs, 0, 64), rises = __shfl(a.rises, 0, 64), falls = __shfl(a.falls, 0, 64);
-    const double up = __shfl(a.up, 0, 64), down = __shfl(a.down, 0, 64), af = __shfl(a.af, 0, 64),
-                 mr = __shfl(a.mr, 0, 64), mf = __shfl(a.mf, 0, 64);
+    const double up = __shfl(a.up, 0, 64), down = __shfl(a.down, 0, 64), af = __shfl(a.after_falls, 0, 64),
+                 mr = __shfl(a.max_rise, 0, 64), mf = __shfl(a.max_fall, 0, 64);
     if (lane < 8) {
         uint64_t w;
         switch (lane) {
@@ -183,16 +146,12 @@ __global__ __launch_bounds__(256) void k_dlt_combine(const DevAggComb *__restric
 hipError_t launch_dlt_tiles(const DevDltTile *tasks, uint32_t n, const double *scratch, const double *carry,
                             DevDltPart *part, hipStream_t s)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dlt_tiles, dim3((n + 3) / 4), dim3(256), 0, s, tasks, n, scratch, carry, part);
-    return hipGetLastError();
+    return launch_wave_tasks(k_dlt_tiles, n, s, tasks, n, scratch, carry, part);
 }
 
 hipError_t launch_dlt_combine(const DevAggComb *tasks, uint32_t n, DevDltPart *part, void *out, hipStream_t s)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dlt_combine, dim3((n + 3) / 4), dim3(256), 0, s, tasks, n, part, (uint64_t *)out);
-    return hipGetLastError();
+    return launch_wave_tasks(k_dlt_combine, n, s, tasks, n, part, (uint64_t *)out);
 }
 
 }  // namespace atsc

@@ -16,7 +16,8 @@
 // begin.  One wavefront selects from one tile or merges one group of 64 partials.  No atomics, no LDS: every partial has
 // one writer, and the lists live one entry per lane in lanes 0 .. k - 1 (k <= 16).
 //
-// The tile kernel keeps k_agg_tiles' 16-byte loads and slot-to-lane mapping and selects in three phases, per end:
+// The tile kernel keeps the 16-byte loads and slot-to-lane mapping of atsc_tile_reduce.h and selects in three phases, per
+// end:
 //   1. every lane finds the entry that is ahead of all others among its own 32 slots;
 //   2. a bitonic sort over the 64 lanes orders those lane-bests; lanes 0 .. k - 1 then hold the start of the list, which
 //      is k members of the answer's candidates already, and lane k - 1 holds the threshold;
@@ -28,7 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "atsc_device.h"
+#include "atsc_tile_reduce.h"
 
 namespace atsc {
 
@@ -93,16 +94,15 @@ __device__ __forceinline__ void ext_insert(uint64_t &lk, uint32_t &lp, uint64_t 
 
 }  // namespace
 
-// One wavefront per DevExtTile: the partial of the slots [lo, hi) of the tile at scratch[src], whose slot 0 is sample t0
+// One wavefront per DevPosTile: the partial of the slots [lo, hi) of the tile at scratch[src], whose slot 0 is sample t0
 // of the stream, into part[dst (2 + 4 k)].
-__global__ __launch_bounds__(256) void k_ext_tiles(const DevExtTile *__restrict__ tasks, uint32_t n,
+__global__ __launch_bounds__(256) void k_ext_tiles(const DevPosTile *__restrict__ tasks, uint32_t n,
                                                    const double *__restrict__ scratch, uint32_t k,
                                                    uint64_t *__restrict__ part)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = wave_lane(), i = wave_task();
     if (i >= n) return;
-    const DevExtTile t = tasks[i];
+    const DevPosTile t = tasks[i];
     const double *x = scratch + t.src;
     // phase 1: the lane's best of each end, and its NaN samples
     uint64_t bkl = 0, bks = 0;
@@ -112,14 +112,13 @@ __global__ __launch_bounds__(256) void k_ext_tiles(const DevExtTile *__restrict_
         const uint32_t v = lane + 64u * kk;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const uint32_t j = 512u * q + 2u * v;
-            double2 d = make_double2(0.0, 0.0);
-            if (j < t.hi && j + 2u > t.lo) d = *(const double2 *)(x + j);  // 16-byte load; scratch tiles are 16-byte aligned
+            const uint32_t j = tile_slot(v, q);
+            const double2 d = tile_load(x, j, t.lo, t.hi, 0.0);
 #pragma unroll
             for (uint32_t e = 0; e < 2; ++e) {
                 const uint32_t p = j + e;
                 const double s = e ? d.y : d.x;
-                const bool in = p >= t.lo && p < t.hi;
+                const bool in = tile_in(p, t.lo, t.hi);
                 const uint64_t kl = in ? ext_key(s) : 0ull, ks = kl ? ~kl : 0ull;
                 nans += in && s != s ? 1u : 0u;
                 if (kl && ext_ahead(kl, p, bkl, bpl)) { bkl = kl; bpl = p; }
@@ -144,14 +143,13 @@ __global__ __launch_bounds__(256) void k_ext_tiles(const DevExtTile *__restrict_
             const uint32_t v = lane + 64u * kk;
 #pragma unroll 1
             for (uint32_t q = 0; q < 4; ++q) {
-                const uint32_t j = 512u * q + 2u * v;
-                double2 d = make_double2(0.0, 0.0);
-                if (j < t.hi && j + 2u > t.lo) d = *(const double2 *)(x + j);
+                const uint32_t j = tile_slot(v, q);
+                const double2 d = tile_load(x, j, t.lo, t.hi, 0.0);
 #pragma unroll
                 for (uint32_t e = 0; e < 2; ++e) {
                     const uint32_t p = j + e;
                     const double s = e ? d.y : d.x;
-                    const bool in = p >= t.lo && p < t.hi;
+                    const bool in = tile_in(p, t.lo, t.hi);
                     const uint64_t kl = in ? ext_key(s) : 0ull, ks = kl ? ~kl : 0ull;
                     const uint32_t p0 = 512u * q + 128u * kk + e;  // lane 0's slot of this step and half
                     uint64_t m = __ballot(kl != 0 && p != bpl && ext_ahead(kl, p, tkl, tpl));
@@ -188,23 +186,21 @@ __global__ __launch_bounds__(256) void k_ext_tiles(const DevExtTile *__restrict_
     }
 }
 
-// One wavefront per DevAggComb: partials j = 64 g .. 64 g + 63 of a window's list (j < n; j == 0 at head, j == n - 1 at
-// tail, else at mid + j), one per lane, into the partial part[dst] or, in the final pass, the window's record out[dst]
-// (positions counted from the window's begin[win]).  count and nans add.  Per end, every lane holds a cursor into its
-// partial's list and the entry under it; k rounds pop the group's first k: the wave maximum of the heads' keys, of equal
+// One wavefront per DevAggComb: the group's partials (comb_entry, comb_at), one per lane, into the partial part[dst] or,
+// in the final pass, the window's record out[dst] (positions counted from the window's begin[win]).  count and nans
+// add.  Per end, every lane holds a cursor into its partial's list and the entry under it; k rounds pop the group's first k: the wave maximum of the heads' keys, of equal
 // keys the lowest lane (partials come in stream order and a list puts equal values earliest first, so that is the
 // earliest position); the winner's entry goes to lane r of the result, and the winner reads its next entry from memory.
 __global__ __launch_bounds__(256) void k_ext_combine(const DevAggComb *__restrict__ tasks, uint32_t n_tasks, uint32_t k,
                                                      uint64_t *__restrict__ part, const uint64_t *__restrict__ begin,
                                                      uint64_t *__restrict__ out)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = wave_lane(), i = wave_task();
     if (i >= n_tasks) return;
     const DevAggComb c = tasks[i];
-    const uint64_t j = 64ull * c.g + lane, words = 2ull + 4ull * k;
+    const uint64_t j = comb_entry(c, lane), words = 2ull + 4ull * k;
     const bool have = j < c.n;
-    const uint64_t *p = part + (have ? (j == 0 ? c.head : j == c.n - 1 ? c.tail : c.mid + j) : 0ull) * words;
+    const uint64_t *p = part + (have ? comb_at(c, j) : 0ull) * words;
     uint64_t cnt = have ? p[0] : 0ull, nans = have ? p[1] : 0ull;
 #pragma unroll
     for (unsigned off = 32; off >= 1; off >>= 1) {
@@ -255,21 +251,16 @@ __global__ __launch_bounds__(256) void k_ext_combine(const DevAggComb *__restric
     }
 }
 
-hipError_t launch_ext_tiles(const DevExtTile *tasks, uint32_t n, const double *scratch, uint32_t k, void *part,
+hipError_t launch_ext_tiles(const DevPosTile *tasks, uint32_t n, const double *scratch, uint32_t k, void *part,
                             hipStream_t s)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ext_tiles, dim3((n + 3) / 4), dim3(256), 0, s, tasks, n, scratch, k, (uint64_t *)part);
-    return hipGetLastError();
+    return launch_wave_tasks(k_ext_tiles, n, s, tasks, n, scratch, k, (uint64_t *)part);
 }
 
 hipError_t launch_ext_combine(const DevAggComb *tasks, uint32_t n, uint32_t k, void *part, const uint64_t *begin,
                               void *out, hipStream_t s)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ext_combine, dim3((n + 3) / 4), dim3(256), 0, s, tasks, n, k, (uint64_t *)part, begin,
-                       (uint64_t *)out);
-    return hipGetLastError();
+    return launch_wave_tasks(k_ext_combine, n, s, tasks, n, k, (uint64_t *)part, begin, (uint64_t *)out);
 }
 
 }  // namespace atsc

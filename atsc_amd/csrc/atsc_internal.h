@@ -213,8 +213,9 @@ struct DevMomPart {
     double mx, m2x, mt, m2t, c;
     uint64_t n;
 };
-// one tile of k_mom_tiles: slots [lo, hi) of the tile whose slot 0 is scratch[src] and sample t0 of the stream -> part[dst]
-struct DevMomTile {
+// one tile of k_mom_tiles, k_run_tiles and k_ext_tiles: slots [lo, hi) of the tile whose slot 0 is scratch[src] and
+// sample t0 of the stream -> part[dst] (extremes: partial dst)
+struct DevPosTile {
     uint64_t src, dst, t0;
     uint32_t lo, hi;
 };
@@ -245,21 +246,11 @@ struct DevRunPart {
     uint64_t samples, inside, runs, longest, longest_at, first_at, last_at, head, tail;
     double excess;
 };
-// one tile of k_run_tiles: slots [lo, hi) of the tile whose slot 0 is scratch[src] and sample t0 of the stream -> part[dst]
-struct DevRunTile {
-    uint64_t src, dst, t0;
-    uint32_t lo, hi;
-};
 
 // windowed extremes (atsc_extremes_windows_dev, atsc_extremes.hip): the aggregates' tiles, pieces and combine passes
 // (DevAggComb) over partials of 2 + 4 k eight-byte words, the record's layout with positions as stream indices: count,
 // nans, k largest entries, k smallest entries, an entry being (value bits, position) and (NaN, ~0) where there is none
 constexpr uint32_t EXT_MAX_K = 16;
-// one tile of k_ext_tiles: slots [lo, hi) of the tile whose slot 0 is scratch[src] and sample t0 of the stream -> partial dst
-struct DevExtTile {
-    uint64_t src, dst, t0;
-    uint32_t lo, hi;
-};
 
 // windowed quantiles (atsc_quantile_windows_dev, atsc_quantile.hip).  The tier of a window is chosen from its length:
 // short (one wavefront, keys in registers), medium (one workgroup, keys in LDS), long (MSD radix select, 8-bit digits)

@@ -7,47 +7,41 @@
 //     n = na + nb; w = (double)nb / (double)n; f = (double)na * w; dx = mxb - mxa; dt = mtb - mta;
 //     mx = mxa + dx * w; mt = mta + dt * w;
 //     M2x = (M2xa + M2xb) + (dx * dx) * f; M2t = (M2ta + M2tb) + (dt * dt) * f; C = (Ca + Cb) + (dx * dt) * f
-// (one rounding per operation: this file is compiled with -ffp-contract=off).  The tree is the aggregate sum's
-// (atsc_aggregate.hip) with + replaced by Merge, the left operand as a.
+// (one rounding per operation: this file is compiled with -ffp-contract=off).  The tree is the tile sum's
+// (tile_lane_sums, atsc_tile_reduce.h) with + replaced by Merge, the left operand as a.
 // One wavefront reduces one tile (lane l holds the virtual lanes l, l + 64, l + 128, l + 192) or one group of 64 tile
 // partials of a window.  No atomics: every partial has one writer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "atsc_device.h"
+#include "atsc_tile_reduce.h"
 
 namespace atsc {
 
 namespace {
 
-// N: the count's type -- 32 bits inside a tile, whose nodes hold at most 2048 samples
-template <class N>
-struct NodeT {
+// the node inside a tile: DevMomPart with a 32-bit count (a tile's nodes hold at most 2048 samples)
+struct Node {
     double mx, m2x, mt, m2t, c;
-    N n;
+    uint32_t n;
 };
-using Node = NodeT<uint32_t>;   // k_mom_tiles
-using WNode = NodeT<uint64_t>;  // k_mom_combine
-
-template <class N>
-__device__ __forceinline__ NodeT<N> node_empty() { return NodeT<N>{0.0, 0.0, 0.0, 0.0, 0.0, 0}; }
 
 // the leaf of sample v at stream position t; ok: inside the window and not NaN
 __device__ __forceinline__ Node node_leaf(double v, double t, bool ok)
 {
-    return ok ? Node{v, 0.0, t, 0.0, 0.0, 1} : node_empty<uint32_t>();
+    return ok ? Node{v, 0.0, t, 0.0, 0.0, 1} : Node{0.0, 0.0, 0.0, 0.0, 0.0, 0};
 }
 
 // Merge(a, b).  EQ: the caller knows na == nb != 0 -- then w = nb / (2 nb) is 0.5 exactly and f = na * 0.5, the bits
-// the divide gives; nothing else differs from the general rule.
-template <bool EQ, class N>
-__device__ __forceinline__ NodeT<N> node_merge(const NodeT<N> &a, const NodeT<N> &b)
+// the divide gives; nothing else differs from the general rule.  ND: Node or DevMomPart.
+template <bool EQ, class ND>
+__device__ __forceinline__ ND node_merge(const ND &a, const ND &b)
 {
-    const N n = a.n + b.n;
+    const decltype(a.n) n = a.n + b.n;
     const double w = EQ ? 0.5 : (double)b.n / (double)n;
     const double f = (double)a.n * w;
     const double dx = b.mx - a.mx, dt = b.mt - a.mt;
-    NodeT<N> r;
+    ND r;
     r.mx = a.mx + dx * w;
     r.mt = a.mt + dt * w;
     r.m2x = (a.m2x + b.m2x) + (dx * dx) * f;
@@ -58,20 +52,7 @@ __device__ __forceinline__ NodeT<N> node_merge(const NodeT<N> &a, const NodeT<N>
     return b.n == 0 ? a : a.n == 0 ? b : r;
 }
 
-template <class N>
-__device__ __forceinline__ NodeT<N> node_shfl_down(const NodeT<N> &a, unsigned off)
-{
-    NodeT<N> o;
-    o.mx = __shfl_down(a.mx, off, 64);
-    o.m2x = __shfl_down(a.m2x, off, 64);
-    o.mt = __shfl_down(a.mt, off, 64);
-    o.m2t = __shfl_down(a.m2t, off, 64);
-    o.c = __shfl_down(a.c, off, 64);
-    o.n = __shfl_down(a.n, off, 64);
-    return o;
-}
-
-// a virtual lane's eight leaves (four 16-byte loads d[q] at slots 512 q + 2 v, positions from t0) into its node
+// a virtual lane's eight leaves (four 16-byte loads d[q] at slots tile_slot(v, q), positions from t0) into its node
 template <bool EQ>
 __device__ __forceinline__ Node lane_node(const double2 (&d)[4], const bool (&ok)[8], double t0)
 {
@@ -88,25 +69,21 @@ __device__ __forceinline__ Node lane_node(const double2 (&d)[4], const bool (&ok
 template <bool EQ>
 __device__ __forceinline__ Node tile_node(const Node (&s)[4])
 {
-    Node a = node_merge<EQ>(node_merge<EQ>(s[0], s[2]), node_merge<EQ>(s[1], s[3]));
-#pragma unroll
-    for (unsigned off = 32; off >= 1; off >>= 1) a = node_merge<EQ>(a, node_shfl_down(a, off));
-    return a;
+    return wave_halve(node_merge<EQ>(node_merge<EQ>(s[0], s[2]), node_merge<EQ>(s[1], s[3])), node_merge<EQ, Node>);
 }
 
 }  // namespace
 
-// One wavefront per DevMomTile: the slots [lo, hi) of the tile at scratch[src], whose slot 0 is sample t0 of the
+// One wavefront per DevPosTile: the slots [lo, hi) of the tile at scratch[src], whose slot 0 is sample t0 of the
 // stream, into part[dst].  A virtual lane's eight leaves are reduced as they are loaded.  Where every one of the
 // wavefront's merges joins two nodes of the same non-zero count (a NaN-free stretch that the window covers), the
 // merges skip the divide behind a wave-uniform test: the same bits, see node_merge.
-__global__ __launch_bounds__(256) void k_mom_tiles(const DevMomTile *__restrict__ tasks, uint32_t n,
+__global__ __launch_bounds__(256) void k_mom_tiles(const DevPosTile *__restrict__ tasks, uint32_t n,
                                                    const double *__restrict__ scratch, DevMomPart *__restrict__ part)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = wave_lane(), i = wave_task();
     if (i >= n) return;
-    const DevMomTile t = tasks[i];
+    const DevPosTile t = tasks[i];
     const double *x = scratch + t.src;
     // positions are exact in f64: a stream index is below 2^53, so (double)t0 + (double)j == (double)(t0 + j)
     const double tb = (double)t.t0;
@@ -120,11 +97,10 @@ __global__ __launch_bounds__(256) void k_mom_tiles(const DevMomTile *__restrict_
         bool all = true;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const uint32_t j = 512u * q + 2u * v;
-            d[q] = make_double2(0.0, 0.0);
-            if (j < t.hi && j + 2u > t.lo) d[q] = *(const double2 *)(x + j);  // 16-byte load; scratch tiles are 16-byte aligned
-            ok[2 * q] = j >= t.lo && j < t.hi && !__builtin_isnan(d[q].x);
-            ok[2 * q + 1] = j + 1u >= t.lo && j + 1u < t.hi && !__builtin_isnan(d[q].y);
+            const uint32_t j = tile_slot(v, q);
+            d[q] = tile_load(x, j, t.lo, t.hi, 0.0);
+            ok[2 * q] = tile_in(j, t.lo, t.hi) && !__builtin_isnan(d[q].x);
+            ok[2 * q + 1] = tile_in(j + 1u, t.lo, t.hi) && !__builtin_isnan(d[q].y);
             all = all && ok[2 * q] && ok[2 * q + 1];
         }
         const double t0 = tb + (double)(2u * v);
@@ -138,30 +114,19 @@ __global__ __launch_bounds__(256) void k_mom_tiles(const DevMomTile *__restrict_
     if (lane == 0) part[t.dst] = DevMomPart{a.mx, a.m2x, a.mt, a.m2t, a.c, a.n};
 }
 
-// One wavefront per DevAggComb: partials j = 64 g .. 64 g + 63 of a window's list (j < n; j == 0 at head, j == n - 1 at
-// tail, else at mid + j) through the pairwise tree (lane l + 2^k into lane l; a missing right operand is the empty
-// node), then into part[dst] or, in the final pass, the window's atsc_window_moments (six 8-byte fields, one per lane):
-// t_mean counted from the window's begin[win], and NaN in the five doubles of a window without a sample.
+// One wavefront per DevAggComb: the group's partials through comb_reduce (a missing right operand is the empty node),
+// then, in the final pass, into the window's atsc_window_moments (six 8-byte fields, one per lane): t_mean counted from
+// the window's begin[win], and NaN in the five doubles of a window without a sample.
 __global__ __launch_bounds__(256) void k_mom_combine(const DevAggComb *__restrict__ tasks, uint32_t n_tasks,
                                                      DevMomPart *__restrict__ part, const uint64_t *__restrict__ begin,
                                                      uint64_t *__restrict__ out)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = wave_lane(), i = wave_task();
     if (i >= n_tasks) return;
     const DevAggComb c = tasks[i];
-    const uint64_t j = 64ull * c.g + lane;
-    WNode a = node_empty<uint64_t>();
-    if (j < c.n) {
-        const DevMomPart p = part[j == 0 ? c.head : j == c.n - 1 ? c.tail : c.mid + j];
-        a = WNode{p.mx, p.m2x, p.mt, p.m2t, p.c, p.n};
-    }
-#pragma unroll
-    for (unsigned off = 1; off < 64; off <<= 1) a = node_merge<false>(a, node_shfl_down(a, off));
-    if (!c.final_) {
-        if (lane == 0) part[c.dst] = DevMomPart{a.mx, a.m2x, a.mt, a.m2t, a.c, a.n};
-        return;
-    }
+    const DevMomPart a =
+        comb_reduce(c, lane, part, DevMomPart{0.0, 0.0, 0.0, 0.0, 0.0, 0}, node_merge<false, DevMomPart>);
+    if (!c.final_) return;
     const uint64_t cnt = __shfl(a.n, 0, 64);
     const double mx = __shfl(a.mx, 0, 64), m2x = __shfl(a.m2x, 0, 64), mt = __shfl(a.mt, 0, 64),
                  m2t = __shfl(a.m2t, 0, 64), cv = __shfl(a.c, 0, 64);
@@ -178,19 +143,15 @@ __global__ __launch_bounds__(256) void k_mom_combine(const DevAggComb *__restric
     }
 }
 
-hipError_t launch_mom_tiles(const DevMomTile *tasks, uint32_t n, const double *scratch, DevMomPart *part, hipStream_t s)
+hipError_t launch_mom_tiles(const DevPosTile *tasks, uint32_t n, const double *scratch, DevMomPart *part, hipStream_t s)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_mom_tiles, dim3((n + 3) / 4), dim3(256), 0, s, tasks, n, scratch, part);
-    return hipGetLastError();
+    return launch_wave_tasks(k_mom_tiles, n, s, tasks, n, scratch, part);
 }
 
 hipError_t launch_mom_combine(const DevAggComb *tasks, uint32_t n, DevMomPart *part, const uint64_t *begin, void *out,
                               hipStream_t s)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_mom_combine, dim3((n + 3) / 4), dim3(256), 0, s, tasks, n, part, begin, (uint64_t *)out);
-    return hipGetLastError();
+    return launch_wave_tasks(k_mom_combine, n, s, tasks, n, part, begin, (uint64_t *)out);
 }
 
 }  // namespace atsc

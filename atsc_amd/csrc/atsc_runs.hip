@@ -7,45 +7,40 @@
 // holds.  The nine integers form an associative, order-dependent monoid (run_merge below, the header's merge rule on
 // absolute stream positions): a run that crosses a tile, a combine group or a piece of the scratch is joined by the merge
 // itself, so no sample is carried from one piece to the next.  The term of an inside sample, fabs(x - limit), sits at the
-// sample's own slot, every other slot holds -0.0, and the sum goes through the aggregate sum's tree (atsc_aggregate.hip)
-// unchanged.
+// sample's own slot, every other slot holds -0.0, and the sum goes through the tile sum's tree (tile_lane_sums,
+// atsc_tile_reduce.h) unchanged.
 // One wavefront reduces one tile or one group of 64 tile partials of a window.  No atomics: every partial has one writer.
 //
-// The tile kernel keeps k_agg_tiles' 16-byte loads and slot-to-lane mapping for the sum.  That mapping interleaves the
-// slots, and the runs need them in stream order: the 64 lanes of one load step hold 128 contiguous slots, so two ballots
-// (the loads' first halves, their second halves) give those slots' inside bits as wave-uniform masks; lane g < 32 keeps
-// the halves that belong to slots [64 g, 64 g + 64), interleaves them once into a 64-bit word, reads the word's node off it
-// with popcount, count-trailing / leading-zeros and six shift-and steps, and a five-step shuffle tree merges the 32 nodes
-// in order.
+// The tile kernel keeps the 16-byte loads and slot-to-lane mapping of atsc_tile_reduce.h for the sum.  That mapping
+// interleaves the slots, and the runs need them in stream order: the 64 lanes of one load step hold 128 contiguous
+// slots, so two ballots (the loads' first halves, their second halves) give those slots' inside bits as wave-uniform
+// masks; lane g < 32 keeps the halves that belong to slots [64 g, 64 g + 64), interleaves them once into a 64-bit word,
+// reads the word's node off it with popcount, count-trailing / leading-zeros and six shift-and steps, and a five-step
+// shuffle tree merges the 32 nodes in order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "atsc_device.h"
+#include "atsc_tile_reduce.h"
 
 namespace atsc {
 
 namespace {
 
-// The node of a stretch of the stream; T: uint32_t inside a tile (positions count from the tile's slot 0, NONE = ~0u),
-// uint64_t between tiles (stream index, NONE = ~0ull).  The empty node: all zero, the three positions NONE.
-template <class T>
+// The node of a stretch of the stream inside a tile: DevRunPart's nine integers in 32 bits, positions counted from the
+// tile's slot 0, NONE = ~0u.  The empty node, here and between tiles: all zero, the three positions NONE.
 struct Run {
-    T samples, inside, runs, longest, longest_at, first_at, last_at, head, tail;
+    uint32_t samples, inside, runs, longest, longest_at, first_at, last_at, head, tail;
 };
-
-template <class T>
-__device__ __forceinline__ Run<T> run_empty()
-{
-    const T none = ~(T)0;
-    return Run<T>{0, 0, 0, 0, none, none, none, 0, 0};
-}
+constexpr Run RUN_EMPTY{0, 0, 0, 0, ~0u, ~0u, ~0u, 0, 0};
 
 // a followed by b.  The run that joins them starts tail(a) samples in front of b's first sample, which is b's first inside
 // sample when head(b) != 0.  Strict comparisons: of equal runs the earliest stays.  Either may be the empty node.
-template <class T>
-__device__ __forceinline__ Run<T> run_merge(const Run<T> &a, const Run<T> &b)
+// R: Run, or DevRunPart, whose nine integers are these with stream indices for positions.
+template <class R>
+__device__ __forceinline__ R run_merge(const R &a, const R &b)
 {
-    Run<T> r;
+    using T = decltype(a.samples);
+    R r = a;
     const bool join = a.tail != 0 && b.head != 0;
     r.samples = a.samples + b.samples;
     r.inside = a.inside + b.inside;
@@ -63,20 +58,12 @@ __device__ __forceinline__ Run<T> run_merge(const Run<T> &a, const Run<T> &b)
     return r;
 }
 
-template <class T>
-__device__ __forceinline__ Run<T> run_shfl_down(const Run<T> &a, unsigned off)
+// two partials: the nodes, and the sums' terms left operand first
+__device__ __forceinline__ DevRunPart part_merge(const DevRunPart &a, const DevRunPart &b)
 {
-    Run<T> o;
-    o.samples = __shfl_down(a.samples, off, 64);
-    o.inside = __shfl_down(a.inside, off, 64);
-    o.runs = __shfl_down(a.runs, off, 64);
-    o.longest = __shfl_down(a.longest, off, 64);
-    o.longest_at = __shfl_down(a.longest_at, off, 64);
-    o.first_at = __shfl_down(a.first_at, off, 64);
-    o.last_at = __shfl_down(a.last_at, off, 64);
-    o.head = __shfl_down(a.head, off, 64);
-    o.tail = __shfl_down(a.tail, off, 64);
-    return o;
+    DevRunPart r = run_merge(a, b);
+    r.excess = a.excess + b.excess;
+    return r;
 }
 
 // bit i of x to bit 2 i
@@ -93,9 +80,9 @@ __device__ __forceinline__ uint64_t spread_bits(uint32_t x)
 
 // The node of 64 slots whose slot 0 is slot `base` of the tile: bit i of m is set iff slot base + i lies in the window and
 // is inside; the window holds the slots [vlo, vhi) of the word (vlo <= vhi <= 64), and m has no bit outside them.
-__device__ __forceinline__ Run<uint32_t> word_node(uint64_t m, uint32_t vlo, uint32_t vhi, uint32_t base)
+__device__ __forceinline__ Run word_node(uint64_t m, uint32_t vlo, uint32_t vhi, uint32_t base)
 {
-    Run<uint32_t> r = run_empty<uint32_t>();
+    Run r = RUN_EMPTY;
     if (vhi <= vlo) return r;
     r.samples = vhi - vlo;
     if (m == 0) return r;
@@ -131,26 +118,27 @@ __device__ __forceinline__ Run<uint32_t> word_node(uint64_t m, uint32_t vlo, uin
 
 }  // namespace
 
-// One wavefront per DevRunTile: the node of the slots [lo, hi) of the tile at scratch[src], whose slot 0 is sample t0 of
+// One wavefront per DevPosTile: the node of the slots [lo, hi) of the tile at scratch[src], whose slot 0 is sample t0 of
 // the stream, into part[dst]; a slot outside [lo, hi) is the empty node.  op, limit: the call's condition.
-__global__ __launch_bounds__(256) void k_run_tiles(const DevRunTile *__restrict__ tasks, uint32_t n,
+__global__ __launch_bounds__(256) void k_run_tiles(const DevPosTile *__restrict__ tasks, uint32_t n,
                                                    const double *__restrict__ scratch, int op, double limit,
                                                    DevRunPart *__restrict__ part)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = wave_lane(), i = wave_task();
     if (i >= n) return;
-    const DevRunTile t = tasks[i];
+    const DevPosTile t = tasks[i];
     const double *x = scratch + t.src;
     // x OP limit from the three ordered comparisons, each false on NaN
     const bool want_gt = op == ATSC_RUNS_GT || op == ATSC_RUNS_GE || op == ATSC_RUNS_NE;
     const bool want_lt = op == ATSC_RUNS_LT || op == ATSC_RUNS_LE || op == ATSC_RUNS_NE;
     const bool want_eq = op == ATSC_RUNS_GE || op == ATSC_RUNS_LE || op == ATSC_RUNS_EQ;
     uint32_t ev = 0, od = 0;  // lane g < 32: the inside bits of the even and of the odd slots of [64 g, 64 g + 64)
-    // The virtual lanes go two at a time, (lane, lane + 128) and then (lane + 64, lane + 192), in a loop that is not
-    // unrolled, as in k_dlt_tiles: the halving tree's first step inside the lane, s[v] + s[v + 128], closes each trip, its
-    // second step joins the two trips.  Unrolled four times the 16 loads' predicates and the 32 ballots spill SGPRs.
-    double ex = -0.0;
+    // The tile sum in the order tile_lane_sums (atsc_tile_reduce.h) defines, written out: through that helper this
+    // kernel comes out with either 14 % more instructions or without its wave-uniform branches on the condition.  The
+    // virtual lanes go two at a time, (lane, lane + 128) and then (lane + 64, lane + 192), in a loop that is not
+    // unrolled, as in k_dlt_tiles: the halving tree's first step inside the lane, s[v] + s[v + 128], closes each trip,
+    // its second step joins the two trips.  Unrolled four times the 16 loads' predicates and the 32 ballots spill SGPRs.
+    double ex[1] = {-0.0};
 #pragma unroll 1
     for (uint32_t kk = 0; kk < 2; ++kk) {
         double s[2];
@@ -160,12 +148,11 @@ __global__ __launch_bounds__(256) void k_run_tiles(const DevRunTile *__restrict_
             double p[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const uint32_t j = 512u * q + 2u * v;
-                double2 d = make_double2(-0.0, -0.0);
-                if (j < t.hi && j + 2u > t.lo) d = *(const double2 *)(x + j);  // 16-byte load; scratch tiles are 16-byte aligned
-                const bool in0 = j >= t.lo && j < t.hi &&
+                const uint32_t j = tile_slot(v, q);
+                const double2 d = tile_load(x, j, t.lo, t.hi, -0.0);
+                const bool in0 = tile_in(j, t.lo, t.hi) &&
                                  ((want_gt && d.x > limit) || (want_lt && d.x < limit) || (want_eq && d.x == limit));
-                const bool in1 = j + 1u >= t.lo && j + 1u < t.hi &&
+                const bool in1 = tile_in(j + 1u, t.lo, t.hi) &&
                                  ((want_gt && d.y > limit) || (want_lt && d.y < limit) || (want_eq && d.y == limit));
                 const double a = in0 ? __builtin_fabs(d.x - limit) : -0.0;
                 const double b = in1 ? __builtin_fabs(d.y - limit) : -0.0;
@@ -180,23 +167,19 @@ __global__ __launch_bounds__(256) void k_run_tiles(const DevRunTile *__restrict_
             }
             s[e] = (p[0] + p[1]) + (p[2] + p[3]);
         }
-        // halving tree over the 256 virtual lanes, h = 128 and 64: (s[l] + s[l + 128]) + (s[l + 64] + s[l + 192])
         const double h = s[0] + s[1];
-        ex = kk ? ex + h : h;
+        ex[0] = kk ? ex[0] + h : h;
     }
-    // then h = 32 .. 1 across the wavefront
-#pragma unroll
-    for (unsigned off = 32; off >= 1; off >>= 1) ex = ex + __shfl_down(ex, off, 64);
+    const double excess = wave_halve(ex[0], [](double a, double b) { return a + b; });
     // lane g < 32: the node of the slots [64 g, 64 g + 64); then lane l + 2^k into lane l, the left operand first
-    Run<uint32_t> r = run_empty<uint32_t>();
+    Run r = RUN_EMPTY;
     if (lane < 32u) {
         const uint32_t base = 64u * lane;
         const uint32_t vlo = t.lo > base ? (t.lo - base < 64u ? t.lo - base : 64u) : 0u;
         const uint32_t vhi = t.hi > base ? (t.hi - base < 64u ? t.hi - base : 64u) : 0u;
         r = word_node(spread_bits(ev) | (spread_bits(od) << 1), vlo, vhi, base);
     }
-#pragma unroll
-    for (unsigned off = 1; off < 32; off <<= 1) r = run_merge(r, run_shfl_down(r, off));
+    r = wave_pairwise<32>(r, run_merge<Run>);
     if (lane == 0) {
         const uint64_t none = ~0ull;
         DevRunPart o;
@@ -209,60 +192,31 @@ __global__ __launch_bounds__(256) void k_run_tiles(const DevRunTile *__restrict_
         o.last_at = r.inside ? t.t0 + r.last_at : none;
         o.head = r.head;
         o.tail = r.tail;
-        o.excess = ex;
+        o.excess = excess;
         part[t.dst] = o;
     }
 }
 
-// One wavefront per DevAggComb: partials j = 64 g .. 64 g + 63 of a window's list (j < n; j == 0 at head, j == n - 1 at
-// tail, else at mid + j) through the pairwise tree (lane l + 2^k into lane l, the left operand first; a missing right
-// operand is the empty node and -0.0), then into part[dst] or, in the final pass, the window's atsc_window_runs (ten
-// 8-byte fields, one per lane): the three positions counted from the window's begin[win], excess +0.0 without a term.
+// One wavefront per DevAggComb: the group's partials through comb_reduce (a missing right operand is the empty node and
+// -0.0), then, in the final pass, into the window's atsc_window_runs (ten 8-byte fields, one per lane): the three
+// positions counted from the window's begin[win], excess +0.0 without a term.
 __global__ __launch_bounds__(256) void k_run_combine(const DevAggComb *__restrict__ tasks, uint32_t n_tasks,
                                                      DevRunPart *__restrict__ part, const uint64_t *__restrict__ begin,
                                                      uint64_t *__restrict__ out)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = wave_lane(), i = wave_task();
     if (i >= n_tasks) return;
     const DevAggComb c = tasks[i];
-    const uint64_t j = 64ull * c.g + lane;
-    Run<uint64_t> a = run_empty<uint64_t>();
-    double ex = -0.0;
-    if (j < c.n) {
-        const DevRunPart p = part[j == 0 ? c.head : j == c.n - 1 ? c.tail : c.mid + j];
-        a = Run<uint64_t>{p.samples, p.inside, p.runs, p.longest, p.longest_at, p.first_at, p.last_at, p.head, p.tail};
-        ex = p.excess;
-    }
-#pragma unroll
-    for (unsigned off = 1; off < 64; off <<= 1) {
-        a = run_merge(a, run_shfl_down(a, off));
-        ex = ex + __shfl_down(ex, off, 64);
-    }
-    if (!c.final_) {
-        if (lane == 0) {
-            DevRunPart o;
-            o.samples = a.samples;
-            o.inside = a.inside;
-            o.runs = a.runs;
-            o.longest = a.longest;
-            o.longest_at = a.longest_at;
-            o.first_at = a.first_at;
-            o.last_at = a.last_at;
-            o.head = a.head;
-            o.tail = a.tail;
-            o.excess = ex;
-            part[c.dst] = o;
-        }
-        return;
-    }
     const uint64_t none = ~0ull;
+    const DevRunPart a =
+        comb_reduce(c, lane, part, DevRunPart{0, 0, 0, 0, none, none, none, 0, 0, -0.0}, part_merge);
+    if (!c.final_) return;
     const uint64_t b0 = c.n ? begin[c.win] : 0;
     const uint64_t samples = __shfl(a.samples, 0, 64), inside = __shfl(a.inside, 0, 64), runs = __shfl(a.runs, 0, 64),
                    longest = __shfl(a.longest, 0, 64), longest_at = __shfl(a.longest_at, 0, 64),
                    first_at = __shfl(a.first_at, 0, 64), last_at = __shfl(a.last_at, 0, 64),
                    head = __shfl(a.head, 0, 64), tail = __shfl(a.tail, 0, 64);
-    const double excess = __shfl(ex, 0, 64);
+    const double excess = __shfl(a.excess, 0, 64);
     if (lane < 10) {
         uint64_t w;
         switch (lane) {
@@ -281,20 +235,16 @@ __global__ __launch_bounds__(256) void k_run_combine(const DevAggComb *__restric
     }
 }
 
-hipError_t launch_run_tiles(const DevRunTile *tasks, uint32_t n, const double *scratch, int op, double limit,
+hipError_t launch_run_tiles(const DevPosTile *tasks, uint32_t n, const double *scratch, int op, double limit,
                             DevRunPart *part, hipStream_t s)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_run_tiles, dim3((n + 3) / 4), dim3(256), 0, s, tasks, n, scratch, op, limit, part);
-    return hipGetLastError();
+    return launch_wave_tasks(k_run_tiles, n, s, tasks, n, scratch, op, limit, part);
 }
 
 hipError_t launch_run_combine(const DevAggComb *tasks, uint32_t n, DevRunPart *part, const uint64_t *begin, void *out,
                               hipStream_t s)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_run_combine, dim3((n + 3) / 4), dim3(256), 0, s, tasks, n, part, begin, (uint64_t *)out);
-    return hipGetLastError();
+    return launch_wave_tasks(k_run_combine, n, s, tasks, n, part, begin, (uint64_t *)out);
 }
 
 }  // namespace atsc

@@ -45,7 +45,7 @@ __attribute__((weak)) hipError_t launch_hst_chunk(const DevHistTask *tasks, uint
                                                   const double *edges, uint32_t n_edges, int closed, uint64_t *out,
                                                   hipStream_t s);
 // the windowed moments' reduce kernels (atsc_moments.hip; weak for the same reason)
-__attribute__((weak)) hipError_t launch_mom_tiles(const DevMomTile *tasks, uint32_t n, const double *scratch,
+__attribute__((weak)) hipError_t launch_mom_tiles(const DevPosTile *tasks, uint32_t n, const double *scratch,
                                                   DevMomPart *part, hipStream_t s);
 __attribute__((weak)) hipError_t launch_mom_combine(const DevAggComb *tasks, uint32_t n, DevMomPart *part,
                                                     const uint64_t *begin, void *out, hipStream_t s);
@@ -55,12 +55,12 @@ __attribute__((weak)) hipError_t launch_dlt_tiles(const DevDltTile *tasks, uint3
 __attribute__((weak)) hipError_t launch_dlt_combine(const DevAggComb *tasks, uint32_t n, DevDltPart *part, void *out,
                                                     hipStream_t s);
 // the windowed runs' reduce kernels (atsc_runs.hip; weak for the same reason)
-__attribute__((weak)) hipError_t launch_run_tiles(const DevRunTile *tasks, uint32_t n, const double *scratch, int op,
+__attribute__((weak)) hipError_t launch_run_tiles(const DevPosTile *tasks, uint32_t n, const double *scratch, int op,
                                                   double limit, DevRunPart *part, hipStream_t s);
 __attribute__((weak)) hipError_t launch_run_combine(const DevAggComb *tasks, uint32_t n, DevRunPart *part,
                                                     const uint64_t *begin, void *out, hipStream_t s);
 // the windowed extremes' selection kernels (atsc_extremes.hip; weak for the same reason)
-__attribute__((weak)) hipError_t launch_ext_tiles(const DevExtTile *tasks, uint32_t n, const double *scratch, uint32_t k,
+__attribute__((weak)) hipError_t launch_ext_tiles(const DevPosTile *tasks, uint32_t n, const double *scratch, uint32_t k,
                                                   void *part, hipStream_t s);
 __attribute__((weak)) hipError_t launch_ext_combine(const DevAggComb *tasks, uint32_t n, uint32_t k, void *part,
                                                     const uint64_t *begin, void *out, hipStream_t s);
@@ -704,8 +704,11 @@ struct AggQuery {
         return reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
     }
 };
+// the tile task of the moments, the runs and the extremes, whose kernels take the tile's place in the stream
+static DevPosTile pos_tile(const DevAggTile &t, uint64_t k) { return DevPosTile{t.src, t.dst, k * AGG_TILE, t.lo, t.hi}; }
+
 struct MomQuery {
-    using Tile = DevMomTile;
+    using Tile = DevPosTile;
     static constexpr const char *CALL = "moments_windows", *RES_NAME = "d_out", *NO_KERNELS = "no moments kernels",
                                 *TILES = "launch k_mom_tiles", *COMBINE = "launch k_mom_combine";
     static constexpr size_t PART = sizeof(DevMomPart);
@@ -715,7 +718,7 @@ struct MomQuery {
     static const DecodeCaller &who() { return BY_MOMENTS; }
     static bool have() { return launch_mom_tiles && launch_mom_combine; }
     static constexpr bool CARRY = false;
-    static Tile tile(const DevAggTile &t, uint64_t k) { return Tile{t.src, t.dst, k * AGG_TILE, t.lo, t.hi}; }
+    static Tile tile(const DevAggTile &t, uint64_t k) { return pos_tile(t, k); }
     static bool carried(const Tile &) { return false; }
     static hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s)
     {
@@ -798,7 +801,7 @@ static void run_empty_record(atsc_window_runs &r)
 // members, which reduce_dev hands to tiles() by calling it on that object.  No carry: the merge joins a run across two
 // tiles, whichever pieces they lie in.
 struct RunQuery {
-    using Tile = DevRunTile;
+    using Tile = DevPosTile;
     static constexpr const char *CALL = "runs_windows", *RES_NAME = "d_out", *NO_KERNELS = "no runs kernels",
                                 *TILES = "launch k_run_tiles", *COMBINE = "launch k_run_combine";
     static constexpr size_t PART = sizeof(DevRunPart);
@@ -810,7 +813,7 @@ struct RunQuery {
     double limit;
     static const DecodeCaller &who() { return BY_RUNS; }
     static bool have() { return launch_run_tiles && launch_run_combine; }
-    static Tile tile(const DevAggTile &t, uint64_t k) { return Tile{t.src, t.dst, k * AGG_TILE, t.lo, t.hi}; }
+    static Tile tile(const DevAggTile &t, uint64_t k) { return pos_tile(t, k); }
     static bool carried(const Tile &) { return false; }
     hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s) const
     {
@@ -855,7 +858,7 @@ static void ext_empty_record(void *rec, uint32_t k)
 // partials, which have the record's layout (2 + 4 k words) with positions as stream indices, so that a shared mid
 // tile's partial serves every window that shares it; the final combine pass subtracts the window's begin.  No carry.
 struct ExtQuery {
-    using Tile = DevExtTile;
+    using Tile = DevPosTile;
     static constexpr const char *CALL = "extremes_windows", *RES_NAME = "d_out", *NO_KERNELS = "no extremes kernels",
                                 *TILES = "launch k_ext_tiles", *COMBINE = "launch k_ext_combine";
     static constexpr bool SIDE_BEGINS = true;
@@ -865,7 +868,7 @@ struct ExtQuery {
     size_t part() const { return ATSC_EXTREMES_BYTES(k); }
     static const DecodeCaller &who() { return BY_EXTREMES; }
     static bool have() { return launch_ext_tiles && launch_ext_combine; }
-    static Tile tile(const DevAggTile &t, uint64_t kt) { return Tile{t.src, t.dst, kt * AGG_TILE, t.lo, t.hi}; }
+    static Tile tile(const DevAggTile &t, uint64_t kt) { return pos_tile(t, kt); }
     static bool carried(const Tile &) { return false; }
     hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s) const
     {

@@ -236,6 +236,34 @@ def test_placed_patterns(A, ctx, torch, placed):
     assert sm((31 * T + 700, 6 * T))[:4] == [(-9.0, t * T + 1000 + t - 31 * T - 700) for t in (31, 32, 33, 34)]
 
 
+def test_64_and_66_tiles_in_one_window(A, ctx, torch):
+    """64 partials fill one combine group exactly, 65 and 66 need a second pass: windows of 64 and 66 tiles (135168
+    samples) and their neighbours, on tile multiples and on odd slots, under the default budget and under the least one,
+    whose pieces of 32 tiles cut every one of them"""
+    nan = float("nan")
+    n = 35 * 4096
+    rng = np.random.default_rng(644)
+    # decoding rounds to the fifth decimal, so the samples are placed on it; a sum of these depends on its order
+    x = np.round(rng.normal(0, 1, n) * 10.0 ** rng.integers(-3, 7, n), 5)
+    x[rng.integers(0, n, 300)] = nan
+    x[rng.integers(0, n, 500)] = 9.0e7   # the largest value many times over, in most tiles: the earliest win
+    x[rng.integers(0, n, 500)] = -9.0e7
+    recs = b"".join(_idw_record(x[k:k + 4096].tolist()) for k in range(0, n, 4096))
+    full = ctx.decompress_host(recs)
+    assert np.array_equal(np.isnan(full), np.isnan(x)) and np.array_equal(full[~np.isnan(x)], x[~np.isnan(x)])
+    wins = [(2 * T, 64 * T), (2 * T - 1, 64 * T + 2), (T, 66 * T), (2 * T + 1, 66 * T - 1), (2 * T, 64 * T - 1),
+            (2 * T + 1, 64 * T), (0, n), (T + 7, 65 * T), (3 * T, 64 * T), (2 * T, 65 * T), (5, 64 * T)]
+    try:
+        for budget in (0, 1):
+            ctx.set_aggregate_scratch(budget)
+            for k in (1, 4, 16):
+                got = _host(ctx, recs, wins, k)
+                _check(full, wins, got, k, "64 tiles, budget %d" % budget)
+                assert _equal(_dev(A, ctx, torch, recs, wins, k), got), (budget, k)
+    finally:
+        ctx.set_aggregate_scratch(0)
+
+
 def test_k_at_the_edges(A, ctx, torch, placed):
     recs, full = placed
     wins = [(14 * T - 100, T + 200), (0, len(full)), (27 * T + 100, 8), (16 * T, T), (25 * T + 10, 10), (3, 0)]

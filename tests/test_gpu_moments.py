@@ -246,6 +246,31 @@ def test_budgets_pieces_and_plan_reuse(A, ctx, torch, mixed):
     assert _equal(_host(ctx, mixed, probe), alone)  # repeated
 
 
+def test_64_and_66_tiles_in_one_window(A, ctx, torch):
+    """64 partials fill one combine group exactly, 65 and 66 need a second pass: windows of 64 and 66 tiles (135168
+    samples) and their neighbours, on tile multiples and on odd slots, under the default budget and under the least one,
+    whose pieces of 32 tiles cut every one of them"""
+    nan = float("nan")
+    n = 35 * 4096
+    rng = np.random.default_rng(642)
+    # decoding rounds to the fifth decimal, so the samples are placed on it; a sum of these depends on its order
+    x = np.round(rng.normal(0, 1, n) * 10.0 ** rng.integers(-3, 7, n), 5)
+    x[rng.integers(0, n, 300)] = nan
+    recs = b"".join(_idw_record(x[k:k + 4096].tolist()) for k in range(0, n, 4096))
+    full = ctx.decompress_host(recs)
+    assert np.array_equal(np.isnan(full), np.isnan(x)) and np.array_equal(full[~np.isnan(x)], x[~np.isnan(x)])
+    wins = [(2 * T, 64 * T), (2 * T - 1, 64 * T + 2), (T, 66 * T), (2 * T + 1, 66 * T - 1), (2 * T, 64 * T - 1),
+            (2 * T + 1, 64 * T), (0, n), (T + 7, 65 * T), (3 * T, 64 * T), (2 * T, 65 * T), (5, 64 * T)]
+    try:
+        for budget in (0, 1):
+            ctx.set_aggregate_scratch(budget)
+            got = _host(ctx, recs, wins)
+            _check(full, wins, got, "64 tiles, budget %d" % budget)
+            assert _equal(_dev(A, ctx, torch, recs, wins), got), budget
+    finally:
+        ctx.set_aggregate_scratch(0)
+
+
 def test_non_finite_values(A, ctx, torch):
     nan, inf = float("nan"), float("inf")
     parts = [(1.0, 3), (nan, 5), (-0.0, 2), (2.5, 4), (nan, 3000), (-7.0, 2), (inf, 3), (1.0, 1), (-inf, 2), (nan, 1),
