@@ -10,6 +10,8 @@ from .capi import RUNS_EQ, RUNS_GE, RUNS_GT, RUNS_LE, RUNS_LT, RUNS_NE, RUNS_NON
 from .capi import EXTREMES_MAX_K, EXTREMES_NONE  # noqa: F401
 from .engine import EXTREME, extremes_merge, window_extremes_dtype  # noqa: F401
 from .stream import extremes_data_windows  # noqa: F401
+from .engine import SELECTED, select_bytes  # noqa: F401
+from .stream import select_data_windows  # noqa: F401
 from .engine import (WINDOW_DELTA, WINDOW_DELTA_FIT, WINDOW_FIT, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, Context, DPlan, Plan,  # noqa: F401
                      bro_find_window, bro_open, bro_prefix, bucket_windows, chunk_sizes, clean_data, delta_derive,
                      histogram_edges_uniform, moments_fit, runs_merge)

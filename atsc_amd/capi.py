@@ -115,6 +115,10 @@ SIGNATURES = {
     "atsc_extremes_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp, _vp]),
     "atsc_extremes_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp]),
     "atsc_extremes_merge": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp]),
+    "atsc_select_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double, C.c_uint64, _vp,
+                                          _vp]),
+    "atsc_select_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double,
+                                      C.c_uint64, _vp]),
     "atsc_quantile_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _vp,
                                             _vp]),
     "atsc_quantile_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p,
@@ -139,6 +143,7 @@ SIGNATURES = {
     "atsc_stream_delta_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_runs_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double, _vp]),
     "atsc_stream_extremes_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp]),
+    "atsc_stream_select_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double, C.c_uint64, _vp]),
     "atsc_stream_quantile_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _f64p]),
     "atsc_stream_histogram_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _u64p]),
     "atsc_free": (None, [_vp]),

@@ -3,7 +3,8 @@
 //
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
-//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K]]]
+//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K]]
+//        [--where OP:LIMIT]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -62,6 +63,9 @@ void usage()
             "                                 where they are, as the last columns: nans, max1, max1_at .. maxK, maxK_at, min1,\n"
             "                                 min1_at .. minK, minK_at (equal values earliest first; *_at the sample's offset\n"
             "                                 in the bucket; both cells empty where the bucket has fewer samples)\n"
+            "      --where <OP:LIMIT>         with -u --samples, without --buckets: write the window's samples with value OP LIMIT\n"
+            "                                 (as --runs) to .sel.csv instead of the .wbro: sample,value, one row per selected\n"
+            "                                 sample, sample its index in the stream\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -131,6 +135,17 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
             if (!rc) rc = write_buckets(ctx, path, a, bro, len, a.window ? a.win_begin : 0, a.window ? a.win_count : ns);
             atsc_free(bro);
             return rc;
+        }
+        if (a.q.have_where) {  // (with --samples) the window's selected samples, no .wbro
+            std::vector<atsc_selected> rows;
+            rc = atsc_bro_open(bro, len, nullptr, nullptr);
+            if (!rc) rc = where_select(ctx, bro, len, a.q, a.win_begin, a.win_count, rows);
+            atsc_free(bro);
+            if (rc) return rc;
+            const uint64_t b0 = a.win_begin;
+            return where_write(with_ext(path, "sel.csv"), "sample", rows, [b0](uint64_t at) { return std::to_string(b0 + at); })
+                       ? ATSC_OK
+                       : ATSC_E_IO;
         }
         double *out = nullptr;
         uint64_t n = 0;
@@ -262,6 +277,7 @@ int main(int argc, char **argv)
     if (a.window && !a.uncompress) { fprintf(stderr, "error: '--samples' needs '-u'\n"); return 2; }
     if (a.buckets && !a.uncompress) { fprintf(stderr, "error: '--buckets' needs '-u'\n"); return 2; }
     if (!bucket_options_complete(a.q, "--buckets", a.buckets != 0)) return 2;
+    if (!where_option_complete(a.q, "--samples", a.window, "--buckets", a.buckets != 0)) return 2;
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) { fprintf(stderr, "[ERROR] %s: No such file or directory\n", a.input.c_str()); return 1; }
     atsc_ctx *ctx = nullptr;

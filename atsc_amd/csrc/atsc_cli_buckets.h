@@ -1,6 +1,7 @@
 // atsc_cli_buckets.h -- what the two command lines (atsc_cli.cpp, csv_compressor_cli.cpp) share: the small text helpers
 // and the bucket queries behind `atsc -u --buckets N` and `csv-compressor -u --from --to --step S`: their options, the
-// usage errors, the calls over the buckets and the columns of the .agg.csv.  The two differ in the row's first cell,
+// usage errors, the calls over the buckets and the columns of the .agg.csv; and `--where OP:LIMIT`, the selected samples
+// of the window itself into a .sel.csv (the end of this file).  The two differ in the row's first cell,
 // in how a failure is reported and in how a position inside a bucket is written: the three run positions, which the
 // caller hands in, and the extremes' positions, which csv-compressor rewrites as times (bucket_extreme_places).
 #pragma once
@@ -62,6 +63,9 @@ struct BucketOptions {
     int runs_op = ATSC_RUNS_GT;
     double runs_limit = 0.0;
     int extremes = 0;  // --extremes K: nans,max1,max1_at,..,maxK,maxK_at,min1,min1_at,..,minK,minK_at
+    bool have_where = false;  // --where OP:LIMIT: no bucket query; the window's selected samples into .sel.csv
+    int where_op = ATSC_RUNS_GT;
+    double where_limit = 0.0;
 };
 
 // --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
@@ -192,6 +196,12 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             return 2;
         }
         o.have_runs = true;
+    } else if (value("--where")) {
+        if (!parse_runs(v, o.where_op, o.where_limit)) {
+            fprintf(stderr, "error: invalid value '%s': '--where' wants OP:LIMIT (OP: gt ge lt le eq ne)\n", v.c_str());
+            return 2;
+        }
+        o.have_where = true;
     } else if (value("--extremes")) {
         if (!parse_int(v, 1, ATSC_EXTREMES_MAX_K, o.extremes)) {
             fprintf(stderr, "error: invalid value '%s' for '--extremes': expected 1..=%d\n", v.c_str(), (int)ATSC_EXTREMES_MAX_K);
@@ -223,6 +233,22 @@ bool bucket_options_complete(const BucketOptions &o, const char *bucketing, bool
             fprintf(stderr, "error: '%s' needs '%s'\n", t.name, t.needs);
             return false;
         }
+    return true;
+}
+
+// --where goes with the option that names the window (window: "--samples", or "--from' and '--to"; windowed: whether it
+// was there) and without the one that cuts buckets.  false: a usage error, reported on stderr.
+bool where_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
+{
+    if (!o.have_where) return true;
+    if (!windowed) {
+        fprintf(stderr, "error: '--where' needs '%s'\n", window);
+        return false;
+    }
+    if (bucketed) {
+        fprintf(stderr, "error: '--where' cannot be used with '%s'\n", bucketing);
+        return false;
+    }
     return true;
 }
 
@@ -365,6 +391,31 @@ void bucket_row(FILE *f, const std::string &first, const BucketOptions &o, const
         }
     }
     fprintf(f, "\n");
+}
+
+// --where: the samples of [begin, begin + count) of a .bro image that meet the condition, in stream order; cap is the
+// window's sample count, so nothing is cut off.
+int where_select(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
+                 std::vector<atsc_selected> &rows)
+{
+    std::vector<uint64_t> block(ATSC_SELECT_BYTES(1, count) / 8);
+    const int rc = atsc_select_windows(ctx, bro + 9, len - 9, 1, 1, &begin, &count, o.where_op, o.where_limit, count, block.data());
+    if (rc) return rc;
+    const atsc_selected *e = (const atsc_selected *)(block.data() + 2);
+    rows.assign(e, e + block[1]);
+    return ATSC_OK;
+}
+
+// the .sel.csv: `first`,value and one row per selected sample; place(at): the first cell of the sample at offset `at` of
+// the window; values as the .agg.csv writes them.  false: the file could not be written.
+template <class Place>
+bool where_write(const std::string &path, const char *first, const std::vector<atsc_selected> &rows, Place place)
+{
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return false;
+    fprintf(f, "%s,value\n", first);
+    for (const atsc_selected &r : rows) fprintf(f, "%s,%s\n", place(r.at).c_str(), debug_f64(r.value).c_str());
+    return fclose(f) == 0;
 }
 
 }  // namespace

@@ -293,6 +293,28 @@ struct DevHistTask {
     uint32_t len, win;
 };
 
+// windowed select (atsc_select_windows_dev, atsc_select.hip): count, scan, ordered write.  A non-empty window is cut into
+// tasks of at most SEL_TASK consecutive samples of one piece of the scratch; a task's slot is its place in (window,
+// position) order, whatever piece it lies in, so the scanned counts lie in result order.
+constexpr uint32_t SEL_TASK = 2048;        // samples per task: one wavefront, 16 load steps of 128 slots
+constexpr uint32_t SEL_SCAN_BLOCK = 2048;  // counts per workgroup of the scan: 256 threads, eight each
+// one task: samples scratch[src, src + len), the first of them `at` samples behind its window's begin -> cnt[slot], and
+// the entries from pre[slot] on
+struct DevSelTask {
+    uint64_t src, at;
+    uint32_t len, slot;
+};
+// words of block sums above the first level of a scan over m values: one per block of each level that has several
+static inline uint64_t sel_scan_sums(uint64_t m)
+{
+    uint64_t words = 0;
+    while (m > SEL_SCAN_BLOCK) {
+        m = (m + SEL_SCAN_BLOCK - 1) / SEL_SCAN_BLOCK;
+        words += m;
+    }
+    return words;
+}
+
 static inline uint32_t varint_len_u64(uint64_t v)
 {
     return v < 251 ? 1u : v < (1ull << 16) ? 3u : v < (1ull << 32) ? 5u : 9u;

@@ -1,5 +1,5 @@
-// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, quantiles and histograms
-// of ranges of the decoded stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
+// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, quantiles, histograms
+// and selected samples of ranges of the decoded stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
@@ -10,6 +10,7 @@
 #include <cstring>
 #include <limits>
 #include <numeric>
+#include <type_traits>
 
 #include "atsc_host_private.h"
 
@@ -64,6 +65,15 @@ __attribute__((weak)) hipError_t launch_ext_tiles(const DevPosTile *tasks, uint3
                                                   void *part, hipStream_t s);
 __attribute__((weak)) hipError_t launch_ext_combine(const DevAggComb *tasks, uint32_t n, uint32_t k, void *part,
                                                     const uint64_t *begin, void *out, hipStream_t s);
+// the windowed select's count, scan and write kernels (atsc_select.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_sel_count(const DevSelTask *tasks, uint32_t n, const double *scratch, int op,
+                                                  double limit, uint64_t *cnt, hipStream_t s);
+__attribute__((weak)) hipError_t launch_sel_scan(uint64_t *cnt, uint64_t n, uint64_t *sums, hipStream_t s);
+__attribute__((weak)) hipError_t launch_sel_offsets(const uint64_t *pre, const uint32_t *first, uint64_t n, uint64_t *off,
+                                                    hipStream_t s);
+__attribute__((weak)) hipError_t launch_sel_write(const DevSelTask *tasks, uint32_t n, const double *scratch, int op,
+                                                  double limit, const uint64_t *pre, uint64_t cap, void *entries,
+                                                  hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -267,7 +277,7 @@ struct DecodeCaller {
 static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE = DECODE_CALLER("quantile"),
                           BY_HISTOGRAM = DECODE_CALLER("histogram"), BY_MOMENTS = DECODE_CALLER("moments"),
                           BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs"),
-                          BY_EXTREMES = DECODE_CALLER("extremes");
+                          BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -327,11 +337,13 @@ static int check_windows(atsc_ctx *ctx, const char *call, const atsc_dplan *dp, 
 //                 result when every window is empty (any == false: the call ends there);
 //   enqueue(dp, d_body, begin2, d_res, stream, org)  its device call on the range plan, whose first sample is sample
 //                 `org` of the stream; begin2: the windows' begins counted from there.
+// A result whose size depends on the data comes back in two copies: its first head_bytes, and once those are on the
+// host the bytes from there up to used(out) (head_bytes == out_bytes: one copy, and used is not called).
 // trace: the ATSC_TRACE_HOST line of the upload.
-template <class Located, class Enqueue>
+template <class Located, class Enqueue, class Used>
 static int window_host_call(atsc_ctx *ctx, const char *call, const uint8_t *body, uint64_t body_len, int has_count,
                             uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *out, size_t out_bytes,
-                            bool trace, Located located, Enqueue enqueue)
+                            size_t head_bytes, bool trace, Located located, Enqueue enqueue, Used used)
 {
     uint64_t pos = 0, max_frames = ~0ull;
     if (has_count) {
@@ -388,8 +400,15 @@ static int window_host_call(atsc_ctx *ctx, const char *call, const uint8_t *body
     WCHK(hipMemcpyAsync(&status, dp->d_status, sizeof(int), hipMemcpyDeviceToHost, ws));
     WCHK(hipStreamSynchronize(ws));
     if (status) { rc = fail_in(ctx, ATSC_E_FORMAT, call, "malformed payload"); goto done; }
-    WCHK(hipMemcpyAsync(out, d_res, out_bytes, hipMemcpyDeviceToHost, ws));
+    WCHK(hipMemcpyAsync(out, d_res, head_bytes, hipMemcpyDeviceToHost, ws));
     WCHK(hipStreamSynchronize(ws));
+    if (head_bytes < out_bytes) {
+        const size_t end = std::min(out_bytes, used(out));
+        if (end > head_bytes) {
+            WCHK(hipMemcpyAsync((char *)out + head_bytes, (const char *)d_res + head_bytes, end - head_bytes, hipMemcpyDeviceToHost, ws));
+            WCHK(hipStreamSynchronize(ws));
+        }
+    }
 #undef WCHK
 done:
     if (rc) (void)hipStreamSynchronize(ws);
@@ -520,11 +539,13 @@ extern "C" int atsc_decompress_window(atsc_ctx *ctx, const uint8_t *body, uint64
     static const bool trace = getenv("ATSC_TRACE_HOST") != nullptr;
     const uint64_t zero = 0;
     const int rc = window_host_call(
-        ctx, "decompress_window", body, body_len, has_count, 1, &begin, &count, out, count * sizeof(double), trace,
+        ctx, "decompress_window", body, body_len, has_count, 1, &begin, &count, out, count * sizeof(double),
+        count * sizeof(double), trace,
         [&](bool) { return out_cap < count ? fail(ctx, ATSC_E_CAPACITY, "decompress_window: out_cap") : ATSC_OK; },
         [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t) {
             return atsc_decompress_windows_dev(ctx, dp, d_body, 1, begin2, &count, &zero, (double *)d_res, ws);
-        });
+        },
+        [](const void *) { return (size_t)0; });
     if (!rc) *out_n = count;
     return rc;
     ATSC_API_END
@@ -1073,6 +1094,25 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
     return ATSC_OK;
 }
 
+// A query whose result's size depends on the data (SelQuery) has two members more: head_bytes(n), the part of the result
+// that says how much of the rest is in use, and used_bytes(head, n), that amount.  The others' results come back whole.
+template <class Q, class = void>
+struct BlockResult : std::false_type {};
+template <class Q>
+struct BlockResult<Q, std::void_t<decltype(&Q::used_bytes)>> : std::true_type {};
+template <class Q>
+static size_t result_head_bytes(const Q &q, uint64_t n)
+{
+    if constexpr (BlockResult<Q>::value) return q.head_bytes(n);
+    else return q.out_bytes(n);
+}
+template <class Q>
+static size_t result_used_bytes(const Q &q, const void *head, uint64_t n)
+{
+    if constexpr (BlockResult<Q>::value) return q.used_bytes(head, n);
+    else return q.out_bytes(n);
+}
+
 // The host call of a query: the argument check, the query's own, then window_host_call into its device call.
 template <class Q>
 static int query_host(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
@@ -1083,14 +1123,16 @@ static int query_host(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int
     if (rc) return rc;
     if (n_windows == 0) return ATSC_OK;
     return window_host_call(
-        ctx, Q::CALL, body, body_len, has_count, n_windows, begin, count, out, q.out_bytes(n_windows), false,
+        ctx, Q::CALL, body, body_len, has_count, n_windows, begin, count, out, q.out_bytes(n_windows),
+        result_head_bytes(q, n_windows), false,
         [&](bool any) {
             if (!any) q.fill_empty(out, n_windows);
             return ATSC_OK;
         },
         [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
             return q.dev(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org);
-        });
+        },
+        [&](const void *head) { return result_used_bytes(q, head, n_windows); });
 }
 
 extern "C" int atsc_aggregate_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
@@ -1722,6 +1764,189 @@ extern "C" int atsc_histogram_windows(atsc_ctx *ctx, const uint8_t *body, uint64
 }
 
 // ------------------------------------------------------------------------------------------
+// windowed select: the samples of sample windows that meet a condition, and where they are (atsc_select.hip)
+// ------------------------------------------------------------------------------------------
+// ctx may be null: then no message is kept
+static int select_check(atsc_ctx *ctx, int op, double limit)
+{
+    if (op < ATSC_RUNS_GT || op > ATSC_RUNS_NE) return fail(ctx, ATSC_E_INVALID, "select_windows: unknown op");
+    if (std::isnan(limit)) return fail(ctx, ATSC_E_INVALID, "select_windows: limit is NaN");
+    return ATSC_OK;
+}
+
+// The device call.  Host work: covering intervals and pieces as histogram_dev's; per window, in the order given, and per
+// touched piece, the window's stretch inside the piece cut into tasks of at most SEL_TASK samples, numbered as they come:
+// a task's slot is its place in (window, position) order, and first[i] the slot of window i's first task (an empty
+// window's: the next window's; first[n_windows]: the number of tasks).  The tasks go up sorted by piece, so that every
+// piece's are one launch.  Then count per piece into cnt[slot], one scan over cnt[] in slot order, the windows' offsets
+// off it, and the write step per piece.  A call whose windows fit one piece writes from the samples the count step left
+// in the scratch; a call of several pieces decodes each piece a second time for the write step.  cap == 0 has no write
+// step.  Everything goes up in one copy; nothing waits on the host between the steps.
+// The scratch is one slot longer than its longest piece: the task kernels load pairs of slots from an even slot on.
+// org: the stream index of the plan's first sample (see reduce_dev).
+static int select_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+                      const uint64_t *count, int op, double limit, uint64_t cap, void *d_out, void *stream, uint64_t org)
+{
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_out)))
+        return fail(ctx, ATSC_E_INVALID, "select_windows: null argument");
+    int rc = select_check(ctx, op, limit);
+    if (rc) return rc;
+    rc = check_windows(ctx, "select_windows", dp, d_out, "d_out", n_windows, begin, count, 0xfffffffeull);
+    if (rc || n_windows == 0) return rc;
+    if (!launch_decompress_window || !launch_window_gather || !launch_sel_count || !launch_sel_scan || !launch_sel_offsets ||
+        !launch_sel_write)
+        return fail(ctx, ATSC_E_UNSUPPORTED, "select_windows: no select kernels");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint64_t W = n_windows;
+    std::vector<Span> cov;
+    for (uint64_t i = 0; i < W; ++i)
+        if (count[i]) cov.emplace_back(org + begin[i], org + begin[i] + count[i]);
+    if (cov.empty()) {  // only empty windows
+        HIPCHK(ctx, hipMemsetAsync(d_out, 0, (W + 1) * sizeof(uint64_t), s));
+        return ATSC_OK;
+    }
+    merge_spans(cov);
+    uint64_t spill;
+    const uint64_t L = piece_samples(ctx, dp, org, cov, 1, &spill);
+    // pieces: samples [S0, S1) of the stream at scratch[0, S1 - S0), ascending and disjoint
+    std::vector<Span> pcs;
+    uint64_t region = 0;
+    for (size_t a = 0; a < cov.size();) {
+        const uint64_t s0 = cov[a].first;
+        uint64_t s1 = cov[a].second;
+        size_t z = a + 1;
+        while (z < cov.size() && cov[z].first < s1 + HST_GAP) s1 = cov[z++].second;
+        for (uint64_t p = s0; p < s1; p += L) pcs.emplace_back(p, std::min(s1, p + L));
+        region = std::max(region, std::min(L, s1 - s0));
+        a = z;
+    }
+    region += 1;  // the pair load's slot behind a piece's last sample
+    const size_t P = pcs.size();
+    // tasks in (window, position) order
+    struct PT {
+        uint32_t piece;
+        DevSelTask t;
+    };
+    std::vector<PT> tk;
+    tk.reserve(W);
+    std::vector<uint32_t> first(W + 1);
+    uint64_t n_tasks = 0;
+    for (uint64_t i = 0; i < W; ++i) {
+        first[i] = (uint32_t)n_tasks;
+        if (!count[i]) continue;
+        const uint64_t b = org + begin[i], e = b + count[i];
+        size_t p = (size_t)(std::upper_bound(pcs.begin(), pcs.end(), b, [](uint64_t v, const Span &x) { return v < x.second; }) -
+                            pcs.begin());
+        for (; p < P && pcs[p].first < e; ++p) {
+            const uint64_t lo = std::max(b, pcs[p].first), hi = std::min(e, pcs[p].second);
+            for (uint64_t o = lo; o < hi; o += SEL_TASK) {
+                if (n_tasks >= 0x7fffffffull) return fail(ctx, ATSC_E_INVALID, "select_windows: more than 2^31 - 1 tasks");
+                tk.push_back(PT{(uint32_t)p, DevSelTask{o - pcs[p].first, o - b, (uint32_t)std::min<uint64_t>(SEL_TASK, hi - o),
+                                                        (uint32_t)n_tasks++}});
+            }
+        }
+    }
+    first[W] = (uint32_t)n_tasks;
+    auto by_piece = [](const PT &x, const PT &y) { return x.piece < y.piece; };
+    if (P > 1 && !std::is_sorted(tk.begin(), tk.end(), by_piece)) std::stable_sort(tk.begin(), tk.end(), by_piece);
+    std::vector<DevSelTask> tasks;
+    tasks.reserve(tk.size());
+    std::vector<size_t> at(P + 1, 0);
+    for (const PT &x : tk) { tasks.push_back(x.t); ++at[x.piece + 1]; }
+    for (size_t p = 0; p < P; ++p) at[p + 1] += at[p];
+    std::vector<PT>().swap(tk);
+    // decode tasks of every piece
+    std::vector<PieceDecode> pdec(P);
+    DecodeTasks D;
+    size_t ci = 0;
+    for (size_t p = 0; p < P; ++p)
+        if (!emit_piece_decode(dp, org, cov, ci, pcs[p].first, pcs[p].second, region, D, pdec[p]))
+            return fail(ctx, ATSC_E_INVALID, "select_windows: internal error (spill slots)");
+    QueryRes &R = dp->res[Q_SELECT];
+    HIPCHK(ctx, R.wait());
+    // one upload: the decode tasks, the select tasks, the windows' first slots; behind them (device only) the counts,
+    // one more than the tasks for the total, and the scan's block sums
+    Upload up;
+    D.place(up);
+    const size_t off_tasks = up.add(tasks), off_first = up.add(first);
+    const size_t off_cnt = up.device_only((n_tasks + 1) * sizeof(uint64_t));
+    const size_t off_sums = up.device_only(sel_scan_sums(n_tasks + 1) * sizeof(uint64_t));
+    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, region + (uint64_t)MAX_FRAME * D.spills_used));
+    unsigned char *d = R.d;
+    up.stage(R.h);
+    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
+    double *scr = R.scratch;
+    const DevSelTask *d_tasks = (const DevSelTask *)(d + off_tasks);
+    uint64_t *cnt = (uint64_t *)(d + off_cnt);
+    hipError_t e;
+    for (size_t p = 0; p < P; ++p) {
+        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_SELECT);
+        if (rc) return rc;
+        e = launch_sel_count(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, op, limit, cnt, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_sel_count", e);
+    }
+    e = launch_sel_scan(cnt, n_tasks, (uint64_t *)(d + off_sums), s);
+    if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_sel_scan", e);
+    e = launch_sel_offsets(cnt, (const uint32_t *)(d + off_first), W + 1, (uint64_t *)d_out, s);
+    if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_sel_offsets", e);
+    for (size_t p = 0; cap && p < P; ++p) {
+        if (P > 1) {  // the scratch holds the last piece: this one's samples again
+            rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_SELECT);
+            if (rc) return rc;
+        }
+        e = launch_sel_write(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, op, limit, cnt, cap,
+                             (char *)d_out + (W + 1) * sizeof(uint64_t), s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_sel_write", e);
+    }
+    HIPCHK(ctx, R.record(s));
+    return ATSC_OK;
+}
+
+// the select's descriptor (see AggQuery): the condition and the entries' capacity are the call's parameters.  Its result
+// is a block whose use depends on the data (BlockResult): the offsets say how many entries there are.
+struct SelQuery {
+    static constexpr const char *CALL = "select_windows";
+    int op;
+    double limit;
+    uint64_t cap;
+    size_t out_bytes(uint64_t n) const { return ATSC_SELECT_BYTES(n, cap); }
+    static size_t head_bytes(uint64_t n) { return ATSC_SELECT_BYTES(n, 0); }
+    size_t used_bytes(const void *head, uint64_t n) const
+    {
+        return ATSC_SELECT_BYTES(n, std::min(((const uint64_t *)head)[n], cap));
+    }
+    int check(atsc_ctx *ctx) const { return select_check(ctx, op, limit); }
+    static void fill_empty(void *out, uint64_t n)
+    {
+        if (n) memset(out, 0, head_bytes(n));
+    }
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *count, void *d_res, void *stream, uint64_t org) const
+    {
+        return select_dev(ctx, dp, d_body, n_windows, begin, count, op, limit, cap, d_res, stream, org);
+    }
+};
+
+extern "C" int atsc_select_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                       const uint64_t *begin, const uint64_t *count, int op, double limit, uint64_t cap,
+                                       void *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    return SelQuery{op, limit, cap}.dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    ATSC_API_END
+}
+
+extern "C" int atsc_select_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                   const uint64_t *begin, const uint64_t *count, int op, double limit, uint64_t cap,
+                                   void *out)
+{
+    ATSC_API_BEGIN
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, SelQuery{op, limit, cap});
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
 // the same queries on a stream under construction (atsc_stream.cpp): its records, then the host call
 // ------------------------------------------------------------------------------------------
 // a stream without a frame holds only empty windows at 0
@@ -1834,5 +2059,13 @@ extern "C" int atsc_stream_histogram_windows(atsc_stream *s, uint64_t n_windows,
 {
     ATSC_API_BEGIN
     return query_stream(s, n_windows, begin, count, out, HstQuery{n_edges, edges, closed});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_select_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                          int op, double limit, uint64_t cap, void *out)
+{
+    ATSC_API_BEGIN
+    return query_stream(s, n_windows, begin, count, out, SelQuery{op, limit, cap});
     ATSC_API_END
 }

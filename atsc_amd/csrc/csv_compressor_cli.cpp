@@ -5,7 +5,7 @@
 //
 //   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
 //                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]
-//                  [--extremes K]]]]
+//                  [--extremes K]] [--where OP:LIMIT]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
@@ -66,6 +66,9 @@ void usage()
             "                                 when they happened, as the last columns: nans, max1, max1_at .. maxK, maxK_at,\n"
             "                                 min1, min1_at .. minK, minK_at (equal values earliest first; *_at the indexed\n"
             "                                 time of the sample; both cells empty where the bucket has fewer samples)\n"
+            "      --where <OP:LIMIT>         with --from/--to, without --step: write the window's samples with value OP LIMIT\n"
+            "                                 (as --runs) to .sel.csv instead of the .wbro and .csv: timestamp,value, one row\n"
+            "                                 per selected sample, timestamp its indexed time\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -122,6 +125,37 @@ int uncompress_window(const Args &a, const std::string &output_base, uint8_t *br
     if (rc) return die("writing wavbrro", rc);
     rc = atsc_samples_csv_write(with_ext(wbro_path, "csv").c_str(), ts.data() + begin, data.data(), n);
     if (rc) return die("failed to write samples to file", rc);
+    return 0;
+}
+
+// -u --from T0 --to T1 --where OP:LIMIT: the index finds the window, the GPU its samples that meet the condition; their
+// timestamps come from the same get_time path as the window's .csv; <out>.sel.csv is all that is written
+int uncompress_where(const Args &a, const std::string &output_base, uint8_t *bro, uint64_t len)
+{
+    atsc_vsri *index = nullptr;
+    int rc = atsc_vsri_load(with_ext(a.input, "vsri").c_str(), &index);
+    if (rc) { atsc_free(bro); return die("failed to read vsri", rc); }
+    uint64_t begin = 0, count = 0;
+    rc = atsc_vsri_sample_window(index, a.t0, a.t1, &begin, &count);
+    if (rc) { atsc_free(bro); atsc_vsri_free(index); return die("vsri window", rc); }
+    std::vector<int64_t> ts(begin + count + 1);
+    rc = atsc_metric_sample_times(index, begin + count, ts.data());
+    atsc_vsri_free(index);
+    if (rc) { atsc_free(bro); return die("called `Option::unwrap()` on a `None` value (index has no time for a sample)"); }
+    std::vector<atsc_selected> rows;
+    if (count) {
+        atsc_ctx *ctx = nullptr;
+        rc = atsc_ctx_create(&ctx, 0);
+        if (rc) { atsc_free(bro); return die("no GPU context", rc); }
+        rc = atsc_bro_open(bro, len, nullptr, nullptr);
+        if (!rc) rc = where_select(ctx, bro, len, a.q, begin, count, rows);
+        if (rc) { int e = die("select", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+        atsc_ctx_destroy(ctx);
+    }
+    atsc_free(bro);
+    if (!where_write(with_ext(output_base, "sel.csv"), "timestamp", rows,
+                     [&](uint64_t at) { return std::to_string((long long)ts[begin + at]); }))
+        return die("failed to write selected samples to file");
     return 0;
 }
 
@@ -197,6 +231,7 @@ int uncompress(const Args &a, const std::string &output_base)  // main.rs:139-17
     if (rc) return die("failed to read bro file", rc);
     if (!bro) return 0;  // not a BRO file: nothing happens
     if (a.step) return uncompress_buckets(a, output_base, bro, len);
+    if (a.q.have_where) return uncompress_where(a, output_base, bro, len);
     if (a.window) return uncompress_window(a, output_base, bro, len);
     atsc_ctx *ctx = nullptr;
     rc = atsc_ctx_create(&ctx, 0);
@@ -326,6 +361,7 @@ int main(int argc, char **argv)
         return 2;
     }
     if (!bucket_options_complete(a.q, "--step", a.step != 0)) return 2;
+    if (!where_option_complete(a.q, "--from' and '--to", have_from, "--step", a.step != 0)) return 2;
     a.window = have_from;
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) return die("Failed to retrieve metadata of the input");  // main.rs:226-229

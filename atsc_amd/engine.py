@@ -44,6 +44,15 @@ EXTREME = np.dtype([("value", "<f8"), ("at", "<u8")])
 EXTREMES_MAX_K, EXTREMES_NONE = capi.EXTREMES_MAX_K, capi.EXTREMES_NONE
 
 
+# one entry of a select call's block (atsc_selected): the sample's own bits and its offset from the window's begin
+SELECTED = np.dtype([("value", "<f8"), ("at", "<u8")])
+
+
+def select_bytes(n_windows, cap):
+    """-> bytes of the block of a select call (ATSC_SELECT_BYTES): n_windows + 1 offsets, then cap entries"""
+    return 8 * (int(n_windows) + 1) + 16 * int(cap)
+
+
 def window_extremes_dtype(k):
     """-> the record of one window of an extremes call with k entries per list (include/atsc_hip.h), 16 + 32 k bytes:
     count, nans, largest[k] and smallest[k], the last two of (value, at); an empty entry is (NaN, EXTREMES_NONE)"""
@@ -73,7 +82,9 @@ def _levels(levels):
 #           call's levels or edges; the device tensor holds at least that many bytes per window.  A function of the
 #           call's own arguments where the record depends on them (the extremes' k)
 #   params  the call's own arguments -> their C arguments, which stand between the windows and the result
-_Query = collections.namedtuple("_Query", "stem dtype extra params")
+#   block   None, or for a result that is one block whose size is not a number of records (the select's offsets and
+#           entries): (n_windows, cargs) -> its bytes; the result is then that many bytes as uint64 words, whole
+_Query = collections.namedtuple("_Query", "stem dtype extra params block", defaults=(None,))
 
 
 def _no_params():
@@ -100,6 +111,28 @@ def _extremes_dtype(k):
     return window_extremes_dtype(min(max(_extremes_k(k), 1), EXTREMES_MAX_K))
 
 
+def _select_params(op, limit, cap):
+    cap = int(cap)
+    if not 0 <= cap < 2 ** 64:
+        raise ValueError("cap outside uint64")
+    return int(op), float(limit), C.c_uint64(cap)
+
+
+def _select_block(n, cargs):
+    return select_bytes(n, cargs[2].value)
+
+
+def _select_result(run, n, cap):
+    """run(cap) -> the block of a select call over n windows as uint64 words.  -> (off, entries): the n + 1 offsets and
+    the SELECTED entries written, min(off[-1], cap) of them; cap None: the sizing call, then the exact one"""
+    if cap is None:
+        cap = int(run(0)[n])
+    blk = run(int(cap))
+    off = blk[: n + 1].copy()
+    m = min(int(off[n]), int(cap))
+    return off, blk[n + 1: n + 1 + 2 * m].copy().view(SELECTED)
+
+
 def _array_params(values, flag):
     """levels and method, or edges and closed"""
     a, pa = _levels(values)
@@ -111,6 +144,7 @@ _MOMENTS = _Query("moments_windows", WINDOW_MOMENTS, None, _no_params)
 _DELTA = _Query("delta_windows", WINDOW_DELTA, None, _no_params)
 _RUNS = _Query("runs_windows", WINDOW_RUNS, None, _runs_params)
 _EXTREMES = _Query("extremes_windows", _extremes_dtype, None, _extremes_params)
+_SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _select_block)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
 _HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
 
@@ -124,11 +158,24 @@ def _query_dtype(q, params):
     return q.dtype(*params) if callable(q.dtype) else q.dtype
 
 
+def _query_bytes(q, n, cargs, params):
+    """bytes of the result of n windows"""
+    return q.block(n, cargs) if q.block else _query_dtype(q, params).itemsize * _query_width(q, cargs) * n
+
+
 def _query_result(q, n, cargs, fn, params=()):
     """-> (the zeroed host result of n windows, at least one, and its pointer as fn's last argument)"""
     rows = max(n, 1)
-    out = np.zeros(rows if q.extra is None else (rows, _query_width(q, cargs)), dtype=_query_dtype(q, params))
+    if q.block:
+        out = np.zeros(q.block(n, cargs) // 8, dtype=np.uint64)
+    else:
+        out = np.zeros(rows if q.extra is None else (rows, _query_width(q, cargs)), dtype=_query_dtype(q, params))
     return out, out.ctypes.data_as(fn.argtypes[-1])
+
+
+def _query_rows(q, out, n):
+    """the result of n windows: its records, or the block whole"""
+    return out if q.block else out[:n]
 
 
 def _query_host(q, ctx, records, begins, counts, has_count, *params):
@@ -140,7 +187,7 @@ def _query_host(q, ctx, records, begins, counts, has_count, *params):
     out, po = _query_result(q, len(wb), cargs, fn, params)
     rc = fn(ctx._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count), len(wb), pb, pc, *cargs, po)
     capi.check(rc, ctx._h)
-    return out[: len(wb)]
+    return _query_rows(q, out, len(wb))
 
 
 def _query_dev(q, dplan, d_body, begins, counts, d_out, stream, *params):
@@ -149,7 +196,7 @@ def _query_dev(q, dplan, d_body, begins, counts, d_out, stream, *params):
     cargs = q.params(*params)
     assert q.extra is None or d_out.element_size() == 8
     assert d_out.is_contiguous()
-    assert d_out.numel() * d_out.element_size() >= _query_dtype(q, params).itemsize * _query_width(q, cargs) * len(b)
+    assert d_out.numel() * d_out.element_size() >= _query_bytes(q, len(b), cargs, params)
     rc = getattr(capi.lib(), "atsc_%s_dev" % q.stem)(dplan.ctx._h, dplan._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
                                                      *cargs, C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
     capi.check(rc, dplan.ctx._h)
@@ -335,6 +382,14 @@ class Context:
         [begins[i], begins[i] + counts[i]) of the decoded records (atsc_runs_windows)"""
         return _query_host(_RUNS, self, records, begins, counts, has_count, op, limit)
 
+    def select_windows_host(self, records, begins, counts, op, limit, cap=None, has_count=False):
+        """-> (off, entries): the samples with x OP limit (op: RUNS_GT .. RUNS_NE) of every window and where they are
+        (atsc_select_windows).  off: n_windows + 1 offsets, off[i + 1] - off[i] the selected samples of window i, always the
+        true numbers; entries: SELECTED records (value, at) in window order and ascending position, the first
+        min(off[-1], cap) of them.  cap None: a sizing call (cap 0), then the exact one"""
+        n = len(np.atleast_1d(begins))
+        return _select_result(lambda c: _query_host(_SELECT, self, records, begins, counts, has_count, op, limit, c), n, cap)
+
     def extremes_windows_host(self, records, begins, counts, k, has_count=False):
         """-> array of window_extremes_dtype(k): the k largest and the k smallest non-NaN samples, each with its offset
         in the window, the number of NaN samples and the length of every window [begins[i], begins[i] + counts[i]) of
@@ -489,6 +544,12 @@ class DPlan:
         """Enqueues the runs of the samples with x OP limit of the windows [begins[i], begins[i] + counts[i]) into d_out,
         a device tensor of at least 80 bytes per window (atsc_runs_windows_dev; WINDOW_RUNS records)"""
         _query_dev(_RUNS, self, d_body, begins, counts, d_out, stream, op, limit)
+
+    def select_windows(self, d_body, begins, counts, op, limit, cap, d_out, stream=0):
+        """the samples with x OP limit of the windows and where they are, enqueued on `stream`, into d_out, a device
+        tensor of at least select_bytes(len(begins), cap) bytes: the offsets, then the entries below cap
+        (atsc_select_windows_dev)"""
+        _query_dev(_SELECT, self, d_body, begins, counts, d_out, stream, op, limit, cap)
 
     def extremes_windows(self, d_body, begins, counts, k, d_out, stream=0):
         """Enqueues the k largest and the k smallest samples of the windows [begins[i], begins[i] + counts[i]) into

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import capi
 from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit  # noqa: F401
-from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _QUANTILE, _RUNS, _query_result
+from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _QUANTILE, _RUNS, _SELECT, _query_result, _query_rows, _select_result
 
 
 def _f64(x):
@@ -34,7 +34,7 @@ def _query_stream(q, stream, begins, counts, *params):
     fn = getattr(capi.lib(), "atsc_stream_" + q.stem)
     out, po = _query_result(q, len(wb), cargs, fn, params)
     capi.check(fn(stream._h, len(wb), pb, pc, *cargs, po), stream.ctx._h)
-    return out[: len(wb)]
+    return _query_rows(q, out, len(wb))
 
 
 def _query_image(q, ctx, bro, begins, counts, *params):
@@ -48,7 +48,7 @@ def _query_image(q, ctx, bro, begins, counts, *params):
     r = b[9:]  # the records from the frame-count varint on, as atsc_decompress_data reads them
     rc = fn(ctx._h, r.ctypes.data_as(C.POINTER(C.c_uint8)), len(r), 1, len(wb), pb, pc, *cargs, po)
     capi.check(rc, ctx._h)
-    return out[: len(wb)]
+    return _query_rows(q, out, len(wb))
 
 
 class CompressedStream:
@@ -133,6 +133,12 @@ class CompressedStream:
         (atsc_stream_runs_windows)"""
         return _query_stream(_RUNS, self, begins, counts, op, limit)
 
+    def select_windows(self, begins, counts, op, limit, cap=None):
+        """-> (off, entries) of the windows [begins[i], begins[i] + counts[i]) under the condition x OP limit, as
+        Context.select_windows_host gives them (atsc_stream_select_windows)"""
+        n = len(np.atleast_1d(begins))
+        return _select_result(lambda c: _query_stream(_SELECT, self, begins, counts, op, limit, c), n, cap)
+
     def extremes_windows(self, begins, counts, k):
         """-> array of window_extremes_dtype(k) of the windows [begins[i], begins[i] + counts[i]): their k largest and k
         smallest samples and where they are (atsc_stream_extremes_windows)"""
@@ -204,6 +210,13 @@ def runs_data_windows(ctx, bro, begins, counts, op, limit):
     """-> WINDOW_RUNS array of windows of decompress_data(ctx, bro) under the condition x OP limit: atsc_bro_open, then
     atsc_runs_windows over the records"""
     return _query_image(_RUNS, ctx, bro, begins, counts, op, limit)
+
+
+def select_data_windows(ctx, bro, begins, counts, op, limit, cap=None):
+    """-> (off, entries) of windows of decompress_data(ctx, bro) under the condition x OP limit, as
+    Context.select_windows_host gives them: atsc_bro_open, then atsc_select_windows over the records"""
+    n = len(np.atleast_1d(begins))
+    return _select_result(lambda c: _query_image(_SELECT, ctx, bro, begins, counts, op, limit, c), n, cap)
 
 
 def extremes_data_windows(ctx, bro, begins, counts, k):

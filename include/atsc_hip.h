@@ -561,6 +561,49 @@ int atsc_extremes_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len,
  * for a null pointer with n > 0, a null out, or k outside 1 .. ATSC_EXTREMES_MAX_K. */
 int atsc_extremes_merge(const void *records, uint64_t n, uint32_t k, void *out);
 
+/* Windowed select: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames) the
+ * samples that meet a condition and where they are, from the same decoded samples as the window decode: every sample
+ * above 0.9 of each hour with its position, WHERE value OP limit pushed down to the device.  The result is as large as
+ * the data makes it; what comes back is the selected samples, not the windows.
+ *   Condition  op is one of the ATSC_RUNS_* operators and limit the same for every window of a call; the rule is
+ *              atsc_runs_windows': a sample is selected iff it is not NaN and x OP limit holds, compared as values.  -0.0
+ *              equals +0.0; +-Inf samples and limits are ordinary values; NaN is never selected, under NE too.
+ *   Block      ATSC_SELECT_BYTES(n_windows, cap) bytes, 8-byte aligned: off[0 .. n_windows] as uint64_t, then, at byte
+ *              8 (n_windows + 1), the entries e[0 .. cap), each an atsc_selected.  off[0] = 0 and off[i + 1] - off[i] is the
+ *              number of selected samples of window i: the offsets are always the true numbers, whatever cap is.  The
+ *              selected samples of window i, in ascending position, are the entries off[i], off[i] + 1, ..; windows go in
+ *              the order given.  Entry r is written iff r < cap: a call with too small a cap returns ATSC_OK and a
+ *              correct prefix, and the caller compares off[n_windows] with cap.  cap == 0 is valid and is the sizing
+ *              pass: only the offsets are written.  Bytes of the block behind entry min(off[n_windows], cap) are
+ *              unspecified; nothing outside the block is ever touched.
+ *   Entries    value is the sample's own bits (a -0.0 stays -0.0), at its offset from `begin`.
+ * There is no floating-point arithmetic in the contract: the result is bit-exact.  The entries of window i depend only on
+ * the stream's samples, the window and the condition, not on the other windows, their order, cap (apart from the
+ * truncation), the budget, piece boundaries or the device.  off[i + 1] - off[i] equals atsc_runs_windows' inside, and the
+ * first and the last entry's at its first_at and last_at.
+ * ATSC_E_INVALID with nothing written, before any GPU work, for an unknown op or a NaN limit.  Validation and the other
+ * semantics are atsc_aggregate_windows_dev's: a window beyond the stream gives ATSC_E_INVALID with nothing written;
+ * payloads are checked only of the frames a window touches; windows may overlap and come in any order, at most 2^32 - 2
+ * of them; count == 0 is valid; n_windows == 0 is valid and writes nothing.  Windows may be of any length: there is no
+ * ATSC_E_CAPACITY case, and the decoded samples stay within the budget of atsc_ctx_set_aggregate_scratch. */
+typedef struct {
+    double value; /* the sample's own bits (a -0.0 stays -0.0) */
+    uint64_t at;  /* its offset from the window's begin */
+} atsc_selected; /* 16 bytes */
+#define ATSC_SELECT_BYTES(n_windows, cap) (8u * ((size_t)(n_windows) + 1u) + 16u * (size_t)(cap))
+/* begin / count are HOST arrays; d_body and d_out are device memory (d_out 8-byte aligned, ATSC_SELECT_BYTES(n_windows,
+ * cap) bytes).  Enqueued on `stream`, not synchronised.  A malformed payload inside a window sets the plan's status word.
+ * The plan keeps the call's tables, counts and scratch: the next select call on the same plan waits (host side) until
+ * this one's work is done; atsc_dplan_destroy frees them. */
+int atsc_select_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                            const uint64_t *begin, const uint64_t *count, int op, double limit, uint64_t cap,
+                            void *d_out, void *stream);
+/* Host bytes in, host block out, synchronous; walks and uploads only the touched records, as atsc_aggregate_windows
+ * does, and brings back the offsets and the entries written, not the rest of the block.  ATSC_E_FORMAT (nothing written)
+ * for a malformed payload inside a window.  When every window is empty: n_windows + 1 zero offsets. */
+int atsc_select_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                        const uint64_t *begin, const uint64_t *count, int op, double limit, uint64_t cap, void *out);
+
 /* Windowed quantiles: exact order statistics of windows [begin, begin + count) of the decoded stream (the indices of
  * atsc_decompress_frames), from the same decoded samples as the window decode.  For window i:
  *   x  the window's non-NaN samples, n of them, sorted in IEEE total order (-0.0 before +0.0), i.e. by the keys
@@ -670,6 +713,9 @@ int atsc_stream_runs_windows(atsc_stream *s, uint64_t n_windows, const uint64_t 
 /* atsc_extremes_windows over the stream's frames */
 int atsc_stream_extremes_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint32_t k, void *out);
+/* atsc_select_windows over the stream's frames */
+int atsc_stream_select_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                               int op, double limit, uint64_t cap, void *out);
 /* atsc_moments_windows over the stream's frames */
 int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 atsc_window_moments *out);
