@@ -11,6 +11,7 @@ from .capi import EXTREMES_MAX_K, EXTREMES_NONE  # noqa: F401
 from .engine import EXTREME, extremes_merge, window_extremes_dtype  # noqa: F401
 from .stream import extremes_data_windows  # noqa: F401
 from .engine import SELECTED, select_bytes  # noqa: F401
+from .engine import WINDOW_PAIR, WINDOW_PAIR_FIT, pair_fit  # noqa: F401
 from .stream import select_data_windows  # noqa: F401
 from .engine import (WINDOW_DELTA, WINDOW_DELTA_FIT, WINDOW_FIT, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, Context, DPlan, Plan,  # noqa: F401
                      bro_find_window, bro_open, bro_prefix, bucket_windows, chunk_sizes, clean_data, delta_derive,

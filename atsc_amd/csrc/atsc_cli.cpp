@@ -3,8 +3,8 @@
 //
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
-//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K]]
-//        [--where OP:LIMIT]]
+//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K]
+//        [--pair OTHER.bro]] [--where OP:LIMIT]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -63,6 +63,10 @@ void usage()
             "                                 where they are, as the last columns: nans, max1, max1_at .. maxK, maxK_at, min1,\n"
             "                                 min1_at .. minK, minK_at (equal values earliest first; *_at the sample's offset\n"
             "                                 in the bucket; both cells empty where the bucket has fewer samples)\n"
+            "      --pair <OTHER.bro>         with --buckets: also every bucket's pair moments against the samples of OTHER.bro at\n"
+            "                                 the same sample indices (OTHER must reach the bucketed range's end), as the last\n"
+            "                                 columns: pair_count (samples where neither value is NaN), covariance (population\n"
+            "                                 form), correlation, and slope and intercept of OTHER's value on this file's\n"
             "      --where <OP:LIMIT>         with -u --samples, without --buckets: write the window's samples with value OP LIMIT\n"
             "                                 (as --runs) to .sel.csv instead of the .wbro: sample,value, one row per selected\n"
             "                                 sample, sample its index in the stream\n"
@@ -230,6 +234,7 @@ int process_directory(atsc_ctx *ctx, const Args &a)
 int main(int argc, char **argv)
 {
     Args a;
+    a.q.pair_allowed = true;
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i], v;
         auto value = [&](const char *name) -> bool {

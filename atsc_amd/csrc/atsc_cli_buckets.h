@@ -63,6 +63,8 @@ struct BucketOptions {
     int runs_op = ATSC_RUNS_GT;
     double runs_limit = 0.0;
     int extremes = 0;  // --extremes K: nans,max1,max1_at,..,maxK,maxK_at,min1,min1_at,..,minK,minK_at
+    bool pair_allowed = false;  // the front end takes --pair (atsc; csv-compressor does not: DESIGN.md "Windowed pair moments")
+    std::string pair;           // --pair OTHER.bro: pair_count,covariance,correlation,slope,intercept against that stream
     bool have_where = false;  // --where OP:LIMIT: no bucket query; the window's selected samples into .sel.csv
     int where_op = ATSC_RUNS_GT;
     double where_limit = 0.0;
@@ -147,6 +149,7 @@ bool parse_runs(const std::string &v, int &op, double &limit)
     return true;
 }
 
+// --pair OTHER.bro is taken only where the front end allows it (o.pair_allowed).
 // One argument of the command line, where it is a bucket-query option.  s: the argument; value(name): whether s is the
 // option `name` with a value, which it leaves in v (the callers' lambda).  0: none of them; 1: taken; 2: a usage error,
 // reported on stderr.
@@ -207,6 +210,12 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             fprintf(stderr, "error: invalid value '%s' for '--extremes': expected 1..=%d\n", v.c_str(), (int)ATSC_EXTREMES_MAX_K);
             return 2;
         }
+    } else if (o.pair_allowed && value("--pair")) {
+        if (v.empty()) {
+            fprintf(stderr, "error: invalid value '' for '--pair': expected the path of a .bro file\n");
+            return 2;
+        }
+        o.pair = v;
     } else {
         return 0;
     }
@@ -227,7 +236,8 @@ bool bucket_options_complete(const BucketOptions &o, const char *bucketing, bool
              {o.moments, given, "--moments", bucketing},
              {o.deltas, given, "--deltas", bucketing},
              {o.have_runs, given, "--runs", bucketing},
-             {o.extremes != 0, given, "--extremes", bucketing}};
+             {o.extremes != 0, given, "--extremes", bucketing},
+             {!o.pair.empty(), given, "--pair", bucketing}};
     for (const auto &t : T)
         if (t.have && !t.needed) {
             fprintf(stderr, "error: '%s' needs '%s'\n", t.name, t.needs);
@@ -266,6 +276,8 @@ struct BucketResults {
     uint32_t ek = 0;                  // --extremes: entries per list
     std::vector<unsigned char> ev;    // the buckets' records, ATSC_EXTREMES_BYTES(ek) each
     std::vector<std::string> eat;     // 2 ek cells per bucket: the entries' places, as offsets in the bucket
+    std::vector<atsc_window_pair> pv;  // --pair
+    std::vector<atsc_window_pair_fit> pf;
     const atsc_window_extremes_head &ext_head(uint64_t k) const
     {
         return *(const atsc_window_extremes_head *)(ev.data() + k * ATSC_EXTREMES_BYTES(ek));
@@ -334,6 +346,21 @@ int bucket_queries(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const Bucket
     if (r.ek) rc = atsc_extremes_windows(ctx, body, body_len, 1, nb, b, c, r.ek, r.ev.data());
     if (!rc && r.ek)
         rc = bucket_extreme_places(r, nb, [](uint64_t, uint64_t at, std::string &cell) { cell = std::to_string(at); return 0; });
+    if (rc) return rc;
+    *failed = "pair";
+    const bool pair = !o.pair.empty();
+    r.pv.resize(pair && nb ? nb : 1);
+    r.pf.resize(r.pv.size());
+    if (pair) {  // the other stream: sample i of it goes with sample i of this one
+        uint8_t *other = nullptr;
+        uint64_t olen = 0;
+        rc = atsc_bro_read_file(o.pair.c_str(), &other, &olen);
+        if (!rc && !other) rc = ATSC_E_FORMAT;  // not a BRO file
+        if (!rc) rc = atsc_bro_open(other, olen, nullptr, nullptr);
+        if (!rc) rc = atsc_pair_windows(ctx, body, body_len, 1, other + 9, olen - 9, 1, nb, b, c, r.pv.data());
+        if (!rc) rc = atsc_pair_fit(r.pv.data(), nb, r.pf.data());
+        atsc_free(other);
+    }
     return rc;
 }
 
@@ -352,6 +379,7 @@ void bucket_header(FILE *f, const char *first, const BucketOptions &o, const Buc
         for (int e = 0; e < 2; ++e)
             for (int j = 1; j <= o.extremes; ++j) fprintf(f, ",%s%d,%s%d_at", e ? "min" : "max", j, e ? "min" : "max", j);
     }
+    if (!o.pair.empty()) fprintf(f, ",pair_count,covariance,correlation,slope,intercept");
     fprintf(f, "\n");
 }
 
@@ -389,6 +417,11 @@ void bucket_row(FILE *f, const std::string &first, const BucketOptions &o, const
             fprintf(f, ",%s,%s", x.at == ATSC_EXTREMES_NONE ? "" : debug_f64(x.value).c_str(),
                     r.eat[2 * (size_t)r.ek * k + j].c_str());
         }
+    }
+    if (!o.pair.empty()) {
+        const atsc_window_pair_fit &pf = r.pf[k];
+        fprintf(f, ",%llu,%s,%s,%s,%s", (unsigned long long)r.pv[k].count, debug_f64(pf.covariance).c_str(),
+                debug_f64(pf.correlation).c_str(), debug_f64(pf.slope).c_str(), debug_f64(pf.intercept).c_str());
     }
     fprintf(f, "\n");
 }

@@ -1,75 +1,28 @@
 // atsc_moments.hip -- gfx950 kernels of the windowed moments (atsc_moments_windows_dev): the centred moments of value x
 // and sample position t of sample windows, reduced from decoded samples in the call's scratch.
 //
-// The merge order is part of the contract (include/atsc_hip.h, DESIGN.md "Windowed moments").  A node is
-// (n, mx, M2x, mt, M2t, C); the leaf of stream index i is (1, x[i], 0, (double)i, 0, 0), a slot outside the window or
-// holding NaN the empty node; Merge(a, b) is a when nb == 0, b when na == 0, else
-//     n = na + nb; w = (double)nb / (double)n; f = (double)na * w; dx = mxb - mxa; dt = mtb - mta;
-//     mx = mxa + dx * w; mt = mta + dt * w;
-//     M2x = (M2xa + M2xb) + (dx * dx) * f; M2t = (M2ta + M2tb) + (dt * dt) * f; C = (Ca + Cb) + (dx * dt) * f
-// (one rounding per operation: this file is compiled with -ffp-contract=off).  The tree is the tile sum's
-// (tile_lane_sums, atsc_tile_reduce.h) with + replaced by Merge, the left operand as a.
+// The node, its merge and the tree are atsc_moment_node.h's, which the windowed pair moments share (the contract:
+// include/atsc_hip.h, DESIGN.md "Windowed moments").  The leaf of stream index i is (1, x[i], 0, (double)i, 0, 0), a slot
+// outside the window or holding NaN the empty node.
 // One wavefront reduces one tile (lane l holds the virtual lanes l, l + 64, l + 128, l + 192) or one group of 64 tile
 // partials of a window.  No atomics: every partial has one writer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "atsc_tile_reduce.h"
+#include "atsc_moment_node.h"
 
 namespace atsc {
 
 namespace {
 
-// the node inside a tile: DevMomPart with a 32-bit count (a tile's nodes hold at most 2048 samples)
-struct Node {
-    double mx, m2x, mt, m2t, c;
-    uint32_t n;
-};
-
-// the leaf of sample v at stream position t; ok: inside the window and not NaN
-__device__ __forceinline__ Node node_leaf(double v, double t, bool ok)
-{
-    return ok ? Node{v, 0.0, t, 0.0, 0.0, 1} : Node{0.0, 0.0, 0.0, 0.0, 0.0, 0};
-}
-
-// Merge(a, b).  EQ: the caller knows na == nb != 0 -- then w = nb / (2 nb) is 0.5 exactly and f = na * 0.5, the bits
-// the divide gives; nothing else differs from the general rule.  ND: Node or DevMomPart.
-template <bool EQ, class ND>
-__device__ __forceinline__ ND node_merge(const ND &a, const ND &b)
-{
-    const decltype(a.n) n = a.n + b.n;
-    const double w = EQ ? 0.5 : (double)b.n / (double)n;
-    const double f = (double)a.n * w;
-    const double dx = b.mx - a.mx, dt = b.mt - a.mt;
-    ND r;
-    r.mx = a.mx + dx * w;
-    r.mt = a.mt + dt * w;
-    r.m2x = (a.m2x + b.m2x) + (dx * dx) * f;
-    r.m2t = (a.m2t + b.m2t) + (dt * dt) * f;
-    r.c = (a.c + b.c) + (dx * dt) * f;
-    r.n = n;
-    if (EQ) return r;
-    return b.n == 0 ? a : a.n == 0 ? b : r;
-}
-
 // a virtual lane's eight leaves (four 16-byte loads d[q] at slots tile_slot(v, q), positions from t0) into its node
 template <bool EQ>
-__device__ __forceinline__ Node lane_node(const double2 (&d)[4], const bool (&ok)[8], double t0)
+__device__ __forceinline__ Node mom_lane_node(const double2 (&d)[4], const bool (&ok)[8], double t0)
 {
-    Node p[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    return lane_node<EQ>([&](int q, int e) {
         const double t = t0 + 512.0 * q;
-        p[q] = node_merge<EQ>(node_leaf(d[q].x, t, ok[2 * q]), node_leaf(d[q].y, t + 1.0, ok[2 * q + 1]));
-    }
-    return node_merge<EQ>(node_merge<EQ>(p[0], p[1]), node_merge<EQ>(p[2], p[3]));
-}
-
-// the halving tree over the 256 virtual lanes: h = 128 and 64 inside the lane, then 32 .. 1 across the wavefront
-template <bool EQ>
-__device__ __forceinline__ Node tile_node(const Node (&s)[4])
-{
-    return wave_halve(node_merge<EQ>(node_merge<EQ>(s[0], s[2]), node_merge<EQ>(s[1], s[3])), node_merge<EQ, Node>);
+        return e ? node_leaf(d[q].y, t + 1.0, ok[2 * q + 1]) : node_leaf(d[q].x, t, ok[2 * q]);
+    });
 }
 
 }  // namespace
@@ -104,8 +57,8 @@ __global__ __launch_bounds__(256) void k_mom_tiles(const DevPosTile *__restrict_
             all = all && ok[2 * q] && ok[2 * q + 1];
         }
         const double t0 = tb + (double)(2u * v);
-        if (__all(all)) s[k] = lane_node<true>(d, ok, t0);
-        else s[k] = lane_node<false>(d, ok, t0);
+        if (__all(all)) s[k] = mom_lane_node<true>(d, ok, t0);
+        else s[k] = mom_lane_node<false>(d, ok, t0);
         full = full && all;
     }
     Node a;

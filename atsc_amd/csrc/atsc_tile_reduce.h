@@ -1,7 +1,7 @@
 // atsc_tile_reduce.h -- what the window reductions over tiles share on the device (atsc_aggregate.hip,
-// atsc_moments.hip, atsc_delta.hip, atsc_runs.hip, atsc_extremes.hip; DESIGN.md "The tile / combine skeleton"): the
-// wavefront-to-task mapping and its launch, the tile's slot-to-lane mapping and masked load, the contract's sum tree,
-// the shuffle trees over whole partials and the combine pass's fetch / reduce / store.
+// atsc_moments.hip, atsc_pair.hip, atsc_delta.hip, atsc_runs.hip, atsc_extremes.hip; DESIGN.md "The tile / combine
+// skeleton"): the wavefront-to-task mapping and its launch, the tile's slot-to-lane mapping and masked load, the
+// contract's sum tree, the shuffle trees over whole partials and the combine pass's fetch / reduce / store.
 #pragma once
 #include "atsc_device.h"
 

@@ -1,5 +1,5 @@
 // atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, quantiles, histograms
-// and selected samples of ranges of the decoded stream without decoding the rest.  Each query has a device call (host tables, one upload, launches on the caller's
+// and selected samples of ranges of the decoded stream without decoding the rest, and the pair moments of the same ranges of two streams.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
@@ -74,6 +74,11 @@ __attribute__((weak)) hipError_t launch_sel_offsets(const uint64_t *pre, const u
 __attribute__((weak)) hipError_t launch_sel_write(const DevSelTask *tasks, uint32_t n, const double *scratch, int op,
                                                   double limit, const uint64_t *pre, uint64_t cap, void *entries,
                                                   hipStream_t s);
+// the windowed pair moments' reduce kernels (atsc_pair.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_pair_tiles(const DevPosTile *tasks, uint32_t n, const double *sx, const double *sy,
+                                                   DevMomPart *part, hipStream_t s);
+__attribute__((weak)) hipError_t launch_pair_combine(const DevAggComb *tasks, uint32_t n, DevMomPart *part, void *out,
+                                                     hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -277,7 +282,8 @@ struct DecodeCaller {
 static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE = DECODE_CALLER("quantile"),
                           BY_HISTOGRAM = DECODE_CALLER("histogram"), BY_MOMENTS = DECODE_CALLER("moments"),
                           BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs"),
-                          BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select");
+                          BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
+                          BY_PAIR = DECODE_CALLER("pair");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -315,14 +321,19 @@ static int launch_piece_decode(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_
 }
 
 // What every device call checks of its result pointer and its windows; `call` names the caller in the message.
-// max_windows: the most windows the call's tasks can name (~0ull: no limit).
+// max_windows: the most windows the call's tasks can name (~0ull: no limit).  A call over several plans checks each:
+// begin counts from sample org0 of the stream, and the plan's first sample is sample org of it.
 static int check_windows(atsc_ctx *ctx, const char *call, const atsc_dplan *dp, const void *d_res, const char *res_name,
-                         uint64_t n_windows, const uint64_t *begin, const uint64_t *count, uint64_t max_windows)
+                         uint64_t n_windows, const uint64_t *begin, const uint64_t *count, uint64_t max_windows,
+                         uint64_t org0 = 0, uint64_t org = 0)
 {
     if ((uintptr_t)d_res & 7u) return fail_in(ctx, ATSC_E_INVALID, call, (std::string(res_name) + " is not 8-byte aligned").c_str());
     const uint64_t ns = dp->n_samples;
-    for (uint64_t i = 0; i < n_windows; ++i)
-        if (begin[i] > ns || count[i] > ns - begin[i]) return fail_in(ctx, ATSC_E_INVALID, call, "window beyond the stream");
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        const uint64_t a = org0 + begin[i];
+        if (a < begin[i] || a < org || a - org > ns || count[i] > ns - (a - org))
+            return fail_in(ctx, ATSC_E_INVALID, call, "window beyond the stream");
+    }
     if (n_windows > max_windows) return fail_in(ctx, ATSC_E_INVALID, call, "more than 2^32 - 2 windows");
     return ATSC_OK;
 }
@@ -332,23 +343,40 @@ static int check_windows(atsc_ctx *ctx, const char *call, const atsc_dplan *dp, 
 // ------------------------------------------------------------------------------------------
 // Walks the headers from the first non-empty window's first record to the record that holds the last window's end,
 // plans those records only and uploads only their bytes; the result comes back once the payloads proved well-formed (a
-// malformed one leaves `out` untouched).  `call` names the caller in the messages.  The caller's two steps:
+// malformed one leaves `out` untouched).  A query over two streams (n_in == 2) does the walk, the range plan and the
+// upload for each body, over the same windows; every body's status word is read before anything is copied out.
+// `call` names the caller in the messages.  The caller's two steps:
 //   located(any)  after the walk, which is what rejects a window beyond the stream: the caller's own checks, and its
 //                 result when every window is empty (any == false: the call ends there);
-//   enqueue(dp, d_body, begin2, d_res, stream, org)  its device call on the range plan, whose first sample is sample
-//                 `org` of the stream; begin2: the windows' begins counted from there.
+//   enqueue(in, begin2, d_res, stream)  its device call on the range plans in[0 .. n_in): in[k].org is the stream index
+//                 of plan k's first sample; begin2: the windows' begins counted from in[0].org.
 // A result whose size depends on the data comes back in two copies: its first head_bytes, and once those are on the
 // host the bytes from there up to used(out) (head_bytes == out_bytes: one copy, and used is not called).
 // trace: the ATSC_TRACE_HOST line of the upload.
+struct HostBody {
+    const uint8_t *body;
+    uint64_t len;
+    int has_count;
+};
+// one plan of a device call with its record bytes on the device; org: the stream index of the plan's first sample
+struct QueryInput {
+    const atsc_dplan *dp;
+    const uint8_t *d_body;
+    uint64_t org;
+};
+static const int MAX_INPUTS = 2;
+
 template <class Located, class Enqueue, class Used>
-static int window_host_call(atsc_ctx *ctx, const char *call, const uint8_t *body, uint64_t body_len, int has_count,
-                            uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *out, size_t out_bytes,
-                            size_t head_bytes, bool trace, Located located, Enqueue enqueue, Used used)
+static int window_host_call(atsc_ctx *ctx, const char *call, const HostBody *hb, int n_in, uint64_t n_windows,
+                            const uint64_t *begin, const uint64_t *count, void *out, size_t out_bytes, size_t head_bytes,
+                            bool trace, Located located, Enqueue enqueue, Used used)
 {
-    uint64_t pos = 0, max_frames = ~0ull;
-    if (has_count) {
-        if (!host_varint(body, body_len, pos, max_frames)) return fail_in(ctx, ATSC_E_FORMAT, call, "frame count");
-        if (max_frames > body_len / 4) return fail_in(ctx, ATSC_E_FORMAT, call, "frame count exceeds the bytes present");
+    uint64_t pos[MAX_INPUTS] = {}, max_frames[MAX_INPUTS];
+    for (int k = 0; k < n_in; ++k) {
+        max_frames[k] = ~0ull;
+        if (!hb[k].has_count) continue;
+        if (!host_varint(hb[k].body, hb[k].len, pos[k], max_frames[k])) return fail_in(ctx, ATSC_E_FORMAT, call, "frame count");
+        if (max_frames[k] > hb[k].len / 4) return fail_in(ctx, ATSC_E_FORMAT, call, "frame count exceeds the bytes present");
     }
     uint64_t B = ~0ull, E = 0;
     for (uint64_t i = 0; i < n_windows; ++i) {
@@ -358,48 +386,59 @@ static int window_host_call(atsc_ctx *ctx, const char *call, const uint8_t *body
     }
     const bool any = B != ~0ull;
     if (!any) B = E;  // only empty windows: the walk checks that each begins inside the stream
-    WindowWalk w;
-    int rc = window_walk(body, body_len, pos, max_frames, B, E - B, true, w);
-    if (rc) return fail_in(ctx, rc, call, rc == ATSC_E_INVALID ? "window beyond the stream" : "record walk");
+    WindowWalk w[MAX_INPUTS];
+    int rc = ATSC_OK;
+    for (int k = 0; k < n_in; ++k) {
+        rc = window_walk(hb[k].body, hb[k].len, pos[k], max_frames[k], B, E - B, true, w[k]);
+        if (rc) return fail_in(ctx, rc, call, rc == ATSC_E_INVALID ? "window beyond the stream" : "record walk");
+    }
     rc = located(any);
     if (rc || !any) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!ctx->work_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->work_stream, hipStreamNonBlocking));
     hipStream_t ws = ctx->work_stream;
-    const uint64_t slice = w.byte_end - w.byte_begin;
-    atsc_dplan *dp = nullptr;
-    rc = dplan_create_range(ctx, body + w.byte_begin, slice, 0, 0, ~0ull, nullptr, &dp);
-    if (rc) return rc;
-    std::vector<uint64_t> begin2(n_windows);
-    for (uint64_t i = 0; i < n_windows; ++i) begin2[i] = count[i] ? begin[i] - w.sample_begin : 0;
-    uint8_t *d_body = nullptr;
+    atsc_dplan *dp[MAX_INPUTS] = {};
+    uint8_t *d_body[MAX_INPUTS] = {};
+    QueryInput in[MAX_INPUTS];
+    int status[MAX_INPUTS] = {};
     void *d_res = nullptr;
-    int status = 0;
     hipError_t e = hipSuccess;
+    // an empty window begins where every plan has a sample: at the last of the plans' first samples
+    uint64_t first = 0;
+    for (int k = 0; k < n_in; ++k) first = std::max(first, w[k].sample_begin);
+    std::vector<uint64_t> begin2(n_windows);
+    for (uint64_t i = 0; i < n_windows; ++i) begin2[i] = (count[i] ? begin[i] : first) - w[0].sample_begin;
 #define WCHK(call_)                                                                 \
     do {                                                                            \
         e = (call_);                                                                \
         if (e != hipSuccess) { rc = fail(ctx, ATSC_E_HIP, #call_, e); goto done; } \
     } while (0)
-    if (dp->class_count[CLASS_LARGE]) {
-        // The large tier's launch forms depend on every large frame of the stream (large_choices): the rest of the
-        // record headers is walked as well, so that the touched large frames decode as the full decode does them.
-        DPlanHost Hw;
-        const char *why;
-        rc = dplan_parse(body, body_len, has_count, Hw, &why);
-        if (rc) { rc = fail(ctx, rc, why); goto done; }
-        large_choices(dp, Hw.tabs.plans, Hw.frames, Hw.cls);
+    for (int k = 0; k < n_in; ++k) {
+        const uint64_t slice = w[k].byte_end - w[k].byte_begin;
+        rc = dplan_create_range(ctx, hb[k].body + w[k].byte_begin, slice, 0, 0, ~0ull, nullptr, &dp[k]);
+        if (rc) goto done;
+        if (dp[k]->class_count[CLASS_LARGE]) {
+            // The large tier's launch forms depend on every large frame of the stream (large_choices): the rest of the
+            // record headers is walked as well, so that the touched large frames decode as the full decode does them.
+            DPlanHost Hw;
+            const char *why;
+            rc = dplan_parse(hb[k].body, hb[k].len, hb[k].has_count, Hw, &why);
+            if (rc) { rc = fail(ctx, rc, why); goto done; }
+            large_choices(dp[k], Hw.tabs.plans, Hw.frames, Hw.cls);
+        }
+        WCHK(pool_alloc(ctx, (void **)&d_body[k], std::max<uint64_t>(slice, 16)));
+        if (k == 0) WCHK(pool_alloc(ctx, &d_res, out_bytes));
+        WCHK(hipMemcpyAsync(d_body[k], hb[k].body + w[k].byte_begin, slice, hipMemcpyHostToDevice, ws));
+        if (trace) fprintf(stderr, "[window]     h2d records %llu bytes (frames %llu..%llu)\n", (unsigned long long)slice,
+                           (unsigned long long)w[k].frame_begin, (unsigned long long)w[k].frame_end);
+        in[k] = QueryInput{dp[k], d_body[k], w[k].sample_begin};
     }
-    WCHK(pool_alloc(ctx, (void **)&d_body, std::max<uint64_t>(slice, 16)));
-    WCHK(pool_alloc(ctx, &d_res, out_bytes));
-    WCHK(hipMemcpyAsync(d_body, body + w.byte_begin, slice, hipMemcpyHostToDevice, ws));
-    if (trace) fprintf(stderr, "[window]     h2d records %llu bytes (frames %llu..%llu)\n", (unsigned long long)slice,
-                       (unsigned long long)w.frame_begin, (unsigned long long)w.frame_end);
-    rc = enqueue(dp, d_body, begin2.data(), d_res, ws, w.sample_begin);
+    rc = enqueue(in, begin2.data(), d_res, ws);
     if (rc) goto done;
-    WCHK(hipMemcpyAsync(&status, dp->d_status, sizeof(int), hipMemcpyDeviceToHost, ws));
+    for (int k = 0; k < n_in; ++k) WCHK(hipMemcpyAsync(&status[k], dp[k]->d_status, sizeof(int), hipMemcpyDeviceToHost, ws));
     WCHK(hipStreamSynchronize(ws));
-    if (status) { rc = fail_in(ctx, ATSC_E_FORMAT, call, "malformed payload"); goto done; }
+    for (int k = 0; k < n_in; ++k)
+        if (status[k]) { rc = fail_in(ctx, ATSC_E_FORMAT, call, "malformed payload"); goto done; }
     WCHK(hipMemcpyAsync(out, d_res, head_bytes, hipMemcpyDeviceToHost, ws));
     WCHK(hipStreamSynchronize(ws));
     if (head_bytes < out_bytes) {
@@ -412,9 +451,9 @@ static int window_host_call(atsc_ctx *ctx, const char *call, const uint8_t *body
 #undef WCHK
 done:
     if (rc) (void)hipStreamSynchronize(ws);
-    pool_free(ctx, d_body);
+    for (int k = 0; k < n_in; ++k) pool_free(ctx, d_body[k]);
     pool_free(ctx, d_res);
-    atsc_dplan_destroy(dp);
+    for (int k = 0; k < n_in; ++k) atsc_dplan_destroy(dp[k]);
     return rc;
 }
 
@@ -538,12 +577,12 @@ extern "C" int atsc_decompress_window(atsc_ctx *ctx, const uint8_t *body, uint64
     *out_n = 0;
     static const bool trace = getenv("ATSC_TRACE_HOST") != nullptr;
     const uint64_t zero = 0;
+    const HostBody hb{body, body_len, has_count};
     const int rc = window_host_call(
-        ctx, "decompress_window", body, body_len, has_count, 1, &begin, &count, out, count * sizeof(double),
-        count * sizeof(double), trace,
+        ctx, "decompress_window", &hb, 1, 1, &begin, &count, out, count * sizeof(double), count * sizeof(double), trace,
         [&](bool) { return out_cap < count ? fail(ctx, ATSC_E_CAPACITY, "decompress_window: out_cap") : ATSC_OK; },
-        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t) {
-            return atsc_decompress_windows_dev(ctx, dp, d_body, 1, begin2, &count, &zero, (double *)d_res, ws);
+        [&](const QueryInput *in, const uint64_t *begin2, void *d_res, hipStream_t ws) {
+            return atsc_decompress_windows_dev(ctx, in[0].dp, in[0].d_body, 1, begin2, &count, &zero, (double *)d_res, ws);
         },
         [](const void *) { return (size_t)0; });
     if (!rc) *out_n = count;
@@ -589,15 +628,28 @@ static bool spans_touch_large(const atsc_dplan *dp, uint64_t org, const std::vec
     return false;
 }
 
-// Piece length in samples, a multiple of `unit`: the budget less *spill, the room for two large frames that cross the
-// piece's ends (none when the covering intervals touch no large frame), and at least AGG_MIN_PIECE.
+// Piece length in samples, a multiple of `unit`: the budget less the spills, spill[k] being the room for two large frames
+// of input k that cross the piece's ends (none when the covering intervals touch no large frame of it), shared evenly
+// by the n_in inputs' regions, and at least AGG_MIN_PIECE.  Without a budget every input has the default of its own.
+static uint64_t piece_samples(const atsc_ctx *ctx, const QueryInput *in, int n_in, const std::vector<Span> &cov,
+                              uint64_t unit, uint64_t *spill)
+{
+    uint64_t want = 0, spills = 0;
+    for (int k = 0; k < n_in; ++k) {
+        const bool large = spans_touch_large(in[k].dp, in[k].org, cov);
+        spills += spill[k] = large ? 2ull * MAX_FRAME : 0;
+        want += scratch_budget_samples(ctx, large);
+    }
+    if (ctx->agg_budget) want = ctx->agg_budget / sizeof(double);
+    return std::max<uint64_t>(AGG_MIN_PIECE, want > spills ? (want - spills) / n_in / unit * unit : 0);
+}
+
+// (one input)
 static uint64_t piece_samples(const atsc_ctx *ctx, const atsc_dplan *dp, uint64_t org, const std::vector<Span> &cov,
                               uint64_t unit, uint64_t *spill)
 {
-    const bool large = spans_touch_large(dp, org, cov);
-    *spill = large ? 2ull * MAX_FRAME : 0;
-    const uint64_t want = scratch_budget_samples(ctx, large);
-    return std::max<uint64_t>(AGG_MIN_PIECE, want > *spill ? (want - *spill) / unit * unit : 0);
+    const QueryInput in{dp, nullptr, org};
+    return piece_samples(ctx, &in, 1, cov, unit, spill);
 }
 
 // The decode tasks of the piece [S0, S1) into scratch[0, S1 - S0): per touched frame, the hull of its covered samples
@@ -667,19 +719,22 @@ static bool emit_piece_decode(const atsc_dplan *dp, uint64_t org, const std::vec
 static const uint64_t AGG_GAP_TILES = 64;
 
 template <class Q>
-static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
-                      const uint64_t *count, void *d_out, void *stream, uint64_t org, const Q &q);
+static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                      void *d_out, void *stream, const Q &q);
 
 // A query's descriptor: what query_host and query_stream (below) need of it, and for the four reductions over tiles
 // what reduce_dev does.  The front end's part:
 //   CALL                the call's name in the messages
+//   INPUTS              the streams the query reads: 1, or 2 (PairQuery) -- that many bodies, streams or plans
 //   out_bytes(n)        bytes of the result of n windows
 //   check(ctx)          the check of the call's parameters (ctx may be null: then no message is kept)
 //   fill_empty(out, n)  the result of n empty windows
-//   dev(...)            the device call; org: the stream index of the plan's first sample
+//   dev(...)            the device call; org: the stream index of the plan's first sample (INPUTS == 2: the list of
+//                       inputs in its place, see query_dev)
 // What the reductions over tiles differ in: the aggregates (atsc_aggregate.hip), the moments (atsc_moments.hip), the
 // deltas (atsc_delta.hip), the runs (atsc_runs.hip) and the extremes (atsc_extremes.hip).
 //   Tile, tile(t, k)   the tile kernel's task, from the plan's DevAggTile of tile k of the stream
+//   tiles(.., scr, ..) the tile kernel's launch; scr[k]: input k's scratch region
 //   part()             bytes of a partial: a member call, so that a query may size its partials by a parameter of the
 //                      call (ExtQuery, by k); the others hand back their static PART
 //   SIDE               the table both kernels share beside the partials: the windows' first / last samples, which the
@@ -687,6 +742,7 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
 //   CARRY, carried(t)  the tile kernel looks at the sample in front of a tile: the side table is one carry slot (device
 //                      only), which holds the previous piece's last sample for a piece's first tile where carried(t)
 struct AggQuery {
+    static constexpr int INPUTS = 1;
     using Tile = DevAggTile;
     static constexpr const char *CALL = "aggregate_windows", *RES_NAME = "d_stats", *NO_KERNELS = "no aggregate kernels",
                                 *TILES = "launch k_agg_tiles", *COMBINE = "launch k_agg_combine";
@@ -699,9 +755,9 @@ struct AggQuery {
     static constexpr bool CARRY = false;
     static Tile tile(const DevAggTile &t, uint64_t) { return t; }
     static bool carried(const Tile &) { return false; }
-    static hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *side, hipStream_t s)
+    static hipError_t tiles(const Tile *t, uint32_t n, const double *const *scr, void *part, void *side, hipStream_t s)
     {
-        return launch_agg_tiles(t, n, scr, (DevAggPart *)part, (double *)side, s);
+        return launch_agg_tiles(t, n, scr[0], (DevAggPart *)part, (double *)side, s);
     }
     static hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *side, void *out, hipStream_t s)
     {
@@ -722,13 +778,15 @@ struct AggQuery {
     int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
             const uint64_t *count, void *d_res, void *stream, uint64_t org) const
     {
-        return reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
+        const QueryInput in{dp, d_body, org};
+        return reduce_dev(ctx, &in, n_windows, begin, count, d_res, stream, *this);
     }
 };
 // the tile task of the moments, the runs and the extremes, whose kernels take the tile's place in the stream
 static DevPosTile pos_tile(const DevAggTile &t, uint64_t k) { return DevPosTile{t.src, t.dst, k * AGG_TILE, t.lo, t.hi}; }
 
 struct MomQuery {
+    static constexpr int INPUTS = 1;
     using Tile = DevPosTile;
     static constexpr const char *CALL = "moments_windows", *RES_NAME = "d_out", *NO_KERNELS = "no moments kernels",
                                 *TILES = "launch k_mom_tiles", *COMBINE = "launch k_mom_combine";
@@ -741,9 +799,9 @@ struct MomQuery {
     static constexpr bool CARRY = false;
     static Tile tile(const DevAggTile &t, uint64_t k) { return pos_tile(t, k); }
     static bool carried(const Tile &) { return false; }
-    static hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s)
+    static hipError_t tiles(const Tile *t, uint32_t n, const double *const *scr, void *part, void *, hipStream_t s)
     {
-        return launch_mom_tiles(t, n, scr, (DevMomPart *)part, s);
+        return launch_mom_tiles(t, n, scr[0], (DevMomPart *)part, s);
     }
     static hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *side, void *out, hipStream_t s)
     {
@@ -763,11 +821,13 @@ struct MomQuery {
     int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
             const uint64_t *count, void *d_res, void *stream, uint64_t org) const
     {
-        return reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
+        const QueryInput in{dp, d_body, org};
+        return reduce_dev(ctx, &in, n_windows, begin, count, d_res, stream, *this);
     }
 };
 
 struct DltQuery {
+    static constexpr int INPUTS = 1;
     using Tile = DevDltTile;
     static constexpr const char *CALL = "delta_windows", *RES_NAME = "d_out", *NO_KERNELS = "no delta kernels",
                                 *TILES = "launch k_dlt_tiles", *COMBINE = "launch k_dlt_combine";
@@ -786,9 +846,9 @@ struct DltQuery {
         return Tile{t.src, t.dst, t.lo, t.hi, cont | (cont && t.src == 0 ? (uint32_t)DLT_CARRY : 0u), 0};
     }
     static bool carried(const Tile &t) { return (t.flags & DLT_CARRY) != 0; }
-    static hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *side, hipStream_t s)
+    static hipError_t tiles(const Tile *t, uint32_t n, const double *const *scr, void *part, void *side, hipStream_t s)
     {
-        return launch_dlt_tiles(t, n, scr, (const double *)side, (DevDltPart *)part, s);
+        return launch_dlt_tiles(t, n, scr[0], (const double *)side, (DevDltPart *)part, s);
     }
     static hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *, void *out, hipStream_t s)
     {
@@ -807,7 +867,8 @@ struct DltQuery {
     int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
             const uint64_t *count, void *d_res, void *stream, uint64_t org) const
     {
-        return reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
+        const QueryInput in{dp, d_body, org};
+        return reduce_dev(ctx, &in, n_windows, begin, count, d_res, stream, *this);
     }
 };
 
@@ -822,6 +883,7 @@ static void run_empty_record(atsc_window_runs &r)
 // members, which reduce_dev hands to tiles() by calling it on that object.  No carry: the merge joins a run across two
 // tiles, whichever pieces they lie in.
 struct RunQuery {
+    static constexpr int INPUTS = 1;
     using Tile = DevPosTile;
     static constexpr const char *CALL = "runs_windows", *RES_NAME = "d_out", *NO_KERNELS = "no runs kernels",
                                 *TILES = "launch k_run_tiles", *COMBINE = "launch k_run_combine";
@@ -836,9 +898,9 @@ struct RunQuery {
     static bool have() { return launch_run_tiles && launch_run_combine; }
     static Tile tile(const DevAggTile &t, uint64_t k) { return pos_tile(t, k); }
     static bool carried(const Tile &) { return false; }
-    hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s) const
+    hipError_t tiles(const Tile *t, uint32_t n, const double *const *scr, void *part, void *, hipStream_t s) const
     {
-        return launch_run_tiles(t, n, scr, op, limit, (DevRunPart *)part, s);
+        return launch_run_tiles(t, n, scr[0], op, limit, (DevRunPart *)part, s);
     }
     static hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *side, void *out, hipStream_t s)
     {
@@ -860,7 +922,8 @@ struct RunQuery {
             const uint64_t *count, void *d_res, void *stream, uint64_t org) const
     {
         const int rc = check(ctx);
-        return rc ? rc : reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
+        const QueryInput in{dp, d_body, org};
+        return rc ? rc : reduce_dev(ctx, &in, n_windows, begin, count, d_res, stream, *this);
     }
 };
 
@@ -879,6 +942,7 @@ static void ext_empty_record(void *rec, uint32_t k)
 // partials, which have the record's layout (2 + 4 k words) with positions as stream indices, so that a shared mid
 // tile's partial serves every window that shares it; the final combine pass subtracts the window's begin.  No carry.
 struct ExtQuery {
+    static constexpr int INPUTS = 1;
     using Tile = DevPosTile;
     static constexpr const char *CALL = "extremes_windows", *RES_NAME = "d_out", *NO_KERNELS = "no extremes kernels",
                                 *TILES = "launch k_ext_tiles", *COMBINE = "launch k_ext_combine";
@@ -891,9 +955,9 @@ struct ExtQuery {
     static bool have() { return launch_ext_tiles && launch_ext_combine; }
     static Tile tile(const DevAggTile &t, uint64_t kt) { return pos_tile(t, kt); }
     static bool carried(const Tile &) { return false; }
-    hipError_t tiles(const Tile *t, uint32_t n, const double *scr, void *part, void *, hipStream_t s) const
+    hipError_t tiles(const Tile *t, uint32_t n, const double *const *scr, void *part, void *, hipStream_t s) const
     {
-        return launch_ext_tiles(t, n, scr, k, part, s);
+        return launch_ext_tiles(t, n, scr[0], k, part, s);
     }
     hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *side, void *out, hipStream_t s) const
     {
@@ -914,30 +978,94 @@ struct ExtQuery {
             const uint64_t *count, void *d_res, void *stream, uint64_t org) const
     {
         const int rc = check(ctx);
-        return rc ? rc : reduce_dev(ctx, dp, d_body, n_windows, begin, count, d_res, stream, org, *this);
+        const QueryInput in{dp, d_body, org};
+        return rc ? rc : reduce_dev(ctx, &in, n_windows, begin, count, d_res, stream, *this);
     }
 };
 
-// The device call of a reduction over tiles (Q: AggQuery, MomQuery, DltQuery, RunQuery or ExtQuery; the kernels named
-// below are the aggregates').  q: the query's parameters of this call, where it has any (RunQuery, ExtQuery).
+// The pair moments (atsc_pair.hip): the one reduction over two inputs.  Its kernels read the same slots of the two
+// inputs' regions; the partial is the moments' node with the second stream's value where that has the position.  No
+// position is counted from a window's begin: no side table.  No carry.
+struct PairQuery {
+    static constexpr int INPUTS = 2;
+    using Tile = DevPosTile;
+    static constexpr const char *CALL = "pair_windows", *RES_NAME = "d_out", *NO_KERNELS = "no pair kernels",
+                                *TILES = "launch k_pair_tiles", *COMBINE = "launch k_pair_combine";
+    static constexpr size_t PART = sizeof(DevMomPart);
+    static size_t part() { return PART; }
+    static constexpr bool SIDE_BEGINS = false, NO_SIDE = true;
+    static constexpr bool CARRY = false;
+    static constexpr QueryKind KIND = Q_PAIR;
+    static const DecodeCaller &who() { return BY_PAIR; }
+    static bool have() { return launch_pair_tiles && launch_pair_combine; }
+    static Tile tile(const DevAggTile &t, uint64_t k) { return pos_tile(t, k); }
+    static bool carried(const Tile &) { return false; }
+    static hipError_t tiles(const Tile *t, uint32_t n, const double *const *scr, void *part, void *, hipStream_t s)
+    {
+        return launch_pair_tiles(t, n, scr[0], scr[1], (DevMomPart *)part, s);
+    }
+    static hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *, void *out, hipStream_t s)
+    {
+        return launch_pair_combine(c, n, (DevMomPart *)part, out, s);
+    }
+    static size_t out_bytes(uint64_t n) { return n * sizeof(atsc_window_pair); }
+    static int check(atsc_ctx *) { return ATSC_OK; }
+    static void fill_empty(void *out, uint64_t n)
+    {
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (uint64_t i = 0; i < n; ++i) {
+            atsc_window_pair &r = ((atsc_window_pair *)out)[i];
+            r.count = 0;
+            r.mean_x = r.m2_x = r.mean_y = r.m2_y = r.c_xy = nan;
+        }
+    }
+    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+            void *d_res, void *stream) const
+    {
+        return reduce_dev(ctx, in, n_windows, begin, count, d_res, stream, *this);
+    }
+};
+
+// The device call of a reduction over tiles (Q: AggQuery, MomQuery, DltQuery, RunQuery, ExtQuery or PairQuery; the
+// kernels named below are the aggregates').  q: the query's parameters of this call, where it has any (RunQuery,
+// ExtQuery).  in: the Q::INPUTS streams it reads, each a plan, its record bytes on the device and the stream index of
+// the plan's first sample; begin[] counts from in[0].org.  Everything below is computed once, in the stream's index,
+// which the inputs share; per piece every input is decoded into a scratch region of its own, with its own decode tasks
+// and spill slots, and the tile kernel gets every region's pointer.  The call's tables, partials and regions are
+// in[0].dp's (res[Q::KIND]).
 // Host work: covering intervals, pieces, the decode tasks of every piece (one per touched frame: its
 // covered samples' hull in the piece), the tile tasks (a full tile that windows cover past their first tile and before
 // their last one is reduced once, into a shared partial; every window's first and last tile are reduced for it alone)
 // and the combine passes (groups of 64 partials until one is left per window).  All of it goes up in one copy; then,
 // per piece, the window decode's launchers into scratch and k_agg_tiles, and k_agg_combine once per pass.
-// org: the stream index of the plan's first sample (a plan of the touched records only, in the host call): tiles lie at
-// multiples of AGG_TILE in the stream's index, not the plan's.  Indices below are the stream's unless named otherwise.
+// org (of an input): the stream index of the plan's first sample (a plan of the touched records only, in the host call):
+// tiles lie at multiples of AGG_TILE in the stream's index, not the plan's.  Indices below are the stream's unless named otherwise.
 // Q::CARRY: a piece's decode overwrites the scratch, and with it the sample in front of the next piece's first tile.
 // Where a window runs on into the next piece, an 8-byte copy behind the piece's tile launch (stream-ordered: behind
 // the launch that read the slot's previous value, in front of the next decode) takes the piece's last sample to the
 // carry slot in the call's tables.  The tile kernel never writes that slot.
+// A query whose kernels share no table beside the partials says so (PairQuery::NO_SIDE).
+template <class Q, class = void>
+struct NoSide : std::false_type {};
 template <class Q>
-static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
-                      const uint64_t *count, void *d_out, void *stream, uint64_t org, const Q &q)
+struct NoSide<Q, std::void_t<decltype(Q::NO_SIDE)>> : std::true_type {};
+
+template <class Q>
+static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                      void *d_out, void *stream, const Q &q)
 {
-    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_out)))
-        return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
-    int rc = check_windows(ctx, Q::CALL, dp, d_out, Q::RES_NAME, n_windows, begin, count, 0xfffffffeull);
+    constexpr int NI = Q::INPUTS;
+    static_assert(NI >= 1 && NI <= MAX_INPUTS, "one or two inputs");
+    if (!ctx) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
+    for (int k = 0; k < NI; ++k)
+        if (!in[k].dp || (n_windows && !in[k].d_body)) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
+    if (n_windows && (!begin || !count || !d_out)) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
+    for (int k = 1; k < NI; ++k)
+        if (in[k].dp->ctx != in[0].dp->ctx) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "plans of different contexts");
+    const uint64_t org = in[0].org;  // begin[] counts from here
+    int rc = ATSC_OK;
+    for (int k = 0; k < NI && !rc; ++k)
+        rc = check_windows(ctx, Q::CALL, in[k].dp, d_out, Q::RES_NAME, n_windows, begin, count, 0xfffffffeull, org, in[k].org);
     if (rc || n_windows == 0) return rc;
     if (!launch_decompress_window || !launch_window_gather || !Q::have()) return fail_in(ctx, ATSC_E_UNSUPPORTED, Q::CALL, Q::NO_KERNELS);
     hipStream_t s = (hipStream_t)stream;
@@ -948,8 +1076,8 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
     for (uint64_t i = 0; i < W; ++i)
         if (count[i]) cov.emplace_back(org + begin[i], org + begin[i] + count[i]);
     merge_spans(cov);
-    uint64_t spill;
-    const uint64_t piece_tiles = piece_samples(ctx, dp, org, cov, T, &spill) / T;
+    uint64_t spill[MAX_INPUTS];
+    const uint64_t piece_tiles = piece_samples(ctx, in, NI, cov, T, spill) / T;
     struct Piece {
         uint64_t k0, k1;  // tiles [k0, k1): samples [k0 T, k1 T) at scratch[0, (k1 - k0) T)
     };
@@ -1031,19 +1159,21 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
             live.swap(next);
         }
     }
-    // decode tasks of every piece (emit_piece_decode) and its tile tasks
-    std::vector<PieceDecode> pdec(pcs.size());
+    // decode tasks of every piece (emit_piece_decode), once per input, and its tile tasks
+    std::vector<PieceDecode> pdec[MAX_INPUTS];
     std::vector<size_t> tile_at(pcs.size());
     std::vector<uint32_t> tile_n(pcs.size());
     std::vector<char> carry_in(pcs.size(), 0);  // the piece's first tile reads the previous piece's last sample
-    DecodeTasks D;
+    DecodeTasks D[MAX_INPUTS];
     std::vector<typename Q::Tile> tiles;
     tiles.reserve(tt.size());
-    size_t ci = 0, ti = 0;
+    size_t ci[MAX_INPUTS] = {}, ti = 0;
+    for (int k = 0; k < NI; ++k) pdec[k].resize(pcs.size());
     for (size_t p = 0; p < pcs.size(); ++p) {
         tile_at[p] = tiles.size();
-        if (!emit_piece_decode(dp, org, cov, ci, pcs[p].k0 * T, pcs[p].k1 * T, region, D, pdec[p]))
-            return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "internal error (spill slots)");
+        for (int k = 0; k < NI; ++k)
+            if (!emit_piece_decode(in[k].dp, in[k].org, cov, ci[k], pcs[p].k0 * T, pcs[p].k1 * T, region, D[k], pdec[k][p]))
+                return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "internal error (spill slots)");
         for (; ti < tt.size() && tt[ti].k < pcs[p].k1; ++ti) {
             DevAggTile t = tt[ti].t;
             t.src = (tt[ti].k - pcs[p].k0) * T;
@@ -1061,29 +1191,42 @@ static int reduce_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
         wb.resize(W);
         for (uint64_t i = 0; i < W; ++i) wb[i] = org + begin[i];
     }
-    QueryRes &R = dp->res[Q::KIND];
+    QueryRes &R = in[0].dp->res[Q::KIND];
     HIPCHK(ctx, R.wait());
-    // one upload: the decode tasks, tile tasks, combine tasks (and the begins); behind them (device only) the partials
-    // (and the windows' first / last samples, or the carry slot)
+    // one upload: the decode tasks of every input, tile tasks, combine tasks (and the begins); behind them (device only)
+    // the partials (and the windows' first / last samples, or the carry slot)
     Upload up;
-    D.place(up);
+    for (int k = 0; k < NI; ++k) D[k].place(up);
     const size_t off_tiles = up.add(tiles), off_comb = up.add(comb);
     const size_t off_begins = Q::SIDE_BEGINS ? up.add(wb) : 0;
     const size_t off_part = up.device_only(part_n * q.part());
-    const size_t off_side = Q::SIDE_BEGINS ? off_begins : up.device_only(Q::CARRY ? sizeof(double) : 2 * W * sizeof(double));
-    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, region + (uint64_t)MAX_FRAME * D.spills_used));
+    const size_t off_side = Q::SIDE_BEGINS    ? off_begins
+                            : NoSide<Q>::value ? off_part
+                                               : up.device_only(Q::CARRY ? sizeof(double) : 2 * W * sizeof(double));
+    // every input's region and behind it the spill slots it uses; region and MAX_FRAME are even numbers of doubles, so
+    // every region begins at a multiple of 16 bytes, as the tile kernels' 16-byte loads need
+    uint64_t scr_at[MAX_INPUTS], scr_n = 0;
+    for (int k = 0; k < NI; ++k) {
+        scr_at[k] = scr_n;
+        scr_n += region + (uint64_t)MAX_FRAME * D[k].spills_used;
+    }
+    static_assert(AGG_TILE % 2 == 0 && MAX_FRAME % 2 == 0, "16-byte aligned regions");
+    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, scr_n));
     unsigned char *d = R.d;
     up.stage(R.h);
     HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
-    double *scr = R.scratch;
+    double *scr[MAX_INPUTS];
+    for (int k = 0; k < NI; ++k) scr[k] = R.scratch + scr_at[k];
     void *part = d + off_part, *side = d + off_side;
     for (size_t p = 0; p < pcs.size(); ++p) {
-        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, Q::who());
-        if (rc) return rc;
+        for (int k = 0; k < NI; ++k) {
+            rc = launch_piece_decode(ctx, in[k].dp, in[k].d_body, d, D[k], pdec[k][p], scr[k], scr[k], scr[k], s, Q::who());
+            if (rc) return rc;
+        }
         const hipError_t e = q.tiles((const typename Q::Tile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, side, s);
         if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, Q::TILES, e);
         if (Q::CARRY && p + 1 < pcs.size() && carry_in[p + 1])
-            HIPCHK(ctx, hipMemcpyAsync(side, scr + (pcs[p].k1 - pcs[p].k0) * T - 1, sizeof(double), hipMemcpyDeviceToDevice, s));
+            HIPCHK(ctx, hipMemcpyAsync(side, scr[0] + (pcs[p].k1 - pcs[p].k0) * T - 1, sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     for (size_t a = 0; a + 1 < pass_at.size(); ++a) {
         const hipError_t e = q.combine((const DevAggComb *)(d + off_comb) + pass_at[a], (uint32_t)(pass_at[a + 1] - pass_at[a]),
@@ -1113,26 +1256,46 @@ static size_t result_used_bytes(const Q &q, const void *head, uint64_t n)
     else return q.out_bytes(n);
 }
 
-// The host call of a query: the argument check, the query's own, then window_host_call into its device call.
+// The device call of a query on the plans in[0 .. Q::INPUTS): a query over one stream takes its plan, bytes and origin.
 template <class Q>
-static int query_host(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
-                      const uint64_t *begin, const uint64_t *count, void *out, const Q &q)
+static int query_dev(const Q &q, atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin,
+                     const uint64_t *count, void *d_res, void *stream)
 {
-    if (!ctx || !body || (n_windows && (!begin || !count || !out))) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
+    if constexpr (Q::INPUTS == 1) return q.dev(ctx, in[0].dp, in[0].d_body, n_windows, begin, count, d_res, stream, in[0].org);
+    else return q.dev(ctx, in, n_windows, begin, count, d_res, stream);
+}
+
+// The host call of a query over the bodies hb[0 .. Q::INPUTS): the argument check, the query's own, then
+// window_host_call into its device call.
+template <class Q>
+static int query_host(atsc_ctx *ctx, const HostBody *hb, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                      void *out, const Q &q)
+{
+    bool bodies = true;
+    for (int k = 0; k < Q::INPUTS; ++k) bodies = bodies && hb[k].body;
+    if (!ctx || !bodies || (n_windows && (!begin || !count || !out))) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
     const int rc = q.check(ctx);
     if (rc) return rc;
     if (n_windows == 0) return ATSC_OK;
     return window_host_call(
-        ctx, Q::CALL, body, body_len, has_count, n_windows, begin, count, out, q.out_bytes(n_windows),
-        result_head_bytes(q, n_windows), false,
+        ctx, Q::CALL, hb, Q::INPUTS, n_windows, begin, count, out, q.out_bytes(n_windows), result_head_bytes(q, n_windows),
+        false,
         [&](bool any) {
             if (!any) q.fill_empty(out, n_windows);
             return ATSC_OK;
         },
-        [&](atsc_dplan *dp, const uint8_t *d_body, const uint64_t *begin2, void *d_res, hipStream_t ws, uint64_t org) {
-            return q.dev(ctx, dp, d_body, n_windows, begin2, count, d_res, ws, org);
+        [&](const QueryInput *in, const uint64_t *begin2, void *d_res, hipStream_t ws) {
+            return query_dev(q, ctx, in, n_windows, begin2, count, d_res, ws);
         },
         [&](const void *head) { return result_used_bytes(q, head, n_windows); });
+}
+// (one body)
+template <class Q>
+static int query_host(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                      const uint64_t *begin, const uint64_t *count, void *out, const Q &q)
+{
+    const HostBody hb{body, body_len, has_count};
+    return query_host(ctx, &hb, n_windows, begin, count, out, q);
 }
 
 extern "C" int atsc_aggregate_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
@@ -1192,6 +1355,59 @@ extern "C" int atsc_moments_fit(const atsc_window_moments *m, uint64_t n, atsc_w
         r.slope = a.t_m2 > 0.0 ? a.c_tx / a.t_m2 : nan;
         const double st = r.slope * a.t_mean;
         r.intercept = a.mean - st;
+    }
+    return ATSC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// windowed pair moments: centred moments and co-moment of the values of two streams over sample windows (atsc_pair.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" int atsc_pair_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp_x, const uint8_t *d_body_x, const atsc_dplan *dp_y,
+                                     const uint8_t *d_body_y, uint64_t n_windows, const uint64_t *begin,
+                                     const uint64_t *count, atsc_window_pair *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    const QueryInput in[2] = {{dp_x, d_body_x, 0}, {dp_y, d_body_y, 0}};
+    return PairQuery().dev(ctx, in, n_windows, begin, count, d_out, stream);
+    ATSC_API_END
+}
+
+extern "C" int atsc_pair_windows(atsc_ctx *ctx, const uint8_t *body_x, uint64_t len_x, int has_count_x, const uint8_t *body_y,
+                                 uint64_t len_y, int has_count_y, uint64_t n_windows, const uint64_t *begin,
+                                 const uint64_t *count, atsc_window_pair *out)
+{
+    ATSC_API_BEGIN
+    const HostBody hb[2] = {{body_x, len_x, has_count_x}, {body_y, len_y, has_count_y}};
+    return query_host(ctx, hb, n_windows, begin, count, out, PairQuery());
+    ATSC_API_END
+}
+
+// Host only: what a caller reads off the pair moments.  Each line is one rounded operation, as include/atsc_hip.h states it.
+extern "C" int atsc_pair_fit(const atsc_window_pair *p, uint64_t n, atsc_window_pair_fit *out)
+{
+    if (n && (!p || !out)) return ATSC_E_INVALID;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (uint64_t i = 0; i < n; ++i) {
+        const atsc_window_pair &a = p[i];
+        atsc_window_pair_fit &r = out[i];
+        if (a.count == 0) {
+            r.covariance = r.sample_covariance = r.correlation = r.slope = r.intercept = r.r2 = r.mean_diff = nan;
+            continue;
+        }
+        r.covariance = a.c_xy / (double)a.count;
+        r.sample_covariance = a.count < 2 ? nan : a.c_xy / (double)(a.count - 1);
+        if (a.m2_x > 0.0 && a.m2_y > 0.0) {
+            const double sx = std::sqrt(a.m2_x), sy = std::sqrt(a.m2_y);
+            const double c = (a.c_xy / sx) / sy;
+            r.correlation = c > 1.0 ? 1.0 : c < -1.0 ? -1.0 : c;  // (a NaN stays)
+        } else {
+            r.correlation = nan;
+        }
+        r.slope = a.m2_x > 0.0 ? a.c_xy / a.m2_x : nan;
+        const double sm = r.slope * a.mean_x;
+        r.intercept = a.mean_y - sm;
+        r.r2 = r.correlation * r.correlation;
+        r.mean_diff = a.mean_x - a.mean_y;
     }
     return ATSC_OK;
 }
@@ -1535,6 +1751,7 @@ static int quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bo
 
 // the quantiles' descriptor (see AggQuery): the levels and the method are the call's parameters
 struct QntQuery {
+    static constexpr int INPUTS = 1;
     static constexpr const char *CALL = "quantile_windows";
     uint32_t n_q;
     const double *q;
@@ -1728,6 +1945,7 @@ static int histogram_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
 
 // the histograms' descriptor (see AggQuery): the edges and the closed side are the call's parameters
 struct HstQuery {
+    static constexpr int INPUTS = 1;
     static constexpr const char *CALL = "histogram_windows";
     uint32_t n_edges;
     const double *edges;
@@ -1906,6 +2124,7 @@ static int select_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
 // the select's descriptor (see AggQuery): the condition and the entries' capacity are the call's parameters.  Its result
 // is a block whose use depends on the data (BlockResult): the offsets say how many entries there are.
 struct SelQuery {
+    static constexpr int INPUTS = 1;
     static constexpr const char *CALL = "select_windows";
     int op;
     double limit;
@@ -1986,24 +2205,41 @@ extern "C" int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uin
     ATSC_API_END
 }
 
-// The stream call of a query.  The query's own check comes without a context (it has never left a message on the
-// stream's) and before the pending chunks are compressed; a stream without a frame gets the query's empty result.
+// The stream call of a query over the streams st[0 .. Q::INPUTS), which must share a context.  The query's own check
+// comes without a context (it has never left a message on the stream's) and before the pending chunks are compressed; a
+// stream without a frame admits only empty windows at 0, and where every stream is one they get the query's empty result.
 template <class Q>
-static int query_stream(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *out, const Q &q)
+static int query_stream(atsc_stream *const *st, uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *out,
+                        const Q &q)
 {
-    if (!s || (n_windows && (!begin || !count || !out))) return ATSC_E_INVALID;
+    for (int k = 0; k < Q::INPUTS; ++k)
+        if (!st[k]) return ATSC_E_INVALID;
+    if (n_windows && (!begin || !count || !out)) return ATSC_E_INVALID;
     int rc = q.check(nullptr);
     if (rc) return rc;
-    std::vector<uint8_t> body;
-    atsc_ctx *ctx = nullptr;
-    rc = stream_body(s, body, &ctx);
-    if (rc) return rc;
-    if (body.empty()) {
+    std::vector<uint8_t> body[MAX_INPUTS];
+    atsc_ctx *ctx[MAX_INPUTS] = {};
+    HostBody hb[MAX_INPUTS];
+    bool none = false;
+    for (int k = 0; k < Q::INPUTS; ++k) {
+        rc = stream_body(st[k], body[k], &ctx[k]);
+        if (rc) return rc;
+        if (ctx[k] != ctx[0]) return fail_in(ctx[0], ATSC_E_INVALID, Q::CALL, "streams of different contexts");
+        none = none || body[k].empty();
+        hb[k] = HostBody{body[k].data(), body[k].size(), 0};
+    }
+    if (none) {
         if (!only_empty_at_zero(n_windows, begin, count)) return ATSC_E_INVALID;
         q.fill_empty(out, n_windows);
         return ATSC_OK;
     }
-    return query_host(ctx, body.data(), body.size(), 0, n_windows, begin, count, out, q);
+    return query_host(ctx[0], hb, n_windows, begin, count, out, q);
+}
+// (one stream)
+template <class Q>
+static int query_stream(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *out, const Q &q)
+{
+    return query_stream(&s, n_windows, begin, count, out, q);
 }
 
 extern "C" int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
@@ -2067,5 +2303,14 @@ extern "C" int atsc_stream_select_windows(atsc_stream *s, uint64_t n_windows, co
 {
     ATSC_API_BEGIN
     return query_stream(s, n_windows, begin, count, out, SelQuery{op, limit, cap});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_pair_windows(atsc_stream *x, atsc_stream *y, uint64_t n_windows, const uint64_t *begin,
+                                        const uint64_t *count, atsc_window_pair *out)
+{
+    ATSC_API_BEGIN
+    atsc_stream *const st[2] = {x, y};
+    return query_stream(st, n_windows, begin, count, out, PairQuery());
     ATSC_API_END
 }

@@ -23,6 +23,12 @@ WINDOW_MOMENTS = np.dtype([("count", "<u8"), ("mean", "<f8"), ("m2", "<f8"), ("t
 # atsc_window_fit: what atsc_moments_fit reads off them, 56 bytes; slope is in value units per sample
 WINDOW_FIT = np.dtype([("mean", "<f8"), ("variance", "<f8"), ("stddev", "<f8"), ("sample_variance", "<f8"),
                        ("sample_stddev", "<f8"), ("slope", "<f8"), ("intercept", "<f8")])
+# atsc_window_pair (include/atsc_hip.h): the centred moments and co-moment of two streams over one window, 48 bytes
+WINDOW_PAIR = np.dtype([("count", "<u8"), ("mean_x", "<f8"), ("m2_x", "<f8"), ("mean_y", "<f8"), ("m2_y", "<f8"),
+                        ("c_xy", "<f8")])
+# atsc_window_pair_fit: what atsc_pair_fit reads off them, 56 bytes; slope and intercept are of y on x
+WINDOW_PAIR_FIT = np.dtype([("covariance", "<f8"), ("sample_covariance", "<f8"), ("correlation", "<f8"), ("slope", "<f8"),
+                            ("intercept", "<f8"), ("r2", "<f8"), ("mean_diff", "<f8")])
 # atsc_window_delta (include/atsc_hip.h): what the samples of one window do from one to the next, 64 bytes
 WINDOW_DELTA = np.dtype([("pairs", "<u8"), ("rises", "<u8"), ("falls", "<u8"), ("up", "<f8"), ("down", "<f8"),
                          ("after_falls", "<f8"), ("max_rise", "<f8"), ("max_fall", "<f8")])
@@ -84,7 +90,9 @@ def _levels(levels):
 #   params  the call's own arguments -> their C arguments, which stand between the windows and the result
 #   block   None, or for a result that is one block whose size is not a number of records (the select's offsets and
 #           entries): (n_windows, cargs) -> its bytes; the result is then that many bytes as uint64 words, whole
-_Query = collections.namedtuple("_Query", "stem dtype extra params block", defaults=(None,))
+#   inputs  the streams the query reads, 1 or 2: each surface takes that many records, (plan, device bytes) or streams,
+#           the first as its own and the others through `others`, in front of the windows in the C call
+_Query = collections.namedtuple("_Query", "stem dtype extra params block inputs", defaults=(None, 1))
 
 
 def _no_params():
@@ -142,6 +150,7 @@ def _array_params(values, flag):
 _AGGREGATE = _Query("aggregate_windows", WINDOW_STATS, None, _no_params)
 _MOMENTS = _Query("moments_windows", WINDOW_MOMENTS, None, _no_params)
 _DELTA = _Query("delta_windows", WINDOW_DELTA, None, _no_params)
+_PAIR = _Query("pair_windows", WINDOW_PAIR, None, _no_params, inputs=2)
 _RUNS = _Query("runs_windows", WINDOW_RUNS, None, _runs_params)
 _EXTREMES = _Query("extremes_windows", _extremes_dtype, None, _extremes_params)
 _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _select_block)
@@ -178,26 +187,38 @@ def _query_rows(q, out, n):
     return out if q.block else out[:n]
 
 
-def _query_host(q, ctx, records, begins, counts, has_count, *params):
-    """Context.*_windows_host: atsc_<stem> over the records"""
-    b = np.frombuffer(bytes(records), dtype=np.uint8)
+def _query_others(q, others):
+    if len(others) != q.inputs - 1:
+        raise ValueError("%s reads %d streams" % (q.stem, q.inputs))
+    return others
+
+
+def _query_host(q, ctx, records, begins, counts, has_count, *params, others=()):
+    """Context.*_windows_host: atsc_<stem> over the records (others: the further streams' records)"""
+    arrays = [np.frombuffer(bytes(r), dtype=np.uint8) for r in (records,) + tuple(_query_others(q, others))]
+    bodies = []
+    for b in arrays:
+        bodies += [b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count)]
     wb, pb, wc, pc = _windows(begins, counts)
     cargs = q.params(*params)
     fn = getattr(capi.lib(), "atsc_" + q.stem)
     out, po = _query_result(q, len(wb), cargs, fn, params)
-    rc = fn(ctx._h, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), int(has_count), len(wb), pb, pc, *cargs, po)
+    rc = fn(ctx._h, *bodies, len(wb), pb, pc, *cargs, po)
     capi.check(rc, ctx._h)
     return _query_rows(q, out, len(wb))
 
 
-def _query_dev(q, dplan, d_body, begins, counts, d_out, stream, *params):
-    """DPlan.*_windows: atsc_<stem>_dev into the device tensor d_out"""
+def _query_dev(q, dplan, d_body, begins, counts, d_out, stream, *params, others=()):
+    """DPlan.*_windows: atsc_<stem>_dev into the device tensor d_out (others: the further streams' (plan, device bytes))"""
     b, pb, c, pc = _windows(begins, counts)
     cargs = q.params(*params)
     assert q.extra is None or d_out.element_size() == 8
     assert d_out.is_contiguous()
     assert d_out.numel() * d_out.element_size() >= _query_bytes(q, len(b), cargs, params)
-    rc = getattr(capi.lib(), "atsc_%s_dev" % q.stem)(dplan.ctx._h, dplan._h, C.c_void_p(d_body.data_ptr()), len(b), pb, pc,
+    plans = [dplan._h, C.c_void_p(d_body.data_ptr())]
+    for dp, body in _query_others(q, others):
+        plans += [dp._h, C.c_void_p(body.data_ptr())]
+    rc = getattr(capi.lib(), "atsc_%s_dev" % q.stem)(dplan.ctx._h, *plans, len(b), pb, pc,
                                                      *cargs, C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
     capi.check(rc, dplan.ctx._h)
 
@@ -220,6 +241,15 @@ def moments_fit(moments):
     m = np.ascontiguousarray(np.atleast_1d(np.asarray(moments, dtype=WINDOW_MOMENTS)))
     out = np.zeros(max(len(m), 1), dtype=WINDOW_FIT)
     capi.check(capi.lib().atsc_moments_fit(C.c_void_p(m.ctypes.data), len(m), C.c_void_p(out.ctypes.data)))
+    return out[: len(m)]
+
+
+def pair_fit(pairs):
+    """-> WINDOW_PAIR_FIT array: population and sample covariance, correlation (clamped to [-1, 1]), the least-squares
+    slope and intercept of y on x, r2 and the difference of the means of every WINDOW_PAIR record (atsc_pair_fit; no GPU)"""
+    m = np.ascontiguousarray(np.atleast_1d(np.asarray(pairs, dtype=WINDOW_PAIR)))
+    out = np.zeros(max(len(m), 1), dtype=WINDOW_PAIR_FIT)
+    capi.check(capi.lib().atsc_pair_fit(C.c_void_p(m.ctypes.data), len(m), C.c_void_p(out.ctypes.data)))
     return out[: len(m)]
 
 
@@ -370,6 +400,11 @@ class Context:
         """-> WINDOW_MOMENTS array: count, mean and the centred moments of value and position of every window
         [begins[i], begins[i] + counts[i]) of the decoded records (atsc_moments_windows)"""
         return _query_host(_MOMENTS, self, records, begins, counts, has_count)
+
+    def pair_windows_host(self, records_x, records_y, begins, counts, has_count=False):
+        """-> WINDOW_PAIR array: count, the means and centred moments of x and y and their co-moment over every window
+        [begins[i], begins[i] + counts[i]) of the two decoded record streams (atsc_pair_windows)"""
+        return _query_host(_PAIR, self, records_x, begins, counts, has_count, others=(records_y,))
 
     def delta_windows_host(self, records, begins, counts, has_count=False):
         """-> WINDOW_DELTA array: the counted pairs of adjacent samples, the rises and falls among them, their sums and
@@ -534,6 +569,12 @@ class DPlan:
         """Enqueues the moments of the windows [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least
         48 bytes per window (atsc_moments_windows_dev; WINDOW_MOMENTS records)"""
         _query_dev(_MOMENTS, self, d_body, begins, counts, d_out, stream)
+
+    def pair_windows(self, d_body, other, other_body, begins, counts, d_out, stream=0):
+        """Enqueues the pair moments of this plan's stream (x) and the plan `other`'s (y, its device bytes other_body)
+        over the windows [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least 48 bytes per window
+        (atsc_pair_windows_dev; WINDOW_PAIR records).  other may be this plan"""
+        _query_dev(_PAIR, self, d_body, begins, counts, d_out, stream, others=((other, other_body),))
 
     def delta_windows(self, d_body, begins, counts, d_out, stream=0):
         """Enqueues the deltas of the windows [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least

@@ -6,8 +6,8 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit  # noqa: F401
-from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _QUANTILE, _RUNS, _SELECT, _query_result, _query_rows, _select_result
+from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit, pair_fit  # noqa: F401
+from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _RUNS, _SELECT, _query_others, _query_result, _query_rows, _select_result
 
 
 def _f64(x):
@@ -27,13 +27,15 @@ def _take_f64(p, n):
     return out
 
 
-def _query_stream(q, stream, begins, counts, *params):
-    """CompressedStream.*_windows: atsc_stream_<stem> (q: the query's description, engine._Query)"""
+def _query_stream(q, stream, begins, counts, *params, others=()):
+    """CompressedStream.*_windows: atsc_stream_<stem> (q: the query's description, engine._Query; others: the further
+    streams)"""
     wb, pb, wc, pc = _windows(begins, counts)
     cargs = q.params(*params)
     fn = getattr(capi.lib(), "atsc_stream_" + q.stem)
     out, po = _query_result(q, len(wb), cargs, fn, params)
-    capi.check(fn(stream._h, len(wb), pb, pc, *cargs, po), stream.ctx._h)
+    handles = [stream._h] + [o._h for o in _query_others(q, others)]
+    capi.check(fn(*handles, len(wb), pb, pc, *cargs, po), stream.ctx._h)
     return _query_rows(q, out, len(wb))
 
 
@@ -123,6 +125,11 @@ class CompressedStream:
     def moments_windows(self, begins, counts):
         """-> WINDOW_MOMENTS array of the windows [begins[i], begins[i] + counts[i]) (atsc_stream_moments_windows)"""
         return _query_stream(_MOMENTS, self, begins, counts)
+
+    def pair_windows(self, other, begins, counts):
+        """-> WINDOW_PAIR array of the windows [begins[i], begins[i] + counts[i]) of this stream (x) and `other` (y)
+        (atsc_stream_pair_windows)"""
+        return _query_stream(_PAIR, self, begins, counts, others=(other,))
 
     def delta_windows(self, begins, counts):
         """-> WINDOW_DELTA array of the windows [begins[i], begins[i] + counts[i]) (atsc_stream_delta_windows)"""

@@ -391,6 +391,73 @@ typedef struct {
 } atsc_window_fit;
 int atsc_moments_fit(const atsc_window_moments *m, uint64_t n, atsc_window_fit *out);
 
+/* Windowed pair moments: per window [begin, begin + count) the centred moments of the values x and y of TWO decoded
+ * streams X and Y over the same index range, and their centred co-moment: what covariance, correlation and the
+ * regression of y on x are read from (atsc_pair_fit).  Sample i of X goes with sample i of Y; the streams may differ in
+ * length, framing, codecs and tiers.  The reduction is the windowed moments' with y where they have the position t, so a
+ * pair of series at 1e9 +- 1e-3 keeps its covariance, and the result is bit-exact: it depends only on the two streams'
+ * samples and the window's (begin, count), not on the other windows, their order, the budget, piece boundaries, either
+ * stream's framing or the device.
+ *   Node   (n, mx, M2x, my, M2y, C).
+ *   Leaf   of stream index i: (1, x[i], 0, y[i], 0, 0); a slot outside the window, or one where x[i] or y[i] is NaN, is
+ *          the empty node (n = 0).
+ *   Merge(a, b)   the moments' rule with t replaced by y: nb == 0: a, bit for bit; na == 0: b; else
+ *          n = na + nb; w = (double)nb / (double)n; f = (double)na * w; dx = mxb - mxa; dy = myb - mya;
+ *          mx = mxa + dx * w; my = mya + dy * w;
+ *          M2x = (M2xa + M2xb) + (dx * dx) * f; M2y = (M2ya + M2yb) + (dy * dy) * f; C = (Ca + Cb) + (dx * dy) * f
+ *          -- every operation one correctly rounded f64 + - * /, evaluated as written, never fused.
+ *   Tree   the moments' tree: tiles of 2048 slots at multiples of 2048 in the stream index, the in-tile order of the
+ *          aggregate sum, then pairwise over the window's tile partials (steps 1 to 3 under "Windowed moments").
+ *   Result count = n, mean_x = mx, m2_x = M2x, mean_y = my, m2_y = M2y, c_xy = C; when count == 0 all five doubles are
+ *          NaN.  +-Inf samples give what IEEE gives under these rules; where the rule yields NaN, any NaN bit pattern
+ *          conforms.
+ * Two consequences: with X and Y swapped the record is the same with the x and y fields swapped, bit for bit; with Y
+ * the same stream as X, mean_y == mean_x and m2_y == c_xy == m2_x, and they are atsc_moments_windows' mean and m2 of that
+ * stream, bit for bit.
+ * With u = 2^-53, L = max(1, ceil(log2 count)), kappa_x = sqrt(1 + count mean_x^2 / m2_x) and kappa_y alike, for finite
+ * data:
+ *   |mean_x - exact| <= (L + 2) u mean|x|;            |m2_x - exact| <= (L + 2) u kappa_x m2_x;    (and for y)
+ *   |c_xy - exact| <= (L + 2) u kappa_x kappa_y sqrt(m2_x m2_y);
+ * m2_x == 0 and c_xy == 0 exactly where x is constant over the window's counted samples (and for y).
+ * Validation and the other semantics are atsc_moments_windows_dev's, for both streams: a window beyond the end of EITHER
+ * stream gives ATSC_E_INVALID with nothing written; payloads are checked only of the frames a window touches; windows
+ * may overlap and come in any order; count == 0 and n_windows == 0 are valid; windows may be of any length. */
+typedef struct {
+    uint64_t count; /* samples of the window where neither x nor y is NaN */
+    double mean_x;  /* of x over those samples */
+    double m2_x;    /* sum (x - mean_x)^2 */
+    double mean_y;  /* of y over those samples */
+    double m2_y;    /* sum (y - mean_y)^2 */
+    double c_xy;    /* sum (x - mean_x)(y - mean_y) */
+} atsc_window_pair; /* 48 bytes */
+/* d_out[i] holds window i.  begin / count are HOST arrays; d_body_x, d_body_y and d_out are device memory (d_out 8-byte
+ * aligned).  The two plans must belong to one context (else ATSC_E_INVALID); dp_x == dp_y is allowed.  Enqueued on
+ * `stream`, not synchronised.  A malformed payload inside a window sets the status word of the plan it belongs to.
+ * dp_x keeps the call's tables, partials and scratch -- one region of decoded samples per stream, which together stay
+ * inside the budget of atsc_ctx_set_aggregate_scratch (raised to one piece's minimum per stream): the next pair call
+ * with the same dp_x waits (host side) until this one's work is done; atsc_dplan_destroy frees them. */
+int atsc_pair_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp_x, const uint8_t *d_body_x, const atsc_dplan *dp_y,
+                          const uint8_t *d_body_y, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                          atsc_window_pair *d_out, void *stream);
+/* Host bytes in, host records out, synchronous; walks and uploads only the touched records of each stream, as
+ * atsc_aggregate_windows does.  ATSC_E_FORMAT (nothing written) for a malformed payload inside a window in either
+ * stream. */
+int atsc_pair_windows(atsc_ctx *ctx, const uint8_t *body_x, uint64_t len_x, int has_count_x, const uint8_t *body_y,
+                      uint64_t len_y, int has_count_y, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                      atsc_window_pair *out);
+/* What is read off the pair moments, host only (no GPU); out[i] from p[i], i < n:
+ *   covariance = c_xy / (double)count (population form);
+ *   sample_covariance = c_xy / (double)(count - 1), NaN when count < 2;
+ *   correlation = (c_xy / sqrt(m2_x)) / sqrt(m2_y), clamped to [-1, 1]; NaN unless m2_x > 0 and m2_y > 0;
+ *   slope = c_xy / m2_x, NaN unless m2_x > 0: the least-squares line of y on x;
+ *   intercept = mean_y - slope * mean_x (not fused);
+ *   r2 = correlation * correlation;     mean_diff = mean_x - mean_y.
+ * count == 0 gives NaN in all seven.  ATSC_E_INVALID for a null pointer with n > 0. */
+typedef struct {
+    double covariance, sample_covariance, correlation, slope, intercept, r2, mean_diff;
+} atsc_window_pair_fit; /* 56 bytes */
+int atsc_pair_fit(const atsc_window_pair *p, uint64_t n, atsc_window_pair_fit *out);
+
 /* Windowed deltas: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames) what
  * its samples do from one to the next, from the same decoded samples as the window decode: how much a counter grew and
  * how often it reset, how much a gauge moved up and down (total variation), the largest single jump and drop.
@@ -719,6 +786,9 @@ int atsc_stream_select_windows(atsc_stream *s, uint64_t n_windows, const uint64_
 /* atsc_moments_windows over the stream's frames */
 int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 atsc_window_moments *out);
+/* atsc_pair_windows over the frames of the streams x and y, which must belong to one context (else ATSC_E_INVALID) */
+int atsc_stream_pair_windows(atsc_stream *x, atsc_stream *y, uint64_t n_windows, const uint64_t *begin,
+                             const uint64_t *count, atsc_window_pair *out);
 /* atsc_quantile_windows over the stream's frames */
 int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint32_t n_q, const double *q, int method, double *out);
