@@ -10,6 +10,9 @@ from .capi import RUNS_EQ, RUNS_GE, RUNS_GT, RUNS_LE, RUNS_LT, RUNS_NE, RUNS_NON
 from .capi import EXTREMES_MAX_K, EXTREMES_NONE  # noqa: F401
 from .engine import EXTREME, extremes_merge, window_extremes_dtype  # noqa: F401
 from .stream import extremes_data_windows  # noqa: F401
+from .capi import VALUES_MAX_K  # noqa: F401
+from .engine import VALUE_COUNT, VALUE_MODE, values_merge, values_mode, window_values_dtype  # noqa: F401
+from .stream import values_data_windows  # noqa: F401
 from .engine import SELECTED, select_bytes  # noqa: F401
 from .engine import WINDOW_PAIR, WINDOW_PAIR_FIT, pair_fit  # noqa: F401
 from .stream import select_data_windows  # noqa: F401

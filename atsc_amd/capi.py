@@ -22,6 +22,8 @@ RUNS_NONE = 2 ** 64 - 1
 # atsc_extremes_windows: the most entries per list, and the position of an empty entry (include/atsc_hip.h)
 EXTREMES_MAX_K = 16
 EXTREMES_NONE = 2 ** 64 - 1
+# atsc_values_windows: the most entries per record (include/atsc_hip.h)
+VALUES_MAX_K = 32
 COMPRESSOR_NAMES = {0: "noop", 1: "fft", 2: "idw", 3: "constant", 4: "polynomial", 5: "auto", 6: "rle"}
 
 OK = 0
@@ -119,6 +121,11 @@ SIGNATURES = {
     "atsc_extremes_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp, _vp]),
     "atsc_extremes_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp]),
     "atsc_extremes_merge": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp]),
+    "atsc_values_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, C.c_double, _vp, _vp]),
+    "atsc_values_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint32, C.c_double,
+                                      _vp]),
+    "atsc_values_merge": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp]),
+    "atsc_values_mode": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp]),
     "atsc_select_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double, C.c_uint64, _vp,
                                           _vp]),
     "atsc_select_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double,
@@ -148,6 +155,7 @@ SIGNATURES = {
     "atsc_stream_delta_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_runs_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double, _vp]),
     "atsc_stream_extremes_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp]),
+    "atsc_stream_values_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, C.c_double, _vp]),
     "atsc_stream_select_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double, C.c_uint64, _vp]),
     "atsc_stream_quantile_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _f64p]),
     "atsc_stream_histogram_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _u64p]),

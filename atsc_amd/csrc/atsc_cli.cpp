@@ -3,7 +3,7 @@
 //
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
-//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K]
+//        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
 //        [--pair OTHER.bro]] [--where OP:LIMIT]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
@@ -67,6 +67,11 @@ void usage()
             "                                 the same sample indices (OTHER must reach the bucketed range's end), as the last\n"
             "                                 columns: pair_count (samples where neither value is NaN), covariance (population\n"
             "                                 form), correlation, and slope and intercept of OTHER's value on this file's\n"
+            "      --values <K[:ABOVE]>       with --buckets: also every bucket's K smallest distinct values (K: 1..32) and how often\n"
+            "                                 each occurs, as the last columns: nans, below, distinct, more, v1, n1 .. vK, nK\n"
+            "                                 (values ascending, -0.0 counted with 0.0; with ABOVE only values greater than it\n"
+            "                                 are listed and the others counted in below; more is 1 where the bucket has more\n"
+            "                                 than K such values; both cells empty where it has fewer)\n"
             "      --where <OP:LIMIT>         with -u --samples, without --buckets: write the window's samples with value OP LIMIT\n"
             "                                 (as --runs) to .sel.csv instead of the .wbro: sample,value, one row per selected\n"
             "                                 sample, sample its index in the stream\n"

@@ -63,6 +63,8 @@ struct BucketOptions {
     int runs_op = ATSC_RUNS_GT;
     double runs_limit = 0.0;
     int extremes = 0;  // --extremes K: nans,max1,max1_at,..,maxK,maxK_at,min1,min1_at,..,minK,minK_at
+    int values = 0;  // --values K[:ABOVE]: nans,below,distinct,more,v1,n1,..,vK,nK
+    double values_above = std::nan("");  // NaN: every value is listed
     bool pair_allowed = false;  // the front end takes --pair (atsc; csv-compressor does not: DESIGN.md "Windowed pair moments")
     std::string pair;           // --pair OTHER.bro: pair_count,covariance,correlation,slope,intercept against that stream
     bool have_where = false;  // --where OP:LIMIT: no bucket query; the window's selected samples into .sel.csv
@@ -149,6 +151,21 @@ bool parse_runs(const std::string &v, int &op, double &limit)
     return true;
 }
 
+// --values K[:ABOVE]: K in 1 .. ATSC_VALUES_MAX_K; ABOVE, where given, a number that is not NaN, nothing behind it
+bool parse_values(const std::string &v, int &k, double &above)
+{
+    const size_t c = v.find(':');
+    if (!parse_int(v.substr(0, c), 1, ATSC_VALUES_MAX_K, k)) return false;
+    above = std::nan("");
+    if (c == std::string::npos) return true;
+    const std::string t = v.substr(c + 1);
+    char *e = nullptr;
+    const double x = strtod(t.c_str(), &e);
+    if (t.empty() || isspace((unsigned char)t[0]) || *e || x != x) return false;
+    above = x;
+    return true;
+}
+
 // --pair OTHER.bro is taken only where the front end allows it (o.pair_allowed).
 // One argument of the command line, where it is a bucket-query option.  s: the argument; value(name): whether s is the
 // option `name` with a value, which it leaves in v (the callers' lambda).  0: none of them; 1: taken; 2: a usage error,
@@ -210,6 +227,12 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             fprintf(stderr, "error: invalid value '%s' for '--extremes': expected 1..=%d\n", v.c_str(), (int)ATSC_EXTREMES_MAX_K);
             return 2;
         }
+    } else if (value("--values")) {
+        if (!parse_values(v, o.values, o.values_above)) {
+            fprintf(stderr, "error: invalid value '%s' for '--values': expected K[:ABOVE], K in 1..=%d, ABOVE a number\n", v.c_str(),
+                    (int)ATSC_VALUES_MAX_K);
+            return 2;
+        }
     } else if (o.pair_allowed && value("--pair")) {
         if (v.empty()) {
             fprintf(stderr, "error: invalid value '' for '--pair': expected the path of a .bro file\n");
@@ -237,6 +260,7 @@ bool bucket_options_complete(const BucketOptions &o, const char *bucketing, bool
              {o.deltas, given, "--deltas", bucketing},
              {o.have_runs, given, "--runs", bucketing},
              {o.extremes != 0, given, "--extremes", bucketing},
+             {o.values != 0, given, "--values", bucketing},
              {!o.pair.empty(), given, "--pair", bucketing}};
     for (const auto &t : T)
         if (t.have && !t.needed) {
@@ -278,6 +302,13 @@ struct BucketResults {
     std::vector<std::string> eat;     // 2 ek cells per bucket: the entries' places, as offsets in the bucket
     std::vector<atsc_window_pair> pv;  // --pair
     std::vector<atsc_window_pair_fit> pf;
+    uint32_t vk = 0;                  // --values: entries per record
+    std::vector<unsigned char> vv;    // the buckets' records, ATSC_VALUES_BYTES(vk) each
+    const atsc_window_values_head &val_head(uint64_t k) const
+    {
+        return *(const atsc_window_values_head *)(vv.data() + k * ATSC_VALUES_BYTES(vk));
+    }
+    const atsc_value_count &val_entry(uint64_t k, uint32_t j) const { return ((const atsc_value_count *)(&val_head(k) + 1))[j]; }
     const atsc_window_extremes_head &ext_head(uint64_t k) const
     {
         return *(const atsc_window_extremes_head *)(ev.data() + k * ATSC_EXTREMES_BYTES(ek));
@@ -361,6 +392,11 @@ int bucket_queries(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const Bucket
         if (!rc) rc = atsc_pair_fit(r.pv.data(), nb, r.pf.data());
         atsc_free(other);
     }
+    if (rc) return rc;
+    *failed = "values";
+    r.vk = (uint32_t)o.values;
+    r.vv.resize(r.vk && nb ? nb * ATSC_VALUES_BYTES(r.vk) : 8);
+    if (r.vk) rc = atsc_values_windows(ctx, body, body_len, 1, nb, b, c, r.vk, o.values_above, r.vv.data());
     return rc;
 }
 
@@ -380,6 +416,10 @@ void bucket_header(FILE *f, const char *first, const BucketOptions &o, const Buc
             for (int j = 1; j <= o.extremes; ++j) fprintf(f, ",%s%d,%s%d_at", e ? "min" : "max", j, e ? "min" : "max", j);
     }
     if (!o.pair.empty()) fprintf(f, ",pair_count,covariance,correlation,slope,intercept");
+    if (o.values) {
+        fprintf(f, ",nans,below,distinct,more");
+        for (int j = 1; j <= o.values; ++j) fprintf(f, ",v%d,n%d", j, j);
+    }
     fprintf(f, "\n");
 }
 
@@ -422,6 +462,15 @@ void bucket_row(FILE *f, const std::string &first, const BucketOptions &o, const
         const atsc_window_pair_fit &pf = r.pf[k];
         fprintf(f, ",%llu,%s,%s,%s,%s", (unsigned long long)r.pv[k].count, debug_f64(pf.covariance).c_str(),
                 debug_f64(pf.correlation).c_str(), debug_f64(pf.slope).c_str(), debug_f64(pf.intercept).c_str());
+    }
+    if (o.values) {
+        const atsc_window_values_head &h = r.val_head(k);
+        fprintf(f, ",%llu,%llu,%u,%u", (unsigned long long)h.nans, (unsigned long long)h.below, h.distinct, h.more);
+        for (uint32_t j = 0; j < r.vk; ++j) {
+            const atsc_value_count &x = r.val_entry(k, j);
+            if (j < h.distinct) fprintf(f, ",%s,%llu", debug_f64(x.value).c_str(), (unsigned long long)x.n);
+            else fprintf(f, ",,");
+        }
     }
     fprintf(f, "\n");
 }

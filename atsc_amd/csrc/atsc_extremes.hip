@@ -38,15 +38,6 @@ namespace {
 constexpr uint64_t EXT_NONE = ~0ull;
 constexpr uint64_t EXT_NAN_BITS = 0x7ff8000000000000ull;
 
-// the key of a sample under the largest list's reading; 0 for NaN
-__device__ __forceinline__ uint64_t ext_key(double v)
-{
-    uint64_t b = (uint64_t)__double_as_longlong(v);
-    b = v == 0.0 ? 0ull : b;
-    const uint64_t k = b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
-    return v != v ? 0ull : k;
-}
-
 template <class P>
 __device__ __forceinline__ bool ext_ahead(uint64_t ka, P pa, uint64_t kb, P pb)
 {
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(256) void k_ext_tiles(const DevPosTile *__restrict_
                 const uint32_t p = j + e;
                 const double s = e ? d.y : d.x;
                 const bool in = tile_in(p, t.lo, t.hi);
-                const uint64_t kl = in ? ext_key(s) : 0ull, ks = kl ? ~kl : 0ull;
+                const uint64_t kl = in ? sample_key(s) : 0ull, ks = kl ? ~kl : 0ull;
                 nans += in && s != s ? 1u : 0u;
                 if (kl && ext_ahead(kl, p, bkl, bpl)) { bkl = kl; bpl = p; }
                 if (ks && ext_ahead(ks, p, bks, bps)) { bks = ks; bps = p; }
@@ -150,7 +141,7 @@ __global__ __launch_bounds__(256) void k_ext_tiles(const DevPosTile *__restrict_
                     const uint32_t p = j + e;
                     const double s = e ? d.y : d.x;
                     const bool in = tile_in(p, t.lo, t.hi);
-                    const uint64_t kl = in ? ext_key(s) : 0ull, ks = kl ? ~kl : 0ull;
+                    const uint64_t kl = in ? sample_key(s) : 0ull, ks = kl ? ~kl : 0ull;
                     const uint32_t p0 = 512u * q + 128u * kk + e;  // lane 0's slot of this step and half
                     uint64_t m = __ballot(kl != 0 && p != bpl && ext_ahead(kl, p, tkl, tpl));
                     while (m) {
@@ -219,7 +210,7 @@ __global__ __launch_bounds__(256) void k_ext_combine(const DevAggComb *__restric
         uint32_t cur = 0;
         uint64_t hv = EXT_NAN_BITS, ha = EXT_NONE, hk = 0;
         if (have) { hv = q[0]; ha = q[1]; }
-        if (ha != EXT_NONE) { hk = ext_key(__longlong_as_double((long long)hv)); hk = end ? ~hk : hk; }
+        if (ha != EXT_NONE) { hk = sample_key(__longlong_as_double((long long)hv)); hk = end ? ~hk : hk; }
         uint64_t ov = EXT_NAN_BITS, oa = EXT_NONE;
 #pragma unroll 1
         for (uint32_t r = 0; r < k; ++r) {
@@ -239,7 +230,7 @@ __global__ __launch_bounds__(256) void k_ext_combine(const DevAggComb *__restric
                 if (cur < k) {
                     hv = q[2u * cur];
                     ha = q[2u * cur + 1u];
-                    if (ha != EXT_NONE) { hk = ext_key(__longlong_as_double((long long)hv)); hk = end ? ~hk : hk; }
+                    if (ha != EXT_NONE) { hk = sample_key(__longlong_as_double((long long)hv)); hk = end ? ~hk : hk; }
                 }
             }
         }

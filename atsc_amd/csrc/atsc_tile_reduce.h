@@ -32,6 +32,17 @@ DEVI double2 tile_load(const double *x, uint32_t j, uint32_t lo, uint32_t hi, do
     return d;
 }
 
+// A sample's key (the extremes, the value counts): its bits mapped so that unsigned integer order is value order, the
+// sign bit flipped for positive values, all bits for negative ones, both zeros on +0.0's key; 0 for NaN.  No sample's
+// key is 0, and none is ~0.
+DEVI uint64_t sample_key(double v)
+{
+    uint64_t b = (uint64_t)__double_as_longlong(v);
+    b = v == 0.0 ? 0ull : b;
+    const uint64_t k = b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
+    return v != v ? 0ull : k;
+}
+
 // THE TILE SUM of the contract (include/atsc_hip.h, DESIGN.md "Windowed aggregates"), NS sums side by side:
 //   * term(k, q, p) gives p[c] = (term of slot j) + (term of slot j + 1) of sum c, j = tile_slot(lane + 64 k, q); a
 //     slot without a term holds -0.0 (IEEE's exact additive identity);

@@ -1,4 +1,4 @@
-// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, quantiles, histograms
+// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms
 // and selected samples of ranges of the decoded stream without decoding the rest, and the pair moments of the same ranges of two streams.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
@@ -65,6 +65,11 @@ __attribute__((weak)) hipError_t launch_ext_tiles(const DevPosTile *tasks, uint3
                                                   void *part, hipStream_t s);
 __attribute__((weak)) hipError_t launch_ext_combine(const DevAggComb *tasks, uint32_t n, uint32_t k, void *part,
                                                     const uint64_t *begin, void *out, hipStream_t s);
+// the windowed value counts' kernels (atsc_values.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_val_tiles(const DevAggTile *tasks, uint32_t n, const double *scratch, uint32_t k,
+                                                  uint64_t above, void *part, hipStream_t s);
+__attribute__((weak)) hipError_t launch_val_combine(const DevAggComb *tasks, uint32_t n, uint32_t k, void *part, void *out,
+                                                    hipStream_t s);
 // the windowed select's count, scan and write kernels (atsc_select.hip; weak for the same reason)
 __attribute__((weak)) hipError_t launch_sel_count(const DevSelTask *tasks, uint32_t n, const double *scratch, int op,
                                                   double limit, uint64_t *cnt, hipStream_t s);
@@ -283,7 +288,7 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_HISTOGRAM = DECODE_CALLER("histogram"), BY_MOMENTS = DECODE_CALLER("moments"),
                           BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs"),
                           BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
-                          BY_PAIR = DECODE_CALLER("pair");
+                          BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -732,11 +737,12 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
 //   dev(...)            the device call; org: the stream index of the plan's first sample (INPUTS == 2: the list of
 //                       inputs in its place, see query_dev)
 // What the reductions over tiles differ in: the aggregates (atsc_aggregate.hip), the moments (atsc_moments.hip), the
-// deltas (atsc_delta.hip), the runs (atsc_runs.hip) and the extremes (atsc_extremes.hip).
+// deltas (atsc_delta.hip), the runs (atsc_runs.hip), the extremes (atsc_extremes.hip) and the value counts
+// (atsc_values.hip).
 //   Tile, tile(t, k)   the tile kernel's task, from the plan's DevAggTile of tile k of the stream
 //   tiles(.., scr, ..) the tile kernel's launch; scr[k]: input k's scratch region
 //   part()             bytes of a partial: a member call, so that a query may size its partials by a parameter of the
-//                      call (ExtQuery, by k); the others hand back their static PART
+//                      call (ExtQuery and ValQuery, by k); the others hand back their static PART
 //   SIDE               the table both kernels share beside the partials: the windows' first / last samples, which the
 //                      tile kernel writes (device only), or the windows' begins in the stream's index (uploaded)
 //   CARRY, carried(t)  the tile kernel looks at the sample in front of a tile: the side table is one carry slot (device
@@ -983,6 +989,78 @@ struct ExtQuery {
     }
 };
 
+static void val_empty_record(void *rec, uint32_t k)
+{
+    atsc_window_values_head *h = (atsc_window_values_head *)rec;
+    h->count = h->nans = h->below = 0;
+    h->distinct = h->more = 0;
+    atsc_value_count *e = (atsc_value_count *)(h + 1);
+    for (uint32_t j = 0; j < k; ++j) {
+        e[j].value = std::numeric_limits<double>::quiet_NaN();
+        e[j].n = 0;
+    }
+}
+
+// A value's key, as the kernels compute it (sample_key, atsc_tile_reduce.h): unsigned order is value order, both zeros
+// on +0.0's key; 0 for NaN.
+static uint64_t val_key(double v)
+{
+    if (v != v) return 0;
+    uint64_t b;
+    memcpy(&b, &v, 8);
+    if (v == 0.0) b = 0;
+    return b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
+}
+
+// The value counts (atsc_values.hip).  k and above are the call's parameters and members, as the extremes' k is; k
+// sizes the partials, which have the record's layout (4 + 2 k words).  A partial holds no position, so a shared mid
+// tile's partial serves every window as it is: no side table, and no carry.
+// The call keeps its tables, partials and scratch in the plan's slot of the extremes (KIND): the two selections over
+// tiles share one set of per-plan resources, so a call of either kind waits (host side) for the plan's previous call of
+// either kind, and the plan's layout and the host code outside this file stay what they were.
+struct ValQuery {
+    static constexpr int INPUTS = 1;
+    using Tile = DevAggTile;
+    static constexpr const char *CALL = "values_windows", *RES_NAME = "d_out", *NO_KERNELS = "no values kernels",
+                                *TILES = "launch k_val_tiles", *COMBINE = "launch k_val_combine";
+    static constexpr bool SIDE_BEGINS = false, NO_SIDE = true;
+    static constexpr bool CARRY = false;
+    static constexpr QueryKind KIND = Q_EXTREMES;
+    uint32_t k;
+    double above;
+    size_t part() const { return ATSC_VALUES_BYTES(k); }
+    static const DecodeCaller &who() { return BY_VALUES; }
+    static bool have() { return launch_val_tiles && launch_val_combine; }
+    static Tile tile(const DevAggTile &t, uint64_t) { return t; }
+    static bool carried(const Tile &) { return false; }
+    hipError_t tiles(const Tile *t, uint32_t n, const double *const *scr, void *part, void *, hipStream_t s) const
+    {
+        return launch_val_tiles(t, n, scr[0], k, val_key(above), part, s);
+    }
+    hipError_t combine(const DevAggComb *c, uint32_t n, void *part, const void *, void *out, hipStream_t s) const
+    {
+        return launch_val_combine(c, n, k, part, out, s);
+    }
+    size_t out_bytes(uint64_t n) const { return n * ATSC_VALUES_BYTES(k); }
+    int check(atsc_ctx *ctx) const
+    {
+        if (k == 0 || k > ATSC_VALUES_MAX_K) return fail(ctx, ATSC_E_INVALID, "values_windows: k outside [1, 32]");
+        return ATSC_OK;
+    }
+    void fill_empty(void *out, uint64_t n) const
+    {
+        for (uint64_t i = 0; i < n; ++i) val_empty_record((char *)out + i * ATSC_VALUES_BYTES(k), k);
+    }
+    // (k is checked in front of the arguments)
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *count, void *d_res, void *stream, uint64_t org) const
+    {
+        const int rc = check(ctx);
+        const QueryInput in{dp, d_body, org};
+        return rc ? rc : reduce_dev(ctx, &in, n_windows, begin, count, d_res, stream, *this);
+    }
+};
+
 // The pair moments (atsc_pair.hip): the one reduction over two inputs.  Its kernels read the same slots of the two
 // inputs' regions; the partial is the moments' node with the second stream's value where that has the position.  No
 // position is counted from a window's begin: no side table.  No carry.
@@ -1026,9 +1104,9 @@ struct PairQuery {
     }
 };
 
-// The device call of a reduction over tiles (Q: AggQuery, MomQuery, DltQuery, RunQuery, ExtQuery or PairQuery; the
-// kernels named below are the aggregates').  q: the query's parameters of this call, where it has any (RunQuery,
-// ExtQuery).  in: the Q::INPUTS streams it reads, each a plan, its record bytes on the device and the stream index of
+// The device call of a reduction over tiles (Q: AggQuery, MomQuery, DltQuery, RunQuery, ExtQuery, ValQuery or PairQuery;
+// the kernels named below are the aggregates').  q: the query's parameters of this call, where it has any (RunQuery,
+// ExtQuery, ValQuery).  in: the Q::INPUTS streams it reads, each a plan, its record bytes on the device and the stream index of
 // the plan's first sample; begin[] counts from in[0].org.  Everything below is computed once, in the stream's index,
 // which the inputs share; per piece every input is decoded into a scratch region of its own, with its own decode tasks
 // and spill slots, and the tile kernel gets every region's pointer.  The call's tables, partials and regions are
@@ -1044,7 +1122,7 @@ struct PairQuery {
 // Where a window runs on into the next piece, an 8-byte copy behind the piece's tile launch (stream-ordered: behind
 // the launch that read the slot's previous value, in front of the next decode) takes the piece's last sample to the
 // carry slot in the call's tables.  The tile kernel never writes that slot.
-// A query whose kernels share no table beside the partials says so (PairQuery::NO_SIDE).
+// A query whose kernels share no table beside the partials says so (PairQuery::NO_SIDE, ValQuery::NO_SIDE).
 template <class Q, class = void>
 struct NoSide : std::false_type {};
 template <class Q>
@@ -1553,6 +1631,86 @@ extern "C" int atsc_extremes_merge(const void *records, uint64_t n, uint32_t k, 
         memcpy(acc, next, bytes);
     }
     memcpy(out, acc, bytes);
+    return ATSC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// windowed value counts: the k smallest distinct values of sample windows and how often each occurs (atsc_values.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" int atsc_values_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                       const uint64_t *begin, const uint64_t *count, uint32_t k, double above, void *d_out,
+                                       void *stream)
+{
+    ATSC_API_BEGIN
+    return ValQuery{k, above}.dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    ATSC_API_END
+}
+
+extern "C" int atsc_values_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                   const uint64_t *begin, const uint64_t *count, uint32_t k, double above, void *out)
+{
+    ATSC_API_BEGIN
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, ValQuery{k, above});
+    ATSC_API_END
+}
+
+// Host only: the records of pairwise disjoint windows into the record of their union (include/atsc_hip.h's rule and
+// its argument).  The heads add; the lists merge by value, the n of equal values added, and the result is cut at k.
+extern "C" int atsc_values_merge(const void *records, uint64_t n, uint32_t k, void *out)
+{
+    if (!out || (n && !records) || k == 0 || k > ATSC_VALUES_MAX_K) return ATSC_E_INVALID;
+    const size_t bytes = ATSC_VALUES_BYTES(k);
+    alignas(8) unsigned char acc[ATSC_VALUES_BYTES(ATSC_VALUES_MAX_K)], next[ATSC_VALUES_BYTES(ATSC_VALUES_MAX_K)];
+    val_empty_record(acc, k);
+    atsc_window_values_head *a = (atsc_window_values_head *)acc;
+    for (uint64_t i = 0; i < n; ++i) {
+        alignas(8) unsigned char part[ATSC_VALUES_BYTES(ATSC_VALUES_MAX_K)];
+        memcpy(part, (const char *)records + i * bytes, bytes);
+        const atsc_window_values_head *b = (const atsc_window_values_head *)part;
+        if (b->count == 0) continue;
+        val_empty_record(next, k);
+        atsc_window_values_head *nh = (atsc_window_values_head *)next;
+        const atsc_value_count *la = (const atsc_value_count *)(a + 1), *lb = (const atsc_value_count *)(b + 1);
+        atsc_value_count *lo = (atsc_value_count *)(nh + 1);
+        const uint32_t na = std::min(a->distinct, k), nb = std::min(b->distinct, k);
+        uint32_t ia = 0, ib = 0, j = 0;
+        for (; j < k && (ia < na || ib < nb); ++j) {
+            const bool ta = ia < na && (ib == nb || la[ia].value <= lb[ib].value);
+            const bool tb = ib < nb && (ia == na || lb[ib].value <= la[ia].value);
+            lo[j].value = ta ? la[ia].value : lb[ib].value;  // (of the zeros only +0.0 is ever listed)
+            lo[j].n = (ta ? la[ia].n : 0) + (tb ? lb[ib].n : 0);
+            ia += ta;
+            ib += tb;
+        }
+        nh->count = a->count + b->count;
+        nh->nans = a->nans + b->nans;
+        nh->below = a->below + b->below;
+        nh->distinct = j;
+        nh->more = (ia < na || ib < nb || a->more || b->more) ? 1 : 0;
+        memcpy(acc, next, bytes);
+    }
+    memcpy(out, acc, bytes);
+    return ATSC_OK;
+}
+
+// Host only: the listed entry with the largest n of every record, of equal n the smallest value.
+extern "C" int atsc_values_mode(const void *records, uint64_t n, uint32_t k, atsc_value_mode *out)
+{
+    if ((n && (!records || !out)) || k == 0 || k > ATSC_VALUES_MAX_K) return ATSC_E_INVALID;
+    for (uint64_t i = 0; i < n; ++i) {
+        alignas(8) unsigned char rec[ATSC_VALUES_BYTES(ATSC_VALUES_MAX_K)];
+        memcpy(rec, (const char *)records + i * ATSC_VALUES_BYTES(k), ATSC_VALUES_BYTES(k));
+        const atsc_window_values_head *h = (const atsc_window_values_head *)rec;
+        const atsc_value_count *e = (const atsc_value_count *)(h + 1);
+        atsc_value_mode r;
+        r.value = std::numeric_limits<double>::quiet_NaN();
+        r.n = 0;
+        r.exact = h->more == 0;
+        r.pad = 0;
+        for (uint32_t j = 0; j < std::min(h->distinct, k); ++j)
+            if (e[j].n > r.n) { r.value = e[j].value; r.n = e[j].n; }
+        out[i] = r;
+    }
     return ATSC_OK;
 }
 
@@ -2279,6 +2437,14 @@ extern "C" int atsc_stream_extremes_windows(atsc_stream *s, uint64_t n_windows, 
 {
     ATSC_API_BEGIN
     return query_stream(s, n_windows, begin, count, out, ExtQuery{k});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_values_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                          uint32_t k, double above, void *out)
+{
+    ATSC_API_BEGIN
+    return query_stream(s, n_windows, begin, count, out, ValQuery{k, above});
     ATSC_API_END
 }
 

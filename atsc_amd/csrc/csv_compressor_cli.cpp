@@ -5,7 +5,7 @@
 //
 //   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
 //                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]
-//                  [--extremes K]] [--where OP:LIMIT]]]
+//                  [--extremes K] [--values K[:ABOVE]]] [--where OP:LIMIT]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
@@ -66,6 +66,11 @@ void usage()
             "                                 when they happened, as the last columns: nans, max1, max1_at .. maxK, maxK_at,\n"
             "                                 min1, min1_at .. minK, minK_at (equal values earliest first; *_at the indexed\n"
             "                                 time of the sample; both cells empty where the bucket has fewer samples)\n"
+            "      --values <K[:ABOVE]>       with --step: also every bucket's K smallest distinct values (K: 1..32) and how often\n"
+            "                                 each occurs, as the last columns: nans, below, distinct, more, v1, n1 .. vK, nK\n"
+            "                                 (values ascending, -0.0 counted with 0.0; with ABOVE only values greater than it\n"
+            "                                 are listed and the others counted in below; more is 1 where the bucket has more\n"
+            "                                 than K such values; both cells empty where it has fewer)\n"
             "      --where <OP:LIMIT>         with --from/--to, without --step: write the window's samples with value OP LIMIT\n"
             "                                 (as --runs) to .sel.csv instead of the .wbro and .csv: timestamp,value, one row\n"
             "                                 per selected sample, timestamp its indexed time\n"

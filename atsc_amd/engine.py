@@ -49,6 +49,12 @@ RUNS_NONE = capi.RUNS_NONE
 EXTREME = np.dtype([("value", "<f8"), ("at", "<u8")])
 EXTREMES_MAX_K, EXTREMES_NONE = capi.EXTREMES_MAX_K, capi.EXTREMES_NONE
 
+# one entry of a window's value counts (atsc_value_count): a distinct value and the window's samples equal to it
+VALUE_COUNT = np.dtype([("value", "<f8"), ("n", "<u8")])
+VALUES_MAX_K = capi.VALUES_MAX_K
+# atsc_value_mode: what atsc_values_mode reads off a record, 24 bytes
+VALUE_MODE = np.dtype([("value", "<f8"), ("n", "<u8"), ("exact", "<u4"), ("pad", "<u4")])
+
 
 # one entry of a select call's block (atsc_selected): the sample's own bits and its offset from the window's begin
 SELECTED = np.dtype([("value", "<f8"), ("at", "<u8")])
@@ -66,6 +72,16 @@ def window_extremes_dtype(k):
     if not 1 <= k <= EXTREMES_MAX_K:
         raise ValueError("k outside 1..%d" % EXTREMES_MAX_K)
     return np.dtype([("count", "<u8"), ("nans", "<u8"), ("largest", EXTREME, (k,)), ("smallest", EXTREME, (k,))])
+
+
+def window_values_dtype(k):
+    """-> the record of one window of a value-count call with k entries (include/atsc_hip.h), 32 + 16 k bytes: count,
+    nans, below, distinct, more and entry[k] of (value, n); an unused entry is (NaN, 0)"""
+    k = int(k)
+    if not 1 <= k <= VALUES_MAX_K:
+        raise ValueError("k outside 1..%d" % VALUES_MAX_K)
+    return np.dtype([("count", "<u8"), ("nans", "<u8"), ("below", "<u8"), ("distinct", "<u4"), ("more", "<u4"),
+                     ("entry", VALUE_COUNT, (k,))])
 
 
 def _windows(begins, counts):
@@ -119,6 +135,15 @@ def _extremes_dtype(k):
     return window_extremes_dtype(min(max(_extremes_k(k), 1), EXTREMES_MAX_K))
 
 
+def _values_params(k, above):
+    return C.c_uint32(_extremes_k(k)), C.c_double(float(above))
+
+
+def _values_dtype(k, above):
+    """the record of a call with k; a k that the library refuses still gets a result to leave untouched"""
+    return window_values_dtype(min(max(_extremes_k(k), 1), VALUES_MAX_K))
+
+
 def _select_params(op, limit, cap):
     cap = int(cap)
     if not 0 <= cap < 2 ** 64:
@@ -153,6 +178,7 @@ _DELTA = _Query("delta_windows", WINDOW_DELTA, None, _no_params)
 _PAIR = _Query("pair_windows", WINDOW_PAIR, None, _no_params, inputs=2)
 _RUNS = _Query("runs_windows", WINDOW_RUNS, None, _runs_params)
 _EXTREMES = _Query("extremes_windows", _extremes_dtype, None, _extremes_params)
+_VALUES = _Query("values_windows", _values_dtype, None, _values_params)
 _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _select_block)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
 _HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
@@ -282,6 +308,29 @@ def extremes_merge(records, k):
     capi.check(capi.lib().atsc_extremes_merge(C.c_void_p(r.ctypes.data if len(r) else None), len(r), int(k),
                                               C.c_void_p(out.ctypes.data)))
     return out[0]
+
+
+def values_merge(records, k):
+    """-> one record of window_values_dtype(k) (a 0-d array): the records of pairwise disjoint windows (one k, one
+    above; any order, any streams) folded into the record of their union, which it equals bit for bit
+    (atsc_values_merge; no GPU)"""
+    dt = window_values_dtype(k)
+    r = np.ascontiguousarray(np.atleast_1d(np.asarray(records, dtype=dt)))
+    out = np.zeros(1, dtype=dt)
+    capi.check(capi.lib().atsc_values_merge(C.c_void_p(r.ctypes.data if len(r) else None), len(r), int(k),
+                                            C.c_void_p(out.ctypes.data)))
+    return out[0]
+
+
+def values_mode(records, k):
+    """-> VALUE_MODE array: of every record of window_values_dtype(k) the listed value with the largest n (of equal n
+    the smallest value), that n, and exact = (more == 0); (NaN, 0) where nothing is listed (atsc_values_mode; no GPU)"""
+    dt = window_values_dtype(k)
+    r = np.ascontiguousarray(np.atleast_1d(np.asarray(records, dtype=dt)))
+    out = np.zeros(max(len(r), 1), dtype=VALUE_MODE)
+    capi.check(capi.lib().atsc_values_mode(C.c_void_p(r.ctypes.data if len(r) else None), len(r), int(k),
+                                           C.c_void_p(out.ctypes.data)))
+    return out[: len(r)]
 
 
 def bucket_windows(begin, count, bucket):
@@ -430,6 +479,12 @@ class Context:
         in the window, the number of NaN samples and the length of every window [begins[i], begins[i] + counts[i]) of
         the decoded records (atsc_extremes_windows)"""
         return _query_host(_EXTREMES, self, records, begins, counts, has_count, k)
+
+    def values_windows_host(self, records, begins, counts, k, above=float("nan"), has_count=False):
+        """-> array of window_values_dtype(k): the k smallest distinct values above `above` (NaN: all of them), each
+        with the number of samples equal to it, the NaN samples, the samples not above `above` and the length of every
+        window [begins[i], begins[i] + counts[i]) of the decoded records (atsc_values_windows)"""
+        return _query_host(_VALUES, self, records, begins, counts, has_count, k, above)
 
     def quantile_windows_host(self, records, begins, counts, levels, method=capi.QUANTILE_LINEAR, has_count=False):
         """-> (n_windows, n_levels) float64 array: the levels of every window [begins[i], begins[i] + counts[i]) of the
@@ -597,6 +652,12 @@ class DPlan:
         d_out, a device tensor of at least 16 + 32 k bytes per window (atsc_extremes_windows_dev; records of
         window_extremes_dtype(k))"""
         _query_dev(_EXTREMES, self, d_body, begins, counts, d_out, stream, k)
+
+    def values_windows(self, d_body, begins, counts, k, d_out, above=float("nan"), stream=0):
+        """Enqueues the k smallest distinct values above `above` (NaN: all of them) of the windows [begins[i],
+        begins[i] + counts[i]) and how often each occurs into d_out, a device tensor of at least 32 + 16 k bytes per
+        window (atsc_values_windows_dev; records of window_values_dtype(k))"""
+        _query_dev(_VALUES, self, d_body, begins, counts, d_out, stream, k, above)
 
     def quantile_windows(self, d_body, begins, counts, levels, d_out, method=capi.QUANTILE_LINEAR, stream=0):
         """Enqueues the levels of the windows [begins[i], begins[i] + counts[i]) into d_out, a float64 device tensor of

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import capi
 from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit, pair_fit  # noqa: F401
-from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _RUNS, _SELECT, _query_others, _query_result, _query_rows, _select_result
+from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _select_result
 
 
 def _f64(x):
@@ -151,6 +151,11 @@ class CompressedStream:
         smallest samples and where they are (atsc_stream_extremes_windows)"""
         return _query_stream(_EXTREMES, self, begins, counts, k)
 
+    def values_windows(self, begins, counts, k, above=float("nan")):
+        """-> array of window_values_dtype(k) of the windows [begins[i], begins[i] + counts[i]): their k smallest
+        distinct values above `above` (NaN: all of them) and how often each occurs (atsc_stream_values_windows)"""
+        return _query_stream(_VALUES, self, begins, counts, k, above)
+
     def quantile_windows(self, begins, counts, levels, method=capi.QUANTILE_LINEAR):
         """-> (n_windows, n_levels) float64 array of the windows' levels (atsc_stream_quantile_windows)"""
         return _query_stream(_QUANTILE, self, begins, counts, levels, method)
@@ -230,6 +235,13 @@ def extremes_data_windows(ctx, bro, begins, counts, k):
     """-> array of window_extremes_dtype(k) of windows of decompress_data(ctx, bro): their k largest and k smallest
     samples and where they are: atsc_bro_open, then atsc_extremes_windows over the records"""
     return _query_image(_EXTREMES, ctx, bro, begins, counts, k)
+
+
+def values_data_windows(ctx, bro, begins, counts, k, above=float("nan")):
+    """-> array of window_values_dtype(k) of windows of decompress_data(ctx, bro): their k smallest distinct values
+    above `above` (NaN: all of them) and how often each occurs: atsc_bro_open, then atsc_values_windows over the
+    records"""
+    return _query_image(_VALUES, ctx, bro, begins, counts, k, above)
 
 
 def quantile_data_windows(ctx, bro, begins, counts, levels, method=capi.QUANTILE_LINEAR):

@@ -628,6 +628,86 @@ int atsc_extremes_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len,
  * for a null pointer with n > 0, a null out, or k outside 1 .. ATSC_EXTREMES_MAX_K. */
 int atsc_extremes_merge(const void *records, uint64_t n, uint32_t k, void *out);
 
+/* Windowed value counts: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames)
+ * its k smallest distinct values with their exact multiplicities, from the same decoded samples as the window decode:
+ * PromQL's count_values and "time in state" for every enum-like series (up, a replica count, an HTTP status, a leader
+ * id, a breaker state, a config version), without knowing the values in advance.  One k, 1 <= k <= ATSC_VALUES_MAX_K,
+ * holds for every window of a call.  The record of a window is ATSC_VALUES_BYTES(k) = 32 + 16 k bytes, 8-byte aligned: an
+ * atsc_window_values_head, then entry[0 .. k), each an atsc_value_count; record i lies at
+ * (char *)out + i * ATSC_VALUES_BYTES(k).
+ *   Equality  Samples are compared as values.  -0.0 equals +0.0, and that class is reported as +0.0 (the fixed sign of
+ *             the aggregates' zero extreme); every other value is reported with its own bits.  +-Inf are ordinary
+ *             values.  A NaN is never a value: it is counted in nans, whatever its payload.
+ *   Order     Entries are in ascending value order.
+ *   above     (a double, for paging)  When above is NaN, every non-NaN sample is listed.  Otherwise only samples with
+ *             x > above (as values) are listed, and the non-NaN samples that are not listed are counted in below.
+ *             above = +Inf lists nothing; above = -Inf leaves out only -Inf samples; above = +-0.0 leaves out the zero
+ *             class and everything negative.  Calling again with above set to the last listed value walks a window with
+ *             D > k distinct values exactly, in ceil(D / k) calls.
+ *   Entries   entry[j] for j < distinct is the (j + 1)-th smallest distinct listed value and the number of the window's
+ *             samples equal to it; the entries from `distinct` on hold value = NaN, n = 0.  count == 0 gives an all-zero
+ *             head and k such entries.  Counts are exact 64-bit integers for windows of any length.
+ * There is no floating-point arithmetic in the contract: the record is bit-exact, and it depends only on the stream's
+ * samples, the window, k and above, not on the other windows, their order, the scratch budget, piece boundaries, the
+ * framing or the device.  Consequences:
+ *   - more == 0 implies count == nans + below + the sum of the entries' n;
+ *   - the first j entries of a call with k are the entries of a call with j < k (same above); that call's distinct is
+ *     min(distinct_k, j) and its more is distinct_k > j || more_k;
+ *   - with above NaN and at least one non-NaN sample, entry[0].value equals atsc_aggregate_windows' min as a value;
+ *   - the n of a listed value v equals atsc_runs_windows(ATSC_RUNS_EQ, v).inside.
+ * ATSC_E_INVALID with nothing written, before any GPU work, for k == 0 or k > ATSC_VALUES_MAX_K.  Validation and the
+ * other semantics are atsc_aggregate_windows_dev's: a window beyond the stream gives ATSC_E_INVALID with nothing written;
+ * payloads are checked only of the frames a window touches; windows may overlap and come in any order; count == 0 and
+ * n_windows == 0 are valid.  Windows may be of any length: there is no ATSC_E_CAPACITY case.  Decoded samples stay inside
+ * the atsc_ctx_set_aggregate_scratch budget. */
+typedef struct {
+    uint64_t count;    /* count[i], NaN included */
+    uint64_t nans;     /* NaN samples */
+    uint64_t below;    /* non-NaN samples not above `above`; 0 when `above` is NaN */
+    uint32_t distinct; /* entries filled: min(D, k), D = number of distinct listed values */
+    uint32_t more;     /* 1 iff D > k, else 0 */
+} atsc_window_values_head; /* 32 bytes */
+typedef struct {
+    double value; /* the value (+0.0 for the zeros); NaN in an unused entry */
+    uint64_t n;   /* the window's samples equal to it; 0 in an unused entry */
+} atsc_value_count; /* 16 bytes */
+#define ATSC_VALUES_MAX_K 32
+#define ATSC_VALUES_BYTES(k) (32u + 16u * (size_t)(k))
+/* Record i at (char *)d_out + i * ATSC_VALUES_BYTES(k).  begin / count are HOST arrays; d_body and d_out are device
+ * memory (d_out 8-byte aligned).  Enqueued on `stream`, not synchronised.  A malformed payload inside a window sets the
+ * plan's status word.  The plan keeps the call's tables, partials (4 + 2 k words each) and scratch, in the place of the
+ * extremes call's: the next value-count or extremes call on the same plan waits (host side) until this one's work is
+ * done, and so does a value-count call behind an extremes call; atsc_dplan_destroy frees them. */
+int atsc_values_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                            const uint64_t *begin, const uint64_t *count, uint32_t k, double above, void *d_out,
+                            void *stream);
+/* Host bytes in, host records out, synchronous; walks and uploads only the touched records, as atsc_aggregate_windows
+ * does.  ATSC_E_FORMAT (nothing written) for a malformed payload inside a window. */
+int atsc_values_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                        const uint64_t *begin, const uint64_t *count, uint32_t k, double above, void *out);
+/* Folds the records of n PAIRWISE DISJOINT windows into the record of their union at `out`, host only (no GPU).  All
+ * records must share one k and one above: that is the caller's duty.  The windows may come in any order, need not be
+ * adjacent, and may belong to different streams (buckets into hours, one day's file into the next, one host's series
+ * into another's).  count, nans and below add; the lists merge by value, the n of equal values added, and the result is
+ * cut at k; more is set iff an entry was cut or any part had more.  Records with count == 0 are skipped; n == 0 gives the
+ * empty record.  The merged record equals the union's own record bit for bit: a part's distinct values are a subset of
+ * the union's, so the union's k-th smallest distinct value is no greater than any part's k-th; hence every value among
+ * the union's first k that occurs in a part lies inside that part's list, with its exact count, and whatever a part's
+ * more hides lies above the union's cut.  ATSC_E_INVALID for a null pointer with n > 0, a null out, or k outside
+ * 1 .. ATSC_VALUES_MAX_K. */
+int atsc_values_merge(const void *records, uint64_t n, uint32_t k, void *out);
+/* What a caller reads off the value counts most often, host only: out[i] is the listed entry of record i with the
+ * largest n, of equal n the smallest value; exact = (more == 0), i.e. whether every listed value was seen;
+ * distinct == 0 gives value = NaN, n = 0.  ATSC_E_INVALID for a null pointer with n > 0 or k outside
+ * 1 .. ATSC_VALUES_MAX_K. */
+typedef struct {
+    double value;
+    uint64_t n;
+    uint32_t exact;
+    uint32_t pad;
+} atsc_value_mode; /* 24 bytes */
+int atsc_values_mode(const void *records, uint64_t n, uint32_t k, atsc_value_mode *out);
+
 /* Windowed select: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames) the
  * samples that meet a condition and where they are, from the same decoded samples as the window decode: every sample
  * above 0.9 of each hour with its position, WHERE value OP limit pushed down to the device.  The result is as large as
@@ -780,6 +860,9 @@ int atsc_stream_runs_windows(atsc_stream *s, uint64_t n_windows, const uint64_t 
 /* atsc_extremes_windows over the stream's frames */
 int atsc_stream_extremes_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint32_t k, void *out);
+/* atsc_values_windows over the stream's frames */
+int atsc_stream_values_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                               uint32_t k, double above, void *out);
 /* atsc_select_windows over the stream's frames */
 int atsc_stream_select_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                int op, double limit, uint64_t cap, void *out);
