@@ -14,6 +14,9 @@ from .capi import VALUES_MAX_K  # noqa: F401
 from .engine import VALUE_COUNT, VALUE_MODE, values_merge, values_mode, window_values_dtype  # noqa: F401
 from .stream import values_data_windows  # noqa: F401
 from .engine import SELECTED, select_bytes  # noqa: F401
+from .capi import ROLLING_MAX_WIDTH  # noqa: F401
+from .engine import WINDOW_ROLLING, rolling_offsets, rolling_outputs  # noqa: F401
+from .stream import rolling_data_windows  # noqa: F401
 from .engine import WINDOW_PAIR, WINDOW_PAIR_FIT, pair_fit  # noqa: F401
 from .stream import select_data_windows  # noqa: F401
 from .engine import (WINDOW_DELTA, WINDOW_DELTA_FIT, WINDOW_FIT, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, Context, DPlan, Plan,  # noqa: F401

@@ -24,6 +24,7 @@ EXTREMES_MAX_K = 16
 EXTREMES_NONE = 2 ** 64 - 1
 # atsc_values_windows: the most entries per record (include/atsc_hip.h)
 VALUES_MAX_K = 32
+ROLLING_MAX_WIDTH = 1 << 20
 COMPRESSOR_NAMES = {0: "noop", 1: "fft", 2: "idw", 3: "constant", 4: "polynomial", 5: "auto", 6: "rle"}
 
 OK = 0
@@ -130,6 +131,10 @@ SIGNATURES = {
                                           _vp]),
     "atsc_select_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double,
                                       C.c_uint64, _vp]),
+    "atsc_rolling_outputs": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64]),
+    "atsc_rolling_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "atsc_rolling_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64,
+                                       _vp]),
     "atsc_quantile_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _vp,
                                             _vp]),
     "atsc_quantile_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p,
@@ -157,6 +162,7 @@ SIGNATURES = {
     "atsc_stream_extremes_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp]),
     "atsc_stream_values_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, C.c_double, _vp]),
     "atsc_stream_select_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double, C.c_uint64, _vp]),
+    "atsc_stream_rolling_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp]),
     "atsc_stream_quantile_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _f64p]),
     "atsc_stream_histogram_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _u64p]),
     "atsc_free": (None, [_vp]),

@@ -4,7 +4,7 @@
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
-//        [--pair OTHER.bro]] [--where OP:LIMIT]]
+//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -75,6 +75,10 @@ void usage()
             "      --where <OP:LIMIT>         with -u --samples, without --buckets: write the window's samples with value OP LIMIT\n"
             "                                 (as --runs) to .sel.csv instead of the .wbro: sample,value, one row per selected\n"
             "                                 sample, sample its index in the stream\n"
+            "      --rolling <W[:S]>          with -u --samples, without --buckets: write the window of W samples at every\n"
+            "                                 S-th position of the samples (S: 1) to .roll.csv instead of the .wbro:\n"
+            "                                 offset,count,min,max,sum,mean, offset the position's first sample counted\n"
+            "                                 from BEGIN; mean is sum / count, empty where count is 0\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -153,6 +157,17 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
             if (rc) return rc;
             const uint64_t b0 = a.win_begin;
             return where_write(with_ext(path, "sel.csv"), "sample", rows, [b0](uint64_t at) { return std::to_string(b0 + at); })
+                       ? ATSC_OK
+                       : ATSC_E_IO;
+        }
+        if (a.q.rolling) {  // (with --samples) the window's rolling records, no .wbro
+            std::vector<atsc_window_rolling> rows;
+            rc = atsc_bro_open(bro, len, nullptr, nullptr);
+            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows);
+            atsc_free(bro);
+            if (rc) return rc;
+            const uint64_t stride = a.q.rolling_stride;  // a position's first sample, counted from the window's begin
+            return rolling_write(with_ext(path, "roll.csv"), "offset", rows, [stride](uint64_t j) { return std::to_string(j * stride); })
                        ? ATSC_OK
                        : ATSC_E_IO;
         }
@@ -288,6 +303,7 @@ int main(int argc, char **argv)
     if (a.buckets && !a.uncompress) { fprintf(stderr, "error: '--buckets' needs '-u'\n"); return 2; }
     if (!bucket_options_complete(a.q, "--buckets", a.buckets != 0)) return 2;
     if (!where_option_complete(a.q, "--samples", a.window, "--buckets", a.buckets != 0)) return 2;
+    if (!rolling_option_complete(a.q, "--samples", a.window, "--buckets", a.buckets != 0)) return 2;
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) { fprintf(stderr, "[ERROR] %s: No such file or directory\n", a.input.c_str()); return 1; }
     atsc_ctx *ctx = nullptr;

@@ -1,6 +1,7 @@
 // atsc_cli_buckets.h -- what the two command lines (atsc_cli.cpp, csv_compressor_cli.cpp) share: the small text helpers
 // and the bucket queries behind `atsc -u --buckets N` and `csv-compressor -u --from --to --step S`: their options, the
-// usage errors, the calls over the buckets and the columns of the .agg.csv; and `--where OP:LIMIT`, the selected samples
+// usage errors, the calls over the buckets and the columns of the .agg.csv; `--rolling W[:S]`, the sliding window's
+// records at every position of a window; and `--where OP:LIMIT`, the selected samples
 // of the window itself into a .sel.csv (the end of this file).  The two differ in the row's first cell,
 // in how a failure is reported and in how a position inside a bucket is written: the three run positions, which the
 // caller hands in, and the extremes' positions, which csv-compressor rewrites as times (bucket_extreme_places).
@@ -70,6 +71,8 @@ struct BucketOptions {
     bool have_where = false;  // --where OP:LIMIT: no bucket query; the window's selected samples into .sel.csv
     int where_op = ATSC_RUNS_GT;
     double where_limit = 0.0;
+    uint64_t rolling = 0;  // --rolling W[:S]: no bucket query; the window's rolling records into .roll.csv
+    uint64_t rolling_stride = 1;
 };
 
 // --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
@@ -166,6 +169,20 @@ bool parse_values(const std::string &v, int &k, double &above)
     return true;
 }
 
+// --rolling W[:S]: the width, 1 .. ATSC_ROLLING_MAX_WIDTH, and the stride, at least 1 (1 where it is left out)
+bool parse_rolling(const std::string &v, uint64_t &width, uint64_t &stride)
+{
+    const size_t c = v.find(':');
+    auto number = [](const std::string &t, uint64_t &x) {
+        char *e = nullptr;
+        x = strtoull(t.c_str(), &e, 10);
+        return !t.empty() && isdigit((unsigned char)t[0]) && !*e && t.size() <= 19 && x >= 1;
+    };
+    stride = 1;
+    if (!number(v.substr(0, c), width) || width > ATSC_ROLLING_MAX_WIDTH) return false;
+    return c == std::string::npos || number(v.substr(c + 1), stride);
+}
+
 // --pair OTHER.bro is taken only where the front end allows it (o.pair_allowed).
 // One argument of the command line, where it is a bucket-query option.  s: the argument; value(name): whether s is the
 // option `name` with a value, which it leaves in v (the callers' lambda).  0: none of them; 1: taken; 2: a usage error,
@@ -222,6 +239,12 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             return 2;
         }
         o.have_where = true;
+    } else if (value("--rolling")) {
+        if (!parse_rolling(v, o.rolling, o.rolling_stride)) {
+            fprintf(stderr, "error: invalid value '%s' for '--rolling': expected W[:S], W in 1..=%llu, S at least 1\n", v.c_str(),
+                    (unsigned long long)ATSC_ROLLING_MAX_WIDTH);
+            return 2;
+        }
     } else if (value("--extremes")) {
         if (!parse_int(v, 1, ATSC_EXTREMES_MAX_K, o.extremes)) {
             fprintf(stderr, "error: invalid value '%s' for '--extremes': expected 1..=%d\n", v.c_str(), (int)ATSC_EXTREMES_MAX_K);
@@ -281,6 +304,22 @@ bool where_option_complete(const BucketOptions &o, const char *window, bool wind
     }
     if (bucketed) {
         fprintf(stderr, "error: '--where' cannot be used with '%s'\n", bucketing);
+        return false;
+    }
+    return true;
+}
+
+// --rolling goes with the option that names the window and without the one that cuts buckets, as --where does, and
+// not with --where.  false: a usage error, reported on stderr.
+bool rolling_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
+{
+    if (!o.rolling) return true;
+    if (!windowed) {
+        fprintf(stderr, "error: '--rolling' needs '%s'\n", window);
+        return false;
+    }
+    if (bucketed || o.have_where) {
+        fprintf(stderr, "error: '--rolling' cannot be used with '%s'\n", bucketed ? bucketing : "--where");
         return false;
     }
     return true;
@@ -497,6 +536,32 @@ bool where_write(const std::string &path, const char *first, const std::vector<a
     if (!f) return false;
     fprintf(f, "%s,value\n", first);
     for (const atsc_selected &r : rows) fprintf(f, "%s,%s\n", place(r.at).c_str(), debug_f64(r.value).c_str());
+    return fclose(f) == 0;
+}
+
+// --rolling: one record per position of the range [begin, begin + count) of a .bro image
+int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
+                  std::vector<atsc_window_rolling> &rows)
+{
+    rows.assign(atsc_rolling_outputs(count, o.rolling, o.rolling_stride), atsc_window_rolling{});
+    atsc_window_rolling none;
+    return atsc_rolling_windows(ctx, bro + 9, len - 9, 1, 1, &begin, &count, o.rolling, o.rolling_stride,
+                                rows.empty() ? &none : rows.data());
+}
+
+// the .roll.csv: `first`,count,min,max,sum,mean and one row per position; place(j): the first cell of position j; values
+// as the .agg.csv writes them, mean = sum / count and empty where count == 0.  false: the file could not be written.
+template <class Place>
+bool rolling_write(const std::string &path, const char *first, const std::vector<atsc_window_rolling> &rows, Place place)
+{
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return false;
+    fprintf(f, "%s,count,min,max,sum,mean\n", first);
+    for (size_t j = 0; j < rows.size(); ++j) {
+        const atsc_window_rolling &r = rows[j];
+        fprintf(f, "%s,%llu,%s,%s,%s,%s\n", place(j).c_str(), (unsigned long long)r.count, debug_f64(r.min).c_str(),
+                debug_f64(r.max).c_str(), debug_f64(r.sum).c_str(), r.count ? debug_f64(r.sum / (double)r.count).c_str() : "");
+    }
     return fclose(f) == 0;
 }
 

@@ -315,6 +315,27 @@ static inline uint64_t sel_scan_sums(uint64_t m)
     return words;
 }
 
+// windowed rolling (atsc_rolling_windows_dev, atsc_rolling.hip): a pyramid of the partials of the aligned chunks
+// [j 2^l, (j + 1) 2^l) of the stream index over one piece of the scratch, then one record per position from its window's
+// canonical chunks.  Levels below ROLL_LOW are not stored: the position kernel forms those chunks from the samples.
+constexpr uint32_t ROLL_TILE_LOG = 11, ROLL_TILE = 1u << ROLL_TILE_LOG;  // samples per workgroup of the pyramid kernel
+constexpr uint32_t ROLL_LOW = 3;                                        // the lowest stored level
+constexpr uint32_t ROLL_MAX_LEVEL = 20;                                 // log2 ATSC_ROLLING_MAX_WIDTH
+constexpr uint32_t ROLL_TASK = 256;                                     // positions per task: one wavefront, four steps
+// one piece: scratch[0] is sample a0 of the stream (a multiple of ROLL_TILE), the region ends in front of sample a1 (one
+// too); the chunk j of level l lies at pyr[off[l] + j - (a0 >> l)] for a0 >> l <= j <= (a1 - 1) >> l, in 32-byte partials
+// (a chunk that sticks out of [a0, a1) has a place and no value)
+struct DevRollPiece {
+    uint64_t a0, a1;
+    uint64_t off[ROLL_MAX_LEVEL + 1];
+};
+// one task: n positions of one range, the first one's window beginning at sample lo of the stream, the others' every
+// `stride` samples behind it; their records from out[rec] on
+struct DevRollTask {
+    uint64_t lo, rec;
+    uint32_t n, pad;
+};
+
 static inline uint32_t varint_len_u64(uint64_t v)
 {
     return v < 251 ? 1u : v < (1ull << 16) ? 3u : v < (1ull << 32) ? 5u : 9u;

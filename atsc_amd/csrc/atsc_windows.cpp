@@ -1,5 +1,5 @@
-// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms
-// and selected samples of ranges of the decoded stream without decoding the rest, and the pair moments of the same ranges of two streams.  Each query has a device call (host tables, one upload, launches on the caller's
+// atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms,
+// rolling windows and selected samples of ranges of the decoded stream without decoding the rest, and the pair moments of the same ranges of two streams.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
@@ -84,6 +84,14 @@ __attribute__((weak)) hipError_t launch_pair_tiles(const DevPosTile *tasks, uint
                                                    DevMomPart *part, hipStream_t s);
 __attribute__((weak)) hipError_t launch_pair_combine(const DevAggComb *tasks, uint32_t n, DevMomPart *part, void *out,
                                                      hipStream_t s);
+// the windowed rolling's pyramid and position kernels (atsc_rolling.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_roll_pyramid(const double *scratch, uint32_t n_tiles, void *pyr, const DevRollPiece *pc,
+                                                     uint32_t lmax, hipStream_t s);
+__attribute__((weak)) hipError_t launch_roll_upper(void *pyr, const DevRollPiece *pc, uint32_t n, uint32_t src, uint32_t lmax,
+                                                   hipStream_t s);
+__attribute__((weak)) hipError_t launch_roll_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
+                                                       const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
+                                                       void *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -288,7 +296,8 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_HISTOGRAM = DECODE_CALLER("histogram"), BY_MOMENTS = DECODE_CALLER("moments"),
                           BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs"),
                           BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
-                          BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values");
+                          BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
+                          BY_ROLLING = DECODE_CALLER("rolling");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -2324,6 +2333,219 @@ extern "C" int atsc_select_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t 
 }
 
 // ------------------------------------------------------------------------------------------
+// windowed rolling: count / min / max / sum of the window at every position of sample ranges (atsc_rolling.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" uint64_t atsc_rolling_outputs(uint64_t count, uint64_t width, uint64_t stride)
+{
+    return width && stride && count >= width ? (count - width) / stride + 1 : 0;
+}
+
+// The check of the call's parameters and the records of its ranges (ctx may be null: then no message is kept).
+static int rolling_check(atsc_ctx *ctx, uint64_t n, const uint64_t *count, uint64_t width, uint64_t stride, uint64_t *total)
+{
+    if (width == 0 || width > ATSC_ROLLING_MAX_WIDTH) return fail(ctx, ATSC_E_INVALID, "rolling_windows: width outside [1, 2^20]");
+    if (stride == 0) return fail(ctx, ATSC_E_INVALID, "rolling_windows: stride is 0");
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        sum += atsc_rolling_outputs(count[i], width, stride);
+        if (sum > 0xfffffffeull) return fail(ctx, ATSC_E_INVALID, "rolling_windows: more than 2^32 - 2 records");
+    }
+    if (total) *total = sum;
+    return ATSC_OK;
+}
+
+// The device call.  Host work, all of it in the stream's index (org: the stream index of the plan's first sample, see
+// reduce_dev): the covering intervals of the ranges' windows (a range's samples behind its last position's window are
+// not decoded), merged where they lie closer than HST_GAP, and cut into pieces of at most Lp samples that overlap by
+// width - 1, so that every position's window lies whole in a piece: the first one that holds it computes it.  A piece
+// lies in the scratch from the multiple of ROLL_TILE at or in front of its first sample on, so that a slot's place in
+// the region and its stream index agree modulo ROLL_TILE; the pyramid of the piece's chunk partials (levels ROLL_LOW ..
+// floor(log2 width), 32 bytes each: at most 8 bytes a sample) follows the region and the spill slots in the same
+// scratch.  Region and pyramid share the budget: a region holds at most half of piece_samples' length, Lr, and a piece
+// Lp = Lr - 3 ROLL_TILE samples.  A width above Lp is ATSC_E_CAPACITY.  Per range and per piece, the run of positions
+// the piece computes is cut into tasks of ROLL_TASK positions.  One upload (decode tasks, tasks, the pieces' level
+// tables); then per piece the decode, the pyramid (with the levels above 11 and above 17 a small launch each) and the
+// positions.
+static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+                       const uint64_t *count, uint64_t width, uint64_t stride, void *d_out, void *stream, uint64_t org)
+{
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count)))
+        return fail(ctx, ATSC_E_INVALID, "rolling_windows: null argument");
+    uint64_t total = 0;
+    int rc = rolling_check(ctx, n_windows, count, width, stride, &total);
+    if (rc) return rc;
+    if (total && !d_out) return fail(ctx, ATSC_E_INVALID, "rolling_windows: null argument");
+    rc = check_windows(ctx, "rolling_windows", dp, d_out, "d_out", n_windows, begin, count, ~0ull);
+    if (rc || total == 0) return rc;
+    if (!launch_decompress_window || !launch_window_gather || !launch_roll_pyramid || !launch_roll_upper || !launch_roll_positions)
+        return fail(ctx, ATSC_E_UNSUPPORTED, "rolling_windows: no rolling kernels");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint64_t W = n_windows, T = ROLL_TILE, w = width;
+    std::vector<uint64_t> m(W);
+    std::vector<Span> cov;
+    for (uint64_t i = 0; i < W; ++i) {
+        m[i] = atsc_rolling_outputs(count[i], w, stride);
+        if (m[i]) cov.emplace_back(org + begin[i], org + begin[i] + (m[i] - 1) * stride + w);
+    }
+    merge_spans(cov);
+    uint64_t spill;
+    const uint64_t Lr = std::max<uint64_t>(AGG_MIN_PIECE, piece_samples(ctx, dp, org, cov, 1, &spill) / 2 / T * T);
+    const uint64_t Lp = Lr - 3 * T;
+    if (w > Lp) {
+        char msg[192];
+        snprintf(msg, sizeof msg,
+                 "rolling_windows: a window of %llu samples does not fit one scratch piece; an aggregate scratch budget of "
+                 "%llu bytes would hold it", (unsigned long long)w, (unsigned long long)((2 * (w + 4 * T) + spill) * sizeof(double)));
+        return fail(ctx, ATSC_E_CAPACITY, msg);
+    }
+    // pieces: samples [first, second) of the stream, ascending; scratch[0] is sample first / T * T
+    std::vector<Span> pcs;
+    uint64_t region = 0;
+    for (size_t a = 0; a < cov.size();) {
+        const uint64_t s0 = cov[a].first;
+        uint64_t s1 = cov[a].second;
+        size_t z = a + 1;
+        while (z < cov.size() && cov[z].first < s1 + HST_GAP) s1 = cov[z++].second;
+        for (uint64_t p = s0;;) {
+            const uint64_t e = std::min(s1, p + Lp);
+            pcs.emplace_back(p, e);
+            region = std::max(region, (e + T - 1) / T * T - p / T * T);
+            if (e == s1) break;
+            p = e - (w - 1);
+        }
+        a = z;
+    }
+    const size_t P = pcs.size();
+    // tasks, by piece: per range the runs of positions whose windows end inside the piece and not inside an earlier one
+    struct PT {
+        uint32_t piece;
+        DevRollTask t;
+    };
+    std::vector<PT> tk;
+    uint64_t rec = 0;
+    for (uint64_t i = 0; i < W; ++i) {
+        if (!m[i]) continue;
+        const uint64_t b = org + begin[i];
+        size_t p = (size_t)(std::lower_bound(pcs.begin(), pcs.end(), b + w, [](const Span &x, uint64_t v) { return x.second < v; }) -
+                            pcs.begin());
+        for (uint64_t j = 0; j < m[i];) {
+            const uint64_t lo = b + j * stride;
+            while (p < P && pcs[p].second < lo + w) ++p;  // (a stride longer than a piece skips pieces)
+            if (p >= P || pcs[p].first > lo)
+                return fail(ctx, ATSC_E_INVALID, "rolling_windows: internal error (position outside the pieces)");
+            const uint64_t je = std::min(m[i], (pcs[p].second - w - b) / stride + 1);  // positions whose windows end in the piece
+            for (; j < je; j += ROLL_TASK)
+                tk.push_back(PT{(uint32_t)p, DevRollTask{b + j * stride, rec + j, (uint32_t)std::min<uint64_t>(ROLL_TASK, je - j), 0}});
+            j = je;
+        }
+        rec += m[i];
+    }
+    auto by_piece = [](const PT &x, const PT &y) { return x.piece < y.piece; };
+    if (P > 1 && !std::is_sorted(tk.begin(), tk.end(), by_piece)) std::stable_sort(tk.begin(), tk.end(), by_piece);
+    std::vector<DevRollTask> tasks;
+    tasks.reserve(tk.size());
+    std::vector<size_t> at(P + 1, 0);
+    for (const PT &x : tk) { tasks.push_back(x.t); ++at[x.piece + 1]; }
+    for (size_t p = 0; p < P; ++p) at[p + 1] += at[p];
+    std::vector<PT>().swap(tk);
+    // the levels' places in the pyramid, the same in every piece: level l has room for (region >> l) + 2 chunks
+    uint32_t lmax = 0;
+    while (lmax < ROLL_MAX_LEVEL && (2ull << lmax) <= w) ++lmax;
+    std::vector<DevRollPiece> pieces(P);
+    uint64_t pyr_n = 0;
+    {
+        DevRollPiece lv{};
+        for (uint32_t l = ROLL_LOW; l <= lmax; ++l) { lv.off[l] = pyr_n; pyr_n += (region >> l) + 2; }
+        for (size_t p = 0; p < P; ++p) {
+            pieces[p] = lv;
+            pieces[p].a0 = pcs[p].first / T * T;
+            pieces[p].a1 = (pcs[p].second + T - 1) / T * T;
+        }
+    }
+    // decode tasks of every piece: the piece's samples and, in front of them, what the ranges cover of its first tile
+    std::vector<PieceDecode> pdec(P);
+    DecodeTasks D;
+    size_t ci = 0;
+    for (size_t p = 0; p < P; ++p)
+        if (!emit_piece_decode(dp, org, cov, ci, pieces[p].a0, pcs[p].second, region, D, pdec[p]))
+            return fail(ctx, ATSC_E_INVALID, "rolling_windows: internal error (spill slots)");
+    QueryRes &R = dp->res[Q_ROLLING];
+    HIPCHK(ctx, R.wait());
+    Upload up;
+    D.place(up);
+    const size_t off_tasks = up.add(tasks), off_pieces = up.add(pieces);
+    // the scratch: the region, the spill slots, the pyramid (four doubles a partial; region and MAX_FRAME are even numbers
+    // of doubles, so the pyramid begins at a multiple of 16 bytes, as its 16-byte loads and stores need)
+    const uint64_t pyr_at = region + (uint64_t)MAX_FRAME * D.spills_used;
+    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, pyr_at + 4 * pyr_n));
+    unsigned char *d = R.d;
+    up.stage(R.h);
+    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
+    double *scr = R.scratch;
+    void *pyr = scr + pyr_at;
+    const DevRollTask *d_tasks = (const DevRollTask *)(d + off_tasks);
+    const DevRollPiece *d_pieces = (const DevRollPiece *)(d + off_pieces);
+    hipError_t e;
+    for (size_t p = 0; p < P; ++p) {
+        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_ROLLING);
+        if (rc) return rc;
+        const uint64_t a0 = pieces[p].a0, last = pieces[p].a1 - 1;
+        e = launch_roll_pyramid(scr, (uint32_t)((pieces[p].a1 - a0) / T), pyr, d_pieces + p, lmax, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_roll_pyramid", e);
+        for (uint32_t src = ROLL_TILE_LOG; src < lmax; src += 6) {
+            e = launch_roll_upper(pyr, d_pieces + p, (uint32_t)(((last >> src) >> 6) - ((a0 >> src) >> 6) + 1), src, lmax, s);
+            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_roll_upper", e);
+        }
+        e = launch_roll_positions(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, pyr, d_pieces + p, w, stride, d_out, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_roll_positions", e);
+    }
+    HIPCHK(ctx, R.record(s));
+    return ATSC_OK;
+}
+
+// the rolling's descriptor (see AggQuery): the width and the stride are the call's parameters, and the size of its
+// result follows from the ranges' lengths, not from their number and not from the data
+struct RollQuery {
+    static constexpr int INPUTS = 1;
+    static constexpr const char *CALL = "rolling_windows";
+    uint64_t width, stride;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_rolling_outputs(count[i], width, stride);
+        return total * sizeof(atsc_window_rolling);
+    }
+    int check(atsc_ctx *ctx) const { return rolling_check(ctx, count ? n_ranges : 0, count, width, stride, nullptr); }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *cnt, void *d_res, void *stream, uint64_t org) const
+    {
+        return rolling_dev(ctx, dp, d_body, n_windows, begin, cnt, width, stride, d_res, stream, org);
+    }
+};
+
+extern "C" int atsc_rolling_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                        const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                        atsc_window_rolling *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    return RollQuery{width, stride, count, n_windows}.dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    ATSC_API_END
+}
+
+extern "C" int atsc_rolling_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                    const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                    atsc_window_rolling *out)
+{
+    ATSC_API_BEGIN
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, RollQuery{width, stride, count, n_windows});
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
 // the same queries on a stream under construction (atsc_stream.cpp): its records, then the host call
 // ------------------------------------------------------------------------------------------
 // a stream without a frame holds only empty windows at 0
@@ -2469,6 +2691,14 @@ extern "C" int atsc_stream_select_windows(atsc_stream *s, uint64_t n_windows, co
 {
     ATSC_API_BEGIN
     return query_stream(s, n_windows, begin, count, out, SelQuery{op, limit, cap});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_rolling_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                           uint64_t width, uint64_t stride, atsc_window_rolling *out)
+{
+    ATSC_API_BEGIN
+    return query_stream(s, n_windows, begin, count, out, RollQuery{width, stride, count, n_windows});
     ATSC_API_END
 }
 

@@ -5,7 +5,7 @@
 //
 //   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
 //                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]
-//                  [--extremes K] [--values K[:ABOVE]]] [--where OP:LIMIT]]]
+//                  [--extremes K] [--values K[:ABOVE]]] [--where OP:LIMIT] [--rolling W[:S]]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
@@ -74,6 +74,10 @@ void usage()
             "      --where <OP:LIMIT>         with --from/--to, without --step: write the window's samples with value OP LIMIT\n"
             "                                 (as --runs) to .sel.csv instead of the .wbro and .csv: timestamp,value, one row\n"
             "                                 per selected sample, timestamp its indexed time\n"
+            "      --rolling <W[:S]>          with --from/--to, without --step: write the window of W samples at every S-th\n"
+            "                                 position of the window's samples (S: 1) to .roll.csv instead of the .wbro and\n"
+            "                                 .csv: timestamp,count,min,max,sum,mean, timestamp the indexed time of the\n"
+            "                                 position's LAST sample; mean is sum / count, empty where count is 0\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -164,6 +168,39 @@ int uncompress_where(const Args &a, const std::string &output_base, uint8_t *bro
     return 0;
 }
 
+// -u --from T0 --to T1 --rolling W[:S]: the index finds the window, the GPU the sliding window's record at every position
+// of it; a row carries the indexed time of its window's LAST sample, where a trailing average is plotted, from the same
+// get_time path as the window's .csv; <out>.roll.csv is all that is written
+int uncompress_rolling(const Args &a, const std::string &output_base, uint8_t *bro, uint64_t len)
+{
+    atsc_vsri *index = nullptr;
+    int rc = atsc_vsri_load(with_ext(a.input, "vsri").c_str(), &index);
+    if (rc) { atsc_free(bro); return die("failed to read vsri", rc); }
+    uint64_t begin = 0, count = 0;
+    rc = atsc_vsri_sample_window(index, a.t0, a.t1, &begin, &count);
+    if (rc) { atsc_free(bro); atsc_vsri_free(index); return die("vsri window", rc); }
+    std::vector<int64_t> ts(begin + count + 1);
+    rc = atsc_metric_sample_times(index, begin + count, ts.data());
+    atsc_vsri_free(index);
+    if (rc) { atsc_free(bro); return die("called `Option::unwrap()` on a `None` value (index has no time for a sample)"); }
+    std::vector<atsc_window_rolling> rows;
+    if (count) {
+        atsc_ctx *ctx = nullptr;
+        rc = atsc_ctx_create(&ctx, 0);
+        if (rc) { atsc_free(bro); return die("no GPU context", rc); }
+        rc = atsc_bro_open(bro, len, nullptr, nullptr);
+        if (!rc) rc = rolling_query(ctx, bro, len, a.q, begin, count, rows);
+        if (rc) { int e = die("rolling", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
+        atsc_ctx_destroy(ctx);
+    }
+    atsc_free(bro);
+    const uint64_t w = a.q.rolling, stride = a.q.rolling_stride;
+    if (!rolling_write(with_ext(output_base, "roll.csv"), "timestamp", rows,
+                       [&](uint64_t j) { return std::to_string((long long)ts[begin + j * stride + w - 1]); }))
+        return die("failed to write rolling records to file");
+    return 0;
+}
+
 // -u --from T0 --to T1 --step S: the time buckets [T0 + k S, min(T0 + (k + 1) S - 1, T1)] as sample windows of the index,
 // one atsc_window_stats row each (timestamp = the bucket's start) into <out>.agg.csv; nothing else is written
 int uncompress_buckets(const Args &a, const std::string &output_base, uint8_t *bro, uint64_t len)
@@ -237,6 +274,7 @@ int uncompress(const Args &a, const std::string &output_base)  // main.rs:139-17
     if (!bro) return 0;  // not a BRO file: nothing happens
     if (a.step) return uncompress_buckets(a, output_base, bro, len);
     if (a.q.have_where) return uncompress_where(a, output_base, bro, len);
+    if (a.q.rolling) return uncompress_rolling(a, output_base, bro, len);
     if (a.window) return uncompress_window(a, output_base, bro, len);
     atsc_ctx *ctx = nullptr;
     rc = atsc_ctx_create(&ctx, 0);
@@ -367,6 +405,7 @@ int main(int argc, char **argv)
     }
     if (!bucket_options_complete(a.q, "--step", a.step != 0)) return 2;
     if (!where_option_complete(a.q, "--from' and '--to", have_from, "--step", a.step != 0)) return 2;
+    if (!rolling_option_complete(a.q, "--from' and '--to", have_from, "--step", a.step != 0)) return 2;
     a.window = have_from;
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) return die("Failed to retrieve metadata of the input");  // main.rs:226-229

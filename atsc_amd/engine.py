@@ -60,6 +60,24 @@ VALUE_MODE = np.dtype([("value", "<f8"), ("n", "<u8"), ("exact", "<u4"), ("pad",
 SELECTED = np.dtype([("value", "<f8"), ("at", "<u8")])
 
 
+# atsc_window_rolling (include/atsc_hip.h): the record of one position of a rolling call, 32 bytes
+WINDOW_ROLLING = np.dtype([("count", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sum", "<f8")])
+ROLLING_MAX_WIDTH = capi.ROLLING_MAX_WIDTH
+
+
+def rolling_outputs(count, width, stride=1):
+    """-> the positions of a range of `count` samples under a window of `width` samples moved by `stride`
+    (atsc_rolling_outputs; no GPU): (count - width) // stride + 1, or 0 where the range is shorter than the window or
+    width or stride is 0"""
+    return int(capi.lib().atsc_rolling_outputs(int(count), int(width), int(stride)))
+
+
+def rolling_offsets(counts, width, stride=1):
+    """-> uint64 array of len(counts) + 1 offsets: the records of range i of a rolling call are [off[i], off[i + 1])"""
+    c = np.atleast_1d(np.asarray(counts, dtype=np.uint64))
+    return np.concatenate([[0], np.cumsum([rolling_outputs(v, width, stride) for v in c], dtype=np.uint64)]).astype(np.uint64)
+
+
 def select_bytes(n_windows, cap):
     """-> bytes of the block of a select call (ATSC_SELECT_BYTES): n_windows + 1 offsets, then cap entries"""
     return 8 * (int(n_windows) + 1) + 16 * int(cap)
@@ -166,6 +184,31 @@ def _select_result(run, n, cap):
     return off, blk[n + 1: n + 1 + 2 * m].copy().view(SELECTED)
 
 
+class _RollArgs(tuple):
+    """the C arguments of a rolling call, and the records of its ranges"""
+    records = 0
+
+
+def _rolling_params(width, stride, records):
+    width, stride = int(width), int(stride)
+    if not (0 <= width < 2 ** 64 and 0 <= stride < 2 ** 64):
+        raise ValueError("width or stride outside uint64")
+    a = _RollArgs((C.c_uint64(width), C.c_uint64(stride)))
+    a.records = int(records)
+    return a
+
+
+def _rolling_block(n, cargs):
+    return WINDOW_ROLLING.itemsize * cargs.records
+
+
+def _rolling_result(run, counts, width, stride):
+    """run(records) -> the block of a rolling call as uint64 words.  -> (records, off): the WINDOW_ROLLING records of
+    every position, range after range, and the ranges' record offsets (rolling_offsets)"""
+    off = rolling_offsets(counts, width, stride)
+    return run(int(off[-1])).view(WINDOW_ROLLING), off
+
+
 def _array_params(values, flag):
     """levels and method, or edges and closed"""
     a, pa = _levels(values)
@@ -180,6 +223,7 @@ _RUNS = _Query("runs_windows", WINDOW_RUNS, None, _runs_params)
 _EXTREMES = _Query("extremes_windows", _extremes_dtype, None, _extremes_params)
 _VALUES = _Query("values_windows", _values_dtype, None, _values_params)
 _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _select_block)
+_ROLLING = _Query("rolling_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_block)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
 _HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
 
@@ -474,6 +518,14 @@ class Context:
         n = len(np.atleast_1d(begins))
         return _select_result(lambda c: _query_host(_SELECT, self, records, begins, counts, has_count, op, limit, c), n, cap)
 
+    def rolling_windows_host(self, records, begins, counts, width, stride=1, has_count=False):
+        """-> (records, off): count / min / max / sum of the window of `width` samples at every `stride`-th position of
+        every range [begins[i], begins[i] + counts[i]) of the decoded records (atsc_rolling_windows).  records: a
+        WINDOW_ROLLING array, range after range; off: len(begins) + 1 offsets, range i's records being
+        records[off[i]:off[i + 1]] (a range shorter than the window has none)"""
+        return _rolling_result(lambda m: _query_host(_ROLLING, self, records, begins, counts, has_count, width, stride, m),
+                               counts, width, stride)
+
     def extremes_windows_host(self, records, begins, counts, k, has_count=False):
         """-> array of window_extremes_dtype(k): the k largest and the k smallest non-NaN samples, each with its offset
         in the window, the number of NaN samples and the length of every window [begins[i], begins[i] + counts[i]) of
@@ -646,6 +698,15 @@ class DPlan:
         tensor of at least select_bytes(len(begins), cap) bytes: the offsets, then the entries below cap
         (atsc_select_windows_dev)"""
         _query_dev(_SELECT, self, d_body, begins, counts, d_out, stream, op, limit, cap)
+
+    def rolling_windows(self, d_body, begins, counts, width, stride, d_out, stream=0):
+        """Enqueues count / min / max / sum of the window of `width` samples at every `stride`-th position of the ranges
+        [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least 32 bytes per position
+        (atsc_rolling_windows_dev; WINDOW_ROLLING records, range after range).  -> the ranges' record offsets
+        (rolling_offsets)"""
+        off = rolling_offsets(counts, width, stride)
+        _query_dev(_ROLLING, self, d_body, begins, counts, d_out, stream, width, stride, int(off[-1]))
+        return off
 
     def extremes_windows(self, d_body, begins, counts, k, d_out, stream=0):
         """Enqueues the k largest and the k smallest samples of the windows [begins[i], begins[i] + counts[i]) into

@@ -6,8 +6,8 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit, pair_fit  # noqa: F401
-from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _select_result
+from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_ROLLING, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit, pair_fit  # noqa: F401
+from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
 
 
 def _f64(x):
@@ -146,6 +146,11 @@ class CompressedStream:
         n = len(np.atleast_1d(begins))
         return _select_result(lambda c: _query_stream(_SELECT, self, begins, counts, op, limit, c), n, cap)
 
+    def rolling_windows(self, begins, counts, width, stride=1):
+        """-> (records, off) of the window of `width` samples at every `stride`-th position of the ranges [begins[i],
+        begins[i] + counts[i]), as Context.rolling_windows_host gives them (atsc_stream_rolling_windows)"""
+        return _rolling_result(lambda m: _query_stream(_ROLLING, self, begins, counts, width, stride, m), counts, width, stride)
+
     def extremes_windows(self, begins, counts, k):
         """-> array of window_extremes_dtype(k) of the windows [begins[i], begins[i] + counts[i]): their k largest and k
         smallest samples and where they are (atsc_stream_extremes_windows)"""
@@ -229,6 +234,13 @@ def select_data_windows(ctx, bro, begins, counts, op, limit, cap=None):
     Context.select_windows_host gives them: atsc_bro_open, then atsc_select_windows over the records"""
     n = len(np.atleast_1d(begins))
     return _select_result(lambda c: _query_image(_SELECT, ctx, bro, begins, counts, op, limit, c), n, cap)
+
+
+def rolling_data_windows(ctx, bro, begins, counts, width, stride=1):
+    """-> (records, off) of the window of `width` samples at every `stride`-th position of ranges of
+    decompress_data(ctx, bro), as Context.rolling_windows_host gives them: atsc_bro_open, then atsc_rolling_windows over
+    the records"""
+    return _rolling_result(lambda m: _query_image(_ROLLING, ctx, bro, begins, counts, width, stride, m), counts, width, stride)
 
 
 def extremes_data_windows(ctx, bro, begins, counts, k):

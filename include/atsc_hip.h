@@ -751,6 +751,62 @@ int atsc_select_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *
 int atsc_select_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
                         const uint64_t *begin, const uint64_t *count, int op, double limit, uint64_t cap, void *out);
 
+/* Windowed rolling: the sliding window of one width at every position of ranges of the decoded stream (the indices of
+ * atsc_decompress_frames), from the same decoded samples as the window decode.  The caller names each range once; the
+ * work grows with the ranges' lengths, not with positions x width.
+ *   Ranges     Range i is [begin[i], begin[i] + count[i]).  One width w, 1 <= w <= ATSC_ROLLING_MAX_WIDTH, and one stride
+ *              s >= 1 hold for every range of a call.  Range i has m_i = count[i] >= w ? (count[i] - w) / s + 1 : 0
+ *              positions (atsc_rolling_outputs; 0 for w == 0 or s == 0); position j is the window [begin[i] + j s,
+ *              begin[i] + j s + w), which lies wholly inside the range.  Records are stored range after range, position
+ *              j of range i at index m_0 + .. + m_(i-1) + j of the result.  A range shorter than w has no record;
+ *              n_windows == 0 and count[i] == 0 are valid.  Ranges may overlap and come in any order.
+ *   count, min, max   what atsc_aggregate_windows returns for the same window, bit for bit, the sign of a zero extreme
+ *              included.
+ *   sum        over the window's non-NaN samples in an order of its own, fixed by the stream's samples and the window
+ *              [lo, lo + w) alone: not by the range the window came from, the stride, the other ranges, the budget, the
+ *              piece boundaries, the framing or the device.
+ *              term(j) = x[j], or -0.0 where x[j] is NaN.
+ *              T(a, 0) = term(a); T(a, l) = T(a, l - 1) + T(a + 2^(l-1), l - 1), for a a multiple of 2^l in the stream
+ *              index (never an index into the part of the stream a call happened to upload).
+ *              The window's chunks, left to right: pos = lo; while pos < lo + w, take the largest l with pos % 2^l == 0
+ *              and pos + 2^l <= lo + w, emit (pos, l), pos += 2^l: at most 2 ceil(log2 w) chunks (one when w == 1).
+ *              sum = ((T(c_1) + T(c_2)) + T(c_3)) + ..., every operation one correctly rounded f64 add, never fused;
+ *              +0.0 when count == 0; +-Inf give what IEEE gives (where that is NaN, any NaN conforms).
+ *              With u = 2^-53 and L = max(1, ceil(log2 w)): |sum - exact| <= 3 L u sum|x| for finite data (the tree
+ *              rounds at most L times, the chain at most 2 L - 1 times).
+ *              This sum MAY DIFFER from atsc_aggregate_windows' sum of the same window in its last bits: the two are
+ *              different orders of the same additions, and each lies within its own stated bound of the exact sum.
+ *              Chunks never reach outside their window, so T depends on no window: every window's sum is read off one
+ *              pyramid of aligned chunk sums, which is what the order is for.
+ * Errors: ATSC_E_INVALID with nothing written and before any GPU work for width == 0, width > ATSC_ROLLING_MAX_WIDTH,
+ * stride == 0, more than 2^32 - 2 records in all, and a range beyond the stream.  Payloads are checked only of the
+ * frames that a position's window touches.  Decoded samples and the chunk sums both live inside the budget of
+ * atsc_ctx_set_aggregate_scratch (raised to one piece's minimum: 65536 samples, as many bytes again of chunk sums, and two
+ * large frames' room); a range longer than a piece is cut into pieces that overlap by w - 1 samples, and every position
+ * is computed from one piece.  A width whose window does not fit one piece under the budget gives ATSC_E_CAPACITY (the
+ * quantiles' rule; never under the default budget). */
+#define ATSC_ROLLING_MAX_WIDTH (1ull << 20)
+typedef struct {
+    uint64_t count; /* samples of the position's window that are not NaN */
+    double min, max; /* over those; NaN when count == 0 */
+    double sum;      /* over those, in the order above; +0.0 when count == 0 */
+} atsc_window_rolling; /* 32 bytes */
+/* Positions of a range of `count` samples (host only, no GPU). */
+uint64_t atsc_rolling_outputs(uint64_t count, uint64_t width, uint64_t stride);
+/* begin / count are HOST arrays; d_body and d_out are device memory (d_out 8-byte aligned, 32 bytes per record).
+ * Enqueued on `stream`, not synchronised.  A malformed payload inside a position's window sets the plan's status word.
+ * The plan keeps the call's tables and scratch: the next rolling call on the same plan waits (host side) until this
+ * one's work is done; atsc_dplan_destroy frees them. */
+int atsc_rolling_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                             const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                             atsc_window_rolling *d_out, void *stream);
+/* Host bytes in, host records out, synchronous; walks and uploads only the touched records, as atsc_aggregate_windows
+ * does, and computes the device call's bits.  ATSC_E_FORMAT (nothing written) for a malformed payload inside a
+ * position's window. */
+int atsc_rolling_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                         const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                         atsc_window_rolling *out);
+
 /* Windowed quantiles: exact order statistics of windows [begin, begin + count) of the decoded stream (the indices of
  * atsc_decompress_frames), from the same decoded samples as the window decode.  For window i:
  *   x  the window's non-NaN samples, n of them, sorted in IEEE total order (-0.0 before +0.0), i.e. by the keys
@@ -866,6 +922,9 @@ int atsc_stream_values_windows(atsc_stream *s, uint64_t n_windows, const uint64_
 /* atsc_select_windows over the stream's frames */
 int atsc_stream_select_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                int op, double limit, uint64_t cap, void *out);
+/* atsc_rolling_windows over the stream's frames */
+int atsc_stream_rolling_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                uint64_t width, uint64_t stride, atsc_window_rolling *out);
 /* atsc_moments_windows over the stream's frames */
 int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 atsc_window_moments *out);
