@@ -4,7 +4,7 @@
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
-//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S]]]
+//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S]] [--across A.bro,B.bro,.. [--across-stride S]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -79,6 +79,14 @@ void usage()
             "                                 S-th position of the samples (S: 1) to .roll.csv instead of the .wbro:\n"
             "                                 offset,count,min,max,sum,mean, offset the position's first sample counted\n"
             "                                 from BEGIN; mean is sum / count, empty where count is 0\n"
+            "      --across <A.bro,B.bro,..>  with -u --samples, without --buckets, --rolling and --where: fold this file (stream\n"
+            "                                 0) and the listed files (streams 1.., at most 63) at the same sample indices and\n"
+            "                                 write one row per sample to .across.csv instead of the .wbro:\n"
+            "                                 offset,count,min,min_at,max,max_at,sum,mean -- offset counted from BEGIN, count the\n"
+            "                                 streams whose sample is not NaN, min_at / max_at the stream that holds the extreme\n"
+            "                                 (the first of equal ones), sum in list order; min_at, max_at and mean (sum / count)\n"
+            "                                 empty where count is 0.  Every file must reach the window's end\n"
+            "      --across-stride <S>        with --across: every S-th sample of the window only [default: 1]\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -171,6 +179,14 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
                        ? ATSC_OK
                        : ATSC_E_IO;
         }
+        if (!a.q.across.empty()) {  // (with --samples) the window's across records over this file and the listed ones, no .wbro
+            std::vector<atsc_across_record> rows;
+            rc = atsc_bro_open(bro, len, nullptr, nullptr);
+            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows);
+            atsc_free(bro);
+            if (rc) return rc;
+            return across_write(with_ext(path, "across.csv"), rows, a.q.across_stride) ? ATSC_OK : ATSC_E_IO;
+        }
         double *out = nullptr;
         uint64_t n = 0;
         if (a.window) {
@@ -255,6 +271,7 @@ int main(int argc, char **argv)
 {
     Args a;
     a.q.pair_allowed = true;
+    a.q.across_allowed = true;
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i], v;
         auto value = [&](const char *name) -> bool {
@@ -304,6 +321,7 @@ int main(int argc, char **argv)
     if (!bucket_options_complete(a.q, "--buckets", a.buckets != 0)) return 2;
     if (!where_option_complete(a.q, "--samples", a.window, "--buckets", a.buckets != 0)) return 2;
     if (!rolling_option_complete(a.q, "--samples", a.window, "--buckets", a.buckets != 0)) return 2;
+    if (!across_option_complete(a.q, "--samples", a.window, "--buckets", a.buckets != 0)) return 2;
     struct stat st;
     if (stat(a.input.c_str(), &st) != 0) { fprintf(stderr, "[ERROR] %s: No such file or directory\n", a.input.c_str()); return 1; }
     atsc_ctx *ctx = nullptr;

@@ -1,8 +1,9 @@
 // atsc_cli_buckets.h -- what the two command lines (atsc_cli.cpp, csv_compressor_cli.cpp) share: the small text helpers
 // and the bucket queries behind `atsc -u --buckets N` and `csv-compressor -u --from --to --step S`: their options, the
 // usage errors, the calls over the buckets and the columns of the .agg.csv; `--rolling W[:S]`, the sliding window's
-// records at every position of a window; and `--where OP:LIMIT`, the selected samples
-// of the window itself into a .sel.csv (the end of this file).  The two differ in the row's first cell,
+// records at every position of a window; `--where OP:LIMIT`, the selected samples
+// of the window itself into a .sel.csv; and `--across A.bro,B.bro,..` (atsc only), the across records of the window over
+// several files into an .across.csv (the end of this file).  The two differ in the row's first cell,
 // in how a failure is reported and in how a position inside a bucket is written: the three run positions, which the
 // caller hands in, and the extremes' positions, which csv-compressor rewrites as times (bucket_extreme_places).
 #pragma once
@@ -73,6 +74,10 @@ struct BucketOptions {
     double where_limit = 0.0;
     uint64_t rolling = 0;  // --rolling W[:S]: no bucket query; the window's rolling records into .roll.csv
     uint64_t rolling_stride = 1;
+    bool across_allowed = false;      // the front end takes --across (atsc; csv-compressor does not: DESIGN.md "Windowed across")
+    std::vector<std::string> across;  // --across A.bro,B.bro,..: no bucket query; the window's across records into .across.csv
+    uint64_t across_stride = 1;       // --across-stride S
+    bool have_across_stride = false;
 };
 
 // --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
@@ -183,7 +188,22 @@ bool parse_rolling(const std::string &v, uint64_t &width, uint64_t &stride)
     return c == std::string::npos || number(v.substr(c + 1), stride);
 }
 
-// --pair OTHER.bro is taken only where the front end allows it (o.pair_allowed).
+// --across A.bro,B.bro,..: one to ATSC_ACROSS_MAX_STREAMS - 1 paths (the input file is stream 0), none of them empty
+bool parse_across(const std::string &v, std::vector<std::string> &files)
+{
+    files.clear();
+    for (size_t p = 0;;) {
+        const size_t c = v.find(',', p);
+        const std::string t = v.substr(p, c == std::string::npos ? std::string::npos : c - p);
+        if (t.empty()) return false;
+        files.push_back(t);
+        if (c == std::string::npos) return files.size() < (size_t)ATSC_ACROSS_MAX_STREAMS;
+        p = c + 1;
+    }
+}
+
+// --pair OTHER.bro, --across and --across-stride are taken only where the front end allows them (o.pair_allowed,
+// o.across_allowed).
 // One argument of the command line, where it is a bucket-query option.  s: the argument; value(name): whether s is the
 // option `name` with a value, which it leaves in v (the callers' lambda).  0: none of them; 1: taken; 2: a usage error,
 // reported on stderr.
@@ -262,6 +282,20 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             return 2;
         }
         o.pair = v;
+    } else if (o.across_allowed && value("--across")) {
+        if (!parse_across(v, o.across)) {
+            fprintf(stderr, "error: invalid value '%s' for '--across': expected 1..=%d paths of .bro files, comma separated\n",
+                    v.c_str(), (int)ATSC_ACROSS_MAX_STREAMS - 1);
+            return 2;
+        }
+    } else if (o.across_allowed && value("--across-stride")) {
+        char *e = nullptr;
+        o.across_stride = strtoull(v.c_str(), &e, 10);
+        if (v.empty() || !isdigit((unsigned char)v[0]) || *e || v.size() > 19 || o.across_stride == 0) {
+            fprintf(stderr, "error: invalid value '%s' for '--across-stride': expected a stride of at least 1\n", v.c_str());
+            return 2;
+        }
+        o.have_across_stride = true;
     } else {
         return 0;
     }
@@ -320,6 +354,25 @@ bool rolling_option_complete(const BucketOptions &o, const char *window, bool wi
     }
     if (bucketed || o.have_where) {
         fprintf(stderr, "error: '--rolling' cannot be used with '%s'\n", bucketed ? bucketing : "--where");
+        return false;
+    }
+    return true;
+}
+
+// --across goes with the option that names the window and without the one that cuts buckets, --rolling and --where;
+// --across-stride goes with --across.  false: a usage error, reported on stderr.
+bool across_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
+{
+    if (o.across.empty()) {
+        if (o.have_across_stride) fprintf(stderr, "error: '--across-stride' needs '--across'\n");
+        return !o.have_across_stride;
+    }
+    if (!windowed) {
+        fprintf(stderr, "error: '--across' needs '%s'\n", window);
+        return false;
+    }
+    if (bucketed || o.rolling || o.have_where) {
+        fprintf(stderr, "error: '--across' cannot be used with '%s'\n", bucketed ? bucketing : o.rolling ? "--rolling" : "--where");
         return false;
     }
     return true;
@@ -561,6 +614,53 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
         const atsc_window_rolling &r = rows[j];
         fprintf(f, "%s,%llu,%s,%s,%s,%s\n", place(j).c_str(), (unsigned long long)r.count, debug_f64(r.min).c_str(),
                 debug_f64(r.max).c_str(), debug_f64(r.sum).c_str(), r.count ? debug_f64(r.sum / (double)r.count).c_str() : "");
+    }
+    return fclose(f) == 0;
+}
+
+// --across: one record per position of the range [begin, begin + count) over the .bro image (stream 0) and the listed
+// files (stream 1 and on): sample i of each goes with sample i of the others
+int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
+                 std::vector<atsc_across_record> &rows)
+{
+    std::vector<uint8_t *> image(o.across.size(), nullptr);
+    std::vector<const uint8_t *> body{bro + 9};
+    std::vector<uint64_t> body_len{len - 9};
+    int rc = ATSC_OK;
+    for (size_t k = 0; k < o.across.size() && !rc; ++k) {
+        uint64_t n = 0;
+        rc = atsc_bro_read_file(o.across[k].c_str(), &image[k], &n);
+        if (!rc && !image[k]) rc = ATSC_E_FORMAT;  // not a BRO file
+        if (!rc) rc = atsc_bro_open(image[k], n, nullptr, nullptr);
+        if (rc) break;
+        body.push_back(image[k] + 9);
+        body_len.push_back(n - 9);
+    }
+    if (!rc) {
+        const std::vector<int> has_count(body.size(), 1);
+        rows.assign(atsc_across_outputs(count, o.across_stride), atsc_across_record{});
+        atsc_across_record none;
+        rc = atsc_across_windows(ctx, (uint32_t)body.size(), body.data(), body_len.data(), has_count.data(), 1, &begin, &count,
+                                 o.across_stride, rows.empty() ? &none : rows.data());
+    }
+    for (uint8_t *p : image) atsc_free(p);
+    return rc;
+}
+
+// the .across.csv: offset,count,min,min_at,max,max_at,sum,mean and one row per position; offset: the position's sample
+// counted from the window's begin; values as the .agg.csv writes them; min_at and max_at (the stream's place in the
+// list, the input file 0) and mean = sum / count empty where count == 0.  false: the file could not be written.
+bool across_write(const std::string &path, const std::vector<atsc_across_record> &rows, uint64_t stride)
+{
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return false;
+    fprintf(f, "offset,count,min,min_at,max,max_at,sum,mean\n");
+    for (size_t j = 0; j < rows.size(); ++j) {
+        const atsc_across_record &r = rows[j];
+        const std::string mn_at = r.count ? std::to_string(r.min_at) : std::string(), mx_at = r.count ? std::to_string(r.max_at) : std::string();
+        fprintf(f, "%llu,%u,%s,%s,%s,%s,%s,%s\n", (unsigned long long)(j * stride), r.count, debug_f64(r.min).c_str(), mn_at.c_str(),
+                debug_f64(r.max).c_str(), mx_at.c_str(), debug_f64(r.sum).c_str(),
+                r.count ? debug_f64(r.sum / (double)r.count).c_str() : "");
     }
     return fclose(f) == 0;
 }

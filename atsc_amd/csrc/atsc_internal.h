@@ -336,6 +336,11 @@ struct DevRollTask {
     uint32_t n, pad;
 };
 
+// windowed across (atsc_across_windows_dev, atsc_across.hip): every stream of a call decoded into a scratch region of
+// its own, the same sample at the same slot of every region, then one record per position from its slot of each.  A
+// task is a DevRollTask: n positions of one range inside one piece, the first at sample lo of the streams.
+constexpr uint32_t ACR_TASK = 512;  // positions per task: one wavefront, four steps of 64 pairs at stride 1
+
 static inline uint32_t varint_len_u64(uint64_t v)
 {
     return v < 251 ? 1u : v < (1ull << 16) ? 3u : v < (1ull << 32) ? 5u : 9u;

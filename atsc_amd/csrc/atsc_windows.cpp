@@ -1,5 +1,6 @@
 // atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms,
-// rolling windows and selected samples of ranges of the decoded stream without decoding the rest, and the pair moments of the same ranges of two streams.  Each query has a device call (host tables, one upload, launches on the caller's
+// rolling windows and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
+// and count, min, max and sum across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
@@ -92,6 +93,10 @@ __attribute__((weak)) hipError_t launch_roll_upper(void *pyr, const DevRollPiece
 __attribute__((weak)) hipError_t launch_roll_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                        const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
                                                        void *out, hipStream_t s);
+// the windowed across' position kernel (atsc_across.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_across_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
+                                                         const uint64_t *reg, uint32_t n_streams, uint64_t a0,
+                                                         uint64_t stride, void *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -297,7 +302,7 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs"),
                           BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
                           BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
-                          BY_ROLLING = DECODE_CALLER("rolling");
+                          BY_ROLLING = DECODE_CALLER("rolling"), BY_ACROSS = DECODE_CALLER("across");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -357,8 +362,8 @@ static int check_windows(atsc_ctx *ctx, const char *call, const atsc_dplan *dp, 
 // ------------------------------------------------------------------------------------------
 // Walks the headers from the first non-empty window's first record to the record that holds the last window's end,
 // plans those records only and uploads only their bytes; the result comes back once the payloads proved well-formed (a
-// malformed one leaves `out` untouched).  A query over two streams (n_in == 2) does the walk, the range plan and the
-// upload for each body, over the same windows; every body's status word is read before anything is copied out.
+// malformed one leaves `out` untouched).  A query over several streams (n_in > 1, at most MAX_INPUTS) does the walk, the
+// range plan and the upload for each body, over the same windows; every body's status word is read before anything is copied out.
 // `call` names the caller in the messages.  The caller's two steps:
 //   located(any)  after the walk, which is what rejects a window beyond the stream: the caller's own checks, and its
 //                 result when every window is empty (any == false: the call ends there);
@@ -378,7 +383,7 @@ struct QueryInput {
     const uint8_t *d_body;
     uint64_t org;
 };
-static const int MAX_INPUTS = 2;
+static const int MAX_INPUTS = ATSC_ACROSS_MAX_STREAMS;  // the most streams a query reads (the across; the pair moments: 2)
 
 template <class Located, class Enqueue, class Used>
 static int window_host_call(atsc_ctx *ctx, const char *call, const HostBody *hb, int n_in, uint64_t n_windows,
@@ -739,7 +744,8 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
 // A query's descriptor: what query_host and query_stream (below) need of it, and for the four reductions over tiles
 // what reduce_dev does.  The front end's part:
 //   CALL                the call's name in the messages
-//   INPUTS              the streams the query reads: 1, or 2 (PairQuery) -- that many bodies, streams or plans
+//   INPUTS              the streams the query reads: 1, or 2 (PairQuery) -- that many bodies, streams or plans; 0 where
+//                       the number is the call's own (AcrossQuery), which inputs() then gives (query_inputs)
 //   out_bytes(n)        bytes of the result of n windows
 //   check(ctx)          the check of the call's parameters (ctx may be null: then no message is kept)
 //   fill_empty(out, n)  the result of n empty windows
@@ -1163,7 +1169,7 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
     for (uint64_t i = 0; i < W; ++i)
         if (count[i]) cov.emplace_back(org + begin[i], org + begin[i] + count[i]);
     merge_spans(cov);
-    uint64_t spill[MAX_INPUTS];
+    uint64_t spill[NI];
     const uint64_t piece_tiles = piece_samples(ctx, in, NI, cov, T, spill) / T;
     struct Piece {
         uint64_t k0, k1;  // tiles [k0, k1): samples [k0 T, k1 T) at scratch[0, (k1 - k0) T)
@@ -1247,14 +1253,14 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
         }
     }
     // decode tasks of every piece (emit_piece_decode), once per input, and its tile tasks
-    std::vector<PieceDecode> pdec[MAX_INPUTS];
+    std::vector<PieceDecode> pdec[NI];
     std::vector<size_t> tile_at(pcs.size());
     std::vector<uint32_t> tile_n(pcs.size());
     std::vector<char> carry_in(pcs.size(), 0);  // the piece's first tile reads the previous piece's last sample
-    DecodeTasks D[MAX_INPUTS];
+    DecodeTasks D[NI];
     std::vector<typename Q::Tile> tiles;
     tiles.reserve(tt.size());
-    size_t ci[MAX_INPUTS] = {}, ti = 0;
+    size_t ci[NI] = {}, ti = 0;
     for (int k = 0; k < NI; ++k) pdec[k].resize(pcs.size());
     for (size_t p = 0; p < pcs.size(); ++p) {
         tile_at[p] = tiles.size();
@@ -1292,7 +1298,7 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
                                                : up.device_only(Q::CARRY ? sizeof(double) : 2 * W * sizeof(double));
     // every input's region and behind it the spill slots it uses; region and MAX_FRAME are even numbers of doubles, so
     // every region begins at a multiple of 16 bytes, as the tile kernels' 16-byte loads need
-    uint64_t scr_at[MAX_INPUTS], scr_n = 0;
+    uint64_t scr_at[NI], scr_n = 0;
     for (int k = 0; k < NI; ++k) {
         scr_at[k] = scr_n;
         scr_n += region + (uint64_t)MAX_FRAME * D[k].spills_used;
@@ -1302,7 +1308,7 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
     unsigned char *d = R.d;
     up.stage(R.h);
     HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
-    double *scr[MAX_INPUTS];
+    double *scr[NI];
     for (int k = 0; k < NI; ++k) scr[k] = R.scratch + scr_at[k];
     void *part = d + off_part, *side = d + off_side;
     for (size_t p = 0; p < pcs.size(); ++p) {
@@ -1343,7 +1349,15 @@ static size_t result_used_bytes(const Q &q, const void *head, uint64_t n)
     else return q.out_bytes(n);
 }
 
-// The device call of a query on the plans in[0 .. Q::INPUTS): a query over one stream takes its plan, bytes and origin.
+// The streams a query reads: its INPUTS constant, or for a query over a runtime number of them (INPUTS == 0) the call's own.
+template <class Q>
+static int query_inputs(const Q &q)
+{
+    if constexpr (Q::INPUTS > 0) return Q::INPUTS;
+    else return q.inputs();
+}
+
+// The device call of a query on the plans in[0 .. query_inputs(q)): a query over one stream takes its plan, bytes and origin.
 template <class Q>
 static int query_dev(const Q &q, atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin,
                      const uint64_t *count, void *d_res, void *stream)
@@ -1352,20 +1366,21 @@ static int query_dev(const Q &q, atsc_ctx *ctx, const QueryInput *in, uint64_t n
     else return q.dev(ctx, in, n_windows, begin, count, d_res, stream);
 }
 
-// The host call of a query over the bodies hb[0 .. Q::INPUTS): the argument check, the query's own, then
-// window_host_call into its device call.
+// The host call of a query over the bodies hb[0 .. query_inputs(q)), at most MAX_INPUTS of them: the argument check, the
+// query's own, then window_host_call into its device call.
 template <class Q>
 static int query_host(atsc_ctx *ctx, const HostBody *hb, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                       void *out, const Q &q)
 {
+    const int n_in = query_inputs(q);
     bool bodies = true;
-    for (int k = 0; k < Q::INPUTS; ++k) bodies = bodies && hb[k].body;
+    for (int k = 0; k < n_in; ++k) bodies = bodies && hb[k].body;
     if (!ctx || !bodies || (n_windows && (!begin || !count || !out))) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
     const int rc = q.check(ctx);
     if (rc) return rc;
     if (n_windows == 0) return ATSC_OK;
     return window_host_call(
-        ctx, Q::CALL, hb, Q::INPUTS, n_windows, begin, count, out, q.out_bytes(n_windows), result_head_bytes(q, n_windows),
+        ctx, Q::CALL, hb, n_in, n_windows, begin, count, out, q.out_bytes(n_windows), result_head_bytes(q, n_windows),
         false,
         [&](bool any) {
             if (!any) q.fill_empty(out, n_windows);
@@ -2546,6 +2561,232 @@ extern "C" int atsc_rolling_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t
 }
 
 // ------------------------------------------------------------------------------------------
+// windowed across: count / min / max / sum over N streams at every position of sample ranges (atsc_across.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" uint64_t atsc_across_outputs(uint64_t count, uint64_t stride)
+{
+    return count && stride ? (count - 1) / stride + 1 : 0;
+}
+
+// The check of the call's parameters and the records of its ranges (ctx may be null: then no message is kept).
+static int across_check(atsc_ctx *ctx, uint32_t n_streams, uint64_t n, const uint64_t *count, uint64_t stride, uint64_t *total)
+{
+    if (n_streams == 0 || n_streams > ATSC_ACROSS_MAX_STREAMS)
+        return fail(ctx, ATSC_E_INVALID, "across_windows: n_streams outside [1, 64]");
+    if (stride == 0) return fail(ctx, ATSC_E_INVALID, "across_windows: stride is 0");
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t m = atsc_across_outputs(count[i], stride);
+        if (m > 0xfffffffeull || (sum += m) > 0xfffffffeull)
+            return fail(ctx, ATSC_E_INVALID, "across_windows: more than 2^32 - 2 records");
+    }
+    if (total) *total = sum;
+    return ATSC_OK;
+}
+
+// The device call over the plans in[0 .. n_in).  Host work, all of it in the stream's index, which the inputs share
+// (in[k].org: the stream index of plan k's first sample, see reduce_dev; begin[] counts from in[0].org): the covering
+// intervals of the ranges -- a range is decoded whole whatever the stride -- cut into pieces at multiples of AGG_TILE
+// as reduce_dev cuts them; per piece and per input the decode tasks into the input's own region (its spill slots behind
+// it); per range and per piece the run of positions that lie in the piece, cut into tasks of ACR_TASK positions.  A
+// position needs one slot of every region and nothing else, so pieces do not overlap and a position is computed by the
+// piece that holds it.
+// Piece length: the budget (without one, the default of ONE input, whatever n_in is) less the inputs' spills, shared
+// evenly by the n_in regions, a multiple of AGG_TILE and at least AGG_MIN_PIECE.
+// One upload (every input's decode tasks, the tasks, the regions' places in the scratch: they differ in spill slots,
+// so they are a table and not base + k x length); then per piece n_in decodes and one launch of the position kernel.
+// The call's tables and scratch are in[0].dp's (res[Q_ACROSS]).
+static int across_dev(atsc_ctx *ctx, const QueryInput *in, int n_in, uint64_t n_windows, const uint64_t *begin,
+                      const uint64_t *count, uint64_t stride, void *d_out, void *stream)
+{
+    static const char *const CALL = "across_windows";
+    if (!ctx || !in || (n_windows && (!begin || !count))) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    uint64_t total = 0;
+    int rc = across_check(ctx, (uint32_t)n_in, n_windows, count, stride, &total);
+    if (rc) return rc;
+    for (int k = 0; k < n_in; ++k)
+        if (!in[k].dp || !in[k].d_body) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    if (total && !d_out) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    for (int k = 1; k < n_in; ++k)
+        if (in[k].dp->ctx != in[0].dp->ctx) return fail_in(ctx, ATSC_E_INVALID, CALL, "plans of different contexts");
+    const uint64_t org = in[0].org;  // begin[] counts from here
+    for (int k = 0; k < n_in && !rc; ++k)
+        rc = check_windows(ctx, CALL, in[k].dp, d_out, "d_out", n_windows, begin, count, ~0ull, org, in[k].org);
+    if (rc || total == 0) return rc;
+    if (!launch_decompress_window || !launch_window_gather || !launch_across_positions)
+        return fail_in(ctx, ATSC_E_UNSUPPORTED, CALL, "no across kernels");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint64_t T = AGG_TILE, W = n_windows;
+    std::vector<uint64_t> m(W);
+    std::vector<Span> cov;
+    for (uint64_t i = 0; i < W; ++i) {
+        m[i] = atsc_across_outputs(count[i], stride);
+        if (m[i]) cov.emplace_back(org + begin[i], org + begin[i] + count[i]);
+    }
+    merge_spans(cov);
+    // piece length
+    uint64_t spills = 0;
+    bool large = false;
+    for (int k = 0; k < n_in; ++k)
+        if (spans_touch_large(in[k].dp, in[k].org, cov)) {
+            large = true;
+            spills += 2ull * MAX_FRAME;
+        }
+    const uint64_t want = scratch_budget_samples(ctx, large);
+    const uint64_t piece_tiles =
+        std::max<uint64_t>(AGG_MIN_PIECE, want > spills ? (want - spills) / (uint64_t)n_in / T * T : 0) / T;
+    // pieces: tiles [first, second), ascending and disjoint; covered tile ranges closer than AGG_GAP_TILES share a span
+    std::vector<Span> pcs;
+    uint64_t region_tiles = 0;
+    for (size_t a = 0; a < cov.size();) {
+        const uint64_t k0 = cov[a].first / T;
+        uint64_t k1 = (cov[a].second + T - 1) / T;
+        size_t z = a + 1;
+        while (z < cov.size() && cov[z].first / T < k1 + AGG_GAP_TILES) k1 = std::max(k1, (cov[z++].second + T - 1) / T);
+        for (uint64_t k = k0; k < k1; k += piece_tiles) {
+            pcs.emplace_back(k, std::min(k1, k + piece_tiles));
+            region_tiles = std::max(region_tiles, pcs.back().second - k);
+        }
+        a = z;
+    }
+    const size_t P = pcs.size();
+    const uint64_t region = region_tiles * T;
+    // tasks, by piece: per range the runs of positions inside each piece
+    struct PT {
+        uint32_t piece;
+        DevRollTask t;
+    };
+    std::vector<PT> tk;
+    uint64_t rec = 0;
+    for (uint64_t i = 0; i < W; ++i) {
+        if (!m[i]) continue;
+        const uint64_t b = org + begin[i];
+        size_t p = (size_t)(std::upper_bound(pcs.begin(), pcs.end(), b / T, [](uint64_t v, const Span &x) { return v < x.second; }) -
+                            pcs.begin());
+        for (uint64_t j = 0; j < m[i];) {
+            const uint64_t lo = b + j * stride;
+            while (p < P && pcs[p].second * T <= lo) ++p;  // (a stride longer than a piece skips pieces)
+            if (p >= P || pcs[p].first * T > lo)
+                return fail_in(ctx, ATSC_E_INVALID, CALL, "internal error (position outside the pieces)");
+            const uint64_t je = std::min(m[i], (pcs[p].second * T - 1 - b) / stride + 1);  // positions in front of the piece's end
+            for (; j < je; j += ACR_TASK)
+                tk.push_back(PT{(uint32_t)p, DevRollTask{b + j * stride, rec + j, (uint32_t)std::min<uint64_t>(ACR_TASK, je - j), 0}});
+            j = je;
+        }
+        rec += m[i];
+    }
+    auto by_piece = [](const PT &x, const PT &y) { return x.piece < y.piece; };
+    if (P > 1 && !std::is_sorted(tk.begin(), tk.end(), by_piece)) std::stable_sort(tk.begin(), tk.end(), by_piece);
+    std::vector<DevRollTask> tasks;
+    tasks.reserve(tk.size());
+    std::vector<size_t> at(P + 1, 0);
+    for (const PT &x : tk) { tasks.push_back(x.t); ++at[x.piece + 1]; }
+    for (size_t p = 0; p < P; ++p) at[p + 1] += at[p];
+    std::vector<PT>().swap(tk);
+    // decode tasks of every piece, once per input
+    std::vector<DecodeTasks> D(n_in);
+    std::vector<std::vector<PieceDecode>> pdec(n_in, std::vector<PieceDecode>(P));
+    for (int k = 0; k < n_in; ++k) {
+        size_t ci = 0;
+        for (size_t p = 0; p < P; ++p)
+            if (!emit_piece_decode(in[k].dp, in[k].org, cov, ci, pcs[p].first * T, pcs[p].second * T, region, D[k], pdec[k][p]))
+                return fail_in(ctx, ATSC_E_INVALID, CALL, "internal error (spill slots)");
+    }
+    // every input's region and behind it the spill slots it uses; region and MAX_FRAME are even numbers of doubles, so
+    // every region begins at a multiple of 16 bytes, as the position kernel's 16-byte loads need
+    std::vector<uint64_t> reg(n_in);
+    uint64_t scr_n = 0;
+    for (int k = 0; k < n_in; ++k) {
+        reg[k] = scr_n;
+        scr_n += region + (uint64_t)MAX_FRAME * D[k].spills_used;
+    }
+    QueryRes &R = in[0].dp->res[Q_ACROSS];
+    HIPCHK(ctx, R.wait());
+    Upload up;
+    for (int k = 0; k < n_in; ++k) D[k].place(up);
+    const size_t off_tasks = up.add(tasks), off_reg = up.add(reg);
+    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, scr_n));
+    unsigned char *d = R.d;
+    up.stage(R.h);
+    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
+    const DevRollTask *d_tasks = (const DevRollTask *)(d + off_tasks);
+    for (size_t p = 0; p < P; ++p) {
+        for (int k = 0; k < n_in; ++k) {
+            double *scr = R.scratch + reg[k];
+            rc = launch_piece_decode(ctx, in[k].dp, in[k].d_body, d, D[k], pdec[k][p], scr, scr, scr, s, BY_ACROSS);
+            if (rc) return rc;
+        }
+        const hipError_t e = launch_across_positions(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), R.scratch,
+                                                     (const uint64_t *)(d + off_reg), (uint32_t)n_in, pcs[p].first * T, stride,
+                                                     d_out, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_across_positions", e);
+    }
+    HIPCHK(ctx, R.record(s));
+    return ATSC_OK;
+}
+
+// the across' descriptor (see AggQuery): the number of streams is the call's own (INPUTS == 0, inputs()); it and the
+// stride are the call's parameters, and the size of its result follows from the ranges' lengths, as the rolling's does
+struct AcrossQuery {
+    static constexpr int INPUTS = 0;
+    static constexpr const char *CALL = "across_windows";
+    uint32_t n_streams;
+    uint64_t stride;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    int inputs() const { return (int)n_streams; }
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
+        return total * sizeof(atsc_across_record);
+    }
+    int check(atsc_ctx *ctx) const { return across_check(ctx, n_streams, count ? n_ranges : 0, count, stride, nullptr); }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
+    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
+            void *stream) const
+    {
+        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream);
+    }
+};
+
+// what every across call checks of its lists before it reads them
+static bool across_lists(uint32_t n_streams, const void *const *a, const void *const *b)
+{
+    if (n_streams == 0 || n_streams > ATSC_ACROSS_MAX_STREAMS || !a) return false;
+    for (uint32_t k = 0; k < n_streams; ++k)
+        if (!a[k] || (b && !b[k])) return false;
+    return true;
+}
+
+extern "C" int atsc_across_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp, const uint8_t *const *d_body,
+                                       uint64_t n_windows, const uint64_t *begin, const uint64_t *count, uint64_t stride,
+                                       atsc_across_record *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
+        return fail(ctx, ATSC_E_INVALID, "across_windows: n_streams outside [1, 64], a null list or a null entry");
+    QueryInput in[MAX_INPUTS];
+    for (uint32_t k = 0; k < n_streams; ++k) in[k] = QueryInput{dp[k], d_body[k], 0};
+    return AcrossQuery{n_streams, stride, count, n_windows}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    ATSC_API_END
+}
+
+extern "C" int atsc_across_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                                   const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                   uint64_t stride, atsc_across_record *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
+        return fail(ctx, ATSC_E_INVALID, "across_windows: n_streams outside [1, 64], a null list or a null entry");
+    HostBody hb[MAX_INPUTS];
+    for (uint32_t k = 0; k < n_streams; ++k) hb[k] = HostBody{body[k], body_len[k], has_count[k]};
+    return query_host(ctx, hb, n_windows, begin, count, out, AcrossQuery{n_streams, stride, count, n_windows});
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
 // the same queries on a stream under construction (atsc_stream.cpp): its records, then the host call
 // ------------------------------------------------------------------------------------------
 // a stream without a frame holds only empty windows at 0
@@ -2585,23 +2826,24 @@ extern "C" int atsc_stream_decompress_window(atsc_stream *s, uint64_t begin, uin
     ATSC_API_END
 }
 
-// The stream call of a query over the streams st[0 .. Q::INPUTS), which must share a context.  The query's own check
+// The stream call of a query over the streams st[0 .. query_inputs(q)), which must share a context.  The query's own check
 // comes without a context (it has never left a message on the stream's) and before the pending chunks are compressed; a
 // stream without a frame admits only empty windows at 0, and where every stream is one they get the query's empty result.
 template <class Q>
 static int query_stream(atsc_stream *const *st, uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *out,
                         const Q &q)
 {
-    for (int k = 0; k < Q::INPUTS; ++k)
+    const int n_in = query_inputs(q);
+    for (int k = 0; k < n_in; ++k)
         if (!st[k]) return ATSC_E_INVALID;
     if (n_windows && (!begin || !count || !out)) return ATSC_E_INVALID;
     int rc = q.check(nullptr);
     if (rc) return rc;
-    std::vector<uint8_t> body[MAX_INPUTS];
+    std::vector<std::vector<uint8_t>> body(n_in);
     atsc_ctx *ctx[MAX_INPUTS] = {};
     HostBody hb[MAX_INPUTS];
     bool none = false;
-    for (int k = 0; k < Q::INPUTS; ++k) {
+    for (int k = 0; k < n_in; ++k) {
         rc = stream_body(st[k], body[k], &ctx[k]);
         if (rc) return rc;
         if (ctx[k] != ctx[0]) return fail_in(ctx[0], ATSC_E_INVALID, Q::CALL, "streams of different contexts");
@@ -2708,5 +2950,14 @@ extern "C" int atsc_stream_pair_windows(atsc_stream *x, atsc_stream *y, uint64_t
     ATSC_API_BEGIN
     atsc_stream *const st[2] = {x, y};
     return query_stream(st, n_windows, begin, count, out, PairQuery());
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_across_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                          const uint64_t *begin, const uint64_t *count, uint64_t stride, atsc_across_record *out)
+{
+    ATSC_API_BEGIN
+    if (!across_lists(n_streams, (const void *const *)streams, nullptr)) return ATSC_E_INVALID;
+    return query_stream(streams, n_windows, begin, count, out, AcrossQuery{n_streams, stride, count, n_windows});
     ATSC_API_END
 }

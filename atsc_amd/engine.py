@@ -78,6 +78,23 @@ def rolling_offsets(counts, width, stride=1):
     return np.concatenate([[0], np.cumsum([rolling_outputs(v, width, stride) for v in c], dtype=np.uint64)]).astype(np.uint64)
 
 
+# atsc_across_record (include/atsc_hip.h): the record of one position of an across call, 32 bytes
+ACROSS_RECORD = np.dtype([("count", "<u4"), ("min_at", "<u2"), ("max_at", "<u2"), ("min", "<f8"), ("max", "<f8"), ("sum", "<f8")])
+ACROSS_MAX_STREAMS = capi.ACROSS_MAX_STREAMS
+
+
+def across_outputs(count, stride=1):
+    """-> the positions of a range of `count` samples taken every `stride` samples (atsc_across_outputs; no GPU):
+    (count - 1) // stride + 1, or 0 where count or stride is 0"""
+    return int(capi.lib().atsc_across_outputs(int(count), int(stride)))
+
+
+def across_offsets(counts, stride=1):
+    """-> uint64 array of len(counts) + 1 offsets: the records of range i of an across call are [off[i], off[i + 1])"""
+    c = np.atleast_1d(np.asarray(counts, dtype=np.uint64))
+    return np.concatenate([[0], np.cumsum([across_outputs(v, stride) for v in c], dtype=np.uint64)]).astype(np.uint64)
+
+
 def select_bytes(n_windows, cap):
     """-> bytes of the block of a select call (ATSC_SELECT_BYTES): n_windows + 1 offsets, then cap entries"""
     return 8 * (int(n_windows) + 1) + 16 * int(cap)
@@ -125,7 +142,8 @@ def _levels(levels):
 #   block   None, or for a result that is one block whose size is not a number of records (the select's offsets and
 #           entries): (n_windows, cargs) -> its bytes; the result is then that many bytes as uint64 words, whole
 #   inputs  the streams the query reads, 1 or 2: each surface takes that many records, (plan, device bytes) or streams,
-#           the first as its own and the others through `others`, in front of the windows in the C call
+#           the first as its own and the others through `others`, in front of the windows in the C call.  None: the
+#           number is the call's own (the across), and the C call takes it and the streams as lists (_across_*)
 _Query = collections.namedtuple("_Query", "stem dtype extra params block inputs", defaults=(None, 1))
 
 
@@ -185,7 +203,7 @@ def _select_result(run, n, cap):
 
 
 class _RollArgs(tuple):
-    """the C arguments of a rolling call, and the records of its ranges"""
+    """the C arguments of a rolling or an across call, and the records of its ranges"""
     records = 0
 
 
@@ -209,6 +227,26 @@ def _rolling_result(run, counts, width, stride):
     return run(int(off[-1])).view(WINDOW_ROLLING), off
 
 
+def _across_params(stride, records):
+    stride = int(stride)
+    if not 0 <= stride < 2 ** 64:
+        raise ValueError("stride outside uint64")
+    a = _RollArgs((C.c_uint64(stride),))
+    a.records = int(records)
+    return a
+
+
+def _across_block(n, cargs):
+    return ACROSS_RECORD.itemsize * cargs.records
+
+
+def _across_result(run, counts, stride):
+    """run(records) -> the block of an across call as uint64 words.  -> (records, off): the ACROSS_RECORD records of
+    every position, range after range, and the ranges' record offsets (across_offsets)"""
+    off = across_offsets(counts, stride)
+    return run(int(off[-1])).view(ACROSS_RECORD), off
+
+
 def _array_params(values, flag):
     """levels and method, or edges and closed"""
     a, pa = _levels(values)
@@ -224,6 +262,7 @@ _EXTREMES = _Query("extremes_windows", _extremes_dtype, None, _extremes_params)
 _VALUES = _Query("values_windows", _values_dtype, None, _values_params)
 _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _select_block)
 _ROLLING = _Query("rolling_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_block)
+_ACROSS = _Query("across_windows", np.dtype(np.uint64), None, _across_params, _across_block, inputs=None)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
 _HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
 
@@ -291,6 +330,39 @@ def _query_dev(q, dplan, d_body, begins, counts, d_out, stream, *params, others=
     rc = getattr(capi.lib(), "atsc_%s_dev" % q.stem)(dplan.ctx._h, *plans, len(b), pb, pc,
                                                      *cargs, C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
     capi.check(rc, dplan.ctx._h)
+
+
+def _across_list(pointers):
+    """a C array of pointers, as the across calls take their streams"""
+    return (C.c_void_p * max(len(pointers), 1))(*pointers)
+
+
+def _across_host(ctx, records_list, begins, counts, has_count, stride, records):
+    """atsc_across_windows over the records of every stream of the list (has_count: one flag for all of them)"""
+    arrays = [np.frombuffer(bytes(r), dtype=np.uint8) for r in records_list]
+    lens, plens = _u64(np.array([len(b) for b in arrays], dtype=np.uint64))
+    flags = np.full(max(len(arrays), 1), int(has_count), dtype=np.int32)
+    wb, pb, wc, pc = _windows(begins, counts)
+    cargs = _ACROSS.params(stride, records)
+    fn = capi.lib().atsc_across_windows
+    out, po = _query_result(_ACROSS, len(wb), cargs, fn)
+    rc = fn(ctx._h, len(arrays), _across_list([b.ctypes.data for b in arrays]), plens,
+            flags.ctypes.data_as(C.POINTER(C.c_int32)), len(wb), pb, pc, *cargs, po)
+    capi.check(rc, ctx._h)
+    return _query_rows(_ACROSS, out, len(wb))
+
+
+def _across_dev(plans, bodies, begins, counts, d_out, stream, stride, records):
+    """atsc_across_windows_dev over the plans and their device bytes into the device tensor d_out"""
+    b, pb, c, pc = _windows(begins, counts)
+    cargs = _ACROSS.params(stride, records)
+    assert len(plans) == len(bodies) and d_out.is_contiguous()
+    assert d_out.numel() * d_out.element_size() >= _query_bytes(_ACROSS, len(b), cargs, ())
+    ctx = plans[0].ctx
+    rc = capi.lib().atsc_across_windows_dev(ctx._h, len(plans), _across_list([p._h.value for p in plans]),
+                                            _across_list([t.data_ptr() for t in bodies]), len(b), pb, pc, *cargs,
+                                            C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
+    capi.check(rc, ctx._h)
 
 
 def histogram_edges_uniform(lo, hi, n_bins):
@@ -526,6 +598,14 @@ class Context:
         return _rolling_result(lambda m: _query_host(_ROLLING, self, records, begins, counts, has_count, width, stride, m),
                                counts, width, stride)
 
+    def across_windows_host(self, records_list, begins, counts, stride=1, has_count=False):
+        """-> (records, off): count / min / max / sum over the streams of records_list (at most ACROSS_MAX_STREAMS
+        decoded record streams, sample j of one going with sample j of every other) at every `stride`-th position of
+        every range [begins[i], begins[i] + counts[i]) (atsc_across_windows).  records: an ACROSS_RECORD array, range
+        after range, min_at / max_at the index in records_list of the stream that holds the extreme; off: len(begins)
+        + 1 offsets, range i's records being records[off[i]:off[i + 1]].  has_count holds for every stream"""
+        return _across_result(lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m), counts, stride)
+
     def extremes_windows_host(self, records, begins, counts, k, has_count=False):
         """-> array of window_extremes_dtype(k): the k largest and the k smallest non-NaN samples, each with its offset
         in the window, the number of NaN samples and the length of every window [begins[i], begins[i] + counts[i]) of
@@ -706,6 +786,16 @@ class DPlan:
         (rolling_offsets)"""
         off = rolling_offsets(counts, width, stride)
         _query_dev(_ROLLING, self, d_body, begins, counts, d_out, stream, width, stride, int(off[-1]))
+        return off
+
+    def across_windows(self, d_body, others, other_bodies, begins, counts, d_out, stride=1, stream=0):
+        """Enqueues count / min / max / sum over this plan's stream (stream 0) and the plans `others` (their device
+        bytes other_bodies; stream 1 and on, in that order) at every `stride`-th position of the ranges [begins[i],
+        begins[i] + counts[i]) into d_out, a device tensor of at least 32 bytes per position
+        (atsc_across_windows_dev; ACROSS_RECORD records, range after range).  A plan may appear more than once.  -> the
+        ranges' record offsets (across_offsets)"""
+        off = across_offsets(counts, stride)
+        _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, int(off[-1]))
         return off
 
     def extremes_windows(self, d_body, begins, counts, k, d_out, stream=0):

@@ -8,6 +8,7 @@ import numpy as np
 from . import capi
 from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_ROLLING, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit, pair_fit  # noqa: F401
 from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
+from .engine import ACROSS_RECORD, _ACROSS, _across_host, _across_list, _across_result  # noqa: F401
 
 
 def _f64(x):
@@ -151,6 +152,22 @@ class CompressedStream:
         begins[i] + counts[i]), as Context.rolling_windows_host gives them (atsc_stream_rolling_windows)"""
         return _rolling_result(lambda m: _query_stream(_ROLLING, self, begins, counts, width, stride, m), counts, width, stride)
 
+    def across_windows(self, others, begins, counts, stride=1):
+        """-> (records, off) over this stream (stream 0) and the streams `others` (stream 1 and on) at every
+        `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as Context.across_windows_host gives
+        them (atsc_stream_across_windows)"""
+        streams = [self] + list(others)
+
+        def run(m):
+            wb, pb, wc, pc = _windows(begins, counts)
+            cargs = _ACROSS.params(stride, m)
+            fn = capi.lib().atsc_stream_across_windows
+            out, po = _query_result(_ACROSS, len(wb), cargs, fn)
+            capi.check(fn(_across_list([s._h.value for s in streams]), len(streams), len(wb), pb, pc, *cargs, po), self.ctx._h)
+            return _query_rows(_ACROSS, out, len(wb))
+
+        return _across_result(run, counts, stride)
+
     def extremes_windows(self, begins, counts, k):
         """-> array of window_extremes_dtype(k) of the windows [begins[i], begins[i] + counts[i]): their k largest and k
         smallest samples and where they are (atsc_stream_extremes_windows)"""
@@ -241,6 +258,17 @@ def rolling_data_windows(ctx, bro, begins, counts, width, stride=1):
     decompress_data(ctx, bro), as Context.rolling_windows_host gives them: atsc_bro_open, then atsc_rolling_windows over
     the records"""
     return _rolling_result(lambda m: _query_image(_ROLLING, ctx, bro, begins, counts, width, stride, m), counts, width, stride)
+
+
+def across_data_windows(ctx, bros, begins, counts, stride=1):
+    """-> (records, off) over the streams decompress_data(ctx, bro) of every .bro image of the list `bros` at every
+    `stride`-th position of the ranges, as Context.across_windows_host gives them: atsc_bro_open of each image, then
+    atsc_across_windows over their records"""
+    images = [np.frombuffer(bytes(b), dtype=np.uint8) for b in bros]
+    for b in images:
+        capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
+    # the records from the frame-count varint (offset 9) on, as atsc_decompress_data reads them
+    return _across_result(lambda m: _across_host(ctx, [b[9:] for b in images], begins, counts, True, stride, m), counts, stride)
 
 
 def extremes_data_windows(ctx, bro, begins, counts, k):

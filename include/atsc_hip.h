@@ -807,6 +807,60 @@ int atsc_rolling_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, 
                          const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
                          atsc_window_rolling *out);
 
+/* Windowed across: count, min, max and sum over N streams at every position of ranges of the decoded streams (the
+ * indices of atsc_decompress_frames): one value per sample index folded across many series -- `sum by (job)(x)`,
+ * `max by (zone)(x)`, how many replicas report at this instant and which one is the worst -- without the decoded
+ * samples leaving the library.  The streams may differ in framing, codecs and tiers.
+ *   Ranges     Range i is [begin[i], begin[i] + count[i]), counted in every stream's own decoded index: sample j of
+ *              stream 0 goes with sample j of every other stream, as in the pair moments.  One stride s >= 1 holds for
+ *              a call.  Range i has m_i = count[i] && s ? (count[i] - 1) / s + 1 : 0 positions (atsc_across_outputs);
+ *              position p is sample begin[i] + p s.  Records are stored range after range, as the rolling's are:
+ *              record m_0 + .. + m_(i-1) + p is position p of range i.  Ranges may overlap, come in any order and be
+ *              empty; n_windows == 0 is valid.
+ *   Record     over x_k = the sample of stream k at the position, k = 0 .. N - 1 in the order of the call's list:
+ *              count   the number of k with x_k not NaN;
+ *              min, min_at   walk k upward: the first x_k that is not NaN starts the minimum, a later one replaces it
+ *                      iff x_k < min.  Of equal values, and of zeros of either sign, the lowest k is kept; min is
+ *                      stream min_at's sample bit for bit;
+ *              max, max_at   the same rule with >;
+ *              sum     ((t_0 + t_1) + t_2) + .. with t_k = x_k, or -0.0 where x_k is NaN: every operation one
+ *                      correctly rounded f64 add, in list order, never fused or reassociated; forced to +0.0 when
+ *                      count == 0.  +-Inf give what IEEE gives (where that is NaN, any NaN conforms).  The sum depends
+ *                      only on the N samples and the order of the list: not on the range, the stride, the budget, the
+ *                      piece boundaries, the framing or the device.
+ *              No other arithmetic touches a sample: every field is bit-exact.
+ *   Stride     a range is decoded whole whatever the stride: a stride does not skip frames, it thins the records.
+ * Errors: ATSC_E_INVALID with nothing written and before any GPU work for n_streams == 0 or n_streams >
+ * ATSC_ACROSS_MAX_STREAMS, a null list or a null entry in a list, stride == 0, more than 2^32 - 2 records in all, a
+ * range beyond the end of ANY of the streams, and plans or streams of different contexts.  The same plan, body or stream
+ * may appear more than once in the list.  Payloads are checked only of the frames (of any stream) that a range touches.
+ * Every stream is decoded piece by piece into a scratch region of its own; the budget of atsc_ctx_set_aggregate_scratch
+ * is shared evenly by the N regions (each raised to one piece's minimum, 65536 samples, and two large frames' room where
+ * the stream has large frames); without a budget the call's total is the default of ONE stream shared by the N regions.
+ * A position needs one slot per stream, so pieces do not overlap; there is no ATSC_E_CAPACITY case. */
+#define ATSC_ACROSS_MAX_STREAMS 64
+typedef struct {
+    uint32_t count;          /* streams whose sample at this position is not NaN */
+    uint16_t min_at, max_at; /* index (into the call's stream list) of the stream that holds min / max; 0xFFFF when count == 0 */
+    double min, max;         /* NaN when count == 0 */
+    double sum;              /* +0.0 when count == 0 */
+} atsc_across_record;        /* 32 bytes */
+/* Positions of a range of `count` samples (host only, no GPU): count && stride ? (count - 1) / stride + 1 : 0. */
+uint64_t atsc_across_outputs(uint64_t count, uint64_t stride);
+/* dp / d_body (n_streams entries each) and begin / count are HOST arrays; d_body[k] and d_out are device memory (d_out
+ * 8-byte aligned, 32 bytes per record).  Enqueued on `stream`, not synchronised.  A malformed payload in a frame of
+ * stream k that a range touches sets dp[k]'s status word.  dp[0] keeps the call's tables and scratch: the next across
+ * call whose first plan is dp[0] waits (host side) until this one's work is done; atsc_dplan_destroy frees them. */
+int atsc_across_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp, const uint8_t *const *d_body,
+                            uint64_t n_windows, const uint64_t *begin, const uint64_t *count, uint64_t stride,
+                            atsc_across_record *d_out, void *stream);
+/* Host bytes in (n_streams bodies, lengths and has_count flags), host records out, synchronous; walks and uploads only
+ * the touched records of every stream, as atsc_aggregate_windows does, and computes the device call's bits.
+ * ATSC_E_FORMAT (nothing written) for a malformed payload in a frame of any stream that a range touches. */
+int atsc_across_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                        const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                        uint64_t stride, atsc_across_record *out);
+
 /* Windowed quantiles: exact order statistics of windows [begin, begin + count) of the decoded stream (the indices of
  * atsc_decompress_frames), from the same decoded samples as the window decode.  For window i:
  *   x  the window's non-NaN samples, n of them, sorted in IEEE total order (-0.0 before +0.0), i.e. by the keys
@@ -931,6 +985,10 @@ int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64
 /* atsc_pair_windows over the frames of the streams x and y, which must belong to one context (else ATSC_E_INVALID) */
 int atsc_stream_pair_windows(atsc_stream *x, atsc_stream *y, uint64_t n_windows, const uint64_t *begin,
                              const uint64_t *count, atsc_window_pair *out);
+/* atsc_across_windows over the frames of the n_streams streams of the list, which must belong to one context (else
+ * ATSC_E_INVALID) */
+int atsc_stream_across_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows, const uint64_t *begin,
+                               const uint64_t *count, uint64_t stride, atsc_across_record *out);
 /* atsc_quantile_windows over the stream's frames */
 int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint32_t n_q, const double *q, int method, double *out);
