@@ -4,7 +4,8 @@
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
-//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S]] [--across A.bro,B.bro,.. [--across-stride S]]]
+//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S]]
+//        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -87,6 +88,10 @@ void usage()
             "                                 (the first of equal ones), sum in list order; min_at, max_at and mean (sum / count)\n"
             "                                 empty where count is 0.  Every file must reach the window's end\n"
             "      --across-stride <S>        with --across: every S-th sample of the window only [default: 1]\n"
+            "      --across-quantiles <Q,Q,..> with --across: also the levels Q (0..1, at most 64) of the streams' samples at\n"
+            "                                 every row's sample index, NaN samples left out: one column q<Q> per level\n"
+            "                                 behind mean, NaN where every stream's sample is NaN\n"
+            "      --across-quantile-method <M>  linear | lower | higher | nearest [default: linear]\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -181,11 +186,13 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
         }
         if (!a.q.across.empty()) {  // (with --samples) the window's across records over this file and the listed ones, no .wbro
             std::vector<atsc_across_record> rows;
+            std::vector<double> levels;
             rc = atsc_bro_open(bro, len, nullptr, nullptr);
-            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows);
+            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, levels);
             atsc_free(bro);
             if (rc) return rc;
-            return across_write(with_ext(path, "across.csv"), rows, a.q.across_stride) ? ATSC_OK : ATSC_E_IO;
+            const bool ok = across_write(with_ext(path, "across.csv"), rows, a.q.across_stride, a.q.across_level_names, levels);
+            return ok ? ATSC_OK : ATSC_E_IO;
         }
         double *out = nullptr;
         uint64_t n = 0;

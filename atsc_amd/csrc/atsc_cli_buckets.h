@@ -78,6 +78,10 @@ struct BucketOptions {
     std::vector<std::string> across;  // --across A.bro,B.bro,..: no bucket query; the window's across records into .across.csv
     uint64_t across_stride = 1;       // --across-stride S
     bool have_across_stride = false;
+    std::vector<double> across_levels;  // --across-quantiles Q,Q,..: one column per level behind .across.csv's own
+    std::vector<std::string> across_level_names;
+    int across_method = ATSC_QUANTILE_LINEAR;  // --across-quantile-method
+    bool have_across_method = false;
 };
 
 // --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
@@ -296,6 +300,23 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             return 2;
         }
         o.have_across_stride = true;
+    } else if (o.across_allowed && value("--across-quantiles")) {
+        if (!parse_levels(v, o.across_levels, o.across_level_names)) {
+            fprintf(stderr, "error: invalid value '%s' for '--across-quantiles': expected levels in 0..=1, comma separated\n",
+                    v.c_str());
+            return 2;
+        }
+        if (o.across_levels.size() > 64) {
+            fprintf(stderr, "error: invalid value for '--across-quantiles': %zu levels, at most 64\n", o.across_levels.size());
+            return 2;
+        }
+    } else if (o.across_allowed && value("--across-quantile-method")) {
+        if (!parse_method(v, o.across_method)) {
+            fprintf(stderr, "error: invalid value '%s' for '--across-quantile-method': linear, lower, higher or nearest\n",
+                    v.c_str());
+            return 2;
+        }
+        o.have_across_method = true;
     } else {
         return 0;
     }
@@ -360,12 +381,18 @@ bool rolling_option_complete(const BucketOptions &o, const char *window, bool wi
 }
 
 // --across goes with the option that names the window and without the one that cuts buckets, --rolling and --where;
-// --across-stride goes with --across.  false: a usage error, reported on stderr.
+// --across-stride and --across-quantiles go with --across, --across-quantile-method with --across-quantiles.  false: a
+// usage error, reported on stderr.
 bool across_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
 {
+    if (o.have_across_method && o.across_levels.empty()) {
+        fprintf(stderr, "error: '--across-quantile-method' needs '--across-quantiles'\n");
+        return false;
+    }
     if (o.across.empty()) {
         if (o.have_across_stride) fprintf(stderr, "error: '--across-stride' needs '--across'\n");
-        return !o.have_across_stride;
+        else if (!o.across_levels.empty()) fprintf(stderr, "error: '--across-quantiles' needs '--across'\n");
+        return !o.have_across_stride && o.across_levels.empty();
     }
     if (!windowed) {
         fprintf(stderr, "error: '--across' needs '%s'\n", window);
@@ -619,9 +646,10 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
 }
 
 // --across: one record per position of the range [begin, begin + count) over the .bro image (stream 0) and the listed
-// files (stream 1 and on): sample i of each goes with sample i of the others
+// files (stream 1 and on): sample i of each goes with sample i of the others.  levels: with --across-quantiles, the
+// same positions' rows of o.across_levels.size() levels
 int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
-                 std::vector<atsc_across_record> &rows)
+                 std::vector<atsc_across_record> &rows, std::vector<double> &levels)
 {
     std::vector<uint8_t *> image(o.across.size(), nullptr);
     std::vector<const uint8_t *> body{bro + 9};
@@ -642,6 +670,14 @@ int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOp
         atsc_across_record none;
         rc = atsc_across_windows(ctx, (uint32_t)body.size(), body.data(), body_len.data(), has_count.data(), 1, &begin, &count,
                                  o.across_stride, rows.empty() ? &none : rows.data());
+        if (!rc && !o.across_levels.empty()) {
+            const uint32_t n_q = (uint32_t)o.across_levels.size();
+            levels.assign(rows.size() * n_q, 0.0);
+            double no_row;
+            rc = atsc_across_quantile_windows(ctx, (uint32_t)body.size(), body.data(), body_len.data(), has_count.data(), 1, &begin,
+                                              &count, o.across_stride, n_q, o.across_levels.data(), o.across_method,
+                                              levels.empty() ? &no_row : levels.data());
+        }
     }
     for (uint8_t *p : image) atsc_free(p);
     return rc;
@@ -649,18 +685,24 @@ int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOp
 
 // the .across.csv: offset,count,min,min_at,max,max_at,sum,mean and one row per position; offset: the position's sample
 // counted from the window's begin; values as the .agg.csv writes them; min_at and max_at (the stream's place in the
-// list, the input file 0) and mean = sum / count empty where count == 0.  false: the file could not be written.
-bool across_write(const std::string &path, const std::vector<atsc_across_record> &rows, uint64_t stride)
+// list, the input file 0) and mean = sum / count empty where count == 0.  names: with --across-quantiles, a column
+// q<level as typed> per level behind them, from the position's row of `levels`.  false: the file could not be written.
+bool across_write(const std::string &path, const std::vector<atsc_across_record> &rows, uint64_t stride,
+                  const std::vector<std::string> &names, const std::vector<double> &levels)
 {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return false;
-    fprintf(f, "offset,count,min,min_at,max,max_at,sum,mean\n");
+    fprintf(f, "offset,count,min,min_at,max,max_at,sum,mean");
+    for (const std::string &n : names) fprintf(f, ",q%s", n.c_str());
+    fprintf(f, "\n");
     for (size_t j = 0; j < rows.size(); ++j) {
         const atsc_across_record &r = rows[j];
         const std::string mn_at = r.count ? std::to_string(r.min_at) : std::string(), mx_at = r.count ? std::to_string(r.max_at) : std::string();
-        fprintf(f, "%llu,%u,%s,%s,%s,%s,%s,%s\n", (unsigned long long)(j * stride), r.count, debug_f64(r.min).c_str(), mn_at.c_str(),
+        fprintf(f, "%llu,%u,%s,%s,%s,%s,%s,%s", (unsigned long long)(j * stride), r.count, debug_f64(r.min).c_str(), mn_at.c_str(),
                 debug_f64(r.max).c_str(), mx_at.c_str(), debug_f64(r.sum).c_str(),
                 r.count ? debug_f64(r.sum / (double)r.count).c_str() : "");
+        for (size_t q = 0; q < names.size(); ++q) fprintf(f, ",%s", debug_f64(levels[j * names.size() + q]).c_str());
+        fprintf(f, "\n");
     }
     return fclose(f) == 0;
 }

@@ -3,7 +3,7 @@
 //
 // The contract (include/atsc_hip.h, DESIGN.md "Windowed quantiles"): a window's non-NaN samples x[0..n) sorted by the
 // total-order key below (-0.0 before +0.0); for level q, v = (double)(n - 1) * q, the ranks and the interpolation of
-// q_pick / q_interp.  Every tier reads its ranks and values through those two functions.
+// q_pick / q_interp (atsc_quantile_rule.h).  Every tier reads its ranks and values through those two functions.
 //   short  (n <= QNT_SHORT_MAX)   one wavefront per window: up to 4 keys per lane, bitonic sort across the wave
 //                                 with __shfl_xor, every level's samples fetched by lane shuffle
 //   medium (n <= QNT_MEDIUM_MAX)  one workgroup per window: the keys bitonic-sorted in LDS
@@ -16,59 +16,13 @@
 #include <stdint.h>
 
 #include "atsc_device.h"
+#include "atsc_quantile_rule.h"
 
 namespace atsc {
 
 namespace {
 
-constexpr uint64_t KEY_NAN = ~0ull;   // NaN sorts above every key and is not counted
 constexpr uint32_t QNT_LDS_ROWS = 32; // k_qnt_hist counts in LDS up to this many live prefixes, in global memory beyond
-
-// IEEE total order as an unsigned key: negative values reversed below the positive ones
-__device__ __forceinline__ uint64_t q_key(double v)
-{
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double q_unkey(uint64_t k)
-{
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-// the rank rule: level q of n >= 1 sorted samples reads x[lo] and x[hi] and interpolates at t
-struct QPick {
-    uint64_t lo, hi;
-    double t;
-};
-
-__device__ __forceinline__ QPick q_pick(uint64_t n, double q, int method)
-{
-    const double v = (double)(n - 1) * q;
-    const double f = __builtin_floor(v);
-    QPick p;
-    p.t = 0.0;
-    if (method == ATSC_QUANTILE_LOWER) {
-        p.lo = p.hi = (uint64_t)f;
-    } else if (method == ATSC_QUANTILE_HIGHER) {
-        p.lo = p.hi = (uint64_t)__builtin_ceil(v);
-    } else if (method == ATSC_QUANTILE_NEAREST) {
-        p.lo = p.hi = (uint64_t)__builtin_rint(v);  // ties to even, as numpy.around
-    } else {
-        p.lo = (uint64_t)f;
-        p.hi = p.lo + 1 < n ? p.lo + 1 : n - 1;
-        p.t = v - f;
-    }
-    return p;
-}
-
-// NumPy's _lerp without contraction (the library is built with -ffp-contract=off)
-__device__ __forceinline__ double q_interp(const QPick &p, double a, double b)
-{
-    if (p.t == 0.0 || p.lo == p.hi) return a;
-    const double d = b - a;
-    return p.t >= 0.5 ? b - d * (1.0 - p.t) : a + d * p.t;
-}
 
 // ---- short tier ---------------------------------------------------------------------------------------------------
 // K keys per lane; element e = lane * K + r lives in v[r]

@@ -1,6 +1,6 @@
 // atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms,
 // rolling windows and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
-// and count, min, max and sum across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
+// and count, min, max, sum and quantiles across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <numeric>
 #include <type_traits>
@@ -97,6 +98,11 @@ __attribute__((weak)) hipError_t launch_roll_positions(const DevRollTask *tasks,
 __attribute__((weak)) hipError_t launch_across_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                          const uint64_t *reg, uint32_t n_streams, uint64_t a0,
                                                          uint64_t stride, void *out, hipStream_t s);
+// the windowed across quantiles' position kernel (atsc_across_quantile.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_across_quantile_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
+                                                                  const uint64_t *reg, uint32_t n_streams, uint64_t a0,
+                                                                  uint64_t stride, const double *q, uint32_t n_q, int method,
+                                                                  double *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -302,7 +308,8 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs"),
                           BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
                           BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
-                          BY_ROLLING = DECODE_CALLER("rolling"), BY_ACROSS = DECODE_CALLER("across");
+                          BY_ROLLING = DECODE_CALLER("rolling"), BY_ACROSS = DECODE_CALLER("across"),
+                          BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -1742,14 +1749,14 @@ extern "C" int atsc_values_mode(const void *records, uint64_t n, uint32_t k, ats
 // windowed quantiles: exact order statistics of sample windows (atsc_quantile.hip)
 // ------------------------------------------------------------------------------------------
 // ctx may be null: then no message is kept
-static int quantile_check_levels(atsc_ctx *ctx, uint32_t n_q, const double *q, int method)
+// (the levels and the method of the windowed quantiles and of the across quantiles; `call` names the caller in the message)
+static int quantile_check_levels(atsc_ctx *ctx, const char *call, uint32_t n_q, const double *q, int method)
 {
-    if (!q) return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
-    if (n_q == 0 || n_q > QNT_MAX_LEVELS) return fail(ctx, ATSC_E_INVALID, "quantile_windows: n_q outside [1, 64]");
+    if (!q) return fail_in(ctx, ATSC_E_INVALID, call, "null argument");
+    if (n_q == 0 || n_q > QNT_MAX_LEVELS) return fail_in(ctx, ATSC_E_INVALID, call, "n_q outside [1, 64]");
     for (uint32_t j = 0; j < n_q; ++j)
-        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(ctx, ATSC_E_INVALID, "quantile_windows: a level is NaN or outside [0, 1]");
-    if (method < ATSC_QUANTILE_LINEAR || method > ATSC_QUANTILE_NEAREST)
-        return fail(ctx, ATSC_E_INVALID, "quantile_windows: unknown method");
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail_in(ctx, ATSC_E_INVALID, call, "a level is NaN or outside [0, 1]");
+    if (method < ATSC_QUANTILE_LINEAR || method > ATSC_QUANTILE_NEAREST) return fail_in(ctx, ATSC_E_INVALID, call, "unknown method");
     return ATSC_OK;
 }
 
@@ -1765,7 +1772,7 @@ static int quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bo
 {
     if (!ctx || !dp || (n_windows && (!d_body || !begin || !count || !d_out)))
         return fail(ctx, ATSC_E_INVALID, "quantile_windows: null argument");
-    int rc = quantile_check_levels(ctx, n_q, q, method);
+    int rc = quantile_check_levels(ctx, "quantile_windows", n_q, q, method);
     if (rc) return rc;
     rc = check_windows(ctx, "quantile_windows", dp, d_out, "d_out", n_windows, begin, count, 0xfffffffeull);
     if (rc || n_windows == 0) return rc;
@@ -1939,7 +1946,7 @@ struct QntQuery {
     const double *q;
     int method;
     size_t out_bytes(uint64_t n) const { return n * n_q * sizeof(double); }
-    int check(atsc_ctx *ctx) const { return quantile_check_levels(ctx, n_q, q, method); }
+    int check(atsc_ctx *ctx) const { return quantile_check_levels(ctx, CALL, n_q, q, method); }
     void fill_empty(void *out, uint64_t n) const
     {
         for (uint64_t i = 0; i < n * n_q; ++i) ((double *)out)[i] = std::numeric_limits<double>::quiet_NaN();
@@ -2568,21 +2575,40 @@ extern "C" uint64_t atsc_across_outputs(uint64_t count, uint64_t stride)
     return count && stride ? (count - 1) / stride + 1 : 0;
 }
 
-// The check of the call's parameters and the records of its ranges (ctx may be null: then no message is kept).
-static int across_check(atsc_ctx *ctx, uint32_t n_streams, uint64_t n, const uint64_t *count, uint64_t stride, uint64_t *total)
+// The check of the call's parameters and the records of its ranges (ctx may be null: then no message is kept); `call`
+// names the caller in the message.
+static int across_check(atsc_ctx *ctx, const char *call, uint32_t n_streams, uint64_t n, const uint64_t *count, uint64_t stride,
+                        uint64_t *total)
 {
-    if (n_streams == 0 || n_streams > ATSC_ACROSS_MAX_STREAMS)
-        return fail(ctx, ATSC_E_INVALID, "across_windows: n_streams outside [1, 64]");
-    if (stride == 0) return fail(ctx, ATSC_E_INVALID, "across_windows: stride is 0");
+    if (n_streams == 0 || n_streams > ATSC_ACROSS_MAX_STREAMS) return fail_in(ctx, ATSC_E_INVALID, call, "n_streams outside [1, 64]");
+    if (stride == 0) return fail_in(ctx, ATSC_E_INVALID, call, "stride is 0");
     uint64_t sum = 0;
     for (uint64_t i = 0; i < n; ++i) {
         const uint64_t m = atsc_across_outputs(count[i], stride);
         if (m > 0xfffffffeull || (sum += m) > 0xfffffffeull)
-            return fail(ctx, ATSC_E_INVALID, "across_windows: more than 2^32 - 2 records");
+            return fail_in(ctx, ATSC_E_INVALID, call, "more than 2^32 - 2 records");
     }
     if (total) *total = sum;
     return ATSC_OK;
 }
+
+// What differs between the device calls that work on the N samples of a position (across_dev): the across and the
+// across quantiles.
+struct AcrossKernel {
+    const char *call;          // names the call in the messages
+    const char *no_kernels;    // ATSC_E_UNSUPPORTED's message
+    const char *launch_name;   // ATSC_E_HIP's message
+    QueryKind kind;            // whose tables and scratch of in[0].dp
+    const DecodeCaller &who;
+    bool present;              // the position kernel is linked in
+    const void *table;         // table_bytes more bytes of the upload (8-byte aligned), handed to launch() on the device
+    size_t table_bytes;
+    // the position kernel over one piece's tasks: slot 0 of every region is sample a0; records from d_out on, whose size
+    // is the kernel's own business (the tasks number records, not bytes)
+    std::function<hipError_t(const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
+                             const void *d_table, void *d_out, hipStream_t s)>
+        launch;
+};
 
 // The device call over the plans in[0 .. n_in).  Host work, all of it in the stream's index, which the inputs share
 // (in[k].org: the stream index of plan k's first sample, see reduce_dev; begin[] counts from in[0].org): the covering
@@ -2595,14 +2621,14 @@ static int across_check(atsc_ctx *ctx, uint32_t n_streams, uint64_t n, const uin
 // evenly by the n_in regions, a multiple of AGG_TILE and at least AGG_MIN_PIECE.
 // One upload (every input's decode tasks, the tasks, the regions' places in the scratch: they differ in spill slots,
 // so they are a table and not base + k x length); then per piece n_in decodes and one launch of the position kernel.
-// The call's tables and scratch are in[0].dp's (res[Q_ACROSS]).
+// The call's tables and scratch are in[0].dp's (res[K.kind]); K's table goes up with the others.
 static int across_dev(atsc_ctx *ctx, const QueryInput *in, int n_in, uint64_t n_windows, const uint64_t *begin,
-                      const uint64_t *count, uint64_t stride, void *d_out, void *stream)
+                      const uint64_t *count, uint64_t stride, void *d_out, void *stream, const AcrossKernel &K)
 {
-    static const char *const CALL = "across_windows";
+    const char *const CALL = K.call;
     if (!ctx || !in || (n_windows && (!begin || !count))) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
     uint64_t total = 0;
-    int rc = across_check(ctx, (uint32_t)n_in, n_windows, count, stride, &total);
+    int rc = across_check(ctx, CALL, (uint32_t)n_in, n_windows, count, stride, &total);
     if (rc) return rc;
     for (int k = 0; k < n_in; ++k)
         if (!in[k].dp || !in[k].d_body) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
@@ -2613,8 +2639,8 @@ static int across_dev(atsc_ctx *ctx, const QueryInput *in, int n_in, uint64_t n_
     for (int k = 0; k < n_in && !rc; ++k)
         rc = check_windows(ctx, CALL, in[k].dp, d_out, "d_out", n_windows, begin, count, ~0ull, org, in[k].org);
     if (rc || total == 0) return rc;
-    if (!launch_decompress_window || !launch_window_gather || !launch_across_positions)
-        return fail_in(ctx, ATSC_E_UNSUPPORTED, CALL, "no across kernels");
+    if (!launch_decompress_window || !launch_window_gather || !K.present)
+        return fail_in(ctx, ATSC_E_UNSUPPORTED, CALL, K.no_kernels);
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const uint64_t T = AGG_TILE, W = n_windows;
@@ -2701,11 +2727,12 @@ static int across_dev(atsc_ctx *ctx, const QueryInput *in, int n_in, uint64_t n_
         reg[k] = scr_n;
         scr_n += region + (uint64_t)MAX_FRAME * D[k].spills_used;
     }
-    QueryRes &R = in[0].dp->res[Q_ACROSS];
+    QueryRes &R = in[0].dp->res[K.kind];
     HIPCHK(ctx, R.wait());
     Upload up;
     for (int k = 0; k < n_in; ++k) D[k].place(up);
     const size_t off_tasks = up.add(tasks), off_reg = up.add(reg);
+    const size_t off_table = K.table_bytes ? up.add(K.table, K.table_bytes) : 0;
     HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, scr_n));
     unsigned char *d = R.d;
     up.stage(R.h);
@@ -2714,13 +2741,12 @@ static int across_dev(atsc_ctx *ctx, const QueryInput *in, int n_in, uint64_t n_
     for (size_t p = 0; p < P; ++p) {
         for (int k = 0; k < n_in; ++k) {
             double *scr = R.scratch + reg[k];
-            rc = launch_piece_decode(ctx, in[k].dp, in[k].d_body, d, D[k], pdec[k][p], scr, scr, scr, s, BY_ACROSS);
+            rc = launch_piece_decode(ctx, in[k].dp, in[k].d_body, d, D[k], pdec[k][p], scr, scr, scr, s, K.who);
             if (rc) return rc;
         }
-        const hipError_t e = launch_across_positions(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), R.scratch,
-                                                     (const uint64_t *)(d + off_reg), (uint32_t)n_in, pcs[p].first * T, stride,
-                                                     d_out, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_across_positions", e);
+        const hipError_t e = K.launch(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), R.scratch, (const uint64_t *)(d + off_reg),
+                                      pcs[p].first * T, d + off_table, d_out, s);
+        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, K.launch_name, e);
     }
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
@@ -2742,12 +2768,64 @@ struct AcrossQuery {
         for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
         return total * sizeof(atsc_across_record);
     }
-    int check(atsc_ctx *ctx) const { return across_check(ctx, n_streams, count ? n_ranges : 0, count, stride, nullptr); }
+    int check(atsc_ctx *ctx) const { return across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, nullptr); }
     static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
     int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
             void *stream) const
     {
-        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream);
+        const uint32_t ns = n_streams;
+        const uint64_t st = stride;
+        const AcrossKernel K{CALL, "no across kernels", "launch k_across_positions", Q_ACROSS, BY_ACROSS,
+                             launch_across_positions != nullptr, nullptr, 0,
+                             [ns, st](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
+                                      const void *, void *d_out, hipStream_t s) {
+                                 return launch_across_positions(tasks, n, scratch, reg, ns, a0, st, d_out, s);
+                             }};
+        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
+    }
+};
+
+// the across quantiles' descriptor: the across' ranges, stride and records, a row of n_q levels per record; the levels
+// and the method are checked as the windowed quantiles check theirs (quantile_check_levels) and go up with the call's tables
+struct AcrossQntQuery {
+    static constexpr int INPUTS = 0;
+    static constexpr const char *CALL = "across_quantile_windows";
+    uint32_t n_streams;
+    uint64_t stride;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    uint32_t n_q;
+    const double *q;
+    int method;
+    int inputs() const { return (int)n_streams; }
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
+        return total * n_q * sizeof(double);
+    }
+    int check(atsc_ctx *ctx) const
+    {
+        const int rc = across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, nullptr);
+        return rc ? rc : quantile_check_levels(ctx, CALL, n_q, q, method);
+    }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
+    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
+            void *stream) const
+    {
+        const int rc = check(ctx);
+        if (rc) return rc;
+        const uint32_t ns = n_streams, nq = n_q;
+        const uint64_t st = stride;
+        const int m = method;
+        const AcrossKernel K{CALL, "no across quantile kernels", "launch k_across_quantile_positions", Q_ACROSS_QUANTILE,
+                             BY_ACROSS_QUANTILE, launch_across_quantile_positions != nullptr, q, n_q * sizeof(double),
+                             [ns, st, nq, m](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg,
+                                             uint64_t a0, const void *d_q, void *d_out, hipStream_t s) {
+                                 return launch_across_quantile_positions(tasks, n, scratch, reg, ns, a0, st, (const double *)d_q, nq,
+                                                                         m, (double *)d_out, s);
+                             }};
+        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
     }
 };
 
@@ -2783,6 +2861,34 @@ extern "C" int atsc_across_windows(atsc_ctx *ctx, uint32_t n_streams, const uint
     HostBody hb[MAX_INPUTS];
     for (uint32_t k = 0; k < n_streams; ++k) hb[k] = HostBody{body[k], body_len[k], has_count[k]};
     return query_host(ctx, hb, n_windows, begin, count, out, AcrossQuery{n_streams, stride, count, n_windows});
+    ATSC_API_END
+}
+
+extern "C" int atsc_across_quantile_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                                const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                                const uint64_t *count, uint64_t stride, uint32_t n_q, const double *q, int method,
+                                                double *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
+        return fail(ctx, ATSC_E_INVALID, "across_quantile_windows: n_streams outside [1, 64], a null list or a null entry");
+    QueryInput in[MAX_INPUTS];
+    for (uint32_t k = 0; k < n_streams; ++k) in[k] = QueryInput{dp[k], d_body[k], 0};
+    return AcrossQntQuery{n_streams, stride, count, n_windows, n_q, q, method}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    ATSC_API_END
+}
+
+extern "C" int atsc_across_quantile_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                                            const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                            uint64_t stride, uint32_t n_q, const double *q, int method, double *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
+        return fail(ctx, ATSC_E_INVALID, "across_quantile_windows: n_streams outside [1, 64], a null list or a null entry");
+    if ((uintptr_t)out & 7u) return fail(ctx, ATSC_E_INVALID, "across_quantile_windows: out is not 8-byte aligned");
+    HostBody hb[MAX_INPUTS];
+    for (uint32_t k = 0; k < n_streams; ++k) hb[k] = HostBody{body[k], body_len[k], has_count[k]};
+    return query_host(ctx, hb, n_windows, begin, count, out, AcrossQntQuery{n_streams, stride, count, n_windows, n_q, q, method});
     ATSC_API_END
 }
 
@@ -2959,5 +3065,16 @@ extern "C" int atsc_stream_across_windows(atsc_stream *const *streams, uint32_t 
     ATSC_API_BEGIN
     if (!across_lists(n_streams, (const void *const *)streams, nullptr)) return ATSC_E_INVALID;
     return query_stream(streams, n_windows, begin, count, out, AcrossQuery{n_streams, stride, count, n_windows});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_across_quantile_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                                   const uint64_t *begin, const uint64_t *count, uint64_t stride, uint32_t n_q,
+                                                   const double *q, int method, double *out)
+{
+    ATSC_API_BEGIN
+    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
+    return query_stream(streams, n_windows, begin, count, out,
+                        AcrossQntQuery{n_streams, stride, count, n_windows, n_q, q, method});
     ATSC_API_END
 }

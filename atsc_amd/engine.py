@@ -247,6 +247,24 @@ def _across_result(run, counts, stride):
     return run(int(off[-1])).view(ACROSS_RECORD), off
 
 
+def _across_quantile_params(stride, records, levels, method):
+    """the across' arguments, then the levels and the method"""
+    a = _RollArgs(tuple(_across_params(stride, records)) + _array_params(levels, method))
+    a.records = int(records)
+    return a
+
+
+def _across_quantile_block(n, cargs):
+    return 8 * cargs[1] * cargs.records
+
+
+def _across_quantile_result(run, counts, stride, levels):
+    """run(records) -> the block of an across quantile call as uint64 words.  -> (rows, off): a (records, n_q) float64
+    array, a row per position, range after range, and the ranges' record offsets (across_offsets)"""
+    off = across_offsets(counts, stride)
+    return run(int(off[-1])).view(np.float64).reshape(int(off[-1]), len(_levels(levels)[0])), off
+
+
 def _array_params(values, flag):
     """levels and method, or edges and closed"""
     a, pa = _levels(values)
@@ -263,6 +281,8 @@ _VALUES = _Query("values_windows", _values_dtype, None, _values_params)
 _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _select_block)
 _ROLLING = _Query("rolling_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_block)
 _ACROSS = _Query("across_windows", np.dtype(np.uint64), None, _across_params, _across_block, inputs=None)
+_ACROSS_QUANTILE = _Query("across_quantile_windows", np.dtype(np.uint64), None, _across_quantile_params, _across_quantile_block,
+                          inputs=None)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
 _HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
 
@@ -337,31 +357,33 @@ def _across_list(pointers):
     return (C.c_void_p * max(len(pointers), 1))(*pointers)
 
 
-def _across_host(ctx, records_list, begins, counts, has_count, stride, records):
-    """atsc_across_windows over the records of every stream of the list (has_count: one flag for all of them)"""
+def _across_host(ctx, records_list, begins, counts, has_count, stride, records, *params, q=_ACROSS):
+    """atsc_across_windows (q: or the across call that takes `params` more) over the records of every stream of the list
+    (has_count: one flag for all of them)"""
     arrays = [np.frombuffer(bytes(r), dtype=np.uint8) for r in records_list]
     lens, plens = _u64(np.array([len(b) for b in arrays], dtype=np.uint64))
     flags = np.full(max(len(arrays), 1), int(has_count), dtype=np.int32)
     wb, pb, wc, pc = _windows(begins, counts)
-    cargs = _ACROSS.params(stride, records)
-    fn = capi.lib().atsc_across_windows
-    out, po = _query_result(_ACROSS, len(wb), cargs, fn)
+    cargs = q.params(stride, records, *params)
+    fn = getattr(capi.lib(), "atsc_" + q.stem)
+    out, po = _query_result(q, len(wb), cargs, fn)
     rc = fn(ctx._h, len(arrays), _across_list([b.ctypes.data for b in arrays]), plens,
             flags.ctypes.data_as(C.POINTER(C.c_int32)), len(wb), pb, pc, *cargs, po)
     capi.check(rc, ctx._h)
-    return _query_rows(_ACROSS, out, len(wb))
+    return _query_rows(q, out, len(wb))
 
 
-def _across_dev(plans, bodies, begins, counts, d_out, stream, stride, records):
-    """atsc_across_windows_dev over the plans and their device bytes into the device tensor d_out"""
+def _across_dev(plans, bodies, begins, counts, d_out, stream, stride, records, *params, q=_ACROSS):
+    """atsc_across_windows_dev (q: or the across call that takes `params` more) over the plans and their device bytes
+    into the device tensor d_out"""
     b, pb, c, pc = _windows(begins, counts)
-    cargs = _ACROSS.params(stride, records)
+    cargs = q.params(stride, records, *params)
     assert len(plans) == len(bodies) and d_out.is_contiguous()
-    assert d_out.numel() * d_out.element_size() >= _query_bytes(_ACROSS, len(b), cargs, ())
+    assert d_out.numel() * d_out.element_size() >= _query_bytes(q, len(b), cargs, ())
     ctx = plans[0].ctx
-    rc = capi.lib().atsc_across_windows_dev(ctx._h, len(plans), _across_list([p._h.value for p in plans]),
-                                            _across_list([t.data_ptr() for t in bodies]), len(b), pb, pc, *cargs,
-                                            C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
+    rc = getattr(capi.lib(), "atsc_%s_dev" % q.stem)(ctx._h, len(plans), _across_list([p._h.value for p in plans]),
+                                                     _across_list([t.data_ptr() for t in bodies]), len(b), pb, pc, *cargs,
+                                                     C.c_void_p(d_out.data_ptr()), C.c_void_p(stream))
     capi.check(rc, ctx._h)
 
 
@@ -606,6 +628,18 @@ class Context:
         + 1 offsets, range i's records being records[off[i]:off[i + 1]].  has_count holds for every stream"""
         return _across_result(lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m), counts, stride)
 
+    def across_quantile_windows_host(self, records_list, begins, counts, levels, stride=1, method=capi.QUANTILE_LINEAR,
+                                     has_count=False):
+        """-> (rows, off): the levels (quantile_windows_host's rule and methods) of the samples that the streams of
+        records_list (at most ACROSS_MAX_STREAMS decoded record streams, as across_windows_host takes them) hold at every
+        `stride`-th position of every range [begins[i], begins[i] + counts[i]) (atsc_across_quantile_windows).  rows: a
+        (records, n_levels) float64 array, a row per position, range after range, NaN where every stream's sample is NaN;
+        off: across_offsets(counts, stride), range i's rows being rows[off[i]:off[i + 1]].  has_count holds for every
+        stream"""
+        return _across_quantile_result(
+            lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m, levels, method, q=_ACROSS_QUANTILE),
+            counts, stride, levels)
+
     def extremes_windows_host(self, records, begins, counts, k, has_count=False):
         """-> array of window_extremes_dtype(k): the k largest and the k smallest non-NaN samples, each with its offset
         in the window, the number of NaN samples and the length of every window [begins[i], begins[i] + counts[i]) of
@@ -797,6 +831,20 @@ class DPlan:
         off = across_offsets(counts, stride)
         _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, int(off[-1]))
         return off
+
+    def across_quantile_windows(self, d_body, others, other_bodies, begins, counts, levels, d_out, stride=1,
+                                method=capi.QUANTILE_LINEAR, stream=0):
+        """Enqueues the levels of the samples that this plan's stream and the plans `others` (their device bytes
+        other_bodies) hold at every `stride`-th position of the ranges [begins[i], begins[i] + counts[i]) into d_out, a
+        float64 device tensor of at least n_levels elements per position, position-major
+        (atsc_across_quantile_windows_dev).  A plan may appear more than once.  -> (rows, off): the (records, n_levels)
+        view of d_out's front, filled once `stream` has run, and the ranges' record offsets (across_offsets)"""
+        off = across_offsets(counts, stride)
+        m, n_q = int(off[-1]), len(_levels(levels)[0])
+        assert d_out.element_size() == 8
+        _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, m, levels, method,
+                    q=_ACROSS_QUANTILE)
+        return d_out.reshape(-1)[: m * n_q].reshape(m, n_q), off
 
     def extremes_windows(self, d_body, begins, counts, k, d_out, stream=0):
         """Enqueues the k largest and the k smallest samples of the windows [begins[i], begins[i] + counts[i]) into

@@ -9,6 +9,7 @@ from . import capi
 from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_ROLLING, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit, pair_fit  # noqa: F401
 from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
 from .engine import ACROSS_RECORD, _ACROSS, _across_host, _across_list, _across_result  # noqa: F401
+from .engine import _ACROSS_QUANTILE, _across_quantile_result
 
 
 def _f64(x):
@@ -156,17 +157,24 @@ class CompressedStream:
         """-> (records, off) over this stream (stream 0) and the streams `others` (stream 1 and on) at every
         `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as Context.across_windows_host gives
         them (atsc_stream_across_windows)"""
+        return _across_result(lambda m: self._across_stream(_ACROSS, others, begins, counts, stride, m), counts, stride)
+
+    def _across_stream(self, q, others, begins, counts, *params):
+        """atsc_stream_<q.stem> over this stream and the streams `others`"""
         streams = [self] + list(others)
+        wb, pb, wc, pc = _windows(begins, counts)
+        cargs = q.params(*params)
+        fn = getattr(capi.lib(), "atsc_stream_" + q.stem)
+        out, po = _query_result(q, len(wb), cargs, fn)
+        capi.check(fn(_across_list([s._h.value for s in streams]), len(streams), len(wb), pb, pc, *cargs, po), self.ctx._h)
+        return _query_rows(q, out, len(wb))
 
-        def run(m):
-            wb, pb, wc, pc = _windows(begins, counts)
-            cargs = _ACROSS.params(stride, m)
-            fn = capi.lib().atsc_stream_across_windows
-            out, po = _query_result(_ACROSS, len(wb), cargs, fn)
-            capi.check(fn(_across_list([s._h.value for s in streams]), len(streams), len(wb), pb, pc, *cargs, po), self.ctx._h)
-            return _query_rows(_ACROSS, out, len(wb))
-
-        return _across_result(run, counts, stride)
+    def across_quantile_windows(self, others, begins, counts, levels, stride=1, method=capi.QUANTILE_LINEAR):
+        """-> (rows, off): the levels of the samples that this stream and the streams `others` hold at every
+        `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as Context.across_quantile_windows_host
+        gives them (atsc_stream_across_quantile_windows)"""
+        return _across_quantile_result(
+            lambda m: self._across_stream(_ACROSS_QUANTILE, others, begins, counts, stride, m, levels, method), counts, stride, levels)
 
     def extremes_windows(self, begins, counts, k):
         """-> array of window_extremes_dtype(k) of the windows [begins[i], begins[i] + counts[i]): their k largest and k
@@ -264,11 +272,27 @@ def across_data_windows(ctx, bros, begins, counts, stride=1):
     """-> (records, off) over the streams decompress_data(ctx, bro) of every .bro image of the list `bros` at every
     `stride`-th position of the ranges, as Context.across_windows_host gives them: atsc_bro_open of each image, then
     atsc_across_windows over their records"""
+    records = _across_images(bros)
+    return _across_result(lambda m: _across_host(ctx, records, begins, counts, True, stride, m), counts, stride)
+
+
+def _across_images(bros):
+    """-> the records of every .bro image of the list, each checked by atsc_bro_open"""
     images = [np.frombuffer(bytes(b), dtype=np.uint8) for b in bros]
     for b in images:
         capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
     # the records from the frame-count varint (offset 9) on, as atsc_decompress_data reads them
-    return _across_result(lambda m: _across_host(ctx, [b[9:] for b in images], begins, counts, True, stride, m), counts, stride)
+    return [b[9:] for b in images]
+
+
+def across_quantile_data_windows(ctx, bros, begins, counts, levels, stride=1, method=capi.QUANTILE_LINEAR):
+    """-> (rows, off): the levels of the samples that the streams decompress_data(ctx, bro) of every .bro image of the
+    list `bros` hold at every `stride`-th position of the ranges, as Context.across_quantile_windows_host gives them:
+    atsc_bro_open of each image, then atsc_across_quantile_windows over their records"""
+    records = _across_images(bros)
+    return _across_quantile_result(
+        lambda m: _across_host(ctx, records, begins, counts, True, stride, m, levels, method, q=_ACROSS_QUANTILE), counts, stride,
+        levels)
 
 
 def extremes_data_windows(ctx, bro, begins, counts, k):

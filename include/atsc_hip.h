@@ -893,6 +893,40 @@ int atsc_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len,
                           const uint64_t *begin, const uint64_t *count, uint32_t n_q, const double *q, int method,
                           double *out);
 
+/* Windowed across quantiles: order statistics of the N samples that the streams of a call hold at every position of
+ * ranges of the decoded streams -- the median replica, the p95 across a zone's hosts, `quantile by (job)(0.9, x)` --
+ * without the decoded samples leaving the library.
+ *   Ranges     atsc_across_windows' exactly: one stride for the call, range i has atsc_across_outputs(count[i], stride)
+ *              positions, records are numbered range after range in the same order.
+ *   Result     record r is a row of n_q doubles at out[r * n_q + j], level j of the call's q.
+ *   Row        x_k = the sample of stream k at the position; the NaN ones are dropped, n are left, sorted in IEEE
+ *              total order (the windowed quantiles' key, -0.0 before +0.0); then the windowed quantiles' rule, unchanged,
+ *              over that sorted column: v = (double)(n - 1) * q[j], the ranks by the method, LINEAR by NumPy's _lerp
+ *              with no fused multiply-add.  n == 0 gives NaN for every level.
+ *              A row depends only on the N samples of its position, the levels and the method: not on the order of the
+ *              list (a reversed list gives the same bytes), the range, the stride, the budget, the piece boundaries, the
+ *              framing or the device.  Every value is bit-exact; where the rule's own arithmetic meets Inf - Inf, any
+ *              NaN conforms.
+ * Errors: ATSC_E_INVALID with nothing written and before any GPU work for every case of atsc_across_windows, a null q,
+ * n_q == 0 or n_q > 64, a level that is NaN or outside [0, 1], an unknown method, a result pointer that is not 8-byte
+ * aligned.  n_windows == 0 and empty ranges write nothing.  Scratch and pieces are the across': there is no
+ * ATSC_E_CAPACITY case. */
+/* dp / d_body (n_streams entries each), begin / count and q are HOST arrays; d_body[k] and d_out are device memory
+ * (d_out 8-byte aligned, n_q doubles per record).  Enqueued on `stream`, not synchronised.  A malformed payload in a
+ * frame of stream k that a range touches sets dp[k]'s status word.  dp[0] keeps the call's tables and scratch, apart from
+ * the across': the next across quantile call whose first plan is dp[0] waits (host side) until this one's work is done;
+ * atsc_dplan_destroy frees them. */
+int atsc_across_quantile_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                     const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                     const uint64_t *count, uint64_t stride, uint32_t n_q, const double *q, int method,
+                                     double *d_out, void *stream);
+/* Host bytes in (n_streams bodies, lengths and has_count flags), host rows out, synchronous; walks and uploads only the
+ * touched records of every stream, as atsc_across_windows does, and computes the device call's bits.  ATSC_E_FORMAT
+ * (nothing written) for a malformed payload in a frame of any stream that a range touches. */
+int atsc_across_quantile_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                                 const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                 uint64_t stride, uint32_t n_q, const double *q, int method, double *out);
+
 /* Windowed histograms: how the samples of windows [begin, begin + count) of the decoded stream (the indices of
  * atsc_decompress_frames) are distributed over value bins, from the same decoded samples as the window decode.  The
  * bins are given by n_edges ascending edges, the same for every window.  For window i:
@@ -989,6 +1023,11 @@ int atsc_stream_pair_windows(atsc_stream *x, atsc_stream *y, uint64_t n_windows,
  * ATSC_E_INVALID) */
 int atsc_stream_across_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows, const uint64_t *begin,
                                const uint64_t *count, uint64_t stride, atsc_across_record *out);
+/* atsc_across_quantile_windows over the frames of the n_streams streams of the list, which must belong to one context
+ * (else ATSC_E_INVALID) */
+int atsc_stream_across_quantile_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                        const uint64_t *begin, const uint64_t *count, uint64_t stride, uint32_t n_q,
+                                        const double *q, int method, double *out);
 /* atsc_quantile_windows over the stream's frames */
 int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint32_t n_q, const double *q, int method, double *out);
