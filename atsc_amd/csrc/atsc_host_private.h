@@ -81,6 +81,12 @@ int fail(atsc_ctx *ctx, int rc, const char *what, hipError_t e = hipSuccess);
         hipError_t e__ = (call);                                             \
         if (e__ != hipSuccess) return fail((ctx), ATSC_E_HIP, #call, e__);   \
     } while (0)
+// the same for a kernel launch, whose message names the kernel: "launch k_x"
+#define LAUNCHCHK(ctx, what, call)                                           \
+    do {                                                                     \
+        hipError_t e__ = (call);                                             \
+        if (e__ != hipSuccess) return fail((ctx), ATSC_E_HIP, (what), e__);  \
+    } while (0)
 
 hipError_t pool_alloc(atsc_ctx *ctx, void **out, size_t bytes);
 // The caller guarantees that no kernel still uses the block (plan destruction synchronises the device

@@ -272,6 +272,56 @@ static void merge_spans(std::vector<Span> &v)
     v.resize(m);
 }
 
+// Cuts the covering intervals (ascending, disjoint, in samples) into the pieces a call decodes one after the other:
+// ascending disjoint spans in units of `unit` samples, a covered range's ends rounded outwards to whole units.  Covered
+// ranges closer than `gap` units share a run, so that scattered windows do not each cost a piece of launches; a run is
+// cut every `len` units.  Hands back the longest piece, in units.
+static uint64_t cut_pieces(const std::vector<Span> &cov, uint64_t unit, uint64_t len, uint64_t gap, std::vector<Span> &pcs)
+{
+    uint64_t longest = 0;
+    for (size_t a = 0; a < cov.size();) {
+        const uint64_t k0 = cov[a].first / unit;
+        uint64_t k1 = (cov[a].second + unit - 1) / unit;
+        size_t z = a + 1;
+        while (z < cov.size() && cov[z].first / unit < k1 + gap) k1 = std::max(k1, (cov[z++].second + unit - 1) / unit);
+        for (uint64_t k = k0; k < k1; k += len) pcs.emplace_back(k, std::min(k1, k + len));
+        longest = std::max(longest, std::min(len, k1 - k0));
+        a = z;
+    }
+    return longest;
+}
+
+// A task and the piece it belongs to, as a call makes them in its own order (by window, by range).
+template <class T>
+struct Placed {
+    uint32_t piece;
+    T t;
+};
+// The placed tasks of P pieces, sorted by piece (stably: a piece's keep their order), into `tasks`: piece p's are
+// tasks[at[p] .. at[p + 1]), one launch.  Frees the placed list.
+template <class T>
+static void group_tasks(std::vector<Placed<T>> &tk, size_t P, std::vector<T> &tasks, std::vector<size_t> &at)
+{
+    auto piece_order = [](const Placed<T> &x, const Placed<T> &y) { return x.piece < y.piece; };
+    if (P > 1 && !std::is_sorted(tk.begin(), tk.end(), piece_order)) std::stable_sort(tk.begin(), tk.end(), piece_order);
+    tasks.reserve(tk.size());
+    at.assign(P + 1, 0);
+    for (const Placed<T> &x : tk) { tasks.push_back(x.t); ++at[x.piece + 1]; }
+    for (size_t p = 0; p < P; ++p) at[p + 1] += at[p];
+    std::vector<Placed<T>>().swap(tk);
+}
+
+// Reserves the tables and the scratch of a device call on R, stages the upload and enqueues its one copy; the tables'
+// device copy is R.d.  scr_n: the scratch's samples.  The caller has waited for R's previous call (R.wait()).
+static int stage_upload(atsc_ctx *ctx, QueryRes &R, const Upload &up, uint64_t scr_n, hipStream_t s)
+{
+    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, scr_n));
+    unsigned char *d = R.d;
+    up.stage(R.h);
+    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
+    return ATSC_OK;
+}
+
 // the decode tasks of all pieces of one call, and their place in the call's upload
 struct DecodeTasks {
     std::vector<DevWTask> small[CLASS_LARGE];
@@ -323,26 +373,22 @@ static int launch_piece_decode(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_
 {
     for (int c = 0; c < CLASS_LARGE; ++c) {
         if (!pt.small_n[c]) continue;
-        const hipError_t e = launch_decompress_window(dp->d_frames, (const DevWTask *)(d + D.off_small[c]) + pt.small_at[c], c,
-                                                      pt.small_n[c], dp->class_lds[c], dp->tabs.d_plans, dp->tabs.d_tw,
-                                                      d_body, out, dp->d_status, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, who.small, e);
+        LAUNCHCHK(ctx, who.small,
+                  launch_decompress_window(dp->d_frames, (const DevWTask *)(d + D.off_small[c]) + pt.small_at[c], c, pt.small_n[c],
+                                           dp->class_lds[c], dp->tabs.d_plans, dp->tabs.d_tw, d_body, out, dp->d_status, s));
     }
-    if (pt.big_n) {
-        const hipError_t e = launch_decompress_large(
-            pt.big_n, (const DevDFrame *)(d + D.off_big) + pt.big_at, (const uint32_t *)(d + D.off_ids), dp->tabs.d_plans,
-            dp->tabs.d_tw, d_body, out, dp->d_status, dp->d_ws, dp->ws_stride, dp->ws_slots, dp->large_tiled ? 1 : 0,
-            large_sparse() ? 1 : 0, s, dp->large_pre.tiles1 ? &dp->large_pre : nullptr,
-            // the (tile, frame) split of the sparse inverse runs for launches of up to LARGE_SPLIT_MAX frames: a window
-            // launch of fewer frames than its plan's full decode takes the full decode's side of that line
-            dp->large_choice_count <= LARGE_SPLIT_MAX ? dp->large_sp_tiles : 0);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, who.large, e);
-    }
-    if (pt.gat_n) {
-        const hipError_t e = launch_window_gather((const DevWGather *)(d + D.off_gat) + pt.gat_at, pt.gat_n, pt.max_len,
-                                                  gat_src, gat_dst, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, who.gather, e);
-    }
+    if (pt.big_n)
+        LAUNCHCHK(ctx, who.large,
+                  launch_decompress_large(
+                      pt.big_n, (const DevDFrame *)(d + D.off_big) + pt.big_at, (const uint32_t *)(d + D.off_ids),
+                      dp->tabs.d_plans, dp->tabs.d_tw, d_body, out, dp->d_status, dp->d_ws, dp->ws_stride, dp->ws_slots,
+                      dp->large_tiled ? 1 : 0, large_sparse() ? 1 : 0, s, dp->large_pre.tiles1 ? &dp->large_pre : nullptr,
+                      // the (tile, frame) split of the sparse inverse runs for launches of up to LARGE_SPLIT_MAX frames: a
+                      // window launch of fewer frames than its plan's full decode takes the full decode's side of that line
+                      dp->large_choice_count <= LARGE_SPLIT_MAX ? dp->large_sp_tiles : 0));
+    if (pt.gat_n)
+        LAUNCHCHK(ctx, who.gather,
+                  launch_window_gather((const DevWGather *)(d + D.off_gat) + pt.gat_at, pt.gat_n, pt.max_len, gat_src, gat_dst, s));
     return ATSC_OK;
 }
 
@@ -734,6 +780,34 @@ static bool emit_piece_decode(const atsc_dplan *dp, uint64_t org, const std::vec
     pt.gat_n = (uint32_t)(D.gat.size() - pt.gat_at);
     D.max_big = std::max(D.max_big, pt.big_n);
     return true;
+}
+
+// The decode tasks of every piece of one input, piece after piece (emit_piece_decode): piece p holds samples
+// [pcs[p].first * unit, pcs[p].second * unit).  `call` names the caller in the message.
+static int emit_pieces_decode(atsc_ctx *ctx, const char *call, const atsc_dplan *dp, uint64_t org, const std::vector<Span> &cov,
+                              const std::vector<Span> &pcs, uint64_t unit, uint64_t region, DecodeTasks &D,
+                              std::vector<PieceDecode> &pdec)
+{
+    pdec.resize(pcs.size());
+    size_t ci = 0;
+    for (size_t p = 0; p < pcs.size(); ++p)
+        if (!emit_piece_decode(dp, org, cov, ci, pcs[p].first * unit, pcs[p].second * unit, region, D, pdec[p]))
+            return fail_in(ctx, ATSC_E_INVALID, call, "internal error (spill slots)");
+    return ATSC_OK;
+}
+
+// The scratch of a call over n_in inputs: every input's region and behind it the spill slots it uses.  at[k]: where
+// input k's region begins; hands back the samples of them all.  region and MAX_FRAME are even numbers of doubles, so every
+// region begins at a multiple of 16 bytes, as the kernels' 16-byte loads need.
+static uint64_t place_regions(const DecodeTasks *D, int n_in, uint64_t region, uint64_t *at)
+{
+    static_assert(AGG_TILE % 2 == 0 && MAX_FRAME % 2 == 0, "16-byte aligned regions");
+    uint64_t scr_n = 0;
+    for (int k = 0; k < n_in; ++k) {
+        at[k] = scr_n;
+        scr_n += region + (uint64_t)MAX_FRAME * D[k].spills_used;
+    }
+    return scr_n;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1178,23 +1252,8 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
     merge_spans(cov);
     uint64_t spill[NI];
     const uint64_t piece_tiles = piece_samples(ctx, in, NI, cov, T, spill) / T;
-    struct Piece {
-        uint64_t k0, k1;  // tiles [k0, k1): samples [k0 T, k1 T) at scratch[0, (k1 - k0) T)
-    };
-    std::vector<Piece> pcs;
-    uint64_t region_tiles = 0;
-    for (size_t a = 0; a < cov.size();) {
-        const uint64_t k0 = cov[a].first / T;
-        uint64_t k1 = (cov[a].second + T - 1) / T;
-        size_t z = a + 1;
-        while (z < cov.size() && cov[z].first / T < k1 + AGG_GAP_TILES) k1 = std::max(k1, (cov[z++].second + T - 1) / T);
-        for (uint64_t k = k0; k < k1; k += piece_tiles) {
-            pcs.push_back(Piece{k, std::min(k1, k + piece_tiles)});
-            region_tiles = std::max(region_tiles, pcs.back().k1 - k);
-        }
-        a = z;
-    }
-    const uint64_t region = region_tiles * T;
+    std::vector<Span> pcs;  // tiles [first, second): samples [first T, second T) at scratch[0, (second - first) T)
+    const uint64_t region = cut_pieces(cov, T, piece_tiles, AGG_GAP_TILES, pcs) * T;
     // shared full tiles: the tiles past a window's first and before its last, merged over the windows
     std::vector<Span> mids;
     for (uint64_t i = 0; i < W; ++i) {
@@ -1259,29 +1318,27 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
             live.swap(next);
         }
     }
-    // decode tasks of every piece (emit_piece_decode), once per input, and its tile tasks
+    // decode tasks of every piece, once per input, and every piece's tile tasks
     std::vector<PieceDecode> pdec[NI];
+    DecodeTasks D[NI];
+    for (int k = 0; k < NI && !rc; ++k) rc = emit_pieces_decode(ctx, Q::CALL, in[k].dp, in[k].org, cov, pcs, T, region, D[k], pdec[k]);
+    if (rc) return rc;
     std::vector<size_t> tile_at(pcs.size());
     std::vector<uint32_t> tile_n(pcs.size());
     std::vector<char> carry_in(pcs.size(), 0);  // the piece's first tile reads the previous piece's last sample
-    DecodeTasks D[NI];
     std::vector<typename Q::Tile> tiles;
     tiles.reserve(tt.size());
-    size_t ci[NI] = {}, ti = 0;
-    for (int k = 0; k < NI; ++k) pdec[k].resize(pcs.size());
+    size_t ti = 0;
     for (size_t p = 0; p < pcs.size(); ++p) {
         tile_at[p] = tiles.size();
-        for (int k = 0; k < NI; ++k)
-            if (!emit_piece_decode(in[k].dp, in[k].org, cov, ci[k], pcs[p].k0 * T, pcs[p].k1 * T, region, D[k], pdec[k][p]))
-                return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "internal error (spill slots)");
-        for (; ti < tt.size() && tt[ti].k < pcs[p].k1; ++ti) {
+        for (; ti < tt.size() && tt[ti].k < pcs[p].second; ++ti) {
             DevAggTile t = tt[ti].t;
-            t.src = (tt[ti].k - pcs[p].k0) * T;
+            t.src = (tt[ti].k - pcs[p].first) * T;
             tiles.push_back(Q::tile(t, tt[ti].k));
             if (Q::carried(tiles.back())) carry_in[p] = 1;
         }
         // (a window that covers the slot in front of the piece covers the tile in front: the previous piece ends there)
-        if (carry_in[p] && (p == 0 || pcs[p - 1].k1 != pcs[p].k0))
+        if (carry_in[p] && (p == 0 || pcs[p - 1].second != pcs[p].first))
             return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "internal error (carry without a previous piece)");
         tile_n[p] = (uint32_t)(tiles.size() - tile_at[p]);
     }
@@ -1303,18 +1360,10 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
     const size_t off_side = Q::SIDE_BEGINS    ? off_begins
                             : NoSide<Q>::value ? off_part
                                                : up.device_only(Q::CARRY ? sizeof(double) : 2 * W * sizeof(double));
-    // every input's region and behind it the spill slots it uses; region and MAX_FRAME are even numbers of doubles, so
-    // every region begins at a multiple of 16 bytes, as the tile kernels' 16-byte loads need
-    uint64_t scr_at[NI], scr_n = 0;
-    for (int k = 0; k < NI; ++k) {
-        scr_at[k] = scr_n;
-        scr_n += region + (uint64_t)MAX_FRAME * D[k].spills_used;
-    }
-    static_assert(AGG_TILE % 2 == 0 && MAX_FRAME % 2 == 0, "16-byte aligned regions");
-    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, scr_n));
+    uint64_t scr_at[NI];
+    rc = stage_upload(ctx, R, up, place_regions(D, NI, region, scr_at), s);
+    if (rc) return rc;
     unsigned char *d = R.d;
-    up.stage(R.h);
-    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
     double *scr[NI];
     for (int k = 0; k < NI; ++k) scr[k] = R.scratch + scr_at[k];
     void *part = d + off_part, *side = d + off_side;
@@ -1323,16 +1372,13 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
             rc = launch_piece_decode(ctx, in[k].dp, in[k].d_body, d, D[k], pdec[k][p], scr[k], scr[k], scr[k], s, Q::who());
             if (rc) return rc;
         }
-        const hipError_t e = q.tiles((const typename Q::Tile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, side, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, Q::TILES, e);
+        LAUNCHCHK(ctx, Q::TILES, q.tiles((const typename Q::Tile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, side, s));
         if (Q::CARRY && p + 1 < pcs.size() && carry_in[p + 1])
-            HIPCHK(ctx, hipMemcpyAsync(side, scr[0] + (pcs[p].k1 - pcs[p].k0) * T - 1, sizeof(double), hipMemcpyDeviceToDevice, s));
+            HIPCHK(ctx, hipMemcpyAsync(side, scr[0] + (pcs[p].second - pcs[p].first) * T - 1, sizeof(double), hipMemcpyDeviceToDevice, s));
     }
-    for (size_t a = 0; a + 1 < pass_at.size(); ++a) {
-        const hipError_t e = q.combine((const DevAggComb *)(d + off_comb) + pass_at[a], (uint32_t)(pass_at[a + 1] - pass_at[a]),
-                                       part, side, d_out, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, Q::COMBINE, e);
-    }
+    for (size_t a = 0; a + 1 < pass_at.size(); ++a)
+        LAUNCHCHK(ctx, Q::COMBINE, q.combine((const DevAggComb *)(d + off_comb) + pass_at[a], (uint32_t)(pass_at[a + 1] - pass_at[a]),
+                                             part, side, d_out, s));
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
 }
@@ -1902,10 +1948,9 @@ static int quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bo
                  off_long = up.add(longs), off_chunk = up.add(chunks);
     const size_t hist_bytes = (size_t)max_long * rows * 256 * sizeof(uint32_t);
     const size_t off_state = up.device_only((size_t)max_long * sizeof(DevQState)), off_hist = up.device_only(hist_bytes);
-    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, std::max<uint64_t>(1, region + (uint64_t)MAX_FRAME * D.spills_used)));
+    rc = stage_upload(ctx, R, up, std::max<uint64_t>(1, region + (uint64_t)MAX_FRAME * D.spills_used), s);
+    if (rc) return rc;
     unsigned char *d = R.d;
-    up.stage(R.h);
-    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
     if (hist_bytes) HIPCHK(ctx, hipMemsetAsync(d + off_hist, 0, hist_bytes, s));  // k_qnt_pick clears what it reads
     double *scr = R.scratch;
     const double *dq = (const double *)(d + off_q);
@@ -1914,24 +1959,20 @@ static int quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bo
     const DevQChunk *d_chunk = (const DevQChunk *)(d + off_chunk);
     DevQState *st = (DevQState *)(d + off_state);
     uint32_t *hist = (uint32_t *)(d + off_hist);
-    hipError_t e = launch_qnt_short(d_short + empty_at, empty_n, scr, dq, n_q, method, d_out, s);
-    if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_short", e);
+    LAUNCHCHK(ctx, "launch k_qnt_short", launch_qnt_short(d_short + empty_at, empty_n, scr, dq, n_q, method, d_out, s));
     for (size_t p = 0; p < pcs.size(); ++p) {
         rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_QUANTILE);
         if (rc) return rc;
         const PieceQ &t = pq[p];
-        e = launch_qnt_short(d_short + t.short_at, t.short_n, scr, dq, n_q, method, d_out, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_short", e);
-        for (uint32_t c = 0; c < n_med; ++c) {
-            e = launch_qnt_medium(d_med + t.med_at[c], t.med_n[c], 512u << c, scr, dq, n_q, method, d_out, s);
-            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_medium", e);
-        }
+        LAUNCHCHK(ctx, "launch k_qnt_short", launch_qnt_short(d_short + t.short_at, t.short_n, scr, dq, n_q, method, d_out, s));
+        for (uint32_t c = 0; c < n_med; ++c)
+            LAUNCHCHK(ctx, "launch k_qnt_medium",
+                      launch_qnt_medium(d_med + t.med_at[c], t.med_n[c], 512u << c, scr, dq, n_q, method, d_out, s));
         if (!t.long_n) continue;
         for (uint32_t pass = 0; pass < QNT_PASSES; ++pass) {
-            e = launch_qnt_hist(d_chunk + t.chunk_at, t.chunk_n, scr, st, hist, rows, pass, s);
-            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_hist", e);
-            e = launch_qnt_pick(d_long + t.long_at, t.long_n, st, hist, rows, pass, dq, n_q, method, d_out, s);
-            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_qnt_pick", e);
+            LAUNCHCHK(ctx, "launch k_qnt_hist", launch_qnt_hist(d_chunk + t.chunk_at, t.chunk_n, scr, st, hist, rows, pass, s));
+            LAUNCHCHK(ctx, "launch k_qnt_pick",
+                      launch_qnt_pick(d_long + t.long_at, t.long_n, st, hist, rows, pass, dq, n_q, method, d_out, s));
         }
     }
     HIPCHK(ctx, R.record(s));
@@ -2046,21 +2087,9 @@ static int histogram_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
     const uint64_t L = piece_samples(ctx, dp, org, cov, 1, &spill);
     // pieces: samples [S0, S1) of the stream at scratch[0, S1 - S0), ascending and disjoint
     std::vector<Span> pcs;
-    uint64_t region = 0;
-    for (size_t a = 0; a < cov.size();) {
-        const uint64_t s0 = cov[a].first;
-        uint64_t s1 = cov[a].second;
-        size_t z = a + 1;
-        while (z < cov.size() && cov[z].first < s1 + HST_GAP) s1 = cov[z++].second;
-        for (uint64_t p = s0; p < s1; p += L) pcs.emplace_back(p, std::min(s1, p + L));
-        region = std::max(region, std::min(L, s1 - s0));
-        a = z;
-    }
+    const uint64_t region = cut_pieces(cov, 1, L, HST_GAP, pcs);
     // tasks, by tier: a window cut by a piece boundary gets tasks on each side
-    struct PT {
-        uint32_t piece;
-        DevHistTask t;
-    };
+    using PT = Placed<DevHistTask>;
     std::vector<PT> tk[2];  // 0: short, 1: chunk
     tk[0].reserve(W);
     for (uint64_t i = 0; i < W; ++i) {
@@ -2087,34 +2116,25 @@ static int histogram_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
     std::vector<DevHistTask> tasks[2];
     std::vector<size_t> at[2];
     for (int k = 0; k < 2; ++k) {
-        auto by_piece = [](const PT &x, const PT &y) { return x.piece < y.piece; };
-        if (P > 1 && !std::is_sorted(tk[k].begin(), tk[k].end(), by_piece)) std::stable_sort(tk[k].begin(), tk[k].end(), by_piece);
-        tasks[k].reserve(tk[k].size());
-        at[k].assign(P + 1, 0);
-        for (const PT &x : tk[k]) { tasks[k].push_back(x.t); ++at[k][x.piece + 1]; }
-        for (size_t p = 0; p < P; ++p) {
-            if (at[k][p + 1] > 0x7fffffffull) return fail(ctx, ATSC_E_INVALID, "histogram_windows: more than 2^31 - 1 tasks in a piece");
-            at[k][p + 1] += at[k][p];
-        }
-        std::vector<PT>().swap(tk[k]);
+        group_tasks(tk[k], P, tasks[k], at[k]);
+        for (size_t p = 0; p < P; ++p)
+            if (at[k][p + 1] - at[k][p] > 0x7fffffffull)
+                return fail(ctx, ATSC_E_INVALID, "histogram_windows: more than 2^31 - 1 tasks in a piece");
     }
     // decode tasks of every piece
-    std::vector<PieceDecode> pdec(P);
+    std::vector<PieceDecode> pdec;
     DecodeTasks D;
-    size_t ci = 0;
-    for (size_t p = 0; p < P; ++p)
-        if (!emit_piece_decode(dp, org, cov, ci, pcs[p].first, pcs[p].second, region, D, pdec[p]))
-            return fail(ctx, ATSC_E_INVALID, "histogram_windows: internal error (spill slots)");
+    rc = emit_pieces_decode(ctx, "histogram_windows", dp, org, cov, pcs, 1, region, D, pdec);
+    if (rc) return rc;
     QueryRes &R = dp->res[Q_HISTOGRAM];
     HIPCHK(ctx, R.wait());
     // one upload: the decode tasks, the edges, the two tiers' task lists
     Upload up;
     D.place(up);
     const size_t off_edges = up.add(edges, n_edges * sizeof(double)), off_short = up.add(tasks[0]), off_chunk = up.add(tasks[1]);
-    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, std::max<uint64_t>(1, region + (uint64_t)MAX_FRAME * D.spills_used)));
+    rc = stage_upload(ctx, R, up, std::max<uint64_t>(1, region + (uint64_t)MAX_FRAME * D.spills_used), s);
+    if (rc) return rc;
     unsigned char *d = R.d;
-    up.stage(R.h);
-    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
     if (!all_own) HIPCHK(ctx, hipMemsetAsync(d_out, 0, W * rows * sizeof(uint64_t), s));
     double *scr = R.scratch;
     const double *d_edges = (const double *)(d + off_edges);
@@ -2122,11 +2142,10 @@ static int histogram_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_b
     for (size_t p = 0; p < P; ++p) {
         rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_HISTOGRAM);
         if (rc) return rc;
-        hipError_t e = launch_hst_short(d_short + at[0][p], (uint32_t)(at[0][p + 1] - at[0][p]), scr, d_edges, n_edges, closed,
-                                        d_out, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_hst_short", e);
-        e = launch_hst_chunk(d_chunk + at[1][p], (uint32_t)(at[1][p + 1] - at[1][p]), scr, d_edges, n_edges, closed, d_out, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_hst_chunk", e);
+        LAUNCHCHK(ctx, "launch k_hst_short",
+                  launch_hst_short(d_short + at[0][p], (uint32_t)(at[0][p + 1] - at[0][p]), scr, d_edges, n_edges, closed, d_out, s));
+        LAUNCHCHK(ctx, "launch k_hst_chunk",
+                  launch_hst_chunk(d_chunk + at[1][p], (uint32_t)(at[1][p + 1] - at[1][p]), scr, d_edges, n_edges, closed, d_out, s));
     }
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
@@ -2218,24 +2237,11 @@ static int select_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
     const uint64_t L = piece_samples(ctx, dp, org, cov, 1, &spill);
     // pieces: samples [S0, S1) of the stream at scratch[0, S1 - S0), ascending and disjoint
     std::vector<Span> pcs;
-    uint64_t region = 0;
-    for (size_t a = 0; a < cov.size();) {
-        const uint64_t s0 = cov[a].first;
-        uint64_t s1 = cov[a].second;
-        size_t z = a + 1;
-        while (z < cov.size() && cov[z].first < s1 + HST_GAP) s1 = cov[z++].second;
-        for (uint64_t p = s0; p < s1; p += L) pcs.emplace_back(p, std::min(s1, p + L));
-        region = std::max(region, std::min(L, s1 - s0));
-        a = z;
-    }
+    uint64_t region = cut_pieces(cov, 1, L, HST_GAP, pcs);
     region += 1;  // the pair load's slot behind a piece's last sample
     const size_t P = pcs.size();
     // tasks in (window, position) order
-    struct PT {
-        uint32_t piece;
-        DevSelTask t;
-    };
-    std::vector<PT> tk;
+    std::vector<Placed<DevSelTask>> tk;
     tk.reserve(W);
     std::vector<uint32_t> first(W + 1);
     uint64_t n_tasks = 0;
@@ -2249,27 +2255,20 @@ static int select_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
             const uint64_t lo = std::max(b, pcs[p].first), hi = std::min(e, pcs[p].second);
             for (uint64_t o = lo; o < hi; o += SEL_TASK) {
                 if (n_tasks >= 0x7fffffffull) return fail(ctx, ATSC_E_INVALID, "select_windows: more than 2^31 - 1 tasks");
-                tk.push_back(PT{(uint32_t)p, DevSelTask{o - pcs[p].first, o - b, (uint32_t)std::min<uint64_t>(SEL_TASK, hi - o),
-                                                        (uint32_t)n_tasks++}});
+                tk.push_back({(uint32_t)p, DevSelTask{o - pcs[p].first, o - b, (uint32_t)std::min<uint64_t>(SEL_TASK, hi - o),
+                                                      (uint32_t)n_tasks++}});
             }
         }
     }
     first[W] = (uint32_t)n_tasks;
-    auto by_piece = [](const PT &x, const PT &y) { return x.piece < y.piece; };
-    if (P > 1 && !std::is_sorted(tk.begin(), tk.end(), by_piece)) std::stable_sort(tk.begin(), tk.end(), by_piece);
     std::vector<DevSelTask> tasks;
-    tasks.reserve(tk.size());
-    std::vector<size_t> at(P + 1, 0);
-    for (const PT &x : tk) { tasks.push_back(x.t); ++at[x.piece + 1]; }
-    for (size_t p = 0; p < P; ++p) at[p + 1] += at[p];
-    std::vector<PT>().swap(tk);
+    std::vector<size_t> at;
+    group_tasks(tk, P, tasks, at);
     // decode tasks of every piece
-    std::vector<PieceDecode> pdec(P);
+    std::vector<PieceDecode> pdec;
     DecodeTasks D;
-    size_t ci = 0;
-    for (size_t p = 0; p < P; ++p)
-        if (!emit_piece_decode(dp, org, cov, ci, pcs[p].first, pcs[p].second, region, D, pdec[p]))
-            return fail(ctx, ATSC_E_INVALID, "select_windows: internal error (spill slots)");
+    rc = emit_pieces_decode(ctx, "select_windows", dp, org, cov, pcs, 1, region, D, pdec);
+    if (rc) return rc;
     QueryRes &R = dp->res[Q_SELECT];
     HIPCHK(ctx, R.wait());
     // one upload: the decode tasks, the select tasks, the windows' first slots; behind them (device only) the counts,
@@ -2279,32 +2278,27 @@ static int select_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body
     const size_t off_tasks = up.add(tasks), off_first = up.add(first);
     const size_t off_cnt = up.device_only((n_tasks + 1) * sizeof(uint64_t));
     const size_t off_sums = up.device_only(sel_scan_sums(n_tasks + 1) * sizeof(uint64_t));
-    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, region + (uint64_t)MAX_FRAME * D.spills_used));
+    rc = stage_upload(ctx, R, up, region + (uint64_t)MAX_FRAME * D.spills_used, s);
+    if (rc) return rc;
     unsigned char *d = R.d;
-    up.stage(R.h);
-    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
     double *scr = R.scratch;
     const DevSelTask *d_tasks = (const DevSelTask *)(d + off_tasks);
     uint64_t *cnt = (uint64_t *)(d + off_cnt);
-    hipError_t e;
     for (size_t p = 0; p < P; ++p) {
         rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_SELECT);
         if (rc) return rc;
-        e = launch_sel_count(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, op, limit, cnt, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_sel_count", e);
+        LAUNCHCHK(ctx, "launch k_sel_count", launch_sel_count(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, op, limit, cnt, s));
     }
-    e = launch_sel_scan(cnt, n_tasks, (uint64_t *)(d + off_sums), s);
-    if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_sel_scan", e);
-    e = launch_sel_offsets(cnt, (const uint32_t *)(d + off_first), W + 1, (uint64_t *)d_out, s);
-    if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_sel_offsets", e);
+    LAUNCHCHK(ctx, "launch k_sel_scan", launch_sel_scan(cnt, n_tasks, (uint64_t *)(d + off_sums), s));
+    LAUNCHCHK(ctx, "launch k_sel_offsets", launch_sel_offsets(cnt, (const uint32_t *)(d + off_first), W + 1, (uint64_t *)d_out, s));
     for (size_t p = 0; cap && p < P; ++p) {
         if (P > 1) {  // the scratch holds the last piece: this one's samples again
             rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_SELECT);
             if (rc) return rc;
         }
-        e = launch_sel_write(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, op, limit, cnt, cap,
-                             (char *)d_out + (W + 1) * sizeof(uint64_t), s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_sel_write", e);
+        LAUNCHCHK(ctx, "launch k_sel_write",
+                  launch_sel_write(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, op, limit, cnt, cap,
+                                   (char *)d_out + (W + 1) * sizeof(uint64_t), s));
     }
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
@@ -2440,11 +2434,7 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
     }
     const size_t P = pcs.size();
     // tasks, by piece: per range the runs of positions whose windows end inside the piece and not inside an earlier one
-    struct PT {
-        uint32_t piece;
-        DevRollTask t;
-    };
-    std::vector<PT> tk;
+    std::vector<Placed<DevRollTask>> tk;
     uint64_t rec = 0;
     for (uint64_t i = 0; i < W; ++i) {
         if (!m[i]) continue;
@@ -2458,23 +2448,19 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
                 return fail(ctx, ATSC_E_INVALID, "rolling_windows: internal error (position outside the pieces)");
             const uint64_t je = std::min(m[i], (pcs[p].second - w - b) / stride + 1);  // positions whose windows end in the piece
             for (; j < je; j += ROLL_TASK)
-                tk.push_back(PT{(uint32_t)p, DevRollTask{b + j * stride, rec + j, (uint32_t)std::min<uint64_t>(ROLL_TASK, je - j), 0}});
+                tk.push_back({(uint32_t)p, DevRollTask{b + j * stride, rec + j, (uint32_t)std::min<uint64_t>(ROLL_TASK, je - j), 0}});
             j = je;
         }
         rec += m[i];
     }
-    auto by_piece = [](const PT &x, const PT &y) { return x.piece < y.piece; };
-    if (P > 1 && !std::is_sorted(tk.begin(), tk.end(), by_piece)) std::stable_sort(tk.begin(), tk.end(), by_piece);
     std::vector<DevRollTask> tasks;
-    tasks.reserve(tk.size());
-    std::vector<size_t> at(P + 1, 0);
-    for (const PT &x : tk) { tasks.push_back(x.t); ++at[x.piece + 1]; }
-    for (size_t p = 0; p < P; ++p) at[p + 1] += at[p];
-    std::vector<PT>().swap(tk);
+    std::vector<size_t> at;
+    group_tasks(tk, P, tasks, at);
     // the levels' places in the pyramid, the same in every piece: level l has room for (region >> l) + 2 chunks
     uint32_t lmax = 0;
     while (lmax < ROLL_MAX_LEVEL && (2ull << lmax) <= w) ++lmax;
     std::vector<DevRollPiece> pieces(P);
+    std::vector<Span> dec(P);  // what a piece decodes: its samples and, in front of them, what the ranges cover of its first tile
     uint64_t pyr_n = 0;
     {
         DevRollPiece lv{};
@@ -2483,15 +2469,13 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
             pieces[p] = lv;
             pieces[p].a0 = pcs[p].first / T * T;
             pieces[p].a1 = (pcs[p].second + T - 1) / T * T;
+            dec[p] = Span(pieces[p].a0, pcs[p].second);
         }
     }
-    // decode tasks of every piece: the piece's samples and, in front of them, what the ranges cover of its first tile
-    std::vector<PieceDecode> pdec(P);
+    std::vector<PieceDecode> pdec;
     DecodeTasks D;
-    size_t ci = 0;
-    for (size_t p = 0; p < P; ++p)
-        if (!emit_piece_decode(dp, org, cov, ci, pieces[p].a0, pcs[p].second, region, D, pdec[p]))
-            return fail(ctx, ATSC_E_INVALID, "rolling_windows: internal error (spill slots)");
+    rc = emit_pieces_decode(ctx, "rolling_windows", dp, org, cov, dec, 1, region, D, pdec);
+    if (rc) return rc;
     QueryRes &R = dp->res[Q_ROLLING];
     HIPCHK(ctx, R.wait());
     Upload up;
@@ -2500,27 +2484,23 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
     // the scratch: the region, the spill slots, the pyramid (four doubles a partial; region and MAX_FRAME are even numbers
     // of doubles, so the pyramid begins at a multiple of 16 bytes, as its 16-byte loads and stores need)
     const uint64_t pyr_at = region + (uint64_t)MAX_FRAME * D.spills_used;
-    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, pyr_at + 4 * pyr_n));
+    rc = stage_upload(ctx, R, up, pyr_at + 4 * pyr_n, s);
+    if (rc) return rc;
     unsigned char *d = R.d;
-    up.stage(R.h);
-    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
     double *scr = R.scratch;
     void *pyr = scr + pyr_at;
     const DevRollTask *d_tasks = (const DevRollTask *)(d + off_tasks);
     const DevRollPiece *d_pieces = (const DevRollPiece *)(d + off_pieces);
-    hipError_t e;
     for (size_t p = 0; p < P; ++p) {
         rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_ROLLING);
         if (rc) return rc;
         const uint64_t a0 = pieces[p].a0, last = pieces[p].a1 - 1;
-        e = launch_roll_pyramid(scr, (uint32_t)((pieces[p].a1 - a0) / T), pyr, d_pieces + p, lmax, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_roll_pyramid", e);
-        for (uint32_t src = ROLL_TILE_LOG; src < lmax; src += 6) {
-            e = launch_roll_upper(pyr, d_pieces + p, (uint32_t)(((last >> src) >> 6) - ((a0 >> src) >> 6) + 1), src, lmax, s);
-            if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_roll_upper", e);
-        }
-        e = launch_roll_positions(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, pyr, d_pieces + p, w, stride, d_out, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, "launch k_roll_positions", e);
+        LAUNCHCHK(ctx, "launch k_roll_pyramid", launch_roll_pyramid(scr, (uint32_t)((pieces[p].a1 - a0) / T), pyr, d_pieces + p, lmax, s));
+        for (uint32_t src = ROLL_TILE_LOG; src < lmax; src += 6)
+            LAUNCHCHK(ctx, "launch k_roll_upper",
+                      launch_roll_upper(pyr, d_pieces + p, (uint32_t)(((last >> src) >> 6) - ((a0 >> src) >> 6) + 1), src, lmax, s));
+        LAUNCHCHK(ctx, "launch k_roll_positions",
+                  launch_roll_positions(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, pyr, d_pieces + p, w, stride, d_out, s));
     }
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
@@ -2662,28 +2642,11 @@ static int across_dev(atsc_ctx *ctx, const QueryInput *in, int n_in, uint64_t n_
     const uint64_t want = scratch_budget_samples(ctx, large);
     const uint64_t piece_tiles =
         std::max<uint64_t>(AGG_MIN_PIECE, want > spills ? (want - spills) / (uint64_t)n_in / T * T : 0) / T;
-    // pieces: tiles [first, second), ascending and disjoint; covered tile ranges closer than AGG_GAP_TILES share a span
-    std::vector<Span> pcs;
-    uint64_t region_tiles = 0;
-    for (size_t a = 0; a < cov.size();) {
-        const uint64_t k0 = cov[a].first / T;
-        uint64_t k1 = (cov[a].second + T - 1) / T;
-        size_t z = a + 1;
-        while (z < cov.size() && cov[z].first / T < k1 + AGG_GAP_TILES) k1 = std::max(k1, (cov[z++].second + T - 1) / T);
-        for (uint64_t k = k0; k < k1; k += piece_tiles) {
-            pcs.emplace_back(k, std::min(k1, k + piece_tiles));
-            region_tiles = std::max(region_tiles, pcs.back().second - k);
-        }
-        a = z;
-    }
+    std::vector<Span> pcs;  // tiles [first, second)
+    const uint64_t region = cut_pieces(cov, T, piece_tiles, AGG_GAP_TILES, pcs) * T;
     const size_t P = pcs.size();
-    const uint64_t region = region_tiles * T;
     // tasks, by piece: per range the runs of positions inside each piece
-    struct PT {
-        uint32_t piece;
-        DevRollTask t;
-    };
-    std::vector<PT> tk;
+    std::vector<Placed<DevRollTask>> tk;
     uint64_t rec = 0;
     for (uint64_t i = 0; i < W; ++i) {
         if (!m[i]) continue;
@@ -2697,46 +2660,30 @@ static int across_dev(atsc_ctx *ctx, const QueryInput *in, int n_in, uint64_t n_
                 return fail_in(ctx, ATSC_E_INVALID, CALL, "internal error (position outside the pieces)");
             const uint64_t je = std::min(m[i], (pcs[p].second * T - 1 - b) / stride + 1);  // positions in front of the piece's end
             for (; j < je; j += ACR_TASK)
-                tk.push_back(PT{(uint32_t)p, DevRollTask{b + j * stride, rec + j, (uint32_t)std::min<uint64_t>(ACR_TASK, je - j), 0}});
+                tk.push_back({(uint32_t)p, DevRollTask{b + j * stride, rec + j, (uint32_t)std::min<uint64_t>(ACR_TASK, je - j), 0}});
             j = je;
         }
         rec += m[i];
     }
-    auto by_piece = [](const PT &x, const PT &y) { return x.piece < y.piece; };
-    if (P > 1 && !std::is_sorted(tk.begin(), tk.end(), by_piece)) std::stable_sort(tk.begin(), tk.end(), by_piece);
     std::vector<DevRollTask> tasks;
-    tasks.reserve(tk.size());
-    std::vector<size_t> at(P + 1, 0);
-    for (const PT &x : tk) { tasks.push_back(x.t); ++at[x.piece + 1]; }
-    for (size_t p = 0; p < P; ++p) at[p + 1] += at[p];
-    std::vector<PT>().swap(tk);
+    std::vector<size_t> at;
+    group_tasks(tk, P, tasks, at);
     // decode tasks of every piece, once per input
     std::vector<DecodeTasks> D(n_in);
-    std::vector<std::vector<PieceDecode>> pdec(n_in, std::vector<PieceDecode>(P));
-    for (int k = 0; k < n_in; ++k) {
-        size_t ci = 0;
-        for (size_t p = 0; p < P; ++p)
-            if (!emit_piece_decode(in[k].dp, in[k].org, cov, ci, pcs[p].first * T, pcs[p].second * T, region, D[k], pdec[k][p]))
-                return fail_in(ctx, ATSC_E_INVALID, CALL, "internal error (spill slots)");
-    }
-    // every input's region and behind it the spill slots it uses; region and MAX_FRAME are even numbers of doubles, so
-    // every region begins at a multiple of 16 bytes, as the position kernel's 16-byte loads need
-    std::vector<uint64_t> reg(n_in);
-    uint64_t scr_n = 0;
-    for (int k = 0; k < n_in; ++k) {
-        reg[k] = scr_n;
-        scr_n += region + (uint64_t)MAX_FRAME * D[k].spills_used;
-    }
+    std::vector<std::vector<PieceDecode>> pdec(n_in);
+    for (int k = 0; k < n_in && !rc; ++k) rc = emit_pieces_decode(ctx, CALL, in[k].dp, in[k].org, cov, pcs, T, region, D[k], pdec[k]);
+    if (rc) return rc;
+    std::vector<uint64_t> reg(n_in);  // the regions' places in the scratch: a table of the upload
+    const uint64_t scr_n = place_regions(D.data(), n_in, region, reg.data());
     QueryRes &R = in[0].dp->res[K.kind];
     HIPCHK(ctx, R.wait());
     Upload up;
     for (int k = 0; k < n_in; ++k) D[k].place(up);
     const size_t off_tasks = up.add(tasks), off_reg = up.add(reg);
     const size_t off_table = K.table_bytes ? up.add(K.table, K.table_bytes) : 0;
-    HIPCHK(ctx, R.reserve(ctx, up.up_bytes, up.bytes, scr_n));
+    rc = stage_upload(ctx, R, up, scr_n, s);
+    if (rc) return rc;
     unsigned char *d = R.d;
-    up.stage(R.h);
-    HIPCHK(ctx, hipMemcpyAsync(d, R.h, up.up_bytes, hipMemcpyHostToDevice, s));
     const DevRollTask *d_tasks = (const DevRollTask *)(d + off_tasks);
     for (size_t p = 0; p < P; ++p) {
         for (int k = 0; k < n_in; ++k) {
@@ -2744,9 +2691,8 @@ static int across_dev(atsc_ctx *ctx, const QueryInput *in, int n_in, uint64_t n_
             rc = launch_piece_decode(ctx, in[k].dp, in[k].d_body, d, D[k], pdec[k][p], scr, scr, scr, s, K.who);
             if (rc) return rc;
         }
-        const hipError_t e = K.launch(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), R.scratch, (const uint64_t *)(d + off_reg),
-                                      pcs[p].first * T, d + off_table, d_out, s);
-        if (e != hipSuccess) return fail(ctx, ATSC_E_HIP, K.launch_name, e);
+        LAUNCHCHK(ctx, K.launch_name, K.launch(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), R.scratch,
+                                               (const uint64_t *)(d + off_reg), pcs[p].first * T, d + off_table, d_out, s));
     }
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;

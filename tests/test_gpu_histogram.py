@@ -232,7 +232,25 @@ def test_non_finite_values(A, ctx, torch):
     assert list(_host(ctx, recs, [(at[13], 300)], [-inf, inf], M.RIGHT_CLOSED)[0]) == [300, 0, 0, 0]
 
 
-def test_independence(A, ctx, torch, mixed):
+@pytest.fixture(scope="module")
+def gaps(A, ctx):
+    """150 Constant records of 4000 samples, each with a value of its own: 600000 samples that cost nothing to decode"""
+    n, fl = 600000, 4000
+    recs, _, _, _ = ctx.compress_host(np.repeat(np.arange(n // fl, dtype=np.float64), fl), H.frame_offsets(n, fl), A.CONSTANT,
+                                      False, 0.0, 0)
+    full = ctx.decompress_host(recs)
+    assert len(full) == n and len(np.unique(full)) == n // fl
+    return recs, full
+
+
+# Windows that leave gaps.  Under the least budget (runs of covered ranges less than 64 * 2048 = 131072 samples apart,
+# cut every 65536 samples): [1000, 6000) and [106000, 206000) lie 100000 apart and share a run of 205000 samples, four
+# pieces from sample 1000 on, of which the first ends in the gap; [400000, 403000) begins 194000 behind that run and
+# [590000, 600000) 187000 behind that: a run each.  One window lies across the piece boundary at 1000 + 2 * 65536.
+GAP_WINS = [(1000, 5000), (106000, 100000), (1000 + 2 * 65536 - 100, 200), (300000, 0), (400000, 3000), (590000, 10000)]
+
+
+def test_independence(A, ctx, torch, mixed, gaps):
     full = ctx.decompress_host(mixed)
     total = len(full)
     rng = np.random.default_rng(29)
@@ -269,6 +287,18 @@ def test_independence(A, ctx, torch, mixed):
         assert np.array_equal(small_dev, alone), budget
         _check(full, probe, edges, M.RIGHT_CLOSED, small_right, budget)
     assert np.array_equal(_host(ctx, mixed, probe, edges), alone)  # repeated
+    # the least budget over windows that leave gaps (GAP_WINS): runs of pieces, a piece that ends between two windows
+    recs, full = gaps
+    edges = np.array([2.0, 26.5, 33.0, 100.0, 148.0])
+    whole = _host(ctx, recs, GAP_WINS, edges)
+    _check(full, GAP_WINS, edges, M.LEFT_CLOSED, whole, "gaps")
+    ctx.set_aggregate_scratch(1)
+    try:
+        small = _host(ctx, recs, GAP_WINS, edges)
+        small_dev = _dev(A, ctx, torch, recs, GAP_WINS, edges)
+    finally:
+        ctx.set_aggregate_scratch(0)
+    assert np.array_equal(small, whole) and np.array_equal(small_dev, whole)
 
 
 def test_validation(A, ctx, torch):

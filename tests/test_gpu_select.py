@@ -15,6 +15,7 @@ from tests import helpers as H
 from tests import select_model as M
 from tests.test_gpu_delta import (LARGE, PIECE, SMALL, A, _idw_record, _rec, _run, _seam_windows,  # noqa: F401
                                   _windows, ctx, decoded, large, mixed, torch)
+from tests.test_gpu_histogram import GAP_WINS, gaps  # noqa: F401  (windows that leave gaps, and their stream)
 
 pytestmark = pytest.mark.gpu
 
@@ -217,12 +218,12 @@ def test_truncation(A, ctx, torch, decoded):
     dp.close()
 
 
-@pytest.mark.parametrize("which", ["mixed", "large", "placed"])
-def test_pieces(A, ctx, torch, decoded, placed, which):
-    """the least budget: pieces of 65536 samples, counted from the first covered sample (0 here: the whole stream is one
-    of the windows).  The write step decodes every piece again; the default budget's result bit for bit, by the host call
-    and repeatedly on one plan"""
-    recs, full = placed if which == "placed" else decoded[which]
+@pytest.mark.parametrize("which", ["mixed", "large", "placed", "gaps"])
+def test_pieces(A, ctx, torch, decoded, placed, gaps, which):
+    """the least budget: pieces of 65536 samples, counted from the first covered sample (0: the whole stream is one of
+    the windows, but for "gaps", where they are counted from the first sample of every run of windows).  The write step
+    decodes every piece again; the default budget's result bit for bit, by the host call and repeatedly on one plan"""
+    recs, full = placed if which == "placed" else gaps if which == "gaps" else decoded[which]
     total = len(full)
     rng = np.random.default_rng(31)
     wins = [(0, total), (PIECE, 1), (PIECE, 2), (PIECE - 10, 10), (0, PIECE), (PIECE - 1, 2), (PIECE - 1, 1), (PIECE - 2, 2),
@@ -232,6 +233,8 @@ def test_pieces(A, ctx, torch, decoded, placed, which):
                  (3 * PIECE - 1, 3)]
         wins += [(int(b), int(rng.integers(0, 150000))) for b in rng.integers(0, total - 150000, 6)]
     wins += [(int(b), 60) for b in rng.integers(PIECE - 100, PIECE + 100, 10)]
+    if which == "gaps":
+        wins = GAP_WINS
     conds = [(M.EQ, 1.0), (M.GT, -inf)] if which == "placed" else [(M.GT, float(np.median(full))), (M.GT, -inf)]
     for op, limit in conds:
         alone = _host(ctx, recs, wins, op, limit)
