@@ -285,7 +285,8 @@ __global__ __launch_bounds__(64 * W) void k_decompress(
                         sv = v0 * (1.0 - nt) + v1 * nt;
                     }
                 }
-                double o = div1e5(round(sv * 100000.0));  // utils/mod.rs:66-74 (min first)
+                // (the division itself, utils/mod.rs:66-74: +-inf stays +-inf for the clamp, a zero keeps its sign)
+                double o = round(sv * 100000.0) / 100000.0;
                 if (o < mn) o = mn;
                 else if (o > mx) o = mx;
                 out[i - j0] = o;

@@ -632,6 +632,12 @@ DEVI double div1e5(double r)
     const double rem = fma(-q, 100000.0, r);
     return fma(rem, y, q);
 }
+// A product x * 1e5 that overflowed: round(+-inf) / 1e5 is +-inf in the reference (and round_and_limit_f64 then clamps
+// it to max / min), while div1e5's residual step makes it NaN (inf - inf).  Reached only from values of about 1.8e303
+// and more, so every caller applies it behind a uniform test of the frame's range (|min|, |max| >= 1e150, or not
+// finite): `wide`.  r: the rounded product, o: div1e5(r).
+DEVI bool wide_range(double mn, double mx) { return !(fabs(mn) < 1e150 && fabs(mx) < 1e150); }
+DEVI double div1e5_fix(double r, double o, bool wide) { return (wide && isinf(r)) ? r : o; }
 
 // 1 / |g| for the MAPE weights (utils/error.rs:104-116 divides by |g|; the product form is within
 // an ulp of it).  v_rcp_f64 + two Newton steps instead of the ~30-instruction IEEE divide, for
@@ -647,6 +653,35 @@ DEVI double recip_abs(double g)
         return r;
     }
     return 1.0 / a;
+}
+// |o - g| / |g| where the weight is not kept: recip_abs's product inside its range, outside it the division itself, as
+// the reference writes it (1 / |g| overflows for subnormal g, and |o - g| * inf is inf where the quotient is finite)
+DEVI double mape_term(double o, double g)
+{
+    const double a = fabs(g), d = fabs(o - g);
+    return (a > 1e-290 && a < 1e290) ? d * recip_abs(g) : d / a;
+}
+// A frame whose range reaches within 1e-290 of zero: only such a frame can hold a subnormal sample, whose 1 / |g|
+// overflows (|g| < 2^-1024), and |o - g| * inf is inf where the reference's |(o - g) / g| is finite.
+DEVI bool tiny_range(double mn, double mx) { return !(mn > 1e-290 || mx < -1e-290); }
+// k_compress's slow sides (a frame with |min| or |max| from 1e150, 1e30f for the FFT candidate, or with a subnormal sample): one
+// error term as the reference writes it -- round_and_limit_f64 (utils/mod.rs:66-74: x * 1e5 may overflow to +-inf, which
+// the clamp takes to max / min) or FFT::round (fft.rs:208-218, max first), then utils/error.rs:112's division.  Two
+// IEEE divides and no branch: beside the fast sides they cost the instantiations no register (an isinf / subnormal
+// fix-up of the fast forms did: 18 -> 28 spilled SGPRs in k_compress<1,5,false,256>, 1.6 % on the headline).
+DEVI double spline_term_slow(double sv, double mn, double mx, double g)
+{
+    double o = round(sv * 100000.0) / 100000.0;
+    if (o < mn) o = mn;
+    else if (o > mx) o = mx;
+    return fabs((o - g) / g);
+}
+DEVI double fft_term_slow(float v, double mn, double mx, double g)
+{
+    double o = round((double)v * 100000.0) / 100000.0;
+    if (o > mx) o = mx;
+    if (o < mn) o = mn;
+    return fabs((o - g) / g);
 }
 
 // --------------------------------------------------------------------------------------------

@@ -525,6 +525,15 @@ __device__ __forceinline__ void compress_frame(
         split_n(smin, mini, fz);
         bitdepth = fr_any ? 0u : bitdepth_of(maxi, mini);
     }
+    // A nonzero sample whose reciprocal overflows (|g| < 2^-1024; looked for as: subnormal) sends the error terms to
+    // the slow sides below.  Only a frame whose range reaches within 1e-290 of zero can hold one, and only such a frame
+    // is searched: one walk and one OR.  Frames that contain a zero or straddle it without one keep the fast sides.
+    bool has_sub = false;
+    if (tiny_range(smin, smax)) {
+        uint32_t sb = 0;
+        for_strided<FN, T, SPL>(tid, n, [&](uint32_t j) { sb |= __builtin_amdgcn_class(xs[j], 0x90) ? 1u : 0u; });
+        has_sub = block_or_u32<W>(sb, red, parity) != 0;
+    }
 
     PH(1);
     if (!LEAN && prm.debug_stop == 1) return;
@@ -844,7 +853,8 @@ __device__ __forceinline__ void compress_frame(
                 // the (step, K, ...) of every trip come from the per-length table (DevPlan::pstep ...)
                 double2 *mm = (double2 *)AB;  // per-segment Hermite tangents (m0, m1); AB is free here
                 const double inv_n = P.inv_n;
-                const bool pfast = fabs(smin) < 1e150 && fabs(smax) < 1e150;  // no overflow/NaN out of the spline
+                // (a frame with a subnormal sample -- 1 / |g| overflows -- counts as slow too)
+                const bool pfast = !wide_range(smin, smax) && !has_sub;  // no overflow/NaN out of the spline
                 const bool nozero = smin > 0.0 || smax < 0.0;                  // every 1/|g| is finite
                 double cur = POLY2GO ? poly_cur : prm.max_err + 1.0;
                 while (round(cur * 10000.0) > prm.poly_q_hi) {  // polynomial.rs:231: target < round(err, 4)
@@ -886,10 +896,14 @@ __device__ __forceinline__ void compress_frame(
                                     }
                                 }
                                 const double sv = hit ? hitv : num / den;
-                                double o = div1e5(round(sv * 100000.0));
-                                if (o < smin) o = smin;
-                                else if (o > smax) o = smax;
-                                s += fabs(o - g[m]) * inv[m];
+                                if (!pfast) {
+                                    s += spline_term_slow(sv, smin, smax, g[m]);
+                                } else {
+                                    double o = div1e5(round(sv * 100000.0));
+                                    if (o < smin) o = smin;
+                                    else if (o > smax) o = smax;
+                                    s += fabs(o - g[m]) * inv[m];
+                                }
                             }
                         }
                         s = block_sum_f64<W>(s, red, parity);
@@ -975,13 +989,10 @@ __device__ __forceinline__ void compress_frame(
                                     sv = v0 * (1.0 - nt) + v1 * nt;
                                 }
                             }
+                            // (the slow side -- sv * 1e5 or 1 / |g| may overflow -- is the reference's arithmetic as written)
+                            if (__builtin_expect(!pfast, 0)) return spline_term_slow(sv, smin, smax, g[m]);
                             double o = div1e5(round(sv * 100000.0));  // utils/mod.rs:66-74
-                            if (pfast) {
-                                o = fmin(fmax(o, smin), smax);  // o is finite: same as the compares
-                            } else {
-                                if (o < smin) o = smin;
-                                else if (o > smax) o = smax;
-                            }
+                            o = fmin(fmax(o, smin), smax);  // o is finite: same as the compares
                             return fabs(o - g[m]) * inv[m];
                         };
                         // Every term is >= 0 and, with a finite range and no zero sample, finite: the sum
@@ -1222,7 +1233,8 @@ __device__ __forceinline__ void compress_frame(
             const double Ld = (double)L;
             // min/max far from f32 overflow: no NaN can come out of the transform, so the clamp is a plain
             // min(max()) (a NaN sample still poisons the sum through o - g); otherwise compare-select
-            const bool fast_clamp = fabsf(mxf) < 1e30f && fabsf(mnf) < 1e30f;
+            // (nor does 1 / |g| overflow: no subnormal sample)
+            const bool fast_clamp = fabsf(mxf) < 1e30f && fabsf(mnf) < 1e30f && !has_sub;
             const double invL = 1.0 / Ld;
             const uint32_t magicL = FIX ? (uint32_t)(0x100000000ull / (FIX ? cL : 1)) + 1u : P.magicL;
             uint32_t used = 0, jump = 0, big = 0;
@@ -1409,7 +1421,7 @@ __device__ __forceinline__ void compress_frame(
                 double s = 0.0;
                 // fft.rs:208-218.  v is an f32, so v * 1e5 is exact (<= 41 significant bits) and
                 // round-half-away equals trunc(x + copysign(0.5, x)) (checked over the f32 range)
-                if (fast_clamp) {
+                if (__builtin_expect(fast_clamp, 1)) {
                     // every o is finite, and the lanes beyond L carry g = 1, 1/|g| = 0: no guard
 #pragma unroll
                     for (int m = 0; m < SPL; ++m) {
@@ -1421,13 +1433,7 @@ __device__ __forceinline__ void compress_frame(
                 } else {
 #pragma unroll
                     for (int m = 0; m < SPL; ++m) {
-                        if (tid + m * T < L) {
-                            const double x5 = (double)(acc[m] + dc) * 100000.0;
-                            double o = div1e5(trunc(x5 + copysign(0.5, x5)));
-                            if (o > mxd) o = mxd;
-                            if (o < mnd) o = mnd;
-                            s += fabs(o - g[m]) * inv[m];
-                        }
+                        if (tid + m * T < L) s += fft_term_slow(acc[m] + dc, mnd, mxd, g[m]);
                     }
                 }
                 s = block_sum_f64<W>(s, red, parity);

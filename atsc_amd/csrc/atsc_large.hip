@@ -910,7 +910,7 @@ __global__ __launch_bounds__(PT) void k_large_pre23(const double *__restrict__ s
     uint32_t zeros = 0;
     auto finish = [&](uint32_t k, float2 z) {
         spec[k] = z;
-        nbits[k] = __float_as_uint((float)sqrt((double)z.x * (double)z.x + (double)z.y * (double)z.y));
+        nbits[k] = __float_as_uint((float)fabs(sqrt((double)z.x * (double)z.x + (double)z.y * (double)z.y)));  // (fabs: a NaN keeps no sign bit)
         zeros += (z.x != 0.0f || z.y != 0.0f) ? 0u : 1u;
         if (dense) Xs[k] = make_float2(0.0f, 0.0f);  // the dense ladder's admitted spectrum
     };
@@ -1205,7 +1205,8 @@ __global__ __launch_bounds__(LT) void k_large_poly1(const double *__restrict__ s
                 sv = v0[u] * (1.0 - nt) + v1[u] * nt;
             }
         }
-        double o = div1e5(round(sv * 100000.0));
+        const double r5 = round(sv * 100000.0);
+        double o = div1e5_fix(r5, div1e5(r5), wide_range(smin, smax));
         if (o < smin) o = smin;
         else if (o > smax) o = smax;
         s += fabs((o - g[u]) / g[u]);
@@ -1664,7 +1665,8 @@ __device__ __forceinline__ void compress_large_frame(
                             }
                             sv = num / den;
                         }
-                        double o = div1e5(round(sv * 100000.0));
+                        const double r5 = round(sv * 100000.0);
+                        double o = div1e5_fix(r5, div1e5(r5), wide_range(smin, smax));
                         if (o < smin) o = smin;
                         else if (o > smax) o = smax;
                         const double g = xs[i];
@@ -1759,7 +1761,8 @@ __device__ __forceinline__ void compress_large_frame(
                                     sv = v0[u] * (1.0 - nt) + v1[u] * nt;
                                 }
                             }
-                            double o = div1e5(round(sv * 100000.0));
+                            const double r5 = round(sv * 100000.0);
+                            double o = div1e5_fix(r5, div1e5(r5), wide_range(smin, smax));
                             if (o < smin) o = smin;
                             else if (o > smax) o = smax;
                             s += fabs((o - g[u]) / g[u]);
@@ -1865,7 +1868,7 @@ __device__ __forceinline__ void compress_large_frame(
                 uint32_t nz = 0;
                 for (uint32_t k = tid; k < bins; k += T) {
                     const float2 z = spec[k];
-                    nbits[k] = __float_as_uint((float)sqrt((double)z.x * (double)z.x + (double)z.y * (double)z.y));
+                    nbits[k] = __float_as_uint((float)fabs(sqrt((double)z.x * (double)z.x + (double)z.y * (double)z.y)));  // (fabs: a NaN keeps no sign bit)
                     nz += (z.x != 0.0f || z.y != 0.0f) ? 1u : 0u;
                     if (!(prm.sparse_inv && P.sp_mf)) Xs[k] = make_float2(0.0f, 0.0f);
                 }
@@ -2171,7 +2174,7 @@ __device__ __forceinline__ void compress_large_frame(
                             double o = div1e5(round(v * 100000.0));
                             if (o > mxd) o = mxd;
                             if (o < mnd) o = mnd;
-                            s += fabs(o - g) * recip_abs(g);  // the product form, as in k_compress
+                            s += mape_term(o, g);
                         },
                         prm.debug_stop >= 16 ? (uint32_t)prm.debug_stop - 16u : 0u);
                 } else {
@@ -2473,7 +2476,7 @@ __global__ __launch_bounds__(LT) void k_large_trip_tiles(
             double o = div1e5(round(v * 100000.0));
             if (o > mxd) o = mxd;
             if (o < mnd) o = mnd;
-            s += fabs(o - g) * recip_abs(g);
+            s += mape_term(o, g);
         });
     int parity = 0;
     s = block_sum_f64<LW>(s, red, parity);
@@ -2947,7 +2950,8 @@ __device__ __forceinline__ void decompress_large_frame(
                         sv = v0 * (1.0 - nt) + v1 * nt;
                     }
                 }
-                double o = div1e5(round(sv * 100000.0));
+                // (the division itself, utils/mod.rs:66-74: +-inf stays +-inf for the clamp, a zero keeps its sign)
+                double o = round(sv * 100000.0) / 100000.0;
                 if (o < mn) o = mn;
                 else if (o > mx) o = mx;
                 out[i] = o;

@@ -408,7 +408,8 @@ DEVI void poly1_piece(const double *xs, const DevPlan &P, unsigned char *ws, con
                     sv = v0[u] * (1.0 - nt) + v1[u] * nt;
                 }
             }
-            double o = div1e5(round(sv * 100000.0));
+            const double r5 = round(sv * 100000.0);
+            double o = div1e5_fix(r5, div1e5(r5), wide_range(smin, smax));
             if (o < smin) o = smin;
             else if (o > smax) o = smax;
             s += fabs((o - g[u]) / g[u]);
@@ -541,7 +542,7 @@ __global__ __launch_bounds__(RT) void k_large_rows9p(const double *__restrict__ 
         const bool dense = !((sparse_inv & 1) && Pl->sp_mf);
         auto finish = [&](uint32_t k, float2 z) {
             spec[k] = z;
-            nbits[k] = __float_as_uint((float)sqrt((double)z.x * (double)z.x + (double)z.y * (double)z.y));
+            nbits[k] = __float_as_uint((float)fabs(sqrt((double)z.x * (double)z.x + (double)z.y * (double)z.y)));  // (fabs: a NaN keeps no sign bit)
             zeros += (z.x != 0.0f || z.y != 0.0f) ? 0u : 1u;
             if (dense) Xs[k] = make_float2(0.0f, 0.0f);
         };
@@ -660,7 +661,7 @@ __global__ __launch_bounds__(RT) void k_large_rows_thread(const double *__restri
     uint32_t zeros = 0;
     auto finish = [&](uint32_t k, float2 v) {
         spec[k] = v;
-        nbits[k] = __float_as_uint((float)sqrt((double)v.x * (double)v.x + (double)v.y * (double)v.y));
+        nbits[k] = __float_as_uint((float)fabs(sqrt((double)v.x * (double)v.x + (double)v.y * (double)v.y)));  // (fabs: a NaN keeps no sign bit)
         zeros += (v.x != 0.0f || v.y != 0.0f) ? 0u : 1u;
         if (dense) Xs[k] = make_float2(0.0f, 0.0f);
     };

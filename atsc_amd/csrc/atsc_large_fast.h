@@ -970,7 +970,8 @@ __global__ __launch_bounds__(TT) void k_large_trip243(
                         sv = v0 * (1.0 - nt) + v1 * nt;
                     }
                 }
-                double o = div1e5(round(sv * 100000.0));
+                // (the division itself, utils/mod.rs:66-74: +-inf stays +-inf for the clamp, a zero keeps its sign)
+                double o = round(sv * 100000.0) / 100000.0;
                 if (o < mn) o = mn;
                 else if (o > mx) o = mx;
                 out[i] = o;
@@ -1131,7 +1132,7 @@ __global__ __launch_bounds__(TT) void k_large_trip243(
             double o = div1e5(round(v * 100000.0));
             if (o > mxd) o = mxd;
             if (o < mnd) o = mnd;
-            s += fabs(o - gg) * recip_abs(gg);
+            s += mape_term(o, gg);
         };
         auto gload = [&](uint32_t m, double2 (&g)[9]) {
 #pragma unroll

@@ -194,7 +194,18 @@ int atsc_ctx_set_profiling(atsc_ctx *ctx, int on);
 int atsc_ctx_profile_read(atsc_ctx *ctx, double *total_ms, uint64_t *launches);
 
 /* Host-pointer convenience: plan + H2D + compress + D2H, synchronous.
- * body_len receives the number of bytes written to `body`. */
+ * body_len receives the number of bytes written to `body`.
+ *
+ * Sample domain (this call and every compress entry point above; tests/test_gpu_extreme_values.py pins it).  Any f64
+ * bit pattern is accepted: no sample value is used as an index.  Finite samples of any magnitude, subnormal numbers
+ * included, give the reference's codec choice, bytes and reported error, with one exception: a frame whose f32
+ * transform can overflow (the sum of its |samples| as f32 reaches FLT_MAX / 2, about 1e36 per sample at 256 samples)
+ * has an FFT candidate whose bins and error depend on the order of the f32 additions, here as between two builds of
+ * the reference; the record is still well formed, and Polynomial / RLE / Constant / Noop stay exact.  Samples beyond
+ * f32 range convert to infinity as the reference's `as f32` does (all of them: the 10-byte FFT payload).  NaN and
+ * +-Inf samples are not cleaned here (atsc_compress_data drops them first, as the reference's front end does): the
+ * exact codecs and the Polynomial / IDW payloads equal the reference's, the lossy errors are NaN, so AUTO takes RLE;
+ * forced FFT returns a well-formed record whose bins are NaN or infinite. */
 int atsc_compress_frames(atsc_ctx *ctx, const double *samples, const uint64_t *frame_off,
                          uint64_t n_frames, int compressor, int bounded, float max_error,
                          int sample_level, uint8_t *body, uint64_t body_cap, uint64_t *body_len,

@@ -45,6 +45,28 @@ def _near_threshold(err, max_error):
     return any(abs(err - c) < BOUNDARY_EPS for c in cands)
 
 
+def same_class(a, b):
+    """Non-finite values match by class: both NaN, or the same infinity."""
+    if np.isnan(a) or np.isnan(b):
+        return bool(np.isnan(a) and np.isnan(b))
+    return a == b
+
+
+def differs(a, b, tol):
+    """|a - b| > tol for finite values; a non-finite value matches only its own class (abs(nan - x) > tol is False:
+    a NaN would otherwise match anything)."""
+    if not (np.isfinite(a) and np.isfinite(b)):
+        return not same_class(a, b)
+    return abs(a - b) > tol
+
+
+def _finite_scale(freqs):
+    """Largest finite |bin| of a frame (the coefficient tolerance's yardstick); 1.0 when there is none."""
+    nr = [float(np.hypot(r, i)) for _, r, i in freqs]
+    nr = [v for v in nr if np.isfinite(v)]
+    return max(nr) if nr else 1.0
+
+
 def compare_frame(oracle, x, max_error, tag, payload, chosen_o, payload_o, report, idx,
                   oracle_errs=None):
     """Returns 'exact' | 'tol' | 'tie' | 'boundary' | 'FAIL:<why>'."""
@@ -59,7 +81,7 @@ def compare_frame(oracle, x, max_error, tag, payload, chosen_o, payload_o, repor
         return "FAIL:bytes differ for codec %d (len %d vs %d)" % (tag, len(payload), len(payload_o))
     fg, mxg, mng = H.parse_fft_payload(payload)
     fo, mxo, mno = H.parse_fft_payload(payload_o)
-    if (mxg, mng) != (mxo, mno):
+    if not (same_class(mxg, mxo) and same_class(mng, mno)):
         return "FAIL:fft min/max"
     if len(fg) != len(fo):
         errs = oracle_errs or {}
@@ -70,13 +92,13 @@ def compare_frame(oracle, x, max_error, tag, payload, chosen_o, payload_o, repor
         # over the common length the norms agree in order while the position sets do not.
         m = min(len(fg), len(fo))
         if m and set(f[0] for f in fg[:m]) != set(f[0] for f in fo[:m]):
-            sc = max(np.hypot(r, i) for _, r, i in (fo if len(fo) >= len(fg) else fg))
+            sc = _finite_scale(fo if len(fo) >= len(fg) else fg)
             ng = [np.hypot(r, i) for _, r, i in fg[:m]]
             no = [np.hypot(r, i) for _, r, i in fo[:m]]
-            if max(abs(a - b) for a, b in zip(ng, no)) <= FFT_COEF_RTOL * sc:
+            if not any(differs(a, b, FFT_COEF_RTOL * sc) for a, b in zip(ng, no)):
                 return "tie"
         return "FAIL:fft K gpu=%d oracle=%d" % (len(fg), len(fo))
-    scale = max(np.hypot(r, i) for _, r, i in fo) if fo else 1.0
+    scale = _finite_scale(fo)
     pos_g = [f[0] for f in fg]
     pos_o = [f[0] for f in fo]
     if pos_g != pos_o:
@@ -88,13 +110,13 @@ def compare_frame(oracle, x, max_error, tag, payload, chosen_o, payload_o, repor
             no = {p: np.hypot(r, i) for p, r, i in fo}
             diff = set(pos_g) ^ set(pos_o)
             norms = [ng.get(p, no.get(p)) for p in diff]
-            if max(norms) - min(norms) > FFT_COEF_RTOL * scale:
+            if not all(np.isfinite(v) for v in norms) or max(norms) - min(norms) > FFT_COEF_RTOL * scale:
                 return "FAIL:fft bin set differs %s" % sorted(diff)
             return "tie"  # different (tied) bins admitted: the reconstructions, hence the errors, differ"
         for (a, ra, ia), (b, rb, ib) in zip(fg, fo):
             if a != b:
                 na, nb = np.hypot(ra, ia), np.hypot(rb, ib)
-                if abs(na - nb) > FFT_COEF_RTOL * scale:
+                if differs(na, nb, FFT_COEF_RTOL * scale):
                     return "FAIL:fft order"
 
     # A stored position can occur twice: `pos as u16` (fft.rs:242) folds bin p + 65536 of a 131072-sample frame onto p,
@@ -111,10 +133,10 @@ def compare_frame(oracle, x, max_error, tag, payload, chosen_o, payload_o, repor
     for key, (r, i) in do.items():
         if key in dg:
             rg, ig = dg[key]
-            if abs(rg - r) > FFT_COEF_RTOL * scale or abs(ig - i) > FFT_COEF_RTOL * scale:
+            if differs(rg, r, FFT_COEF_RTOL * scale) or differs(ig, i, FFT_COEF_RTOL * scale):
                 # the two occurrences of a folded position may have swapped (near-equal norms): try the other one
                 alt = dg.get((key[0], 1 - key[1])) if key[1] < 2 else None
-                if alt is not None and abs(alt[0] - r) <= FFT_COEF_RTOL * scale and abs(alt[1] - i) <= FFT_COEF_RTOL * scale:
+                if alt is not None and not differs(alt[0], r, FFT_COEF_RTOL * scale) and not differs(alt[1], i, FFT_COEF_RTOL * scale):
                     continue
                 return "FAIL:fft coef pos=%d gpu=(%r,%r) oracle=(%r,%r) scale=%r" % (
                     key[0], rg, ig, r, i, scale)
@@ -173,7 +195,7 @@ def compare_batch(oracle, ctx, x, off, compressor, bounded, max_error, level=0, 
             # still held together, with the tolerance widened by the decode bar's full noise term (TIE_ERR_FACTOR x).
             if tag == oracle.FFT and chosen_same_k(payload, po):
                 tol = TIE_ERR_FACTOR * (FFT_ERR_ATOL + FFT_ERR_RTOL * abs(eo) + fft_err_noise(fx)) + tie_swap_bound(payload, po, fx)
-                if not (abs(err[i] - eo) <= tol or (np.isnan(err[i]) and np.isnan(eo))):
+                if differs(err[i], eo, tol):
                     summary["fail"].append((i, "FAIL:err of a tie frame gpu=%r oracle=%r tol=%r" % (err[i], eo, tol)))
         else:
             summary[verdict] += 1
@@ -183,7 +205,7 @@ def compare_batch(oracle, ctx, x, off, compressor, bounded, max_error, level=0, 
                 # reported error: exact codecs report 0.0; lossy within tolerance
                 tol = (FFT_ERR_ATOL + FFT_ERR_RTOL * abs(eo) + fft_err_noise(fx)) if tag == oracle.FFT \
                     else max(POLY_ERR_RTOL * abs(eo), 1e-300)
-                if not (err[i] == eo or abs(err[i] - eo) <= tol or (np.isnan(err[i]) and np.isnan(eo))):
+                if err[i] != eo and differs(err[i], eo, tol):
                     summary["fail"].append((i, "FAIL:err gpu=%r oracle=%r" % (err[i], eo)))
     return summary
 
