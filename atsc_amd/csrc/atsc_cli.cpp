@@ -5,7 +5,8 @@
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
 //        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S]]
-//        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]]]
+//        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]
+//        [--across-extremes K]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -92,6 +93,11 @@ void usage()
             "                                 every row's sample index, NaN samples left out: one column q<Q> per level\n"
             "                                 behind mean, NaN where every stream's sample is NaN\n"
             "      --across-quantile-method <M>  linear | lower | higher | nearest [default: linear]\n"
+            "      --across-extremes <K>      with --across: also the K (1..16) largest and the K smallest of the streams' samples\n"
+            "                                 at every row's sample index and the streams that hold them (of equal values the\n"
+            "                                 first in the list first), NaN samples left out and counted: nans,top1,top1_at,..,\n"
+            "                                 topK,topK_at,bottom1,bottom1_at,..,bottomK,bottomK_at behind the columns above,\n"
+            "                                 the cells of unused entries empty\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -187,11 +193,13 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
         if (!a.q.across.empty()) {  // (with --samples) the window's across records over this file and the listed ones, no .wbro
             std::vector<atsc_across_record> rows;
             std::vector<double> levels;
+            std::vector<uint64_t> extremes;
             rc = atsc_bro_open(bro, len, nullptr, nullptr);
-            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, levels);
+            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, levels, extremes);
             atsc_free(bro);
             if (rc) return rc;
-            const bool ok = across_write(with_ext(path, "across.csv"), rows, a.q.across_stride, a.q.across_level_names, levels);
+            const bool ok = across_write(with_ext(path, "across.csv"), rows, a.q.across_stride, a.q.across_level_names, levels,
+                                         (uint32_t)a.q.across_extremes, extremes);
             return ok ? ATSC_OK : ATSC_E_IO;
         }
         double *out = nullptr;

@@ -82,6 +82,7 @@ struct BucketOptions {
     std::vector<std::string> across_level_names;
     int across_method = ATSC_QUANTILE_LINEAR;  // --across-quantile-method
     bool have_across_method = false;
+    int across_extremes = 0;  // --across-extremes K: nans,top1,top1_at,..,topK,topK_at,bottom1,bottom1_at,..,bottomK,bottomK_at
 };
 
 // --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
@@ -317,6 +318,11 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             return 2;
         }
         o.have_across_method = true;
+    } else if (o.across_allowed && value("--across-extremes")) {
+        if (!parse_int(v, 1, ATSC_EXTREMES_MAX_K, o.across_extremes)) {
+            fprintf(stderr, "error: invalid value '%s' for '--across-extremes': expected 1..=%d\n", v.c_str(), (int)ATSC_EXTREMES_MAX_K);
+            return 2;
+        }
     } else {
         return 0;
     }
@@ -381,8 +387,8 @@ bool rolling_option_complete(const BucketOptions &o, const char *window, bool wi
 }
 
 // --across goes with the option that names the window and without the one that cuts buckets, --rolling and --where;
-// --across-stride and --across-quantiles go with --across, --across-quantile-method with --across-quantiles.  false: a
-// usage error, reported on stderr.
+// --across-stride, --across-quantiles and --across-extremes go with --across, --across-quantile-method with
+// --across-quantiles.  false: a usage error, reported on stderr.
 bool across_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
 {
     if (o.have_across_method && o.across_levels.empty()) {
@@ -392,7 +398,8 @@ bool across_option_complete(const BucketOptions &o, const char *window, bool win
     if (o.across.empty()) {
         if (o.have_across_stride) fprintf(stderr, "error: '--across-stride' needs '--across'\n");
         else if (!o.across_levels.empty()) fprintf(stderr, "error: '--across-quantiles' needs '--across'\n");
-        return !o.have_across_stride && o.across_levels.empty();
+        else if (o.across_extremes) fprintf(stderr, "error: '--across-extremes' needs '--across'\n");
+        return !o.have_across_stride && o.across_levels.empty() && !o.across_extremes;
     }
     if (!windowed) {
         fprintf(stderr, "error: '--across' needs '%s'\n", window);
@@ -647,9 +654,10 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
 
 // --across: one record per position of the range [begin, begin + count) over the .bro image (stream 0) and the listed
 // files (stream 1 and on): sample i of each goes with sample i of the others.  levels: with --across-quantiles, the
-// same positions' rows of o.across_levels.size() levels
+// same positions' rows of o.across_levels.size() levels; extremes: with --across-extremes K, the same positions'
+// extremes records of k = K, ATSC_EXTREMES_BYTES(K) / 8 words each
 int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
-                 std::vector<atsc_across_record> &rows, std::vector<double> &levels)
+                 std::vector<atsc_across_record> &rows, std::vector<double> &levels, std::vector<uint64_t> &extremes)
 {
     std::vector<uint8_t *> image(o.across.size(), nullptr);
     std::vector<const uint8_t *> body{bro + 9};
@@ -678,6 +686,13 @@ int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOp
                                               &count, o.across_stride, n_q, o.across_levels.data(), o.across_method,
                                               levels.empty() ? &no_row : levels.data());
         }
+        if (!rc && o.across_extremes) {
+            extremes.assign(rows.size() * (ATSC_EXTREMES_BYTES(o.across_extremes) / 8), 0);
+            uint64_t no_record;
+            rc = atsc_across_extremes_windows(ctx, (uint32_t)body.size(), body.data(), body_len.data(), has_count.data(), 1, &begin,
+                                              &count, o.across_stride, (uint32_t)o.across_extremes,
+                                              extremes.empty() ? &no_record : extremes.data());
+        }
     }
     for (uint8_t *p : image) atsc_free(p);
     return rc;
@@ -686,14 +701,23 @@ int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOp
 // the .across.csv: offset,count,min,min_at,max,max_at,sum,mean and one row per position; offset: the position's sample
 // counted from the window's begin; values as the .agg.csv writes them; min_at and max_at (the stream's place in the
 // list, the input file 0) and mean = sum / count empty where count == 0.  names: with --across-quantiles, a column
-// q<level as typed> per level behind them, from the position's row of `levels`.  false: the file could not be written.
+// q<level as typed> per level behind them, from the position's row of `levels`.  k: with --across-extremes K, behind
+// those nans,top1,top1_at,..,topK,topK_at,bottom1,bottom1_at,..,bottomK,bottomK_at from the position's record of
+// `extremes`: the K largest and the K smallest samples and the streams that hold them, the cells of unused entries
+// empty.  false: the file could not be written.
 bool across_write(const std::string &path, const std::vector<atsc_across_record> &rows, uint64_t stride,
-                  const std::vector<std::string> &names, const std::vector<double> &levels)
+                  const std::vector<std::string> &names, const std::vector<double> &levels, uint32_t k,
+                  const std::vector<uint64_t> &extremes)
 {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return false;
     fprintf(f, "offset,count,min,min_at,max,max_at,sum,mean");
     for (const std::string &n : names) fprintf(f, ",q%s", n.c_str());
+    if (k) {
+        fprintf(f, ",nans");
+        for (uint32_t e = 0; e < k; ++e) fprintf(f, ",top%u,top%u_at", e + 1, e + 1);
+        for (uint32_t e = 0; e < k; ++e) fprintf(f, ",bottom%u,bottom%u_at", e + 1, e + 1);
+    }
     fprintf(f, "\n");
     for (size_t j = 0; j < rows.size(); ++j) {
         const atsc_across_record &r = rows[j];
@@ -702,6 +726,15 @@ bool across_write(const std::string &path, const std::vector<atsc_across_record>
                 debug_f64(r.max).c_str(), mx_at.c_str(), debug_f64(r.sum).c_str(),
                 r.count ? debug_f64(r.sum / (double)r.count).c_str() : "");
         for (size_t q = 0; q < names.size(); ++q) fprintf(f, ",%s", debug_f64(levels[j * names.size() + q]).c_str());
+        if (k) {
+            const uint64_t *rec = extremes.data() + j * (ATSC_EXTREMES_BYTES(k) / 8);
+            const atsc_extreme *x = (const atsc_extreme *)(rec + 2);
+            fprintf(f, ",%llu", (unsigned long long)((const atsc_window_extremes_head *)rec)->nans);
+            for (uint32_t e = 0; e < 2 * k; ++e) {
+                if (x[e].at == ATSC_EXTREMES_NONE) fprintf(f, ",,");
+                else fprintf(f, ",%s,%llu", debug_f64(x[e].value).c_str(), (unsigned long long)x[e].at);
+            }
+        }
         fprintf(f, "\n");
     }
     return fclose(f) == 0;

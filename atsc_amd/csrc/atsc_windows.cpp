@@ -103,6 +103,10 @@ __attribute__((weak)) hipError_t launch_across_quantile_positions(const DevRollT
                                                                   const uint64_t *reg, uint32_t n_streams, uint64_t a0,
                                                                   uint64_t stride, const double *q, uint32_t n_q, int method,
                                                                   double *out, hipStream_t s);
+// the windowed across extremes' position kernel (atsc_across_extremes.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_across_extremes_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
+                                                                  const uint64_t *reg, uint32_t n_streams, uint64_t a0,
+                                                                  uint64_t stride, uint32_t k, void *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -359,7 +363,8 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
                           BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
                           BY_ROLLING = DECODE_CALLER("rolling"), BY_ACROSS = DECODE_CALLER("across"),
-                          BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile");
+                          BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile"),
+                          BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -2573,7 +2578,7 @@ static int across_check(atsc_ctx *ctx, const char *call, uint32_t n_streams, uin
 }
 
 // What differs between the device calls that work on the N samples of a position (across_dev): the across and the
-// across quantiles.
+// across quantiles and the across extremes.
 struct AcrossKernel {
     const char *call;          // names the call in the messages
     const char *no_kernels;    // ATSC_E_UNSUPPORTED's message
@@ -2775,6 +2780,50 @@ struct AcrossQntQuery {
     }
 };
 
+// the across extremes' descriptor: the across' ranges, stride and record numbering, the windowed extremes' record (of k
+// entries per list) per position; k is checked as the windowed extremes check theirs and goes to the kernel by value.
+// The call keeps its tables and scratch in the across quantiles' place on in[0].dp (Q_ACROSS_QUANTILE): the two kinds of
+// call on one first plan wait for each other, and atsc_dplan stays as it is (DESIGN.md "Windowed across extremes")
+struct AcrossExtQuery {
+    static constexpr int INPUTS = 0;
+    static constexpr const char *CALL = "across_extremes_windows";
+    uint32_t n_streams;
+    uint64_t stride;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    uint32_t k;
+    int inputs() const { return (int)n_streams; }
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
+        return total * ATSC_EXTREMES_BYTES(std::min<uint32_t>(k, ATSC_EXTREMES_MAX_K));
+    }
+    int check(atsc_ctx *ctx) const
+    {
+        const int rc = across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, nullptr);
+        if (rc) return rc;
+        if (k == 0 || k > ATSC_EXTREMES_MAX_K) return fail_in(ctx, ATSC_E_INVALID, CALL, "k outside [1, 16]");
+        return ATSC_OK;
+    }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
+    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
+            void *stream) const
+    {
+        const int rc = check(ctx);
+        if (rc) return rc;
+        const uint32_t ns = n_streams, kk = k;
+        const uint64_t st = stride;
+        const AcrossKernel K{CALL, "no across extremes kernels", "launch k_across_extremes_positions", Q_ACROSS_QUANTILE,
+                             BY_ACROSS_EXTREMES, launch_across_extremes_positions != nullptr, nullptr, 0,
+                             [ns, st, kk](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg,
+                                          uint64_t a0, const void *, void *d_out, hipStream_t s) {
+                                 return launch_across_extremes_positions(tasks, n, scratch, reg, ns, a0, st, kk, d_out, s);
+                             }};
+        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
+    }
+};
+
 // what every across call checks of its lists before it reads them
 static bool across_lists(uint32_t n_streams, const void *const *a, const void *const *b)
 {
@@ -2835,6 +2884,33 @@ extern "C" int atsc_across_quantile_windows(atsc_ctx *ctx, uint32_t n_streams, c
     HostBody hb[MAX_INPUTS];
     for (uint32_t k = 0; k < n_streams; ++k) hb[k] = HostBody{body[k], body_len[k], has_count[k]};
     return query_host(ctx, hb, n_windows, begin, count, out, AcrossQntQuery{n_streams, stride, count, n_windows, n_q, q, method});
+    ATSC_API_END
+}
+
+extern "C" int atsc_across_extremes_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                                const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                                const uint64_t *count, uint64_t stride, uint32_t k, void *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
+        return fail(ctx, ATSC_E_INVALID, "across_extremes_windows: n_streams outside [1, 64], a null list or a null entry");
+    QueryInput in[MAX_INPUTS];
+    for (uint32_t j = 0; j < n_streams; ++j) in[j] = QueryInput{dp[j], d_body[j], 0};
+    return AcrossExtQuery{n_streams, stride, count, n_windows, k}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    ATSC_API_END
+}
+
+extern "C" int atsc_across_extremes_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                                            const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                            uint64_t stride, uint32_t k, void *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
+        return fail(ctx, ATSC_E_INVALID, "across_extremes_windows: n_streams outside [1, 64], a null list or a null entry");
+    if ((uintptr_t)out & 7u) return fail(ctx, ATSC_E_INVALID, "across_extremes_windows: out is not 8-byte aligned");
+    HostBody hb[MAX_INPUTS];
+    for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
+    return query_host(ctx, hb, n_windows, begin, count, out, AcrossExtQuery{n_streams, stride, count, n_windows, k});
     ATSC_API_END
 }
 
@@ -3022,5 +3098,15 @@ extern "C" int atsc_stream_across_quantile_windows(atsc_stream *const *streams, 
     if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
     return query_stream(streams, n_windows, begin, count, out,
                         AcrossQntQuery{n_streams, stride, count, n_windows, n_q, q, method});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_across_extremes_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                                   const uint64_t *begin, const uint64_t *count, uint64_t stride, uint32_t k,
+                                                   void *out)
+{
+    ATSC_API_BEGIN
+    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
+    return query_stream(streams, n_windows, begin, count, out, AcrossExtQuery{n_streams, stride, count, n_windows, k});
     ATSC_API_END
 }

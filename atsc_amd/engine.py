@@ -265,6 +265,26 @@ def _across_quantile_result(run, counts, stride, levels):
     return run(int(off[-1])).view(np.float64).reshape(int(off[-1]), len(_levels(levels)[0])), off
 
 
+def _across_extremes_params(stride, records, k):
+    """the across' arguments, then k"""
+    a = _RollArgs(tuple(_across_params(stride, records)) + _extremes_params(k))
+    a.records = int(records)
+    return a
+
+
+def _across_extremes_block(n, cargs):
+    """(a k that the library refuses still gets a result to leave untouched)"""
+    return _extremes_dtype(cargs[1].value).itemsize * cargs.records
+
+
+def _across_extremes_result(run, counts, stride, k):
+    """run(records) -> the block of an across extremes call as uint64 words.  -> (records, off): the
+    window_extremes_dtype(k) records of every position, range after range, and the ranges' record offsets
+    (across_offsets)"""
+    off = across_offsets(counts, stride)
+    return run(int(off[-1])).view(_extremes_dtype(k)), off
+
+
 def _array_params(values, flag):
     """levels and method, or edges and closed"""
     a, pa = _levels(values)
@@ -282,6 +302,8 @@ _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _s
 _ROLLING = _Query("rolling_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_block)
 _ACROSS = _Query("across_windows", np.dtype(np.uint64), None, _across_params, _across_block, inputs=None)
 _ACROSS_QUANTILE = _Query("across_quantile_windows", np.dtype(np.uint64), None, _across_quantile_params, _across_quantile_block,
+                          inputs=None)
+_ACROSS_EXTREMES = _Query("across_extremes_windows", np.dtype(np.uint64), None, _across_extremes_params, _across_extremes_block,
                           inputs=None)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
 _HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
@@ -640,6 +662,17 @@ class Context:
             lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m, levels, method, q=_ACROSS_QUANTILE),
             counts, stride, levels)
 
+    def across_extremes_windows_host(self, records_list, begins, counts, k, stride=1, has_count=False):
+        """-> (records, off): the k largest and the k smallest of the samples that the streams of records_list (at most
+        ACROSS_MAX_STREAMS decoded record streams, as across_windows_host takes them) hold at every `stride`-th position
+        of every range [begins[i], begins[i] + counts[i]), and which streams hold them (atsc_across_extremes_windows).
+        records: an array of window_extremes_dtype(k), one per position, range after range: the windowed extremes' record
+        of the position's column, `at` being the stream's index in records_list; extremes_merge over the records of one
+        position from consecutive sub-lists is the record of the whole list.  off: across_offsets(counts, stride), range
+        i's records being records[off[i]:off[i + 1]].  has_count holds for every stream"""
+        return _across_extremes_result(
+            lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m, k, q=_ACROSS_EXTREMES), counts, stride, k)
+
     def extremes_windows_host(self, records, begins, counts, k, has_count=False):
         """-> array of window_extremes_dtype(k): the k largest and the k smallest non-NaN samples, each with its offset
         in the window, the number of NaN samples and the length of every window [begins[i], begins[i] + counts[i]) of
@@ -845,6 +878,21 @@ class DPlan:
         _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, m, levels, method,
                     q=_ACROSS_QUANTILE)
         return d_out.reshape(-1)[: m * n_q].reshape(m, n_q), off
+
+    def across_extremes_windows(self, d_body, others, other_bodies, begins, counts, k, d_out, stride=1, stream=0):
+        """Enqueues the k largest and the k smallest of the samples that this plan's stream (stream 0) and the plans
+        `others` (their device bytes other_bodies; stream 1 and on, in that order) hold at every `stride`-th position of
+        the ranges [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least 16 + 32 k bytes per
+        position (atsc_across_extremes_windows_dev).  A plan may appear more than once.  -> (records, off): the view of
+        d_out's front as window_extremes_dtype(k) records, one per position (a uint8 tensor of 16 + 32 k bytes a row;
+        .cpu().numpy().view(window_extremes_dtype(k)) gives the fields), filled once `stream` has run, and the ranges'
+        record offsets (across_offsets)"""
+        import torch  # (d_out is a torch tensor: the module is loaded)
+        off = across_offsets(counts, stride)
+        m, size = int(off[-1]), _extremes_dtype(k).itemsize
+        _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, m, k,
+                    q=_ACROSS_EXTREMES)
+        return d_out.reshape(-1).view(torch.uint8)[: m * size].reshape(m, size), off
 
     def extremes_windows(self, d_body, begins, counts, k, d_out, stream=0):
         """Enqueues the k largest and the k smallest samples of the windows [begins[i], begins[i] + counts[i]) into

@@ -10,6 +10,7 @@ from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_ROLLING, W
 from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
 from .engine import ACROSS_RECORD, _ACROSS, _across_host, _across_list, _across_result  # noqa: F401
 from .engine import _ACROSS_QUANTILE, _across_quantile_result
+from .engine import _ACROSS_EXTREMES, _across_extremes_result
 
 
 def _f64(x):
@@ -176,6 +177,14 @@ class CompressedStream:
         return _across_quantile_result(
             lambda m: self._across_stream(_ACROSS_QUANTILE, others, begins, counts, stride, m, levels, method), counts, stride, levels)
 
+    def across_extremes_windows(self, others, begins, counts, k, stride=1):
+        """-> (records, off): the k largest and the k smallest of the samples that this stream (stream 0) and the streams
+        `others` (stream 1 and on) hold at every `stride`-th position of the ranges [begins[i], begins[i] + counts[i]),
+        and which streams hold them, as Context.across_extremes_windows_host gives them
+        (atsc_stream_across_extremes_windows)"""
+        return _across_extremes_result(
+            lambda m: self._across_stream(_ACROSS_EXTREMES, others, begins, counts, stride, m, k), counts, stride, k)
+
     def extremes_windows(self, begins, counts, k):
         """-> array of window_extremes_dtype(k) of the windows [begins[i], begins[i] + counts[i]): their k largest and k
         smallest samples and where they are (atsc_stream_extremes_windows)"""
@@ -293,6 +302,16 @@ def across_quantile_data_windows(ctx, bros, begins, counts, levels, stride=1, me
     return _across_quantile_result(
         lambda m: _across_host(ctx, records, begins, counts, True, stride, m, levels, method, q=_ACROSS_QUANTILE), counts, stride,
         levels)
+
+
+def across_extremes_data_windows(ctx, bros, begins, counts, k, stride=1):
+    """-> (records, off): the k largest and the k smallest of the samples that the streams decompress_data(ctx, bro) of
+    every .bro image of the list `bros` hold at every `stride`-th position of the ranges, and which streams hold them, as
+    Context.across_extremes_windows_host gives them: atsc_bro_open of each image, then atsc_across_extremes_windows over
+    their records"""
+    records = _across_images(bros)
+    return _across_extremes_result(
+        lambda m: _across_host(ctx, records, begins, counts, True, stride, m, k, q=_ACROSS_EXTREMES), counts, stride, k)
 
 
 def extremes_data_windows(ctx, bro, begins, counts, k):

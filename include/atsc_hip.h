@@ -938,6 +938,53 @@ int atsc_across_quantile_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_
                                  const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint64_t stride, uint32_t n_q, const double *q, int method, double *out);
 
+/* Windowed across extremes: the k largest and the k smallest of the N samples that the streams of a call hold at every
+ * position of ranges of the decoded streams, and which streams hold them -- `topk(3, x)` / `bottomk(5, x)`, the three
+ * slowest replicas at every step, who was second worst when the worst one was restarted -- without the decoded samples
+ * leaving the library.
+ *   Ranges     atsc_across_windows' exactly: one stride for the call, range i has atsc_across_outputs(count[i], stride)
+ *              positions, records are numbered range after range in the same order.
+ *   Result     record r is the ATSC_EXTREMES_BYTES(k) bytes at (char *)out + r * ATSC_EXTREMES_BYTES(k), laid out as the
+ *              windowed extremes lay theirs out: an atsc_window_extremes_head, largest[0 .. k), smallest[0 .. k), each
+ *              an atsc_extreme.  One k, 1 <= k <= ATSC_EXTREMES_MAX_K, holds for a call.
+ *   Record     the windowed extremes' record of the column x_0 .. x_(N-1), x_j = the sample of stream j at the position,
+ *              j the stream's place in the call's list: what atsc_extremes_windows gives for a window of those N samples.
+ *              count is n_streams, NaN included; nans the number of j with x_j NaN.  largest lists the x_j that are not
+ *              NaN by value descending, smallest by value ascending; samples are compared as values (-0.0 equals +0.0,
+ *              +-Inf are ordinary values) and among equal values the lowest j comes first.  An entry's value is the
+ *              sample's own bits (a -0.0 stays -0.0), its `at` is j.  NaN is never listed; unused entries -- all of them
+ *              beyond N when k > N -- hold value = NaN, at = ATSC_EXTREMES_NONE.  One stream may appear in both lists.
+ *              No floating-point arithmetic touches a sample: the record is bit-exact, and it depends only on the N
+ *              samples of its position, the order of the list and k: not on the range, the stride, the other ranges, the
+ *              budget, the piece boundaries, the framing, the codecs or the device.
+ *   It follows that
+ *              - the first j entries of a call with k are the entries of a call with j < k;
+ *              - where atsc_across_windows' count > 0, largest[0] is its max and max_at and smallest[0] its min and
+ *                min_at, bit for bit; count - nans is its count;
+ *              - atsc_extremes_merge over the records of one position from calls over consecutive sub-lists L_0, L_1, ..
+ *                of a list (the same k) is the record of the concatenated list, bit for bit: it shifts every `at` by the
+ *                counts in front, which here are the sub-lists' sizes.  A list of more than ATSC_ACROSS_MAX_STREAMS
+ *                streams is queried that way;
+ *              - under a reordering of the list the listed values stay the same as values, and every `at` maps through
+ *                the reordering except among equal values.
+ * Errors: ATSC_E_INVALID with nothing written and before any GPU work for every case of atsc_across_windows, k == 0 or
+ * k > ATSC_EXTREMES_MAX_K, a result pointer that is not 8-byte aligned.  n_windows == 0 and empty ranges write nothing.
+ * Scratch and pieces are the across': there is no ATSC_E_CAPACITY case. */
+/* dp / d_body (n_streams entries each) and begin / count are HOST arrays; d_body[j] and d_out are device memory (d_out
+ * 8-byte aligned, ATSC_EXTREMES_BYTES(k) bytes per record).  Enqueued on `stream`, not synchronised.  A malformed
+ * payload in a frame of stream j that a range touches sets dp[j]'s status word.  dp[0] keeps the call's tables and
+ * scratch in the place of the across quantiles': the next across extremes or across quantile call whose first plan is
+ * dp[0] waits (host side) until this one's work is done; atsc_dplan_destroy frees them. */
+int atsc_across_extremes_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                     const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                     const uint64_t *count, uint64_t stride, uint32_t k, void *d_out, void *stream);
+/* Host bytes in (n_streams bodies, lengths and has_count flags), host records out, synchronous; walks and uploads only
+ * the touched records of every stream, as atsc_across_windows does, and computes the device call's bits.  ATSC_E_FORMAT
+ * (nothing written) for a malformed payload in a frame of any stream that a range touches. */
+int atsc_across_extremes_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                                 const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                 uint64_t stride, uint32_t k, void *out);
+
 /* Windowed histograms: how the samples of windows [begin, begin + count) of the decoded stream (the indices of
  * atsc_decompress_frames) are distributed over value bins, from the same decoded samples as the window decode.  The
  * bins are given by n_edges ascending edges, the same for every window.  For window i:
@@ -1039,6 +1086,11 @@ int atsc_stream_across_windows(atsc_stream *const *streams, uint32_t n_streams, 
 int atsc_stream_across_quantile_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
                                         const uint64_t *begin, const uint64_t *count, uint64_t stride, uint32_t n_q,
                                         const double *q, int method, double *out);
+/* atsc_across_extremes_windows over the frames of the n_streams streams of the list, which must belong to one context
+ * (else ATSC_E_INVALID) */
+int atsc_stream_across_extremes_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                        const uint64_t *begin, const uint64_t *count, uint64_t stride, uint32_t k,
+                                        void *out);
 /* atsc_quantile_windows over the stream's frames */
 int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint32_t n_q, const double *q, int method, double *out);
