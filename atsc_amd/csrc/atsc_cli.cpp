@@ -6,7 +6,7 @@
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
 //        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S]]
 //        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]
-//        [--across-extremes K]]]
+//        [--across-extremes K] [--across-moments]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -98,6 +98,10 @@ void usage()
             "                                 first in the list first), NaN samples left out and counted: nans,top1,top1_at,..,\n"
             "                                 topK,topK_at,bottom1,bottom1_at,..,bottomK,bottomK_at behind the columns above,\n"
             "                                 the cells of unused entries empty\n"
+            "      --across-moments           with --across: also nonnan,avg,stdvar,stddev behind the columns above: how many of the\n"
+            "                                 streams' samples at every row's sample index are not NaN, their mean and their\n"
+            "                                 variance and standard deviation (population forms), merged from centred moments and\n"
+            "                                 never from a sum of squares; the four cells empty where every sample is NaN\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -194,12 +198,13 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
             std::vector<atsc_across_record> rows;
             std::vector<double> levels;
             std::vector<uint64_t> extremes;
+            std::vector<atsc_across_moments> moments;
             rc = atsc_bro_open(bro, len, nullptr, nullptr);
-            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, levels, extremes);
+            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, levels, extremes, moments);
             atsc_free(bro);
             if (rc) return rc;
             const bool ok = across_write(with_ext(path, "across.csv"), rows, a.q.across_stride, a.q.across_level_names, levels,
-                                         (uint32_t)a.q.across_extremes, extremes);
+                                         (uint32_t)a.q.across_extremes, extremes, a.q.across_moments, moments);
             return ok ? ATSC_OK : ATSC_E_IO;
         }
         double *out = nullptr;

@@ -83,6 +83,7 @@ struct BucketOptions {
     int across_method = ATSC_QUANTILE_LINEAR;  // --across-quantile-method
     bool have_across_method = false;
     int across_extremes = 0;  // --across-extremes K: nans,top1,top1_at,..,topK,topK_at,bottom1,bottom1_at,..,bottomK,bottomK_at
+    bool across_moments = false;  // --across-moments: nonnan,avg,stdvar,stddev
 };
 
 // --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
@@ -323,6 +324,8 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             fprintf(stderr, "error: invalid value '%s' for '--across-extremes': expected 1..=%d\n", v.c_str(), (int)ATSC_EXTREMES_MAX_K);
             return 2;
         }
+    } else if (o.across_allowed && s == "--across-moments") {
+        o.across_moments = true;
     } else {
         return 0;
     }
@@ -387,7 +390,7 @@ bool rolling_option_complete(const BucketOptions &o, const char *window, bool wi
 }
 
 // --across goes with the option that names the window and without the one that cuts buckets, --rolling and --where;
-// --across-stride, --across-quantiles and --across-extremes go with --across, --across-quantile-method with
+// --across-stride, --across-quantiles, --across-extremes and --across-moments go with --across, --across-quantile-method with
 // --across-quantiles.  false: a usage error, reported on stderr.
 bool across_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
 {
@@ -399,7 +402,8 @@ bool across_option_complete(const BucketOptions &o, const char *window, bool win
         if (o.have_across_stride) fprintf(stderr, "error: '--across-stride' needs '--across'\n");
         else if (!o.across_levels.empty()) fprintf(stderr, "error: '--across-quantiles' needs '--across'\n");
         else if (o.across_extremes) fprintf(stderr, "error: '--across-extremes' needs '--across'\n");
-        return !o.have_across_stride && o.across_levels.empty() && !o.across_extremes;
+        else if (o.across_moments) fprintf(stderr, "error: '--across-moments' needs '--across'\n");
+        return !o.have_across_stride && o.across_levels.empty() && !o.across_extremes && !o.across_moments;
     }
     if (!windowed) {
         fprintf(stderr, "error: '--across' needs '%s'\n", window);
@@ -655,9 +659,11 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
 // --across: one record per position of the range [begin, begin + count) over the .bro image (stream 0) and the listed
 // files (stream 1 and on): sample i of each goes with sample i of the others.  levels: with --across-quantiles, the
 // same positions' rows of o.across_levels.size() levels; extremes: with --across-extremes K, the same positions'
-// extremes records of k = K, ATSC_EXTREMES_BYTES(K) / 8 words each
+// extremes records of k = K, ATSC_EXTREMES_BYTES(K) / 8 words each; moments: with --across-moments, the same
+// positions' across moments
 int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
-                 std::vector<atsc_across_record> &rows, std::vector<double> &levels, std::vector<uint64_t> &extremes)
+                 std::vector<atsc_across_record> &rows, std::vector<double> &levels, std::vector<uint64_t> &extremes,
+                 std::vector<atsc_across_moments> &moments)
 {
     std::vector<uint8_t *> image(o.across.size(), nullptr);
     std::vector<const uint8_t *> body{bro + 9};
@@ -693,6 +699,12 @@ int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOp
                                               &count, o.across_stride, (uint32_t)o.across_extremes,
                                               extremes.empty() ? &no_record : extremes.data());
         }
+        if (!rc && o.across_moments) {
+            moments.assign(rows.size(), atsc_across_moments{});
+            atsc_across_moments no_moments;
+            rc = atsc_across_moments_windows(ctx, (uint32_t)body.size(), body.data(), body_len.data(), has_count.data(), 1, &begin,
+                                             &count, o.across_stride, moments.empty() ? &no_moments : moments.data());
+        }
     }
     for (uint8_t *p : image) atsc_free(p);
     return rc;
@@ -704,10 +716,12 @@ int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOp
 // q<level as typed> per level behind them, from the position's row of `levels`.  k: with --across-extremes K, behind
 // those nans,top1,top1_at,..,topK,topK_at,bottom1,bottom1_at,..,bottomK,bottomK_at from the position's record of
 // `extremes`: the K largest and the K smallest samples and the streams that hold them, the cells of unused entries
-// empty.  false: the file could not be written.
+// empty.  with_moments: with --across-moments, behind those nonnan,avg,stdvar,stddev from the position's record of
+// `moments`: its count, mean and the population variance and standard deviation that atsc_across_moments_fit reads off
+// it, all four empty where count == 0 (the count column says so).  false: the file could not be written.
 bool across_write(const std::string &path, const std::vector<atsc_across_record> &rows, uint64_t stride,
                   const std::vector<std::string> &names, const std::vector<double> &levels, uint32_t k,
-                  const std::vector<uint64_t> &extremes)
+                  const std::vector<uint64_t> &extremes, bool with_moments, const std::vector<atsc_across_moments> &moments)
 {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return false;
@@ -718,6 +732,7 @@ bool across_write(const std::string &path, const std::vector<atsc_across_record>
         for (uint32_t e = 0; e < k; ++e) fprintf(f, ",top%u,top%u_at", e + 1, e + 1);
         for (uint32_t e = 0; e < k; ++e) fprintf(f, ",bottom%u,bottom%u_at", e + 1, e + 1);
     }
+    if (with_moments) fprintf(f, ",nonnan,avg,stdvar,stddev");
     fprintf(f, "\n");
     for (size_t j = 0; j < rows.size(); ++j) {
         const atsc_across_record &r = rows[j];
@@ -734,6 +749,13 @@ bool across_write(const std::string &path, const std::vector<atsc_across_record>
                 if (x[e].at == ATSC_EXTREMES_NONE) fprintf(f, ",,");
                 else fprintf(f, ",%s,%llu", debug_f64(x[e].value).c_str(), (unsigned long long)x[e].at);
             }
+        }
+        if (with_moments) {
+            atsc_across_fit fit;
+            atsc_across_moments_fit(&moments[j], 1, &fit);
+            if (moments[j].count == 0) fprintf(f, ",,,,");
+            else fprintf(f, ",%u,%s,%s,%s", moments[j].count, debug_f64(fit.mean).c_str(), debug_f64(fit.variance).c_str(),
+                         debug_f64(fit.stddev).c_str());
         }
         fprintf(f, "\n");
     }

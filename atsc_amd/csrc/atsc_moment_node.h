@@ -7,8 +7,10 @@
 //     mx = mxa + dx * w; mt = mta + dt * w;
 //     M2x = (M2xa + M2xb) + (dx * dx) * f; M2t = (M2ta + M2tb) + (dt * dt) * f; C = (Ca + Cb) + (dx * dt) * f
 // (one rounding per operation: the files that include this are compiled with -ffp-contract=off).  The tree is the tile
-// sum's (tile_lane_sums, atsc_tile_reduce.h) with + replaced by Merge, the left operand as a.
+// sum's (tile_lane_sums, atsc_tile_reduce.h) with + replaced by Merge, the left operand as a.  Merge itself is
+// node_merge of atsc_moment_rule.h, which the host shares.
 #pragma once
+#include "atsc_moment_rule.h"
 #include "atsc_tile_reduce.h"
 
 namespace atsc {
@@ -25,26 +27,6 @@ struct Node {
 __device__ __forceinline__ Node node_leaf(double v, double t, bool ok)
 {
     return ok ? Node{v, 0.0, t, 0.0, 0.0, 1} : Node{0.0, 0.0, 0.0, 0.0, 0.0, 0};
-}
-
-// Merge(a, b).  EQ: the caller knows na == nb != 0 -- then w = nb / (2 nb) is 0.5 exactly and f = na * 0.5, the bits
-// the divide gives; nothing else differs from the general rule.  ND: Node or DevMomPart.
-template <bool EQ, class ND>
-__device__ __forceinline__ ND node_merge(const ND &a, const ND &b)
-{
-    const decltype(a.n) n = a.n + b.n;
-    const double w = EQ ? 0.5 : (double)b.n / (double)n;
-    const double f = (double)a.n * w;
-    const double dx = b.mx - a.mx, dt = b.mt - a.mt;
-    ND r;
-    r.mx = a.mx + dx * w;
-    r.mt = a.mt + dt * w;
-    r.m2x = (a.m2x + b.m2x) + (dx * dx) * f;
-    r.m2t = (a.m2t + b.m2t) + (dt * dt) * f;
-    r.c = (a.c + b.c) + (dx * dt) * f;
-    r.n = n;
-    if (EQ) return r;
-    return b.n == 0 ? a : a.n == 0 ? b : r;
 }
 
 // a virtual lane's eight leaves into its node: leaf(q, e) is the leaf of slot tile_slot(v, q) + e

@@ -1,6 +1,6 @@
 // atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms,
 // rolling windows and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
-// and count, min, max, sum and quantiles across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
+// and count, min, max, sum, quantiles, extremes and moments across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "atsc_host_private.h"
+#include "atsc_moment_rule.h"
 
 namespace atsc {
 // (weak: the sanitizer build of the host sources, tests/asan, links without the window kernels and never decodes a window)
@@ -107,6 +108,10 @@ __attribute__((weak)) hipError_t launch_across_quantile_positions(const DevRollT
 __attribute__((weak)) hipError_t launch_across_extremes_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                                   const uint64_t *reg, uint32_t n_streams, uint64_t a0,
                                                                   uint64_t stride, uint32_t k, void *out, hipStream_t s);
+// the windowed across moments' position kernel (atsc_across_moments.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_across_moments_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
+                                                                 const uint64_t *reg, uint32_t n_streams, uint64_t a0,
+                                                                 uint64_t stride, void *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -364,7 +369,8 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
                           BY_ROLLING = DECODE_CALLER("rolling"), BY_ACROSS = DECODE_CALLER("across"),
                           BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile"),
-                          BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes");
+                          BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes"),
+                          BY_ACROSS_MOMENTS = DECODE_CALLER("across moments");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -2578,7 +2584,7 @@ static int across_check(atsc_ctx *ctx, const char *call, uint32_t n_streams, uin
 }
 
 // What differs between the device calls that work on the N samples of a position (across_dev): the across and the
-// across quantiles and the across extremes.
+// across quantiles, the across extremes and the across moments.
 struct AcrossKernel {
     const char *call;          // names the call in the messages
     const char *no_kernels;    // ATSC_E_UNSUPPORTED's message
@@ -2824,6 +2830,41 @@ struct AcrossExtQuery {
     }
 };
 
+// the across moments' descriptor: the across' ranges, stride and record numbering, an atsc_across_moments per position.
+// The call has no parameter of its own.  Like the across extremes it keeps its tables and scratch in the across
+// quantiles' place on in[0].dp (Q_ACROSS_QUANTILE): the three kinds of call on one first plan wait for each other, and
+// atsc_dplan stays as it is (DESIGN.md "Windowed across moments")
+struct AcrossMomQuery {
+    static constexpr int INPUTS = 0;
+    static constexpr const char *CALL = "across_moments_windows";
+    uint32_t n_streams;
+    uint64_t stride;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    int inputs() const { return (int)n_streams; }
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
+        return total * sizeof(atsc_across_moments);
+    }
+    int check(atsc_ctx *ctx) const { return across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, nullptr); }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
+    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
+            void *stream) const
+    {
+        const uint32_t ns = n_streams;
+        const uint64_t st = stride;
+        const AcrossKernel K{CALL, "no across moments kernels", "launch k_across_moments_positions", Q_ACROSS_QUANTILE,
+                             BY_ACROSS_MOMENTS, launch_across_moments_positions != nullptr, nullptr, 0,
+                             [ns, st](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
+                                      const void *, void *d_out, hipStream_t s) {
+                                 return launch_across_moments_positions(tasks, n, scratch, reg, ns, a0, st, d_out, s);
+                             }};
+        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
+    }
+};
+
 // what every across call checks of its lists before it reads them
 static bool across_lists(uint32_t n_streams, const void *const *a, const void *const *b)
 {
@@ -2912,6 +2953,77 @@ extern "C" int atsc_across_extremes_windows(atsc_ctx *ctx, uint32_t n_streams, c
     for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
     return query_host(ctx, hb, n_windows, begin, count, out, AcrossExtQuery{n_streams, stride, count, n_windows, k});
     ATSC_API_END
+}
+
+extern "C" int atsc_across_moments_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                               const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                               const uint64_t *count, uint64_t stride, atsc_across_moments *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
+        return fail(ctx, ATSC_E_INVALID, "across_moments_windows: n_streams outside [1, 64], a null list or a null entry");
+    QueryInput in[MAX_INPUTS];
+    for (uint32_t j = 0; j < n_streams; ++j) in[j] = QueryInput{dp[j], d_body[j], 0};
+    return AcrossMomQuery{n_streams, stride, count, n_windows}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    ATSC_API_END
+}
+
+extern "C" int atsc_across_moments_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                                           const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                           uint64_t stride, atsc_across_moments *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
+        return fail(ctx, ATSC_E_INVALID, "across_moments_windows: n_streams outside [1, 64], a null list or a null entry");
+    if ((uintptr_t)out & 7u) return fail(ctx, ATSC_E_INVALID, "across_moments_windows: out is not 8-byte aligned");
+    HostBody hb[MAX_INPUTS];
+    for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
+    return query_host(ctx, hb, n_windows, begin, count, out, AcrossMomQuery{n_streams, stride, count, n_windows});
+    ATSC_API_END
+}
+
+// Host only: the records of one position from consecutive sub-lists, folded from the left by the moments' Merge
+// (node_merge, atsc_moment_rule.h: the kernels' own copy; this file is compiled with -ffp-contract=off as they are).
+// The position half of a node stays zero.
+extern "C" int atsc_across_moments_merge(const atsc_across_moments *records, uint64_t n, atsc_across_moments *out)
+{
+    struct HostNode {
+        double mx, m2x, mt, m2t, c;
+        uint64_t n;
+    };
+    if (!out || (n && !records)) return ATSC_E_INVALID;
+    HostNode a{0.0, 0.0, 0.0, 0.0, 0.0, 0};
+    uint64_t nans = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const atsc_across_moments &r = records[i];
+        nans += r.nans;
+        if (a.n + r.count > 0xFFFFFFFFull || nans > 0xFFFFFFFFull) return ATSC_E_INVALID;
+        a = node_merge<false>(a, HostNode{r.mean, r.m2, 0.0, 0.0, 0.0, r.count});
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    *out = atsc_across_moments{(uint32_t)a.n, (uint32_t)nans, a.n ? a.mx : nan, a.n ? a.m2x : nan};
+    return ATSC_OK;
+}
+
+// Host only: what a caller reads off the across moments, by atsc_moments_fit's definitions.
+extern "C" int atsc_across_moments_fit(const atsc_across_moments *m, uint64_t n, atsc_across_fit *out)
+{
+    if (n && (!m || !out)) return ATSC_E_INVALID;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (uint64_t i = 0; i < n; ++i) {
+        const atsc_across_moments &a = m[i];
+        atsc_across_fit &r = out[i];
+        if (a.count == 0) {
+            r.mean = r.variance = r.stddev = r.sample_variance = r.sample_stddev = nan;
+            continue;
+        }
+        r.mean = a.mean;
+        r.variance = a.m2 / (double)a.count;
+        r.stddev = std::sqrt(r.variance);
+        r.sample_variance = a.count < 2 ? nan : a.m2 / (double)(a.count - 1);
+        r.sample_stddev = std::sqrt(r.sample_variance);
+    }
+    return ATSC_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3108,5 +3220,15 @@ extern "C" int atsc_stream_across_extremes_windows(atsc_stream *const *streams, 
     ATSC_API_BEGIN
     if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
     return query_stream(streams, n_windows, begin, count, out, AcrossExtQuery{n_streams, stride, count, n_windows, k});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_across_moments_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                                  const uint64_t *begin, const uint64_t *count, uint64_t stride,
+                                                  atsc_across_moments *out)
+{
+    ATSC_API_BEGIN
+    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
+    return query_stream(streams, n_windows, begin, count, out, AcrossMomQuery{n_streams, stride, count, n_windows});
     ATSC_API_END
 }

@@ -83,6 +83,13 @@ ACROSS_RECORD = np.dtype([("count", "<u4"), ("min_at", "<u2"), ("max_at", "<u2")
 ACROSS_MAX_STREAMS = capi.ACROSS_MAX_STREAMS
 
 
+# atsc_across_moments (include/atsc_hip.h): the record of one position of an across moments call, 24 bytes
+ACROSS_MOMENTS = np.dtype([("count", "<u4"), ("nans", "<u4"), ("mean", "<f8"), ("m2", "<f8")])
+# atsc_across_fit: what atsc_across_moments_fit reads off them, 40 bytes
+ACROSS_FIT = np.dtype([("mean", "<f8"), ("variance", "<f8"), ("stddev", "<f8"), ("sample_variance", "<f8"),
+                       ("sample_stddev", "<f8")])
+
+
 def across_outputs(count, stride=1):
     """-> the positions of a range of `count` samples taken every `stride` samples (atsc_across_outputs; no GPU):
     (count - 1) // stride + 1, or 0 where count or stride is 0"""
@@ -285,6 +292,17 @@ def _across_extremes_result(run, counts, stride, k):
     return run(int(off[-1])).view(_extremes_dtype(k)), off
 
 
+def _across_moments_block(n, cargs):
+    return ACROSS_MOMENTS.itemsize * cargs.records
+
+
+def _across_moments_result(run, counts, stride):
+    """run(records) -> the block of an across moments call as uint64 words.  -> (records, off): the ACROSS_MOMENTS
+    records of every position, range after range, and the ranges' record offsets (across_offsets)"""
+    off = across_offsets(counts, stride)
+    return run(int(off[-1])).view(ACROSS_MOMENTS), off
+
+
 def _array_params(values, flag):
     """levels and method, or edges and closed"""
     a, pa = _levels(values)
@@ -305,6 +323,7 @@ _ACROSS_QUANTILE = _Query("across_quantile_windows", np.dtype(np.uint64), None, 
                           inputs=None)
 _ACROSS_EXTREMES = _Query("across_extremes_windows", np.dtype(np.uint64), None, _across_extremes_params, _across_extremes_block,
                           inputs=None)
+_ACROSS_MOMENTS = _Query("across_moments_windows", np.dtype(np.uint64), None, _across_params, _across_moments_block, inputs=None)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
 _HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
 
@@ -428,6 +447,26 @@ def moments_fit(moments):
     out = np.zeros(max(len(m), 1), dtype=WINDOW_FIT)
     capi.check(capi.lib().atsc_moments_fit(C.c_void_p(m.ctypes.data), len(m), C.c_void_p(out.ctypes.data)))
     return out[: len(m)]
+
+
+def across_moments_fit(moments):
+    """-> ACROSS_FIT array: mean, population and sample variance / stddev of every ACROSS_MOMENTS record
+    (atsc_across_moments_fit; no GPU)"""
+    m = np.ascontiguousarray(np.atleast_1d(np.asarray(moments, dtype=ACROSS_MOMENTS)))
+    out = np.zeros(max(len(m), 1), dtype=ACROSS_FIT)
+    capi.check(capi.lib().atsc_across_moments_fit(C.c_void_p(m.ctypes.data), len(m), C.c_void_p(out.ctypes.data)))
+    return out[: len(m)]
+
+
+def across_moments_merge(records):
+    """-> one ACROSS_MOMENTS record (a 0-d array): the records of one position from calls over consecutive sub-lists of a
+    list, left to right, folded by the moments' Merge into the record of the whole list (atsc_across_moments_merge; no
+    GPU) -- how more than ACROSS_MAX_STREAMS streams are queried"""
+    r = np.ascontiguousarray(np.atleast_1d(np.asarray(records, dtype=ACROSS_MOMENTS)))
+    out = np.zeros(1, dtype=ACROSS_MOMENTS)
+    capi.check(capi.lib().atsc_across_moments_merge(C.c_void_p(r.ctypes.data if len(r) else None), len(r),
+                                                    C.c_void_p(out.ctypes.data)))
+    return out[0]
 
 
 def pair_fit(pairs):
@@ -673,6 +712,16 @@ class Context:
         return _across_extremes_result(
             lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m, k, q=_ACROSS_EXTREMES), counts, stride, k)
 
+    def across_moments_windows_host(self, records_list, begins, counts, stride=1, has_count=False):
+        """-> (records, off): count, mean and m2 = sum (x - mean)^2 of the samples that the streams of records_list (at
+        most ACROSS_MAX_STREAMS decoded record streams, as across_windows_host takes them) hold at every `stride`-th
+        position of every range [begins[i], begins[i] + counts[i]) (atsc_across_moments_windows).  records: an array of
+        ACROSS_MOMENTS, one per position, range after range; across_moments_fit reads mean, variance and stddev off them,
+        across_moments_merge folds the records of one position from consecutive sub-lists.  off: across_offsets(counts,
+        stride), range i's records being records[off[i]:off[i + 1]].  has_count holds for every stream"""
+        return _across_moments_result(
+            lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m, q=_ACROSS_MOMENTS), counts, stride)
+
     def extremes_windows_host(self, records, begins, counts, k, has_count=False):
         """-> array of window_extremes_dtype(k): the k largest and the k smallest non-NaN samples, each with its offset
         in the window, the number of NaN samples and the length of every window [begins[i], begins[i] + counts[i]) of
@@ -892,6 +941,20 @@ class DPlan:
         m, size = int(off[-1]), _extremes_dtype(k).itemsize
         _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, m, k,
                     q=_ACROSS_EXTREMES)
+        return d_out.reshape(-1).view(torch.uint8)[: m * size].reshape(m, size), off
+
+    def across_moments_windows(self, d_body, others, other_bodies, begins, counts, d_out, stride=1, stream=0):
+        """Enqueues count, mean and m2 of the samples that this plan's stream (stream 0) and the plans `others` (their
+        device bytes other_bodies; stream 1 and on, in that order) hold at every `stride`-th position of the ranges
+        [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least 24 bytes per position
+        (atsc_across_moments_windows_dev).  A plan may appear more than once.  -> (records, off): the view of d_out's front
+        as ACROSS_MOMENTS records, one per position (a uint8 tensor of 24 bytes a row; .cpu().numpy().view(ACROSS_MOMENTS)
+        gives the fields), filled once `stream` has run, and the ranges' record offsets (across_offsets)"""
+        import torch  # (d_out is a torch tensor: the module is loaded)
+        off = across_offsets(counts, stride)
+        m, size = int(off[-1]), ACROSS_MOMENTS.itemsize
+        _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, m,
+                    q=_ACROSS_MOMENTS)
         return d_out.reshape(-1).view(torch.uint8)[: m * size].reshape(m, size), off
 
     def extremes_windows(self, d_body, begins, counts, k, d_out, stream=0):

@@ -11,6 +11,7 @@ from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, 
 from .engine import ACROSS_RECORD, _ACROSS, _across_host, _across_list, _across_result  # noqa: F401
 from .engine import _ACROSS_QUANTILE, _across_quantile_result
 from .engine import _ACROSS_EXTREMES, _across_extremes_result
+from .engine import _ACROSS_MOMENTS, _across_moments_result
 
 
 def _f64(x):
@@ -185,6 +186,13 @@ class CompressedStream:
         return _across_extremes_result(
             lambda m: self._across_stream(_ACROSS_EXTREMES, others, begins, counts, stride, m, k), counts, stride, k)
 
+    def across_moments_windows(self, others, begins, counts, stride=1):
+        """-> (records, off): count, mean and m2 of the samples that this stream (stream 0) and the streams `others`
+        (stream 1 and on) hold at every `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as
+        Context.across_moments_windows_host gives them (atsc_stream_across_moments_windows)"""
+        return _across_moments_result(
+            lambda m: self._across_stream(_ACROSS_MOMENTS, others, begins, counts, stride, m), counts, stride)
+
     def extremes_windows(self, begins, counts, k):
         """-> array of window_extremes_dtype(k) of the windows [begins[i], begins[i] + counts[i]): their k largest and k
         smallest samples and where they are (atsc_stream_extremes_windows)"""
@@ -312,6 +320,15 @@ def across_extremes_data_windows(ctx, bros, begins, counts, k, stride=1):
     records = _across_images(bros)
     return _across_extremes_result(
         lambda m: _across_host(ctx, records, begins, counts, True, stride, m, k, q=_ACROSS_EXTREMES), counts, stride, k)
+
+
+def across_moments_data_windows(ctx, bros, begins, counts, stride=1):
+    """-> (records, off): count, mean and m2 of the samples that the streams decompress_data(ctx, bro) of every .bro
+    image of the list `bros` hold at every `stride`-th position of the ranges, as Context.across_moments_windows_host
+    gives them: atsc_bro_open of each image, then atsc_across_moments_windows over their records"""
+    records = _across_images(bros)
+    return _across_moments_result(
+        lambda m: _across_host(ctx, records, begins, counts, True, stride, m, q=_ACROSS_MOMENTS), counts, stride)
 
 
 def extremes_data_windows(ctx, bro, begins, counts, k):
