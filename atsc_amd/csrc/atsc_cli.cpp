@@ -4,7 +4,7 @@
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
-//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S]]
+//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas]]
 //        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]
 //        [--across-extremes K] [--across-moments]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
@@ -81,6 +81,9 @@ void usage()
             "                                 S-th position of the samples (S: 1) to .roll.csv instead of the .wbro:\n"
             "                                 offset,count,min,max,sum,mean, offset the position's first sample counted\n"
             "                                 from BEGIN; mean is sum / count, empty where count is 0\n"
+            "      --rolling-deltas           with --rolling: also every position's steps from one sample to the next, as the\n"
+            "                                 last columns: pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase\n"
+            "                                 (as --deltas; increase = up + after_falls, the counter increase of the window)\n"
             "      --across <A.bro,B.bro,..>  with -u --samples, without --buckets, --rolling and --where: fold this file (stream\n"
             "                                 0) and the listed files (streams 1.., at most 63) at the same sample indices and\n"
             "                                 write one row per sample to .across.csv instead of the .wbro:\n"
@@ -185,12 +188,15 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
         }
         if (a.q.rolling) {  // (with --samples) the window's rolling records, no .wbro
             std::vector<atsc_window_rolling> rows;
+            std::vector<atsc_window_delta> deltas;
+            std::vector<atsc_window_delta_fit> fits;
             rc = atsc_bro_open(bro, len, nullptr, nullptr);
-            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows);
+            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, deltas, fits);
             atsc_free(bro);
             if (rc) return rc;
             const uint64_t stride = a.q.rolling_stride;  // a position's first sample, counted from the window's begin
-            return rolling_write(with_ext(path, "roll.csv"), "offset", rows, [stride](uint64_t j) { return std::to_string(j * stride); })
+            return rolling_write(with_ext(path, "roll.csv"), "offset", rows, a.q.rolling_deltas, deltas, fits,
+                                 [stride](uint64_t j) { return std::to_string(j * stride); })
                        ? ATSC_OK
                        : ATSC_E_IO;
         }

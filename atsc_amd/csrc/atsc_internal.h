@@ -323,7 +323,7 @@ constexpr uint32_t ROLL_LOW = 3;                                        // the l
 constexpr uint32_t ROLL_MAX_LEVEL = 20;                                 // log2 ATSC_ROLLING_MAX_WIDTH
 constexpr uint32_t ROLL_TASK = 256;                                     // positions per task: one wavefront, four steps
 // one piece: scratch[0] is sample a0 of the stream (a multiple of ROLL_TILE), the region ends in front of sample a1 (one
-// too); the chunk j of level l lies at pyr[off[l] + j - (a0 >> l)] for a0 >> l <= j <= (a1 - 1) >> l, in 32-byte partials
+// too); the chunk j of level l lies at pyr[off[l] + j - (a0 >> l)] for a0 >> l <= j <= (a1 - 1) >> l, in the call's partials
 // (a chunk that sticks out of [a0, a1) has a place and no value)
 struct DevRollPiece {
     uint64_t a0, a1;
@@ -335,6 +335,12 @@ struct DevRollTask {
     uint64_t lo, rec;
     uint32_t n, pad;
 };
+
+// windowed rolling deltas (atsc_rolling_delta_windows_dev, atsc_rolling_delta.hip): the rolling's pieces, tasks and
+// pyramid over the pair slots of the stream, slot j holding the deltas' terms of the pair (x[j - 1], x[j]); a window's
+// chunks are those of [lo + 1, lo + w), and the highest level floor(log2(w - 1))
+constexpr uint32_t ROLL_DELTA_LOW = 3;    // the lowest stored level
+constexpr uint32_t ROLL_DELTA_PART = 48;  // bytes of a partial: three sums, two maxima, the three counts in one word
 
 // windowed across (atsc_across_windows_dev, atsc_across.hip): every stream of a call decoded into a scratch region of
 // its own, the same sample at the same slot of every region, then one record per position from its slot of each.  A

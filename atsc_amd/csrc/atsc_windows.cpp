@@ -1,5 +1,5 @@
 // atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms,
-// rolling windows and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
+// rolling windows, rolling deltas and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
 // and count, min, max, sum, quantiles, extremes and moments across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
@@ -95,6 +95,14 @@ __attribute__((weak)) hipError_t launch_roll_upper(void *pyr, const DevRollPiece
 __attribute__((weak)) hipError_t launch_roll_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                        const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
                                                        void *out, hipStream_t s);
+// the windowed rolling deltas' pyramid and position kernels (atsc_rolling_delta.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_rdl_pyramid(const double *scratch, uint32_t n_tiles, void *pyr, const DevRollPiece *pc,
+                                                    uint32_t lmax, hipStream_t s);
+__attribute__((weak)) hipError_t launch_rdl_upper(void *pyr, const DevRollPiece *pc, uint32_t n, uint32_t src, uint32_t lmax,
+                                                  hipStream_t s);
+__attribute__((weak)) hipError_t launch_rdl_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
+                                                      const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
+                                                      void *out, hipStream_t s);
 // the windowed across' position kernel (atsc_across.hip; weak for the same reason)
 __attribute__((weak)) hipError_t launch_across_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                          const uint64_t *reg, uint32_t n_streams, uint64_t a0,
@@ -367,7 +375,8 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs"),
                           BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
                           BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
-                          BY_ROLLING = DECODE_CALLER("rolling"), BY_ACROSS = DECODE_CALLER("across"),
+                          BY_ROLLING = DECODE_CALLER("rolling"), BY_ROLLING_DELTA = DECODE_CALLER("rolling delta"),
+                          BY_ACROSS = DECODE_CALLER("across"),
                           BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile"),
                           BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes"),
                           BY_ACROSS_MOMENTS = DECODE_CALLER("across moments");
@@ -2367,45 +2376,67 @@ extern "C" uint64_t atsc_rolling_outputs(uint64_t count, uint64_t width, uint64_
     return width && stride && count >= width ? (count - width) / stride + 1 : 0;
 }
 
-// The check of the call's parameters and the records of its ranges (ctx may be null: then no message is kept).
-static int rolling_check(atsc_ctx *ctx, uint64_t n, const uint64_t *count, uint64_t width, uint64_t stride, uint64_t *total)
+// The check of the call's parameters and the records of its ranges (ctx may be null: then no message is kept); `call`
+// names the caller in the message.
+static int rolling_check(atsc_ctx *ctx, const char *call, uint64_t n, const uint64_t *count, uint64_t width, uint64_t stride,
+                         uint64_t *total)
 {
-    if (width == 0 || width > ATSC_ROLLING_MAX_WIDTH) return fail(ctx, ATSC_E_INVALID, "rolling_windows: width outside [1, 2^20]");
-    if (stride == 0) return fail(ctx, ATSC_E_INVALID, "rolling_windows: stride is 0");
+    if (width == 0 || width > ATSC_ROLLING_MAX_WIDTH) return fail_in(ctx, ATSC_E_INVALID, call, "width outside [1, 2^20]");
+    if (stride == 0) return fail_in(ctx, ATSC_E_INVALID, call, "stride is 0");
     uint64_t sum = 0;
     for (uint64_t i = 0; i < n; ++i) {
         sum += atsc_rolling_outputs(count[i], width, stride);
-        if (sum > 0xfffffffeull) return fail(ctx, ATSC_E_INVALID, "rolling_windows: more than 2^32 - 2 records");
+        if (sum > 0xfffffffeull) return fail_in(ctx, ATSC_E_INVALID, call, "more than 2^32 - 2 records");
     }
     if (total) *total = sum;
     return ATSC_OK;
 }
+
+// What differs between the device calls that read every position's window off a pyramid of chunk partials
+// (rolling_dev): the rolling and the rolling deltas.
+struct RollKernel {
+    const char *call;            // names the call in the messages
+    const char *no_kernels;      // ATSC_E_UNSUPPORTED's message
+    const char *launch_name[3];  // ATSC_E_HIP's messages: pyramid, upper, positions
+    const DecodeCaller &who;
+    uint32_t part_bytes;         // a partial of the pyramid: a multiple of 16
+    uint32_t low;                // the lowest stored level
+    uint32_t first;              // a window's chunks are those of [lo + first, lo + w): 0, or 1 where the leaf is a pair
+    uint32_t rec_bytes;          // a position's record
+    decltype(&launch_roll_pyramid) pyramid;
+    decltype(&launch_roll_upper) upper;
+    decltype(&launch_roll_positions) positions;
+    // the pyramid's bytes per sample of the region: the levels low, low + 1, .. hold less than 2 / 2^low partials a sample
+    uint64_t pyramid_bytes() const { return (2ull * part_bytes) >> low; }
+};
 
 // The device call.  Host work, all of it in the stream's index (org: the stream index of the plan's first sample, see
 // reduce_dev): the covering intervals of the ranges' windows (a range's samples behind its last position's window are
 // not decoded), merged where they lie closer than HST_GAP, and cut into pieces of at most Lp samples that overlap by
 // width - 1, so that every position's window lies whole in a piece: the first one that holds it computes it.  A piece
 // lies in the scratch from the multiple of ROLL_TILE at or in front of its first sample on, so that a slot's place in
-// the region and its stream index agree modulo ROLL_TILE; the pyramid of the piece's chunk partials (levels ROLL_LOW ..
-// floor(log2 width), 32 bytes each: at most 8 bytes a sample) follows the region and the spill slots in the same
-// scratch.  Region and pyramid share the budget: a region holds at most half of piece_samples' length, Lr, and a piece
-// Lp = Lr - 3 ROLL_TILE samples.  A width above Lp is ATSC_E_CAPACITY.  Per range and per piece, the run of positions
-// the piece computes is cut into tasks of ROLL_TASK positions.  One upload (decode tasks, tasks, the pieces' level
-// tables); then per piece the decode, the pyramid (with the levels above 11 and above 17 a small launch each) and the
-// positions.
+// the region and its stream index agree modulo ROLL_TILE; the pyramid of the piece's chunk partials (levels K.low ..
+// floor(log2(width - K.first)); the rolling's 32 bytes each: at most 8 bytes a sample, the rolling deltas' 48: at most 12)
+// follows the region and the spill slots in the same scratch.  Region and pyramid share the budget in the proportion of
+// their bytes per sample, 8 to K.pyramid_bytes(): a region holds at most that share of piece_samples' length, Lr (the
+// rolling's half, the rolling deltas' two fifths), and a piece Lp = Lr - 3 ROLL_TILE samples.  A width above Lp is
+// ATSC_E_CAPACITY.  Per range and per piece, the run of positions the piece computes is cut into tasks of ROLL_TASK
+// positions.  One upload (decode tasks, tasks, the pieces' level tables); then per piece the decode, the pyramid (with
+// the levels above 11 and above 17 a small launch each) and the positions.
 static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
-                       const uint64_t *count, uint64_t width, uint64_t stride, void *d_out, void *stream, uint64_t org)
+                       const uint64_t *count, uint64_t width, uint64_t stride, void *d_out, void *stream, uint64_t org,
+                       const RollKernel &K)
 {
-    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count)))
-        return fail(ctx, ATSC_E_INVALID, "rolling_windows: null argument");
+    const char *const CALL = K.call;
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count))) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
     uint64_t total = 0;
-    int rc = rolling_check(ctx, n_windows, count, width, stride, &total);
+    int rc = rolling_check(ctx, CALL, n_windows, count, width, stride, &total);
     if (rc) return rc;
-    if (total && !d_out) return fail(ctx, ATSC_E_INVALID, "rolling_windows: null argument");
-    rc = check_windows(ctx, "rolling_windows", dp, d_out, "d_out", n_windows, begin, count, ~0ull);
+    if (total && !d_out) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    rc = check_windows(ctx, CALL, dp, d_out, "d_out", n_windows, begin, count, ~0ull);
     if (rc || total == 0) return rc;
-    if (!launch_decompress_window || !launch_window_gather || !launch_roll_pyramid || !launch_roll_upper || !launch_roll_positions)
-        return fail(ctx, ATSC_E_UNSUPPORTED, "rolling_windows: no rolling kernels");
+    if (!launch_decompress_window || !launch_window_gather || !K.pyramid || !K.upper || !K.positions)
+        return fail_in(ctx, ATSC_E_UNSUPPORTED, CALL, K.no_kernels);
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const uint64_t W = n_windows, T = ROLL_TILE, w = width;
@@ -2417,13 +2448,16 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
     }
     merge_spans(cov);
     uint64_t spill;
-    const uint64_t Lr = std::max<uint64_t>(AGG_MIN_PIECE, piece_samples(ctx, dp, org, cov, 1, &spill) / 2 / T * T);
+    const uint64_t pyr_bytes = K.pyramid_bytes();
+    const uint64_t L = piece_samples(ctx, dp, org, cov, 1, &spill);
+    const uint64_t Lr = std::max<uint64_t>(AGG_MIN_PIECE, L * sizeof(double) / (sizeof(double) + pyr_bytes) / T * T);
     const uint64_t Lp = Lr - 3 * T;
     if (w > Lp) {
         char msg[192];
         snprintf(msg, sizeof msg,
-                 "rolling_windows: a window of %llu samples does not fit one scratch piece; an aggregate scratch budget of "
-                 "%llu bytes would hold it", (unsigned long long)w, (unsigned long long)((2 * (w + 4 * T) + spill) * sizeof(double)));
+                 "%s: a window of %llu samples does not fit one scratch piece; an aggregate scratch budget of "
+                 "%llu bytes would hold it", CALL, (unsigned long long)w,
+                 (unsigned long long)((w + 4 * T) * (sizeof(double) + pyr_bytes) + spill * sizeof(double)));
         return fail(ctx, ATSC_E_CAPACITY, msg);
     }
     // pieces: samples [first, second) of the stream, ascending; scratch[0] is sample first / T * T
@@ -2456,7 +2490,7 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
             const uint64_t lo = b + j * stride;
             while (p < P && pcs[p].second < lo + w) ++p;  // (a stride longer than a piece skips pieces)
             if (p >= P || pcs[p].first > lo)
-                return fail(ctx, ATSC_E_INVALID, "rolling_windows: internal error (position outside the pieces)");
+                return fail_in(ctx, ATSC_E_INVALID, CALL, "internal error (position outside the pieces)");
             const uint64_t je = std::min(m[i], (pcs[p].second - w - b) / stride + 1);  // positions whose windows end in the piece
             for (; j < je; j += ROLL_TASK)
                 tk.push_back({(uint32_t)p, DevRollTask{b + j * stride, rec + j, (uint32_t)std::min<uint64_t>(ROLL_TASK, je - j), 0}});
@@ -2469,13 +2503,13 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
     group_tasks(tk, P, tasks, at);
     // the levels' places in the pyramid, the same in every piece: level l has room for (region >> l) + 2 chunks
     uint32_t lmax = 0;
-    while (lmax < ROLL_MAX_LEVEL && (2ull << lmax) <= w) ++lmax;
+    while (lmax < ROLL_MAX_LEVEL && (2ull << lmax) <= w - K.first) ++lmax;
     std::vector<DevRollPiece> pieces(P);
     std::vector<Span> dec(P);  // what a piece decodes: its samples and, in front of them, what the ranges cover of its first tile
     uint64_t pyr_n = 0;
     {
         DevRollPiece lv{};
-        for (uint32_t l = ROLL_LOW; l <= lmax; ++l) { lv.off[l] = pyr_n; pyr_n += (region >> l) + 2; }
+        for (uint32_t l = K.low; l <= lmax; ++l) { lv.off[l] = pyr_n; pyr_n += (region >> l) + 2; }
         for (size_t p = 0; p < P; ++p) {
             pieces[p] = lv;
             pieces[p].a0 = pcs[p].first / T * T;
@@ -2485,17 +2519,17 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
     }
     std::vector<PieceDecode> pdec;
     DecodeTasks D;
-    rc = emit_pieces_decode(ctx, "rolling_windows", dp, org, cov, dec, 1, region, D, pdec);
+    rc = emit_pieces_decode(ctx, CALL, dp, org, cov, dec, 1, region, D, pdec);
     if (rc) return rc;
     QueryRes &R = dp->res[Q_ROLLING];
     HIPCHK(ctx, R.wait());
     Upload up;
     D.place(up);
     const size_t off_tasks = up.add(tasks), off_pieces = up.add(pieces);
-    // the scratch: the region, the spill slots, the pyramid (four doubles a partial; region and MAX_FRAME are even numbers
-    // of doubles, so the pyramid begins at a multiple of 16 bytes, as its 16-byte loads and stores need)
+    // the scratch: the region, the spill slots, the pyramid (four or six doubles a partial; region and MAX_FRAME are even
+    // numbers of doubles, so the pyramid begins at a multiple of 16 bytes, as its 16-byte loads and stores need)
     const uint64_t pyr_at = region + (uint64_t)MAX_FRAME * D.spills_used;
-    rc = stage_upload(ctx, R, up, pyr_at + 4 * pyr_n, s);
+    rc = stage_upload(ctx, R, up, pyr_at + K.part_bytes / sizeof(double) * pyr_n, s);
     if (rc) return rc;
     unsigned char *d = R.d;
     double *scr = R.scratch;
@@ -2503,25 +2537,45 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
     const DevRollTask *d_tasks = (const DevRollTask *)(d + off_tasks);
     const DevRollPiece *d_pieces = (const DevRollPiece *)(d + off_pieces);
     for (size_t p = 0; p < P; ++p) {
-        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_ROLLING);
+        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, K.who);
         if (rc) return rc;
         const uint64_t a0 = pieces[p].a0, last = pieces[p].a1 - 1;
-        LAUNCHCHK(ctx, "launch k_roll_pyramid", launch_roll_pyramid(scr, (uint32_t)((pieces[p].a1 - a0) / T), pyr, d_pieces + p, lmax, s));
+        LAUNCHCHK(ctx, K.launch_name[0], K.pyramid(scr, (uint32_t)((pieces[p].a1 - a0) / T), pyr, d_pieces + p, lmax, s));
         for (uint32_t src = ROLL_TILE_LOG; src < lmax; src += 6)
-            LAUNCHCHK(ctx, "launch k_roll_upper",
-                      launch_roll_upper(pyr, d_pieces + p, (uint32_t)(((last >> src) >> 6) - ((a0 >> src) >> 6) + 1), src, lmax, s));
-        LAUNCHCHK(ctx, "launch k_roll_positions",
-                  launch_roll_positions(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, pyr, d_pieces + p, w, stride, d_out, s));
+            LAUNCHCHK(ctx, K.launch_name[1],
+                      K.upper(pyr, d_pieces + p, (uint32_t)(((last >> src) >> 6) - ((a0 >> src) >> 6) + 1), src, lmax, s));
+        LAUNCHCHK(ctx, K.launch_name[2],
+                  K.positions(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, pyr, d_pieces + p, w, stride, d_out, s));
     }
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
 }
 
-// the rolling's descriptor (see AggQuery): the width and the stride are the call's parameters, and the size of its
-// result follows from the ranges' lengths, not from their number and not from the data
-struct RollQuery {
-    static constexpr int INPUTS = 1;
+// The rolling's descriptor (see AggQuery): the width and the stride are the call's parameters, and the size of its result
+// follows from the ranges' lengths, not from their number and not from the data.  KERNEL: whose pyramid and records
+// (RollKernel): the rolling's or the rolling deltas'.
+struct RollKernelPlain {
     static constexpr const char *CALL = "rolling_windows";
+    static RollKernel kernel()
+    {
+        return RollKernel{CALL, "no rolling kernels", {"launch k_roll_pyramid", "launch k_roll_upper", "launch k_roll_positions"},
+                          BY_ROLLING, sizeof(DevAggPart), ROLL_LOW, 0, sizeof(atsc_window_rolling),
+                          &launch_roll_pyramid, &launch_roll_upper, &launch_roll_positions};
+    }
+};
+struct RollKernelDelta {
+    static constexpr const char *CALL = "rolling_delta_windows";
+    static RollKernel kernel()
+    {
+        return RollKernel{CALL, "no rolling delta kernels", {"launch k_rdl_pyramid", "launch k_rdl_upper", "launch k_rdl_positions"},
+                          BY_ROLLING_DELTA, ROLL_DELTA_PART, ROLL_DELTA_LOW, 1, sizeof(atsc_window_delta),
+                          &launch_rdl_pyramid, &launch_rdl_upper, &launch_rdl_positions};
+    }
+};
+template <class KERNEL>
+struct RollQueryOf {
+    static constexpr int INPUTS = 1;
+    static constexpr const char *CALL = KERNEL::CALL;
     uint64_t width, stride;
     const uint64_t *count;  // the call's ranges' lengths
     uint64_t n_ranges;
@@ -2529,16 +2583,18 @@ struct RollQuery {
     {
         uint64_t total = 0;
         for (uint64_t i = 0; count && i < n; ++i) total += atsc_rolling_outputs(count[i], width, stride);
-        return total * sizeof(atsc_window_rolling);
+        return total * KERNEL::kernel().rec_bytes;
     }
-    int check(atsc_ctx *ctx) const { return rolling_check(ctx, count ? n_ranges : 0, count, width, stride, nullptr); }
+    int check(atsc_ctx *ctx) const { return rolling_check(ctx, CALL, count ? n_ranges : 0, count, width, stride, nullptr); }
     static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
     int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
             const uint64_t *cnt, void *d_res, void *stream, uint64_t org) const
     {
-        return rolling_dev(ctx, dp, d_body, n_windows, begin, cnt, width, stride, d_res, stream, org);
+        return rolling_dev(ctx, dp, d_body, n_windows, begin, cnt, width, stride, d_res, stream, org, KERNEL::kernel());
     }
 };
+using RollQuery = RollQueryOf<RollKernelPlain>;
+using RollDeltaQuery = RollQueryOf<RollKernelDelta>;
 
 extern "C" int atsc_rolling_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
                                         const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
@@ -2555,6 +2611,26 @@ extern "C" int atsc_rolling_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t
 {
     ATSC_API_BEGIN
     return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, RollQuery{width, stride, count, n_windows});
+    ATSC_API_END
+}
+
+// windowed rolling deltas: the deltas' record of the window at every position of sample ranges (atsc_rolling_delta.hip),
+// through the rolling's device call: its tables and scratch are the rolling's, dp->res[Q_ROLLING]
+extern "C" int atsc_rolling_delta_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                              const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                              atsc_window_delta *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    return RollDeltaQuery{width, stride, count, n_windows}.dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    ATSC_API_END
+}
+
+extern "C" int atsc_rolling_delta_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                          const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                          atsc_window_delta *out)
+{
+    ATSC_API_BEGIN
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, RollDeltaQuery{width, stride, count, n_windows});
     ATSC_API_END
 }
 
@@ -3181,6 +3257,14 @@ extern "C" int atsc_stream_rolling_windows(atsc_stream *s, uint64_t n_windows, c
 {
     ATSC_API_BEGIN
     return query_stream(s, n_windows, begin, count, out, RollQuery{width, stride, count, n_windows});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_rolling_delta_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                                 uint64_t width, uint64_t stride, atsc_window_delta *out)
+{
+    ATSC_API_BEGIN
+    return query_stream(s, n_windows, begin, count, out, RollDeltaQuery{width, stride, count, n_windows});
     ATSC_API_END
 }
 

@@ -227,11 +227,16 @@ def _rolling_block(n, cargs):
     return WINDOW_ROLLING.itemsize * cargs.records
 
 
-def _rolling_result(run, counts, width, stride):
-    """run(records) -> the block of a rolling call as uint64 words.  -> (records, off): the WINDOW_ROLLING records of
-    every position, range after range, and the ranges' record offsets (rolling_offsets)"""
+def _rolling_delta_block(n, cargs):
+    return WINDOW_DELTA.itemsize * cargs.records
+
+
+def _rolling_result(run, counts, width, stride, record=WINDOW_ROLLING):
+    """run(records) -> the block of a rolling call as uint64 words.  -> (records, off): the `record` records
+    (WINDOW_ROLLING; the rolling deltas': WINDOW_DELTA) of every position, range after range, and the ranges' record
+    offsets (rolling_offsets)"""
     off = rolling_offsets(counts, width, stride)
-    return run(int(off[-1])).view(WINDOW_ROLLING), off
+    return run(int(off[-1])).view(record), off
 
 
 def _across_params(stride, records):
@@ -318,6 +323,7 @@ _EXTREMES = _Query("extremes_windows", _extremes_dtype, None, _extremes_params)
 _VALUES = _Query("values_windows", _values_dtype, None, _values_params)
 _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _select_block)
 _ROLLING = _Query("rolling_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_block)
+_ROLLING_DELTA = _Query("rolling_delta_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_delta_block)
 _ACROSS = _Query("across_windows", np.dtype(np.uint64), None, _across_params, _across_block, inputs=None)
 _ACROSS_QUANTILE = _Query("across_quantile_windows", np.dtype(np.uint64), None, _across_quantile_params, _across_quantile_block,
                           inputs=None)
@@ -681,6 +687,14 @@ class Context:
         return _rolling_result(lambda m: _query_host(_ROLLING, self, records, begins, counts, has_count, width, stride, m),
                                counts, width, stride)
 
+    def rolling_delta_windows_host(self, records, begins, counts, width, stride=1, has_count=False):
+        """-> (records, off): the deltas' record (pairs, rises, falls, their sums and largest steps) of the window of
+        `width` samples at every `stride`-th position of every range [begins[i], begins[i] + counts[i]) of the decoded
+        records (atsc_rolling_delta_windows).  records: a WINDOW_DELTA array, range after range, which delta_derive
+        takes; off: as rolling_windows_host's"""
+        return _rolling_result(lambda m: _query_host(_ROLLING_DELTA, self, records, begins, counts, has_count, width, stride, m),
+                               counts, width, stride, WINDOW_DELTA)
+
     def across_windows_host(self, records_list, begins, counts, stride=1, has_count=False):
         """-> (records, off): count / min / max / sum over the streams of records_list (at most ACROSS_MAX_STREAMS
         decoded record streams, sample j of one going with sample j of every other) at every `stride`-th position of
@@ -902,6 +916,15 @@ class DPlan:
         (rolling_offsets)"""
         off = rolling_offsets(counts, width, stride)
         _query_dev(_ROLLING, self, d_body, begins, counts, d_out, stream, width, stride, int(off[-1]))
+        return off
+
+    def rolling_delta_windows(self, d_body, begins, counts, width, stride, d_out, stream=0):
+        """Enqueues the deltas' record of the window of `width` samples at every `stride`-th position of the ranges
+        [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least 64 bytes per position
+        (atsc_rolling_delta_windows_dev; WINDOW_DELTA records, range after range).  -> the ranges' record offsets
+        (rolling_offsets)"""
+        off = rolling_offsets(counts, width, stride)
+        _query_dev(_ROLLING_DELTA, self, d_body, begins, counts, d_out, stream, width, stride, int(off[-1]))
         return off
 
     def across_windows(self, d_body, others, other_bodies, begins, counts, d_out, stride=1, stream=0):

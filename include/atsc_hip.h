@@ -818,6 +818,47 @@ int atsc_rolling_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, 
                          const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
                          atsc_window_rolling *out);
 
+/* Windowed rolling deltas: the deltas' record (atsc_window_delta, 64 bytes) of the sliding window at every position of
+ * ranges of the decoded stream: `increase(x[5m])`, `resets(x[5m])` and the total variation evaluated at every step,
+ * without listing one window per position for atsc_delta_windows.
+ *   Ranges     Ranges, width, stride, the number and the order of the records (atsc_rolling_outputs), the limits
+ *              1 <= width <= ATSC_ROLLING_MAX_WIDTH and 2^32 - 2 records, validation, the errors (ATSC_E_INVALID with
+ *              nothing written and before any GPU work; ATSC_E_FORMAT or the plan's status word for a malformed payload
+ *              inside a position's window), pieces and ATSC_E_CAPACITY are atsc_rolling_windows'.  The messages name
+ *              rolling_delta_windows.
+ *   Pairs      For the position whose window is [lo, lo + w) the pairs are those of the stream indices lo < j < lo + w,
+ *              exactly as atsc_delta_windows defines them for (begin, count) = (lo, w): what is counted, what a rise and
+ *              a fall is, the terms, and the NaN handling.
+ *   pairs, rises, falls, max_rise, max_fall   atsc_delta_windows' of that window, bit for bit (exact in any order).
+ *   up, down, after_falls   in the rolling's order, over pair slots.  For each sum c:
+ *              term_c(j) = the deltas' term of pair j for sum c, or -0.0 (a pair that is not counted or of the wrong
+ *              direction).
+ *              T(a, 0) = term(a); T(a, l) = T(a, l - 1) + T(a + 2^(l-1), l - 1), for a a multiple of 2^l in the stream
+ *              index.
+ *              The window's chunks are the canonical chunks of [lo + 1, lo + w), left to right: pos = lo + 1; while
+ *              pos < lo + w, take the largest l with pos % 2^l == 0 and pos + 2^l <= lo + w, emit (pos, l),
+ *              pos += 2^l.  sum = ((T(c_1) + T(c_2)) + T(c_3)) + ..., every operation one correctly rounded f64 add.
+ *              A sum without a term is +0.0: up where rises == 0, down and after_falls where falls == 0.
+ *              With u = 2^-53 and L = max(1, ceil(log2 w)), for finite data |up - exact| <= (3 L + 1) u up_exact, and
+ *              likewise for down (one rounding for the subtract, then the rolling's 3 L).  On integer samples whose
+ *              sums stay below 2^53 all three sums are exact, and then equal atsc_delta_windows' bit for bit; otherwise
+ *              they MAY DIFFER from atsc_delta_windows' in their last bits, each within its own stated bound.
+ * Width 1 gives the all-zero record.  A position's bytes depend on the stream's samples and (lo, w) only: not on the
+ * range the window came from, the stride, the other ranges, the budget, the piece boundaries, the framing, the host or
+ * the device call.  atsc_delta_derive applies to the records unchanged.
+ * The chunk partials are 48 bytes (the rolling's: 32), at most 12 bytes a sample beside the 8 of the decoded sample, inside
+ * the budget of atsc_ctx_set_aggregate_scratch as the rolling's are; the default budget holds every width.
+ * begin / count are HOST arrays; d_body and d_out are device memory (d_out 8-byte aligned, 64 bytes per record).  Enqueued
+ * on `stream`, not synchronised.  The call keeps its tables and scratch in the rolling's place of the plan: a rolling
+ * call and a rolling delta call on the same plan wait (host side) for each other. */
+int atsc_rolling_delta_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                   const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                   atsc_window_delta *d_out, void *stream);
+/* Host bytes in, host records out, synchronous, as atsc_rolling_windows is; computes the device call's bits. */
+int atsc_rolling_delta_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                               const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                               atsc_window_delta *out);
+
 /* Windowed across: count, min, max and sum over N streams at every position of ranges of the decoded streams (the
  * indices of atsc_decompress_frames): one value per sample index folded across many series -- `sum by (job)(x)`,
  * `max by (zone)(x)`, how many replicas report at this instant and which one is the worst -- without the decoded
@@ -1140,6 +1181,9 @@ int atsc_stream_select_windows(atsc_stream *s, uint64_t n_windows, const uint64_
 /* atsc_rolling_windows over the stream's frames */
 int atsc_stream_rolling_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 uint64_t width, uint64_t stride, atsc_window_rolling *out);
+/* atsc_rolling_delta_windows over the stream's frames */
+int atsc_stream_rolling_delta_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                      uint64_t width, uint64_t stride, atsc_window_delta *out);
 /* atsc_moments_windows over the stream's frames */
 int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 atsc_window_moments *out);
