@@ -260,7 +260,9 @@ DEVI void for_strided(uint32_t tid, uint32_t n, F &&f)
 #pragma unroll
         for (int m = 0; m < (FN + T - 1) / T; ++m) {
             const uint32_t j = tid + (uint32_t)(m * T);
-            if (FN % T == 0 || j < (uint32_t)FN) f(j);
+            // (a slice that lies wholly below FN carries no guard: tid_now hides tid < T from the compiler, which
+            // would otherwise keep a branch region, and a wait of its own for a load inside it, per slice)
+            if ((m + 1) * T <= FN || j < (uint32_t)FN) f(j);
         }
     } else if constexpr (MAXIT != 0) {
 #pragma unroll
@@ -270,6 +272,37 @@ DEVI void for_strided(uint32_t tid, uint32_t n, F &&f)
         }
     } else {
         for (uint32_t j = tid; j < n; j += T) f(j);
+    }
+}
+// Slice m of a hand-unrolled strided walk (j = tid + m * T) against its bound.  CB != 0: the bound at compile time, and
+// a slice that lies wholly below it is in without a test (see for_strided).
+template <int CB, int T>
+DEVI bool slice_in(int m, uint32_t j, uint32_t bound)
+{
+    return (CB != 0 && (m + 1) * T <= CB) || j < bound;
+}
+// A strided copy of cnt >= 1 elements in two steps, so that every load of the walk is in flight before the first store
+// (a guarded load-and-store per slice compiles to one exec-mask region per slice, each with its own wait for its load).
+// The loads carry no guard: a lane past the end reads the last element again, and stores nothing.  CN != 0: cnt at
+// compile time; NS slices cover cnt by the caller's contract.
+template <int CN, int T, int NS, typename V>
+DEVI void walk_load(V (&r)[NS], const V *__restrict__ src, uint32_t tid, uint32_t cnt)
+{
+#pragma unroll
+    for (int m = 0; m < NS; ++m) {
+        if (CN != 0 && m * T >= CN) continue;
+        const uint32_t j = tid + (uint32_t)(m * T);
+        r[m] = src[(CN != 0 && (m + 1) * T <= CN) ? j : min(j, cnt - 1u)];
+    }
+}
+template <int CN, int T, int NS, typename V>
+DEVI void walk_store(const V (&r)[NS], V *dst, uint32_t tid, uint32_t cnt)
+{
+#pragma unroll
+    for (int m = 0; m < NS; ++m) {
+        if (CN != 0 && m * T >= CN) continue;
+        const uint32_t j = tid + (uint32_t)(m * T);
+        if (slice_in<CN, T>(m, j, cnt)) dst[j] = r[m];
     }
 }
 
@@ -653,6 +686,31 @@ DEVI double recip_abs(double g)
         return r;
     }
     return 1.0 / a;
+}
+// recip_abs of a lane's N values in straight-line code, the same bits: the fast reciprocal of every value without a
+// test (it neither traps nor is kept outside its range), then -- only when some lane of the wavefront holds a value
+// outside the range, one ballot -- the divide of every value, and a select per value.
+template <int N>
+DEVI void recip_abs_all(const double (&g)[N], double (&inv)[N])
+{
+    bool any_out = false;
+#pragma unroll
+    for (int m = 0; m < N; ++m) {
+        const double a = fabs(g[m]);
+        double r = __builtin_amdgcn_rcp(a);
+        r = fma(fma(-a, r, 1.0), r, r);
+        r = fma(fma(-a, r, 1.0), r, r);
+        inv[m] = r;
+        any_out |= !(a > 1e-290 && a < 1e290);
+    }
+    if (__ballot(any_out)) {
+#pragma unroll
+        for (int m = 0; m < N; ++m) {
+            const double a = fabs(g[m]);
+            const double q = 1.0 / a;
+            inv[m] = (a > 1e-290 && a < 1e290) ? inv[m] : q;
+        }
+    }
 }
 // |o - g| / |g| where the weight is not kept: recip_abs's product inside its range, outside it the division itself, as
 // the reference writes it (1 / |g| overflows for subnormal g, and |o - g| * inf is inf where the quotient is finite)

@@ -759,6 +759,7 @@ extern "C" int atsc_plan_create(atsc_ctx *ctx, const uint64_t *frame_off, uint64
             u.slot_stride = stride;
             u.n = f0.n;
             u.plan = f0.plan;
+            u.tw_off = p->tabs.plans[f0.plan].tw_off;
         }
     }
     p->large_tiled = choose_large_tiled(p->class_count[CLASS_LARGE]);
@@ -1232,6 +1233,7 @@ static int compress_impl(atsc_ctx *ctx, const atsc_plan *plan, const double *d_s
                 auto gcd = [](uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; };
                 while (gcd(sp, u.count) != 1) sp += 2;
                 u.spread = sp % u.count;
+                u.spread_m = spread_magic(u.count);
             }
             e = launch_compress_class(c, plan->class_count[c], plan->class_lds[c], d_samples,
                                       plan->d_frames, ids_main + plan->class_first[c],

@@ -157,7 +157,18 @@ struct UniArgs {
     uint32_t n;
     uint32_t plan;
     uint32_t spread, count;  // spread != 0: workgroup b takes frame (b * spread) % count of the class (spread coprime to count)
+    uint64_t spread_m;       // 2^64 / count + 1: (b * spread) % count by two multiplies while b * spread < 2^32 (spread_mod)
+    uint64_t tw_off;         // the plan's DevPlan::tw_off: a frame asks for its twiddles before it has read the plan table
 };
+// x % d for x < 2^32 and 1 <= d < 2^32 from m = 2^64 / d + 1 (Lemire, Kaser, Kurz: "Faster remainder by direct
+// computation", 2019: exact for all 32-bit x and d): the low 64 bits of m * x are the fraction x / d, times d is the rest.
+ATSC_HD constexpr uint64_t spread_magic(uint32_t d) { return d > 1 ? ~0ull / d + 1ull : 0ull; }
+ATSC_HD constexpr uint32_t spread_mod(uint32_t x, uint64_t m, uint32_t d)
+{
+    const uint64_t frac = m * x;  // (mod 2^64)
+    const uint64_t lo = (frac & 0xffffffffull) * d, hi = (frac >> 32) * d + (lo >> 32);  // (frac * d) >> 64, d < 2^32
+    return (uint32_t)(hi >> 32);
+}
 
 // parsed frame record for decompression
 struct DevDFrame {

@@ -353,8 +353,13 @@ __device__ __forceinline__ void compress_frame(
         // every stretch of the launch is a mix of the batch's blocks (results are positional: nothing else changes).
         // (the same for every lane; said so, because a pointer that reached this function through memory makes
         // the load a per-lane one and everything derived from it per-lane arithmetic)
+        // (the remainder by the host's reciprocal, a few scalar multiplies, while the product fits 32 bits -- classes
+        // of up to 65536 frames at least; the software `%` sat on the way to the frame's first load address)
+        const uint64_t dealt = (uint64_t)bid * uni.spread;
         const uint32_t r = uni.adaptive ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(ids[bid] - uni.fid0))
-                           : uni.spread ? (uint32_t)(((uint64_t)bid * uni.spread) % uni.count) : bid;
+                           : !uni.spread ? bid
+                           : (dealt >> 32) == 0 ? spread_mod((uint32_t)dealt, uni.spread_m, uni.count)
+                                                : (uint32_t)(dealt % uni.count);
         fid = uni.fid0 + r;
         fr.sample_off = uni.sample_off0 + (uint64_t)r * uni.n;
         fr.slot_off = uni.slot_off0 + (uint64_t)r * uni.slot_stride;
@@ -414,8 +419,44 @@ __device__ __forceinline__ void compress_frame(
     bool reg_stats = false;
     double rs_mn = 0.0, rs_mx = 0.0;
     uint32_t rs_frac = 0, rs_pk = 0;
-    // ---- load samples (the twiddles follow when the FFT candidate starts: until then and after
-    // its ladder their region hosts `aux` and the RLE group table) ----------------------------
+    // The twiddle table goes to LDS in 16-byte pieces where its place in the pool allows (even L and offset), every
+    // load of the walk in flight before the first LDS write.
+    constexpr int TW4 = (SPL + 1) / 2;  // slices of the 16-byte walk
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    auto tw_copy = [&](const float2 *twp, const bool off_even) {
+        if ((L & 1u) == 0 && off_even) {
+            f32x4 r[TW4];
+            walk_load<FIX ? (int)cL / 2 : 0, T, TW4>(r, (const f32x4 *)twp, tid, L >> 1);
+            walk_store<FIX ? (int)cL / 2 : 0, T, TW4>(r, (f32x4 *)tw, tid, L >> 1);
+        } else {
+            float2 r[SPL];
+            walk_load<FIX ? (int)cL : 0, T, SPL>(r, twp, tid, L);
+            walk_store<FIX ? (int)cL : 0, T, SPL>(r, tw, tid, L);
+        }
+    };
+    // ---- load samples and, one-wavefront frames of a fixed length, the twiddles -----------------
+    // The twiddle region hosts `aux` and the RLE group table before the FFT candidate and after its ladder.  A
+    // fixed-length one-wavefront frame still asks for its table here, ahead of its samples: the table comes from L2
+    // and is in LDS while the frame waits for its samples from HBM, where the FFT candidate used to wait for it
+    // with nothing else to do.  tw_ready (the same in every lane) says that the region still holds the table: who
+    // writes to the region before the FFT candidate clears it (rle_sort_and_group, the only one), and the candidate
+    // then copies the table again.  The address comes from the launch arguments (UniArgs::tw_off): no wait for the
+    // plan table.
+    // Twiddles first: vector loads come back in the order they went out, so behind the samples the table could
+    // only be written once the samples are in -- on the frame's path -- while ahead of them the LDS writes are
+    // done under the samples' latency, for three more address computations in front of the sample loads.  Both
+    // orders were built and timed in alternation: this one 0.1229-0.1234 ms for the 40960 x 256 batch, the other
+    // 0.1238-0.1240 in each of three rounds; the phase stamps do not tell them apart
+    // (profiles/frame_walks_ab.txt).
+    constexpr bool TWPRE = FIX && W == 1 && cL % 2 == 0 && FN != 128;  // (128: the extra state spills)
+    bool tw_ready = false;
+    f32x4 twr[TW4];
+    if constexpr (TWPRE) {
+        tw_ready = (uni.tw_off & 1ull) == 0;
+        if (tw_ready) walk_load<(int)cL / 2, T, TW4>(twr, (const f32x4 *)(twpool + uni.tw_off), tid, cL / 2);
+    }
+#define TW_PUT() do { if constexpr (TWPRE) { \
+        if (tw_ready) walk_store<(int)cL / 2, T, TW4>(twr, (f32x4 *)tw, tid, cL / 2); } } while (0)
     {
         const double *src = samples + fr.sample_off;
         if constexpr (REGSTAT) {
@@ -431,6 +472,7 @@ __device__ __forceinline__ void compress_frame(
                 double2 v[NP];
 #pragma unroll
                 for (int m = 0; m < NP; ++m) v[m] = src2[tid + 64 * m];
+                TW_PUT();
 #pragma unroll
                 for (int m = 0; m < NP; ++m) xs2[tid + 64 * m] = v[m];
                 const double x0 = lane_f64(v[0].x, 0);
@@ -464,6 +506,7 @@ __device__ __forceinline__ void compress_frame(
         } else {
             for (uint32_t j = tid; j < n; j += T) xs[j] = src[j];
         }
+        if (!reg_stats) TW_PUT();
     }
     __syncthreads();
 
@@ -650,6 +693,7 @@ __device__ __forceinline__ void compress_frame(
     // the groups.  Leaves: rrec sorted, aux[i] = heads before i, rhp[g] = index of the first run of
     // group g (rhp[D] = R), rph[g] = header bytes of group g.
     auto rle_sort_and_group = [&](uint32_t *rrec, uint32_t *rhp, uint32_t *rph) {
+        tw_ready = false;  // aux (and rph, where it is rph_std) lie in the twiddle region
         __syncthreads();
         for (uint32_t j = tid; j < n; j += T)
             aux[j] = (j + 1 >= n || xs[j + 1] != xs[j]) ? 1u : 0u;  // run ends (rle.rs:154)
@@ -802,19 +846,21 @@ __device__ __forceinline__ void compress_frame(
     // A payload below 19 bytes (FFT with one bin; Polynomial needs at least 23) already beats both
     // ladders: skip loading their operands.
     if (!(prune && best_size < 19)) {
+        // Straight-line: the reads of all slices (the index is clamped into the frame, so a lane past L reads too
+        // and drops what it read), then all reciprocals (recip_abs_all).  A lane past L holds g = 1, which is inside
+        // the fast reciprocal's range, and weighs 0.
 #pragma unroll
         for (int m = 0; m < SPL; ++m) {
             const uint32_t j = tid + m * T;
-            if (j < L) {
-                int32_t i = (int32_t)j - (int32_t)pre;
-                i = i < 0 ? 0 : (i >= (int32_t)n ? (int32_t)n - 1 : i);
-                g[m] = xs[i];
-                inv[m] = recip_abs(g[m]);
-            } else {
-                g[m] = 1.0;
-                inv[m] = 0.0;
-            }
+            int32_t i = (int32_t)j - (int32_t)pre;
+            i = i < 0 ? 0 : (i >= (int32_t)n ? (int32_t)n - 1 : i);
+            const double x = xs[i];
+            g[m] = slice_in<FIX ? (int)cL : 0, T>(m, j, L) ? x : 1.0;
         }
+        recip_abs_all<SPL>(g, inv);
+#pragma unroll
+        for (int m = 0; m < SPL; ++m)
+            if (!slice_in<FIX ? (int)cL : 0, T>(m, tid + m * T, L)) inv[m] = 0.0;
     }
 
     PH(3);
@@ -1052,9 +1098,9 @@ __device__ __forceinline__ void compress_frame(
             // even a single stored bin is larger than a payload that already passes
         } else {
             rle_early = false;  // AB and the twiddle region (aux) are about to be overwritten
-            {
-                const float2 *twp = twpool + P.tw_off;
-                for_strided<FIX ? (int)cL : 0, T, SPL>(tid, L, [&](uint32_t j) { tw[j] = twp[j]; });
+            if (!tw_ready) {  // (not fetched at the frame's start, or the region was used since)
+                const uint64_t tw_off = P.tw_off;
+                tw_copy(twpool + tw_off, (tw_off & 1ull) == 0);
             }
             float2 *spec;
             if (FIX && chalf) {
@@ -1062,7 +1108,7 @@ __device__ __forceinline__ void compress_frame(
 #pragma unroll
                 for (int m = 0; m < SPL; ++m) {
                     const uint32_t j = tid + m * T;
-                    if (j < L) Af[j] = (float)g[m];
+                    if (slice_in<FIX ? (int)cL : 0, T>(m, j, L)) Af[j] = (float)g[m];
                 }
                 __syncthreads();
                 float2 *Z = fft_forward_fixed<W, FIX ? cM : 2, 2>(A, B, tw);
@@ -1072,7 +1118,7 @@ __device__ __forceinline__ void compress_frame(
 #pragma unroll
                 for (int m = 0; m < SPL; ++m) {
                     const uint32_t j = tid + m * T;
-                    if (j < L) A[j] = make_float2((float)g[m], 0.0f);
+                    if (slice_in<FIX ? (int)cL : 0, T>(m, j, L)) A[j] = make_float2((float)g[m], 0.0f);
                 }
                 __syncthreads();
                 spec = fft_forward_fixed<W, FIX ? cM : 3, 1>(A, B, tw);
@@ -1085,7 +1131,7 @@ __device__ __forceinline__ void compress_frame(
 #pragma unroll
                 for (int m = 0; m < SPL; ++m) {
                     const uint32_t j = tid + m * T;
-                    if (j < L) Af[j] = (float)g[m];
+                    if (slice_in<FIX ? (int)cL : 0, T>(m, j, L)) Af[j] = (float)g[m];
                 }
                 __syncthreads();
                 float2 *Z = fft_forward<W>(P_GENERIC, A, B, tw);
@@ -1095,7 +1141,7 @@ __device__ __forceinline__ void compress_frame(
 #pragma unroll
                 for (int m = 0; m < SPL; ++m) {
                     const uint32_t j = tid + m * T;
-                    if (j < L) A[j] = make_float2((float)g[m], 0.0f);
+                    if (slice_in<FIX ? (int)cL : 0, T>(m, j, L)) A[j] = make_float2((float)g[m], 0.0f);
                 }
                 __syncthreads();
                 spec = fft_forward<W>(P_GENERIC, A, B, tw);
@@ -1121,7 +1167,7 @@ __device__ __forceinline__ void compress_frame(
                     nb[m] = 0;
                     bre[m] = 0.0f;
                     bim[m] = 0.0f;
-                    if (k < bins) {
+                    if (slice_in<FIX ? (int)cL / 2 + 1 : 0, 64>(m, k, bins)) {
                         const float2 z = spec[k];
                         bre[m] = z.x;
                         bim[m] = z.y;
@@ -1366,7 +1412,7 @@ __device__ __forceinline__ void compress_frame(
 #pragma unroll
                                 for (int m = 0; m < KPL; ++m) {
                                     const uint32_t k = tid + 64 * m;
-                                    if (k < bins) {
+                                    if (slice_in<FIX ? (int)cL / 2 + 1 : 0, 64>(m, k, bins)) {
                                         const float nrm = (float)sqrt((double)bre[m] * (double)bre[m] +
                                                                       (double)bim[m] * (double)bim[m]);
                                         keys[k] = ((uint64_t)__float_as_uint(nrm) << 32) | (uint64_t)k;
