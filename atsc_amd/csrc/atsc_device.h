@@ -105,6 +105,50 @@ DEVI void put_u64(uint8_t *p, uint64_t u)
     put_u32(p + 4, (uint32_t)(u >> 32));
 }
 DEVI void put_f64(uint8_t *p, double d) { put_u64(p, (uint64_t)__double_as_longlong(d)); }
+// The same fields as one store each, at any byte address (gfx950 takes unaligned LDS and global accesses: a
+// byte-aligned copy of 2, 4 or 8 bytes is one ds_write / global_store of that width).  WIDE = false: the byte stores.
+template <bool WIDE>
+DEVI void putx_u16(uint8_t *p, uint32_t u)
+{
+    if constexpr (WIDE) { const uint16_t h = (uint16_t)u; __builtin_memcpy(p, &h, 2); }
+    else { p[0] = (uint8_t)u; p[1] = (uint8_t)(u >> 8); }
+}
+template <bool WIDE>
+DEVI void putx_u32(uint8_t *p, uint32_t u)
+{
+    if constexpr (WIDE) __builtin_memcpy(p, &u, 4);
+    else put_u32(p, u);
+}
+template <bool WIDE>
+DEVI void putx_f32(uint8_t *p, float f) { putx_u32<WIDE>(p, __float_as_uint(f)); }
+template <bool WIDE>
+DEVI void putx_f32x2(uint8_t *p, float a, float b)
+{
+    if constexpr (WIDE) {
+        const uint64_t u = (uint64_t)__float_as_uint(a) | ((uint64_t)__float_as_uint(b) << 32);
+        __builtin_memcpy(p, &u, 8);
+    } else {
+        put_f32(p, a);
+        put_f32(p + 4, b);
+    }
+}
+template <bool WIDE>
+DEVI void putx_f64(uint8_t *p, double d)
+{
+    if constexpr (WIDE) __builtin_memcpy(p, &d, 8);
+    else put_f64(p, d);
+}
+template <bool WIDE>
+DEVI uint32_t putx_varint(uint8_t *p, uint64_t v)  // put_varint: the tag byte, then the value as one store
+{
+    if constexpr (!WIDE) return put_varint(p, v);
+    if (v < 251) { p[0] = (uint8_t)v; return 1; }
+    if (v < (1ull << 16)) { p[0] = 251; putx_u16<true>(p + 1, (uint32_t)v); return 3; }
+    if (v < (1ull << 32)) { p[0] = 252; putx_u32<true>(p + 1, (uint32_t)v); return 5; }
+    p[0] = 253;
+    __builtin_memcpy(p + 1, &v, 8);
+    return 9;
+}
 
 // optimizer/utils.rs:115-160  split_n: integer part and "fraction is non-zero"
 DEVI void split_n(double x, int64_t &ip, bool &frac_nz)
@@ -156,6 +200,20 @@ DEVI uint32_t put_value(uint8_t *p, uint32_t bitdepth, double v)
     if (bitdepth == 1) return put_varint(p, zigzag((int64_t)sat_i32(v)));
     put_f64(p, v);
     return 8;
+}
+template <bool WIDE>
+DEVI uint32_t putx_value(uint8_t *p, uint32_t bitdepth, double v)
+{
+    if (bitdepth == 3) { p[0] = (uint8_t)sat_u8(v); return 1; }
+    if (bitdepth == 2) return putx_varint<WIDE>(p, zigzag((int64_t)sat_i16(v)));
+    if (bitdepth == 1) return putx_varint<WIDE>(p, zigzag((int64_t)sat_i32(v)));
+    putx_f64<WIDE>(p, v);
+    return 8;
+}
+// lanes below this one whose bit is set in a wavefront mask (a ballot)
+DEVI uint32_t mask_below(uint64_t m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
 // --------------------------------------------------------------------------------------------

@@ -334,7 +334,18 @@ __device__ __forceinline__ void compress_frame(
     const uint32_t tid = tid_now<W>();  // (opaque: see tid_now)
     uint32_t fid;
     DevFrame fr;
-    const long long t_start = prm.cost ? clock64() : 0;
+    // Fixed-length one-wavefront frames: everything of the launch arguments that stands between the kernel's entry
+    // and the first sample load is asked for here, in one batch of scalar loads behind one wait.  Left to itself the
+    // compiler requests each argument in the block that first uses it: `prm.cost` and `uni.adaptive` for the two
+    // branches at the top, then the UniArgs block and the twiddle pool, then `samples` alone behind the dealing
+    // arithmetic -- three scalar round trips in a row in front of every frame's first vector load.  (The empty
+    // statement only says that the values are in scalar registers at this point; the clock is read unconditionally
+    // for the same reason: no branch on `prm.cost` ahead of the loads.)
+    constexpr bool ARGS1 = FIX_ && W == 1;
+    if constexpr (ARGS1)
+        asm volatile("" ::"s"(samples), "s"(ids), "s"(twpool), "s"(prm.cost), "s"(uni.adaptive), "s"(uni.fid0),
+                     "s"(uni.sample_off0), "s"(uni.spread), "s"(uni.count), "s"(uni.spread_m), "s"(uni.tw_off));
+    const long long t_start = (ARGS1 || prm.cost) ? clock64() : 0;
 #ifdef ATSC_STAMPS
     __shared__ unsigned long long ph_acc[16];
     if (tid < 16) ph_acc[tid] = 0;
@@ -356,12 +367,15 @@ __device__ __forceinline__ void compress_frame(
         // (the remainder by the host's reciprocal, a few scalar multiplies, while the product fits 32 bits -- classes
         // of up to 65536 frames at least; the software `%` sat on the way to the frame's first load address)
         const uint64_t dealt = (uint64_t)bid * uni.spread;
-        const uint32_t r = uni.adaptive ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(ids[bid] - uni.fid0))
+        // (ids[] through the constant address space, as the plan table below: read-only for the life of the kernel, and
+        // a scalar load)
+        typedef const __attribute__((address_space(4))) uint32_t IdConst;
+        const uint32_t r = uni.adaptive ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(*(IdConst *)(ids + bid) - uni.fid0))
                            : !uni.spread ? bid
                            : (dealt >> 32) == 0 ? spread_mod((uint32_t)dealt, uni.spread_m, uni.count)
                                                 : (uint32_t)(dealt % uni.count);
         fid = uni.fid0 + r;
-        fr.sample_off = uni.sample_off0 + (uint64_t)r * uni.n;
+        fr.sample_off = uni.sample_off0 + (uint64_t)r * (FIX_ ? (uint32_t)FN : uni.n);
         fr.slot_off = uni.slot_off0 + (uint64_t)r * uni.slot_stride;
         fr.n = uni.n;
         fr.plan = uni.plan;
@@ -399,6 +413,19 @@ __device__ __forceinline__ void compress_frame(
     const uint32_t o_sel = FIX ? lay.o_sel : P.o_sel, o_aux = FIX ? lay.o_aux : P.o_aux, o_red = FIX ? lay.o_red : P.o_red;
     const uint32_t o_hist = FIX ? lay.o_hist : P.o_hist;
     const uint32_t kcap = FIX ? ckcap : P.kcap;
+    // Fixed-length one-wavefront frames, the frame's end:
+    //  FFT1B: every bin position is below 251, a one-byte varint (128 and 256 samples: 73 and 145 bins), so record i
+    //         of the FFT payload sits at 9 i -- no offsets to scan, no three-byte positions to count;
+    //  STAGE: the FFT, polynomial and few-runs RLE emitters assemble the payload in LDS (AB + 128: AB is free once the
+    //         ladders are done, and its first 128 bytes are the few-runs records), each field one LDS write of its
+    //         width, and the slot gets it in 16-byte pieces.  Slots start on 16-byte boundaries and are padded to a
+    //         multiple of 16 (atsc_host.cpp), and the packing kernels read `len` bytes: what the last piece carries
+    //         behind the payload is never looked at.  The largest payload, a polynomial that stores every sample
+    //         (8 n + 22 bytes), fits behind the records at every such length.
+    constexpr bool FFT1B = FIX && W == 1 && cL / 2 + 1 <= 251;
+    constexpr bool STAGE = FIX && W == 1 && FN != 128;  // (128: the emitters' extra addresses spill)
+    constexpr uint32_t STG_OFF = 128;
+    static_assert(!STAGE || STG_OFF + ((8u * FN + 22u + 15u) & ~15u) <= lay.ab_bytes, "payload staging fits in AB");
 
     double *xs = (double *)(smem + o_xs);
     float2 *tw = (float2 *)(smem + o_tw);
@@ -419,6 +446,10 @@ __device__ __forceinline__ void compress_frame(
     bool reg_stats = false;
     double rs_mn = 0.0, rs_mx = 0.0;
     uint32_t rs_frac = 0, rs_pk = 0;
+    // run starts as wavefront masks: bit `lane` of rs_fa[m] / rs_fb[m] says that sample 2 * (lane + 64 m) / the one
+    // behind it starts a run.  Read once, by the few-runs RLE sizing right behind the statistics (rle_small_build).
+    constexpr int RNP = REGSTAT ? FN / 128 : 1;
+    uint64_t rs_fa[RNP] = {}, rs_fb[RNP] = {};
     // The twiddle table goes to LDS in 16-byte pieces where its place in the pool allows (even L and offset), every
     // load of the walk in flight before the first LDS write.
     constexpr int TW4 = (SPL + 1) / 2;  // slices of the 16-byte walk
@@ -492,8 +523,11 @@ __device__ __forceinline__ void compress_frame(
                         left = (tid == 0) ? wrap : left;
                     }
                     const uint32_t jx = 2u * (tid + 64u * (uint32_t)m);
-                    if (jx == 0 || a != left) rs_pk += (vlen(jx) << 13) | 1u;
-                    if (b != a) rs_pk += (vlen(jx + 1) << 13) | 1u;
+                    const bool sa = jx == 0 || a != left, sb = b != a;
+                    if (sa) rs_pk += (vlen(jx) << 13) | 1u;
+                    if (sb) rs_pk += (vlen(jx + 1) << 13) | 1u;
+                    rs_fa[m] = __ballot(sa);
+                    rs_fb[m] = __ballot(sb);
                 }
                 reg_stats = true;
             }
@@ -589,9 +623,8 @@ __device__ __forceinline__ void compress_frame(
     // ---- Constant: frame/mod.rs:82-88 (auto shortcut) or forced (constant.rs:135-139) ------
     if (mode == ATSC_CONSTANT || (mode == ATSC_AUTO && (LEAN || !prm.trial) && smin == smax)) {
         if (tid == 0) {
-            out[0] = 30;
-            out[1] = (uint8_t)bitdepth;
-            const uint32_t vb = put_value(out + 2, bitdepth, smin);
+            putx_u16<STAGE>(out, 30u | (bitdepth << 8));
+            const uint32_t vb = putx_value<STAGE>(out + 2, bitdepth, smin);
             res[fid].err = 0.0;
             res[fid].len = 2 + vb;
             res[fid].chosen = ATSC_CONSTANT;
@@ -744,31 +777,64 @@ __device__ __forceinline__ void compress_frame(
     //  group: sorted run i sits in lane i; a group head differs from its left neighbour (row_shr:1,
     //         R <= 16 keeps everything in DPP row 0); the ballot of the heads gives the group count
     //         and every group's length; header / index bytes are prefix sums across lanes.
+    //  build from the register flags (REGSTAT frames at an even sample offset, the sizing right behind the
+    //         statistics): the run starts were found when the samples arrived (rs_fa / rs_fb).  Sample order is
+    //         chunk m, lane, half of the pair, so a start's rank is the starts of the chunks before (popcounts),
+    //         those of the lanes below in its own chunk (mbcnt of the two masks) and, for a second half, the first
+    //         half's flag.  Only the at most 16 run starts go to LDS: no walk over the samples, no scan.
     bool rle_small = false;
-    struct RleLane { uint32_t rec, cnt, hb, D, hb_total; bool head, live; };
-    auto rle_small_build = [&]() {
+    struct RleLane { uint32_t rec, cnt, hb, hbs, D, hb_total; bool head, live; };  // hbs: header bytes up to and including this run's group
+    // Where the frame can afford a register for it (REGSTAT: 256 and 512 samples), lane i keeps sorted record i from
+    // the sizing to the emitter (rle_rec): the record reaches its lane by a lane permute instead of through AB, and the
+    // emitter needs no second build after a ladder has overwritten AB.
+    constexpr bool RLEKEEP = REGSTAT;
+    uint32_t rle_rec = 0;
+    auto rle_small_build = [&](const bool from_flags) {
         uint32_t *srt = (uint32_t *)AB, *ends = srt + 16;
-        __syncthreads();
-        const uint32_t C = (n + 63) >> 6, j0 = tid * C;
-        uint32_t cnt = 0;
-        for (uint32_t k = 0; k < C; ++k) {
-            const uint32_t j = j0 + k;
-            if (j < n && (j + 1 >= n || xs[j + 1] != xs[j])) ++cnt;
-        }
-        uint32_t pos = wave_incl_scan_u32(cnt) - cnt;
-        for (uint32_t k = 0; k < C; ++k) {
-            const uint32_t j = j0 + k;
-            if (j < n && (j + 1 >= n || xs[j + 1] != xs[j])) ends[pos++] = j;
-        }
         __syncthreads();
         const uint32_t R = rle_R;
         uint32_t rec = 0, klo = 0, khi = 0;
-        if (tid < R) {
-            const uint32_t e = ends[tid], st = tid ? ends[tid - 1] + 1 : 0;
-            rec = (st << 16) | e;
-            const uint64_t key = (uint64_t)__double_as_longlong(xs[e]);
-            klo = (uint32_t)key;
-            khi = (uint32_t)(key >> 32);
+        if (REGSTAT && from_flags) {
+            uint32_t *starts = ends;
+            uint32_t base = 0;
+#pragma unroll
+            for (int m = 0; m < RNP; ++m) {
+                const uint64_t fa = rs_fa[m], fb = rs_fb[m];
+                const bool sa = ((fa >> tid) & 1ull) != 0, sb = ((fb >> tid) & 1ull) != 0;
+                const uint32_t at = base + mask_below(fa) + mask_below(fb);  // (< R <= 16 wherever a flag is set)
+                const uint32_t jx = 2u * (tid + 64u * (uint32_t)m);
+                if (sa) starts[at] = jx;
+                if (sb) starts[at + (sa ? 1u : 0u)] = jx + 1;
+                base += (uint32_t)__popcll(fa) + (uint32_t)__popcll(fb);
+            }
+            __syncthreads();
+            if (tid < R) {
+                const uint32_t st = starts[tid], e = (tid + 1 < R) ? starts[tid + 1] - 1 : n - 1;
+                rec = (st << 16) | e;
+                const uint64_t key = (uint64_t)__double_as_longlong(xs[e]);
+                klo = (uint32_t)key;
+                khi = (uint32_t)(key >> 32);
+            }
+        } else {
+            const uint32_t C = (n + 63) >> 6, j0 = tid * C;
+            uint32_t cnt = 0;
+            for (uint32_t k = 0; k < C; ++k) {
+                const uint32_t j = j0 + k;
+                if (j < n && (j + 1 >= n || xs[j + 1] != xs[j])) ++cnt;
+            }
+            uint32_t pos = wave_incl_scan_u32(cnt) - cnt;
+            for (uint32_t k = 0; k < C; ++k) {
+                const uint32_t j = j0 + k;
+                if (j < n && (j + 1 >= n || xs[j + 1] != xs[j])) ends[pos++] = j;
+            }
+            __syncthreads();
+            if (tid < R) {
+                const uint32_t e = ends[tid], st = tid ? ends[tid - 1] + 1 : 0;
+                rec = (st << 16) | e;
+                const uint64_t key = (uint64_t)__double_as_longlong(xs[e]);
+                klo = (uint32_t)key;
+                khi = (uint32_t)(key >> 32);
+            }
         }
         uint32_t rank = 0;
         for (uint32_t q = 0; q < R; ++q) {  // runs are in start order: q < tid  <=>  start_q < start_tid
@@ -777,15 +843,22 @@ __device__ __forceinline__ void compress_frame(
             const bool less = qhi < khi || (qhi == khi && (qlo < klo || (qlo == klo && q < tid)));
             rank += less ? 1u : 0u;
         }
-        if (tid < R) srt[rank] = rec;
-        __syncthreads();
+        if constexpr (RLEKEEP) {
+            // lane `rank` takes the record straight from this lane (a forward permute; the idle lanes aim at lane 63,
+            // which holds no run: R <= 16): no write to AB, no wait, no read
+            const uint32_t got = (uint32_t)__builtin_amdgcn_ds_permute((int)(((tid < R) ? rank : 63u) << 2), (int)rec);
+            rle_rec = (tid < R) ? got : 0u;
+        } else {
+            if (tid < R) srt[rank] = rec;
+            __syncthreads();
+        }
     };
-    auto rle_small_group = [&]() -> RleLane {
+    auto rle_small_group = [&](const bool kept) -> RleLane {  // kept: the lane's record is in rle_rec, not in AB
         const uint32_t *srt = (const uint32_t *)AB;
         const uint32_t R = rle_R;
         RleLane g;
         g.live = tid < R;
-        g.rec = g.live ? srt[tid] : 0u;
+        g.rec = kept ? rle_rec : g.live ? srt[tid] : 0u;
         const uint64_t key = g.live ? (uint64_t)__double_as_longlong(xs[g.rec & 0xffffu]) : 0ull;
         const uint32_t plo = dpp_u32<0x111, 0xf>((uint32_t)key), phi = dpp_u32<0x111, 0xf>((uint32_t)(key >> 32));
         g.head = g.live && (tid == 0 || plo != (uint32_t)key || phi != (uint32_t)(key >> 32));
@@ -795,7 +868,8 @@ __device__ __forceinline__ void compress_frame(
         const uint32_t next = after ? tid + 1 + (uint32_t)__builtin_ctzll(after) : R;
         g.cnt = next - tid;
         g.hb = g.head ? value_bytes(bitdepth, xs[g.rec & 0xffffu]) + vlen(g.cnt) : 0u;
-        g.hb_total = wave_sum_u32(g.hb);
+        g.hbs = wave_incl_scan_u32(g.hb);
+        g.hb_total = (uint32_t)__builtin_amdgcn_readlane((int)g.hbs, 63);
         return g;
     };
     if (run_rle) {
@@ -819,8 +893,8 @@ __device__ __forceinline__ void compress_frame(
         const uint32_t minval = (bitdepth == 0) ? 8u : 1u;
         rle_lb = 3 + rle_ib + (rle_R >= 2 ? 2u : 1u) * (minval + 1);
         if (W == 1 && rle_R <= 16 && ab_bytes >= 128) {
-            rle_small_build();
-            const RleLane g = rle_small_group();
+            rle_small_build(reg_stats);
+            const RleLane g = rle_small_group(RLEKEEP);
             rle_D = g.D;
             rle_size = 2 + vlen(g.D) + g.hb_total + rle_ib;
             rle_small = true;
@@ -1439,7 +1513,7 @@ __device__ __forceinline__ void compress_frame(
                         z = spec[pos];
                     }
                     if (tid == 0) { sel[used].pos = pos; sel[used].re = z.x; sel[used].im = z.y; }
-                    big += (pos >= 251) ? 1u : 0u;
+                    if constexpr (!FFT1B) big += (pos >= 251) ? 1u : 0u;
                     // fft.rs:401-422 mirror: bin 0 and (for even L) bin L/2 contribute once;
                     // the 1/L of fft.rs:343 is folded into the coefficient
                     const double cf = ((pos == 0 || 2 * pos == L) ? 1.0 : 2.0) * invL;
@@ -1587,22 +1661,33 @@ __device__ __forceinline__ void compress_frame(
         }
         return;
     }
+    // where the FFT, polynomial and few-runs RLE emitters write: the staging region in LDS, or the slot itself
+    uint8_t *const ob = STAGE ? AB + STG_OFF : out;
+    bool staged = STAGE;
     if (chosen == ATSC_FFT) {  // fft.rs:119-130
         const uint32_t hdr = 1 + vlen(fft_k);
-        for (uint32_t i = tid; i < fft_k; i += T) aux[i] = vlen(sel[i].pos) + 8;
-        __syncthreads();
-        const uint32_t body = block_excl_scan<W>(aux, fft_k, wsum);
-        for (uint32_t i = tid; i < fft_k; i += T) {
-            uint8_t *p = out + hdr + aux[i];
-            p += put_varint(p, sel[i].pos & 0xffffu);  // `pos as u16` (fft.rs:242)
-            put_f32(p, sel[i].re);
-            put_f32(p + 4, sel[i].im);
+        uint32_t body;
+        if constexpr (FFT1B) {
+            body = 9 * fft_k;
+            for (uint32_t i = tid; i < fft_k; i += T) {
+                uint8_t *p = ob + hdr + 9 * i;
+                p[0] = (uint8_t)sel[i].pos;
+                putx_f32x2<STAGE>(p + 1, sel[i].re, sel[i].im);
+            }
+        } else {
+            for (uint32_t i = tid; i < fft_k; i += T) aux[i] = vlen(sel[i].pos) + 8;
+            __syncthreads();
+            body = block_excl_scan<W>(aux, fft_k, wsum);
+            for (uint32_t i = tid; i < fft_k; i += T) {
+                uint8_t *p = ob + hdr + aux[i];
+                p += putx_varint<STAGE>(p, sel[i].pos & 0xffffu);  // `pos as u16` (fft.rs:242)
+                putx_f32x2<STAGE>(p, sel[i].re, sel[i].im);
+            }
         }
         if (tid == 0) {
-            out[0] = 15;
-            put_varint(out + 1, fft_k);
-            put_f32(out + hdr + body, mxf);
-            put_f32(out + hdr + body + 4, mnf);
+            ob[0] = 15;
+            putx_varint<STAGE>(ob + 1, fft_k);
+            putx_f32x2<STAGE>(ob + hdr + body, mxf, mnf);
         }
         out_len = hdr + body + 8;
     } else if (chosen == ATSC_POLYNOMIAL || chosen == ATSC_IDW) {  // polynomial.rs:54-87
@@ -1613,8 +1698,17 @@ __device__ __forceinline__ void compress_frame(
             body = poly_K * vbytes;
             for (uint32_t k = tid; k < poly_K; k += T) {
                 const uint32_t t = (k == poly_K - 1) ? (n - 1) : k * poly_step;
-                put_value(out + hdr + k * vbytes, bitdepth, xs[t]);
+                putx_value<STAGE>(ob + hdr + k * vbytes, bitdepth, xs[t]);
             }
+        } else if (STAGE && poly_K <= 64) {
+            // one point per lane: its offset is a prefix sum across the wavefront, no scan through LDS
+            const bool on = tid < poly_K;
+            const uint32_t t = !on ? 0u : (tid == poly_K - 1) ? (n - 1) : tid * poly_step;
+            const double v = xs[t];
+            const uint32_t vb = on ? value_bytes(bitdepth, v) : 0u;
+            const uint32_t in = wave_incl_scan_u32(vb);
+            body = (uint32_t)__builtin_amdgcn_readlane((int)in, 63);
+            if (on) putx_value<STAGE>(ob + hdr + (in - vb), bitdepth, v);
         } else {
             for (uint32_t k = tid; k < poly_K; k += T) {
                 const uint32_t t = (k == poly_K - 1) ? (n - 1) : k * poly_step;
@@ -1624,38 +1718,37 @@ __device__ __forceinline__ void compress_frame(
             body = block_excl_scan<W>(aux, poly_K, wsum);
             for (uint32_t k = tid; k < poly_K; k += T) {
                 const uint32_t t = (k == poly_K - 1) ? (n - 1) : k * poly_step;
-                put_value(out + hdr + aux[k], bitdepth, xs[t]);
+                putx_value<STAGE>(ob + hdr + aux[k], bitdepth, xs[t]);
             }
         }
         if (tid == 0) {
-            out[0] = idw ? 1 : 0;  // PolynomialType::{Polynomial, Idw}
-            out[1] = (uint8_t)bitdepth;
-            put_varint(out + 2, poly_K);
-            put_f64(out + hdr + body, smin);
-            put_f64(out + hdr + body + 8, smax);
-            out[hdr + body + 16] = (uint8_t)poly_step;  // `step as u8`
+            putx_u16<STAGE>(ob, (idw ? 1u : 0u) | (bitdepth << 8));  // PolynomialType::{Polynomial, Idw}, bitdepth
+            putx_varint<STAGE>(ob + 2, poly_K);
+            putx_f64<STAGE>(ob + hdr + body, smin);
+            putx_f64<STAGE>(ob + hdr + body + 8, smax);
+            ob[hdr + body + 16] = (uint8_t)poly_step;  // `step as u8`
         }
         out_len = hdr + body + 17;
     } else if (rle_small) {  // RLE with one run per lane: rle.rs:40-67
-        if (!rle_early) rle_small_build();  // a ladder overwrote the sorted records
-        const RleLane g = rle_small_group();
+        if (!RLEKEEP && !rle_early) rle_small_build(false);  // a ladder overwrote the sorted records
+        const RleLane g = rle_small_group(RLEKEEP);
         const uint32_t hdr = 2 + vlen(g.D);
         const uint32_t st = g.rec >> 16, vl = g.live ? vlen(st) : 0u;
         const uint32_t vls = wave_incl_scan_u32(vl);  // index varint bytes up to and including this run
-        const uint32_t hbs = wave_incl_scan_u32(g.hb);  // header bytes up to and including this run's group
+        const uint32_t hbs = g.hbs;
         if (g.head) {
-            uint8_t *p = out + hdr + (hbs - g.hb) + (vls - vl);
-            p += put_value(p, bitdepth, xs[g.rec & 0xffffu]);
-            put_varint(p, g.cnt);
+            uint8_t *p = ob + hdr + (hbs - g.hb) + (vls - vl);
+            p += putx_value<STAGE>(p, bitdepth, xs[g.rec & 0xffffu]);
+            putx_varint<STAGE>(p, g.cnt);
         }
-        if (g.live) put_varint(out + hdr + hbs + (vls - vl), st);
+        if (g.live) putx_varint<STAGE>(ob + hdr + hbs + (vls - vl), st);
         if (tid == 0) {
-            out[0] = 60;
-            out[1] = (uint8_t)bitdepth;
-            put_varint(out + 2, g.D);
+            putx_u16<STAGE>(ob, 60u | (bitdepth << 8));
+            putx_varint<STAGE>(ob + 2, g.D);
         }
         out_len = hdr + g.hb_total + (uint32_t)__builtin_amdgcn_readlane((int)vls, 63);
     } else {  // RLE: rle.rs:40-67
+        staged = false;  // (up to n runs: the records fill AB, and the payload goes to the slot as before)
         // runs are sorted by (value bits, start); rhp = hp[]; rph = hb[]
         uint32_t *rrec = rrec_std, *rhp = rhp_std, *rph = rph_std;
         if (rle_early) {  // sized before the ladders, and no ladder touched AB since
@@ -1699,6 +1792,15 @@ __device__ __forceinline__ void compress_frame(
             put_varint(out + 2, D);
         }
         out_len = hdr + hb + ibt;
+    }
+    if constexpr (STAGE) {
+        if (staged) {  // the staged payload to the slot, 16 bytes per lane (the last piece may run past out_len: see STAGE)
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            __syncthreads();
+            const u32x4 *s16 = (const u32x4 *)(AB + STG_OFF);
+            u32x4 *d16 = (u32x4 *)out;
+            for (uint32_t c = tid; c < (out_len + 15u) >> 4; c += T) d16[c] = s16[c];
+        }
     }
     PH(12);
 #ifdef ATSC_STAMPS
