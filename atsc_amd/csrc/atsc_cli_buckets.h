@@ -1,7 +1,8 @@
 // atsc_cli_buckets.h -- what the two command lines (atsc_cli.cpp, csv_compressor_cli.cpp) share: the small text helpers
 // and the bucket queries behind `atsc -u --buckets N` and `csv-compressor -u --from --to --step S`: their options, the
 // usage errors, the calls over the buckets and the columns of the .agg.csv; `--rolling W[:S]`, the sliding window's
-// records at every position of a window (with `--rolling-deltas`, its deltas beside them); `--where OP:LIMIT`, the selected samples
+// records at every position of a window (with `--rolling-deltas`, its deltas beside them, with `--rolling-moments`, its
+// moments); `--where OP:LIMIT`, the selected samples
 // of the window itself into a .sel.csv; and `--across A.bro,B.bro,..` (atsc only), the across records of the window over
 // several files into an .across.csv (the end of this file).  The two differ in the row's first cell,
 // in how a failure is reported and in how a position inside a bucket is written: the three run positions, which the
@@ -75,6 +76,7 @@ struct BucketOptions {
     uint64_t rolling = 0;  // --rolling W[:S]: no bucket query; the window's rolling records into .roll.csv
     uint64_t rolling_stride = 1;
     bool rolling_deltas = false;  // --rolling-deltas: pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase behind .roll.csv's own
+    bool rolling_moments = false;  // --rolling-moments: nonnan,avg,stdvar,stddev,slope,intercept behind those
     bool across_allowed = false;      // the front end takes --across (atsc; csv-compressor does not: DESIGN.md "Windowed across")
     std::vector<std::string> across;  // --across A.bro,B.bro,..: no bucket query; the window's across records into .across.csv
     uint64_t across_stride = 1;       // --across-stride S
@@ -274,6 +276,8 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
         }
     } else if (s == "--rolling-deltas") {
         o.rolling_deltas = true;
+    } else if (s == "--rolling-moments") {
+        o.rolling_moments = true;
     } else if (value("--extremes")) {
         if (!parse_int(v, 1, ATSC_EXTREMES_MAX_K, o.extremes)) {
             fprintf(stderr, "error: invalid value '%s' for '--extremes': expected 1..=%d\n", v.c_str(), (int)ATSC_EXTREMES_MAX_K);
@@ -377,12 +381,13 @@ bool where_option_complete(const BucketOptions &o, const char *window, bool wind
 }
 
 // --rolling goes with the option that names the window and without the one that cuts buckets, as --where does, and
-// not with --where; --rolling-deltas goes with --rolling.  false: a usage error, reported on stderr.
+// not with --where; --rolling-deltas and --rolling-moments go with --rolling.  false: a usage error, reported on stderr.
 bool rolling_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
 {
     if (!o.rolling) {
         if (o.rolling_deltas) fprintf(stderr, "error: '--rolling-deltas' needs '--rolling'\n");
-        return !o.rolling_deltas;
+        if (o.rolling_moments) fprintf(stderr, "error: '--rolling-moments' needs '--rolling'\n");
+        return !o.rolling_deltas && !o.rolling_moments;
     }
     if (!windowed) {
         fprintf(stderr, "error: '--rolling' needs '%s'\n", window);
@@ -637,36 +642,50 @@ bool where_write(const std::string &path, const char *first, const std::vector<a
 }
 
 // --rolling: one record per position of the range [begin, begin + count) of a .bro image; deltas: with --rolling-deltas,
-// the same positions' rolling deltas and what atsc_delta_derive reads off them
+// the same positions' rolling deltas and what atsc_delta_derive reads off them; moments: with --rolling-moments, the
+// same positions' rolling moments
 int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
                   std::vector<atsc_window_rolling> &rows, std::vector<atsc_window_delta> &deltas,
-                  std::vector<atsc_window_delta_fit> &fits)
+                  std::vector<atsc_window_delta_fit> &fits, std::vector<atsc_window_moments> &moments)
 {
     rows.assign(atsc_rolling_outputs(count, o.rolling, o.rolling_stride), atsc_window_rolling{});
     atsc_window_rolling none;
     int rc = atsc_rolling_windows(ctx, bro + 9, len - 9, 1, 1, &begin, &count, o.rolling, o.rolling_stride,
                                   rows.empty() ? &none : rows.data());
-    if (rc || !o.rolling_deltas) return rc;
-    deltas.assign(rows.size(), atsc_window_delta{});
-    fits.assign(rows.size(), atsc_window_delta_fit{});
-    atsc_window_delta none_d;
-    rc = atsc_rolling_delta_windows(ctx, bro + 9, len - 9, 1, 1, &begin, &count, o.rolling, o.rolling_stride,
-                                    deltas.empty() ? &none_d : deltas.data());
-    if (!rc && !deltas.empty()) rc = atsc_delta_derive(deltas.data(), deltas.size(), fits.data());
+    if (!rc && o.rolling_deltas) {
+        deltas.assign(rows.size(), atsc_window_delta{});
+        fits.assign(rows.size(), atsc_window_delta_fit{});
+        atsc_window_delta none_d;
+        rc = atsc_rolling_delta_windows(ctx, bro + 9, len - 9, 1, 1, &begin, &count, o.rolling, o.rolling_stride,
+                                        deltas.empty() ? &none_d : deltas.data());
+        if (!rc && !deltas.empty()) rc = atsc_delta_derive(deltas.data(), deltas.size(), fits.data());
+    }
+    if (!rc && o.rolling_moments) {
+        moments.assign(rows.size(), atsc_window_moments{});
+        atsc_window_moments none_m;
+        rc = atsc_rolling_moments_windows(ctx, bro + 9, len - 9, 1, 1, &begin, &count, o.rolling, o.rolling_stride,
+                                          moments.empty() ? &none_m : moments.data());
+    }
     return rc;
 }
 
 // the .roll.csv: `first`,count,min,max,sum,mean and one row per position; place(j): the first cell of position j; values
 // as the .agg.csv writes them, mean = sum / count and empty where count == 0.  with_deltas (--rolling-deltas): behind
-// them pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase.  false: the file could not be written.
+// them pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase.  with_moments (--rolling-moments): behind those
+// nonnan,avg,stdvar,stddev,slope,intercept from the position's record of `moments`: its count and the mean, the
+// population variance and standard deviation, and the least-squares line (slope per sample, intercept at the position's
+// first sample) that atsc_moments_fit reads off it, all six empty where the count is 0 (the count column says so); the
+// column is avg because mean is taken: sum / count in the rolling's order.  false: the file could not be written.
 template <class Place>
 bool rolling_write(const std::string &path, const char *first, const std::vector<atsc_window_rolling> &rows, bool with_deltas,
-                   const std::vector<atsc_window_delta> &deltas, const std::vector<atsc_window_delta_fit> &fits, Place place)
+                   const std::vector<atsc_window_delta> &deltas, const std::vector<atsc_window_delta_fit> &fits,
+                   bool with_moments, const std::vector<atsc_window_moments> &moments, Place place)
 {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return false;
-    fprintf(f, "%s,count,min,max,sum,mean%s\n", first,
-            with_deltas ? ",pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase" : "");
+    fprintf(f, "%s,count,min,max,sum,mean%s%s\n", first,
+            with_deltas ? ",pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase" : "",
+            with_moments ? ",nonnan,avg,stdvar,stddev,slope,intercept" : "");
     for (size_t j = 0; j < rows.size(); ++j) {
         const atsc_window_rolling &r = rows[j];
         fprintf(f, "%s,%llu,%s,%s,%s,%s", place(j).c_str(), (unsigned long long)r.count, debug_f64(r.min).c_str(),
@@ -677,6 +696,14 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
                     (unsigned long long)d.falls, debug_f64(d.up).c_str(), debug_f64(d.down).c_str(),
                     debug_f64(d.after_falls).c_str(), debug_f64(d.max_rise).c_str(), debug_f64(d.max_fall).c_str(),
                     debug_f64(fits[j].increase).c_str());
+        }
+        if (with_moments) {
+            atsc_window_fit fit;
+            atsc_moments_fit(&moments[j], 1, &fit);
+            if (moments[j].count == 0) fprintf(f, ",,,,,,");
+            else fprintf(f, ",%llu,%s,%s,%s,%s,%s", (unsigned long long)moments[j].count, debug_f64(fit.mean).c_str(),
+                         debug_f64(fit.variance).c_str(), debug_f64(fit.stddev).c_str(), debug_f64(fit.slope).c_str(),
+                         debug_f64(fit.intercept).c_str());
         }
         fprintf(f, "\n");
     }

@@ -353,6 +353,12 @@ struct DevRollTask {
 constexpr uint32_t ROLL_DELTA_LOW = 3;    // the lowest stored level
 constexpr uint32_t ROLL_DELTA_PART = 48;  // bytes of a partial: three sums, two maxima, the three counts in one word
 
+// windowed rolling moments (atsc_rolling_moments_windows_dev, atsc_rolling_moments.hip): the rolling's pieces, tasks,
+// pyramid and chunks over nodes of the centred moments of value and position (DevMomPart's fields), the position being
+// the stream index; the highest level is floor(log2 w)
+constexpr uint32_t ROLL_MOMENTS_LOW = 3;    // the lowest stored level
+constexpr uint32_t ROLL_MOMENTS_PART = 48;  // bytes of a partial: the node's five doubles, the count in a 64-bit word
+
 // windowed across (atsc_across_windows_dev, atsc_across.hip): every stream of a call decoded into a scratch region of
 // its own, the same sample at the same slot of every region, then one record per position from its slot of each.  A
 // task is a DevRollTask: n positions of one range inside one piece, the first at sample lo of the streams.

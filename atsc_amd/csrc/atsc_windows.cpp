@@ -103,6 +103,14 @@ __attribute__((weak)) hipError_t launch_rdl_upper(void *pyr, const DevRollPiece 
 __attribute__((weak)) hipError_t launch_rdl_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                       const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
                                                       void *out, hipStream_t s);
+// the windowed rolling moments' pyramid and position kernels (atsc_rolling_moments.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_rmo_pyramid(const double *scratch, uint32_t n_tiles, void *pyr, const DevRollPiece *pc,
+                                                    uint32_t lmax, hipStream_t s);
+__attribute__((weak)) hipError_t launch_rmo_upper(void *pyr, const DevRollPiece *pc, uint32_t n, uint32_t src, uint32_t lmax,
+                                                  hipStream_t s);
+__attribute__((weak)) hipError_t launch_rmo_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
+                                                      const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
+                                                      void *out, hipStream_t s);
 // the windowed across' position kernel (atsc_across.hip; weak for the same reason)
 __attribute__((weak)) hipError_t launch_across_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                          const uint64_t *reg, uint32_t n_streams, uint64_t a0,
@@ -376,7 +384,7 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
                           BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
                           BY_ROLLING = DECODE_CALLER("rolling"), BY_ROLLING_DELTA = DECODE_CALLER("rolling delta"),
-                          BY_ACROSS = DECODE_CALLER("across"),
+                          BY_ROLLING_MOMENTS = DECODE_CALLER("rolling moments"), BY_ACROSS = DECODE_CALLER("across"),
                           BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile"),
                           BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes"),
                           BY_ACROSS_MOMENTS = DECODE_CALLER("across moments");
@@ -2393,7 +2401,7 @@ static int rolling_check(atsc_ctx *ctx, const char *call, uint64_t n, const uint
 }
 
 // What differs between the device calls that read every position's window off a pyramid of chunk partials
-// (rolling_dev): the rolling and the rolling deltas.
+// (rolling_dev): the rolling, the rolling deltas and the rolling moments.
 struct RollKernel {
     const char *call;            // names the call in the messages
     const char *no_kernels;      // ATSC_E_UNSUPPORTED's message
@@ -2416,7 +2424,8 @@ struct RollKernel {
 // width - 1, so that every position's window lies whole in a piece: the first one that holds it computes it.  A piece
 // lies in the scratch from the multiple of ROLL_TILE at or in front of its first sample on, so that a slot's place in
 // the region and its stream index agree modulo ROLL_TILE; the pyramid of the piece's chunk partials (levels K.low ..
-// floor(log2(width - K.first)); the rolling's 32 bytes each: at most 8 bytes a sample, the rolling deltas' 48: at most 12)
+// floor(log2(width - K.first)); the rolling's 32 bytes each: at most 8 bytes a sample, the rolling deltas' and the rolling
+// moments' 48: at most 12)
 // follows the region and the spill slots in the same scratch.  Region and pyramid share the budget in the proportion of
 // their bytes per sample, 8 to K.pyramid_bytes(): a region holds at most that share of piece_samples' length, Lr (the
 // rolling's half, the rolling deltas' two fifths), and a piece Lp = Lr - 3 ROLL_TILE samples.  A width above Lp is
@@ -2553,7 +2562,7 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
 
 // The rolling's descriptor (see AggQuery): the width and the stride are the call's parameters, and the size of its result
 // follows from the ranges' lengths, not from their number and not from the data.  KERNEL: whose pyramid and records
-// (RollKernel): the rolling's or the rolling deltas'.
+// (RollKernel): the rolling's, the rolling deltas' or the rolling moments'.
 struct RollKernelPlain {
     static constexpr const char *CALL = "rolling_windows";
     static RollKernel kernel()
@@ -2570,6 +2579,15 @@ struct RollKernelDelta {
         return RollKernel{CALL, "no rolling delta kernels", {"launch k_rdl_pyramid", "launch k_rdl_upper", "launch k_rdl_positions"},
                           BY_ROLLING_DELTA, ROLL_DELTA_PART, ROLL_DELTA_LOW, 1, sizeof(atsc_window_delta),
                           &launch_rdl_pyramid, &launch_rdl_upper, &launch_rdl_positions};
+    }
+};
+struct RollKernelMoments {
+    static constexpr const char *CALL = "rolling_moments_windows";
+    static RollKernel kernel()
+    {
+        return RollKernel{CALL, "no rolling moments kernels", {"launch k_rmo_pyramid", "launch k_rmo_upper", "launch k_rmo_positions"},
+                          BY_ROLLING_MOMENTS, ROLL_MOMENTS_PART, ROLL_MOMENTS_LOW, 0, sizeof(atsc_window_moments),
+                          &launch_rmo_pyramid, &launch_rmo_upper, &launch_rmo_positions};
     }
 };
 template <class KERNEL>
@@ -2595,6 +2613,7 @@ struct RollQueryOf {
 };
 using RollQuery = RollQueryOf<RollKernelPlain>;
 using RollDeltaQuery = RollQueryOf<RollKernelDelta>;
+using RollMomentsQuery = RollQueryOf<RollKernelMoments>;
 
 extern "C" int atsc_rolling_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
                                         const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
@@ -2631,6 +2650,27 @@ extern "C" int atsc_rolling_delta_windows(atsc_ctx *ctx, const uint8_t *body, ui
 {
     ATSC_API_BEGIN
     return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, RollDeltaQuery{width, stride, count, n_windows});
+    ATSC_API_END
+}
+
+// windowed rolling moments: the moments' record of the window at every position of sample ranges
+// (atsc_rolling_moments.hip), through the rolling's device call: its tables and scratch are the rolling's,
+// dp->res[Q_ROLLING]
+extern "C" int atsc_rolling_moments_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                                const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                                atsc_window_moments *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    return RollMomentsQuery{width, stride, count, n_windows}.dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    ATSC_API_END
+}
+
+extern "C" int atsc_rolling_moments_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                            const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                            atsc_window_moments *out)
+{
+    ATSC_API_BEGIN
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, RollMomentsQuery{width, stride, count, n_windows});
     ATSC_API_END
 }
 
@@ -3265,6 +3305,14 @@ extern "C" int atsc_stream_rolling_delta_windows(atsc_stream *s, uint64_t n_wind
 {
     ATSC_API_BEGIN
     return query_stream(s, n_windows, begin, count, out, RollDeltaQuery{width, stride, count, n_windows});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_rolling_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                                   uint64_t width, uint64_t stride, atsc_window_moments *out)
+{
+    ATSC_API_BEGIN
+    return query_stream(s, n_windows, begin, count, out, RollMomentsQuery{width, stride, count, n_windows});
     ATSC_API_END
 }
 

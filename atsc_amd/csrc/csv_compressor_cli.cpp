@@ -5,7 +5,7 @@
 //
 //   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
 //                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]
-//                  [--extremes K] [--values K[:ABOVE]]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas]]]]
+//                  [--extremes K] [--values K[:ABOVE]]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments]]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
@@ -81,6 +81,10 @@ void usage()
             "      --rolling-deltas           with --rolling: also every position's steps from one sample to the next, as the\n"
             "                                 last columns: pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase\n"
             "                                 (as --deltas; increase = up + after_falls, the counter increase of the window)\n"
+            "      --rolling-moments          with --rolling: also every position's mean, spread and trend, as the last\n"
+            "                                 columns: nonnan,avg,stdvar,stddev,slope,intercept (as --moments: population\n"
+            "                                 forms, slope per sample, intercept at the position's first sample; all empty\n"
+            "                                 where the window holds no sample)\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -189,18 +193,19 @@ int uncompress_rolling(const Args &a, const std::string &output_base, uint8_t *b
     std::vector<atsc_window_rolling> rows;
     std::vector<atsc_window_delta> deltas;
     std::vector<atsc_window_delta_fit> fits;
+    std::vector<atsc_window_moments> moments;
     if (count) {
         atsc_ctx *ctx = nullptr;
         rc = atsc_ctx_create(&ctx, 0);
         if (rc) { atsc_free(bro); return die("no GPU context", rc); }
         rc = atsc_bro_open(bro, len, nullptr, nullptr);
-        if (!rc) rc = rolling_query(ctx, bro, len, a.q, begin, count, rows, deltas, fits);
+        if (!rc) rc = rolling_query(ctx, bro, len, a.q, begin, count, rows, deltas, fits, moments);
         if (rc) { int e = die("rolling", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
         atsc_ctx_destroy(ctx);
     }
     atsc_free(bro);
     const uint64_t w = a.q.rolling, stride = a.q.rolling_stride;
-    if (!rolling_write(with_ext(output_base, "roll.csv"), "timestamp", rows, a.q.rolling_deltas, deltas, fits,
+    if (!rolling_write(with_ext(output_base, "roll.csv"), "timestamp", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments,
                        [&](uint64_t j) { return std::to_string((long long)ts[begin + j * stride + w - 1]); }))
         return die("failed to write rolling records to file");
     return 0;

@@ -231,9 +231,13 @@ def _rolling_delta_block(n, cargs):
     return WINDOW_DELTA.itemsize * cargs.records
 
 
+def _rolling_moments_block(n, cargs):
+    return WINDOW_MOMENTS.itemsize * cargs.records
+
+
 def _rolling_result(run, counts, width, stride, record=WINDOW_ROLLING):
     """run(records) -> the block of a rolling call as uint64 words.  -> (records, off): the `record` records
-    (WINDOW_ROLLING; the rolling deltas': WINDOW_DELTA) of every position, range after range, and the ranges' record
+    (WINDOW_ROLLING; the rolling deltas': WINDOW_DELTA; the rolling moments': WINDOW_MOMENTS) of every position, range after range, and the ranges' record
     offsets (rolling_offsets)"""
     off = rolling_offsets(counts, width, stride)
     return run(int(off[-1])).view(record), off
@@ -324,6 +328,7 @@ _VALUES = _Query("values_windows", _values_dtype, None, _values_params)
 _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _select_block)
 _ROLLING = _Query("rolling_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_block)
 _ROLLING_DELTA = _Query("rolling_delta_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_delta_block)
+_ROLLING_MOMENTS = _Query("rolling_moments_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_moments_block)
 _ACROSS = _Query("across_windows", np.dtype(np.uint64), None, _across_params, _across_block, inputs=None)
 _ACROSS_QUANTILE = _Query("across_quantile_windows", np.dtype(np.uint64), None, _across_quantile_params, _across_quantile_block,
                           inputs=None)
@@ -695,6 +700,14 @@ class Context:
         return _rolling_result(lambda m: _query_host(_ROLLING_DELTA, self, records, begins, counts, has_count, width, stride, m),
                                counts, width, stride, WINDOW_DELTA)
 
+    def rolling_moments_windows_host(self, records, begins, counts, width, stride=1, has_count=False):
+        """-> (records, off): the moments' record (count, mean, m2, t_mean, t_m2, c_tx) of the window of `width` samples
+        at every `stride`-th position of every range [begins[i], begins[i] + counts[i]) of the decoded records
+        (atsc_rolling_moments_windows).  records: a WINDOW_MOMENTS array, range after range, which moments_fit takes
+        (the slope per sample, t_mean from the window's first sample); off: as rolling_windows_host's"""
+        return _rolling_result(lambda m: _query_host(_ROLLING_MOMENTS, self, records, begins, counts, has_count, width, stride, m),
+                               counts, width, stride, WINDOW_MOMENTS)
+
     def across_windows_host(self, records_list, begins, counts, stride=1, has_count=False):
         """-> (records, off): count / min / max / sum over the streams of records_list (at most ACROSS_MAX_STREAMS
         decoded record streams, sample j of one going with sample j of every other) at every `stride`-th position of
@@ -925,6 +938,15 @@ class DPlan:
         (rolling_offsets)"""
         off = rolling_offsets(counts, width, stride)
         _query_dev(_ROLLING_DELTA, self, d_body, begins, counts, d_out, stream, width, stride, int(off[-1]))
+        return off
+
+    def rolling_moments_windows(self, d_body, begins, counts, width, stride, d_out, stream=0):
+        """Enqueues the moments' record of the window of `width` samples at every `stride`-th position of the ranges
+        [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least 48 bytes per position
+        (atsc_rolling_moments_windows_dev; WINDOW_MOMENTS records, range after range).  -> the ranges' record offsets
+        (rolling_offsets)"""
+        off = rolling_offsets(counts, width, stride)
+        _query_dev(_ROLLING_MOMENTS, self, d_body, begins, counts, d_out, stream, width, stride, int(off[-1]))
         return off
 
     def across_windows(self, d_body, others, other_bodies, begins, counts, d_out, stride=1, stream=0):

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import capi
 from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_ROLLING, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit, pair_fit  # noqa: F401
-from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _ROLLING_DELTA, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
+from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _ROLLING_DELTA, _ROLLING_MOMENTS, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
 from .engine import ACROSS_RECORD, _ACROSS, _across_host, _across_list, _across_result  # noqa: F401
 from .engine import _ACROSS_QUANTILE, _across_quantile_result
 from .engine import _ACROSS_EXTREMES, _across_extremes_result
@@ -162,6 +162,13 @@ class CompressedStream:
         return _rolling_result(lambda m: _query_stream(_ROLLING_DELTA, self, begins, counts, width, stride, m), counts, width,
                                stride, WINDOW_DELTA)
 
+    def rolling_moments_windows(self, begins, counts, width, stride=1):
+        """-> (records, off): the moments' record of the window of `width` samples at every `stride`-th position of the
+        ranges [begins[i], begins[i] + counts[i]), as Context.rolling_moments_windows_host gives them
+        (atsc_stream_rolling_moments_windows)"""
+        return _rolling_result(lambda m: _query_stream(_ROLLING_MOMENTS, self, begins, counts, width, stride, m), counts, width,
+                               stride, WINDOW_MOMENTS)
+
     def across_windows(self, others, begins, counts, stride=1):
         """-> (records, off) over this stream (stream 0) and the streams `others` (stream 1 and on) at every
         `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as Context.across_windows_host gives
@@ -298,6 +305,14 @@ def rolling_delta_data_windows(ctx, bro, begins, counts, width, stride=1):
     atsc_rolling_delta_windows over the records"""
     return _rolling_result(lambda m: _query_image(_ROLLING_DELTA, ctx, bro, begins, counts, width, stride, m), counts, width,
                            stride, WINDOW_DELTA)
+
+
+def rolling_moments_data_windows(ctx, bro, begins, counts, width, stride=1):
+    """-> (records, off): the moments' record of the window of `width` samples at every `stride`-th position of ranges
+    of decompress_data(ctx, bro), as Context.rolling_moments_windows_host gives them: atsc_bro_open, then
+    atsc_rolling_moments_windows over the records"""
+    return _rolling_result(lambda m: _query_image(_ROLLING_MOMENTS, ctx, bro, begins, counts, width, stride, m), counts, width,
+                           stride, WINDOW_MOMENTS)
 
 
 def across_data_windows(ctx, bros, begins, counts, stride=1):

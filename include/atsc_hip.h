@@ -859,6 +859,52 @@ int atsc_rolling_delta_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body
                                const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
                                atsc_window_delta *out);
 
+/* Windowed rolling moments: the moments' record (atsc_window_moments, 48 bytes) of the sliding window at every position
+ * of ranges of the decoded stream: `stddev_over_time(x[5m])`, `stdvar_over_time`, `deriv(x[5m])` and `predict_linear`
+ * evaluated at every step, a z-score against a trailing baseline, a moving least-squares slope -- without listing one
+ * window per position for atsc_moments_windows.  atsc_moments_fit applies to the records unchanged.
+ *   Ranges     Ranges, width, stride, the number and the order of the records (atsc_rolling_outputs), the limits
+ *              1 <= width <= ATSC_ROLLING_MAX_WIDTH and 2^32 - 2 records, validation, the errors (ATSC_E_INVALID with
+ *              nothing written and before any GPU work; ATSC_E_FORMAT or the plan's status word for a malformed payload
+ *              inside a position's window), pieces and ATSC_E_CAPACITY are atsc_rolling_windows'.  The messages name
+ *              rolling_moments_windows.
+ *   Node, leaf, Merge   atsc_moments_windows', word for word: the node is (n, mx, M2x, mt, M2t, C); the leaf of stream
+ *              index j is (1, x[j], 0, (double)j, 0, 0), a slot holding NaN the empty node (n = 0); Merge(a, b) is a,
+ *              bit for bit, when nb == 0, b when na == 0, else the rule given there, every operation one correctly
+ *              rounded f64 + - * /, never fused.  The position t of a leaf is its index in the stream (never an index
+ *              into the part of the stream a call happened to upload), so a chunk's node depends on no window, range,
+ *              piece or budget.
+ *   Order      N(a, 0) = leaf(a); N(a, l) = Merge(N(a, l - 1), N(a + 2^(l-1), l - 1)), for a a multiple of 2^l in the
+ *              stream index.  The window's chunks are the rolling's, left to right: pos = lo; while pos < lo + w, take
+ *              the largest l with pos % 2^l == 0 and pos + 2^l <= lo + w, emit (pos, l), pos += 2^l.
+ *              R = Merge(Merge(Merge(N(c_1), N(c_2)), N(c_3)), ...), the left operand as a.
+ *   Record     count = n, mean = mx, m2 = M2x, t_m2 = M2t, c_tx = C, t_mean = mt - (double)lo (one subtract); when
+ *              count == 0 all five doubles are NaN.  +-Inf samples give what IEEE gives under these rules; where the
+ *              rule yields NaN, any NaN bit pattern conforms.
+ *   count      atsc_moments_windows' of the window (lo, w), exactly.  The five doubles come from another tree than that
+ *              call's and MAY DIFFER from its in their last bits; each lies within its own stated bound.
+ * With u = 2^-53, L = max(1, ceil(log2 w)), kappa = sqrt(1 + count mean^2 / m2) and r = (lo + w) / w, for finite data:
+ *   |mean - exact| <= (3 L + 2) u mean|x|;            |m2 - exact| <= (3 L + 2) u kappa m2;
+ *   |t_m2 - exact| <= (3 L + 2) u r t_m2;             |c_tx - exact| <= (3 L + 2) u r kappa sqrt(t_m2 m2);
+ *   |t_mean - exact| <= (3 L + 2) u (lo + w);
+ * the windowed moments' bounds with 3 L for L: a node passes at most L merges inside a chunk and at most 2 L - 1 in the
+ * chain (the rolling's count).  m2 == 0 and c_tx == 0 exactly on a constant window.
+ * A position's bytes depend on the stream's samples and (lo, w) only: not on the range the window came from, the stride,
+ * the other ranges, the budget, the piece boundaries, the framing, the host or the device call.
+ * The chunk partials are 48 bytes (the node; the count in a 64-bit word), at most 12 bytes a sample beside the 8 of the
+ * decoded sample, inside the budget of atsc_ctx_set_aggregate_scratch as the rolling deltas' are; the default budget holds
+ * every width.
+ * begin / count are HOST arrays; d_body and d_out are device memory (d_out 8-byte aligned, 48 bytes per record).  Enqueued
+ * on `stream`, not synchronised.  The call keeps its tables and scratch in the rolling's place of the plan: a rolling, a
+ * rolling delta and a rolling moments call on the same plan wait (host side) for each other. */
+int atsc_rolling_moments_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                     const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                     atsc_window_moments *d_out, void *stream);
+/* Host bytes in, host records out, synchronous, as atsc_rolling_windows is; computes the device call's bits. */
+int atsc_rolling_moments_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                 const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                 atsc_window_moments *out);
+
 /* Windowed across: count, min, max and sum over N streams at every position of ranges of the decoded streams (the
  * indices of atsc_decompress_frames): one value per sample index folded across many series -- `sum by (job)(x)`,
  * `max by (zone)(x)`, how many replicas report at this instant and which one is the worst -- without the decoded
@@ -1184,6 +1230,9 @@ int atsc_stream_rolling_windows(atsc_stream *s, uint64_t n_windows, const uint64
 /* atsc_rolling_delta_windows over the stream's frames */
 int atsc_stream_rolling_delta_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                       uint64_t width, uint64_t stride, atsc_window_delta *out);
+/* atsc_rolling_moments_windows over the stream's frames */
+int atsc_stream_rolling_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                        uint64_t width, uint64_t stride, atsc_window_moments *out);
 /* atsc_moments_windows over the stream's frames */
 int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 atsc_window_moments *out);
