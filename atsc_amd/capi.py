@@ -25,6 +25,7 @@ EXTREMES_NONE = 2 ** 64 - 1
 # atsc_values_windows: the most entries per record (include/atsc_hip.h)
 VALUES_MAX_K = 32
 ROLLING_MAX_WIDTH = 1 << 20
+ROLLING_QUANTILE_MAX_WIDTH = 8192
 # atsc_across_windows: the most streams of a call (include/atsc_hip.h)
 ACROSS_MAX_STREAMS = 64
 COMPRESSOR_NAMES = {0: "noop", 1: "fft", 2: "idw", 3: "constant", 4: "polynomial", 5: "auto", 6: "rle"}
@@ -143,6 +144,10 @@ SIGNATURES = {
     "atsc_rolling_moments_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp, _vp]),
     "atsc_rolling_moments_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint64,
                                                C.c_uint64, _vp]),
+    "atsc_rolling_quantile_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                    _f64p, C.c_int, _vp, _vp]),
+    "atsc_rolling_quantile_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint64,
+                                                C.c_uint64, C.c_uint32, _f64p, C.c_int, _vp]),
     "atsc_across_outputs": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "atsc_across_windows_dev": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, _vp, _vp]),
     "atsc_across_windows": (C.c_int, [_vp, C.c_uint32, _vp, _u64p, _i32p, C.c_uint64, _u64p, _u64p, C.c_uint64, _vp]),
@@ -188,6 +193,8 @@ SIGNATURES = {
     "atsc_stream_rolling_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp]),
     "atsc_stream_rolling_delta_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp]),
     "atsc_stream_rolling_moments_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp]),
+    "atsc_stream_rolling_quantile_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                       _f64p, C.c_int, _vp]),
     "atsc_stream_across_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, _vp]),
     "atsc_stream_across_quantile_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint32,
                                                       _f64p, C.c_int, _vp]),

@@ -4,7 +4,8 @@
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
-//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments]]
+//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments]
+//        [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]]]
 //        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]
 //        [--across-extremes K] [--across-moments]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
@@ -88,6 +89,10 @@ void usage()
             "                                 columns: nonnan,avg,stdvar,stddev,slope,intercept (as --moments: population\n"
             "                                 forms, slope per sample, intercept at the position's first sample; all empty\n"
             "                                 where the window holds no sample)\n"
+            "      --rolling-quantiles <Q,Q,..>  with --rolling, W at most 8192: also every position's levels (0 <= Q <= 1, as\n"
+            "                                 --quantiles), as the last columns: one q<Q> per level as typed; NaN where the\n"
+            "                                 window holds no sample\n"
+            "      --rolling-quantile-method <M>  with --rolling-quantiles: linear (default), lower, higher or nearest\n"
             "      --across <A.bro,B.bro,..>  with -u --samples, without --buckets, --rolling and --where: fold this file (stream\n"
             "                                 0) and the listed files (streams 1.., at most 63) at the same sample indices and\n"
             "                                 write one row per sample to .across.csv instead of the .wbro:\n"
@@ -195,12 +200,13 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
             std::vector<atsc_window_delta> deltas;
             std::vector<atsc_window_delta_fit> fits;
             std::vector<atsc_window_moments> moments;
+            std::vector<double> levels;
             rc = atsc_bro_open(bro, len, nullptr, nullptr);
-            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, deltas, fits, moments);
+            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, deltas, fits, moments, levels);
             atsc_free(bro);
             if (rc) return rc;
             const uint64_t stride = a.q.rolling_stride;  // a position's first sample, counted from the window's begin
-            return rolling_write(with_ext(path, "roll.csv"), "offset", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments,
+            return rolling_write(with_ext(path, "roll.csv"), "offset", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments, a.q.rolling_level_names, levels,
                                  [stride](uint64_t j) { return std::to_string(j * stride); })
                        ? ATSC_OK
                        : ATSC_E_IO;

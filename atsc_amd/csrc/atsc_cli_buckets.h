@@ -2,7 +2,7 @@
 // and the bucket queries behind `atsc -u --buckets N` and `csv-compressor -u --from --to --step S`: their options, the
 // usage errors, the calls over the buckets and the columns of the .agg.csv; `--rolling W[:S]`, the sliding window's
 // records at every position of a window (with `--rolling-deltas`, its deltas beside them, with `--rolling-moments`, its
-// moments); `--where OP:LIMIT`, the selected samples
+// moments, with `--rolling-quantiles Q,Q,..`, its levels); `--where OP:LIMIT`, the selected samples
 // of the window itself into a .sel.csv; and `--across A.bro,B.bro,..` (atsc only), the across records of the window over
 // several files into an .across.csv (the end of this file).  The two differ in the row's first cell,
 // in how a failure is reported and in how a position inside a bucket is written: the three run positions, which the
@@ -77,6 +77,10 @@ struct BucketOptions {
     uint64_t rolling_stride = 1;
     bool rolling_deltas = false;  // --rolling-deltas: pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase behind .roll.csv's own
     bool rolling_moments = false;  // --rolling-moments: nonnan,avg,stdvar,stddev,slope,intercept behind those
+    std::vector<double> rolling_levels;  // --rolling-quantiles Q,Q,..: one column per level behind those
+    std::vector<std::string> rolling_level_names;
+    int rolling_method = ATSC_QUANTILE_LINEAR;  // --rolling-quantile-method
+    bool have_rolling_method = false;
     bool across_allowed = false;      // the front end takes --across (atsc; csv-compressor does not: DESIGN.md "Windowed across")
     std::vector<std::string> across;  // --across A.bro,B.bro,..: no bucket query; the window's across records into .across.csv
     uint64_t across_stride = 1;       // --across-stride S
@@ -278,6 +282,23 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
         o.rolling_deltas = true;
     } else if (s == "--rolling-moments") {
         o.rolling_moments = true;
+    } else if (value("--rolling-quantiles")) {
+        if (!parse_levels(v, o.rolling_levels, o.rolling_level_names)) {
+            fprintf(stderr, "error: invalid value '%s' for '--rolling-quantiles': expected levels in 0..=1, comma separated\n",
+                    v.c_str());
+            return 2;
+        }
+        if (o.rolling_levels.size() > 64) {
+            fprintf(stderr, "error: invalid value for '--rolling-quantiles': %zu levels, at most 64\n", o.rolling_levels.size());
+            return 2;
+        }
+    } else if (value("--rolling-quantile-method")) {
+        if (!parse_method(v, o.rolling_method)) {
+            fprintf(stderr, "error: invalid value '%s' for '--rolling-quantile-method': linear, lower, higher or nearest\n",
+                    v.c_str());
+            return 2;
+        }
+        o.have_rolling_method = true;
     } else if (value("--extremes")) {
         if (!parse_int(v, 1, ATSC_EXTREMES_MAX_K, o.extremes)) {
             fprintf(stderr, "error: invalid value '%s' for '--extremes': expected 1..=%d\n", v.c_str(), (int)ATSC_EXTREMES_MAX_K);
@@ -381,13 +402,25 @@ bool where_option_complete(const BucketOptions &o, const char *window, bool wind
 }
 
 // --rolling goes with the option that names the window and without the one that cuts buckets, as --where does, and
-// not with --where; --rolling-deltas and --rolling-moments go with --rolling.  false: a usage error, reported on stderr.
+// not with --where; --rolling-deltas, --rolling-moments and --rolling-quantiles go with --rolling, --rolling-quantile-method
+// with --rolling-quantiles, and --rolling-quantiles with a W of at most ATSC_ROLLING_QUANTILE_MAX_WIDTH.  false: a usage
+// error, reported on stderr.
 bool rolling_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
 {
+    if (o.have_rolling_method && o.rolling_levels.empty()) {
+        fprintf(stderr, "error: '--rolling-quantile-method' needs '--rolling-quantiles'\n");
+        return false;
+    }
     if (!o.rolling) {
         if (o.rolling_deltas) fprintf(stderr, "error: '--rolling-deltas' needs '--rolling'\n");
         if (o.rolling_moments) fprintf(stderr, "error: '--rolling-moments' needs '--rolling'\n");
-        return !o.rolling_deltas && !o.rolling_moments;
+        if (!o.rolling_levels.empty()) fprintf(stderr, "error: '--rolling-quantiles' needs '--rolling'\n");
+        return !o.rolling_deltas && !o.rolling_moments && o.rolling_levels.empty();
+    }
+    if (!o.rolling_levels.empty() && o.rolling > ATSC_ROLLING_QUANTILE_MAX_WIDTH) {
+        fprintf(stderr, "error: '--rolling-quantiles' needs a '--rolling' W in 1..=%llu\n",
+                (unsigned long long)ATSC_ROLLING_QUANTILE_MAX_WIDTH);
+        return false;
     }
     if (!windowed) {
         fprintf(stderr, "error: '--rolling' needs '%s'\n", window);
@@ -643,10 +676,11 @@ bool where_write(const std::string &path, const char *first, const std::vector<a
 
 // --rolling: one record per position of the range [begin, begin + count) of a .bro image; deltas: with --rolling-deltas,
 // the same positions' rolling deltas and what atsc_delta_derive reads off them; moments: with --rolling-moments, the
-// same positions' rolling moments
+// same positions' rolling moments; levels: with --rolling-quantiles, the same positions' rows of levels
 int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
                   std::vector<atsc_window_rolling> &rows, std::vector<atsc_window_delta> &deltas,
-                  std::vector<atsc_window_delta_fit> &fits, std::vector<atsc_window_moments> &moments)
+                  std::vector<atsc_window_delta_fit> &fits, std::vector<atsc_window_moments> &moments,
+                  std::vector<double> &levels)
 {
     rows.assign(atsc_rolling_outputs(count, o.rolling, o.rolling_stride), atsc_window_rolling{});
     atsc_window_rolling none;
@@ -666,6 +700,13 @@ int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketO
         rc = atsc_rolling_moments_windows(ctx, bro + 9, len - 9, 1, 1, &begin, &count, o.rolling, o.rolling_stride,
                                           moments.empty() ? &none_m : moments.data());
     }
+    if (!rc && !o.rolling_levels.empty()) {
+        levels.assign(rows.size() * o.rolling_levels.size(), 0.0);
+        double none_q;
+        rc = atsc_rolling_quantile_windows(ctx, bro + 9, len - 9, 1, 1, &begin, &count, o.rolling, o.rolling_stride,
+                                           (uint32_t)o.rolling_levels.size(), o.rolling_levels.data(), o.rolling_method,
+                                           levels.empty() ? &none_q : levels.data());
+    }
     return rc;
 }
 
@@ -675,17 +716,22 @@ int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketO
 // nonnan,avg,stdvar,stddev,slope,intercept from the position's record of `moments`: its count and the mean, the
 // population variance and standard deviation, and the least-squares line (slope per sample, intercept at the position's
 // first sample) that atsc_moments_fit reads off it, all six empty where the count is 0 (the count column says so); the
-// column is avg because mean is taken: sum / count in the rolling's order.  false: the file could not be written.
+// column is avg because mean is taken: sum / count in the rolling's order.  names (--rolling-quantiles): behind those a
+// column q<level as typed> per level, from the position's row of `levels` (NaN where the window holds no sample).
+// false: the file could not be written.
 template <class Place>
 bool rolling_write(const std::string &path, const char *first, const std::vector<atsc_window_rolling> &rows, bool with_deltas,
                    const std::vector<atsc_window_delta> &deltas, const std::vector<atsc_window_delta_fit> &fits,
-                   bool with_moments, const std::vector<atsc_window_moments> &moments, Place place)
+                   bool with_moments, const std::vector<atsc_window_moments> &moments, const std::vector<std::string> &names,
+                   const std::vector<double> &levels, Place place)
 {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return false;
-    fprintf(f, "%s,count,min,max,sum,mean%s%s\n", first,
+    fprintf(f, "%s,count,min,max,sum,mean%s%s", first,
             with_deltas ? ",pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase" : "",
             with_moments ? ",nonnan,avg,stdvar,stddev,slope,intercept" : "");
+    for (const std::string &n : names) fprintf(f, ",q%s", n.c_str());
+    fprintf(f, "\n");
     for (size_t j = 0; j < rows.size(); ++j) {
         const atsc_window_rolling &r = rows[j];
         fprintf(f, "%s,%llu,%s,%s,%s,%s", place(j).c_str(), (unsigned long long)r.count, debug_f64(r.min).c_str(),
@@ -705,6 +751,7 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
                          debug_f64(fit.variance).c_str(), debug_f64(fit.stddev).c_str(), debug_f64(fit.slope).c_str(),
                          debug_f64(fit.intercept).c_str());
         }
+        for (size_t q = 0; q < names.size(); ++q) fprintf(f, ",%s", debug_f64(levels[j * names.size() + q]).c_str());
         fprintf(f, "\n");
     }
     return fclose(f) == 0;

@@ -359,6 +359,18 @@ constexpr uint32_t ROLL_DELTA_PART = 48;  // bytes of a partial: three sums, two
 constexpr uint32_t ROLL_MOMENTS_LOW = 3;    // the lowest stored level
 constexpr uint32_t ROLL_MOMENTS_PART = 48;  // bytes of a partial: the node's five doubles, the count in a 64-bit word
 
+// windowed rolling quantiles (atsc_rolling_quantile_windows_dev, atsc_rolling_quantile.hip): the rolling's pieces and
+// tasks without a pyramid.  A task's windows cover a span of (n - 1) stride + w samples, which one workgroup sorts in
+// P slots of LDS and reads every position's levels off.  P by the width alone: the least power of two in
+// [RQ_SPAN_MIN, RQ_SPAN_MAX] that holds two windows, RQ_SPAN_MAX above that; a task holds (P - w) / stride + 1 positions.
+constexpr uint32_t RQ_SPAN_MIN = 512, RQ_SPAN_MAX = 8192;  // RQ_SPAN_MAX: ATSC_ROLLING_QUANTILE_MAX_WIDTH, QNT_MEDIUM_MAX
+static inline uint32_t rq_span_keys(uint64_t w)
+{
+    uint32_t P = RQ_SPAN_MIN;
+    while (P < RQ_SPAN_MAX && P < 2 * w) P <<= 1;
+    return P;
+}
+
 // windowed across (atsc_across_windows_dev, atsc_across.hip): every stream of a call decoded into a scratch region of
 // its own, the same sample at the same slot of every region, then one record per position from its slot of each.  A
 // task is a DevRollTask: n positions of one range inside one piece, the first at sample lo of the streams.

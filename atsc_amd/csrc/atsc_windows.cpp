@@ -111,6 +111,10 @@ __attribute__((weak)) hipError_t launch_rmo_upper(void *pyr, const DevRollPiece 
 __attribute__((weak)) hipError_t launch_rmo_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                       const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
                                                       void *out, hipStream_t s);
+// the windowed rolling quantiles' span kernel (atsc_rolling_quantile.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_rq_span(const DevRollTask *tasks, uint32_t n, uint32_t P, uint64_t B,
+                                                const double *scratch, uint64_t a0, uint32_t w, uint64_t stride,
+                                                const double *q, uint32_t n_q, int method, double *out, hipStream_t s);
 // the windowed across' position kernel (atsc_across.hip; weak for the same reason)
 __attribute__((weak)) hipError_t launch_across_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                          const uint64_t *reg, uint32_t n_streams, uint64_t a0,
@@ -384,7 +388,8 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
                           BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
                           BY_ROLLING = DECODE_CALLER("rolling"), BY_ROLLING_DELTA = DECODE_CALLER("rolling delta"),
-                          BY_ROLLING_MOMENTS = DECODE_CALLER("rolling moments"), BY_ACROSS = DECODE_CALLER("across"),
+                          BY_ROLLING_MOMENTS = DECODE_CALLER("rolling moments"),
+                          BY_ROLLING_QUANTILE = DECODE_CALLER("rolling quantile"), BY_ACROSS = DECODE_CALLER("across"),
                           BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile"),
                           BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes"),
                           BY_ACROSS_MOMENTS = DECODE_CALLER("across moments");
@@ -2675,6 +2680,174 @@ extern "C" int atsc_rolling_moments_windows(atsc_ctx *ctx, const uint8_t *body, 
 }
 
 // ------------------------------------------------------------------------------------------
+// windowed rolling quantiles: the levels of the window at every position of sample ranges (atsc_rolling_quantile.hip)
+// ------------------------------------------------------------------------------------------
+// rolling_check with the rolling quantiles' width limit, then the quantiles' levels and method
+static int rolling_quantile_check(atsc_ctx *ctx, const char *call, uint64_t n, const uint64_t *count, uint64_t width,
+                                  uint64_t stride, uint32_t n_q, const double *q, int method, uint64_t *total)
+{
+    if (width > ATSC_ROLLING_QUANTILE_MAX_WIDTH)
+        return fail_in(ctx, ATSC_E_INVALID, call,
+                       "width above 8192 (ATSC_ROLLING_QUANTILE_MAX_WIDTH); wider windows: atsc_quantile_windows with listed windows");
+    const int rc = rolling_check(ctx, call, n, count, width, stride, total);
+    return rc ? rc : quantile_check_levels(ctx, call, n_q, q, method);
+}
+
+// The device call.  Covering intervals, pieces that overlap by width - 1 and the rule "the first piece that holds a
+// position's window computes it" are rolling_dev's; there is no pyramid, so a piece takes the whole of piece_samples'
+// length and lies in the scratch from its first sample on.  width <= 8192 is far below the least piece, so every window
+// fits one.  Per range and per piece, the run of positions the piece computes is cut into tasks of B = (P - width) /
+// stride + 1 positions, P = rq_span_keys(width): a task's windows cover at most P samples.  One upload (decode tasks,
+// levels, tasks); then per piece the decode and the one launch, which is told B: where no task holds more than one
+// position the kernel sorts the keys without their places in the span.
+static int rolling_quantile_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride, uint32_t n_q,
+                                const double *q, int method, double *d_out, void *stream, uint64_t org)
+{
+    static const char *const CALL = "rolling_quantile_windows";
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count))) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    uint64_t total = 0;
+    int rc = rolling_quantile_check(ctx, CALL, n_windows, count, width, stride, n_q, q, method, &total);
+    if (rc) return rc;
+    if (total && !d_out) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    rc = check_windows(ctx, CALL, dp, d_out, "d_out", n_windows, begin, count, ~0ull);
+    if (rc || total == 0) return rc;
+    if (!launch_decompress_window || !launch_window_gather || !launch_rq_span)
+        return fail_in(ctx, ATSC_E_UNSUPPORTED, CALL, "no rolling quantile kernels");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint64_t W = n_windows, w = width;
+    std::vector<uint64_t> m(W);
+    std::vector<Span> cov;
+    for (uint64_t i = 0; i < W; ++i) {
+        m[i] = atsc_rolling_outputs(count[i], w, stride);
+        if (m[i]) cov.emplace_back(org + begin[i], org + begin[i] + (m[i] - 1) * stride + w);
+    }
+    merge_spans(cov);
+    uint64_t spill;
+    const uint64_t Lp = piece_samples(ctx, dp, org, cov, 1, &spill);
+    static_assert(ATSC_ROLLING_QUANTILE_MAX_WIDTH < AGG_MIN_PIECE, "a window fits the least piece");
+    // pieces: samples [first, second) of the stream, ascending; scratch[0] is sample first
+    std::vector<Span> pcs;
+    uint64_t region = 0;
+    for (size_t a = 0; a < cov.size();) {
+        const uint64_t s0 = cov[a].first;
+        uint64_t s1 = cov[a].second;
+        size_t z = a + 1;
+        while (z < cov.size() && cov[z].first < s1 + HST_GAP) s1 = cov[z++].second;
+        for (uint64_t p = s0;;) {
+            const uint64_t e = std::min(s1, p + Lp);
+            pcs.emplace_back(p, e);
+            region = std::max(region, e - p);
+            if (e == s1) break;
+            p = e - (w - 1);
+        }
+        a = z;
+    }
+    region += region & 1;  // an even number of doubles, as the spill slots behind it expect
+    const size_t P = pcs.size();
+    // tasks, by piece: per range the runs of positions whose windows end inside the piece and not inside an earlier one
+    const uint32_t keys = rq_span_keys(w);
+    const uint64_t B = (keys - w) / stride + 1;
+    std::vector<Placed<DevRollTask>> tk;
+    uint64_t rec = 0;
+    for (uint64_t i = 0; i < W; ++i) {
+        if (!m[i]) continue;
+        const uint64_t b = org + begin[i];
+        size_t p = (size_t)(std::lower_bound(pcs.begin(), pcs.end(), b + w, [](const Span &x, uint64_t v) { return x.second < v; }) -
+                            pcs.begin());
+        for (uint64_t j = 0; j < m[i];) {
+            const uint64_t lo = b + j * stride;
+            while (p < P && pcs[p].second < lo + w) ++p;  // (a stride longer than a piece skips pieces)
+            if (p >= P || pcs[p].first > lo)
+                return fail_in(ctx, ATSC_E_INVALID, CALL, "internal error (position outside the pieces)");
+            const uint64_t je = std::min(m[i], (pcs[p].second - w - b) / stride + 1);  // positions whose windows end in the piece
+            for (; j < je; j += B)
+                tk.push_back({(uint32_t)p, DevRollTask{b + j * stride, rec + j, (uint32_t)std::min<uint64_t>(B, je - j), 0}});
+            j = je;
+        }
+        rec += m[i];
+    }
+    std::vector<DevRollTask> tasks;
+    std::vector<size_t> at;
+    group_tasks(tk, P, tasks, at);
+    std::vector<PieceDecode> pdec;
+    DecodeTasks D;
+    rc = emit_pieces_decode(ctx, CALL, dp, org, cov, pcs, 1, region, D, pdec);
+    if (rc) return rc;
+    QueryRes &R = dp->res[Q_ROLLING];
+    HIPCHK(ctx, R.wait());
+    Upload up;
+    D.place(up);
+    const size_t off_q = up.add(q, n_q * sizeof(double)), off_tasks = up.add(tasks);
+    rc = stage_upload(ctx, R, up, region + (uint64_t)MAX_FRAME * D.spills_used, s);
+    if (rc) return rc;
+    unsigned char *d = R.d;
+    double *scr = R.scratch;
+    const double *dq = (const double *)(d + off_q);
+    const DevRollTask *d_tasks = (const DevRollTask *)(d + off_tasks);
+    for (size_t p = 0; p < P; ++p) {
+        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_ROLLING_QUANTILE);
+        if (rc) return rc;
+        LAUNCHCHK(ctx, "launch k_rq_span",
+                  launch_rq_span(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), keys, B, scr, pcs[p].first, (uint32_t)w, stride,
+                                 dq, n_q, method, d_out, s));
+    }
+    HIPCHK(ctx, R.record(s));
+    return ATSC_OK;
+}
+
+// The rolling quantiles' descriptor (see AggQuery): RollQueryOf's shape with the levels and the method; a position's row
+// is n_q doubles.
+struct RollQuantileQuery {
+    static constexpr int INPUTS = 1;
+    static constexpr const char *CALL = "rolling_quantile_windows";
+    uint64_t width, stride;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    uint32_t n_q;
+    const double *q;
+    int method;
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_rolling_outputs(count[i], width, stride);
+        return total * n_q * sizeof(double);
+    }
+    int check(atsc_ctx *ctx) const
+    {
+        return rolling_quantile_check(ctx, CALL, count ? n_ranges : 0, count, width, stride, n_q, q, method, nullptr);
+    }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no row
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *cnt, void *d_res, void *stream, uint64_t org) const
+    {
+        return rolling_quantile_dev(ctx, dp, d_body, n_windows, begin, cnt, width, stride, n_q, q, method, (double *)d_res,
+                                    stream, org);
+    }
+};
+
+extern "C" int atsc_rolling_quantile_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                                 const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                                 uint32_t n_q, const double *q, int method, double *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    return RollQuantileQuery{width, stride, count, n_windows, n_q, q, method}.dev(ctx, dp, d_body, n_windows, begin, count, d_out,
+                                                                                  stream, 0);
+    ATSC_API_END
+}
+
+extern "C" int atsc_rolling_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count,
+                                             uint64_t n_windows, const uint64_t *begin, const uint64_t *count, uint64_t width,
+                                             uint64_t stride, uint32_t n_q, const double *q, int method, double *out)
+{
+    ATSC_API_BEGIN
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out,
+                      RollQuantileQuery{width, stride, count, n_windows, n_q, q, method});
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
 // windowed across: count / min / max / sum over N streams at every position of sample ranges (atsc_across.hip)
 // ------------------------------------------------------------------------------------------
 extern "C" uint64_t atsc_across_outputs(uint64_t count, uint64_t stride)
@@ -3313,6 +3486,15 @@ extern "C" int atsc_stream_rolling_moments_windows(atsc_stream *s, uint64_t n_wi
 {
     ATSC_API_BEGIN
     return query_stream(s, n_windows, begin, count, out, RollMomentsQuery{width, stride, count, n_windows});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_rolling_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin,
+                                                    const uint64_t *count, uint64_t width, uint64_t stride, uint32_t n_q,
+                                                    const double *q, int method, double *out)
+{
+    ATSC_API_BEGIN
+    return query_stream(s, n_windows, begin, count, out, RollQuantileQuery{width, stride, count, n_windows, n_q, q, method});
     ATSC_API_END
 }
 

@@ -243,6 +243,24 @@ def _rolling_result(run, counts, width, stride, record=WINDOW_ROLLING):
     return run(int(off[-1])).view(record), off
 
 
+def _rolling_quantile_params(width, stride, records, levels, method):
+    """the rolling's arguments, then the levels and the method"""
+    a = _RollArgs(tuple(_rolling_params(width, stride, records)) + _array_params(levels, method))
+    a.records = int(records)
+    return a
+
+
+def _rolling_quantile_block(n, cargs):
+    return 8 * cargs[2] * cargs.records
+
+
+def _rolling_quantile_result(run, counts, width, stride, levels):
+    """run(records) -> the block of a rolling quantile call as uint64 words.  -> (rows, off): a (records, n_q) float64
+    array, a row per position, range after range, and the ranges' record offsets (rolling_offsets)"""
+    off = rolling_offsets(counts, width, stride)
+    return run(int(off[-1])).view(np.float64).reshape(int(off[-1]), len(_levels(levels)[0])), off
+
+
 def _across_params(stride, records):
     stride = int(stride)
     if not 0 <= stride < 2 ** 64:
@@ -329,6 +347,7 @@ _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _s
 _ROLLING = _Query("rolling_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_block)
 _ROLLING_DELTA = _Query("rolling_delta_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_delta_block)
 _ROLLING_MOMENTS = _Query("rolling_moments_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_moments_block)
+_ROLLING_QUANTILE = _Query("rolling_quantile_windows", np.dtype(np.uint64), None, _rolling_quantile_params, _rolling_quantile_block)
 _ACROSS = _Query("across_windows", np.dtype(np.uint64), None, _across_params, _across_block, inputs=None)
 _ACROSS_QUANTILE = _Query("across_quantile_windows", np.dtype(np.uint64), None, _across_quantile_params, _across_quantile_block,
                           inputs=None)
@@ -708,6 +727,17 @@ class Context:
         return _rolling_result(lambda m: _query_host(_ROLLING_MOMENTS, self, records, begins, counts, has_count, width, stride, m),
                                counts, width, stride, WINDOW_MOMENTS)
 
+    def rolling_quantile_windows_host(self, records, begins, counts, width, levels, stride=1, method=capi.QUANTILE_LINEAR,
+                                      has_count=False):
+        """-> (rows, off): the levels (quantile_windows_host's rule and methods) of the window of `width` samples, at most
+        ROLLING_QUANTILE_MAX_WIDTH, at every `stride`-th position of every range [begins[i], begins[i] + counts[i]) of
+        the decoded records (atsc_rolling_quantile_windows).  rows: a (records, n_levels) float64 array, a row per
+        position, range after range: the row quantile_windows_host gives for the listed window; NaN where the window
+        holds no sample; off: as rolling_windows_host's"""
+        return _rolling_quantile_result(
+            lambda m: _query_host(_ROLLING_QUANTILE, self, records, begins, counts, has_count, width, stride, m, levels, method),
+            counts, width, stride, levels)
+
     def across_windows_host(self, records_list, begins, counts, stride=1, has_count=False):
         """-> (records, off): count / min / max / sum over the streams of records_list (at most ACROSS_MAX_STREAMS
         decoded record streams, sample j of one going with sample j of every other) at every `stride`-th position of
@@ -948,6 +978,17 @@ class DPlan:
         off = rolling_offsets(counts, width, stride)
         _query_dev(_ROLLING_MOMENTS, self, d_body, begins, counts, d_out, stream, width, stride, int(off[-1]))
         return off
+
+    def rolling_quantile_windows(self, d_body, begins, counts, width, stride, levels, d_out, method=capi.QUANTILE_LINEAR,
+                                 stream=0):
+        """Enqueues the levels of the window of `width` samples at every `stride`-th position of the ranges [begins[i],
+        begins[i] + counts[i]) into d_out, a float64 device tensor of at least n_levels elements per position,
+        position-major (atsc_rolling_quantile_windows_dev).  -> (rows, off): the (records, n_levels) view of d_out and
+        the ranges' record offsets (rolling_offsets)"""
+        off = rolling_offsets(counts, width, stride)
+        m, n_q = int(off[-1]), len(_levels(levels)[0])
+        _query_dev(_ROLLING_QUANTILE, self, d_body, begins, counts, d_out, stream, width, stride, m, levels, method)
+        return d_out.view(-1)[: m * n_q].view(m, n_q), off
 
     def across_windows(self, d_body, others, other_bodies, begins, counts, d_out, stride=1, stream=0):
         """Enqueues count / min / max / sum over this plan's stream (stream 0) and the plans `others` (their device

@@ -10,6 +10,7 @@ from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_ROLLING, W
 from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _ROLLING_DELTA, _ROLLING_MOMENTS, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
 from .engine import ACROSS_RECORD, _ACROSS, _across_host, _across_list, _across_result  # noqa: F401
 from .engine import _ACROSS_QUANTILE, _across_quantile_result
+from .engine import _ROLLING_QUANTILE, _rolling_quantile_result
 from .engine import _ACROSS_EXTREMES, _across_extremes_result
 from .engine import _ACROSS_MOMENTS, _across_moments_result
 
@@ -169,6 +170,14 @@ class CompressedStream:
         return _rolling_result(lambda m: _query_stream(_ROLLING_MOMENTS, self, begins, counts, width, stride, m), counts, width,
                                stride, WINDOW_MOMENTS)
 
+    def rolling_quantile_windows(self, begins, counts, width, levels, stride=1, method=capi.QUANTILE_LINEAR):
+        """-> (rows, off): the levels of the window of `width` samples at every `stride`-th position of the ranges
+        [begins[i], begins[i] + counts[i]), as Context.rolling_quantile_windows_host gives them
+        (atsc_stream_rolling_quantile_windows)"""
+        return _rolling_quantile_result(
+            lambda m: _query_stream(_ROLLING_QUANTILE, self, begins, counts, width, stride, m, levels, method), counts, width,
+            stride, levels)
+
     def across_windows(self, others, begins, counts, stride=1):
         """-> (records, off) over this stream (stream 0) and the streams `others` (stream 1 and on) at every
         `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as Context.across_windows_host gives
@@ -313,6 +322,15 @@ def rolling_moments_data_windows(ctx, bro, begins, counts, width, stride=1):
     atsc_rolling_moments_windows over the records"""
     return _rolling_result(lambda m: _query_image(_ROLLING_MOMENTS, ctx, bro, begins, counts, width, stride, m), counts, width,
                            stride, WINDOW_MOMENTS)
+
+
+def rolling_quantile_data_windows(ctx, bro, begins, counts, width, levels, stride=1, method=capi.QUANTILE_LINEAR):
+    """-> (rows, off): the levels of the window of `width` samples at every `stride`-th position of ranges of
+    decompress_data(ctx, bro), as Context.rolling_quantile_windows_host gives them: atsc_bro_open, then
+    atsc_rolling_quantile_windows over the records"""
+    return _rolling_quantile_result(
+        lambda m: _query_image(_ROLLING_QUANTILE, ctx, bro, begins, counts, width, stride, m, levels, method), counts, width,
+        stride, levels)
 
 
 def across_data_windows(ctx, bros, begins, counts, stride=1):

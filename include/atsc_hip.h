@@ -905,6 +905,43 @@ int atsc_rolling_moments_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t bo
                                  const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
                                  atsc_window_moments *out);
 
+/* Windowed rolling quantiles: the levels q[0 .. n_q) of the sliding window at every position of ranges of the decoded
+ * stream: `quantile_over_time(0.99, x[5m])` evaluated at every step, a rolling median for despiking (a Hampel filter is
+ * a rolling median and a rolling MAD), a p95 band round a moving baseline -- without listing one window per position
+ * for atsc_quantile_windows.
+ *   Ranges     Ranges, width w, stride s, the number and the order of the positions (atsc_rolling_outputs), the limit of
+ *              2^32 - 2 positions in all and validation are atsc_rolling_windows'; the width's limit is
+ *              1 <= w <= ATSC_ROLLING_QUANTILE_MAX_WIDTH.  The messages name rolling_quantile_windows.
+ *   Result     n_q doubles per position: with m_i = atsc_rolling_outputs(count[i], w, s), row j of range i is at
+ *              out[(m_0 + .. + m_(i-1) + j) * n_q], level t of it at + t.
+ *   Row        The row of the position whose window is [lo, lo + w) is, bit for bit, the row atsc_quantile_windows
+ *              returns for (begin, count) = (lo, w) with the same levels and method: the window's non-NaN samples in the
+ *              total order of the quantiles' key (-0.0 before +0.0), ranks and interpolation by the rule stated there
+ *              (q_pick / q_interp of atsc_quantile_rule.h and nothing else); an empty or all-NaN window gives NaN at
+ *              every level (any NaN bit pattern conforms).  Selection is exact: a position's bits depend on the stream's
+ *              samples and (lo, w) alone, not on the range the window came from, the stride, the other ranges, the
+ *              budget, the piece boundaries, how positions were grouped, the framing, the host or the device call.
+ * Errors: ATSC_E_INVALID with nothing written and before any GPU work for every case of atsc_rolling_windows, for
+ * width > ATSC_ROLLING_QUANTILE_MAX_WIDTH (the message says the limit and names atsc_quantile_windows with listed
+ * windows, which takes any width), a null q, n_q == 0 or n_q > 64, a level that is NaN or outside [0, 1], an unknown
+ * method, a d_out that is not 8-byte aligned.  ATSC_E_FORMAT (host form) or the plan's status word (device form) for a
+ * malformed payload inside a position's window.
+ * The limit is the length up to which one window's keys fit one workgroup's LDS (the windowed quantiles' medium tier).
+ * It is far below the least piece of the scratch (65536 samples), so every window fits a piece whatever the budget of
+ * atsc_ctx_set_aggregate_scratch: the call has NO ATSC_E_CAPACITY case.  The scratch holds the decoded samples only (8
+ * bytes a sample).
+ * begin / count / q are HOST arrays; d_body and d_out are device memory (d_out 8-byte aligned, 8 n_q bytes per
+ * position).  Enqueued on `stream`, not synchronised.  The call keeps its tables and scratch in the rolling's place of
+ * the plan: it and the rolling calls on the same plan wait (host side) for each other. */
+#define ATSC_ROLLING_QUANTILE_MAX_WIDTH 8192
+int atsc_rolling_quantile_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                      const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                      uint32_t n_q, const double *q, int method, double *d_out, void *stream);
+/* Host bytes in, host rows out, synchronous, as atsc_rolling_windows is; computes the device call's bits. */
+int atsc_rolling_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                  const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                  uint32_t n_q, const double *q, int method, double *out);
+
 /* Windowed across: count, min, max and sum over N streams at every position of ranges of the decoded streams (the
  * indices of atsc_decompress_frames): one value per sample index folded across many series -- `sum by (job)(x)`,
  * `max by (zone)(x)`, how many replicas report at this instant and which one is the worst -- without the decoded
@@ -1233,6 +1270,10 @@ int atsc_stream_rolling_delta_windows(atsc_stream *s, uint64_t n_windows, const 
 /* atsc_rolling_moments_windows over the stream's frames */
 int atsc_stream_rolling_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                         uint64_t width, uint64_t stride, atsc_window_moments *out);
+/* atsc_rolling_quantile_windows over the stream's frames */
+int atsc_stream_rolling_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                         uint64_t width, uint64_t stride, uint32_t n_q, const double *q, int method,
+                                         double *out);
 /* atsc_moments_windows over the stream's frames */
 int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 atsc_window_moments *out);
