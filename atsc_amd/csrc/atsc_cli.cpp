@@ -5,7 +5,7 @@
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
 //        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments]
-//        [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]]]
+//        [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]] [--rolling-pair OTHER.bro]]
 //        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]
 //        [--across-extremes K] [--across-moments]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
@@ -93,6 +93,10 @@ void usage()
             "                                 --quantiles), as the last columns: one q<Q> per level as typed; NaN where the\n"
             "                                 window holds no sample\n"
             "      --rolling-quantile-method <M>  with --rolling-quantiles: linear (default), lower, higher or nearest\n"
+            "      --rolling-pair <OTHER.bro> with --rolling: also every position's pair moments against the samples of\n"
+            "                                 OTHER.bro at the same indices (x: this file, y: OTHER), as the last columns:\n"
+            "                                 pair_count,covariance,correlation,slope,intercept (as --pair; the four empty\n"
+            "                                 where pair_count is 0).  OTHER must not end before a position's window\n"
             "      --across <A.bro,B.bro,..>  with -u --samples, without --buckets, --rolling and --where: fold this file (stream\n"
             "                                 0) and the listed files (streams 1.., at most 63) at the same sample indices and\n"
             "                                 write one row per sample to .across.csv instead of the .wbro:\n"
@@ -202,11 +206,13 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
             std::vector<atsc_window_moments> moments;
             std::vector<double> levels;
             rc = atsc_bro_open(bro, len, nullptr, nullptr);
-            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, deltas, fits, moments, levels);
+            std::vector<atsc_window_pair> pairs;
+            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, deltas, fits, moments, levels, &pairs);
             atsc_free(bro);
             if (rc) return rc;
             const uint64_t stride = a.q.rolling_stride;  // a position's first sample, counted from the window's begin
             return rolling_write(with_ext(path, "roll.csv"), "offset", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments, a.q.rolling_level_names, levels,
+                                 a.q.rolling_pair.empty() ? nullptr : &pairs,
                                  [stride](uint64_t j) { return std::to_string(j * stride); })
                        ? ATSC_OK
                        : ATSC_E_IO;

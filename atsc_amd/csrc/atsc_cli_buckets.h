@@ -2,7 +2,8 @@
 // and the bucket queries behind `atsc -u --buckets N` and `csv-compressor -u --from --to --step S`: their options, the
 // usage errors, the calls over the buckets and the columns of the .agg.csv; `--rolling W[:S]`, the sliding window's
 // records at every position of a window (with `--rolling-deltas`, its deltas beside them, with `--rolling-moments`, its
-// moments, with `--rolling-quantiles Q,Q,..`, its levels); `--where OP:LIMIT`, the selected samples
+// moments, with `--rolling-quantiles Q,Q,..`, its levels, with `--rolling-pair OTHER.bro` (atsc only), its pair moments
+// against another file); `--where OP:LIMIT`, the selected samples
 // of the window itself into a .sel.csv; and `--across A.bro,B.bro,..` (atsc only), the across records of the window over
 // several files into an .across.csv (the end of this file).  The two differ in the row's first cell,
 // in how a failure is reported and in how a position inside a bucket is written: the three run positions, which the
@@ -79,6 +80,7 @@ struct BucketOptions {
     bool rolling_moments = false;  // --rolling-moments: nonnan,avg,stdvar,stddev,slope,intercept behind those
     std::vector<double> rolling_levels;  // --rolling-quantiles Q,Q,..: one column per level behind those
     std::vector<std::string> rolling_level_names;
+    std::string rolling_pair;  // --rolling-pair OTHER.bro (where pair_allowed): pair_count,covariance,correlation,slope,intercept as the last columns
     int rolling_method = ATSC_QUANTILE_LINEAR;  // --rolling-quantile-method
     bool have_rolling_method = false;
     bool across_allowed = false;      // the front end takes --across (atsc; csv-compressor does not: DESIGN.md "Windowed across")
@@ -316,6 +318,12 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             return 2;
         }
         o.pair = v;
+    } else if (o.pair_allowed && value("--rolling-pair")) {
+        if (v.empty()) {
+            fprintf(stderr, "error: invalid value '' for '--rolling-pair': expected the path of a .bro file\n");
+            return 2;
+        }
+        o.rolling_pair = v;
     } else if (o.across_allowed && value("--across")) {
         if (!parse_across(v, o.across)) {
             fprintf(stderr, "error: invalid value '%s' for '--across': expected 1..=%d paths of .bro files, comma separated\n",
@@ -402,7 +410,7 @@ bool where_option_complete(const BucketOptions &o, const char *window, bool wind
 }
 
 // --rolling goes with the option that names the window and without the one that cuts buckets, as --where does, and
-// not with --where; --rolling-deltas, --rolling-moments and --rolling-quantiles go with --rolling, --rolling-quantile-method
+// not with --where; --rolling-deltas, --rolling-moments, --rolling-quantiles and --rolling-pair go with --rolling, --rolling-quantile-method
 // with --rolling-quantiles, and --rolling-quantiles with a W of at most ATSC_ROLLING_QUANTILE_MAX_WIDTH.  false: a usage
 // error, reported on stderr.
 bool rolling_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
@@ -415,7 +423,8 @@ bool rolling_option_complete(const BucketOptions &o, const char *window, bool wi
         if (o.rolling_deltas) fprintf(stderr, "error: '--rolling-deltas' needs '--rolling'\n");
         if (o.rolling_moments) fprintf(stderr, "error: '--rolling-moments' needs '--rolling'\n");
         if (!o.rolling_levels.empty()) fprintf(stderr, "error: '--rolling-quantiles' needs '--rolling'\n");
-        return !o.rolling_deltas && !o.rolling_moments && o.rolling_levels.empty();
+        if (!o.rolling_pair.empty()) fprintf(stderr, "error: '--rolling-pair' needs '--rolling'\n");
+        return !o.rolling_deltas && !o.rolling_moments && o.rolling_levels.empty() && o.rolling_pair.empty();
     }
     if (!o.rolling_levels.empty() && o.rolling > ATSC_ROLLING_QUANTILE_MAX_WIDTH) {
         fprintf(stderr, "error: '--rolling-quantiles' needs a '--rolling' W in 1..=%llu\n",
@@ -676,11 +685,13 @@ bool where_write(const std::string &path, const char *first, const std::vector<a
 
 // --rolling: one record per position of the range [begin, begin + count) of a .bro image; deltas: with --rolling-deltas,
 // the same positions' rolling deltas and what atsc_delta_derive reads off them; moments: with --rolling-moments, the
-// same positions' rolling moments; levels: with --rolling-quantiles, the same positions' rows of levels
+// same positions' rolling moments; levels: with --rolling-quantiles, the same positions' rows of levels; pairs: with
+// --rolling-pair OTHER.bro, the same positions' rolling pair moments against that file's samples (sample i of it goes
+// with sample i of this one; a file that ends before a window fails as --pair's does)
 int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
                   std::vector<atsc_window_rolling> &rows, std::vector<atsc_window_delta> &deltas,
                   std::vector<atsc_window_delta_fit> &fits, std::vector<atsc_window_moments> &moments,
-                  std::vector<double> &levels)
+                  std::vector<double> &levels, std::vector<atsc_window_pair> *pairs = nullptr)
 {
     rows.assign(atsc_rolling_outputs(count, o.rolling, o.rolling_stride), atsc_window_rolling{});
     atsc_window_rolling none;
@@ -707,6 +718,19 @@ int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketO
                                            (uint32_t)o.rolling_levels.size(), o.rolling_levels.data(), o.rolling_method,
                                            levels.empty() ? &none_q : levels.data());
     }
+    if (!rc && pairs && !o.rolling_pair.empty()) {
+        pairs->assign(rows.size(), atsc_window_pair{});
+        atsc_window_pair none_p;
+        uint8_t *other = nullptr;
+        uint64_t olen = 0;
+        rc = atsc_bro_read_file(o.rolling_pair.c_str(), &other, &olen);
+        if (!rc && !other) rc = ATSC_E_FORMAT;  // not a BRO file
+        if (!rc) rc = atsc_bro_open(other, olen, nullptr, nullptr);
+        if (!rc)
+            rc = atsc_rolling_pair_windows(ctx, bro + 9, len - 9, 1, other + 9, olen - 9, 1, 1, &begin, &count, o.rolling,
+                                           o.rolling_stride, pairs->empty() ? &none_p : pairs->data());
+        atsc_free(other);
+    }
     return rc;
 }
 
@@ -718,12 +742,14 @@ int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketO
 // first sample) that atsc_moments_fit reads off it, all six empty where the count is 0 (the count column says so); the
 // column is avg because mean is taken: sum / count in the rolling's order.  names (--rolling-quantiles): behind those a
 // column q<level as typed> per level, from the position's row of `levels` (NaN where the window holds no sample).
+// pairs (--rolling-pair; null without it): as the last columns pair_count,covariance,correlation,slope,intercept, --pair's
+// columns, from the position's record and what atsc_pair_fit reads off it; the four cells empty where pair_count is 0.
 // false: the file could not be written.
 template <class Place>
 bool rolling_write(const std::string &path, const char *first, const std::vector<atsc_window_rolling> &rows, bool with_deltas,
                    const std::vector<atsc_window_delta> &deltas, const std::vector<atsc_window_delta_fit> &fits,
                    bool with_moments, const std::vector<atsc_window_moments> &moments, const std::vector<std::string> &names,
-                   const std::vector<double> &levels, Place place)
+                   const std::vector<double> &levels, const std::vector<atsc_window_pair> *pairs, Place place)
 {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return false;
@@ -731,6 +757,7 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
             with_deltas ? ",pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase" : "",
             with_moments ? ",nonnan,avg,stdvar,stddev,slope,intercept" : "");
     for (const std::string &n : names) fprintf(f, ",q%s", n.c_str());
+    if (pairs) fprintf(f, ",pair_count,covariance,correlation,slope,intercept");
     fprintf(f, "\n");
     for (size_t j = 0; j < rows.size(); ++j) {
         const atsc_window_rolling &r = rows[j];
@@ -752,6 +779,14 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
                          debug_f64(fit.intercept).c_str());
         }
         for (size_t q = 0; q < names.size(); ++q) fprintf(f, ",%s", debug_f64(levels[j * names.size() + q]).c_str());
+        if (pairs) {
+            const atsc_window_pair &p = (*pairs)[j];
+            atsc_window_pair_fit pf;
+            atsc_pair_fit(&p, 1, &pf);
+            if (p.count == 0) fprintf(f, ",0,,,,");
+            else fprintf(f, ",%llu,%s,%s,%s,%s", (unsigned long long)p.count, debug_f64(pf.covariance).c_str(),
+                         debug_f64(pf.correlation).c_str(), debug_f64(pf.slope).c_str(), debug_f64(pf.intercept).c_str());
+        }
         fprintf(f, "\n");
     }
     return fclose(f) == 0;

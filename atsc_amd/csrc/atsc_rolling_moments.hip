@@ -15,7 +15,8 @@
 //   upper      one wavefront per 64 aligned chunks of level 11 (and of level 17): the six levels above by shuffles;
 //   positions  one wavefront per task, a lane per position: the lane walks its window's chunks left to right, a chunk
 //              below ROLL_MOMENTS_LOW formed from the samples by the same tree, the others read from the pyramid.
-// A partial is the node's five doubles and its count in a 64-bit word: 48 bytes.  No atomics: every partial and every
+// A partial is the node's five doubles and its count in a 64-bit word: 48 bytes (atsc_rolling_node.h, which the rolling
+// pair moments share: atsc_rolling_pair.hip; that call runs this file's upper kernel over its own pyramid).  No atomics: every partial and every
 // record has one writer, and a chunk's node is the same bits wherever it is formed.
 //
 // The divide: Merge divides by the joint count.  Two nodes of the same non-zero count -- every merge of a NaN-free chunk
@@ -24,18 +25,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "atsc_moment_node.h"
+#include "atsc_rolling_node.h"
 
 namespace atsc {
 
 namespace {
-
-// a partial as the pyramid holds it; in registers it is a Node (a chunk holds at most 2^20 samples)
-struct alignas(16) RmPart {
-    double mx, m2x, mt, m2t, c;
-    uint64_t n;
-};
-static_assert(sizeof(RmPart) == ROLL_MOMENTS_PART, "a partial is 48 bytes");
 
 // the record as the position kernel stores it, at the 8-byte alignment the result has
 struct alignas(8) RmRec {
@@ -44,30 +38,8 @@ struct alignas(8) RmRec {
 };
 static_assert(sizeof(RmRec) == sizeof(atsc_window_moments), "the record's layout");
 
-DEVI Node rm_none() { return Node{0.0, 0.0, 0.0, 0.0, 0.0, 0}; }
-
 // the leaf of the sample v at stream index j (below 2^53: exact in f64)
 DEVI Node rm_leaf(double v, uint64_t j) { return node_leaf(v, (double)j, !__builtin_isnan(v)); }
-
-// Merge(a, b): equal non-zero counts skip the divide (the same bits: node_merge)
-DEVI Node rm_merge(const Node &a, const Node &b)
-{
-    if (a.n == b.n && a.n != 0) return node_merge<true>(a, b);
-    return node_merge<false>(a, b);
-}
-
-DEVI Node rm_load(const RmPart *p)
-{
-    const double2 a = ((const double2 *)p)[0], b = ((const double2 *)p)[1], c = ((const double2 *)p)[2];  // three 16-byte loads
-    return Node{a.x, a.y, b.x, b.y, c.x, (uint32_t)(uint64_t)__double_as_longlong(c.y)};
-}
-
-DEVI void rm_store(RmPart *p, const Node &r)
-{
-    ((double2 *)p)[0] = make_double2(r.mx, r.m2x);
-    ((double2 *)p)[1] = make_double2(r.mt, r.m2t);
-    ((double2 *)p)[2] = make_double2(r.c, __longlong_as_double((long long)(uint64_t)r.n));
-}
 
 }  // namespace
 

@@ -111,6 +111,13 @@ __attribute__((weak)) hipError_t launch_rmo_upper(void *pyr, const DevRollPiece 
 __attribute__((weak)) hipError_t launch_rmo_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                       const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
                                                       void *out, hipStream_t s);
+// the windowed rolling pair moments' pyramid and position kernels (atsc_rolling_pair.hip; weak for the same reason); the
+// levels above 11 are launch_rmo_upper's
+__attribute__((weak)) hipError_t launch_rpa_pyramid(const double *sx, const double *sy, uint32_t n_tiles, void *pyr,
+                                                    const DevRollPiece *pc, uint32_t lmax, hipStream_t s);
+__attribute__((weak)) hipError_t launch_rpa_positions(const DevRollTask *tasks, uint32_t n, const double *sx, const double *sy,
+                                                      const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
+                                                      void *out, hipStream_t s);
 // the windowed rolling quantiles' span kernel (atsc_rolling_quantile.hip; weak for the same reason)
 __attribute__((weak)) hipError_t launch_rq_span(const DevRollTask *tasks, uint32_t n, uint32_t P, uint64_t B,
                                                 const double *scratch, uint64_t a0, uint32_t w, uint64_t stride,
@@ -388,7 +395,7 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
                           BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
                           BY_ROLLING = DECODE_CALLER("rolling"), BY_ROLLING_DELTA = DECODE_CALLER("rolling delta"),
-                          BY_ROLLING_MOMENTS = DECODE_CALLER("rolling moments"),
+                          BY_ROLLING_MOMENTS = DECODE_CALLER("rolling moments"), BY_ROLLING_PAIR = DECODE_CALLER("rolling pair"),
                           BY_ROLLING_QUANTILE = DECODE_CALLER("rolling quantile"), BY_ACROSS = DECODE_CALLER("across"),
                           BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile"),
                           BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes"),
@@ -2406,7 +2413,35 @@ static int rolling_check(atsc_ctx *ctx, const char *call, uint64_t n, const uint
 }
 
 // What differs between the device calls that read every position's window off a pyramid of chunk partials
-// (rolling_dev): the rolling, the rolling deltas and the rolling moments.
+// (rolling_dev): the rolling, the rolling deltas, the rolling moments and the rolling pair moments.  The launchers take
+// the list of the inputs' regions: the adapters below forward scr[0], or scr[0] and scr[1], to the kernels' own.
+using RollPyramidFn = hipError_t (*)(const double *const *scr, uint32_t n_tiles, void *pyr, const DevRollPiece *pc, uint32_t lmax,
+                                     hipStream_t s);
+using RollPositionsFn = hipError_t (*)(const DevRollTask *tasks, uint32_t n, const double *const *scr, const void *pyr,
+                                       const DevRollPiece *pc, uint64_t w, uint64_t stride, void *out, hipStream_t s);
+template <decltype(&launch_roll_pyramid) F>
+static hipError_t roll_pyramid_one(const double *const *scr, uint32_t n_tiles, void *pyr, const DevRollPiece *pc, uint32_t lmax,
+                                   hipStream_t s)
+{
+    return F(scr[0], n_tiles, pyr, pc, lmax, s);
+}
+template <decltype(&launch_roll_positions) F>
+static hipError_t roll_positions_one(const DevRollTask *tasks, uint32_t n, const double *const *scr, const void *pyr,
+                                     const DevRollPiece *pc, uint64_t w, uint64_t stride, void *out, hipStream_t s)
+{
+    return F(tasks, n, scr[0], pyr, pc, w, stride, out, s);
+}
+static hipError_t roll_pyramid_pair(const double *const *scr, uint32_t n_tiles, void *pyr, const DevRollPiece *pc, uint32_t lmax,
+                                    hipStream_t s)
+{
+    return launch_rpa_pyramid(scr[0], scr[1], n_tiles, pyr, pc, lmax, s);
+}
+static hipError_t roll_positions_pair(const DevRollTask *tasks, uint32_t n, const double *const *scr, const void *pyr,
+                                      const DevRollPiece *pc, uint64_t w, uint64_t stride, void *out, hipStream_t s)
+{
+    return launch_rpa_positions(tasks, n, scr[0], scr[1], pyr, pc, w, stride, out, s);
+}
+
 struct RollKernel {
     const char *call;            // names the call in the messages
     const char *no_kernels;      // ATSC_E_UNSUPPORTED's message
@@ -2416,9 +2451,11 @@ struct RollKernel {
     uint32_t low;                // the lowest stored level
     uint32_t first;              // a window's chunks are those of [lo + first, lo + w): 0, or 1 where the leaf is a pair
     uint32_t rec_bytes;          // a position's record
-    decltype(&launch_roll_pyramid) pyramid;
+    int inputs;                  // the streams the kernels read: 1, or 2 (the pair)
+    bool have;                   // the kernels' launchers are linked in (they are weak)
+    RollPyramidFn pyramid;
     decltype(&launch_roll_upper) upper;
-    decltype(&launch_roll_positions) positions;
+    RollPositionsFn positions;
     // the pyramid's bytes per sample of the region: the levels low, low + 1, .. hold less than 2 / 2^low partials a sample
     uint64_t pyramid_bytes() const { return (2ull * part_bytes) >> low; }
 };
@@ -2437,20 +2474,32 @@ struct RollKernel {
 // ATSC_E_CAPACITY.  Per range and per piece, the run of positions the piece computes is cut into tasks of ROLL_TASK
 // positions.  One upload (decode tasks, tasks, the pieces' level tables); then per piece the decode, the pyramid (with
 // the levels above 11 and above 17 a small launch each) and the positions.
-static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
-                       const uint64_t *count, uint64_t width, uint64_t stride, void *d_out, void *stream, uint64_t org,
-                       const RollKernel &K)
+// in: the K.inputs streams the kernels read (1, or the pair's 2), as reduce_dev takes them; begin[] counts from
+// in[0].org.  All of the above is computed once, in the stream's index, which the inputs share; per piece every input is
+// decoded with its own decode tasks into a region of its own, its spill slots behind it (place_regions), and the one
+// pyramid follows all regions.  A slot then costs 8 K.inputs + K.pyramid_bytes() bytes: Lr is that share of all the
+// inputs' piece_samples together.  Every input's windows are checked against its own plan; the call's tables and scratch
+// are in[0].dp's (res[Q_ROLLING]).
+static int rolling_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                       uint64_t width, uint64_t stride, void *d_out, void *stream, const RollKernel &K)
 {
     const char *const CALL = K.call;
-    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count))) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    const int NI = K.inputs;
+    if (!ctx || NI < 1 || NI > 2 || (n_windows && (!begin || !count))) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    for (int k = 0; k < NI; ++k)
+        if (!in[k].dp || (n_windows && !in[k].d_body)) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    for (int k = 1; k < NI; ++k)
+        if (in[k].dp->ctx != in[0].dp->ctx) return fail_in(ctx, ATSC_E_INVALID, CALL, "plans of different contexts");
+    const atsc_dplan *const dp = in[0].dp;
+    const uint64_t org = in[0].org;  // begin[] counts from here
     uint64_t total = 0;
     int rc = rolling_check(ctx, CALL, n_windows, count, width, stride, &total);
     if (rc) return rc;
     if (total && !d_out) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
-    rc = check_windows(ctx, CALL, dp, d_out, "d_out", n_windows, begin, count, ~0ull);
+    for (int k = 0; k < NI && !rc; ++k)
+        rc = check_windows(ctx, CALL, in[k].dp, d_out, "d_out", n_windows, begin, count, ~0ull, org, in[k].org);
     if (rc || total == 0) return rc;
-    if (!launch_decompress_window || !launch_window_gather || !K.pyramid || !K.upper || !K.positions)
-        return fail_in(ctx, ATSC_E_UNSUPPORTED, CALL, K.no_kernels);
+    if (!launch_decompress_window || !launch_window_gather || !K.have) return fail_in(ctx, ATSC_E_UNSUPPORTED, CALL, K.no_kernels);
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const uint64_t W = n_windows, T = ROLL_TILE, w = width;
@@ -2461,17 +2510,17 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
         if (m[i]) cov.emplace_back(org + begin[i], org + begin[i] + (m[i] - 1) * stride + w);
     }
     merge_spans(cov);
-    uint64_t spill;
-    const uint64_t pyr_bytes = K.pyramid_bytes();
-    const uint64_t L = piece_samples(ctx, dp, org, cov, 1, &spill);
-    const uint64_t Lr = std::max<uint64_t>(AGG_MIN_PIECE, L * sizeof(double) / (sizeof(double) + pyr_bytes) / T * T);
+    uint64_t spill[2] = {0, 0};
+    const uint64_t slot_bytes = sizeof(double) * NI + K.pyramid_bytes();  // of one slot: its sample in every region, its share of the pyramid
+    const uint64_t L = piece_samples(ctx, in, NI, cov, 1, spill);
+    const uint64_t Lr = std::max<uint64_t>(AGG_MIN_PIECE, L * NI * sizeof(double) / slot_bytes / T * T);
     const uint64_t Lp = Lr - 3 * T;
     if (w > Lp) {
         char msg[192];
         snprintf(msg, sizeof msg,
                  "%s: a window of %llu samples does not fit one scratch piece; an aggregate scratch budget of "
                  "%llu bytes would hold it", CALL, (unsigned long long)w,
-                 (unsigned long long)((w + 4 * T) * (sizeof(double) + pyr_bytes) + spill * sizeof(double)));
+                 (unsigned long long)((w + 4 * T) * slot_bytes + (spill[0] + spill[1]) * sizeof(double)));
         return fail(ctx, ATSC_E_CAPACITY, msg);
     }
     // pieces: samples [first, second) of the stream, ascending; scratch[0] is sample first / T * T
@@ -2531,28 +2580,32 @@ static int rolling_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_bod
             dec[p] = Span(pieces[p].a0, pcs[p].second);
         }
     }
-    std::vector<PieceDecode> pdec;
-    DecodeTasks D;
-    rc = emit_pieces_decode(ctx, CALL, dp, org, cov, dec, 1, region, D, pdec);
+    std::vector<PieceDecode> pdec[2];
+    DecodeTasks D[2];
+    for (int k = 0; k < NI && !rc; ++k) rc = emit_pieces_decode(ctx, CALL, in[k].dp, in[k].org, cov, dec, 1, region, D[k], pdec[k]);
     if (rc) return rc;
     QueryRes &R = dp->res[Q_ROLLING];
     HIPCHK(ctx, R.wait());
     Upload up;
-    D.place(up);
+    for (int k = 0; k < NI; ++k) D[k].place(up);
     const size_t off_tasks = up.add(tasks), off_pieces = up.add(pieces);
-    // the scratch: the region, the spill slots, the pyramid (four or six doubles a partial; region and MAX_FRAME are even
-    // numbers of doubles, so the pyramid begins at a multiple of 16 bytes, as its 16-byte loads and stores need)
-    const uint64_t pyr_at = region + (uint64_t)MAX_FRAME * D.spills_used;
+    // the scratch: every input's region and spill slots, then the pyramid (four or six doubles a partial; region and
+    // MAX_FRAME are even numbers of doubles, so the pyramid begins at a multiple of 16 bytes, as its 16-byte loads and
+    // stores need)
+    uint64_t scr_at[2] = {0, 0};
+    const uint64_t pyr_at = place_regions(D, NI, region, scr_at);
     rc = stage_upload(ctx, R, up, pyr_at + K.part_bytes / sizeof(double) * pyr_n, s);
     if (rc) return rc;
     unsigned char *d = R.d;
-    double *scr = R.scratch;
-    void *pyr = scr + pyr_at;
+    double *scr[2] = {R.scratch + scr_at[0], R.scratch + scr_at[1]};
+    void *pyr = R.scratch + pyr_at;
     const DevRollTask *d_tasks = (const DevRollTask *)(d + off_tasks);
     const DevRollPiece *d_pieces = (const DevRollPiece *)(d + off_pieces);
     for (size_t p = 0; p < P; ++p) {
-        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, K.who);
-        if (rc) return rc;
+        for (int k = 0; k < NI; ++k) {
+            rc = launch_piece_decode(ctx, in[k].dp, in[k].d_body, d, D[k], pdec[k][p], scr[k], scr[k], scr[k], s, K.who);
+            if (rc) return rc;
+        }
         const uint64_t a0 = pieces[p].a0, last = pieces[p].a1 - 1;
         LAUNCHCHK(ctx, K.launch_name[0], K.pyramid(scr, (uint32_t)((pieces[p].a1 - a0) / T), pyr, d_pieces + p, lmax, s));
         for (uint32_t src = ROLL_TILE_LOG; src < lmax; src += 6)
@@ -2573,8 +2626,9 @@ struct RollKernelPlain {
     static RollKernel kernel()
     {
         return RollKernel{CALL, "no rolling kernels", {"launch k_roll_pyramid", "launch k_roll_upper", "launch k_roll_positions"},
-                          BY_ROLLING, sizeof(DevAggPart), ROLL_LOW, 0, sizeof(atsc_window_rolling),
-                          &launch_roll_pyramid, &launch_roll_upper, &launch_roll_positions};
+                          BY_ROLLING, sizeof(DevAggPart), ROLL_LOW, 0, sizeof(atsc_window_rolling), 1,
+                          launch_roll_pyramid && launch_roll_upper && launch_roll_positions,
+                          &roll_pyramid_one<&launch_roll_pyramid>, &launch_roll_upper, &roll_positions_one<&launch_roll_positions>};
     }
 };
 struct RollKernelDelta {
@@ -2582,8 +2636,9 @@ struct RollKernelDelta {
     static RollKernel kernel()
     {
         return RollKernel{CALL, "no rolling delta kernels", {"launch k_rdl_pyramid", "launch k_rdl_upper", "launch k_rdl_positions"},
-                          BY_ROLLING_DELTA, ROLL_DELTA_PART, ROLL_DELTA_LOW, 1, sizeof(atsc_window_delta),
-                          &launch_rdl_pyramid, &launch_rdl_upper, &launch_rdl_positions};
+                          BY_ROLLING_DELTA, ROLL_DELTA_PART, ROLL_DELTA_LOW, 1, sizeof(atsc_window_delta), 1,
+                          launch_rdl_pyramid && launch_rdl_upper && launch_rdl_positions,
+                          &roll_pyramid_one<&launch_rdl_pyramid>, &launch_rdl_upper, &roll_positions_one<&launch_rdl_positions>};
     }
 };
 struct RollKernelMoments {
@@ -2591,8 +2646,20 @@ struct RollKernelMoments {
     static RollKernel kernel()
     {
         return RollKernel{CALL, "no rolling moments kernels", {"launch k_rmo_pyramid", "launch k_rmo_upper", "launch k_rmo_positions"},
-                          BY_ROLLING_MOMENTS, ROLL_MOMENTS_PART, ROLL_MOMENTS_LOW, 0, sizeof(atsc_window_moments),
-                          &launch_rmo_pyramid, &launch_rmo_upper, &launch_rmo_positions};
+                          BY_ROLLING_MOMENTS, ROLL_MOMENTS_PART, ROLL_MOMENTS_LOW, 0, sizeof(atsc_window_moments), 1,
+                          launch_rmo_pyramid && launch_rmo_upper && launch_rmo_positions,
+                          &roll_pyramid_one<&launch_rmo_pyramid>, &launch_rmo_upper, &roll_positions_one<&launch_rmo_positions>};
+    }
+};
+// the rolling pair moments: two inputs, the rolling moments' partial and its upper levels (they merge partials only)
+struct RollKernelPair {
+    static constexpr const char *CALL = "rolling_pair_windows";
+    static RollKernel kernel()
+    {
+        return RollKernel{CALL, "no rolling pair kernels", {"launch k_rpa_pyramid", "launch k_rmo_upper", "launch k_rpa_positions"},
+                          BY_ROLLING_PAIR, ROLL_MOMENTS_PART, ROLL_MOMENTS_LOW, 0, sizeof(atsc_window_pair), 2,
+                          launch_rpa_pyramid && launch_rmo_upper && launch_rpa_positions,
+                          &roll_pyramid_pair, &launch_rmo_upper, &roll_positions_pair};
     }
 };
 template <class KERNEL>
@@ -2613,7 +2680,29 @@ struct RollQueryOf {
     int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
             const uint64_t *cnt, void *d_res, void *stream, uint64_t org) const
     {
-        return rolling_dev(ctx, dp, d_body, n_windows, begin, cnt, width, stride, d_res, stream, org, KERNEL::kernel());
+        const QueryInput in{dp, d_body, org};
+        return rolling_dev(ctx, &in, n_windows, begin, cnt, width, stride, d_res, stream, KERNEL::kernel());
+    }
+};
+// The rolling pair moments' descriptor (see PairQuery): the one rolling call over two inputs.
+struct RollPairQuery {
+    static constexpr int INPUTS = 2;
+    static constexpr const char *CALL = RollKernelPair::CALL;
+    uint64_t width, stride;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_rolling_outputs(count[i], width, stride);
+        return total * sizeof(atsc_window_pair);
+    }
+    int check(atsc_ctx *ctx) const { return rolling_check(ctx, CALL, count ? n_ranges : 0, count, width, stride, nullptr); }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
+    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
+            void *stream) const
+    {
+        return rolling_dev(ctx, in, n_windows, begin, cnt, width, stride, d_res, stream, RollKernelPair::kernel());
     }
 };
 using RollQuery = RollQueryOf<RollKernelPlain>;
@@ -2676,6 +2765,31 @@ extern "C" int atsc_rolling_moments_windows(atsc_ctx *ctx, const uint8_t *body, 
 {
     ATSC_API_BEGIN
     return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, RollMomentsQuery{width, stride, count, n_windows});
+    ATSC_API_END
+}
+
+// windowed rolling pair moments: the pair moments' record of the window at every position of sample ranges of two
+// streams (atsc_rolling_pair.hip), through the rolling's device call with two inputs: its tables and scratch are the
+// rolling's of dp_x, dp_x->res[Q_ROLLING]
+extern "C" int atsc_rolling_pair_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp_x, const uint8_t *d_body_x, const atsc_dplan *dp_y,
+                                             const uint8_t *d_body_y, uint64_t n_windows, const uint64_t *begin,
+                                             const uint64_t *count, uint64_t width, uint64_t stride, atsc_window_pair *d_out,
+                                             void *stream)
+{
+    ATSC_API_BEGIN
+    const QueryInput in[2] = {{dp_x, d_body_x, 0}, {dp_y, d_body_y, 0}};
+    return RollPairQuery{width, stride, count, n_windows}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    ATSC_API_END
+}
+
+extern "C" int atsc_rolling_pair_windows(atsc_ctx *ctx, const uint8_t *body_x, uint64_t len_x, int has_count_x,
+                                         const uint8_t *body_y, uint64_t len_y, int has_count_y, uint64_t n_windows,
+                                         const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                         atsc_window_pair *out)
+{
+    ATSC_API_BEGIN
+    const HostBody hb[2] = {{body_x, len_x, has_count_x}, {body_y, len_y, has_count_y}};
+    return query_host(ctx, hb, n_windows, begin, count, out, RollPairQuery{width, stride, count, n_windows});
     ATSC_API_END
 }
 
@@ -3504,6 +3618,15 @@ extern "C" int atsc_stream_pair_windows(atsc_stream *x, atsc_stream *y, uint64_t
     ATSC_API_BEGIN
     atsc_stream *const st[2] = {x, y};
     return query_stream(st, n_windows, begin, count, out, PairQuery());
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_rolling_pair_windows(atsc_stream *x, atsc_stream *y, uint64_t n_windows, const uint64_t *begin,
+                                                const uint64_t *count, uint64_t width, uint64_t stride, atsc_window_pair *out)
+{
+    ATSC_API_BEGIN
+    atsc_stream *const st[2] = {x, y};
+    return query_stream(st, n_windows, begin, count, out, RollPairQuery{width, stride, count, n_windows});
     ATSC_API_END
 }
 

@@ -211,7 +211,7 @@ int uncompress_rolling(const Args &a, const std::string &output_base, uint8_t *b
     }
     atsc_free(bro);
     const uint64_t w = a.q.rolling, stride = a.q.rolling_stride;
-    if (!rolling_write(with_ext(output_base, "roll.csv"), "timestamp", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments, a.q.rolling_level_names, levels,
+    if (!rolling_write(with_ext(output_base, "roll.csv"), "timestamp", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments, a.q.rolling_level_names, levels, nullptr,
                        [&](uint64_t j) { return std::to_string((long long)ts[begin + j * stride + w - 1]); }))
         return die("failed to write rolling records to file");
     return 0;

@@ -235,9 +235,13 @@ def _rolling_moments_block(n, cargs):
     return WINDOW_MOMENTS.itemsize * cargs.records
 
 
+def _rolling_pair_block(n, cargs):
+    return WINDOW_PAIR.itemsize * cargs.records
+
+
 def _rolling_result(run, counts, width, stride, record=WINDOW_ROLLING):
     """run(records) -> the block of a rolling call as uint64 words.  -> (records, off): the `record` records
-    (WINDOW_ROLLING; the rolling deltas': WINDOW_DELTA; the rolling moments': WINDOW_MOMENTS) of every position, range after range, and the ranges' record
+    (WINDOW_ROLLING; the rolling deltas': WINDOW_DELTA; the rolling moments': WINDOW_MOMENTS; the rolling pair moments': WINDOW_PAIR) of every position, range after range, and the ranges' record
     offsets (rolling_offsets)"""
     off = rolling_offsets(counts, width, stride)
     return run(int(off[-1])).view(record), off
@@ -347,6 +351,7 @@ _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _s
 _ROLLING = _Query("rolling_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_block)
 _ROLLING_DELTA = _Query("rolling_delta_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_delta_block)
 _ROLLING_MOMENTS = _Query("rolling_moments_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_moments_block)
+_ROLLING_PAIR = _Query("rolling_pair_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_pair_block, inputs=2)
 _ROLLING_QUANTILE = _Query("rolling_quantile_windows", np.dtype(np.uint64), None, _rolling_quantile_params, _rolling_quantile_block)
 _ACROSS = _Query("across_windows", np.dtype(np.uint64), None, _across_params, _across_block, inputs=None)
 _ACROSS_QUANTILE = _Query("across_quantile_windows", np.dtype(np.uint64), None, _across_quantile_params, _across_quantile_block,
@@ -738,6 +743,16 @@ class Context:
             lambda m: _query_host(_ROLLING_QUANTILE, self, records, begins, counts, has_count, width, stride, m, levels, method),
             counts, width, stride, levels)
 
+    def rolling_pair_windows_host(self, records_x, records_y, begins, counts, width, stride=1, has_count=False):
+        """-> (records, off): the pair moments' record (count, mean_x, m2_x, mean_y, m2_y, c_xy) of the window of `width`
+        samples at every `stride`-th position of every range [begins[i], begins[i] + counts[i]) of the two decoded
+        record streams (atsc_rolling_pair_windows): sample j of x goes with sample j of y, and a position's window must
+        lie inside both.  records: a WINDOW_PAIR array, range after range, which pair_fit takes (covariance,
+        correlation, the slope and intercept of y on x); off: as rolling_windows_host's"""
+        return _rolling_result(lambda m: _query_host(_ROLLING_PAIR, self, records_x, begins, counts, has_count, width, stride, m,
+                                                     others=(records_y,)),
+                               counts, width, stride, WINDOW_PAIR)
+
     def across_windows_host(self, records_list, begins, counts, stride=1, has_count=False):
         """-> (records, off): count / min / max / sum over the streams of records_list (at most ACROSS_MAX_STREAMS
         decoded record streams, sample j of one going with sample j of every other) at every `stride`-th position of
@@ -989,6 +1004,17 @@ class DPlan:
         m, n_q = int(off[-1]), len(_levels(levels)[0])
         _query_dev(_ROLLING_QUANTILE, self, d_body, begins, counts, d_out, stream, width, stride, m, levels, method)
         return d_out.view(-1)[: m * n_q].view(m, n_q), off
+
+    def rolling_pair_windows(self, d_body, other, other_body, begins, counts, width, stride, d_out, stream=0):
+        """Enqueues the pair moments' record of this plan's stream (x) and the plan `other`'s (y; its device bytes
+        other_body) over the window of `width` samples at every `stride`-th position of the ranges [begins[i],
+        begins[i] + counts[i]) into d_out, a device tensor of at least 48 bytes per position
+        (atsc_rolling_pair_windows_dev; WINDOW_PAIR records, range after range).  other may be this plan.  -> the
+        ranges' record offsets (rolling_offsets)"""
+        off = rolling_offsets(counts, width, stride)
+        _query_dev(_ROLLING_PAIR, self, d_body, begins, counts, d_out, stream, width, stride, int(off[-1]),
+                   others=((other, other_body),))
+        return off
 
     def across_windows(self, d_body, others, other_bodies, begins, counts, d_out, stride=1, stream=0):
         """Enqueues count / min / max / sum over this plan's stream (stream 0) and the plans `others` (their device

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import capi
 from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_ROLLING, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit, pair_fit  # noqa: F401
-from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _ROLLING_DELTA, _ROLLING_MOMENTS, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
+from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _ROLLING_DELTA, _ROLLING_MOMENTS, _ROLLING_PAIR, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
 from .engine import ACROSS_RECORD, _ACROSS, _across_host, _across_list, _across_result  # noqa: F401
 from .engine import _ACROSS_QUANTILE, _across_quantile_result
 from .engine import _ROLLING_QUANTILE, _rolling_quantile_result
@@ -178,6 +178,13 @@ class CompressedStream:
             lambda m: _query_stream(_ROLLING_QUANTILE, self, begins, counts, width, stride, m, levels, method), counts, width,
             stride, levels)
 
+    def rolling_pair_windows(self, other, begins, counts, width, stride=1):
+        """-> (records, off): the pair moments' record of this stream (x) and `other` (y) over the window of `width`
+        samples at every `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as
+        Context.rolling_pair_windows_host gives them (atsc_stream_rolling_pair_windows)"""
+        return _rolling_result(lambda m: _query_stream(_ROLLING_PAIR, self, begins, counts, width, stride, m, others=(other,)),
+                               counts, width, stride, WINDOW_PAIR)
+
     def across_windows(self, others, begins, counts, stride=1):
         """-> (records, off) over this stream (stream 0) and the streams `others` (stream 1 and on) at every
         `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as Context.across_windows_host gives
@@ -331,6 +338,19 @@ def rolling_quantile_data_windows(ctx, bro, begins, counts, width, levels, strid
     return _rolling_quantile_result(
         lambda m: _query_image(_ROLLING_QUANTILE, ctx, bro, begins, counts, width, stride, m, levels, method), counts, width,
         stride, levels)
+
+
+def rolling_pair_data_windows(ctx, bro_x, bro_y, begins, counts, width, stride=1):
+    """-> (records, off): the pair moments' record of the window of `width` samples at every `stride`-th position of
+    ranges of decompress_data(ctx, bro_x) (x) and decompress_data(ctx, bro_y) (y), as
+    Context.rolling_pair_windows_host gives them: atsc_bro_open of each image, then atsc_rolling_pair_windows over the
+    records of both"""
+    bodies = []
+    for bro in (bro_x, bro_y):
+        b = np.frombuffer(bytes(bro), dtype=np.uint8)
+        capi.check(capi.lib().atsc_bro_open(b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), None, None))
+        bodies.append(b[9:].tobytes())  # the records from the frame-count varint on, as atsc_decompress_data reads them
+    return ctx.rolling_pair_windows_host(bodies[0], bodies[1], begins, counts, width, stride, has_count=True)
 
 
 def across_data_windows(ctx, bros, begins, counts, stride=1):

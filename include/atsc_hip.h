@@ -942,6 +942,59 @@ int atsc_rolling_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t b
                                   const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
                                   uint32_t n_q, const double *q, int method, double *out);
 
+/* Windowed rolling pair moments: the pair moments' record (atsc_window_pair, 48 bytes) of the sliding window at every
+ * position of ranges of TWO decoded streams X and Y: a rolling correlation ("does latency follow load over the last five
+ * minutes, at every step"), a rolling beta (the regression slope of y on x), the covariance against a reference series
+ * -- without listing one window per position for atsc_pair_windows.  Sample j of X goes with sample j of Y; the streams
+ * may differ in length, framing, codecs and tiers.  atsc_pair_fit applies to the records unchanged.
+ *   Ranges     Ranges, width, stride, the number and the order of the records (atsc_rolling_outputs), the limits
+ *              1 <= width <= ATSC_ROLLING_MAX_WIDTH and 2^32 - 2 records, validation, the errors (ATSC_E_INVALID with
+ *              nothing written and before any GPU work; ATSC_E_FORMAT or the status word of the plan it belongs to for a
+ *              malformed payload inside a position's window), pieces and ATSC_E_CAPACITY are atsc_rolling_windows'.  The
+ *              messages name rolling_pair_windows.  A range that reaches beyond the end of EITHER stream is
+ *              ATSC_E_INVALID.  The two plans (or streams) must belong to one context, else ATSC_E_INVALID; dp_x == dp_y
+ *              is allowed.
+ *   Node, leaf, Merge   atsc_pair_windows', word for word: the node is (n, mx, M2x, my, M2y, C); the leaf of stream
+ *              index j is (1, x[j], 0, y[j], 0, 0), the empty node (n = 0) where x[j] or y[j] is NaN; Merge(a, b) is a,
+ *              bit for bit, when nb == 0, b when na == 0, else the rule given there, every operation one correctly
+ *              rounded f64 + - * /, never fused.
+ *   Order      atsc_rolling_moments_windows', word for word: N(a, 0) = leaf(a); N(a, l) = Merge(N(a, l - 1),
+ *              N(a + 2^(l-1), l - 1)), for a a multiple of 2^l in the stream index.  The window's chunks are the
+ *              rolling's, left to right: pos = lo; while pos < lo + w, take the largest l with pos % 2^l == 0 and
+ *              pos + 2^l <= lo + w, emit (pos, l), pos += 2^l.  R = Merge(Merge(Merge(empty, N(c_1)), N(c_2)), ...), the
+ *              left operand as a.
+ *   Record     count = n, mean_x = mx, m2_x = M2x, mean_y = my, m2_y = M2y, c_xy = C; when count == 0 all five doubles
+ *              are NaN.  No field is counted from lo: there is no subtract.  +-Inf samples give what IEEE gives under
+ *              these rules; where the rule yields NaN, any NaN bit pattern conforms.
+ * Consequences: a position's bytes depend on the two streams' samples and (lo, w) only: not on the range the window came
+ * from, the stride, the other ranges, the budget, the piece boundaries, either stream's framing, the host, the device or
+ * the stream call.  With X and Y swapped the record is the same with the x and y fields swapped, bit for bit.  With Y the
+ * same stream as X, mean_y == mean_x and m2_y == c_xy == m2_x, and count, mean_x and m2_x are
+ * atsc_rolling_moments_windows' count, mean and m2 of that stream, bit for bit (the tree and the merge are the same).
+ * count is atsc_pair_windows' of the listed window (lo, w), exactly; the five doubles come from another tree than that
+ * call's and MAY DIFFER from its in their last bits; each lies within its own stated bound.
+ * With u = 2^-53, L = max(1, ceil(log2 w)), kappa_x = sqrt(1 + count mean_x^2 / m2_x) and kappa_y alike, for finite data:
+ *   |mean_x - exact| <= (3 L + 2) u mean|x|;          |m2_x - exact| <= (3 L + 2) u kappa_x m2_x;    (and for y)
+ *   |c_xy - exact| <= (3 L + 2) u kappa_x kappa_y sqrt(m2_x m2_y);
+ * the pair's bounds with 3 L + 2 for L + 2, the step the rolling moments took from the windowed moments: a node passes
+ * at most L merges inside a chunk and at most 2 L - 1 in the chain.  m2_x == 0 and c_xy == 0 exactly where x is constant
+ * over the window's counted samples (and for y).
+ * The chunk partials are the rolling moments' 48 bytes, at most 12 bytes a slot beside the 8 of each stream's decoded
+ * sample: 28 bytes a slot inside the budget of atsc_ctx_set_aggregate_scratch (the rolling moments': 20); a width that
+ * the budget's piece does not hold is ATSC_E_CAPACITY, and the message names the budget that would hold it,
+ * (w + 4 * 2048) * 28 bytes and the spill slots of the large frames.  The default budget holds every width.
+ * begin / count are HOST arrays; d_body_x, d_body_y and d_out are device memory (d_out 8-byte aligned, 48 bytes per
+ * record).  Enqueued on `stream`, not synchronised.  The call keeps its tables and scratch in the rolling's place of
+ * dp_x: it and the rolling, rolling delta and rolling moments calls on dp_x wait (host side) for each other. */
+int atsc_rolling_pair_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp_x, const uint8_t *d_body_x, const atsc_dplan *dp_y,
+                                  const uint8_t *d_body_y, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                  uint64_t width, uint64_t stride, atsc_window_pair *d_out, void *stream);
+/* Host bytes in, host records out, synchronous, as atsc_pair_windows is; computes the device call's bits.  ATSC_E_FORMAT
+ * (nothing written) for a malformed payload inside a position's window in either stream. */
+int atsc_rolling_pair_windows(atsc_ctx *ctx, const uint8_t *body_x, uint64_t len_x, int has_count_x, const uint8_t *body_y,
+                              uint64_t len_y, int has_count_y, uint64_t n_windows, const uint64_t *begin,
+                              const uint64_t *count, uint64_t width, uint64_t stride, atsc_window_pair *out);
+
 /* Windowed across: count, min, max and sum over N streams at every position of ranges of the decoded streams (the
  * indices of atsc_decompress_frames): one value per sample index folded across many series -- `sum by (job)(x)`,
  * `max by (zone)(x)`, how many replicas report at this instant and which one is the worst -- without the decoded
@@ -1274,6 +1327,9 @@ int atsc_stream_rolling_moments_windows(atsc_stream *s, uint64_t n_windows, cons
 int atsc_stream_rolling_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                          uint64_t width, uint64_t stride, uint32_t n_q, const double *q, int method,
                                          double *out);
+/* atsc_rolling_pair_windows over the frames of two streams of one context (x and y may be the same stream) */
+int atsc_stream_rolling_pair_windows(atsc_stream *x, atsc_stream *y, uint64_t n_windows, const uint64_t *begin,
+                                     const uint64_t *count, uint64_t width, uint64_t stride, atsc_window_pair *out);
 /* atsc_moments_windows over the stream's frames */
 int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                 atsc_window_moments *out);
