@@ -17,7 +17,7 @@ from .engine import SELECTED, select_bytes  # noqa: F401
 from .capi import ROLLING_MAX_WIDTH  # noqa: F401
 from .engine import WINDOW_ROLLING, rolling_offsets, rolling_outputs  # noqa: F401
 from .stream import rolling_data_windows, rolling_delta_data_windows, rolling_moments_data_windows  # noqa: F401
-from .stream import rolling_pair_data_windows  # noqa: F401
+from .stream import rolling_pair_data_windows, rolling_runs_data_windows  # noqa: F401
 from .capi import ROLLING_QUANTILE_MAX_WIDTH  # noqa: F401
 from .stream import rolling_quantile_data_windows  # noqa: F401
 from .capi import ACROSS_MAX_STREAMS  # noqa: F401

@@ -141,6 +141,10 @@ SIGNATURES = {
     "atsc_rolling_delta_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp, _vp]),
     "atsc_rolling_delta_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint64,
                                              C.c_uint64, _vp]),
+    "atsc_rolling_runs_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, C.c_int,
+                                                C.c_double, _vp, _vp]),
+    "atsc_rolling_runs_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint64,
+                                            C.c_uint64, C.c_int, C.c_double, _vp]),
     "atsc_rolling_moments_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp, _vp]),
     "atsc_rolling_moments_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint64,
                                                C.c_uint64, _vp]),
@@ -195,6 +199,8 @@ SIGNATURES = {
     "atsc_stream_select_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double, C.c_uint64, _vp]),
     "atsc_stream_rolling_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp]),
     "atsc_stream_rolling_delta_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp]),
+    "atsc_stream_rolling_runs_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, C.c_int, C.c_double,
+                                                   _vp]),
     "atsc_stream_rolling_moments_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp]),
     "atsc_stream_rolling_quantile_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, C.c_uint32,
                                                        _f64p, C.c_int, _vp]),

@@ -4,7 +4,7 @@
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
-//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments]
+//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments] [--rolling-runs OP:LIMIT]
 //        [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]] [--rolling-pair OTHER.bro]]
 //        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]
 //        [--across-extremes K] [--across-moments]]]
@@ -89,6 +89,11 @@ void usage()
             "                                 columns: nonnan,avg,stdvar,stddev,slope,intercept (as --moments: population\n"
             "                                 forms, slope per sample, intercept at the position's first sample; all empty\n"
             "                                 where the window holds no sample)\n"
+            "      --rolling-runs <OP:LIMIT>  with --rolling: also every position's samples with value OP LIMIT and their runs (as\n"
+            "                                 --runs), behind those columns: samples,inside,runs,longest,longest_at,first_at,\n"
+            "                                 last_at,head,tail,excess; the three positions count from the position's first\n"
+            "                                 sample and are empty where there is none (inside == samples: every sample of the\n"
+            "                                 window meets the condition, an alert's `for:`)\n"
             "      --rolling-quantiles <Q,Q,..>  with --rolling, W at most 8192: also every position's levels (0 <= Q <= 1, as\n"
             "                                 --quantiles), as the last columns: one q<Q> per level as typed; NaN where the\n"
             "                                 window holds no sample\n"
@@ -207,12 +212,13 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
             std::vector<double> levels;
             rc = atsc_bro_open(bro, len, nullptr, nullptr);
             std::vector<atsc_window_pair> pairs;
-            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, deltas, fits, moments, levels, &pairs);
+            std::vector<atsc_window_runs> runs;
+            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, deltas, fits, moments, levels, runs, &pairs);
             atsc_free(bro);
             if (rc) return rc;
             const uint64_t stride = a.q.rolling_stride;  // a position's first sample, counted from the window's begin
             return rolling_write(with_ext(path, "roll.csv"), "offset", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments, a.q.rolling_level_names, levels,
-                                 a.q.rolling_pair.empty() ? nullptr : &pairs,
+                                 a.q.rolling_runs, runs, a.q.rolling_pair.empty() ? nullptr : &pairs,
                                  [stride](uint64_t j) { return std::to_string(j * stride); })
                        ? ATSC_OK
                        : ATSC_E_IO;

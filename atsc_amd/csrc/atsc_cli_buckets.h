@@ -78,6 +78,9 @@ struct BucketOptions {
     uint64_t rolling_stride = 1;
     bool rolling_deltas = false;  // --rolling-deltas: pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase behind .roll.csv's own
     bool rolling_moments = false;  // --rolling-moments: nonnan,avg,stdvar,stddev,slope,intercept behind those
+    bool rolling_runs = false;  // --rolling-runs OP:LIMIT: samples,inside,runs,longest,longest_at,first_at,last_at,head,tail,excess behind those
+    int rolling_runs_op = ATSC_RUNS_GT;
+    double rolling_runs_limit = 0.0;
     std::vector<double> rolling_levels;  // --rolling-quantiles Q,Q,..: one column per level behind those
     std::vector<std::string> rolling_level_names;
     std::string rolling_pair;  // --rolling-pair OTHER.bro (where pair_allowed): pair_count,covariance,correlation,slope,intercept as the last columns
@@ -284,6 +287,12 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
         o.rolling_deltas = true;
     } else if (s == "--rolling-moments") {
         o.rolling_moments = true;
+    } else if (value("--rolling-runs")) {
+        if (!parse_runs(v, o.rolling_runs_op, o.rolling_runs_limit)) {
+            fprintf(stderr, "error: invalid value '%s': '--rolling-runs' wants OP:LIMIT (OP: gt ge lt le eq ne)\n", v.c_str());
+            return 2;
+        }
+        o.rolling_runs = true;
     } else if (value("--rolling-quantiles")) {
         if (!parse_levels(v, o.rolling_levels, o.rolling_level_names)) {
             fprintf(stderr, "error: invalid value '%s' for '--rolling-quantiles': expected levels in 0..=1, comma separated\n",
@@ -410,7 +419,7 @@ bool where_option_complete(const BucketOptions &o, const char *window, bool wind
 }
 
 // --rolling goes with the option that names the window and without the one that cuts buckets, as --where does, and
-// not with --where; --rolling-deltas, --rolling-moments, --rolling-quantiles and --rolling-pair go with --rolling, --rolling-quantile-method
+// not with --where; --rolling-deltas, --rolling-moments, --rolling-runs, --rolling-quantiles and --rolling-pair go with --rolling, --rolling-quantile-method
 // with --rolling-quantiles, and --rolling-quantiles with a W of at most ATSC_ROLLING_QUANTILE_MAX_WIDTH.  false: a usage
 // error, reported on stderr.
 bool rolling_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
@@ -422,9 +431,10 @@ bool rolling_option_complete(const BucketOptions &o, const char *window, bool wi
     if (!o.rolling) {
         if (o.rolling_deltas) fprintf(stderr, "error: '--rolling-deltas' needs '--rolling'\n");
         if (o.rolling_moments) fprintf(stderr, "error: '--rolling-moments' needs '--rolling'\n");
+        if (o.rolling_runs) fprintf(stderr, "error: '--rolling-runs' needs '--rolling'\n");
         if (!o.rolling_levels.empty()) fprintf(stderr, "error: '--rolling-quantiles' needs '--rolling'\n");
         if (!o.rolling_pair.empty()) fprintf(stderr, "error: '--rolling-pair' needs '--rolling'\n");
-        return !o.rolling_deltas && !o.rolling_moments && o.rolling_levels.empty() && o.rolling_pair.empty();
+        return !o.rolling_deltas && !o.rolling_moments && !o.rolling_runs && o.rolling_levels.empty() && o.rolling_pair.empty();
     }
     if (!o.rolling_levels.empty() && o.rolling > ATSC_ROLLING_QUANTILE_MAX_WIDTH) {
         fprintf(stderr, "error: '--rolling-quantiles' needs a '--rolling' W in 1..=%llu\n",
@@ -685,13 +695,14 @@ bool where_write(const std::string &path, const char *first, const std::vector<a
 
 // --rolling: one record per position of the range [begin, begin + count) of a .bro image; deltas: with --rolling-deltas,
 // the same positions' rolling deltas and what atsc_delta_derive reads off them; moments: with --rolling-moments, the
-// same positions' rolling moments; levels: with --rolling-quantiles, the same positions' rows of levels; pairs: with
+// same positions' rolling moments; levels: with --rolling-quantiles, the same positions' rows of levels; runs: with
+// --rolling-runs OP:LIMIT, the same positions' rolling runs under that condition; pairs: with
 // --rolling-pair OTHER.bro, the same positions' rolling pair moments against that file's samples (sample i of it goes
 // with sample i of this one; a file that ends before a window fails as --pair's does)
 int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
                   std::vector<atsc_window_rolling> &rows, std::vector<atsc_window_delta> &deltas,
                   std::vector<atsc_window_delta_fit> &fits, std::vector<atsc_window_moments> &moments,
-                  std::vector<double> &levels, std::vector<atsc_window_pair> *pairs = nullptr)
+                  std::vector<double> &levels, std::vector<atsc_window_runs> &runs, std::vector<atsc_window_pair> *pairs = nullptr)
 {
     rows.assign(atsc_rolling_outputs(count, o.rolling, o.rolling_stride), atsc_window_rolling{});
     atsc_window_rolling none;
@@ -718,6 +729,12 @@ int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketO
                                            (uint32_t)o.rolling_levels.size(), o.rolling_levels.data(), o.rolling_method,
                                            levels.empty() ? &none_q : levels.data());
     }
+    if (!rc && o.rolling_runs) {
+        runs.assign(rows.size(), atsc_window_runs{});
+        atsc_window_runs none_r;
+        rc = atsc_rolling_runs_windows(ctx, bro + 9, len - 9, 1, 1, &begin, &count, o.rolling, o.rolling_stride, o.rolling_runs_op,
+                                       o.rolling_runs_limit, runs.empty() ? &none_r : runs.data());
+    }
     if (!rc && pairs && !o.rolling_pair.empty()) {
         pairs->assign(rows.size(), atsc_window_pair{});
         atsc_window_pair none_p;
@@ -742,6 +759,9 @@ int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketO
 // first sample) that atsc_moments_fit reads off it, all six empty where the count is 0 (the count column says so); the
 // column is avg because mean is taken: sum / count in the rolling's order.  names (--rolling-quantiles): behind those a
 // column q<level as typed> per level, from the position's row of `levels` (NaN where the window holds no sample).
+// with_runs (--rolling-runs): behind those samples,inside,runs,longest,longest_at,first_at,last_at,head,tail,excess from
+// the position's record of `runs`, the three positions counted from the position's first sample and empty where the
+// record has ATSC_RUNS_NONE, as --runs' cells are.
 // pairs (--rolling-pair; null without it): as the last columns pair_count,covariance,correlation,slope,intercept, --pair's
 // columns, from the position's record and what atsc_pair_fit reads off it; the four cells empty where pair_count is 0.
 // false: the file could not be written.
@@ -749,7 +769,8 @@ template <class Place>
 bool rolling_write(const std::string &path, const char *first, const std::vector<atsc_window_rolling> &rows, bool with_deltas,
                    const std::vector<atsc_window_delta> &deltas, const std::vector<atsc_window_delta_fit> &fits,
                    bool with_moments, const std::vector<atsc_window_moments> &moments, const std::vector<std::string> &names,
-                   const std::vector<double> &levels, const std::vector<atsc_window_pair> *pairs, Place place)
+                   const std::vector<double> &levels, bool with_runs, const std::vector<atsc_window_runs> &runs,
+                   const std::vector<atsc_window_pair> *pairs, Place place)
 {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return false;
@@ -757,6 +778,7 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
             with_deltas ? ",pairs,rises,falls,up,down,after_falls,max_rise,max_fall,increase" : "",
             with_moments ? ",nonnan,avg,stdvar,stddev,slope,intercept" : "");
     for (const std::string &n : names) fprintf(f, ",q%s", n.c_str());
+    if (with_runs) fprintf(f, ",samples,inside,runs,longest,longest_at,first_at,last_at,head,tail,excess");
     if (pairs) fprintf(f, ",pair_count,covariance,correlation,slope,intercept");
     fprintf(f, "\n");
     for (size_t j = 0; j < rows.size(); ++j) {
@@ -779,6 +801,13 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
                          debug_f64(fit.intercept).c_str());
         }
         for (size_t q = 0; q < names.size(); ++q) fprintf(f, ",%s", debug_f64(levels[j * names.size() + q]).c_str());
+        if (with_runs) {
+            const atsc_window_runs &rv = runs[j];
+            auto pos = [](uint64_t p) { return p == ATSC_RUNS_NONE ? std::string() : std::to_string(p); };
+            fprintf(f, ",%llu,%llu,%llu,%llu,%s,%s,%s,%llu,%llu,%s", (unsigned long long)rv.samples, (unsigned long long)rv.inside,
+                    (unsigned long long)rv.runs, (unsigned long long)rv.longest, pos(rv.longest_at).c_str(), pos(rv.first_at).c_str(),
+                    pos(rv.last_at).c_str(), (unsigned long long)rv.head, (unsigned long long)rv.tail, debug_f64(rv.excess).c_str());
+        }
         if (pairs) {
             const atsc_window_pair &p = (*pairs)[j];
             atsc_window_pair_fit pf;

@@ -359,7 +359,13 @@ constexpr uint32_t ROLL_DELTA_PART = 48;  // bytes of a partial: three sums, two
 constexpr uint32_t ROLL_MOMENTS_LOW = 3;    // the lowest stored level
 constexpr uint32_t ROLL_MOMENTS_PART = 48;  // bytes of a partial: the node's five doubles, the count in a 64-bit word
 
-// windowed rolling quantiles (atsc_rolling_quantile_windows_dev, atsc_rolling_quantile.hip): the rolling's pieces and
+// windowed rolling runs (atsc_rolling_runs_windows_dev, atsc_rolling_runs.hip): the rolling's pieces, tasks, pyramid and
+// chunks over the runs' nodes (DevRunPart's merge rule), positions counted from the chunk's first sample; the condition
+// is an argument of the pyramid and the position kernels; the highest level is floor(log2 w)
+constexpr uint32_t ROLL_RUNS_LOW = 3;    // the lowest stored level
+constexpr uint32_t ROLL_RUNS_PART = 32;  // bytes of a partial: five 21-bit and three 20-bit fields in three words, the f64 excess
+
+// windowed rolling quantiles (atsc_rolling_quantile_windows_dev,atsc_rolling_quantile.hip): the rolling's pieces and
 // tasks without a pyramid.  A task's windows cover a span of (n - 1) stride + w samples, which one workgroup sorts in
 // P slots of LDS and reads every position's levels off.  P by the width alone: the least power of two in
 // [RQ_SPAN_MIN, RQ_SPAN_MAX] that holds two windows, RQ_SPAN_MAX above that; a task holds (P - w) / stride + 1 positions.

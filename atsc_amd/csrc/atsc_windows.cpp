@@ -1,5 +1,5 @@
 // atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms,
-// rolling windows, rolling deltas and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
+// rolling windows, rolling deltas, rolling runs and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
 // and count, min, max, sum, quantiles, extremes and moments across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
@@ -118,6 +118,15 @@ __attribute__((weak)) hipError_t launch_rpa_pyramid(const double *sx, const doub
 __attribute__((weak)) hipError_t launch_rpa_positions(const DevRollTask *tasks, uint32_t n, const double *sx, const double *sy,
                                                       const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
                                                       void *out, hipStream_t s);
+// the windowed rolling runs' pyramid and position kernels (atsc_rolling_runs.hip; weak for the same reason); op, limit: the
+// call's condition
+__attribute__((weak)) hipError_t launch_rru_pyramid(const double *scratch, uint32_t n_tiles, void *pyr, const DevRollPiece *pc,
+                                                    uint32_t lmax, int op, double limit, hipStream_t s);
+__attribute__((weak)) hipError_t launch_rru_upper(void *pyr, const DevRollPiece *pc, uint32_t n, uint32_t src, uint32_t lmax,
+                                                  hipStream_t s);
+__attribute__((weak)) hipError_t launch_rru_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
+                                                      const void *pyr, const DevRollPiece *pc, uint64_t w, uint64_t stride,
+                                                      int op, double limit, void *out, hipStream_t s);
 // the windowed rolling quantiles' span kernel (atsc_rolling_quantile.hip; weak for the same reason)
 __attribute__((weak)) hipError_t launch_rq_span(const DevRollTask *tasks, uint32_t n, uint32_t P, uint64_t B,
                                                 const double *scratch, uint64_t a0, uint32_t w, uint64_t stride,
@@ -396,6 +405,7 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
                           BY_ROLLING = DECODE_CALLER("rolling"), BY_ROLLING_DELTA = DECODE_CALLER("rolling delta"),
                           BY_ROLLING_MOMENTS = DECODE_CALLER("rolling moments"), BY_ROLLING_PAIR = DECODE_CALLER("rolling pair"),
+                          BY_ROLLING_RUNS = DECODE_CALLER("rolling runs"),
                           BY_ROLLING_QUANTILE = DECODE_CALLER("rolling quantile"), BY_ACROSS = DECODE_CALLER("across"),
                           BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile"),
                           BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes"),
@@ -1014,6 +1024,14 @@ struct DltQuery {
     }
 };
 
+// the runs' check of a call's condition (the rolling runs' too); `call` names the caller in the message
+static int runs_condition_check(atsc_ctx *ctx, const char *call, int op, double limit)
+{
+    if (op < ATSC_RUNS_GT || op > ATSC_RUNS_NE) return fail_in(ctx, ATSC_E_INVALID, call, "unknown op");
+    if (std::isnan(limit)) return fail_in(ctx, ATSC_E_INVALID, call, "limit is NaN");
+    return ATSC_OK;
+}
+
 static void run_empty_record(atsc_window_runs &r)
 {
     r.samples = r.inside = r.runs = r.longest = r.head = r.tail = 0;
@@ -1049,12 +1067,7 @@ struct RunQuery {
         return launch_run_combine(c, n, (DevRunPart *)part, (const uint64_t *)side, out, s);
     }
     static size_t out_bytes(uint64_t n) { return n * sizeof(atsc_window_runs); }
-    int check(atsc_ctx *ctx) const
-    {
-        if (op < ATSC_RUNS_GT || op > ATSC_RUNS_NE) return fail(ctx, ATSC_E_INVALID, "runs_windows: unknown op");
-        if (std::isnan(limit)) return fail(ctx, ATSC_E_INVALID, "runs_windows: limit is NaN");
-        return ATSC_OK;
-    }
+    int check(atsc_ctx *ctx) const { return runs_condition_check(ctx, CALL, op, limit); }
     static void fill_empty(void *out, uint64_t n)
     {
         for (uint64_t i = 0; i < n; ++i) run_empty_record(((atsc_window_runs *)out)[i]);
@@ -2413,33 +2426,53 @@ static int rolling_check(atsc_ctx *ctx, const char *call, uint64_t n, const uint
 }
 
 // What differs between the device calls that read every position's window off a pyramid of chunk partials
-// (rolling_dev): the rolling, the rolling deltas, the rolling moments and the rolling pair moments.  The launchers take
-// the list of the inputs' regions: the adapters below forward scr[0], or scr[0] and scr[1], to the kernels' own.
+// (rolling_dev): the rolling, the rolling deltas, the rolling moments, the rolling pair moments and the rolling runs.  The
+// launchers take the list of the inputs' regions and the call's condition (RollCond: the rolling runs' op and limit, the
+// one parameter of a call that a pyramid depends on): the adapters below forward scr[0], or scr[0] and scr[1], and where
+// the kernels take it the condition, to the kernels' own.
+struct RollCond {
+    int op;
+    double limit;
+};
 using RollPyramidFn = hipError_t (*)(const double *const *scr, uint32_t n_tiles, void *pyr, const DevRollPiece *pc, uint32_t lmax,
-                                     hipStream_t s);
+                                     const RollCond &cond, hipStream_t s);
 using RollPositionsFn = hipError_t (*)(const DevRollTask *tasks, uint32_t n, const double *const *scr, const void *pyr,
-                                       const DevRollPiece *pc, uint64_t w, uint64_t stride, void *out, hipStream_t s);
+                                       const DevRollPiece *pc, uint64_t w, uint64_t stride, const RollCond &cond, void *out,
+                                       hipStream_t s);
 template <decltype(&launch_roll_pyramid) F>
 static hipError_t roll_pyramid_one(const double *const *scr, uint32_t n_tiles, void *pyr, const DevRollPiece *pc, uint32_t lmax,
-                                   hipStream_t s)
+                                   const RollCond &, hipStream_t s)
 {
     return F(scr[0], n_tiles, pyr, pc, lmax, s);
 }
 template <decltype(&launch_roll_positions) F>
 static hipError_t roll_positions_one(const DevRollTask *tasks, uint32_t n, const double *const *scr, const void *pyr,
-                                     const DevRollPiece *pc, uint64_t w, uint64_t stride, void *out, hipStream_t s)
+                                     const DevRollPiece *pc, uint64_t w, uint64_t stride, const RollCond &, void *out,
+                                     hipStream_t s)
 {
     return F(tasks, n, scr[0], pyr, pc, w, stride, out, s);
 }
 static hipError_t roll_pyramid_pair(const double *const *scr, uint32_t n_tiles, void *pyr, const DevRollPiece *pc, uint32_t lmax,
-                                    hipStream_t s)
+                                    const RollCond &, hipStream_t s)
 {
     return launch_rpa_pyramid(scr[0], scr[1], n_tiles, pyr, pc, lmax, s);
 }
 static hipError_t roll_positions_pair(const DevRollTask *tasks, uint32_t n, const double *const *scr, const void *pyr,
-                                      const DevRollPiece *pc, uint64_t w, uint64_t stride, void *out, hipStream_t s)
+                                      const DevRollPiece *pc, uint64_t w, uint64_t stride, const RollCond &, void *out,
+                                      hipStream_t s)
 {
     return launch_rpa_positions(tasks, n, scr[0], scr[1], pyr, pc, w, stride, out, s);
+}
+static hipError_t roll_pyramid_runs(const double *const *scr, uint32_t n_tiles, void *pyr, const DevRollPiece *pc, uint32_t lmax,
+                                    const RollCond &cond, hipStream_t s)
+{
+    return launch_rru_pyramid(scr[0], n_tiles, pyr, pc, lmax, cond.op, cond.limit, s);
+}
+static hipError_t roll_positions_runs(const DevRollTask *tasks, uint32_t n, const double *const *scr, const void *pyr,
+                                      const DevRollPiece *pc, uint64_t w, uint64_t stride, const RollCond &cond, void *out,
+                                      hipStream_t s)
+{
+    return launch_rru_positions(tasks, n, scr[0], pyr, pc, w, stride, cond.op, cond.limit, out, s);
 }
 
 struct RollKernel {
@@ -2456,6 +2489,7 @@ struct RollKernel {
     RollPyramidFn pyramid;
     decltype(&launch_roll_upper) upper;
     RollPositionsFn positions;
+    RollCond cond = {0, 0.0};    // the call's condition (the rolling runs'); the other calls' kernels take none
     // the pyramid's bytes per sample of the region: the levels low, low + 1, .. hold less than 2 / 2^low partials a sample
     uint64_t pyramid_bytes() const { return (2ull * part_bytes) >> low; }
 };
@@ -2466,8 +2500,8 @@ struct RollKernel {
 // width - 1, so that every position's window lies whole in a piece: the first one that holds it computes it.  A piece
 // lies in the scratch from the multiple of ROLL_TILE at or in front of its first sample on, so that a slot's place in
 // the region and its stream index agree modulo ROLL_TILE; the pyramid of the piece's chunk partials (levels K.low ..
-// floor(log2(width - K.first)); the rolling's 32 bytes each: at most 8 bytes a sample, the rolling deltas' and the rolling
-// moments' 48: at most 12)
+// floor(log2(width - K.first)); the rolling's and the rolling runs' 32 bytes each: at most 8 bytes a sample, the rolling
+// deltas' and the rolling moments' 48: at most 12)
 // follows the region and the spill slots in the same scratch.  Region and pyramid share the budget in the proportion of
 // their bytes per sample, 8 to K.pyramid_bytes(): a region holds at most that share of piece_samples' length, Lr (the
 // rolling's half, the rolling deltas' two fifths), and a piece Lp = Lr - 3 ROLL_TILE samples.  A width above Lp is
@@ -2607,12 +2641,12 @@ static int rolling_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, 
             if (rc) return rc;
         }
         const uint64_t a0 = pieces[p].a0, last = pieces[p].a1 - 1;
-        LAUNCHCHK(ctx, K.launch_name[0], K.pyramid(scr, (uint32_t)((pieces[p].a1 - a0) / T), pyr, d_pieces + p, lmax, s));
+        LAUNCHCHK(ctx, K.launch_name[0], K.pyramid(scr, (uint32_t)((pieces[p].a1 - a0) / T), pyr, d_pieces + p, lmax, K.cond, s));
         for (uint32_t src = ROLL_TILE_LOG; src < lmax; src += 6)
             LAUNCHCHK(ctx, K.launch_name[1],
                       K.upper(pyr, d_pieces + p, (uint32_t)(((last >> src) >> 6) - ((a0 >> src) >> 6) + 1), src, lmax, s));
         LAUNCHCHK(ctx, K.launch_name[2],
-                  K.positions(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, pyr, d_pieces + p, w, stride, d_out, s));
+                  K.positions(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, pyr, d_pieces + p, w, stride, K.cond, d_out, s));
     }
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
@@ -2705,6 +2739,48 @@ struct RollPairQuery {
         return rolling_dev(ctx, in, n_windows, begin, cnt, width, stride, d_res, stream, RollKernelPair::kernel());
     }
 };
+// The rolling runs' descriptor: the rolling's, with the runs' condition, which is checked in front of the rolling's own
+// parameters and handed to the kernels through the RollKernel (the runs' rule: RunQuery::check).
+struct RollKernelRuns {
+    static constexpr const char *CALL = "rolling_runs_windows";
+    static RollKernel kernel(int op, double limit)
+    {
+        return RollKernel{CALL, "no rolling runs kernels", {"launch k_rru_pyramid", "launch k_rru_upper", "launch k_rru_positions"},
+                          BY_ROLLING_RUNS, ROLL_RUNS_PART, ROLL_RUNS_LOW, 0, sizeof(atsc_window_runs), 1,
+                          launch_rru_pyramid && launch_rru_upper && launch_rru_positions,
+                          &roll_pyramid_runs, &launch_rru_upper, &roll_positions_runs, RollCond{op, limit}};
+    }
+};
+struct RollRunsQuery {
+    static constexpr int INPUTS = 1;
+    static constexpr const char *CALL = RollKernelRuns::CALL;
+    uint64_t width, stride;
+    int op;
+    double limit;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_rolling_outputs(count[i], width, stride);
+        return total * sizeof(atsc_window_runs);
+    }
+    int check(atsc_ctx *ctx) const
+    {
+        const int rc = runs_condition_check(ctx, CALL, op, limit);
+        return rc ? rc : rolling_check(ctx, CALL, count ? n_ranges : 0, count, width, stride, nullptr);
+    }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
+    // (the condition is checked in front of the arguments, as RunQuery's is)
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *cnt, void *d_res, void *stream, uint64_t org) const
+    {
+        const int rc = runs_condition_check(ctx, CALL, op, limit);
+        if (rc) return rc;
+        const QueryInput in{dp, d_body, org};
+        return rolling_dev(ctx, &in, n_windows, begin, cnt, width, stride, d_res, stream, RollKernelRuns::kernel(op, limit));
+    }
+};
 using RollQuery = RollQueryOf<RollKernelPlain>;
 using RollDeltaQuery = RollQueryOf<RollKernelDelta>;
 using RollMomentsQuery = RollQueryOf<RollKernelMoments>;
@@ -2744,6 +2820,27 @@ extern "C" int atsc_rolling_delta_windows(atsc_ctx *ctx, const uint8_t *body, ui
 {
     ATSC_API_BEGIN
     return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out, RollDeltaQuery{width, stride, count, n_windows});
+    ATSC_API_END
+}
+
+// windowed rolling runs: the runs' record of the window at every position of sample ranges under the condition x OP limit
+// (atsc_rolling_runs.hip), through the rolling's device call: its tables and scratch are the rolling's, dp->res[Q_ROLLING]
+extern "C" int atsc_rolling_runs_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                             const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                             int op, double limit, atsc_window_runs *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    return RollRunsQuery{width, stride, op, limit, count, n_windows}.dev(ctx, dp, d_body, n_windows, begin, count, d_out, stream, 0);
+    ATSC_API_END
+}
+
+extern "C" int atsc_rolling_runs_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                         const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride, int op,
+                                         double limit, atsc_window_runs *out)
+{
+    ATSC_API_BEGIN
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out,
+                      RollRunsQuery{width, stride, op, limit, count, n_windows});
     ATSC_API_END
 }
 
@@ -3592,6 +3689,14 @@ extern "C" int atsc_stream_rolling_delta_windows(atsc_stream *s, uint64_t n_wind
 {
     ATSC_API_BEGIN
     return query_stream(s, n_windows, begin, count, out, RollDeltaQuery{width, stride, count, n_windows});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_rolling_runs_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                                uint64_t width, uint64_t stride, int op, double limit, atsc_window_runs *out)
+{
+    ATSC_API_BEGIN
+    return query_stream(s, n_windows, begin, count, out, RollRunsQuery{width, stride, op, limit, count, n_windows});
     ATSC_API_END
 }
 

@@ -5,7 +5,7 @@
 //
 //   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
 //                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]
-//                  [--extremes K] [--values K[:ABOVE]]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments]
+//                  [--extremes K] [--values K[:ABOVE]]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments] [--rolling-runs OP:LIMIT]
 //                  [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]]]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
@@ -86,6 +86,11 @@ void usage()
             "                                 columns: nonnan,avg,stdvar,stddev,slope,intercept (as --moments: population\n"
             "                                 forms, slope per sample, intercept at the position's first sample; all empty\n"
             "                                 where the window holds no sample)\n"
+            "      --rolling-runs <OP:LIMIT>  with --rolling: also every position's samples with value OP LIMIT and their runs (as\n"
+            "                                 --runs), behind those columns: samples,inside,runs,longest,longest_at,first_at,\n"
+            "                                 last_at,head,tail,excess; the three positions count samples from the position's\n"
+            "                                 first one and are empty where there is none (inside == samples: every sample of\n"
+            "                                 the window meets the condition, an alert's `for:`)\n"
             "      --rolling-quantiles <Q,Q,..>  with --rolling, W at most 8192: also every position's levels (0 <= Q <= 1, as\n"
             "                                 --quantiles), as the last columns: one q<Q> per level as typed; NaN where the\n"
             "                                 window holds no sample\n"
@@ -199,19 +204,20 @@ int uncompress_rolling(const Args &a, const std::string &output_base, uint8_t *b
     std::vector<atsc_window_delta> deltas;
     std::vector<atsc_window_delta_fit> fits;
     std::vector<atsc_window_moments> moments;
+    std::vector<atsc_window_runs> runs;
     std::vector<double> levels;
     if (count) {
         atsc_ctx *ctx = nullptr;
         rc = atsc_ctx_create(&ctx, 0);
         if (rc) { atsc_free(bro); return die("no GPU context", rc); }
         rc = atsc_bro_open(bro, len, nullptr, nullptr);
-        if (!rc) rc = rolling_query(ctx, bro, len, a.q, begin, count, rows, deltas, fits, moments, levels);
+        if (!rc) rc = rolling_query(ctx, bro, len, a.q, begin, count, rows, deltas, fits, moments, levels, runs);
         if (rc) { int e = die("rolling", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
         atsc_ctx_destroy(ctx);
     }
     atsc_free(bro);
     const uint64_t w = a.q.rolling, stride = a.q.rolling_stride;
-    if (!rolling_write(with_ext(output_base, "roll.csv"), "timestamp", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments, a.q.rolling_level_names, levels, nullptr,
+    if (!rolling_write(with_ext(output_base, "roll.csv"), "timestamp", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments, a.q.rolling_level_names, levels, a.q.rolling_runs, runs, nullptr,
                        [&](uint64_t j) { return std::to_string((long long)ts[begin + j * stride + w - 1]); }))
         return die("failed to write rolling records to file");
     return 0;

@@ -239,9 +239,20 @@ def _rolling_pair_block(n, cargs):
     return WINDOW_PAIR.itemsize * cargs.records
 
 
+def _rolling_runs_params(width, stride, records, op, limit):
+    """the rolling's arguments, then the runs' condition"""
+    a = _RollArgs(tuple(_rolling_params(width, stride, records)) + _runs_params(op, limit))
+    a.records = int(records)
+    return a
+
+
+def _rolling_runs_block(n, cargs):
+    return WINDOW_RUNS.itemsize * cargs.records
+
+
 def _rolling_result(run, counts, width, stride, record=WINDOW_ROLLING):
     """run(records) -> the block of a rolling call as uint64 words.  -> (records, off): the `record` records
-    (WINDOW_ROLLING; the rolling deltas': WINDOW_DELTA; the rolling moments': WINDOW_MOMENTS; the rolling pair moments': WINDOW_PAIR) of every position, range after range, and the ranges' record
+    (WINDOW_ROLLING; the rolling deltas': WINDOW_DELTA; the rolling moments': WINDOW_MOMENTS; the rolling pair moments': WINDOW_PAIR; the rolling runs': WINDOW_RUNS) of every position, range after range, and the ranges' record
     offsets (rolling_offsets)"""
     off = rolling_offsets(counts, width, stride)
     return run(int(off[-1])).view(record), off
@@ -351,6 +362,7 @@ _SELECT = _Query("select_windows", np.dtype(np.uint64), None, _select_params, _s
 _ROLLING = _Query("rolling_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_block)
 _ROLLING_DELTA = _Query("rolling_delta_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_delta_block)
 _ROLLING_MOMENTS = _Query("rolling_moments_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_moments_block)
+_ROLLING_RUNS = _Query("rolling_runs_windows", np.dtype(np.uint64), None, _rolling_runs_params, _rolling_runs_block)
 _ROLLING_PAIR = _Query("rolling_pair_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_pair_block, inputs=2)
 _ROLLING_QUANTILE = _Query("rolling_quantile_windows", np.dtype(np.uint64), None, _rolling_quantile_params, _rolling_quantile_block)
 _ACROSS = _Query("across_windows", np.dtype(np.uint64), None, _across_params, _across_block, inputs=None)
@@ -724,6 +736,17 @@ class Context:
         return _rolling_result(lambda m: _query_host(_ROLLING_DELTA, self, records, begins, counts, has_count, width, stride, m),
                                counts, width, stride, WINDOW_DELTA)
 
+    def rolling_runs_windows_host(self, records, begins, counts, width, op, limit, stride=1, has_count=False):
+        """-> (records, off): the runs' record (samples, inside, runs, the longest run and where, the first and last
+        inside sample, head, tail, excess) under the condition x OP limit (op: RUNS_GT .. RUNS_NE) of the window of
+        `width` samples at every `stride`-th position of every range [begins[i], begins[i] + counts[i]) of the decoded
+        records (atsc_rolling_runs_windows).  records: a WINDOW_RUNS array, range after range, positions counted from
+        each window's first sample; runs_merge folds the records of adjacent disjoint positions (stride == width); off:
+        as rolling_windows_host's"""
+        return _rolling_result(
+            lambda m: _query_host(_ROLLING_RUNS, self, records, begins, counts, has_count, width, stride, m, op, limit),
+            counts, width, stride, WINDOW_RUNS)
+
     def rolling_moments_windows_host(self, records, begins, counts, width, stride=1, has_count=False):
         """-> (records, off): the moments' record (count, mean, m2, t_mean, t_m2, c_tx) of the window of `width` samples
         at every `stride`-th position of every range [begins[i], begins[i] + counts[i]) of the decoded records
@@ -983,6 +1006,15 @@ class DPlan:
         (rolling_offsets)"""
         off = rolling_offsets(counts, width, stride)
         _query_dev(_ROLLING_DELTA, self, d_body, begins, counts, d_out, stream, width, stride, int(off[-1]))
+        return off
+
+    def rolling_runs_windows(self, d_body, begins, counts, width, stride, op, limit, d_out, stream=0):
+        """Enqueues the runs' record under the condition x OP limit of the window of `width` samples at every
+        `stride`-th position of the ranges [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least
+        80 bytes per position (atsc_rolling_runs_windows_dev; WINDOW_RUNS records, range after range).  -> the ranges'
+        record offsets (rolling_offsets)"""
+        off = rolling_offsets(counts, width, stride)
+        _query_dev(_ROLLING_RUNS, self, d_body, begins, counts, d_out, stream, width, stride, int(off[-1]), op, limit)
         return off
 
     def rolling_moments_windows(self, d_body, begins, counts, width, stride, d_out, stream=0):

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import capi
 from .engine import WINDOW_DELTA, WINDOW_MOMENTS, WINDOW_PAIR, WINDOW_ROLLING, WINDOW_RUNS, WINDOW_STATS, _levels, _windows, delta_derive, moments_fit, pair_fit  # noqa: F401
-from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _ROLLING_DELTA, _ROLLING_MOMENTS, _ROLLING_PAIR, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
+from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, _QUANTILE, _ROLLING, _ROLLING_DELTA, _ROLLING_MOMENTS, _ROLLING_PAIR, _ROLLING_RUNS, _RUNS, _SELECT, _VALUES, _query_others, _query_result, _query_rows, _rolling_result, _select_result
 from .engine import ACROSS_RECORD, _ACROSS, _across_host, _across_list, _across_result  # noqa: F401
 from .engine import _ACROSS_QUANTILE, _across_quantile_result
 from .engine import _ROLLING_QUANTILE, _rolling_quantile_result
@@ -162,6 +162,13 @@ class CompressedStream:
         (atsc_stream_rolling_delta_windows)"""
         return _rolling_result(lambda m: _query_stream(_ROLLING_DELTA, self, begins, counts, width, stride, m), counts, width,
                                stride, WINDOW_DELTA)
+
+    def rolling_runs_windows(self, begins, counts, width, op, limit, stride=1):
+        """-> (records, off): the runs' record under the condition x OP limit of the window of `width` samples at every
+        `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as Context.rolling_runs_windows_host
+        gives them (atsc_stream_rolling_runs_windows)"""
+        return _rolling_result(lambda m: _query_stream(_ROLLING_RUNS, self, begins, counts, width, stride, m, op, limit),
+                               counts, width, stride, WINDOW_RUNS)
 
     def rolling_moments_windows(self, begins, counts, width, stride=1):
         """-> (records, off): the moments' record of the window of `width` samples at every `stride`-th position of the
@@ -321,6 +328,14 @@ def rolling_delta_data_windows(ctx, bro, begins, counts, width, stride=1):
     atsc_rolling_delta_windows over the records"""
     return _rolling_result(lambda m: _query_image(_ROLLING_DELTA, ctx, bro, begins, counts, width, stride, m), counts, width,
                            stride, WINDOW_DELTA)
+
+
+def rolling_runs_data_windows(ctx, bro, begins, counts, width, op, limit, stride=1):
+    """-> (records, off): the runs' record under the condition x OP limit of the window of `width` samples at every
+    `stride`-th position of ranges of decompress_data(ctx, bro), as Context.rolling_runs_windows_host gives them:
+    atsc_bro_open, then atsc_rolling_runs_windows over the records"""
+    return _rolling_result(lambda m: _query_image(_ROLLING_RUNS, ctx, bro, begins, counts, width, stride, m, op, limit),
+                           counts, width, stride, WINDOW_RUNS)
 
 
 def rolling_moments_data_windows(ctx, bro, begins, counts, width, stride=1):

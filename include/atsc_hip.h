@@ -859,6 +859,52 @@ int atsc_rolling_delta_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body
                                const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
                                atsc_window_delta *out);
 
+/* Windowed rolling runs: the runs' record (atsc_window_runs, 80 bytes) of the sliding window at every position of ranges
+ * of the decoded stream under the condition x OP limit: an alerting rule's `for: 5m` (inside == samples) evaluated at
+ * every step, how long the series has been over the limit (tail), the excursions of the trailing hour (runs), the time a
+ * signal spent in a state (inside) -- without listing one window per position for atsc_runs_windows.
+ *   Ranges     Ranges, width, stride, the number and the order of the records (atsc_rolling_outputs), the limits
+ *              1 <= width <= ATSC_ROLLING_MAX_WIDTH and 2^32 - 2 records, validation, the errors (ATSC_E_INVALID with
+ *              nothing written and before any GPU work; ATSC_E_FORMAT or the plan's status word for a malformed payload
+ *              inside a position's window), pieces and ATSC_E_CAPACITY are atsc_rolling_windows'.  The messages name
+ *              rolling_runs_windows.  In addition an unknown op or a NaN limit is ATSC_E_INVALID, nothing written and
+ *              before any GPU work: atsc_runs_windows' rule.
+ *   Condition  atsc_runs_windows', unchanged: op is one of the ATSC_RUNS_* operators and limit the same for every position
+ *              of a call; a sample is inside iff it is not NaN and x OP limit holds.  NaN is never inside, under
+ *              ATSC_RUNS_NE too; -0.0 equals +0.0; +-Inf samples and limits compare as values.
+ *   samples, inside, runs, longest, longest_at, first_at, last_at, head, tail   For the position whose window is
+ *              [lo, lo + w) they are atsc_runs_windows' of (begin, count) = (lo, w), exactly: samples = w, offsets count
+ *              from lo, of equal longest runs the earliest wins, and ATSC_RUNS_NONE stands where that call has it.  The
+ *              merge rule of the nine integers is associative, so they are exact in any order.
+ *   excess     in the rolling's order, over sample slots.
+ *              term(j) = fabs(x[j] - limit) where x[j] is inside (the subtract one correctly rounded operation), else
+ *              -0.0.
+ *              T(a, 0) = term(a); T(a, l) = T(a, l - 1) + T(a + 2^(l-1), l - 1), for a a multiple of 2^l in the stream
+ *              index.  The window's chunks are the rolling's, left to right: pos = lo; while pos < lo + w, take the
+ *              largest l with pos % 2^l == 0 and pos + 2^l <= lo + w, emit (pos, l), pos += 2^l.
+ *              excess = ((T(c_1) + T(c_2)) + T(c_3)) + ..., every operation one correctly rounded f64 add, never fused;
+ *              +0.0 where inside == 0; where IEEE gives NaN (Inf - Inf only) any NaN conforms.
+ *              With u = 2^-53 and L = max(1, ceil(log2 w)), for finite data |excess - exact| <= (3 L + 1) u exact (one
+ *              rounding for the subtract, then the rolling's 3 L).  On integer samples and an integer limit whose sums
+ *              stay below 2^53 excess is exact, and then equals atsc_runs_windows' bit for bit; otherwise it MAY DIFFER
+ *              from atsc_runs_windows' excess of the same window in its last bits, each within its own stated bound.
+ * A position's 80 bytes depend on the stream's samples, (lo, w) and the condition only: not on the range the window came
+ * from, the stride, the other ranges, the budget, the piece boundaries, the framing, the host, the device or the stream
+ * call.  atsc_runs_merge applies unchanged to the records of adjacent disjoint positions, which needs stride == width.
+ * The chunk partials are 32 bytes, the rolling's size (the nine integers without the chunk's length, packed, and
+ * excess), at most 8 bytes a sample beside the 8 of the decoded sample, inside the budget of
+ * atsc_ctx_set_aggregate_scratch as the rolling's are; the default budget holds every width.
+ * begin / count are HOST arrays; d_body and d_out are device memory (d_out 8-byte aligned, 80 bytes per record).  Enqueued
+ * on `stream`, not synchronised.  The call keeps its tables and scratch in the rolling's place of the plan: it and the
+ * other rolling calls on the same plan wait (host side) for each other. */
+int atsc_rolling_runs_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                  const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride, int op,
+                                  double limit, atsc_window_runs *d_out, void *stream);
+/* Host bytes in, host records out, synchronous, as atsc_rolling_windows is; computes the device call's bits. */
+int atsc_rolling_runs_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                              const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride, int op,
+                              double limit, atsc_window_runs *out);
+
 /* Windowed rolling moments: the moments' record (atsc_window_moments, 48 bytes) of the sliding window at every position
  * of ranges of the decoded stream: `stddev_over_time(x[5m])`, `stdvar_over_time`, `deriv(x[5m])` and `predict_linear`
  * evaluated at every step, a z-score against a trailing baseline, a moving least-squares slope -- without listing one
@@ -1320,6 +1366,9 @@ int atsc_stream_rolling_windows(atsc_stream *s, uint64_t n_windows, const uint64
 /* atsc_rolling_delta_windows over the stream's frames */
 int atsc_stream_rolling_delta_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                       uint64_t width, uint64_t stride, atsc_window_delta *out);
+/* atsc_rolling_runs_windows over the stream's frames */
+int atsc_stream_rolling_runs_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                     uint64_t width, uint64_t stride, int op, double limit, atsc_window_runs *out);
 /* atsc_rolling_moments_windows over the stream's frames */
 int atsc_stream_rolling_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                         uint64_t width, uint64_t stride, atsc_window_moments *out);
