@@ -20,6 +20,7 @@ from .stream import rolling_data_windows, rolling_delta_data_windows, rolling_mo
 from .stream import rolling_pair_data_windows, rolling_runs_data_windows  # noqa: F401
 from .capi import ROLLING_QUANTILE_MAX_WIDTH  # noqa: F401
 from .stream import rolling_quantile_data_windows  # noqa: F401
+from .stream import rolling_histogram_data_windows  # noqa: F401
 from .capi import ACROSS_MAX_STREAMS  # noqa: F401
 from .engine import ACROSS_RECORD, across_offsets, across_outputs  # noqa: F401
 from .stream import across_data_windows, across_extremes_data_windows, across_quantile_data_windows  # noqa: F401

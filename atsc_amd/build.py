@@ -10,14 +10,14 @@ CSRC = os.path.join(HERE, "csrc")
 VARIANT = os.environ.get("ATSC_BUILD_VARIANT", "")
 LIB = os.path.join(HERE, "libatsc_hip%s.so" % ("_" + VARIANT if VARIANT else ""))
 SOURCES = ["atsc_kernels.hip", "atsc_large.hip", "atsc_decode.hip", "atsc_aggregate.hip", "atsc_quantile.hip",
-           "atsc_histogram.hip", "atsc_moments.hip", "atsc_pair.hip", "atsc_delta.hip", "atsc_runs.hip", "atsc_extremes.hip", "atsc_values.hip", "atsc_select.hip", "atsc_rolling.hip", "atsc_rolling_delta.hip", "atsc_rolling_moments.hip", "atsc_rolling_pair.hip", "atsc_rolling_quantile.hip", "atsc_rolling_runs.hip", "atsc_across.hip", "atsc_across_quantile.hip", "atsc_across_extremes.hip", "atsc_across_moments.hip", "atsc_host.cpp", "atsc_windows.cpp", "atsc_stream.cpp", "atsc_vsri.cpp"]
+           "atsc_histogram.hip", "atsc_moments.hip", "atsc_pair.hip", "atsc_delta.hip", "atsc_runs.hip", "atsc_extremes.hip", "atsc_values.hip", "atsc_select.hip", "atsc_rolling.hip", "atsc_rolling_delta.hip", "atsc_rolling_moments.hip", "atsc_rolling_pair.hip", "atsc_rolling_quantile.hip", "atsc_rolling_histogram.hip", "atsc_rolling_runs.hip", "atsc_across.hip", "atsc_across_quantile.hip", "atsc_across_extremes.hip", "atsc_across_moments.hip", "atsc_host.cpp", "atsc_windows.cpp", "atsc_stream.cpp", "atsc_vsri.cpp"]
 CLI = os.path.join(HERE, "bin", "atsc")
 CLI_SRC = "atsc_cli.cpp"
 CLI2 = os.path.join(HERE, "bin", "csv-compressor")
 CLI2_SRC = "csv_compressor_cli.cpp"
 CLI_HEADER = "atsc_cli_buckets.h"  # what the two front ends share; no library source includes it
 DEPS = SOURCES + ["atsc_device.h", "atsc_internal.h", "atsc_host_private.h", "atsc_large_cols.h", "atsc_large_fast.h",
-                  "atsc_tile_reduce.h", "atsc_moment_node.h", "atsc_rolling_node.h", "atsc_moment_rule.h", "atsc_quantile_rule.h", os.path.join("..", "..", "include", "atsc_hip.h")]
+                  "atsc_tile_reduce.h", "atsc_moment_node.h", "atsc_rolling_node.h", "atsc_moment_rule.h", "atsc_quantile_rule.h", "atsc_hist_bins.h", os.path.join("..", "..", "include", "atsc_hip.h")]
 # -ffp-contract=off: the f64 spline / rounding arithmetic must evaluate exactly as written
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -40,7 +40,7 @@ def stale():
 
 OBJDIR = os.path.join(HERE, "build" + ("_" + VARIANT if VARIANT else ""))
 HEADERS = ["atsc_device.h", "atsc_internal.h", "atsc_host_private.h", "atsc_large_cols.h", "atsc_large_fast.h",
-           "atsc_tile_reduce.h", "atsc_moment_node.h", "atsc_rolling_node.h", "atsc_moment_rule.h", "atsc_quantile_rule.h", os.path.join("..", "..", "include", "atsc_hip.h")]
+           "atsc_tile_reduce.h", "atsc_moment_node.h", "atsc_rolling_node.h", "atsc_moment_rule.h", "atsc_quantile_rule.h", "atsc_hist_bins.h", os.path.join("..", "..", "include", "atsc_hip.h")]
 CFLAGS = [f for f in FLAGS if f != "-shared"] + os.environ.get("ATSC_BUILD_DEFS", "").split()
 
 

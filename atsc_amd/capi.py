@@ -152,6 +152,10 @@ SIGNATURES = {
                                                     _f64p, C.c_int, _vp, _vp]),
     "atsc_rolling_quantile_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint64,
                                                 C.c_uint64, C.c_uint32, _f64p, C.c_int, _vp]),
+    "atsc_rolling_histogram_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                     _f64p, C.c_int, _vp, _vp]),
+    "atsc_rolling_histogram_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, C.c_uint64,
+                                                 C.c_uint64, C.c_uint32, _f64p, C.c_int, _vp]),
     "atsc_rolling_pair_windows_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp, _vp]),
     "atsc_rolling_pair_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p,
                                             C.c_uint64, C.c_uint64, _vp]),
@@ -204,6 +208,8 @@ SIGNATURES = {
     "atsc_stream_rolling_moments_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp]),
     "atsc_stream_rolling_quantile_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, C.c_uint32,
                                                        _f64p, C.c_int, _vp]),
+    "atsc_stream_rolling_histogram_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                        _f64p, C.c_int, _vp]),
     "atsc_stream_rolling_pair_windows": (C.c_int, [_vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint64, _vp]),
     "atsc_stream_across_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, _vp]),
     "atsc_stream_across_quantile_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint32,

@@ -5,7 +5,8 @@
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
 //        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments] [--rolling-runs OP:LIMIT]
-//        [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]] [--rolling-pair OTHER.bro]]
+//        [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]] [--rolling-pair OTHER.bro]
+//        [--rolling-histogram E,E,..|LO:HI:N]]
 //        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]
 //        [--across-extremes K] [--across-moments]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
@@ -98,6 +99,9 @@ void usage()
             "                                 --quantiles), as the last columns: one q<Q> per level as typed; NaN where the\n"
             "                                 window holds no sample\n"
             "      --rolling-quantile-method <M>  with --rolling-quantiles: linear (default), lower, higher or nearest\n"
+            "      --rolling-histogram <SPEC> with --rolling: also every position's counts over the value bins of the edges\n"
+            "                                 (SPEC and --histogram-closed as --histogram), as the last columns:\n"
+            "                                 h0 .. h<n_edges>,hnan; a row's counters sum to W\n"
             "      --rolling-pair <OTHER.bro> with --rolling: also every position's pair moments against the samples of\n"
             "                                 OTHER.bro at the same indices (x: this file, y: OTHER), as the last columns:\n"
             "                                 pair_count,covariance,correlation,slope,intercept (as --pair; the four empty\n"
@@ -213,13 +217,15 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
             rc = atsc_bro_open(bro, len, nullptr, nullptr);
             std::vector<atsc_window_pair> pairs;
             std::vector<atsc_window_runs> runs;
-            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, deltas, fits, moments, levels, runs, &pairs);
+            std::vector<uint64_t> hist;
+            if (!rc) rc = rolling_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, deltas, fits, moments, levels, runs, &pairs, &hist);
             atsc_free(bro);
             if (rc) return rc;
             const uint64_t stride = a.q.rolling_stride;  // a position's first sample, counted from the window's begin
             return rolling_write(with_ext(path, "roll.csv"), "offset", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments, a.q.rolling_level_names, levels,
                                  a.q.rolling_runs, runs, a.q.rolling_pair.empty() ? nullptr : &pairs,
-                                 [stride](uint64_t j) { return std::to_string(j * stride); })
+                                 [stride](uint64_t j) { return std::to_string(j * stride); }, a.q.rolling_hist ? &hist : nullptr,
+                                 a.q.rolling_edges.size() + 2)
                        ? ATSC_OK
                        : ATSC_E_IO;
         }

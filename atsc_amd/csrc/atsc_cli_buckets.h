@@ -3,7 +3,7 @@
 // usage errors, the calls over the buckets and the columns of the .agg.csv; `--rolling W[:S]`, the sliding window's
 // records at every position of a window (with `--rolling-deltas`, its deltas beside them, with `--rolling-moments`, its
 // moments, with `--rolling-quantiles Q,Q,..`, its levels, with `--rolling-pair OTHER.bro` (atsc only), its pair moments
-// against another file); `--where OP:LIMIT`, the selected samples
+// against another file, with `--rolling-histogram E,E,..|LO:HI:N`, its value-bin counts); `--where OP:LIMIT`, the selected samples
 // of the window itself into a .sel.csv; and `--across A.bro,B.bro,..` (atsc only), the across records of the window over
 // several files into an .across.csv (the end of this file).  The two differ in the row's first cell,
 // in how a failure is reported and in how a position inside a bucket is written: the three run positions, which the
@@ -83,6 +83,8 @@ struct BucketOptions {
     double rolling_runs_limit = 0.0;
     std::vector<double> rolling_levels;  // --rolling-quantiles Q,Q,..: one column per level behind those
     std::vector<std::string> rolling_level_names;
+    std::vector<double> rolling_edges;  // --rolling-histogram E,E,..|LO:HI:N: h0 .. h<n_edges>,hnan as the last columns (closed: --histogram-closed)
+    bool rolling_hist = false;
     std::string rolling_pair;  // --rolling-pair OTHER.bro (where pair_allowed): pair_count,covariance,correlation,slope,intercept as the last columns
     int rolling_method = ATSC_QUANTILE_LINEAR;  // --rolling-quantile-method
     bool have_rolling_method = false;
@@ -303,6 +305,18 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             fprintf(stderr, "error: invalid value for '--rolling-quantiles': %zu levels, at most 64\n", o.rolling_levels.size());
             return 2;
         }
+    } else if (value("--rolling-histogram")) {
+        const int bad = parse_histogram(v, o.rolling_edges);
+        if (bad == 1) {
+            fprintf(stderr, "error: invalid value '%s' for '--rolling-histogram': expected ascending edges E,E,.. or LO:HI:N\n",
+                    v.c_str());
+            return 2;
+        }
+        if (bad == 2) {
+            fprintf(stderr, "error: invalid value for '--rolling-histogram': more than %d edges\n", (int)ATSC_HIST_MAX_EDGES);
+            return 2;
+        }
+        o.rolling_hist = true;
     } else if (value("--rolling-quantile-method")) {
         if (!parse_method(v, o.rolling_method)) {
             fprintf(stderr, "error: invalid value '%s' for '--rolling-quantile-method': linear, lower, higher or nearest\n",
@@ -387,7 +401,7 @@ bool bucket_options_complete(const BucketOptions &o, const char *bucketing, bool
     } T[] = {{!o.levels.empty(), given, "--quantiles", bucketing},
              {o.have_method, !o.levels.empty(), "--quantile-method", "--quantiles"},
              {o.have_hist, given, "--histogram", bucketing},
-             {o.have_closed, o.have_hist, "--histogram-closed", "--histogram"},
+             {o.have_closed, o.have_hist || o.rolling_hist, "--histogram-closed", "--histogram"},
              {o.moments, given, "--moments", bucketing},
              {o.deltas, given, "--deltas", bucketing},
              {o.have_runs, given, "--runs", bucketing},
@@ -419,7 +433,7 @@ bool where_option_complete(const BucketOptions &o, const char *window, bool wind
 }
 
 // --rolling goes with the option that names the window and without the one that cuts buckets, as --where does, and
-// not with --where; --rolling-deltas, --rolling-moments, --rolling-runs, --rolling-quantiles and --rolling-pair go with --rolling, --rolling-quantile-method
+// not with --where; --rolling-deltas, --rolling-moments, --rolling-runs, --rolling-quantiles, --rolling-histogram and --rolling-pair go with --rolling, --rolling-quantile-method
 // with --rolling-quantiles, and --rolling-quantiles with a W of at most ATSC_ROLLING_QUANTILE_MAX_WIDTH.  false: a usage
 // error, reported on stderr.
 bool rolling_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
@@ -434,7 +448,9 @@ bool rolling_option_complete(const BucketOptions &o, const char *window, bool wi
         if (o.rolling_runs) fprintf(stderr, "error: '--rolling-runs' needs '--rolling'\n");
         if (!o.rolling_levels.empty()) fprintf(stderr, "error: '--rolling-quantiles' needs '--rolling'\n");
         if (!o.rolling_pair.empty()) fprintf(stderr, "error: '--rolling-pair' needs '--rolling'\n");
-        return !o.rolling_deltas && !o.rolling_moments && !o.rolling_runs && o.rolling_levels.empty() && o.rolling_pair.empty();
+        if (o.rolling_hist) fprintf(stderr, "error: '--rolling-histogram' needs '--rolling'\n");
+        return !o.rolling_deltas && !o.rolling_moments && !o.rolling_runs && o.rolling_levels.empty() && o.rolling_pair.empty() &&
+               !o.rolling_hist;
     }
     if (!o.rolling_levels.empty() && o.rolling > ATSC_ROLLING_QUANTILE_MAX_WIDTH) {
         fprintf(stderr, "error: '--rolling-quantiles' needs a '--rolling' W in 1..=%llu\n",
@@ -698,11 +714,13 @@ bool where_write(const std::string &path, const char *first, const std::vector<a
 // same positions' rolling moments; levels: with --rolling-quantiles, the same positions' rows of levels; runs: with
 // --rolling-runs OP:LIMIT, the same positions' rolling runs under that condition; pairs: with
 // --rolling-pair OTHER.bro, the same positions' rolling pair moments against that file's samples (sample i of it goes
-// with sample i of this one; a file that ends before a window fails as --pair's does)
+// with sample i of this one; a file that ends before a window fails as --pair's does); hist: with
+// --rolling-histogram, the same positions' rows of o.rolling_edges.size() + 2 counters (--histogram-closed's side)
 int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
                   std::vector<atsc_window_rolling> &rows, std::vector<atsc_window_delta> &deltas,
                   std::vector<atsc_window_delta_fit> &fits, std::vector<atsc_window_moments> &moments,
-                  std::vector<double> &levels, std::vector<atsc_window_runs> &runs, std::vector<atsc_window_pair> *pairs = nullptr)
+                  std::vector<double> &levels, std::vector<atsc_window_runs> &runs, std::vector<atsc_window_pair> *pairs = nullptr,
+                  std::vector<uint64_t> *hist = nullptr)
 {
     rows.assign(atsc_rolling_outputs(count, o.rolling, o.rolling_stride), atsc_window_rolling{});
     atsc_window_rolling none;
@@ -748,6 +766,13 @@ int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketO
                                            o.rolling_stride, pairs->empty() ? &none_p : pairs->data());
         atsc_free(other);
     }
+    if (!rc && hist && o.rolling_hist) {
+        hist->assign(rows.size() * (o.rolling_edges.size() + 2), 0);
+        uint64_t none_h;
+        rc = atsc_rolling_histogram_windows(ctx, bro + 9, len - 9, 1, 1, &begin, &count, o.rolling, o.rolling_stride,
+                                            (uint32_t)o.rolling_edges.size(), o.rolling_edges.data(), o.closed,
+                                            hist->empty() ? &none_h : hist->data());
+    }
     return rc;
 }
 
@@ -764,13 +789,16 @@ int rolling_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketO
 // record has ATSC_RUNS_NONE, as --runs' cells are.
 // pairs (--rolling-pair; null without it): as the last columns pair_count,covariance,correlation,slope,intercept, --pair's
 // columns, from the position's record and what atsc_pair_fit reads off it; the four cells empty where pair_count is 0.
+// hist (--rolling-histogram; null without it): behind all of those h0 .. h<n_edges>,hnan, --histogram's columns, from the
+// position's row of n_hist = n_edges + 2 counters.
 // false: the file could not be written.
 template <class Place>
 bool rolling_write(const std::string &path, const char *first, const std::vector<atsc_window_rolling> &rows, bool with_deltas,
                    const std::vector<atsc_window_delta> &deltas, const std::vector<atsc_window_delta_fit> &fits,
                    bool with_moments, const std::vector<atsc_window_moments> &moments, const std::vector<std::string> &names,
                    const std::vector<double> &levels, bool with_runs, const std::vector<atsc_window_runs> &runs,
-                   const std::vector<atsc_window_pair> *pairs, Place place)
+                   const std::vector<atsc_window_pair> *pairs, Place place, const std::vector<uint64_t> *hist = nullptr,
+                   size_t n_hist = 0)
 {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return false;
@@ -780,6 +808,10 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
     for (const std::string &n : names) fprintf(f, ",q%s", n.c_str());
     if (with_runs) fprintf(f, ",samples,inside,runs,longest,longest_at,first_at,last_at,head,tail,excess");
     if (pairs) fprintf(f, ",pair_count,covariance,correlation,slope,intercept");
+    if (hist) {
+        for (size_t k = 0; k + 1 < n_hist; ++k) fprintf(f, ",h%zu", k);
+        fprintf(f, ",hnan");
+    }
     fprintf(f, "\n");
     for (size_t j = 0; j < rows.size(); ++j) {
         const atsc_window_rolling &r = rows[j];
@@ -816,6 +848,8 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
             else fprintf(f, ",%llu,%s,%s,%s,%s", (unsigned long long)p.count, debug_f64(pf.covariance).c_str(),
                          debug_f64(pf.correlation).c_str(), debug_f64(pf.slope).c_str(), debug_f64(pf.intercept).c_str());
         }
+        if (hist)
+            for (size_t k = 0; k < n_hist; ++k) fprintf(f, ",%llu", (unsigned long long)(*hist)[j * n_hist + k]);
         fprintf(f, "\n");
     }
     return fclose(f) == 0;

@@ -377,6 +377,19 @@ static inline uint32_t rq_span_keys(uint64_t w)
     return P;
 }
 
+// windowed rolling histograms (atsc_rolling_histogram_windows_dev, atsc_rolling_histogram.hip): the rolling's pieces and
+// tasks without a pyramid.  One wavefront counts a task's first window and slides the row over the task's other
+// positions.  B, the positions a task holds, by the width and the stride alone: eight windows' worth of positions, so
+// that the first window's count is at most a sixteenth of the slide's 2 (B - 1) stride sample visits, at least
+// RH_TASK_MIN (short windows still fill a task) and at most RH_TASK_MAX (a long task is one wavefront's serial work).
+constexpr uint64_t RH_TASK_MIN = 64, RH_TASK_MAX = 2048;
+static inline uint64_t rh_task_positions(uint64_t w, uint64_t s)
+{
+    const uint64_t per = w / s + (w % s ? 1 : 0);  // ceil(w / s); w <= 2^20
+    const uint64_t b = 8 * per;
+    return b < RH_TASK_MIN ? RH_TASK_MIN : b > RH_TASK_MAX ? RH_TASK_MAX : b;
+}
+
 // windowed across (atsc_across_windows_dev, atsc_across.hip): every stream of a call decoded into a scratch region of
 // its own, the same sample at the same slot of every region, then one record per position from its slot of each.  A
 // task is a DevRollTask: n positions of one range inside one piece, the first at sample lo of the streams.

@@ -1,5 +1,5 @@
 // atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms,
-// rolling windows, rolling deltas, rolling runs and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
+// rolling windows, rolling deltas, rolling runs, rolling quantiles, rolling histograms and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
 // and count, min, max, sum, quantiles, extremes and moments across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
@@ -131,6 +131,10 @@ __attribute__((weak)) hipError_t launch_rru_positions(const DevRollTask *tasks, 
 __attribute__((weak)) hipError_t launch_rq_span(const DevRollTask *tasks, uint32_t n, uint32_t P, uint64_t B,
                                                 const double *scratch, uint64_t a0, uint32_t w, uint64_t stride,
                                                 const double *q, uint32_t n_q, int method, double *out, hipStream_t s);
+// the windowed rolling histograms' sliding kernel (atsc_rolling_histogram.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_rh_slide(const DevRollTask *tasks, uint32_t n, const double *scratch, uint64_t a0,
+                                                 uint32_t w, uint64_t stride, const double *edges, uint32_t n_edges,
+                                                 int closed, uint64_t *out, hipStream_t s);
 // the windowed across' position kernel (atsc_across.hip; weak for the same reason)
 __attribute__((weak)) hipError_t launch_across_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                          const uint64_t *reg, uint32_t n_streams, uint64_t a0,
@@ -406,7 +410,8 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_ROLLING = DECODE_CALLER("rolling"), BY_ROLLING_DELTA = DECODE_CALLER("rolling delta"),
                           BY_ROLLING_MOMENTS = DECODE_CALLER("rolling moments"), BY_ROLLING_PAIR = DECODE_CALLER("rolling pair"),
                           BY_ROLLING_RUNS = DECODE_CALLER("rolling runs"),
-                          BY_ROLLING_QUANTILE = DECODE_CALLER("rolling quantile"), BY_ACROSS = DECODE_CALLER("across"),
+                          BY_ROLLING_QUANTILE = DECODE_CALLER("rolling quantile"),
+                          BY_ROLLING_HISTOGRAM = DECODE_CALLER("rolling histogram"), BY_ACROSS = DECODE_CALLER("across"),
                           BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile"),
                           BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes"),
                           BY_ACROSS_MOMENTS = DECODE_CALLER("across moments");
@@ -2076,17 +2081,18 @@ extern "C" int atsc_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_
 // Covering intervals closer than this share a span of pieces, as the aggregates' AGG_GAP_TILES tiles
 static const uint64_t HST_GAP = 64ull * AGG_TILE;
 
-// ctx may be null: then no message is kept
-static int histogram_check_edges(atsc_ctx *ctx, uint32_t n_edges, const double *edges, int closed)
+// ctx may be null: then no message is kept; `call` names the caller in the message
+static int histogram_check_edges(atsc_ctx *ctx, uint32_t n_edges, const double *edges, int closed,
+                                 const char *call = "histogram_windows")
 {
-    if (!edges) return fail(ctx, ATSC_E_INVALID, "histogram_windows: null argument");
-    if (n_edges == 0 || n_edges > HST_MAX_EDGES) return fail(ctx, ATSC_E_INVALID, "histogram_windows: n_edges outside [1, 1024]");
+    if (!edges) return fail_in(ctx, ATSC_E_INVALID, call, "null argument");
+    if (n_edges == 0 || n_edges > HST_MAX_EDGES) return fail_in(ctx, ATSC_E_INVALID, call, "n_edges outside [1, 1024]");
     for (uint32_t j = 0; j < n_edges; ++j)
-        if (edges[j] != edges[j]) return fail(ctx, ATSC_E_INVALID, "histogram_windows: an edge is NaN");
+        if (edges[j] != edges[j]) return fail_in(ctx, ATSC_E_INVALID, call, "an edge is NaN");
     for (uint32_t j = 1; j < n_edges; ++j)
-        if (!(edges[j - 1] < edges[j])) return fail(ctx, ATSC_E_INVALID, "histogram_windows: edges are not strictly ascending");
+        if (!(edges[j - 1] < edges[j])) return fail_in(ctx, ATSC_E_INVALID, call, "edges are not strictly ascending");
     if (closed != ATSC_HIST_LEFT_CLOSED && closed != ATSC_HIST_RIGHT_CLOSED)
-        return fail(ctx, ATSC_E_INVALID, "histogram_windows: unknown closed");
+        return fail_in(ctx, ATSC_E_INVALID, call, "unknown closed");
     return ATSC_OK;
 }
 
@@ -3059,6 +3065,183 @@ extern "C" int atsc_rolling_quantile_windows(atsc_ctx *ctx, const uint8_t *body,
 }
 
 // ------------------------------------------------------------------------------------------
+// windowed rolling histograms: the value-bin counts of the window at every position of sample ranges
+// (atsc_rolling_histogram.hip)
+// ------------------------------------------------------------------------------------------
+// rolling_check, then the histograms' edges, then the limit that keeps a counter's index in 32 bits
+static int rolling_histogram_check(atsc_ctx *ctx, const char *call, uint64_t n, const uint64_t *count, uint64_t width,
+                                   uint64_t stride, uint32_t n_edges, const double *edges, int closed, uint64_t *total)
+{
+    uint64_t sum = 0;
+    int rc = rolling_check(ctx, call, n, count, width, stride, &sum);
+    if (!rc) rc = histogram_check_edges(ctx, n_edges, edges, closed, call);
+    if (rc) return rc;
+    if (sum * ((uint64_t)n_edges + 2) > 0xfffffffeull)  // (sum < 2^32 and n_edges + 2 <= 1026: no overflow)
+        return fail_in(ctx, ATSC_E_INVALID, call, "positions x (n_edges + 2) is not below 2^32 - 1 counters");
+    if (total) *total = sum;
+    return ATSC_OK;
+}
+
+// The device call.  Covering intervals, pieces that overlap by width - 1 and the rule "the first piece that holds a
+// position's window computes it" are rolling_quantile_dev's: there is no pyramid, so a piece takes the whole of
+// piece_samples' length and lies in the scratch from its first sample on, and the scratch holds decoded samples only.  A
+// width above a piece is ATSC_E_CAPACITY, as in rolling_dev.  Per range and per piece, the run of positions the piece
+// computes is cut into tasks of B = rh_task_positions(width, stride) positions.  One upload (decode tasks, edges,
+// tasks); then per piece the decode and the one launch.
+static int rolling_histogram_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                 const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                 uint32_t n_edges, const double *edges, int closed, uint64_t *d_out, void *stream, uint64_t org)
+{
+    static const char *const CALL = "rolling_histogram_windows";
+    if (!ctx || !dp || (n_windows && (!d_body || !begin || !count))) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    uint64_t total = 0;
+    int rc = rolling_histogram_check(ctx, CALL, n_windows, count, width, stride, n_edges, edges, closed, &total);
+    if (rc) return rc;
+    if (total && !d_out) return fail_in(ctx, ATSC_E_INVALID, CALL, "null argument");
+    rc = check_windows(ctx, CALL, dp, d_out, "d_out", n_windows, begin, count, ~0ull);
+    if (rc || total == 0) return rc;
+    if (!launch_decompress_window || !launch_window_gather || !launch_rh_slide)
+        return fail_in(ctx, ATSC_E_UNSUPPORTED, CALL, "no rolling histogram kernels");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint64_t W = n_windows, w = width;
+    std::vector<uint64_t> m(W);
+    std::vector<Span> cov;
+    for (uint64_t i = 0; i < W; ++i) {
+        m[i] = atsc_rolling_outputs(count[i], w, stride);
+        if (m[i]) cov.emplace_back(org + begin[i], org + begin[i] + (m[i] - 1) * stride + w);
+    }
+    merge_spans(cov);
+    uint64_t spill;
+    const uint64_t Lp = piece_samples(ctx, dp, org, cov, 1, &spill);
+    if (w > Lp) {
+        char msg[192];
+        snprintf(msg, sizeof msg,
+                 "%s: a window of %llu samples does not fit one scratch piece; an aggregate scratch budget of "
+                 "%llu bytes would hold it", CALL, (unsigned long long)w, (unsigned long long)((w + spill) * sizeof(double)));
+        return fail(ctx, ATSC_E_CAPACITY, msg);
+    }
+    // pieces: samples [first, second) of the stream, ascending; scratch[0] is sample first
+    std::vector<Span> pcs;
+    uint64_t region = 0;
+    for (size_t a = 0; a < cov.size();) {
+        const uint64_t s0 = cov[a].first;
+        uint64_t s1 = cov[a].second;
+        size_t z = a + 1;
+        while (z < cov.size() && cov[z].first < s1 + HST_GAP) s1 = cov[z++].second;
+        for (uint64_t p = s0;;) {
+            const uint64_t e = std::min(s1, p + Lp);
+            pcs.emplace_back(p, e);
+            region = std::max(region, e - p);
+            if (e == s1) break;
+            p = e - (w - 1);
+        }
+        a = z;
+    }
+    region += region & 1;  // an even number of doubles, as the spill slots behind it expect
+    const size_t P = pcs.size();
+    // tasks, by piece: per range the runs of positions whose windows end inside the piece and not inside an earlier one
+    const uint64_t B = rh_task_positions(w, stride);
+    std::vector<Placed<DevRollTask>> tk;
+    uint64_t rec = 0;
+    for (uint64_t i = 0; i < W; ++i) {
+        if (!m[i]) continue;
+        const uint64_t b = org + begin[i];
+        size_t p = (size_t)(std::lower_bound(pcs.begin(), pcs.end(), b + w, [](const Span &x, uint64_t v) { return x.second < v; }) -
+                            pcs.begin());
+        for (uint64_t j = 0; j < m[i];) {
+            const uint64_t lo = b + j * stride;
+            while (p < P && pcs[p].second < lo + w) ++p;  // (a stride longer than a piece skips pieces)
+            if (p >= P || pcs[p].first > lo)
+                return fail_in(ctx, ATSC_E_INVALID, CALL, "internal error (position outside the pieces)");
+            const uint64_t je = std::min(m[i], (pcs[p].second - w - b) / stride + 1);  // positions whose windows end in the piece
+            for (; j < je; j += B)
+                tk.push_back({(uint32_t)p, DevRollTask{b + j * stride, rec + j, (uint32_t)std::min<uint64_t>(B, je - j), 0}});
+            j = je;
+        }
+        rec += m[i];
+    }
+    std::vector<DevRollTask> tasks;
+    std::vector<size_t> at;
+    group_tasks(tk, P, tasks, at);
+    std::vector<PieceDecode> pdec;
+    DecodeTasks D;
+    rc = emit_pieces_decode(ctx, CALL, dp, org, cov, pcs, 1, region, D, pdec);
+    if (rc) return rc;
+    QueryRes &R = dp->res[Q_ROLLING];
+    HIPCHK(ctx, R.wait());
+    Upload up;
+    D.place(up);
+    const size_t off_edges = up.add(edges, n_edges * sizeof(double)), off_tasks = up.add(tasks);
+    rc = stage_upload(ctx, R, up, region + (uint64_t)MAX_FRAME * D.spills_used, s);
+    if (rc) return rc;
+    unsigned char *d = R.d;
+    double *scr = R.scratch;
+    const double *d_edges = (const double *)(d + off_edges);
+    const DevRollTask *d_tasks = (const DevRollTask *)(d + off_tasks);
+    for (size_t p = 0; p < P; ++p) {
+        rc = launch_piece_decode(ctx, dp, d_body, d, D, pdec[p], scr, scr, scr, s, BY_ROLLING_HISTOGRAM);
+        if (rc) return rc;
+        LAUNCHCHK(ctx, "launch k_rh_slide",
+                  launch_rh_slide(d_tasks + at[p], (uint32_t)(at[p + 1] - at[p]), scr, pcs[p].first, (uint32_t)w, stride, d_edges,
+                                  n_edges, closed, d_out, s));
+    }
+    HIPCHK(ctx, R.record(s));
+    return ATSC_OK;
+}
+
+// The rolling histograms' descriptor (see AggQuery): RollQuantileQuery's shape with the edges and the closed side; a
+// position's row is n_edges + 2 counters.
+struct RollHistogramQuery {
+    static constexpr int INPUTS = 1;
+    static constexpr const char *CALL = "rolling_histogram_windows";
+    uint64_t width, stride;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    uint32_t n_edges;
+    const double *edges;
+    int closed;
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_rolling_outputs(count[i], width, stride);
+        return total * ((size_t)n_edges + 2) * sizeof(uint64_t);
+    }
+    int check(atsc_ctx *ctx) const
+    {
+        return rolling_histogram_check(ctx, CALL, count ? n_ranges : 0, count, width, stride, n_edges, edges, closed, nullptr);
+    }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no row
+    int dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows, const uint64_t *begin,
+            const uint64_t *cnt, void *d_res, void *stream, uint64_t org) const
+    {
+        return rolling_histogram_dev(ctx, dp, d_body, n_windows, begin, cnt, width, stride, n_edges, edges, closed,
+                                     (uint64_t *)d_res, stream, org);
+    }
+};
+
+extern "C" int atsc_rolling_histogram_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                                  const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                                  uint32_t n_edges, const double *edges, int closed, uint64_t *d_out,
+                                                  void *stream)
+{
+    ATSC_API_BEGIN
+    return RollHistogramQuery{width, stride, count, n_windows, n_edges, edges, closed}.dev(ctx, dp, d_body, n_windows, begin, count,
+                                                                                          d_out, stream, 0);
+    ATSC_API_END
+}
+
+extern "C" int atsc_rolling_histogram_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count,
+                                              uint64_t n_windows, const uint64_t *begin, const uint64_t *count, uint64_t width,
+                                              uint64_t stride, uint32_t n_edges, const double *edges, int closed, uint64_t *out)
+{
+    ATSC_API_BEGIN
+    return query_host(ctx, body, body_len, has_count, n_windows, begin, count, out,
+                      RollHistogramQuery{width, stride, count, n_windows, n_edges, edges, closed});
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
 // windowed across: count / min / max / sum over N streams at every position of sample ranges (atsc_across.hip)
 // ------------------------------------------------------------------------------------------
 extern "C" uint64_t atsc_across_outputs(uint64_t count, uint64_t stride)
@@ -3714,6 +3897,16 @@ extern "C" int atsc_stream_rolling_quantile_windows(atsc_stream *s, uint64_t n_w
 {
     ATSC_API_BEGIN
     return query_stream(s, n_windows, begin, count, out, RollQuantileQuery{width, stride, count, n_windows, n_q, q, method});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_rolling_histogram_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin,
+                                                     const uint64_t *count, uint64_t width, uint64_t stride, uint32_t n_edges,
+                                                     const double *edges, int closed, uint64_t *out)
+{
+    ATSC_API_BEGIN
+    return query_stream(s, n_windows, begin, count, out,
+                        RollHistogramQuery{width, stride, count, n_windows, n_edges, edges, closed});
     ATSC_API_END
 }
 

@@ -6,7 +6,7 @@
 //   csv-compressor [-o OUT] [-u [--from T0 --to T1 [--step S [--quantiles Q,Q,.. [--quantile-method M]]
 //                  [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT]
 //                  [--extremes K] [--values K[:ABOVE]]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments] [--rolling-runs OP:LIMIT]
-//                  [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]]]]]
+//                  [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]] [--rolling-histogram E,E,..|LO:HI:N]]]]
 //                  [--no-compression] [--output-vsri] [--output-wavbrro]
 //                  [--output-csv] [--compressor auto|noop|fft|constant|polynomial|idw] [-e 0..50] [-c 0..6] <INPUT>
 #include <sys/stat.h>
@@ -95,6 +95,9 @@ void usage()
             "                                 --quantiles), as the last columns: one q<Q> per level as typed; NaN where the\n"
             "                                 window holds no sample\n"
             "      --rolling-quantile-method <M>  with --rolling-quantiles: linear (default), lower, higher or nearest\n"
+            "      --rolling-histogram <SPEC> with --rolling: also every position's counts over the value bins of the edges\n"
+            "                                 (SPEC and --histogram-closed as --histogram), as the last columns:\n"
+            "                                 h0 .. h<n_edges>,hnan; a row's counters sum to W\n"
             "      --no-compression           do not write the .bro\n"
             "      --output-vsri              write the generated VSRI index\n"
             "      --output-wavbrro           write the generated WavBrro\n"
@@ -206,19 +209,21 @@ int uncompress_rolling(const Args &a, const std::string &output_base, uint8_t *b
     std::vector<atsc_window_moments> moments;
     std::vector<atsc_window_runs> runs;
     std::vector<double> levels;
+    std::vector<uint64_t> hist;
     if (count) {
         atsc_ctx *ctx = nullptr;
         rc = atsc_ctx_create(&ctx, 0);
         if (rc) { atsc_free(bro); return die("no GPU context", rc); }
         rc = atsc_bro_open(bro, len, nullptr, nullptr);
-        if (!rc) rc = rolling_query(ctx, bro, len, a.q, begin, count, rows, deltas, fits, moments, levels, runs);
+        if (!rc) rc = rolling_query(ctx, bro, len, a.q, begin, count, rows, deltas, fits, moments, levels, runs, nullptr, &hist);
         if (rc) { int e = die("rolling", rc, atsc_ctx_last_error(ctx)); atsc_ctx_destroy(ctx); atsc_free(bro); return e; }
         atsc_ctx_destroy(ctx);
     }
     atsc_free(bro);
     const uint64_t w = a.q.rolling, stride = a.q.rolling_stride;
     if (!rolling_write(with_ext(output_base, "roll.csv"), "timestamp", rows, a.q.rolling_deltas, deltas, fits, a.q.rolling_moments, moments, a.q.rolling_level_names, levels, a.q.rolling_runs, runs, nullptr,
-                       [&](uint64_t j) { return std::to_string((long long)ts[begin + j * stride + w - 1]); }))
+                       [&](uint64_t j) { return std::to_string((long long)ts[begin + j * stride + w - 1]); },
+                       a.q.rolling_hist ? &hist : nullptr, a.q.rolling_edges.size() + 2))
         return die("failed to write rolling records to file");
     return 0;
 }

@@ -276,6 +276,24 @@ def _rolling_quantile_result(run, counts, width, stride, levels):
     return run(int(off[-1])).view(np.float64).reshape(int(off[-1]), len(_levels(levels)[0])), off
 
 
+def _rolling_histogram_params(width, stride, records, edges, closed):
+    """the rolling's arguments, then the edges and the closed side"""
+    a = _RollArgs(tuple(_rolling_params(width, stride, records)) + _array_params(edges, closed))
+    a.records = int(records)
+    return a
+
+
+def _rolling_histogram_block(n, cargs):
+    return 8 * (cargs[2] + 2) * cargs.records
+
+
+def _rolling_histogram_result(run, counts, width, stride, edges):
+    """run(records) -> the block of a rolling histogram call as uint64 words.  -> (rows, off): a (records, n_edges + 2)
+    uint64 array, a row per position, range after range, and the ranges' record offsets (rolling_offsets)"""
+    off = rolling_offsets(counts, width, stride)
+    return run(int(off[-1])).reshape(int(off[-1]), len(_levels(edges)[0]) + 2), off
+
+
 def _across_params(stride, records):
     stride = int(stride)
     if not 0 <= stride < 2 ** 64:
@@ -365,6 +383,8 @@ _ROLLING_MOMENTS = _Query("rolling_moments_windows", np.dtype(np.uint64), None, 
 _ROLLING_RUNS = _Query("rolling_runs_windows", np.dtype(np.uint64), None, _rolling_runs_params, _rolling_runs_block)
 _ROLLING_PAIR = _Query("rolling_pair_windows", np.dtype(np.uint64), None, _rolling_params, _rolling_pair_block, inputs=2)
 _ROLLING_QUANTILE = _Query("rolling_quantile_windows", np.dtype(np.uint64), None, _rolling_quantile_params, _rolling_quantile_block)
+_ROLLING_HISTOGRAM = _Query("rolling_histogram_windows", np.dtype(np.uint64), None, _rolling_histogram_params,
+                           _rolling_histogram_block)
 _ACROSS = _Query("across_windows", np.dtype(np.uint64), None, _across_params, _across_block, inputs=None)
 _ACROSS_QUANTILE = _Query("across_quantile_windows", np.dtype(np.uint64), None, _across_quantile_params, _across_quantile_block,
                           inputs=None)
@@ -766,6 +786,17 @@ class Context:
             lambda m: _query_host(_ROLLING_QUANTILE, self, records, begins, counts, has_count, width, stride, m, levels, method),
             counts, width, stride, levels)
 
+    def rolling_histogram_windows_host(self, records, begins, counts, width, edges, stride=1, closed=capi.HIST_LEFT_CLOSED,
+                                       has_count=False):
+        """-> (rows, off): the value-bin counts (histogram_windows_host's edges, closed side and layout) of the window of
+        `width` samples at every `stride`-th position of every range [begins[i], begins[i] + counts[i]) of the decoded
+        records (atsc_rolling_histogram_windows).  rows: a (records, n_edges + 2) uint64 array, a row per position, range
+        after range: the row histogram_windows_host gives for the listed window, its counters summing to `width`; off: as
+        rolling_windows_host's"""
+        return _rolling_histogram_result(
+            lambda m: _query_host(_ROLLING_HISTOGRAM, self, records, begins, counts, has_count, width, stride, m, edges, closed),
+            counts, width, stride, edges)
+
     def rolling_pair_windows_host(self, records_x, records_y, begins, counts, width, stride=1, has_count=False):
         """-> (records, off): the pair moments' record (count, mean_x, m2_x, mean_y, m2_y, c_xy) of the window of `width`
         samples at every `stride`-th position of every range [begins[i], begins[i] + counts[i]) of the two decoded
@@ -1036,6 +1067,17 @@ class DPlan:
         m, n_q = int(off[-1]), len(_levels(levels)[0])
         _query_dev(_ROLLING_QUANTILE, self, d_body, begins, counts, d_out, stream, width, stride, m, levels, method)
         return d_out.view(-1)[: m * n_q].view(m, n_q), off
+
+    def rolling_histogram_windows(self, d_body, begins, counts, width, stride, edges, d_out, closed=capi.HIST_LEFT_CLOSED,
+                                  stream=0):
+        """Enqueues the value-bin counts of the window of `width` samples at every `stride`-th position of the ranges
+        [begins[i], begins[i] + counts[i]) into d_out, a 64-bit integer device tensor of at least n_edges + 2 elements per
+        position, position-major (atsc_rolling_histogram_windows_dev).  -> (rows, off): the (records, n_edges + 2) view
+        of d_out and the ranges' record offsets (rolling_offsets)"""
+        off = rolling_offsets(counts, width, stride)
+        m, rows = int(off[-1]), len(_levels(edges)[0]) + 2
+        _query_dev(_ROLLING_HISTOGRAM, self, d_body, begins, counts, d_out, stream, width, stride, m, edges, closed)
+        return d_out.view(-1)[: m * rows].view(m, rows), off
 
     def rolling_pair_windows(self, d_body, other, other_body, begins, counts, width, stride, d_out, stream=0):
         """Enqueues the pair moments' record of this plan's stream (x) and the plan `other`'s (y; its device bytes

@@ -11,6 +11,7 @@ from .engine import _AGGREGATE, _DELTA, _EXTREMES, _HISTOGRAM, _MOMENTS, _PAIR, 
 from .engine import ACROSS_RECORD, _ACROSS, _across_host, _across_list, _across_result  # noqa: F401
 from .engine import _ACROSS_QUANTILE, _across_quantile_result
 from .engine import _ROLLING_QUANTILE, _rolling_quantile_result
+from .engine import _ROLLING_HISTOGRAM, _rolling_histogram_result
 from .engine import _ACROSS_EXTREMES, _across_extremes_result
 from .engine import _ACROSS_MOMENTS, _across_moments_result
 
@@ -185,6 +186,14 @@ class CompressedStream:
             lambda m: _query_stream(_ROLLING_QUANTILE, self, begins, counts, width, stride, m, levels, method), counts, width,
             stride, levels)
 
+    def rolling_histogram_windows(self, begins, counts, width, edges, stride=1, closed=capi.HIST_LEFT_CLOSED):
+        """-> (rows, off): the value-bin counts of the window of `width` samples at every `stride`-th position of the
+        ranges [begins[i], begins[i] + counts[i]), as Context.rolling_histogram_windows_host gives them
+        (atsc_stream_rolling_histogram_windows)"""
+        return _rolling_histogram_result(
+            lambda m: _query_stream(_ROLLING_HISTOGRAM, self, begins, counts, width, stride, m, edges, closed), counts, width,
+            stride, edges)
+
     def rolling_pair_windows(self, other, begins, counts, width, stride=1):
         """-> (records, off): the pair moments' record of this stream (x) and `other` (y) over the window of `width`
         samples at every `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as
@@ -353,6 +362,15 @@ def rolling_quantile_data_windows(ctx, bro, begins, counts, width, levels, strid
     return _rolling_quantile_result(
         lambda m: _query_image(_ROLLING_QUANTILE, ctx, bro, begins, counts, width, stride, m, levels, method), counts, width,
         stride, levels)
+
+
+def rolling_histogram_data_windows(ctx, bro, begins, counts, width, edges, stride=1, closed=capi.HIST_LEFT_CLOSED):
+    """-> (rows, off): the value-bin counts of the window of `width` samples at every `stride`-th position of ranges of
+    decompress_data(ctx, bro), as Context.rolling_histogram_windows_host gives them: atsc_bro_open, then
+    atsc_rolling_histogram_windows over the records"""
+    return _rolling_histogram_result(
+        lambda m: _query_image(_ROLLING_HISTOGRAM, ctx, bro, begins, counts, width, stride, m, edges, closed), counts, width,
+        stride, edges)
 
 
 def rolling_pair_data_windows(ctx, bro_x, bro_y, begins, counts, width, stride=1):

@@ -988,6 +988,43 @@ int atsc_rolling_quantile_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t b
                                   const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
                                   uint32_t n_q, const double *q, int method, double *out);
 
+/* Windowed rolling histograms: the value-bin counts of the sliding window at every position of ranges of the decoded
+ * stream: a latency heat map at every step, the Prometheus `le` bucket counts over `x[5m]` at every evaluation time (the
+ * input of `histogram_quantile`), an SLO's "share of samples under 200 ms over the trailing hour" at every step --
+ * without listing one window per position for atsc_histogram_windows.
+ *   Ranges     Ranges, width w, stride s, the number and the order of the positions (atsc_rolling_outputs),
+ *              1 <= w <= ATSC_ROLLING_MAX_WIDTH, s >= 1, the limit of 2^32 - 2 positions in all and validation are
+ *              atsc_rolling_windows'.  The messages name rolling_histogram_windows.
+ *   Edges      edges[0 .. n_edges), closed and their validation are atsc_histogram_windows': n_edges in
+ *              1 .. ATSC_HIST_MAX_EDGES, strictly ascending as values, no NaN edge, +-Inf allowed.
+ *   Result     n_edges + 2 u64 counters per position, in the histograms' layout (bins 0 .. n_edges, then the NaN samples):
+ *              with m_i = atsc_rolling_outputs(count[i], w, s), row j of range i is at
+ *              out[(m_0 + .. + m_(i-1) + j) * (n_edges + 2)].  positions x (n_edges + 2) must be below 2^32 - 1, so that
+ *              a counter's index fits 32 bits.  The caller sizes the result: sum m_i x (n_edges + 2) x 8 bytes.
+ *   Row        The row of the position whose window is [lo, lo + w) is, bit for bit, the row atsc_histogram_windows
+ *              returns for (begin, count) = (lo, w) with the same edges and closed; its counters sum to w.  Counts are
+ *              integers: a position's bytes depend on the stream's samples, (lo, w), the edges and closed alone, not on
+ *              the range the window came from, the stride, the other ranges, the budget, the piece boundaries, how
+ *              positions were grouped, the framing, the host or the device call.
+ * Errors: ATSC_E_INVALID with nothing written and before any GPU work for every case of atsc_rolling_windows, for every
+ * case of atsc_histogram_windows' edge checks (null edges, n_edges == 0 or above ATSC_HIST_MAX_EDGES, a NaN edge, edges
+ * not strictly ascending, an unknown closed), for positions x (n_edges + 2) >= 2^32 - 1 (the message says so), a d_out
+ * that is not 8-byte aligned.  ATSC_E_CAPACITY when a window is longer than one scratch piece under the budget of
+ * atsc_ctx_set_aggregate_scratch (the message says the budget that would hold it; the default budget holds every
+ * width).  ATSC_E_FORMAT (host form) or the plan's status word (device form) for a malformed payload inside a
+ * position's window.
+ * The scratch holds the decoded samples only (8 bytes a sample); consecutive pieces overlap by w - 1 samples.
+ * begin / count / edges are HOST arrays; d_body and d_out are device memory (d_out 8-byte aligned, 8 (n_edges + 2) bytes
+ * per position).  Enqueued on `stream`, not synchronised.  The call keeps its tables and scratch in the rolling's place
+ * of the plan: it and the rolling calls on the same plan wait (host side) for each other. */
+int atsc_rolling_histogram_windows_dev(atsc_ctx *ctx, const atsc_dplan *dp, const uint8_t *d_body, uint64_t n_windows,
+                                       const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                       uint32_t n_edges, const double *edges, int closed, uint64_t *d_out, void *stream);
+/* Host bytes in, host rows out, synchronous, as atsc_rolling_windows is; computes the device call's bits. */
+int atsc_rolling_histogram_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len, int has_count, uint64_t n_windows,
+                                   const uint64_t *begin, const uint64_t *count, uint64_t width, uint64_t stride,
+                                   uint32_t n_edges, const double *edges, int closed, uint64_t *out);
+
 /* Windowed rolling pair moments: the pair moments' record (atsc_window_pair, 48 bytes) of the sliding window at every
  * position of ranges of TWO decoded streams X and Y: a rolling correlation ("does latency follow load over the last five
  * minutes, at every step"), a rolling beta (the regression slope of y on x), the covariance against a reference series
@@ -1376,6 +1413,10 @@ int atsc_stream_rolling_moments_windows(atsc_stream *s, uint64_t n_windows, cons
 int atsc_stream_rolling_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                          uint64_t width, uint64_t stride, uint32_t n_q, const double *q, int method,
                                          double *out);
+/* atsc_rolling_histogram_windows over the stream's frames */
+int atsc_stream_rolling_histogram_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                          uint64_t width, uint64_t stride, uint32_t n_edges, const double *edges, int closed,
+                                          uint64_t *out);
 /* atsc_rolling_pair_windows over the frames of two streams of one context (x and y may be the same stream) */
 int atsc_stream_rolling_pair_windows(atsc_stream *x, atsc_stream *y, uint64_t n_windows, const uint64_t *begin,
                                      const uint64_t *count, uint64_t width, uint64_t stride, atsc_window_pair *out);
