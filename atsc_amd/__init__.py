@@ -26,6 +26,7 @@ from .engine import ACROSS_RECORD, across_offsets, across_outputs  # noqa: F401
 from .stream import across_data_windows, across_extremes_data_windows, across_quantile_data_windows  # noqa: F401
 from .engine import ACROSS_FIT, ACROSS_MOMENTS, across_moments_fit, across_moments_merge  # noqa: F401
 from .stream import across_moments_data_windows  # noqa: F401
+from .stream import across_histogram_data_windows  # noqa: F401
 from .engine import WINDOW_PAIR, WINDOW_PAIR_FIT, pair_fit  # noqa: F401
 from .stream import select_data_windows  # noqa: F401
 from .engine import (WINDOW_DELTA, WINDOW_DELTA_FIT, WINDOW_FIT, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, Context, DPlan, Plan,  # noqa: F401

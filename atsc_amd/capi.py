@@ -172,6 +172,10 @@ SIGNATURES = {
                                                C.c_uint32, _vp]),
     "atsc_across_moments_windows_dev": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, _vp, _vp]),
     "atsc_across_moments_windows": (C.c_int, [_vp, C.c_uint32, _vp, _u64p, _i32p, C.c_uint64, _u64p, _u64p, C.c_uint64, _vp]),
+    "atsc_across_histogram_windows_dev": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64,
+                                                    C.c_uint32, _f64p, C.c_int, _vp, _vp]),
+    "atsc_across_histogram_windows": (C.c_int, [_vp, C.c_uint32, _vp, _u64p, _i32p, C.c_uint64, _u64p, _u64p, C.c_uint64,
+                                                C.c_uint32, _f64p, C.c_int, _vp]),
     "atsc_across_moments_merge": (C.c_int, [_vp, C.c_uint64, _vp]),
     "atsc_across_moments_fit": (C.c_int, [_vp, C.c_uint64, _vp]),
     "atsc_quantile_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _vp,
@@ -217,6 +221,8 @@ SIGNATURES = {
     "atsc_stream_across_extremes_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint32,
                                                       _vp]),
     "atsc_stream_across_moments_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, _vp]),
+    "atsc_stream_across_histogram_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint32,
+                                                       _f64p, C.c_int, _vp]),
     "atsc_stream_quantile_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _f64p]),
     "atsc_stream_histogram_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _f64p, C.c_int, _u64p]),
     "atsc_free": (None, [_vp]),

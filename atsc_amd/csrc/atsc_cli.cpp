@@ -8,7 +8,7 @@
 //        [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]] [--rolling-pair OTHER.bro]
 //        [--rolling-histogram E,E,..|LO:HI:N]]
 //        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]
-//        [--across-extremes K] [--across-moments]]]
+//        [--across-extremes K] [--across-moments] [--across-histogram E,E,..|LO:HI:N]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -127,6 +127,9 @@ void usage()
             "                                 streams' samples at every row's sample index are not NaN, their mean and their\n"
             "                                 variance and standard deviation (population forms), merged from centred moments and\n"
             "                                 never from a sum of squares; the four cells empty where every sample is NaN\n"
+            "      --across-histogram <SPEC>  with --across: also how many of the streams' samples at every row's sample index\n"
+            "                                 lie in each value bin of the edges (SPEC and --histogram-closed as --histogram), as\n"
+            "                                 the last columns: h0 .. h<n_edges>,hnan; a row's counters sum to the number of streams\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -234,12 +237,14 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
             std::vector<double> levels;
             std::vector<uint64_t> extremes;
             std::vector<atsc_across_moments> moments;
+            std::vector<uint64_t> hist;
             rc = atsc_bro_open(bro, len, nullptr, nullptr);
-            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, levels, extremes, moments);
+            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, levels, extremes, moments, hist);
             atsc_free(bro);
             if (rc) return rc;
             const bool ok = across_write(with_ext(path, "across.csv"), rows, a.q.across_stride, a.q.across_level_names, levels,
-                                         (uint32_t)a.q.across_extremes, extremes, a.q.across_moments, moments);
+                                         (uint32_t)a.q.across_extremes, extremes, a.q.across_moments, moments,
+                                         a.q.across_hist ? &hist : nullptr, a.q.across_edges.size() + 2);
             return ok ? ATSC_OK : ATSC_E_IO;
         }
         double *out = nullptr;

@@ -98,6 +98,8 @@ struct BucketOptions {
     bool have_across_method = false;
     int across_extremes = 0;  // --across-extremes K: nans,top1,top1_at,..,topK,topK_at,bottom1,bottom1_at,..,bottomK,bottomK_at
     bool across_moments = false;  // --across-moments: nonnan,avg,stdvar,stddev
+    std::vector<double> across_edges;  // --across-histogram E,E,..|LO:HI:N: h0 .. h<n_edges>,hnan as the last columns (closed: --histogram-closed)
+    bool across_hist = false;
 };
 
 // --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
@@ -160,6 +162,15 @@ int parse_histogram(const std::string &v, std::vector<double> &edges)
         if (c == std::string::npos) return edges.size() > (size_t)ATSC_HIST_MAX_EDGES ? 2 : 0;
         p = c + 1;
     }
+}
+
+// the value of --histogram, --rolling-histogram or --across-histogram (`name`) into edges.  false: a usage error, reported
+bool histogram_option(const char *name, const std::string &v, std::vector<double> &edges)
+{
+    const int bad = parse_histogram(v, edges);
+    if (bad == 1) fprintf(stderr, "error: invalid value '%s' for '%s': expected ascending edges E,E,.. or LO:HI:N\n", v.c_str(), name);
+    if (bad == 2) fprintf(stderr, "error: invalid value for '%s': more than %d edges\n", name, (int)ATSC_HIST_MAX_EDGES);
+    return bad == 0;
 }
 
 // --runs OP:LIMIT: OP one of gt ge lt le eq ne, LIMIT a number that is not NaN, nothing behind it
@@ -246,15 +257,7 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
         }
         o.have_method = true;
     } else if (value("--histogram")) {
-        const int bad = parse_histogram(v, o.edges);
-        if (bad == 1) {
-            fprintf(stderr, "error: invalid value '%s' for '--histogram': expected ascending edges E,E,.. or LO:HI:N\n", v.c_str());
-            return 2;
-        }
-        if (bad == 2) {
-            fprintf(stderr, "error: invalid value for '--histogram': more than %d edges\n", (int)ATSC_HIST_MAX_EDGES);
-            return 2;
-        }
+        if (!histogram_option("--histogram", v, o.edges)) return 2;
         o.have_hist = true;
     } else if (value("--histogram-closed")) {
         if (v != "left" && v != "right") {
@@ -306,16 +309,7 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             return 2;
         }
     } else if (value("--rolling-histogram")) {
-        const int bad = parse_histogram(v, o.rolling_edges);
-        if (bad == 1) {
-            fprintf(stderr, "error: invalid value '%s' for '--rolling-histogram': expected ascending edges E,E,.. or LO:HI:N\n",
-                    v.c_str());
-            return 2;
-        }
-        if (bad == 2) {
-            fprintf(stderr, "error: invalid value for '--rolling-histogram': more than %d edges\n", (int)ATSC_HIST_MAX_EDGES);
-            return 2;
-        }
+        if (!histogram_option("--rolling-histogram", v, o.rolling_edges)) return 2;
         o.rolling_hist = true;
     } else if (value("--rolling-quantile-method")) {
         if (!parse_method(v, o.rolling_method)) {
@@ -385,6 +379,9 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
         }
     } else if (o.across_allowed && s == "--across-moments") {
         o.across_moments = true;
+    } else if (o.across_allowed && value("--across-histogram")) {
+        if (!histogram_option("--across-histogram", v, o.across_edges)) return 2;
+        o.across_hist = true;
     } else {
         return 0;
     }
@@ -401,7 +398,7 @@ bool bucket_options_complete(const BucketOptions &o, const char *bucketing, bool
     } T[] = {{!o.levels.empty(), given, "--quantiles", bucketing},
              {o.have_method, !o.levels.empty(), "--quantile-method", "--quantiles"},
              {o.have_hist, given, "--histogram", bucketing},
-             {o.have_closed, o.have_hist || o.rolling_hist, "--histogram-closed", "--histogram"},
+             {o.have_closed, o.have_hist || o.rolling_hist || o.across_hist, "--histogram-closed", "--histogram"},
              {o.moments, given, "--moments", bucketing},
              {o.deltas, given, "--deltas", bucketing},
              {o.have_runs, given, "--runs", bucketing},
@@ -469,8 +466,8 @@ bool rolling_option_complete(const BucketOptions &o, const char *window, bool wi
 }
 
 // --across goes with the option that names the window and without the one that cuts buckets, --rolling and --where;
-// --across-stride, --across-quantiles, --across-extremes and --across-moments go with --across, --across-quantile-method with
-// --across-quantiles.  false: a usage error, reported on stderr.
+// --across-stride, --across-quantiles, --across-extremes, --across-moments and --across-histogram go with --across,
+// --across-quantile-method with --across-quantiles.  false: a usage error, reported on stderr.
 bool across_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
 {
     if (o.have_across_method && o.across_levels.empty()) {
@@ -482,7 +479,8 @@ bool across_option_complete(const BucketOptions &o, const char *window, bool win
         else if (!o.across_levels.empty()) fprintf(stderr, "error: '--across-quantiles' needs '--across'\n");
         else if (o.across_extremes) fprintf(stderr, "error: '--across-extremes' needs '--across'\n");
         else if (o.across_moments) fprintf(stderr, "error: '--across-moments' needs '--across'\n");
-        return !o.have_across_stride && o.across_levels.empty() && !o.across_extremes && !o.across_moments;
+        else if (o.across_hist) fprintf(stderr, "error: '--across-histogram' needs '--across'\n");
+        return !o.have_across_stride && o.across_levels.empty() && !o.across_extremes && !o.across_moments && !o.across_hist;
     }
     if (!windowed) {
         fprintf(stderr, "error: '--across' needs '%s'\n", window);
@@ -859,10 +857,11 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
 // files (stream 1 and on): sample i of each goes with sample i of the others.  levels: with --across-quantiles, the
 // same positions' rows of o.across_levels.size() levels; extremes: with --across-extremes K, the same positions'
 // extremes records of k = K, ATSC_EXTREMES_BYTES(K) / 8 words each; moments: with --across-moments, the same
-// positions' across moments
+// positions' across moments; hist: with --across-histogram, the same positions' rows of o.across_edges.size() + 2 counters
+// (--histogram-closed's side)
 int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
                  std::vector<atsc_across_record> &rows, std::vector<double> &levels, std::vector<uint64_t> &extremes,
-                 std::vector<atsc_across_moments> &moments)
+                 std::vector<atsc_across_moments> &moments, std::vector<uint64_t> &hist)
 {
     std::vector<uint8_t *> image(o.across.size(), nullptr);
     std::vector<const uint8_t *> body{bro + 9};
@@ -904,6 +903,13 @@ int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOp
             rc = atsc_across_moments_windows(ctx, (uint32_t)body.size(), body.data(), body_len.data(), has_count.data(), 1, &begin,
                                              &count, o.across_stride, moments.empty() ? &no_moments : moments.data());
         }
+        if (!rc && o.across_hist) {
+            hist.assign(rows.size() * (o.across_edges.size() + 2), 0);
+            uint64_t no_row;
+            rc = atsc_across_histogram_windows(ctx, (uint32_t)body.size(), body.data(), body_len.data(), has_count.data(), 1, &begin,
+                                               &count, o.across_stride, (uint32_t)o.across_edges.size(), o.across_edges.data(),
+                                               o.closed, hist.empty() ? &no_row : hist.data());
+        }
     }
     for (uint8_t *p : image) atsc_free(p);
     return rc;
@@ -917,10 +923,13 @@ int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOp
 // `extremes`: the K largest and the K smallest samples and the streams that hold them, the cells of unused entries
 // empty.  with_moments: with --across-moments, behind those nonnan,avg,stdvar,stddev from the position's record of
 // `moments`: its count, mean and the population variance and standard deviation that atsc_across_moments_fit reads off
-// it, all four empty where count == 0 (the count column says so).  false: the file could not be written.
+// it, all four empty where count == 0 (the count column says so).  hist (--across-histogram; null without it): as the
+// last columns h0 .. h<n_edges>,hnan, --histogram's columns, from the position's row of n_hist = n_edges + 2 counters.
+// false: the file could not be written.
 bool across_write(const std::string &path, const std::vector<atsc_across_record> &rows, uint64_t stride,
                   const std::vector<std::string> &names, const std::vector<double> &levels, uint32_t k,
-                  const std::vector<uint64_t> &extremes, bool with_moments, const std::vector<atsc_across_moments> &moments)
+                  const std::vector<uint64_t> &extremes, bool with_moments, const std::vector<atsc_across_moments> &moments,
+                  const std::vector<uint64_t> *hist = nullptr, size_t n_hist = 0)
 {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return false;
@@ -932,6 +941,10 @@ bool across_write(const std::string &path, const std::vector<atsc_across_record>
         for (uint32_t e = 0; e < k; ++e) fprintf(f, ",bottom%u,bottom%u_at", e + 1, e + 1);
     }
     if (with_moments) fprintf(f, ",nonnan,avg,stdvar,stddev");
+    if (hist) {
+        for (size_t b = 0; b + 1 < n_hist; ++b) fprintf(f, ",h%zu", b);
+        fprintf(f, ",hnan");
+    }
     fprintf(f, "\n");
     for (size_t j = 0; j < rows.size(); ++j) {
         const atsc_across_record &r = rows[j];
@@ -956,6 +969,8 @@ bool across_write(const std::string &path, const std::vector<atsc_across_record>
             else fprintf(f, ",%u,%s,%s,%s", moments[j].count, debug_f64(fit.mean).c_str(), debug_f64(fit.variance).c_str(),
                          debug_f64(fit.stddev).c_str());
         }
+        if (hist)
+            for (size_t b = 0; b < n_hist; ++b) fprintf(f, ",%llu", (unsigned long long)(*hist)[j * n_hist + b]);
         fprintf(f, "\n");
     }
     return fclose(f) == 0;

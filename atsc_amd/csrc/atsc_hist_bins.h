@@ -1,7 +1,8 @@
-// atsc_hist_bins.h -- the value bins of the histograms, shared by the windowed histograms' kernels (atsc_histogram.hip)
-// and the windowed rolling histograms' (atsc_rolling_histogram.hip): the bin of one sample by a branch-free search over
-// the edges in LDS, and a wavefront's counting of its lanes' bins with LDS integer atomics.  One text, so that a row of
-// the rolling call and a row of the listed windows cannot part.
+// atsc_hist_bins.h -- the value bins of the histograms, shared by the windowed histograms' kernels (atsc_histogram.hip),
+// the windowed rolling histograms' (atsc_rolling_histogram.hip) and the windowed across histograms'
+// (atsc_across_histogram.hip): the bin of one sample by a branch-free search over the edges in LDS, a wavefront's
+// counting of its lanes' bins with LDS integer atomics, and the fence pair that orders a wavefront's LDS rows between
+// its lanes.  One text, so that a row of the rolling or the across call and a row of the listed windows cannot part.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,6 +47,14 @@ __device__ __forceinline__ void count_bins(uint32_t *cnt, uint32_t bin, uint32_t
     const uint64_t above = lane == 63u ? 0ull : heads >> (lane + 1u);
     const uint32_t run = above ? (uint32_t)__ffsll((unsigned long long)above) : 64u - lane;
     if (head && bin != HST_NONE) atomicAdd(&cnt[bin], run);
+}
+
+// orders this wavefront's LDS accesses in front of the call against those behind it, whichever lanes made them
+__device__ __forceinline__ void rh_row_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 }  // namespace

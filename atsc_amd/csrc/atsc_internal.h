@@ -395,6 +395,21 @@ static inline uint64_t rh_task_positions(uint64_t w, uint64_t s)
 // task is a DevRollTask: n positions of one range inside one piece, the first at sample lo of the streams.
 constexpr uint32_t ACR_TASK = 512;  // positions per task: one wavefront, four steps of 64 pairs at stride 1
 
+// windowed across histograms (atsc_across_histogram_windows_dev, atsc_across_histogram.hip): a wavefront counts the rows
+// of G positions at a time in byte counters in LDS (a count cannot pass ATSC_ACROSS_MAX_STREAMS = 64).  A row's pitch is
+// an odd number of 4-byte words, so that lanes that land in one bin of neighbouring rows meet different banks; G is what
+// fits a wavefront's share of LDS, at most a lane per row:
+//   words(n_edges) = ceil((n_edges + 2) / 4) | 1,  pitch = 4 words bytes,  G = min(64, floor(AH_WAVE_LDS / pitch)).
+// G is 64 up to n_edges = 218, 62 at 219 and 13 at 1024; with the edges a workgroup of four wavefronts holds
+// 8 n_edges + 4 G pitch <= 8192 + 4 x 14336 = 65536 bytes.
+constexpr uint32_t AH_WAVE_LDS = 14336;
+static inline uint32_t ah_row_pitch(uint32_t n_edges) { return 4u * (((n_edges + 2u + 3u) / 4u) | 1u); }
+static inline uint32_t ah_rows_a_pass(uint32_t n_edges)
+{
+    const uint32_t g = AH_WAVE_LDS / ah_row_pitch(n_edges);
+    return g < 64u ? g : 64u;
+}
+
 static inline uint32_t varint_len_u64(uint64_t v)
 {
     return v < 251 ? 1u : v < (1ull << 16) ? 3u : v < (1ull << 32) ? 5u : 9u;

@@ -19,7 +19,8 @@
 //           two are one bin), and the wavefront stores the row, 64 counters a trip, widened to u64;
 //   recount (stride >= w) the windows are disjoint: every position is a first row.
 // Visibility of the counters across lanes: the row a wavefront stores was written by other lanes' LDS atomics, and the
-// next position's atomics follow other lanes' reads of the row.  Both are ordered in the source by rh_row_sync: a
+// next position's atomics follow other lanes' reads of the row.  Both are ordered in the source by rh_row_sync
+// (atsc_hist_bins.h): a
 // wavefront-scope release fence, __builtin_amdgcn_wave_barrier() and a wavefront-scope acquire fence (rds_fill's pair in
 // atsc_device.h, with the acquire side spelled out), so wavefronts run their tasks with trip counts of their own and the
 // workgroup synchronises once, behind the edges' load.
@@ -33,14 +34,6 @@
 namespace atsc {
 
 namespace {
-
-// orders this wavefront's LDS accesses in front of the call against those behind it, whichever lanes made them
-__device__ __forceinline__ void rh_row_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // the wavefront's counters as one row of the result, then the barrier in front of the next change of the counters
 __device__ __forceinline__ void rh_store_row(const uint32_t *cnt, uint32_t rows, uint64_t *__restrict__ row, uint32_t lane)

@@ -1,6 +1,6 @@
 // atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms,
 // rolling windows, rolling deltas, rolling runs, rolling quantiles, rolling histograms and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
-// and count, min, max, sum, quantiles, extremes and moments across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
+// and count, min, max, sum, quantiles, extremes, moments and histograms across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
@@ -152,6 +152,11 @@ __attribute__((weak)) hipError_t launch_across_extremes_positions(const DevRollT
 __attribute__((weak)) hipError_t launch_across_moments_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
                                                                  const uint64_t *reg, uint32_t n_streams, uint64_t a0,
                                                                  uint64_t stride, void *out, hipStream_t s);
+// the windowed across histograms' position kernel (atsc_across_histogram.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_across_histogram_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
+                                                                   const uint64_t *reg, uint32_t n_streams, uint64_t a0,
+                                                                   uint64_t stride, const double *edges, uint32_t n_edges,
+                                                                   int closed, uint64_t *out, hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -414,7 +419,8 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_ROLLING_HISTOGRAM = DECODE_CALLER("rolling histogram"), BY_ACROSS = DECODE_CALLER("across"),
                           BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile"),
                           BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes"),
-                          BY_ACROSS_MOMENTS = DECODE_CALLER("across moments");
+                          BY_ACROSS_MOMENTS = DECODE_CALLER("across moments"),
+                          BY_ACROSS_HISTOGRAM = DECODE_CALLER("across histogram");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -3267,7 +3273,7 @@ static int across_check(atsc_ctx *ctx, const char *call, uint32_t n_streams, uin
 }
 
 // What differs between the device calls that work on the N samples of a position (across_dev): the across and the
-// across quantiles, the across extremes and the across moments.
+// across quantiles, the across extremes, the across moments and the across histograms.
 struct AcrossKernel {
     const char *call;          // names the call in the messages
     const char *no_kernels;    // ATSC_E_UNSUPPORTED's message
@@ -3548,6 +3554,59 @@ struct AcrossMomQuery {
     }
 };
 
+// the across histograms' descriptor: the across' ranges, stride and record numbering, the histograms' row of n_edges + 2
+// counters per position; the edges and `closed` are checked as the windowed histograms check theirs
+// (histogram_check_edges), the edges go up with the call's tables, and the rolling histograms' limit keeps a counter's
+// index in 32 bits.  Like the across extremes and moments it keeps its tables and scratch in the across quantiles' place
+// on in[0].dp (Q_ACROSS_QUANTILE): the four kinds of call on one first plan wait for each other, and atsc_dplan stays
+// as it is (DESIGN.md "Windowed across histograms")
+struct AcrossHistQuery {
+    static constexpr int INPUTS = 0;
+    static constexpr const char *CALL = "across_histogram_windows";
+    uint32_t n_streams;
+    uint64_t stride;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    uint32_t n_edges;
+    const double *edges;
+    int closed;
+    int inputs() const { return (int)n_streams; }
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
+        return total * ((size_t)n_edges + 2) * sizeof(uint64_t);
+    }
+    int check(atsc_ctx *ctx) const
+    {
+        uint64_t total = 0;
+        int rc = across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, &total);
+        if (!rc) rc = histogram_check_edges(ctx, n_edges, edges, closed, CALL);
+        if (rc) return rc;
+        if (total * ((uint64_t)n_edges + 2) > 0xfffffffeull)  // (total < 2^32 and n_edges + 2 <= 1026: no overflow)
+            return fail_in(ctx, ATSC_E_INVALID, CALL, "positions x (n_edges + 2) is not below 2^32 - 1 counters");
+        return ATSC_OK;
+    }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no row
+    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
+            void *stream) const
+    {
+        const int rc = check(ctx);
+        if (rc) return rc;
+        const uint32_t ns = n_streams, ne = n_edges;
+        const uint64_t st = stride;
+        const int cl = closed;
+        const AcrossKernel K{CALL, "no across histogram kernels", "launch k_across_histogram_positions", Q_ACROSS_QUANTILE,
+                             BY_ACROSS_HISTOGRAM, launch_across_histogram_positions != nullptr, edges, n_edges * sizeof(double),
+                             [ns, st, ne, cl](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg,
+                                              uint64_t a0, const void *d_edges, void *d_out, hipStream_t s) {
+                                 return launch_across_histogram_positions(tasks, n, scratch, reg, ns, a0, st,
+                                                                          (const double *)d_edges, ne, cl, (uint64_t *)d_out, s);
+                             }};
+        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
+    }
+};
+
 // what every across call checks of its lists before it reads them
 static bool across_lists(uint32_t n_streams, const void *const *a, const void *const *b)
 {
@@ -3662,6 +3721,37 @@ extern "C" int atsc_across_moments_windows(atsc_ctx *ctx, uint32_t n_streams, co
     HostBody hb[MAX_INPUTS];
     for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
     return query_host(ctx, hb, n_windows, begin, count, out, AcrossMomQuery{n_streams, stride, count, n_windows});
+    ATSC_API_END
+}
+
+extern "C" int atsc_across_histogram_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                                 const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                                 const uint64_t *count, uint64_t stride, uint32_t n_edges, const double *edges,
+                                                 int closed, uint64_t *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
+        return fail(ctx, ATSC_E_INVALID, "across_histogram_windows: n_streams outside [1, 64], a null list or a null entry");
+    QueryInput in[MAX_INPUTS];
+    for (uint32_t j = 0; j < n_streams; ++j) in[j] = QueryInput{dp[j], d_body[j], 0};
+    return AcrossHistQuery{n_streams, stride, count, n_windows, n_edges, edges, closed}.dev(ctx, in, n_windows, begin, count, d_out,
+                                                                                            stream);
+    ATSC_API_END
+}
+
+extern "C" int atsc_across_histogram_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body,
+                                             const uint64_t *body_len, const int *has_count, uint64_t n_windows,
+                                             const uint64_t *begin, const uint64_t *count, uint64_t stride, uint32_t n_edges,
+                                             const double *edges, int closed, uint64_t *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
+        return fail(ctx, ATSC_E_INVALID, "across_histogram_windows: n_streams outside [1, 64], a null list or a null entry");
+    if ((uintptr_t)out & 7u) return fail(ctx, ATSC_E_INVALID, "across_histogram_windows: out is not 8-byte aligned");
+    HostBody hb[MAX_INPUTS];
+    for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
+    return query_host(ctx, hb, n_windows, begin, count, out,
+                      AcrossHistQuery{n_streams, stride, count, n_windows, n_edges, edges, closed});
     ATSC_API_END
 }
 
@@ -3965,5 +4055,16 @@ extern "C" int atsc_stream_across_moments_windows(atsc_stream *const *streams, u
     ATSC_API_BEGIN
     if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
     return query_stream(streams, n_windows, begin, count, out, AcrossMomQuery{n_streams, stride, count, n_windows});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_across_histogram_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                                    const uint64_t *begin, const uint64_t *count, uint64_t stride,
+                                                    uint32_t n_edges, const double *edges, int closed, uint64_t *out)
+{
+    ATSC_API_BEGIN
+    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
+    return query_stream(streams, n_windows, begin, count, out,
+                        AcrossHistQuery{n_streams, stride, count, n_windows, n_edges, edges, closed});
     ATSC_API_END
 }

@@ -363,6 +363,17 @@ def _across_moments_result(run, counts, stride):
     return run(int(off[-1])).view(ACROSS_MOMENTS), off
 
 
+def _across_histogram_block(n, cargs):
+    return 8 * (cargs[1] + 2) * cargs.records
+
+
+def _across_histogram_result(run, counts, stride, edges):
+    """run(records) -> the block of an across histogram call as uint64 words.  -> (rows, off): a (records, n_edges + 2)
+    uint64 array, a row per position, range after range, and the ranges' record offsets (across_offsets)"""
+    off = across_offsets(counts, stride)
+    return run(int(off[-1])).reshape(int(off[-1]), len(_levels(edges)[0]) + 2), off
+
+
 def _array_params(values, flag):
     """levels and method, or edges and closed"""
     a, pa = _levels(values)
@@ -391,6 +402,9 @@ _ACROSS_QUANTILE = _Query("across_quantile_windows", np.dtype(np.uint64), None, 
 _ACROSS_EXTREMES = _Query("across_extremes_windows", np.dtype(np.uint64), None, _across_extremes_params, _across_extremes_block,
                           inputs=None)
 _ACROSS_MOMENTS = _Query("across_moments_windows", np.dtype(np.uint64), None, _across_params, _across_moments_block, inputs=None)
+# (the across quantiles' arguments serve: the stride, then the edges and the closed side in the levels' and the method's place)
+_ACROSS_HISTOGRAM = _Query("across_histogram_windows", np.dtype(np.uint64), None, _across_quantile_params, _across_histogram_block,
+                           inputs=None)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
 _HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
 
@@ -827,6 +841,19 @@ class Context:
             lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m, levels, method, q=_ACROSS_QUANTILE),
             counts, stride, levels)
 
+    def across_histogram_windows_host(self, records_list, begins, counts, edges, stride=1, closed=capi.HIST_LEFT_CLOSED,
+                                      has_count=False):
+        """-> (rows, off): how many of the streams of records_list (at most ACROSS_MAX_STREAMS decoded record streams, as
+        across_windows_host takes them) hold a sample in each value bin (histogram_windows_host's edges, `closed` and
+        rule) at every `stride`-th position of every range [begins[i], begins[i] + counts[i])
+        (atsc_across_histogram_windows).  rows: a (records, n_edges + 2) uint64 array, a row per position, range after
+        range: bins 0 .. n_edges, then the streams whose sample is NaN; a row sums to len(records_list), and the rows of
+        sub-lists add to the row of the whole list.  off: across_offsets(counts, stride), range i's rows being
+        rows[off[i]:off[i + 1]].  has_count holds for every stream"""
+        return _across_histogram_result(
+            lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m, edges, closed, q=_ACROSS_HISTOGRAM),
+            counts, stride, edges)
+
     def across_extremes_windows_host(self, records_list, begins, counts, k, stride=1, has_count=False):
         """-> (records, off): the k largest and the k smallest of the samples that the streams of records_list (at most
         ACROSS_MAX_STREAMS decoded record streams, as across_windows_host takes them) hold at every `stride`-th position
@@ -1113,6 +1140,21 @@ class DPlan:
         _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, m, levels, method,
                     q=_ACROSS_QUANTILE)
         return d_out.reshape(-1)[: m * n_q].reshape(m, n_q), off
+
+    def across_histogram_windows(self, d_body, others, other_bodies, begins, counts, edges, d_out, stride=1,
+                                 closed=capi.HIST_LEFT_CLOSED, stream=0):
+        """Enqueues, for every `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), how many of this
+        plan's stream and the plans `others` (their device bytes other_bodies) hold a sample in each value bin into
+        d_out, a uint64 (or int64) device tensor of at least n_edges + 2 elements per position, position-major
+        (atsc_across_histogram_windows_dev).  A plan may appear more than once.  -> (rows, off): the
+        (records, n_edges + 2) view of d_out's front, filled once `stream` has run, and the ranges' record offsets
+        (across_offsets)"""
+        off = across_offsets(counts, stride)
+        m, rows = int(off[-1]), len(_levels(edges)[0]) + 2
+        assert d_out.element_size() == 8
+        _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, m, edges, closed,
+                    q=_ACROSS_HISTOGRAM)
+        return d_out.reshape(-1)[: m * rows].reshape(m, rows), off
 
     def across_extremes_windows(self, d_body, others, other_bodies, begins, counts, k, d_out, stride=1, stream=0):
         """Enqueues the k largest and the k smallest of the samples that this plan's stream (stream 0) and the plans

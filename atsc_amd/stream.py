@@ -14,6 +14,7 @@ from .engine import _ROLLING_QUANTILE, _rolling_quantile_result
 from .engine import _ROLLING_HISTOGRAM, _rolling_histogram_result
 from .engine import _ACROSS_EXTREMES, _across_extremes_result
 from .engine import _ACROSS_MOMENTS, _across_moments_result
+from .engine import _ACROSS_HISTOGRAM, _across_histogram_result
 
 
 def _f64(x):
@@ -224,6 +225,13 @@ class CompressedStream:
         return _across_quantile_result(
             lambda m: self._across_stream(_ACROSS_QUANTILE, others, begins, counts, stride, m, levels, method), counts, stride, levels)
 
+    def across_histogram_windows(self, others, begins, counts, edges, stride=1, closed=capi.HIST_LEFT_CLOSED):
+        """-> (rows, off): how many of this stream and the streams `others` hold a sample in each value bin at every
+        `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), as
+        Context.across_histogram_windows_host gives them (atsc_stream_across_histogram_windows)"""
+        return _across_histogram_result(
+            lambda m: self._across_stream(_ACROSS_HISTOGRAM, others, begins, counts, stride, m, edges, closed), counts, stride, edges)
+
     def across_extremes_windows(self, others, begins, counts, k, stride=1):
         """-> (records, off): the k largest and the k smallest of the samples that this stream (stream 0) and the streams
         `others` (stream 1 and on) hold at every `stride`-th position of the ranges [begins[i], begins[i] + counts[i]),
@@ -411,6 +419,16 @@ def across_quantile_data_windows(ctx, bros, begins, counts, levels, stride=1, me
     return _across_quantile_result(
         lambda m: _across_host(ctx, records, begins, counts, True, stride, m, levels, method, q=_ACROSS_QUANTILE), counts, stride,
         levels)
+
+
+def across_histogram_data_windows(ctx, bros, begins, counts, edges, stride=1, closed=capi.HIST_LEFT_CLOSED):
+    """-> (rows, off): how many of the streams decompress_data(ctx, bro) of every .bro image of the list `bros` hold a
+    sample in each value bin at every `stride`-th position of the ranges, as Context.across_histogram_windows_host gives
+    them: atsc_bro_open of each image, then atsc_across_histogram_windows over their records"""
+    records = _across_images(bros)
+    return _across_histogram_result(
+        lambda m: _across_host(ctx, records, begins, counts, True, stride, m, edges, closed, q=_ACROSS_HISTOGRAM), counts, stride,
+        edges)
 
 
 def across_extremes_data_windows(ctx, bros, begins, counts, k, stride=1):

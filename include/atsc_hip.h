@@ -1355,6 +1355,54 @@ int atsc_histogram_windows(atsc_ctx *ctx, const uint8_t *body, uint64_t body_len
  * overflow bin (bin n_bins + 1 of the row) under ATSC_HIST_LEFT_CLOSED. */
 int atsc_histogram_edges_uniform(double lo, double hi, uint32_t n_bins, double *edges);
 
+/* Windowed across histograms: at every position of ranges of the decoded streams, how many of the N streams of a call
+ * hold a sample in each value bin -- a fleet heat map (how many of a job's 64 replicas sit in each latency band at every
+ * step), `count by (job)(x > 0.9)` (one edge), an SLO's "at least 60 of 64 hosts under 200 ms" (one `le` bucket) --
+ * without the decoded samples leaving the library and without one 1-sample window per position and stream.
+ *   Ranges     atsc_across_windows' exactly: n_streams in 1 .. ATSC_ACROSS_MAX_STREAMS, one stride for the call, range i
+ *              has atsc_across_outputs(count[i], stride) positions, rows are numbered range after range in the across'
+ *              record order.  The same plan may appear in the list more than once; all plans belong to one context.
+ *   Edges      edges[0 .. n_edges), closed and their validation are atsc_histogram_windows': n_edges in
+ *              1 .. ATSC_HIST_MAX_EDGES, strictly ascending as values, no NaN edge, +-Inf allowed; closed is
+ *              ATSC_HIST_LEFT_CLOSED or ATSC_HIST_RIGHT_CLOSED.
+ *   Result     n_edges + 2 u64 counters per position, in the histograms' layout (bins 0 .. n_edges, then NaN): with
+ *              m_i = atsc_across_outputs(count[i], stride), row j of range i is at
+ *              out[(m_0 + .. + m_(i-1) + j) * (n_edges + 2)].  positions x (n_edges + 2) must be below 2^32 - 1, so that
+ *              a counter's index fits 32 bits.  The caller sizes the result: sum m_i x (n_edges + 2) x 8 bytes.  The
+ *              call writes every counter of every row: the caller does not have to clear the result.
+ *   Row        The counter of bin b is the number of streams k whose sample at the position has bin b by the histograms'
+ *              rule: -0.0 equals +0.0, +-Inf samples are counted like any value, NaN samples are counted apart in the
+ *              last counter.  A row's counters sum to n_streams.
+ *   A row depends on the N samples of its position, the edges and closed alone: not on the order of the list, the range
+ *   that reached the position, the stride, the other ranges, the budget, the piece boundaries, the framing, or which of
+ *   the three forms (device, host, stream) was called.  It follows that
+ *              - with n_streams == 1 the row is atsc_histogram_windows' row of the window (position, 1), byte for byte;
+ *              - for any N the row is the sum over k of those rows of the streams;
+ *              - the NaN counter equals n_streams - atsc_across_windows' count at that position;
+ *              - the rows of sub-lists add to the row of the whole list: a list of more than ATSC_ACROSS_MAX_STREAMS
+ *                streams is queried that way, with plain integer addition (there is no merge function).
+ * Errors: ATSC_E_INVALID with nothing written and before any GPU work for every case of atsc_across_windows, for every
+ * case of atsc_histogram_windows' edge checks (null edges, n_edges == 0 or above ATSC_HIST_MAX_EDGES, a NaN edge, edges
+ * not strictly ascending, an unknown closed), for positions x (n_edges + 2) >= 2^32 - 1 (the message says so), a result
+ * pointer that is not 8-byte aligned.  The messages name across_histogram_windows.  n_windows == 0 and empty ranges
+ * write nothing.  Scratch and pieces are the across': there is no ATSC_E_CAPACITY case. */
+/* dp / d_body (n_streams entries each), begin / count and edges are HOST arrays; d_body[k] and d_out are device memory
+ * (d_out 8-byte aligned, 8 (n_edges + 2) bytes per position).  Enqueued on `stream`, not synchronised.  A malformed
+ * payload in a frame of stream k that a range touches sets dp[k]'s status word.  dp[0] keeps the call's tables and scratch
+ * in the place of the across quantiles', which the across extremes and moments share: the next across histogram, across
+ * moments, across extremes or across quantile call whose first plan is dp[0] waits (host side) until this one's work is
+ * done; atsc_dplan_destroy frees them. */
+int atsc_across_histogram_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                      const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                      const uint64_t *count, uint64_t stride, uint32_t n_edges, const double *edges,
+                                      int closed, uint64_t *d_out, void *stream);
+/* Host bytes in (n_streams bodies, lengths and has_count flags), host rows out, synchronous; walks and uploads only the
+ * touched records of every stream, as atsc_across_windows does, and computes the device call's bytes.  ATSC_E_FORMAT
+ * (nothing written) for a malformed payload in a frame of any stream that a range touches. */
+int atsc_across_histogram_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                                  const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                  uint64_t stride, uint32_t n_edges, const double *edges, int closed, uint64_t *out);
+
 /* ------------------------------------------------------------------------ */
 /* CompressedStream mirror (atsc/src/data.rs:29-110)                          */
 /* ------------------------------------------------------------------------ */
@@ -1445,6 +1493,11 @@ int atsc_stream_across_extremes_windows(atsc_stream *const *streams, uint32_t n_
 int atsc_stream_across_moments_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
                                        const uint64_t *begin, const uint64_t *count, uint64_t stride,
                                        atsc_across_moments *out);
+/* atsc_across_histogram_windows over the frames of the n_streams streams of the list, which must belong to one context
+ * (else ATSC_E_INVALID) */
+int atsc_stream_across_histogram_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                         const uint64_t *begin, const uint64_t *count, uint64_t stride, uint32_t n_edges,
+                                         const double *edges, int closed, uint64_t *out);
 /* atsc_quantile_windows over the stream's frames */
 int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint32_t n_q, const double *q, int method, double *out);
