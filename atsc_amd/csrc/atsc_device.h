@@ -295,6 +295,28 @@ DEVI double dpp_f64_full(double v)
     const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
 }
+// f32 sum across the wavefront, one add per step where the f64 sum pays two moves and an add.  Every value goes
+// through at most six additions; the order is the f64 sum's.
+template <int CTRL, int ROWMASK>
+DEVI float dpp_f32(float v)  // lanes without a source read 0
+{
+    return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), CTRL, ROWMASK, 0xf, false));
+}
+template <int CTRL>
+DEVI float dpp_f32_full(float v)
+{
+    return __uint_as_float((uint32_t)__builtin_amdgcn_mov_dpp((int)__float_as_uint(v), CTRL, 0xf, 0xf, true));
+}
+DEVI float wave_sum_f32(float v)
+{
+    v += dpp_f32_full<0xb1>(v);
+    v += dpp_f32_full<0x4e>(v);
+    v += dpp_f32_full<0x124>(v);
+    v += dpp_f32_full<0x128>(v);
+    v += dpp_f32<0x142, 0xa>(v);
+    v += dpp_f32<0x143, 0xc>(v);
+    return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), 63));
+}
 DEVI double wave_sum_f64(double v)
 {
     v += dpp_f64_full<0xb1>(v);
@@ -527,6 +549,25 @@ DEVI uint32_t mod_magic(uint32_t x, uint32_t L, uint32_t magic)
     uint32_t r = x - __umulhi(x, magic) * L;
     if (r >= L) r += L;
     return r;
+}
+// a * b mod L for a compile-time L and a * b < XMAX <= 2^15, at full rate: 24-bit multiplies and a 22-bit reciprocal
+// (mod_magic's three 32-bit multiplies run at a quarter of it).  Exact over the whole range, checked when compiled.
+template <uint32_t L, uint32_t XMAX>
+constexpr bool mod_small_exact()
+{
+    constexpr uint32_t R = ((1u << 22) + L - 1) / L;
+    for (uint32_t x = 0; x < XMAX; ++x)
+        if (((x * R) >> 22) != x / L) return false;
+    return true;
+}
+template <uint32_t L, uint32_t XMAX>
+DEVI uint32_t mod_small(uint32_t a, uint32_t b)
+{
+    static_assert(XMAX <= (1u << 15) && L >= 2 && L < (1u << 15), "the products fit 32 bits");
+    static_assert(mod_small_exact<L, XMAX>(), "the 22-bit reciprocal is exact over the range");
+    constexpr uint32_t R = ((1u << 22) + L - 1) / L;
+    const uint32_t x = __umul24(a, b);
+    return x - __umul24(__umul24(x, R) >> 22, L);
 }
 // a / d for small non-negative integers a <= d <= 4096 (spline parameter r / gap), correctly
 // rounded: q = a*y with y = RN(1/d), one FMA residual step.  Checked exhaustively for all pairs.

@@ -315,8 +315,11 @@ __device__ unsigned long long g_phase_cyc[64 * 16];
 __device__ unsigned long long g_frame_span[4 * 65536 * 3];  // wall clock (100 MHz) at a frame's start and end, by launch slot; HW_ID | XCC_ID << 32
 #define PH(i) do { if (FN != 0) { const long long now_ = clock64(); \
     if (tid == 0) atomicAdd(&ph_acc[i], (unsigned long long)(now_ - ph_t)); ph_t = clock64(); } } while (0)
+// a count instead of cycles (rows 13, 14: ladder trips evaluated exactly / decided by the error screen)
+#define PHN(i) do { if (FN != 0 && tid == 0) atomicAdd(&ph_acc[i], 1ull); } while (0)
 #else
 #define PH(i) do {} while (0)
+#define PHN(i) do {} while (0)
 #endif
 // one-wavefront frames of the 256-sample class: ask for 6 wavefronts per SIMD (<= 80 VGPRs).
 // FN != 0: every frame of the launch has FN samples (FN >= 128, even transform length) and the frame
@@ -1359,9 +1362,42 @@ __device__ __forceinline__ void compress_frame(
             const uint32_t magicL = FIX ? (uint32_t)(0x100000000ull / (FIX ? cL : 1)) + 1u : P.magicL;
             uint32_t used = 0, jump = 0, big = 0;
             double cur = prm.max_err + 1.0;
-            // bounded: fft.rs:334 loop.  Unbounded (FFT::compress, fft.rs:366-388): one pass that only
+            // The error screen of the fixed-length one-wavefront ladders ("The ladder's error
+            // screen").  Nearly every trip fails, and all a failing trip's f64 evaluation yields is the bit "go on".
+            // An f32 estimate Q of the mean error is within B = scr_abs + 2^-20 Q of the exact `cur`; a trip whose
+            // Q - B clears the exit threshold scr_thr fails for certain and skips the f64 evaluation and its sum.
+            // Every other trip -- in the band, passing, the trip at the cap -- is evaluated as before, so the `cur`
+            // of the trip that ends the loop is the exact one.  A skipped trip leaves `cur` stale, which only a
+            // pruned ladder hands on (fft_err), and nothing reads that: fft_done is off, so no offer, and FFT cannot
+            // be chosen; the fixed-length instantiations keep no diagnostics record.
+            // Non-finite values need no test of their own: scr_abs carries the mean of 1 / |g|, which is Inf or NaN
+            // when a sample is zero or NaN, an Inf or NaN in acc[] (finite samples below 1e30 give a finite
+            // spectrum, so only a NaN sample gets one there) makes Q Inf or NaN only together with a NaN 1 / |g|: the
+            // limit is +Inf or NaN, the compare is false and the trip is evaluated exactly.
+            constexpr bool SCREEN = FIX && W == 1;
+            float scr_lim = 0.0f;  // Q (1 - 2^-18) above it: the trip fails (one scalar register)
+            const float invLf = 1.0f / (float)(FIX ? cL : 1);
+            if constexpr (SCREEN) {
+                float si = 0.0f;
+#pragma unroll
+                for (int m = 0; m < SPL; ++m) si += (float)inv[m];
+                // |o - clamp(v)| <= 5e-6 (the rounding) + 2^-52 max(|min|, |max|) (the division's own rounding)
+                const float delta = 5.0005e-6f + 0x1p-51f * fmaxf(fabsf(mnf), fabsf(mxf));
+                const float scr_abs = delta * (wave_sum_f32(si) * invLf) + 0x1p-23f;
+                // the loop goes on iff fl(cur * 1000) >= max_err_m + 1 (max_err_m + 1 <= 0: always); a bound so
+                // large that max_err_m + 1 could saturate is never screened
+                const float scr_thr = prm.max_err_m < (1 << 30) ? fmaxf((float)prm.max_err_m + 1.0f, 0.0f) * 1.0e-3f
+                                                                : __builtin_inff();
+                // (1.001: every rounding of this block, upwards.  A limit from 1e30 is no limit: below it, a Q that
+                // overflowed stands for a mean of 1e36 and more, far beyond the band and the threshold)
+                const float lim = (scr_abs + scr_thr) * 1.001f;
+                scr_lim = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane(
+                    (int)__float_as_uint(lim < 1e30f ? lim : __builtin_inff())));
+            }
+            // bounded: fft.rs:334 loop. Unbounded (FFT::compress, fft.rs:366-388): one pass that only
             // admits the max(3, n/100) largest bins; nothing is reconstructed or measured.
-            while (bounded ? (prm.max_err_m < sat_i32(cur * 1000.0)) : (fft_trips == 0)) {
+            bool scr_fail = false;  // the screen decided the last trip: it failed, `cur` was not computed
+            while (bounded ? (scr_fail || prm.max_err_m < sat_i32(cur * 1000.0)) : (fft_trips == 0)) {
                 const uint32_t K = min(mf + jump, Z);
                 if (prune && !can_win(1 + vlen(K) + 9 * K + 8, 0)) { fft_pruned = true; break; }
                 ++fft_trips;
@@ -1522,7 +1558,9 @@ __device__ __forceinline__ void compress_frame(
                     if (pos == 0) {
                         dc = a;
                     } else {
-                        uint32_t idx = mod_magic(pos * tid, L, magicL);
+                        uint32_t idx;
+                        if constexpr (SCREEN) idx = mod_small<cL, 64u * (cL / 2 + 1)>(pos, tid);  // pos <= L / 2, tid < 64
+                        else idx = mod_magic(pos * tid, L, magicL);
                         const uint32_t stp = mod_magic(pos * (uint32_t)T, L, magicL);
 #pragma unroll
                         for (int m = 0; m < SPL; ++m) {
@@ -1538,26 +1576,46 @@ __device__ __forceinline__ void compress_frame(
                 }
                 PH(7);
                 if (!bounded) { cur = 0.0; break; }
-                double s = 0.0;
-                // fft.rs:208-218.  v is an f32, so v * 1e5 is exact (<= 41 significant bits) and
-                // round-half-away equals trunc(x + copysign(0.5, x)) (checked over the f32 range)
-                if (__builtin_expect(fast_clamp, 1)) {
-                    // every o is finite, and the lanes beyond L carry g = 1, 1/|g| = 0: no guard
+                if constexpr (SCREEN) {
+                    scr_fail = false;
+                    if (fast_clamp && fft_trips <= 22) {  // (the trip at the cap hands its `cur` on)
+                        // Q = sum |clamp(v) - (float)g| (float)(1 / |g|) / L: v is the f32 the exact side converts,
+                        // the bounds are f32 values (v_med3_f32 is the clamp), a lane beyond L weighs 0
+                        float s32 = 0.0f;
 #pragma unroll
-                    for (int m = 0; m < SPL; ++m) {
-                        const double x5 = (double)(acc[m] + dc) * 100000.0;
-                        double o = div1e5(trunc(x5 + copysign(0.5, x5)));
-                        o = fmin(fmax(o, mnd), mxd);
-                        s += fabs(o - g[m]) * inv[m];  // utils/error.rs:104-116
+                        for (int m = 0; m < SPL; ++m) {
+                            // (g and 1 / |g| are converted here, trip by trip: f32 copies kept across the ladder
+                            // are ten registers the kernel does not have)
+                            asm volatile("" : "+v"(g[m]), "+v"(inv[m]));
+                            s32 += fabsf(__builtin_amdgcn_fmed3f(acc[m] + dc, mnf, mxf) - (float)g[m]) * (float)inv[m];
+                        }
+                        const float q = wave_sum_f32(s32) * invLf;
+                        scr_fail = q * (1.0f - 0x1p-18f) > scr_lim;  // (false for NaN)
                     }
-                } else {
-#pragma unroll
-                    for (int m = 0; m < SPL; ++m) {
-                        if (tid + m * T < L) s += fft_term_slow(acc[m] + dc, mnd, mxd, g[m]);
-                    }
+                    PHN(scr_fail ? 14 : 13);
                 }
-                s = block_sum_f64<W>(s, red, parity);
-                cur = s * invL;  // mean over the L padded samples (utils/error.rs:115); 1/L rounded once
+                if (!scr_fail) {
+                    double s = 0.0;
+                    // fft.rs:208-218.  v is an f32, so v * 1e5 is exact (<= 41 significant bits) and
+                    // round-half-away equals trunc(x + copysign(0.5, x)) (checked over the f32 range)
+                    if (__builtin_expect(fast_clamp, 1)) {
+                        // every o is finite, and the lanes beyond L carry g = 1, 1/|g| = 0: no guard
+#pragma unroll
+                        for (int m = 0; m < SPL; ++m) {
+                            const double x5 = (double)(acc[m] + dc) * 100000.0;
+                            double o = div1e5(trunc(x5 + copysign(0.5, x5)));
+                            o = fmin(fmax(o, mnd), mxd);
+                            s += fabs(o - g[m]) * inv[m];  // utils/error.rs:104-116
+                        }
+                    } else {
+#pragma unroll
+                        for (int m = 0; m < SPL; ++m) {
+                            if (tid + m * T < L) s += fft_term_slow(acc[m] + dc, mnd, mxd, g[m]);
+                        }
+                    }
+                    s = block_sum_f64<W>(s, red, parity);
+                    cur = s * invL;  // mean over the L padded samples (utils/error.rs:115); 1/L rounded once
+                }
                 PH(8);
                 if (fft_trips <= 17) jump += dk1;       // fft.rs:348-352
                 else if (fft_trips <= 22) jump += dk2;

@@ -45,6 +45,9 @@ for klass in ((None, 0, 1, 2, 3) if F == 256 else (None,)):
     print("class %s: %.0f cycles per frame" % (klass, tot))
     for nm, c in zip(NAMES, cyc):
         print("   %-26s %8.0f  %5.1f %%" % (nm, c, 100.0 * c / tot))
+    # rows 13 / 14 are counts, not cycles: ladder trips per frame by how their exit test was decided
+    print("   ladder trips per frame: %.2f evaluated exactly, %.2f decided by the f32 error screen" % (
+        buf[13] / (reps * float(NF)), buf[14] / (reps * float(NF))))
 
 # occupancy over time of the last launch: frames in flight at every 1 us tick (wall clock, 100 MHz)
 L.atsc_dev_span_read.restype = C.c_int
