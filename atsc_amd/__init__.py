@@ -28,6 +28,8 @@ from .engine import ACROSS_FIT, ACROSS_MOMENTS, across_moments_fit, across_momen
 from .stream import across_moments_data_windows  # noqa: F401
 from .stream import across_histogram_data_windows  # noqa: F401
 from .engine import WINDOW_PAIR, WINDOW_PAIR_FIT, pair_fit  # noqa: F401
+from .engine import pair_matrix_correlation, pair_matrix_index, pair_matrix_records  # noqa: F401
+from .stream import pair_matrix_data_windows  # noqa: F401
 from .stream import select_data_windows  # noqa: F401
 from .engine import (WINDOW_DELTA, WINDOW_DELTA_FIT, WINDOW_FIT, WINDOW_MOMENTS, WINDOW_RUNS, WINDOW_STATS, Context, DPlan, Plan,  # noqa: F401
                      bro_find_window, bro_open, bro_prefix, bucket_windows, chunk_sizes, clean_data, delta_derive,

@@ -115,6 +115,10 @@ SIGNATURES = {
     "atsc_pair_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p,
                                     _vp]),
     "atsc_pair_fit": (C.c_int, [_vp, C.c_uint64, _vp]),
+    "atsc_pair_matrix_records": (C.c_uint64, [C.c_uint32]),
+    "atsc_pair_matrix_index": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "atsc_pair_matrix_windows_dev": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint64, _u64p, _u64p, _vp, _vp]),
+    "atsc_pair_matrix_windows": (C.c_int, [_vp, C.c_uint32, _vp, _u64p, _i32p, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_delta_windows_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p, _u64p, _vp, _vp]),
     "atsc_delta_windows": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_int, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_delta_derive": (C.c_int, [_vp, C.c_uint64, _vp]),
@@ -200,6 +204,7 @@ SIGNATURES = {
     "atsc_stream_aggregate_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_moments_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_pair_windows": (C.c_int, [_vp, _vp, C.c_uint64, _u64p, _u64p, _vp]),
+    "atsc_stream_pair_matrix_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_delta_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, _vp]),
     "atsc_stream_runs_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_int, C.c_double, _vp]),
     "atsc_stream_extremes_windows": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp]),

@@ -4,7 +4,7 @@
 //   atsc [--compressor auto|noop|fft|constant|polynomial|idw|rle] [-e 0..50] [-u [--samples BEGIN:COUNT] [--buckets N
 //        [--quantiles Q,Q,.. [--quantile-method linear|lower|higher|nearest]]
 //        [--histogram E,E,..|LO:HI:N [--histogram-closed left|right]] [--moments] [--deltas] [--runs OP:LIMIT] [--extremes K] [--values K[:ABOVE]]
-//        [--pair OTHER.bro]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments] [--rolling-runs OP:LIMIT]
+//        [--pair OTHER.bro | --pair-matrix A.bro,B.bro,..]] [--where OP:LIMIT] [--rolling W[:S] [--rolling-deltas] [--rolling-moments] [--rolling-runs OP:LIMIT]
 //        [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]] [--rolling-pair OTHER.bro]
 //        [--rolling-histogram E,E,..|LO:HI:N]]
 //        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]
@@ -71,6 +71,11 @@ void usage()
             "                                 the same sample indices (OTHER must reach the bucketed range's end), as the last\n"
             "                                 columns: pair_count (samples where neither value is NaN), covariance (population\n"
             "                                 form), correlation, and slope and intercept of OTHER's value on this file's\n"
+            "      --pair-matrix <A.bro,B.bro,..>  with --buckets, without --pair: also the pair moments of every pair of this file\n"
+            "                                 (stream 0) and the listed files (streams 1.., at most 63; each must reach the\n"
+            "                                 bucketed range's end) over every bucket, one row per (bucket, i, j), i <= j, to\n"
+            "                                 .pairs.csv: bucket,begin,count,i,j,pair_count,mean_i,mean_j,covariance,correlation,\n"
+            "                                 slope,intercept (of stream j's value on stream i's; i == j: the stream's own moments)\n"
             "      --values <K[:ABOVE]>       with --buckets: also every bucket's K smallest distinct values (K: 1..32) and how often\n"
             "                                 each occurs, as the last columns: nans, below, distinct, more, v1, n1 .. vK, nK\n"
             "                                 (values ascending, -0.0 counted with 0.0; with ABOVE only values greater than it\n"
@@ -181,7 +186,14 @@ int write_buckets(atsc_ctx *ctx, const std::string &path, const Args &a, const u
         }
         bucket_row(f, std::to_string(b[k]), a.q, r, k, at);
     }
-    return fclose(f) == 0 ? ATSC_OK : ATSC_E_IO;
+    if (fclose(f) != 0) return ATSC_E_IO;
+    if (a.q.pair_matrix.empty()) return ATSC_OK;
+    // --pair-matrix: beside the .agg.csv, every pair's row of every bucket
+    std::vector<atsc_window_pair> recs;
+    uint32_t n_streams = 0;
+    const int rcm = pair_matrix_query(ctx, bro, len, a.q, nb, b.data(), c.data(), recs, &n_streams);
+    if (rcm) return rcm;
+    return pair_matrix_write(with_ext(path, "pairs.csv"), nb, b.data(), c.data(), n_streams, recs) ? ATSC_OK : ATSC_E_IO;
 }
 
 int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)

@@ -71,6 +71,7 @@ struct BucketOptions {
     double values_above = std::nan("");  // NaN: every value is listed
     bool pair_allowed = false;  // the front end takes --pair (atsc; csv-compressor does not: DESIGN.md "Windowed pair moments")
     std::string pair;           // --pair OTHER.bro: pair_count,covariance,correlation,slope,intercept against that stream
+    std::vector<std::string> pair_matrix;  // --pair-matrix A.bro,B.bro,.. (where pair_allowed): every pair's row per bucket into .pairs.csv
     bool have_where = false;  // --where OP:LIMIT: no bucket query; the window's selected samples into .sel.csv
     int where_op = ATSC_RUNS_GT;
     double where_limit = 0.0;
@@ -233,7 +234,7 @@ bool parse_across(const std::string &v, std::vector<std::string> &files)
     }
 }
 
-// --pair OTHER.bro, --across and --across-stride are taken only where the front end allows them (o.pair_allowed,
+// --pair OTHER.bro, --pair-matrix, --across and --across-stride are taken only where the front end allows them (o.pair_allowed,
 // o.across_allowed).
 // One argument of the command line, where it is a bucket-query option.  s: the argument; value(name): whether s is the
 // option `name` with a value, which it leaves in v (the callers' lambda).  0: none of them; 1: taken; 2: a usage error,
@@ -335,6 +336,12 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
             return 2;
         }
         o.pair = v;
+    } else if (o.pair_allowed && value("--pair-matrix")) {
+        if (!parse_across(v, o.pair_matrix)) {
+            fprintf(stderr, "error: invalid value '%s' for '--pair-matrix': expected 1..=%d paths of .bro files, comma separated\n",
+                    v.c_str(), (int)ATSC_ACROSS_MAX_STREAMS - 1);
+            return 2;
+        }
     } else if (o.pair_allowed && value("--rolling-pair")) {
         if (v.empty()) {
             fprintf(stderr, "error: invalid value '' for '--rolling-pair': expected the path of a .bro file\n");
@@ -404,12 +411,18 @@ bool bucket_options_complete(const BucketOptions &o, const char *bucketing, bool
              {o.have_runs, given, "--runs", bucketing},
              {o.extremes != 0, given, "--extremes", bucketing},
              {o.values != 0, given, "--values", bucketing},
-             {!o.pair.empty(), given, "--pair", bucketing}};
+             {!o.pair.empty(), given, "--pair", bucketing},
+             {!o.pair_matrix.empty(), given, "--pair-matrix", bucketing}};
     for (const auto &t : T)
         if (t.have && !t.needed) {
             fprintf(stderr, "error: '%s' needs '%s'\n", t.name, t.needs);
             return false;
         }
+    // (--pair's columns are the matrix' pair (0, 1) of that file: one or the other)
+    if (!o.pair_matrix.empty() && !o.pair.empty()) {
+        fprintf(stderr, "error: '--pair-matrix' cannot be used with '--pair'\n");
+        return false;
+    }
     return true;
 }
 
@@ -973,6 +986,62 @@ bool across_write(const std::string &path, const std::vector<atsc_across_record>
             for (size_t b = 0; b < n_hist; ++b) fprintf(f, ",%llu", (unsigned long long)(*hist)[j * n_hist + b]);
         fprintf(f, "\n");
     }
+    return fclose(f) == 0;
+}
+
+// --pair-matrix: the pair moments of every pair of the .bro image (stream 0) and the listed files (stream 1 and on) over
+// the nb buckets (b, c): sample i of each goes with sample i of the others, and a file that ends before a bucket fails
+// as --pair's does.  recs: nb rows of atsc_pair_matrix_records(*n_streams) records.
+int pair_matrix_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t nb, const uint64_t *b,
+                      const uint64_t *c, std::vector<atsc_window_pair> &recs, uint32_t *n_streams)
+{
+    std::vector<uint8_t *> image(o.pair_matrix.size(), nullptr);
+    std::vector<const uint8_t *> body{bro + 9};
+    std::vector<uint64_t> body_len{len - 9};
+    int rc = ATSC_OK;
+    for (size_t k = 0; k < o.pair_matrix.size() && !rc; ++k) {
+        uint64_t n = 0;
+        rc = atsc_bro_read_file(o.pair_matrix[k].c_str(), &image[k], &n);
+        if (!rc && !image[k]) rc = ATSC_E_FORMAT;  // not a BRO file
+        if (!rc) rc = atsc_bro_open(image[k], n, nullptr, nullptr);
+        if (rc) break;
+        body.push_back(image[k] + 9);
+        body_len.push_back(n - 9);
+    }
+    if (!rc) {
+        const std::vector<int> has_count(body.size(), 1);
+        *n_streams = (uint32_t)body.size();
+        recs.assign(nb * atsc_pair_matrix_records(*n_streams), atsc_window_pair{});
+        atsc_window_pair none;
+        rc = atsc_pair_matrix_windows(ctx, *n_streams, body.data(), body_len.data(), has_count.data(), nb, b, c,
+                                      recs.empty() ? &none : recs.data());
+    }
+    for (uint8_t *p : image) atsc_free(p);
+    return rc;
+}
+
+// the .pairs.csv: bucket,begin,count,i,j,pair_count,mean_i,mean_j,covariance,correlation,slope,intercept and one row per
+// (bucket, i, j), i <= j, in the records' order: the bucket's number, first sample and length, the two streams' places in
+// the list (the input file 0), the record's count and means and what atsc_pair_fit reads off it (the slope and intercept
+// of stream j on stream i); values as the .agg.csv writes them.  false: the file could not be written.
+bool pair_matrix_write(const std::string &path, uint64_t nb, const uint64_t *b, const uint64_t *c, uint32_t n_streams,
+                       const std::vector<atsc_window_pair> &recs)
+{
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return false;
+    fprintf(f, "bucket,begin,count,i,j,pair_count,mean_i,mean_j,covariance,correlation,slope,intercept\n");
+    const uint64_t P = atsc_pair_matrix_records(n_streams);
+    for (uint64_t k = 0; k < nb; ++k)
+        for (uint32_t i = 0; i < n_streams; ++i)
+            for (uint32_t j = i; j < n_streams; ++j) {
+                const atsc_window_pair &p = recs[k * P + atsc_pair_matrix_index(n_streams, i, j)];
+                atsc_window_pair_fit pf;
+                atsc_pair_fit(&p, 1, &pf);
+                fprintf(f, "%llu,%llu,%llu,%u,%u,%llu,%s,%s,%s,%s,%s,%s\n", (unsigned long long)k, (unsigned long long)b[k],
+                        (unsigned long long)c[k], i, j, (unsigned long long)p.count, debug_f64(p.mean_x).c_str(),
+                        debug_f64(p.mean_y).c_str(), debug_f64(pf.covariance).c_str(), debug_f64(pf.correlation).c_str(),
+                        debug_f64(pf.slope).c_str(), debug_f64(pf.intercept).c_str());
+            }
     return fclose(f) == 0;
 }
 

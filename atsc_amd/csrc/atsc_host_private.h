@@ -97,8 +97,8 @@ void pool_free(atsc_ctx *ctx, void *p);
 // staging `h` and the device copy `d`, which the call's device-only tables follow -- its scratch of decoded samples, and
 // the event that marks the end of its work.  A plan holds one per kind of query, so that a call waits only for the
 // previous call of its own kind (atsc_dplan::res, by QueryKind).  A call over several plans (Q_PAIR, Q_ACROSS,
-// Q_ACROSS_QUANTILE) keeps everything on its first plan's.
-enum QueryKind { Q_WINDOW, Q_AGGREGATE, Q_QUANTILE, Q_HISTOGRAM, Q_MOMENTS, Q_DELTA, Q_RUNS, Q_EXTREMES, Q_SELECT, Q_PAIR, Q_ROLLING, Q_ACROSS, Q_ACROSS_QUANTILE, Q_KINDS };
+// Q_ACROSS_QUANTILE, Q_PAIR_MATRIX) keeps everything on its first plan's.
+enum QueryKind { Q_WINDOW, Q_AGGREGATE, Q_QUANTILE, Q_HISTOGRAM, Q_MOMENTS, Q_DELTA, Q_RUNS, Q_EXTREMES, Q_SELECT, Q_PAIR, Q_ROLLING, Q_ACROSS, Q_ACROSS_QUANTILE, Q_PAIR_MATRIX, Q_KINDS };
 struct QueryRes {
     unsigned char *h = nullptr, *d = nullptr;
     size_t h_cap = 0, d_cap = 0;

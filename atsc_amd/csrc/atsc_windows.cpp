@@ -1,5 +1,5 @@
 // atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms,
-// rolling windows, rolling deltas, rolling runs, rolling quantiles, rolling histograms and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams,
+// rolling windows, rolling deltas, rolling runs, rolling quantiles, rolling histograms and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams and of every pair of up to 64,
 // and count, min, max, sum, quantiles, extremes, moments and histograms across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
@@ -87,6 +87,12 @@ __attribute__((weak)) hipError_t launch_pair_tiles(const DevPosTile *tasks, uint
                                                    DevMomPart *part, hipStream_t s);
 __attribute__((weak)) hipError_t launch_pair_combine(const DevAggComb *tasks, uint32_t n, DevMomPart *part, void *out,
                                                      hipStream_t s);
+// the windowed pair matrix' reduce kernels (atsc_pair_matrix.hip; weak for the same reason); reg: where each stream's
+// region begins in the scratch; part_n: the nodes of one pair
+__attribute__((weak)) hipError_t launch_pmx_tiles(const DevPosTile *tasks, uint32_t n, const double *scratch, const uint64_t *reg,
+                                                  uint32_t n_streams, DevMomPart *part, uint64_t part_n, hipStream_t s);
+__attribute__((weak)) hipError_t launch_pmx_combine(const DevAggComb *tasks, uint32_t n, DevMomPart *part, uint64_t part_n,
+                                                    uint32_t n_streams, void *out, hipStream_t s);
 // the windowed rolling's pyramid and position kernels (atsc_rolling.hip; weak for the same reason)
 __attribute__((weak)) hipError_t launch_roll_pyramid(const double *scratch, uint32_t n_tiles, void *pyr, const DevRollPiece *pc,
                                                      uint32_t lmax, hipStream_t s);
@@ -411,7 +417,8 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_HISTOGRAM = DECODE_CALLER("histogram"), BY_MOMENTS = DECODE_CALLER("moments"),
                           BY_DELTA = DECODE_CALLER("delta"), BY_RUNS = DECODE_CALLER("runs"),
                           BY_EXTREMES = DECODE_CALLER("extremes"), BY_SELECT = DECODE_CALLER("select"),
-                          BY_PAIR = DECODE_CALLER("pair"), BY_VALUES = DECODE_CALLER("values"),
+                          BY_PAIR = DECODE_CALLER("pair"), BY_PAIR_MATRIX = DECODE_CALLER("pair matrix"),
+                          BY_VALUES = DECODE_CALLER("values"),
                           BY_ROLLING = DECODE_CALLER("rolling"), BY_ROLLING_DELTA = DECODE_CALLER("rolling delta"),
                           BY_ROLLING_MOMENTS = DECODE_CALLER("rolling moments"), BY_ROLLING_PAIR = DECODE_CALLER("rolling pair"),
                           BY_ROLLING_RUNS = DECODE_CALLER("rolling runs"),
@@ -763,17 +770,21 @@ static bool spans_touch_large(const atsc_dplan *dp, uint64_t org, const std::vec
 
 // Piece length in samples, a multiple of `unit`: the budget less the spills, spill[k] being the room for two large frames
 // of input k that cross the piece's ends (none when the covering intervals touch no large frame of it), shared evenly
-// by the n_in inputs' regions, and at least AGG_MIN_PIECE.  Without a budget every input has the default of its own.
+// by the n_in inputs' regions, and at least AGG_MIN_PIECE.  Without a budget every input has the default of its own, or
+// (one_default, the across' rule: a query over a list of streams) the inputs share the default of one.
 static uint64_t piece_samples(const atsc_ctx *ctx, const QueryInput *in, int n_in, const std::vector<Span> &cov,
-                              uint64_t unit, uint64_t *spill)
+                              uint64_t unit, uint64_t *spill, bool one_default = false)
 {
     uint64_t want = 0, spills = 0;
+    bool any_large = false;
     for (int k = 0; k < n_in; ++k) {
         const bool large = spans_touch_large(in[k].dp, in[k].org, cov);
         spills += spill[k] = large ? 2ull * MAX_FRAME : 0;
         want += scratch_budget_samples(ctx, large);
+        any_large = any_large || large;
     }
     if (ctx->agg_budget) want = ctx->agg_budget / sizeof(double);
+    else if (one_default) want = scratch_budget_samples(ctx, any_large);
     return std::max<uint64_t>(AGG_MIN_PIECE, want > spills ? (want - spills) / n_in / unit * unit : 0);
 }
 
@@ -887,7 +898,7 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
 // what reduce_dev does.  The front end's part:
 //   CALL                the call's name in the messages
 //   INPUTS              the streams the query reads: 1, or 2 (PairQuery) -- that many bodies, streams or plans; 0 where
-//                       the number is the call's own (AcrossQuery), which inputs() then gives (query_inputs)
+//                       the number is the call's own (AcrossQuery, PairMatrixQuery), which inputs() then gives (query_inputs)
 //   out_bytes(n)        bytes of the result of n windows
 //   check(ctx)          the check of the call's parameters (ctx may be null: then no message is kept)
 //   fill_empty(out, n)  the result of n empty windows
@@ -897,7 +908,8 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
 // deltas (atsc_delta.hip), the runs (atsc_runs.hip), the extremes (atsc_extremes.hip) and the value counts
 // (atsc_values.hip).
 //   Tile, tile(t, k)   the tile kernel's task, from the plan's DevAggTile of tile k of the stream
-//   tiles(.., scr, ..) the tile kernel's launch; scr[k]: input k's scratch region
+//   tiles(.., scr, ..) the tile kernel's launch; scr[k]: input k's scratch region (a query over a list, INPUTS == 0: the
+//                      scratch, the table of the regions' places and the number of partials, see reduce_dev)
 //   part()             bytes of a partial: a member call, so that a query may size its partials by a parameter of the
 //                      call (ExtQuery and ValQuery, by k); the others hand back their static PART
 //   SIDE               the table both kernels share beside the partials: the windows' first / last samples, which the
@@ -1264,9 +1276,66 @@ struct PairQuery {
     }
 };
 
-// The device call of a reduction over tiles (Q: AggQuery, MomQuery, DltQuery, RunQuery, ExtQuery, ValQuery or PairQuery;
+extern "C" uint64_t atsc_pair_matrix_records(uint32_t n_streams) { return (uint64_t)n_streams * ((uint64_t)n_streams + 1) / 2; }
+
+extern "C" uint64_t atsc_pair_matrix_index(uint32_t n_streams, uint32_t i, uint32_t j)
+{
+    if (i > j || j >= n_streams) return ~0ull;
+    return (uint64_t)i * (2ull * n_streams - i + 1) / 2 + (j - i);
+}
+
+// The pair matrix (atsc_pair_matrix.hip): the pair moments of every pair (i, j), i <= j, of a list of n_streams inputs.
+// The one reduction over a list (INPUTS == 0, see reduce_dev): its partial is a block of P = n_streams (n_streams + 1) / 2
+// of the pair's nodes, which the kernels keep pair-major (pair p's node of partial d at part[p part_n + d]); its kernels
+// make their grids from the tile tasks and the combine groups, so the host lists nothing per pair.  No side table, no
+// carry.  n_windows is a member for the check of the result's size.
+struct PairMatrixQuery {
+    static constexpr int INPUTS = 0;
+    using Tile = DevPosTile;
+    static constexpr const char *CALL = "pair_matrix_windows", *RES_NAME = "d_out", *NO_KERNELS = "no pair matrix kernels",
+                                *TILES = "launch k_pmx_tiles", *COMBINE = "launch k_pmx_combine";
+    static constexpr bool SIDE_BEGINS = false, NO_SIDE = true;
+    static constexpr bool CARRY = false;
+    static constexpr QueryKind KIND = Q_PAIR_MATRIX;
+    uint32_t n_streams;
+    uint64_t n_windows;
+    int inputs() const { return (int)n_streams; }
+    uint64_t pairs() const { return atsc_pair_matrix_records(n_streams); }
+    size_t part() const { return pairs() * sizeof(DevMomPart); }
+    static const DecodeCaller &who() { return BY_PAIR_MATRIX; }
+    static bool have() { return launch_pmx_tiles && launch_pmx_combine; }
+    static Tile tile(const DevAggTile &t, uint64_t k) { return pos_tile(t, k); }
+    static bool carried(const Tile &) { return false; }
+    hipError_t tiles(const Tile *t, uint32_t n, const double *scratch, const uint64_t *reg, void *part, uint64_t part_n,
+                     hipStream_t s) const
+    {
+        return launch_pmx_tiles(t, n, scratch, reg, n_streams, (DevMomPart *)part, part_n, s);
+    }
+    hipError_t combine(const DevAggComb *c, uint32_t n, void *part, uint64_t part_n, void *out, hipStream_t s) const
+    {
+        return launch_pmx_combine(c, n, (DevMomPart *)part, part_n, n_streams, out, s);
+    }
+    size_t out_bytes(uint64_t n) const { return n * pairs() * sizeof(atsc_window_pair); }
+    int check(atsc_ctx *ctx) const
+    {
+        if (n_streams == 0 || n_streams > ATSC_ACROSS_MAX_STREAMS) return fail_in(ctx, ATSC_E_INVALID, CALL, "n_streams outside [1, 64]");
+        if (n_windows > 0xfffffffeull / pairs()) return fail_in(ctx, ATSC_E_INVALID, CALL, "more than 2^32 - 2 records");
+        return ATSC_OK;
+    }
+    void fill_empty(void *out, uint64_t n) const { PairQuery::fill_empty(out, n * pairs()); }
+    // (the list's length and the result's size are checked in front of the arguments)
+    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n, const uint64_t *begin, const uint64_t *count, void *d_res,
+            void *stream) const
+    {
+        const int rc = check(ctx);
+        return rc ? rc : reduce_dev(ctx, in, n, begin, count, d_res, stream, *this);
+    }
+};
+
+// The device call of a reduction over tiles (Q: AggQuery, MomQuery, DltQuery, RunQuery, ExtQuery, ValQuery, PairQuery or
+// PairMatrixQuery;
 // the kernels named below are the aggregates').  q: the query's parameters of this call, where it has any (RunQuery,
-// ExtQuery, ValQuery).  in: the Q::INPUTS streams it reads, each a plan, its record bytes on the device and the stream index of
+// ExtQuery, ValQuery).  in: the query_inputs(q) streams it reads, each a plan, its record bytes on the device and the stream index of
 // the plan's first sample; begin[] counts from in[0].org.  Everything below is computed once, in the stream's index,
 // which the inputs share; per piece every input is decoded into a scratch region of its own, with its own decode tasks
 // and spill slots, and the tile kernel gets every region's pointer.  The call's tables, partials and regions are
@@ -1283,18 +1352,33 @@ struct PairQuery {
 // the launch that read the slot's previous value, in front of the next decode) takes the piece's last sample to the
 // carry slot in the call's tables.  The tile kernel never writes that slot.
 // A query whose kernels share no table beside the partials says so (PairQuery::NO_SIDE, ValQuery::NO_SIDE).
+// A query over a list of streams (INPUTS == 0: PairMatrixQuery, whose partial is a block of nodes, one per pair) reads
+// inputs() of them, at most MAX_INPUTS.  Its regions share one input's default budget, as the across' do (across_dev);
+// the regions' places in the scratch go up as a table, which the tile kernel gets with the scratch in place of the
+// list of pointers; and both kernels get the number of partials.  The geometry -- tiles, shared mid tiles, combine
+// passes -- does not look inside a partial and is the same.
 template <class Q, class = void>
 struct NoSide : std::false_type {};
 template <class Q>
 struct NoSide<Q, std::void_t<decltype(Q::NO_SIDE)>> : std::true_type {};
 
+// The streams a query reads: its INPUTS constant, or for a query over a runtime number of them (INPUTS == 0) the call's own.
+template <class Q>
+static int query_inputs(const Q &q)
+{
+    if constexpr (Q::INPUTS > 0) return Q::INPUTS;
+    else return q.inputs();
+}
+
 template <class Q>
 static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                       void *d_out, void *stream, const Q &q)
 {
-    constexpr int NI = Q::INPUTS;
-    static_assert(NI >= 1 && NI <= MAX_INPUTS, "one or two inputs");
+    constexpr bool LIST = Q::INPUTS == 0;
+    static_assert(Q::INPUTS <= 2, "one or two inputs, or a list");
     if (!ctx) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
+    const int NI = query_inputs(q);
+    if (NI < 1 || NI > MAX_INPUTS) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "n_streams outside [1, 64]");
     for (int k = 0; k < NI; ++k)
         if (!in[k].dp || (n_windows && !in[k].d_body)) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
     if (n_windows && (!begin || !count || !d_out)) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "null argument");
@@ -1314,8 +1398,8 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
     for (uint64_t i = 0; i < W; ++i)
         if (count[i]) cov.emplace_back(org + begin[i], org + begin[i] + count[i]);
     merge_spans(cov);
-    uint64_t spill[NI];
-    const uint64_t piece_tiles = piece_samples(ctx, in, NI, cov, T, spill) / T;
+    uint64_t spill[MAX_INPUTS];
+    const uint64_t piece_tiles = piece_samples(ctx, in, NI, cov, T, spill, LIST) / T;
     std::vector<Span> pcs;  // tiles [first, second): samples [first T, second T) at scratch[0, (second - first) T)
     const uint64_t region = cut_pieces(cov, T, piece_tiles, AGG_GAP_TILES, pcs) * T;
     // shared full tiles: the tiles past a window's first and before its last, merged over the windows
@@ -1383,8 +1467,8 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
         }
     }
     // decode tasks of every piece, once per input, and every piece's tile tasks
-    std::vector<PieceDecode> pdec[NI];
-    DecodeTasks D[NI];
+    std::vector<std::vector<PieceDecode>> pdec(NI);
+    std::vector<DecodeTasks> D(NI);
     for (int k = 0; k < NI && !rc; ++k) rc = emit_pieces_decode(ctx, Q::CALL, in[k].dp, in[k].org, cov, pcs, T, region, D[k], pdec[k]);
     if (rc) return rc;
     std::vector<size_t> tile_at(pcs.size());
@@ -1420,29 +1504,42 @@ static int reduce_dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, c
     for (int k = 0; k < NI; ++k) D[k].place(up);
     const size_t off_tiles = up.add(tiles), off_comb = up.add(comb);
     const size_t off_begins = Q::SIDE_BEGINS ? up.add(wb) : 0;
+    uint64_t scr_at[MAX_INPUTS];
+    const uint64_t scr_n = place_regions(D.data(), NI, region, scr_at);
+    const size_t off_reg = LIST ? up.add(scr_at, NI * sizeof(uint64_t)) : 0;
     const size_t off_part = up.device_only(part_n * q.part());
     const size_t off_side = Q::SIDE_BEGINS    ? off_begins
                             : NoSide<Q>::value ? off_part
                                                : up.device_only(Q::CARRY ? sizeof(double) : 2 * W * sizeof(double));
-    uint64_t scr_at[NI];
-    rc = stage_upload(ctx, R, up, place_regions(D, NI, region, scr_at), s);
+    rc = stage_upload(ctx, R, up, scr_n, s);
     if (rc) return rc;
     unsigned char *d = R.d;
-    double *scr[NI];
+    double *scr[MAX_INPUTS];
     for (int k = 0; k < NI; ++k) scr[k] = R.scratch + scr_at[k];
     void *part = d + off_part, *side = d + off_side;
+    // a query over a list: the tile kernel takes the scratch and the table of the regions' places in it, and both
+    // kernels the number of partials, which is how far one pair's nodes lie from the next pair's
+    auto run_tiles = [&](size_t p) {
+        const typename Q::Tile *t = (const typename Q::Tile *)(d + off_tiles) + tile_at[p];
+        if constexpr (LIST) return q.tiles(t, tile_n[p], R.scratch, (const uint64_t *)(d + off_reg), part, part_n, s);
+        else return q.tiles(t, tile_n[p], scr, part, side, s);
+    };
+    auto run_combine = [&](size_t a) {
+        const DevAggComb *c = (const DevAggComb *)(d + off_comb) + pass_at[a];
+        const uint32_t n = (uint32_t)(pass_at[a + 1] - pass_at[a]);
+        if constexpr (LIST) return q.combine(c, n, part, part_n, d_out, s);
+        else return q.combine(c, n, part, side, d_out, s);
+    };
     for (size_t p = 0; p < pcs.size(); ++p) {
         for (int k = 0; k < NI; ++k) {
             rc = launch_piece_decode(ctx, in[k].dp, in[k].d_body, d, D[k], pdec[k][p], scr[k], scr[k], scr[k], s, Q::who());
             if (rc) return rc;
         }
-        LAUNCHCHK(ctx, Q::TILES, q.tiles((const typename Q::Tile *)(d + off_tiles) + tile_at[p], tile_n[p], scr, part, side, s));
+        LAUNCHCHK(ctx, Q::TILES, run_tiles(p));
         if (Q::CARRY && p + 1 < pcs.size() && carry_in[p + 1])
             HIPCHK(ctx, hipMemcpyAsync(side, scr[0] + (pcs[p].second - pcs[p].first) * T - 1, sizeof(double), hipMemcpyDeviceToDevice, s));
     }
-    for (size_t a = 0; a + 1 < pass_at.size(); ++a)
-        LAUNCHCHK(ctx, Q::COMBINE, q.combine((const DevAggComb *)(d + off_comb) + pass_at[a], (uint32_t)(pass_at[a + 1] - pass_at[a]),
-                                             part, side, d_out, s));
+    for (size_t a = 0; a + 1 < pass_at.size(); ++a) LAUNCHCHK(ctx, Q::COMBINE, run_combine(a));
     HIPCHK(ctx, R.record(s));
     return ATSC_OK;
 }
@@ -1464,14 +1561,6 @@ static size_t result_used_bytes(const Q &q, const void *head, uint64_t n)
 {
     if constexpr (BlockResult<Q>::value) return q.used_bytes(head, n);
     else return q.out_bytes(n);
-}
-
-// The streams a query reads: its INPUTS constant, or for a query over a runtime number of them (INPUTS == 0) the call's own.
-template <class Q>
-static int query_inputs(const Q &q)
-{
-    if constexpr (Q::INPUTS > 0) return Q::INPUTS;
-    else return q.inputs();
 }
 
 // The device call of a query on the plans in[0 .. query_inputs(q)): a query over one stream takes its plan, bytes and origin.
@@ -3800,6 +3889,35 @@ extern "C" int atsc_across_moments_fit(const atsc_across_moments *m, uint64_t n,
 }
 
 // ------------------------------------------------------------------------------------------
+// windowed pair matrix: the pair moments of every pair of up to 64 streams over sample windows (atsc_pair_matrix.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" int atsc_pair_matrix_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                            const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                            const uint64_t *count, atsc_window_pair *d_out, void *stream)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
+        return fail(ctx, ATSC_E_INVALID, "pair_matrix_windows: n_streams outside [1, 64], a null list or a null entry");
+    QueryInput in[MAX_INPUTS];
+    for (uint32_t k = 0; k < n_streams; ++k) in[k] = QueryInput{dp[k], d_body[k], 0};
+    return PairMatrixQuery{n_streams, n_windows}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    ATSC_API_END
+}
+
+extern "C" int atsc_pair_matrix_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                                        const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                        atsc_window_pair *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
+        return fail(ctx, ATSC_E_INVALID, "pair_matrix_windows: n_streams outside [1, 64], a null list or a null entry");
+    HostBody hb[MAX_INPUTS];
+    for (uint32_t k = 0; k < n_streams; ++k) hb[k] = HostBody{body[k], body_len[k], has_count[k]};
+    return query_host(ctx, hb, n_windows, begin, count, out, PairMatrixQuery{n_streams, n_windows});
+    ATSC_API_END
+}
+
+// ------------------------------------------------------------------------------------------
 // the same queries on a stream under construction (atsc_stream.cpp): its records, then the host call
 // ------------------------------------------------------------------------------------------
 // a stream without a frame holds only empty windows at 0
@@ -4066,5 +4184,14 @@ extern "C" int atsc_stream_across_histogram_windows(atsc_stream *const *streams,
     if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
     return query_stream(streams, n_windows, begin, count, out,
                         AcrossHistQuery{n_streams, stride, count, n_windows, n_edges, edges, closed});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_pair_matrix_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                               const uint64_t *begin, const uint64_t *count, atsc_window_pair *out)
+{
+    ATSC_API_BEGIN
+    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
+    return query_stream(streams, n_windows, begin, count, out, PairMatrixQuery{n_streams, n_windows});
     ATSC_API_END
 }

@@ -307,6 +307,47 @@ def _across_block(n, cargs):
     return ACROSS_RECORD.itemsize * cargs.records
 
 
+def _pair_matrix_params(stride, records):
+    """no C argument of its own, and the records of the call"""
+    a = _RollArgs(())
+    a.records = int(records)
+    return a
+
+
+def pair_matrix_records(n):
+    """-> P = n (n + 1) / 2, the records per window of a pair matrix call over n streams (atsc_pair_matrix_records; no GPU)"""
+    return int(capi.lib().atsc_pair_matrix_records(int(n)))
+
+
+def pair_matrix_index(n, i, j):
+    """-> p, the place of pair (i, j), i <= j < n, among a window's records of a pair matrix call over n streams
+    (atsc_pair_matrix_index; no GPU); ValueError for i > j or j >= n"""
+    p = int(capi.lib().atsc_pair_matrix_index(int(n), int(i), int(j)))
+    if p == 2 ** 64 - 1:
+        raise ValueError("no pair (%d, %d) among %d streams" % (i, j, n))
+    return p
+
+
+def _pair_matrix_result(run, n_streams, n_windows):
+    """run(records) -> the block of a pair matrix call as uint64 words.  -> the (n_windows, P) WINDOW_PAIR array"""
+    p = pair_matrix_records(n_streams)
+    return run(n_windows * p).view(WINDOW_PAIR).reshape(n_windows, p)
+
+
+def pair_matrix_correlation(records, n):
+    """-> the (W, n, n) float64 array of the correlations of every pair of the n streams, symmetric, from the (W, P)
+    WINDOW_PAIR records of a pair matrix call, read through pair_fit: NaN where pair_fit gives NaN (a pair without a
+    counted sample, or a stream that is constant over them).  NumPy only"""
+    n = int(n)
+    rec = np.asarray(records, dtype=WINDOW_PAIR).reshape(-1, pair_matrix_records(n))
+    corr = pair_fit(rec.reshape(-1))["correlation"].reshape(rec.shape)
+    out = np.empty((rec.shape[0], n, n), dtype=np.float64)
+    i, j = np.triu_indices(n)  # row-major over i <= j: the records' order
+    out[:, i, j] = corr
+    out[:, j, i] = corr
+    return out
+
+
 def _across_result(run, counts, stride):
     """run(records) -> the block of an across call as uint64 words.  -> (records, off): the ACROSS_RECORD records of
     every position, range after range, and the ranges' record offsets (across_offsets)"""
@@ -405,6 +446,8 @@ _ACROSS_MOMENTS = _Query("across_moments_windows", np.dtype(np.uint64), None, _a
 # (the across quantiles' arguments serve: the stride, then the edges and the closed side in the levels' and the method's place)
 _ACROSS_HISTOGRAM = _Query("across_histogram_windows", np.dtype(np.uint64), None, _across_quantile_params, _across_histogram_block,
                            inputs=None)
+# (the pair matrix takes its streams as lists, as the across calls do, and nothing of its own: `stride` is not passed on)
+_PAIR_MATRIX = _Query("pair_matrix_windows", np.dtype(np.uint64), None, _pair_matrix_params, _rolling_pair_block, inputs=None)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
 _HISTOGRAM = _Query("histogram_windows", np.dtype(np.uint64), 2, _array_params)
 
@@ -821,6 +864,14 @@ class Context:
                                                      others=(records_y,)),
                                counts, width, stride, WINDOW_PAIR)
 
+    def pair_matrix_windows_host(self, records_list, begins, counts, has_count=False):
+        """-> (W, P) WINDOW_PAIR array: per window [begins[i], begins[i] + counts[i]) the pair moments of every pair
+        (i, j), i <= j, of the decoded record streams of records_list (at most ACROSS_MAX_STREAMS; has_count holds for
+        every one of them), at column pair_matrix_index(n, i, j): bit for bit what pair_windows_host gives for streams i
+        and j (atsc_pair_matrix_windows).  pair_fit and pair_matrix_correlation read covariance and correlation off it"""
+        return _pair_matrix_result(lambda m: _across_host(self, records_list, begins, counts, has_count, 0, m, q=_PAIR_MATRIX),
+                                   len(records_list), len(np.atleast_1d(begins)))
+
     def across_windows_host(self, records_list, begins, counts, stride=1, has_count=False):
         """-> (records, off): count / min / max / sum over the streams of records_list (at most ACROSS_MAX_STREAMS
         decoded record streams, sample j of one going with sample j of every other) at every `stride`-th position of
@@ -1031,6 +1082,19 @@ class DPlan:
         over the windows [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least 48 bytes per window
         (atsc_pair_windows_dev; WINDOW_PAIR records).  other may be this plan"""
         _query_dev(_PAIR, self, d_body, begins, counts, d_out, stream, others=((other, other_body),))
+
+    def pair_matrix_windows(self, d_body, others, other_bodies, begins, counts, d_out, stream=0):
+        """Enqueues the pair moments of every pair (i, j), i <= j, of this plan's stream (stream 0) and the plans `others`'
+        (stream 1 and on, their device bytes other_bodies; at most ACROSS_MAX_STREAMS in all) over the windows
+        [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least 48 P bytes per window
+        (atsc_pair_matrix_windows_dev).  A plan may appear more than once.  -> the view of d_out's front as (W, P)
+        WINDOW_PAIR records (a uint8 tensor of shape (W, P, 48); .cpu().numpy().view(WINDOW_PAIR)[..., 0] gives the
+        fields), filled once `stream` has run"""
+        import torch  # (d_out is a torch tensor: the module is loaded)
+        plans = [self] + list(others)
+        n, p, size = len(np.atleast_1d(begins)), pair_matrix_records(len(plans)), WINDOW_PAIR.itemsize
+        _across_dev(plans, [d_body] + list(other_bodies), begins, counts, d_out, stream, 0, n * p, q=_PAIR_MATRIX)
+        return d_out.reshape(-1).view(torch.uint8)[: n * p * size].reshape(n, p, size)
 
     def delta_windows(self, d_body, begins, counts, d_out, stream=0):
         """Enqueues the deltas of the windows [begins[i], begins[i] + counts[i]) into d_out, a device tensor of at least

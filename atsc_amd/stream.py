@@ -15,6 +15,7 @@ from .engine import _ROLLING_HISTOGRAM, _rolling_histogram_result
 from .engine import _ACROSS_EXTREMES, _across_extremes_result
 from .engine import _ACROSS_MOMENTS, _across_moments_result
 from .engine import _ACROSS_HISTOGRAM, _across_histogram_result
+from .engine import _PAIR_MATRIX, _pair_matrix_result
 
 
 def _f64(x):
@@ -208,6 +209,13 @@ class CompressedStream:
         them (atsc_stream_across_windows)"""
         return _across_result(lambda m: self._across_stream(_ACROSS, others, begins, counts, stride, m), counts, stride)
 
+    def pair_matrix_windows(self, others, begins, counts):
+        """-> (W, P) WINDOW_PAIR array: the pair moments of every pair of this stream (stream 0) and the streams `others`
+        (stream 1 and on) over the windows [begins[i], begins[i] + counts[i]), as Context.pair_matrix_windows_host gives
+        them (atsc_stream_pair_matrix_windows)"""
+        return _pair_matrix_result(lambda m: self._across_stream(_PAIR_MATRIX, others, begins, counts, 0, m),
+                                   1 + len(others), len(np.atleast_1d(begins)))
+
     def _across_stream(self, q, others, begins, counts, *params):
         """atsc_stream_<q.stem> over this stream and the streams `others`"""
         streams = [self] + list(others)
@@ -400,6 +408,13 @@ def across_data_windows(ctx, bros, begins, counts, stride=1):
     atsc_across_windows over their records"""
     records = _across_images(bros)
     return _across_result(lambda m: _across_host(ctx, records, begins, counts, True, stride, m), counts, stride)
+
+
+def pair_matrix_data_windows(ctx, bros, begins, counts):
+    """-> (W, P) WINDOW_PAIR array: the pair moments of every pair of the BRO images of the list `bros` over the windows,
+    as Context.pair_matrix_windows_host gives them: atsc_bro_open of each image, then atsc_pair_matrix_windows over their
+    records"""
+    return ctx.pair_matrix_windows_host(_across_images(bros), begins, counts, has_count=True)
 
 
 def _across_images(bros):

@@ -469,6 +469,46 @@ typedef struct {
 } atsc_window_pair_fit; /* 56 bytes */
 int atsc_pair_fit(const atsc_window_pair *p, uint64_t n, atsc_window_pair_fit *out);
 
+/* Windowed pair matrix: per window the pair moments of EVERY pair of n_streams decoded streams, 1 <= n_streams <=
+ * ATSC_ACROSS_MAX_STREAMS, in one call that decodes every stream once: what the covariance and the correlation matrix
+ * of a fleet's series are read from.  Streams come as lists, as the across calls take them; windows as atsc_pair_windows
+ * takes them (begin[] / count[] on the host, no stride).
+ * Per window the result holds P = n_streams (n_streams + 1) / 2 atsc_window_pair records, one for every pair (i, j) with
+ * i <= j, window-major: window w's record of (i, j) is d_out[w * P + p], p = i (2 n_streams - i + 1) / 2 + (j - i).
+ *   THE CONTRACT: record (i, j) of window w is atsc_pair_windows' record of stream i as X and stream j as Y over that
+ *   window, bit for bit.
+ * Leaf, the pairwise-complete NaN rule (a slot counts where neither x_i nor x_j is NaN, whatever the other streams hold
+ * there), Merge and the tree are the pair's, above.  Where the rule yields NaN, any NaN bit pattern conforms; a window
+ * with count == 0 gives count == 0 and five NaNs in each of its P records.  It follows that
+ *   - a record depends only on its two streams' samples and the window's (begin, count): not on the other streams,
+ *     their order in the list, the other windows, the budget, the pieces or either stream's framing;
+ *   - (i, i) is the diagonal: there m2_y == c_xy == m2_x, and they are atsc_moments_windows' mean and m2 of stream i;
+ *   - a stream listed twice gives, at its off-diagonal place, its own diagonal record;
+ *   - atsc_pair_fit applies to the W * P records unchanged;
+ *   - no tolerance appears anywhere: the error bounds are the pair's.
+ * ATSC_E_INVALID, with nothing written and before any GPU work, for: n_streams outside [1, 64]; a null list or a null
+ * entry; plans of different contexts; a window beyond the end of ANY stream; d_out not 8-byte aligned; more than
+ * 2^32 - 2 records (n_windows * P).  n_windows == 0 is valid.  The calls have no ATSC_E_CAPACITY case.
+ * Memory the call holds on dp[0] (its tables, partials and scratch, of a kind of their own: the next pair matrix call
+ * with the same dp[0] waits, host side, until this one's work is done; atsc_dplan_destroy frees them):
+ *   - decoded regions as the across calls': one input's default shared among the n_streams regions, bounded by
+ *     atsc_ctx_set_aggregate_scratch, at least one piece's minimum (32 tiles of 2048 samples) per region;
+ *   - a partial table of (shared full tiles + 2 n_windows + combine levels) * P * 48 bytes. */
+/* host only: P of n_streams, and p of (i, j) -- ~0ull for i > j or j >= n_streams */
+uint64_t atsc_pair_matrix_records(uint32_t n_streams);
+uint64_t atsc_pair_matrix_index(uint32_t n_streams, uint32_t i, uint32_t j);
+/* begin / count are HOST arrays, dp and d_body host lists of n_streams entries; the bodies and d_out are device memory.
+ * Enqueued on `stream`, not synchronised.  A malformed payload inside a window sets the status word of the plan it
+ * belongs to. */
+int atsc_pair_matrix_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                 const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                 const uint64_t *count, atsc_window_pair *d_out, void *stream);
+/* Host bytes in, host records out, synchronous; walks and uploads only the touched records of each stream.
+ * ATSC_E_FORMAT (nothing written) for a malformed payload inside a window in any stream. */
+int atsc_pair_matrix_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                             const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                             atsc_window_pair *out);
+
 /* Windowed deltas: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames) what
  * its samples do from one to the next, from the same decoded samples as the window decode: how much a counter grew and
  * how often it reset, how much a gauge moved up and down (total variation), the largest single jump and drop.
@@ -1474,6 +1514,10 @@ int atsc_stream_moments_windows(atsc_stream *s, uint64_t n_windows, const uint64
 /* atsc_pair_windows over the frames of the streams x and y, which must belong to one context (else ATSC_E_INVALID) */
 int atsc_stream_pair_windows(atsc_stream *x, atsc_stream *y, uint64_t n_windows, const uint64_t *begin,
                              const uint64_t *count, atsc_window_pair *out);
+/* atsc_pair_matrix_windows over the frames of the n_streams streams of the list, which must belong to one context (else
+ * ATSC_E_INVALID); out: n_windows * P records */
+int atsc_stream_pair_matrix_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                    const uint64_t *begin, const uint64_t *count, atsc_window_pair *out);
 /* atsc_across_windows over the frames of the n_streams streams of the list, which must belong to one context (else
  * ATSC_E_INVALID) */
 int atsc_stream_across_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows, const uint64_t *begin,
