@@ -27,6 +27,7 @@ from .stream import across_data_windows, across_extremes_data_windows, across_qu
 from .engine import ACROSS_FIT, ACROSS_MOMENTS, across_moments_fit, across_moments_merge  # noqa: F401
 from .stream import across_moments_data_windows  # noqa: F401
 from .stream import across_histogram_data_windows  # noqa: F401
+from .stream import across_values_data_windows  # noqa: F401
 from .engine import WINDOW_PAIR, WINDOW_PAIR_FIT, pair_fit  # noqa: F401
 from .engine import pair_matrix_correlation, pair_matrix_index, pair_matrix_records  # noqa: F401
 from .stream import pair_matrix_data_windows  # noqa: F401

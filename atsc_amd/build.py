@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 VARIANT = os.environ.get("ATSC_BUILD_VARIANT", "")
 LIB = os.path.join(HERE, "libatsc_hip%s.so" % ("_" + VARIANT if VARIANT else ""))
 SOURCES = ["atsc_kernels.hip", "atsc_large.hip", "atsc_decode.hip", "atsc_aggregate.hip", "atsc_quantile.hip",
-           "atsc_histogram.hip", "atsc_moments.hip", "atsc_pair.hip", "atsc_pair_matrix.hip", "atsc_delta.hip", "atsc_runs.hip", "atsc_extremes.hip", "atsc_values.hip", "atsc_select.hip", "atsc_rolling.hip", "atsc_rolling_delta.hip", "atsc_rolling_moments.hip", "atsc_rolling_pair.hip", "atsc_rolling_quantile.hip", "atsc_rolling_histogram.hip", "atsc_rolling_runs.hip", "atsc_across.hip", "atsc_across_quantile.hip", "atsc_across_extremes.hip", "atsc_across_moments.hip", "atsc_across_histogram.hip", "atsc_host.cpp", "atsc_windows.cpp", "atsc_stream.cpp", "atsc_vsri.cpp"]
+           "atsc_histogram.hip", "atsc_moments.hip", "atsc_pair.hip", "atsc_pair_matrix.hip", "atsc_delta.hip", "atsc_runs.hip", "atsc_extremes.hip", "atsc_values.hip", "atsc_select.hip", "atsc_rolling.hip", "atsc_rolling_delta.hip", "atsc_rolling_moments.hip", "atsc_rolling_pair.hip", "atsc_rolling_quantile.hip", "atsc_rolling_histogram.hip", "atsc_rolling_runs.hip", "atsc_across.hip", "atsc_across_quantile.hip", "atsc_across_extremes.hip", "atsc_across_moments.hip", "atsc_across_histogram.hip", "atsc_across_values.hip", "atsc_host.cpp", "atsc_windows.cpp", "atsc_stream.cpp", "atsc_vsri.cpp"]
 CLI = os.path.join(HERE, "bin", "atsc")
 CLI_SRC = "atsc_cli.cpp"
 CLI2 = os.path.join(HERE, "bin", "csv-compressor")

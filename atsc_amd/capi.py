@@ -174,6 +174,10 @@ SIGNATURES = {
                                                    C.c_uint32, _vp, _vp]),
     "atsc_across_extremes_windows": (C.c_int, [_vp, C.c_uint32, _vp, _u64p, _i32p, C.c_uint64, _u64p, _u64p, C.c_uint64,
                                                C.c_uint32, _vp]),
+    "atsc_across_values_windows_dev": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64,
+                                                 C.c_uint32, C.c_double, _vp, _vp]),
+    "atsc_across_values_windows": (C.c_int, [_vp, C.c_uint32, _vp, _u64p, _i32p, C.c_uint64, _u64p, _u64p, C.c_uint64,
+                                             C.c_uint32, C.c_double, _vp]),
     "atsc_across_moments_windows_dev": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64, _vp, _vp]),
     "atsc_across_moments_windows": (C.c_int, [_vp, C.c_uint32, _vp, _u64p, _i32p, C.c_uint64, _u64p, _u64p, C.c_uint64, _vp]),
     "atsc_across_histogram_windows_dev": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint64,
@@ -225,6 +229,8 @@ SIGNATURES = {
                                                       _f64p, C.c_int, _vp]),
     "atsc_stream_across_extremes_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint32,
                                                       _vp]),
+    "atsc_stream_across_values_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint32,
+                                                    C.c_double, _vp]),
     "atsc_stream_across_moments_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, _vp]),
     "atsc_stream_across_histogram_windows": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _u64p, _u64p, C.c_uint64, C.c_uint32,
                                                        _f64p, C.c_int, _vp]),

@@ -5,7 +5,8 @@
 // scratch as the windowed across leaves them (atsc_across.hip): a region per stream, slot j of every region the same
 // sample index.  A lane per position, one wavefront per 64 positions of a task, so the 64 lanes read 64 consecutive
 // slots of a region at stride 1.  A lane holds its position's column in registers: G = the power of two >= N keys
-// (atsc_quantile_rule.h), NaN and padding as KEY_NAN, put in order by a fully unrolled bitonic network; x[lo] and x[hi]
+// (atsc_quantile_rule.h), NaN and padding as KEY_NAN, put in order by a fully unrolled bitonic network (column_sort,
+// atsc_tile_reduce.h, which the across value counts share); x[lo] and x[hi]
 // of a level come out of the G registers through a binary tree of selects on the rank's bits.  Every index into the
 // column is a compile-time constant: no scratch memory, no LDS, no shuffles, no atomics.  Every stride goes through
 // the same code, one 8-byte load per stream and position.
@@ -18,27 +19,6 @@
 namespace atsc {
 
 namespace {
-
-// the bitonic network over G keys, ascending: G/2 compare-exchanges per step, log2 G (log2 G + 1) / 2 steps
-template <int G>
-DEVI void column_sort(uint64_t (&v)[G])
-{
-#pragma unroll
-    for (int k = 2; k <= G; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const int l = i ^ j;
-                if (l < i) continue;
-                const uint64_t a = v[i], b = v[l];
-                const bool sw = (i & k) == 0 ? a > b : a < b;
-                v[i] = sw ? b : a;
-                v[l] = sw ? a : b;
-            }
-        }
-    }
-}
 
 // v[e], e < G: the rank's bit b halves the candidates, G - 1 selects in all.  The selects are written on the bits (a
 // mask of the rank's bit): as `odd ? v[1] : v[0]` the compiler turns the first level into a load from a selected

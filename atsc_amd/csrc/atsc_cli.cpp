@@ -8,7 +8,7 @@
 //        [--rolling-quantiles Q,Q,.. [--rolling-quantile-method M]] [--rolling-pair OTHER.bro]
 //        [--rolling-histogram E,E,..|LO:HI:N]]
 //        [--across A.bro,B.bro,.. [--across-stride S] [--across-quantiles Q,Q,.. [--across-quantile-method M]]
-//        [--across-extremes K] [--across-moments] [--across-histogram E,E,..|LO:HI:N]]]
+//        [--across-extremes K] [--across-moments] [--across-histogram E,E,..|LO:HI:N] [--across-values K[:ABOVE]]]]
 //        [-c 0..6] [--verbose] [--csv] [--no-header] [--fields=TIME,VALUE] <file-or-directory>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -135,6 +135,13 @@ void usage()
             "      --across-histogram <SPEC>  with --across: also how many of the streams' samples at every row's sample index\n"
             "                                 lie in each value bin of the edges (SPEC and --histogram-closed as --histogram), as\n"
             "                                 the last columns: h0 .. h<n_edges>,hnan; a row's counters sum to the number of streams\n"
+            "      --across-values <K[:ABOVE]>  with --across: also which values the streams hold at every row's sample index and\n"
+            "                                 how many streams hold each (count_values), behind every other column:\n"
+            "                                 vcount,vnans,vbelow,vdistinct,vmore,v0,n0 .. v<K-1>,n<K-1>: the streams, those whose\n"
+            "                                 sample is NaN, those whose sample is not above ABOVE, the entries filled, whether more\n"
+            "                                 distinct values follow, then the K (1..=32) smallest distinct values above ABOVE (all\n"
+            "                                 without it; -0.0 counts as +0.0) and the number of streams that hold each, the cells\n"
+            "                                 of unused entries empty; page on with ABOVE = the last value listed\n"
             "  -c, --compression-selection-sample-level <0..6>  [default: 0]\n"
             "      --verbose                  dump every sample\n"
             "      --csv                      input is a CSV file\n"
@@ -249,14 +256,15 @@ int process_single_file(atsc_ctx *ctx, const std::string &path, const Args &a)
             std::vector<double> levels;
             std::vector<uint64_t> extremes;
             std::vector<atsc_across_moments> moments;
-            std::vector<uint64_t> hist;
+            std::vector<uint64_t> hist, values;
             rc = atsc_bro_open(bro, len, nullptr, nullptr);
-            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, levels, extremes, moments, hist);
+            if (!rc) rc = across_query(ctx, bro, len, a.q, a.win_begin, a.win_count, rows, levels, extremes, moments, hist, values);
             atsc_free(bro);
             if (rc) return rc;
             const bool ok = across_write(with_ext(path, "across.csv"), rows, a.q.across_stride, a.q.across_level_names, levels,
                                          (uint32_t)a.q.across_extremes, extremes, a.q.across_moments, moments,
-                                         a.q.across_hist ? &hist : nullptr, a.q.across_edges.size() + 2);
+                                         a.q.across_hist ? &hist : nullptr, a.q.across_edges.size() + 2,
+                                         (uint32_t)a.q.across_values, &values);
             return ok ? ATSC_OK : ATSC_E_IO;
         }
         double *out = nullptr;

@@ -101,6 +101,8 @@ struct BucketOptions {
     bool across_moments = false;  // --across-moments: nonnan,avg,stdvar,stddev
     std::vector<double> across_edges;  // --across-histogram E,E,..|LO:HI:N: h0 .. h<n_edges>,hnan as the last columns (closed: --histogram-closed)
     bool across_hist = false;
+    int across_values = 0;  // --across-values K[:ABOVE]: vcount,vnans,vbelow,vdistinct,vmore,v0,n0,..,v<K-1>,n<K-1> as the last columns
+    double across_values_above = std::nan("");  // NaN: every value is listed
 };
 
 // --quantiles Q,Q,..: levels in [0, 1] as typed (the column names), at most ATSC's 64
@@ -389,6 +391,12 @@ int bucket_option(const std::string &s, const std::string &v, Value value, Bucke
     } else if (o.across_allowed && value("--across-histogram")) {
         if (!histogram_option("--across-histogram", v, o.across_edges)) return 2;
         o.across_hist = true;
+    } else if (o.across_allowed && value("--across-values")) {
+        if (!parse_values(v, o.across_values, o.across_values_above)) {
+            fprintf(stderr, "error: invalid value '%s' for '--across-values': expected K[:ABOVE], K in 1..=%d, ABOVE a number\n",
+                    v.c_str(), (int)ATSC_VALUES_MAX_K);
+            return 2;
+        }
     } else {
         return 0;
     }
@@ -479,7 +487,7 @@ bool rolling_option_complete(const BucketOptions &o, const char *window, bool wi
 }
 
 // --across goes with the option that names the window and without the one that cuts buckets, --rolling and --where;
-// --across-stride, --across-quantiles, --across-extremes, --across-moments and --across-histogram go with --across,
+// --across-stride, --across-quantiles, --across-extremes, --across-moments, --across-histogram and --across-values go with --across,
 // --across-quantile-method with --across-quantiles.  false: a usage error, reported on stderr.
 bool across_option_complete(const BucketOptions &o, const char *window, bool windowed, const char *bucketing, bool bucketed)
 {
@@ -493,7 +501,9 @@ bool across_option_complete(const BucketOptions &o, const char *window, bool win
         else if (o.across_extremes) fprintf(stderr, "error: '--across-extremes' needs '--across'\n");
         else if (o.across_moments) fprintf(stderr, "error: '--across-moments' needs '--across'\n");
         else if (o.across_hist) fprintf(stderr, "error: '--across-histogram' needs '--across'\n");
-        return !o.have_across_stride && o.across_levels.empty() && !o.across_extremes && !o.across_moments && !o.across_hist;
+        else if (o.across_values) fprintf(stderr, "error: '--across-values' needs '--across'\n");
+        return !o.have_across_stride && o.across_levels.empty() && !o.across_extremes && !o.across_moments && !o.across_hist &&
+               !o.across_values;
     }
     if (!windowed) {
         fprintf(stderr, "error: '--across' needs '%s'\n", window);
@@ -871,10 +881,11 @@ bool rolling_write(const std::string &path, const char *first, const std::vector
 // same positions' rows of o.across_levels.size() levels; extremes: with --across-extremes K, the same positions'
 // extremes records of k = K, ATSC_EXTREMES_BYTES(K) / 8 words each; moments: with --across-moments, the same
 // positions' across moments; hist: with --across-histogram, the same positions' rows of o.across_edges.size() + 2 counters
-// (--histogram-closed's side)
+// (--histogram-closed's side); values: with --across-values K[:ABOVE], the same positions' value-count records of k = K,
+// ATSC_VALUES_BYTES(K) / 8 words each
 int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOptions &o, uint64_t begin, uint64_t count,
                  std::vector<atsc_across_record> &rows, std::vector<double> &levels, std::vector<uint64_t> &extremes,
-                 std::vector<atsc_across_moments> &moments, std::vector<uint64_t> &hist)
+                 std::vector<atsc_across_moments> &moments, std::vector<uint64_t> &hist, std::vector<uint64_t> &values)
 {
     std::vector<uint8_t *> image(o.across.size(), nullptr);
     std::vector<const uint8_t *> body{bro + 9};
@@ -923,6 +934,13 @@ int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOp
                                                &count, o.across_stride, (uint32_t)o.across_edges.size(), o.across_edges.data(),
                                                o.closed, hist.empty() ? &no_row : hist.data());
         }
+        if (!rc && o.across_values) {
+            values.assign(rows.size() * (ATSC_VALUES_BYTES(o.across_values) / 8), 0);
+            uint64_t no_record;
+            rc = atsc_across_values_windows(ctx, (uint32_t)body.size(), body.data(), body_len.data(), has_count.data(), 1, &begin,
+                                            &count, o.across_stride, (uint32_t)o.across_values, o.across_values_above,
+                                            values.empty() ? &no_record : values.data());
+        }
     }
     for (uint8_t *p : image) atsc_free(p);
     return rc;
@@ -937,12 +955,17 @@ int across_query(atsc_ctx *ctx, const uint8_t *bro, uint64_t len, const BucketOp
 // empty.  with_moments: with --across-moments, behind those nonnan,avg,stdvar,stddev from the position's record of
 // `moments`: its count, mean and the population variance and standard deviation that atsc_across_moments_fit reads off
 // it, all four empty where count == 0 (the count column says so).  hist (--across-histogram; null without it): as the
-// last columns h0 .. h<n_edges>,hnan, --histogram's columns, from the position's row of n_hist = n_edges + 2 counters.
+// columns behind those h0 .. h<n_edges>,hnan, --histogram's columns, from the position's row of n_hist = n_edges + 2
+// counters.  vk: with --across-values K[:ABOVE], as the last columns vcount,vnans,vbelow,vdistinct,vmore,v0,n0,..,
+// v<K-1>,n<K-1> from the position's record of `values` (null without it): the number of streams, those whose sample is
+// NaN, those whose sample is not above ABOVE, the entries filled, whether more distinct values lie above them, then the
+// K smallest distinct values and the number of streams that hold each, the cells of unused entries empty.
 // false: the file could not be written.
 bool across_write(const std::string &path, const std::vector<atsc_across_record> &rows, uint64_t stride,
                   const std::vector<std::string> &names, const std::vector<double> &levels, uint32_t k,
                   const std::vector<uint64_t> &extremes, bool with_moments, const std::vector<atsc_across_moments> &moments,
-                  const std::vector<uint64_t> *hist = nullptr, size_t n_hist = 0)
+                  const std::vector<uint64_t> *hist = nullptr, size_t n_hist = 0, uint32_t vk = 0,
+                  const std::vector<uint64_t> *values = nullptr)
 {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return false;
@@ -957,6 +980,10 @@ bool across_write(const std::string &path, const std::vector<atsc_across_record>
     if (hist) {
         for (size_t b = 0; b + 1 < n_hist; ++b) fprintf(f, ",h%zu", b);
         fprintf(f, ",hnan");
+    }
+    if (vk) {
+        fprintf(f, ",vcount,vnans,vbelow,vdistinct,vmore");
+        for (uint32_t e = 0; e < vk; ++e) fprintf(f, ",v%u,n%u", e, e);
     }
     fprintf(f, "\n");
     for (size_t j = 0; j < rows.size(); ++j) {
@@ -984,6 +1011,17 @@ bool across_write(const std::string &path, const std::vector<atsc_across_record>
         }
         if (hist)
             for (size_t b = 0; b < n_hist; ++b) fprintf(f, ",%llu", (unsigned long long)(*hist)[j * n_hist + b]);
+        if (vk) {
+            const uint64_t *rec = values->data() + j * (ATSC_VALUES_BYTES(vk) / 8);
+            const atsc_window_values_head &h = *(const atsc_window_values_head *)rec;
+            const atsc_value_count *x = (const atsc_value_count *)(&h + 1);
+            fprintf(f, ",%llu,%llu,%llu,%u,%u", (unsigned long long)h.count, (unsigned long long)h.nans, (unsigned long long)h.below,
+                    h.distinct, h.more);
+            for (uint32_t e = 0; e < vk; ++e) {
+                if (e < h.distinct) fprintf(f, ",%s,%llu", debug_f64(x[e].value).c_str(), (unsigned long long)x[e].n);
+                else fprintf(f, ",,");
+            }
+        }
         fprintf(f, "\n");
     }
     return fclose(f) == 0;

@@ -43,6 +43,34 @@ DEVI uint64_t sample_key(double v)
     return v != v ? 0ull : k;
 }
 
+// the bits of the value of a sample's key: +0.0 for the zeros' key, every other value's own
+DEVI uint64_t val_bits(uint64_t key)
+{
+    return (key >> 63) ? key ^ 0x8000000000000000ull : ~key;
+}
+
+// A lane's column of G keys in registers (the across quantiles, the across value counts), ascending by the bitonic
+// network: G/2 compare-exchanges per step, log2 G (log2 G + 1) / 2 steps, every index a compile-time constant
+template <int G>
+DEVI void column_sort(uint64_t (&v)[G])
+{
+#pragma unroll
+    for (int k = 2; k <= G; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const int l = i ^ j;
+                if (l < i) continue;
+                const uint64_t a = v[i], b = v[l];
+                const bool sw = (i & k) == 0 ? a > b : a < b;
+                v[i] = sw ? b : a;
+                v[l] = sw ? a : b;
+            }
+        }
+    }
+}
+
 // THE TILE SUM of the contract (include/atsc_hip.h, DESIGN.md "Windowed aggregates"), NS sums side by side:
 //   * term(k, q, p) gives p[c] = (term of slot j) + (term of slot j + 1) of sum c, j = tile_slot(lane + 64 k, q); a
 //     slot without a term holds -0.0 (IEEE's exact additive identity);

@@ -31,12 +31,6 @@ namespace {
 constexpr uint64_t VAL_NONE = ~0ull;
 constexpr uint64_t VAL_NAN_BITS = 0x7ff8000000000000ull;
 
-// the bits of the value of a key: +0.0 for the zeros' key, every other value's own
-__device__ __forceinline__ uint64_t val_bits(uint64_t key)
-{
-    return (key >> 63) ? key ^ 0x8000000000000000ull : ~key;
-}
-
 __device__ __forceinline__ uint64_t val_wave_min(uint64_t v)
 {
 #pragma unroll

@@ -1,6 +1,6 @@
 // atsc_windows.cpp -- the window queries of libatsc_hip.so: samples, aggregates, moments, deltas, runs, extremes, value counts, quantiles, histograms,
 // rolling windows, rolling deltas, rolling runs, rolling quantiles, rolling histograms and selected samples of ranges of the decoded stream without decoding the rest, the pair moments of the same ranges of two streams and of every pair of up to 64,
-// and count, min, max, sum, quantiles, extremes, moments and histograms across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
+// and count, min, max, sum, quantiles, extremes, moments, histograms and value counts across up to 64 streams at every position of such ranges.  Each query has a device call (host tables, one upload, launches on the caller's
 // stream) and a host call (the touched records only: walk, range plan, upload, device call, result back).  What the
 // queries have in common comes first: the record walk, the per-plan resources, the upload, the decode of pieces into
 // scratch, the argument checks and the host call.  Last, the same queries on a stream under construction.  Context, plans
@@ -163,6 +163,11 @@ __attribute__((weak)) hipError_t launch_across_histogram_positions(const DevRoll
                                                                    const uint64_t *reg, uint32_t n_streams, uint64_t a0,
                                                                    uint64_t stride, const double *edges, uint32_t n_edges,
                                                                    int closed, uint64_t *out, hipStream_t s);
+// the windowed across value counts' position kernel (atsc_across_values.hip; weak for the same reason)
+__attribute__((weak)) hipError_t launch_across_values_positions(const DevRollTask *tasks, uint32_t n, const double *scratch,
+                                                                const uint64_t *reg, uint32_t n_streams, uint64_t a0,
+                                                                uint64_t stride, uint32_t k, uint64_t above, void *out,
+                                                                hipStream_t s);
 }  // namespace atsc
 
 using namespace atsc;
@@ -427,7 +432,8 @@ static const DecodeCaller BY_AGGREGATE = DECODE_CALLER("aggregate"), BY_QUANTILE
                           BY_ACROSS_QUANTILE = DECODE_CALLER("across quantile"),
                           BY_ACROSS_EXTREMES = DECODE_CALLER("across extremes"),
                           BY_ACROSS_MOMENTS = DECODE_CALLER("across moments"),
-                          BY_ACROSS_HISTOGRAM = DECODE_CALLER("across histogram");
+                          BY_ACROSS_HISTOGRAM = DECODE_CALLER("across histogram"),
+                          BY_ACROSS_VALUES = DECODE_CALLER("across values");
 #undef DECODE_CALLER
 // (the window decode's gather message carries no word)
 static const DecodeCaller BY_WINDOW = {"launch k_decompress (window)", "launch k_decompress_large (window)",
@@ -3362,7 +3368,7 @@ static int across_check(atsc_ctx *ctx, const char *call, uint32_t n_streams, uin
 }
 
 // What differs between the device calls that work on the N samples of a position (across_dev): the across and the
-// across quantiles, the across extremes, the across moments and the across histograms.
+// across quantiles, the across extremes, the across moments, the across histograms and the across value counts.
 struct AcrossKernel {
     const char *call;          // names the call in the messages
     const char *no_kernels;    // ATSC_E_UNSUPPORTED's message
@@ -3696,6 +3702,52 @@ struct AcrossHistQuery {
     }
 };
 
+// the across value counts' descriptor: the across' ranges, stride and record numbering, the windowed value counts' record
+// (of k entries) per position; k is checked as the windowed value counts check theirs, and k and `above` (as its key,
+// val_key) go to the kernel by value.  Like the across extremes, moments and histograms it keeps its tables and scratch in
+// the across quantiles' place on in[0].dp (Q_ACROSS_QUANTILE): the five kinds of call on one first plan wait for each
+// other, and atsc_dplan stays as it is (DESIGN.md "Windowed across value counts")
+struct AcrossValQuery {
+    static constexpr int INPUTS = 0;
+    static constexpr const char *CALL = "across_values_windows";
+    uint32_t n_streams;
+    uint64_t stride;
+    const uint64_t *count;  // the call's ranges' lengths
+    uint64_t n_ranges;
+    uint32_t k;
+    double above;
+    int inputs() const { return (int)n_streams; }
+    size_t out_bytes(uint64_t n) const
+    {
+        uint64_t total = 0;
+        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
+        return total * ATSC_VALUES_BYTES(std::min<uint32_t>(k, ATSC_VALUES_MAX_K));
+    }
+    int check(atsc_ctx *ctx) const
+    {
+        const int rc = across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, nullptr);
+        if (rc) return rc;
+        if (k == 0 || k > ATSC_VALUES_MAX_K) return fail_in(ctx, ATSC_E_INVALID, CALL, "k outside [1, 32]");
+        return ATSC_OK;
+    }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
+    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
+            void *stream) const
+    {
+        const int rc = check(ctx);
+        if (rc) return rc;
+        const uint32_t ns = n_streams, kk = k;
+        const uint64_t st = stride, ak = val_key(above);
+        const AcrossKernel K{CALL, "no across values kernels", "launch k_across_values_positions", Q_ACROSS_QUANTILE,
+                             BY_ACROSS_VALUES, launch_across_values_positions != nullptr, nullptr, 0,
+                             [ns, st, kk, ak](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg,
+                                              uint64_t a0, const void *, void *d_out, hipStream_t s) {
+                                 return launch_across_values_positions(tasks, n, scratch, reg, ns, a0, st, kk, ak, d_out, s);
+                             }};
+        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
+    }
+};
+
 // what every across call checks of its lists before it reads them
 static bool across_lists(uint32_t n_streams, const void *const *a, const void *const *b)
 {
@@ -3783,6 +3835,34 @@ extern "C" int atsc_across_extremes_windows(atsc_ctx *ctx, uint32_t n_streams, c
     HostBody hb[MAX_INPUTS];
     for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
     return query_host(ctx, hb, n_windows, begin, count, out, AcrossExtQuery{n_streams, stride, count, n_windows, k});
+    ATSC_API_END
+}
+
+extern "C" int atsc_across_values_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                              const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                              const uint64_t *count, uint64_t stride, uint32_t k, double above, void *d_out,
+                                              void *stream)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
+        return fail(ctx, ATSC_E_INVALID, "across_values_windows: n_streams outside [1, 64], a null list or a null entry");
+    QueryInput in[MAX_INPUTS];
+    for (uint32_t j = 0; j < n_streams; ++j) in[j] = QueryInput{dp[j], d_body[j], 0};
+    return AcrossValQuery{n_streams, stride, count, n_windows, k, above}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    ATSC_API_END
+}
+
+extern "C" int atsc_across_values_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                                          const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                                          uint64_t stride, uint32_t k, double above, void *out)
+{
+    ATSC_API_BEGIN
+    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
+        return fail(ctx, ATSC_E_INVALID, "across_values_windows: n_streams outside [1, 64], a null list or a null entry");
+    if ((uintptr_t)out & 7u) return fail(ctx, ATSC_E_INVALID, "across_values_windows: out is not 8-byte aligned");
+    HostBody hb[MAX_INPUTS];
+    for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
+    return query_host(ctx, hb, n_windows, begin, count, out, AcrossValQuery{n_streams, stride, count, n_windows, k, above});
     ATSC_API_END
 }
 
@@ -4163,6 +4243,16 @@ extern "C" int atsc_stream_across_extremes_windows(atsc_stream *const *streams, 
     ATSC_API_BEGIN
     if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
     return query_stream(streams, n_windows, begin, count, out, AcrossExtQuery{n_streams, stride, count, n_windows, k});
+    ATSC_API_END
+}
+
+extern "C" int atsc_stream_across_values_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                                 const uint64_t *begin, const uint64_t *count, uint64_t stride, uint32_t k,
+                                                 double above, void *out)
+{
+    ATSC_API_BEGIN
+    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
+    return query_stream(streams, n_windows, begin, count, out, AcrossValQuery{n_streams, stride, count, n_windows, k, above});
     ATSC_API_END
 }
 

@@ -415,6 +415,26 @@ def _across_histogram_result(run, counts, stride, edges):
     return run(int(off[-1])).reshape(int(off[-1]), len(_levels(edges)[0]) + 2), off
 
 
+def _across_values_params(stride, records, k, above):
+    """the across' arguments, then k and above"""
+    a = _RollArgs(tuple(_across_params(stride, records)) + _values_params(k, above))
+    a.records = int(records)
+    return a
+
+
+def _across_values_block(n, cargs):
+    """(a k that the library refuses still gets a result to leave untouched)"""
+    return _values_dtype(cargs[1].value, None).itemsize * cargs.records
+
+
+def _across_values_result(run, counts, stride, k):
+    """run(records) -> the block of an across value-count call as uint64 words.  -> (records, off): the
+    window_values_dtype(k) records of every position, range after range, and the ranges' record offsets
+    (across_offsets)"""
+    off = across_offsets(counts, stride)
+    return run(int(off[-1])).view(_values_dtype(k, None)), off
+
+
 def _array_params(values, flag):
     """levels and method, or edges and closed"""
     a, pa = _levels(values)
@@ -446,6 +466,8 @@ _ACROSS_MOMENTS = _Query("across_moments_windows", np.dtype(np.uint64), None, _a
 # (the across quantiles' arguments serve: the stride, then the edges and the closed side in the levels' and the method's place)
 _ACROSS_HISTOGRAM = _Query("across_histogram_windows", np.dtype(np.uint64), None, _across_quantile_params, _across_histogram_block,
                            inputs=None)
+_ACROSS_VALUES = _Query("across_values_windows", np.dtype(np.uint64), None, _across_values_params, _across_values_block,
+                        inputs=None)
 # (the pair matrix takes its streams as lists, as the across calls do, and nothing of its own: `stride` is not passed on)
 _PAIR_MATRIX = _Query("pair_matrix_windows", np.dtype(np.uint64), None, _pair_matrix_params, _rolling_pair_block, inputs=None)
 _QUANTILE = _Query("quantile_windows", np.dtype(np.float64), 0, _array_params)
@@ -916,6 +938,20 @@ class Context:
         return _across_extremes_result(
             lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m, k, q=_ACROSS_EXTREMES), counts, stride, k)
 
+    def across_values_windows_host(self, records_list, begins, counts, k, stride=1, above=float("nan"), has_count=False):
+        """-> (records, off): which values the streams of records_list (at most ACROSS_MAX_STREAMS decoded record streams,
+        as across_windows_host takes them) hold at every `stride`-th position of every range
+        [begins[i], begins[i] + counts[i]), and how many streams hold each: PromQL's count_values
+        (atsc_across_values_windows).  records: an array of window_values_dtype(k), one per position, range after range:
+        the windowed value counts' record of the position's column -- count = len(records_list), the k smallest distinct
+        values above `above` (NaN: all of them) with the number of streams that hold each; values_merge over the records
+        of one position from sub-lists is the record of the whole list, values_mode reads the majority value off it.
+        off: across_offsets(counts, stride), range i's records being records[off[i]:off[i + 1]].  has_count holds for
+        every stream"""
+        return _across_values_result(
+            lambda m: _across_host(self, records_list, begins, counts, has_count, stride, m, k, above, q=_ACROSS_VALUES),
+            counts, stride, k)
+
     def across_moments_windows_host(self, records_list, begins, counts, stride=1, has_count=False):
         """-> (records, off): count, mean and m2 = sum (x - mean)^2 of the samples that the streams of records_list (at
         most ACROSS_MAX_STREAMS decoded record streams, as across_windows_host takes them) hold at every `stride`-th
@@ -1233,6 +1269,21 @@ class DPlan:
         m, size = int(off[-1]), _extremes_dtype(k).itemsize
         _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, m, k,
                     q=_ACROSS_EXTREMES)
+        return d_out.reshape(-1).view(torch.uint8)[: m * size].reshape(m, size), off
+
+    def across_values_windows(self, d_body, others, other_bodies, begins, counts, k, d_out, stride=1, above=float("nan"), stream=0):
+        """Enqueues which values this plan's stream and the plans `others` (their device bytes other_bodies) hold at every
+        `stride`-th position of the ranges [begins[i], begins[i] + counts[i]), and how many streams hold each, into
+        d_out, a device tensor of at least 32 + 16 k bytes per position (atsc_across_values_windows_dev): the k smallest
+        distinct values above `above` (NaN: all of them).  A plan may appear more than once.  -> (records, off): the view
+        of d_out's front as window_values_dtype(k) records, one per position (a uint8 tensor of 32 + 16 k bytes a row;
+        .cpu().numpy().view(window_values_dtype(k)) gives the fields), filled once `stream` has run, and the ranges'
+        record offsets (across_offsets)"""
+        import torch  # (d_out is a torch tensor: the module is loaded)
+        off = across_offsets(counts, stride)
+        m, size = int(off[-1]), _values_dtype(k, None).itemsize
+        _across_dev([self] + list(others), [d_body] + list(other_bodies), begins, counts, d_out, stream, stride, m, k, above,
+                    q=_ACROSS_VALUES)
         return d_out.reshape(-1).view(torch.uint8)[: m * size].reshape(m, size), off
 
     def across_moments_windows(self, d_body, others, other_bodies, begins, counts, d_out, stride=1, stream=0):

@@ -15,6 +15,7 @@ from .engine import _ROLLING_HISTOGRAM, _rolling_histogram_result
 from .engine import _ACROSS_EXTREMES, _across_extremes_result
 from .engine import _ACROSS_MOMENTS, _across_moments_result
 from .engine import _ACROSS_HISTOGRAM, _across_histogram_result
+from .engine import _ACROSS_VALUES, _across_values_result
 from .engine import _PAIR_MATRIX, _pair_matrix_result
 
 
@@ -240,6 +241,13 @@ class CompressedStream:
         return _across_histogram_result(
             lambda m: self._across_stream(_ACROSS_HISTOGRAM, others, begins, counts, stride, m, edges, closed), counts, stride, edges)
 
+    def across_values_windows(self, others, begins, counts, k, stride=1, above=float("nan")):
+        """-> (records, off): which values this stream and the streams `others` hold at every `stride`-th position of the
+        ranges [begins[i], begins[i] + counts[i]), and how many streams hold each, as
+        Context.across_values_windows_host gives them (atsc_stream_across_values_windows)"""
+        return _across_values_result(
+            lambda m: self._across_stream(_ACROSS_VALUES, others, begins, counts, stride, m, k, above), counts, stride, k)
+
     def across_extremes_windows(self, others, begins, counts, k, stride=1):
         """-> (records, off): the k largest and the k smallest of the samples that this stream (stream 0) and the streams
         `others` (stream 1 and on) hold at every `stride`-th position of the ranges [begins[i], begins[i] + counts[i]),
@@ -444,6 +452,15 @@ def across_histogram_data_windows(ctx, bros, begins, counts, edges, stride=1, cl
     return _across_histogram_result(
         lambda m: _across_host(ctx, records, begins, counts, True, stride, m, edges, closed, q=_ACROSS_HISTOGRAM), counts, stride,
         edges)
+
+
+def across_values_data_windows(ctx, bros, begins, counts, k, stride=1, above=float("nan")):
+    """-> (records, off): which values the streams decompress_data(ctx, bro) of every .bro image of the list `bros` hold
+    at every `stride`-th position of the ranges, and how many streams hold each, as Context.across_values_windows_host
+    gives them: atsc_bro_open of each image, then atsc_across_values_windows over their records"""
+    records = _across_images(bros)
+    return _across_values_result(
+        lambda m: _across_host(ctx, records, begins, counts, True, stride, m, k, above, q=_ACROSS_VALUES), counts, stride, k)
 
 
 def across_extremes_data_windows(ctx, bros, begins, counts, k, stride=1):

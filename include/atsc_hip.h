@@ -681,8 +681,9 @@ int atsc_extremes_merge(const void *records, uint64_t n, uint32_t k, void *out);
 
 /* Windowed value counts: per window [begin, begin + count) of the decoded stream (the indices of atsc_decompress_frames)
  * its k smallest distinct values with their exact multiplicities, from the same decoded samples as the window decode:
- * PromQL's count_values and "time in state" for every enum-like series (up, a replica count, an HTTP status, a leader
- * id, a breaker state, a config version), without knowing the values in advance.  One k, 1 <= k <= ATSC_VALUES_MAX_K,
+ * "time in each state" for every enum-like series (up, a replica count, an HTTP status, a leader id, a breaker state, a
+ * config version), without knowing the values in advance (PromQL's count_values, an aggregation across series at one
+ * instant, is atsc_across_values_windows, which returns this record per position).  One k, 1 <= k <= ATSC_VALUES_MAX_K,
  * holds for every window of a call.  The record of a window is ATSC_VALUES_BYTES(k) = 32 + 16 k bytes, 8-byte aligned: an
  * atsc_window_values_head, then entry[0 .. k), each an atsc_value_count; record i lies at
  * (char *)out + i * ATSC_VALUES_BYTES(k).
@@ -1443,6 +1444,61 @@ int atsc_across_histogram_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8
                                   const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                   uint64_t stride, uint32_t n_edges, const double *edges, int closed, uint64_t *out);
 
+/* Windowed across value counts: at every position of ranges of the decoded streams, which values the N streams of a call
+ * hold there and how many streams hold each, without knowing the values in advance.  This is PromQL's count_values
+ * proper, an aggregation across series at one instant: how many replicas report each build_info version at every step,
+ * how many members name each leader id, how many hosts are in each breaker state, whether the replicas of a config gauge
+ * agree at all.  (atsc_values_windows is the same record over one series in time: "time in each state".)
+ *   Ranges     atsc_across_windows' exactly: n_streams in 1 .. ATSC_ACROSS_MAX_STREAMS, one stride for the call, range i
+ *              has atsc_across_outputs(count[i], stride) positions, records are numbered range after range in the
+ *              across' record order.  The same plan may appear in the list more than once; all plans belong to one
+ *              context.
+ *   Result     record r is the ATSC_VALUES_BYTES(k) bytes at (char *)out + r * ATSC_VALUES_BYTES(k), in the windowed
+ *              value counts' layout: an atsc_window_values_head, then entry[0 .. k) of atsc_value_count.  One k,
+ *              1 <= k <= ATSC_VALUES_MAX_K, holds for a call.  The caller sizes the result: sum m_i x
+ *              ATSC_VALUES_BYTES(k) bytes.  The call writes every byte of every record: the caller does not have to
+ *              clear the result.
+ *   Record     atsc_values_windows' rule, unchanged, applied to the column x_0 .. x_(N-1) of the streams' samples at the
+ *              position as if it were a window of N samples: count = n_streams, always; nans = the NaN ones; above and
+ *              below keep their windowed meaning (above NaN lists every non-NaN sample, else only x > above, and below
+ *              counts the non-NaN samples not listed); -0.0 and +0.0 are one class, reported as +0.0; +-Inf are ordinary
+ *              values; entries ascending, unused entries (NaN, 0); distinct = min(D, k) and more = (D > k), D the number
+ *              of distinct listed values.  D can reach 64 and k only 32: calling again with above set to the last listed
+ *              value walks a column exactly, in ceil(D / k) calls.
+ * No arithmetic touches a sample, so the record is bit-exact.  It depends on the N samples of its position, k and above
+ * alone: not on the order of the list, the range that reached the position, the stride, the other ranges, the budget,
+ * the piece boundaries, the framing, the device, or which of the three forms (device, host, stream) was called.  It
+ * follows that
+ *              - the record equals atsc_values_merge of the N streams' atsc_values_windows records of the window
+ *                (position, 1), with the same k and above (with n_streams == 1 it is that record, byte for byte);
+ *              - atsc_values_merge over the records of sub-lists gives the whole list's record byte for byte (the merge
+ *                already allows parts from different streams): a list of more than ATSC_ACROSS_MAX_STREAMS streams is
+ *                queried that way, and there is no new merge function;
+ *              - atsc_values_mode applies unchanged: the majority value at every step;
+ *              - count - nans equals atsc_across_windows' count at that position;
+ *              - with above NaN and a non-NaN sample, entry[0].value equals the across' min as a value;
+ *              - the sum of the n of the entries whose value falls in a bin equals that bin of
+ *                atsc_across_histogram_windows (more == 0, above NaN).
+ * Errors: ATSC_E_INVALID with nothing written and before any GPU work for every case of atsc_across_windows, for k == 0
+ * or k > ATSC_VALUES_MAX_K, a result pointer that is not 8-byte aligned.  The messages name across_values_windows.
+ * n_windows == 0 and empty ranges write nothing.  Scratch and pieces are the across': there is no ATSC_E_CAPACITY case. */
+/* dp / d_body (n_streams entries each), begin / count are HOST arrays; d_body[j] and d_out are device memory (d_out
+ * 8-byte aligned, ATSC_VALUES_BYTES(k) bytes per position).  Enqueued on `stream`, not synchronised.  A malformed
+ * payload in a frame of stream j that a range touches sets dp[j]'s status word.  dp[0] keeps the call's tables and scratch
+ * in the place of the across quantiles', which the across extremes, moments and histograms share: the next across call
+ * of any of these five kinds whose first plan is dp[0] waits (host side) until this one's work is done;
+ * atsc_dplan_destroy frees them. */
+int atsc_across_values_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp,
+                                   const uint8_t *const *d_body, uint64_t n_windows, const uint64_t *begin,
+                                   const uint64_t *count, uint64_t stride, uint32_t k, double above, void *d_out,
+                                   void *stream);
+/* Host bytes in (n_streams bodies, lengths and has_count flags), host records out, synchronous; walks and uploads only
+ * the touched records of every stream, as atsc_across_windows does, and computes the device call's bytes.  ATSC_E_FORMAT
+ * (nothing written) for a malformed payload in a frame of any stream that a range touches. */
+int atsc_across_values_windows(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                               const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
+                               uint64_t stride, uint32_t k, double above, void *out);
+
 /* ------------------------------------------------------------------------ */
 /* CompressedStream mirror (atsc/src/data.rs:29-110)                          */
 /* ------------------------------------------------------------------------ */
@@ -1542,6 +1598,11 @@ int atsc_stream_across_moments_windows(atsc_stream *const *streams, uint32_t n_s
 int atsc_stream_across_histogram_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
                                          const uint64_t *begin, const uint64_t *count, uint64_t stride, uint32_t n_edges,
                                          const double *edges, int closed, uint64_t *out);
+/* atsc_across_values_windows over the frames of the n_streams streams of the list, which must belong to one context
+ * (else ATSC_E_INVALID) */
+int atsc_stream_across_values_windows(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows,
+                                      const uint64_t *begin, const uint64_t *count, uint64_t stride, uint32_t k,
+                                      double above, void *out);
 /* atsc_quantile_windows over the stream's frames */
 int atsc_stream_quantile_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
                                  uint32_t n_q, const double *q, int method, double *out);
