@@ -17,7 +17,7 @@ CLI2 = os.path.join(HERE, "bin", "csv-compressor")
 CLI2_SRC = "csv_compressor_cli.cpp"
 CLI_HEADER = "atsc_cli_buckets.h"  # what the two front ends share; no library source includes it
 DEPS = SOURCES + ["atsc_device.h", "atsc_internal.h", "atsc_host_private.h", "atsc_large_cols.h", "atsc_large_fast.h",
-                  "atsc_tile_reduce.h", "atsc_moment_node.h", "atsc_rolling_node.h", "atsc_moment_rule.h", "atsc_quantile_rule.h", "atsc_hist_bins.h", os.path.join("..", "..", "include", "atsc_hip.h")]
+                  "atsc_tile_reduce.h", "atsc_across_positions.h", "atsc_moment_node.h", "atsc_rolling_node.h", "atsc_moment_rule.h", "atsc_quantile_rule.h", "atsc_hist_bins.h", os.path.join("..", "..", "include", "atsc_hip.h")]
 # -ffp-contract=off: the f64 spline / rounding arithmetic must evaluate exactly as written
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -40,7 +40,7 @@ def stale():
 
 OBJDIR = os.path.join(HERE, "build" + ("_" + VARIANT if VARIANT else ""))
 HEADERS = ["atsc_device.h", "atsc_internal.h", "atsc_host_private.h", "atsc_large_cols.h", "atsc_large_fast.h",
-           "atsc_tile_reduce.h", "atsc_moment_node.h", "atsc_rolling_node.h", "atsc_moment_rule.h", "atsc_quantile_rule.h", "atsc_hist_bins.h", os.path.join("..", "..", "include", "atsc_hip.h")]
+           "atsc_tile_reduce.h", "atsc_across_positions.h", "atsc_moment_node.h", "atsc_rolling_node.h", "atsc_moment_rule.h", "atsc_quantile_rule.h", "atsc_hist_bins.h", os.path.join("..", "..", "include", "atsc_hip.h")]
 CFLAGS = [f for f in FLAGS if f != "-shared"] + os.environ.get("ATSC_BUILD_DEFS", "").split()
 
 

@@ -1,18 +1,17 @@
 // atsc_across.hip -- gfx950 kernel of the windowed across (atsc_across_windows_dev): count, min, max and sum over the N
 // streams of a call at every position of a range, from the streams' decoded samples in the call's scratch.
 //
-// The contract is include/atsc_hip.h's (DESIGN.md "Windowed across").  Every stream of the call is decoded into a region
-// of its own; slot j of every region of a piece is the same sample index, so a position reads one slot per stream and
-// folds them in list order: min and max keep the first of equal values, the sum is ((t_0 + t_1) + t_2) + .. with t_k the
-// sample, or -0.0 where it is NaN.  One wavefront per task (a run of positions of one range inside one piece), a lane
-// per position; the loop over the streams is the same in every lane.  At stride 1 a lane takes two adjacent positions
-// whose first slot is even, with one 16-byte load per stream; the odd first and last position of a run, and every
-// position at another stride, go one slot at a time through the same fold, so both give the same bytes.  No atomics,
-// no LDS: every record has one writer.
+// The contract is include/atsc_hip.h's (DESIGN.md "Windowed across"); the regions, the tasks and what the across kernels
+// share are atsc_across_positions.h's.  A position reads one slot per stream and folds them in list order: min and max
+// keep the first of equal values, the sum is ((t_0 + t_1) + t_2) + .. with t_k the sample, or -0.0 where it is NaN.  One
+// wavefront per task, a lane per position in a lane-strided loop (the fold is short); the loop over the streams is the
+// same in every lane.  At stride 1 a lane takes two adjacent positions whose first slot is even (pair_split); the odd
+// first and last position of a run, and every position at another stride, go one slot at a time through the same fold,
+// so both give the same bytes.  No LDS.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "atsc_tile_reduce.h"
+#include "atsc_across_positions.h"
 
 namespace atsc {
 
@@ -44,8 +43,7 @@ DEVI void across_step(AcrossAcc &a, double v, uint32_t k)
     a.count += ok ? 1u : 0u;
 }
 
-// A16: the result lies at a multiple of 16 bytes (the same for every record: a record is 32 bytes), and a record goes out
-// as two 16-byte stores; else as four of 8 bytes, at the alignment the contract asks of the result
+// A16: the result lies at a multiple of 16 bytes (the same for every record: a record is 32 bytes)
 template <bool A16>
 DEVI void across_store(AcrossRec *p, const AcrossAcc &a)
 {
@@ -53,15 +51,8 @@ DEVI void across_store(AcrossRec *p, const AcrossAcc &a)
     const bool any = a.count != 0;
     const uint64_t head = (uint64_t)a.count | ((uint64_t)(a.mn_at & 0xFFFFu) << 32) | ((uint64_t)(a.mx_at & 0xFFFFu) << 48);
     const double mn = any ? a.mn : nan, mx = any ? a.mx : nan, sum = any ? a.sum : 0.0;
-    if constexpr (A16) {
-        ((double2 *)p)[0] = make_double2(__longlong_as_double((long long)head), mn);
-        ((double2 *)p)[1] = make_double2(mx, sum);
-    } else {
-        p->head = head;
-        p->mn = mn;
-        p->mx = mx;
-        p->sum = sum;
-    }
+    store_words<A16>((uint64_t *)p, head, (uint64_t)__double_as_longlong(mn));
+    store_words<A16>((uint64_t *)p + 2, (uint64_t)__double_as_longlong(mx), (uint64_t)__double_as_longlong(sum));
 }
 
 // the position whose slot is `slot` of every region
@@ -77,9 +68,7 @@ DEVI void across_one(const double *__restrict__ scratch, const uint64_t *__restr
 
 }  // namespace
 
-// One wavefront per DevRollTask: t.n positions, the first at sample t.lo of the streams, the others every `stride`
-// samples behind it, into out[t.rec ..].  reg[k]: where stream k's region begins in the scratch (an even number of
-// doubles); slot 0 of every region is sample a0 (even) of the streams.
+// One wavefront per DevRollTask, into out[t.rec ..].
 template <bool A16>
 __global__ __launch_bounds__(256) void k_across_positions(const DevRollTask *__restrict__ tasks, uint32_t n,
                                                           const double *__restrict__ scratch,
@@ -95,9 +84,9 @@ __global__ __launch_bounds__(256) void k_across_positions(const DevRollTask *__r
         for (uint32_t p = lane; p < t.n; p += 64u) across_one<A16>(scratch, reg, ns, s0 + (uint64_t)p * stride, o + p);
         return;
     }
-    // stride 1: an odd first slot and what is left behind the pairs one at a time, the rest in pairs from an even slot
-    const uint32_t head = t.n ? (uint32_t)(s0 & 1u) : 0u, pairs = (t.n - head) >> 1, tail = (t.n - head) & 1u;
-    for (uint32_t j = lane; j < pairs; j += 64u) {
+    const PairSplit sp = pair_split(s0, t.n);
+    const uint32_t head = sp.head;
+    for (uint32_t j = lane; j < sp.pairs; j += 64u) {
         const uint64_t slot = s0 + head + 2ull * j;
         AcrossAcc a = across_none(), b = across_none();
 #pragma unroll 4
@@ -110,7 +99,7 @@ __global__ __launch_bounds__(256) void k_across_positions(const DevRollTask *__r
         across_store<A16>(o + head + 2u * j + 1u, b);
     }
     if (head && lane == 0) across_one<A16>(scratch, reg, ns, s0, o);
-    if (tail && lane == 1) across_one<A16>(scratch, reg, ns, s0 + t.n - 1u, o + (t.n - 1u));
+    if (sp.tail && lane == 1) across_one<A16>(scratch, reg, ns, s0 + t.n - 1u, o + (t.n - 1u));
 }
 
 hipError_t launch_across_positions(const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg,

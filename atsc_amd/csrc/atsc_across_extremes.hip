@@ -3,9 +3,8 @@
 // index of the stream that holds each.
 //
 // The contract is include/atsc_hip.h's (DESIGN.md "Windowed across extremes"): the windowed extremes' record of the
-// column x_0 .. x_(N-1), a sample's offset being its stream's place in the list.  The streams lie decoded in the call's
-// scratch as the windowed across leaves them (atsc_across.hip): a region per stream, slot j of every region the same
-// sample index.  A lane per position, one wavefront per 64 positions of a task, as in atsc_across_quantile.hip.
+// column x_0 .. x_(N-1), a sample's offset being its stream's place in the list.  The regions, the tasks and the mapping
+// of positions to lanes are atsc_across_positions.h's.
 //
 // A lane keeps two sorted lists of KP entries (value, stream index) in registers, KP the power of two >= k.  It walks
 // the streams in list order -- the loop is the same in every lane -- and puts every sample that is not NaN through a
@@ -19,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "atsc_tile_reduce.h"
+#include "atsc_across_positions.h"
 
 namespace atsc {
 
@@ -69,36 +68,19 @@ DEVI void aex_insert(AexList<KP> &l, double x, uint32_t k, bool ok)
     l.at[0] = c[0] ? k : l.at[0];
 }
 
-// A16: the result lies at a multiple of 16 bytes (a record is 16 + 32 k bytes, so every entry of every record does),
-// and an entry goes out as one 16-byte store; else as two of 8 bytes, at the alignment the contract asks of the result
-template <bool A16>
-DEVI void aex_store(uint64_t *p, uint64_t a, uint64_t b)
-{
-    if constexpr (A16) {
-        *(ulonglong2 *)p = make_ulonglong2(a, b);
-    } else {
-        p[0] = a;
-        p[1] = b;
-    }
-}
-
+// A16: the result lies at a multiple of 16 bytes (a record is 16 + 32 k bytes, so every entry of every record does)
 template <bool A16, int KP>
 DEVI void aex_store_list(uint64_t *p, const AexList<KP> &l, uint32_t k)
 {
 #pragma unroll
     for (int j = 0; j < KP; ++j)
         if ((uint32_t)j < k)
-            aex_store<A16>(p + 2 * j, (uint64_t)__double_as_longlong(l.v[j]), l.at[j] == AEX_NONE ? ~0ull : (uint64_t)l.at[j]);
+            store_words<A16>(p + 2 * j, (uint64_t)__double_as_longlong(l.v[j]), l.at[j] == AEX_NONE ? ~0ull : (uint64_t)l.at[j]);
 }
 
 }  // namespace
 
-// A task's positions go 64 to a wavefront, ACR_SLABS wavefronts a task, as the across quantiles' do.
-constexpr uint32_t AEX_SLABS = ACR_TASK / 64u;
-
-// DevRollTask t: t.n positions, the first at sample t.lo of the streams, the others every `stride` samples behind it;
-// position p's record is the 2 + 4 k words at out[(t.rec + p) (2 + 4 k) ..].  reg[s]: where stream s's region begins
-// in the scratch; slot 0 of every region is sample a0 of the streams.  1 <= k <= KP, ns >= 1.
+// Position p's record is the 2 + 4 k words at out[(t.rec + p) (2 + 4 k) ..].  1 <= k <= KP, ns >= 1.
 template <int KP, bool A16>
 __global__ __launch_bounds__(256) void k_across_extremes_positions(const DevRollTask *__restrict__ tasks, uint32_t n,
                                                                    const double *__restrict__ scratch,
@@ -106,12 +88,10 @@ __global__ __launch_bounds__(256) void k_across_extremes_positions(const DevRoll
                                                                    uint64_t a0, uint64_t stride, uint32_t k,
                                                                    uint64_t *__restrict__ out)
 {
-    const uint32_t lane = wave_lane(), w = wave_task(), i = w / AEX_SLABS;
-    if (i >= n) return;
-    const DevRollTask t = tasks[i];
-    const uint32_t p = (w % AEX_SLABS) * 64u + lane;
-    if (p >= t.n) return;
-    const uint64_t slot = t.lo - a0 + (uint64_t)p * stride;
+    DevRollTask t;
+    uint32_t p;
+    if (!slab_position(tasks, n, t, p)) return;
+    const uint64_t slot = slab_slot(t, a0, p, stride);
     AexList<KP> big, small;
     aex_clear(big);
     aex_clear(small);
@@ -126,7 +106,7 @@ __global__ __launch_bounds__(256) void k_across_extremes_positions(const DevRoll
         aex_insert<false>(small, x, s, ok);
     }
     uint64_t *rec = out + (t.rec + p) * (2u + 4ull * k);
-    aex_store<A16>(rec, ns, nans);
+    store_words<A16>(rec, ns, nans);
     aex_store_list<A16>(rec + 2, big, k);
     aex_store_list<A16>(rec + 2 + 2ull * k, small, k);
 }
@@ -135,25 +115,13 @@ hipError_t launch_across_extremes_positions(const DevRollTask *tasks, uint32_t n
                                             uint32_t n_streams, uint64_t a0, uint64_t stride, uint32_t k, void *out,
                                             hipStream_t s)
 {
-    static_assert(ACR_TASK % 64u == 0, "whole wavefronts");
-    if (n > 0xFFFFFFFFu / AEX_SLABS) return hipErrorInvalidValue;  // (more tasks in a piece than a grid has wavefronts)
     if (k == 0 || n_streams == 0) return hipErrorInvalidValue;
     const bool a16 = ((uintptr_t)out & 15u) == 0;
-#define ACROSS_EXTREMES_KP(KP)                                                                                          \
-    if (k <= KP) {                                                                                                      \
-        if (a16)                                                                                                        \
-            return launch_wave_tasks(k_across_extremes_positions<KP, true>, n * AEX_SLABS, s, tasks, n, scratch, reg,  \
-                                     n_streams, a0, stride, k, (uint64_t *)out);                                       \
-        return launch_wave_tasks(k_across_extremes_positions<KP, false>, n * AEX_SLABS, s, tasks, n, scratch, reg,     \
-                                 n_streams, a0, stride, k, (uint64_t *)out);                                           \
-    }
-    ACROSS_EXTREMES_KP(1)
-    ACROSS_EXTREMES_KP(2)
-    ACROSS_EXTREMES_KP(4)
-    ACROSS_EXTREMES_KP(8)
-    ACROSS_EXTREMES_KP(16)
-#undef ACROSS_EXTREMES_KP
-    return hipErrorInvalidValue;
+    return pow2_dispatch<16>(k, [&](auto kp) {
+        constexpr int KP = decltype(kp)::value;
+        return launch_slab_tasks(a16 ? k_across_extremes_positions<KP, true> : k_across_extremes_positions<KP, false>, n, s, tasks,
+                                 n, scratch, reg, n_streams, a0, stride, k, (uint64_t *)out);
+    });
 }
 
 }  // namespace atsc

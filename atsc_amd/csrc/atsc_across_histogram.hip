@@ -4,14 +4,10 @@
 //
 // The contract is include/atsc_hip.h's (DESIGN.md "Windowed across histograms"): a position's row is n_edges + 2 u64
 // counters, bins 0 .. n_edges by bin_of (atsc_hist_bins.h, the text atsc_histogram.hip bins with), then the NaN
-// samples; it is the sum over the streams of atsc_histogram_windows' rows of the window (position, 1).  The streams lie
-// decoded in the call's scratch as the windowed across leaves them (atsc_across.hip): a region per stream, slot j of
-// every region the same sample index.
-//
-// A task (DevRollTask) is up to ACR_TASK consecutive positions of one range; a wavefront takes 64 of them, a lane per
-// position, as k_across_moments_positions does, so a task is spread over ACR_TASK / 64 wavefronts and a workgroup of
-// 256 threads runs four of them.  Dynamic LDS: the edges once, then per wavefront G rows of byte counters (a count
-// cannot pass 64 streams) at a pitch of an odd number of 4-byte words:
+// samples; it is the sum over the streams of atsc_histogram_windows' rows of the window (position, 1).  The regions, the
+// tasks and the wavefront's 64 positions of a task are atsc_across_positions.h's (slab_wave); a workgroup of 256 threads
+// runs four wavefronts.  Dynamic LDS: the edges once, then per wavefront G rows of byte counters (a count cannot pass
+// 64 streams) at a pitch of an odd number of 4-byte words:
 //   words = ceil((n_edges + 2) / 4) | 1,  pitch = 4 words,  G = min(64, floor(14336 / pitch))   (ah_rows_a_pass)
 // -- 64 rows up to n_edges = 218, 62 at 219, 13 at 1024; 8 n_edges + 4 G pitch <= 65536 bytes a workgroup, and 3.2 KB
 // at 10 edges, so that the wavefront slots and not the LDS bound the occupancy there.  The odd pitch sends the lanes of
@@ -30,19 +26,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "atsc_device.h"
+#include "atsc_across_positions.h"
 #include "atsc_hist_bins.h"
-#include "atsc_tile_reduce.h"
 
 namespace atsc {
 
-constexpr uint32_t AH_SLABS = ACR_TASK / 64u;  // wavefronts per task
-constexpr uint32_t AH_BATCH = 8;               // streams whose samples a lane loads together
+constexpr uint32_t AH_BATCH = 8;  // streams whose samples a lane loads together
 
-// DevRollTask t: t.n <= ACR_TASK positions, the first at sample t.lo of the streams, the others every `stride` samples
-// behind it; position p's row is the n_edges + 2 counters at out[(t.rec + p) (n_edges + 2) ..].  reg[k]: where stream k's
-// region begins in the scratch; slot 0 of every region is sample a0 of the streams.  G rows of `pitch` bytes a
-// wavefront (ah_rows_a_pass, ah_row_pitch).
+// Position p's row is the n_edges + 2 counters at out[(t.rec + p) (n_edges + 2) ..].  G rows of `pitch` bytes a wavefront
+// (ah_rows_a_pass, ah_row_pitch).
 template <int CLOSED>
 __global__ __launch_bounds__(256) void k_across_histogram_positions(const DevRollTask *__restrict__ tasks, uint32_t n,
                                                                     const double *__restrict__ scratch,
@@ -53,13 +45,14 @@ __global__ __launch_bounds__(256) void k_across_histogram_positions(const DevRol
 {
     extern __shared__ double s_mem[];
     double *s_edge = s_mem;
-    const uint32_t rows = n_edges + 2u, lane = wave_lane(), w = wave_task(), i = w / AH_SLABS;
+    const uint32_t rows = n_edges + 2u, lane = wave_lane();
+    uint32_t i, p0;  // the wavefront's task and its first position of it: the lanes change roles between the steps
+    const bool listed = slab_wave(n, i, p0);
     uint8_t *cnt = (uint8_t *)(s_mem + n_edges) + (threadIdx.x >> 6) * G * pitch;
     load_edges(s_edge, edges, n_edges);
-    __syncthreads();
-    if (i >= n) return;
+    __syncthreads();  // (in front of every return)
+    if (!listed) return;
     const DevRollTask t = tasks[i];
-    const uint32_t p0 = (w % AH_SLABS) * 64u;  // the wavefront's first position of the task
     if (p0 >= t.n) return;
     const uint32_t m = min(64u, t.n - p0);
     const uint64_t s0 = t.lo - a0 + (uint64_t)p0 * stride;
@@ -107,13 +100,12 @@ hipError_t launch_across_histogram_positions(const DevRollTask *tasks, uint32_t 
                                              uint32_t n_streams, uint64_t a0, uint64_t stride, const double *edges,
                                              uint32_t n_edges, int closed, uint64_t *out, hipStream_t s)
 {
-    static_assert(ACR_TASK % 64u == 0, "whole wavefronts");
     static_assert(8u * HST_MAX_EDGES + 4u * AH_WAVE_LDS <= 65536u, "a workgroup's LDS");
     if (n == 0) return hipSuccess;
-    if (n > 0xFFFFFFFFu / AH_SLABS) return hipErrorInvalidValue;  // (more tasks in a piece than a grid has wavefronts)
+    if (!slab_grid_fits(n)) return hipErrorInvalidValue;
     if (n_streams == 0 || n_streams > 255u || n_edges == 0 || n_edges > HST_MAX_EDGES || ((uintptr_t)out & 7u))
         return hipErrorInvalidValue;
-    const uint32_t G = ah_rows_a_pass(n_edges), pitch = ah_row_pitch(n_edges), grid = (n * AH_SLABS + 3u) / 4u;
+    const uint32_t G = ah_rows_a_pass(n_edges), pitch = ah_row_pitch(n_edges), grid = (n * ACR_SLABS + 3u) / 4u;
     const size_t lds = (size_t)n_edges * sizeof(double) + 4u * (size_t)G * pitch;
     if (closed == ATSC_HIST_RIGHT_CLOSED)
         hipLaunchKernelGGL(k_across_histogram_positions<ATSC_HIST_RIGHT_CLOSED>, dim3(grid), dim3(256), lds, s, tasks, n, scratch,

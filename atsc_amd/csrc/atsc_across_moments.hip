@@ -5,23 +5,22 @@
 // The contract is include/atsc_hip.h's (DESIGN.md "Windowed across moments"): the x half of
 // Merge(.. Merge(Merge(leaf_0, leaf_1), leaf_2) .., leaf_(N-1)), Merge being the windowed moments' rule
 // (atsc_moment_rule.h, the one copy of it) and leaf_k the node of stream k's sample, empty where that is NaN.  The
-// position half of a node (mt, m2t, c) is fed zeros and never stored: the compiler drops it.  The streams lie decoded in
-// the call's scratch as the windowed across leaves them (atsc_across.hip): a region per stream, slot j of every region
-// the same sample index.
+// position half of a node (mt, m2t, c) is fed zeros and never stored: the compiler drops it.  The regions, the tasks and
+// the mapping of positions to lanes are atsc_across_positions.h's.
 //
-// A lane per position; the loop over the streams is the same in every lane, and a lane's node and NaN count stay in
-// registers: no LDS, no atomics, no scratch memory, one writer per record.  A task's positions are spread over several
-// wavefronts (as in atsc_across_quantile.hip), since a lane's fold is a chain of N dependent merges with a divide each.
-//   stride != 1   64 positions to a wavefront, ACR_TASK / 64 wavefronts a task; a record goes out as three 8-byte stores.
-//   stride == 1   a lane takes two adjacent positions whose first slot is even, with one 16-byte load per stream, as the
-//                 across does: 64 pairs to a wavefront, ACR_TASK / 128 wavefronts a task.  The two records are 48
-//                 adjacent bytes and go out as three 16-byte stores where they begin at a multiple of 16, else as 8, 16,
-//                 16 and 8 bytes.  The odd first and last position of a task go one at a time through the same fold.
+// The loop over the streams is the same in every lane, and a lane's node and NaN count stay in registers: no LDS, no
+// scratch memory.  A lane's fold is a chain of N dependent merges with a divide each.
+//   stride != 1   the shared mapping; a record goes out as three 8-byte stores.
+//   stride == 1   a lane takes two adjacent positions whose first slot is even (pair_split): 64 pairs to a wavefront,
+//                 ACR_TASK / 128 wavefronts a task.  The two records are 48 adjacent bytes and go out as three 16-byte
+//                 stores where they begin at a multiple of 16, else as 8, 16, 16 and 8 bytes.  The odd first and last
+//                 position of a task go one at a time through the same fold.
 // Both paths put the same samples through the same merges in the same order: the same bytes.
 // 1.0 / (double)n is a divide, as the rule writes it (DESIGN.md says what a table of the 64 quotients would need).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "atsc_across_positions.h"
 #include "atsc_moment_node.h"
 
 namespace atsc {
@@ -88,31 +87,30 @@ DEVI void amo_store_two(uint64_t *p, const AmoRec &a, const AmoRec &b)
 
 }  // namespace
 
-// wavefronts per task: 64 positions each, or 64 pairs of positions at stride 1
-constexpr uint32_t AMO_SLABS = ACR_TASK / 64u, AMO_PAIR_SLABS = ACR_TASK / 128u;
+// wavefronts per task at stride 1: 64 pairs of positions each
+constexpr uint32_t AMO_PAIR_SLABS = ACR_TASK / 128u;
 
-// DevRollTask t: t.n <= ACR_TASK positions, the first at sample t.lo of the streams, the others every `stride` samples
-// behind it; position p's record is the three words at out[3 (t.rec + p) ..].  reg[k]: where stream k's region begins
-// in the scratch (an even number of doubles); slot 0 of every region is sample a0 (even) of the streams.  PAIRS: stride
-// is 1.
+// Position p's record is the three words at out[3 (t.rec + p) ..].  PAIRS: stride is 1.
 template <bool PAIRS>
 __global__ __launch_bounds__(256) void k_across_moments_positions(const DevRollTask *__restrict__ tasks, uint32_t n,
                                                                   const double *__restrict__ scratch,
                                                                   const uint64_t *__restrict__ reg, uint32_t ns, uint64_t a0,
                                                                   uint64_t stride, uint64_t *__restrict__ out)
 {
-    constexpr uint32_t SLABS = PAIRS ? AMO_PAIR_SLABS : AMO_SLABS;
-    const uint32_t lane = wave_lane(), w = wave_task(), i = w / SLABS;
-    if (i >= n) return;
-    const DevRollTask t = tasks[i];
-    const uint64_t s0 = t.lo - a0;
-    uint64_t *o = out + 3ull * t.rec;
-    const uint32_t j = (w % SLABS) * 64u + lane;  // the lane's position of the task, or its pair
     if constexpr (!PAIRS) {
-        if (j < t.n) amo_one(scratch, reg, ns, s0 + (uint64_t)j * stride, o + 3ull * j);
+        DevRollTask t;
+        uint32_t p;
+        if (!slab_position(tasks, n, t, p)) return;
+        amo_one(scratch, reg, ns, slab_slot(t, a0, p, stride), out + 3ull * t.rec + 3ull * p);
     } else {
-        // an odd first slot and what is left behind the pairs one at a time, the rest in pairs from an even slot
-        const uint32_t head = t.n ? (uint32_t)(s0 & 1u) : 0u, pairs = (t.n - head) >> 1, tail = (t.n - head) & 1u;
+        uint32_t i, j;
+        if (!slab_wave<AMO_PAIR_SLABS>(n, i, j)) return;
+        j += wave_lane();  // the lane's pair of the task
+        const DevRollTask t = tasks[i];
+        const uint64_t s0 = t.lo - a0;
+        uint64_t *o = out + 3ull * t.rec;
+        const PairSplit sp = pair_split(s0, t.n);
+        const uint32_t head = sp.head, pairs = sp.pairs, tail = sp.tail;
         if (j < pairs) {
             const uint64_t slot = s0 + head + 2ull * j;
             AmoAcc a = amo_none(), b = amo_none();
@@ -137,12 +135,11 @@ hipError_t launch_across_moments_positions(const DevRollTask *tasks, uint32_t n,
                                            uint32_t n_streams, uint64_t a0, uint64_t stride, void *out, hipStream_t s)
 {
     static_assert(ACR_TASK % 128u == 0 && (ACR_TASK & (ACR_TASK - 1u)) == 0, "whole wavefronts of pairs; the index mask");
-    if (n > 0xFFFFFFFFu / AMO_SLABS) return hipErrorInvalidValue;  // (more tasks in a piece than a grid has wavefronts)
     if (n_streams == 0 || ((uintptr_t)out & 7u)) return hipErrorInvalidValue;
     if (stride == 1)
-        return launch_wave_tasks(k_across_moments_positions<true>, n * AMO_PAIR_SLABS, s, tasks, n, scratch, reg, n_streams, a0,
-                                 stride, (uint64_t *)out);
-    return launch_wave_tasks(k_across_moments_positions<false>, n * AMO_SLABS, s, tasks, n, scratch, reg, n_streams, a0, stride,
+        return launch_slab_tasks<AMO_PAIR_SLABS>(k_across_moments_positions<true>, n, s, tasks, n, scratch, reg, n_streams, a0,
+                                                 stride, (uint64_t *)out);
+    return launch_slab_tasks(k_across_moments_positions<false>, n, s, tasks, n, scratch, reg, n_streams, a0, stride,
                              (uint64_t *)out);
 }
 

@@ -3493,262 +3493,199 @@ static int across_dev(atsc_ctx *ctx, const QueryInput *in, int n_in, uint64_t n_
     return ATSC_OK;
 }
 
-// the across' descriptor (see AggQuery): the number of streams is the call's own (INPUTS == 0, inputs()); it and the
-// stride are the call's parameters, and the size of its result follows from the ranges' lengths, as the rolling's does
-struct AcrossQuery {
+// What the six across descriptors share (see AggQuery): the number of streams is the call's own (INPUTS == 0, inputs());
+// it and the stride are the call's parameters, and the size of a result follows from the ranges' lengths, as the
+// rolling's does.  A query adds CALL, its own parameters, out_bytes (positions(n) records of its size), check (the
+// ranges, then its parameters: the first check that fails decides the code and the message) and dev, which describes
+// its position kernel to across_dev (run).  Every query but the across keeps its tables and scratch in the across
+// quantiles' place on in[0].dp (Q_ACROSS_QUANTILE): those kinds of call on one first plan wait for each other, and
+// atsc_dplan stays as it is (DESIGN.md "Windowed across extremes").
+struct AcrossBase {
     static constexpr int INPUTS = 0;
-    static constexpr const char *CALL = "across_windows";
     uint32_t n_streams;
     uint64_t stride;
     const uint64_t *count;  // the call's ranges' lengths
     uint64_t n_ranges;
     int inputs() const { return (int)n_streams; }
-    size_t out_bytes(uint64_t n) const
+    uint64_t positions(uint64_t n) const
     {
         uint64_t total = 0;
         for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
-        return total * sizeof(atsc_across_record);
+        return total;
     }
-    int check(atsc_ctx *ctx) const { return across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, nullptr); }
-    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
-    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
-            void *stream) const
+    int check_ranges(atsc_ctx *ctx, const char *call, uint64_t *total = nullptr) const
     {
-        const uint32_t ns = n_streams;
-        const uint64_t st = stride;
-        const AcrossKernel K{CALL, "no across kernels", "launch k_across_positions", Q_ACROSS, BY_ACROSS,
-                             launch_across_positions != nullptr, nullptr, 0,
-                             [ns, st](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
-                                      const void *, void *d_out, hipStream_t s) {
-                                 return launch_across_positions(tasks, n, scratch, reg, ns, a0, st, d_out, s);
-                             }};
+        return across_check(ctx, call, n_streams, count ? n_ranges : 0, count, stride, total);
+    }
+    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
+    int run(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
+            void *stream, const AcrossKernel &K) const
+    {
         return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
     }
 };
 
-// the across quantiles' descriptor: the across' ranges, stride and records, a row of n_q levels per record; the levels
-// and the method are checked as the windowed quantiles check theirs (quantile_check_levels) and go up with the call's tables
-struct AcrossQntQuery {
-    static constexpr int INPUTS = 0;
+// the across' descriptor: no parameter of its own, and no check in front of across_dev's
+struct AcrossQuery : AcrossBase {
+    static constexpr const char *CALL = "across_windows";
+    size_t out_bytes(uint64_t n) const { return positions(n) * sizeof(atsc_across_record); }
+    int check(atsc_ctx *ctx) const { return check_ranges(ctx, CALL); }
+    int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
+            void *stream) const
+    {
+        return run(ctx, in, n_windows, begin, cnt, d_res, stream,
+                   {CALL, "no across kernels", "launch k_across_positions", Q_ACROSS, BY_ACROSS, launch_across_positions != nullptr,
+                    nullptr, 0,
+                    [this](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
+                           const void *, void *d_out, hipStream_t s) {
+                        return launch_across_positions(tasks, n, scratch, reg, n_streams, a0, stride, d_out, s);
+                    }});
+    }
+};
+
+// the across quantiles' descriptor: a row of n_q levels per record; the levels and the method are checked as the
+// windowed quantiles check theirs (quantile_check_levels) and go up with the call's tables
+struct AcrossQntQuery : AcrossBase {
     static constexpr const char *CALL = "across_quantile_windows";
-    uint32_t n_streams;
-    uint64_t stride;
-    const uint64_t *count;  // the call's ranges' lengths
-    uint64_t n_ranges;
     uint32_t n_q;
     const double *q;
     int method;
-    int inputs() const { return (int)n_streams; }
-    size_t out_bytes(uint64_t n) const
-    {
-        uint64_t total = 0;
-        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
-        return total * n_q * sizeof(double);
-    }
+    size_t out_bytes(uint64_t n) const { return positions(n) * n_q * sizeof(double); }
     int check(atsc_ctx *ctx) const
     {
-        const int rc = across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, nullptr);
+        const int rc = check_ranges(ctx, CALL);
         return rc ? rc : quantile_check_levels(ctx, CALL, n_q, q, method);
     }
-    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
     int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
             void *stream) const
     {
         const int rc = check(ctx);
         if (rc) return rc;
-        const uint32_t ns = n_streams, nq = n_q;
-        const uint64_t st = stride;
-        const int m = method;
-        const AcrossKernel K{CALL, "no across quantile kernels", "launch k_across_quantile_positions", Q_ACROSS_QUANTILE,
-                             BY_ACROSS_QUANTILE, launch_across_quantile_positions != nullptr, q, n_q * sizeof(double),
-                             [ns, st, nq, m](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg,
-                                             uint64_t a0, const void *d_q, void *d_out, hipStream_t s) {
-                                 return launch_across_quantile_positions(tasks, n, scratch, reg, ns, a0, st, (const double *)d_q, nq,
-                                                                         m, (double *)d_out, s);
-                             }};
-        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
+        return run(ctx, in, n_windows, begin, cnt, d_res, stream,
+                   {CALL, "no across quantile kernels", "launch k_across_quantile_positions", Q_ACROSS_QUANTILE, BY_ACROSS_QUANTILE,
+                    launch_across_quantile_positions != nullptr, q, n_q * sizeof(double),
+                    [this](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
+                           const void *d_q, void *d_out, hipStream_t s) {
+                        return launch_across_quantile_positions(tasks, n, scratch, reg, n_streams, a0, stride, (const double *)d_q,
+                                                                n_q, method, (double *)d_out, s);
+                    }});
     }
 };
 
-// the across extremes' descriptor: the across' ranges, stride and record numbering, the windowed extremes' record (of k
-// entries per list) per position; k is checked as the windowed extremes check theirs and goes to the kernel by value.
-// The call keeps its tables and scratch in the across quantiles' place on in[0].dp (Q_ACROSS_QUANTILE): the two kinds of
-// call on one first plan wait for each other, and atsc_dplan stays as it is (DESIGN.md "Windowed across extremes")
-struct AcrossExtQuery {
-    static constexpr int INPUTS = 0;
+// the across extremes' descriptor: the windowed extremes' record (of k entries per list) per position; k is checked as
+// the windowed extremes check theirs and goes to the kernel by value
+struct AcrossExtQuery : AcrossBase {
     static constexpr const char *CALL = "across_extremes_windows";
-    uint32_t n_streams;
-    uint64_t stride;
-    const uint64_t *count;  // the call's ranges' lengths
-    uint64_t n_ranges;
     uint32_t k;
-    int inputs() const { return (int)n_streams; }
-    size_t out_bytes(uint64_t n) const
-    {
-        uint64_t total = 0;
-        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
-        return total * ATSC_EXTREMES_BYTES(std::min<uint32_t>(k, ATSC_EXTREMES_MAX_K));
-    }
+    size_t out_bytes(uint64_t n) const { return positions(n) * ATSC_EXTREMES_BYTES(std::min<uint32_t>(k, ATSC_EXTREMES_MAX_K)); }
     int check(atsc_ctx *ctx) const
     {
-        const int rc = across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, nullptr);
+        const int rc = check_ranges(ctx, CALL);
         if (rc) return rc;
         if (k == 0 || k > ATSC_EXTREMES_MAX_K) return fail_in(ctx, ATSC_E_INVALID, CALL, "k outside [1, 16]");
         return ATSC_OK;
     }
-    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
     int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
             void *stream) const
     {
         const int rc = check(ctx);
         if (rc) return rc;
-        const uint32_t ns = n_streams, kk = k;
-        const uint64_t st = stride;
-        const AcrossKernel K{CALL, "no across extremes kernels", "launch k_across_extremes_positions", Q_ACROSS_QUANTILE,
-                             BY_ACROSS_EXTREMES, launch_across_extremes_positions != nullptr, nullptr, 0,
-                             [ns, st, kk](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg,
-                                          uint64_t a0, const void *, void *d_out, hipStream_t s) {
-                                 return launch_across_extremes_positions(tasks, n, scratch, reg, ns, a0, st, kk, d_out, s);
-                             }};
-        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
+        return run(ctx, in, n_windows, begin, cnt, d_res, stream,
+                   {CALL, "no across extremes kernels", "launch k_across_extremes_positions", Q_ACROSS_QUANTILE, BY_ACROSS_EXTREMES,
+                    launch_across_extremes_positions != nullptr, nullptr, 0,
+                    [this](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
+                           const void *, void *d_out, hipStream_t s) {
+                        return launch_across_extremes_positions(tasks, n, scratch, reg, n_streams, a0, stride, k, d_out, s);
+                    }});
     }
 };
 
-// the across moments' descriptor: the across' ranges, stride and record numbering, an atsc_across_moments per position.
-// The call has no parameter of its own.  Like the across extremes it keeps its tables and scratch in the across
-// quantiles' place on in[0].dp (Q_ACROSS_QUANTILE): the three kinds of call on one first plan wait for each other, and
-// atsc_dplan stays as it is (DESIGN.md "Windowed across moments")
-struct AcrossMomQuery {
-    static constexpr int INPUTS = 0;
+// the across moments' descriptor: an atsc_across_moments per position; no parameter of its own, and no check in front of
+// across_dev's
+struct AcrossMomQuery : AcrossBase {
     static constexpr const char *CALL = "across_moments_windows";
-    uint32_t n_streams;
-    uint64_t stride;
-    const uint64_t *count;  // the call's ranges' lengths
-    uint64_t n_ranges;
-    int inputs() const { return (int)n_streams; }
-    size_t out_bytes(uint64_t n) const
-    {
-        uint64_t total = 0;
-        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
-        return total * sizeof(atsc_across_moments);
-    }
-    int check(atsc_ctx *ctx) const { return across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, nullptr); }
-    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
+    size_t out_bytes(uint64_t n) const { return positions(n) * sizeof(atsc_across_moments); }
+    int check(atsc_ctx *ctx) const { return check_ranges(ctx, CALL); }
     int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
             void *stream) const
     {
-        const uint32_t ns = n_streams;
-        const uint64_t st = stride;
-        const AcrossKernel K{CALL, "no across moments kernels", "launch k_across_moments_positions", Q_ACROSS_QUANTILE,
-                             BY_ACROSS_MOMENTS, launch_across_moments_positions != nullptr, nullptr, 0,
-                             [ns, st](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
-                                      const void *, void *d_out, hipStream_t s) {
-                                 return launch_across_moments_positions(tasks, n, scratch, reg, ns, a0, st, d_out, s);
-                             }};
-        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
+        return run(ctx, in, n_windows, begin, cnt, d_res, stream,
+                   {CALL, "no across moments kernels", "launch k_across_moments_positions", Q_ACROSS_QUANTILE, BY_ACROSS_MOMENTS,
+                    launch_across_moments_positions != nullptr, nullptr, 0,
+                    [this](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
+                           const void *, void *d_out, hipStream_t s) {
+                        return launch_across_moments_positions(tasks, n, scratch, reg, n_streams, a0, stride, d_out, s);
+                    }});
     }
 };
 
-// the across histograms' descriptor: the across' ranges, stride and record numbering, the histograms' row of n_edges + 2
-// counters per position; the edges and `closed` are checked as the windowed histograms check theirs
-// (histogram_check_edges), the edges go up with the call's tables, and the rolling histograms' limit keeps a counter's
-// index in 32 bits.  Like the across extremes and moments it keeps its tables and scratch in the across quantiles' place
-// on in[0].dp (Q_ACROSS_QUANTILE): the four kinds of call on one first plan wait for each other, and atsc_dplan stays
-// as it is (DESIGN.md "Windowed across histograms")
-struct AcrossHistQuery {
-    static constexpr int INPUTS = 0;
+// the across histograms' descriptor: the histograms' row of n_edges + 2 counters per position; the edges and `closed` are
+// checked as the windowed histograms check theirs (histogram_check_edges), the edges go up with the call's tables, and
+// the rolling histograms' limit keeps a counter's index in 32 bits
+struct AcrossHistQuery : AcrossBase {
     static constexpr const char *CALL = "across_histogram_windows";
-    uint32_t n_streams;
-    uint64_t stride;
-    const uint64_t *count;  // the call's ranges' lengths
-    uint64_t n_ranges;
     uint32_t n_edges;
     const double *edges;
     int closed;
-    int inputs() const { return (int)n_streams; }
-    size_t out_bytes(uint64_t n) const
-    {
-        uint64_t total = 0;
-        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
-        return total * ((size_t)n_edges + 2) * sizeof(uint64_t);
-    }
+    size_t out_bytes(uint64_t n) const { return positions(n) * ((size_t)n_edges + 2) * sizeof(uint64_t); }
     int check(atsc_ctx *ctx) const
     {
         uint64_t total = 0;
-        int rc = across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, &total);
+        int rc = check_ranges(ctx, CALL, &total);
         if (!rc) rc = histogram_check_edges(ctx, n_edges, edges, closed, CALL);
         if (rc) return rc;
         if (total * ((uint64_t)n_edges + 2) > 0xfffffffeull)  // (total < 2^32 and n_edges + 2 <= 1026: no overflow)
             return fail_in(ctx, ATSC_E_INVALID, CALL, "positions x (n_edges + 2) is not below 2^32 - 1 counters");
         return ATSC_OK;
     }
-    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no row
     int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
             void *stream) const
     {
         const int rc = check(ctx);
         if (rc) return rc;
-        const uint32_t ns = n_streams, ne = n_edges;
-        const uint64_t st = stride;
-        const int cl = closed;
-        const AcrossKernel K{CALL, "no across histogram kernels", "launch k_across_histogram_positions", Q_ACROSS_QUANTILE,
-                             BY_ACROSS_HISTOGRAM, launch_across_histogram_positions != nullptr, edges, n_edges * sizeof(double),
-                             [ns, st, ne, cl](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg,
-                                              uint64_t a0, const void *d_edges, void *d_out, hipStream_t s) {
-                                 return launch_across_histogram_positions(tasks, n, scratch, reg, ns, a0, st,
-                                                                          (const double *)d_edges, ne, cl, (uint64_t *)d_out, s);
-                             }};
-        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
+        return run(ctx, in, n_windows, begin, cnt, d_res, stream,
+                   {CALL, "no across histogram kernels", "launch k_across_histogram_positions", Q_ACROSS_QUANTILE,
+                    BY_ACROSS_HISTOGRAM, launch_across_histogram_positions != nullptr, edges, n_edges * sizeof(double),
+                    [this](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
+                           const void *d_edges, void *d_out, hipStream_t s) {
+                        return launch_across_histogram_positions(tasks, n, scratch, reg, n_streams, a0, stride,
+                                                                 (const double *)d_edges, n_edges, closed, (uint64_t *)d_out, s);
+                    }});
     }
 };
 
-// the across value counts' descriptor: the across' ranges, stride and record numbering, the windowed value counts' record
-// (of k entries) per position; k is checked as the windowed value counts check theirs, and k and `above` (as its key,
-// val_key) go to the kernel by value.  Like the across extremes, moments and histograms it keeps its tables and scratch in
-// the across quantiles' place on in[0].dp (Q_ACROSS_QUANTILE): the five kinds of call on one first plan wait for each
-// other, and atsc_dplan stays as it is (DESIGN.md "Windowed across value counts")
-struct AcrossValQuery {
-    static constexpr int INPUTS = 0;
+// the across value counts' descriptor: the windowed value counts' record (of k entries) per position; k is checked as the
+// windowed value counts check theirs, and k and `above` (as its key, val_key) go to the kernel by value
+struct AcrossValQuery : AcrossBase {
     static constexpr const char *CALL = "across_values_windows";
-    uint32_t n_streams;
-    uint64_t stride;
-    const uint64_t *count;  // the call's ranges' lengths
-    uint64_t n_ranges;
     uint32_t k;
     double above;
-    int inputs() const { return (int)n_streams; }
-    size_t out_bytes(uint64_t n) const
-    {
-        uint64_t total = 0;
-        for (uint64_t i = 0; count && i < n; ++i) total += atsc_across_outputs(count[i], stride);
-        return total * ATSC_VALUES_BYTES(std::min<uint32_t>(k, ATSC_VALUES_MAX_K));
-    }
+    size_t out_bytes(uint64_t n) const { return positions(n) * ATSC_VALUES_BYTES(std::min<uint32_t>(k, ATSC_VALUES_MAX_K)); }
     int check(atsc_ctx *ctx) const
     {
-        const int rc = across_check(ctx, CALL, n_streams, count ? n_ranges : 0, count, stride, nullptr);
+        const int rc = check_ranges(ctx, CALL);
         if (rc) return rc;
         if (k == 0 || k > ATSC_VALUES_MAX_K) return fail_in(ctx, ATSC_E_INVALID, CALL, "k outside [1, 32]");
         return ATSC_OK;
     }
-    static void fill_empty(void *, uint64_t) {}  // ranges without a sample have no record
     int dev(atsc_ctx *ctx, const QueryInput *in, uint64_t n_windows, const uint64_t *begin, const uint64_t *cnt, void *d_res,
             void *stream) const
     {
         const int rc = check(ctx);
         if (rc) return rc;
-        const uint32_t ns = n_streams, kk = k;
-        const uint64_t st = stride, ak = val_key(above);
-        const AcrossKernel K{CALL, "no across values kernels", "launch k_across_values_positions", Q_ACROSS_QUANTILE,
-                             BY_ACROSS_VALUES, launch_across_values_positions != nullptr, nullptr, 0,
-                             [ns, st, kk, ak](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg,
-                                              uint64_t a0, const void *, void *d_out, hipStream_t s) {
-                                 return launch_across_values_positions(tasks, n, scratch, reg, ns, a0, st, kk, ak, d_out, s);
-                             }};
-        return across_dev(ctx, in, (int)n_streams, n_windows, begin, cnt, stride, d_res, stream, K);
+        const uint64_t ak = val_key(above);
+        return run(ctx, in, n_windows, begin, cnt, d_res, stream,
+                   {CALL, "no across values kernels", "launch k_across_values_positions", Q_ACROSS_QUANTILE, BY_ACROSS_VALUES,
+                    launch_across_values_positions != nullptr, nullptr, 0,
+                    [this, ak](const DevRollTask *tasks, uint32_t n, const double *scratch, const uint64_t *reg, uint64_t a0,
+                               const void *, void *d_out, hipStream_t s) {
+                        return launch_across_values_positions(tasks, n, scratch, reg, n_streams, a0, stride, k, ak, d_out, s);
+                    }});
     }
 };
 
-// what every across call checks of its lists before it reads them
+// The entry points of a call over a list of streams (the six across calls and the pair matrix) are one statement each,
+// as the single-stream queries' are.  What every such call checks of its lists before it reads them:
 static bool across_lists(uint32_t n_streams, const void *const *a, const void *const *b)
 {
     if (n_streams == 0 || n_streams > ATSC_ACROSS_MAX_STREAMS || !a) return false;
@@ -3756,17 +3693,44 @@ static bool across_lists(uint32_t n_streams, const void *const *a, const void *c
         if (!a[k] || (b && !b[k])) return false;
     return true;
 }
+static constexpr const char *ACROSS_LISTS = "n_streams outside [1, 64], a null list or a null entry";
+// whether a host or stream call tests that `out` lies at a multiple of 8 bytes: every call but the across' own and the
+// pair matrix's host call
+enum OutAlign { OUT_ANY, OUT_ALIGN8 };
+
+// the device call: the lists, then the inputs, then the query's own dev
+template <class Q>
+static int across_call_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp, const uint8_t *const *d_body,
+                           uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *d_out, void *stream, const Q &q)
+{
+    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
+        return fail_in(ctx, ATSC_E_INVALID, Q::CALL, ACROSS_LISTS);
+    QueryInput in[MAX_INPUTS];
+    for (uint32_t k = 0; k < n_streams; ++k) in[k] = QueryInput{dp[k], d_body[k], 0};
+    return q.dev(ctx, in, n_windows, begin, count, d_out, stream);
+}
+
+// the host call: the lists, then out's alignment where the call tests it, then query_host
+template <class Q>
+static int across_call_host(atsc_ctx *ctx, uint32_t n_streams, const uint8_t *const *body, const uint64_t *body_len,
+                            const int *has_count, uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *out,
+                            OutAlign align, const Q &q)
+{
+    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
+        return fail_in(ctx, ATSC_E_INVALID, Q::CALL, ACROSS_LISTS);
+    if (align == OUT_ALIGN8 && ((uintptr_t)out & 7u)) return fail_in(ctx, ATSC_E_INVALID, Q::CALL, "out is not 8-byte aligned");
+    HostBody hb[MAX_INPUTS];
+    for (uint32_t k = 0; k < n_streams; ++k) hb[k] = HostBody{body[k], body_len[k], has_count[k]};
+    return query_host(ctx, hb, n_windows, begin, count, out, q);
+}
 
 extern "C" int atsc_across_windows_dev(atsc_ctx *ctx, uint32_t n_streams, const atsc_dplan *const *dp, const uint8_t *const *d_body,
                                        uint64_t n_windows, const uint64_t *begin, const uint64_t *count, uint64_t stride,
                                        atsc_across_record *d_out, void *stream)
 {
     ATSC_API_BEGIN
-    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
-        return fail(ctx, ATSC_E_INVALID, "across_windows: n_streams outside [1, 64], a null list or a null entry");
-    QueryInput in[MAX_INPUTS];
-    for (uint32_t k = 0; k < n_streams; ++k) in[k] = QueryInput{dp[k], d_body[k], 0};
-    return AcrossQuery{n_streams, stride, count, n_windows}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    return across_call_dev(ctx, n_streams, dp, d_body, n_windows, begin, count, d_out, stream,
+                           AcrossQuery{{n_streams, stride, count, n_windows}});
     ATSC_API_END
 }
 
@@ -3775,11 +3739,8 @@ extern "C" int atsc_across_windows(atsc_ctx *ctx, uint32_t n_streams, const uint
                                    uint64_t stride, atsc_across_record *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
-        return fail(ctx, ATSC_E_INVALID, "across_windows: n_streams outside [1, 64], a null list or a null entry");
-    HostBody hb[MAX_INPUTS];
-    for (uint32_t k = 0; k < n_streams; ++k) hb[k] = HostBody{body[k], body_len[k], has_count[k]};
-    return query_host(ctx, hb, n_windows, begin, count, out, AcrossQuery{n_streams, stride, count, n_windows});
+    return across_call_host(ctx, n_streams, body, body_len, has_count, n_windows, begin, count, out, OUT_ANY,
+                            AcrossQuery{{n_streams, stride, count, n_windows}});
     ATSC_API_END
 }
 
@@ -3789,11 +3750,8 @@ extern "C" int atsc_across_quantile_windows_dev(atsc_ctx *ctx, uint32_t n_stream
                                                 double *d_out, void *stream)
 {
     ATSC_API_BEGIN
-    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
-        return fail(ctx, ATSC_E_INVALID, "across_quantile_windows: n_streams outside [1, 64], a null list or a null entry");
-    QueryInput in[MAX_INPUTS];
-    for (uint32_t k = 0; k < n_streams; ++k) in[k] = QueryInput{dp[k], d_body[k], 0};
-    return AcrossQntQuery{n_streams, stride, count, n_windows, n_q, q, method}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    return across_call_dev(ctx, n_streams, dp, d_body, n_windows, begin, count, d_out, stream,
+                           AcrossQntQuery{{n_streams, stride, count, n_windows}, n_q, q, method});
     ATSC_API_END
 }
 
@@ -3802,12 +3760,8 @@ extern "C" int atsc_across_quantile_windows(atsc_ctx *ctx, uint32_t n_streams, c
                                             uint64_t stride, uint32_t n_q, const double *q, int method, double *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
-        return fail(ctx, ATSC_E_INVALID, "across_quantile_windows: n_streams outside [1, 64], a null list or a null entry");
-    if ((uintptr_t)out & 7u) return fail(ctx, ATSC_E_INVALID, "across_quantile_windows: out is not 8-byte aligned");
-    HostBody hb[MAX_INPUTS];
-    for (uint32_t k = 0; k < n_streams; ++k) hb[k] = HostBody{body[k], body_len[k], has_count[k]};
-    return query_host(ctx, hb, n_windows, begin, count, out, AcrossQntQuery{n_streams, stride, count, n_windows, n_q, q, method});
+    return across_call_host(ctx, n_streams, body, body_len, has_count, n_windows, begin, count, out, OUT_ALIGN8,
+                            AcrossQntQuery{{n_streams, stride, count, n_windows}, n_q, q, method});
     ATSC_API_END
 }
 
@@ -3816,11 +3770,8 @@ extern "C" int atsc_across_extremes_windows_dev(atsc_ctx *ctx, uint32_t n_stream
                                                 const uint64_t *count, uint64_t stride, uint32_t k, void *d_out, void *stream)
 {
     ATSC_API_BEGIN
-    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
-        return fail(ctx, ATSC_E_INVALID, "across_extremes_windows: n_streams outside [1, 64], a null list or a null entry");
-    QueryInput in[MAX_INPUTS];
-    for (uint32_t j = 0; j < n_streams; ++j) in[j] = QueryInput{dp[j], d_body[j], 0};
-    return AcrossExtQuery{n_streams, stride, count, n_windows, k}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    return across_call_dev(ctx, n_streams, dp, d_body, n_windows, begin, count, d_out, stream,
+                           AcrossExtQuery{{n_streams, stride, count, n_windows}, k});
     ATSC_API_END
 }
 
@@ -3829,12 +3780,8 @@ extern "C" int atsc_across_extremes_windows(atsc_ctx *ctx, uint32_t n_streams, c
                                             uint64_t stride, uint32_t k, void *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
-        return fail(ctx, ATSC_E_INVALID, "across_extremes_windows: n_streams outside [1, 64], a null list or a null entry");
-    if ((uintptr_t)out & 7u) return fail(ctx, ATSC_E_INVALID, "across_extremes_windows: out is not 8-byte aligned");
-    HostBody hb[MAX_INPUTS];
-    for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
-    return query_host(ctx, hb, n_windows, begin, count, out, AcrossExtQuery{n_streams, stride, count, n_windows, k});
+    return across_call_host(ctx, n_streams, body, body_len, has_count, n_windows, begin, count, out, OUT_ALIGN8,
+                            AcrossExtQuery{{n_streams, stride, count, n_windows}, k});
     ATSC_API_END
 }
 
@@ -3844,11 +3791,8 @@ extern "C" int atsc_across_values_windows_dev(atsc_ctx *ctx, uint32_t n_streams,
                                               void *stream)
 {
     ATSC_API_BEGIN
-    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
-        return fail(ctx, ATSC_E_INVALID, "across_values_windows: n_streams outside [1, 64], a null list or a null entry");
-    QueryInput in[MAX_INPUTS];
-    for (uint32_t j = 0; j < n_streams; ++j) in[j] = QueryInput{dp[j], d_body[j], 0};
-    return AcrossValQuery{n_streams, stride, count, n_windows, k, above}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    return across_call_dev(ctx, n_streams, dp, d_body, n_windows, begin, count, d_out, stream,
+                           AcrossValQuery{{n_streams, stride, count, n_windows}, k, above});
     ATSC_API_END
 }
 
@@ -3857,12 +3801,8 @@ extern "C" int atsc_across_values_windows(atsc_ctx *ctx, uint32_t n_streams, con
                                           uint64_t stride, uint32_t k, double above, void *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
-        return fail(ctx, ATSC_E_INVALID, "across_values_windows: n_streams outside [1, 64], a null list or a null entry");
-    if ((uintptr_t)out & 7u) return fail(ctx, ATSC_E_INVALID, "across_values_windows: out is not 8-byte aligned");
-    HostBody hb[MAX_INPUTS];
-    for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
-    return query_host(ctx, hb, n_windows, begin, count, out, AcrossValQuery{n_streams, stride, count, n_windows, k, above});
+    return across_call_host(ctx, n_streams, body, body_len, has_count, n_windows, begin, count, out, OUT_ALIGN8,
+                            AcrossValQuery{{n_streams, stride, count, n_windows}, k, above});
     ATSC_API_END
 }
 
@@ -3871,11 +3811,8 @@ extern "C" int atsc_across_moments_windows_dev(atsc_ctx *ctx, uint32_t n_streams
                                                const uint64_t *count, uint64_t stride, atsc_across_moments *d_out, void *stream)
 {
     ATSC_API_BEGIN
-    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
-        return fail(ctx, ATSC_E_INVALID, "across_moments_windows: n_streams outside [1, 64], a null list or a null entry");
-    QueryInput in[MAX_INPUTS];
-    for (uint32_t j = 0; j < n_streams; ++j) in[j] = QueryInput{dp[j], d_body[j], 0};
-    return AcrossMomQuery{n_streams, stride, count, n_windows}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    return across_call_dev(ctx, n_streams, dp, d_body, n_windows, begin, count, d_out, stream,
+                           AcrossMomQuery{{n_streams, stride, count, n_windows}});
     ATSC_API_END
 }
 
@@ -3884,12 +3821,8 @@ extern "C" int atsc_across_moments_windows(atsc_ctx *ctx, uint32_t n_streams, co
                                            uint64_t stride, atsc_across_moments *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
-        return fail(ctx, ATSC_E_INVALID, "across_moments_windows: n_streams outside [1, 64], a null list or a null entry");
-    if ((uintptr_t)out & 7u) return fail(ctx, ATSC_E_INVALID, "across_moments_windows: out is not 8-byte aligned");
-    HostBody hb[MAX_INPUTS];
-    for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
-    return query_host(ctx, hb, n_windows, begin, count, out, AcrossMomQuery{n_streams, stride, count, n_windows});
+    return across_call_host(ctx, n_streams, body, body_len, has_count, n_windows, begin, count, out, OUT_ALIGN8,
+                            AcrossMomQuery{{n_streams, stride, count, n_windows}});
     ATSC_API_END
 }
 
@@ -3899,12 +3832,8 @@ extern "C" int atsc_across_histogram_windows_dev(atsc_ctx *ctx, uint32_t n_strea
                                                  int closed, uint64_t *d_out, void *stream)
 {
     ATSC_API_BEGIN
-    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
-        return fail(ctx, ATSC_E_INVALID, "across_histogram_windows: n_streams outside [1, 64], a null list or a null entry");
-    QueryInput in[MAX_INPUTS];
-    for (uint32_t j = 0; j < n_streams; ++j) in[j] = QueryInput{dp[j], d_body[j], 0};
-    return AcrossHistQuery{n_streams, stride, count, n_windows, n_edges, edges, closed}.dev(ctx, in, n_windows, begin, count, d_out,
-                                                                                            stream);
+    return across_call_dev(ctx, n_streams, dp, d_body, n_windows, begin, count, d_out, stream,
+                           AcrossHistQuery{{n_streams, stride, count, n_windows}, n_edges, edges, closed});
     ATSC_API_END
 }
 
@@ -3914,13 +3843,8 @@ extern "C" int atsc_across_histogram_windows(atsc_ctx *ctx, uint32_t n_streams, 
                                              const double *edges, int closed, uint64_t *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
-        return fail(ctx, ATSC_E_INVALID, "across_histogram_windows: n_streams outside [1, 64], a null list or a null entry");
-    if ((uintptr_t)out & 7u) return fail(ctx, ATSC_E_INVALID, "across_histogram_windows: out is not 8-byte aligned");
-    HostBody hb[MAX_INPUTS];
-    for (uint32_t j = 0; j < n_streams; ++j) hb[j] = HostBody{body[j], body_len[j], has_count[j]};
-    return query_host(ctx, hb, n_windows, begin, count, out,
-                      AcrossHistQuery{n_streams, stride, count, n_windows, n_edges, edges, closed});
+    return across_call_host(ctx, n_streams, body, body_len, has_count, n_windows, begin, count, out, OUT_ALIGN8,
+                            AcrossHistQuery{{n_streams, stride, count, n_windows}, n_edges, edges, closed});
     ATSC_API_END
 }
 
@@ -3976,11 +3900,8 @@ extern "C" int atsc_pair_matrix_windows_dev(atsc_ctx *ctx, uint32_t n_streams, c
                                             const uint64_t *count, atsc_window_pair *d_out, void *stream)
 {
     ATSC_API_BEGIN
-    if (!ctx || !d_body || !across_lists(n_streams, (const void *const *)dp, (const void *const *)d_body))
-        return fail(ctx, ATSC_E_INVALID, "pair_matrix_windows: n_streams outside [1, 64], a null list or a null entry");
-    QueryInput in[MAX_INPUTS];
-    for (uint32_t k = 0; k < n_streams; ++k) in[k] = QueryInput{dp[k], d_body[k], 0};
-    return PairMatrixQuery{n_streams, n_windows}.dev(ctx, in, n_windows, begin, count, d_out, stream);
+    return across_call_dev(ctx, n_streams, dp, d_body, n_windows, begin, count, d_out, stream,
+                           PairMatrixQuery{n_streams, n_windows});
     ATSC_API_END
 }
 
@@ -3989,11 +3910,8 @@ extern "C" int atsc_pair_matrix_windows(atsc_ctx *ctx, uint32_t n_streams, const
                                         atsc_window_pair *out)
 {
     ATSC_API_BEGIN
-    if (!ctx || !body_len || !has_count || !across_lists(n_streams, (const void *const *)body, nullptr))
-        return fail(ctx, ATSC_E_INVALID, "pair_matrix_windows: n_streams outside [1, 64], a null list or a null entry");
-    HostBody hb[MAX_INPUTS];
-    for (uint32_t k = 0; k < n_streams; ++k) hb[k] = HostBody{body[k], body_len[k], has_count[k]};
-    return query_host(ctx, hb, n_windows, begin, count, out, PairMatrixQuery{n_streams, n_windows});
+    return across_call_host(ctx, n_streams, body, body_len, has_count, n_windows, begin, count, out, OUT_ANY,
+                            PairMatrixQuery{n_streams, n_windows});
     ATSC_API_END
 }
 
@@ -4073,6 +3991,15 @@ template <class Q>
 static int query_stream(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count, void *out, const Q &q)
 {
     return query_stream(&s, n_windows, begin, count, out, q);
+}
+// (a list of streams: the across calls and the pair matrix; a bare code, as above, where the list or out's alignment fails)
+template <class Q>
+static int across_call_stream(atsc_stream *const *streams, uint32_t n_streams, uint64_t n_windows, const uint64_t *begin,
+                              const uint64_t *count, void *out, OutAlign align, const Q &q)
+{
+    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || (align == OUT_ALIGN8 && ((uintptr_t)out & 7u)))
+        return ATSC_E_INVALID;
+    return query_stream(streams, n_windows, begin, count, out, q);
 }
 
 extern "C" int atsc_stream_aggregate_windows(atsc_stream *s, uint64_t n_windows, const uint64_t *begin, const uint64_t *count,
@@ -4220,8 +4147,8 @@ extern "C" int atsc_stream_across_windows(atsc_stream *const *streams, uint32_t 
                                           const uint64_t *begin, const uint64_t *count, uint64_t stride, atsc_across_record *out)
 {
     ATSC_API_BEGIN
-    if (!across_lists(n_streams, (const void *const *)streams, nullptr)) return ATSC_E_INVALID;
-    return query_stream(streams, n_windows, begin, count, out, AcrossQuery{n_streams, stride, count, n_windows});
+    return across_call_stream(streams, n_streams, n_windows, begin, count, out, OUT_ANY,
+                              AcrossQuery{{n_streams, stride, count, n_windows}});
     ATSC_API_END
 }
 
@@ -4230,9 +4157,8 @@ extern "C" int atsc_stream_across_quantile_windows(atsc_stream *const *streams, 
                                                    const double *q, int method, double *out)
 {
     ATSC_API_BEGIN
-    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
-    return query_stream(streams, n_windows, begin, count, out,
-                        AcrossQntQuery{n_streams, stride, count, n_windows, n_q, q, method});
+    return across_call_stream(streams, n_streams, n_windows, begin, count, out, OUT_ALIGN8,
+                              AcrossQntQuery{{n_streams, stride, count, n_windows}, n_q, q, method});
     ATSC_API_END
 }
 
@@ -4241,8 +4167,8 @@ extern "C" int atsc_stream_across_extremes_windows(atsc_stream *const *streams, 
                                                    void *out)
 {
     ATSC_API_BEGIN
-    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
-    return query_stream(streams, n_windows, begin, count, out, AcrossExtQuery{n_streams, stride, count, n_windows, k});
+    return across_call_stream(streams, n_streams, n_windows, begin, count, out, OUT_ALIGN8,
+                              AcrossExtQuery{{n_streams, stride, count, n_windows}, k});
     ATSC_API_END
 }
 
@@ -4251,8 +4177,8 @@ extern "C" int atsc_stream_across_values_windows(atsc_stream *const *streams, ui
                                                  double above, void *out)
 {
     ATSC_API_BEGIN
-    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
-    return query_stream(streams, n_windows, begin, count, out, AcrossValQuery{n_streams, stride, count, n_windows, k, above});
+    return across_call_stream(streams, n_streams, n_windows, begin, count, out, OUT_ALIGN8,
+                              AcrossValQuery{{n_streams, stride, count, n_windows}, k, above});
     ATSC_API_END
 }
 
@@ -4261,8 +4187,8 @@ extern "C" int atsc_stream_across_moments_windows(atsc_stream *const *streams, u
                                                   atsc_across_moments *out)
 {
     ATSC_API_BEGIN
-    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
-    return query_stream(streams, n_windows, begin, count, out, AcrossMomQuery{n_streams, stride, count, n_windows});
+    return across_call_stream(streams, n_streams, n_windows, begin, count, out, OUT_ALIGN8,
+                              AcrossMomQuery{{n_streams, stride, count, n_windows}});
     ATSC_API_END
 }
 
@@ -4271,9 +4197,8 @@ extern "C" int atsc_stream_across_histogram_windows(atsc_stream *const *streams,
                                                     uint32_t n_edges, const double *edges, int closed, uint64_t *out)
 {
     ATSC_API_BEGIN
-    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
-    return query_stream(streams, n_windows, begin, count, out,
-                        AcrossHistQuery{n_streams, stride, count, n_windows, n_edges, edges, closed});
+    return across_call_stream(streams, n_streams, n_windows, begin, count, out, OUT_ALIGN8,
+                              AcrossHistQuery{{n_streams, stride, count, n_windows}, n_edges, edges, closed});
     ATSC_API_END
 }
 
@@ -4281,7 +4206,7 @@ extern "C" int atsc_stream_pair_matrix_windows(atsc_stream *const *streams, uint
                                                const uint64_t *begin, const uint64_t *count, atsc_window_pair *out)
 {
     ATSC_API_BEGIN
-    if (!across_lists(n_streams, (const void *const *)streams, nullptr) || ((uintptr_t)out & 7u)) return ATSC_E_INVALID;
-    return query_stream(streams, n_windows, begin, count, out, PairMatrixQuery{n_streams, n_windows});
+    return across_call_stream(streams, n_streams, n_windows, begin, count, out, OUT_ALIGN8,
+                              PairMatrixQuery{n_streams, n_windows});
     ATSC_API_END
 }

@@ -3,7 +3,9 @@
 NaN equal to any NaN, no tolerance.  Five streams of different framings (256-sample frames, 4096-sample frames, the
 mixed-length ladder under several codecs, one with a large frame, one of hand-built Constant records), every one with a
 zone of Constant records in front where all of them are NaN and where zeros of both signs meet in both orders; 64 Noop
-streams; N = 1 against the window decode; one position through different ranges and strides; budgets that cut a range
+streams; N = 1 against the window decode; one position through different ranges and strides; the shapes at which the
+kernel takes another path (pairs, single positions, a full task from an odd sample, a result 8 bytes off a multiple of
+16); budgets that cut a range
 into pieces with a large frame across a piece's end; the host, device, stream and image calls; every error of the
 contract with the result untouched; a malformed payload in one stream of three; the atsc command line."""
 import ctypes as C
@@ -237,6 +239,33 @@ def test_one_position_through_different_ranges_and_strides(A, ctx, five):
             got, off = ctx.across_windows_host(recs, [0, b, 2048], [3, c, 30], s)
             j = int(off[1]) + (q - b) // s
             assert (q - b) % s == 0 and j < int(off[2]) and got[j: j + 1].tobytes() == ref.tobytes(), (q, b, c, s)
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+def test_shapes_where_the_kernel_takes_another_path(A, ctx, torch, five, shift):
+    """ranges with an odd and an even first sample of every length around a pair, a wavefront and a task -- one position
+    and two positions from an odd sample (a head alone; a head and a tail, no pair), a full task from an odd sample --
+    at stride 1 (pairs) and at another; the result at a multiple of 16 bytes and 8 bytes off one"""
+    recs, fulls, total = five
+    task = 512  # ACR_TASK
+    rg = [(b0, n) for b0 in (1001, 1000) for n in (0, 1, 2, 3, 63, 64, 65, task - 1, task, task + 1)] + [(2047, 2), (total, 0)]
+    b, c = [x[0] for x in rg], [x[1] for x in rg]
+    bodies = [torch.from_numpy(np.frombuffer(r, dtype=np.uint8).copy()).to("cuda") for r in recs]
+    dps = [A.DPlan(ctx, r) for r in recs]
+    try:
+        for s in (1, 3):
+            want, woff = M.across(fulls, b, c, s)
+            d = torch.full((shift + 4 * len(want) + 8,), SENT, dtype=torch.int64, device="cuda")
+            doff = dps[0].across_windows(bodies[0], dps[1:], bodies[1:], b, c, d[shift:], s,
+                                         torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            assert (d.data_ptr() + 8 * shift) % 16 == 8 * shift
+            h = d.cpu().numpy().view(np.uint64)
+            assert doff.tolist() == woff.tolist() and np.all(h[:shift] == SENT) and np.all(h[shift + 4 * len(want):] == SENT)
+            _assert_same(h[shift: shift + 4 * len(want)].view(A.ACROSS_RECORD), want, (s, shift))
+    finally:
+        for dp in dps:
+            dp.close()
 
 
 def _pieces(n, budget, n_in, n_large):
